@@ -181,7 +181,8 @@ class ViewPipeline:
         if _lib.hw_queues_late():
             # the schedule below is built on streams that run CONCURRENTLY; with the HIP runtime's default of 4 hardware queues
             # (fewer once RCCL has taken its own) the side streams share a queue with the caller's and the step becomes front +
-            # scatter.  The package asks for 8 when it is imported (_lib.py), which only works before the first HIP call.
+            # scatter.  The package asks for _lib.HW_QUEUES_WANTED when it is imported, which only works before the first HIP
+            # call.
             raise _lib.GwbpError(
                 "ViewPipeline needs GPU_MAX_HW_QUEUES >= %d, read by the HIP runtime when it starts: import gsbp_amd (or set "
                 "the variable) before the first CUDA/HIP call of the process, or run the views with pipeline=False"
@@ -199,8 +200,8 @@ class ViewPipeline:
                 e.scatter_workgroups = int(scatter_workgroups)
                 e.caps.scatter_workgroups = e.scatter_workgroups
         # High priority = a hardware queue of its own.  With default priority the side stream can land on the main
-        # stream's hardware queue (it does once RCCL has created its streams: GPU_MAX_HW_QUEUES is 4), the two streams
-        # then run strictly one after the other and the step is front + scatter (5.06 instead of 4.27 ms/view at C2).
+        # stream's hardware queue (it does once RCCL has created its streams), the two streams then run strictly one after
+        # the other and the step is front + scatter (5.06 instead of 4.27 ms/view at C2).
         self.scatter_dim = scatter_dim
         self.allow_wide = bool(allow_wide)
         # Narrow maps (D <= 16): the front stage stops after the sort, and blend + scatter run as ONE kernel on the caller's

@@ -163,6 +163,34 @@ def test_bench_starts_its_own_ranks_for_gpus_n(monkeypatch):
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_bench_dump_outputs_writes_a_fixed_bounded_sample(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: F and d as float32 .npy files, all rows when they fit the byte budget, else the same seeded
+    rows on every call (two builds are compared row for row), with the rows' global indices beside them."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n, D, row0 = 1000, 8, 5000
+    F = torch.arange(n * D, dtype=torch.float32).reshape(n, D)
+    d = torch.arange(n, dtype=torch.float32) * 0.5
+    bench.dump_outputs(str(tmp_path / "all"), F, d, row0)
+    rows = np.load(tmp_path / "all" / "rows.npy")
+    assert rows.dtype == np.float64 and np.array_equal(rows, np.arange(n) + row0)
+    Fa, da = np.load(tmp_path / "all" / "F.npy"), np.load(tmp_path / "all" / "d.npy")
+    assert Fa.dtype == da.dtype == np.float32 and np.array_equal(Fa, F.numpy()) and np.array_equal(da, d.numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 100 * (4 * D + 12))
+    for sub in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / sub), F, d, row0)
+    files = [tmp_path / "s1" / f for f in ("F.npy", "d.npy", "rows.npy")]
+    assert sum(os.path.getsize(f) for f in files) <= bench.DUMP_BYTES + 3 * 128  # (npy headers)
+    r = np.load(tmp_path / "s1" / "rows.npy")
+    assert len(r) == 100 and len(np.unique(r)) == 100 and np.array_equal(r, np.load(tmp_path / "s2" / "rows.npy"))
+    local = (r - row0).astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "s1" / "F.npy"), F.numpy()[local])
+    assert np.array_equal(np.load(tmp_path / "s1" / "d.npy"), d.numpy()[local])
+
+
 def test_bench_finds_the_committed_counters_of_the_kernel_it_timed(tmp_path):
     """bench.py's `roofline.traffic` comes from profiles/traffic.json and only when that file's passes profiled the kernel
     the run timed: the file holds rocprof's names (namespace, template arguments), the bench its own short ones."""
@@ -306,17 +334,17 @@ def test_zero_table_verdict_is_rechecked_on_a_sample_and_can_be_invalidated():
 
 def test_view_pipeline_refuses_to_run_on_shared_hardware_queues(monkeypatch):
     """GPU_MAX_HW_QUEUES was set by bench.py only, so the product CLI and library callers ran the pipeline on the
-    runtime's default 4 queues.  The package now asks for 8 when it is imported; if that came too late (runtime already up) or
-    the caller asked for fewer, ViewPipeline says so instead of silently running front + scatter back to back."""
+    runtime's default queues.  The package now asks for its queues when it is imported; if that came too late (runtime already
+    up) or the caller asked for fewer, ViewPipeline says so instead of silently running front + scatter back to back."""
     from gsbp_amd import _lib
     assert os.environ.get("GPU_MAX_HW_QUEUES") is not None and _lib.hw_queues_ok()
-    monkeypatch.setenv("GPU_MAX_HW_QUEUES", "8")
+    monkeypatch.setenv("GPU_MAX_HW_QUEUES", str(_lib.HW_QUEUES_WANTED))
     monkeypatch.setattr(_lib, "_QUEUES_LATE", True)  # the runtime was up before the package could ask: refuse
     assert not _lib.hw_queues_ok() and _lib.hw_queues_late()
     with pytest.raises(gsbp_amd.GwbpError, match="GPU_MAX_HW_QUEUES"):
         gsbp_amd.ViewPipeline(100, 64, 48, "cpu")
     monkeypatch.setattr(_lib, "_QUEUES_LATE", False)
-    monkeypatch.setenv("GPU_MAX_HW_QUEUES", "4")     # somebody chose fewer: say so, do not refuse
+    monkeypatch.setenv("GPU_MAX_HW_QUEUES", str(_lib.HW_QUEUES_WANTED - 1))  # somebody chose fewer: say so, do not refuse
     assert not _lib.hw_queues_ok() and not _lib.hw_queues_late()
     with pytest.warns(RuntimeWarning, match="GPU_MAX_HW_QUEUES"):
         try:

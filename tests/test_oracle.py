@@ -106,7 +106,12 @@ def test_autograd_formulation_equals_direct_accumulation(orc, gold):
     (out * feats).sum().backward()
     (Wt @ colors_feats_0).sum().backward()
     F_auto, d_auto = colors_feats.grad.numpy(), colors_feats_0.grad[:, 0].numpy()
-    assert torch.equal(colors_feats_0.grad[:, 0], colors_feats_0.grad[:, 2])  # channel-equal gradients
+    # channel-equal gradients: every channel is the same sum of a column of W >= 0, but the BLAS behind the backward may order
+    # it differently per channel (MKL's AVX2 kernels do), so the channels agree to within the rounding bound of two summation
+    # orders of n nonnegative terms, 2 (n - 1) u * sum
+    g0 = colors_feats_0.grad
+    bound = 2 * (Wt.shape[0] - 1) * (torch.finfo(torch.float64).eps / 2) * g0[:, :1]
+    assert bool(Wt.min() >= 0) and bool(((g0 - g0[:, :1]).abs() <= bound).all())
     proj = orc.project(g["means"], g["quats"], g["scales"], g["vms"][1], g["K"], W0, H0)
     bins = orc.bin_sort(proj, W0, H0)
     F = np.zeros((256, 8), np.float64)
