@@ -50,7 +50,7 @@ LIB_PATH = os.path.join(_HERE, "libgwbp.so")
 CSRC = os.path.join(_HERE, "csrc")
 
 EXPORTS = [
-    "gwbp_version", "gwbp_last_error_string", "gwbp_workspace_size", "gwbp_project", "gwbp_bin_sort",
+    "gwbp_version", "gwbp_last_error_string", "gwbp_workspace_size", "gwbp_project", "gwbp_project_camera", "gwbp_bin_sort",
     "gwbp_blend_weights", "gwbp_blend_weights_d", "gwbp_blend_scatter", "gwbp_blend_scatter_encoded", "gwbp_blend_tokens", "gwbp_scatter_tokens", "gwbp_accumulate_d", "gwbp_scatter", "gwbp_scatter_encoded", "gwbp_scatter_upsampled", "gwbp_scatter_bilinear", "gwbp_render", "gwbp_render_pixels", "gwbp_sh_colors",
     "gwbp_backproject_view", "gwbp_encode_map", "gwbp_finalize",
     "gwbp_accumulate_stats", "gwbp_read_stats", "gwbp_dump_pairs",
@@ -83,6 +83,10 @@ FLAG_TIGHT_BINNING = 1  # GWBP_FLAG_TIGHT_BINNING (include/gwbp.h)
 FLAG_FRONT_PRIORITY = 2  # GWBP_FLAG_FRONT_PRIORITY
 FLAG_NARROW_SCATTER = 4  # GWBP_FLAG_NARROW_SCATTER
 FLAG_SPLIT_ENCODER = 16  # GWBP_FLAG_SPLIT_ENCODER
+
+# gwbp_project_camera: gsplat.rasterization's camera_model / rasterize_mode names -> GWBP_CAMERA_* / GWBP_RASTERIZE_*
+CAMERA_MODELS = {"pinhole": 0, "ortho": 1, "fisheye": 2}
+RASTERIZE_MODES = {"classic": 0, "antialiased": 1}
 
 
 class GwbpError(RuntimeError):
@@ -133,6 +137,7 @@ _MAP = [_P, _I64, _I64, _I64, _I32]         # feats, fs_y, fs_x, fs_c, D
 ARGTYPES = {
     "gwbp_workspace_size": [C.POINTER(Caps), C.POINTER(C.c_size_t)],
     "gwbp_project": _WSV + [_P] * 8 + [_P],
+    "gwbp_project_camera": _WSV + [_I32, _I32] + [_P] * 9 + [_P],
     "gwbp_bin_sort": _WSV + [_P] * 3 + [_P],
     "gwbp_blend_weights": _WSV + [_P, _P],
     "gwbp_blend_weights_d": _WSV + [_P, _F, _P, _P],
@@ -205,7 +210,13 @@ def check(rc: int, what: str):
 
 
 def make_view(viewmat, K, width: int, height: int, near_plane=0.01, far_plane=1e10, eps2d=0.3,
-              radius_clip=0.0) -> View:
+              radius_clip=0.0, camera_model: str = "pinhole", rasterize_mode: str = "classic") -> View:
+    """The gwbp_view struct of one camera.  camera_model / rasterize_mode (gsplat's names) do not fit the struct, whose size
+    is part of the ABI: they ride along as Python attributes of the returned View, and Engine.project picks them up."""
+    if camera_model not in CAMERA_MODELS:
+        raise ValueError(f"camera_model must be one of {sorted(CAMERA_MODELS)}, got {camera_model!r}")
+    if rasterize_mode not in RASTERIZE_MODES:
+        raise ValueError(f"rasterize_mode must be one of {sorted(RASTERIZE_MODES)}, got {rasterize_mode!r}")
     v = View()
     vm = [float(x) for x in viewmat.detach().reshape(-1).cpu().tolist()]
     kk = [float(x) for x in K.detach().reshape(-1).cpu().tolist()]
@@ -215,7 +226,17 @@ def make_view(viewmat, K, width: int, height: int, near_plane=0.01, far_plane=1e
     v.K[:] = kk
     v.width, v.height = int(width), int(height)
     v.near_plane, v.far_plane, v.eps2d, v.radius_clip = near_plane, far_plane, eps2d, radius_clip
+    v.camera_model, v.rasterize_mode = camera_model, rasterize_mode
     return v
+
+
+def camera_of(view):
+    """(camera_model, rasterize_mode) of a View; a View built without make_view is pinhole / classic."""
+    return getattr(view, "camera_model", "pinhole"), getattr(view, "rasterize_mode", "classic")
+
+
+def is_default_camera(view) -> bool:
+    return camera_of(view) == ("pinhole", "classic")
 
 
 def ptr(t: Optional[torch.Tensor]):

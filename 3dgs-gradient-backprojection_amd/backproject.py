@@ -517,7 +517,8 @@ def create_feature_field(means, quats, scales, opacities, viewmats, K, width: in
                          gather: bool = True, allow_wide: bool = True, fuse_encoder: bool = False,
                          fuse_small: bool = True, feature_fn_stream_safe: bool = False,
                          encoder_in_blend: Optional[bool] = None, token_space: bool = True,
-                         encoder_split: Optional[bool] = None):
+                         encoder_split: Optional[bool] = None, camera_model: str = "pinhole",
+                         rasterize_mode: str = "classic"):
     """Build the [N, dim_out] per-Gaussian feature field.
 
     means/quats/scales/opacities: post-activation Gaussians (backproject.py:55-57), device tensors.
@@ -563,6 +564,9 @@ def create_feature_field(means, quats, scales, opacities, viewmats, K, width: in
     field; False returns this rank's block only (rows row0 .. of `return_partials`' stats["row0"]).
     return_partials: also return (F_rows, d, stats): the summed, un-normalised accumulators (this rank's row block of F,
     all of d) and the counters.
+    camera_model ("pinhole" | "ortho" | "fisheye") / rasterize_mode ("classic" | "antialiased"): gsplat's projection options of
+    the scene (a scene trained antialiased is back-projected with w = (o x compensation) T); every path above reads them from
+    the projection (gwbp_project_camera), the one-call gwbp_backproject_view is used for pinhole / classic only.
     """
     dist, rank, world = _dist()
     n = means.shape[0]
@@ -615,7 +619,8 @@ def create_feature_field(means, quats, scales, opacities, viewmats, K, width: in
                                     engines=[eng] + [Engine(n, width, height, device=dev, tight_binning=eng.tight_binning,
                                                             isect_cap=eng.isect_cap, pair_cap=eng.pair_cap)
                                                      for _ in range(depth - 1)])
-                views = [eng.view(vm_host[v], K_host, width, height) for v in my_views]
+                views = [eng.view(vm_host[v], K_host, width, height, camera_model=camera_model,
+                                  rasterize_mode=rasterize_mode) for v in my_views]
                 for j in range(min(pipe.lookahead, len(my_views))):
                     pipe.front(views[j], means, quats, scales, opacities, d, sd)
                 # with an encoder the feature function runs one view ahead, so that view v+1's map is encoded on a third
@@ -681,12 +686,13 @@ def create_feature_field(means, quats, scales, opacities, viewmats, K, width: in
                     feats = feature_fn(v)
                     if encoder is not None:
                         feats = encode_features(eng, feats, encoder)
-                    view = eng.view(vm_host[v], K_host, width, height)
+                    view = eng.view(vm_host[v], K_host, width, height, camera_model=camera_model,
+                                    rasterize_mode=rasterize_mode)
                     if upsample is None and fuse_small and Engine.can_blend_scatter(feats):
                         eng.project(view, means, quats, scales, opacities)
                         eng.bin_sort(view)
                         eng.blend_scatter(view, feats, F, d, sf, sd)
-                    elif upsample is None:
+                    elif upsample is None and camera_model == "pinhole" and rasterize_mode == "classic":
                         eng.backproject_view(view, means, quats, scales, opacities, feats, F, d, sf, sd)
                     elif token_space and upsample == "nearest" and Engine.can_scatter_tokens(feats, height, width):
                         eng.project(view, means, quats, scales, opacities)

@@ -250,6 +250,20 @@ int gwbp_project(const gwbp_caps *caps, void *workspace, size_t workspace_bytes,
                  const float *means, const float *quats, const float *scales, const float *opacities,
                  int32_t *radii, float *means2d, float *depths, float *conics, void *stream)
 {
+    return gwbp_project_camera(caps, workspace, workspace_bytes, view_host, GWBP_CAMERA_PINHOLE, GWBP_RASTERIZE_CLASSIC,
+                               means, quats, scales, opacities, radii, means2d, depths, conics, nullptr, stream);
+}
+
+int gwbp_project_camera(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                        int32_t camera_model, int32_t rasterize_mode, const float *means, const float *quats,
+                        const float *scales, const float *opacities, int32_t *radii, float *means2d, float *depths,
+                        float *conics, float *compensations, void *stream)
+{
+    // validated before anything touches the device
+    if (camera_model != GWBP_CAMERA_PINHOLE && camera_model != GWBP_CAMERA_ORTHO && camera_model != GWBP_CAMERA_FISHEYE)
+        return set_error(GWBP_EINVAL, "unknown camera model %d", (int)camera_model);
+    if (rasterize_mode != GWBP_RASTERIZE_CLASSIC && rasterize_mode != GWBP_RASTERIZE_ANTIALIASED)
+        return set_error(GWBP_EINVAL, "unknown rasterize mode %d", (int)rasterize_mode);
     Layout L;
     Ws W;
     ViewDev V;
@@ -263,7 +277,7 @@ int gwbp_project(const gwbp_caps *caps, void *workspace, size_t workspace_bytes,
     if (reinterpret_cast<uintptr_t>(quats) & 15)
         return set_error(GWBP_EINVAL, "quats must be 16-B aligned");
     return launch_project(L, W, V, means, quats, scales, opacities, radii, means2d, depths, conics,
-                          static_cast<hipStream_t>(stream));
+                          static_cast<hipStream_t>(stream), camera_model, rasterize_mode, compensations);
 }
 
 int gwbp_bin_sort(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,

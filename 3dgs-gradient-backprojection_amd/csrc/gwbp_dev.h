@@ -152,7 +152,8 @@ inline int sort_passes(int n_tiles)
 // stage launchers (one per .hip file)
 int launch_project(const Layout &L, const Ws &W, const ViewDev &V, const float *means, const float *quats,
                    const float *scales, const float *opac, int32_t *radii, float *means2d, float *depths,
-                   float *conics, hipStream_t s);
+                   float *conics, hipStream_t s, int camera_model = GWBP_CAMERA_PINHOLE,
+                   int rasterize_mode = GWBP_RASTERIZE_CLASSIC, float *compensations = nullptr);
 int launch_emit(const Layout &L, const Ws &W, const ViewDev &V, const u32 *order, hipStream_t s);
 int launch_emit_scanned(const Layout &L, const Ws &W, const ViewDev &V, const u32 *order, hipStream_t s);
 int launch_bin_sort(const Layout &L, const Ws &W, const ViewDev &V, int64_t *isect_ids, int32_t *flatten_ids,

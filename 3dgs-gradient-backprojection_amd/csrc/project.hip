@@ -1,4 +1,5 @@
-// project.hip -- EWA projection of every Gaussian for one pinhole view + tiles-per-Gaussian count.
+// project.hip -- EWA projection of every Gaussian for one view (pinhole, ortho or fisheye camera; classic or antialiased
+// opacities) + tiles-per-Gaussian count.
 //
 // Replaces gsplat 1.4.0's fully_fused_projection (first stage of rasterization(), reference call sites
 // backproject.py:115,133).  One lane per Gaussian, coalesced AoS loads (12/16/12/4 B per lane, contiguous across the
@@ -11,12 +12,18 @@
 
 namespace gwbp {
 
+// Camera model and rasterize mode are uniform per launch: template parameters, no per-lane branch.  <kPinhole, false> is the
+// kernel the parity tests pin bit for bit; the other five instances differ only in the Jacobian / mean (ortho, fisheye) and in
+// the opacity they file (antialiased: o * compensation).
+enum CameraModel : int { kPinhole = GWBP_CAMERA_PINHOLE, kOrtho = GWBP_CAMERA_ORTHO, kFisheye = GWBP_CAMERA_FISHEYE };
+
+template <int CAM, bool AA>
 __global__ __launch_bounds__(kScanBlock) void k_project(
     int64_t N, ViewDev V, const float *__restrict__ means, const float *__restrict__ quats,
     const float *__restrict__ scales, const float *__restrict__ opac, G2D *__restrict__ g2d,
     uint2 *__restrict__ rect, u32 *__restrict__ touched, u32 *__restrict__ dkeys, u32 *__restrict__ dvals,
     Counters *__restrict__ ctr, int32_t *__restrict__ o_radii, float *__restrict__ o_means2d, float *__restrict__ o_depths,
-    float *__restrict__ o_conics, int tight, int prio)
+    float *__restrict__ o_conics, float *__restrict__ o_comp, int tight, int prio)
 {
     front_priority(prio);
     const int64_t i = (int64_t)blockIdx.x * kScanBlock + threadIdx.x;
@@ -24,6 +31,7 @@ __global__ __launch_bounds__(kScanBlock) void k_project(
     G2D g;
     g.mx = g.my = g.opac = g.depth = g.ca = g.cb = g.cc = 0.f;
     g.radius = 0;
+    float comp = 0.f; // antialiased: sqrt(det(Sigma2) / det(Sigma2 + eps2d I)) of a visible Gaussian
     uint2 rc = make_uint2(0u, 0u);
 
     if (i < N) {
@@ -71,33 +79,78 @@ __global__ __launch_bounds__(kScanBlock) void k_project(
             const float C22 = dot3f(A20, A21, A22, V.R[6], V.R[7], V.R[8]);
 
             const float Wf = (float)V.W, Hf = (float)V.H;
-            const float tan_fovx = 0.5f * Wf / V.fx, tan_fovy = 0.5f * Hf / V.fy;
-            const float lim_x_pos = (Wf - V.cx) / V.fx + kClampMargin * tan_fovx;
-            const float lim_x_neg = V.cx / V.fx + kClampMargin * tan_fovx;
-            const float lim_y_pos = (Hf - V.cy) / V.fy + kClampMargin * tan_fovy;
-            const float lim_y_neg = V.cy / V.fy + kClampMargin * tan_fovy;
-            const float rz = 1.0f / z;
-            const float rz2 = rz * rz;
-            const float txc = z * __builtin_fminf(lim_x_pos, __builtin_fmaxf(-lim_x_neg, x * rz));
-            const float tyc = z * __builtin_fminf(lim_y_pos, __builtin_fmaxf(-lim_y_neg, y * rz));
-            const float J00 = V.fx * rz, J02 = -(V.fx * txc * rz2);
-            const float J11 = V.fy * rz, J12 = -(V.fy * tyc * rz2);
-            const float B00 = __builtin_fmaf(C02, J02, C00 * J00);
-            const float B02 = __builtin_fmaf(C22, J02, C02 * J00);
-            const float B10 = __builtin_fmaf(C02, J12, C01 * J11);
-            const float B11 = __builtin_fmaf(C12, J12, C11 * J11);
-            const float B12 = __builtin_fmaf(C22, J12, C12 * J11);
-            float c00 = __builtin_fmaf(J02, B02, J00 * B00);
-            const float c01 = __builtin_fmaf(J02, B12, J00 * B10);
-            float c11 = __builtin_fmaf(J12, B12, J11 * B11);
-            const float u = __builtin_fmaf(V.fx, x * rz, V.cx);
-            const float v = __builtin_fmaf(V.fy, y * rz, V.cy);
+            float c00, c01, c11, u, v;
+            if constexpr (CAM == kPinhole) {
+                const float tan_fovx = 0.5f * Wf / V.fx, tan_fovy = 0.5f * Hf / V.fy;
+                const float lim_x_pos = (Wf - V.cx) / V.fx + kClampMargin * tan_fovx;
+                const float lim_x_neg = V.cx / V.fx + kClampMargin * tan_fovx;
+                const float lim_y_pos = (Hf - V.cy) / V.fy + kClampMargin * tan_fovy;
+                const float lim_y_neg = V.cy / V.fy + kClampMargin * tan_fovy;
+                const float rz = 1.0f / z;
+                const float rz2 = rz * rz;
+                const float txc = z * __builtin_fminf(lim_x_pos, __builtin_fmaxf(-lim_x_neg, x * rz));
+                const float tyc = z * __builtin_fminf(lim_y_pos, __builtin_fmaxf(-lim_y_neg, y * rz));
+                const float J00 = V.fx * rz, J02 = -(V.fx * txc * rz2);
+                const float J11 = V.fy * rz, J12 = -(V.fy * tyc * rz2);
+                const float B00 = __builtin_fmaf(C02, J02, C00 * J00);
+                const float B02 = __builtin_fmaf(C22, J02, C02 * J00);
+                const float B10 = __builtin_fmaf(C02, J12, C01 * J11);
+                const float B11 = __builtin_fmaf(C12, J12, C11 * J11);
+                const float B12 = __builtin_fmaf(C22, J12, C12 * J11);
+                c00 = __builtin_fmaf(J02, B02, J00 * B00);
+                c01 = __builtin_fmaf(J02, B12, J00 * B10);
+                c11 = __builtin_fmaf(J12, B12, J11 * B11);
+                u = __builtin_fmaf(V.fx, x * rz, V.cx);
+                v = __builtin_fmaf(V.fy, y * rz, V.cy);
+            } else {
+                // J = d(u, v) / d(x, y, z), full 2 x 3; Sigma2 = J C J^T.  No clamp of x/z, y/z (gsplat clamps only the pinhole).
+                float J00, J01, J02, J10, J11, J12;
+                if constexpr (CAM == kOrtho) { // gsplat ortho_proj: u = fx x + cx, v = fy y + cy
+                    J00 = V.fx, J01 = 0.f, J02 = 0.f;
+                    J10 = 0.f, J11 = V.fy, J12 = 0.f;
+                    u = __builtin_fmaf(V.fx, x, V.cx);
+                    v = __builtin_fmaf(V.fy, y, V.cy);
+                } else { // gsplat fisheye_proj, ideal equidistant: u = fx x theta / rho + cx, theta = atan2(rho, z)
+                    // 1e-7 on rho, on z inside theta and on x^2 keeps the optical axis (rho = 0) finite: there J -> diag(fx, fy) / z.
+                    // Accurate atan2f / sqrtf (not the __ fast variants): theta enters the mean directly.
+                    constexpr float eps = 1e-7f;
+                    const float rho = sqrtf(x * x + y * y) + eps;
+                    const float theta = atan2f(rho, z + eps);
+                    const float xx = x * x + eps, yy = y * y, xy = x * y;
+                    const float r2 = xx + yy;
+                    const float iR2 = 1.0f / (r2 + z * z);
+                    const float a = z * iR2 / r2;    // z / (R^2 rho^2)
+                    const float b = theta / rho / r2; // theta / rho^3
+                    J00 = V.fx * (xx * a + yy * b), J01 = V.fx * xy * (a - b), J02 = -(V.fx * x * iR2);
+                    J10 = V.fy * xy * (a - b), J11 = V.fy * (yy * a + xx * b), J12 = -(V.fy * y * iR2);
+                    const float s = theta / rho;
+                    u = __builtin_fmaf(V.fx, x * s, V.cx);
+                    v = __builtin_fmaf(V.fy, y * s, V.cy);
+                }
+                // B = J C (C symmetric), Sigma2 = B J^T
+                const float B00 = dot3f(J00, J01, J02, C00, C01, C02);
+                const float B01 = dot3f(J00, J01, J02, C01, C11, C12);
+                const float B02 = dot3f(J00, J01, J02, C02, C12, C22);
+                const float B10 = dot3f(J10, J11, J12, C00, C01, C02);
+                const float B11 = dot3f(J10, J11, J12, C01, C11, C12);
+                const float B12 = dot3f(J10, J11, J12, C02, C12, C22);
+                c00 = dot3f(B00, B01, B02, J00, J01, J02);
+                c01 = dot3f(B00, B01, B02, J10, J11, J12);
+                c11 = dot3f(B10, B11, B12, J10, J11, J12);
+            }
 
+            // antialiased (gsplat rasterize_mode="antialiased"): the determinant BEFORE the low-pass filter
+            const float det_orig = AA ? c00 * c11 - c01 * c01 : 0.f;
             c00 += V.eps2d;
             c11 += V.eps2d;
             const float det = c00 * c11 - c01 * c01;
             ok = det > 0.f;
             if (ok) {
+                float o = opac[i];
+                if constexpr (AA) {
+                    comp = __builtin_sqrtf(__builtin_fmaxf(0.f, det_orig / det));
+                    o = o * comp;
+                }
                 const float inv_det = 1.0f / det;
                 const float b = 0.5f * (c00 + c11);
                 const float v1 = b + __builtin_sqrtf(__builtin_fmaxf(kRadiusFloor, b * b - det));
@@ -118,7 +171,7 @@ __global__ __launch_bounds__(kScanBlock) void k_project(
                         // sigma >= dx^2 / (2 Sxx) for every dy (Sxx = c00, the 2-D covariance), so a pixel centre farther
                         // than sqrt(2 L c00) from the mean in x (c11 in y) cannot contribute.  Same bound, same 5 % + 1 px
                         // margin and same 1e-3 slack on L as the strip mask of k_blend (which the parity tests pin).
-                        const float L = __logf(255.0f * opac[i]) + 1e-3f;
+                        const float L = __logf(255.0f * o) + 1e-3f;
                         if (!(L > 0.f)) {
                             x1 = x0, y1 = y0; // o <= 1/255: never reaches alpha >= 1/255
                         } else {
@@ -137,7 +190,7 @@ __global__ __launch_bounds__(kScanBlock) void k_project(
                             }
                         }
                     }
-                    g.mx = u, g.my = v, g.opac = opac[i], g.depth = z;
+                    g.mx = u, g.my = v, g.opac = o, g.depth = z;
                     g.ca = c11 * inv_det, g.cb = -c01 * inv_det, g.cc = c00 * inv_det;
                     g.radius = (int)radf;
                     rc = make_uint2(x0 | (x1 << 16), y0 | (y1 << 16));
@@ -162,6 +215,8 @@ __global__ __launch_bounds__(kScanBlock) void k_project(
             o_depths[i] = g.depth;
         if (o_conics)
             o_conics[3 * i] = g.ca, o_conics[3 * i + 1] = g.cb, o_conics[3 * i + 2] = g.cc;
+        if (AA && o_comp)
+            o_comp[i] = g.radius > 0 ? comp : 0.f;
     }
 
     // visible-Gaussian count
@@ -327,7 +382,7 @@ int launch_emit_scanned(const Layout &L, const Ws &W, const ViewDev &V, const u3
 
 int launch_project(const Layout &L, const Ws &W, const ViewDev &V, const float *means, const float *quats,
                    const float *scales, const float *opac, int32_t *radii, float *means2d, float *depths,
-                   float *conics, hipStream_t s)
+                   float *conics, hipStream_t s, int camera_model, int rasterize_mode, float *compensations)
 {
     const int prio = (L.flags & GWBP_FLAG_FRONT_PRIORITY) ? 1 : 0;
     // counters and the pool shard heads / scatter queues are adjacent sub-buffers (g2d follows): one memset node
@@ -337,9 +392,17 @@ int launch_project(const Layout &L, const Ws &W, const ViewDev &V, const float *
         return rc;
     if (L.n == 0)
         return GWBP_OK;
-    hipLaunchKernelGGL(k_project, dim3(L.n_scan_blocks), dim3(kScanBlock), 0, s, L.n, V, means, quats, scales, opac,
+    const bool aa = rasterize_mode == GWBP_RASTERIZE_ANTIALIASED;
+    decltype(&k_project<kPinhole, false>) k = nullptr;
+    switch (camera_model) {
+    case kPinhole: k = aa ? k_project<kPinhole, true> : k_project<kPinhole, false>; break;
+    case kOrtho: k = aa ? k_project<kOrtho, true> : k_project<kOrtho, false>; break;
+    case kFisheye: k = aa ? k_project<kFisheye, true> : k_project<kFisheye, false>; break;
+    default: return set_error(GWBP_EINVAL, "unknown camera model %d", camera_model);
+    }
+    hipLaunchKernelGGL(k, dim3(L.n_scan_blocks), dim3(kScanBlock), 0, s, L.n, V, means, quats, scales, opac,
                        W.g2d, W.rect, W.touched, W.dkeys[0], W.dvals[0], W.counters, radii, means2d, depths, conics,
-                       L.flags & GWBP_FLAG_TIGHT_BINNING, prio);
+                       compensations, L.flags & GWBP_FLAG_TIGHT_BINNING, prio);
     return check_hip(hipGetLastError(), "project launch");
 }
 

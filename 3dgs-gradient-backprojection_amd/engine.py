@@ -153,23 +153,37 @@ class Engine:
         return C.byref(self.caps), self._ws_ptr, C.c_size_t(self.ws_bytes)
 
     def view(self, viewmat, K, width, height, **kw):
+        """make_view: near_plane, far_plane, eps2d, radius_clip, camera_model ("pinhole" | "ortho" | "fisheye") and
+        rasterize_mode ("classic" | "antialiased") as keywords."""
         return make_view(viewmat, K, int(width), int(height), **kw)
 
     # ---- stages ------------------------------------------------------------------------------------------
     def project(self, view, means, quats, scales, opacities, want_outputs=False):
+        """Projection of `view` under the camera model and rasterize mode it carries (Engine.view / make_view): the default
+        pinhole / classic view issues gwbp_project, any other gwbp_project_camera; every later stage of the view reads the
+        projected table either writes.  want_outputs: radii, means2d, depths, conics -- and, under antialiased, compensations."""
         means, quats = _req(means, "means", (3,)), _req(quats, "quats", (4,))
         scales, opacities = _req(scales, "scales", (3,)), _req(opacities, "opacities")
         if means.shape[0] != self.n:
             raise GwbpError(f"engine was sized for {self.n} Gaussians, got {means.shape[0]}")
+        model, mode = _lib.camera_of(view)
         out = {}
         if want_outputs:
             out = dict(radii=torch.empty(self.n, dtype=torch.int32, device=self.device),
                        means2d=torch.empty(self.n, 2, device=self.device),
                        depths=torch.empty(self.n, device=self.device),
                        conics=torch.empty(self.n, 3, device=self.device))
-        self._call("gwbp_project", *self._args(), C.byref(view), ptr(means), ptr(quats), ptr(scales),
-                                    ptr(opacities), ptr(out.get("radii")), ptr(out.get("means2d")),
-                                    ptr(out.get("depths")), ptr(out.get("conics")), self._stream())
+            if mode == "antialiased":
+                out["compensations"] = torch.empty(self.n, device=self.device)
+        if model == "pinhole" and mode == "classic":
+            self._call("gwbp_project", *self._args(), C.byref(view), ptr(means), ptr(quats), ptr(scales),
+                                        ptr(opacities), ptr(out.get("radii")), ptr(out.get("means2d")),
+                                        ptr(out.get("depths")), ptr(out.get("conics")), self._stream())
+            return out
+        self._call("gwbp_project_camera", *self._args(), C.byref(view), _lib.CAMERA_MODELS[model],
+                   _lib.RASTERIZE_MODES[mode], ptr(means), ptr(quats), ptr(scales), ptr(opacities), ptr(out.get("radii")),
+                   ptr(out.get("means2d")), ptr(out.get("depths")), ptr(out.get("conics")), ptr(out.get("compensations")),
+                   self._stream())
         return out
 
     def bin_sort(self, view, want_outputs=False):
@@ -510,7 +524,11 @@ class Engine:
             raise GwbpError(f"d must be a contiguous float32 HIP tensor [{self.n}]")
 
     def backproject_view(self, view, means, quats, scales, opacities, feats, F, d, scale_f=1.0, scale_d=1.0):
-        """Per-view body of create_feature_field_* (backproject.py:115-151), one fused call."""
+        """Per-view body of create_feature_field_* (backproject.py:115-151), one fused call (pinhole / classic views only:
+        gwbp_backproject_view has no camera settings)."""
+        if not _lib.is_default_camera(view):
+            raise GwbpError("backproject_view is pinhole / classic only; use project + bin_sort + blend_weights + scatter "
+                            f"for {_lib.camera_of(view)}")
         sy, sx, sc, D = self._feat_strides(feats, view)
         self._check_acc(F, d, D)
         means, quats = _req(means, "means", (3,)), _req(quats, "quats", (4,))

@@ -35,8 +35,9 @@ def _group():
 
 
 def gradient_mask(splats: Dict[str, torch.Tensor], viewmats: torch.Tensor, K: torch.Tensor, width: int,
-                  height: int) -> torch.Tensor:
-    """bool[N]: Gaussians that receive weight in at least one of the views (utils.py:236-257).
+                  height: int, camera_model: str = "pinhole", rasterize_mode: str = "classic") -> torch.Tensor:
+    """bool[N]: Gaussians that receive weight in at least one of the views (utils.py:236-257), projected with gsplat's
+    camera_model / rasterize_mode.
 
     Under a process group the views are sharded r, r + R, ... like the field build and the per-rank weight sums are
     all-reduced: every rank returns the SAME mask (an all-reduce hands every rank the same bits), so the Gaussian slices and
@@ -50,7 +51,7 @@ def gradient_mask(splats: Dict[str, torch.Tensor], viewmats: torch.Tensor, K: to
     d = torch.zeros(n, device=dev)
     vm_host, K_host = viewmats.detach().cpu(), K.detach().cpu()
     for v in view_shard(viewmats.shape[0], rank, world):
-        view = eng.view(vm_host[v], K_host, width, height)
+        view = eng.view(vm_host[v], K_host, width, height, camera_model=camera_model, rasterize_mode=rasterize_mode)
         while True:
             eng.project(view, means, quats, scales, opac)
             eng.bin_sort(view)
@@ -66,10 +67,11 @@ def gradient_mask(splats: Dict[str, torch.Tensor], viewmats: torch.Tensor, K: to
 
 
 def prune_by_gradients(splats: Dict[str, torch.Tensor], viewmats: torch.Tensor, K: torch.Tensor, width: int,
-                       height: int) -> Tuple[Dict[str, torch.Tensor], torch.Tensor]:
+                       height: int, camera_model: str = "pinhole",
+                       rasterize_mode: str = "classic") -> Tuple[Dict[str, torch.Tensor], torch.Tensor]:
     """(pruned copy of the splats dict, mask): utils.py:222-271 with the cameras passed explicitly instead of through
     splats["colmap_project"]."""
-    mask = gradient_mask(splats, viewmats, K, width, height)
+    mask = gradient_mask(splats, viewmats, K, width, height, camera_model, rasterize_mode)
     out = dict(splats)
     for k in _PER_GAUSSIAN:
         if k in out:
@@ -78,7 +80,8 @@ def prune_by_gradients(splats: Dict[str, torch.Tensor], viewmats: torch.Tensor, 
 
 
 def check_proper_pruning(splats: Dict[str, torch.Tensor], pruned: Dict[str, torch.Tensor], viewmats: torch.Tensor,
-                         K: torch.Tensor, width: int, height: int) -> Dict[str, float]:
+                         K: torch.Tensor, width: int, height: int, camera_model: str = "pinhole",
+                         rasterize_mode: str = "classic") -> Dict[str, float]:
     """utils.test_proper_pruning (utils.py:292-360): SH-degree-3 render of every view before and after pruning through
     the drop-in rasterization(); asserts max |difference| < 1 / (255 * 2) like utils.py:353-355.  Under a process group each rank
     renders its shard of the views; the maximum and the total are reduced, every rank asserts on the same numbers."""
@@ -92,7 +95,7 @@ def check_proper_pruning(splats: Dict[str, torch.Tensor], pruned: Dict[str, torc
     with torch.no_grad():
         for v in view_shard(viewmats.shape[0], rank, world):
             kw = dict(viewmats=viewmats[v][None], Ks=K[None], sh_degree=3, width=int(width), height=int(height),
-                      want_meta=False)
+                      want_meta=False, camera_model=camera_model, rasterize_mode=rasterize_mode)
             out, _, _ = rasterization(*a, cols(splats), **kw)
             out_p, _, _ = rasterization(*b, cols(pruned), **kw)
             diff = (out - out_p).abs()

@@ -17,6 +17,7 @@ from typing import Dict, Optional, Tuple
 import torch
 from torch.utils import _pytree
 
+from . import _lib
 from ._lib import GwbpError
 from .engine import TILE, Engine
 
@@ -133,7 +134,7 @@ def _front_key(view, tensors):
     tensors THEMSELVES are kept in the cache entry and compared with `is` (_same_tensors): a (data_ptr, _version) key alone
     would match a NEW temporary that the caching allocator placed at a freed tensor's address (opac.clone() twice from a
     fixed camera: the second call would silently reuse the first one's projection and weight store)."""
-    return (bytes(view), tuple((t._version, tuple(t.shape), tuple(t.stride())) for t in tensors))
+    return (bytes(view), _lib.camera_of(view), tuple((t._version, tuple(t.shape), tuple(t.stride())) for t in tensors))
 
 
 def _same_tensors(held, tensors) -> bool:
@@ -400,15 +401,19 @@ class LazyMeta(dict):
     """meta dict of gsplat.rasterization (packed=True layout); the packed index tensors are materialised on
     first access because building them (nonzero) synchronises the host."""
 
-    def __init__(self, eager, holders, n_cameras):
+    def __init__(self, eager, holders, n_cameras, antialiased=False):
         super().__init__(eager)
         self._h, self._c = holders, n_cameras
+        self._aa = antialiased
+        if antialiased:  # gsplat: meta["opacities"] are the compensated opacities the blend used, meta["compensations"] beside
+            self._LAZY = self._LAZY + ("compensations",)
 
     _LAZY = ("camera_ids", "gaussian_ids", "radii", "means2d", "depths", "conics", "opacities", "tiles_per_gauss",
              "isect_ids", "flatten_ids", "isect_offsets")
 
     def _build(self):
-        cams, gids, parts = [], [], {k: [] for k in ("radii", "means2d", "depths", "conics")}
+        cams, gids = [], []
+        parts = {k: [] for k in ("radii", "means2d", "depths", "conics") + (("compensations",) if self._aa else ())}
         isect, flat, offs, base = [], [], [], 0
         for c, h in enumerate(self._h):
             p, b = h["proj"], h["bins"]
@@ -429,6 +434,8 @@ class LazyMeta(dict):
         for k in parts:
             self[k] = torch.cat(parts[k])
         self["opacities"] = self._opac[self["gaussian_ids"]]
+        if self._aa:
+            self["opacities"] = self["opacities"] * self["compensations"]
         self["isect_ids"], self["flatten_ids"] = torch.cat(isect), torch.cat(flat)
         self["isect_offsets"] = torch.stack(offs).reshape(self._c, self["tile_height"], self["tile_width"])
         r = self["radii"].to(torch.float32) / TILE
@@ -459,11 +466,16 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
 
     Returns (render_colors [C,H,W,D'], render_alphas [C,H,W,1], meta).  `channel_chunk`, `packed`, `sparse_grad`
     are accepted for compatibility and have no effect (the kernels are channel-count generic and unpacked).
+    camera_model "pinhole" | "ortho" | "fisheye" (gsplat's ideal models, no distortion) and rasterize_mode "classic" |
+    "antialiased" (opacity x compensation; meta["opacities"] then holds the compensated opacities, meta["compensations"] the
+    factors) select the projection kernel; depth render modes keep camera z for every model, like gsplat.
     """
     if tile_size != TILE:
         raise GwbpError(f"tile_size must be {TILE}: the tile rectangle is part of the numerics")
-    if camera_model != "pinhole" or covars is not None or distributed or absgrad or rasterize_mode != "classic":
-        raise NotImplementedError("only pinhole / classic / single-process rasterization is on the reference's path")
+    if (camera_model not in _lib.CAMERA_MODELS or covars is not None or distributed or absgrad
+            or rasterize_mode not in _lib.RASTERIZE_MODES):
+        raise NotImplementedError("only pinhole / ortho / fisheye cameras, classic / antialiased rasterization and "
+                                  "single-process calls without covars / absgrad are implemented")
     if render_mode not in ("RGB", "D", "ED", "RGB+D", "RGB+ED"):
         raise ValueError(render_mode)
     if not means.is_cuda:
@@ -471,7 +483,8 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     width, height = int(width), int(height)  # utils.py:247-248 passes 0-d tensors
     C_ = viewmats.shape[0]
     N = means.shape[0]
-    kw = dict(near_plane=near_plane, far_plane=far_plane, eps2d=eps2d, radius_clip=radius_clip)
+    kw = dict(near_plane=near_plane, far_plane=far_plane, eps2d=eps2d, radius_clip=radius_clip, camera_model=camera_model,
+              rasterize_mode=rasterize_mode)
 
     outs, alphas, holders = [], [], []
     for c in range(C_):
@@ -506,7 +519,7 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
         holders.append(holder)
     tw, th = -(-width // TILE), -(-height // TILE)
     eager = dict(tile_width=tw, tile_height=th, width=width, height=height, tile_size=TILE, n_cameras=C_)
-    meta = LazyMeta(eager, holders, C_) if want_meta else eager
+    meta = LazyMeta(eager, holders, C_, antialiased=rasterize_mode == "antialiased") if want_meta else eager
     if want_meta:
         meta._opac = opacities
     if C_ == 1:  # (no copy of a 3.5 GB render: a view with the camera axis in front)

@@ -20,6 +20,8 @@ _CAMERA_MODELS = {0: ("SIMPLE_PINHOLE", 3), 1: ("PINHOLE", 4), 2: ("SIMPLE_RADIA
                   4: ("OPENCV", 8), 5: ("OPENCV_FISHEYE", 8), 6: ("FULL_OPENCV", 12), 7: ("FOV", 5),
                   8: ("SIMPLE_RADIAL_FISHEYE", 4), 9: ("RADIAL_FISHEYE", 5), 10: ("THIN_PRISM_FISHEYE", 12)}
 
+_FISHEYE_MODELS = ("SIMPLE_RADIAL_FISHEYE", "RADIAL_FISHEYE", "OPENCV_FISHEYE", "THIN_PRISM_FISHEYE")
+
 
 @dataclass
 class Camera:
@@ -49,6 +51,17 @@ class Camera:
     @property
     def cy(self):
         return float(self.params[3] if self._two_focal else self.params[2])
+
+    @property
+    def gsplat_camera_model(self) -> str:
+        """gsplat.rasterization's camera_model for this COLMAP model: the fisheye family -> "fisheye" (gsplat's ideal
+        equidistant model), everything else -> "pinhole".  Distortion coefficients are ignored either way (`distortion`)."""
+        return "fisheye" if self.model in _FISHEYE_MODELS else "pinhole"
+
+    @property
+    def distortion(self) -> np.ndarray:
+        """The parameters after focal length(s) and principal point: the distortion coefficients (empty for PINHOLE)."""
+        return np.asarray(self.params[4:] if self._two_focal else self.params[3:])
 
 
 @dataclass
@@ -228,6 +241,7 @@ def load_checkpoint(checkpoint: str, data_dir: str, format: Optional[str] = "gsp
             splats[k] = val.detach()
     cam = next(iter(colmap_project.cameras.values()))  # "Assuming only one camera" (utils.py:92)
     splats["camera_matrix"] = camera_matrix(cam, data_factor)
+    splats["camera_model"] = cam.gsplat_camera_model  # what gsplat.rasterization should be told (not read by the reference)
     splats["colmap_project"] = colmap_project
     splats["colmap_dir"] = data_dir
     return splats

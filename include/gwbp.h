@@ -131,6 +131,27 @@ GWBP_API int gwbp_project(const gwbp_caps *caps, void *workspace, size_t workspa
                  const float *means, const float *quats, const float *scales, const float *opacities,
                  int32_t *radii, float *means2d, float *depths, float *conics, void *stream);
 
+/* Camera models and rasterize modes of gwbp_project_camera (gsplat.rasterization's camera_model / rasterize_mode). */
+#define GWBP_CAMERA_PINHOLE 0 /* u = fx x / z + cx; x/z, y/z clamped to the frustum + 30 % margin inside the Jacobian */
+#define GWBP_CAMERA_ORTHO 1   /* u = fx x + cx, v = fy y + cy; J = [[fx, 0, 0], [0, fy, 0]] */
+#define GWBP_CAMERA_FISHEYE 2 /* ideal equidistant: u = fx x theta / rho + cx, rho = |(x, y)|, theta = atan2(rho, z); no
+                               * distortion coefficients; exact Jacobian of that map */
+#define GWBP_RASTERIZE_CLASSIC 0
+#define GWBP_RASTERIZE_ANTIALIASED 1 /* opacity x compensation, compensation = sqrt(det(S) / det(S + eps2d I)) of the 2-D
+                                      * covariance S; radius, culling and conic as in classic */
+
+/* gwbp_project under a camera model and a rasterize mode.  Everything downstream (bin_sort, every blend / scatter / render
+ * entry point) reads the projected table it writes, so it takes the place of gwbp_project for the view; under
+ * GWBP_RASTERIZE_ANTIALIASED the table holds the compensated opacities (as does the GWBP_FLAG_TIGHT_BINNING bound).
+ * compensations[N] (optional) is gsplat's meta["compensations"]: written under GWBP_RASTERIZE_ANTIALIASED only, 0 for culled
+ * Gaussians.
+ * Equal to gwbp_project bit for bit for (GWBP_CAMERA_PINHOLE, GWBP_RASTERIZE_CLASSIC).  An unknown model or mode is
+ * GWBP_EINVAL, checked before anything else.  gwbp_backproject_view stays pinhole / classic. */
+GWBP_API int gwbp_project_camera(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                 int32_t camera_model, int32_t rasterize_mode, const float *means, const float *quats, const float *scales,
+                 const float *opacities, int32_t *radii, float *means2d, float *depths, float *conics,
+                 float *compensations, void *stream);
+
 /* isect_tiles + stable radix sort by (tile, depth) + isect_offset_encode.  Optional outputs:
  * isect_ids[isect_cap] int64 sorted keys, flatten_ids[isect_cap] int32, tile_offsets[tiles+1] int32. */
 GWBP_API int gwbp_bin_sort(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
@@ -255,7 +276,8 @@ GWBP_API int gwbp_sh_colors(int64_t N, int32_t degree, int32_t K, const float *m
 /* ---- fused entry points --------------------------------------------------------------------------------- */
 
 /* project -> bin_sort -> blend_weights -> scatter for one view: the per-view body of
- * create_feature_field_lseg (backproject.py:115-151) in one call, one blend instead of two. */
+ * create_feature_field_lseg (backproject.py:115-151) in one call, one blend instead of two.  Pinhole camera, classic
+ * rasterize mode only: other camera settings go through gwbp_project_camera and the stage entry points. */
 GWBP_API int gwbp_backproject_view(const gwbp_caps *caps, void *workspace, size_t workspace_bytes,
                           const gwbp_view *view_host, const float *means, const float *quats, const float *scales,
                           const float *opacities, const float *feats, int64_t fs_y, int64_t fs_x, int64_t fs_c,

@@ -18,7 +18,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 
-def main():
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--data-dir", default="./data/garden")
     ap.add_argument("--checkpoint", default="./data/garden/ckpts/ckpt_29999_rank0.pt")
@@ -51,7 +51,33 @@ def main():
     ap.add_argument("--dist-backend", default="nccl", help="process-group backend under torchrun (nccl = RCCL over xGMI)")
     ap.add_argument("--one-device", action="store_true",
                     help="every rank uses cuda:0 (with --dist-backend gloo: the N > 1 bookkeeping on a one-GPU box)")
-    args = ap.parse_args()
+    # gsplat.rasterization's projection options (not flags of the reference's main(), which always rasterises pinhole / classic)
+    ap.add_argument("--camera-model", choices=["pinhole", "ortho", "fisheye"], default=None,
+                    help="camera model of the projection (default pinhole; gsplat's fisheye is the ideal equidistant model, "
+                         "no distortion coefficients)")
+    ap.add_argument("--rasterize-mode", choices=["classic", "antialiased"], default="classic",
+                    help="antialiased: opacity x compensation, for scenes trained with gsplat's antialiased switch")
+    return ap
+
+
+def camera_warnings(cam, camera_model_arg):
+    """One-line warnings about a COLMAP camera the projection does not model exactly: a fisheye model without --camera-model
+    (it is projected as a pinhole), and fisheye distortion coefficients (gsplat's fisheye model ignores them too)."""
+    out = []
+    if cam.gsplat_camera_model == "fisheye":
+        if camera_model_arg is None:
+            out.append(f"warning: the COLMAP camera is {cam.model}, a fisheye model, and --camera-model was not given: "
+                       "projecting as pinhole (pass --camera-model fisheye)")
+        if cam.distortion.size and bool((cam.distortion != 0).any()):
+            out.append(f"warning: the {cam.model} camera has non-zero distortion coefficients "
+                       f"{[float(k) for k in cam.distortion]}; they are ignored (gsplat's fisheye model has none)")
+    return out
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    camera_model = args.camera_model or "pinhole"
+    cam_kw = dict(camera_model=camera_model, rasterize_mode=args.rasterize_mode)
 
     import gsbp_amd  # BEFORE the first HIP call: the package asks the runtime for the hardware queues its view pipeline needs
     if not torch.cuda.is_available():
@@ -85,6 +111,9 @@ def main():
         scales, opac = torch.exp(splats["scaling"]).to(dev).float(), torch.sigmoid(splats["opacity"]).to(dev).float()
         splats = {k: (v.to(dev).float() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in splats.items()}
         K = splats["camera_matrix"]
+        if rank == 0:
+            for line in camera_warnings(next(iter(splats["colmap_project"].cameras.values())), args.camera_model):
+                print(line, file=sys.stderr)
         W, H = int(K[0, 2] * 2), int(K[1, 2] * 2)  # backproject.py:85-86
         images = sorted(splats["colmap_project"].images.values(), key=lambda im: im.name)  # backproject.py:74
         viewmats = torch.stack([scene_io.get_viewmat_from_colmap_image(im) for im in images])
@@ -123,20 +152,20 @@ def main():
             print("Remaining", int(keep.sum()), "splats")
         if "features_dc" in splats:  # utils.test_proper_pruning renders with the SH colours (checkpoints only)
             pruned = {k: (v[keep] if k in gsbp_amd.pruning._PER_GAUSSIAN else v) for k, v in splats.items()}
-            rep = gsbp_amd.check_proper_pruning(splats, pruned, vm_dev, K_dev, W, H)
+            rep = gsbp_amd.check_proper_pruning(splats, pruned, vm_dev, K_dev, W, H, **cam_kw)
             if rank == 0:
                 print("Percentage pruned: ", rep["percentage_pruned"])  # utils.py:348-359
                 print("Max pixel error: ", rep["max_pixel_error"])
                 print("Total pixel error: ", rep["total_pixel_error"])
 
     if not args.no_prune and not args.prune_by_product:
-        keep = gsbp_amd.pruning.gradient_mask(splats, vm_dev, K_dev, W, H)
+        keep = gsbp_amd.pruning.gradient_mask(splats, vm_dev, K_dev, W, H, **cam_kw)
         report_and_check(keep)
         means, quats, scales, opac = means[keep], quats[keep], scales[keep], opac[keep]
 
     out, F, d, stats = gsbp_amd.create_feature_field(means, quats, scales, opac, viewmats, K, W, H, feature_fn, dim,
                                                      reduction=reduction, encoder=encoder, return_partials=True,
-                                                     verbose=True, upsample=upsample)
+                                                     verbose=True, upsample=upsample, **cam_kw)
     if args.prune_by_product and not args.no_prune:
         # "the mask comes free from the fused kernel" -- d is the all-reduced denominator of every Gaussian,
         # identical on every rank

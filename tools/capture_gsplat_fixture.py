@@ -17,7 +17,8 @@ Gaussians, 4 views 400 x 300, D = 32: the fused blend + scatter kernels), T1 wit
 
 and commits the resulting .npz DATA files (inputs are already committed; nothing of gsplat's or the reference's source
 travels).  tests/test_oracle.py::test_oracle_against_gsplat_capture (CPU) and tests/test_gpu_parity.py::
-test_hip_against_gsplat_capture (GPU) consume the files when present and are skipped otherwise.
+test_hip_against_gsplat_capture (GPU) consume the files when present and are skipped otherwise; CAMERA_CASES (fisheye,
+ortho, pinhole + antialiased on T1) go to tests/golden/gsplat_camera_*.npz for tests/test_gpu_camera_models_capture.py.
 
 What is captured, per view, mirrors the reference's per-view body (backproject.py:115-151) literally:
   * rasterization(means, quats, scales, opacities, zeros[N, D], viewmat[None], K[None], width=W, height=H)
@@ -48,6 +49,13 @@ CASES = [
 # F.interpolate(mode="nearest") and reduces with .mean() exactly like backproject.py:244-248,263,283
 TOKEN_CASES = [
     ("gsplat_t1_tokens8x12_d256.npz", "T1", 256, (8, 12)),
+]
+# gsplat's projection options on T1: (file, seeded config, camera_model, rasterize_mode).  Consumed by
+# tests/test_gpu_camera_models_capture.py (skipped while the files are absent)
+CAMERA_CASES = [
+    ("gsplat_camera_t1_fisheye.npz", "T1", "fisheye", "classic"),
+    ("gsplat_camera_t1_ortho.npz", "T1", "ortho", "classic"),
+    ("gsplat_camera_t1_pinhole_antialiased.npz", "T1", "pinhole", "antialiased"),
 ]
 ENCODER_SEED = 7
 TOKEN_SEED0 = 500
@@ -94,6 +102,7 @@ def capture(inp, out_path, per_view=True):
     t = {k: torch.from_numpy(np.asarray(inp[k])).to(dev) for k in ("means", "quats", "scales", "opac", "K", "vms", "feats")}
     if inp.get("encoder") is not None:  # backproject_compressed.py:127: feats @ encoder, then the D = 16 loop
         t["feats"] = t["feats"] @ torch.from_numpy(np.asarray(inp["encoder"])).to(dev)
+    cam = {k: str(inp[k]) for k in ("camera_model", "rasterize_mode") if k in inp}  # CAMERA_CASES only
     mean = inp.get("reduction") == "mean"  # dino: .mean() instead of .sum() (backproject.py:263,283)
     if inp.get("upsample") == "nearest":   # dino: the tokens are upsampled to the view first (backproject.py:244-248)
         Wv, Hv = int(2 * float(inp["K"][0][2])), int(2 * float(inp["K"][1][2]))  # backproject.py:85-86
@@ -106,13 +115,13 @@ def capture(inp, out_path, per_view=True):
     for v in range(V):
         colors = torch.zeros(N, D, device=dev, requires_grad=True)
         out, alphas, meta = rasterization(t["means"], t["quats"], t["scales"], t["opac"], colors, t["vms"][v][None],
-                                          t["K"][None], width=W, height=H)
+                                          t["K"][None], width=W, height=H, **cam)
         prod = out[0] * t["feats"][v]
         (prod.mean() if mean else prod.sum()).backward()
         Fv.append(colors.grad.detach().clone())
         c3 = torch.zeros(N, 3, device=dev, requires_grad=True)
         out3, _, _ = rasterization(t["means"], t["quats"], t["scales"], t["opac"], c3, t["vms"][v][None], t["K"][None],
-                                   width=W, height=H)
+                                   width=W, height=H, **cam)
         (out3.mean() if mean else out3.sum()).backward()
         dv.append(c3.grad[:, 0].detach().clone())
         F += Fv[-1]
@@ -135,7 +144,7 @@ def capture(inp, out_path, per_view=True):
         save["F_views"] = torch.stack(Fv).cpu().numpy()
     # packed=True (gsplat's default) returns per-visible-Gaussian arrays + gaussian_ids; both layouts are stored as given
     for key in ("means2d", "radii", "conics", "depths", "gaussian_ids", "camera_ids", "isect_ids", "flatten_ids",
-                "isect_offsets", "tiles_per_gauss"):
+                "isect_offsets", "tiles_per_gauss") + (("opacities", "compensations") if cam else ()):
         val = m(key)
         if val is not None:
             save["v0_" + key] = val
@@ -159,6 +168,8 @@ def main():
         capture(inp, os.path.join(GOLD, fname), per_view=(dim or 0) < 128)
     for fname, cfgname, dim, grid in TOKEN_CASES:
         capture(token_case_inputs(cfgname, dim, grid), os.path.join(GOLD, fname), per_view=False)
+    for fname, cfgname, model, mode in CAMERA_CASES:
+        capture({**case_inputs(cfgname), "camera_model": model, "rasterize_mode": mode}, os.path.join(GOLD, fname))
 
 
 if __name__ == "__main__":
