@@ -13,10 +13,13 @@ follows if the whole field is wanted on every rank.
 from __future__ import annotations
 
 import time
+import warnings
+from collections import namedtuple
 from typing import Callable, Dict, Optional, Sequence
 
 import torch
 
+from . import _lib
 from .engine import Engine
 from .synthetic import view_shard
 
@@ -34,15 +37,6 @@ def reduce_partials(F: torch.Tensor, d: torch.Tensor) -> None:
     if world > 1:
         dist.all_reduce(F, op=dist.ReduceOp.SUM)
         dist.all_reduce(d, op=dist.ReduceOp.SUM)
-
-
-def encode_features(eng: Engine, feats: torch.Tensor, encoder: torch.Tensor, **kw) -> torch.Tensor:
-    """backproject_compressed.py:127 for the DRIVER: the hand-written kernel (Engine.encode_map), whose domain -- [H,W,K]
-    float32 maps with channel-contiguous 16-B aligned pixels, K % 16 == 0, K <= 2048, at most 16 outputs -- includes the
-    reference's 512 -> 16 encoder.  Anything else RAISES (Engine.encode_map's own error): the drivers never switch to a
-    library GEMM behind the caller's back.  Whoever wants one encodes in the feature function (`feats @ encoder`) and passes
-    encoder=None."""
-    return eng.encode_map(feats, encoder, **kw)
 
 
 def rows_per_rank(n: int, world: int) -> int:
@@ -126,7 +120,7 @@ def wide_kernel_selfcheck(device) -> bool:
     kernels differ only in summation order: 1.4e-7 measured over every build variant of round 5).  On disagreement
     ViewPipeline.choose_scatter_kernel warns and stays on the 128-channel kernel -- 5 % slower at BASELINE size, never wrong.
     A few milliseconds, once per process and device, before the first D % 256 == 0 job."""
-    from . import _lib, synthetic as syn
+    from . import synthetic as syn
     dev = torch.device(device)
     key = (_lib._lib_path, dev.index if dev.index is not None else torch.cuda.current_device())
     if key in _WIDE_OK:
@@ -153,6 +147,35 @@ def wide_kernel_selfcheck(device) -> bool:
     return ok
 
 
+def _scatter_weighted(e: Engine, view, feats, F, d, scale_f, scale_d, upsample=None, encoder=None) -> None:
+    """Scatter a view whose weight store has been blended (feats @ encoder with the encoder fused into the slab staging)."""
+    if encoder is not None:
+        e.scatter_encoded(view, feats, encoder, F, d, scale_f, scale_d)
+    else:
+        e.scatter(view, feats, F, d, scale_f, scale_d, upsample=upsample)
+
+
+def _blend_and_scatter(e: Engine, view, feats, F, d, scale_f, scale_d, upsample=None, encoder=None, fuse: bool = True,
+                       tokens: bool = False) -> None:
+    """Blend and scatter a projected and sorted view by the first form that suits its map: the fused blend + scatter kernel
+    (`fuse`; with `encoder` the encoder runs in its tile prologue), token space (`tokens`), or a weight store + scatter."""
+    if fuse and upsample is None and encoder is None and Engine.can_blend_scatter(feats):
+        e.blend_scatter(view, feats, F, d, scale_f, scale_d)
+    elif fuse and upsample is None and encoder is not None and Engine.can_blend_scatter_encoded(feats, encoder):
+        e.blend_scatter_encoded(view, feats, encoder, F, d, scale_f, scale_d)
+    elif tokens and upsample == "nearest" and encoder is None and Engine.can_scatter_tokens(feats, view.height, view.width):
+        e.blend_tokens(view, feats.shape[0], feats.shape[1])
+        e.scatter_tokens(view, feats, F, d, scale_f, scale_d)
+    else:
+        e.blend_weights(view)
+        _scatter_weighted(e, view, feats, F, d, scale_f, scale_d, upsample, encoder)
+
+
+# a view whose front stage has been enqueued (ViewPipeline.front): were its denominators added by the blend on the side
+# stream, its weight store blended, its token-quadrant weight sums blended (Engine.blend_tokens)?
+_Pending = namedtuple("_Pending", "view d_done blended tokens")
+
+
 class ViewPipeline:
     """Software pipeline over views on the caller's stream + side streams, one workspace per view in flight (two by default).
 
@@ -177,7 +200,6 @@ class ViewPipeline:
         # token-quadrant weight sums instead of a weight store) and scatter() runs Engine.scatter_tokens -- one plain
         # read-modify-write of every F row that receives weight, no atomics (csrc/token.hip)
         self.token_grid = tuple(int(x) for x in token_grid) if token_grid is not None else None
-        from . import _lib
         if _lib.hw_queues_late():
             # the schedule below is built on streams that run CONCURRENTLY; with the HIP runtime's default of 4 hardware queues
             # (fewer once RCCL has taken its own) the side streams share a queue with the caller's and the step becomes front +
@@ -188,7 +210,6 @@ class ViewPipeline:
                 "the variable) before the first CUDA/HIP call of the process, or run the views with pipeline=False"
                 % _lib.HW_QUEUES_WANTED)
         if not _lib.hw_queues_ok():  # somebody CHOSE fewer queues (the variable was set before the package was imported)
-            import warnings
             warnings.warn("GPU_MAX_HW_QUEUES=%s < %d: the view pipeline's streams may share hardware queues and run back to back"
                           % (__import__("os").environ.get("GPU_MAX_HW_QUEUES"), _lib.HW_QUEUES_WANTED), RuntimeWarning)
         self.eng = list(engines) if engines else [Engine(n_gaussians, width, height, device=self.dev, tight_binning=True)
@@ -266,7 +287,6 @@ class ViewPipeline:
         if wide and n_pairs is not None and n_headers:
             wide = n_pairs / n_headers >= self.WIDE_MIN_PAIRS_PER_RECORD
         if wide and self.dev.type == "cuda" and not wide_kernel_selfcheck(self.dev):
-            import warnings
             warnings.warn("the 256-channel scatter kernel of this build disagrees with the 128-channel one on the self-check "
                           "view (wide_kernel_selfcheck): using the 128-channel kernel.  Rebuild libgwbp.so "
                           "(python __graft_entry__.py) and report the toolchain version.", RuntimeWarning)
@@ -290,15 +310,14 @@ class ViewPipeline:
         elif not self.independent:
             side.wait_event(self.ev_done[b])  # workspace b is free once scatter(i-K) has finished
         # (independent: scatter(i-K) was enqueued on this very stream)
+        e = self.eng[b]
         if self.independent:  # the engine is bound to `side`
-            e = self.eng[b]
             e.project(view, means, quats, scales, opacities)
             e.bin_sort(view)
-            self.pending[self.i_front] = (view, False, False, False)
+            self.pending[self.i_front] = _Pending(view, False, False, False)
             self.i_front += 1
             return
         with torch.cuda.stream(side):
-            e = self.eng[b]
             e.project(view, means, quats, scales, opacities)
             e.bin_sort(view)
             d_done = d is not None and self.wide and not self.fuse_small and self.token_grid is None
@@ -307,7 +326,7 @@ class ViewPipeline:
             elif not self.fuse_small:
                 e.blend_weights(view, d=d if d_done else None, scale_d=scale_d)
             self.ev_front[b].record(side)
-        self.pending[self.i_front] = (view, d_done, not self.fuse_small, self.token_grid is not None)
+        self.pending[self.i_front] = _Pending(view, d_done, not self.fuse_small, self.token_grid is not None)
         self.i_front += 1
 
     # Encoder workgroups per CU beside the pipeline (see encode_ahead): None = 1 next to the separate blend and small-D
@@ -331,7 +350,7 @@ class ViewPipeline:
             per_cu = self.ENCODER_WORKGROUPS_PER_CU or (2.0 if self.fuse_small else 1.0)
             # stream=: in the view-per-stream schedule eng[0] is BOUND to sides[0]; the encoder must run here, behind
             # `ready`, and `done` must cover it
-            out = encode_features(self.eng[0], feats, encoder, workgroups=max(1, int(per_cu * n_cu)), stream=self.enc_stream)
+            out = self.eng[0].encode_map(feats, encoder, workgroups=max(1, int(per_cu * n_cu)), stream=self.enc_stream)
             done = torch.cuda.Event()
             done.record(self.enc_stream)
         feats.record_stream(self.enc_stream)
@@ -372,34 +391,22 @@ class ViewPipeline:
         self.i_scatter += 1
 
     def _scatter_on(self, main, b, feats, F, d, scale_f, scale_d, t0, t1, upsample, encoder):
-        i = self.i_scatter
         e = self.eng[b]
         if t0 is not None:
             t0.record(main)
-        view, d_done, blended, tok = self.pending.pop(i)
-        fused = not blended and encoder is None and upsample is None and Engine.can_blend_scatter(feats)
-        if tok:
+        p = self.pending.pop(self.i_scatter)
+        view = p.view
+        if p.tokens:
             if (upsample == "nearest" and encoder is None and tuple(feats.shape[:2]) == self.token_grid
                     and Engine.can_scatter_tokens(feats, view.height, view.width)):
                 e.scatter_tokens(view, feats, F, d, scale_f, scale_d)
             else:  # this view's map does not suit the token path after all: blend a weight store here, then the usual scatter
                 e.blend_weights(view)
-                if encoder is not None:
-                    e.scatter_encoded(view, feats, encoder, F, d, scale_f, scale_d)
-                else:
-                    e.scatter(view, feats, F, d, scale_f, scale_d, upsample=upsample)
-        elif fused:
-            e.blend_scatter(view, feats, F, d, scale_f, scale_d)
-        elif not blended and encoder is not None and upsample is None and Engine.can_blend_scatter_encoded(feats, encoder):
-            # the compressed variant in ONE kernel: encoder in the tile prologue, then blend + scatter from registers
-            e.blend_scatter_encoded(view, feats, encoder, F, d, scale_f, scale_d)
+                _scatter_weighted(e, view, feats, F, d, scale_f, scale_d, upsample, encoder)
+        elif not p.blended:
+            _blend_and_scatter(e, view, feats, F, d, scale_f, scale_d, upsample, encoder)
         else:
-            if not blended:  # the map does not suit the fused kernel after all: blend here, then the usual scatter
-                e.blend_weights(view)
-            if encoder is not None:
-                e.scatter_encoded(view, feats, encoder, F, None if d_done else d, scale_f, scale_d)
-            else:
-                e.scatter(view, feats, F, None if d_done else d, scale_f, scale_d, upsample=upsample)
+            _scatter_weighted(e, view, feats, F, None if p.d_done else d, scale_f, scale_d, upsample, encoder)
         if t1 is not None:
             t1.record(main)
         e.accumulate_stats(self.accums[b if self.independent else 0])
@@ -509,6 +516,154 @@ def pipeline_depth(n_gaussians: int, width: int, height: int, dim: Optional[int]
     return 3
 
 
+# the inputs every attempt of create_feature_field works on (gaussians = (means, quats, scales, opacities); camera = the
+# camera_model / rasterize_mode keywords of Engine.view)
+_Job = namedtuple("_Job", "gaussians F d sf sd feature_fn view_ids vm_host K_host width height camera encoder upsample")
+# one attempt's schedule, decided before its first view from the options and the first map (_plan).  first_map: view 0's map,
+# fetched early when its layout decides the schedule.  encode: where the encoder runs -- None (no encoder) | "blend" (the fused
+# blend + scatter kernel's tile prologue) | "staging" (the scatter kernel's slab staging) | "ahead" (a separate kernel on a
+# third stream while the view before is scattered: the feature function runs one view ahead, two full-width maps are alive)
+_Plan = namedtuple("_Plan", "pipelined first_map token_grid encode depth split view_per_stream fuse_small",
+                   defaults=(None, None, None, 0, False, None, True))
+
+
+def _plan(job: _Job, pipeline, token_space, fuse_small, fuse_encoder, encoder_in_blend, encoder_split, split_allowed) -> _Plan:
+    """create_feature_field's schedule for one attempt (the predicates and feature_fn are called in this order)."""
+    if not (pipeline and len(job.view_ids) > 1):
+        return _Plan(False)
+    if _lib.hw_queues_late():
+        # Somebody touched the GPU before this package was imported (a notebook, another library): the request for
+        # hardware queues came too late and the pipeline's streams would share queues.  That costs speed, not results,
+        # so the DRIVER degrades by itself: one stream, same F and d (ADVICE r5).  Constructing a ViewPipeline
+        # explicitly still raises -- whoever asks for the overlapped schedule by name should hear that it cannot run.
+        warnings.warn("gsbp_amd was imported after the HIP runtime had started: GPU_MAX_HW_QUEUES=%d could not be "
+                      "requested, create_feature_field runs its views on ONE stream (pipeline=False; ~20 %% slower at "
+                      "BASELINE size).  Import gsbp_amd, or set the variable, before the first CUDA/HIP call."
+                      % _lib.HW_QUEUES_WANTED, RuntimeWarning, stacklevel=3)
+        return _Plan(False)
+    encoder, upsample, width, height = job.encoder, job.upsample, job.width, job.height
+    first_map = job.feature_fn(job.view_ids[0]) if (encoder is not None or upsample == "nearest") else None
+    # the dino shape -- a nearest-upsampled map whose texels are at least a tile wide and high, D % 4 == 0 -- goes
+    # through token space (Engine.blend_tokens / scatter_tokens); decided on the first map, checked per view
+    token_grid = (tuple(first_map.shape[:2]) if (token_space and upsample == "nearest" and encoder is None
+                                                 and Engine.can_scatter_tokens(first_map, height, width)) else None)
+    enc_blend = (encoder is not None and fuse_small and not fuse_encoder and upsample is None
+                 and encoder_in_blend is not False and Engine.can_blend_scatter_encoded(first_map, encoder))
+    n, d_out = job.F.shape
+    depth = pipeline_depth(n, width, height, d_out, encoder_in_blend=enc_blend) if pipeline is True else max(2, int(pipeline))
+    split = bool(enc_blend and split_allowed and (encoder_split if encoder_split is not None
+                                                  else (-(-width // 16)) * (-(-height // 16)) >= SPLIT_ENCODER_MIN_TILES))
+    encode = (None if encoder is None else "blend" if enc_blend else "staging"
+              if fuse_encoder and upsample is None and Engine.can_fuse_encoder(first_map, encoder) else "ahead")
+    return _Plan(True, first_map, token_grid, encode, depth, split, True if (enc_blend and depth > 2) else None,
+                 fuse_small and not (fuse_encoder and encoder is not None))
+
+
+def _run_pipelined(job: _Job, plan: _Plan, eng: Engine, allow_wide: bool, stream_safe: bool) -> Dict[str, int]:
+    """The views through a ViewPipeline of plan.depth workspaces (eng's and new ones); returns the counters.  An overflow seen
+    after view 2 or by a later probe (every OVERFLOW_CHECK_EVERY views) ends the pass early: the counters then show it."""
+    (means, quats, scales, opacities), F, d, sf, sd, feature_fn, ids, _, _, width, height, _, encoder, upsample = job
+    n, first_map = means.shape[0], plan.first_map
+    pipe = ViewPipeline(n, width, height, means.device, scatter_dim=F.shape[1], token_grid=plan.token_grid,
+                        split_encoder=plan.split, allow_wide=allow_wide, fuse_small=plan.fuse_small,
+                        view_per_stream=plan.view_per_stream,
+                        engines=[eng] + [Engine(n, width, height, device=means.device, tight_binning=eng.tight_binning,
+                                                isect_cap=eng.isect_cap, pair_cap=eng.pair_cap)
+                                         for _ in range(plan.depth - 1)])
+    views = [eng.view(job.vm_host[v], job.K_host, width, height, **job.camera) for v in ids]
+    for j in range(min(pipe.lookahead, len(ids))):
+        pipe.front(views[j], means, quats, scales, opacities, d, sd)
+    enc_blend, staging = plan.encode == "blend", plan.encode == "staging"
+    ahead = pipe.encode_ahead(first_map, encoder) if plan.encode == "ahead" else None
+    probe = None  # (pinned copy of the counters, event): an overflow costs at most OVERFLOW_CHECK_EVERY views
+    for i, v in enumerate(ids):
+        if i == 2:  # one host sync per job: views 0 and 1 are counted, pick the scatter kernel for the rest
+            st01 = pipe.stats()
+            if st01["overflow"]:
+                break
+            pipe.choose_scatter_kernel(st01["n_pairs"], st01["n_headers"])
+        if probe is not None and all(e.query() for e in probe[1]):  # non-blocking: the copy was enqueued views ago
+            if any(Engine.decode_stats(a)["overflow"] for a in probe[0]):
+                break
+            probe = None
+        if i > 2 and i % OVERFLOW_CHECK_EVERY == 0 and probe is None:
+            probe = pipe.stats_async()
+        if i + pipe.lookahead < len(ids):
+            pipe.front(views[i + pipe.lookahead], means, quats, scales, opacities, d, sd)
+        pipe.wait_for_slot()  # (view-per-stream schedule only: the host stays at most `depth` maps ahead)
+        if enc_blend or staging:  # the encoder inside the fused blend + scatter kernel or the scatter kernel's staging
+            feats, fenc = (first_map if i == 0 else feature_fn(v)), encoder
+            if staging and not Engine.can_fuse_encoder(feats, encoder):
+                feats, fenc = eng.encode_map(feats, encoder), None
+            pipe.scatter(feats, F, d, sf, sd, encoder=fenc)
+            continue
+        if encoder is not None:
+            feats, after = ahead
+            if i + 1 < len(ids):
+                ahead = pipe.encode_ahead(feature_fn(ids[i + 1]), encoder)
+        elif stream_safe:
+            # (view-per-stream schedule: the feature function runs on the stream that consumes its map)
+            with torch.cuda.stream(pipe.scatter_stream()):
+                feats, after = feature_fn(v), None
+        elif upsample == "nearest" and i == 0:
+            feats, after = first_map, None
+        else:
+            feats, after = feature_fn(v), None  # on the caller's stream; scatter() waits for it with an event
+        pipe.scatter(feats, F, d, sf, sd, upsample=upsample, after=after, ready=encoder is None and stream_safe)
+    stats = pipe.stats()
+    pipe.release()
+    return stats
+
+
+def _run_serial(job: _Job, eng: Engine, fuse_small: bool, token_space: bool) -> Dict[str, int]:
+    """The views one after the other on the caller's stream; returns the counters (synchronises)."""
+    accum = torch.zeros(32, dtype=torch.uint8, device=job.F.device)
+    for v in job.view_ids:
+        feats = job.feature_fn(v)
+        if job.encoder is not None:
+            # backproject_compressed.py:127 through the hand-written kernel, whose domain includes the reference's 512 -> 16
+            # encoder; anything else RAISES (Engine.encode_map): the drivers never switch to a library GEMM behind the
+            # caller's back (whoever wants one encodes in the feature function and passes encoder=None)
+            feats = eng.encode_map(feats, job.encoder)
+        view = eng.view(job.vm_host[v], job.K_host, job.width, job.height, **job.camera)
+        if (job.upsample is None and not (fuse_small and Engine.can_blend_scatter(feats))
+                and _lib.is_default_camera(view)):
+            eng.backproject_view(view, *job.gaussians, feats, job.F, job.d, job.sf, job.sd)  # project, sort, blend, scatter: one C call
+        else:
+            eng.project(view, *job.gaussians)
+            eng.bin_sort(view)
+            _blend_and_scatter(eng, view, feats, job.F, job.d, job.sf, job.sd, job.upsample, fuse=fuse_small,
+                               tokens=token_space)
+        eng.accumulate_stats(accum)
+    return Engine.decode_stats(accum)
+
+
+def _overflow_action(overflow: int, split_allowed: bool, attempt: int) -> Optional[str]:
+    """After an attempt with these overflow flags: None (done), "grow" (the workspace) or "no_split" (rebuild without the
+    producer / consumer kernel); raises where a rerun cannot help."""
+    if overflow & 16:
+        # a wave of the producer / consumer kernel gave up waiting on its LDS ring (its waits are bounded so that a
+        # scheduling accident cannot hang the device): the accumulators are incomplete.  Never seen in 2000-view soaks
+        # and the fuzz; if it happens, say so and build the field again with the one-wave-per-tile form of the kernel.
+        if not split_allowed:
+            raise RuntimeError("gwbp_stats.overflow bit 4 (ring stall) without the producer / consumer kernel: internal error")
+        warnings.warn("a wave of gwbp_blend_scatter_encoded's producer / consumer kernel gave up waiting on its LDS ring "
+                      "(gwbp_stats.overflow bit 4); building the field again with encoder_split=False -- please report it",
+                      RuntimeWarning, stacklevel=3)
+        return "no_split"
+    if overflow & 8:
+        raise RuntimeError("gwbp_blend_tokens met a tile that spans more than 2 x 2 texels (gwbp_stats.overflow bit 3): "
+                           "the map is finer than Engine.token_geometry_ok() admitted")
+    if overflow & 4:
+        raise RuntimeError("a view was scattered with a kernel that did not match its blend (gwbp_stats.overflow "
+                           "bit 2): F and d are incomplete")
+    if not overflow:
+        return None
+    if attempt == 5:
+        raise RuntimeError(f"workspace overflow (flags {overflow}) after five enlargements")
+    return "grow"
+
+
 def create_feature_field(means, quats, scales, opacities, viewmats, K, width: int, height: int,
                          feature_fn: Callable[[int], torch.Tensor], dim: int, reduction: str = "sum",
                          encoder: Optional[torch.Tensor] = None, engine: Optional[Engine] = None,
@@ -571,175 +726,40 @@ def create_feature_field(means, quats, scales, opacities, viewmats, K, width: in
     dist, rank, world = _dist()
     n = means.shape[0]
     d_out = dim if encoder is None else encoder.shape[1]
-    dev = means.device
-    F, d, F_store = alloc_accumulators(n, d_out, dev, world)
-    my_views = list(views) if views is not None else view_shard(viewmats.shape[0], rank, world)
-    vm_host, K_host = viewmats.detach().cpu(), K.detach().cpu()  # one D2H copy, not one per view
-    if reduction == "sum":
-        sf, sd = 1.0, 1.0
-    elif reduction == "mean":
-        sf, sd = 1.0 / (height * width * d_out), 1.0 / (height * width * 3)
-    else:
+    F, d, F_store = alloc_accumulators(n, d_out, means.device, world)
+    if reduction not in ("sum", "mean"):
         raise ValueError(reduction)
+    sf, sd = (1.0, 1.0) if reduction == "sum" else (1.0 / (height * width * d_out), 1.0 / (height * width * 3))
+    # one D2H copy of the cameras, not one per view
+    job = _Job((means, quats, scales, opacities), F, d, sf, sd, feature_fn,
+               list(views) if views is not None else view_shard(viewmats.shape[0], rank, world),
+               viewmats.detach().cpu(), K.detach().cpu(), width, height,
+               dict(camera_model=camera_model, rasterize_mode=rasterize_mode), encoder, upsample)
 
     t0 = time.time()
     stats: Dict[str, int] = {}
     if view_fn is None:
-        eng = engine or Engine(n, width, height, device=dev, tight_binning=True)  # same F and d, shorter tile lists
-        if pipeline and len(my_views) > 1:
-            from . import _lib
-            if _lib.hw_queues_late():
-                # Somebody touched the GPU before this package was imported (a notebook, another library): the request for
-                # hardware queues came too late and the pipeline's streams would share queues.  That costs speed, not results,
-                # so the DRIVER degrades by itself: one stream, same F and d.  Constructing a ViewPipeline
-                # explicitly still raises -- whoever asks for the overlapped schedule by name should hear that it cannot run.
-                import warnings
-                warnings.warn("gsbp_amd was imported after the HIP runtime had started: GPU_MAX_HW_QUEUES=%d could not be "
-                              "requested, create_feature_field runs its views on ONE stream (pipeline=False; ~20 %% slower at "
-                              "BASELINE size).  Import gsbp_amd, or set the variable, before the first CUDA/HIP call."
-                              % _lib.HW_QUEUES_WANTED, RuntimeWarning, stacklevel=2)
-                pipeline = False
+        eng = engine or Engine(n, width, height, device=means.device, tight_binning=True)  # same F and d, shorter tile lists
         split_allowed = True
         for attempt in range(6):  # a capacity overflow invalidates the accumulators: grow the workspace, start over
-            if pipeline and len(my_views) > 1:
-                first_map = feature_fn(my_views[0]) if (encoder is not None or upsample == "nearest") else None
-                # the dino shape -- a nearest-upsampled map whose texels are at least a tile wide and high, D % 4 == 0 -- goes
-                # through token space (Engine.blend_tokens / scatter_tokens); decided on the first map, checked per view
-                token_grid = (tuple(first_map.shape[:2]) if (token_space and upsample == "nearest" and encoder is None
-                                                             and Engine.can_scatter_tokens(first_map, height, width)) else None)
-                enc_blend = (encoder is not None and fuse_small and not fuse_encoder and upsample is None
-                             and encoder_in_blend is not False and Engine.can_blend_scatter_encoded(first_map, encoder))
-                depth = (pipeline_depth(n, width, height, d_out, encoder_in_blend=enc_blend) if pipeline is True
-                         else max(2, int(pipeline)))
-                split = bool(enc_blend and split_allowed and (encoder_split if encoder_split is not None
-                                            else (-(-width // 16)) * (-(-height // 16)) >= SPLIT_ENCODER_MIN_TILES))
-                pipe = ViewPipeline(n, width, height, dev, scatter_dim=d_out, token_grid=token_grid, split_encoder=split,
-                                    allow_wide=allow_wide, fuse_small=fuse_small and not (fuse_encoder and encoder is not None),
-                                    view_per_stream=True if (enc_blend and depth > 2) else None,
-                                    engines=[eng] + [Engine(n, width, height, device=dev, tight_binning=eng.tight_binning,
-                                                            isect_cap=eng.isect_cap, pair_cap=eng.pair_cap)
-                                                     for _ in range(depth - 1)])
-                views = [eng.view(vm_host[v], K_host, width, height, camera_model=camera_model,
-                                  rasterize_mode=rasterize_mode) for v in my_views]
-                for j in range(min(pipe.lookahead, len(my_views))):
-                    pipe.front(views[j], means, quats, scales, opacities, d, sd)
-                # with an encoder the feature function runs one view ahead, so that view v+1's map is encoded on a third
-                # stream while view v is scattered (two full-width maps are alive at a time)
-                fused = None  # decided on the first map: its layout must suit gwbp_scatter_encoded
-                ahead = None
-                if encoder is not None and not enc_blend:
-                    fused = fuse_encoder and upsample is None and Engine.can_fuse_encoder(first_map, encoder)
-                    ahead = (first_map, None) if fused else pipe.encode_ahead(first_map, encoder)
-                probe = None  # (pinned copy of the counters, event): an overflow costs at most OVERFLOW_CHECK_EVERY views
-                overflowed = False
-                for i, v in enumerate(my_views):
-                    if i == 2:  # one host sync per job: views 0 and 1 are counted, pick the scatter kernel for the rest
-                        st01 = pipe.stats()
-                        if st01["overflow"]:
-                            overflowed = True
-                            break
-                        pipe.choose_scatter_kernel(st01["n_pairs"], st01["n_headers"])
-                    if probe is not None and all(e.query() for e in probe[1]):  # non-blocking: the copy was enqueued views ago
-                        if any(Engine.decode_stats(a)["overflow"] for a in probe[0]):
-                            overflowed = True
-                            break
-                        probe = None
-                    if i > 2 and i % OVERFLOW_CHECK_EVERY == 0 and probe is None:
-                        probe = pipe.stats_async()
-                    if i + pipe.lookahead < len(my_views):
-                        pipe.front(views[i + pipe.lookahead], means, quats, scales, opacities, d, sd)
-                    pipe.wait_for_slot()  # (view-per-stream schedule only: the host stays at most `depth` maps ahead)
-                    if enc_blend:
-                        # encoder + blend + scatter of the view in one kernel, on the view's own stream
-                        feats = first_map if i == 0 else feature_fn(v)
-                        pipe.scatter(feats, F, d, sf, sd, encoder=encoder)
-                        continue
-                    if fused:
-                        # the encoder is applied inside the scatter kernel's slab staging: no [H,W,dim_out] map at all
-                        feats = ahead[0] if i == 0 else feature_fn(v)
-                        if not Engine.can_fuse_encoder(feats, encoder):
-                            feats, fenc = encode_features(eng, feats, encoder), None
-                        else:
-                            fenc = encoder
-                        pipe.scatter(feats, F, d, sf, sd, encoder=fenc)
-                        continue
-                    if encoder is not None:
-                        feats, after = ahead
-                        if i + 1 < len(my_views):
-                            ahead = pipe.encode_ahead(feature_fn(my_views[i + 1]), encoder)
-                    elif feature_fn_stream_safe:
-                        # (view-per-stream schedule: the feature function runs on the stream that consumes its map)
-                        with torch.cuda.stream(pipe.scatter_stream()):
-                            feats, after = feature_fn(v), None
-                    elif upsample == "nearest" and i == 0:
-                        feats, after = first_map, None  # (already produced to read its shape)
-                    else:
-                        feats, after = feature_fn(v), None  # on the caller's stream; scatter() waits for it with an event
-                    pipe.scatter(feats, F, d, sf, sd, upsample=upsample, after=after,
-                                 ready=encoder is None and feature_fn_stream_safe)
-                stats = pipe.stats()
-                pipe.release()
-                assert not overflowed or stats["overflow"]
-            else:
-                accum = torch.zeros(32, dtype=torch.uint8, device=dev)
-                for i, v in enumerate(my_views):
-                    feats = feature_fn(v)
-                    if encoder is not None:
-                        feats = encode_features(eng, feats, encoder)
-                    view = eng.view(vm_host[v], K_host, width, height, camera_model=camera_model,
-                                    rasterize_mode=rasterize_mode)
-                    if upsample is None and fuse_small and Engine.can_blend_scatter(feats):
-                        eng.project(view, means, quats, scales, opacities)
-                        eng.bin_sort(view)
-                        eng.blend_scatter(view, feats, F, d, sf, sd)
-                    elif upsample is None and camera_model == "pinhole" and rasterize_mode == "classic":
-                        eng.backproject_view(view, means, quats, scales, opacities, feats, F, d, sf, sd)
-                    elif token_space and upsample == "nearest" and Engine.can_scatter_tokens(feats, height, width):
-                        eng.project(view, means, quats, scales, opacities)
-                        eng.bin_sort(view)
-                        eng.blend_tokens(view, feats.shape[0], feats.shape[1])
-                        eng.scatter_tokens(view, feats, F, d, sf, sd)
-                    else:
-                        eng.project(view, means, quats, scales, opacities)
-                        eng.bin_sort(view)
-                        eng.blend_weights(view)
-                        eng.scatter(view, feats, F, d, sf, sd, upsample=upsample)
-                    eng.accumulate_stats(accum)
-                stats = Engine.decode_stats(accum)  # synchronises
-            if stats["overflow"] & 16:
-                # a wave of the producer / consumer kernel gave up waiting on its LDS ring (its waits are bounded so that a
-                # scheduling accident cannot hang the device): the accumulators are incomplete.  Never seen in 2000-view soaks
-                # and the fuzz; if it happens, say so and build the field again with the one-wave-per-tile form of the kernel.
-                if not split_allowed:
-                    raise RuntimeError("gwbp_stats.overflow bit 4 (ring stall) without the producer / consumer kernel: internal error")
-                import warnings
-                warnings.warn("a wave of gwbp_blend_scatter_encoded's producer / consumer kernel gave up waiting on its LDS ring "
-                              "(gwbp_stats.overflow bit 4); building the field again with encoder_split=False -- please report it",
-                              RuntimeWarning, stacklevel=2)
-                split_allowed = False
-                F.zero_()
-                d.zero_()
-                continue
-            if stats["overflow"] & 8:
-                raise RuntimeError("gwbp_blend_tokens met a tile that spans more than 2 x 2 texels (gwbp_stats.overflow bit 3): "
-                                   "the map is finer than Engine.token_geometry_ok() admitted")
-            if stats["overflow"] & 4:
-                raise RuntimeError("a view was scattered with a kernel that did not match its blend (gwbp_stats.overflow "
-                                   "bit 2): F and d are incomplete")
-            if not stats["overflow"]:
+            plan = _plan(job, pipeline, token_space, fuse_small, fuse_encoder, encoder_in_blend, encoder_split, split_allowed)
+            pipeline = plan.pipelined and pipeline  # (a late hardware-queue request downgrades the job once)
+            stats = (_run_pipelined(job, plan, eng, allow_wide, feature_fn_stream_safe) if plan.pipelined
+                     else _run_serial(job, eng, fuse_small, token_space))
+            action = _overflow_action(stats["overflow"], split_allowed, attempt)
+            if action is None:
                 break
-            if attempt == 5:
-                raise RuntimeError(f"workspace overflow (flags {stats['overflow']}) after five enlargements")
-            eng.grow(stats, views=len(my_views))
+            if action == "grow":
+                eng.grow(stats, views=len(job.view_ids))
+            else:
+                split_allowed = False
             F.zero_()
             d.zero_()
     else:
         eng = None
-        for v in my_views:
+        for v in job.view_ids:
             feats = feature_fn(v)
-            if encoder is not None:
-                feats = feats @ encoder
-            view_fn(v, feats)
+            view_fn(v, feats if encoder is None else feats @ encoder)
     # The single exchange step: reduce-scatter of F (+ all-reduce of d), row-local finalise of this rank's block
     # (backproject.py:166-169 needs nothing but the row), and an all-gather of the finalised blocks only when the caller
     # wants the whole field on every rank (the reference writes one file, backproject.py:330).

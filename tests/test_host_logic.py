@@ -474,3 +474,47 @@ def test_token_geometry_rule_follows_the_exact_index_maps():
         assert all(b >= a for a, b in zip(m, m[1:])) and m[-1] <= n_in - 1  # non-decreasing, inside the map
         brute = all(m[min(t + 15, n_out - 1)] - m[t] <= 1 for t in range(0, n_out, 16))
         assert Engine.token_geometry_ok(n_in, 1, n_out, 16) == brute, (n_in, n_out)
+
+
+def test_feature_field_plan_depth_split_threshold_and_late_queue_downgrade(monkeypatch):
+    """create_feature_field's per-attempt schedule (backproject._plan) without a GPU: the Engine predicates and the queue check
+    are stubbed.  Depth 4 on small scenes and with the encoder in the fused kernel, 2 for maps narrow enough for the fused
+    kernel on large images, 3 otherwise, an explicit pipeline=int as given (at least 2); the producer / consumer form of the
+    encoder-fused kernel from SPLIT_ENCODER_MIN_TILES tiles on; a late hardware-queue request degrades to one stream with a
+    warning and without fetching a map."""
+    from gsbp_amd import _lib, backproject as bp
+    monkeypatch.setattr(_lib, "hw_queues_late", lambda: False)
+    for name in ("can_scatter_tokens", "can_blend_scatter_encoded", "can_fuse_encoder"):
+        monkeypatch.setattr(gsbp_amd.Engine, name, staticmethod(lambda *a: True))
+    fetched = []
+
+    def plan(n, w, h, d_out, encoder=None, upsample=None, pipeline=True, encoder_split=None, split_allowed=True, views=3):
+        def feature_fn(v):
+            fetched.append(v)
+            return torch.zeros(h, w, 64)
+        job = bp._Job((torch.zeros(n, 3),) * 4, torch.zeros(n, d_out), torch.zeros(n), 1.0, 1.0, feature_fn,
+                      list(range(7, 7 + views)), None, None, w, h, {}, encoder, upsample)
+        return bp._plan(job, pipeline, True, True, False, None, encoder_split, split_allowed)
+
+    enc = torch.zeros(64, 16)
+    assert plan(10_000, 400, 300, 32).depth == 4                       # small scene (C1)
+    assert plan(1_000_000, 1600, 1060, 16, encoder=enc).depth == 4     # encoder in the fused kernel (C5)
+    assert plan(1_000_000, 1600, 1060, 16).depth == 2                  # fused blend + scatter, two workspaces
+    assert plan(1_000_000, 1600, 1060, 512).depth == 3                 # C2
+    assert plan(1_000_000, 1600, 1060, 512, pipeline=5).depth == 5
+    assert plan(10_000, 400, 300, 32, pipeline=1).depth == 2
+    assert fetched == [7]  # only the encoder job looks at its first map
+    p = plan(1_000_000, 1600, 1060, 16, encoder=enc)
+    assert (p.encode, p.view_per_stream, p.first_map.shape) == ("blend", True, (1060, 1600, 64))
+    assert p.split and not plan(1_000_000, 1600, 1060, 16, encoder=enc, split_allowed=False).split
+    assert bp.SPLIT_ENCODER_MIN_TILES == 64 * 64
+    assert plan(1000, 64 * 16, 64 * 16, 16, encoder=enc).split                    # 4096 tiles
+    assert not plan(1000, 64 * 16, 64 * 16 - 16, 16, encoder=enc).split           # 64 x 63 tiles
+    assert plan(1000, 64 * 16, 64 * 16 - 16, 16, encoder=enc, encoder_split=True).split
+    assert not plan(1000, 64 * 16, 64 * 16, 16, encoder=enc, encoder_split=False).split
+    assert not plan(1000, 64, 48, 16, views=1).pipelined and not plan(1000, 64, 48, 16, pipeline=False).pipelined
+    monkeypatch.setattr(_lib, "hw_queues_late", lambda: True)
+    fetched.clear()
+    with pytest.warns(RuntimeWarning, match="ONE stream"):
+        p = plan(1_000_000, 1600, 1060, 16, encoder=enc)
+    assert not p.pipelined and p.first_map is None and fetched == []
