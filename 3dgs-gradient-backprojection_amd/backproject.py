@@ -677,8 +677,10 @@ def create_feature_field(means, quats, scales, opacities, viewmats, K, width: in
     """Build the [N, dim_out] per-Gaussian feature field.
 
     means/quats/scales/opacities: post-activation Gaussians (backproject.py:55-57), device tensors.
-    viewmats [V,4,4], K [3,3]; feature_fn(v) -> feats[H,W,dim] float32 on the same device (stands in for the
-    LSeg/DINO forward of backproject.py:102-113 / :236-249).
+    viewmats [V,4,4], K [3,3]; feature_fn(v) -> feats[H,W,dim] float32, float16 or bfloat16 on the same device (stands in for
+    the LSeg/DINO forward of backproject.py:102-113 / :236-249).  A half map gets the schedule an fp32 map of its shape gets;
+    the 128- and 256-channel scatter kernels and token space read it as it is (Engine.scatter, Engine.scatter_tokens), the
+    other kernels (D <= 64, the encoder) from a .float() copy made at the call.  F and d equal those of feats.float().
     reduction: "sum" (lseg, backproject.py:127,145) or "mean" (dino, backproject.py:263,283).
     encoder [dim, dim_out]: backproject_compressed.py:127 (feats @ encoder before back-projection).
     upsample="nearest" | "bilinear": feature_fn returns the network's LOW-RESOLUTION map [h,w,dim] (dino patch tokens,

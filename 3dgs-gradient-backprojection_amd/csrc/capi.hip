@@ -405,7 +405,8 @@ int gwbp_accumulate_d(const gwbp_caps *caps, void *workspace, size_t workspace_b
 }
 
 static int scatter_impl(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
-                        const FeatMap &M, int32_t D, float scale_f, float scale_d, float *F, float *d, void *stream)
+                        const FeatMap &M, int32_t D, float scale_f, float scale_d, float *F, float *d, void *stream,
+                        int mt = GWBP_MAP_F32)
 {
     Layout L;
     Ws W;
@@ -419,8 +420,10 @@ static int scatter_impl(const gwbp_caps *caps, void *workspace, size_t workspace
         return rc;
     if (!F && L.n > 0)
         return set_error(GWBP_EINVAL, "null F");
-    return launch_scatter(L, W, V, M, D, scale_f, scale_d, F, d, static_cast<hipStream_t>(stream));
+    return launch_scatter(L, W, V, M, D, scale_f, scale_d, F, d, static_cast<hipStream_t>(stream), mt);
 }
+
+static bool known_map_type(int32_t mt) { return mt == GWBP_MAP_F32 || mt == GWBP_MAP_F16 || mt == GWBP_MAP_BF16; }
 
 int gwbp_scatter(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
                  const float *feats, int64_t fs_y, int64_t fs_x, int64_t fs_c, int32_t D, float scale_f,
@@ -461,6 +464,74 @@ int gwbp_scatter_bilinear(const gwbp_caps *caps, void *workspace, size_t workspa
         return set_error(GWBP_EINVAL, "gwbp_scatter_bilinear needs both index maps, both weight maps and the map size");
     const FeatMap M{feats, fs_y, fs_x, fs_c, y0, x0, ly, lx, lr_h, lr_w};
     return scatter_impl(caps, workspace, workspace_bytes, view_host, M, D, scale_f, scale_d, F, d, stream);
+}
+
+// The typed entry points: the map type is validated before anything else; GWBP_MAP_F32 is the untyped function's call.
+// (The feature pointer travels in FeatMap::p as it is; only the kernels of the map type dereference it.)
+int gwbp_scatter_typed(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                       const void *feats, int32_t map_type, int64_t fs_y, int64_t fs_x, int64_t fs_c, int32_t D, float scale_f,
+                       float scale_d, float *F, float *d, void *stream)
+{
+    if (!known_map_type(map_type))
+        return set_error(GWBP_EINVAL, "unknown map type %d", (int)map_type);
+    if (map_type == GWBP_MAP_F32)
+        return gwbp_scatter(caps, workspace, workspace_bytes, view_host, static_cast<const float *>(feats), fs_y, fs_x, fs_c, D,
+                            scale_f, scale_d, F, d, stream);
+    const FeatMap M{static_cast<const float *>(feats), fs_y, fs_x, fs_c, nullptr, nullptr, nullptr, nullptr, 0, 0};
+    return scatter_impl(caps, workspace, workspace_bytes, view_host, M, D, scale_f, scale_d, F, d, stream, map_type);
+}
+
+int gwbp_scatter_upsampled_typed(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                                 const void *feats, int32_t map_type, int64_t fs_y, int64_t fs_x, int64_t fs_c, int32_t D,
+                                 const int32_t *ymap, const int32_t *xmap, float scale_f, float scale_d, float *F, float *d,
+                                 void *stream)
+{
+    if (!known_map_type(map_type))
+        return set_error(GWBP_EINVAL, "unknown map type %d", (int)map_type);
+    if (map_type == GWBP_MAP_F32)
+        return gwbp_scatter_upsampled(caps, workspace, workspace_bytes, view_host, static_cast<const float *>(feats), fs_y, fs_x,
+                                      fs_c, D, ymap, xmap, scale_f, scale_d, F, d, stream);
+    if (!ymap || !xmap)
+        return set_error(GWBP_EINVAL, "gwbp_scatter_upsampled_typed needs both index maps");
+    const FeatMap M{static_cast<const float *>(feats), fs_y, fs_x, fs_c, ymap, xmap, nullptr, nullptr, 0, 0};
+    return scatter_impl(caps, workspace, workspace_bytes, view_host, M, D, scale_f, scale_d, F, d, stream, map_type);
+}
+
+int gwbp_scatter_bilinear_typed(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                                const void *feats, int32_t map_type, int64_t fs_y, int64_t fs_x, int64_t fs_c, int32_t D,
+                                int32_t lr_h, int32_t lr_w, const int32_t *y0, const float *ly, const int32_t *x0,
+                                const float *lx, float scale_f, float scale_d, float *F, float *d, void *stream)
+{
+    if (!known_map_type(map_type))
+        return set_error(GWBP_EINVAL, "unknown map type %d", (int)map_type);
+    if (map_type == GWBP_MAP_F32)
+        return gwbp_scatter_bilinear(caps, workspace, workspace_bytes, view_host, static_cast<const float *>(feats), fs_y, fs_x,
+                                     fs_c, D, lr_h, lr_w, y0, ly, x0, lx, scale_f, scale_d, F, d, stream);
+    if (!y0 || !x0 || !ly || !lx || lr_h < 1 || lr_w < 1)
+        return set_error(GWBP_EINVAL, "gwbp_scatter_bilinear_typed needs both index maps, both weight maps and the map size");
+    const FeatMap M{static_cast<const float *>(feats), fs_y, fs_x, fs_c, y0, x0, ly, lx, lr_h, lr_w};
+    return scatter_impl(caps, workspace, workspace_bytes, view_host, M, D, scale_f, scale_d, F, d, stream, map_type);
+}
+
+int gwbp_scatter_tokens_typed(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                              const void *tokens, int32_t map_type, int64_t ts_y, int64_t ts_x, int32_t D, const int32_t *ymap,
+                              const int32_t *xmap, float scale_f, float scale_d, float *F, float *d, void *stream)
+{
+    if (!known_map_type(map_type))
+        return set_error(GWBP_EINVAL, "unknown map type %d", (int)map_type);
+    if (map_type == GWBP_MAP_F32)
+        return gwbp_scatter_tokens(caps, workspace, workspace_bytes, view_host, static_cast<const float *>(tokens), ts_y, ts_x, D,
+                                   ymap, xmap, scale_f, scale_d, F, d, stream);
+    Layout L;
+    Ws W;
+    ViewDev V;
+    int rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W);
+    if (rc)
+        return rc;
+    if ((rc = make_view(view_host, caps, &V)))
+        return rc;
+    return launch_token_apply_half(L, W, V, tokens, ts_y, ts_x, D, ymap, xmap, scale_f, scale_d, F, d,
+                                   static_cast<hipStream_t>(stream), map_type);
 }
 
 int gwbp_render(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,

@@ -202,13 +202,22 @@ struct FeatMap {
         return h0 * (w0 * a + w1 * b) + h1 * (w0 * c + w1 * d); // UpSampleBilinear2d: same association
     }
 };
+// mt (GWBP_MAP_*): the element type of M.p (strides in elements); half maps take the 256- and 128-channel kernels only
 int launch_scatter(const Layout &L, const Ws &W, const ViewDev &V, const FeatMap &M, int D, float scale_f,
-                   float scale_d, float *F, float *d, hipStream_t s);
+                   float scale_d, float *F, float *d, hipStream_t s, int mt = GWBP_MAP_F32);
 int launch_scatter_full(const Layout &L, const Ws &W, const ViewDev &V, const FeatMap &M, int D, float scale_f,
                         float scale_d, float *F, float *d, hipStream_t s);
 int launch_accum_d(const Layout &L, const Ws &W, const ViewDev &V, float scale_d, float *d, hipStream_t s);
 int launch_scatter_wide(const Layout &L, const Ws &W, const ViewDev &V, const FeatMap &M, int D, float scale_f,
                         float *F, hipStream_t s);
+// the half-map instantiations (scatter_wide_half.hip, scatter_full_half.hip, token_half.hip): mt = GWBP_MAP_F16 / GWBP_MAP_BF16
+int launch_scatter_wide_half(const Layout &L, const Ws &W, const ViewDev &V, const FeatMap &M, int D, float scale_f,
+                             float *F, hipStream_t s, int mt);
+int launch_scatter_full_half(const Layout &L, const Ws &W, const ViewDev &V, const FeatMap &M, int D, float scale_f,
+                             float scale_d, float *F, float *d, hipStream_t s, int mt);
+int launch_token_apply_half(const Layout &L, const Ws &W, const ViewDev &V, const void *tokens, int64_t ts_y, int64_t ts_x,
+                            int D, const int32_t *ymap, const int32_t *xmap, float scale_f, float scale_d, float *F, float *d,
+                            hipStream_t s, int mt);
 int launch_render(const Layout &L, const Ws &W, const ViewDev &V, const float *colors, int D, float *out,
                   hipStream_t s);
 int launch_render_px(const Ws &W, const ViewDev &V, const float *colors, int D, float *out, float *alphas,
@@ -292,6 +301,49 @@ __device__ __forceinline__ float wave_sum(float v)
     const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
     return (r0 + r1) + (r2 + r3);
 }
+// ---- feature-map element types (GWBP_MAP_*) ------------------------------------------------------------------------------
+// A half map is widened to fp32 exactly where the staging writes it into LDS (or, for a value used at once, where it is
+// loaded): slabs, sums and F / d stay fp32.  `raw` is what a load lands; `land` keeps a loaded scalar's bits in a 32-bit
+// register (the 256-channel kernel's landing area is float-typed) and `widen` turns those bits into the value; `cvt4` widens
+// the four channels of one `raw4` (float4, or the four 16-bit halves of a uint2).  For GWBP_MAP_F32 all of it is the identity.
+template <int MT>
+struct MapElem;
+template <>
+struct MapElem<GWBP_MAP_F32> {
+    typedef float raw;
+    typedef float4 raw4;
+    static __device__ __forceinline__ float cvt(float x) { return x; }
+    static __device__ __forceinline__ float land(float x) { return x; }
+    static __device__ __forceinline__ float widen(float x) { return x; }
+    static __device__ __forceinline__ float4 cvt4(float4 x) { return x; }
+};
+template <>
+struct MapElem<GWBP_MAP_F16> {
+    typedef unsigned short raw;
+    typedef uint2 raw4;
+    static __device__ __forceinline__ float cvt(unsigned short x) { return (float)__builtin_bit_cast(_Float16, x); }
+    static __device__ __forceinline__ float land(unsigned short x) { return __uint_as_float((u32)x); }
+    static __device__ __forceinline__ float widen(float b) { return cvt((unsigned short)__float_as_uint(b)); }
+    static __device__ __forceinline__ float4 cvt4(uint2 x)
+    {
+        return make_float4(cvt((unsigned short)x.x), cvt((unsigned short)(x.x >> 16)), cvt((unsigned short)x.y),
+                           cvt((unsigned short)(x.y >> 16)));
+    }
+};
+template <>
+struct MapElem<GWBP_MAP_BF16> {
+    typedef unsigned short raw;
+    typedef uint2 raw4;
+    static __device__ __forceinline__ float cvt(unsigned short x) { return __uint_as_float((u32)x << 16); }
+    static __device__ __forceinline__ float land(unsigned short x) { return __uint_as_float((u32)x); }
+    static __device__ __forceinline__ float widen(float b) { return __uint_as_float(__float_as_uint(b) << 16); }
+    static __device__ __forceinline__ float4 cvt4(uint2 x)
+    {
+        return make_float4(__uint_as_float(x.x << 16), __uint_as_float(x.x & 0xFFFF0000u), __uint_as_float(x.y << 16),
+                           __uint_as_float(x.y & 0xFFFF0000u));
+    }
+};
+
 __device__ __forceinline__ u32 uniform(u32 v) { return (u32)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ __forceinline__ u64 uniform64(u64 v)
 {

@@ -276,8 +276,20 @@ int launch_accum_d(const Layout &L, const Ws &W, const ViewDev &V, float scale_d
 }
 
 int launch_scatter(const Layout &L, const Ws &W, const ViewDev &V, const FeatMap &M, int D, float scale_f,
-                   float scale_d, float *F, float *d, hipStream_t s)
+                   float scale_d, float *F, float *d, hipStream_t s, int mt)
 {
+    if (mt != GWBP_MAP_F32) {
+        // half maps: the 256- and the 128-channel kernel, which widen them while they stage the slab
+        if (D % 256 == 0 && M.fs_c == 1 && !(L.flags & GWBP_FLAG_NARROW_SCATTER)) {
+            if (d) {
+                const int rc = launch_accum_d(L, W, V, scale_d, d, s);
+                if (rc)
+                    return rc;
+            }
+            return launch_scatter_wide_half(L, W, V, M, D, scale_f, F, s, mt);
+        }
+        return launch_scatter_full_half(L, W, V, M, D, scale_f, scale_d, F, d, s, mt);
+    }
     const int n_tiles = V.tile_w * V.tile_h;
     const int n_tiles_pad = (n_tiles + 7) & ~7;
     const int n_chunks = (D + kChunk - 1) / kChunk;

@@ -14,6 +14,9 @@ from . import _lib
 from ._lib import Caps, GwbpError, Stats, check, make_view, ptr
 
 TILE = 16
+# feature-map element types the scatter entry points take (GWBP_MAP_*); everything else the Engine computes in is float32
+MAP_TYPES = {torch.float32: _lib.MAP_F32, torch.float16: _lib.MAP_F16, torch.bfloat16: _lib.MAP_BF16}
+HALF_TYPES = (torch.float16, torch.bfloat16)
 
 
 def nearest_index(n_in: int, n_out: int) -> torch.Tensor:
@@ -152,6 +155,31 @@ class Engine:
     def _args(self):
         return C.byref(self.caps), self._ws_ptr, C.c_size_t(self.ws_bytes)
 
+    def _widen(self, feats: torch.Tensor) -> torch.Tensor:
+        """A half map for a kernel that reads float32 only: feats.float() (exact), made on the stream the kernel runs on.
+        What it costs is that of the copy: one read of the map, one write and one read of twice its size."""
+        if feats.dtype not in HALF_TYPES:
+            return feats
+        if self.stream is None:
+            return feats.float()
+        with torch.cuda.stream(self.stream):
+            return feats.float()
+
+    def half_native(self, feats: torch.Tensor) -> bool:
+        """Does scatter() read this fp16 / bf16 map as it is (gwbp_scatter_typed and its upsampled / bilinear forms)?  The
+        256-channel kernel takes D % 256 == 0 with unit channel stride; the 128-channel kernel (D % 128 == 0, and D % 256 == 0
+        with set_narrow_scatter(True)) also needs pixel strides that are multiples of 8 elements and a 16-B aligned map.
+        Other half maps are widened with .float() at the call."""
+        if feats.dim() != 3 or feats.dtype not in HALF_TYPES:
+            return False
+        sy, sx, sc = feats.stride()
+        D = feats.shape[2]
+        if sc != 1 or D % 128 != 0 or min(sy, sx) < 0:
+            return False
+        if D % 256 == 0 and not (self.caps.flags & _lib.FLAG_NARROW_SCATTER):
+            return True
+        return sy % 8 == 0 and sx % 8 == 0 and feats.data_ptr() % 16 == 0
+
     def view(self, viewmat, K, width, height, **kw):
         """make_view: near_plane, far_plane, eps2d, radius_clip, camera_model ("pinhole" | "ortho" | "fisheye") and
         rasterize_mode ("classic" | "antialiased") as keywords."""
@@ -230,8 +258,8 @@ class Engine:
     @classmethod
     def can_blend_scatter(cls, feats: torch.Tensor) -> bool:
         """Maps gwbp_blend_scatter takes: [H,W,D] float32 at full resolution, D <= 16 (<= 32 on small images), unit channel
-        stride, non-negative strides."""
-        return (feats.dim() == 3 and feats.is_cuda and feats.dtype == torch.float32
+        stride, non-negative strides.  (fp16 / bf16 maps of that shape too: blend_scatter widens them with .float().)"""
+        return (feats.dim() == 3 and feats.is_cuda and feats.dtype in MAP_TYPES
                 and 1 <= feats.shape[2] <= cls.fused_max_dim(feats.shape[1], feats.shape[0])
                 and feats.stride(2) == 1 and min(feats.stride()) >= 0)
 
@@ -239,11 +267,13 @@ class Engine:
         """blend_weights + scatter of one view in ONE kernel for narrow maps (D <= 16: the compressed variant after its
         encoder, backproject_compressed.py:127-165): the tile's pixels sit in registers while it is blended, each
         contributing record is reduced across the wave and added to F / d at once.  No weight store is written: the
-        view cannot be scattered or rendered again without a new blend_weights()."""
+        view cannot be scattered or rendered again without a new blend_weights().  A half map is widened with .float()
+        first (the kernel reads float32)."""
         if not self.can_blend_scatter(feats):
             raise GwbpError(f"blend_scatter: [H,W,D] float32 map with unit channel stride and D <= {self.FUSED_MAX_DIM} "
                             f"(<= {self.FUSED_MAX_DIM_SMALL} on images of at most {self.FUSED_SMALL_TILES} tiles) required, "
                             f"got {tuple(feats.shape)} strides {tuple(feats.stride())}")
+        feats = self._widen(feats)
         sy, sx, _, D = self._feat_strides(feats, view)
         self._check_acc(F, d, D)
         alphas = torch.empty(view.height, view.width, device=self.device) if want_alphas else None
@@ -255,14 +285,15 @@ class Engine:
     @staticmethod
     def can_blend_scatter_encoded(feats: torch.Tensor, encoder: torch.Tensor) -> bool:
         """Shapes gwbp_blend_scatter_encoded takes: [H,W,K] float32 with channel-contiguous 16-B aligned pixels, K % 16 == 0,
-        16 <= K <= 512, at most 16 outputs (the reference's encoder is 512 -> 16, backproject_compressed.py:26,127)."""
+        16 <= K <= 512, at most 16 outputs (the reference's encoder is 512 -> 16, backproject_compressed.py:26,127).  fp16 / bf16
+        maps of that shape and layout too: blend_scatter_encoded widens them with .float()."""
         if feats.dim() != 3 or encoder.dim() != 2 or feats.shape[2] != encoder.shape[0]:
             return False
         sy, sx, sc = feats.stride()
         K, n = encoder.shape
         # (a row must span less than 4 GB: the kernel's per-lane column offsets are 32-bit -- a channel slice of a much wider
         # tensor falls back to encode_map, like any other layout the kernel does not take)
-        return (feats.is_cuda and feats.dtype == torch.float32 and encoder.dtype == torch.float32 and 1 <= n <= 16
+        return (feats.is_cuda and feats.dtype in MAP_TYPES and encoder.dtype == torch.float32 and 1 <= n <= 16
                 and K % 16 == 0 and 16 <= K <= 512 and sc == 1 and sy % 4 == 0 and sx % 4 == 0 and sy >= 0 and sx >= K
                 and feats.data_ptr() % 16 == 0 and ((feats.shape[1] - 1) * sx + K) * 4 < (1 << 32))
 
@@ -277,6 +308,7 @@ class Engine:
                             f"@ {tuple(encoder.shape)}")
         if feats.shape[0] != view.height or feats.shape[1] != view.width:
             raise GwbpError(f"feature map must be [{view.height},{view.width},K], got {tuple(feats.shape)}")
+        feats = self._widen(feats)
         sy, sx, _ = feats.stride()
         K, n = encoder.shape
         self._check_acc(F, d, n)
@@ -291,8 +323,8 @@ class Engine:
     def _feat_strides(feats: torch.Tensor, view, lowres: bool = False) -> Tuple[int, int, int, int]:
         if feats.dim() != 3 or (not lowres and (feats.shape[0] != view.height or feats.shape[1] != view.width)):
             raise GwbpError(f"feature map must be [H,W,D] = [{view.height},{view.width},D], got {tuple(feats.shape)}")
-        if feats.dtype != torch.float32 or not feats.is_cuda:
-            raise GwbpError("feature map must be a float32 HIP tensor")
+        if feats.dtype not in MAP_TYPES or not feats.is_cuda:
+            raise GwbpError(f"feature map must be a float32, float16 or bfloat16 HIP tensor, got {feats.dtype}")
         sy, sx, sc = feats.stride()
         if min(sy, sx, sc) < 0:
             raise GwbpError("negative feature-map strides are not supported")
@@ -323,11 +355,11 @@ class Engine:
 
     @classmethod
     def can_scatter_tokens(cls, tokens: torch.Tensor, height: int, width: int) -> bool:
-        """Low-resolution maps the token-space path takes: [h, w, D] float32 on the device, D % 4 == 0 and D >= 64 (the 384 / 768 /
-        1024 / 1536 channels of the DINOv2 backbones), channel-contiguous
-        16-B aligned rows, texels at least a tile wide and high (token_geometry_ok), views of at most 4096 x 4096 pixels.
-        Anything else goes through blend_weights + scatter(upsample="nearest")."""
-        if tokens.dim() != 3 or not tokens.is_cuda or tokens.dtype != torch.float32:
+        """Low-resolution maps the token-space path takes: [h, w, D] float32, float16 or bfloat16 on the device, D % 4 == 0 and
+        D >= 64 (the 384 / 768 / 1024 / 1536 channels of the DINOv2 backbones), channel-contiguous rows whose strides are multiples
+        of 4 elements, a 16-B aligned map, texels at least a tile wide and high (token_geometry_ok), views of at most 4096 x 4096
+        pixels.  Anything else goes through blend_weights + scatter(upsample="nearest")."""
+        if tokens.dim() != 3 or not tokens.is_cuda or tokens.dtype not in MAP_TYPES:
             return False
         if max(int(height), int(width)) > cls.TOKEN_MAX_VIEW:
             return False
@@ -354,17 +386,23 @@ class Engine:
     def scatter_tokens(self, view, tokens, F, d, scale_f=1.0, scale_d=1.0):
         """F[g,:] += scale_f * sum_t omega_{g,t} tokens[t,:], d[g] += scale_d * sum_t omega_{g,t} from the sums blend_tokens left:
         equals scatter(view, tokens, F, d, upsample="nearest") up to summation order, with one plain read-modify-write of every
-        row that receives weight (no atomics: deterministic) and the token map read from L2 / Infinity Cache."""
+        row that receives weight (no atomics: deterministic) and the token map read from L2 / Infinity Cache.  fp16 / bf16 tokens
+        are read as they are and widened in the kernel: F and d equal those of tokens.float() bit for bit."""
         if getattr(self, "_tokens", None) != (int(tokens.shape[0]), int(tokens.shape[1])):
             raise GwbpError("scatter_tokens needs blend_tokens(view, h, w) of the same view and map size first")
         if not self.can_scatter_tokens(tokens, view.height, view.width):
-            raise GwbpError(f"scatter_tokens: [h,w,D] float32 map with D % 4 == 0, D >= 64, channel-contiguous 16-B aligned rows and texels "
+            raise GwbpError(f"scatter_tokens: [h,w,D] float32 / float16 / bfloat16 map with D % 4 == 0, D >= 64, channel-contiguous 16-B aligned rows and texels "
                             f"of at least a tile at a view of at most {self.TOKEN_MAX_VIEW} x {self.TOKEN_MAX_VIEW} pixels required, got "
                             f"{tuple(tokens.shape)} strides {tuple(tokens.stride())} at {view.width} x {view.height}")
         D = tokens.shape[2]
         self._check_acc(F, d, D)
         ymap, xmap = self.nearest_maps(tokens.shape[0], tokens.shape[1], view.height, view.width)
         sy, sx, _ = tokens.stride()
+        if tokens.dtype in HALF_TYPES:
+            self._call("gwbp_scatter_tokens_typed", *self._args(), C.byref(view), ptr(tokens), MAP_TYPES[tokens.dtype],
+                       C.c_int64(sy), C.c_int64(sx), D, ptr(ymap), ptr(xmap), C.c_float(scale_f), C.c_float(scale_d), ptr(F),
+                       ptr(d), self._stream())
+            return
         self._call("gwbp_scatter_tokens", *self._args(), C.byref(view), ptr(tokens), C.c_int64(sy), C.c_int64(sx), D, ptr(ymap),
                    ptr(xmap), C.c_float(scale_f), C.c_float(scale_d), ptr(F), ptr(d), self._stream())
 
@@ -405,7 +443,11 @@ class Engine:
 
         upsample="nearest" / "bilinear": feats is a LOW-RESOLUTION map [h,w,D]; the result equals scattering
         F.interpolate(feats, size=(H,W), mode=...) (dino: backproject.py:244-248; lseg: backproject.py:110-112,
-        align_corners=False) without building that map -- the interpolation happens while the tile slabs are staged."""
+        align_corners=False) without building that map -- the interpolation happens while the tile slabs are staged.
+
+        feats may be float32, float16 or bfloat16.  A half map that half_native() admits is read as it is and widened to fp32
+        while the slabs are staged: F and d equal those of feats.float() up to the order of the atomic sums.  Any other half map
+        (D <= 64 or not a multiple of 128, fs_c != 1, misaligned for the 128-channel kernel) is widened with .float() here."""
         if self._tokens is not None:
             raise GwbpError("this view was blended with blend_tokens (no weight store): scatter_tokens() is its consumer; "
                             "blend_weights() first for scatter()")
@@ -418,6 +460,10 @@ class Engine:
                 return self.scatter(view, feats, F, d, scale_f, scale_d, upsample)
             finally:
                 self.caps.flags = saved
+        if feats.dtype in HALF_TYPES:
+            if not self.half_native(feats):
+                return self.scatter(view, self._widen(feats), F, d, scale_f, scale_d, upsample)
+            return self._scatter_half(view, feats, F, d, scale_f, scale_d, upsample)
         if upsample is None:
             sy, sx, sc, D = self._feat_strides(feats, view)
             self._check_acc(F, d, D)
@@ -442,25 +488,45 @@ class Engine:
                                               C.c_int64(sc), D, ptr(ymap), ptr(xmap), C.c_float(scale_f),
                                               C.c_float(scale_d), ptr(F), ptr(d), self._stream())
 
+    def _scatter_half(self, view, feats, F, d, scale_f, scale_d, upsample):
+        """scatter() of a half map that half_native() admits: the typed entry points."""
+        if upsample not in (None, "nearest", "bilinear"):
+            raise GwbpError(f"upsample must be None, 'nearest' or 'bilinear', got {upsample!r}")
+        sy, sx, sc, D = self._feat_strides(feats, view, lowres=upsample is not None)
+        self._check_acc(F, d, D)
+        head = (*self._args(), C.byref(view), ptr(feats), MAP_TYPES[feats.dtype], C.c_int64(sy), C.c_int64(sx), C.c_int64(sc), D)
+        tail = (C.c_float(scale_f), C.c_float(scale_d), ptr(F), ptr(d), self._stream())
+        if upsample is None:
+            self._call("gwbp_scatter_typed", *head, *tail)
+        elif upsample == "bilinear":
+            y0, ly, x0, lx = self.bilinear_maps(feats.shape[0], feats.shape[1], view.height, view.width)
+            self._call("gwbp_scatter_bilinear_typed", *head, int(feats.shape[0]), int(feats.shape[1]), ptr(y0), ptr(ly), ptr(x0),
+                       ptr(lx), *tail)
+        else:
+            ymap, xmap = self.nearest_maps(feats.shape[0], feats.shape[1], view.height, view.width)
+            self._call("gwbp_scatter_upsampled_typed", *head, ptr(ymap), ptr(xmap), *tail)
+
     @staticmethod
     def can_fuse_encoder(feats: torch.Tensor, encoder: torch.Tensor) -> bool:
         """Shapes gwbp_scatter_encoded takes: [H,W,K] float32 with channel-contiguous 16-B aligned pixels, K % 16 == 0,
-        K <= 1024, at most 16 outputs."""
+        K <= 1024, at most 16 outputs.  (fp16 / bf16 maps of that shape and layout too: scatter_encoded widens them.)"""
         if feats.dim() != 3 or encoder.dim() != 2 or feats.shape[2] != encoder.shape[0]:
             return False
         sy, sx, sc = feats.stride()
         K, n = encoder.shape
-        return (feats.is_cuda and feats.dtype == torch.float32 and encoder.dtype == torch.float32 and n <= 16
+        return (feats.is_cuda and feats.dtype in MAP_TYPES and encoder.dtype == torch.float32 and n <= 16
                 and K % 16 == 0 and 16 <= K <= 1024 and sc == 1 and sy % 4 == 0 and sx % 4 == 0 and sy >= 0 and sx >= 0
                 and feats.data_ptr() % 16 == 0)
 
     def scatter_encoded(self, view, feats, encoder, F, d, scale_f=1.0, scale_d=1.0):
         """scatter(view, feats @ encoder, ...) of the compressed variant (backproject_compressed.py:127-165) in ONE kernel:
-        the [H,W,K] map is read once, tile by tile, and multiplied by the encoder while the slabs are staged."""
+        the [H,W,K] map is read once, tile by tile, and multiplied by the encoder while the slabs are staged.  A half map is
+        widened with .float() first (the fused encoder reads float32)."""
         if not self.can_fuse_encoder(feats, encoder):
             raise GwbpError("scatter_encoded: [H,W,K] float32 channel-contiguous map, K % 16 == 0, K <= 1024, <= 16 outputs")
         if feats.shape[0] != view.height or feats.shape[1] != view.width:
             raise GwbpError(f"feature map must be [{view.height},{view.width},K], got {tuple(feats.shape)}")
+        feats = self._widen(feats)
         sy, sx, _ = feats.stride()
         K, n = encoder.shape
         self._check_acc(F, d, n)
@@ -525,10 +591,17 @@ class Engine:
 
     def backproject_view(self, view, means, quats, scales, opacities, feats, F, d, scale_f=1.0, scale_d=1.0):
         """Per-view body of create_feature_field_* (backproject.py:115-151), one fused call (pinhole / classic views only:
-        gwbp_backproject_view has no camera settings)."""
+        gwbp_backproject_view has no camera settings).  An fp16 / bf16 map: project + bin_sort + blend_weights + scatter
+        (the fused call reads float32 only), which scatter() reads natively where it can."""
         if not _lib.is_default_camera(view):
             raise GwbpError("backproject_view is pinhole / classic only; use project + bin_sort + blend_weights + scatter "
                             f"for {_lib.camera_of(view)}")
+        if feats.dtype in HALF_TYPES:
+            self._feat_strides(feats, view)
+            self.project(view, means, quats, scales, opacities)
+            self.bin_sort(view)
+            self.blend_weights(view)
+            return self.scatter(view, feats, F, d, scale_f, scale_d)
         sy, sx, sc, D = self._feat_strides(feats, view)
         self._check_acc(F, d, D)
         means, quats = _req(means, "means", (3,)), _req(quats, "quats", (4,))
@@ -547,7 +620,7 @@ class Engine:
             return False
         sy, sx, sc = feats.stride()
         K, n = encoder.shape
-        return (feats.is_cuda and feats.dtype == torch.float32 and encoder.dtype == torch.float32 and n <= 16 and
+        return (feats.is_cuda and feats.dtype in MAP_TYPES and encoder.dtype == torch.float32 and n <= 16 and
                 K % 16 == 0 and K <= 2048 and sc == 1 and sy % 4 == 0 and sx % 4 == 0 and feats.data_ptr() % 16 == 0
                 and sy >= 0 and sx >= 0)
 
@@ -558,13 +631,20 @@ class Engine:
         RAISE: the hot stage never falls back to a library GEMM silently -- callers that want one write `feats @ encoder`.
         workgroups: 0 = fastest alone; one per CU when the call overlaps latency-bound kernels on other streams
         (ViewPipeline.encode_ahead).  stream: launch there instead of on this engine's stream (an engine bound to a view's
-        stream by bind_stream must not run another view's encoder on it); the output is allocated under that stream."""
+        stream by bind_stream must not run another view's encoder on it); the output is allocated under that stream.  A half
+        map (fp16 / bf16) is widened with .float() on that stream first: the encoder reads float32."""
         if feats.dim() != 3 or encoder.dim() != 2 or feats.shape[2] != encoder.shape[0]:
             raise GwbpError(f"encode_map: [H,W,K] @ [K,n] expected, got {tuple(feats.shape)} @ {tuple(encoder.shape)}")
         if not self.can_encode_map(feats, encoder):
             raise GwbpError("encode_map: [H,W,K] float32 channel-contiguous 16-B aligned map, K % 16 == 0, K <= 2048, "
                             f"<= 16 outputs required, got {tuple(feats.shape)} strides {tuple(feats.stride())} @ "
                             f"{tuple(encoder.shape)} (use feats @ encoder for other shapes)")
+        if feats.dtype in HALF_TYPES:
+            if stream is None:
+                feats = self._widen(feats)
+            else:
+                with torch.cuda.stream(stream):
+                    feats = feats.float()
         H, W, K = feats.shape
         n = encoder.shape[1]
         sy, sx, _ = feats.stride()

@@ -257,6 +257,39 @@ GWBP_API int gwbp_scatter_bilinear(const gwbp_caps *caps, void *workspace, size_
                           int32_t lr_w, const int32_t *y0, const float *ly, const int32_t *x0, const float *lx,
                           float scale_f, float scale_d, float *F, float *d, void *stream);
 
+/* Element type of the feature map of the typed scatter entry points below. */
+#define GWBP_MAP_F32 0  /* float32 */
+#define GWBP_MAP_F16 1  /* IEEE binary16 */
+#define GWBP_MAP_BF16 2 /* bfloat16 (the upper half of a float32) */
+
+/* Typed forms of gwbp_scatter, gwbp_scatter_upsampled, gwbp_scatter_bilinear and gwbp_scatter_tokens: `feats` / `tokens` hold
+ * elements of `map_type` and every stride counts ELEMENTS.  An unknown map_type is GWBP_EINVAL, checked before anything else.
+ * GWBP_MAP_F32 does exactly what the untyped function does.  A half map (GWBP_MAP_F16 / GWBP_MAP_BF16) is widened to fp32 as it
+ * is staged (exact), so F and d equal the untyped function's on the fp32 copy of the map up to the order of the atomic sums
+ * (gwbp_scatter_tokens_typed: bit for bit).  Half maps are read natively on these paths only, GWBP_EUNSUPPORTED otherwise:
+ *   - gwbp_scatter_typed / _upsampled_typed / _bilinear_typed: D % 128 == 0 and fs_c == 1.  The 256-channel kernel (D % 256 == 0,
+ *     no GWBP_FLAG_NARROW_SCATTER) takes any such map.  The 128-channel kernel reads 4 channels per 8-B load and needs fs_x and
+ *     fs_y to be multiples of 8 elements and feats 16-B aligned.
+ *   - gwbp_scatter_tokens_typed: D % 4 == 0 and D >= 4 (as the untyped function), ts_x and ts_y multiples of 4 elements, tokens
+ *     16-B aligned, ts_x >= D.
+ * Small D (<= 64), the encoder-fused entry points and maps with fs_c != 1 take float32 only. */
+GWBP_API int gwbp_scatter_typed(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                                const void *feats, int32_t map_type, int64_t fs_y, int64_t fs_x, int64_t fs_c, int32_t D,
+                                float scale_f, float scale_d, float *F, float *d, void *stream);
+GWBP_API int gwbp_scatter_upsampled_typed(const gwbp_caps *caps, void *workspace, size_t workspace_bytes,
+                                          const gwbp_view *view_host, const void *feats, int32_t map_type, int64_t fs_y,
+                                          int64_t fs_x, int64_t fs_c, int32_t D, const int32_t *ymap, const int32_t *xmap,
+                                          float scale_f, float scale_d, float *F, float *d, void *stream);
+GWBP_API int gwbp_scatter_bilinear_typed(const gwbp_caps *caps, void *workspace, size_t workspace_bytes,
+                                         const gwbp_view *view_host, const void *feats, int32_t map_type, int64_t fs_y,
+                                         int64_t fs_x, int64_t fs_c, int32_t D, int32_t lr_h, int32_t lr_w, const int32_t *y0,
+                                         const float *ly, const int32_t *x0, const float *lx, float scale_f, float scale_d,
+                                         float *F, float *d, void *stream);
+GWBP_API int gwbp_scatter_tokens_typed(const gwbp_caps *caps, void *workspace, size_t workspace_bytes,
+                                       const gwbp_view *view_host, const void *tokens, int32_t map_type, int64_t ts_y,
+                                       int64_t ts_x, int32_t D, const int32_t *ymap, const int32_t *xmap, float scale_f,
+                                       float scale_d, float *F, float *d, void *stream);
+
 /* Forward render (what rasterization() returns): out[p,:] = sum_g w_g(p) * colors[g,:], out is [H,W,D]. */
 GWBP_API int gwbp_render(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
                 const float *colors, int32_t D, float *out, void *stream);

@@ -57,6 +57,9 @@ def build_parser() -> argparse.ArgumentParser:
                          "no distortion coefficients)")
     ap.add_argument("--rasterize-mode", choices=["classic", "antialiased"], default="classic",
                     help="antialiased: opacity x compensation, for scenes trained with gsplat's antialiased switch")
+    ap.add_argument("--map-dtype", choices=["float32", "keep"], default="float32",
+                    help="keep: hand fp16 / bf16 feature maps to the library as stored (read natively by the 128- and "
+                         "256-channel kernels and token space, no fp32 copy); float32: convert every map first")
     return ap
 
 
@@ -130,9 +133,12 @@ def main(argv=None):
         reduction = "mean" if args.feature == "dino" else "sum"  # backproject.py:263,283 vs :127,145
 
         def feature_fn(v):
-            f = torch.load(os.path.join(args.feature_maps, images[v].name + ".pt")).to(dev).float()
+            f = torch.load(os.path.join(args.feature_maps, images[v].name + ".pt")).to(dev)
+            if args.map_dtype == "float32" or f.dtype not in (torch.float16, torch.bfloat16):
+                f = f.float()
             if upsample is not None or tuple(f.shape[:2]) == (H, W):
                 return f
+            f = f.float()  # (a map the CLI upsamples itself: interpolated in fp32, as before)
             kw = {"align_corners": False} if mode == "bilinear" else {}
             return torch.nn.functional.interpolate(f.permute(2, 0, 1)[None], size=(H, W), mode=mode, **kw)[0].permute(1, 2, 0)
 

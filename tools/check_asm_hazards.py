@@ -129,8 +129,18 @@ def wide_kernel_facts(path):
     return sg, {k: int(v) for k, v in vg.items()}
 
 
-def check_wide(path):
-    """Everything the build asserts about a scatter_wide assembly (Makefile: every variant; tests/test_capi_cpu.py: -O3, -O2)."""
+def wide_instantiations(path):
+    """{template arguments: num_vgpr} of every k_scatter_wide kernel in the file, e.g. {"Lb0ELi1E": 104} (BILINEAR = false,
+    map type 1 = fp16); wide_kernel_facts keys by BILINEAR alone."""
+    vg = re.findall(r"k_scatter_wideI(\S+?)EEvN\S*\.num_vgpr, (\d+)", open(path).read())
+    return {k: int(v) for k, v in vg}
+
+
+def check_wide(path, kernels=2):
+    """Everything the build asserts about a scatter_wide assembly (Makefile: every variant; tests/test_capi_cpu.py: -O3, -O2).
+    `kernels`: the k_scatter_wide instantiations the object must hold (scatter_wide.hip 2, scatter_wide_half.hip 4), each
+    within the register budget of scatter_wide.hip ("REGISTER BUDGET"): at most 104 for the full-resolution instantiations,
+    112 for the bilinear ones."""
     msgs = [f"HAZARD {p}  ->  {l}" for p, l in scan(path)]
     msgs += [f"RESERVED SGPR outside inline asm: {l}" for l in reserved_sgpr_uses(path)]
     msgs += [f"IN-FLIGHT landing register named by compiler code: {l}" for l in inflight_register_uses(path)]
@@ -139,6 +149,12 @@ def check_wide(path):
         msgs.append(f"k_scatter_wide: .amdhsa_next_free_sgpr must be 100 (the descriptor must cover s[68:99]), found {sorted(sg)}")
     if len(vg) != 2:
         msgs.append(f"k_scatter_wide: expected two instantiations, found {vg}")
+    inst = wide_instantiations(path)
+    if len(inst) != kernels:
+        msgs.append(f"k_scatter_wide: expected {kernels} instantiations, found {sorted(inst)}")
+    for k, v in inst.items():
+        if v > (112 if k.startswith("Lb1E") else 104):
+            msgs.append(f"k_scatter_wide<{k}>: {v} VGPRs is over the register budget")
     txt = open(path).read()
     for t in ("s_load_dwordx16 s[68:68+15]", "s_load_dwordx16 s[84:84+15]"):
         if t not in txt:
@@ -148,8 +164,11 @@ def check_wide(path):
 
 if __name__ == "__main__":
     if len(sys.argv) > 2 and sys.argv[1] == "--wide":  # the Makefile's build-time gate for every scatter_wide object
-        msgs = [f"{f}: {m}" for f in sys.argv[2:] for m in check_wide(f)]
-        print("\n".join(msgs) if msgs else "scatter_wide asm checks ok: " + " ".join(sys.argv[2:]))
+        files, kernels = sys.argv[2:], 2
+        if len(files) > 2 and files[0] == "--kernels":
+            kernels, files = int(files[1]), files[2:]
+        msgs = [f"{f}: {m}" for f in files for m in check_wide(f, kernels)]
+        print("\n".join(msgs) if msgs else "scatter_wide asm checks ok: " + " ".join(files))
         sys.exit(1 if msgs else 0)
     total = 0
     for f in sys.argv[1:]:
