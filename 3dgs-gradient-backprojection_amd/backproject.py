@@ -776,6 +776,133 @@ def create_feature_field(means, quats, scales, opacities, viewmats, K, width: in
     return out
 
 
+class _LabelPipeline(ViewPipeline):
+    """The ViewPipeline of create_label_field: the front stage blends a weight store and adds the view's denominators on its side
+    stream (gwbp_blend_weights_d), the scatter stage is Engine.scatter_labels, which then adds F only.  No feature scatter kernel
+    is chosen and no fused or token-space blend runs: the label kernel reads the weight store."""
+
+    def __init__(self, *args, num_classes: int, **kw):
+        self.num_classes = int(num_classes)
+        super().__init__(*args, scatter_dim=None, fuse_small=False, **kw)
+
+    def choose_scatter_kernel(self, n_pairs, n_headers) -> str:
+        self.wide = True  # (what front() reads: the blend takes the record sums and adds d)
+        for e in self.eng:
+            e.set_narrow_scatter(False)
+            e.set_front_priority(False)
+        return "labels"
+
+    def _scatter_on(self, main, b, labels, F, d, scale_f, scale_d, t0, t1, upsample, encoder):
+        e = self.eng[b]
+        if t0 is not None:
+            t0.record(main)
+        p = self.pending.pop(self.i_scatter)
+        e.scatter_labels(p.view, labels, F, None if p.d_done else d, self.num_classes, scale_f, scale_d, upsample=upsample)
+        if t1 is not None:
+            t1.record(main)
+        e.accumulate_stats(self.accums[0])
+
+
+def _run_labels_pipelined(job: _Job, eng: Engine, depth: int, num_classes: int) -> Dict[str, int]:
+    """create_label_field's views through a _LabelPipeline of `depth` workspaces; an overflow seen after view 2 or by a later
+    probe ends the pass early (as in _run_pipelined)."""
+    (means, quats, scales, opacities), F, d, sf, sd, label_fn, ids, _, _, width, height, _, _, upsample = job
+    n = means.shape[0]
+    pipe = _LabelPipeline(n, width, height, means.device, num_classes=num_classes,
+                          engines=[eng] + [Engine(n, width, height, device=means.device, tight_binning=eng.tight_binning,
+                                                  isect_cap=eng.isect_cap, pair_cap=eng.pair_cap) for _ in range(depth - 1)])
+    views = [eng.view(job.vm_host[v], job.K_host, width, height, **job.camera) for v in ids]
+    for j in range(min(pipe.lookahead, len(ids))):
+        pipe.front(views[j], means, quats, scales, opacities, d, sd)
+    probe = None
+    for i, v in enumerate(ids):
+        if i == 2 and pipe.stats()["overflow"]:
+            break
+        if probe is not None and all(e.query() for e in probe[1]):
+            if any(Engine.decode_stats(a)["overflow"] for a in probe[0]):
+                break
+            probe = None
+        if i > 2 and i % OVERFLOW_CHECK_EVERY == 0 and probe is None:
+            probe = pipe.stats_async()
+        if i + pipe.lookahead < len(ids):
+            pipe.front(views[i + pipe.lookahead], means, quats, scales, opacities, d, sd)
+        pipe.scatter(label_fn(v), F, d, sf, sd, upsample=upsample)
+    stats = pipe.stats()
+    pipe.release()
+    return stats
+
+
+def _run_labels_serial(job: _Job, eng: Engine, num_classes: int) -> Dict[str, int]:
+    """create_label_field's views one after the other on the caller's stream; the label kernel adds d too (synchronises)."""
+    accum = torch.zeros(32, dtype=torch.uint8, device=job.F.device)
+    for v in job.view_ids:
+        labels = job.feature_fn(v)
+        view = eng.view(job.vm_host[v], job.K_host, job.width, job.height, **job.camera)
+        eng.project(view, *job.gaussians)
+        eng.bin_sort(view)
+        eng.blend_weights(view)
+        eng.scatter_labels(view, labels, job.F, job.d, num_classes, job.sf, job.sd, upsample=job.upsample)
+        eng.accumulate_stats(accum)
+    return Engine.decode_stats(accum)
+
+
+def label_fractions(F: torch.Tensor, d: torch.Tensor) -> torch.Tensor:
+    """P = F / d[:, None] with 0 where d == 0: each Gaussian's share of its blend weight per class."""
+    den = d[:, None]
+    return torch.where(den > 0, F / torch.where(den > 0, den, torch.ones_like(den)), torch.zeros_like(F))
+
+
+def create_label_field(means, quats, scales, opacities, viewmats, K, width: int, height: int,
+                       label_fn: Callable[[int], torch.Tensor], num_classes: int, *, upsample: Optional[str] = None,
+                       views: Optional[Sequence[int]] = None, pipeline: bool = True, gather: bool = True,
+                       return_partials: bool = False, camera_model: str = "pinhole", rasterize_mode: str = "classic",
+                       engine: Optional[Engine] = None):
+    """Lift per-view integer LABEL maps (a segmenter's class or instance ids, a binary mask) onto the Gaussians: the [N, num_classes]
+    field P[g, k] = F[g, k] / d[g] (0 where d[g] == 0) with
+        F[g, k] = sum_v sum_p w_g(p) [L_v(p) == k],    d[g] = sum_v sum_p w_g(p),
+    i.e. the fraction of each Gaussian's blend weight that fell on class k.  This is create_feature_field on one_hot(L_v) with
+    reduction "sum" (the reference's (render * feats).sum().backward(), backproject.py:127-131, with a 0/1 map), without the
+    one-hot map: gwbp_scatter_labels adds one atomic per (Gaussian, tile) record and distinct label.  Rows sum to at most 1; the
+    shortfall is the share that fell on labels outside [0, num_classes), which are ignored.  A 3-D mask is a threshold on a column.
+    P is not L2-normalised like the feature field.
+
+    label_fn(v) -> [height, width] (with upsample="nearest": any [h, w]) integer map on the device: uint8, bool, int16 or int32
+    read as stored, int64 narrowed (engine.narrow_labels).
+    views, pipeline (True, an int >= 2 workspaces, or False), gather, camera_model, rasterize_mode, engine: as create_feature_field.
+    return_partials: also return (F_rows, d, stats) -- the summed accumulators (this rank's row block of F, all of d)."""
+    if upsample not in (None, "nearest"):
+        raise ValueError(f"upsample must be None or 'nearest' for label maps, got {upsample!r}")
+    dist, rank, world = _dist()
+    n = means.shape[0]
+    F, d, F_store = alloc_accumulators(n, int(num_classes), means.device, world)
+    job = _Job((means, quats, scales, opacities), F, d, 1.0, 1.0, label_fn,
+               list(views) if views is not None else view_shard(viewmats.shape[0], rank, world),
+               viewmats.detach().cpu(), K.detach().cpu(), width, height,
+               dict(camera_model=camera_model, rasterize_mode=rasterize_mode), None, upsample)
+    pipelined = bool(pipeline) and len(job.view_ids) > 1
+    if pipelined and _lib.hw_queues_late():
+        warnings.warn("gsbp_amd was imported after the HIP runtime had started: create_label_field runs its views on ONE stream",
+                      RuntimeWarning, stacklevel=2)
+        pipelined = False
+    depth = (pipeline_depth(n, width, height) if pipeline is True else max(2, int(pipeline))) if pipelined else 1
+    eng = engine or Engine(n, width, height, device=means.device, tight_binning=True)
+    stats: Dict[str, int] = {}
+    for attempt in range(6):  # a capacity overflow invalidates the accumulators: grow the workspace, start over
+        stats = (_run_labels_pipelined(job, eng, depth, int(num_classes)) if pipelined
+                 else _run_labels_serial(job, eng, int(num_classes)))
+        if _overflow_action(stats["overflow"], False, attempt) is None:
+            break
+        eng.grow(stats, views=len(job.view_ids))
+        F.zero_()
+        d.zero_()
+    F_rows, d_rows, row0 = reduce_partials_sharded(F, d, F_store)
+    P = label_fractions(F_rows, d_rows)
+    out = gather_rows(P, n) if gather else P
+    if return_partials:
+        return out, F_rows, d, dict(stats, row0=row0)
+    return out
+
+
 def prune_mask(d: torch.Tensor) -> torch.Tensor:
     """utils.prune_by_gradients (utils.py:222-271) keeps Gaussians whose accumulated colour-gradient norm is
     > 0 over all views; that norm is 2/(3HW) * sum_v sum_p w, i.e. the mask is exactly d > 0."""

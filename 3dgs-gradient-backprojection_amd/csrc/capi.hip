@@ -534,6 +534,36 @@ int gwbp_scatter_tokens_typed(const gwbp_caps *caps, void *workspace, size_t wor
                                    static_cast<hipStream_t>(stream), map_type);
 }
 
+int gwbp_scatter_labels(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                        const void *labels, int32_t label_type, int64_t ls_y, int64_t ls_x, int32_t num_classes,
+                        const int32_t *ymap, const int32_t *xmap, float scale_f, float scale_d, float *F, int64_t ldf, float *d,
+                        void *stream)
+{
+    // the label arguments first: nothing of the caps, the workspace or the view is looked at before they pass
+    if (label_type != GWBP_LABEL_U8 && label_type != GWBP_LABEL_I16 && label_type != GWBP_LABEL_I32)
+        return set_error(GWBP_EINVAL, "unknown label type %d", (int)label_type);
+    if (num_classes <= 0)
+        return set_error(GWBP_EINVAL, "num_classes must be positive (got %d)", (int)num_classes);
+    if (ldf < num_classes)
+        return set_error(GWBP_EINVAL, "ldf %lld < num_classes %d", (long long)ldf, (int)num_classes);
+    if (!F)
+        return set_error(GWBP_EINVAL, "null F");
+    if (!ymap != !xmap)
+        return set_error(GWBP_EINVAL, "gwbp_scatter_labels needs both index maps or neither");
+    if (!labels || ls_y < 0 || ls_x < 0)
+        return set_error(GWBP_EINVAL, "bad label map arguments (strides %lld %lld)", (long long)ls_y, (long long)ls_x);
+    Layout L;
+    Ws W;
+    ViewDev V;
+    int rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W);
+    if (rc)
+        return rc;
+    if ((rc = make_view(view_host, caps, &V)))
+        return rc;
+    return launch_scatter_labels(L, W, V, labels, label_type, ls_y, ls_x, ymap, xmap, num_classes, scale_f, scale_d, F, ldf, d,
+                                 static_cast<hipStream_t>(stream));
+}
+
 int gwbp_render(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
                 const float *colors, int32_t D, float *out, void *stream)
 {

@@ -218,6 +218,10 @@ int launch_scatter_full_half(const Layout &L, const Ws &W, const ViewDev &V, con
 int launch_token_apply_half(const Layout &L, const Ws &W, const ViewDev &V, const void *tokens, int64_t ts_y, int64_t ts_x,
                             int D, const int32_t *ymap, const int32_t *xmap, float scale_f, float scale_d, float *F, float *d,
                             hipStream_t s, int mt);
+// integer label maps (label.hip): F[g, L(p)] += scale_f * w, d[g] += scale_d * w; label_type = GWBP_LABEL_*
+int launch_scatter_labels(const Layout &L, const Ws &W, const ViewDev &V, const void *labels, int label_type, int64_t ls_y,
+                          int64_t ls_x, const int32_t *ymap, const int32_t *xmap, int K, float scale_f, float scale_d, float *F,
+                          int64_t ldf, float *d, hipStream_t s);
 int launch_render(const Layout &L, const Ws &W, const ViewDev &V, const float *colors, int D, float *out,
                   hipStream_t s);
 int launch_render_px(const Ws &W, const ViewDev &V, const float *colors, int D, float *out, float *alphas,

@@ -44,6 +44,16 @@ def bilinear_index(n_in: int, n_out: int):
     return i0.to(torch.int32), lam
 
 
+# label-map element types gwbp_scatter_labels reads natively (GWBP_LABEL_*); a bool mask is read as its uint8 bytes
+LABEL_TYPES = {torch.uint8: _lib.LABEL_U8, torch.bool: _lib.LABEL_U8, torch.int16: _lib.LABEL_I16, torch.int32: _lib.LABEL_I32}
+
+
+def narrow_labels(labels: torch.Tensor, num_classes: int) -> torch.Tensor:
+    """An int64 label map as the int32 map gwbp_scatter_labels reads: every id outside [0, num_classes) becomes -1 (ignored)
+    BEFORE the narrowing, so that no wide id can wrap into range."""
+    return torch.where((labels < 0) | (labels >= num_classes), -1, labels).to(torch.int32)
+
+
 def _req(t: torch.Tensor, name: str, shape_tail=None) -> torch.Tensor:
     if not t.is_cuda:
         raise GwbpError(f"{name} must be a CUDA/HIP tensor (no CPU fallback exists for this path)")
@@ -487,6 +497,47 @@ class Engine:
         self._call("gwbp_scatter_upsampled", *self._args(), C.byref(view), ptr(feats), C.c_int64(sy), C.c_int64(sx),
                                               C.c_int64(sc), D, ptr(ymap), ptr(xmap), C.c_float(scale_f),
                                               C.c_float(scale_d), ptr(F), ptr(d), self._stream())
+
+    def scatter_labels(self, view, labels, F, d, num_classes: int, scale_f=1.0, scale_d=1.0, upsample: Optional[str] = None):
+        """F[g, k] += scale_f * sum_p w_g(p) [labels[p] == k], d[g] += scale_d * sum_p w_g(p) from the view's weight store: scatter()
+        of one_hot(labels, num_classes) without the one-hot map (gwbp_scatter_labels: one atomic per record and distinct label).
+        A label outside [0, num_classes) adds to no column of F; its weight still counts in d.
+
+        labels: [H, W] uint8 / bool / int16 / int32 read as stored, any non-negative strides; int64 is narrowed first
+        (narrow_labels).  upsample="nearest": a LOW-RESOLUTION [h, w] map read through F.interpolate(mode="nearest")'s index maps.
+        F: float32 [N, num_classes] with unit column stride (its row stride may be wider); d: float32 [N] or None."""
+        if self._tokens is not None:
+            raise GwbpError("this view was blended with blend_tokens (no weight store): blend_weights() first for scatter_labels()")
+        if not torch.is_tensor(labels) or not labels.is_cuda:
+            raise GwbpError("labels must be a HIP tensor (no CPU fallback exists for this path)")
+        if labels.dtype == torch.int64:
+            labels = narrow_labels(labels, num_classes)
+        if labels.dtype not in LABEL_TYPES:
+            raise GwbpError(f"labels must be an integer map (uint8, bool, int16, int32 or int64), got {labels.dtype}")
+        if labels.dtype == torch.bool:
+            labels = labels.view(torch.uint8)
+        if upsample not in (None, "nearest"):
+            raise GwbpError(f"upsample must be None or 'nearest' for a label map, got {upsample!r}")
+        if labels.dim() != 2 or (upsample is None and tuple(labels.shape) != (view.height, view.width)):
+            want = f"[H,W] = [{view.height},{view.width}]" if upsample is None else "[h,w]"
+            raise GwbpError(f"label map must be {want}, got {tuple(labels.shape)}")
+        if min(labels.stride()) < 0:
+            raise GwbpError("negative label-map strides are not supported")
+        K = int(num_classes)
+        if K < 1:
+            raise GwbpError(f"num_classes must be positive, got {K}")
+        if (F.dtype != torch.float32 or not F.is_cuda or F.dim() != 2 or tuple(F.shape) != (self.n, K)
+                or (K > 1 and F.stride(1) != 1) or F.stride(0) < K):
+            raise GwbpError(f"F must be a float32 HIP tensor [{self.n},{K}] with unit column stride")
+        if d is not None and (d.dtype != torch.float32 or not d.is_cuda or not d.is_contiguous() or tuple(d.shape) != (self.n,)):
+            raise GwbpError(f"d must be a contiguous float32 HIP tensor [{self.n}]")
+        ymap = xmap = None
+        if upsample == "nearest":
+            ymap, xmap = self.nearest_maps(labels.shape[0], labels.shape[1], view.height, view.width)
+        sy, sx = labels.stride()
+        self._call("gwbp_scatter_labels", *self._args(), C.byref(view), ptr(labels), LABEL_TYPES[labels.dtype], C.c_int64(sy),
+                   C.c_int64(sx), K, ptr(ymap), ptr(xmap), C.c_float(scale_f), C.c_float(scale_d), ptr(F), C.c_int64(F.stride(0)),
+                   ptr(d), self._stream())
 
     def _scatter_half(self, view, feats, F, d, scale_f, scale_d, upsample):
         """scatter() of a half map that half_native() admits: the typed entry points."""

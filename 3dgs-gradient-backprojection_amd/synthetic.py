@@ -140,6 +140,33 @@ def make_feature_map(cfg: Config, view: int, device="cpu", dim: Optional[int] = 
     return f
 
 
+LABEL_SEED0 = 20_000
+
+
+def make_label_map(cfg: Config, view: int, num_classes: int, device="cpu", n_seeds: int = 200, per_pixel: bool = False,
+                   size: Optional[tuple] = None) -> torch.Tensor:
+    """[H,W] int32 label map of view `view` (seed 20000 + view) with ids in [0, num_classes): piecewise constant -- the Voronoi
+    cells of `n_seeds` random points, each cell one random id, like a segmenter's regions -- or, with per_pixel=True, an
+    independent random id per pixel (the worst case of a per-record reduction by label).  size=(h, w): a map of that shape
+    instead of the view's (a low-resolution segmenter output)."""
+    h, w = size if size is not None else (cfg.height, cfg.width)
+    g = torch.Generator(device="cpu").manual_seed(LABEL_SEED0 + view)
+    if per_pixel:
+        return torch.randint(0, num_classes, (h, w), generator=g, dtype=torch.int32).to(device)
+    pts = torch.rand(n_seeds, 2, generator=g) * torch.tensor([float(h), float(w)])
+    ids = torch.randint(0, num_classes, (n_seeds,), generator=g, dtype=torch.int32)
+    pts, ids = pts.to(device), ids.to(device)
+    ys = torch.arange(h, device=device, dtype=torch.float32) + 0.5
+    xs = torch.arange(w, device=device, dtype=torch.float32) + 0.5
+    out = torch.empty(h, w, dtype=torch.int32, device=device)
+    step = max(1, (1 << 22) // max(1, w * n_seeds))  # rows per block: a [rows, w, n_seeds] distance table of ~16 MB
+    for y0 in range(0, h, step):
+        dy = (ys[y0:y0 + step, None, None] - pts[:, 0]) ** 2
+        dx = (xs[None, :, None] - pts[:, 1]) ** 2
+        out[y0:y0 + step] = ids[(dy + dx).argmin(dim=-1)]
+    return out
+
+
 def upsample_map(cfg: Config, low: torch.Tensor) -> torch.Tensor:
     """The reference's own upsampling of a network map to the view ([h,w,D] -> [H,W,D]): F.interpolate(mode=cfg.upsample)
     (backproject.py:110-112 bilinear, align_corners=False; :244-248 nearest).  Used by checks and the CPU baseline, which

@@ -111,7 +111,8 @@ typedef struct gwbp_stats {
                            * bit3: gwbp_blend_tokens met a tile that spans more than 2 x 2 tokens (precondition violated) -> invalid;
                            * bit2: gwbp_scatter / gwbp_accumulate_d asked for the 256-channel kernel on a view that was
                            * blended WITH GWBP_FLAG_NARROW_SCATTER (no half-tile lists / weight sums): that call left
-                           * F and d untouched -- scatter again with the flag set */
+                           * F and d untouched -- scatter again with the flag set; also set by gwbp_scatter_labels (and
+                           * gwbp_scatter_tokens) on a workspace that holds no weight store (token sums): F and d untouched */
     uint32_t reserved;    /* what the last blend of this view left: 0 = weight store, 1 = store + half-tile lists, 2 = nothing (gwbp_blend_scatter), 3 = token-quadrant weight sums (gwbp_blend_tokens) */
 } gwbp_stats;
 
@@ -289,6 +290,29 @@ GWBP_API int gwbp_scatter_tokens_typed(const gwbp_caps *caps, void *workspace, s
                                        const gwbp_view *view_host, const void *tokens, int32_t map_type, int64_t ts_y,
                                        int64_t ts_x, int32_t D, const int32_t *ymap, const int32_t *xmap, float scale_f,
                                        float scale_d, float *F, float *d, void *stream);
+
+/* Element type of the label map of gwbp_scatter_labels. */
+#define GWBP_LABEL_U8 0  /* uint8_t */
+#define GWBP_LABEL_I16 1 /* int16_t */
+#define GWBP_LABEL_I32 2 /* int32_t (wider ids: the caller narrows them, sending every id outside [0, num_classes) to -1) */
+
+/* Back-projection of an integer LABEL map (a segmenter's class or instance ids, a binary mask):
+ *     F[g, k] += scale_f * sum_p w_g(p) * [L(p) == k],     d[g] += scale_d * sum_p w_g(p)
+ * = gwbp_scatter on one_hot(L, num_classes) without the one-hot map: per (Gaussian, tile) record the weights are summed by label
+ * and ONE fp32 atomic is added per (record, distinct label); the other columns of the row are never touched.  A label outside
+ * [0, num_classes) adds to no column of F but its weight still counts in d (an all-zero one-hot row).  F and d equal
+ * gwbp_scatter's on the one-hot map up to the order of the atomic sums.
+ * labels[y * ls_y + x * ls_x] (strides in ELEMENTS of label_type); with ymap / xmap (both or neither) a LOW-RESOLUTION map read
+ * with PyTorch's nearest rule, pixel (y, x) -> labels[ymap[y] * ls_y + xmap[x] * ls_x] (the index maps of gwbp_scatter_upsampled).
+ * F is [N, ldf] fp32 row-major with ldf >= num_classes; d may be NULL (a caller that added d in gwbp_blend_weights_d).
+ * GWBP_EINVAL before anything else for an unknown label_type, num_classes <= 0, ldf < num_classes, a NULL F or labels, negative
+ * strides, or exactly one of ymap / xmap NULL.  Needs the weight store of the view (gwbp_blend_weights or _d, with or without
+ * GWBP_FLAG_NARROW_SCATTER); after gwbp_blend_scatter / gwbp_blend_scatter_encoded / gwbp_blend_tokens the workspace holds none:
+ * the call then sets gwbp_stats.overflow bit 2 and leaves F and d untouched. */
+GWBP_API int gwbp_scatter_labels(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                                 const void *labels, int32_t label_type, int64_t ls_y, int64_t ls_x, int32_t num_classes,
+                                 const int32_t *ymap, const int32_t *xmap, float scale_f, float scale_d, float *F, int64_t ldf,
+                                 float *d, void *stream);
 
 /* Forward render (what rasterization() returns): out[p,:] = sum_g w_g(p) * colors[g,:], out is [H,W,D]. */
 GWBP_API int gwbp_render(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,

@@ -36,7 +36,15 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--run-feature-field-on-cpu", action=argparse.BooleanOptionalAction, default=False,
                     help="accepted for compatibility: the reference moves only its LSeg network to the CPU with it; the "
                          "feature maps are supplied here, the back-projection always runs on the GPU")
-    ap.add_argument("--feature-maps", default=None, help="directory with <image name>.pt tensors [H,W,D]")
+    maps = ap.add_mutually_exclusive_group()
+    maps.add_argument("--feature-maps", default=None, help="directory with <image name>.pt tensors [H,W,D]")
+    maps.add_argument("--label-maps", default=None,
+                      help="directory with <image name>.pt INTEGER tensors [H,W] (a segmenter's class / instance ids, a mask; "
+                           "another shape is a low-resolution map, upsampled with mode='nearest'): writes label_field.pt, the "
+                           "[N, --num-classes] fraction of every Gaussian's blend weight per class, instead of a feature field")
+    ap.add_argument("--num-classes", type=int, default=None,
+                    help="number of classes K of --label-maps (ids outside [0, K) are ignored); with --synthetic: use seeded "
+                         "piecewise-constant (Voronoi) label maps with K classes instead of feature maps")
     ap.add_argument("--encoder", default=None, help="[512,16] encoder tensor (.pt): backproject_compressed.py")
     ap.add_argument("--synthetic", default=None, help="run a seeded synthetic config (C1, C2, ...) instead of files")
     ap.add_argument("--no-prune", action="store_true",
@@ -77,8 +85,24 @@ def camera_warnings(cam, camera_model_arg):
     return out
 
 
+def load_label_map(label_dir: str, image_name: str) -> torch.Tensor:
+    """<label_dir>/<image name>.pt: an integer label map (uint8, bool, int16, int32 or int64), as stored."""
+    lab = torch.load(os.path.join(label_dir, image_name + ".pt"))
+    if not torch.is_tensor(lab) or lab.is_floating_point() or lab.is_complex() or lab.dim() != 2:
+        raise SystemExit(f"{image_name}.pt in {label_dir}: a 2-D integer label tensor is required, got "
+                         f"{lab.dtype if torch.is_tensor(lab) else type(lab).__name__}"
+                         f"{' ' + str(tuple(lab.shape)) if torch.is_tensor(lab) else ''}")
+    return lab
+
+
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    labels_mode = bool(args.label_maps) or (bool(args.synthetic) and args.num_classes is not None)
+    if labels_mode and (args.num_classes is None or args.num_classes < 1):
+        ap.error("--label-maps needs --num-classes K >= 1")
+    if labels_mode and args.encoder:
+        ap.error("--encoder applies to feature maps, not to --label-maps / --num-classes")
     camera_model = args.camera_model or "pinhole"
     cam_kw = dict(camera_model=camera_model, rasterize_mode=args.rasterize_mode)
 
@@ -107,6 +131,10 @@ def main(argv=None):
 
         def feature_fn(v):
             return syn.make_feature_map(cfg, v, device=dev)
+
+        def label_fn(v):
+            return syn.make_label_map(cfg, v, args.num_classes, device=dev)
+        label_upsample = None
     else:
         splats = scene_io.load_checkpoint(args.checkpoint, args.data_dir, format=args.format,
                                           data_factor=args.data_factor, rasterizer=args.rasterizer)
@@ -120,16 +148,23 @@ def main(argv=None):
         W, H = int(K[0, 2] * 2), int(K[1, 2] * 2)  # backproject.py:85-86
         images = sorted(splats["colmap_project"].images.values(), key=lambda im: im.name)  # backproject.py:74
         viewmats = torch.stack([scene_io.get_viewmat_from_colmap_image(im) for im in images])
-        if not args.feature_maps:
+        if labels_mode:
+            # a map at another resolution than the view's is read with F.interpolate(mode="nearest")'s index maps in the kernel
+            first_labels = load_label_map(args.label_maps, images[0].name)
+            label_upsample = "nearest" if tuple(first_labels.shape) != (H, W) else None
+
+            def label_fn(v):
+                return load_label_map(args.label_maps, images[v].name).to(dev)
+        elif not args.feature_maps:
             raise SystemExit("--feature-maps is required (no LSeg/DINO weights offline)")
         encoder = torch.load(args.encoder).to(dev).float() if args.encoder else None
-        first = torch.load(os.path.join(args.feature_maps, images[0].name + ".pt"))
-        dim = first.shape[-1]
+        first = torch.load(os.path.join(args.feature_maps, images[0].name + ".pt")) if not labels_mode else None
+        dim = first.shape[-1] if first is not None else None
         # A map at the network's resolution is upsampled the way the reference does it -- bilinear for lseg (backproject.py:110-112),
         # nearest for dino's patch tokens (:244-248) -- INSIDE the kernels (dino maps whose tokens cover a tile: token space); with an
         # encoder the map is materialised first (the encoder-fused kernels read full-resolution pixels)
         mode = "nearest" if args.feature == "dino" else "bilinear"
-        upsample = mode if (tuple(first.shape[:2]) != (H, W) and encoder is None) else None
+        upsample = mode if (first is not None and tuple(first.shape[:2]) != (H, W) and encoder is None) else None
         reduction = "mean" if args.feature == "dino" else "sum"  # backproject.py:263,283 vs :127,145
 
         def feature_fn(v):
@@ -169,9 +204,15 @@ def main(argv=None):
         report_and_check(keep)
         means, quats, scales, opac = means[keep], quats[keep], scales[keep], opac[keep]
 
-    out, F, d, stats = gsbp_amd.create_feature_field(means, quats, scales, opac, viewmats, K, W, H, feature_fn, dim,
-                                                     reduction=reduction, encoder=encoder, return_partials=True,
-                                                     verbose=True, upsample=upsample, **cam_kw)
+    if labels_mode:
+        # the same prune step, then the [N_kept, K] class fractions of every Gaussian's blend weight (label_field.pt)
+        out, F, d, stats = gsbp_amd.create_label_field(means, quats, scales, opac, viewmats, K, W, H, label_fn,
+                                                       args.num_classes, upsample=label_upsample, return_partials=True,
+                                                       **cam_kw)
+    else:
+        out, F, d, stats = gsbp_amd.create_feature_field(means, quats, scales, opac, viewmats, K, W, H, feature_fn, dim,
+                                                         reduction=reduction, encoder=encoder, return_partials=True,
+                                                         verbose=True, upsample=upsample, **cam_kw)
     if args.prune_by_product and not args.no_prune:
         # "the mask comes free from the fused kernel" -- d is the all-reduced denominator of every Gaussian,
         # identical on every rank
@@ -179,7 +220,8 @@ def main(argv=None):
         report_and_check(keep)
         out = out[keep]
     if rank == 0:
-        name = "features_lseg_compressed.pt" if encoder is not None else f"features_{args.feature}.pt"
+        name = ("label_field.pt" if labels_mode else "features_lseg_compressed.pt" if encoder is not None
+                else f"features_{args.feature}.pt")
         print("saved", scene_io.save_features(out.cpu(), args.results_dir, name), tuple(out.shape),
               f"(of {n_all} Gaussians)", stats)
         if keep is not None:  # the rows of the features file are the kept Gaussians, in order (like the reference's)
