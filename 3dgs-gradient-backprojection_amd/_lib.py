@@ -54,6 +54,8 @@ EXPORTS = [
     "gwbp_blend_weights", "gwbp_blend_weights_d", "gwbp_blend_scatter", "gwbp_blend_scatter_encoded", "gwbp_blend_tokens", "gwbp_scatter_tokens", "gwbp_accumulate_d", "gwbp_scatter", "gwbp_scatter_encoded", "gwbp_scatter_upsampled", "gwbp_scatter_bilinear", "gwbp_scatter_typed", "gwbp_scatter_upsampled_typed", "gwbp_scatter_bilinear_typed", "gwbp_scatter_tokens_typed", "gwbp_scatter_labels", "gwbp_render", "gwbp_render_pixels", "gwbp_sh_colors",
     "gwbp_backproject_view", "gwbp_encode_map", "gwbp_finalize",
     "gwbp_accumulate_stats", "gwbp_read_stats", "gwbp_dump_pairs",
+    "gwbp_blend_weights_ex", "gwbp_blend_weights_d_ex", "gwbp_blend_tokens_ex", "gwbp_blend_scatter_ex",
+    "gwbp_blend_scatter_encoded_ex",
 ]
 
 
@@ -78,6 +80,13 @@ class Stats(C.Structure):
         # ("reserved" = what the last blend left in the workspace: 0 store, 1 + half-tile lists, 2 nothing)
         return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"} | {"blend_kind": int(self.reserved)}
 
+
+class PixelWeights(C.Structure):
+    """gwbp_pixel_weights (include/gwbp.h): a per-pixel weight map c(x, y) = data[y * ws_y + x * ws_x] (strides in elements)."""
+    _fields_ = [("data", C.c_void_p), ("ws_y", C.c_int64), ("ws_x", C.c_int64), ("dtype", C.c_int32), ("reserved", C.c_int32)]
+
+
+PIXW_F32, PIXW_F16, PIXW_BF16, PIXW_U8 = 0, 1, 2, 3  # GWBP_PIXW_* (element type of a gwbp_pixel_weights map)
 
 FLAG_TIGHT_BINNING = 1  # GWBP_FLAG_TIGHT_BINNING (include/gwbp.h)
 FLAG_FRONT_PRIORITY = 2  # GWBP_FLAG_FRONT_PRIORITY
@@ -166,6 +175,12 @@ ARGTYPES = {
     "gwbp_accumulate_stats": _WS + [_P, _P],
     "gwbp_read_stats": _WS + [C.POINTER(Stats), _P],
     "gwbp_dump_pairs": _WSV + [_I64, _P, _P, _P, C.POINTER(C.c_int64), _P],
+    # the _ex forms: the unweighted argument list + const gwbp_pixel_weights * before the stream
+    "gwbp_blend_weights_ex": _WSV + [_P, C.POINTER(PixelWeights), _P],
+    "gwbp_blend_weights_d_ex": _WSV + [_P, _F, _P, C.POINTER(PixelWeights), _P],
+    "gwbp_blend_tokens_ex": _WSV + [_P, _P, _P, C.POINTER(PixelWeights), _P],
+    "gwbp_blend_scatter_ex": _WSV + [_P, _I64, _I64, _I32, _F, _F, _P, _P, _P, C.POINTER(PixelWeights), _P],
+    "gwbp_blend_scatter_encoded_ex": _WSV + [_P, _I64, _I64, _I32, _P, _I32, _F, _F, _P, _P, _P, C.POINTER(PixelWeights), _P],
 }
 
 _lib: Optional[C.CDLL] = None

@@ -156,9 +156,22 @@ def _scatter_weighted(e: Engine, view, feats, F, d, scale_f, scale_d, upsample=N
 
 
 def _blend_and_scatter(e: Engine, view, feats, F, d, scale_f, scale_d, upsample=None, encoder=None, fuse: bool = True,
-                       tokens: bool = False) -> None:
+                       tokens: bool = False, pw: Optional[torch.Tensor] = None) -> None:
     """Blend and scatter a projected and sorted view by the first form that suits its map: the fused blend + scatter kernel
-    (`fuse`; with `encoder` the encoder runs in its tile prologue), token space (`tokens`), or a weight store + scatter."""
+    (`fuse`; with `encoder` the encoder runs in its tile prologue), token space (`tokens`), or a weight store + scatter.
+    pw: the view's per-pixel weight map -- every form then runs its weighted blend (Engine.*_weighted)."""
+    if pw is not None:
+        if fuse and upsample is None and encoder is None and Engine.can_blend_scatter(feats):
+            e.blend_scatter_weighted(view, feats, pw, F, d, scale_f, scale_d)
+        elif fuse and upsample is None and encoder is not None and Engine.can_blend_scatter_encoded(feats, encoder):
+            e.blend_scatter_encoded_weighted(view, feats, encoder, pw, F, d, scale_f, scale_d)
+        elif tokens and upsample == "nearest" and encoder is None and Engine.can_scatter_tokens(feats, view.height, view.width):
+            e.blend_tokens_weighted(view, feats.shape[0], feats.shape[1], pw)
+            e.scatter_tokens(view, feats, F, d, scale_f, scale_d)
+        else:
+            e.blend_weighted(view, pw)
+            _scatter_weighted(e, view, feats, F, d, scale_f, scale_d, upsample, encoder)
+        return
     if fuse and upsample is None and encoder is None and Engine.can_blend_scatter(feats):
         e.blend_scatter(view, feats, F, d, scale_f, scale_d)
     elif fuse and upsample is None and encoder is not None and Engine.can_blend_scatter_encoded(feats, encoder):
@@ -173,7 +186,8 @@ def _blend_and_scatter(e: Engine, view, feats, F, d, scale_f, scale_d, upsample=
 
 # a view whose front stage has been enqueued (ViewPipeline.front): were its denominators added by the blend on the side
 # stream, its weight store blended, its token-quadrant weight sums blended (Engine.blend_tokens)?
-_Pending = namedtuple("_Pending", "view d_done blended tokens")
+# pw: the view's per-pixel weight map (create_feature_field(pixel_weight_fn=...)), held until the view's blend has been enqueued
+_Pending = namedtuple("_Pending", "view d_done blended tokens pw", defaults=(None,))
 
 
 class ViewPipeline:
@@ -297,10 +311,13 @@ class ViewPipeline:
             e.set_front_priority(wide if self.front_priority is None else bool(self.front_priority))
         return "wide" if wide else "narrow"
 
-    def front(self, view, means, quats, scales, opacities, d=None, scale_d=1.0):
+    def front(self, view, means, quats, scales, opacities, d=None, scale_d=1.0, pixel_weights: Optional[torch.Tensor] = None):
         """d (optional): the denominator accumulator.  With the 256-channel scatter kernel chosen, the view's share of d
         is added by the blend itself on the side stream (gwbp_blend_weights_d) and scatter() then leaves d alone: the
-        denominators cost nothing on the scatter's stream."""
+        denominators cost nothing on the scatter's stream.
+        pixel_weights (optional): the view's [H, W] weight map, produced on the caller's stream before this call: the view's
+        stream waits for it, and whichever stage blends the view (this one, or scatter() for the fused kernels) runs the
+        weighted blend."""
         K = len(self.eng)
         b = self.i_front % K
         side = self.sides[self.i_front % len(self.sides)]
@@ -310,11 +327,17 @@ class ViewPipeline:
         elif not self.independent:
             side.wait_event(self.ev_done[b])  # workspace b is free once scatter(i-K) has finished
         # (independent: scatter(i-K) was enqueued on this very stream)
+        if pixel_weights is not None:
+            if self.i_front >= K:
+                ready = torch.cuda.Event()
+                ready.record(main)
+                side.wait_event(ready)
+            pixel_weights.record_stream(side)  # (the map is also held in _Pending until the view's blend is enqueued)
         e = self.eng[b]
         if self.independent:  # the engine is bound to `side`
             e.project(view, means, quats, scales, opacities)
             e.bin_sort(view)
-            self.pending[self.i_front] = _Pending(view, False, False, False)
+            self.pending[self.i_front] = _Pending(view, False, False, False, pixel_weights)
             self.i_front += 1
             return
         with torch.cuda.stream(side):
@@ -322,11 +345,17 @@ class ViewPipeline:
             e.bin_sort(view)
             d_done = d is not None and self.wide and not self.fuse_small and self.token_grid is None
             if self.token_grid is not None:
-                e.blend_tokens(view, *self.token_grid)
+                if pixel_weights is not None:
+                    e.blend_tokens_weighted(view, *self.token_grid, pixel_weights)
+                else:
+                    e.blend_tokens(view, *self.token_grid)
             elif not self.fuse_small:
-                e.blend_weights(view, d=d if d_done else None, scale_d=scale_d)
+                if pixel_weights is not None:
+                    e.blend_weighted(view, pixel_weights, d=d if d_done else None, scale_d=scale_d)
+                else:
+                    e.blend_weights(view, d=d if d_done else None, scale_d=scale_d)
             self.ev_front[b].record(side)
-        self.pending[self.i_front] = _Pending(view, d_done, not self.fuse_small, self.token_grid is not None)
+        self.pending[self.i_front] = _Pending(view, d_done, not self.fuse_small, self.token_grid is not None, pixel_weights)
         self.i_front += 1
 
     # Encoder workgroups per CU beside the pipeline (see encode_ahead): None = 1 next to the separate blend and small-D
@@ -401,10 +430,13 @@ class ViewPipeline:
                     and Engine.can_scatter_tokens(feats, view.height, view.width)):
                 e.scatter_tokens(view, feats, F, d, scale_f, scale_d)
             else:  # this view's map does not suit the token path after all: blend a weight store here, then the usual scatter
-                e.blend_weights(view)
+                if p.pw is not None:
+                    e.blend_weighted(view, p.pw)
+                else:
+                    e.blend_weights(view)
                 _scatter_weighted(e, view, feats, F, d, scale_f, scale_d, upsample, encoder)
         elif not p.blended:
-            _blend_and_scatter(e, view, feats, F, d, scale_f, scale_d, upsample, encoder)
+            _blend_and_scatter(e, view, feats, F, d, scale_f, scale_d, upsample, encoder, pw=p.pw)
         else:
             _scatter_weighted(e, view, feats, F, None if p.d_done else d, scale_f, scale_d, upsample, encoder)
         if t1 is not None:
@@ -518,7 +550,9 @@ def pipeline_depth(n_gaussians: int, width: int, height: int, dim: Optional[int]
 
 # the inputs every attempt of create_feature_field works on (gaussians = (means, quats, scales, opacities); camera = the
 # camera_model / rasterize_mode keywords of Engine.view)
-_Job = namedtuple("_Job", "gaussians F d sf sd feature_fn view_ids vm_host K_host width height camera encoder upsample")
+# pixel_weight_fn: v -> the view's [height, width] weight map, or None (unweighted)
+_Job = namedtuple("_Job", "gaussians F d sf sd feature_fn view_ids vm_host K_host width height camera encoder upsample "
+                          "pixel_weight_fn", defaults=(None,))
 # one attempt's schedule, decided before its first view from the options and the first map (_plan).  first_map: view 0's map,
 # fetched early when its layout decides the schedule.  encode: where the encoder runs -- None (no encoder) | "blend" (the fused
 # blend + scatter kernel's tile prologue) | "staging" (the scatter kernel's slab staging) | "ahead" (a separate kernel on a
@@ -562,7 +596,7 @@ def _plan(job: _Job, pipeline, token_space, fuse_small, fuse_encoder, encoder_in
 def _run_pipelined(job: _Job, plan: _Plan, eng: Engine, allow_wide: bool, stream_safe: bool) -> Dict[str, int]:
     """The views through a ViewPipeline of plan.depth workspaces (eng's and new ones); returns the counters.  An overflow seen
     after view 2 or by a later probe (every OVERFLOW_CHECK_EVERY views) ends the pass early: the counters then show it."""
-    (means, quats, scales, opacities), F, d, sf, sd, feature_fn, ids, _, _, width, height, _, encoder, upsample = job
+    (means, quats, scales, opacities), F, d, sf, sd, feature_fn, ids, _, _, width, height, _, encoder, upsample, pwf = job
     n, first_map = means.shape[0], plan.first_map
     pipe = ViewPipeline(n, width, height, means.device, scatter_dim=F.shape[1], token_grid=plan.token_grid,
                         split_encoder=plan.split, allow_wide=allow_wide, fuse_small=plan.fuse_small,
@@ -571,8 +605,13 @@ def _run_pipelined(job: _Job, plan: _Plan, eng: Engine, allow_wide: bool, stream
                                                 isect_cap=eng.isect_cap, pair_cap=eng.pair_cap)
                                          for _ in range(plan.depth - 1)])
     views = [eng.view(job.vm_host[v], job.K_host, width, height, **job.camera) for v in ids]
+
+    def front(j):  # (a weight map is made on the caller's stream right before its view's front is enqueued)
+        pipe.front(views[j], means, quats, scales, opacities, d, sd,
+                   pixel_weights=pwf(ids[j]) if pwf is not None else None)
+
     for j in range(min(pipe.lookahead, len(ids))):
-        pipe.front(views[j], means, quats, scales, opacities, d, sd)
+        front(j)
     enc_blend, staging = plan.encode == "blend", plan.encode == "staging"
     ahead = pipe.encode_ahead(first_map, encoder) if plan.encode == "ahead" else None
     probe = None  # (pinned copy of the counters, event): an overflow costs at most OVERFLOW_CHECK_EVERY views
@@ -589,7 +628,7 @@ def _run_pipelined(job: _Job, plan: _Plan, eng: Engine, allow_wide: bool, stream
         if i > 2 and i % OVERFLOW_CHECK_EVERY == 0 and probe is None:
             probe = pipe.stats_async()
         if i + pipe.lookahead < len(ids):
-            pipe.front(views[i + pipe.lookahead], means, quats, scales, opacities, d, sd)
+            front(i + pipe.lookahead)
         pipe.wait_for_slot()  # (view-per-stream schedule only: the host stays at most `depth` maps ahead)
         if enc_blend or staging:  # the encoder inside the fused blend + scatter kernel or the scatter kernel's staging
             feats, fenc = (first_map if i == 0 else feature_fn(v)), encoder
@@ -626,14 +665,15 @@ def _run_serial(job: _Job, eng: Engine, fuse_small: bool, token_space: bool) -> 
             # caller's back (whoever wants one encodes in the feature function and passes encoder=None)
             feats = eng.encode_map(feats, job.encoder)
         view = eng.view(job.vm_host[v], job.K_host, job.width, job.height, **job.camera)
-        if (job.upsample is None and not (fuse_small and Engine.can_blend_scatter(feats))
+        pw = job.pixel_weight_fn(v) if job.pixel_weight_fn is not None else None
+        if (pw is None and job.upsample is None and not (fuse_small and Engine.can_blend_scatter(feats))
                 and _lib.is_default_camera(view)):
             eng.backproject_view(view, *job.gaussians, feats, job.F, job.d, job.sf, job.sd)  # project, sort, blend, scatter: one C call
-        else:
+        else:  # (gwbp_backproject_view has no weight map: a weighted view always takes the stages)
             eng.project(view, *job.gaussians)
             eng.bin_sort(view)
             _blend_and_scatter(eng, view, feats, job.F, job.d, job.sf, job.sd, job.upsample, fuse=fuse_small,
-                               tokens=token_space)
+                               tokens=token_space, pw=pw)
         eng.accumulate_stats(accum)
     return Engine.decode_stats(accum)
 
@@ -673,7 +713,8 @@ def create_feature_field(means, quats, scales, opacities, viewmats, K, width: in
                          fuse_small: bool = True, feature_fn_stream_safe: bool = False,
                          encoder_in_blend: Optional[bool] = None, token_space: bool = True,
                          encoder_split: Optional[bool] = None, camera_model: str = "pinhole",
-                         rasterize_mode: str = "classic"):
+                         rasterize_mode: str = "classic",
+                         pixel_weight_fn: Optional[Callable[[int], torch.Tensor]] = None):
     """Build the [N, dim_out] per-Gaussian feature field.
 
     means/quats/scales/opacities: post-activation Gaussians (backproject.py:55-57), device tensors.
@@ -724,6 +765,14 @@ def create_feature_field(means, quats, scales, opacities, viewmats, K, width: in
     camera_model ("pinhole" | "ortho" | "fisheye") / rasterize_mode ("classic" | "antialiased"): gsplat's projection options of
     the scene (a scene trained antialiased is back-projected with w = (o x compensation) T); every path above reads them from
     the projection (gwbp_project_camera), the one-call gwbp_backproject_view is used for pinhole / classic only.
+    pixel_weight_fn: v -> c_v, a [height, width] weight map of view v at FULL resolution whatever `upsample` is (bool, uint8 with
+    non-zero = 1, float16, bfloat16 or float32 on the device; any non-negative strides): which pixels count and how much --
+    undistortion borders, sky or transients, a segmenter's don't-care region, a network's confidence.  Every view then adds
+        F[g] += scale_f * sum_p w_g(p) c_v(p) f_v(p),     d[g] += scale_d * sum_p w_g(p) c_v(p)
+    (the reference's loop, backproject.py:115-151, with both targets multiplied by c_v); the transmittance is unchanged.  Every
+    schedule above runs its weighted blend (the serial path then never takes gwbp_backproject_view); a row whose d is 0
+    finalises to 0, and reduction="mean" keeps its scales.  It is called on the caller's stream up to `pipeline` views before
+    the view's feature_fn, and the map must not be overwritten before that view has been scattered.
     """
     dist, rank, world = _dist()
     n = means.shape[0]
@@ -736,7 +785,9 @@ def create_feature_field(means, quats, scales, opacities, viewmats, K, width: in
     job = _Job((means, quats, scales, opacities), F, d, sf, sd, feature_fn,
                list(views) if views is not None else view_shard(viewmats.shape[0], rank, world),
                viewmats.detach().cpu(), K.detach().cpu(), width, height,
-               dict(camera_model=camera_model, rasterize_mode=rasterize_mode), encoder, upsample)
+               dict(camera_model=camera_model, rasterize_mode=rasterize_mode), encoder, upsample, pixel_weight_fn)
+    if view_fn is not None and pixel_weight_fn is not None:
+        raise ValueError("view_fn takes a feature map only: it cannot apply pixel_weight_fn's weights")
 
     t0 = time.time()
     stats: Dict[str, int] = {}
@@ -806,14 +857,19 @@ class _LabelPipeline(ViewPipeline):
 def _run_labels_pipelined(job: _Job, eng: Engine, depth: int, num_classes: int) -> Dict[str, int]:
     """create_label_field's views through a _LabelPipeline of `depth` workspaces; an overflow seen after view 2 or by a later
     probe ends the pass early (as in _run_pipelined)."""
-    (means, quats, scales, opacities), F, d, sf, sd, label_fn, ids, _, _, width, height, _, _, upsample = job
+    (means, quats, scales, opacities), F, d, sf, sd, label_fn, ids, _, _, width, height, _, _, upsample, pwf = job
     n = means.shape[0]
     pipe = _LabelPipeline(n, width, height, means.device, num_classes=num_classes,
                           engines=[eng] + [Engine(n, width, height, device=means.device, tight_binning=eng.tight_binning,
                                                   isect_cap=eng.isect_cap, pair_cap=eng.pair_cap) for _ in range(depth - 1)])
     views = [eng.view(job.vm_host[v], job.K_host, width, height, **job.camera) for v in ids]
+
+    def front(j):  # (a weight map is made on the caller's stream right before its view's front is enqueued)
+        pipe.front(views[j], means, quats, scales, opacities, d, sd,
+                   pixel_weights=pwf(ids[j]) if pwf is not None else None)
+
     for j in range(min(pipe.lookahead, len(ids))):
-        pipe.front(views[j], means, quats, scales, opacities, d, sd)
+        front(j)
     probe = None
     for i, v in enumerate(ids):
         if i == 2 and pipe.stats()["overflow"]:
@@ -825,7 +881,7 @@ def _run_labels_pipelined(job: _Job, eng: Engine, depth: int, num_classes: int) 
         if i > 2 and i % OVERFLOW_CHECK_EVERY == 0 and probe is None:
             probe = pipe.stats_async()
         if i + pipe.lookahead < len(ids):
-            pipe.front(views[i + pipe.lookahead], means, quats, scales, opacities, d, sd)
+            front(i + pipe.lookahead)
         pipe.scatter(label_fn(v), F, d, sf, sd, upsample=upsample)
     stats = pipe.stats()
     pipe.release()
@@ -840,7 +896,10 @@ def _run_labels_serial(job: _Job, eng: Engine, num_classes: int) -> Dict[str, in
         view = eng.view(job.vm_host[v], job.K_host, job.width, job.height, **job.camera)
         eng.project(view, *job.gaussians)
         eng.bin_sort(view)
-        eng.blend_weights(view)
+        if job.pixel_weight_fn is not None:
+            eng.blend_weighted(view, job.pixel_weight_fn(v))
+        else:
+            eng.blend_weights(view)
         eng.scatter_labels(view, labels, job.F, job.d, num_classes, job.sf, job.sd, upsample=job.upsample)
         eng.accumulate_stats(accum)
     return Engine.decode_stats(accum)
@@ -856,7 +915,7 @@ def create_label_field(means, quats, scales, opacities, viewmats, K, width: int,
                        label_fn: Callable[[int], torch.Tensor], num_classes: int, *, upsample: Optional[str] = None,
                        views: Optional[Sequence[int]] = None, pipeline: bool = True, gather: bool = True,
                        return_partials: bool = False, camera_model: str = "pinhole", rasterize_mode: str = "classic",
-                       engine: Optional[Engine] = None):
+                       engine: Optional[Engine] = None, pixel_weight_fn: Optional[Callable[[int], torch.Tensor]] = None):
     """Lift per-view integer LABEL maps (a segmenter's class or instance ids, a binary mask) onto the Gaussians: the [N, num_classes]
     field P[g, k] = F[g, k] / d[g] (0 where d[g] == 0) with
         F[g, k] = sum_v sum_p w_g(p) [L_v(p) == k],    d[g] = sum_v sum_p w_g(p),
@@ -869,7 +928,9 @@ def create_label_field(means, quats, scales, opacities, viewmats, K, width: int,
     label_fn(v) -> [height, width] (with upsample="nearest": any [h, w]) integer map on the device: uint8, bool, int16 or int32
     read as stored, int64 narrowed (engine.narrow_labels).
     views, pipeline (True, an int >= 2 workspaces, or False), gather, camera_model, rasterize_mode, engine: as create_feature_field.
-    return_partials: also return (F_rows, d, stats) -- the summed accumulators (this rank's row block of F, all of d)."""
+    return_partials: also return (F_rows, d, stats) -- the summed accumulators (this rank's row block of F, all of d).
+    pixel_weight_fn: v -> c_v, the view's [height, width] weight map (as create_feature_field's): F and d then sum w_g(p) c_v(p),
+    so each row's fractions sum to 1 over the WEIGHTED pixels (pixels of weight 0 count for no class and not in d)."""
     if upsample not in (None, "nearest"):
         raise ValueError(f"upsample must be None or 'nearest' for label maps, got {upsample!r}")
     dist, rank, world = _dist()
@@ -878,7 +939,7 @@ def create_label_field(means, quats, scales, opacities, viewmats, K, width: int,
     job = _Job((means, quats, scales, opacities), F, d, 1.0, 1.0, label_fn,
                list(views) if views is not None else view_shard(viewmats.shape[0], rank, world),
                viewmats.detach().cpu(), K.detach().cpu(), width, height,
-               dict(camera_model=camera_model, rasterize_mode=rasterize_mode), None, upsample)
+               dict(camera_model=camera_model, rasterize_mode=rasterize_mode), None, upsample, pixel_weight_fn)
     pipelined = bool(pipeline) and len(job.view_ids) > 1
     if pipelined and _lib.hw_queues_late():
         warnings.warn("gsbp_amd was imported after the HIP runtime had started: create_label_field runs its views on ONE stream",

@@ -103,6 +103,63 @@ struct FusedArgs { // kFused only
     u32 *pc_queue;              // next tile (index into tile_order) a producer wave takes; zero when the kernel starts
 };
 
+// The weighted kernels (PIXW = true) take BlendArgs<true>, i.e. FusedArgs plus the weight map (PixW, gwbp_dev.h); BlendArgs<false>
+// has FusedArgs' layout byte for byte, so the unweighted instantiations keep their argument block and their code.
+template <bool PIXW>
+struct BlendArgs : FusedArgs {
+};
+template <>
+struct BlendArgs<true> : FusedArgs {
+    PixW pw;
+};
+static_assert(sizeof(BlendArgs<false>) == sizeof(FusedArgs), "the unweighted kernels' argument block must not change");
+
+// c(p) of pixel (min(ix, W - 1), min(iy, H - 1)) -- a clamped address, so that lanes outside the image read inside it; the caller
+// zeroes their weight.  The switch is on a kernel argument (wave-uniform): one branch per tile, not per pair.  GWBP_PIXW_U8 reads
+// any non-zero byte as 1 (0 / 255 masks and bool tensors); the others are values.
+template <int N>
+__device__ __forceinline__ void load_pixel_weights(const PixW &pw, int ix, const int (&iy)[N], int W, int H, float (&c)[N])
+{
+    int64_t off[N];
+    const int64_t xo = (int64_t)min(ix, W - 1) * pw.ws_x;
+#pragma unroll
+    for (int q = 0; q < N; ++q)
+        off[q] = (int64_t)min(iy[q], H - 1) * pw.ws_y + xo;
+    switch (pw.dtype) {
+    case GWBP_PIXW_U8: {
+        const unsigned char *p = static_cast<const unsigned char *>(pw.data);
+#pragma unroll
+        for (int q = 0; q < N; ++q)
+            c[q] = p[off[q]] != 0 ? 1.0f : 0.0f;
+        break;
+    }
+    case GWBP_PIXW_F16: {
+        const unsigned short *p = static_cast<const unsigned short *>(pw.data);
+#pragma unroll
+        for (int q = 0; q < N; ++q)
+            c[q] = MapElem<GWBP_MAP_F16>::cvt(p[off[q]]);
+        break;
+    }
+    case GWBP_PIXW_BF16: {
+        const unsigned short *p = static_cast<const unsigned short *>(pw.data);
+#pragma unroll
+        for (int q = 0; q < N; ++q)
+            c[q] = MapElem<GWBP_MAP_BF16>::cvt(p[off[q]]);
+        break;
+    }
+    default: {
+        const float *p = static_cast<const float *>(pw.data);
+#pragma unroll
+        for (int q = 0; q < N; ++q)
+            c[q] = p[off[q]];
+        break;
+    }
+    }
+#pragma unroll
+    for (int q = 0; q < N; ++q)
+        c[q] = (ix < W && iy[q] < H) ? c[q] : 0.0f;
+}
+
 
 // Sum of 16 per-lane values over the 64 lanes, transposed: lane l returns the wave total of value c(l),
 //   c(l) = bit2(l) | bit3(l) << 1 | bit0(l) << 2 | bit1(l) << 3        (the same in all four rows of 16 lanes).
@@ -313,14 +370,18 @@ __device__ __forceinline__ void encode_quarter(const float *feats, int64_t fs_y,
     }
 }
 
-template <int MODE, int WAVES = 1>
+// PIXW: the pixel-weighted form (gwbp_*_ex with a gwbp_pixel_weights map).  alpha, T and the alpha map are computed exactly as
+// without it; what the blend adds or stores is w c(p) instead of w, and only for pixels with c(p) != 0 (the store mask of a
+// quarter is m_valid & ballot(c != 0), formed once per tile).  Every consumer downstream -- the scatter kernels through the
+// entries, headers and record sums, d, the token-quadrant sums, the fused kernels' register sums -- is thereby weighted.
+template <int MODE, int WAVES = 1, bool PIXW = false>
 __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_blend(ViewDev V, const u32 *__restrict__ tile_offsets,
                                               const u32 *__restrict__ vals, const G2D *__restrict__ g2d,
                                               Counters *__restrict__ ctr, Header *__restrict__ headers,
                                               u32 *__restrict__ hdr_count, WPair *__restrict__ wpool, u32 pair_cap,
                                               u32 *__restrict__ shards, const u32 *__restrict__ tile_order, float *__restrict__ alphas,
                                               int dbg_arg, int prio,
-                                              float *__restrict__ d_out, float scale_d, FusedArgs fu)
+                                              float *__restrict__ d_out, float scale_d, BlendArgs<PIXW> fu)
 {
 #ifdef GWBP_PROFILE
     const int dbg = dbg_arg; // ablation bits (make PROFILE=1 only; results invalid)
@@ -635,6 +696,34 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 8
             out_on = lane < 16 ? my_ch < fu.D : (lane == 16 && d_out != nullptr);
         }
 
+        // PIXW (loaded behind the features: not live across the encoder prologue): the weights c of the lane's four pixels (0 outside the image) and, per quarter, the lanes whose c is non-zero.  With
+        // no alpha map to report, a pixel of weight 0 starts terminated (T = 0): it could add nothing, and a tile without any
+        // weight ends before its first batch.
+        // The fused modes have no four registers to spare (their 64 feature registers fill the 128 a wave may have): they park
+        // the weights in a 1-KB LDS row of the wave and read a quarter's back when a record has an entry there.
+        float cpix[PIXW ? 4 : 1];
+        u64 cnz[PIXW ? 4 : 1];
+        float *s_c = nullptr;
+        if constexpr (PIXW) {
+            int iyq[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                iyq[q] = iy0 + 4 * q;
+            load_pixel_weights(fu.pw, ix, iyq, V.W, V.H, cpix);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                cnz[q] = __ballot(cpix[q] != 0.f);
+                if (!alphas)
+                    T[q] = cpix[q] != 0.f ? T[q] : 0.f;
+            }
+            if constexpr (FUSED) {
+                __shared__ float s_c_[BW][kTilePix];
+                s_c = s_c_[bw];
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    s_c[q * 64 + lane] = cpix[q];
+            }
+        }
         for (u32 batch = beg; batch < end; batch += kBatch) {
             // quarters that still have a live pixel; stop when the whole tile has terminated (gsplat: all threads done)
             u32 alive = 0;
@@ -717,6 +806,14 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 8
                         T[q] = mask_select(m_valid, next_T, T_else);
                         Tout[q] = mask_select(m_valid, next_T, Tout[q]);
                         m[q] = m_valid;
+                        if constexpr (PIXW) { // what is added or stored: w c, at pixels with c != 0 only
+                            // (fused modes: an atomic load, so that the compiler does not hoist the four reads out of the loop
+                            // into the registers this is about)
+                            const float cq = FUSED ? __hip_atomic_load(&s_c[q * 64 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT)
+                                                   : cpix[q];
+                            w[q] = w[q] * cq;
+                            m[q] = m_valid & cnz[q];
+                        }
                     }
                 }
                 if ((m[0] | m[1] | m[2] | m[3]) == 0ull) {
@@ -889,13 +986,13 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 8
 constexpr int kQuarterMaxTiles = 4096;
 constexpr int kQuarterMaxCh = 32;
 
-template <int CH> // 16 or 32 channels held per pixel (D <= CH)
+template <int CH, bool PIXW = false> // 16 or 32 channels held per pixel (D <= CH); PIXW: see k_blend
 __global__ __launch_bounds__(64) void k_blend_scatter_quarter(ViewDev V, const u32 *__restrict__ tile_offsets,
                                                               const u32 *__restrict__ vals, const G2D *__restrict__ g2d,
                                                               Counters *__restrict__ ctr, u32 *__restrict__ hdr_count,
                                                               const u32 *__restrict__ tile_order, float *__restrict__ alphas,
                                                               int dbg_arg, int prio, float *__restrict__ d_out, float scale_d,
-                                                              FusedArgs fu)
+                                                              BlendArgs<PIXW> fu)
 {
 #ifdef GWBP_PROFILE
     const int dbg = dbg_arg; // ablation bits (make PROFILE=1 only; results invalid)
@@ -915,6 +1012,17 @@ __global__ __launch_bounds__(64) void k_blend_scatter_quarter(ViewDev V, const u
     const float px = (float)ix + 0.5f, py = (float)iy + 0.5f;
     const u32 beg = tile_offsets[tile], end = tile_offsets[tile + 1];
     float T = (ix < V.W && iy < V.H) ? 1.0f : 0.0f, Tout = 1.0f;
+    float cpix = 1.0f; // PIXW: the pixel's weight (0 outside the image) and the lanes whose weight is non-zero
+    u64 cnz = ~0ull;
+    if constexpr (PIXW) {
+        float c1[1];
+        const int iy1[1] = {iy};
+        load_pixel_weights(fu.pw, ix, iy1, V.W, V.H, c1);
+        cpix = c1[0];
+        cnz = __ballot(cpix != 0.f);
+        if (!alphas)
+            T = cpix != 0.f ? T : 0.f;
+    }
 
     float f[CH];
     {
@@ -996,12 +1104,17 @@ __global__ __launch_bounds__(64) void k_blend_scatter_quarter(ViewDev V, const u
             const u64 m_ok = __builtin_amdgcn_ballot_w64(sigma >= 0.f) & __builtin_amdgcn_ballot_w64(alpha >= kAlphaMin);
             const u64 m_valid = m_ok & __builtin_amdgcn_ballot_w64(next_T > kTMin);
             const float T_else = mask_select(m_ok, 0.f, T);
-            const float w = alpha * T;
+            float w = alpha * T;
             T = mask_select(m_valid, next_T, T_else);
             Tout = mask_select(m_valid, next_T, Tout);
-            if (m_valid == 0ull)
+            u64 m_st = m_valid; // the lanes that add
+            if constexpr (PIXW) {
+                w = w * cpix;
+                m_st = m_valid & cnz;
+            }
+            if (m_st == 0ull)
                 continue;
-            const float wq = mask_select(m_valid, w, 0.f);
+            const float wq = mask_select(m_st, w, 0.f);
             float p0[16], tot1 = 0.f;
 #pragma unroll
             for (int c = 0; c < 16; ++c)
@@ -1014,7 +1127,7 @@ __global__ __launch_bounds__(64) void k_blend_scatter_quarter(ViewDev V, const u
                     p1[c] = wq * f[16 + c];
                 tot1 = transposed_sum16(p1);
             }
-            if ((m_valid & bad) != 0ull)
+            if ((m_st & bad) != 0ull)
                 tot0 = tot1 = __builtin_nanf("");
             float wl = wq;
             wl += dpp_get<0xB1>(wl);
@@ -1027,7 +1140,7 @@ __global__ __launch_bounds__(64) void k_blend_scatter_quarter(ViewDev V, const u
                 const float val = lane < 16 ? tot0 : (lane < CH ? tot1 : ws);
                 atomicAdd(out_base + (size_t)gid * out_mul, val * out_scale);
             }
-            npairs += (u32)__popcll(m_valid);
+            npairs += (u32)__popcll(m_st);
             ++nrec;
         }
     }
@@ -1092,8 +1205,24 @@ __global__ void k_pool_stats(const u32 *__restrict__ shards, Counters *__restric
     ctr->pool_head = mx * (u32)kShards;
 }
 
+// The argument block of a k_blend / k_blend_scatter_quarter launch: BlendArgs<false> (FusedArgs' layout) without a weight map, the
+// weighted instantiation's BlendArgs<true> with one.
+static BlendArgs<false> plain_args(const FusedArgs &fu)
+{
+    BlendArgs<false> a;
+    static_cast<FusedArgs &>(a) = fu;
+    return a;
+}
+static BlendArgs<true> weighted_args(const FusedArgs &fu, const PixW &pw)
+{
+    BlendArgs<true> a;
+    static_cast<FusedArgs &>(a) = fu;
+    a.pw = pw;
+    return a;
+}
+
 int launch_blend(const Layout &L, const Ws &W, const ViewDev &V, float *alphas, float *d, float scale_d, hipStream_t s,
-                 const FeatMap *M, int D, float scale_f, float *F)
+                 const FeatMap *M, int D, float scale_f, float *F, const PixW *pw)
 {
     const bool fused = M != nullptr;
     FusedArgs fu = {};
@@ -1133,32 +1262,42 @@ int launch_blend(const Layout &L, const Ws &W, const ViewDev &V, float *alphas, 
     // profiling knobs, read once per process (results are invalid when GWBP_ABLATE_BLEND is set)
     const int ablate = profile_knob("GWBP_ABLATE_BLEND");
     const int extra_lds = profile_knob("GWBP_BLEND_LDS"); // experiment knob: pad the workgroup's LDS footprint
+    // one launch of KERNEL (a k_blend or k_blend_scatter_quarter template-id whose last template argument, PIXW, is appended here)
+    // with the argument block that goes with it
+#define GWBP_COMMA ,
+#define GWBP_LAUNCH(KERNEL, GRID, BLOCK, LDS, ...)                                                                          \
+    do {                                                                                                                  \
+        if (pw)                                                                                                           \
+            hipLaunchKernelGGL((KERNEL, true>), GRID, BLOCK, LDS, s, __VA_ARGS__, weighted_args(fu, *pw));                \
+        else                                                                                                              \
+            hipLaunchKernelGGL((KERNEL, false>), GRID, BLOCK, LDS, s, __VA_ARGS__, plain_args(fu));                       \
+    } while (0)
 #define GWBP_BLEND(H)                                                                                                 \
-    hipLaunchKernelGGL(k_blend<H>, dim3(n_tiles), dim3(64), (size_t)extra_lds, s, V, W.tile_offsets, W.vals[fin], W.g2d,  \
-                       W.counters, W.headers, W.hdr_count, W.wpool, (u32)L.pair_cap, W.shards, W.tile_order, alphas,  \
-                       ablate, prio, d, scale_d, fu)
+    GWBP_LAUNCH(k_blend<H GWBP_COMMA 1, dim3(n_tiles), dim3(64), (size_t)extra_lds, V, W.tile_offsets, W.vals[fin], W.g2d, W.counters, \
+                W.headers, W.hdr_count, W.wpool, (u32)L.pair_cap, W.shards, W.tile_order, alphas, ablate, prio, d, scale_d)
     if (fused_enc && (L.flags & GWBP_FLAG_SPLIT_ENCODER)) {
         // producer / consumer form: ONE persistent workgroup per CU (kPcProd encoder waves + blend waves around a ring of encoded
         // tiles in LDS); the tile counter is the first scatter queue word, which gwbp_project's memset left zero
         const size_t lds = (size_t)fu.enc_k * kFusedCh * sizeof(float) + (size_t)kPcRing * kPcTileFloats * sizeof(float) + 64;
         int n_cu = 0;
         int rc = device_cus(&n_cu);
-        if (rc || (rc = ensure_dynamic_lds(reinterpret_cast<const void *>(k_blend<kFusedPC, kPcWaves>),
-                                           kEncMaxK * kFusedCh * 4 + kPcRing * kPcTileFloats * 4 + 64, 14)))
+        const int lds_max = kEncMaxK * kFusedCh * 4 + kPcRing * kPcTileFloats * 4 + 64;
+        if (rc || (rc = pw ? ensure_dynamic_lds(reinterpret_cast<const void *>(k_blend<kFusedPC, kPcWaves, true>), lds_max, 15)
+                           : ensure_dynamic_lds(reinterpret_cast<const void *>(k_blend<kFusedPC, kPcWaves, false>), lds_max, 14)))
             return rc;
         fu.pc_queue = W.shards + kShards * 16;
-        hipLaunchKernelGGL((k_blend<kFusedPC, kPcWaves>), dim3(n_cu), dim3(64 * kPcWaves), lds, s, V, W.tile_offsets, W.vals[fin],
-                           W.g2d, W.counters, W.headers, W.hdr_count, W.wpool, (u32)L.pair_cap, W.shards, W.tile_order, alphas,
-                           ablate, prio, d, scale_d, fu);
+        GWBP_LAUNCH(k_blend<kFusedPC GWBP_COMMA kPcWaves, dim3(n_cu), dim3(64 * kPcWaves), lds, V, W.tile_offsets, W.vals[fin], W.g2d,
+                    W.counters, W.headers, W.hdr_count, W.wpool, (u32)L.pair_cap, W.shards, W.tile_order, alphas, ablate, prio, d,
+                    scale_d);
     } else if (fused_enc) {
         const size_t lds = (size_t)fu.enc_k * kFusedCh * sizeof(float);
-        hipLaunchKernelGGL((k_blend<kFusedEnc, kEncWaves>), dim3((n_tiles + kEncWaves - 1) / kEncWaves), dim3(64 * kEncWaves), lds, s,
-                           V, W.tile_offsets, W.vals[fin], W.g2d, W.counters, W.headers, W.hdr_count, W.wpool, (u32)L.pair_cap,
-                           W.shards, W.tile_order, alphas, ablate, prio, d, scale_d, fu);
+        GWBP_LAUNCH(k_blend<kFusedEnc GWBP_COMMA kEncWaves, dim3((n_tiles + kEncWaves - 1) / kEncWaves), dim3(64 * kEncWaves), lds, V,
+                    W.tile_offsets, W.vals[fin], W.g2d, W.counters, W.headers, W.hdr_count, W.wpool, (u32)L.pair_cap, W.shards,
+                    W.tile_order, alphas, ablate, prio, d, scale_d);
     } else if (fused && n_tiles <= kQuarterMaxTiles) {
 #define GWBP_QUARTER(C)                                                                                               \
-    hipLaunchKernelGGL(k_blend_scatter_quarter<C>, dim3(4 * n_tiles), dim3(64), 0, s, V, W.tile_offsets, W.vals[fin], W.g2d, \
-                       W.counters, W.hdr_count, W.tile_order, alphas, ablate, prio, d, scale_d, fu)
+    GWBP_LAUNCH(k_blend_scatter_quarter<C, dim3(4 * n_tiles), dim3(64), 0, V, W.tile_offsets, W.vals[fin], W.g2d, W.counters, \
+                W.hdr_count, W.tile_order, alphas, ablate, prio, d, scale_d)
         if (D <= 16)
             GWBP_QUARTER(16);
         else
@@ -1171,6 +1310,8 @@ int launch_blend(const Layout &L, const Ws &W, const ViewDev &V, float *alphas, 
     else
         GWBP_BLEND(kHalves);
 #undef GWBP_BLEND
+#undef GWBP_LAUNCH
+#undef GWBP_COMMA
     if (!fused)
         hipLaunchKernelGGL(k_pool_stats, dim3(1), dim3(1), 0, s, W.shards, W.counters,
                            (L.flags & GWBP_FLAG_NARROW_SCATTER) ? 0u : kBlendHalves);
@@ -1178,9 +1319,10 @@ int launch_blend(const Layout &L, const Ws &W, const ViewDev &V, float *alphas, 
 }
 
 // gwbp_blend_tokens: the blend whose product is the per-(Gaussian, tile) token-quadrant weight sums (k_blend<kToken>) in the
-// workspace's header region (16 of its 64 B per intersection), zeroed for this view's intersections first.
+// workspace's header region (16 of its 64 B per intersection), zeroed for this view's intersections first -- so a record that a
+// weight map left without weight (no line written) reads as zero in k_token_apply.
 int launch_blend_tokens(const Layout &L, const Ws &W, const ViewDev &V, float *alphas, const int32_t *ymap, const int32_t *xmap,
-                        hipStream_t s)
+                        hipStream_t s, const PixW *pw)
 {
     if (!ymap || !xmap)
         return set_error(GWBP_EINVAL, "gwbp_blend_tokens needs both index maps");
@@ -1193,8 +1335,14 @@ int launch_blend_tokens(const Layout &L, const Ws &W, const ViewDev &V, float *a
     const int n_tiles = V.tile_w * V.tile_h;
     const int fin = sort_passes(n_tiles) & 1;
     const int ablate = profile_knob("GWBP_ABLATE_BLEND");
-    hipLaunchKernelGGL(k_blend<kToken>, dim3(n_tiles), dim3(64), 0, s, V, W.tile_offsets, W.vals[fin], W.g2d, W.counters, W.headers,
-                       W.hdr_count, W.wpool, (u32)L.pair_cap, W.shards, W.tile_order, alphas, ablate, prio, nullptr, 0.f, fu);
+    if (pw)
+        hipLaunchKernelGGL((k_blend<kToken, 1, true>), dim3(n_tiles), dim3(64), 0, s, V, W.tile_offsets, W.vals[fin], W.g2d,
+                           W.counters, W.headers, W.hdr_count, W.wpool, (u32)L.pair_cap, W.shards, W.tile_order, alphas, ablate,
+                           prio, nullptr, 0.f, weighted_args(fu, *pw));
+    else
+        hipLaunchKernelGGL((k_blend<kToken, 1, false>), dim3(n_tiles), dim3(64), 0, s, V, W.tile_offsets, W.vals[fin], W.g2d,
+                           W.counters, W.headers, W.hdr_count, W.wpool, (u32)L.pair_cap, W.shards, W.tile_order, alphas, ablate,
+                           prio, nullptr, 0.f, plain_args(fu));
     return check_hip(hipGetLastError(), "blend_tokens launch");
 }
 

@@ -218,9 +218,29 @@ static int check_feats(const float *feats, int64_t fs_y, int64_t fs_x, int64_t f
     return GWBP_OK;
 }
 
+// gwbp_pixel_weights -> PixW; NULL -> no map.  Checked before anything else of an _ex call.
+static int check_pixel_weights(const gwbp_pixel_weights *pw, PixW *out, const PixW **use)
+{
+    *use = nullptr;
+    if (!pw)
+        return GWBP_OK;
+    if (pw->dtype != GWBP_PIXW_F32 && pw->dtype != GWBP_PIXW_F16 && pw->dtype != GWBP_PIXW_BF16 && pw->dtype != GWBP_PIXW_U8)
+        return set_error(GWBP_EINVAL, "unknown pixel weight type %d", (int)pw->dtype);
+    if (!pw->data)
+        return set_error(GWBP_EINVAL, "null pixel weight map");
+    if (pw->ws_y < 0 || pw->ws_x < 0)
+        return set_error(GWBP_EINVAL, "negative pixel weight strides (%lld %lld)", (long long)pw->ws_y, (long long)pw->ws_x);
+    if (pw->reserved != 0)
+        return set_error(GWBP_EINVAL, "gwbp_pixel_weights.reserved must be 0 (got %d)", (int)pw->reserved);
+    out->data = pw->data, out->ws_y = pw->ws_y, out->ws_x = pw->ws_x, out->dtype = pw->dtype;
+    *use = out;
+    return GWBP_OK;
+}
+
 } // namespace gwbp
 
 using namespace gwbp;
+static_assert(sizeof(gwbp_pixel_weights) == 32, "gwbp_pixel_weights is part of the ABI");
 
 extern "C" {
 
@@ -297,58 +317,103 @@ int gwbp_bin_sort(const gwbp_caps *caps, void *workspace, size_t workspace_bytes
 int gwbp_blend_weights(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
                        float *alphas, void *stream)
 {
+    return gwbp_blend_weights_ex(caps, workspace, workspace_bytes, view_host, alphas, nullptr, stream);
+}
+
+int gwbp_blend_weights_ex(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                          float *alphas, const gwbp_pixel_weights *pixel_weights, void *stream)
+{
+    PixW P;
+    const PixW *pw;
+    int rc = check_pixel_weights(pixel_weights, &P, &pw);
+    if (rc)
+        return rc;
     Layout L;
     Ws W;
     ViewDev V;
-    int rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W);
-    if (rc)
+    if ((rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W)))
         return rc;
     if ((rc = make_view(view_host, caps, &V)))
         return rc;
-    return launch_blend(L, W, V, alphas, nullptr, 0.f, static_cast<hipStream_t>(stream));
+    return launch_blend(L, W, V, alphas, nullptr, 0.f, static_cast<hipStream_t>(stream), nullptr, 0, 1.0f, nullptr, pw);
 }
 
 int gwbp_blend_weights_d(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
                          float *alphas, float scale_d, float *d, void *stream)
 {
+    return gwbp_blend_weights_d_ex(caps, workspace, workspace_bytes, view_host, alphas, scale_d, d, nullptr, stream);
+}
+
+int gwbp_blend_weights_d_ex(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                            float *alphas, float scale_d, float *d, const gwbp_pixel_weights *pixel_weights, void *stream)
+{
+    PixW P;
+    const PixW *pw;
+    int rc = check_pixel_weights(pixel_weights, &P, &pw);
+    if (rc)
+        return rc;
     Layout L;
     Ws W;
     ViewDev V;
-    int rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W);
-    if (rc)
+    if ((rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W)))
         return rc;
     if ((rc = make_view(view_host, caps, &V)))
         return rc;
     if (!d)
         return set_error(GWBP_EINVAL, "null d");
-    return launch_blend(L, W, V, alphas, d, scale_d, static_cast<hipStream_t>(stream));
+    return launch_blend(L, W, V, alphas, d, scale_d, static_cast<hipStream_t>(stream), nullptr, 0, 1.0f, nullptr, pw);
 }
 
 int gwbp_blend_scatter(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
                        const float *feats, int64_t fs_y, int64_t fs_x, int32_t D, float scale_f, float scale_d, float *F,
                        float *d, float *alphas, void *stream)
 {
+    return gwbp_blend_scatter_ex(caps, workspace, workspace_bytes, view_host, feats, fs_y, fs_x, D, scale_f, scale_d, F, d, alphas,
+                                 nullptr, stream);
+}
+
+int gwbp_blend_scatter_ex(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                          const float *feats, int64_t fs_y, int64_t fs_x, int32_t D, float scale_f, float scale_d, float *F,
+                          float *d, float *alphas, const gwbp_pixel_weights *pixel_weights, void *stream)
+{
+    PixW P;
+    const PixW *pw;
+    int rc = check_pixel_weights(pixel_weights, &P, &pw);
+    if (rc)
+        return rc;
     Layout L;
     Ws W;
     ViewDev V;
-    int rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W);
-    if (rc)
+    if ((rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W)))
         return rc;
     if ((rc = make_view(view_host, caps, &V)))
         return rc;
     const FeatMap M{feats, fs_y, fs_x, 1, nullptr, nullptr, nullptr, nullptr, 0, 0};
-    return launch_blend(L, W, V, alphas, d, scale_d, static_cast<hipStream_t>(stream), &M, D, scale_f, F);
+    return launch_blend(L, W, V, alphas, d, scale_d, static_cast<hipStream_t>(stream), &M, D, scale_f, F, pw);
 }
 
 int gwbp_blend_scatter_encoded(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
                                const float *feats, int64_t fs_y, int64_t fs_x, int32_t K, const float *encoder, int32_t n_out,
                                float scale_f, float scale_d, float *F, float *d, float *alphas, void *stream)
 {
+    return gwbp_blend_scatter_encoded_ex(caps, workspace, workspace_bytes, view_host, feats, fs_y, fs_x, K, encoder, n_out, scale_f,
+                                         scale_d, F, d, alphas, nullptr, stream);
+}
+
+int gwbp_blend_scatter_encoded_ex(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                                  const float *feats, int64_t fs_y, int64_t fs_x, int32_t K, const float *encoder, int32_t n_out,
+                                  float scale_f, float scale_d, float *F, float *d, float *alphas,
+                                  const gwbp_pixel_weights *pixel_weights, void *stream)
+{
+    PixW P;
+    const PixW *pw;
+    int rc = check_pixel_weights(pixel_weights, &P, &pw);
+    if (rc)
+        return rc;
     Layout L;
     Ws W;
     ViewDev V;
-    int rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W);
-    if (rc)
+    if ((rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W)))
         return rc;
     if ((rc = make_view(view_host, caps, &V)))
         return rc;
@@ -356,21 +421,32 @@ int gwbp_blend_scatter_encoded(const gwbp_caps *caps, void *workspace, size_t wo
         return set_error(GWBP_EINVAL, "null encoder");
     FeatMap M{feats, fs_y, fs_x, 1, nullptr, nullptr, nullptr, nullptr, 0, 0};
     M.enc = encoder, M.enc_k = K;
-    return launch_blend(L, W, V, alphas, d, scale_d, static_cast<hipStream_t>(stream), &M, n_out, scale_f, F);
+    return launch_blend(L, W, V, alphas, d, scale_d, static_cast<hipStream_t>(stream), &M, n_out, scale_f, F, pw);
 }
 
 int gwbp_blend_tokens(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
                       const int32_t *ymap, const int32_t *xmap, float *alphas, void *stream)
 {
+    return gwbp_blend_tokens_ex(caps, workspace, workspace_bytes, view_host, ymap, xmap, alphas, nullptr, stream);
+}
+
+int gwbp_blend_tokens_ex(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                         const int32_t *ymap, const int32_t *xmap, float *alphas, const gwbp_pixel_weights *pixel_weights,
+                         void *stream)
+{
+    PixW P;
+    const PixW *pw;
+    int rc = check_pixel_weights(pixel_weights, &P, &pw);
+    if (rc)
+        return rc;
     Layout L;
     Ws W;
     ViewDev V;
-    int rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W);
-    if (rc)
+    if ((rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W)))
         return rc;
     if ((rc = make_view(view_host, caps, &V)))
         return rc;
-    return launch_blend_tokens(L, W, V, alphas, ymap, xmap, static_cast<hipStream_t>(stream));
+    return launch_blend_tokens(L, W, V, alphas, ymap, xmap, static_cast<hipStream_t>(stream), pw);
 }
 
 int gwbp_scatter_tokens(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,

@@ -159,12 +159,20 @@ int launch_emit_scanned(const Layout &L, const Ws &W, const ViewDev &V, const u3
 int launch_bin_sort(const Layout &L, const Ws &W, const ViewDev &V, int64_t *isect_ids, int32_t *flatten_ids,
                     int32_t *tile_offsets, hipStream_t s);
 struct FeatMap;
-// M != nullptr: the fused small-D form (gwbp_blend_scatter): F[gid, :D] and d are accumulated by the blend itself
+// Per-pixel weight map of the gwbp_*_ex entry points (a validated gwbp_pixel_weights): c(x, y) = data[y * ws_y + x * ws_x], strides
+// in elements, element type dtype (GWBP_PIXW_*).
+struct PixW {
+    const void *data;
+    int64_t ws_y, ws_x;
+    int dtype;
+};
+// M != nullptr: the fused small-D form (gwbp_blend_scatter): F[gid, :D] and d are accumulated by the blend itself.
+// pw != nullptr: every blend form weighted by the map (what it adds or stores is w c(p)).
 int launch_blend(const Layout &L, const Ws &W, const ViewDev &V, float *alphas, float *d, float scale_d, hipStream_t s,
-                 const FeatMap *M = nullptr, int D = 0, float scale_f = 1.0f, float *F = nullptr);
+                 const FeatMap *M = nullptr, int D = 0, float scale_f = 1.0f, float *F = nullptr, const PixW *pw = nullptr);
 // token-space path of a nearest-upsampled low-resolution map (blend.hip: k_blend<kToken>; token.hip)
 int launch_blend_tokens(const Layout &L, const Ws &W, const ViewDev &V, float *alphas, const int32_t *ymap, const int32_t *xmap,
-                        hipStream_t s);
+                        hipStream_t s, const PixW *pw = nullptr);
 int launch_zero_omega(const Layout &L, const Ws &W, hipStream_t s);
 int launch_token_apply(const Layout &L, const Ws &W, const ViewDev &V, const float *tokens, int64_t ts_y, int64_t ts_x, int D,
                        const int32_t *ymap, const int32_t *xmap, float scale_f, float scale_d, float *F, float *d, hipStream_t s);

@@ -48,6 +48,12 @@ def bilinear_index(n_in: int, n_out: int):
 LABEL_TYPES = {torch.uint8: _lib.LABEL_U8, torch.bool: _lib.LABEL_U8, torch.int16: _lib.LABEL_I16, torch.int32: _lib.LABEL_I32}
 
 
+# per-pixel weight-map element types the _ex blends read natively (GWBP_PIXW_*); a bool mask is read as its uint8 bytes, and
+# GWBP_PIXW_U8 counts any non-zero byte as 1
+PIXEL_WEIGHT_TYPES = {torch.float32: _lib.PIXW_F32, torch.float16: _lib.PIXW_F16, torch.bfloat16: _lib.PIXW_BF16,
+                      torch.uint8: _lib.PIXW_U8, torch.bool: _lib.PIXW_U8}
+
+
 def narrow_labels(labels: torch.Tensor, num_classes: int) -> torch.Tensor:
     """An int64 label map as the int32 map gwbp_scatter_labels reads: every id outside [0, num_classes) becomes -1 (ignored)
     BEFORE the narrowing, so that no wide id can wrap into range."""
@@ -254,6 +260,97 @@ class Engine:
                        self._stream())
             return alphas
         self._call("gwbp_blend_weights", *self._args(), C.byref(view), ptr(alphas), self._stream())
+        return alphas
+
+    # ---- per-pixel weight maps (masks, confidences): the _ex blends ---------------------------------------------------
+    def pixel_weights(self, c: torch.Tensor, view) -> _lib.PixelWeights:
+        """The gwbp_pixel_weights of a [view.height, view.width] weight map on this engine's device: bool, uint8 (non-zero = 1),
+        float16, bfloat16 or float32, any non-negative strides (a channel of an [H, W, C] tensor works).  Raises GwbpError on
+        anything else.  The returned struct points into `c`: keep `c` alive until the blend that reads it has run."""
+        if not torch.is_tensor(c):
+            raise GwbpError(f"pixel weights must be a tensor, got {type(c).__name__}")
+        if c.dtype not in PIXEL_WEIGHT_TYPES:
+            raise GwbpError(f"pixel weights must be bool, uint8, float16, bfloat16 or float32, got {c.dtype}")
+        if not c.is_cuda or c.device.index != self._dev_index:
+            raise GwbpError(f"pixel weights must be on the engine's device cuda:{self._dev_index}, got {c.device}")
+        if tuple(c.shape) != (view.height, view.width):
+            raise GwbpError(f"pixel weights must be [H,W] = [{view.height},{view.width}], got {tuple(c.shape)}")
+        if min(c.stride()) < 0:
+            raise GwbpError("negative pixel-weight strides are not supported")
+        pw = _lib.PixelWeights()
+        pw.data = c.data_ptr() or None
+        pw.ws_y, pw.ws_x = c.stride()
+        pw.dtype = PIXEL_WEIGHT_TYPES[c.dtype]
+        pw.reserved = 0
+        return pw
+
+    def blend_weighted(self, view, pixel_weights: torch.Tensor, want_alphas=False, d=None, scale_d=1.0):
+        """blend_weights with a per-pixel weight map c (gwbp_blend_weights_ex / _d_ex): the store holds w c(p) for the pixels with
+        c(p) != 0 only, so every scatter of the view (scatter, scatter_labels, accumulate_d, ...) adds
+        F[g] += scale_f sum_p w_g(p) c(p) f(p), d[g] += scale_d sum_p w_g(p) c(p).  The alpha map is the unweighted one."""
+        pw = self.pixel_weights(pixel_weights, view)
+        alphas = torch.empty(view.height, view.width, device=self.device) if want_alphas else None
+        self._tokens = None
+        self._halves = self._wide_requested()
+        if d is not None:
+            if d.dtype != torch.float32 or not d.is_cuda or d.shape != (self.n,) or not d.is_contiguous():
+                raise GwbpError("d must be a contiguous float32 HIP tensor [N]")
+            if not self._halves:
+                raise GwbpError("blend_weighted(d=...) needs the 256-channel scatter kernel enabled "
+                                "(set_narrow_scatter(False)): a narrow blend takes no weight sums")
+            self._call("gwbp_blend_weights_d_ex", *self._args(), C.byref(view), ptr(alphas), C.c_float(scale_d), ptr(d),
+                       C.byref(pw), self._stream())
+            return alphas
+        self._call("gwbp_blend_weights_ex", *self._args(), C.byref(view), ptr(alphas), C.byref(pw), self._stream())
+        return alphas
+
+    def blend_tokens_weighted(self, view, lr_h: int, lr_w: int, pixel_weights: torch.Tensor, want_alphas=False):
+        """blend_tokens with a per-pixel weight map (gwbp_blend_tokens_ex): the token-quadrant sums are sums of w c(p)."""
+        pw = self.pixel_weights(pixel_weights, view)
+        if not self.token_geometry_ok(lr_h, lr_w, view.height, view.width):
+            raise GwbpError(f"blend_tokens_weighted: a {lr_h}x{lr_w} map has texels narrower than a tile at "
+                            f"{view.height}x{view.width}; use blend_weighted + scatter(upsample='nearest')")
+        ymap, xmap = self.nearest_maps(lr_h, lr_w, view.height, view.width)
+        alphas = torch.empty(view.height, view.width, device=self.device) if want_alphas else None
+        self._halves = False
+        self._tokens = (int(lr_h), int(lr_w))
+        self._call("gwbp_blend_tokens_ex", *self._args(), C.byref(view), ptr(ymap), ptr(xmap), ptr(alphas), C.byref(pw),
+                   self._stream())
+        return alphas
+
+    def blend_scatter_weighted(self, view, feats, pixel_weights: torch.Tensor, F, d, scale_f=1.0, scale_d=1.0, want_alphas=False):
+        """blend_scatter with a per-pixel weight map (gwbp_blend_scatter_ex)."""
+        pw = self.pixel_weights(pixel_weights, view)
+        if not self.can_blend_scatter(feats):
+            raise GwbpError(f"blend_scatter_weighted: [H,W,D] map with unit channel stride and D <= "
+                            f"{self.fused_max_dim(view.width, view.height)} required, got {tuple(feats.shape)}")
+        feats = self._widen(feats)
+        sy, sx, _, D = self._feat_strides(feats, view)
+        self._check_acc(F, d, D)
+        alphas = torch.empty(view.height, view.width, device=self.device) if want_alphas else None
+        self._halves, self._tokens = False, None
+        self._call("gwbp_blend_scatter_ex", *self._args(), C.byref(view), ptr(feats), sy, sx, D, C.c_float(scale_f),
+                   C.c_float(scale_d), ptr(F), ptr(d), ptr(alphas), C.byref(pw), self._stream())
+        return alphas
+
+    def blend_scatter_encoded_weighted(self, view, feats, encoder, pixel_weights: torch.Tensor, F, d, scale_f=1.0, scale_d=1.0,
+                                       want_alphas=False):
+        """blend_scatter_encoded with a per-pixel weight map (gwbp_blend_scatter_encoded_ex)."""
+        pw = self.pixel_weights(pixel_weights, view)
+        if not self.can_blend_scatter_encoded(feats, encoder):
+            raise GwbpError("blend_scatter_encoded_weighted: [H,W,K] channel-contiguous 16-B aligned map, K % 16 == 0, "
+                            f"16 <= K <= 512, <= 16 outputs required, got {tuple(feats.shape)} @ {tuple(encoder.shape)}")
+        if feats.shape[0] != view.height or feats.shape[1] != view.width:
+            raise GwbpError(f"feature map must be [{view.height},{view.width},K], got {tuple(feats.shape)}")
+        feats = self._widen(feats)
+        sy, sx, _ = feats.stride()
+        K, n = encoder.shape
+        self._check_acc(F, d, n)
+        enc = encoder.contiguous()
+        alphas = torch.empty(view.height, view.width, device=self.device) if want_alphas else None
+        self._halves, self._tokens = False, None
+        self._call("gwbp_blend_scatter_encoded_ex", *self._args(), C.byref(view), ptr(feats), sy, sx, K, ptr(enc), n,
+                   C.c_float(scale_f), C.c_float(scale_d), ptr(F), ptr(d), ptr(alphas), C.byref(pw), self._stream())
         return alphas
 
     FUSED_MAX_DIM = 16         # gwbp_blend_scatter holds 4 pixels x 16 channels per lane in registers ...

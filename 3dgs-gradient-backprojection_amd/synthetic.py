@@ -167,6 +167,33 @@ def make_label_map(cfg: Config, view: int, num_classes: int, device="cpu", n_see
     return out
 
 
+PIXEL_WEIGHT_SEED0 = 30000
+
+
+def make_pixel_weights(cfg: Config, view: int, device="cpu", kind: str = "mask", border: float = 0.05,
+                       n_seeds: int = 40) -> torch.Tensor:
+    """[H,W] per-pixel weight map of view `view` (seed 30000 + view) for create_feature_field(pixel_weight_fn=...): a band of
+    `border` x the smaller side along the image edges (an undistortion border) and one of the Voronoi cells of `n_seeds` random
+    points (a transient) are 0, everything else 1.  kind="mask": bool; kind="confidence": float32, the mask times a uniform
+    random value in [0.25, 1) per pixel."""
+    h, w = cfg.height, cfg.width
+    g = torch.Generator(device="cpu").manual_seed(PIXEL_WEIGHT_SEED0 + view)
+    b = int(border * min(h, w))
+    keep = torch.zeros(h, w, dtype=torch.bool)
+    keep[b:h - b, b:w - b] = True
+    pts = torch.rand(n_seeds, 2, generator=g) * torch.tensor([float(h), float(w)])
+    ys = torch.arange(h, dtype=torch.float32)[:, None, None] + 0.5
+    xs = torch.arange(w, dtype=torch.float32)[None, :, None] + 0.5
+    cell = ((ys - pts[:, 0]) ** 2 + (xs - pts[:, 1]) ** 2).argmin(dim=-1)
+    keep &= cell != int(torch.randint(0, n_seeds, (1,), generator=g))
+    if kind == "mask":
+        return keep.to(device)
+    if kind != "confidence":
+        raise ValueError(f"kind must be 'mask' or 'confidence', got {kind!r}")
+    conf = 0.25 + 0.75 * torch.rand(h, w, generator=g)
+    return (conf * keep).to(device)
+
+
 def upsample_map(cfg: Config, low: torch.Tensor) -> torch.Tensor:
     """The reference's own upsampling of a network map to the view ([h,w,D] -> [H,W,D]): F.interpolate(mode=cfg.upsample)
     (backproject.py:110-112 bilinear, align_corners=False; :244-248 nearest).  Used by checks and the CPU baseline, which

@@ -215,6 +215,44 @@ GWBP_API int gwbp_scatter_tokens(const gwbp_caps *caps, void *workspace, size_t 
                                  const float *tokens, int64_t ts_y, int64_t ts_x, int32_t D, const int32_t *ymap,
                                  const int32_t *xmap, float scale_f, float scale_d, float *F, float *d, void *stream);
 
+/* ---- per-pixel weight maps (masks, confidences) ----------------------------------------------------------------
+ * The _ex forms of the five blends take a map c(p) >= 0 at the view's resolution and weight what the view adds by it:
+ *     F[g] += scale_f * sum_p w_g(p) c(p) f(p),     d[g] += scale_d * sum_p w_g(p) c(p)
+ * -- the reference's per-view loop (backproject.py:115-151) with both of its targets multiplied by c.  The blend computes alpha
+ * and T exactly as without a map (the alpha map is unchanged); what it adds or stores is w c(p), for pixels with c(p) != 0 only:
+ * a pixel of weight 0 has no entry in the weight store, and a (Gaussian, tile) record left without one has no header.  Every
+ * consumer of the blend (gwbp_scatter and its upsampled / bilinear / typed / encoded forms, gwbp_scatter_labels,
+ * gwbp_accumulate_d, gwbp_scatter_tokens) is thereby weighted with no argument of its own.
+ * Element (x, y) of the map is data[y * ws_y + x * ws_x] (strides in ELEMENTS, >= 0: a channel of an [H, W, C] tensor works).
+ * GWBP_PIXW_U8 reads any non-zero byte as 1 (0 / 255 masks, bool tensors); the other types are values (negative or non-finite
+ * values are carried through linearly / undefined).  reserved must be 0.  pixel_weights == NULL is the unweighted function, bit
+ * for bit; the unweighted functions are these with NULL.  An unknown dtype, a NULL data, a negative stride or a non-zero reserved
+ * returns GWBP_EINVAL before anything else is looked at. */
+#define GWBP_PIXW_F32 0  /* float32 */
+#define GWBP_PIXW_F16 1  /* IEEE binary16 */
+#define GWBP_PIXW_BF16 2 /* bfloat16 */
+#define GWBP_PIXW_U8 3   /* uint8 / bool: 0 or 1 */
+typedef struct gwbp_pixel_weights {
+    const void *data; /* device */
+    int64_t ws_y, ws_x;
+    int32_t dtype;    /* GWBP_PIXW_* */
+    int32_t reserved; /* 0 */
+} gwbp_pixel_weights;  /* 32 B */
+GWBP_API int gwbp_blend_weights_ex(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                                   float *alphas, const gwbp_pixel_weights *pixel_weights, void *stream);
+GWBP_API int gwbp_blend_weights_d_ex(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                                     float *alphas, float scale_d, float *d, const gwbp_pixel_weights *pixel_weights, void *stream);
+GWBP_API int gwbp_blend_tokens_ex(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                                  const int32_t *ymap, const int32_t *xmap, float *alphas, const gwbp_pixel_weights *pixel_weights,
+                                  void *stream);
+GWBP_API int gwbp_blend_scatter_ex(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                                   const float *feats, int64_t fs_y, int64_t fs_x, int32_t D, float scale_f, float scale_d,
+                                   float *F, float *d, float *alphas, const gwbp_pixel_weights *pixel_weights, void *stream);
+GWBP_API int gwbp_blend_scatter_encoded_ex(const gwbp_caps *caps, void *workspace, size_t workspace_bytes,
+                                           const gwbp_view *view_host, const float *feats, int64_t fs_y, int64_t fs_x, int32_t K,
+                                           const float *encoder, int32_t n_out, float scale_f, float scale_d, float *F, float *d,
+                                           float *alphas, const gwbp_pixel_weights *pixel_weights, void *stream);
+
 /* d[g] += scale_d * sum_p w_g(p) alone, from the per-record weight sums gwbp_blend_weights left in the workspace
  * (needs a blend WITHOUT GWBP_FLAG_NARROW_SCATTER).  A caller that overlaps the front stage of view v+1 with the
  * scatter of view v issues it behind the blend on the front's stream and passes d = NULL to gwbp_scatter: the

@@ -45,6 +45,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--num-classes", type=int, default=None,
                     help="number of classes K of --label-maps (ids outside [0, K) are ignored); with --synthetic: use seeded "
                          "piecewise-constant (Voronoi) label maps with K classes instead of feature maps")
+    ap.add_argument("--pixel-weights", default=None, metavar="DIR",
+                    help="directory with <image name>.pt per-pixel weight maps [H,W] at the view's resolution (bool, uint8 with "
+                         "non-zero = 1, float16, bfloat16 or float32): which pixels count and how much, for feature and label "
+                         "maps alike.  With --synthetic: 'mask' or 'confidence' for the seeded maps of synthetic.make_pixel_weights")
     ap.add_argument("--encoder", default=None, help="[512,16] encoder tensor (.pt): backproject_compressed.py")
     ap.add_argument("--synthetic", default=None, help="run a seeded synthetic config (C1, C2, ...) instead of files")
     ap.add_argument("--no-prune", action="store_true",
@@ -95,6 +99,17 @@ def load_label_map(label_dir: str, image_name: str) -> torch.Tensor:
     return lab
 
 
+def load_pixel_weights(weight_dir: str, image_name: str, H: int, W: int) -> torch.Tensor:
+    """<weight_dir>/<image name>.pt: an [H, W] weight map of a type the weighted blend reads."""
+    c = torch.load(os.path.join(weight_dir, image_name + ".pt"))
+    ok = (torch.float32, torch.float16, torch.bfloat16, torch.uint8, torch.bool)
+    if not torch.is_tensor(c) or c.dtype not in ok or tuple(c.shape) != (H, W):
+        raise SystemExit(f"{image_name}.pt in {weight_dir}: an [{H},{W}] bool / uint8 / float16 / bfloat16 / float32 weight map is "
+                         f"required, got {c.dtype if torch.is_tensor(c) else type(c).__name__}"
+                         f"{' ' + str(tuple(c.shape)) if torch.is_tensor(c) else ''}")
+    return c
+
+
 def main(argv=None):
     ap = build_parser()
     args = ap.parse_args(argv)
@@ -135,6 +150,13 @@ def main(argv=None):
         def label_fn(v):
             return syn.make_label_map(cfg, v, args.num_classes, device=dev)
         label_upsample = None
+        pixel_weight_fn = None
+        if args.pixel_weights:
+            if args.pixel_weights not in ("mask", "confidence"):
+                raise SystemExit("--pixel-weights with --synthetic takes 'mask' or 'confidence'")
+
+            def pixel_weight_fn(v):
+                return syn.make_pixel_weights(cfg, v, device=dev, kind=args.pixel_weights)
     else:
         splats = scene_io.load_checkpoint(args.checkpoint, args.data_dir, format=args.format,
                                           data_factor=args.data_factor, rasterizer=args.rasterizer)
@@ -163,6 +185,10 @@ def main(argv=None):
         # A map at the network's resolution is upsampled the way the reference does it -- bilinear for lseg (backproject.py:110-112),
         # nearest for dino's patch tokens (:244-248) -- INSIDE the kernels (dino maps whose tokens cover a tile: token space); with an
         # encoder the map is materialised first (the encoder-fused kernels read full-resolution pixels)
+        pixel_weight_fn = None
+        if args.pixel_weights:
+            def pixel_weight_fn(v):
+                return load_pixel_weights(args.pixel_weights, images[v].name, H, W).to(dev)
         mode = "nearest" if args.feature == "dino" else "bilinear"
         upsample = mode if (first is not None and tuple(first.shape[:2]) != (H, W) and encoder is None) else None
         reduction = "mean" if args.feature == "dino" else "sum"  # backproject.py:263,283 vs :127,145
@@ -208,11 +234,12 @@ def main(argv=None):
         # the same prune step, then the [N_kept, K] class fractions of every Gaussian's blend weight (label_field.pt)
         out, F, d, stats = gsbp_amd.create_label_field(means, quats, scales, opac, viewmats, K, W, H, label_fn,
                                                        args.num_classes, upsample=label_upsample, return_partials=True,
-                                                       **cam_kw)
+                                                       pixel_weight_fn=pixel_weight_fn, **cam_kw)
     else:
         out, F, d, stats = gsbp_amd.create_feature_field(means, quats, scales, opac, viewmats, K, W, H, feature_fn, dim,
                                                          reduction=reduction, encoder=encoder, return_partials=True,
-                                                         verbose=True, upsample=upsample, **cam_kw)
+                                                         verbose=True, upsample=upsample, pixel_weight_fn=pixel_weight_fn,
+                                                         **cam_kw)
     if args.prune_by_product and not args.no_prune:
         # "the mask comes free from the fused kernel" -- d is the all-reduced denominator of every Gaussian,
         # identical on every rank
