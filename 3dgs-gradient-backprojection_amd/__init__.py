@@ -4,10 +4,11 @@ JojiJoseph/3dgs-gradient-backprojection), hand-written HIP kernels behind a C AB
     from gsbp_amd import rasterization            # drop-in for `from gsplat import rasterization`
     from gsbp_amd import create_feature_field     # fused counterpart of create_feature_field_lseg/_dino
     from gsbp_amd import create_label_field       # integer label maps -> per-Gaussian class weights
+    from gsbp_amd import create_mask_feature_field  # mask maps + one embedding per mask -> feature field
 """
 from . import synthetic  # noqa: F401
 from ._lib import GwbpError, build, lib  # noqa: F401
-from .backproject import ViewPipeline, create_feature_field, create_label_field, finalize_reference, prune_mask, reduce_partials, reduce_partials_sharded  # noqa: F401
+from .backproject import ViewPipeline, create_feature_field, create_label_field, create_mask_feature_field, finalize_reference, prune_mask, reduce_partials, reduce_partials_sharded  # noqa: F401
 from .engine import Engine, bilinear_index, narrow_labels, nearest_index  # noqa: F401
 from . import scene_io  # noqa: F401
 from .rasterization import rasterization  # noqa: F401

@@ -51,7 +51,7 @@ CSRC = os.path.join(_HERE, "csrc")
 
 EXPORTS = [
     "gwbp_version", "gwbp_last_error_string", "gwbp_workspace_size", "gwbp_project", "gwbp_project_camera", "gwbp_bin_sort",
-    "gwbp_blend_weights", "gwbp_blend_weights_d", "gwbp_blend_scatter", "gwbp_blend_scatter_encoded", "gwbp_blend_tokens", "gwbp_scatter_tokens", "gwbp_accumulate_d", "gwbp_scatter", "gwbp_scatter_encoded", "gwbp_scatter_upsampled", "gwbp_scatter_bilinear", "gwbp_scatter_typed", "gwbp_scatter_upsampled_typed", "gwbp_scatter_bilinear_typed", "gwbp_scatter_tokens_typed", "gwbp_scatter_labels", "gwbp_render", "gwbp_render_pixels", "gwbp_sh_colors",
+    "gwbp_blend_weights", "gwbp_blend_weights_d", "gwbp_blend_scatter", "gwbp_blend_scatter_encoded", "gwbp_blend_tokens", "gwbp_scatter_tokens", "gwbp_accumulate_d", "gwbp_scatter", "gwbp_scatter_encoded", "gwbp_scatter_upsampled", "gwbp_scatter_bilinear", "gwbp_scatter_typed", "gwbp_scatter_upsampled_typed", "gwbp_scatter_bilinear_typed", "gwbp_scatter_tokens_typed", "gwbp_scatter_labels", "gwbp_scatter_mask_features", "gwbp_render", "gwbp_render_pixels", "gwbp_sh_colors",
     "gwbp_backproject_view", "gwbp_encode_map", "gwbp_finalize",
     "gwbp_accumulate_stats", "gwbp_read_stats", "gwbp_dump_pairs",
     "gwbp_blend_weights_ex", "gwbp_blend_weights_d_ex", "gwbp_blend_tokens_ex", "gwbp_blend_scatter_ex",
@@ -94,6 +94,7 @@ FLAG_NARROW_SCATTER = 4  # GWBP_FLAG_NARROW_SCATTER
 FLAG_SPLIT_ENCODER = 16  # GWBP_FLAG_SPLIT_ENCODER
 MAP_F32, MAP_F16, MAP_BF16 = 0, 1, 2  # GWBP_MAP_* (feature-map element type of the typed scatter entry points)
 LABEL_U8, LABEL_I16, LABEL_I32 = 0, 1, 2  # GWBP_LABEL_* (element type of gwbp_scatter_labels' label map)
+MASK_SLOT_BYTES = 32  # GWBP_MASK_SLOT_BYTES (gwbp_scatter_mask_features' slot store per intersection)
 
 # gwbp_project_camera: gsplat.rasterization's camera_model / rasterize_mode names -> GWBP_CAMERA_* / GWBP_RASTERIZE_*
 CAMERA_MODELS = {"pinhole": 0, "ortho": 1, "fisheye": 2}
@@ -166,6 +167,8 @@ ARGTYPES = {
     "gwbp_scatter_bilinear_typed": _WSV + [_P, _I32, _I64, _I64, _I64, _I32] + [_I32, _I32, _P, _P, _P, _P, _F, _F, _P, _P, _P],
     "gwbp_scatter_tokens_typed": _WSV + [_P, _I32, _I64, _I64, _I32, _P, _P, _F, _F, _P, _P, _P],
     "gwbp_scatter_labels": _WSV + [_P, _I32, _I64, _I64, _I32, _P, _P, _F, _F, _P, _I64, _P, _P],
+    "gwbp_scatter_mask_features": _WSV + [_P, _I32, _I64, _I64, _P, _P, _P, _I32, _I64, _I32, _I32, _F, _F, _P, _P, _P, _SZ, _P,
+                                          _P],
     "gwbp_render": _WSV + [_P, _I32, _P, _P],
     "gwbp_render_pixels": _WSV + [_P, _I32, _P, _P, _P],
     "gwbp_sh_colors": [_I64, _I32, _I32, _P, _P, C.POINTER(C.c_float), _P, _P],

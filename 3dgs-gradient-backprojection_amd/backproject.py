@@ -15,7 +15,7 @@ from __future__ import annotations
 import time
 import warnings
 from collections import namedtuple
-from typing import Callable, Dict, Optional, Sequence
+from typing import Callable, Dict, Optional, Sequence, Tuple
 
 import torch
 
@@ -959,6 +959,159 @@ def create_label_field(means, quats, scales, opacities, viewmats, K, width: int,
     F_rows, d_rows, row0 = reduce_partials_sharded(F, d, F_store)
     P = label_fractions(F_rows, d_rows)
     out = gather_rows(P, n) if gather else P
+    if return_partials:
+        return out, F_rows, d, dict(stats, row0=row0)
+    return out
+
+
+class _MaskPipeline(_LabelPipeline):
+    """The ViewPipeline of create_mask_feature_field: the front of create_label_field (a weight store, d added on the side stream);
+    the scatter stage is Engine.scatter_mask_features of the view's (labels, table)."""
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, num_classes=1, **kw)
+
+    def choose_scatter_kernel(self, n_pairs, n_headers) -> str:
+        super().choose_scatter_kernel(n_pairs, n_headers)
+        return "mask_features"
+
+    def _scatter_on(self, main, b, mask, F, d, scale_f, scale_d, t0, t1, upsample, encoder):
+        e = self.eng[b]
+        if t0 is not None:
+            t0.record(main)
+        p = self.pending.pop(self.i_scatter)
+        labels, table = mask
+        e.scatter_mask_features(p.view, labels, table, F, None if p.d_done else d, scale_f, scale_d, upsample=upsample)
+        if t1 is not None:
+            t1.record(main)
+        e.accumulate_stats(self.accums[0])
+
+
+def _mask_of(mask_fn, v: int, dim: int):
+    """mask_fn(v) -> (labels, table), the table checked against the field's width."""
+    out = mask_fn(v)
+    if not (isinstance(out, (tuple, list)) and len(out) == 2):
+        raise ValueError(f"mask_fn({v}) must return (labels, table)")
+    labels, table = out
+    if not torch.is_tensor(table) or table.dim() != 2 or table.shape[1] != dim:
+        raise ValueError(f"mask_fn({v}): table must be a [M, {dim}] tensor, got "
+                         f"{tuple(table.shape) if torch.is_tensor(table) else type(table).__name__}")
+    return labels, table
+
+
+def _mask_spills(engines) -> int:
+    return sum(int(e.mask_spilled.item()) for e in engines if getattr(e, "mask_spilled", None) is not None)
+
+
+def _run_masks_pipelined(job: _Job, eng: Engine, depth: int, dim: int) -> Dict[str, int]:
+    """create_mask_feature_field's views through a _MaskPipeline of `depth` workspaces (the schedule of _run_labels_pipelined)."""
+    (means, quats, scales, opacities), F, d, sf, sd, mask_fn, ids, _, _, width, height, _, _, upsample, pwf = job
+    n = means.shape[0]
+    engines = [eng] + [Engine(n, width, height, device=means.device, tight_binning=eng.tight_binning,
+                              isect_cap=eng.isect_cap, pair_cap=eng.pair_cap) for _ in range(depth - 1)]
+    spilled0 = _mask_spills(engines)
+    pipe = _MaskPipeline(n, width, height, means.device, engines=engines)
+    views = [eng.view(job.vm_host[v], job.K_host, width, height, **job.camera) for v in ids]
+
+    def front(j):
+        pipe.front(views[j], means, quats, scales, opacities, d, sd,
+                   pixel_weights=pwf(ids[j]) if pwf is not None else None)
+
+    for j in range(min(pipe.lookahead, len(ids))):
+        front(j)
+    probe = None
+    for i, v in enumerate(ids):
+        if i == 2 and pipe.stats()["overflow"]:
+            break
+        if probe is not None and all(e.query() for e in probe[1]):
+            if any(Engine.decode_stats(a)["overflow"] for a in probe[0]):
+                break
+            probe = None
+        if i > 2 and i % OVERFLOW_CHECK_EVERY == 0 and probe is None:
+            probe = pipe.stats_async()
+        if i + pipe.lookahead < len(ids):
+            front(i + pipe.lookahead)
+        pipe.scatter(_mask_of(mask_fn, v, dim), F, d, sf, sd, upsample=upsample)
+    stats = pipe.stats()
+    pipe.release()
+    stats["mask_spilled"] = _mask_spills(engines) - spilled0
+    return stats
+
+
+def _run_masks_serial(job: _Job, eng: Engine, dim: int) -> Dict[str, int]:
+    """create_mask_feature_field's views one after the other on the caller's stream; the apply kernel adds d too (synchronises)."""
+    accum = torch.zeros(32, dtype=torch.uint8, device=job.F.device)
+    spilled0 = _mask_spills([eng])
+    for v in job.view_ids:
+        labels, table = _mask_of(job.feature_fn, v, dim)
+        view = eng.view(job.vm_host[v], job.K_host, job.width, job.height, **job.camera)
+        eng.project(view, *job.gaussians)
+        eng.bin_sort(view)
+        if job.pixel_weight_fn is not None:
+            eng.blend_weighted(view, job.pixel_weight_fn(v))
+        else:
+            eng.blend_weights(view)
+        eng.scatter_mask_features(view, labels, table, job.F, job.d, job.sf, job.sd, upsample=job.upsample)
+        eng.accumulate_stats(accum)
+    stats = Engine.decode_stats(accum)
+    stats["mask_spilled"] = _mask_spills([eng]) - spilled0
+    return stats
+
+
+def create_mask_feature_field(means, quats, scales, opacities, viewmats, K, width: int, height: int,
+                              mask_fn: Callable[[int], Tuple[torch.Tensor, torch.Tensor]], dim: int, *, reduction: str = "sum",
+                              upsample: Optional[str] = None, views: Optional[Sequence[int]] = None, pipeline: bool = True,
+                              gather: bool = True, return_partials: bool = False, camera_model: str = "pinhole",
+                              rasterize_mode: str = "classic", engine: Optional[Engine] = None,
+                              pixel_weight_fn: Optional[Callable[[int], torch.Tensor]] = None):
+    """Build the [N, dim] feature field from MASK-POOLED features: per view a segmenter's mask or instance map L_v and one
+    embedding per mask, table E_v [M_v, dim] (SAM masks with a CLIP / LSeg vector each, superpixel-pooled DINO features).  The
+    result equals create_feature_field(feature_fn=lambda v: E_v[L_v]) -- a zero row wherever a label lies outside [0, M_v), whose
+    weight still counts in d -- up to the order of the sums, and is finalised the same way (L2-normalised, NaN -> 0), without the
+    [H, W, dim] map: per (Gaussian, tile) record the weights are summed by label (csrc/mask_features.hip) and every F row that
+    receives weight gets one read-modify-write per view from the table rows.
+
+    mask_fn(v) -> (labels, table): labels [height, width] (with upsample="nearest": any [h, w], read with F.interpolate's nearest
+    rule) on the device, uint8, bool, int16 or int32 read as stored, int64 narrowed; table [M_v, dim] float32, float16 or bfloat16
+    with unit channel stride (a half table is widened as it is read: F equals that of table.float()).  M_v may differ per view.
+    A dim that is no multiple of 4 materialises E_v[L_v] per view and takes the feature scatter (same F and d).
+    reduction: "sum" or "mean", with create_feature_field's scales (the D of 1/(H W D) is dim).
+    views, pipeline (True, an int >= 2 workspaces, or False), gather, return_partials, camera_model, rasterize_mode, engine,
+    pixel_weight_fn: as create_feature_field.  stats (return_partials) gains "mask_spilled": records with more than four
+    distinct labels, whose rest was added with atomics (F is then no longer the same bit for bit from run to run)."""
+    if upsample not in (None, "nearest"):
+        raise ValueError(f"upsample must be None or 'nearest' for mask maps, got {upsample!r}")
+    if reduction not in ("sum", "mean"):
+        raise ValueError(reduction)
+    dim = int(dim)
+    if dim < 1:
+        raise ValueError(f"dim must be positive, got {dim}")
+    dist, rank, world = _dist()
+    n = means.shape[0]
+    F, d, F_store = alloc_accumulators(n, dim, means.device, world)
+    sf, sd = (1.0, 1.0) if reduction == "sum" else (1.0 / (height * width * dim), 1.0 / (height * width * 3))
+    job = _Job((means, quats, scales, opacities), F, d, sf, sd, mask_fn,
+               list(views) if views is not None else view_shard(viewmats.shape[0], rank, world),
+               viewmats.detach().cpu(), K.detach().cpu(), width, height,
+               dict(camera_model=camera_model, rasterize_mode=rasterize_mode), None, upsample, pixel_weight_fn)
+    pipelined = bool(pipeline) and len(job.view_ids) > 1
+    if pipelined and _lib.hw_queues_late():
+        warnings.warn("gsbp_amd was imported after the HIP runtime had started: create_mask_feature_field runs its views on ONE "
+                      "stream", RuntimeWarning, stacklevel=2)
+        pipelined = False
+    depth = (pipeline_depth(n, width, height) if pipeline is True else max(2, int(pipeline))) if pipelined else 1
+    eng = engine or Engine(n, width, height, device=means.device, tight_binning=True)
+    stats: Dict[str, int] = {}
+    for attempt in range(6):  # a capacity overflow invalidates the accumulators: grow the workspace, start over
+        stats = _run_masks_pipelined(job, eng, depth, dim) if pipelined else _run_masks_serial(job, eng, dim)
+        if _overflow_action(stats["overflow"], False, attempt) is None:
+            break
+        eng.grow(stats, views=len(job.view_ids))
+        F.zero_()
+        d.zero_()
+    F_rows, d_rows, row0 = reduce_partials_sharded(F, d, F_store)
+    out_rows = eng.finalize(F_rows, d_rows)
+    out = gather_rows(out_rows, n) if gather else out_rows
     if return_partials:
         return out, F_rows, d, dict(stats, row0=row0)
     return out

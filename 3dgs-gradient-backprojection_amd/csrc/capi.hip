@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "gwbp_dev.h"
+#include "mask_features.h"
 
 namespace gwbp {
 
@@ -638,6 +639,53 @@ int gwbp_scatter_labels(const gwbp_caps *caps, void *workspace, size_t workspace
         return rc;
     return launch_scatter_labels(L, W, V, labels, label_type, ls_y, ls_x, ymap, xmap, num_classes, scale_f, scale_d, F, ldf, d,
                                  static_cast<hipStream_t>(stream));
+}
+
+int gwbp_scatter_mask_features(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                               const void *labels, int32_t label_type, int64_t ls_y, int64_t ls_x, const int32_t *ymap,
+                               const int32_t *xmap, const void *table, int32_t table_type, int64_t ts_row, int32_t num_masks,
+                               int32_t D, float scale_f, float scale_d, float *F, float *d, void *slots, size_t slots_bytes,
+                               uint32_t *n_spilled, void *stream)
+{
+    // the map, table and slot arguments first: nothing of the workspace or the view is looked at before they pass
+    if (label_type != GWBP_LABEL_U8 && label_type != GWBP_LABEL_I16 && label_type != GWBP_LABEL_I32)
+        return set_error(GWBP_EINVAL, "unknown label type %d", (int)label_type);
+    if (!known_map_type(table_type))
+        return set_error(GWBP_EINVAL, "unknown table type %d", (int)table_type);
+    if (num_masks <= 0)
+        return set_error(GWBP_EINVAL, "num_masks must be positive (got %d)", (int)num_masks);
+    if (D < 4 || D % 4 != 0)
+        return set_error(GWBP_EINVAL, "gwbp_scatter_mask_features: D must be a positive multiple of 4 (got %d)", (int)D);
+    if (!labels || ls_y < 0 || ls_x < 0)
+        return set_error(GWBP_EINVAL, "bad label map arguments (strides %lld %lld)", (long long)ls_y, (long long)ls_x);
+    if (!ymap != !xmap)
+        return set_error(GWBP_EINVAL, "gwbp_scatter_mask_features needs both index maps or neither");
+    const uintptr_t talign = table_type == GWBP_MAP_F32 ? 15 : 7; // one float4 / four halves per lane load
+    if (!table || ts_row < D || (ts_row & 3) || (reinterpret_cast<uintptr_t>(table) & talign))
+        return set_error(GWBP_EINVAL, "table rows must be %d-B aligned runs of D contiguous elements (row stride %lld)",
+                         (int)talign + 1, (long long)ts_row);
+    if (!F || (reinterpret_cast<uintptr_t>(F) & 15))
+        return set_error(GWBP_EINVAL, "F must be a non-null, 16-B aligned [N, D] array");
+    if (!slots || (reinterpret_cast<uintptr_t>(slots) & 15))
+        return set_error(GWBP_EINVAL, "slots must be a non-null, 16-B aligned buffer");
+    Layout L;
+    Ws W;
+    ViewDev V;
+    int rc = make_layout(caps, &L);
+    if (rc)
+        return rc;
+    if (slots_bytes / GWBP_MASK_SLOT_BYTES < (size_t)L.isect_cap)
+        return set_error(GWBP_EINVAL, "slots: have %zu bytes, need %d x isect_cap = %zu", slots_bytes, GWBP_MASK_SLOT_BYTES,
+                         (size_t)GWBP_MASK_SLOT_BYTES * (size_t)L.isect_cap);
+    if ((rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W)))
+        return rc;
+    if ((rc = make_view(view_host, caps, &V)))
+        return rc;
+    MaskSlots S;
+    S.labels = static_cast<int4 *>(slots);
+    S.sums = reinterpret_cast<float4 *>(static_cast<char *>(slots) + (size_t)L.isect_cap * sizeof(int4));
+    return launch_mask_features(L, W, V, labels, label_type, ls_y, ls_x, ymap, xmap, table, table_type, ts_row, num_masks, D,
+                                scale_f, scale_d, F, d, S, n_spilled, static_cast<hipStream_t>(stream));
 }
 
 int gwbp_render(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,

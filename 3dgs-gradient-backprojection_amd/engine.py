@@ -636,6 +636,82 @@ class Engine:
                    C.c_int64(sx), K, ptr(ymap), ptr(xmap), C.c_float(scale_f), C.c_float(scale_d), ptr(F), C.c_int64(F.stride(0)),
                    ptr(d), self._stream())
 
+    @staticmethod
+    def mask_fast_path(dim: int) -> bool:
+        """Table widths gwbp_scatter_mask_features takes (every other width materialises table[labels], see
+        scatter_mask_features)."""
+        return dim >= 4 and dim % 4 == 0
+
+    def _mask_buffers(self):
+        """(slot store, spill counter) of gwbp_scatter_mask_features: allocated on first use, again after grow(); made on the stream
+        this engine's kernels run on (one buffer serves every view of this engine: its views are scattered in stream order)."""
+        need = self.isect_cap * _lib.MASK_SLOT_BYTES
+        if getattr(self, "_mask_slots", None) is None or self._mask_slots.numel() < need:
+            ctx = torch.cuda.stream(self.stream) if self.stream is not None else torch.cuda.stream(torch.cuda.current_stream(self.device))
+            with ctx:
+                self._mask_slots = torch.empty(need, dtype=torch.uint8, device=self.device)
+                if getattr(self, "mask_spilled", None) is None:
+                    self.mask_spilled = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return self._mask_slots, self.mask_spilled
+
+    def scatter_mask_features(self, view, labels, table, F, d, scale_f=1.0, scale_d=1.0, upsample: Optional[str] = None):
+        """F[g, :] += scale_f * sum_p w_g(p) table[labels[p], :], d[g] += scale_d * sum_p w_g(p) from the view's weight store: scatter()
+        of the materialised map table[labels] (a zero row where a label is outside [0, M)) without building it
+        (gwbp_scatter_mask_features: per-record label sums filed at the emit positions, then ONE read-modify-write of every F row
+        that receives weight).  Records with more than four distinct labels add the rest with atomics and count in
+        `mask_spilled` (a device int32 counter of this engine, never reset here).
+
+        labels: [H, W] (with upsample="nearest": [h, w]) uint8 / bool / int16 / int32 read as stored, any non-negative strides;
+        int64 is narrowed first (narrow_labels).  table: [M, D] float32, float16 or bfloat16 with unit channel stride; a half
+        table is widened as it is read (F equals that of table.float()).  F: float32 [N, D] contiguous; d: float32 [N] or None.
+        A D that is no multiple of 4 (mask_fast_path) builds table[labels] and calls scatter(): same F and d."""
+        if self._tokens is not None:
+            raise GwbpError("this view was blended with blend_tokens (no weight store): blend_weights() first for "
+                            "scatter_mask_features()")
+        if not torch.is_tensor(labels) or not labels.is_cuda or not torch.is_tensor(table) or not table.is_cuda:
+            raise GwbpError("labels and table must be HIP tensors (no CPU fallback exists for this path)")
+        if table.dim() != 2 or table.dtype not in MAP_TYPES or table.shape[0] < 1 or table.shape[1] < 1:
+            raise GwbpError(f"table must be a float32 / float16 / bfloat16 [M, D] tensor with M, D >= 1, got "
+                            f"{table.dtype} {tuple(table.shape)}")
+        if table.shape[1] > 1 and table.stride(1) != 1:
+            raise GwbpError("table must have unit channel stride")
+        M, D = int(table.shape[0]), int(table.shape[1])
+        if labels.dtype == torch.int64:
+            labels = narrow_labels(labels, M)
+        if labels.dtype not in LABEL_TYPES:
+            raise GwbpError(f"labels must be an integer map (uint8, bool, int16, int32 or int64), got {labels.dtype}")
+        if labels.dtype == torch.bool:
+            labels = labels.view(torch.uint8)
+        if upsample not in (None, "nearest"):
+            raise GwbpError(f"upsample must be None or 'nearest' for a label map, got {upsample!r}")
+        if labels.dim() != 2 or (upsample is None and tuple(labels.shape) != (view.height, view.width)):
+            want = f"[H,W] = [{view.height},{view.width}]" if upsample is None else "[h,w]"
+            raise GwbpError(f"label map must be {want}, got {tuple(labels.shape)}")
+        if min(labels.stride()) < 0:
+            raise GwbpError("negative label-map strides are not supported")
+        if F.dtype != torch.float32 or not F.is_cuda or F.dim() != 2 or tuple(F.shape) != (self.n, D) or not F.is_contiguous():
+            raise GwbpError(f"F must be a contiguous float32 HIP tensor [{self.n},{D}]")
+        if d is not None and (d.dtype != torch.float32 or not d.is_cuda or not d.is_contiguous() or tuple(d.shape) != (self.n,)):
+            raise GwbpError(f"d must be a contiguous float32 HIP tensor [{self.n}]")
+        if not self.mask_fast_path(D) or F.data_ptr() % 16:
+            # the map the fast path avoids: a zero row wherever a label is outside [0, M)
+            idx = labels.to(torch.int64)
+            ok = ((idx >= 0) & (idx < M)).unsqueeze(-1)
+            feats = torch.where(ok, table[idx.clamp(0, M - 1)], torch.zeros((), dtype=table.dtype, device=table.device))
+            return self.scatter(view, feats, F, d, scale_f, scale_d, upsample=upsample)
+        align = 16 if table.dtype == torch.float32 else 8
+        if table.stride(0) % 4 or table.data_ptr() % align:
+            table = table.contiguous() if not table.is_contiguous() else table.clone()  # (a fresh allocation is 256-B aligned)
+        ymap = xmap = None
+        if upsample == "nearest":
+            ymap, xmap = self.nearest_maps(labels.shape[0], labels.shape[1], view.height, view.width)
+        slots, spilled = self._mask_buffers()
+        sy, sx = labels.stride()
+        self._call("gwbp_scatter_mask_features", *self._args(), C.byref(view), ptr(labels), LABEL_TYPES[labels.dtype],
+                   C.c_int64(sy), C.c_int64(sx), ptr(ymap), ptr(xmap), ptr(table), MAP_TYPES[table.dtype],
+                   C.c_int64(table.stride(0) if M > 1 else D), M, D, C.c_float(scale_f), C.c_float(scale_d), ptr(F), ptr(d),
+                   ptr(slots), C.c_size_t(slots.numel()), ptr(spilled), self._stream())
+
     def _scatter_half(self, view, feats, F, d, scale_f, scale_d, upsample):
         """scatter() of a half map that half_native() admits: the typed entry points."""
         if upsample not in (None, "nearest", "bilinear"):

@@ -167,6 +167,22 @@ def make_label_map(cfg: Config, view: int, num_classes: int, device="cpu", n_see
     return out
 
 
+MASK_TABLE_SEED0 = 40_000
+
+
+def make_mask_features(cfg: Config, view: int, n_masks: int, dim: int, device="cpu", per_pixel: bool = False,
+                       size: Optional[tuple] = None):
+    """(labels, table) of view `view` for create_mask_feature_field: a [H,W] int32 map of mask ids in [0, n_masks) --
+    make_label_map's Voronoi cells (n_masks seeds, so about one cell per mask) or, with per_pixel=True, a random id per pixel --
+    and a [n_masks, dim] fp32 table of N(0,1) rows L2-normalised like a CLIP / LSeg embedding (seed 40000 + view).  size=(h, w):
+    a low-resolution map of that shape."""
+    labels = make_label_map(cfg, view, n_masks, device=device, n_seeds=n_masks, per_pixel=per_pixel, size=size)
+    g = torch.Generator(device="cpu").manual_seed(MASK_TABLE_SEED0 + view)
+    table = torch.randn(n_masks, dim, generator=g)
+    table /= table.norm(dim=-1, keepdim=True)
+    return labels, table.to(device)
+
+
 PIXEL_WEIGHT_SEED0 = 30000
 
 

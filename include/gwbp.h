@@ -352,6 +352,34 @@ GWBP_API int gwbp_scatter_labels(const gwbp_caps *caps, void *workspace, size_t 
                                  const int32_t *ymap, const int32_t *xmap, float scale_f, float scale_d, float *F, int64_t ldf,
                                  float *d, void *stream);
 
+/* Bytes of gwbp_scatter_mask_features' slot store per (Gaussian, tile) intersection: four (int32 label, fp32 sum) slots. */
+#define GWBP_MASK_SLOT_BYTES 32
+
+/* Back-projection of MASK-POOLED features: a label map L (a segmenter's masks or instances, superpixels) and one embedding per
+ * label, table[k * ts_row + c] (k < num_masks, c < D, elements of table_type = GWBP_MAP_*):
+ *     F[g, :] += scale_f * sum_p w_g(p) table[L(p), :],     d[g] += scale_d * sum_p w_g(p)
+ * = gwbp_scatter on the materialised map table[L] (a zero row where L(p) is outside [0, num_masks): such a pixel adds nothing to
+ * F, its weight still counts in d) without the [H, W, D] map, up to the order of the sums.  Per (Gaussian, tile) record the weights
+ * are summed by label into up to four (label, sum) slots filed at the record's emit position in `slots`; one wave per Gaussian
+ * then multiplies its slots with table rows and updates F[g, :] and d[g] with ONE plain read-modify-write per view -- no atomics,
+ * F and d the same bit for bit from run to run.  A record with more than four distinct labels adds the rest with fp32 atomics
+ * (the order of those sums varies) and adds 1 to *n_spilled (device, optional).
+ * labels, label_type, ls_y, ls_x, ymap, xmap: as gwbp_scatter_labels.  table: 16-B aligned (fp32) or 8-B aligned (fp16 / bf16),
+ * ts_row >= D and a multiple of 4; a half table is widened as it is read (F equals that of the fp32 table).  F is [N, D] fp32
+ * dense and 16-B aligned, D a positive multiple of 4; d may be NULL (a caller that added d in gwbp_blend_weights_d).
+ * slots: caller-owned device scratch of at least GWBP_MASK_SLOT_BYTES * caps->isect_cap bytes, 16-B aligned, only used during
+ * the call's kernels (one buffer per stream).
+ * GWBP_EINVAL before anything else for an unknown label or table type, num_masks <= 0, a D that is no positive multiple of 4,
+ * bad map or table arguments, exactly one of ymap / xmap NULL, a NULL or misaligned F, or missing / short slots.  Needs the
+ * weight store of the view (as gwbp_scatter_labels); after gwbp_blend_scatter / gwbp_blend_scatter_encoded / gwbp_blend_tokens
+ * the call sets gwbp_stats.overflow bit 2 and leaves F and d untouched. */
+GWBP_API int gwbp_scatter_mask_features(const gwbp_caps *caps, void *workspace, size_t workspace_bytes,
+                                        const gwbp_view *view_host, const void *labels, int32_t label_type, int64_t ls_y,
+                                        int64_t ls_x, const int32_t *ymap, const int32_t *xmap, const void *table,
+                                        int32_t table_type, int64_t ts_row, int32_t num_masks, int32_t D, float scale_f,
+                                        float scale_d, float *F, float *d, void *slots, size_t slots_bytes,
+                                        uint32_t *n_spilled, void *stream);
+
 /* Forward render (what rasterization() returns): out[p,:] = sum_g w_g(p) * colors[g,:], out is [H,W,D]. */
 GWBP_API int gwbp_render(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
                 const float *colors, int32_t D, float *out, void *stream);

@@ -42,6 +42,14 @@ def build_parser() -> argparse.ArgumentParser:
                       help="directory with <image name>.pt INTEGER tensors [H,W] (a segmenter's class / instance ids, a mask; "
                            "another shape is a low-resolution map, upsampled with mode='nearest'): writes label_field.pt, the "
                            "[N, --num-classes] fraction of every Gaussian's blend weight per class, instead of a feature field")
+    maps.add_argument("--mask-features", default=None, metavar="DIR",
+                      help="directory with <image name>.pt files holding {'labels': [H,W] integer mask / instance ids (another "
+                           "shape is a low-resolution map, upsampled with mode='nearest'), 'table': [M,D] one embedding per mask "
+                           "(float32 / float16 / bfloat16)}: the feature map is table[labels] (a zero row outside [0, M)), "
+                           "back-projected without materialising it; writes the same features_<feature>.pt as --feature-maps.  "
+                           "With --synthetic: 'synthetic' for seeded Voronoi mask maps and tables (synthetic.make_mask_features)")
+    ap.add_argument("--num-masks", type=int, default=200,
+                    help="masks per view of --synthetic --mask-features synthetic (default 200)")
     ap.add_argument("--num-classes", type=int, default=None,
                     help="number of classes K of --label-maps (ids outside [0, K) are ignored); with --synthetic: use seeded "
                          "piecewise-constant (Voronoi) label maps with K classes instead of feature maps")
@@ -99,6 +107,17 @@ def load_label_map(label_dir: str, image_name: str) -> torch.Tensor:
     return lab
 
 
+def load_mask_features(mask_dir: str, image_name: str):
+    """<mask_dir>/<image name>.pt: {"labels": [h, w] integer map, "table": [M, D] float32 / float16 / bfloat16}, as stored."""
+    m = torch.load(os.path.join(mask_dir, image_name + ".pt"))
+    lab, tab = (m.get("labels"), m.get("table")) if isinstance(m, dict) else (None, None)
+    if (not torch.is_tensor(lab) or lab.is_floating_point() or lab.is_complex() or lab.dim() != 2 or not torch.is_tensor(tab)
+            or tab.dtype not in (torch.float32, torch.float16, torch.bfloat16) or tab.dim() != 2):
+        raise SystemExit(f"{image_name}.pt in {mask_dir}: a dict with a 2-D integer 'labels' tensor and a 2-D float32 / float16 / "
+                         "bfloat16 'table' tensor is required")
+    return lab, tab
+
+
 def load_pixel_weights(weight_dir: str, image_name: str, H: int, W: int) -> torch.Tensor:
     """<weight_dir>/<image name>.pt: an [H, W] weight map of a type the weighted blend reads."""
     c = torch.load(os.path.join(weight_dir, image_name + ".pt"))
@@ -118,6 +137,13 @@ def main(argv=None):
         ap.error("--label-maps needs --num-classes K >= 1")
     if labels_mode and args.encoder:
         ap.error("--encoder applies to feature maps, not to --label-maps / --num-classes")
+    masks_mode = bool(args.mask_features)
+    if masks_mode and (args.encoder or args.num_classes is not None):
+        ap.error("--mask-features takes neither --encoder nor --num-classes")
+    if masks_mode and args.synthetic and args.mask_features != "synthetic":
+        ap.error("with --synthetic, --mask-features takes 'synthetic' (seeded mask maps)")
+    if masks_mode and args.num_masks < 1:
+        ap.error("--num-masks must be positive")
     camera_model = args.camera_model or "pinhole"
     cam_kw = dict(camera_model=camera_model, rasterize_mode=args.rasterize_mode)
 
@@ -150,6 +176,9 @@ def main(argv=None):
         def label_fn(v):
             return syn.make_label_map(cfg, v, args.num_classes, device=dev)
         label_upsample = None
+
+        def mask_fn(v):
+            return syn.make_mask_features(cfg, v, args.num_masks, dim, device=dev)
         pixel_weight_fn = None
         if args.pixel_weights:
             if args.pixel_weights not in ("mask", "confidence"):
@@ -177,11 +206,21 @@ def main(argv=None):
 
             def label_fn(v):
                 return load_label_map(args.label_maps, images[v].name).to(dev)
+        elif masks_mode:
+            first_labels, first_table = load_mask_features(args.mask_features, images[0].name)
+            label_upsample = "nearest" if tuple(first_labels.shape) != (H, W) else None
+            dim = int(first_table.shape[1])
+
+            def mask_fn(v):
+                lab, tab = load_mask_features(args.mask_features, images[v].name)
+                return lab.to(dev), tab.to(dev)
         elif not args.feature_maps:
             raise SystemExit("--feature-maps is required (no LSeg/DINO weights offline)")
         encoder = torch.load(args.encoder).to(dev).float() if args.encoder else None
-        first = torch.load(os.path.join(args.feature_maps, images[0].name + ".pt")) if not labels_mode else None
-        dim = first.shape[-1] if first is not None else None
+        first = (torch.load(os.path.join(args.feature_maps, images[0].name + ".pt"))
+                 if not (labels_mode or masks_mode) else None)
+        if not masks_mode:
+            dim = first.shape[-1] if first is not None else None
         # A map at the network's resolution is upsampled the way the reference does it -- bilinear for lseg (backproject.py:110-112),
         # nearest for dino's patch tokens (:244-248) -- INSIDE the kernels (dino maps whose tokens cover a tile: token space); with an
         # encoder the map is materialised first (the encoder-fused kernels read full-resolution pixels)
@@ -235,6 +274,11 @@ def main(argv=None):
         out, F, d, stats = gsbp_amd.create_label_field(means, quats, scales, opac, viewmats, K, W, H, label_fn,
                                                        args.num_classes, upsample=label_upsample, return_partials=True,
                                                        pixel_weight_fn=pixel_weight_fn, **cam_kw)
+    elif masks_mode:
+        # the feature field of the maps table[labels], built from the masks and their embeddings (features_<feature>.pt)
+        out, F, d, stats = gsbp_amd.create_mask_feature_field(means, quats, scales, opac, viewmats, K, W, H, mask_fn, dim,
+                                                              reduction=reduction, upsample=label_upsample,
+                                                              return_partials=True, pixel_weight_fn=pixel_weight_fn, **cam_kw)
     else:
         out, F, d, stats = gsbp_amd.create_feature_field(means, quats, scales, opac, viewmats, K, W, H, feature_fn, dim,
                                                          reduction=reduction, encoder=encoder, return_partials=True,
