@@ -55,7 +55,7 @@ EXPORTS = [
     "gwbp_backproject_view", "gwbp_encode_map", "gwbp_finalize",
     "gwbp_accumulate_stats", "gwbp_read_stats", "gwbp_dump_pairs",
     "gwbp_blend_weights_ex", "gwbp_blend_weights_d_ex", "gwbp_blend_tokens_ex", "gwbp_blend_scatter_ex",
-    "gwbp_blend_scatter_encoded_ex",
+    "gwbp_blend_scatter_encoded_ex", "gwbp_blend_weights_rgb", "gwbp_blend_weights_d_rgb", "gwbp_blend_tokens_rgb",
 ]
 
 
@@ -184,6 +184,10 @@ ARGTYPES = {
     "gwbp_blend_tokens_ex": _WSV + [_P, _P, _P, C.POINTER(PixelWeights), _P],
     "gwbp_blend_scatter_ex": _WSV + [_P, _I64, _I64, _I32, _F, _F, _P, _P, _P, C.POINTER(PixelWeights), _P],
     "gwbp_blend_scatter_encoded_ex": _WSV + [_P, _I64, _I64, _I32, _P, _I32, _F, _F, _P, _P, _P, C.POINTER(PixelWeights), _P],
+    # the _rgb forms: the _ex argument list + colors [N,3], image [H,W,3] before the stream
+    "gwbp_blend_weights_rgb": _WSV + [_P, C.POINTER(PixelWeights), _P, _P, _P],
+    "gwbp_blend_weights_d_rgb": _WSV + [_P, _F, _P, C.POINTER(PixelWeights), _P, _P, _P],
+    "gwbp_blend_tokens_rgb": _WSV + [_P, _P, _P, C.POINTER(PixelWeights), _P, _P, _P],
 }
 
 _lib: Optional[C.CDLL] = None

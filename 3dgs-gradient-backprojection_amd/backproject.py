@@ -311,13 +311,22 @@ class ViewPipeline:
             e.set_front_priority(wide if self.front_priority is None else bool(self.front_priority))
         return "wide" if wide else "narrow"
 
-    def front(self, view, means, quats, scales, opacities, d=None, scale_d=1.0, pixel_weights: Optional[torch.Tensor] = None):
+    # render=: where the view's RGB render is made, per blend of the front stage -- True: composited by that blend itself
+    # (gwbp_blend_*_rgb), False: gwbp_render_pixels right after bin_sort on the same workspace.  The fused blend + scatter
+    # kernels need the map the network makes from the render, so their views always take render_pixels.
+    RENDER_IN_BLEND = {"store": True, "halves": True, "tokens": True}
+
+    def front(self, view, means, quats, scales, opacities, d=None, scale_d=1.0, pixel_weights: Optional[torch.Tensor] = None,
+              render=None, image: Optional[torch.Tensor] = None):
         """d (optional): the denominator accumulator.  With the 256-channel scatter kernel chosen, the view's share of d
         is added by the blend itself on the side stream (gwbp_blend_weights_d) and scatter() then leaves d alone: the
         denominators cost nothing on the scatter's stream.
         pixel_weights (optional): the view's [H, W] weight map, produced on the caller's stream before this call: the view's
         stream waits for it, and whichever stage blends the view (this one, or scatter() for the fused kernels) runs the
-        weighted blend."""
+        weighted blend.
+        render = (colors, sh_degree), image (optional): also render the view's RGB into `image`, an [H, W, 3] float32 tensor
+        allocated on the caller's stream before this call (create_feature_field(render_colors=...)).  Returns the event the
+        caller's stream waits on before it reads the image (None without one)."""
         K = len(self.eng)
         b = self.i_front % K
         side = self.sides[self.i_front % len(self.sides)]
@@ -327,36 +336,58 @@ class ViewPipeline:
         elif not self.independent:
             side.wait_event(self.ev_done[b])  # workspace b is free once scatter(i-K) has finished
         # (independent: scatter(i-K) was enqueued on this very stream)
-        if pixel_weights is not None:
+        if pixel_weights is not None or image is not None:
             if self.i_front >= K:
                 ready = torch.cuda.Event()
                 ready.record(main)
                 side.wait_event(ready)
-            pixel_weights.record_stream(side)  # (the map is also held in _Pending until the view's blend is enqueued)
+            if pixel_weights is not None:
+                pixel_weights.record_stream(side)  # (the map is also held in _Pending until the view's blend is enqueued)
+            if image is not None:
+                image.record_stream(side)  # (the caller owns the image: its memory is recycled behind this stream only)
         e = self.eng[b]
+        ev_image = torch.cuda.Event() if image is not None else None
         if self.independent:  # the engine is bound to `side`
             e.project(view, means, quats, scales, opacities)
             e.bin_sort(view)
+            if image is not None:  # (a fused kernel blends these views: render_pixels; colours allocated on `side`)
+                with torch.cuda.stream(side):
+                    e.render_rgb(view, e.view_colors(view, means, *render), image)
+                ev_image.record(side)
             self.pending[self.i_front] = _Pending(view, False, False, False, pixel_weights)
             self.i_front += 1
-            return
+            return ev_image
         with torch.cuda.stream(side):
             e.project(view, means, quats, scales, opacities)
             e.bin_sort(view)
             d_done = d is not None and self.wide and not self.fuse_small and self.token_grid is None
+            kind = "tokens" if self.token_grid is not None else None if self.fuse_small else "halves" if e._wide_requested() \
+                else "store"
+            cols = e.view_colors(view, means, *render) if image is not None else None
+            composite = cols is not None and kind is not None and self.RENDER_IN_BLEND[kind]
+            if cols is not None and not composite:
+                e.render_rgb(view, cols, image)
+                ev_image.record(side)
             if self.token_grid is not None:
-                if pixel_weights is not None:
+                if composite:
+                    e.blend_tokens_rgb(view, *self.token_grid, cols, image, pixel_weights)
+                elif pixel_weights is not None:
                     e.blend_tokens_weighted(view, *self.token_grid, pixel_weights)
                 else:
                     e.blend_tokens(view, *self.token_grid)
             elif not self.fuse_small:
-                if pixel_weights is not None:
+                if composite:
+                    e.blend_weights_rgb(view, cols, image, pixel_weights, d=d if d_done else None, scale_d=scale_d)
+                elif pixel_weights is not None:
                     e.blend_weighted(view, pixel_weights, d=d if d_done else None, scale_d=scale_d)
                 else:
                     e.blend_weights(view, d=d if d_done else None, scale_d=scale_d)
+            if composite:
+                ev_image.record(side)
             self.ev_front[b].record(side)
         self.pending[self.i_front] = _Pending(view, d_done, not self.fuse_small, self.token_grid is not None, pixel_weights)
         self.i_front += 1
+        return ev_image
 
     # Encoder workgroups per CU beside the pipeline (see encode_ahead): None = 1 next to the separate blend and small-D
     # scatter kernels (both latency-bound: C5 2.19 -> 1.96 ms/view against 4 per CU), 2 next to the fused blend+scatter
@@ -551,8 +582,83 @@ def pipeline_depth(n_gaussians: int, width: int, height: int, dim: Optional[int]
 # the inputs every attempt of create_feature_field works on (gaussians = (means, quats, scales, opacities); camera = the
 # camera_model / rasterize_mode keywords of Engine.view)
 # pixel_weight_fn: v -> the view's [height, width] weight map, or None (unweighted)
+# render: a _Render -- the views' RGB renders are made by the front and handed to feature_fn(v, image) -- or None
 _Job = namedtuple("_Job", "gaussians F d sf sd feature_fn view_ids vm_host K_host width height camera encoder upsample "
-                          "pixel_weight_fn", defaults=(None,))
+                          "pixel_weight_fn render", defaults=(None, None))
+# what rasterization(..., colors, sh_degree=sh_degree) renders: [N, 3] colours (sh_degree None) or [N, K, 3] SH coefficients
+_Render = namedtuple("_Render", "colors sh_degree")
+
+
+def _render_of(render_colors, sh_degree, n: int, device, view_fn=None) -> Optional[_Render]:
+    """Check the render_colors / sh_degree keywords of the drivers before any GPU work; None without render_colors."""
+    if render_colors is None:
+        if sh_degree is not None:
+            raise ValueError("sh_degree needs render_colors (the SH coefficients it evaluates)")
+        return None
+    if view_fn is not None:
+        raise ValueError("view_fn takes a feature map only: it cannot hand the view's render to the network")
+    if not torch.is_tensor(render_colors):
+        raise ValueError(f"render_colors must be a tensor, got {type(render_colors).__name__}")
+    if render_colors.dtype != torch.float32:
+        raise ValueError(f"render_colors must be float32, got {render_colors.dtype}")
+    if render_colors.device != torch.device(device):
+        raise ValueError(f"render_colors must be on the Gaussians' device {device}, got {render_colors.device}")
+    shape = tuple(render_colors.shape)
+    if sh_degree is None:
+        if shape != (n, 3):
+            raise ValueError(f"render_colors without sh_degree must be [N, 3] = [{n}, 3] colours, got {list(shape)}")
+        return _Render(render_colors, None)
+    if isinstance(sh_degree, bool) or not isinstance(sh_degree, int) or not 0 <= sh_degree <= 3:
+        raise ValueError(f"sh_degree must be an int in 0..3 (the SH kernel's degrees), got {sh_degree!r}")
+    if len(shape) != 3 or shape[0] != n or shape[2] != 3 or shape[1] < (sh_degree + 1) ** 2:
+        raise ValueError(f"render_colors with sh_degree={sh_degree} must be [N, K, 3] SH coefficients with N = {n} and "
+                         f"K >= {(sh_degree + 1) ** 2}, got {list(shape)}")
+    return _Render(render_colors, int(sh_degree))
+
+
+def _render_view(eng: Engine, job: _Job, v: int, view=None) -> torch.Tensor:
+    """View v's RGB render by project + bin_sort + render_pixels on `eng` (on the caller's stream): the render of a view whose
+    map is needed before its front stage (_plan), and of the serial paths whose blend follows the map."""
+    if view is None:
+        view = eng.view(job.vm_host[v], job.K_host, job.width, job.height, **job.camera)
+    eng.project(view, *job.gaussians)
+    eng.bin_sort(view)
+    return eng.render_rgb(view, eng.view_colors(view, job.gaussians[0], *job.render))
+
+
+def _call_fn(job: _Job, v: int, image=None):
+    """feature_fn(v), or feature_fn(v, image) for a job that renders."""
+    return job.feature_fn(v) if job.render is None else job.feature_fn(v, image)
+
+
+class _Renders:
+    """The pipelined drivers' handoff of the views' renders: front(j) enqueues view j's front stage through pipe.front, with a
+    fresh image allocated on the caller's stream when the job renders (and view j needs one), and take(j) returns that image
+    behind the event after which it is written, waited for on torch's current stream (None without render_colors)."""
+
+    def __init__(self, pipe: "ViewPipeline", job: _Job, views, skip_first: bool = False):
+        self.pipe, self.job, self.views = pipe, job, views
+        self.skip_first = skip_first  # view 0 was rendered by _plan: its front renders nothing
+        self.images = {}  # j -> (view j's image, its event)
+
+    def front(self, j: int) -> None:
+        job, pwf = self.job, self.job.pixel_weight_fn
+        img = None
+        if job.render is not None and not (j == 0 and self.skip_first):
+            img = torch.empty(job.height, job.width, 3, device=job.F.device)
+        ev = self.pipe.front(self.views[j], *job.gaussians, job.d, job.sd,
+                             pixel_weights=pwf(job.view_ids[j]) if pwf is not None else None, render=job.render, image=img)
+        if img is not None:
+            self.images[j] = (img, ev)
+
+    def take(self, j: int) -> Optional[torch.Tensor]:
+        if self.job.render is None:
+            return None
+        img, ev = self.images.pop(j)
+        torch.cuda.current_stream(img.device).wait_event(ev)
+        return img
+
+
 # one attempt's schedule, decided before its first view from the options and the first map (_plan).  first_map: view 0's map,
 # fetched early when its layout decides the schedule.  encode: where the encoder runs -- None (no encoder) | "blend" (the fused
 # blend + scatter kernel's tile prologue) | "staging" (the scatter kernel's slab staging) | "ahead" (a separate kernel on a
@@ -561,8 +667,10 @@ _Plan = namedtuple("_Plan", "pipelined first_map token_grid encode depth split v
                    defaults=(None, None, None, 0, False, None, True))
 
 
-def _plan(job: _Job, pipeline, token_space, fuse_small, fuse_encoder, encoder_in_blend, encoder_split, split_allowed) -> _Plan:
-    """create_feature_field's schedule for one attempt (the predicates and feature_fn are called in this order)."""
+def _plan(job: _Job, pipeline, token_space, fuse_small, fuse_encoder, encoder_in_blend, encoder_split, split_allowed,
+          eng: Optional[Engine] = None) -> _Plan:
+    """create_feature_field's schedule for one attempt (the predicates and feature_fn are called in this order).  A job that
+    renders gets view 0's render for an early map from a standalone project + bin_sort + render_pixels on `eng`."""
     if not (pipeline and len(job.view_ids) > 1):
         return _Plan(False)
     if _lib.hw_queues_late():
@@ -576,7 +684,10 @@ def _plan(job: _Job, pipeline, token_space, fuse_small, fuse_encoder, encoder_in
                       % _lib.HW_QUEUES_WANTED, RuntimeWarning, stacklevel=3)
         return _Plan(False)
     encoder, upsample, width, height = job.encoder, job.upsample, job.width, job.height
-    first_map = job.feature_fn(job.view_ids[0]) if (encoder is not None or upsample == "nearest") else None
+    first_map = None
+    if encoder is not None or upsample == "nearest":
+        v0 = job.view_ids[0]
+        first_map = _call_fn(job, v0, _render_view(eng, job, v0) if job.render is not None else None)
     # the dino shape -- a nearest-upsampled map whose texels are at least a tile wide and high, D % 4 == 0 -- goes
     # through token space (Engine.blend_tokens / scatter_tokens); decided on the first map, checked per view
     token_grid = (tuple(first_map.shape[:2]) if (token_space and upsample == "nearest" and encoder is None
@@ -596,7 +707,7 @@ def _plan(job: _Job, pipeline, token_space, fuse_small, fuse_encoder, encoder_in
 def _run_pipelined(job: _Job, plan: _Plan, eng: Engine, allow_wide: bool, stream_safe: bool) -> Dict[str, int]:
     """The views through a ViewPipeline of plan.depth workspaces (eng's and new ones); returns the counters.  An overflow seen
     after view 2 or by a later probe (every OVERFLOW_CHECK_EVERY views) ends the pass early: the counters then show it."""
-    (means, quats, scales, opacities), F, d, sf, sd, feature_fn, ids, _, _, width, height, _, encoder, upsample, pwf = job
+    (means, _, _, _), F, d, sf, sd, _, ids, _, _, width, height, _, encoder, upsample, _, render = job
     n, first_map = means.shape[0], plan.first_map
     pipe = ViewPipeline(n, width, height, means.device, scatter_dim=F.shape[1], token_grid=plan.token_grid,
                         split_encoder=plan.split, allow_wide=allow_wide, fuse_small=plan.fuse_small,
@@ -605,10 +716,15 @@ def _run_pipelined(job: _Job, plan: _Plan, eng: Engine, allow_wide: bool, stream
                                                 isect_cap=eng.isect_cap, pair_cap=eng.pair_cap)
                                          for _ in range(plan.depth - 1)])
     views = [eng.view(job.vm_host[v], job.K_host, width, height, **job.camera) for v in ids]
+    # (a weight map and an image are made on the caller's stream right before their view's front is enqueued; view 0's map may
+    # exist already: _plan rendered that view by itself)
+    renders = _Renders(pipe, job, views, skip_first=first_map is not None)
+    front = renders.front
 
-    def front(j):  # (a weight map is made on the caller's stream right before its view's front is enqueued)
-        pipe.front(views[j], means, quats, scales, opacities, d, sd,
-                   pixel_weights=pwf(ids[j]) if pwf is not None else None)
+    def fmap(j):  # view j's map, made on torch's current stream (behind the view's render)
+        if render is not None and j == 0 and first_map is not None:
+            return first_map  # (a job that renders has view 0's image from _plan only: its map is not made twice)
+        return _call_fn(job, ids[j], renders.take(j))
 
     for j in range(min(pipe.lookahead, len(ids))):
         front(j)
@@ -631,7 +747,7 @@ def _run_pipelined(job: _Job, plan: _Plan, eng: Engine, allow_wide: bool, stream
             front(i + pipe.lookahead)
         pipe.wait_for_slot()  # (view-per-stream schedule only: the host stays at most `depth` maps ahead)
         if enc_blend or staging:  # the encoder inside the fused blend + scatter kernel or the scatter kernel's staging
-            feats, fenc = (first_map if i == 0 else feature_fn(v)), encoder
+            feats, fenc = (first_map if i == 0 else fmap(i)), encoder
             if staging and not Engine.can_fuse_encoder(feats, encoder):
                 feats, fenc = eng.encode_map(feats, encoder), None
             pipe.scatter(feats, F, d, sf, sd, encoder=fenc)
@@ -639,15 +755,15 @@ def _run_pipelined(job: _Job, plan: _Plan, eng: Engine, allow_wide: bool, stream
         if encoder is not None:
             feats, after = ahead
             if i + 1 < len(ids):
-                ahead = pipe.encode_ahead(feature_fn(ids[i + 1]), encoder)
+                ahead = pipe.encode_ahead(fmap(i + 1), encoder)
         elif stream_safe:
             # (view-per-stream schedule: the feature function runs on the stream that consumes its map)
             with torch.cuda.stream(pipe.scatter_stream()):
-                feats, after = feature_fn(v), None
+                feats, after = fmap(i), None
         elif upsample == "nearest" and i == 0:
             feats, after = first_map, None
         else:
-            feats, after = feature_fn(v), None  # on the caller's stream; scatter() waits for it with an event
+            feats, after = fmap(i), None  # on the caller's stream; scatter() waits for it with an event
         pipe.scatter(feats, F, d, sf, sd, upsample=upsample, after=after, ready=encoder is None and stream_safe)
     stats = pipe.stats()
     pipe.release()
@@ -657,6 +773,8 @@ def _run_pipelined(job: _Job, plan: _Plan, eng: Engine, allow_wide: bool, stream
 def _run_serial(job: _Job, eng: Engine, fuse_small: bool, token_space: bool) -> Dict[str, int]:
     """The views one after the other on the caller's stream; returns the counters (synchronises)."""
     accum = torch.zeros(32, dtype=torch.uint8, device=job.F.device)
+    if job.render is not None:
+        return _run_serial_rendered(job, eng, fuse_small, token_space, accum)
     for v in job.view_ids:
         feats = job.feature_fn(v)
         if job.encoder is not None:
@@ -674,6 +792,21 @@ def _run_serial(job: _Job, eng: Engine, fuse_small: bool, token_space: bool) -> 
             eng.bin_sort(view)
             _blend_and_scatter(eng, view, feats, job.F, job.d, job.sf, job.sd, job.upsample, fuse=fuse_small,
                                tokens=token_space, pw=pw)
+        eng.accumulate_stats(accum)
+    return Engine.decode_stats(accum)
+
+
+def _run_serial_rendered(job: _Job, eng: Engine, fuse_small: bool, token_space: bool, accum: torch.Tensor) -> Dict[str, int]:
+    """_run_serial of a job that renders: per view project, bin_sort, render_pixels, feature_fn(v, image), then the blend and
+    scatter that suit the map (never gwbp_backproject_view: the map exists only after the front)."""
+    for v in job.view_ids:
+        view = eng.view(job.vm_host[v], job.K_host, job.width, job.height, **job.camera)
+        feats = job.feature_fn(v, _render_view(eng, job, v, view))
+        if job.encoder is not None:
+            feats = eng.encode_map(feats, job.encoder)
+        pw = job.pixel_weight_fn(v) if job.pixel_weight_fn is not None else None
+        _blend_and_scatter(eng, view, feats, job.F, job.d, job.sf, job.sd, job.upsample, fuse=fuse_small, tokens=token_space,
+                           pw=pw)
         eng.accumulate_stats(accum)
     return Engine.decode_stats(accum)
 
@@ -714,7 +847,8 @@ def create_feature_field(means, quats, scales, opacities, viewmats, K, width: in
                          encoder_in_blend: Optional[bool] = None, token_space: bool = True,
                          encoder_split: Optional[bool] = None, camera_model: str = "pinhole",
                          rasterize_mode: str = "classic",
-                         pixel_weight_fn: Optional[Callable[[int], torch.Tensor]] = None):
+                         pixel_weight_fn: Optional[Callable[[int], torch.Tensor]] = None,
+                         render_colors: Optional[torch.Tensor] = None, sh_degree: Optional[int] = None):
     """Build the [N, dim_out] per-Gaussian feature field.
 
     means/quats/scales/opacities: post-activation Gaussians (backproject.py:55-57), device tensors.
@@ -773,7 +907,19 @@ def create_feature_field(means, quats, scales, opacities, viewmats, K, width: in
     schedule above runs its weighted blend (the serial path then never takes gwbp_backproject_view); a row whose d is 0
     finalises to 0, and reduction="mean" keeps its scales.  It is called on the caller's stream up to `pipeline` views before
     the view's feature_fn, and the map must not be overwritten before that view has been scattered.
+    render_colors / sh_degree: the reference's per-view loop renders each view (rasterization(..., colors_all, sh_degree=3),
+    backproject.py:89-100) and runs the 2-D network on that RENDER.  With render_colors ([N, 3] float32 colours, or [N, K, 3] SH
+    coefficients with sh_degree 0..3, meaning what rasterization()'s colors / sh_degree mean) the front stage that projects and
+    sorts the view for the lift also renders it, and the callback is called as feature_fn(v, image): image is a fresh contiguous
+    [height, width, 3] float32 device tensor that the caller owns and may keep, equal bit for bit to
+    rasterization(means, quats, scales, opacities, render_colors, viewmats[v][None], K[None], width, height, sh_degree=sh_degree,
+    camera_model=..., rasterize_mode=...)[0][0] (no background; unweighted whatever pixel_weight_fn is).  The storing and token
+    blends composite it while they blend (gwbp_blend_*_rgb); the fused blend + scatter schedules render it with render_pixels on
+    the same workspace before their blend.  Not with view_fn.
+    feature_fn may be called more than once per view: a workspace overflow restarts the job with larger capacities, and every
+    view's map is asked for again.
     """
+    render = _render_of(render_colors, sh_degree, means.shape[0], means.device, view_fn)
     dist, rank, world = _dist()
     n = means.shape[0]
     d_out = dim if encoder is None else encoder.shape[1]
@@ -785,7 +931,7 @@ def create_feature_field(means, quats, scales, opacities, viewmats, K, width: in
     job = _Job((means, quats, scales, opacities), F, d, sf, sd, feature_fn,
                list(views) if views is not None else view_shard(viewmats.shape[0], rank, world),
                viewmats.detach().cpu(), K.detach().cpu(), width, height,
-               dict(camera_model=camera_model, rasterize_mode=rasterize_mode), encoder, upsample, pixel_weight_fn)
+               dict(camera_model=camera_model, rasterize_mode=rasterize_mode), encoder, upsample, pixel_weight_fn, render)
     if view_fn is not None and pixel_weight_fn is not None:
         raise ValueError("view_fn takes a feature map only: it cannot apply pixel_weight_fn's weights")
 
@@ -795,7 +941,7 @@ def create_feature_field(means, quats, scales, opacities, viewmats, K, width: in
         eng = engine or Engine(n, width, height, device=means.device, tight_binning=True)  # same F and d, shorter tile lists
         split_allowed = True
         for attempt in range(6):  # a capacity overflow invalidates the accumulators: grow the workspace, start over
-            plan = _plan(job, pipeline, token_space, fuse_small, fuse_encoder, encoder_in_blend, encoder_split, split_allowed)
+            plan = _plan(job, pipeline, token_space, fuse_small, fuse_encoder, encoder_in_blend, encoder_split, split_allowed, eng)
             pipeline = plan.pipelined and pipeline  # (a late hardware-queue request downgrades the job once)
             stats = (_run_pipelined(job, plan, eng, allow_wide, feature_fn_stream_safe) if plan.pipelined
                      else _run_serial(job, eng, fuse_small, token_space))
@@ -857,16 +1003,15 @@ class _LabelPipeline(ViewPipeline):
 def _run_labels_pipelined(job: _Job, eng: Engine, depth: int, num_classes: int) -> Dict[str, int]:
     """create_label_field's views through a _LabelPipeline of `depth` workspaces; an overflow seen after view 2 or by a later
     probe ends the pass early (as in _run_pipelined)."""
-    (means, quats, scales, opacities), F, d, sf, sd, label_fn, ids, _, _, width, height, _, _, upsample, pwf = job
+    (means, _, _, _), F, d, sf, sd, _, ids, _, _, width, height, _, _, upsample, _, _ = job
     n = means.shape[0]
     pipe = _LabelPipeline(n, width, height, means.device, num_classes=num_classes,
                           engines=[eng] + [Engine(n, width, height, device=means.device, tight_binning=eng.tight_binning,
                                                   isect_cap=eng.isect_cap, pair_cap=eng.pair_cap) for _ in range(depth - 1)])
     views = [eng.view(job.vm_host[v], job.K_host, width, height, **job.camera) for v in ids]
 
-    def front(j):  # (a weight map is made on the caller's stream right before its view's front is enqueued)
-        pipe.front(views[j], means, quats, scales, opacities, d, sd,
-                   pixel_weights=pwf(ids[j]) if pwf is not None else None)
+    renders = _Renders(pipe, job, views)  # (weight maps and images are made on the caller's stream before their view's front)
+    front, image_of = renders.front, renders.take
 
     for j in range(min(pipe.lookahead, len(ids))):
         front(j)
@@ -882,24 +1027,38 @@ def _run_labels_pipelined(job: _Job, eng: Engine, depth: int, num_classes: int) 
             probe = pipe.stats_async()
         if i + pipe.lookahead < len(ids):
             front(i + pipe.lookahead)
-        pipe.scatter(label_fn(v), F, d, sf, sd, upsample=upsample)
+        pipe.scatter(_call_fn(job, v, image_of(i)), F, d, sf, sd, upsample=upsample)
     stats = pipe.stats()
     pipe.release()
     return stats
+
+
+def _blend_rendered(eng: Engine, job: _Job, v: int, view) -> torch.Tensor:
+    """The serial label and mask paths' weight-store blend of a projected, sorted view (weighted by pixel_weight_fn) with the RGB
+    composite of job.render; returns the image."""
+    cols = eng.view_colors(view, job.gaussians[0], *job.render)
+    pw = job.pixel_weight_fn(v) if job.pixel_weight_fn is not None else None
+    return eng.blend_weights_rgb(view, cols, pixel_weights=pw)[0]
 
 
 def _run_labels_serial(job: _Job, eng: Engine, num_classes: int) -> Dict[str, int]:
     """create_label_field's views one after the other on the caller's stream; the label kernel adds d too (synchronises)."""
     accum = torch.zeros(32, dtype=torch.uint8, device=job.F.device)
     for v in job.view_ids:
-        labels = job.feature_fn(v)
         view = eng.view(job.vm_host[v], job.K_host, job.width, job.height, **job.camera)
-        eng.project(view, *job.gaussians)
-        eng.bin_sort(view)
-        if job.pixel_weight_fn is not None:
-            eng.blend_weighted(view, job.pixel_weight_fn(v))
+        if job.render is not None:  # the blend composites the render; the labels are made from it behind the blend
+            eng.project(view, *job.gaussians)
+            eng.bin_sort(view)
+            image = _blend_rendered(eng, job, v, view)
+            labels = job.feature_fn(v, image)
         else:
-            eng.blend_weights(view)
+            labels = job.feature_fn(v)
+            eng.project(view, *job.gaussians)
+            eng.bin_sort(view)
+            if job.pixel_weight_fn is not None:
+                eng.blend_weighted(view, job.pixel_weight_fn(v))
+            else:
+                eng.blend_weights(view)
         eng.scatter_labels(view, labels, job.F, job.d, num_classes, job.sf, job.sd, upsample=job.upsample)
         eng.accumulate_stats(accum)
     return Engine.decode_stats(accum)
@@ -915,7 +1074,8 @@ def create_label_field(means, quats, scales, opacities, viewmats, K, width: int,
                        label_fn: Callable[[int], torch.Tensor], num_classes: int, *, upsample: Optional[str] = None,
                        views: Optional[Sequence[int]] = None, pipeline: bool = True, gather: bool = True,
                        return_partials: bool = False, camera_model: str = "pinhole", rasterize_mode: str = "classic",
-                       engine: Optional[Engine] = None, pixel_weight_fn: Optional[Callable[[int], torch.Tensor]] = None):
+                       engine: Optional[Engine] = None, pixel_weight_fn: Optional[Callable[[int], torch.Tensor]] = None,
+                       render_colors: Optional[torch.Tensor] = None, sh_degree: Optional[int] = None):
     """Lift per-view integer LABEL maps (a segmenter's class or instance ids, a binary mask) onto the Gaussians: the [N, num_classes]
     field P[g, k] = F[g, k] / d[g] (0 where d[g] == 0) with
         F[g, k] = sum_v sum_p w_g(p) [L_v(p) == k],    d[g] = sum_v sum_p w_g(p),
@@ -930,16 +1090,19 @@ def create_label_field(means, quats, scales, opacities, viewmats, K, width: int,
     views, pipeline (True, an int >= 2 workspaces, or False), gather, camera_model, rasterize_mode, engine: as create_feature_field.
     return_partials: also return (F_rows, d, stats) -- the summed accumulators (this rank's row block of F, all of d).
     pixel_weight_fn: v -> c_v, the view's [height, width] weight map (as create_feature_field's): F and d then sum w_g(p) c_v(p),
-    so each row's fractions sum to 1 over the WEIGHTED pixels (pixels of weight 0 count for no class and not in d)."""
+    so each row's fractions sum to 1 over the WEIGHTED pixels (pixels of weight 0 count for no class and not in d).
+    render_colors / sh_degree: as create_feature_field's -- label_fn is then called as label_fn(v, image) with the view's RGB
+    render, made by the front stage's blend; label_fn may be called more than once per view (an overflow restarts the job)."""
     if upsample not in (None, "nearest"):
         raise ValueError(f"upsample must be None or 'nearest' for label maps, got {upsample!r}")
+    render = _render_of(render_colors, sh_degree, means.shape[0], means.device)
     dist, rank, world = _dist()
     n = means.shape[0]
     F, d, F_store = alloc_accumulators(n, int(num_classes), means.device, world)
     job = _Job((means, quats, scales, opacities), F, d, 1.0, 1.0, label_fn,
                list(views) if views is not None else view_shard(viewmats.shape[0], rank, world),
                viewmats.detach().cpu(), K.detach().cpu(), width, height,
-               dict(camera_model=camera_model, rasterize_mode=rasterize_mode), None, upsample, pixel_weight_fn)
+               dict(camera_model=camera_model, rasterize_mode=rasterize_mode), None, upsample, pixel_weight_fn, render)
     pipelined = bool(pipeline) and len(job.view_ids) > 1
     if pipelined and _lib.hw_queues_late():
         warnings.warn("gsbp_amd was imported after the HIP runtime had started: create_label_field runs its views on ONE stream",
@@ -987,9 +1150,9 @@ class _MaskPipeline(_LabelPipeline):
         e.accumulate_stats(self.accums[0])
 
 
-def _mask_of(mask_fn, v: int, dim: int):
-    """mask_fn(v) -> (labels, table), the table checked against the field's width."""
-    out = mask_fn(v)
+def _mask_of(mask_fn, v: int, dim: int, render: bool = False, image=None):
+    """mask_fn(v) -> (labels, table) (mask_fn(v, image) for a job that renders), the table checked against the field's width."""
+    out = mask_fn(v, image) if render else mask_fn(v)
     if not (isinstance(out, (tuple, list)) and len(out) == 2):
         raise ValueError(f"mask_fn({v}) must return (labels, table)")
     labels, table = out
@@ -1005,7 +1168,7 @@ def _mask_spills(engines) -> int:
 
 def _run_masks_pipelined(job: _Job, eng: Engine, depth: int, dim: int) -> Dict[str, int]:
     """create_mask_feature_field's views through a _MaskPipeline of `depth` workspaces (the schedule of _run_labels_pipelined)."""
-    (means, quats, scales, opacities), F, d, sf, sd, mask_fn, ids, _, _, width, height, _, _, upsample, pwf = job
+    (means, _, _, _), F, d, sf, sd, mask_fn, ids, _, _, width, height, _, _, upsample, _, render = job
     n = means.shape[0]
     engines = [eng] + [Engine(n, width, height, device=means.device, tight_binning=eng.tight_binning,
                               isect_cap=eng.isect_cap, pair_cap=eng.pair_cap) for _ in range(depth - 1)]
@@ -1013,9 +1176,8 @@ def _run_masks_pipelined(job: _Job, eng: Engine, depth: int, dim: int) -> Dict[s
     pipe = _MaskPipeline(n, width, height, means.device, engines=engines)
     views = [eng.view(job.vm_host[v], job.K_host, width, height, **job.camera) for v in ids]
 
-    def front(j):
-        pipe.front(views[j], means, quats, scales, opacities, d, sd,
-                   pixel_weights=pwf(ids[j]) if pwf is not None else None)
+    renders = _Renders(pipe, job, views)  # (weight maps and images are made on the caller's stream before their view's front)
+    front, image_of = renders.front, renders.take
 
     for j in range(min(pipe.lookahead, len(ids))):
         front(j)
@@ -1031,7 +1193,7 @@ def _run_masks_pipelined(job: _Job, eng: Engine, depth: int, dim: int) -> Dict[s
             probe = pipe.stats_async()
         if i + pipe.lookahead < len(ids):
             front(i + pipe.lookahead)
-        pipe.scatter(_mask_of(mask_fn, v, dim), F, d, sf, sd, upsample=upsample)
+        pipe.scatter(_mask_of(mask_fn, v, dim, render is not None, image_of(i)), F, d, sf, sd, upsample=upsample)
     stats = pipe.stats()
     pipe.release()
     stats["mask_spilled"] = _mask_spills(engines) - spilled0
@@ -1043,14 +1205,20 @@ def _run_masks_serial(job: _Job, eng: Engine, dim: int) -> Dict[str, int]:
     accum = torch.zeros(32, dtype=torch.uint8, device=job.F.device)
     spilled0 = _mask_spills([eng])
     for v in job.view_ids:
-        labels, table = _mask_of(job.feature_fn, v, dim)
-        view = eng.view(job.vm_host[v], job.K_host, job.width, job.height, **job.camera)
-        eng.project(view, *job.gaussians)
-        eng.bin_sort(view)
-        if job.pixel_weight_fn is not None:
-            eng.blend_weighted(view, job.pixel_weight_fn(v))
+        if job.render is not None:  # (as _run_labels_serial)
+            view = eng.view(job.vm_host[v], job.K_host, job.width, job.height, **job.camera)
+            eng.project(view, *job.gaussians)
+            eng.bin_sort(view)
+            labels, table = _mask_of(job.feature_fn, v, dim, True, _blend_rendered(eng, job, v, view))
         else:
-            eng.blend_weights(view)
+            labels, table = _mask_of(job.feature_fn, v, dim)
+            view = eng.view(job.vm_host[v], job.K_host, job.width, job.height, **job.camera)
+            eng.project(view, *job.gaussians)
+            eng.bin_sort(view)
+            if job.pixel_weight_fn is not None:
+                eng.blend_weighted(view, job.pixel_weight_fn(v))
+            else:
+                eng.blend_weights(view)
         eng.scatter_mask_features(view, labels, table, job.F, job.d, job.sf, job.sd, upsample=job.upsample)
         eng.accumulate_stats(accum)
     stats = Engine.decode_stats(accum)
@@ -1063,7 +1231,8 @@ def create_mask_feature_field(means, quats, scales, opacities, viewmats, K, widt
                               upsample: Optional[str] = None, views: Optional[Sequence[int]] = None, pipeline: bool = True,
                               gather: bool = True, return_partials: bool = False, camera_model: str = "pinhole",
                               rasterize_mode: str = "classic", engine: Optional[Engine] = None,
-                              pixel_weight_fn: Optional[Callable[[int], torch.Tensor]] = None):
+                              pixel_weight_fn: Optional[Callable[[int], torch.Tensor]] = None,
+                              render_colors: Optional[torch.Tensor] = None, sh_degree: Optional[int] = None):
     """Build the [N, dim] feature field from MASK-POOLED features: per view a segmenter's mask or instance map L_v and one
     embedding per mask, table E_v [M_v, dim] (SAM masks with a CLIP / LSeg vector each, superpixel-pooled DINO features).  The
     result equals create_feature_field(feature_fn=lambda v: E_v[L_v]) -- a zero row wherever a label lies outside [0, M_v), whose
@@ -1078,9 +1247,12 @@ def create_mask_feature_field(means, quats, scales, opacities, viewmats, K, widt
     reduction: "sum" or "mean", with create_feature_field's scales (the D of 1/(H W D) is dim).
     views, pipeline (True, an int >= 2 workspaces, or False), gather, return_partials, camera_model, rasterize_mode, engine,
     pixel_weight_fn: as create_feature_field.  stats (return_partials) gains "mask_spilled": records with more than four
-    distinct labels, whose rest was added with atomics (F is then no longer the same bit for bit from run to run)."""
+    distinct labels, whose rest was added with atomics (F is then no longer the same bit for bit from run to run).
+    render_colors / sh_degree: as create_feature_field's -- mask_fn is then called as mask_fn(v, image) with the view's RGB
+    render, made by the front stage's blend; mask_fn may be called more than once per view (an overflow restarts the job)."""
     if upsample not in (None, "nearest"):
         raise ValueError(f"upsample must be None or 'nearest' for mask maps, got {upsample!r}")
+    render = _render_of(render_colors, sh_degree, means.shape[0], means.device)
     if reduction not in ("sum", "mean"):
         raise ValueError(reduction)
     dim = int(dim)
@@ -1093,7 +1265,7 @@ def create_mask_feature_field(means, quats, scales, opacities, viewmats, K, widt
     job = _Job((means, quats, scales, opacities), F, d, sf, sd, mask_fn,
                list(views) if views is not None else view_shard(viewmats.shape[0], rank, world),
                viewmats.detach().cpu(), K.detach().cpu(), width, height,
-               dict(camera_model=camera_model, rasterize_mode=rasterize_mode), None, upsample, pixel_weight_fn)
+               dict(camera_model=camera_model, rasterize_mode=rasterize_mode), None, upsample, pixel_weight_fn, render)
     pipelined = bool(pipeline) and len(job.view_ids) > 1
     if pipelined and _lib.hw_queues_late():
         warnings.warn("gsbp_amd was imported after the HIP runtime had started: create_mask_feature_field runs its views on ONE "

@@ -104,13 +104,24 @@ struct FusedArgs { // kFused only
 };
 
 // The weighted kernels (PIXW = true) take BlendArgs<true>, i.e. FusedArgs plus the weight map (PixW, gwbp_dev.h); BlendArgs<false>
-// has FusedArgs' layout byte for byte, so the unweighted instantiations keep their argument block and their code.
-template <bool PIXW>
+// has FusedArgs' layout byte for byte, so the unweighted instantiations keep their argument block and their code.  The rendering
+// kernels (RENDER = true: kStore / kHalves / kToken with an RGB composite, gwbp_blend_*_rgb) append the colour table and the image
+// (RgbOut, gwbp_dev.h).
+template <bool PIXW, bool RENDER = false>
 struct BlendArgs : FusedArgs {
 };
 template <>
-struct BlendArgs<true> : FusedArgs {
+struct BlendArgs<true, false> : FusedArgs {
     PixW pw;
+};
+template <>
+struct BlendArgs<false, true> : FusedArgs {
+    RgbOut rgb;
+};
+template <>
+struct BlendArgs<true, true> : FusedArgs {
+    PixW pw;
+    RgbOut rgb;
 };
 static_assert(sizeof(BlendArgs<false>) == sizeof(FusedArgs), "the unweighted kernels' argument block must not change");
 
@@ -374,14 +385,21 @@ __device__ __forceinline__ void encode_quarter(const float *feats, int64_t fs_y,
 // without it; what the blend adds or stores is w c(p) instead of w, and only for pixels with c(p) != 0 (the store mask of a
 // quarter is m_valid & ballot(c != 0), formed once per tile).  Every consumer downstream -- the scatter kernels through the
 // entries, headers and record sums, d, the token-quadrant sums, the fused kernels' register sums -- is thereby weighted.
-template <int MODE, int WAVES = 1, bool PIXW = false>
+// RENDER (kStore, kHalves, kToken; gwbp_blend_*_rgb): the blend also composites the view's RGB render while it runs,
+//   image[p] = sum_g w_g(p) colors[g]   with the UNWEIGHTED w = alpha T,
+// accumulated front to back with the fmaf and the select of k_render_px (render.hip), so the image equals gwbp_render_pixels' bit
+// for bit.  The batch's colours are staged in LDS beside its Gaussians (one 16-B broadcast read per contributing quarter), the
+// lane's four pixels get three accumulators each, and the image is written once at the end of the tile.  Everything else the
+// blend produces is unchanged: a weighted blend keeps blending the pixels of weight 0 (they are in the render), as it does
+// whenever it writes the alpha map.
+template <int MODE, int WAVES = 1, bool PIXW = false, bool RENDER = false>
 __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_blend(ViewDev V, const u32 *__restrict__ tile_offsets,
                                               const u32 *__restrict__ vals, const G2D *__restrict__ g2d,
                                               Counters *__restrict__ ctr, Header *__restrict__ headers,
                                               u32 *__restrict__ hdr_count, WPair *__restrict__ wpool, u32 pair_cap,
                                               u32 *__restrict__ shards, const u32 *__restrict__ tile_order, float *__restrict__ alphas,
                                               int dbg_arg, int prio,
-                                              float *__restrict__ d_out, float scale_d, BlendArgs<PIXW> fu)
+                                              float *__restrict__ d_out, float scale_d, BlendArgs<PIXW, RENDER> fu)
 {
 #ifdef GWBP_PROFILE
     const int dbg = dbg_arg; // ablation bits (make PROFILE=1 only; results invalid)
@@ -389,6 +407,8 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 8
     constexpr int dbg = 0;   // the product kernel does not even contain the ablation branches
     (void)dbg_arg;
 #endif
+    static_assert(!RENDER || ((MODE == kStore || MODE == kHalves || MODE == kToken) && WAVES == 1),
+                  "the RGB composite is built for the one-wave storing and token blends");
     constexpr bool WSUM = MODE == kHalves; // the record's weight sum in its header (+ d[gid] right here)
     constexpr bool PC = MODE == kFusedPC;
     constexpr bool FUSED = MODE == kFused || MODE == kFusedEnc || PC;
@@ -399,11 +419,13 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 8
     __shared__ float4 s_b_[BW][kBatch]; // ca, cb, cc, strip mask
     __shared__ float s_thr_[BW][kBatch]; // ln(255 o) + margin: sigma above this cannot reach alpha >= 1/255
     __shared__ u32 s_pos_[TOKEN ? WAVES : 1][TOKEN ? kBatch : 1]; // kToken: emit position of the (Gaussian, tile) pair
+    __shared__ float4 s_rgb_[RENDER ? BW : 1][RENDER ? kBatch : 1]; // RENDER: the Gaussian's colour (r, g, b, -)
     const int wave = WAVES > 1 ? (int)uniform(threadIdx.x >> 6) : 0;
     const int bw = PC ? max(wave - kPcProd, 0) : wave;
     float4 *const s_a = s_a_[bw], *const s_b = s_b_[bw];
     float *const s_thr = s_thr_[bw];
     u32 *const s_pos = s_pos_[TOKEN ? wave : 0];
+    float4 *const s_rgb = s_rgb_[RENDER ? bw : 0];
     const int lane = (int)(threadIdx.x & 63u);
 
     const int n_tiles_all = V.tile_w * V.tile_h;
@@ -713,7 +735,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 8
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 cnz[q] = __ballot(cpix[q] != 0.f);
-                if (!alphas)
+                if (!alphas && !RENDER)
                     T[q] = cpix[q] != 0.f ? T[q] : 0.f;
             }
             if constexpr (FUSED) {
@@ -723,6 +745,13 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 8
                 for (int q = 0; q < 4; ++q)
                     s_c[q * 64 + lane] = cpix[q];
             }
+        }
+        // RENDER: the lane's four pixels' colour sums (k_render_px's acc)
+        float rgb[RENDER ? 4 : 1][3];
+        if constexpr (RENDER) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                rgb[q][0] = rgb[q][1] = rgb[q][2] = 0.f;
         }
         for (u32 batch = beg; batch < end; batch += kBatch) {
             // quarters that still have a live pixel; stop when the whole tile has terminated (gsplat: all threads done)
@@ -765,6 +794,10 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 8
                 s_b[lane] = make_float4(b.x, b.y, b.z, __int_as_float((int)smask));
                 // alpha = o exp(-sigma) >= 1/255  <=>  sigma <= ln(255 o); 1e-3 absorbs the error of __logf and exp_neg
                 s_thr[lane] = L + 1e-3f;
+                if constexpr (RENDER) {
+                    const float *cp = fu.rgb.colors + (size_t)gid * 3;
+                    s_rgb[lane] = make_float4(cp[0], cp[1], cp[2], 0.f);
+                }
                 if constexpr (TOKEN) { // this (Gaussian, tile) pair's emit position: k_emit walked the rectangle row-major from estart
                     const uint2 rc = fu.rect[gid];
                     const u32 rx0 = rc.x & 0xFFFFu, rx1 = rc.x >> 16, ry0 = rc.y & 0xFFFFu;
@@ -806,6 +839,14 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 8
                         T[q] = mask_select(m_valid, next_T, T_else);
                         Tout[q] = mask_select(m_valid, next_T, Tout[q]);
                         m[q] = m_valid;
+                        if constexpr (RENDER) { // the composite: k_render_px's valid ? fmaf(w, c, acc) : acc, before any weighting
+                            if (m_valid != 0ull) {
+                                const float4 c = s_rgb[j];
+                                rgb[q][0] = mask_select(m_valid, __builtin_fmaf(w[q], c.x, rgb[q][0]), rgb[q][0]);
+                                rgb[q][1] = mask_select(m_valid, __builtin_fmaf(w[q], c.y, rgb[q][1]), rgb[q][1]);
+                                rgb[q][2] = mask_select(m_valid, __builtin_fmaf(w[q], c.z, rgb[q][2]), rgb[q][2]);
+                            }
+                        }
                         if constexpr (PIXW) { // what is added or stored: w c, at pixels with c != 0 only
                             // (fused modes: an atomic load, so that the compiler does not hoist the four reads out of the loop
                             // into the registers this is about)
@@ -970,6 +1011,16 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 8
                 const int iy = iy0 + 4 * q;
                 if (ix < V.W && iy < V.H)
                     alphas[(size_t)iy * V.W + ix] = 1.0f - Tout[q];
+            }
+        }
+        if constexpr (RENDER) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int iy = iy0 + 4 * q;
+                if (ix < V.W && iy < V.H) {
+                    float *o = fu.rgb.image + ((size_t)iy * V.W + ix) * 3;
+                    o[0] = rgb[q][0], o[1] = rgb[q][1], o[2] = rgb[q][2];
+                }
             }
         }
         if constexpr (!PC)
@@ -1220,11 +1271,46 @@ static BlendArgs<true> weighted_args(const FusedArgs &fu, const PixW &pw)
     a.pw = pw;
     return a;
 }
+static BlendArgs<false, true> render_args(const FusedArgs &fu, const RgbOut &rgb)
+{
+    BlendArgs<false, true> a;
+    static_cast<FusedArgs &>(a) = fu;
+    a.rgb = rgb;
+    return a;
+}
+static BlendArgs<true, true> weighted_render_args(const FusedArgs &fu, const PixW &pw, const RgbOut &rgb)
+{
+    BlendArgs<true, true> a;
+    static_cast<FusedArgs &>(a) = fu;
+    a.pw = pw;
+    a.rgb = rgb;
+    return a;
+}
+
+// One launch of k_blend<MODE, 1, *, true>: the storing or token blend with the RGB composite (gwbp_blend_*_rgb).
+template <int MODE>
+static void launch_blend_render(const Layout &L, const Ws &W, const ViewDev &V, float *alphas, float *d, float scale_d,
+                                const FusedArgs &fu, const PixW *pw, const RgbOut &rgb, int ablate, int prio, size_t lds,
+                                hipStream_t s)
+{
+    const int n_tiles = V.tile_w * V.tile_h;
+    const int fin = sort_passes(n_tiles) & 1;
+    if (pw)
+        hipLaunchKernelGGL((k_blend<MODE, 1, true, true>), dim3(n_tiles), dim3(64), lds, s, V, W.tile_offsets, W.vals[fin], W.g2d,
+                           W.counters, W.headers, W.hdr_count, W.wpool, (u32)L.pair_cap, W.shards, W.tile_order, alphas, ablate,
+                           prio, d, scale_d, weighted_render_args(fu, *pw, rgb));
+    else
+        hipLaunchKernelGGL((k_blend<MODE, 1, false, true>), dim3(n_tiles), dim3(64), lds, s, V, W.tile_offsets, W.vals[fin], W.g2d,
+                           W.counters, W.headers, W.hdr_count, W.wpool, (u32)L.pair_cap, W.shards, W.tile_order, alphas, ablate,
+                           prio, d, scale_d, render_args(fu, rgb));
+}
 
 int launch_blend(const Layout &L, const Ws &W, const ViewDev &V, float *alphas, float *d, float scale_d, hipStream_t s,
-                 const FeatMap *M, int D, float scale_f, float *F, const PixW *pw)
+                 const FeatMap *M, int D, float scale_f, float *F, const PixW *pw, const RgbOut *rgb)
 {
     const bool fused = M != nullptr;
+    if (rgb && fused)
+        return set_error(GWBP_EINVAL, "the RGB composite is part of the storing blends only (the fused blends run after the map)");
     FusedArgs fu = {};
     const bool fused_enc = fused && M->enc != nullptr;
     if (fused) {
@@ -1305,6 +1391,10 @@ int launch_blend(const Layout &L, const Ws &W, const ViewDev &V, float *alphas, 
 #undef GWBP_QUARTER
     } else if (fused)
         GWBP_BLEND(kFused);
+    else if (rgb && (L.flags & GWBP_FLAG_NARROW_SCATTER))
+        launch_blend_render<kStore>(L, W, V, alphas, d, scale_d, fu, pw, *rgb, ablate, prio, (size_t)extra_lds, s);
+    else if (rgb)
+        launch_blend_render<kHalves>(L, W, V, alphas, d, scale_d, fu, pw, *rgb, ablate, prio, (size_t)extra_lds, s);
     else if (L.flags & GWBP_FLAG_NARROW_SCATTER)
         GWBP_BLEND(kStore);
     else
@@ -1322,7 +1412,7 @@ int launch_blend(const Layout &L, const Ws &W, const ViewDev &V, float *alphas, 
 // workspace's header region (16 of its 64 B per intersection), zeroed for this view's intersections first -- so a record that a
 // weight map left without weight (no line written) reads as zero in k_token_apply.
 int launch_blend_tokens(const Layout &L, const Ws &W, const ViewDev &V, float *alphas, const int32_t *ymap, const int32_t *xmap,
-                        hipStream_t s, const PixW *pw)
+                        hipStream_t s, const PixW *pw, const RgbOut *rgb)
 {
     if (!ymap || !xmap)
         return set_error(GWBP_EINVAL, "gwbp_blend_tokens needs both index maps");
@@ -1335,7 +1425,9 @@ int launch_blend_tokens(const Layout &L, const Ws &W, const ViewDev &V, float *a
     const int n_tiles = V.tile_w * V.tile_h;
     const int fin = sort_passes(n_tiles) & 1;
     const int ablate = profile_knob("GWBP_ABLATE_BLEND");
-    if (pw)
+    if (rgb)
+        launch_blend_render<kToken>(L, W, V, alphas, nullptr, 0.f, fu, pw, *rgb, ablate, prio, 0, s);
+    else if (pw)
         hipLaunchKernelGGL((k_blend<kToken, 1, true>), dim3(n_tiles), dim3(64), 0, s, V, W.tile_offsets, W.vals[fin], W.g2d,
                            W.counters, W.headers, W.hdr_count, W.wpool, (u32)L.pair_cap, W.shards, W.tile_order, alphas, ablate,
                            prio, nullptr, 0.f, weighted_args(fu, *pw));

@@ -243,6 +243,20 @@ static int check_pixel_weights(const gwbp_pixel_weights *pw, PixW *out, const Pi
 using namespace gwbp;
 static_assert(sizeof(gwbp_pixel_weights) == 32, "gwbp_pixel_weights is part of the ABI");
 
+// The RGB composite of the gwbp_blend_*_rgb forms: both pointers or neither (*use = nullptr: the _ex function).
+static int check_rgb(const float *colors, float *image, RgbOut *out, const RgbOut **use)
+{
+    *use = nullptr;
+    if (!colors && !image)
+        return GWBP_OK;
+    if (!colors || !image)
+        return set_error(GWBP_EINVAL, "the RGB composite needs both colors [N,3] and image [H,W,3] (got %s colors, %s image)",
+                         colors ? "a" : "null", image ? "an" : "null");
+    out->colors = colors, out->image = image;
+    *use = out;
+    return GWBP_OK;
+}
+
 extern "C" {
 
 const char *gwbp_version(void)
@@ -324,10 +338,19 @@ int gwbp_blend_weights(const gwbp_caps *caps, void *workspace, size_t workspace_
 int gwbp_blend_weights_ex(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
                           float *alphas, const gwbp_pixel_weights *pixel_weights, void *stream)
 {
+    return gwbp_blend_weights_rgb(caps, workspace, workspace_bytes, view_host, alphas, pixel_weights, nullptr, nullptr, stream);
+}
+
+int gwbp_blend_weights_rgb(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                           float *alphas, const gwbp_pixel_weights *pixel_weights, const float *colors, float *image,
+                           void *stream)
+{
     PixW P;
     const PixW *pw;
+    RgbOut R;
+    const RgbOut *rgb;
     int rc = check_pixel_weights(pixel_weights, &P, &pw);
-    if (rc)
+    if (rc || (rc = check_rgb(colors, image, &R, &rgb)))
         return rc;
     Layout L;
     Ws W;
@@ -336,7 +359,7 @@ int gwbp_blend_weights_ex(const gwbp_caps *caps, void *workspace, size_t workspa
         return rc;
     if ((rc = make_view(view_host, caps, &V)))
         return rc;
-    return launch_blend(L, W, V, alphas, nullptr, 0.f, static_cast<hipStream_t>(stream), nullptr, 0, 1.0f, nullptr, pw);
+    return launch_blend(L, W, V, alphas, nullptr, 0.f, static_cast<hipStream_t>(stream), nullptr, 0, 1.0f, nullptr, pw, rgb);
 }
 
 int gwbp_blend_weights_d(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
@@ -348,10 +371,20 @@ int gwbp_blend_weights_d(const gwbp_caps *caps, void *workspace, size_t workspac
 int gwbp_blend_weights_d_ex(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
                             float *alphas, float scale_d, float *d, const gwbp_pixel_weights *pixel_weights, void *stream)
 {
+    return gwbp_blend_weights_d_rgb(caps, workspace, workspace_bytes, view_host, alphas, scale_d, d, pixel_weights, nullptr,
+                                    nullptr, stream);
+}
+
+int gwbp_blend_weights_d_rgb(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                             float *alphas, float scale_d, float *d, const gwbp_pixel_weights *pixel_weights,
+                             const float *colors, float *image, void *stream)
+{
     PixW P;
     const PixW *pw;
+    RgbOut R;
+    const RgbOut *rgb;
     int rc = check_pixel_weights(pixel_weights, &P, &pw);
-    if (rc)
+    if (rc || (rc = check_rgb(colors, image, &R, &rgb)))
         return rc;
     Layout L;
     Ws W;
@@ -362,7 +395,7 @@ int gwbp_blend_weights_d_ex(const gwbp_caps *caps, void *workspace, size_t works
         return rc;
     if (!d)
         return set_error(GWBP_EINVAL, "null d");
-    return launch_blend(L, W, V, alphas, d, scale_d, static_cast<hipStream_t>(stream), nullptr, 0, 1.0f, nullptr, pw);
+    return launch_blend(L, W, V, alphas, d, scale_d, static_cast<hipStream_t>(stream), nullptr, 0, 1.0f, nullptr, pw, rgb);
 }
 
 int gwbp_blend_scatter(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
@@ -435,10 +468,20 @@ int gwbp_blend_tokens_ex(const gwbp_caps *caps, void *workspace, size_t workspac
                          const int32_t *ymap, const int32_t *xmap, float *alphas, const gwbp_pixel_weights *pixel_weights,
                          void *stream)
 {
+    return gwbp_blend_tokens_rgb(caps, workspace, workspace_bytes, view_host, ymap, xmap, alphas, pixel_weights, nullptr, nullptr,
+                                 stream);
+}
+
+int gwbp_blend_tokens_rgb(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                          const int32_t *ymap, const int32_t *xmap, float *alphas, const gwbp_pixel_weights *pixel_weights,
+                          const float *colors, float *image, void *stream)
+{
     PixW P;
     const PixW *pw;
+    RgbOut R;
+    const RgbOut *rgb;
     int rc = check_pixel_weights(pixel_weights, &P, &pw);
-    if (rc)
+    if (rc || (rc = check_rgb(colors, image, &R, &rgb)))
         return rc;
     Layout L;
     Ws W;
@@ -447,7 +490,7 @@ int gwbp_blend_tokens_ex(const gwbp_caps *caps, void *workspace, size_t workspac
         return rc;
     if ((rc = make_view(view_host, caps, &V)))
         return rc;
-    return launch_blend_tokens(L, W, V, alphas, ymap, xmap, static_cast<hipStream_t>(stream), pw);
+    return launch_blend_tokens(L, W, V, alphas, ymap, xmap, static_cast<hipStream_t>(stream), pw, rgb);
 }
 
 int gwbp_scatter_tokens(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,

@@ -168,11 +168,17 @@ struct PixW {
 };
 // M != nullptr: the fused small-D form (gwbp_blend_scatter): F[gid, :D] and d are accumulated by the blend itself.
 // pw != nullptr: every blend form weighted by the map (what it adds or stores is w c(p)).
+// rgb != nullptr (storing and token blends only): the RGB composite of gwbp_blend_*_rgb, image[p] = sum_g alpha T colors[g].
+struct RgbOut {
+    const float *colors; // [N, 3]
+    float *image;        // [H, W, 3]
+};
 int launch_blend(const Layout &L, const Ws &W, const ViewDev &V, float *alphas, float *d, float scale_d, hipStream_t s,
-                 const FeatMap *M = nullptr, int D = 0, float scale_f = 1.0f, float *F = nullptr, const PixW *pw = nullptr);
+                 const FeatMap *M = nullptr, int D = 0, float scale_f = 1.0f, float *F = nullptr, const PixW *pw = nullptr,
+                 const RgbOut *rgb = nullptr);
 // token-space path of a nearest-upsampled low-resolution map (blend.hip: k_blend<kToken>; token.hip)
 int launch_blend_tokens(const Layout &L, const Ws &W, const ViewDev &V, float *alphas, const int32_t *ymap, const int32_t *xmap,
-                        hipStream_t s, const PixW *pw = nullptr);
+                        hipStream_t s, const PixW *pw = nullptr, const RgbOut *rgb = nullptr);
 int launch_zero_omega(const Layout &L, const Ws &W, hipStream_t s);
 int launch_token_apply(const Layout &L, const Ws &W, const ViewDev &V, const float *tokens, int64_t ts_y, int64_t ts_x, int D,
                        const int32_t *ymap, const int32_t *xmap, float scale_f, float scale_d, float *F, float *d, hipStream_t s);

@@ -806,6 +806,81 @@ class Engine:
                                       cp, ptr(out), self._stream())
         return out
 
+    # ---- the view's RGB render for the 2-D network (create_feature_field(render_colors=...)) ----------------------------------
+    @staticmethod
+    def campos(view) -> Tuple[float, float, float]:
+        """Camera centre of a view in world space, computed as rasterization() computes it for sh_degree (float32 on the host:
+        -R^T t of the view matrix), so that the SH colours below are those of its render bit for bit."""
+        vm = torch.tensor(list(view.viewmat), dtype=torch.float32).reshape(4, 4)
+        return tuple((-(vm[:3, :3].T @ vm[:3, 3])).tolist())
+
+    def view_colors(self, view, means, colors, sh_degree: Optional[int] = None) -> torch.Tensor:
+        """The [N,3] colours of `view` that rasterization(..., colors, sh_degree=sh_degree) renders: `colors` itself without
+        sh_degree, the SH evaluation (sh_colors: +0.5, clamped at 0) toward the view's camera centre with it."""
+        if sh_degree is None:
+            return _req(colors, "render colors", (3,))
+        return self.sh_colors(int(sh_degree), means, colors, self.campos(view))
+
+    def _image(self, view, image: Optional[torch.Tensor]) -> torch.Tensor:
+        if image is None:
+            return torch.empty(view.height, view.width, 3, device=self.device)
+        if (image.dtype != torch.float32 or not image.is_cuda or not image.is_contiguous()
+                or tuple(image.shape) != (view.height, view.width, 3)):
+            raise GwbpError(f"image must be a contiguous float32 HIP tensor [{view.height},{view.width},3]")
+        return image
+
+    def blend_weights_rgb(self, view, colors, image: Optional[torch.Tensor] = None, pixel_weights: Optional[torch.Tensor] = None,
+                          d=None, scale_d=1.0, want_alphas=False):
+        """blend_weights / blend_weighted (`pixel_weights`) that also composites the view's RGB render with [N,3] `colors` while it
+        blends (gwbp_blend_weights_rgb / _d_rgb): returns (image [H,W,3], alphas or None) -- the image written into `image` when
+        given, equal to render_pixels(view, colors) bit for bit and unweighted whatever `pixel_weights` is.  The weight store, d
+        and the alpha map are those of the blend without it."""
+        colors = _req(colors, "colors", (3,))
+        image = self._image(view, image)
+        pw = self.pixel_weights(pixel_weights, view) if pixel_weights is not None else None
+        alphas = torch.empty(view.height, view.width, device=self.device) if want_alphas else None
+        self._tokens = None
+        self._halves = self._wide_requested()
+        pwp = C.byref(pw) if pw is not None else None
+        if d is not None:
+            if d.dtype != torch.float32 or not d.is_cuda or d.shape != (self.n,) or not d.is_contiguous():
+                raise GwbpError("d must be a contiguous float32 HIP tensor [N]")
+            if not self._halves:
+                raise GwbpError("blend_weights_rgb(d=...) needs the 256-channel scatter kernel enabled "
+                                "(set_narrow_scatter(False)): a narrow blend takes no weight sums")
+            self._call("gwbp_blend_weights_d_rgb", *self._args(), C.byref(view), ptr(alphas), C.c_float(scale_d), ptr(d), pwp,
+                       ptr(colors), ptr(image), self._stream())
+        else:
+            self._call("gwbp_blend_weights_rgb", *self._args(), C.byref(view), ptr(alphas), pwp, ptr(colors), ptr(image),
+                       self._stream())
+        return image, alphas
+
+    def blend_tokens_rgb(self, view, lr_h: int, lr_w: int, colors, image: Optional[torch.Tensor] = None,
+                         pixel_weights: Optional[torch.Tensor] = None, want_alphas=False):
+        """blend_tokens / blend_tokens_weighted that also composites the view's RGB render (gwbp_blend_tokens_rgb); returns
+        (image, alphas or None) as blend_weights_rgb."""
+        colors = _req(colors, "colors", (3,))
+        image = self._image(view, image)
+        pw = self.pixel_weights(pixel_weights, view) if pixel_weights is not None else None
+        if not self.token_geometry_ok(lr_h, lr_w, view.height, view.width):
+            raise GwbpError(f"blend_tokens_rgb: a {lr_h}x{lr_w} map has texels narrower than a tile at "
+                            f"{view.height}x{view.width}; use blend_weights_rgb + scatter(upsample='nearest')")
+        ymap, xmap = self.nearest_maps(lr_h, lr_w, view.height, view.width)
+        alphas = torch.empty(view.height, view.width, device=self.device) if want_alphas else None
+        self._halves = False
+        self._tokens = (int(lr_h), int(lr_w))
+        self._call("gwbp_blend_tokens_rgb", *self._args(), C.byref(view), ptr(ymap), ptr(xmap), ptr(alphas),
+                   C.byref(pw) if pw is not None else None, ptr(colors), ptr(image), self._stream())
+        return image, alphas
+
+    def render_rgb(self, view, colors, image: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The [H,W,3] render of a projected and sorted view into `image` (gwbp_render_pixels, no alpha map): the render of the
+        schedules whose blend needs the feature map, which the network makes from this image."""
+        colors = _req(colors, "colors", (3,))
+        image = self._image(view, image)
+        self._call("gwbp_render_pixels", *self._args(), C.byref(view), ptr(colors), 3, ptr(image), None, self._stream())
+        return image
+
     def _check_acc(self, F, d, D):
         if F.dtype != torch.float32 or not F.is_cuda or not F.is_contiguous() or tuple(F.shape) != (self.n, D):
             raise GwbpError(f"F must be a contiguous float32 HIP tensor [{self.n},{D}]")

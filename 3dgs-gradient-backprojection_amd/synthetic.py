@@ -221,6 +221,21 @@ def upsample_map(cfg: Config, low: torch.Tensor) -> torch.Tensor:
     return up[0].permute(1, 2, 0)
 
 
+SH_SEED = 40000
+
+
+def make_sh_coeffs(cfg: Config, degree: int = 3, device="cpu", seed: int = SH_SEED) -> torch.Tensor:
+    """[N, (degree+1)^2, 3] SH coefficients (a trained scene's colors_all, backproject.py:59-60): a DC term that puts the base
+    colour in [0, 1] after gsplat's +0.5, higher bands decaying with the degree.  For create_feature_field(render_colors=...)."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    k = (degree + 1) ** 2
+    sh = torch.randn(cfg.n_gaussians, k, 3, generator=g)
+    band = torch.tensor([math.floor(math.sqrt(i)) for i in range(k)], dtype=torch.float32)
+    sh *= (0.3 / (1.0 + band))[None, :, None]
+    sh[:, 0] = (torch.rand(cfg.n_gaussians, 3, generator=g) - 0.5) / 0.28209479177387814
+    return sh.contiguous().to(device)
+
+
 def make_encoder(cfg: Config, seed: int = ENCODER_SEED) -> torch.Tensor:
     """Random stand-in for encoder_decoder.ckpt's encoder (backproject_compressed.py:26,127)."""
     assert cfg.encoder_dim is not None

@@ -253,6 +253,25 @@ GWBP_API int gwbp_blend_scatter_encoded_ex(const gwbp_caps *caps, void *workspac
                                            const float *encoder, int32_t n_out, float scale_f, float scale_d, float *F, float *d,
                                            float *alphas, const gwbp_pixel_weights *pixel_weights, void *stream);
 
+/* ---- the view's RGB render as a by-product of the storing and token blends ---------------------------------------
+ * The _rgb forms are the _ex functions above plus an RGB composite written while each tile is blended:
+ *     image[p] = sum_g w_g(p) * colors[g]      (w = alpha * T, UNWEIGHTED even when pixel_weights is given)
+ * accumulated front to back with fmaf(w, c, acc) exactly as gwbp_render_pixels does, so image equals gwbp_render_pixels(colors,
+ * D = 3) of the same view bit for bit; no background.  colors is [N, 3] float32, image [H, W, 3] float32 (device, contiguous).
+ * Everything else the blend produces (weight store, headers, d, token-quadrant sums, alphas) is unchanged bit for bit.
+ * colors == NULL and image == NULL is the _ex function; exactly one of them NULL returns GWBP_EINVAL before anything else is
+ * looked at (after the pixel weights).  The fused blends (gwbp_blend_scatter*) have no _rgb form: their blend needs the feature
+ * map, which the network computes from this very render -- render those views with gwbp_render_pixels after gwbp_bin_sort. */
+GWBP_API int gwbp_blend_weights_rgb(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                                    float *alphas, const gwbp_pixel_weights *pixel_weights, const float *colors, float *image,
+                                    void *stream);
+GWBP_API int gwbp_blend_weights_d_rgb(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                                      float *alphas, float scale_d, float *d, const gwbp_pixel_weights *pixel_weights,
+                                      const float *colors, float *image, void *stream);
+GWBP_API int gwbp_blend_tokens_rgb(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                                   const int32_t *ymap, const int32_t *xmap, float *alphas, const gwbp_pixel_weights *pixel_weights,
+                                   const float *colors, float *image, void *stream);
+
 /* d[g] += scale_d * sum_p w_g(p) alone, from the per-record weight sums gwbp_blend_weights left in the workspace
  * (needs a blend WITHOUT GWBP_FLAG_NARROW_SCATTER).  A caller that overlaps the front stage of view v+1 with the
  * scatter of view v issues it behind the blend on the front's stream and passes d = NULL to gwbp_scatter: the
