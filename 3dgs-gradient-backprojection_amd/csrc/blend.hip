@@ -100,7 +100,7 @@ struct FusedArgs { // kFused only
     const u32 *estart;          // first emit position of every Gaussian (k_emit)
     const uint2 *rect;          // the tile rectangle the emit walked (k_project)
     // kFusedPC only
-    u32 *pc_queue;              // next tile (index into tile_order) a producer wave takes; zero when the kernel starts
+    u32 *pc_queue;              // next tile (index into tile_order) a producer wave takes; zero when the kernel starts and ends
 };
 
 // The weighted kernels (PIXW = true) take BlendArgs<true>, i.e. FusedArgs plus the weight map (PixW, gwbp_dev.h); BlendArgs<false>
@@ -169,6 +169,57 @@ __device__ __forceinline__ void load_pixel_weights(const PixW &pw, int ix, const
 #pragma unroll
     for (int q = 0; q < N; ++q)
         c[q] = (ix < W && iy[q] < H) ? c[q] : 0.0f;
+}
+
+// The blend's counts (gwbp_stats n_headers, n_pairs, pool_used).  A tile's wave adds its counts to its shard's line
+// (kShardHeaders, kShardPairs: gwbp_dev.h), not to Counters.  Whatever ends the blend moves them into Counters and zeroes the
+// lines, so gwbp_stats describes the view's LAST blend and a blend repeated on one projection starts from zero.  The storing
+// blends end in k_pool_stats (launched behind them anyway); the fused and token blends in the wave that leaves last.
+__device__ __forceinline__ void add_blend_counts(u32 *line, u32 n_headers, u32 n_pairs) // one lane
+{
+    if (n_headers)
+        atomicAdd(line + kShardHeaders, n_headers);
+    if (n_pairs)
+        atomicAdd(reinterpret_cast<u64 *>(line + kShardPairs), (u64)n_pairs);
+}
+// Whole wave, lane i < kShards takes line i: Counters <- the lines' counts, and pool_head <- kShards x the fullest shard; the
+// lines' counts and heads <- 0.  Rewinding the heads is safe: the store's pages are named by its headers, nothing reads a
+// head after the blend (a blend that stores nothing finds them zero: pool_head = 0).
+__device__ __forceinline__ void publish_blend_counts(u32 *shards, Counters *ctr, int lane)
+{
+    u32 h = 0, head = 0;
+    u64 p = 0;
+    if (lane < kShards) {
+        u32 *line = shards + lane * 16;
+        h = atomicExch(line + kShardHeaders, 0u);
+        p = atomicExch(reinterpret_cast<u64 *>(line + kShardPairs), 0ull);
+        head = atomicExch(line + kShardHead, 0u);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        h += __shfl_xor(h, o);
+        p += __shfl_xor(p, o);
+        head = max(head, (u32)__shfl_xor(head, o));
+    }
+    if (lane == 0) {
+        ctr->n_headers = h;
+        ctr->n_pairs = p;
+        ctr->pool_head = head * (u32)kShards;
+    }
+}
+// The end of a fused or token blend (whole wave): every wave counts itself out behind its counts; the last of n publishes them
+// and re-arms the count.
+__device__ __forceinline__ void blend_leave(u32 *shards, Counters *ctr, u32 n, int lane)
+{
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this wave's count atomics are performed before it counts itself out
+    u32 old = 0;
+    if (lane == 0)
+        old = atomicAdd(shards + kBlendLeavers, 1u);
+    if (uniform(old) == n - 1u) {
+        publish_blend_counts(shards, ctr, lane);
+        if (lane == 0)
+            atomicExch(shards + kBlendLeavers, 0u);
+    }
 }
 
 
@@ -512,8 +563,15 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 8
                     more = false;
                 }
             }
-            if (lane == 0)
+            if (lane == 0) {
                 atomicAdd(&pc_state[kPcRing], 1u); // (behind this wave's last publication: LDS operations of a wave complete in order)
+                // the launch re-arms its tile counter, as k_scatter_full its queue: the last of the grid's producer waves to count
+                // itself out (each behind its last claim, the ring-stall exit included) zeroes the counter and the count
+                if (atomicAdd(shards + kPcProducerLeavers, 1u) == gridDim.x * (u32)kPcProd - 1u) {
+                    atomicExch(shards + kPcProducerLeavers, 0u);
+                    atomicExch(fu.pc_queue, 0u);
+                }
+            }
             return;
         }
     }
@@ -557,8 +615,10 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 8
                     __builtin_amdgcn_s_sleep(8);
                 }
             }
-            if (got < 0)
+            if (got < 0) {
+                blend_leave(shards, ctr, gridDim.x * (u32)BW, lane);
                 return;
+            }
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             pc_slot = (u32)got & 0xFFu;
             tile_sel = got >> 8;
@@ -1000,10 +1060,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 8
             if ((FUSED || TOKEN) && !PC && slot == 0)
                 ctr->blend_kind = TOKEN ? kBlendToken : kBlendFused; // (no k_pool_stats launch behind these: the pool is untouched)
             hdr_count[tile] = (FUSED || TOKEN) ? 0u : hdr_n; // kFused / kToken: the store stays empty
-            if (hdr_n)
-                atomicAdd(&ctr->n_headers, hdr_n);
-            if (npairs)
-                atomicAdd(&ctr->n_pairs, (u64)npairs);
+            add_blend_counts(shard_head, hdr_n, npairs);
         }
         if (alphas) {
 #pragma unroll
@@ -1023,6 +1080,8 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 8
                 }
             }
         }
+        if constexpr ((FUSED || TOKEN) && !PC)
+            blend_leave(shards, ctr, (u32)n_tiles_all, lane); // one wave per tile
         if constexpr (!PC)
             break;
     } // for (;;): the next tile of a kFusedPC blend wave
@@ -1041,7 +1100,8 @@ template <int CH, bool PIXW = false> // 16 or 32 channels held per pixel (D <= C
 __global__ __launch_bounds__(64) void k_blend_scatter_quarter(ViewDev V, const u32 *__restrict__ tile_offsets,
                                                               const u32 *__restrict__ vals, const G2D *__restrict__ g2d,
                                                               Counters *__restrict__ ctr, u32 *__restrict__ hdr_count,
-                                                              const u32 *__restrict__ tile_order, float *__restrict__ alphas,
+                                                              u32 *__restrict__ shards, const u32 *__restrict__ tile_order,
+                                                              float *__restrict__ alphas,
                                                               int dbg_arg, int prio, float *__restrict__ d_out, float scale_d,
                                                               BlendArgs<PIXW> fu)
 {
@@ -1200,13 +1260,12 @@ __global__ __launch_bounds__(64) void k_blend_scatter_quarter(ViewDev V, const u
             ctr->blend_kind = kBlendFused; // (no k_pool_stats launch behind the fused kernels: the pool is untouched)
         if (q == 0)
             hdr_count[tile] = 0u; // the store stays empty
-        if (nrec)
-            atomicAdd(&ctr->n_headers, nrec); // (Gaussian, quarter-tile) flushes here, not (Gaussian, tile) records
-        if (npairs)
-            atomicAdd(&ctr->n_pairs, (u64)npairs);
+        // n_headers counts (Gaussian, quarter-tile) flushes here, not (Gaussian, tile) records
+        add_blend_counts(shards + (u32)tile % (u32)kShards * 16, nrec, npairs);
     }
     if (alphas && ix < V.W && iy < V.H)
         alphas[(size_t)iy * V.W + ix] = 1.0f - Tout;
+    blend_leave(shards, ctr, gridDim.x, lane); // one wave per quarter tile
 }
 
 // Test/debug: expand the weight store into (gid, pix, w) triples.
@@ -1247,13 +1306,12 @@ __global__ __launch_bounds__(256) void k_dump_pairs(ViewDev V, const u32 *__rest
     }
 }
 
-__global__ void k_pool_stats(const u32 *__restrict__ shards, Counters *__restrict__ ctr, u32 blend_kind)
+// The end of a storing blend (one wave): its counts into Counters, the shard heads rewound (publish_blend_counts).
+__global__ __launch_bounds__(64) void k_pool_stats(u32 *__restrict__ shards, Counters *__restrict__ ctr, u32 blend_kind)
 {
-    ctr->blend_kind = blend_kind; // which scatter kernels may read this view's store (half-tile lists, weight sums)
-    u32 mx = 0;
-    for (int i = 0; i < kShards; ++i)
-        mx = max(mx, shards[i * 16]);
-    ctr->pool_head = mx * (u32)kShards;
+    if (threadIdx.x == 0)
+        ctr->blend_kind = blend_kind; // which scatter kernels may read this view's store (half-tile lists, weight sums)
+    publish_blend_counts(shards, ctr, (int)threadIdx.x);
 }
 
 // The argument block of a k_blend / k_blend_scatter_quarter launch: BlendArgs<false> (FusedArgs' layout) without a weight map, the
@@ -1363,7 +1421,7 @@ int launch_blend(const Layout &L, const Ws &W, const ViewDev &V, float *alphas, 
                 W.headers, W.hdr_count, W.wpool, (u32)L.pair_cap, W.shards, W.tile_order, alphas, ablate, prio, d, scale_d)
     if (fused_enc && (L.flags & GWBP_FLAG_SPLIT_ENCODER)) {
         // producer / consumer form: ONE persistent workgroup per CU (kPcProd encoder waves + blend waves around a ring of encoded
-        // tiles in LDS); the tile counter is the first scatter queue word, which gwbp_project's memset left zero
+        // tiles in LDS); its tile counter is a word of shard line 0 that every launch leaves zero
         const size_t lds = (size_t)fu.enc_k * kFusedCh * sizeof(float) + (size_t)kPcRing * kPcTileFloats * sizeof(float) + 64;
         int n_cu = 0;
         int rc = device_cus(&n_cu);
@@ -1371,7 +1429,7 @@ int launch_blend(const Layout &L, const Ws &W, const ViewDev &V, float *alphas, 
         if (rc || (rc = pw ? ensure_dynamic_lds(reinterpret_cast<const void *>(k_blend<kFusedPC, kPcWaves, true>), lds_max, 15)
                            : ensure_dynamic_lds(reinterpret_cast<const void *>(k_blend<kFusedPC, kPcWaves, false>), lds_max, 14)))
             return rc;
-        fu.pc_queue = W.shards + kShards * 16;
+        fu.pc_queue = W.shards + kPcTileCounter;
         GWBP_LAUNCH(k_blend<kFusedPC GWBP_COMMA kPcWaves, dim3(n_cu), dim3(64 * kPcWaves), lds, V, W.tile_offsets, W.vals[fin], W.g2d,
                     W.counters, W.headers, W.hdr_count, W.wpool, (u32)L.pair_cap, W.shards, W.tile_order, alphas, ablate, prio, d,
                     scale_d);
@@ -1383,7 +1441,7 @@ int launch_blend(const Layout &L, const Ws &W, const ViewDev &V, float *alphas, 
     } else if (fused && n_tiles <= kQuarterMaxTiles) {
 #define GWBP_QUARTER(C)                                                                                               \
     GWBP_LAUNCH(k_blend_scatter_quarter<C, dim3(4 * n_tiles), dim3(64), 0, V, W.tile_offsets, W.vals[fin], W.g2d, W.counters, \
-                W.hdr_count, W.tile_order, alphas, ablate, prio, d, scale_d)
+                W.hdr_count, W.shards, W.tile_order, alphas, ablate, prio, d, scale_d)
         if (D <= 16)
             GWBP_QUARTER(16);
         else
@@ -1403,7 +1461,7 @@ int launch_blend(const Layout &L, const Ws &W, const ViewDev &V, float *alphas, 
 #undef GWBP_LAUNCH
 #undef GWBP_COMMA
     if (!fused)
-        hipLaunchKernelGGL(k_pool_stats, dim3(1), dim3(1), 0, s, W.shards, W.counters,
+        hipLaunchKernelGGL(k_pool_stats, dim3(1), dim3(64), 0, s, W.shards, W.counters,
                            (L.flags & GWBP_FLAG_NARROW_SCATTER) ? 0u : kBlendHalves);
     return check_hip(hipGetLastError(), "blend launch");
 }

@@ -22,6 +22,12 @@ constexpr int kTilePix = 256;
 constexpr int kPage = 1024;          // weight-pool page (pairs) grabbed per (tile, wave) stream
 constexpr int kQueues = 8;           // scatter work queues, one per XCD class (blockIdx % 8), 64 B apart, after the shard heads
 constexpr int kShards = 32;          // independently counted regions of the weight pool (one head word per 64-B line)
+// Words of a shard's 64-B line (blend.hip): the head, then what the running blend has counted of the tiles of that shard -- its
+// n_headers and (8-B aligned) n_pairs -- until the blend's end moves them into Counters and zeroes them.  Line 0 also holds the
+// leaver counts of the blends that end in their own last wave (fused, token) and the split encoder's tile counter.  All of them
+// are zero between two blends.
+constexpr int kShardHead = 0, kShardHeaders = 1, kShardPairs = 2; // kShardPairs: a u64 (words 2 and 3)
+constexpr int kBlendLeavers = 4, kPcTileCounter = 5, kPcProducerLeavers = 6; // in line 0
 constexpr int kListPad = 8;          // every record's entry list is padded to a multiple of kListPad entries (kHalves: each half's)
 constexpr unsigned kPadPix = 640;    // "pixel" of a padding entry {0, kPadPix}: its slab row lies beyond the 160 KB an LDS allocation
                                      // can have in the 256-channel kernel (1 KB rows), where an out-of-range read returns 0; every

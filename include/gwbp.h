@@ -92,13 +92,15 @@ typedef struct gwbp_caps {
  * tile after tile through the matrix cores into a ring of encoded tiles in LDS while its fourteen blend waves drain
  * it -- the HBM-bound encoder stream and the issue-bound blend loops run concurrently for the whole launch instead of one after
  * the other in every wave.  Same encoded pixels and weights bit for bit; F and d differ by summation order only.  Pays on images of
- * many tiles per CU (C5: 6700 tiles on 256 CUs); needs gwbp_project of the view to have run on this workspace (the tile counter
- * is a word its memset clears). */
+ * many tiles per CU (C5: 6700 tiles on 256 CUs). */
 #define GWBP_FLAG_SPLIT_ENCODER 16
 /* (bit 3 was GWBP_FLAG_GROUP_SCATTER, an experimental block-sparse scatter on the matrix cores: measured slower than the
  * vector kernels and removed; unknown flag bits are rejected with GWBP_EINVAL.) */
 
-/* Device-resident per-view counters, readable after the stream has drained (gwbp_read_stats). */
+/* Device-resident per-view counters, readable after the stream has drained (gwbp_read_stats).  gwbp_project (or
+ * gwbp_project_camera) zeroes them.  n_pairs, n_headers, pool_used and reserved describe the view's LAST blend: a blend repeated
+ * on one projection reports what it alone counted, and starts from an empty weight pool.  The overflow bits are sticky: once set,
+ * they stay set until the next gwbp_project of a view on this workspace. */
 typedef struct gwbp_stats {
     uint64_t n_pairs;     /* contributing (Gaussian, pixel) pairs = sum over pixels of #weights */
     uint32_t n_isect;     /* (Gaussian, tile) intersections emitted */
