@@ -5,10 +5,11 @@ JojiJoseph/3dgs-gradient-backprojection), hand-written HIP kernels behind a C AB
     from gsbp_amd import create_feature_field     # fused counterpart of create_feature_field_lseg/_dino
     from gsbp_amd import create_label_field       # integer label maps -> per-Gaussian class weights
     from gsbp_amd import create_mask_feature_field  # mask maps + one embedding per mask -> feature field
+    from gsbp_amd import create_vote_field          # per-view binary / projection / gradient votes -> 3-D masks
 """
 from . import synthetic  # noqa: F401
 from ._lib import GwbpError, build, lib  # noqa: F401
-from .backproject import ViewPipeline, create_feature_field, create_label_field, create_mask_feature_field, finalize_reference, prune_mask, reduce_partials, reduce_partials_sharded  # noqa: F401
+from .backproject import ViewPipeline, create_feature_field, create_label_field, create_mask_feature_field, create_vote_field, finalize_reference, mask3d_from_votes, prune_mask, reduce_partials, reduce_partials_sharded  # noqa: F401
 from .engine import Engine, bilinear_index, narrow_labels, nearest_index  # noqa: F401
 from . import scene_io  # noqa: F401
 from .rasterization import rasterization  # noqa: F401

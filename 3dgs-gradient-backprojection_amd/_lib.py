@@ -56,6 +56,7 @@ EXPORTS = [
     "gwbp_accumulate_stats", "gwbp_read_stats", "gwbp_dump_pairs",
     "gwbp_blend_weights_ex", "gwbp_blend_weights_d_ex", "gwbp_blend_tokens_ex", "gwbp_blend_scatter_ex",
     "gwbp_blend_scatter_encoded_ex", "gwbp_blend_weights_rgb", "gwbp_blend_weights_d_rgb", "gwbp_blend_tokens_rgb",
+    "gwbp_vote_labels", "gwbp_vote_projected",
 ]
 
 
@@ -188,6 +189,9 @@ ARGTYPES = {
     "gwbp_blend_weights_rgb": _WSV + [_P, C.POINTER(PixelWeights), _P, _P, _P],
     "gwbp_blend_weights_d_rgb": _WSV + [_P, _F, _P, C.POINTER(PixelWeights), _P, _P, _P],
     "gwbp_blend_tokens_rgb": _WSV + [_P, _P, _P, C.POINTER(PixelWeights), _P, _P, _P],
+    # the votes: labels, label_type, ls_y, ls_x, ymap, xmap, then (seen | pixel weights), num_classes, C, ldc, n, stream
+    "gwbp_vote_labels": _WSV + [_P, _I32, _I64, _I64, _P, _P, _I32, _P, _P, _I64, _P, _P],
+    "gwbp_vote_projected": _WSV + [_P, _I32, _I64, _I64, _P, _P, C.POINTER(PixelWeights), _I32, _P, _I64, _P, _P],
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1000,12 +1000,12 @@ class _LabelPipeline(ViewPipeline):
         e.accumulate_stats(self.accums[0])
 
 
-def _run_labels_pipelined(job: _Job, eng: Engine, depth: int, num_classes: int) -> Dict[str, int]:
-    """create_label_field's views through a _LabelPipeline of `depth` workspaces; an overflow seen after view 2 or by a later
-    probe ends the pass early (as in _run_pipelined)."""
+def _run_labels_pipelined(job: _Job, eng: Engine, depth: int, num_classes: int, pipe_cls=None) -> Dict[str, int]:
+    """create_label_field's views through a _LabelPipeline (or `pipe_cls`, a subclass) of `depth` workspaces; an overflow seen
+    after view 2 or by a later probe ends the pass early (as in _run_pipelined)."""
     (means, _, _, _), F, d, sf, sd, _, ids, _, _, width, height, _, _, upsample, _, _ = job
     n = means.shape[0]
-    pipe = _LabelPipeline(n, width, height, means.device, num_classes=num_classes,
+    pipe = (pipe_cls or _LabelPipeline)(n, width, height, means.device, num_classes=num_classes,
                           engines=[eng] + [Engine(n, width, height, device=means.device, tight_binning=eng.tight_binning,
                                                   isect_cap=eng.isect_cap, pair_cap=eng.pair_cap) for _ in range(depth - 1)])
     views = [eng.view(job.vm_host[v], job.K_host, width, height, **job.camera) for v in ids]
@@ -1293,3 +1293,161 @@ def prune_mask(d: torch.Tensor) -> torch.Tensor:
     """utils.prune_by_gradients (utils.py:222-271) keeps Gaussians whose accumulated colour-gradient norm is
     > 0 over all views; that norm is 2/(3HW) * sum_v sum_p w, i.e. the mask is exactly d > 0."""
     return d > 0
+
+
+# ---- 3-D masks from 2-D masks by per-view voting (the binary / projection / gradient votes of a masklet lift) ------------------
+VOTE_METHODS = ("binary", "projection", "gradient")
+
+
+class _VotePipeline(_LabelPipeline):
+    """The ViewPipeline of create_vote_field(method="binary"): the front stage blends a weight store WITHOUT the denominators
+    (n counts views, not weight: no gwbp_blend_weights_d, hence no half-tile lists either), the scatter stage is
+    Engine.vote_labels -- the bitset kernel and its commit -- into C and n."""
+
+    def choose_scatter_kernel(self, n_pairs, n_headers) -> str:
+        self.wide = False  # (what front() reads: the blend adds nothing to d)
+        for e in self.eng:
+            e.set_narrow_scatter(True)
+            e.set_front_priority(False)
+        return "votes"
+
+    def _scatter_on(self, main, b, labels, C, n, scale_f, scale_d, t0, t1, upsample, encoder):
+        e = self.eng[b]
+        if t0 is not None:
+            t0.record(main)
+        p = self.pending.pop(self.i_scatter)
+        e.vote_labels(p.view, labels, C, n, self.num_classes, upsample=upsample)
+        if t1 is not None:
+            t1.record(main)
+        e.accumulate_stats(self.accums[0])
+
+
+def _run_votes_serial(job: _Job, eng: Engine, num_classes: int) -> Dict[str, int]:
+    """The binary vote's views one after the other on the caller's stream (synchronises)."""
+    accum = torch.zeros(32, dtype=torch.uint8, device=job.F.device)
+    for v in job.view_ids:
+        view = eng.view(job.vm_host[v], job.K_host, job.width, job.height, **job.camera)
+        if job.render is not None:  # the blend composites the render; the labels are made from it behind the blend
+            eng.project(view, *job.gaussians)
+            eng.bin_sort(view)
+            labels = job.feature_fn(v, _blend_rendered(eng, job, v, view))
+        else:
+            labels = job.feature_fn(v)
+            eng.project(view, *job.gaussians)
+            eng.bin_sort(view)
+            if job.pixel_weight_fn is not None:
+                eng.blend_weighted(view, job.pixel_weight_fn(v))
+            else:
+                eng.blend_weights(view)
+        eng.vote_labels(view, labels, job.F, job.d, num_classes, upsample=job.upsample)
+        eng.accumulate_stats(accum)
+    return Engine.decode_stats(accum)
+
+
+def _run_votes_projected(job: _Job, eng: Engine, num_classes: int) -> Dict[str, int]:
+    """The projection vote: per view project -> vote (no sort, no blend); a job that renders also sorts the view and renders it
+    with render_pixels before label_fn(v, image).  Only the render can overflow a capacity (synchronises)."""
+    accum = torch.zeros(32, dtype=torch.uint8, device=job.F.device)
+    for v in job.view_ids:
+        view = eng.view(job.vm_host[v], job.K_host, job.width, job.height, **job.camera)
+        if job.render is not None:
+            labels = job.feature_fn(v, _render_view(eng, job, v, view))
+            eng.accumulate_stats(accum)
+        else:
+            labels = job.feature_fn(v)
+            eng.project(view, *job.gaussians)
+        pw = job.pixel_weight_fn(v) if job.pixel_weight_fn is not None else None
+        eng.vote_projected(view, labels, job.F, job.d, num_classes, upsample=job.upsample, pixel_weights=pw)
+    return Engine.decode_stats(accum)
+
+
+def create_vote_field(means, quats, scales, opacities, viewmats, K, width: int, height: int,
+                      label_fn: Callable[[int], torch.Tensor], num_classes: int, *, method: str = "binary",
+                      upsample: Optional[str] = None, views: Optional[Sequence[int]] = None, pipeline: bool = True,
+                      gather: bool = True, return_partials: bool = False, camera_model: str = "pinhole",
+                      rasterize_mode: str = "classic", engine: Optional[Engine] = None,
+                      pixel_weight_fn: Optional[Callable[[int], torch.Tensor]] = None,
+                      render_colors: Optional[torch.Tensor] = None, sh_degree: Optional[int] = None):
+    """Per-Gaussian VOTES of per-view label maps (a segmenter's masks or masklets): returns (C, n), C float32 [N, num_classes],
+    n float32 [N].  The 3-D mask of two classes is mask3d_from_votes(C): votes = C[:, 1] - C[:, 0] > 0.
+      method="binary":     C[g, k] = number of views in which g has at least one contributing pixel (w = alpha T > 0) of label k,
+                           n[g] = number of views in which g has any contributing pixel (Engine.vote_labels: a bitset per view
+                           over the weight store, no float atomic per pixel).
+      method="projection": per view, a Gaussian with radius > 0 whose centre, rounded half to even (np.round of means2d), lies in
+                           the image adds 1 to C[g, label there] and to n[g] (Engine.vote_projected: no sort, no blend).
+      method="gradient":   C and n are create_label_field's raw sums F and d (sum_v sum_p w [L_v(p) == k] and sum_v sum_p w).
+    A label outside [0, num_classes) is ignored: it counts in n and in no column.  Counts are exact up to 2^24 views.
+    label_fn, upsample, views, pipeline, gather, camera_model, rasterize_mode, engine, pixel_weight_fn, render_colors / sh_degree:
+    as create_label_field (label_fn(v, image) with render_colors).  With pixel_weight_fn a pixel of weight 0 casts no vote: for
+    "binary" only entries with w c(p) > 0 vote, for "projection" a Gaussian whose pixel has c <= 0 does not vote at all.
+    pipeline applies to "binary" and "gradient"; "projection" is one short kernel per view.
+    return_partials: also return the counters, (C, n, stats) with stats["row0"] (C is this rank's row block when gather=False).
+    A capacity overflow grows the workspace and starts over with C and n zeroed; if no attempt finishes cleanly it raises."""
+    if method not in VOTE_METHODS:
+        raise ValueError(f"method must be one of {VOTE_METHODS}, got {method!r}")
+    if upsample not in (None, "nearest"):
+        raise ValueError(f"upsample must be None or 'nearest' for label maps, got {upsample!r}")
+    if isinstance(num_classes, bool) or int(num_classes) < 1:
+        raise ValueError(f"num_classes must be a positive int, got {num_classes!r}")
+    kw = dict(upsample=upsample, views=views, pipeline=pipeline, camera_model=camera_model, rasterize_mode=rasterize_mode,
+              engine=engine, pixel_weight_fn=pixel_weight_fn, render_colors=render_colors, sh_degree=sh_degree)
+    n_g = means.shape[0]
+    if method == "gradient":  # the raw label-field sums: no kernel of its own
+        _, C_rows, n_all, stats = create_label_field(means, quats, scales, opacities, viewmats, K, width, height, label_fn,
+                                                     num_classes, gather=False, return_partials=True, **kw)
+        row0 = stats["row0"]
+    else:
+        render = _render_of(render_colors, sh_degree, n_g, means.device)
+        dist, rank, world = _dist()
+        Cacc, n_acc, C_store = alloc_accumulators(n_g, int(num_classes), means.device, world)
+        job = _Job((means, quats, scales, opacities), Cacc, n_acc, 1.0, 1.0, label_fn,
+                   list(views) if views is not None else view_shard(viewmats.shape[0], rank, world),
+                   viewmats.detach().cpu(), K.detach().cpu(), width, height,
+                   dict(camera_model=camera_model, rasterize_mode=rasterize_mode), None, upsample, pixel_weight_fn, render)
+        pipelined = method == "binary" and bool(pipeline) and len(job.view_ids) > 1
+        if pipelined and _lib.hw_queues_late():
+            warnings.warn("gsbp_amd was imported after the HIP runtime had started: create_vote_field runs its views on ONE "
+                          "stream", RuntimeWarning, stacklevel=2)
+            pipelined = False
+        depth = (pipeline_depth(n_g, width, height) if pipeline is True else max(2, int(pipeline))) if pipelined else 1
+        eng = engine or Engine(n_g, width, height, device=means.device, tight_binning=True)
+        stats: Dict[str, int] = {}
+        clean = False
+        for attempt in range(6):  # a capacity overflow invalidates the counts: grow the workspace, start over
+            if method == "projection":
+                stats = _run_votes_projected(job, eng, int(num_classes))
+            elif pipelined:
+                stats = _run_labels_pipelined(job, eng, depth, int(num_classes), pipe_cls=_VotePipeline)
+            else:
+                stats = _run_votes_serial(job, eng, int(num_classes))
+            if _overflow_action(stats["overflow"], False, attempt) is None:
+                clean = True
+                break
+            eng.grow(stats, views=len(job.view_ids))
+            Cacc.zero_()
+            n_acc.zero_()
+        if not clean:
+            raise RuntimeError(f"create_vote_field: no pass over the views finished without a workspace overflow "
+                               f"(flags {stats.get('overflow')})")
+        C_rows, n_rows, row0 = reduce_partials_sharded(Cacc, n_acc, C_store)
+        n_all = n_acc
+    C_out = gather_rows(C_rows, n_g) if gather else C_rows
+    n_out = n_all if gather else n_all[row0:row0 + C_rows.shape[0]]
+    if return_partials:
+        return C_out, n_out, dict(stats, row0=row0)
+    return C_out, n_out
+
+
+def mask3d_from_votes(C: torch.Tensor, positive: int = 1, negative: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(mask3d, mask3d_inverted) of get_mask3d: votes = C[:, positive] - C[:, negative], mask3d = votes > 0,
+    mask3d_inverted = votes < 0 (Gaussians that never voted, or as often for both classes, are in neither)."""
+    if not torch.is_tensor(C) or C.dim() != 2:
+        raise ValueError(f"C must be an [N, K] tensor of votes, got {type(C).__name__ if not torch.is_tensor(C) else tuple(C.shape)}")
+    K = C.shape[1]
+    for name, col in (("positive", positive), ("negative", negative)):
+        if isinstance(col, bool) or not isinstance(col, int) or not 0 <= col < K:
+            raise ValueError(f"{name} must be a column index in [0, {K}), got {col!r}")
+    if positive == negative:
+        raise ValueError(f"positive and negative must be different columns, got {positive} for both")
+    votes = C[:, positive] - C[:, negative]
+    return votes > 0, votes < 0

@@ -731,6 +731,68 @@ int gwbp_scatter_mask_features(const gwbp_caps *caps, void *workspace, size_t wo
                                 scale_f, scale_d, F, d, S, n_spilled, static_cast<hipStream_t>(stream));
 }
 
+// The label, count and bitset arguments of the two vote entry points, checked before the caps, the workspace or the view.
+static int check_vote_args(const char *fn, const void *labels, int32_t label_type, int64_t ls_y, int64_t ls_x, const int32_t *ymap,
+                           const int32_t *xmap, int32_t num_classes, const float *C, int64_t ldc)
+{
+    if (label_type != GWBP_LABEL_U8 && label_type != GWBP_LABEL_I16 && label_type != GWBP_LABEL_I32)
+        return set_error(GWBP_EINVAL, "unknown label type %d", (int)label_type);
+    if (num_classes <= 0)
+        return set_error(GWBP_EINVAL, "num_classes must be positive (got %d)", (int)num_classes);
+    if (ldc < num_classes)
+        return set_error(GWBP_EINVAL, "ldc %lld < num_classes %d", (long long)ldc, (int)num_classes);
+    if (!C)
+        return set_error(GWBP_EINVAL, "null C");
+    if (!ymap != !xmap)
+        return set_error(GWBP_EINVAL, "%s needs both index maps or neither", fn);
+    if (!labels || ls_y < 0 || ls_x < 0)
+        return set_error(GWBP_EINVAL, "bad label map arguments (strides %lld %lld)", (long long)ls_y, (long long)ls_x);
+    return GWBP_OK;
+}
+
+int gwbp_vote_labels(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                     const void *labels, int32_t label_type, int64_t ls_y, int64_t ls_x, const int32_t *ymap, const int32_t *xmap,
+                     int32_t num_classes, uint32_t *seen, float *C, int64_t ldc, float *n, void *stream)
+{
+    int rc = check_vote_args("gwbp_vote_labels", labels, label_type, ls_y, ls_x, ymap, xmap, num_classes, C, ldc);
+    if (rc)
+        return rc;
+    if (!seen || (reinterpret_cast<uintptr_t>(seen) & 3))
+        return set_error(GWBP_EINVAL, "seen must be a non-null, 4-B aligned uint32 bitset");
+    Layout L;
+    Ws W;
+    ViewDev V;
+    if ((rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W)))
+        return rc;
+    if ((rc = make_view(view_host, caps, &V)))
+        return rc;
+    return launch_vote_labels(L, W, V, labels, label_type, ls_y, ls_x, ymap, xmap, num_classes, seen, C, ldc, n,
+                              static_cast<hipStream_t>(stream));
+}
+
+int gwbp_vote_projected(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                        const void *labels, int32_t label_type, int64_t ls_y, int64_t ls_x, const int32_t *ymap,
+                        const int32_t *xmap, const gwbp_pixel_weights *pixel_weights, int32_t num_classes, float *C, int64_t ldc,
+                        float *n, void *stream)
+{
+    PixW P;
+    const PixW *pw;
+    int rc = check_pixel_weights(pixel_weights, &P, &pw);
+    if (rc)
+        return rc;
+    if ((rc = check_vote_args("gwbp_vote_projected", labels, label_type, ls_y, ls_x, ymap, xmap, num_classes, C, ldc)))
+        return rc;
+    Layout L;
+    Ws W;
+    ViewDev V;
+    if ((rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W)))
+        return rc;
+    if ((rc = make_view(view_host, caps, &V)))
+        return rc;
+    return launch_vote_projected(L, W, V, labels, label_type, ls_y, ls_x, ymap, xmap, pw, num_classes, C, ldc, n,
+                                 static_cast<hipStream_t>(stream));
+}
+
 int gwbp_render(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
                 const float *colors, int32_t D, float *out, void *stream)
 {

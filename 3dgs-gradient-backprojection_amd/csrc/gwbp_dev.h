@@ -242,6 +242,14 @@ int launch_token_apply_half(const Layout &L, const Ws &W, const ViewDev &V, cons
 int launch_scatter_labels(const Layout &L, const Ws &W, const ViewDev &V, const void *labels, int label_type, int64_t ls_y,
                           int64_t ls_x, const int32_t *ymap, const int32_t *xmap, int K, float scale_f, float scale_d, float *F,
                           int64_t ldf, float *d, hipStream_t s);
+// per-view votes of label maps (votes.hip): the binary vote over the weight store (k_vote_labels + k_vote_commit, seen: the caller's
+// [N][ceil((K + 1) / 32)] bitset, all zero between calls) and the projection vote over the projected table (k_vote_projected)
+int launch_vote_labels(const Layout &L, const Ws &W, const ViewDev &V, const void *labels, int label_type, int64_t ls_y,
+                       int64_t ls_x, const int32_t *ymap, const int32_t *xmap, int K, u32 *seen, float *C, int64_t ldc, float *n,
+                       hipStream_t s);
+int launch_vote_projected(const Layout &L, const Ws &W, const ViewDev &V, const void *labels, int label_type, int64_t ls_y,
+                          int64_t ls_x, const int32_t *ymap, const int32_t *xmap, const PixW *pw, int K, float *C, int64_t ldc,
+                          float *n, hipStream_t s);
 int launch_render(const Layout &L, const Ws &W, const ViewDev &V, const float *colors, int D, float *out,
                   hipStream_t s);
 int launch_render_px(const Ws &W, const ViewDev &V, const float *colors, int D, float *out, float *alphas,

@@ -5,6 +5,7 @@ Everything is enqueued on torch's current HIP stream of the tensors' device; not
 """
 from __future__ import annotations
 
+import ctypes
 import ctypes as C
 from typing import Dict, Optional, Tuple
 
@@ -635,6 +636,81 @@ class Engine:
         self._call("gwbp_scatter_labels", *self._args(), C.byref(view), ptr(labels), LABEL_TYPES[labels.dtype], C.c_int64(sy),
                    C.c_int64(sx), K, ptr(ymap), ptr(xmap), C.c_float(scale_f), C.c_float(scale_d), ptr(F), C.c_int64(F.stride(0)),
                    ptr(d), self._stream())
+
+    # ---- per-view votes of label maps (gwbp_vote_labels, gwbp_vote_projected) -----------------------------------------------
+    def _vote_args(self, view, labels, C, n, num_classes: int, upsample: Optional[str]):
+        """(label map as read, ymap, xmap, K) of the two votes, validated as scatter_labels validates its arguments.  The map may be
+        a narrowed copy: the caller holds it until its kernel is enqueued."""
+        if not torch.is_tensor(labels) or not labels.is_cuda:
+            raise GwbpError("labels must be a HIP tensor (no CPU fallback exists for this path)")
+        K = int(num_classes)
+        if K < 1:
+            raise GwbpError(f"num_classes must be positive, got {K}")
+        if labels.dtype == torch.int64:
+            labels = narrow_labels(labels, K)
+        if labels.dtype not in LABEL_TYPES:
+            raise GwbpError(f"labels must be an integer map (uint8, bool, int16, int32 or int64), got {labels.dtype}")
+        if labels.dtype == torch.bool:
+            labels = labels.view(torch.uint8)
+        if upsample not in (None, "nearest"):
+            raise GwbpError(f"upsample must be None or 'nearest' for a label map, got {upsample!r}")
+        if labels.dim() != 2 or (upsample is None and tuple(labels.shape) != (view.height, view.width)):
+            want = f"[H,W] = [{view.height},{view.width}]" if upsample is None else "[h,w]"
+            raise GwbpError(f"label map must be {want}, got {tuple(labels.shape)}")
+        if min(labels.stride()) < 0:
+            raise GwbpError("negative label-map strides are not supported")
+        if (not torch.is_tensor(C) or C.dtype != torch.float32 or not C.is_cuda or C.dim() != 2 or tuple(C.shape) != (self.n, K)
+                or (K > 1 and C.stride(1) != 1) or C.stride(0) < K):
+            raise GwbpError(f"C must be a float32 HIP tensor [{self.n},{K}] with unit column stride")
+        if n is not None and (n.dtype != torch.float32 or not n.is_cuda or not n.is_contiguous() or tuple(n.shape) != (self.n,)):
+            raise GwbpError(f"n must be a contiguous float32 HIP tensor [{self.n}]")
+        ymap = xmap = None
+        if upsample == "nearest":
+            ymap, xmap = self.nearest_maps(labels.shape[0], labels.shape[1], view.height, view.width)
+        return labels, ymap, xmap, K
+
+    @staticmethod
+    def vote_words(num_classes: int) -> int:
+        """uint32 words per Gaussian of gwbp_vote_labels' bitset: bit 0 = "seen", label k = bit k + 1."""
+        return (int(num_classes) + 1 + 31) // 32
+
+    def _vote_seen(self, num_classes: int) -> torch.Tensor:
+        """The bitset of gwbp_vote_labels, [N * vote_words(K)] int32: allocated zeroed on first use (grown with K) on the stream
+        this engine's kernels run on, and kept all zero by the commit kernel after every call."""
+        need = self.n * self.vote_words(num_classes)
+        if getattr(self, "_seen", None) is None or self._seen.numel() < need:
+            st = self.stream if self.stream is not None else torch.cuda.current_stream(self.device)
+            with torch.cuda.stream(st):
+                self._seen = torch.zeros(max(need, 1), dtype=torch.int32, device=self.device)
+        return self._seen
+
+    def vote_labels(self, view, labels, C, n, num_classes: int, upsample: Optional[str] = None):
+        """Binary vote of one view from its weight store (gwbp_vote_labels): C[g, k] += 1 if Gaussian g has at least one
+        contributing pixel (w > 0) of label k, n[g] += 1 if it has any contributing pixel.  A label outside [0, num_classes)
+        counts in n and in no column.  labels, upsample: as scatter_labels.  C: float32 [N, num_classes] with unit column stride;
+        n: float32 [N] or None.  Needs blend_weights / blend_weighted / blend_weights_rgb of the view (a pixel of weight 0 then
+        casts no vote)."""
+        if self._tokens is not None:
+            raise GwbpError("this view was blended with blend_tokens (no weight store): blend_weights() first for vote_labels()")
+        labels, ymap, xmap, K = self._vote_args(view, labels, C, n, num_classes, upsample)
+        seen = self._vote_seen(K)
+        sy, sx = labels.stride()
+        self._call("gwbp_vote_labels", *self._args(), ctypes.byref(view), ptr(labels), LABEL_TYPES[labels.dtype],
+                   ctypes.c_int64(sy), ctypes.c_int64(sx), ptr(ymap), ptr(xmap), K, ptr(seen), ptr(C),
+                   ctypes.c_int64(C.stride(0)), ptr(n), self._stream())
+
+    def vote_projected(self, view, labels, C, n, num_classes: int, upsample: Optional[str] = None,
+                       pixel_weights: Optional[torch.Tensor] = None):
+        """Projection vote of one view from its projected table (gwbp_vote_projected; needs project() of the view only): a
+        Gaussian with radius > 0 whose centre, rounded half to even, lies in the image adds 1 to C[g, label there] (if that label
+        is in [0, num_classes)) and to n[g].  pixel_weights (optional, [H, W] at full resolution, as blend_weighted): a Gaussian
+        whose pixel has a weight that is not > 0 casts no vote.  labels, upsample, C, n: as vote_labels."""
+        labels, ymap, xmap, K = self._vote_args(view, labels, C, n, num_classes, upsample)
+        pw = ctypes.byref(self.pixel_weights(pixel_weights, view)) if pixel_weights is not None else None
+        sy, sx = labels.stride()
+        self._call("gwbp_vote_projected", *self._args(), ctypes.byref(view), ptr(labels), LABEL_TYPES[labels.dtype],
+                   ctypes.c_int64(sy), ctypes.c_int64(sx), ptr(ymap), ptr(xmap), pw, K, ptr(C), ctypes.c_int64(C.stride(0)),
+                   ptr(n), self._stream())
 
     @staticmethod
     def mask_fast_path(dim: int) -> bool:

@@ -373,6 +373,36 @@ GWBP_API int gwbp_scatter_labels(const gwbp_caps *caps, void *workspace, size_t 
                                  const int32_t *ymap, const int32_t *xmap, float scale_f, float scale_d, float *F, int64_t ldf,
                                  float *d, void *stream);
 
+/* ---- per-view VOTES of label maps (3-D masks from 2-D masks or masklets) ----------------------------------------------
+ * Both entry points add whole votes, per view, to C[g * ldc + k] (fp32 counts, [N, ldc] row-major, ldc >= num_classes) and
+ * n[g] (fp32 [N]; may be NULL): C[g, k] += 1 if Gaussian g votes for label k in this view, n[g] += 1 if it votes at all.  A label
+ * outside [0, num_classes) is ignored: it counts in n and in no column.  labels, label_type, ls_y, ls_x, ymap, xmap: as
+ * gwbp_scatter_labels.  The adds are fp32 atomics (exact up to 2^24 views): several workspaces may add into one C and n at once.
+ *
+ * gwbp_vote_labels (binary vote): g votes for k if it has at least one weight-store entry (g, p) with w > 0 and L(p) == k, and
+ * votes at all if it has one entry with w > 0.  Needs the weight store of the view (gwbp_blend_weights or its _d / _ex / _rgb
+ * forms, with or without GWBP_FLAG_NARROW_SCATTER; a pixel weight map's zero or negative values then cast no vote).  seen is the
+ * caller's bitset, uint32 [N][ceil((num_classes + 1) / 32)], 4-B aligned, ALL ZERO before the call: the call ORs the view's bits
+ * into it and its second kernel adds them to C and n and writes the words back to zero, so one buffer serves every view of one
+ * stream (no memset).  After gwbp_blend_scatter / gwbp_blend_scatter_encoded / gwbp_blend_tokens the workspace holds no weight
+ * store: the call sets gwbp_stats.overflow bit 2 and adds nothing.
+ *
+ * gwbp_vote_projected (projection vote): needs gwbp_project (or gwbp_project_camera) of the view only.  A Gaussian with radius > 0
+ * whose centre, rounded half to even (x = rint(mx), y = rint(my) of the means2d the projection writes), lies in [0, W) x [0, H)
+ * votes for the label at (y, x).  pixel_weights (optional, as the _ex blends, full resolution): a Gaussian whose pixel has a
+ * weight that is not > 0 casts no vote.
+ *
+ * GWBP_EINVAL before anything else for an unknown label_type or pixel weight map, num_classes <= 0, ldc < num_classes, a NULL C,
+ * labels or (gwbp_vote_labels) seen, a misaligned seen, negative strides, or exactly one of ymap / xmap NULL. */
+GWBP_API int gwbp_vote_labels(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                              const void *labels, int32_t label_type, int64_t ls_y, int64_t ls_x, const int32_t *ymap,
+                              const int32_t *xmap, int32_t num_classes, uint32_t *seen, float *C, int64_t ldc, float *n,
+                              void *stream);
+GWBP_API int gwbp_vote_projected(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                                 const void *labels, int32_t label_type, int64_t ls_y, int64_t ls_x, const int32_t *ymap,
+                                 const int32_t *xmap, const gwbp_pixel_weights *pixel_weights, int32_t num_classes, float *C,
+                                 int64_t ldc, float *n, void *stream);
+
 /* Bytes of gwbp_scatter_mask_features' slot store per (Gaussian, tile) intersection: four (int32 label, fp32 sum) slots. */
 #define GWBP_MASK_SLOT_BYTES 32
 

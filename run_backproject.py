@@ -53,6 +53,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--num-classes", type=int, default=None,
                     help="number of classes K of --label-maps (ids outside [0, K) are ignored); with --synthetic: use seeded "
                          "piecewise-constant (Voronoi) label maps with K classes instead of feature maps")
+    ap.add_argument("--votes", choices=["binary", "projection", "gradient"], default=None,
+                    help="with --label-maps (or --synthetic) and --num-classes: per-view votes of the label maps instead of the "
+                         "label field (get_mask3d's voting_method; create_vote_field) on the loaded scene, not pruned: writes "
+                         "votes.pt = {'counts': [N, K] votes, 'views': [N] views that voted, 'method'} and, for K = 2, "
+                         "'mask3d' / 'mask3d_inverted' (votes for class 1 minus votes for class 0, > 0 / < 0)")
     ap.add_argument("--pixel-weights", default=None, metavar="DIR",
                     help="directory with <image name>.pt per-pixel weight maps [H,W] at the view's resolution (bool, uint8 with "
                          "non-zero = 1, float16, bfloat16 or float32): which pixels count and how much, for feature and label "
@@ -137,6 +142,8 @@ def main(argv=None):
         ap.error("--label-maps needs --num-classes K >= 1")
     if labels_mode and args.encoder:
         ap.error("--encoder applies to feature maps, not to --label-maps / --num-classes")
+    if args.votes and not labels_mode:
+        ap.error("--votes needs label maps: --label-maps DIR --num-classes K, or --synthetic CFG --num-classes K")
     masks_mode = bool(args.mask_features)
     if masks_mode and (args.encoder or args.num_classes is not None):
         ap.error("--mask-features takes neither --encoder nor --num-classes")
@@ -263,6 +270,23 @@ def main(argv=None):
                 print("Percentage pruned: ", rep["percentage_pruned"])  # utils.py:348-359
                 print("Max pixel error: ", rep["max_pixel_error"])
                 print("Total pixel error: ", rep["total_pixel_error"])
+
+    if args.votes:
+        # get_mask3d (affordance_transfer/demo_affordance_transfer.py) votes on the loaded Gaussians: no prune step
+        C, n, stats = gsbp_amd.create_vote_field(means, quats, scales, opac, viewmats, K, W, H, label_fn, args.num_classes,
+                                                 method=args.votes, upsample=label_upsample, return_partials=True,
+                                                 pixel_weight_fn=pixel_weight_fn, **cam_kw)
+        if rank == 0:
+            out = {"counts": C.cpu(), "views": n.cpu(), "method": args.votes}
+            if args.num_classes == 2:
+                out["mask3d"], out["mask3d_inverted"] = (m.cpu() for m in gsbp_amd.mask3d_from_votes(C))
+            os.makedirs(args.results_dir, exist_ok=True)
+            path = os.path.join(args.results_dir, "votes.pt")
+            torch.save(out, path)
+            print("saved", path, tuple(C.shape), stats)
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        return
 
     if not args.no_prune and not args.prune_by_product:
         keep = gsbp_amd.pruning.gradient_mask(splats, vm_dev, K_dev, W, H, **cam_kw)
