@@ -6,6 +6,7 @@ JojiJoseph/3dgs-gradient-backprojection), hand-written HIP kernels behind a C AB
     from gsbp_amd import create_label_field       # integer label maps -> per-Gaussian class weights
     from gsbp_amd import create_mask_feature_field  # mask maps + one embedding per mask -> feature field
     from gsbp_amd import create_vote_field          # per-view binary / projection / gradient votes -> 3-D masks
+    from gsbp_amd import knn_search, transfer_labels  # few-shot labels on a finished field: exact inner-product k-NN + majority
 """
 from . import synthetic  # noqa: F401
 from ._lib import GwbpError, build, lib  # noqa: F401
@@ -13,4 +14,5 @@ from .backproject import ViewPipeline, create_feature_field, create_label_field,
 from .engine import Engine, bilinear_index, narrow_labels, nearest_index  # noqa: F401
 from . import scene_io  # noqa: F401
 from .rasterization import rasterization  # noqa: F401
+from .transfer import knn_search, transfer_labels, vote_labels  # noqa: F401
 from .pruning import check_proper_pruning, gradient_mask, prune_by_gradients  # noqa: F401

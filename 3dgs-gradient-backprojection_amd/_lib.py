@@ -57,6 +57,7 @@ EXPORTS = [
     "gwbp_blend_weights_ex", "gwbp_blend_weights_d_ex", "gwbp_blend_tokens_ex", "gwbp_blend_scatter_ex",
     "gwbp_blend_scatter_encoded_ex", "gwbp_blend_weights_rgb", "gwbp_blend_weights_d_rgb", "gwbp_blend_tokens_rgb",
     "gwbp_vote_labels", "gwbp_vote_projected",
+    "gwbp_knn_search", "gwbp_knn_vote",
 ]
 
 
@@ -192,6 +193,9 @@ ARGTYPES = {
     # the votes: labels, label_type, ls_y, ls_x, ymap, xmap, then (seen | pixel weights), num_classes, C, ldc, n, stream
     "gwbp_vote_labels": _WSV + [_P, _I32, _I64, _I64, _P, _P, _I32, _P, _P, _I64, _P, _P],
     "gwbp_vote_projected": _WSV + [_P, _I32, _I64, _I64, _P, _P, C.POINTER(PixelWeights), _I32, _P, _I64, _P, _P],
+    # N, M, D, k, Q, ldq, S, lds, idx, score, stream  /  N, M, k, idx, labels, num_classes, label_out, counts, ldc, stream
+    "gwbp_knn_search": [_I64, _I32, _I32, _I32, _P, _I64, _P, _I64, _P, _P, _P],
+    "gwbp_knn_vote": [_I64, _I32, _I32, _P, _P, _I32, _P, _P, _I64, _P],
 }
 
 _lib: Optional[C.CDLL] = None

@@ -886,6 +886,40 @@ int gwbp_finalize(int64_t N, int32_t D, const float *F, const float *d, float *o
     return launch_finalize(N, D, F, d, out, static_cast<hipStream_t>(stream));
 }
 
+int gwbp_knn_search(int64_t N, int32_t M, int32_t D, int32_t k, const float *Q, int64_t ldq, const float *S, int64_t lds_,
+                    int32_t *idx, float *score, void *stream)
+{
+    if (N < 0 || M < 1 || D < 1)
+        return set_error(GWBP_EINVAL, "knn_search: bad sizes (N=%lld M=%d D=%d)", (long long)N, (int)M, (int)D);
+    if (k < 1 || k > 32)
+        return set_error(GWBP_EINVAL, "knn_search: k must be in [1, 32] (got %d)", (int)k);
+    if (k > M)
+        return set_error(GWBP_EINVAL, "knn_search: k = %d exceeds the number of sources M = %d", (int)k, (int)M);
+    if (ldq < D || lds_ < D)
+        return set_error(GWBP_EINVAL, "knn_search: row strides (%lld, %lld) below D = %d", (long long)ldq, (long long)lds_, (int)D);
+    if (!S || (N > 0 && (!Q || !idx || !score)))
+        return set_error(GWBP_EINVAL, "knn_search: null Q, S, idx or score");
+    if ((reinterpret_cast<uintptr_t>(Q) & 3) || (reinterpret_cast<uintptr_t>(S) & 3))
+        return set_error(GWBP_EINVAL, "knn_search: Q and S must be 4-B aligned");
+    return launch_knn_search(N, M, D, k, Q, ldq, S, lds_, idx, score, static_cast<hipStream_t>(stream));
+}
+
+int gwbp_knn_vote(int64_t N, int32_t M, int32_t k, const int32_t *idx, const int32_t *labels, int32_t num_classes,
+                  int32_t *label_out, int32_t *counts, int64_t ldc, void *stream)
+{
+    if (N < 0 || M < 1)
+        return set_error(GWBP_EINVAL, "knn_vote: bad sizes (N=%lld M=%d)", (long long)N, (int)M);
+    if (k < 1 || k > 32)
+        return set_error(GWBP_EINVAL, "knn_vote: k must be in [1, 32] (got %d)", (int)k);
+    if (num_classes <= 0)
+        return set_error(GWBP_EINVAL, "knn_vote: num_classes must be positive (got %d)", (int)num_classes);
+    if (counts && ldc < num_classes)
+        return set_error(GWBP_EINVAL, "knn_vote: ldc %lld < num_classes %d", (long long)ldc, (int)num_classes);
+    if (!labels || (N > 0 && (!idx || !label_out)))
+        return set_error(GWBP_EINVAL, "knn_vote: null idx, labels or label_out");
+    return launch_knn_vote(N, M, k, idx, labels, num_classes, label_out, counts, ldc, static_cast<hipStream_t>(stream));
+}
+
 int gwbp_accumulate_stats(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, gwbp_stats *accum,
                           void *stream)
 {

@@ -259,6 +259,11 @@ int launch_sh_colors(int64_t N, int degree, int K, const float *means, const flo
 int launch_encode_map(const float *feats, int64_t fs_y, int64_t fs_x, int H, int W, int K, const float *enc, int n_out,
                       float *out, int workgroups, hipStream_t s);
 int launch_finalize(int64_t N, int D, const float *F, const float *d, float *out, hipStream_t s);
+// inner-product k-NN search and the majority label of each row's neighbours (knn.hip)
+int launch_knn_search(int64_t N, int M, int D, int k, const float *Q, int64_t ldq, const float *S, int64_t lds_, int32_t *idx,
+                      float *score, hipStream_t s);
+int launch_knn_vote(int64_t N, int M, int k, const int32_t *idx, const int32_t *labels, int num_classes, int32_t *label_out,
+                    int32_t *counts, int64_t ldc, hipStream_t s);
 int launch_dump_pairs(const Layout &L, const Ws &W, const ViewDev &V, int64_t cap, int32_t *gid, int32_t *pix,
                       float *w, u64 *n_dev, hipStream_t s);
 int launch_accum_stats(const Ws &W, gwbp_stats *accum, hipStream_t s);

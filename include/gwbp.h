@@ -467,6 +467,29 @@ GWBP_API int gwbp_encode_map(const float *feats, int64_t fs_y, int64_t fs_x, int
 /* backproject.py:63,166-169: out = normalize(F / (1e-12 + d)), NaN -> 0.  out may alias F. */
 GWBP_API int gwbp_finalize(int64_t N, int32_t D, const float *F, const float *d, float *out, void *stream);
 
+/* Inner-product k-nearest-neighbour search on a finished field (faiss IndexFlatIP.search; the reference's transfer_affordance,
+ * affordance_transfer/demo_affordance_transfer.py:1377-1396): for every query row Q[g * ldq + 0..D-1], g < N, the k source rows
+ * S[j * lds_ + 0..D-1], j < M, of largest inner product.  idx[N, k] (int32) and score[N, k] (fp32) are dense; each row is sorted
+ * by score descending, then index ascending.  1 <= k <= 32, k <= M < 2^31, D >= 1, ldq >= D, lds_ >= D (strides in floats: the
+ * padded storage of a field goes in as it is).  Scores and selection are fused in one kernel: no score reaches global memory,
+ * and the call needs no workspace.
+ * Arithmetic: every score is one chain of fp32 fused multiply-adds over the D index in an order that depends only on D (the fp32
+ * matrix cores; no reduced-precision operand): results do not depend on a row's position in Q or S, on N, M, k or the launch;
+ * identical source rows tie bit for bit and come in index order; a zero query row scores +0 against every finite source and
+ * returns 0 .. k-1.  A NaN score (a NaN, or 0 x inf, in either row) orders after every number, NaNs among themselves by index.
+ * Rows whose addresses and strides are 16-B aligned are read with 16-B loads, others element by element (same results).
+ * GWBP_EINVAL before any HIP call: N < 0, M < 1, D < 1, k outside [1, 32], k > M, a stride below D, a null or misaligned pointer. */
+GWBP_API int gwbp_knn_search(int64_t N, int32_t M, int32_t D, int32_t k, const float *Q, int64_t ldq, const float *S,
+                             int64_t lds_, int32_t *idx, float *score, void *stream);
+
+/* The majority label of each row of gwbp_knn_search's idx[N, k]: label_out[g] = the most frequent of labels[idx[g, 0..k-1]], the
+ * SMALLEST label among equally frequent ones (np.bincount(row).argmax()).  labels: int32 [M]; a label outside [0, num_classes)
+ * and an index outside [0, M) are ignored; a row with nothing left gets -1.  counts (optional, may be NULL): int32
+ * counts[g * ldc + c], c < num_classes, the row's histogram (overwritten).
+ * GWBP_EINVAL before any HIP call: N < 0, M < 1, k outside [1, 32], num_classes <= 0, ldc < num_classes, a null pointer. */
+GWBP_API int gwbp_knn_vote(int64_t N, int32_t M, int32_t k, const int32_t *idx, const int32_t *labels, int32_t num_classes,
+                           int32_t *label_out, int32_t *counts, int64_t ldc, void *stream);
+
 /* Adds this view's counters into `accum` (device, gwbp_stats) -- used by bench/driver to total pairs. */
 GWBP_API int gwbp_accumulate_stats(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, gwbp_stats *accum,
                           void *stream);
