@@ -49,17 +49,6 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgwbp.so")
 CSRC = os.path.join(_HERE, "csrc")
 
-EXPORTS = [
-    "gwbp_version", "gwbp_last_error_string", "gwbp_workspace_size", "gwbp_project", "gwbp_project_camera", "gwbp_bin_sort",
-    "gwbp_blend_weights", "gwbp_blend_weights_d", "gwbp_blend_scatter", "gwbp_blend_scatter_encoded", "gwbp_blend_tokens", "gwbp_scatter_tokens", "gwbp_accumulate_d", "gwbp_scatter", "gwbp_scatter_encoded", "gwbp_scatter_upsampled", "gwbp_scatter_bilinear", "gwbp_scatter_typed", "gwbp_scatter_upsampled_typed", "gwbp_scatter_bilinear_typed", "gwbp_scatter_tokens_typed", "gwbp_scatter_labels", "gwbp_scatter_mask_features", "gwbp_render", "gwbp_render_pixels", "gwbp_sh_colors",
-    "gwbp_backproject_view", "gwbp_encode_map", "gwbp_finalize",
-    "gwbp_accumulate_stats", "gwbp_read_stats", "gwbp_dump_pairs",
-    "gwbp_blend_weights_ex", "gwbp_blend_weights_d_ex", "gwbp_blend_tokens_ex", "gwbp_blend_scatter_ex",
-    "gwbp_blend_scatter_encoded_ex", "gwbp_blend_weights_rgb", "gwbp_blend_weights_d_rgb", "gwbp_blend_tokens_rgb",
-    "gwbp_vote_labels", "gwbp_vote_projected",
-    "gwbp_knn_search", "gwbp_knn_vote",
-]
-
 
 class View(C.Structure):
     _fields_ = [("viewmat", C.c_float * 16), ("K", C.c_float * 9), ("width", C.c_int32), ("height", C.c_int32),
@@ -197,6 +186,8 @@ ARGTYPES = {
     "gwbp_knn_search": [_I64, _I32, _I32, _I32, _P, _I64, _P, _I64, _P, _P, _P],
     "gwbp_knn_vote": [_I64, _I32, _I32, _P, _P, _I32, _P, _P, _I64, _P],
 }
+# every symbol of include/gwbp.h: the two functions that return strings, then the int-returning ones declared above
+EXPORTS = ["gwbp_version", "gwbp_last_error_string", *ARGTYPES]
 
 _lib: Optional[C.CDLL] = None
 _lib_path = LIB_PATH
@@ -228,12 +219,12 @@ def lib() -> C.CDLL:
             raise GwbpError(f"{path} is a PROFILE build ({L.gwbp_version().decode()}); it is only loaded through "
                             "use_library(path, allow_profile=True) (bench.py --lib, tools/stamp_scatter.py)")
         L.gwbp_last_error_string.restype = C.c_char_p
-        for name in EXPORTS[2:]:
+        for name, argtypes in ARGTYPES.items():
             if path != LIB_PATH and not hasattr(L, name):
                 continue  # an older A/B build; calling the missing entry point still raises
             fn = getattr(L, name)
             fn.restype = C.c_int
-            fn.argtypes = ARGTYPES[name]
+            fn.argtypes = argtypes
         _lib = L
     return _lib
 

@@ -243,6 +243,27 @@ static int check_pixel_weights(const gwbp_pixel_weights *pw, PixW *out, const Pi
 using namespace gwbp;
 static_assert(sizeof(gwbp_pixel_weights) == 32, "gwbp_pixel_weights is part of the ABI");
 
+static hipStream_t as_stream(void *stream) { return static_cast<hipStream_t>(stream); }
+
+// One call on one view of a workspace: what every launcher of such a call takes.
+struct Bound {
+    Layout L;
+    Ws W;
+    ViewDev V;
+    hipStream_t s;
+};
+
+// The caps, then the workspace, then the view: the order include/gwbp.h gives for them.
+static int bind(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host, void *stream,
+                Bound *B)
+{
+    int rc = bind_workspace(caps, workspace, workspace_bytes, &B->L, &B->W);
+    if (rc)
+        return rc;
+    B->s = as_stream(stream);
+    return make_view(view_host, caps, &B->V);
+}
+
 // The RGB composite of the gwbp_blend_*_rgb forms: both pointers or neither (*use = nullptr: the _ex function).
 static int check_rgb(const float *colors, float *image, RgbOut *out, const RgbOut **use)
 {
@@ -255,6 +276,62 @@ static int check_rgb(const float *colors, float *image, RgbOut *out, const RgbOu
     out->colors = colors, out->image = image;
     *use = out;
     return GWBP_OK;
+}
+
+// The pixel-weight map and the RGB composite of the three _rgb blends, checked in that order before anything else.
+struct BlendExtras {
+    PixW P;
+    RgbOut R;
+    const PixW *pw;
+    const RgbOut *rgb;
+};
+
+static int check_blend_extras(const gwbp_pixel_weights *pixel_weights, const float *colors, float *image, BlendExtras *X)
+{
+    const int rc = check_pixel_weights(pixel_weights, &X->P, &X->pw);
+    return rc ? rc : check_rgb(colors, image, &X->R, &X->rgb);
+}
+
+static bool known_map_type(int32_t mt) { return mt == GWBP_MAP_F32 || mt == GWBP_MAP_F16 || mt == GWBP_MAP_BF16; }
+
+static int check_label_type(int32_t label_type)
+{
+    if (label_type != GWBP_LABEL_U8 && label_type != GWBP_LABEL_I16 && label_type != GWBP_LABEL_I32)
+        return set_error(GWBP_EINVAL, "unknown label type %d", (int)label_type);
+    return GWBP_OK;
+}
+
+static int check_index_maps(const char *fn, const int32_t *ymap, const int32_t *xmap)
+{
+    if (!ymap != !xmap)
+        return set_error(GWBP_EINVAL, "%s needs both index maps or neither", fn);
+    return GWBP_OK;
+}
+
+static int check_label_map(const void *labels, int64_t ls_y, int64_t ls_x)
+{
+    if (!labels || ls_y < 0 || ls_x < 0)
+        return set_error(GWBP_EINVAL, "bad label map arguments (strides %lld %lld)", (long long)ls_y, (long long)ls_x);
+    return GWBP_OK;
+}
+
+// The label map and the [N, num_classes] accumulator (F of gwbp_scatter_labels, C of the votes; `acc` and `ld` are its name and
+// its leading dimension's in the messages), checked before the caps, the workspace or the view.
+static int check_label_args(const char *fn, const void *labels, int32_t label_type, int64_t ls_y, int64_t ls_x, const int32_t *ymap,
+                            const int32_t *xmap, int32_t num_classes, const char *acc, const float *A, const char *ld, int64_t lda)
+{
+    int rc = check_label_type(label_type);
+    if (rc)
+        return rc;
+    if (num_classes <= 0)
+        return set_error(GWBP_EINVAL, "num_classes must be positive (got %d)", (int)num_classes);
+    if (lda < num_classes)
+        return set_error(GWBP_EINVAL, "%s %lld < num_classes %d", ld, (long long)lda, (int)num_classes);
+    if (!A)
+        return set_error(GWBP_EINVAL, "null %s", acc);
+    if ((rc = check_index_maps(fn, ymap, xmap)))
+        return rc;
+    return check_label_map(labels, ls_y, ls_x);
 }
 
 extern "C" {
@@ -299,34 +376,26 @@ int gwbp_project_camera(const gwbp_caps *caps, void *workspace, size_t workspace
         return set_error(GWBP_EINVAL, "unknown camera model %d", (int)camera_model);
     if (rasterize_mode != GWBP_RASTERIZE_CLASSIC && rasterize_mode != GWBP_RASTERIZE_ANTIALIASED)
         return set_error(GWBP_EINVAL, "unknown rasterize mode %d", (int)rasterize_mode);
-    Layout L;
-    Ws W;
-    ViewDev V;
-    int rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W);
+    Bound B;
+    int rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B);
     if (rc)
         return rc;
-    if ((rc = make_view(view_host, caps, &V)))
-        return rc;
-    if (L.n > 0 && (!means || !quats || !scales || !opacities))
+    if (B.L.n > 0 && (!means || !quats || !scales || !opacities))
         return set_error(GWBP_EINVAL, "null Gaussian parameter pointer");
     if (reinterpret_cast<uintptr_t>(quats) & 15)
         return set_error(GWBP_EINVAL, "quats must be 16-B aligned");
-    return launch_project(L, W, V, means, quats, scales, opacities, radii, means2d, depths, conics,
-                          static_cast<hipStream_t>(stream), camera_model, rasterize_mode, compensations);
+    return launch_project(B.L, B.W, B.V, means, quats, scales, opacities, radii, means2d, depths, conics, B.s, camera_model,
+                          rasterize_mode, compensations);
 }
 
 int gwbp_bin_sort(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
                   int64_t *isect_ids, int32_t *flatten_ids, int32_t *tile_offsets, void *stream)
 {
-    Layout L;
-    Ws W;
-    ViewDev V;
-    int rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W);
+    Bound B;
+    int rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B);
     if (rc)
         return rc;
-    if ((rc = make_view(view_host, caps, &V)))
-        return rc;
-    return launch_bin_sort(L, W, V, isect_ids, flatten_ids, tile_offsets, static_cast<hipStream_t>(stream));
+    return launch_bin_sort(B.L, B.W, B.V, isect_ids, flatten_ids, tile_offsets, B.s);
 }
 
 int gwbp_blend_weights(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
@@ -345,21 +414,14 @@ int gwbp_blend_weights_rgb(const gwbp_caps *caps, void *workspace, size_t worksp
                            float *alphas, const gwbp_pixel_weights *pixel_weights, const float *colors, float *image,
                            void *stream)
 {
-    PixW P;
-    const PixW *pw;
-    RgbOut R;
-    const RgbOut *rgb;
-    int rc = check_pixel_weights(pixel_weights, &P, &pw);
-    if (rc || (rc = check_rgb(colors, image, &R, &rgb)))
+    BlendExtras X;
+    int rc = check_blend_extras(pixel_weights, colors, image, &X);
+    if (rc)
         return rc;
-    Layout L;
-    Ws W;
-    ViewDev V;
-    if ((rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W)))
+    Bound B;
+    if ((rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B)))
         return rc;
-    if ((rc = make_view(view_host, caps, &V)))
-        return rc;
-    return launch_blend(L, W, V, alphas, nullptr, 0.f, static_cast<hipStream_t>(stream), nullptr, 0, 1.0f, nullptr, pw, rgb);
+    return launch_blend(B.L, B.W, B.V, alphas, nullptr, 0.f, B.s, nullptr, 0, 1.0f, nullptr, X.pw, X.rgb);
 }
 
 int gwbp_blend_weights_d(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
@@ -379,23 +441,16 @@ int gwbp_blend_weights_d_rgb(const gwbp_caps *caps, void *workspace, size_t work
                              float *alphas, float scale_d, float *d, const gwbp_pixel_weights *pixel_weights,
                              const float *colors, float *image, void *stream)
 {
-    PixW P;
-    const PixW *pw;
-    RgbOut R;
-    const RgbOut *rgb;
-    int rc = check_pixel_weights(pixel_weights, &P, &pw);
-    if (rc || (rc = check_rgb(colors, image, &R, &rgb)))
+    BlendExtras X;
+    int rc = check_blend_extras(pixel_weights, colors, image, &X);
+    if (rc)
         return rc;
-    Layout L;
-    Ws W;
-    ViewDev V;
-    if ((rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W)))
-        return rc;
-    if ((rc = make_view(view_host, caps, &V)))
+    Bound B;
+    if ((rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B)))
         return rc;
     if (!d)
         return set_error(GWBP_EINVAL, "null d");
-    return launch_blend(L, W, V, alphas, d, scale_d, static_cast<hipStream_t>(stream), nullptr, 0, 1.0f, nullptr, pw, rgb);
+    return launch_blend(B.L, B.W, B.V, alphas, d, scale_d, B.s, nullptr, 0, 1.0f, nullptr, X.pw, X.rgb);
 }
 
 int gwbp_blend_scatter(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
@@ -415,15 +470,11 @@ int gwbp_blend_scatter_ex(const gwbp_caps *caps, void *workspace, size_t workspa
     int rc = check_pixel_weights(pixel_weights, &P, &pw);
     if (rc)
         return rc;
-    Layout L;
-    Ws W;
-    ViewDev V;
-    if ((rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W)))
-        return rc;
-    if ((rc = make_view(view_host, caps, &V)))
+    Bound B;
+    if ((rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B)))
         return rc;
     const FeatMap M{feats, fs_y, fs_x, 1, nullptr, nullptr, nullptr, nullptr, 0, 0};
-    return launch_blend(L, W, V, alphas, d, scale_d, static_cast<hipStream_t>(stream), &M, D, scale_f, F, pw);
+    return launch_blend(B.L, B.W, B.V, alphas, d, scale_d, B.s, &M, D, scale_f, F, pw);
 }
 
 int gwbp_blend_scatter_encoded(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
@@ -444,18 +495,14 @@ int gwbp_blend_scatter_encoded_ex(const gwbp_caps *caps, void *workspace, size_t
     int rc = check_pixel_weights(pixel_weights, &P, &pw);
     if (rc)
         return rc;
-    Layout L;
-    Ws W;
-    ViewDev V;
-    if ((rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W)))
-        return rc;
-    if ((rc = make_view(view_host, caps, &V)))
+    Bound B;
+    if ((rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B)))
         return rc;
     if (!encoder)
         return set_error(GWBP_EINVAL, "null encoder");
     FeatMap M{feats, fs_y, fs_x, 1, nullptr, nullptr, nullptr, nullptr, 0, 0};
     M.enc = encoder, M.enc_k = K;
-    return launch_blend(L, W, V, alphas, d, scale_d, static_cast<hipStream_t>(stream), &M, n_out, scale_f, F, pw);
+    return launch_blend(B.L, B.W, B.V, alphas, d, scale_d, B.s, &M, n_out, scale_f, F, pw);
 }
 
 int gwbp_blend_tokens(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
@@ -476,81 +523,105 @@ int gwbp_blend_tokens_rgb(const gwbp_caps *caps, void *workspace, size_t workspa
                           const int32_t *ymap, const int32_t *xmap, float *alphas, const gwbp_pixel_weights *pixel_weights,
                           const float *colors, float *image, void *stream)
 {
-    PixW P;
-    const PixW *pw;
-    RgbOut R;
-    const RgbOut *rgb;
-    int rc = check_pixel_weights(pixel_weights, &P, &pw);
-    if (rc || (rc = check_rgb(colors, image, &R, &rgb)))
+    BlendExtras X;
+    int rc = check_blend_extras(pixel_weights, colors, image, &X);
+    if (rc)
         return rc;
-    Layout L;
-    Ws W;
-    ViewDev V;
-    if ((rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W)))
+    Bound B;
+    if ((rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B)))
         return rc;
-    if ((rc = make_view(view_host, caps, &V)))
+    return launch_blend_tokens(B.L, B.W, B.V, alphas, ymap, xmap, B.s, X.pw, X.rgb);
+}
+
+// gwbp_scatter_tokens and its typed form.  (The token pointer travels as it is; only the kernels of the map type dereference it.)
+static int scatter_tokens(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                          const void *tokens, int mt, int64_t ts_y, int64_t ts_x, int32_t D, const int32_t *ymap,
+                          const int32_t *xmap, float scale_f, float scale_d, float *F, float *d, void *stream)
+{
+    Bound B;
+    int rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B);
+    if (rc)
         return rc;
-    return launch_blend_tokens(L, W, V, alphas, ymap, xmap, static_cast<hipStream_t>(stream), pw, rgb);
+    if (mt == GWBP_MAP_F32)
+        return launch_token_apply(B.L, B.W, B.V, static_cast<const float *>(tokens), ts_y, ts_x, D, ymap, xmap, scale_f, scale_d, F,
+                                  d, B.s);
+    return launch_token_apply_half(B.L, B.W, B.V, tokens, ts_y, ts_x, D, ymap, xmap, scale_f, scale_d, F, d, B.s, mt);
 }
 
 int gwbp_scatter_tokens(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
                         const float *tokens, int64_t ts_y, int64_t ts_x, int32_t D, const int32_t *ymap, const int32_t *xmap,
                         float scale_f, float scale_d, float *F, float *d, void *stream)
 {
-    Layout L;
-    Ws W;
-    ViewDev V;
-    int rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W);
-    if (rc)
-        return rc;
-    if ((rc = make_view(view_host, caps, &V)))
-        return rc;
-    return launch_token_apply(L, W, V, tokens, ts_y, ts_x, D, ymap, xmap, scale_f, scale_d, F, d, static_cast<hipStream_t>(stream));
+    return scatter_tokens(caps, workspace, workspace_bytes, view_host, tokens, GWBP_MAP_F32, ts_y, ts_x, D, ymap, xmap, scale_f,
+                          scale_d, F, d, stream);
 }
 
 int gwbp_accumulate_d(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
                       float scale_d, float *d, void *stream)
 {
-    Layout L;
-    Ws W;
-    ViewDev V;
-    int rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W);
+    Bound B;
+    int rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B);
     if (rc)
-        return rc;
-    if ((rc = make_view(view_host, caps, &V)))
         return rc;
     if (!d)
         return set_error(GWBP_EINVAL, "null d");
-    return launch_accum_d(L, W, V, scale_d, d, static_cast<hipStream_t>(stream));
+    return launch_accum_d(B.L, B.W, B.V, scale_d, d, B.s);
 }
 
+// The scatter family.  Each form (plain, upsampled, bilinear) has ONE function that runs its pointer checks, in the name `fn` of
+// the entry point that was called, and builds its FeatMap; the untyped entry point is its GWBP_MAP_F32 call.  (The feature
+// pointer travels in FeatMap::p as it is; only the kernels of the map type dereference it.)
 static int scatter_impl(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
                         const FeatMap &M, int32_t D, float scale_f, float scale_d, float *F, float *d, void *stream,
                         int mt = GWBP_MAP_F32)
 {
-    Layout L;
-    Ws W;
-    ViewDev V;
-    int rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W);
+    Bound B;
+    int rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B);
     if (rc)
-        return rc;
-    if ((rc = make_view(view_host, caps, &V)))
         return rc;
     if ((rc = check_feats(M.p, M.fs_y, M.fs_x, M.fs_c, D)))
         return rc;
-    if (!F && L.n > 0)
+    if (!F && B.L.n > 0)
         return set_error(GWBP_EINVAL, "null F");
-    return launch_scatter(L, W, V, M, D, scale_f, scale_d, F, d, static_cast<hipStream_t>(stream), mt);
+    return launch_scatter(B.L, B.W, B.V, M, D, scale_f, scale_d, F, d, B.s, mt);
 }
 
-static bool known_map_type(int32_t mt) { return mt == GWBP_MAP_F32 || mt == GWBP_MAP_F16 || mt == GWBP_MAP_BF16; }
+static int scatter_plain(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                         const void *feats, int mt, int64_t fs_y, int64_t fs_x, int64_t fs_c, int32_t D, float scale_f,
+                         float scale_d, float *F, float *d, void *stream)
+{
+    const FeatMap M{static_cast<const float *>(feats), fs_y, fs_x, fs_c, nullptr, nullptr, nullptr, nullptr, 0, 0};
+    return scatter_impl(caps, workspace, workspace_bytes, view_host, M, D, scale_f, scale_d, F, d, stream, mt);
+}
+
+static int scatter_upsampled(const char *fn, const gwbp_caps *caps, void *workspace, size_t workspace_bytes,
+                             const gwbp_view *view_host, const void *feats, int mt, int64_t fs_y, int64_t fs_x, int64_t fs_c,
+                             int32_t D, const int32_t *ymap, const int32_t *xmap, float scale_f, float scale_d, float *F, float *d,
+                             void *stream)
+{
+    if (!ymap || !xmap)
+        return set_error(GWBP_EINVAL, "%s needs both index maps", fn);
+    const FeatMap M{static_cast<const float *>(feats), fs_y, fs_x, fs_c, ymap, xmap, nullptr, nullptr, 0, 0};
+    return scatter_impl(caps, workspace, workspace_bytes, view_host, M, D, scale_f, scale_d, F, d, stream, mt);
+}
+
+static int scatter_bilinear(const char *fn, const gwbp_caps *caps, void *workspace, size_t workspace_bytes,
+                            const gwbp_view *view_host, const void *feats, int mt, int64_t fs_y, int64_t fs_x, int64_t fs_c,
+                            int32_t D, int32_t lr_h, int32_t lr_w, const int32_t *y0, const float *ly, const int32_t *x0,
+                            const float *lx, float scale_f, float scale_d, float *F, float *d, void *stream)
+{
+    if (!y0 || !x0 || !ly || !lx || lr_h < 1 || lr_w < 1)
+        return set_error(GWBP_EINVAL, "%s needs both index maps, both weight maps and the map size", fn);
+    const FeatMap M{static_cast<const float *>(feats), fs_y, fs_x, fs_c, y0, x0, ly, lx, lr_h, lr_w};
+    return scatter_impl(caps, workspace, workspace_bytes, view_host, M, D, scale_f, scale_d, F, d, stream, mt);
+}
 
 int gwbp_scatter(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
                  const float *feats, int64_t fs_y, int64_t fs_x, int64_t fs_c, int32_t D, float scale_f,
                  float scale_d, float *F, float *d, void *stream)
 {
-    const FeatMap M{feats, fs_y, fs_x, fs_c, nullptr, nullptr, nullptr, nullptr, 0, 0};
-    return scatter_impl(caps, workspace, workspace_bytes, view_host, M, D, scale_f, scale_d, F, d, stream);
+    return scatter_plain(caps, workspace, workspace_bytes, view_host, feats, GWBP_MAP_F32, fs_y, fs_x, fs_c, D, scale_f, scale_d, F,
+                         d, stream);
 }
 
 int gwbp_scatter_encoded(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
@@ -569,10 +640,8 @@ int gwbp_scatter_upsampled(const gwbp_caps *caps, void *workspace, size_t worksp
                            int32_t D, const int32_t *ymap, const int32_t *xmap, float scale_f, float scale_d, float *F,
                            float *d, void *stream)
 {
-    if (!ymap || !xmap)
-        return set_error(GWBP_EINVAL, "gwbp_scatter_upsampled needs both index maps");
-    const FeatMap M{feats, fs_y, fs_x, fs_c, ymap, xmap, nullptr, nullptr, 0, 0};
-    return scatter_impl(caps, workspace, workspace_bytes, view_host, M, D, scale_f, scale_d, F, d, stream);
+    return scatter_upsampled("gwbp_scatter_upsampled", caps, workspace, workspace_bytes, view_host, feats, GWBP_MAP_F32, fs_y, fs_x,
+                             fs_c, D, ymap, xmap, scale_f, scale_d, F, d, stream);
 }
 
 int gwbp_scatter_bilinear(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
@@ -580,25 +649,20 @@ int gwbp_scatter_bilinear(const gwbp_caps *caps, void *workspace, size_t workspa
                           int32_t lr_w, const int32_t *y0, const float *ly, const int32_t *x0, const float *lx,
                           float scale_f, float scale_d, float *F, float *d, void *stream)
 {
-    if (!y0 || !x0 || !ly || !lx || lr_h < 1 || lr_w < 1)
-        return set_error(GWBP_EINVAL, "gwbp_scatter_bilinear needs both index maps, both weight maps and the map size");
-    const FeatMap M{feats, fs_y, fs_x, fs_c, y0, x0, ly, lx, lr_h, lr_w};
-    return scatter_impl(caps, workspace, workspace_bytes, view_host, M, D, scale_f, scale_d, F, d, stream);
+    return scatter_bilinear("gwbp_scatter_bilinear", caps, workspace, workspace_bytes, view_host, feats, GWBP_MAP_F32, fs_y, fs_x,
+                            fs_c, D, lr_h, lr_w, y0, ly, x0, lx, scale_f, scale_d, F, d, stream);
 }
 
-// The typed entry points: the map type is validated before anything else; GWBP_MAP_F32 is the untyped function's call.
-// (The feature pointer travels in FeatMap::p as it is; only the kernels of the map type dereference it.)
+// The typed entry points: the map type is validated before anything else; GWBP_MAP_F32 is the untyped function's call, with
+// that function's name in its messages.
 int gwbp_scatter_typed(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
                        const void *feats, int32_t map_type, int64_t fs_y, int64_t fs_x, int64_t fs_c, int32_t D, float scale_f,
                        float scale_d, float *F, float *d, void *stream)
 {
     if (!known_map_type(map_type))
         return set_error(GWBP_EINVAL, "unknown map type %d", (int)map_type);
-    if (map_type == GWBP_MAP_F32)
-        return gwbp_scatter(caps, workspace, workspace_bytes, view_host, static_cast<const float *>(feats), fs_y, fs_x, fs_c, D,
-                            scale_f, scale_d, F, d, stream);
-    const FeatMap M{static_cast<const float *>(feats), fs_y, fs_x, fs_c, nullptr, nullptr, nullptr, nullptr, 0, 0};
-    return scatter_impl(caps, workspace, workspace_bytes, view_host, M, D, scale_f, scale_d, F, d, stream, map_type);
+    return scatter_plain(caps, workspace, workspace_bytes, view_host, feats, map_type, fs_y, fs_x, fs_c, D, scale_f, scale_d, F, d,
+                         stream);
 }
 
 int gwbp_scatter_upsampled_typed(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
@@ -608,13 +672,9 @@ int gwbp_scatter_upsampled_typed(const gwbp_caps *caps, void *workspace, size_t 
 {
     if (!known_map_type(map_type))
         return set_error(GWBP_EINVAL, "unknown map type %d", (int)map_type);
-    if (map_type == GWBP_MAP_F32)
-        return gwbp_scatter_upsampled(caps, workspace, workspace_bytes, view_host, static_cast<const float *>(feats), fs_y, fs_x,
-                                      fs_c, D, ymap, xmap, scale_f, scale_d, F, d, stream);
-    if (!ymap || !xmap)
-        return set_error(GWBP_EINVAL, "gwbp_scatter_upsampled_typed needs both index maps");
-    const FeatMap M{static_cast<const float *>(feats), fs_y, fs_x, fs_c, ymap, xmap, nullptr, nullptr, 0, 0};
-    return scatter_impl(caps, workspace, workspace_bytes, view_host, M, D, scale_f, scale_d, F, d, stream, map_type);
+    return scatter_upsampled(map_type == GWBP_MAP_F32 ? "gwbp_scatter_upsampled" : "gwbp_scatter_upsampled_typed", caps, workspace,
+                             workspace_bytes, view_host, feats, map_type, fs_y, fs_x, fs_c, D, ymap, xmap, scale_f, scale_d, F, d,
+                             stream);
 }
 
 int gwbp_scatter_bilinear_typed(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
@@ -624,13 +684,9 @@ int gwbp_scatter_bilinear_typed(const gwbp_caps *caps, void *workspace, size_t w
 {
     if (!known_map_type(map_type))
         return set_error(GWBP_EINVAL, "unknown map type %d", (int)map_type);
-    if (map_type == GWBP_MAP_F32)
-        return gwbp_scatter_bilinear(caps, workspace, workspace_bytes, view_host, static_cast<const float *>(feats), fs_y, fs_x,
-                                     fs_c, D, lr_h, lr_w, y0, ly, x0, lx, scale_f, scale_d, F, d, stream);
-    if (!y0 || !x0 || !ly || !lx || lr_h < 1 || lr_w < 1)
-        return set_error(GWBP_EINVAL, "gwbp_scatter_bilinear_typed needs both index maps, both weight maps and the map size");
-    const FeatMap M{static_cast<const float *>(feats), fs_y, fs_x, fs_c, y0, x0, ly, lx, lr_h, lr_w};
-    return scatter_impl(caps, workspace, workspace_bytes, view_host, M, D, scale_f, scale_d, F, d, stream, map_type);
+    return scatter_bilinear(map_type == GWBP_MAP_F32 ? "gwbp_scatter_bilinear" : "gwbp_scatter_bilinear_typed", caps, workspace,
+                            workspace_bytes, view_host, feats, map_type, fs_y, fs_x, fs_c, D, lr_h, lr_w, y0, ly, x0, lx, scale_f,
+                            scale_d, F, d, stream);
 }
 
 int gwbp_scatter_tokens_typed(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
@@ -639,19 +695,8 @@ int gwbp_scatter_tokens_typed(const gwbp_caps *caps, void *workspace, size_t wor
 {
     if (!known_map_type(map_type))
         return set_error(GWBP_EINVAL, "unknown map type %d", (int)map_type);
-    if (map_type == GWBP_MAP_F32)
-        return gwbp_scatter_tokens(caps, workspace, workspace_bytes, view_host, static_cast<const float *>(tokens), ts_y, ts_x, D,
-                                   ymap, xmap, scale_f, scale_d, F, d, stream);
-    Layout L;
-    Ws W;
-    ViewDev V;
-    int rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W);
-    if (rc)
-        return rc;
-    if ((rc = make_view(view_host, caps, &V)))
-        return rc;
-    return launch_token_apply_half(L, W, V, tokens, ts_y, ts_x, D, ymap, xmap, scale_f, scale_d, F, d,
-                                   static_cast<hipStream_t>(stream), map_type);
+    return scatter_tokens(caps, workspace, workspace_bytes, view_host, tokens, map_type, ts_y, ts_x, D, ymap, xmap, scale_f, scale_d,
+                          F, d, stream);
 }
 
 int gwbp_scatter_labels(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
@@ -660,28 +705,14 @@ int gwbp_scatter_labels(const gwbp_caps *caps, void *workspace, size_t workspace
                         void *stream)
 {
     // the label arguments first: nothing of the caps, the workspace or the view is looked at before they pass
-    if (label_type != GWBP_LABEL_U8 && label_type != GWBP_LABEL_I16 && label_type != GWBP_LABEL_I32)
-        return set_error(GWBP_EINVAL, "unknown label type %d", (int)label_type);
-    if (num_classes <= 0)
-        return set_error(GWBP_EINVAL, "num_classes must be positive (got %d)", (int)num_classes);
-    if (ldf < num_classes)
-        return set_error(GWBP_EINVAL, "ldf %lld < num_classes %d", (long long)ldf, (int)num_classes);
-    if (!F)
-        return set_error(GWBP_EINVAL, "null F");
-    if (!ymap != !xmap)
-        return set_error(GWBP_EINVAL, "gwbp_scatter_labels needs both index maps or neither");
-    if (!labels || ls_y < 0 || ls_x < 0)
-        return set_error(GWBP_EINVAL, "bad label map arguments (strides %lld %lld)", (long long)ls_y, (long long)ls_x);
-    Layout L;
-    Ws W;
-    ViewDev V;
-    int rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W);
+    int rc = check_label_args("gwbp_scatter_labels", labels, label_type, ls_y, ls_x, ymap, xmap, num_classes, "F", F, "ldf", ldf);
     if (rc)
         return rc;
-    if ((rc = make_view(view_host, caps, &V)))
+    Bound B;
+    if ((rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B)))
         return rc;
-    return launch_scatter_labels(L, W, V, labels, label_type, ls_y, ls_x, ymap, xmap, num_classes, scale_f, scale_d, F, ldf, d,
-                                 static_cast<hipStream_t>(stream));
+    return launch_scatter_labels(B.L, B.W, B.V, labels, label_type, ls_y, ls_x, ymap, xmap, num_classes, scale_f, scale_d, F, ldf, d,
+                                 B.s);
 }
 
 int gwbp_scatter_mask_features(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
@@ -691,18 +722,19 @@ int gwbp_scatter_mask_features(const gwbp_caps *caps, void *workspace, size_t wo
                                uint32_t *n_spilled, void *stream)
 {
     // the map, table and slot arguments first: nothing of the workspace or the view is looked at before they pass
-    if (label_type != GWBP_LABEL_U8 && label_type != GWBP_LABEL_I16 && label_type != GWBP_LABEL_I32)
-        return set_error(GWBP_EINVAL, "unknown label type %d", (int)label_type);
+    int rc = check_label_type(label_type);
+    if (rc)
+        return rc;
     if (!known_map_type(table_type))
         return set_error(GWBP_EINVAL, "unknown table type %d", (int)table_type);
     if (num_masks <= 0)
         return set_error(GWBP_EINVAL, "num_masks must be positive (got %d)", (int)num_masks);
     if (D < 4 || D % 4 != 0)
         return set_error(GWBP_EINVAL, "gwbp_scatter_mask_features: D must be a positive multiple of 4 (got %d)", (int)D);
-    if (!labels || ls_y < 0 || ls_x < 0)
-        return set_error(GWBP_EINVAL, "bad label map arguments (strides %lld %lld)", (long long)ls_y, (long long)ls_x);
-    if (!ymap != !xmap)
-        return set_error(GWBP_EINVAL, "gwbp_scatter_mask_features needs both index maps or neither");
+    if ((rc = check_label_map(labels, ls_y, ls_x)))
+        return rc;
+    if ((rc = check_index_maps("gwbp_scatter_mask_features", ymap, xmap)))
+        return rc;
     const uintptr_t talign = table_type == GWBP_MAP_F32 ? 15 : 7; // one float4 / four halves per lane load
     if (!table || ts_row < D || (ts_row & 3) || (reinterpret_cast<uintptr_t>(table) & talign))
         return set_error(GWBP_EINVAL, "table rows must be %d-B aligned runs of D contiguous elements (row stride %lld)",
@@ -711,63 +743,36 @@ int gwbp_scatter_mask_features(const gwbp_caps *caps, void *workspace, size_t wo
         return set_error(GWBP_EINVAL, "F must be a non-null, 16-B aligned [N, D] array");
     if (!slots || (reinterpret_cast<uintptr_t>(slots) & 15))
         return set_error(GWBP_EINVAL, "slots must be a non-null, 16-B aligned buffer");
-    Layout L;
-    Ws W;
-    ViewDev V;
-    int rc = make_layout(caps, &L);
-    if (rc)
+    // the slot store is sized by the caps alone: checked against the layout before the workspace is bound
+    Bound B;
+    if ((rc = make_layout(caps, &B.L)))
         return rc;
-    if (slots_bytes / GWBP_MASK_SLOT_BYTES < (size_t)L.isect_cap)
+    if (slots_bytes / GWBP_MASK_SLOT_BYTES < (size_t)B.L.isect_cap)
         return set_error(GWBP_EINVAL, "slots: have %zu bytes, need %d x isect_cap = %zu", slots_bytes, GWBP_MASK_SLOT_BYTES,
-                         (size_t)GWBP_MASK_SLOT_BYTES * (size_t)L.isect_cap);
-    if ((rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W)))
-        return rc;
-    if ((rc = make_view(view_host, caps, &V)))
+                         (size_t)GWBP_MASK_SLOT_BYTES * (size_t)B.L.isect_cap);
+    if ((rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B)))
         return rc;
     MaskSlots S;
     S.labels = static_cast<int4 *>(slots);
-    S.sums = reinterpret_cast<float4 *>(static_cast<char *>(slots) + (size_t)L.isect_cap * sizeof(int4));
-    return launch_mask_features(L, W, V, labels, label_type, ls_y, ls_x, ymap, xmap, table, table_type, ts_row, num_masks, D,
-                                scale_f, scale_d, F, d, S, n_spilled, static_cast<hipStream_t>(stream));
-}
-
-// The label, count and bitset arguments of the two vote entry points, checked before the caps, the workspace or the view.
-static int check_vote_args(const char *fn, const void *labels, int32_t label_type, int64_t ls_y, int64_t ls_x, const int32_t *ymap,
-                           const int32_t *xmap, int32_t num_classes, const float *C, int64_t ldc)
-{
-    if (label_type != GWBP_LABEL_U8 && label_type != GWBP_LABEL_I16 && label_type != GWBP_LABEL_I32)
-        return set_error(GWBP_EINVAL, "unknown label type %d", (int)label_type);
-    if (num_classes <= 0)
-        return set_error(GWBP_EINVAL, "num_classes must be positive (got %d)", (int)num_classes);
-    if (ldc < num_classes)
-        return set_error(GWBP_EINVAL, "ldc %lld < num_classes %d", (long long)ldc, (int)num_classes);
-    if (!C)
-        return set_error(GWBP_EINVAL, "null C");
-    if (!ymap != !xmap)
-        return set_error(GWBP_EINVAL, "%s needs both index maps or neither", fn);
-    if (!labels || ls_y < 0 || ls_x < 0)
-        return set_error(GWBP_EINVAL, "bad label map arguments (strides %lld %lld)", (long long)ls_y, (long long)ls_x);
-    return GWBP_OK;
+    S.sums = reinterpret_cast<float4 *>(static_cast<char *>(slots) + (size_t)B.L.isect_cap * sizeof(int4));
+    return launch_mask_features(B.L, B.W, B.V, labels, label_type, ls_y, ls_x, ymap, xmap, table, table_type, ts_row, num_masks, D,
+                                scale_f, scale_d, F, d, S, n_spilled, B.s);
 }
 
 int gwbp_vote_labels(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
                      const void *labels, int32_t label_type, int64_t ls_y, int64_t ls_x, const int32_t *ymap, const int32_t *xmap,
                      int32_t num_classes, uint32_t *seen, float *C, int64_t ldc, float *n, void *stream)
 {
-    int rc = check_vote_args("gwbp_vote_labels", labels, label_type, ls_y, ls_x, ymap, xmap, num_classes, C, ldc);
+    // the label, count and bitset arguments before the caps, the workspace or the view
+    int rc = check_label_args("gwbp_vote_labels", labels, label_type, ls_y, ls_x, ymap, xmap, num_classes, "C", C, "ldc", ldc);
     if (rc)
         return rc;
     if (!seen || (reinterpret_cast<uintptr_t>(seen) & 3))
         return set_error(GWBP_EINVAL, "seen must be a non-null, 4-B aligned uint32 bitset");
-    Layout L;
-    Ws W;
-    ViewDev V;
-    if ((rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W)))
+    Bound B;
+    if ((rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B)))
         return rc;
-    if ((rc = make_view(view_host, caps, &V)))
-        return rc;
-    return launch_vote_labels(L, W, V, labels, label_type, ls_y, ls_x, ymap, xmap, num_classes, seen, C, ldc, n,
-                              static_cast<hipStream_t>(stream));
+    return launch_vote_labels(B.L, B.W, B.V, labels, label_type, ls_y, ls_x, ymap, xmap, num_classes, seen, C, ldc, n, B.s);
 }
 
 int gwbp_vote_projected(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
@@ -780,49 +785,36 @@ int gwbp_vote_projected(const gwbp_caps *caps, void *workspace, size_t workspace
     int rc = check_pixel_weights(pixel_weights, &P, &pw);
     if (rc)
         return rc;
-    if ((rc = check_vote_args("gwbp_vote_projected", labels, label_type, ls_y, ls_x, ymap, xmap, num_classes, C, ldc)))
+    if ((rc = check_label_args("gwbp_vote_projected", labels, label_type, ls_y, ls_x, ymap, xmap, num_classes, "C", C, "ldc", ldc)))
         return rc;
-    Layout L;
-    Ws W;
-    ViewDev V;
-    if ((rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W)))
+    Bound B;
+    if ((rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B)))
         return rc;
-    if ((rc = make_view(view_host, caps, &V)))
-        return rc;
-    return launch_vote_projected(L, W, V, labels, label_type, ls_y, ls_x, ymap, xmap, pw, num_classes, C, ldc, n,
-                                 static_cast<hipStream_t>(stream));
+    return launch_vote_projected(B.L, B.W, B.V, labels, label_type, ls_y, ls_x, ymap, xmap, pw, num_classes, C, ldc, n, B.s);
 }
 
 int gwbp_render(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
                 const float *colors, int32_t D, float *out, void *stream)
 {
-    Layout L;
-    Ws W;
-    ViewDev V;
-    int rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W);
+    Bound B;
+    int rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B);
     if (rc)
-        return rc;
-    if ((rc = make_view(view_host, caps, &V)))
         return rc;
     if (!colors || !out || D < 1)
         return set_error(GWBP_EINVAL, "bad render arguments");
-    return launch_render(L, W, V, colors, D, out, static_cast<hipStream_t>(stream));
+    return launch_render(B.L, B.W, B.V, colors, D, out, B.s);
 }
 
 int gwbp_render_pixels(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
                        const float *colors, int32_t D, float *out, float *alphas, void *stream)
 {
-    Layout L;
-    Ws W;
-    ViewDev V;
-    int rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W);
+    Bound B;
+    int rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B);
     if (rc)
-        return rc;
-    if ((rc = make_view(view_host, caps, &V)))
         return rc;
     if (!colors || !out || D < 1 || D > 32)
         return set_error(GWBP_EINVAL, "render_pixels needs colors, out and 1 <= D <= 32 (got D=%d)", D);
-    return launch_render_px(W, V, colors, D, out, alphas, static_cast<hipStream_t>(stream));
+    return launch_render_px(B.W, B.V, colors, D, out, alphas, B.s);
 }
 
 int gwbp_sh_colors(int64_t N, int32_t degree, int32_t K, const float *means, const float *coeffs,
@@ -831,7 +823,7 @@ int gwbp_sh_colors(int64_t N, int32_t degree, int32_t K, const float *means, con
     if (N < 0 || degree < 0 || degree > 3 || K < (degree + 1) * (degree + 1) || !campos_host ||
         (N > 0 && (!means || !coeffs || !out)))
         return set_error(GWBP_EINVAL, "bad sh_colors arguments (N=%lld degree=%d K=%d)", (long long)N, degree, K);
-    return launch_sh_colors(N, degree, K, means, coeffs, campos_host, out, static_cast<hipStream_t>(stream));
+    return launch_sh_colors(N, degree, K, means, coeffs, campos_host, out, as_stream(stream));
 }
 
 int gwbp_backproject_view(const gwbp_caps *caps, void *workspace, size_t workspace_bytes,
@@ -839,31 +831,26 @@ int gwbp_backproject_view(const gwbp_caps *caps, void *workspace, size_t workspa
                           const float *opacities, const float *feats, int64_t fs_y, int64_t fs_x, int64_t fs_c,
                           int32_t D, float scale_f, float scale_d, float *F, float *d, void *stream)
 {
-    Layout L;
-    Ws W;
-    ViewDev V;
-    int rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W);
+    Bound B;
+    int rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B);
     if (rc)
-        return rc;
-    if ((rc = make_view(view_host, caps, &V)))
         return rc;
     if ((rc = check_feats(feats, fs_y, fs_x, fs_c, D)))
         return rc;
-    if (!F && L.n > 0)
+    if (!F && B.L.n > 0)
         return set_error(GWBP_EINVAL, "null F");
-    if (L.n > 0 && (!means || !quats || !scales || !opacities))
+    if (B.L.n > 0 && (!means || !quats || !scales || !opacities))
         return set_error(GWBP_EINVAL, "null Gaussian parameter pointer");
     if (reinterpret_cast<uintptr_t>(quats) & 15)
         return set_error(GWBP_EINVAL, "quats must be 16-B aligned");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if ((rc = launch_project(L, W, V, means, quats, scales, opacities, nullptr, nullptr, nullptr, nullptr, s)))
+    if ((rc = launch_project(B.L, B.W, B.V, means, quats, scales, opacities, nullptr, nullptr, nullptr, nullptr, B.s)))
         return rc;
-    if ((rc = launch_bin_sort(L, W, V, nullptr, nullptr, nullptr, s)))
+    if ((rc = launch_bin_sort(B.L, B.W, B.V, nullptr, nullptr, nullptr, B.s)))
         return rc;
-    if ((rc = launch_blend(L, W, V, nullptr, nullptr, 0.f, s)))
+    if ((rc = launch_blend(B.L, B.W, B.V, nullptr, nullptr, 0.f, B.s)))
         return rc;
     const FeatMap M{feats, fs_y, fs_x, fs_c, nullptr, nullptr, nullptr, nullptr, 0, 0};
-    return launch_scatter(L, W, V, M, D, scale_f, scale_d, F, d, s);
+    return launch_scatter(B.L, B.W, B.V, M, D, scale_f, scale_d, F, d, B.s);
 }
 
 int gwbp_encode_map(const float *feats, int64_t fs_y, int64_t fs_x, int32_t height, int32_t width, int32_t K,
@@ -876,14 +863,14 @@ int gwbp_encode_map(const float *feats, int64_t fs_y, int64_t fs_x, int32_t heig
     if ((reinterpret_cast<uintptr_t>(feats) & 15) || (fs_y & 3) || (fs_x & 3))
         return set_error(GWBP_EINVAL, "encode_map needs channel-contiguous pixels at 16-B aligned addresses");
     return launch_encode_map(feats, fs_y, fs_x, height, width, K, encoder, n_out, out, workgroups < 0 ? 0 : workgroups,
-                             static_cast<hipStream_t>(stream));
+                             as_stream(stream));
 }
 
 int gwbp_finalize(int64_t N, int32_t D, const float *F, const float *d, float *out, void *stream)
 {
     if (N < 0 || D < 1 || (N > 0 && (!F || !d || !out)))
         return set_error(GWBP_EINVAL, "bad finalize arguments");
-    return launch_finalize(N, D, F, d, out, static_cast<hipStream_t>(stream));
+    return launch_finalize(N, D, F, d, out, as_stream(stream));
 }
 
 int gwbp_knn_search(int64_t N, int32_t M, int32_t D, int32_t k, const float *Q, int64_t ldq, const float *S, int64_t lds_,
@@ -901,7 +888,7 @@ int gwbp_knn_search(int64_t N, int32_t M, int32_t D, int32_t k, const float *Q, 
         return set_error(GWBP_EINVAL, "knn_search: null Q, S, idx or score");
     if ((reinterpret_cast<uintptr_t>(Q) & 3) || (reinterpret_cast<uintptr_t>(S) & 3))
         return set_error(GWBP_EINVAL, "knn_search: Q and S must be 4-B aligned");
-    return launch_knn_search(N, M, D, k, Q, ldq, S, lds_, idx, score, static_cast<hipStream_t>(stream));
+    return launch_knn_search(N, M, D, k, Q, ldq, S, lds_, idx, score, as_stream(stream));
 }
 
 int gwbp_knn_vote(int64_t N, int32_t M, int32_t k, const int32_t *idx, const int32_t *labels, int32_t num_classes,
@@ -917,7 +904,7 @@ int gwbp_knn_vote(int64_t N, int32_t M, int32_t k, const int32_t *idx, const int
         return set_error(GWBP_EINVAL, "knn_vote: ldc %lld < num_classes %d", (long long)ldc, (int)num_classes);
     if (!labels || (N > 0 && (!idx || !label_out)))
         return set_error(GWBP_EINVAL, "knn_vote: null idx, labels or label_out");
-    return launch_knn_vote(N, M, k, idx, labels, num_classes, label_out, counts, ldc, static_cast<hipStream_t>(stream));
+    return launch_knn_vote(N, M, k, idx, labels, num_classes, label_out, counts, ldc, as_stream(stream));
 }
 
 int gwbp_accumulate_stats(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, gwbp_stats *accum,
@@ -930,7 +917,7 @@ int gwbp_accumulate_stats(const gwbp_caps *caps, void *workspace, size_t workspa
         return rc;
     if (!accum)
         return set_error(GWBP_EINVAL, "null accum");
-    return launch_accum_stats(W, accum, static_cast<hipStream_t>(stream));
+    return launch_accum_stats(W, accum, as_stream(stream));
 }
 
 int gwbp_read_stats(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, gwbp_stats *stats_host,
@@ -943,7 +930,7 @@ int gwbp_read_stats(const gwbp_caps *caps, void *workspace, size_t workspace_byt
         return rc;
     if (!stats_host)
         return set_error(GWBP_EINVAL, "null stats_host");
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipStream_t s = as_stream(stream);
     if ((rc = check_hip(hipMemcpyAsync(stats_host, W.counters, sizeof(gwbp_stats), hipMemcpyDeviceToHost, s),
                         "stats copy")))
         return rc;
@@ -953,27 +940,22 @@ int gwbp_read_stats(const gwbp_caps *caps, void *workspace, size_t workspace_byt
 int gwbp_dump_pairs(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
                     int64_t cap, int32_t *gid, int32_t *pix, float *w, int64_t *n_host, void *stream)
 {
-    Layout L;
-    Ws W;
-    ViewDev V;
-    int rc = bind_workspace(caps, workspace, workspace_bytes, &L, &W);
+    Bound B;
+    int rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B);
     if (rc)
-        return rc;
-    if ((rc = make_view(view_host, caps, &V)))
         return rc;
     if (!n_host || cap < 0 || (cap > 0 && (!gid || !pix || !w)))
         return set_error(GWBP_EINVAL, "bad dump arguments");
-    hipStream_t s = static_cast<hipStream_t>(stream);
     // scratch counter: reuse digit_total[0..1] (free once the sort has finished)
-    u64 *n_dev = reinterpret_cast<u64 *>(W.digit_total);
-    if ((rc = check_hip(hipMemsetAsync(n_dev, 0, sizeof(u64), s), "dump memset")))
+    u64 *n_dev = reinterpret_cast<u64 *>(B.W.digit_total);
+    if ((rc = check_hip(hipMemsetAsync(n_dev, 0, sizeof(u64), B.s), "dump memset")))
         return rc;
-    if ((rc = launch_dump_pairs(L, W, V, cap, gid, pix, w, n_dev, s)))
+    if ((rc = launch_dump_pairs(B.L, B.W, B.V, cap, gid, pix, w, n_dev, B.s)))
         return rc;
     u64 n = 0;
-    if ((rc = check_hip(hipMemcpyAsync(&n, n_dev, sizeof(u64), hipMemcpyDeviceToHost, s), "dump copy")))
+    if ((rc = check_hip(hipMemcpyAsync(&n, n_dev, sizeof(u64), hipMemcpyDeviceToHost, B.s), "dump copy")))
         return rc;
-    if ((rc = check_hip(hipStreamSynchronize(s), "dump sync")))
+    if ((rc = check_hip(hipStreamSynchronize(B.s), "dump sync")))
         return rc;
     *n_host = (int64_t)n;
     return GWBP_OK;

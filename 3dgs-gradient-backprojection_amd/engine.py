@@ -5,8 +5,7 @@ Everything is enqueued on torch's current HIP stream of the tensors' device; not
 """
 from __future__ import annotations
 
-import ctypes
-import ctypes as C
+from ctypes import byref, c_float, c_int64, c_size_t, c_void_p
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -97,31 +96,28 @@ class Engine:
         self.stream, self._stream_handle = None, None
         self._alloc()
 
+    def _set_flag(self, bit: int, on: bool) -> None:
+        if on:
+            self.caps.flags |= bit
+        else:
+            self.caps.flags &= ~bit
+
     def set_front_priority(self, on: bool) -> None:
         """GWBP_FLAG_FRONT_PRIORITY for this engine's project / bin_sort / blend_weights launches: raised wave priority.
         Only useful when they run on a second stream beside a D % 256 == 0 scatter (ViewPipeline sets it)."""
-        if on:
-            self.caps.flags |= _lib.FLAG_FRONT_PRIORITY
-        else:
-            self.caps.flags &= ~_lib.FLAG_FRONT_PRIORITY
+        self._set_flag(_lib.FLAG_FRONT_PRIORITY, on)
 
     def set_split_encoder(self, on: bool) -> None:
         """GWBP_FLAG_SPLIT_ENCODER: blend_scatter_encoded as ONE persistent launch of encoder (producer) waves and blend (consumer)
         waves around an LDS ring of encoded tiles (the compressed variant on large images, see gwbp.h)."""
-        if on:
-            self.caps.flags |= _lib.FLAG_SPLIT_ENCODER
-        else:
-            self.caps.flags &= ~_lib.FLAG_SPLIT_ENCODER
+        self._set_flag(_lib.FLAG_SPLIT_ENCODER, on)
 
     def set_narrow_scatter(self, on: bool) -> None:
         """GWBP_FLAG_NARROW_SCATTER: the 128-channel scatter kernel even when D % 256 == 0 (short records, see gwbp.h).
         An Engine starts narrow (k_blend then skips the half-tile lists only the 256-channel kernel reads); whoever
         knows that a D % 256 == 0 scatter follows switches it off BEFORE blend_weights of that view (ViewPipeline,
         the drop-in operator)."""
-        if on:
-            self.caps.flags |= _lib.FLAG_NARROW_SCATTER
-        else:
-            self.caps.flags &= ~_lib.FLAG_NARROW_SCATTER
+        self._set_flag(_lib.FLAG_NARROW_SCATTER, on)
 
     def _alloc(self):
         # run-time flags survive a re-allocation (grow); a new engine starts narrow
@@ -129,12 +125,12 @@ class Engine:
                if hasattr(self, "caps") else _lib.FLAG_NARROW_SCATTER)
         base = _lib.FLAG_TIGHT_BINNING if self.tight_binning else 0
         self.caps = Caps(self.n, self.isect_cap, self.pair_cap, self.max_w, self.max_h, self.scatter_workgroups, base | run)
-        nbytes = C.c_size_t(0)
-        self._call("gwbp_workspace_size", C.byref(self.caps), C.byref(nbytes))
+        nbytes = c_size_t(0)
+        self._call("gwbp_workspace_size", byref(self.caps), byref(nbytes))
         self.ws_bytes = int(nbytes.value)
         self.ws = torch.empty(self.ws_bytes + 256, dtype=torch.uint8, device=self.device)
         off = (-self.ws.data_ptr()) % 256
-        self._ws_ptr = C.c_void_p(self.ws.data_ptr() + off)
+        self._ws_ptr = c_void_p(self.ws.data_ptr() + off)
 
     def grow(self, stats: Dict[str, int], views: int = 1):
         """Enlarge whichever capacity overflowed (bit0 = isect, bit1 = pairs) and reallocate.  The pair counter keeps
@@ -151,13 +147,13 @@ class Engine:
     def _stream(self):
         if self.stream is not None:  # bound by a driver that keeps this engine on one stream (no context switch per call)
             return self._stream_handle
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def bind_stream(self, stream: Optional[torch.cuda.Stream]):
         """Launch this engine's kernels on `stream` whatever torch's current stream is (None: follow the current stream).
         Methods that allocate outputs (want_alphas, render, ...) still allocate on the current stream."""
         self.stream = stream
-        self._stream_handle = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._stream_handle = c_void_p(stream.cuda_stream) if stream is not None else None
 
     def _call(self, name: str, *args):
         """One C-ABI call with this engine's device current: libgwbp launches on the CURRENT HIP device, while the
@@ -170,16 +166,23 @@ class Engine:
             check(fn(*args), name)
 
     def _args(self):
-        return C.byref(self.caps), self._ws_ptr, C.c_size_t(self.ws_bytes)
+        return byref(self.caps), self._ws_ptr, c_size_t(self.ws_bytes)
+
+    def _on_stream(self):
+        """Context in which torch allocates and computes on the stream this engine's kernels run on: the bound stream, or, with none
+        bound (torch.cuda.stream(None) changes nothing), torch's current one."""
+        return torch.cuda.stream(self.stream)
+
+    def _alphas(self, view, want: bool) -> Optional[torch.Tensor]:
+        """The [H, W] alpha map a blend writes when asked for it."""
+        return torch.empty(view.height, view.width, device=self.device) if want else None
 
     def _widen(self, feats: torch.Tensor) -> torch.Tensor:
         """A half map for a kernel that reads float32 only: feats.float() (exact), made on the stream the kernel runs on.
         What it costs is that of the copy: one read of the map, one write and one read of twice its size."""
         if feats.dtype not in HALF_TYPES:
             return feats
-        if self.stream is None:
-            return feats.float()
-        with torch.cuda.stream(self.stream):
+        with self._on_stream():
             return feats.float()
 
     def half_native(self, feats: torch.Tensor) -> bool:
@@ -221,11 +224,11 @@ class Engine:
             if mode == "antialiased":
                 out["compensations"] = torch.empty(self.n, device=self.device)
         if model == "pinhole" and mode == "classic":
-            self._call("gwbp_project", *self._args(), C.byref(view), ptr(means), ptr(quats), ptr(scales),
+            self._call("gwbp_project", *self._args(), byref(view), ptr(means), ptr(quats), ptr(scales),
                                         ptr(opacities), ptr(out.get("radii")), ptr(out.get("means2d")),
                                         ptr(out.get("depths")), ptr(out.get("conics")), self._stream())
             return out
-        self._call("gwbp_project_camera", *self._args(), C.byref(view), _lib.CAMERA_MODELS[model],
+        self._call("gwbp_project_camera", *self._args(), byref(view), _lib.CAMERA_MODELS[model],
                    _lib.RASTERIZE_MODES[mode], ptr(means), ptr(quats), ptr(scales), ptr(opacities), ptr(out.get("radii")),
                    ptr(out.get("means2d")), ptr(out.get("depths")), ptr(out.get("conics")), ptr(out.get("compensations")),
                    self._stream())
@@ -238,7 +241,7 @@ class Engine:
             out = dict(isect_ids=torch.empty(self.isect_cap, dtype=torch.int64, device=self.device),
                        flatten_ids=torch.empty(self.isect_cap, dtype=torch.int32, device=self.device),
                        tile_offsets=torch.empty(nt + 1, dtype=torch.int32, device=self.device))
-        self._call("gwbp_bin_sort", *self._args(), C.byref(view), ptr(out.get("isect_ids")),
+        self._call("gwbp_bin_sort", *self._args(), byref(view), ptr(out.get("isect_ids")),
                                      ptr(out.get("flatten_ids")), ptr(out.get("tile_offsets")), self._stream())
         return out
 
@@ -248,19 +251,16 @@ class Engine:
     def blend_weights(self, view, want_alphas=False, d=None, scale_d=1.0):
         """d (optional, float32[N]): also add this view's denominators d[g] += scale_d * sum_p w_g(p) from inside the blend
         (gwbp_blend_weights_d; needs the 256-channel scatter kernel enabled, like accumulate_d)."""
-        alphas = torch.empty(view.height, view.width, device=self.device) if want_alphas else None
+        alphas = self._alphas(view, want_alphas)
         self._tokens = None
         self._halves = self._wide_requested()  # k_blend<HALVES> writes the lists only without NARROW_SCATTER
         if d is not None:
-            if d.dtype != torch.float32 or not d.is_cuda or d.shape != (self.n,) or not d.is_contiguous():
-                raise GwbpError("d must be a contiguous float32 HIP tensor [N]")
-            if not self._halves:
-                raise GwbpError("blend_weights(d=...) needs the 256-channel scatter kernel enabled "
-                                "(set_narrow_scatter(False)): a narrow blend takes no weight sums")
-            self._call("gwbp_blend_weights_d", *self._args(), C.byref(view), ptr(alphas), C.c_float(scale_d), ptr(d),
+            self._check_denominator(d)
+            self._need_weight_sums("blend_weights", blend=True)
+            self._call("gwbp_blend_weights_d", *self._args(), byref(view), ptr(alphas), c_float(scale_d), ptr(d),
                        self._stream())
             return alphas
-        self._call("gwbp_blend_weights", *self._args(), C.byref(view), ptr(alphas), self._stream())
+        self._call("gwbp_blend_weights", *self._args(), byref(view), ptr(alphas), self._stream())
         return alphas
 
     # ---- per-pixel weight maps (masks, confidences): the _ex blends ---------------------------------------------------
@@ -290,19 +290,16 @@ class Engine:
         c(p) != 0 only, so every scatter of the view (scatter, scatter_labels, accumulate_d, ...) adds
         F[g] += scale_f sum_p w_g(p) c(p) f(p), d[g] += scale_d sum_p w_g(p) c(p).  The alpha map is the unweighted one."""
         pw = self.pixel_weights(pixel_weights, view)
-        alphas = torch.empty(view.height, view.width, device=self.device) if want_alphas else None
+        alphas = self._alphas(view, want_alphas)
         self._tokens = None
         self._halves = self._wide_requested()
         if d is not None:
-            if d.dtype != torch.float32 or not d.is_cuda or d.shape != (self.n,) or not d.is_contiguous():
-                raise GwbpError("d must be a contiguous float32 HIP tensor [N]")
-            if not self._halves:
-                raise GwbpError("blend_weighted(d=...) needs the 256-channel scatter kernel enabled "
-                                "(set_narrow_scatter(False)): a narrow blend takes no weight sums")
-            self._call("gwbp_blend_weights_d_ex", *self._args(), C.byref(view), ptr(alphas), C.c_float(scale_d), ptr(d),
-                       C.byref(pw), self._stream())
+            self._check_denominator(d)
+            self._need_weight_sums("blend_weighted", blend=True)
+            self._call("gwbp_blend_weights_d_ex", *self._args(), byref(view), ptr(alphas), c_float(scale_d), ptr(d),
+                       byref(pw), self._stream())
             return alphas
-        self._call("gwbp_blend_weights_ex", *self._args(), C.byref(view), ptr(alphas), C.byref(pw), self._stream())
+        self._call("gwbp_blend_weights_ex", *self._args(), byref(view), ptr(alphas), byref(pw), self._stream())
         return alphas
 
     def blend_tokens_weighted(self, view, lr_h: int, lr_w: int, pixel_weights: torch.Tensor, want_alphas=False):
@@ -312,10 +309,10 @@ class Engine:
             raise GwbpError(f"blend_tokens_weighted: a {lr_h}x{lr_w} map has texels narrower than a tile at "
                             f"{view.height}x{view.width}; use blend_weighted + scatter(upsample='nearest')")
         ymap, xmap = self.nearest_maps(lr_h, lr_w, view.height, view.width)
-        alphas = torch.empty(view.height, view.width, device=self.device) if want_alphas else None
+        alphas = self._alphas(view, want_alphas)
         self._halves = False
         self._tokens = (int(lr_h), int(lr_w))
-        self._call("gwbp_blend_tokens_ex", *self._args(), C.byref(view), ptr(ymap), ptr(xmap), ptr(alphas), C.byref(pw),
+        self._call("gwbp_blend_tokens_ex", *self._args(), byref(view), ptr(ymap), ptr(xmap), ptr(alphas), byref(pw),
                    self._stream())
         return alphas
 
@@ -328,10 +325,10 @@ class Engine:
         feats = self._widen(feats)
         sy, sx, _, D = self._feat_strides(feats, view)
         self._check_acc(F, d, D)
-        alphas = torch.empty(view.height, view.width, device=self.device) if want_alphas else None
+        alphas = self._alphas(view, want_alphas)
         self._halves, self._tokens = False, None
-        self._call("gwbp_blend_scatter_ex", *self._args(), C.byref(view), ptr(feats), sy, sx, D, C.c_float(scale_f),
-                   C.c_float(scale_d), ptr(F), ptr(d), ptr(alphas), C.byref(pw), self._stream())
+        self._call("gwbp_blend_scatter_ex", *self._args(), byref(view), ptr(feats), sy, sx, D, c_float(scale_f),
+                   c_float(scale_d), ptr(F), ptr(d), ptr(alphas), byref(pw), self._stream())
         return alphas
 
     def blend_scatter_encoded_weighted(self, view, feats, encoder, pixel_weights: torch.Tensor, F, d, scale_f=1.0, scale_d=1.0,
@@ -348,10 +345,10 @@ class Engine:
         K, n = encoder.shape
         self._check_acc(F, d, n)
         enc = encoder.contiguous()
-        alphas = torch.empty(view.height, view.width, device=self.device) if want_alphas else None
+        alphas = self._alphas(view, want_alphas)
         self._halves, self._tokens = False, None
-        self._call("gwbp_blend_scatter_encoded_ex", *self._args(), C.byref(view), ptr(feats), sy, sx, K, ptr(enc), n,
-                   C.c_float(scale_f), C.c_float(scale_d), ptr(F), ptr(d), ptr(alphas), C.byref(pw), self._stream())
+        self._call("gwbp_blend_scatter_encoded_ex", *self._args(), byref(view), ptr(feats), sy, sx, K, ptr(enc), n,
+                   c_float(scale_f), c_float(scale_d), ptr(F), ptr(d), ptr(alphas), byref(pw), self._stream())
         return alphas
 
     FUSED_MAX_DIM = 16         # gwbp_blend_scatter holds 4 pixels x 16 channels per lane in registers ...
@@ -384,10 +381,10 @@ class Engine:
         feats = self._widen(feats)
         sy, sx, _, D = self._feat_strides(feats, view)
         self._check_acc(F, d, D)
-        alphas = torch.empty(view.height, view.width, device=self.device) if want_alphas else None
+        alphas = self._alphas(view, want_alphas)
         self._halves, self._tokens = False, None  # the store is empty: no scatter kernel has anything to read
-        self._call("gwbp_blend_scatter", *self._args(), C.byref(view), ptr(feats), sy, sx, D, C.c_float(scale_f),
-                   C.c_float(scale_d), ptr(F), ptr(d), ptr(alphas), self._stream())
+        self._call("gwbp_blend_scatter", *self._args(), byref(view), ptr(feats), sy, sx, D, c_float(scale_f),
+                   c_float(scale_d), ptr(F), ptr(d), ptr(alphas), self._stream())
         return alphas
 
     @staticmethod
@@ -395,15 +392,13 @@ class Engine:
         """Shapes gwbp_blend_scatter_encoded takes: [H,W,K] float32 with channel-contiguous 16-B aligned pixels, K % 16 == 0,
         16 <= K <= 512, at most 16 outputs (the reference's encoder is 512 -> 16, backproject_compressed.py:26,127).  fp16 / bf16
         maps of that shape and layout too: blend_scatter_encoded widens them with .float()."""
-        if feats.dim() != 3 or encoder.dim() != 2 or feats.shape[2] != encoder.shape[0]:
+        if not Engine._encoder_layout(feats, encoder, 512):
             return False
-        sy, sx, sc = feats.stride()
         K, n = encoder.shape
+        sx = feats.stride(1)
         # (a row must span less than 4 GB: the kernel's per-lane column offsets are 32-bit -- a channel slice of a much wider
         # tensor falls back to encode_map, like any other layout the kernel does not take)
-        return (feats.is_cuda and feats.dtype in MAP_TYPES and encoder.dtype == torch.float32 and 1 <= n <= 16
-                and K % 16 == 0 and 16 <= K <= 512 and sc == 1 and sy % 4 == 0 and sx % 4 == 0 and sy >= 0 and sx >= K
-                and feats.data_ptr() % 16 == 0 and ((feats.shape[1] - 1) * sx + K) * 4 < (1 << 32))
+        return n >= 1 and K >= 16 and sx >= K and ((feats.shape[1] - 1) * sx + K) * 4 < (1 << 32)
 
     def blend_scatter_encoded(self, view, feats, encoder, F, d, scale_f=1.0, scale_d=1.0, want_alphas=False):
         """blend_scatter(view, feats @ encoder, ...) of the compressed variant (backproject_compressed.py:127-165) in ONE
@@ -421,10 +416,10 @@ class Engine:
         K, n = encoder.shape
         self._check_acc(F, d, n)
         enc = encoder.contiguous()
-        alphas = torch.empty(view.height, view.width, device=self.device) if want_alphas else None
+        alphas = self._alphas(view, want_alphas)
         self._halves, self._tokens = False, None  # the store is empty: no scatter kernel has anything to read
-        self._call("gwbp_blend_scatter_encoded", *self._args(), C.byref(view), ptr(feats), sy, sx, K, ptr(enc), n,
-                   C.c_float(scale_f), C.c_float(scale_d), ptr(F), ptr(d), ptr(alphas), self._stream())
+        self._call("gwbp_blend_scatter_encoded", *self._args(), byref(view), ptr(feats), sy, sx, K, ptr(enc), n,
+                   c_float(scale_f), c_float(scale_d), ptr(F), ptr(d), ptr(alphas), self._stream())
         return alphas
 
     @staticmethod
@@ -485,10 +480,10 @@ class Engine:
             raise GwbpError(f"blend_tokens: a {lr_h}x{lr_w} map has texels narrower than a tile at {view.height}x{view.width}; "
                             "use blend_weights + scatter(upsample='nearest')")
         ymap, xmap = self.nearest_maps(lr_h, lr_w, view.height, view.width)
-        alphas = torch.empty(view.height, view.width, device=self.device) if want_alphas else None
+        alphas = self._alphas(view, want_alphas)
         self._halves = False  # no weight store: only scatter_tokens can consume this view
         self._tokens = (int(lr_h), int(lr_w))
-        self._call("gwbp_blend_tokens", *self._args(), C.byref(view), ptr(ymap), ptr(xmap), ptr(alphas), self._stream())
+        self._call("gwbp_blend_tokens", *self._args(), byref(view), ptr(ymap), ptr(xmap), ptr(alphas), self._stream())
         return alphas
 
     def scatter_tokens(self, view, tokens, F, d, scale_f=1.0, scale_d=1.0):
@@ -507,21 +502,18 @@ class Engine:
         ymap, xmap = self.nearest_maps(tokens.shape[0], tokens.shape[1], view.height, view.width)
         sy, sx, _ = tokens.stride()
         if tokens.dtype in HALF_TYPES:
-            self._call("gwbp_scatter_tokens_typed", *self._args(), C.byref(view), ptr(tokens), MAP_TYPES[tokens.dtype],
-                       C.c_int64(sy), C.c_int64(sx), D, ptr(ymap), ptr(xmap), C.c_float(scale_f), C.c_float(scale_d), ptr(F),
+            self._call("gwbp_scatter_tokens_typed", *self._args(), byref(view), ptr(tokens), MAP_TYPES[tokens.dtype],
+                       c_int64(sy), c_int64(sx), D, ptr(ymap), ptr(xmap), c_float(scale_f), c_float(scale_d), ptr(F),
                        ptr(d), self._stream())
             return
-        self._call("gwbp_scatter_tokens", *self._args(), C.byref(view), ptr(tokens), C.c_int64(sy), C.c_int64(sx), D, ptr(ymap),
-                   ptr(xmap), C.c_float(scale_f), C.c_float(scale_d), ptr(F), ptr(d), self._stream())
+        self._call("gwbp_scatter_tokens", *self._args(), byref(view), ptr(tokens), c_int64(sy), c_int64(sx), D, ptr(ymap),
+                   ptr(xmap), c_float(scale_f), c_float(scale_d), ptr(F), ptr(d), self._stream())
 
     def accumulate_d(self, view, d, scale_d=1.0):
         """d += scale_d * sum_p w from the blend's per-record weight sums (needs a blend with the wide scatter enabled)."""
-        if d is None or d.dtype != torch.float32 or not d.is_cuda or d.shape != (self.n,) or not d.is_contiguous():
-            raise GwbpError("d must be a contiguous float32 HIP tensor [N]")
-        if not self._halves:
-            raise GwbpError("accumulate_d needs a view blended with the 256-channel scatter kernel enabled "
-                            "(set_narrow_scatter(False) BEFORE blend_weights): this view's headers hold no weight sums")
-        self._call("gwbp_accumulate_d", *self._args(), C.byref(view), C.c_float(scale_d), ptr(d), self._stream())
+        self._check_denominator(d)
+        self._need_weight_sums("accumulate_d")
+        self._call("gwbp_accumulate_d", *self._args(), byref(view), c_float(scale_d), ptr(d), self._stream())
 
     def has_weight_sums(self) -> bool:
         """The view in the workspace was blended with the 256-channel scatter kernel enabled: its records carry their weight
@@ -532,9 +524,7 @@ class Engine:
         """F[g, :] += value * sum_p w_g(p): the scatter of a map whose every entry is `value` (a 0-d float32 HIP tensor, read
         on the device), from the per-record weight sums -- the backward of `render.sum()`, which is what the reference's
         denominator pass asks for (backproject.py:145-147).  Needs has_weight_sums()."""
-        if not self._halves:
-            raise GwbpError("scatter_uniform needs a view blended with the 256-channel scatter kernel enabled "
-                            "(set_narrow_scatter(False) BEFORE blend_weights): this view's headers hold no weight sums")
+        self._need_weight_sums("scatter_uniform")
         if F.dtype != torch.float32 or not F.is_cuda or F.dim() != 2 or F.shape[0] != self.n:
             raise GwbpError(f"F must be a float32 HIP tensor [{self.n},D]")
         sums = torch.zeros(self.n, device=self.device, dtype=torch.float32)
@@ -575,8 +565,8 @@ class Engine:
         if upsample is None:
             sy, sx, sc, D = self._feat_strides(feats, view)
             self._check_acc(F, d, D)
-            self._call("gwbp_scatter", *self._args(), C.byref(view), ptr(feats), C.c_int64(sy), C.c_int64(sx),
-                                        C.c_int64(sc), D, C.c_float(scale_f), C.c_float(scale_d), ptr(F), ptr(d),
+            self._call("gwbp_scatter", *self._args(), byref(view), ptr(feats), c_int64(sy), c_int64(sx),
+                                        c_int64(sc), D, c_float(scale_f), c_float(scale_d), ptr(F), ptr(d),
                                         self._stream())
             return
         if upsample not in ("nearest", "bilinear"):
@@ -585,16 +575,16 @@ class Engine:
         self._check_acc(F, d, D)
         if upsample == "bilinear":
             y0, ly, x0, lx = self.bilinear_maps(feats.shape[0], feats.shape[1], view.height, view.width)
-            self._call("gwbp_scatter_bilinear", *self._args(), C.byref(view), ptr(feats), C.c_int64(sy),
-                                                 C.c_int64(sx), C.c_int64(sc), D, int(feats.shape[0]),
+            self._call("gwbp_scatter_bilinear", *self._args(), byref(view), ptr(feats), c_int64(sy),
+                                                 c_int64(sx), c_int64(sc), D, int(feats.shape[0]),
                                                  int(feats.shape[1]), ptr(y0), ptr(ly), ptr(x0), ptr(lx),
-                                                 C.c_float(scale_f), C.c_float(scale_d), ptr(F), ptr(d),
+                                                 c_float(scale_f), c_float(scale_d), ptr(F), ptr(d),
                                                  self._stream())
             return
         ymap, xmap = self.nearest_maps(feats.shape[0], feats.shape[1], view.height, view.width)
-        self._call("gwbp_scatter_upsampled", *self._args(), C.byref(view), ptr(feats), C.c_int64(sy), C.c_int64(sx),
-                                              C.c_int64(sc), D, ptr(ymap), ptr(xmap), C.c_float(scale_f),
-                                              C.c_float(scale_d), ptr(F), ptr(d), self._stream())
+        self._call("gwbp_scatter_upsampled", *self._args(), byref(view), ptr(feats), c_int64(sy), c_int64(sx),
+                                              c_int64(sc), D, ptr(ymap), ptr(xmap), c_float(scale_f),
+                                              c_float(scale_d), ptr(F), ptr(d), self._stream())
 
     def scatter_labels(self, view, labels, F, d, num_classes: int, scale_f=1.0, scale_d=1.0, upsample: Optional[str] = None):
         """F[g, k] += scale_f * sum_p w_g(p) [labels[p] == k], d[g] += scale_d * sum_p w_g(p) from the view's weight store: scatter()
@@ -606,48 +596,21 @@ class Engine:
         F: float32 [N, num_classes] with unit column stride (its row stride may be wider); d: float32 [N] or None."""
         if self._tokens is not None:
             raise GwbpError("this view was blended with blend_tokens (no weight store): blend_weights() first for scatter_labels()")
-        if not torch.is_tensor(labels) or not labels.is_cuda:
-            raise GwbpError("labels must be a HIP tensor (no CPU fallback exists for this path)")
-        if labels.dtype == torch.int64:
-            labels = narrow_labels(labels, num_classes)
-        if labels.dtype not in LABEL_TYPES:
-            raise GwbpError(f"labels must be an integer map (uint8, bool, int16, int32 or int64), got {labels.dtype}")
-        if labels.dtype == torch.bool:
-            labels = labels.view(torch.uint8)
-        if upsample not in (None, "nearest"):
-            raise GwbpError(f"upsample must be None or 'nearest' for a label map, got {upsample!r}")
-        if labels.dim() != 2 or (upsample is None and tuple(labels.shape) != (view.height, view.width)):
-            want = f"[H,W] = [{view.height},{view.width}]" if upsample is None else "[h,w]"
-            raise GwbpError(f"label map must be {want}, got {tuple(labels.shape)}")
-        if min(labels.stride()) < 0:
-            raise GwbpError("negative label-map strides are not supported")
-        K = int(num_classes)
-        if K < 1:
-            raise GwbpError(f"num_classes must be positive, got {K}")
-        if (F.dtype != torch.float32 or not F.is_cuda or F.dim() != 2 or tuple(F.shape) != (self.n, K)
-                or (K > 1 and F.stride(1) != 1) or F.stride(0) < K):
-            raise GwbpError(f"F must be a float32 HIP tensor [{self.n},{K}] with unit column stride")
-        if d is not None and (d.dtype != torch.float32 or not d.is_cuda or not d.is_contiguous() or tuple(d.shape) != (self.n,)):
-            raise GwbpError(f"d must be a contiguous float32 HIP tensor [{self.n}]")
-        ymap = xmap = None
-        if upsample == "nearest":
-            ymap, xmap = self.nearest_maps(labels.shape[0], labels.shape[1], view.height, view.width)
+        labels, ymap, xmap, K = self._class_args(view, labels, F, "F", d, "d", num_classes, upsample)
         sy, sx = labels.stride()
-        self._call("gwbp_scatter_labels", *self._args(), C.byref(view), ptr(labels), LABEL_TYPES[labels.dtype], C.c_int64(sy),
-                   C.c_int64(sx), K, ptr(ymap), ptr(xmap), C.c_float(scale_f), C.c_float(scale_d), ptr(F), C.c_int64(F.stride(0)),
+        self._call("gwbp_scatter_labels", *self._args(), byref(view), ptr(labels), LABEL_TYPES[labels.dtype], c_int64(sy),
+                   c_int64(sx), K, ptr(ymap), ptr(xmap), c_float(scale_f), c_float(scale_d), ptr(F), c_int64(F.stride(0)),
                    ptr(d), self._stream())
 
-    # ---- per-view votes of label maps (gwbp_vote_labels, gwbp_vote_projected) -----------------------------------------------
-    def _vote_args(self, view, labels, C, n, num_classes: int, upsample: Optional[str]):
-        """(label map as read, ymap, xmap, K) of the two votes, validated as scatter_labels validates its arguments.  The map may be
-        a narrowed copy: the caller holds it until its kernel is enqueued."""
+    def _label_map(self, view, labels, num_ids: int, upsample: Optional[str]):
+        """(label map as the kernels read it, ymap, xmap) of scatter_labels, the votes and scatter_mask_features: an [H, W] map --
+        with upsample="nearest" an [h, w] map and F.interpolate(mode="nearest")'s index maps -- of uint8 / int16 / int32 with
+        non-negative strides on the device; bool is read as its bytes, int64 narrowed to the ids in [0, num_ids) (narrow_labels).
+        The map may be a narrowed copy: the caller holds it until its kernel is enqueued."""
         if not torch.is_tensor(labels) or not labels.is_cuda:
             raise GwbpError("labels must be a HIP tensor (no CPU fallback exists for this path)")
-        K = int(num_classes)
-        if K < 1:
-            raise GwbpError(f"num_classes must be positive, got {K}")
         if labels.dtype == torch.int64:
-            labels = narrow_labels(labels, K)
+            labels = narrow_labels(labels, num_ids)
         if labels.dtype not in LABEL_TYPES:
             raise GwbpError(f"labels must be an integer map (uint8, bool, int16, int32 or int64), got {labels.dtype}")
         if labels.dtype == torch.bool:
@@ -659,16 +622,24 @@ class Engine:
             raise GwbpError(f"label map must be {want}, got {tuple(labels.shape)}")
         if min(labels.stride()) < 0:
             raise GwbpError("negative label-map strides are not supported")
-        if (not torch.is_tensor(C) or C.dtype != torch.float32 or not C.is_cuda or C.dim() != 2 or tuple(C.shape) != (self.n, K)
-                or (K > 1 and C.stride(1) != 1) or C.stride(0) < K):
-            raise GwbpError(f"C must be a float32 HIP tensor [{self.n},{K}] with unit column stride")
-        if n is not None and (n.dtype != torch.float32 or not n.is_cuda or not n.is_contiguous() or tuple(n.shape) != (self.n,)):
-            raise GwbpError(f"n must be a contiguous float32 HIP tensor [{self.n}]")
         ymap = xmap = None
         if upsample == "nearest":
             ymap, xmap = self.nearest_maps(labels.shape[0], labels.shape[1], view.height, view.width)
+        return labels, ymap, xmap
+
+    def _class_args(self, view, labels, acc, acc_name: str, den, den_name: str, num_classes: int, upsample: Optional[str]):
+        """(label map as read, ymap, xmap, K) of scatter_labels (acc = F, den = d) and of the two votes (C, n), validated alike; the
+        names go into the messages."""
+        K = int(num_classes)
+        if K < 1:
+            raise GwbpError(f"num_classes must be positive, got {K}")
+        labels, ymap, xmap = self._label_map(view, labels, K, upsample)
+        self._check_class_acc(acc, acc_name, K)
+        if den is not None:
+            self._check_denominator(den, den_name)
         return labels, ymap, xmap, K
 
+    # ---- per-view votes of label maps (gwbp_vote_labels, gwbp_vote_projected) -----------------------------------------------
     @staticmethod
     def vote_words(num_classes: int) -> int:
         """uint32 words per Gaussian of gwbp_vote_labels' bitset: bit 0 = "seen", label k = bit k + 1."""
@@ -679,8 +650,7 @@ class Engine:
         this engine's kernels run on, and kept all zero by the commit kernel after every call."""
         need = self.n * self.vote_words(num_classes)
         if getattr(self, "_seen", None) is None or self._seen.numel() < need:
-            st = self.stream if self.stream is not None else torch.cuda.current_stream(self.device)
-            with torch.cuda.stream(st):
+            with self._on_stream():
                 self._seen = torch.zeros(max(need, 1), dtype=torch.int32, device=self.device)
         return self._seen
 
@@ -692,12 +662,12 @@ class Engine:
         casts no vote)."""
         if self._tokens is not None:
             raise GwbpError("this view was blended with blend_tokens (no weight store): blend_weights() first for vote_labels()")
-        labels, ymap, xmap, K = self._vote_args(view, labels, C, n, num_classes, upsample)
+        labels, ymap, xmap, K = self._class_args(view, labels, C, "C", n, "n", num_classes, upsample)
         seen = self._vote_seen(K)
         sy, sx = labels.stride()
-        self._call("gwbp_vote_labels", *self._args(), ctypes.byref(view), ptr(labels), LABEL_TYPES[labels.dtype],
-                   ctypes.c_int64(sy), ctypes.c_int64(sx), ptr(ymap), ptr(xmap), K, ptr(seen), ptr(C),
-                   ctypes.c_int64(C.stride(0)), ptr(n), self._stream())
+        self._call("gwbp_vote_labels", *self._args(), byref(view), ptr(labels), LABEL_TYPES[labels.dtype],
+                   c_int64(sy), c_int64(sx), ptr(ymap), ptr(xmap), K, ptr(seen), ptr(C),
+                   c_int64(C.stride(0)), ptr(n), self._stream())
 
     def vote_projected(self, view, labels, C, n, num_classes: int, upsample: Optional[str] = None,
                        pixel_weights: Optional[torch.Tensor] = None):
@@ -705,11 +675,11 @@ class Engine:
         Gaussian with radius > 0 whose centre, rounded half to even, lies in the image adds 1 to C[g, label there] (if that label
         is in [0, num_classes)) and to n[g].  pixel_weights (optional, [H, W] at full resolution, as blend_weighted): a Gaussian
         whose pixel has a weight that is not > 0 casts no vote.  labels, upsample, C, n: as vote_labels."""
-        labels, ymap, xmap, K = self._vote_args(view, labels, C, n, num_classes, upsample)
-        pw = ctypes.byref(self.pixel_weights(pixel_weights, view)) if pixel_weights is not None else None
+        labels, ymap, xmap, K = self._class_args(view, labels, C, "C", n, "n", num_classes, upsample)
+        pw = byref(self.pixel_weights(pixel_weights, view)) if pixel_weights is not None else None
         sy, sx = labels.stride()
-        self._call("gwbp_vote_projected", *self._args(), ctypes.byref(view), ptr(labels), LABEL_TYPES[labels.dtype],
-                   ctypes.c_int64(sy), ctypes.c_int64(sx), ptr(ymap), ptr(xmap), pw, K, ptr(C), ctypes.c_int64(C.stride(0)),
+        self._call("gwbp_vote_projected", *self._args(), byref(view), ptr(labels), LABEL_TYPES[labels.dtype],
+                   c_int64(sy), c_int64(sx), ptr(ymap), ptr(xmap), pw, K, ptr(C), c_int64(C.stride(0)),
                    ptr(n), self._stream())
 
     @staticmethod
@@ -723,8 +693,7 @@ class Engine:
         this engine's kernels run on (one buffer serves every view of this engine: its views are scattered in stream order)."""
         need = self.isect_cap * _lib.MASK_SLOT_BYTES
         if getattr(self, "_mask_slots", None) is None or self._mask_slots.numel() < need:
-            ctx = torch.cuda.stream(self.stream) if self.stream is not None else torch.cuda.stream(torch.cuda.current_stream(self.device))
-            with ctx:
+            with self._on_stream():
                 self._mask_slots = torch.empty(need, dtype=torch.uint8, device=self.device)
                 if getattr(self, "mask_spilled", None) is None:
                     self.mask_spilled = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -752,23 +721,11 @@ class Engine:
         if table.shape[1] > 1 and table.stride(1) != 1:
             raise GwbpError("table must have unit channel stride")
         M, D = int(table.shape[0]), int(table.shape[1])
-        if labels.dtype == torch.int64:
-            labels = narrow_labels(labels, M)
-        if labels.dtype not in LABEL_TYPES:
-            raise GwbpError(f"labels must be an integer map (uint8, bool, int16, int32 or int64), got {labels.dtype}")
-        if labels.dtype == torch.bool:
-            labels = labels.view(torch.uint8)
-        if upsample not in (None, "nearest"):
-            raise GwbpError(f"upsample must be None or 'nearest' for a label map, got {upsample!r}")
-        if labels.dim() != 2 or (upsample is None and tuple(labels.shape) != (view.height, view.width)):
-            want = f"[H,W] = [{view.height},{view.width}]" if upsample is None else "[h,w]"
-            raise GwbpError(f"label map must be {want}, got {tuple(labels.shape)}")
-        if min(labels.stride()) < 0:
-            raise GwbpError("negative label-map strides are not supported")
+        labels, ymap, xmap = self._label_map(view, labels, M, upsample)
         if F.dtype != torch.float32 or not F.is_cuda or F.dim() != 2 or tuple(F.shape) != (self.n, D) or not F.is_contiguous():
             raise GwbpError(f"F must be a contiguous float32 HIP tensor [{self.n},{D}]")
-        if d is not None and (d.dtype != torch.float32 or not d.is_cuda or not d.is_contiguous() or tuple(d.shape) != (self.n,)):
-            raise GwbpError(f"d must be a contiguous float32 HIP tensor [{self.n}]")
+        if d is not None:
+            self._check_denominator(d)
         if not self.mask_fast_path(D) or F.data_ptr() % 16:
             # the map the fast path avoids: a zero row wherever a label is outside [0, M)
             idx = labels.to(torch.int64)
@@ -778,15 +735,12 @@ class Engine:
         align = 16 if table.dtype == torch.float32 else 8
         if table.stride(0) % 4 or table.data_ptr() % align:
             table = table.contiguous() if not table.is_contiguous() else table.clone()  # (a fresh allocation is 256-B aligned)
-        ymap = xmap = None
-        if upsample == "nearest":
-            ymap, xmap = self.nearest_maps(labels.shape[0], labels.shape[1], view.height, view.width)
         slots, spilled = self._mask_buffers()
         sy, sx = labels.stride()
-        self._call("gwbp_scatter_mask_features", *self._args(), C.byref(view), ptr(labels), LABEL_TYPES[labels.dtype],
-                   C.c_int64(sy), C.c_int64(sx), ptr(ymap), ptr(xmap), ptr(table), MAP_TYPES[table.dtype],
-                   C.c_int64(table.stride(0) if M > 1 else D), M, D, C.c_float(scale_f), C.c_float(scale_d), ptr(F), ptr(d),
-                   ptr(slots), C.c_size_t(slots.numel()), ptr(spilled), self._stream())
+        self._call("gwbp_scatter_mask_features", *self._args(), byref(view), ptr(labels), LABEL_TYPES[labels.dtype],
+                   c_int64(sy), c_int64(sx), ptr(ymap), ptr(xmap), ptr(table), MAP_TYPES[table.dtype],
+                   c_int64(table.stride(0) if M > 1 else D), M, D, c_float(scale_f), c_float(scale_d), ptr(F), ptr(d),
+                   ptr(slots), c_size_t(slots.numel()), ptr(spilled), self._stream())
 
     def _scatter_half(self, view, feats, F, d, scale_f, scale_d, upsample):
         """scatter() of a half map that half_native() admits: the typed entry points."""
@@ -794,8 +748,8 @@ class Engine:
             raise GwbpError(f"upsample must be None, 'nearest' or 'bilinear', got {upsample!r}")
         sy, sx, sc, D = self._feat_strides(feats, view, lowres=upsample is not None)
         self._check_acc(F, d, D)
-        head = (*self._args(), C.byref(view), ptr(feats), MAP_TYPES[feats.dtype], C.c_int64(sy), C.c_int64(sx), C.c_int64(sc), D)
-        tail = (C.c_float(scale_f), C.c_float(scale_d), ptr(F), ptr(d), self._stream())
+        head = (*self._args(), byref(view), ptr(feats), MAP_TYPES[feats.dtype], c_int64(sy), c_int64(sx), c_int64(sc), D)
+        tail = (c_float(scale_f), c_float(scale_d), ptr(F), ptr(d), self._stream())
         if upsample is None:
             self._call("gwbp_scatter_typed", *head, *tail)
         elif upsample == "bilinear":
@@ -807,16 +761,24 @@ class Engine:
             self._call("gwbp_scatter_upsampled_typed", *head, ptr(ymap), ptr(xmap), *tail)
 
     @staticmethod
-    def can_fuse_encoder(feats: torch.Tensor, encoder: torch.Tensor) -> bool:
-        """Shapes gwbp_scatter_encoded takes: [H,W,K] float32 with channel-contiguous 16-B aligned pixels, K % 16 == 0,
-        K <= 1024, at most 16 outputs.  (fp16 / bf16 maps of that shape and layout too: scatter_encoded widens them.)"""
+    def _encoder_layout(feats: torch.Tensor, encoder: torch.Tensor, max_k: int) -> bool:
+        """What the three encoder kernels (gwbp_encode_map, gwbp_scatter_encoded, gwbp_blend_scatter_encoded) ask alike of
+        feats [H,W,K] @ encoder [K,n]: a float32 / float16 / bfloat16 map on the device with channel-contiguous 16-B aligned pixels
+        (non-negative pixel strides that are multiples of 4 elements), a float32 encoder, K % 16 == 0, K <= max_k, n <= 16.  Each
+        can_* predicate adds what only its kernel asks."""
         if feats.dim() != 3 or encoder.dim() != 2 or feats.shape[2] != encoder.shape[0]:
             return False
         sy, sx, sc = feats.stride()
         K, n = encoder.shape
         return (feats.is_cuda and feats.dtype in MAP_TYPES and encoder.dtype == torch.float32 and n <= 16
-                and K % 16 == 0 and 16 <= K <= 1024 and sc == 1 and sy % 4 == 0 and sx % 4 == 0 and sy >= 0 and sx >= 0
+                and K % 16 == 0 and K <= max_k and sc == 1 and sy % 4 == 0 and sx % 4 == 0 and sy >= 0 and sx >= 0
                 and feats.data_ptr() % 16 == 0)
+
+    @staticmethod
+    def can_fuse_encoder(feats: torch.Tensor, encoder: torch.Tensor) -> bool:
+        """Shapes gwbp_scatter_encoded takes: [H,W,K] float32 with channel-contiguous 16-B aligned pixels, K % 16 == 0,
+        K <= 1024, at most 16 outputs.  (fp16 / bf16 maps of that shape and layout too: scatter_encoded widens them.)"""
+        return Engine._encoder_layout(feats, encoder, 1024) and encoder.shape[0] >= 16
 
     def scatter_encoded(self, view, feats, encoder, F, d, scale_f=1.0, scale_d=1.0):
         """scatter(view, feats @ encoder, ...) of the compressed variant (backproject_compressed.py:127-165) in ONE kernel:
@@ -831,8 +793,8 @@ class Engine:
         K, n = encoder.shape
         self._check_acc(F, d, n)
         enc = encoder.contiguous()
-        self._call("gwbp_scatter_encoded", *self._args(), C.byref(view), ptr(feats), sy, sx, K, ptr(enc), n,
-                   C.c_float(scale_f), C.c_float(scale_d), ptr(F), ptr(d), self._stream())
+        self._call("gwbp_scatter_encoded", *self._args(), byref(view), ptr(feats), sy, sx, K, ptr(enc), n,
+                   c_float(scale_f), c_float(scale_d), ptr(F), ptr(d), self._stream())
 
     def bilinear_maps(self, h: int, w: int, H: int, W: int):
         """device maps of F.interpolate(mode="bilinear", align_corners=False): (y0[H], ly[H], x0[W], lx[W]); cached."""
@@ -857,7 +819,7 @@ class Engine:
         colors = _req(colors, "colors")
         D = colors.shape[1]
         out = torch.empty(view.height, view.width, D, device=self.device)
-        self._call("gwbp_render", *self._args(), C.byref(view), ptr(colors), D, ptr(out), self._stream())
+        self._call("gwbp_render", *self._args(), byref(view), ptr(colors), D, ptr(out), self._stream())
         return out
 
     def render_pixels(self, view, colors, want_alphas=True):
@@ -865,8 +827,8 @@ class Engine:
         colors = _req(colors, "colors")
         D = colors.shape[1]
         out = torch.empty(view.height, view.width, D, device=self.device)
-        alphas = torch.empty(view.height, view.width, device=self.device) if want_alphas else None
-        self._call("gwbp_render_pixels", *self._args(), C.byref(view), ptr(colors), D, ptr(out), ptr(alphas),
+        alphas = self._alphas(view, want_alphas)
+        self._call("gwbp_render_pixels", *self._args(), byref(view), ptr(colors), D, ptr(out), ptr(alphas),
                                           self._stream())
         return out, alphas
 
@@ -877,8 +839,8 @@ class Engine:
         if coeffs.dim() != 3 or coeffs.shape[2] != 3 or coeffs.shape[0] != means.shape[0]:
             raise GwbpError(f"SH coefficients must be [N,K,3], got {tuple(coeffs.shape)}")
         out = torch.empty(means.shape[0], 3, device=self.device)
-        cp = (C.c_float * 3)(*[float(v) for v in campos])
-        self._call("gwbp_sh_colors", C.c_int64(means.shape[0]), int(degree), coeffs.shape[1], ptr(means), ptr(coeffs),
+        cp = (c_float * 3)(*[float(v) for v in campos])
+        self._call("gwbp_sh_colors", c_int64(means.shape[0]), int(degree), coeffs.shape[1], ptr(means), ptr(coeffs),
                                       cp, ptr(out), self._stream())
         return out
 
@@ -914,20 +876,17 @@ class Engine:
         colors = _req(colors, "colors", (3,))
         image = self._image(view, image)
         pw = self.pixel_weights(pixel_weights, view) if pixel_weights is not None else None
-        alphas = torch.empty(view.height, view.width, device=self.device) if want_alphas else None
+        alphas = self._alphas(view, want_alphas)
         self._tokens = None
         self._halves = self._wide_requested()
-        pwp = C.byref(pw) if pw is not None else None
+        pwp = byref(pw) if pw is not None else None
         if d is not None:
-            if d.dtype != torch.float32 or not d.is_cuda or d.shape != (self.n,) or not d.is_contiguous():
-                raise GwbpError("d must be a contiguous float32 HIP tensor [N]")
-            if not self._halves:
-                raise GwbpError("blend_weights_rgb(d=...) needs the 256-channel scatter kernel enabled "
-                                "(set_narrow_scatter(False)): a narrow blend takes no weight sums")
-            self._call("gwbp_blend_weights_d_rgb", *self._args(), C.byref(view), ptr(alphas), C.c_float(scale_d), ptr(d), pwp,
+            self._check_denominator(d)
+            self._need_weight_sums("blend_weights_rgb", blend=True)
+            self._call("gwbp_blend_weights_d_rgb", *self._args(), byref(view), ptr(alphas), c_float(scale_d), ptr(d), pwp,
                        ptr(colors), ptr(image), self._stream())
         else:
-            self._call("gwbp_blend_weights_rgb", *self._args(), C.byref(view), ptr(alphas), pwp, ptr(colors), ptr(image),
+            self._call("gwbp_blend_weights_rgb", *self._args(), byref(view), ptr(alphas), pwp, ptr(colors), ptr(image),
                        self._stream())
         return image, alphas
 
@@ -942,11 +901,11 @@ class Engine:
             raise GwbpError(f"blend_tokens_rgb: a {lr_h}x{lr_w} map has texels narrower than a tile at "
                             f"{view.height}x{view.width}; use blend_weights_rgb + scatter(upsample='nearest')")
         ymap, xmap = self.nearest_maps(lr_h, lr_w, view.height, view.width)
-        alphas = torch.empty(view.height, view.width, device=self.device) if want_alphas else None
+        alphas = self._alphas(view, want_alphas)
         self._halves = False
         self._tokens = (int(lr_h), int(lr_w))
-        self._call("gwbp_blend_tokens_rgb", *self._args(), C.byref(view), ptr(ymap), ptr(xmap), ptr(alphas),
-                   C.byref(pw) if pw is not None else None, ptr(colors), ptr(image), self._stream())
+        self._call("gwbp_blend_tokens_rgb", *self._args(), byref(view), ptr(ymap), ptr(xmap), ptr(alphas),
+                   byref(pw) if pw is not None else None, ptr(colors), ptr(image), self._stream())
         return image, alphas
 
     def render_rgb(self, view, colors, image: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -954,15 +913,37 @@ class Engine:
         schedules whose blend needs the feature map, which the network makes from this image."""
         colors = _req(colors, "colors", (3,))
         image = self._image(view, image)
-        self._call("gwbp_render_pixels", *self._args(), C.byref(view), ptr(colors), 3, ptr(image), None, self._stream())
+        self._call("gwbp_render_pixels", *self._args(), byref(view), ptr(colors), 3, ptr(image), None, self._stream())
         return image
 
     def _check_acc(self, F, d, D):
         if F.dtype != torch.float32 or not F.is_cuda or not F.is_contiguous() or tuple(F.shape) != (self.n, D):
             raise GwbpError(f"F must be a contiguous float32 HIP tensor [{self.n},{D}]")
-        if d is not None and (d.dtype != torch.float32 or not d.is_cuda or not d.is_contiguous()
-                              or tuple(d.shape) != (self.n,)):
-            raise GwbpError(f"d must be a contiguous float32 HIP tensor [{self.n}]")
+        if d is not None:
+            self._check_denominator(d)
+
+    def _check_denominator(self, t, name: str = "d") -> None:
+        """d of the scatters and blends, n of the votes: one float32 per Gaussian, contiguous, on the device."""
+        if (not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
+                or tuple(t.shape) != (self.n,)):
+            raise GwbpError(f"{name} must be a contiguous float32 HIP tensor [{self.n}]")
+
+    def _check_class_acc(self, t, name: str, K: int) -> None:
+        """F of scatter_labels, C of the votes: float32 [N, K] on the device whose rows may be wider than K."""
+        if (not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_cuda or t.dim() != 2 or tuple(t.shape) != (self.n, K)
+                or (K > 1 and t.stride(1) != 1) or t.stride(0) < K):
+            raise GwbpError(f"{name} must be a float32 HIP tensor [{self.n},{K}] with unit column stride")
+
+    def _need_weight_sums(self, what: str, blend: bool = False) -> None:
+        """`what` reads per-record weight sums, which only a blend with the 256-channel scatter kernel enabled leaves: the view in
+        the workspace must have been blended so, or (blend=True) the blend that `what` is about to issue must be."""
+        if self._halves:
+            return
+        if blend:
+            raise GwbpError(f"{what}(d=...) needs the 256-channel scatter kernel enabled "
+                            "(set_narrow_scatter(False)): a narrow blend takes no weight sums")
+        raise GwbpError(f"{what} needs a view blended with the 256-channel scatter kernel enabled "
+                        "(set_narrow_scatter(False) BEFORE blend_weights): this view's headers hold no weight sums")
 
     def backproject_view(self, view, means, quats, scales, opacities, feats, F, d, scale_f=1.0, scale_d=1.0):
         """Per-view body of create_feature_field_* (backproject.py:115-151), one fused call (pinhole / classic views only:
@@ -982,22 +963,16 @@ class Engine:
         means, quats = _req(means, "means", (3,)), _req(quats, "quats", (4,))
         scales, opacities = _req(scales, "scales", (3,)), _req(opacities, "opacities")
         self._halves, self._tokens = self._wide_requested(), None
-        self._call("gwbp_backproject_view", *self._args(), C.byref(view), ptr(means), ptr(quats), ptr(scales),
-                                             ptr(opacities), ptr(feats), C.c_int64(sy), C.c_int64(sx),
-                                             C.c_int64(sc), D, C.c_float(scale_f), C.c_float(scale_d), ptr(F),
+        self._call("gwbp_backproject_view", *self._args(), byref(view), ptr(means), ptr(quats), ptr(scales),
+                                             ptr(opacities), ptr(feats), c_int64(sy), c_int64(sx),
+                                             c_int64(sc), D, c_float(scale_f), c_float(scale_d), ptr(F),
                                              ptr(d), self._stream())
 
     @staticmethod
     def can_encode_map(feats: torch.Tensor, encoder: torch.Tensor) -> bool:
         """Shapes gwbp_encode_map takes: [H,W,K] float32 with channel-contiguous 16-B aligned pixels, K % 16 == 0, K <= 2048,
         at most 16 outputs (the reference's encoder is 512 -> 16, backproject_compressed.py:26,127)."""
-        if feats.dim() != 3 or encoder.dim() != 2 or feats.shape[2] != encoder.shape[0]:
-            return False
-        sy, sx, sc = feats.stride()
-        K, n = encoder.shape
-        return (feats.is_cuda and feats.dtype in MAP_TYPES and encoder.dtype == torch.float32 and n <= 16 and
-                K % 16 == 0 and K <= 2048 and sc == 1 and sy % 4 == 0 and sx % 4 == 0 and feats.data_ptr() % 16 == 0
-                and sy >= 0 and sx >= 0)
+        return Engine._encoder_layout(feats, encoder, 2048)
 
     def encode_map(self, feats: torch.Tensor, encoder: torch.Tensor, workgroups: int = 0,
                    stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
@@ -1024,7 +999,7 @@ class Engine:
         n = encoder.shape[1]
         sy, sx, _ = feats.stride()
         enc = encoder.contiguous()
-        handle = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
+        handle = self._stream() if stream is None else c_void_p(stream.cuda_stream)
         if stream is None:
             out = torch.empty(H, W, n, device=feats.device, dtype=torch.float32)
         else:
@@ -1035,7 +1010,7 @@ class Engine:
 
     def finalize(self, F, d, out=None):
         out = torch.empty_like(F) if out is None else out
-        self._call("gwbp_finalize", C.c_int64(F.shape[0]), F.shape[1], ptr(F), ptr(d), ptr(out), self._stream())
+        self._call("gwbp_finalize", c_int64(F.shape[0]), F.shape[1], ptr(F), ptr(d), ptr(out), self._stream())
         return out
 
     # ---- counters ----------------------------------------------------------------------------------------
@@ -1045,7 +1020,7 @@ class Engine:
 
     def stats(self) -> Dict[str, int]:
         st = Stats()
-        self._call("gwbp_read_stats", *self._args(), C.byref(st), self._stream())
+        self._call("gwbp_read_stats", *self._args(), byref(st), self._stream())
         return st.as_dict()
 
     @staticmethod
@@ -1059,8 +1034,8 @@ class Engine:
         gid = torch.empty(cap, dtype=torch.int32, device=self.device)
         pix = torch.empty(cap, dtype=torch.int32, device=self.device)
         w = torch.empty(cap, device=self.device)
-        n = C.c_int64(0)
-        self._call("gwbp_dump_pairs", *self._args(), C.byref(view), C.c_int64(cap), ptr(gid), ptr(pix), ptr(w),
-                                       C.byref(n), self._stream())
+        n = c_int64(0)
+        self._call("gwbp_dump_pairs", *self._args(), byref(view), c_int64(cap), ptr(gid), ptr(pix), ptr(w),
+                                       byref(n), self._stream())
         k = int(n.value)
         return gid[:k], pix[:k], w[:k]

@@ -102,6 +102,61 @@ def test_workspace_size_and_argument_validation():
     assert rc == -1 and b"32-bit" in lib.gwbp_last_error_string(), lib.gwbp_last_error_string()
 
 
+# Every entry point that takes (caps, workspace, workspace_bytes, view_host), with what its own arguments need to pass the
+# checks it runs BEFORE it binds the workspace: {argument index: value}; every other pointer is a fake aligned address (never
+# dereferenced: these calls return before any device call), every other integer 4, every float 1.  The typed scatters are
+# called as GWBP_MAP_F32 (the untyped function's call) and as GWBP_MAP_F16.
+_LABEL = {5: _lib.LABEL_I32}
+BOUND_CALLS = [(name, {}) for name, at in _lib.ARGTYPES.items() if at[:4] == _lib._WSV and not name.endswith("_typed")
+               and name not in ("gwbp_project_camera", "gwbp_scatter_labels", "gwbp_scatter_mask_features", "gwbp_vote_labels",
+                                "gwbp_vote_projected")]
+BOUND_CALLS += [(name, {5: mt}) for name in _lib.ARGTYPES if name.endswith("_typed") for mt in (_lib.MAP_F32, _lib.MAP_F16)]
+BOUND_CALLS += [("gwbp_project_camera", {4: 0, 5: 0}), ("gwbp_scatter_labels", _LABEL), ("gwbp_vote_labels", _LABEL),
+                ("gwbp_vote_projected", _LABEL),
+                ("gwbp_scatter_mask_features", {5: _lib.LABEL_I32, 11: _lib.MAP_F32, 20: _lib.MASK_SLOT_BYTES << 16})]
+
+
+def _bound_args(name, own, caps, ws, nbytes, view):
+    buf = (C.c_char * 512)()
+    fake = C.c_void_p((C.addressof(buf) + 255) & ~255)
+    args = [caps, fake if ws else None, nbytes, view]
+    for i, t in enumerate(_lib.ARGTYPES[name][4:], 4):
+        if i in own:
+            args.append(own[i])
+        elif t in (C.c_int64, C.c_int32, C.c_size_t):
+            args.append(4)
+        elif t is C.c_float:
+            args.append(1.0)
+        elif t is C.c_void_p:
+            args.append(fake)
+        elif t._type_ is C.c_int64:  # gwbp_dump_pairs' n_host
+            args.append(C.byref(C.c_int64(0)))
+        else:                        # const gwbp_pixel_weights *: no map
+            args.append(None)
+    return args
+
+
+@pytest.mark.parametrize("name, own", BOUND_CALLS, ids=[f"{n}-{o.get(5, '')}" for n, o in BOUND_CALLS])
+def test_caps_workspace_and_view_are_checked_in_that_order_before_any_device_call(name, own):
+    """Valid own arguments, then: NULL caps, a NULL workspace, a workspace that is too small, a NULL view and a view larger than
+    the caps.  Each is refused with its own code and message before the next is looked at."""
+    L = _lib.lib()
+    small = _lib.Caps(10, 1 << 16, 1 << 20, 64, 64)
+    nbytes = C.c_size_t(0)
+    assert L.gwbp_workspace_size(C.byref(small), C.byref(nbytes)) == 0
+    view, big = _lib.View(), _lib.View()
+    view.width, view.height, big.width, big.height = 64, 64, 65, 64
+    view.K[0] = view.K[4] = big.K[0] = big.K[4] = 50.0
+    f = getattr(L, name)
+    for caps, ws, n, v, rc, msg in ((None, True, nbytes, C.byref(view), -1, b"null caps"),
+                                    (C.byref(small), False, nbytes, C.byref(view), -1, b"null workspace"),
+                                    (C.byref(small), True, C.c_size_t(1024), C.byref(view), -2, b"workspace too small"),
+                                    (C.byref(small), True, nbytes, None, -1, b"null view"),
+                                    (C.byref(small), True, nbytes, C.byref(big), -1, b"view 65x64 outside caps 64x64")):
+        assert f(*_bound_args(name, own, caps, ws, n, v)) == rc, (msg, L.gwbp_last_error_string())
+        assert msg in L.gwbp_last_error_string(), (msg, L.gwbp_last_error_string())
+
+
 def test_product_path_fails_loudly_without_gpu():
     import torch
     if torch.cuda.is_available():

@@ -106,6 +106,33 @@ def test_unknown_map_type_is_einval_before_any_device_call(fn, code):
     assert b"unknown map type" in L.gwbp_last_error_string()
 
 
+# argument index -> the value that fails the function's one check of its index maps (NULL caps: refused before any device call)
+UPSAMPLED_BAD = [{10: None}, {11: None}]                                     # ymap, xmap
+BILINEAR_BAD = [{10: 0}, {11: 0}, {12: None}, {13: None}, {14: None}, {15: None}]  # lr_h, lr_w, y0, ly, x0, lx
+
+
+@pytest.mark.parametrize("fn, bad, msg", [("gwbp_scatter_upsampled_typed", b, "needs both index maps") for b in UPSAMPLED_BAD] +
+                         [("gwbp_scatter_bilinear_typed", b, "needs both index maps, both weight maps and the map size")
+                          for b in BILINEAR_BAD])
+@pytest.mark.parametrize("map_type", [_lib.MAP_F32, _lib.MAP_F16, _lib.MAP_BF16])
+def test_typed_index_map_checks_name_their_function(fn, bad, msg, map_type):
+    """A missing index or weight map is refused before the caps are looked at, in the name of the function that runs the check:
+    GWBP_MAP_F32 is the untyped function's call, so the message is that function's."""
+    L = _lib.lib()
+    buf = (C.c_char * 64)()
+    fake = C.c_void_p(C.addressof(buf))
+    args = [None, None, 0, None]
+    for i, t in enumerate(_lib.ARGTYPES[fn][4:], 4):
+        args.append(bad[i] if i in bad else map_type if i == 5 else 4 if t in (C.c_int64, C.c_int32) else 1.0 if t is C.c_float
+                    else fake)
+    assert getattr(L, fn)(*args) == -1
+    name = fn[:-len("_typed")] if map_type == _lib.MAP_F32 else fn
+    assert L.gwbp_last_error_string() == f"{name} {msg}".encode()
+    for i, v in bad.items():  # and with the argument mended the call reaches the caps
+        args[i] = 4 if v == 0 else fake
+    assert getattr(L, fn)(*args) == -1 and L.gwbp_last_error_string() == b"null caps"
+
+
 @pytest.mark.parametrize("opt", ["-O3", "-O2"])
 def test_half_wide_object_passes_the_assembly_gate(tmp_path, opt):
     """scatter_wide_half.hip: four k_scatter_wide instantiations (fp16, bf16 x full resolution, bilinear) under every check the
