@@ -7,6 +7,7 @@ JojiJoseph/3dgs-gradient-backprojection), hand-written HIP kernels behind a C AB
     from gsbp_amd import create_mask_feature_field  # mask maps + one embedding per mask -> feature field
     from gsbp_amd import create_vote_field          # per-view binary / projection / gradient votes -> 3-D masks
     from gsbp_amd import knn_search, transfer_labels  # few-shot labels on a finished field: exact inner-product k-NN + majority
+    from gsbp_amd import fit_pca, pca_colors, render_pca  # look at a finished field: PCA fit, colours and frames (visualize_pca.py)
 """
 from . import synthetic  # noqa: F401
 from ._lib import GwbpError, build, lib  # noqa: F401
@@ -15,4 +16,5 @@ from .engine import Engine, bilinear_index, narrow_labels, nearest_index  # noqa
 from . import scene_io  # noqa: F401
 from .rasterization import rasterization  # noqa: F401
 from .transfer import knn_search, transfer_labels, vote_labels  # noqa: F401
+from .pca import PCABasis, fit_pca, pca_colors, pca_transform, render_pca  # noqa: F401
 from .pruning import check_proper_pruning, gradient_mask, prune_by_gradients  # noqa: F401

@@ -185,6 +185,13 @@ ARGTYPES = {
     # N, M, D, k, Q, ldq, S, lds, idx, score, stream  /  N, M, k, idx, labels, num_classes, label_out, counts, ldc, stream
     "gwbp_knn_search": [_I64, _I32, _I32, _I32, _P, _I64, _P, _I64, _P, _P, _P],
     "gwbp_knn_vote": [_I64, _I32, _I32, _P, _P, _I32, _P, _P, _I64, _P],
+    # PCA: N, D, bytes*  /  N, D, X, ldx, mean, workspace, bytes, stream  /  N, D, X, ldx, mean, gram, workspace, bytes, stream  /
+    # N, D, k, X, ldx, mean, components, Y, minmax, stream  /  n, Y, lo_hi, colors, stream
+    "gwbp_pca_workspace_size": [_I64, _I32, C.POINTER(C.c_size_t)],
+    "gwbp_column_means": [_I64, _I32, _P, _I64, _P, _P, _SZ, _P],
+    "gwbp_centered_gram": [_I64, _I32, _P, _I64, _P, _P, _P, _SZ, _P],
+    "gwbp_pca_project": [_I64, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P],
+    "gwbp_pca_colors": [_I64, _P, _P, _P, _P],
 }
 # every symbol of include/gwbp.h: the two functions that return strings, then the int-returning ones declared above
 EXPORTS = ["gwbp_version", "gwbp_last_error_string", *ARGTYPES]

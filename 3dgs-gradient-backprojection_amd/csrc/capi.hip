@@ -907,6 +907,80 @@ int gwbp_knn_vote(int64_t N, int32_t M, int32_t k, const int32_t *idx, const int
     return launch_knn_vote(N, M, k, idx, labels, num_classes, label_out, counts, ldc, as_stream(stream));
 }
 
+// the checks the two passes of the fit share
+static int check_pca_rows(const char *what, int64_t N, int32_t D, const float *X, int64_t ldx, const void *workspace,
+                          size_t workspace_bytes)
+{
+    if (N < 2 || D < 1 || D > GWBP_PCA_MAX_D)
+        return set_error(GWBP_EINVAL, "%s: bad sizes (N=%lld D=%d): N >= 2, 1 <= D <= %d", what, (long long)N, (int)D,
+                         GWBP_PCA_MAX_D);
+    if (ldx < D)
+        return set_error(GWBP_EINVAL, "%s: row stride %lld below D = %d", what, (long long)ldx, (int)D);
+    if (!X || !workspace)
+        return set_error(GWBP_EINVAL, "%s: null X or workspace", what);
+    if ((reinterpret_cast<uintptr_t>(X) & 3) || (reinterpret_cast<uintptr_t>(workspace) & 7))
+        return set_error(GWBP_EINVAL, "%s: X must be 4-B aligned, the workspace 8-B", what);
+    const size_t need = pca_workspace_bytes(N, D);
+    if (workspace_bytes < need)
+        return set_error(GWBP_EWORKSPACE, "%s: workspace has %zu bytes, needs %zu", what, workspace_bytes, need);
+    return GWBP_OK;
+}
+
+int gwbp_pca_workspace_size(int64_t N, int32_t D, size_t *bytes)
+{
+    if (N < 2 || D < 1 || D > GWBP_PCA_MAX_D || !bytes)
+        return set_error(GWBP_EINVAL, "pca_workspace_size: bad arguments (N=%lld D=%d): N >= 2, 1 <= D <= %d", (long long)N, (int)D,
+                         GWBP_PCA_MAX_D);
+    *bytes = pca_workspace_bytes(N, D);
+    return GWBP_OK;
+}
+
+int gwbp_column_means(int64_t N, int32_t D, const float *X, int64_t ldx, float *mean_out, void *workspace, size_t workspace_bytes,
+                      void *stream)
+{
+    const int rc = check_pca_rows("column_means", N, D, X, ldx, workspace, workspace_bytes);
+    if (rc)
+        return rc;
+    if (!mean_out)
+        return set_error(GWBP_EINVAL, "column_means: null mean_out");
+    return launch_column_means(N, D, X, ldx, mean_out, workspace, as_stream(stream));
+}
+
+int gwbp_centered_gram(int64_t N, int32_t D, const float *X, int64_t ldx, const float *mean, double *gram_out, void *workspace,
+                       size_t workspace_bytes, void *stream)
+{
+    const int rc = check_pca_rows("centered_gram", N, D, X, ldx, workspace, workspace_bytes);
+    if (rc)
+        return rc;
+    if (!mean || !gram_out || (reinterpret_cast<uintptr_t>(gram_out) & 7))
+        return set_error(GWBP_EINVAL, "centered_gram: null mean or gram_out, or gram_out not 8-B aligned");
+    return launch_centered_gram(N, D, X, ldx, mean, gram_out, workspace, as_stream(stream));
+}
+
+int gwbp_pca_project(int64_t N, int32_t D, int32_t k, const float *X, int64_t ldx, const float *mean, const float *components,
+                     float *Y, float *minmax_partials, void *stream)
+{
+    if (N < 1 || D < 1 || D > GWBP_PCA_MAX_D)
+        return set_error(GWBP_EINVAL, "pca_project: bad sizes (N=%lld D=%d): N >= 1, 1 <= D <= %d", (long long)N, (int)D,
+                         GWBP_PCA_MAX_D);
+    if (k < 1 || k > GWBP_PCA_MAX_K)
+        return set_error(GWBP_EINVAL, "pca_project: k must be in [1, %d] (got %d)", GWBP_PCA_MAX_K, (int)k);
+    if (ldx < D)
+        return set_error(GWBP_EINVAL, "pca_project: row stride %lld below D = %d", (long long)ldx, (int)D);
+    if (!X || !mean || !components || !Y || !minmax_partials)
+        return set_error(GWBP_EINVAL, "pca_project: null X, mean, components, Y or minmax_partials");
+    if (reinterpret_cast<uintptr_t>(X) & 3)
+        return set_error(GWBP_EINVAL, "pca_project: X must be 4-B aligned");
+    return launch_pca_project(N, D, k, X, ldx, mean, components, Y, minmax_partials, as_stream(stream));
+}
+
+int gwbp_pca_colors(int64_t n, const float *Y, const float *lo_hi, float *colors, void *stream)
+{
+    if (n < 0 || !lo_hi || (n > 0 && (!Y || !colors)))
+        return set_error(GWBP_EINVAL, "pca_colors: bad arguments");
+    return launch_pca_colors(n, Y, lo_hi, colors, as_stream(stream));
+}
+
 int gwbp_accumulate_stats(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, gwbp_stats *accum,
                           void *stream)
 {

@@ -264,6 +264,14 @@ int launch_knn_search(int64_t N, int M, int D, int k, const float *Q, int64_t ld
                       float *score, hipStream_t s);
 int launch_knn_vote(int64_t N, int M, int k, const int32_t *idx, const int32_t *labels, int num_classes, int32_t *label_out,
                     int32_t *counts, int64_t ldc, hipStream_t s);
+// PCA of a finished field (pca.hip): column means, centred Gram, projection onto k <= 16 components, colours.  ws: the caller's
+// pca_workspace_bytes(N, D) bytes (the slices' partial sums), free again when the call's kernels have run.
+size_t pca_workspace_bytes(int64_t N, int D);
+int launch_column_means(int64_t N, int D, const float *X, int64_t ldx, float *mean, void *ws, hipStream_t s);
+int launch_centered_gram(int64_t N, int D, const float *X, int64_t ldx, const float *mean, double *gram, void *ws, hipStream_t s);
+int launch_pca_project(int64_t N, int D, int k, const float *X, int64_t ldx, const float *mean, const float *V, float *Y,
+                       float *minmax, hipStream_t s);
+int launch_pca_colors(int64_t n, const float *Y, const float *lo_hi, float *colors, hipStream_t s);
 int launch_dump_pairs(const Layout &L, const Ws &W, const ViewDev &V, int64_t cap, int32_t *gid, int32_t *pix,
                       float *w, u64 *n_dev, hipStream_t s);
 int launch_accum_stats(const Ws &W, gwbp_stats *accum, hipStream_t s);
@@ -380,6 +388,26 @@ struct MapElem<GWBP_MAP_BF16> {
                            __uint_as_float(x.y & 0xFFFF0000u));
     }
 };
+
+// Four consecutive floats of row `p` (nullptr: a row beyond the matrix) at column c, zero beyond D.  VEC: rows are 16-B aligned.
+template <bool VEC>
+__device__ __forceinline__ float4 load4(const float *__restrict__ p, int c, int D)
+{
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!p)
+        return v;
+    if (VEC && c + 4 <= D)
+        return *reinterpret_cast<const float4 *>(p + c);
+    if (c < D)
+        v.x = p[c];
+    if (c + 1 < D)
+        v.y = p[c + 1];
+    if (c + 2 < D)
+        v.z = p[c + 2];
+    if (c + 3 < D)
+        v.w = p[c + 3];
+    return v;
+}
 
 __device__ __forceinline__ u32 uniform(u32 v) { return (u32)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ __forceinline__ u64 uniform64(u64 v)

@@ -53,26 +53,6 @@ __device__ __forceinline__ float key_score(u32 key)
     return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
 }
 
-// Four consecutive floats of row `p` (nullptr: a row beyond the matrix) at column c, zero beyond D.  VEC: rows are 16-B aligned.
-template <bool VEC>
-__device__ __forceinline__ float4 load4(const float *__restrict__ p, int c, int D)
-{
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (!p)
-        return v;
-    if (VEC && c + 4 <= D)
-        return *reinterpret_cast<const float4 *>(p + c);
-    if (c < D)
-        v.x = p[c];
-    if (c + 1 < D)
-        v.y = p[c + 1];
-    if (c + 2 < D)
-        v.z = p[c + 2];
-    if (c + 3 < D)
-        v.w = p[c + 3];
-    return v;
-}
-
 template <bool VEC>
 __global__ __launch_bounds__(kKnnThreads) void k_knn_search(int64_t N, int M, int D, int k, const float *__restrict__ Q,
                                                             int64_t ldq, const float *__restrict__ S, int64_t lds_,

@@ -490,6 +490,47 @@ GWBP_API int gwbp_knn_search(int64_t N, int32_t M, int32_t D, int32_t k, const f
 GWBP_API int gwbp_knn_vote(int64_t N, int32_t M, int32_t k, const int32_t *idx, const int32_t *labels, int32_t num_classes,
                            int32_t *label_out, int32_t *counts, int64_t ldc, void *stream);
 
+/* ---- PCA of a finished field (the reference's visualize_pca.py: sklearn PCA(3) on the host copy of the [N, D] field) -------------
+ * The [N, D] passes of the fit and of the transform; the D x D eigen-decomposition between them is the caller's (float64 eigh of
+ * gram / (N - 1); sklearn's covariance_eigh solver does the same).  X[g * ldx + 0..D-1], g < N, is read in place, fp32, any row
+ * stride ldx >= D (in floats); rows whose addresses and stride are 16-B aligned are read with 16-B loads, others element by element,
+ * with bit-equal results.  No [N, D] intermediate is made: x - mean is one fp32 subtraction on the way into LDS.  No atomics: every
+ * output is bit-reproducible run to run.  2 <= N, 1 <= D <= GWBP_PCA_MAX_D.
+ * GWBP_EINVAL before any HIP call: sizes out of range, a stride below D, a null or (X: 4-B, gram / workspace: 8-B) misaligned
+ * pointer; GWBP_EWORKSPACE: a workspace below gwbp_pca_workspace_size. */
+#define GWBP_PCA_MAX_D 2048
+#define GWBP_PCA_MAX_K 16
+#define GWBP_PCA_PROJECT_ROWS 128 /* rows of X per workgroup of gwbp_pca_project = per (min, max) pair of its partials */
+
+/* Bytes of device workspace gwbp_column_means and gwbp_centered_gram need for an [N, D] field: the per-slice partial sums,
+ * max(mean slices x D x 8, Gram slices x D x D x 4); the Gram's slices are min(512 / tiles, N / 32) with tiles = the 128 x 128
+ * tiles of the upper triangle, so the figure never exceeds 64 MiB and never grows with N.  The workspace carries nothing between
+ * calls. */
+GWBP_API int gwbp_pca_workspace_size(int64_t N, int32_t D, size_t *bytes);
+
+/* mean_out[c] = (1 / N) sum_g X[g, c]: float64 column sums per fixed row slice (ascending rows), the slices added in ascending
+ * order in float64, one rounding to fp32. */
+GWBP_API int gwbp_column_means(int64_t N, int32_t D, const float *X, int64_t ldx, float *mean_out, void *workspace,
+                               size_t workspace_bytes, void *stream);
+
+/* gram_out[a * D + b] (float64, dense [D, D], symmetric) = sum_g (X[g, a] - mean[a]) (X[g, b] - mean[b]).  The rows are cut into
+ * slices that depend on (N, D) alone; within a slice every entry of the upper triangle is one chain of fp32 fused multiply-adds
+ * over the rows (the fp32 matrix cores; no reduced-precision operand); the slices are added in ascending order in float64 and
+ * the lower triangle is the mirror image.  A non-finite X entry makes the entries of its column non-finite. */
+GWBP_API int gwbp_centered_gram(int64_t N, int32_t D, const float *X, int64_t ldx, const float *mean, double *gram_out,
+                                void *workspace, size_t workspace_bytes, void *stream);
+
+/* Y[g * k + j] = sum_c (X[g, c] - mean[c]) components[j * D + c], j < k <= GWBP_PCA_MAX_K: one pass over X, one chain of fp32
+ * fused multiply-adds per entry in an order that depends only on D.  minmax_partials[2 * w], [2 * w + 1], w < ceil(N /
+ * GWBP_PCA_PROJECT_ROWS): the smallest and the largest Y entry of rows w * GWBP_PCA_PROJECT_ROWS ...; min and max are exact, so
+ * the smallest / largest of them is Y's (NaN entries are skipped).  N >= 1 here. */
+GWBP_API int gwbp_pca_project(int64_t N, int32_t D, int32_t k, const float *X, int64_t ldx, const float *mean,
+                              const float *components, float *Y, float *minmax_partials, void *stream);
+
+/* colors[e] = (Y[e] - lo) / (hi - lo), e < n, with lo = lo_hi[0], hi = lo_hi[1] read from DEVICE memory (one pair for every
+ * channel: visualize_pca.py takes np.min / np.max over all three); hi == lo gives 0.5 everywhere.  colors may alias Y. */
+GWBP_API int gwbp_pca_colors(int64_t n, const float *Y, const float *lo_hi, float *colors, void *stream);
+
 /* Adds this view's counters into `accum` (device, gwbp_stats) -- used by bench/driver to total pairs. */
 GWBP_API int gwbp_accumulate_stats(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, gwbp_stats *accum,
                           void *stream);
