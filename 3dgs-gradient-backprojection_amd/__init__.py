@@ -8,6 +8,7 @@ JojiJoseph/3dgs-gradient-backprojection), hand-written HIP kernels behind a C AB
     from gsbp_amd import create_vote_field          # per-view binary / projection / gradient votes -> 3-D masks
     from gsbp_amd import knn_search, transfer_labels  # few-shot labels on a finished field: exact inner-product k-NN + majority
     from gsbp_amd import fit_pca, pca_colors, render_pca  # look at a finished field: PCA fit, colours and frames (visualize_pca.py)
+    from gsbp_amd import prompt_mask, probe_pixels, render_prompt_mask, ClickSession  # ask a finished field: prompts and clicks
 """
 from . import synthetic  # noqa: F401
 from ._lib import GwbpError, build, lib  # noqa: F401
@@ -17,4 +18,5 @@ from . import scene_io  # noqa: F401
 from .rasterization import rasterization  # noqa: F401
 from .transfer import knn_search, transfer_labels, vote_labels  # noqa: F401
 from .pca import PCABasis, fit_pca, pca_colors, pca_transform, render_pca  # noqa: F401
+from .segment import ClickSession, apply_mask3d, probe_pixels, prompt_mask, prompt_scores, render_prompt_mask  # noqa: F401
 from .pruning import check_proper_pruning, gradient_mask, prune_by_gradients  # noqa: F401

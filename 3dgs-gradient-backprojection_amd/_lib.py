@@ -192,6 +192,10 @@ ARGTYPES = {
     "gwbp_centered_gram": [_I64, _I32, _P, _I64, _P, _P, _P, _SZ, _P],
     "gwbp_pca_project": [_I64, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P],
     "gwbp_pca_colors": [_I64, _P, _P, _P, _P],
+    # queries: N, D, P, n_pos, X, ldx, prompts, normalize, threshold*, mask, scores, stream  /
+    # M, xy, X, ldx, D, out, depth, alpha, stream
+    "gwbp_prompt_scores": [_I64, _I32, _I32, _I32, _P, _I64, _P, _I32, C.POINTER(C.c_float), _P, _P, _P],
+    "gwbp_probe_pixels": _WSV + [_I32, _P, _P, _I64, _I32, _P, _P, _P, _P],
 }
 # every symbol of include/gwbp.h: the two functions that return strings, then the int-returning ones declared above
 EXPORTS = ["gwbp_version", "gwbp_last_error_string", *ARGTYPES]

@@ -981,6 +981,63 @@ int gwbp_pca_colors(int64_t n, const float *Y, const float *lo_hi, float *colors
     return launch_pca_colors(n, Y, lo_hi, colors, as_stream(stream));
 }
 
+// The field as the two queries read it: D, the row stride and the pointer, checked once for both.
+static int check_field_rows(const char *what, int32_t D, const float *X, int64_t ldx)
+{
+    if (D < 1 || D > GWBP_PCA_MAX_D)
+        return set_error(GWBP_EINVAL, "%s: D must be in [1, %d] (got %d)", what, GWBP_PCA_MAX_D, (int)D);
+    if (ldx < D)
+        return set_error(GWBP_EINVAL, "%s: row stride %lld below D = %d", what, (long long)ldx, (int)D);
+    if (!X)
+        return set_error(GWBP_EINVAL, "%s: null X", what);
+    if (reinterpret_cast<uintptr_t>(X) & 3)
+        return set_error(GWBP_EINVAL, "%s: X must be 4-B aligned", what);
+    return GWBP_OK;
+}
+
+int gwbp_prompt_scores(int64_t N, int32_t D, int32_t P, int32_t n_pos, const float *X, int64_t ldx, const float *prompts,
+                       int32_t normalize, const float *threshold_host, uint8_t *mask, float *scores, void *stream)
+{
+    if (N < 0)
+        return set_error(GWBP_EINVAL, "prompt_scores: N must not be negative (got %lld)", (long long)N);
+    if (P < 1 || P > GWBP_QUERY_MAX_P)
+        return set_error(GWBP_EINVAL, "prompt_scores: P must be in [1, %d] (got %d)", GWBP_QUERY_MAX_P, (int)P);
+    if (n_pos < 1 || n_pos > P)
+        return set_error(GWBP_EINVAL, "prompt_scores: n_pos must be in [1, P = %d] (got %d)", (int)P, (int)n_pos);
+    const int rc = check_field_rows("prompt_scores", D, X, ldx);
+    if (rc)
+        return rc;
+    if (!prompts || (reinterpret_cast<uintptr_t>(prompts) & 3))
+        return set_error(GWBP_EINVAL, "prompt_scores: prompts must be a non-null, 4-B aligned [P, D] array");
+    if (!mask && !scores)
+        return set_error(GWBP_EINVAL, "prompt_scores: mask and scores are both null");
+    if (reinterpret_cast<uintptr_t>(scores) & 3)
+        return set_error(GWBP_EINVAL, "prompt_scores: scores must be 4-B aligned");
+    if (mask && n_pos == P && !threshold_host)
+        return set_error(GWBP_EINVAL, "prompt_scores: a mask without negative prompts (n_pos == P) needs a threshold");
+    return launch_prompt_scores(N, D, P, n_pos, X, ldx, prompts, normalize != 0, threshold_host, mask, scores, as_stream(stream));
+}
+
+int gwbp_probe_pixels(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host, int32_t M,
+                      const int32_t *xy, const float *X, int64_t ldx, int32_t D, float *out, float *depth, float *alpha,
+                      void *stream)
+{
+    // the probe's own arguments first: nothing of the caps, the workspace or the view is looked at before they pass
+    if (M < 1 || M > GWBP_PROBE_MAX_PIXELS)
+        return set_error(GWBP_EINVAL, "probe_pixels: M must be in [1, %d] (got %d)", GWBP_PROBE_MAX_PIXELS, (int)M);
+    int rc = check_field_rows("probe_pixels", D, X, ldx);
+    if (rc)
+        return rc;
+    if (!xy || !out || (reinterpret_cast<uintptr_t>(xy) & 3) || (reinterpret_cast<uintptr_t>(out) & 3))
+        return set_error(GWBP_EINVAL, "probe_pixels: xy and out must be non-null and 4-B aligned");
+    if ((reinterpret_cast<uintptr_t>(depth) & 3) || (reinterpret_cast<uintptr_t>(alpha) & 3))
+        return set_error(GWBP_EINVAL, "probe_pixels: depth and alpha must be 4-B aligned");
+    Bound B;
+    if ((rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B)))
+        return rc;
+    return launch_probe_pixels(B.W, B.V, M, xy, X, ldx, D, out, depth, alpha, B.s);
+}
+
 int gwbp_accumulate_stats(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, gwbp_stats *accum,
                           void *stream)
 {

@@ -272,6 +272,12 @@ int launch_centered_gram(int64_t N, int D, const float *X, int64_t ldx, const fl
 int launch_pca_project(int64_t N, int D, int k, const float *X, int64_t ldx, const float *mean, const float *V, float *Y,
                        float *minmax, hipStream_t s);
 int launch_pca_colors(int64_t n, const float *Y, const float *lo_hi, float *colors, hipStream_t s);
+// questions asked of a finished field (query.hip): prompt scores + 3-D mask in one pass over X; the field rendered at M pixels
+// of a projected and sorted view.  threshold: host pointer or nullptr.
+int launch_prompt_scores(int64_t N, int D, int P, int n_pos, const float *X, int64_t ldx, const float *prompts, int normalize,
+                         const float *threshold, uint8_t *mask, float *scores, hipStream_t s);
+int launch_probe_pixels(const Ws &W, const ViewDev &V, int M, const int32_t *xy, const float *X, int64_t ldx, int D, float *out,
+                        float *depth, float *alpha, hipStream_t s);
 int launch_dump_pairs(const Layout &L, const Ws &W, const ViewDev &V, int64_t cap, int32_t *gid, int32_t *pix,
                       float *w, u64 *n_dev, hipStream_t s);
 int launch_accum_stats(const Ws &W, gwbp_stats *accum, hipStream_t s);

@@ -832,6 +832,29 @@ class Engine:
                                           self._stream())
         return out, alphas
 
+    def probe_pixels(self, view, xy, table, want_depth=True, want_alpha=True):
+        """The render of `table` [N, D] (any row stride >= D, read in place) at the pixels xy [M, 2] (int32, (x, y)) only:
+        (out [M, D], depth [M] or None, alpha [M] or None); needs project + bin_sort of `view` (not the weight store).  depth
+        accumulates the PROJECTION's camera depths; rasterization()'s "+D" channel computes its depths in torch -- render that
+        column as a one-channel table to get its bits."""
+        if not torch.is_tensor(table) or not table.is_cuda or table.dtype != torch.float32 or table.dim() != 2:
+            raise GwbpError("the probed table must be a float32 [N, D] HIP tensor")
+        if table.shape[0] != self.n:
+            raise GwbpError(f"engine was sized for {self.n} Gaussians, the table has {table.shape[0]} rows")
+        if (table.shape[1] > 1 and table.stride(1) != 1) or (self.n > 1 and table.stride(0) < table.shape[1]):
+            table = table.contiguous()
+        if xy.dtype != torch.int32 or xy.dim() != 2 or xy.shape[1] != 2 or not xy.is_cuda:
+            raise GwbpError("xy must be an int32 [M, 2] HIP tensor of (x, y) pixels")
+        xy = xy.contiguous()
+        M, D = xy.shape[0], table.shape[1]
+        ld = int(table.stride(0)) if self.n > 1 else D
+        out = torch.empty(M, D, device=self.device)
+        depth = torch.empty(M, device=self.device) if want_depth else None
+        alpha = torch.empty(M, device=self.device) if want_alpha else None
+        self._call("gwbp_probe_pixels", *self._args(), byref(view), M, ptr(xy), ptr(table), c_int64(ld), D, ptr(out), ptr(depth),
+                   ptr(alpha), self._stream())
+        return out, depth, alpha
+
     def sh_colors(self, degree: int, means, coeffs, campos):
         """[N,K,3] SH coefficients -> [N,3] view-dependent colours (+0.5, clamped at 0) on the device."""
         means = _req(means, "means", (3,))

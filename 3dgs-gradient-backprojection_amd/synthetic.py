@@ -243,6 +243,21 @@ def make_encoder(cfg: Config, seed: int = ENCODER_SEED) -> torch.Tensor:
     return torch.randn(cfg.feat_dim, cfg.encoder_dim, generator=g) / math.sqrt(cfg.feat_dim)
 
 
+PROMPT_SEED = 31
+
+
+def make_prompts(features: torch.Tensor, n_prompts: int = 4, n_pos: int = 1, seed: int = PROMPT_SEED):
+    """Stand-ins for the text embeddings of segment.py (no text encoder exists here): `n_prompts` seeded rows of the finished
+    field, each normalised to unit length, the first `n_pos` of them the positive prompts.  Rows without length are skipped.
+    Returns (prompts [P, D] float32 on the host, n_pos)."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    f = features.detach().float().cpu()
+    live = torch.nonzero(f.norm(dim=1) > 0)[:, 0]
+    assert live.numel() >= n_prompts >= n_pos >= 1
+    pick = live[torch.randperm(live.numel(), generator=g)[:n_prompts]]
+    return torch.nn.functional.normalize(f[pick], dim=1).contiguous(), int(n_pos)
+
+
 def view_shard(n_views: int, rank: int, world: int) -> List[int]:
     """Views r, r+R, r+2R, ... (interleaved to balance scene coverage)."""
     return list(range(rank, n_views, world))

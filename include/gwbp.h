@@ -531,6 +531,40 @@ GWBP_API int gwbp_pca_project(int64_t N, int32_t D, int32_t k, const float *X, i
  * channel: visualize_pca.py takes np.min / np.max over all three); hi == lo gives 0.5 everywhere.  colors may alias Y. */
 GWBP_API int gwbp_pca_colors(int64_t n, const float *Y, const float *lo_hi, float *colors, void *stream);
 
+/* ---- questions asked of a finished field (the reference's segment.py, segment_compressed.py, click_and_segment.py) ---------------
+ * Scores of every row of X[g * ldx + 0..D-1], g < N, against P prompt vectors prompts[j * D + 0..D-1] (dense), and the 3-D mask of
+ * get_mask3d_lseg, in ONE pass over X; no workspace, no view.
+ *   s[g, j]  = X[g] . prompts[j] / max(|X[g]|_2, 1e-12)  with normalize != 0 (F.normalize's rule: a zero row scores 0), the bare
+ *              dot product otherwise (click_and_segment.py's form)
+ *   mask[g]  = max_{j < n_pos} s[g, j] > max_{j >= n_pos} s[g, j], ANDed with s[g, 0] > *threshold_host when that pointer is given
+ *              (read on the host at the call).  n_pos == P: no negatives, the mask is the threshold test alone and the threshold
+ *              is required.  A NaN score loses every comparison (the maxima propagate NaN as torch.max does).
+ * mask (uint8 [N], 0 / 1) and scores (fp32 [N, P] dense) may each be NULL, not both.  1 <= P <= GWBP_QUERY_MAX_P (the channel limit
+ * of gwbp_render_pixels, which renders the scores), 1 <= n_pos <= P, 1 <= D <= GWBP_PCA_MAX_D, ldx >= D, N >= 0.
+ * Arithmetic: every dot product and the row's sum of squares is one chain of fp32 fused multiply-adds over the channel index in
+ * an order that depends only on D (the fp32 matrix cores; no reduced-precision operand); one correctly rounded sqrt and divide.
+ * Results do not depend on the row's position, on N, P or the launch; rows whose address and stride are 16-B aligned are read with
+ * 16-B loads, others element by element, with bit-equal results; padding beyond D is never read; no atomics.
+ * GWBP_EINVAL before any HIP call: sizes out of range, a stride below D, a null or (4-B) misaligned X or prompts, both outputs
+ * null, no negatives and no threshold. */
+#define GWBP_QUERY_MAX_P 32
+GWBP_API int gwbp_prompt_scores(int64_t N, int32_t D, int32_t P, int32_t n_pos, const float *X, int64_t ldx, const float *prompts,
+                                int32_t normalize, const float *threshold_host, uint8_t *mask, float *scores, void *stream);
+
+/* The field rendered at M pixels only (click_and_segment.py:241-254 renders all [H, W, D + 1] values to read one pixel's): needs
+ * gwbp_project (or gwbp_project_camera) + gwbp_bin_sort of the view in the workspace, like gwbp_render_pixels; no weight store.
+ *   out[m, :] = sum_g w_g(p_m) X[g, :]   depth[m] = sum_g w_g(p_m) z_g (z: the projection's camera depth; gsplat's accumulated "D"
+ *   channel, not the expected depth)   alpha[m] = 1 - T          p_m = (xy[2 m], xy[2 m + 1]) = (x, y), int32 on the DEVICE
+ * X[g * ldx + 0..D-1] has a row for every Gaussian of the caps.  out is dense [M, D]; depth and alpha ([M]) may be NULL.  A pixel
+ * outside the image gives a zero row, depth 0 and alpha 0.  The weights are the blend's bit for bit, and every channel is summed
+ * front to back with fmaf(w, x, acc): the result equals that pixel of gwbp_render / gwbp_render_pixels of the same table.
+ * 1 <= M <= GWBP_PROBE_MAX_PIXELS, 1 <= D <= GWBP_PCA_MAX_D, ldx >= D.
+ * GWBP_EINVAL before the workspace is looked at: sizes out of range, a stride below D, a null or (4-B) misaligned xy, X or out. */
+#define GWBP_PROBE_MAX_PIXELS 4096
+GWBP_API int gwbp_probe_pixels(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                               int32_t M, const int32_t *xy, const float *X, int64_t ldx, int32_t D, float *out, float *depth,
+                               float *alpha, void *stream);
+
 /* Adds this view's counters into `accum` (device, gwbp_stats) -- used by bench/driver to total pairs. */
 GWBP_API int gwbp_accumulate_stats(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, gwbp_stats *accum,
                           void *stream);
