@@ -196,6 +196,8 @@ ARGTYPES = {
     # M, xy, X, ldx, D, out, depth, alpha, stream
     "gwbp_prompt_scores": [_I64, _I32, _I32, _I32, _P, _I64, _P, _I32, C.POINTER(C.c_float), _P, _P, _P],
     "gwbp_probe_pixels": _WSV + [_I32, _P, _P, _I64, _I32, _P, _P, _P, _P],
+    # labels, num_classes, maps, alphas, argmax, argmax_sums, min_opacity, gt, cut, counts, stream
+    "gwbp_render_labels": _WSV + [_P, _I32, _P, _P, _P, _P, _F, _P, _I32, _P, _P],
 }
 # every symbol of include/gwbp.h: the two functions that return strings, then the int-returning ones declared above
 EXPORTS = ["gwbp_version", "gwbp_last_error_string", *ARGTYPES]

@@ -1038,6 +1038,39 @@ int gwbp_probe_pixels(const gwbp_caps *caps, void *workspace, size_t workspace_b
     return launch_probe_pixels(B.W, B.V, M, xy, X, ldx, D, out, depth, alpha, B.s);
 }
 
+int gwbp_render_labels(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                       const int32_t *labels, int32_t num_classes, float *maps, float *alphas, int32_t *argmax, float *argmax_sums,
+                       float min_opacity, const int32_t *gt, int32_t cut, uint64_t *counts, void *stream)
+{
+    // the call's own arguments first: nothing of the caps, the workspace or the view is looked at before they pass
+    if (num_classes < 1 || num_classes > GWBP_RENDER_LABELS_MAX_CLASSES)
+        return set_error(GWBP_EINVAL, "render_labels: num_classes must be in [1, %d] (got %d)", GWBP_RENDER_LABELS_MAX_CLASSES,
+                         (int)num_classes);
+    if (!labels || (reinterpret_cast<uintptr_t>(labels) & 3))
+        return set_error(GWBP_EINVAL, "render_labels: labels must be a non-null, 4-B aligned int32 [N] array");
+    if (!maps && !alphas && !argmax && !argmax_sums && !counts)
+        return set_error(GWBP_EINVAL, "render_labels: every output is null");
+    if ((reinterpret_cast<uintptr_t>(maps) & 3) || (reinterpret_cast<uintptr_t>(alphas) & 3) ||
+        (reinterpret_cast<uintptr_t>(argmax) & 3) || (reinterpret_cast<uintptr_t>(argmax_sums) & 3))
+        return set_error(GWBP_EINVAL, "render_labels: maps, alphas, argmax and argmax_sums must be 4-B aligned");
+    if (argmax && !argmax_sums && num_classes > 64)
+        return set_error(GWBP_EINVAL, "render_labels: argmax of %d > 64 classes needs argmax_sums (the carry between class chunks)",
+                         (int)num_classes);
+    if (!gt != !counts)
+        return set_error(GWBP_EINVAL, "render_labels: gt and counts go together (got %s gt, %s counts)", gt ? "a" : "null",
+                         counts ? "a" : "null");
+    if ((reinterpret_cast<uintptr_t>(gt) & 3) || (reinterpret_cast<uintptr_t>(counts) & 7))
+        return set_error(GWBP_EINVAL, "render_labels: gt must be 4-B aligned, counts 8-B");
+    if (cut < 0 || cut > 255)
+        return set_error(GWBP_EINVAL, "render_labels: cut must be in [0, 255] (got %d)", (int)cut);
+    Bound B;
+    const int rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B);
+    if (rc)
+        return rc;
+    return launch_render_labels(B.W, B.V, labels, num_classes, maps, alphas, argmax, argmax_sums, min_opacity, gt, cut,
+                                reinterpret_cast<u64 *>(counts), B.s);
+}
+
 int gwbp_accumulate_stats(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, gwbp_stats *accum,
                           void *stream)
 {

@@ -256,6 +256,10 @@ int launch_render_px(const Ws &W, const ViewDev &V, const float *colors, int D, 
                      hipStream_t s);
 int launch_sh_colors(int64_t N, int degree, int K, const float *means, const float *coeffs, const float *campos,
                      float *out, hipStream_t s);
+// per-Gaussian labels rendered to class maps, their argmax and the counts against a ground-truth map (label_render.hip); every
+// output may be nullptr; best: the largest class sum per pixel, needed beside argmax from K > 64 on (the carry between chunks)
+int launch_render_labels(const Ws &W, const ViewDev &V, const int32_t *labels, int K, float *maps, float *alphas, int32_t *argmax,
+                         float *best, float min_opacity, const int32_t *gt, int cut, u64 *counts, hipStream_t s);
 int launch_encode_map(const float *feats, int64_t fs_y, int64_t fs_x, int H, int W, int K, const float *enc, int n_out,
                       float *out, int workgroups, hipStream_t s);
 int launch_finalize(int64_t N, int D, const float *F, const float *d, float *out, hipStream_t s);

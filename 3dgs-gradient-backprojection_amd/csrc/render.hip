@@ -4,9 +4,10 @@
 // "Next" row N3 of SURVEY.md section 8(f): the step BEFORE the hot path in the reference (backproject.py:89-100 renders
 // the view with sh_degree=3 and feeds it to the 2-D feature network) and utils.test_proper_pruning (utils.py:316-340).
 // k_render_px is the classic tile rasteriser: workgroup = 16x16 tile, thread = pixel, Gaussian records staged in LDS per
-// batch, same blend arithmetic as k_blend (so alpha / T / early termination are bit-identical), colours accumulated
+// batch, same blend arithmetic as k_blend (px_blend.h: alpha / T / early termination are bit-identical), colours accumulated
 // front to back in registers.  It needs only project + bin_sort, not the weight store.
 #include "gwbp_dev.h"
+#include "px_blend.h"
 
 namespace gwbp {
 
@@ -45,11 +46,7 @@ __global__ __launch_bounds__(256) void k_render_px(ViewDev V, const u32 *__restr
         if (threadIdx.x < bn) {
             const u32 gid = vals[batch + threadIdx.x];
             const float4 *gp = reinterpret_cast<const float4 *>(g2d + gid);
-            float4 a = gp[0];
-            // alpha = o exp(-sigma) >= 1/255  <=>  sigma <= ln(255 o); 1e-3 absorbs the error of __logf and exp_neg (k_blend's
-            // s_thr); o <= 1/255 gives a negative bound that no sigma >= 0 meets
-            a.w = __logf(255.0f * a.z) + 1e-3f;
-            s_a[threadIdx.x] = a;
+            s_a[threadIdx.x] = px_stage(gp[0]);
             s_b[threadIdx.x] = gp[1];
             const float *cp = colors + (size_t)gid * D;
             float cv[CH];
@@ -65,19 +62,12 @@ __global__ __launch_bounds__(256) void k_render_px(ViewDev V, const u32 *__restr
             if (__ballot(!done) == 0ull)
                 break;
             const float4 a = s_a[j], b = s_b[j];
-            const float dx = a.x - px, dy = a.y - py;
-            const float sigma = __builtin_fmaf(b.y * dx, dy, 0.5f * __builtin_fmaf(b.x * dx, dx, (b.z * dy) * dy));
-            if (__ballot(!done && sigma <= a.w) == 0ull)
+            const float sigma = px_sigma(a, b, px, py);
+            if (px_quarter_outside(done, sigma, a.w))
                 continue; // no live pixel of this quarter inside the alpha >= 1/255 ellipse
-            const float alpha = __builtin_fminf(kAlphaMax, a.z * exp_neg(-__builtin_fmaxf(sigma, 0.f)));
-            const bool ok = !done && (sigma >= 0.f) && (alpha >= kAlphaMin);
-            const float next_T = T * (1.0f - alpha);
-            const bool term = ok && (next_T <= kTMin);
-            const bool valid = ok && !term;
-            const float w = valid ? alpha * T : 0.f;
-            T = valid ? next_T : T;
-            done = done || term;
-            if (__ballot(valid) == 0ull)
+            float w;
+            const bool valid = px_step(sigma, a.z, T, done, w);
+            if (px_nobody(valid))
                 continue; // nobody takes colour from this Gaussian
 #pragma unroll
             for (int c4 = 0; c4 < CH / 4; ++c4) {

@@ -855,6 +855,52 @@ class Engine:
                    ptr(alpha), self._stream())
         return out, depth, alpha
 
+    def render_labels(self, view, labels, num_classes: int, want_maps=True, want_alphas=True, want_argmax=False, gt=None,
+                      counts=None, cut: int = 64, min_opacity: float = 0.0):
+        """Per-Gaussian labels [N] (any integer type; int64 narrowed by narrow_labels; a label outside [0, num_classes) adds to
+        alpha and to no class) rendered in one blend pass (gwbp_render_labels; needs project + bin_sort of `view`, not the weight
+        store).  Returns (maps float32 [H, W, K] or None, alphas [H, W] or None, argmax int32 [H, W] or None, counts or None).
+        maps equal the render of the one-hot [N, K] table bit for bit; argmax is the class of the largest sum (lowest index among
+        equals), -1 where nothing contributed or that sum lies below min_opacity.  gt: an integer [H, W] label map; the call then
+        ADDS the {intersection, predicted, ground truth} pixel counts of every class into counts (int64 [K, 3] on the device;
+        made, zeroed, when None), predicted being uint8(clamp(maps, 0, 1) * 255) > cut."""
+        K = int(num_classes)
+        if isinstance(num_classes, bool) or K < 1:
+            raise GwbpError(f"num_classes must be a positive int, got {num_classes!r}")
+        if (not torch.is_tensor(labels) or labels.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
+                or labels.dim() != 1):
+            raise GwbpError("labels must be an integer [N] tensor")
+        if not labels.is_cuda or labels.device.index != self._dev_index:
+            raise GwbpError(f"labels must be on the engine's device cuda:{self._dev_index}, got {labels.device}")
+        if labels.shape[0] != self.n:
+            raise GwbpError(f"engine was sized for {self.n} Gaussians, got {labels.shape[0]} labels")
+        with self._on_stream():
+            # (only an int64 id can wrap into range when narrowed; the kernel ignores what lies outside [0, K) itself)
+            labels = (narrow_labels(labels, K) if labels.dtype == torch.int64 else labels.to(torch.int32)).contiguous()
+            if counts is not None and gt is None:
+                raise GwbpError("counts without a ground-truth map gt")
+            if gt is not None:
+                if not torch.is_tensor(gt) or gt.is_floating_point() or gt.is_complex() or gt.dtype == torch.bool:
+                    raise GwbpError("gt must be an integer [H,W] label map")
+                if tuple(gt.shape) != (view.height, view.width):
+                    raise GwbpError(f"gt must be [H,W] = [{view.height},{view.width}], got {tuple(gt.shape)}")
+                gt = gt.to(self.device)
+                gt = (narrow_labels(gt, K) if gt.dtype == torch.int64 else gt.to(torch.int32)).contiguous()
+                if counts is None:
+                    counts = torch.zeros(K, 3, dtype=torch.int64, device=self.device)
+                elif (not torch.is_tensor(counts) or counts.dtype != torch.int64 or not counts.is_cuda
+                      or counts.device.index != self._dev_index or not counts.is_contiguous() or tuple(counts.shape) != (K, 3)):
+                    raise GwbpError(f"counts must be a contiguous int64 HIP tensor [{K},3]")
+            if not (want_maps or want_alphas or want_argmax or gt is not None):
+                raise GwbpError("render_labels: no output asked for")
+            maps = torch.empty(view.height, view.width, K, device=self.device) if want_maps else None
+            alphas = self._alphas(view, want_alphas)
+            argmax = torch.empty(view.height, view.width, dtype=torch.int32, device=self.device) if want_argmax else None
+            sums = torch.empty(view.height, view.width, device=self.device) if want_argmax and K > 64 else None
+        self._call("gwbp_render_labels", *self._args(), byref(view), ptr(labels), K, ptr(maps), ptr(alphas), ptr(argmax), ptr(sums),
+                   c_float(min_opacity), ptr(gt), int(cut), ptr(counts), self._stream())
+        return maps, alphas, argmax, counts
+
     def sh_colors(self, degree: int, means, coeffs, campos):
         """[N,K,3] SH coefficients -> [N,3] view-dependent colours (+0.5, clamped at 0) on the device."""
         means = _req(means, "means", (3,))

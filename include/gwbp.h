@@ -565,6 +565,33 @@ GWBP_API int gwbp_probe_pixels(const gwbp_caps *caps, void *workspace, size_t wo
                                int32_t M, const int32_t *xy, const float *X, int64_t ldx, int32_t D, float *out, float *depth,
                                float *alpha, void *stream);
 
+/* ---- per-Gaussian labels rendered to 2-D class maps and scored (the reference's evaluate_results and render_affordance,
+ * affordance_transfer/demo_affordance_transfer.py:1445-1611, 1399-1439) ------------------------------------------------------------
+ * One blend pass over a projected and sorted view (gwbp_project or gwbp_project_camera + gwbp_bin_sort, like gwbp_render_pixels; no
+ * weight store) with ONE int32 per Gaussian as its payload: labels[g], g < caps->n_gaussians.  A label outside [0, num_classes)
+ * contributes to alpha and to no class.  Every output may be NULL (not all of them); a NULL output costs no store.
+ *   maps   float [H, W, num_classes]: maps[p, k] = sum of w_g(p) over the Gaussians of label k, front to back.  Equal bit for bit
+ *          to the gwbp_render_pixels / gwbp_render of the one-hot [N, num_classes] table, which nobody has to build.
+ *   alphas float [H, W]: as gwbp_render_pixels.
+ *   argmax int32 [H, W]: the class of the largest sum, the lowest index among equals; -1 where no class has a sum above 0 or the
+ *          largest sum lies below min_opacity.  argmax_sums float [H, W]: that largest sum (0 where nothing contributed); it is
+ *          the carry between the chunks of 64 classes a wide table is rendered in, so argmax needs it from num_classes > 64 on.
+ *   counts uint64 [num_classes, 3]: {intersection, predicted, ground truth} pixel counts of every class against gt (int32 [H, W],
+ *          dense), ADDED to what is there:
+ *            predicted(p, k)    <=>  fl32(min(max(maps[p, k], 0), 1) * 255.0f) >= cut + 1   (the reference's
+ *                                    torch_to_cv(render) > cut: clamp, one fp32 multiply, truncation to uint8; cut = 64 there)
+ *            ground truth(p, k) <=>  gt[p] == k   (a value outside [0, num_classes) matches no class)
+ *          Integer atomics only: the counts do not depend on the order of the additions.  gt and counts come together.
+ * num_classes > 64 costs one blend pass per 64 classes (class sums are independent: the result is that of one pass).
+ * GWBP_EINVAL before the workspace is looked at: num_classes outside [1, GWBP_RENDER_LABELS_MAX_CLASSES], null or misaligned
+ * labels, every output null, a misaligned output (counts: 8 B, others 4 B), argmax of more than 64 classes without argmax_sums,
+ * gt without counts or counts without gt, cut outside [0, 255]. */
+#define GWBP_RENDER_LABELS_MAX_CLASSES 65536
+GWBP_API int gwbp_render_labels(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                                const int32_t *labels, int32_t num_classes, float *maps, float *alphas, int32_t *argmax,
+                                float *argmax_sums, float min_opacity, const int32_t *gt, int32_t cut, uint64_t *counts,
+                                void *stream);
+
 /* Adds this view's counters into `accum` (device, gwbp_stats) -- used by bench/driver to total pairs. */
 GWBP_API int gwbp_accumulate_stats(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, gwbp_stats *accum,
                           void *stream);
