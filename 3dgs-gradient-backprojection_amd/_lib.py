@@ -198,6 +198,8 @@ ARGTYPES = {
     "gwbp_probe_pixels": _WSV + [_I32, _P, _P, _I64, _I32, _P, _P, _P, _P],
     # labels, num_classes, maps, alphas, argmax, argmax_sums, min_opacity, gt, cut, counts, stream
     "gwbp_render_labels": _WSV + [_P, _I32, _P, _P, _P, _P, _F, _P, _I32, _P, _P],
+    # features, ldf, D, map, map_type, ms_y, ms_x, lr_h, lr_w, ymap, xmap, planes, table, stream
+    "gwbp_field_compare": _WSV + [_P, _I64, _I32, _P, _I32, _I64, _I64, _I32, _I32, _P, _P, _P, _P, _P],
 }
 # every symbol of include/gwbp.h: the two functions that return strings, then the int-returning ones declared above
 EXPORTS = ["gwbp_version", "gwbp_last_error_string", *ARGTYPES]

@@ -242,6 +242,9 @@ static int check_pixel_weights(const gwbp_pixel_weights *pw, PixW *out, const Pi
 
 using namespace gwbp;
 static_assert(sizeof(gwbp_pixel_weights) == 32, "gwbp_pixel_weights is part of the ABI");
+// the rows' partial sums of gwbp_field_compare live in the carry slices (field_compare.hip)
+static_assert((size_t)GWBP_FIELD_COMPARE_MAX_TILES * 16 * 6 * sizeof(double) <= (size_t)kCarryWgs * kCarryRows * 256 * sizeof(float),
+              "GWBP_FIELD_COMPARE_MAX_TILES does not fit the carry slices");
 
 static hipStream_t as_stream(void *stream) { return static_cast<hipStream_t>(stream); }
 
@@ -1069,6 +1072,46 @@ int gwbp_render_labels(const gwbp_caps *caps, void *workspace, size_t workspace_
         return rc;
     return launch_render_labels(B.W, B.V, labels, num_classes, maps, alphas, argmax, argmax_sums, min_opacity, gt, cut,
                                 reinterpret_cast<u64 *>(counts), B.s);
+}
+
+int gwbp_field_compare(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                       const float *features, int64_t ldf, int32_t D, const void *map, int32_t map_type, int64_t ms_y, int64_t ms_x,
+                       int32_t lr_h, int32_t lr_w, const int32_t *ymap, const int32_t *xmap, float *planes, double *table,
+                       void *stream)
+{
+    // the caps, the workspace and the view first (as gwbp_render), then the call's own arguments, each kind once
+    Bound B;
+    int rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B);
+    if (rc)
+        return rc;
+    if (!known_map_type(map_type))
+        return set_error(GWBP_EINVAL, "field_compare: unknown map type %d", (int)map_type);
+    if (D < 1 || D > GWBP_PCA_MAX_D)
+        return set_error(GWBP_EINVAL, "field_compare: D must be in [1, %d] (got %d)", GWBP_PCA_MAX_D, (int)D);
+    if (ldf < D)
+        return set_error(GWBP_EINVAL, "field_compare: row stride %lld below D = %d", (long long)ldf, (int)D);
+    if ((!features && B.L.n > 0) || (reinterpret_cast<uintptr_t>(features) & 3))
+        return set_error(GWBP_EINVAL, "field_compare: features must be a non-null, 4-B aligned [N, D] array");
+    if (!map || (reinterpret_cast<uintptr_t>(map) & (map_type == GWBP_MAP_F32 ? 3 : 1)))
+        return set_error(GWBP_EINVAL, "field_compare: the map must be non-null and aligned to its element type");
+    if (ms_y < 0 || ms_x < 0)
+        return set_error(GWBP_EINVAL, "field_compare: negative map strides (%lld %lld)", (long long)ms_y, (long long)ms_x);
+    if ((rc = check_index_maps("gwbp_field_compare", ymap, xmap)))
+        return rc;
+    if (ymap && (lr_h < 1 || lr_w < 1))
+        return set_error(GWBP_EINVAL, "field_compare: index maps need the low-resolution map's shape (got %d x %d)", (int)lr_h,
+                         (int)lr_w);
+    if ((reinterpret_cast<uintptr_t>(ymap) & 3) || (reinterpret_cast<uintptr_t>(xmap) & 3))
+        return set_error(GWBP_EINVAL, "field_compare: the index maps must be 4-B aligned");
+    if (reinterpret_cast<uintptr_t>(planes) & 3)
+        return set_error(GWBP_EINVAL, "field_compare: planes must be 4-B aligned");
+    if (!table || (reinterpret_cast<uintptr_t>(table) & 7))
+        return set_error(GWBP_EINVAL, "field_compare: table must be a non-null, 8-B aligned float64 [8] array");
+    if (B.V.tile_w * B.V.tile_h > GWBP_FIELD_COMPARE_MAX_TILES)
+        return set_error(GWBP_EINVAL, "field_compare: a view of %d tiles exceeds GWBP_FIELD_COMPARE_MAX_TILES = %d",
+                         B.V.tile_w * B.V.tile_h, GWBP_FIELD_COMPARE_MAX_TILES);
+    return launch_field_compare(B.L, B.W, B.V, features, ldf, D, map, map_type, ms_y, ms_x, ymap ? lr_h : 0, ymap ? lr_w : 0, ymap,
+                                xmap, planes, table, B.s);
 }
 
 int gwbp_accumulate_stats(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, gwbp_stats *accum,

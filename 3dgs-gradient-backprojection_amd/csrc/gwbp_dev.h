@@ -260,6 +260,12 @@ int launch_sh_colors(int64_t N, int degree, int K, const float *means, const flo
 // output may be nullptr; best: the largest class sum per pixel, needed beside argmax from K > 64 on (the carry between chunks)
 int launch_render_labels(const Ws &W, const ViewDev &V, const int32_t *labels, int K, float *maps, float *alphas, int32_t *argmax,
                          float *best, float min_opacity, const int32_t *gt, int cut, u64 *counts, hipStream_t s);
+// a field rendered from the weight store and compared with the view's map (field_compare.hip): planes [6][H][W] or nullptr, table
+// [8] float64; the rows' partial sums take field_compare_scratch_bytes(tiles) of the workspace's carry slices
+size_t field_compare_scratch_bytes(int n_tiles);
+int launch_field_compare(const Layout &L, const Ws &W, const ViewDev &V, const float *feats, int64_t ldf, int D, const void *map,
+                         int mt, int64_t ms_y, int64_t ms_x, int lr_h, int lr_w, const int32_t *ymap, const int32_t *xmap,
+                         float *planes, double *table, hipStream_t s);
 int launch_encode_map(const float *feats, int64_t fs_y, int64_t fs_x, int H, int W, int K, const float *enc, int n_out,
                       float *out, int workgroups, hipStream_t s);
 int launch_finalize(int64_t N, int D, const float *F, const float *d, float *out, hipStream_t s);

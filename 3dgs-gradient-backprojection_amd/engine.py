@@ -822,6 +822,54 @@ class Engine:
         self._call("gwbp_render", *self._args(), byref(view), ptr(colors), D, ptr(out), self._stream())
         return out
 
+    def field_compare(self, view, features, fmap, index=None, want_planes=True, table=None):
+        """The field `features` [N, D] (float32, any row stride >= D, read in place) rendered from the view's weight store and
+        compared with the view's map inside the kernel (gwbp_field_compare): needs project + bin_sort + blend_weights of `view`,
+        like render().  Returns (planes, table): planes float32 [6, H, W] = dot, rr, mm, l1, l2, cosine of the rendered row r and
+        the map row m per pixel (None with want_planes=False: no plane is written), table float64 [8] on the device = sum cosine,
+        sum l1, sum l2, sum mm (over the valid pixels), n_valid, n_bad, n_pixels, D.
+        fmap: [H, W, D] float32 / float16 / bfloat16 with unit channel stride and non-negative pixel strides, read as stored; with
+        index = (ymap int32 [H], xmap int32 [W]) (nearest_maps) a low-resolution [h, w, D] map read through them.
+        table: a float64 [8] device tensor to fill (a row of a [V, 8] table) instead of a new one."""
+        if self._tokens is not None:
+            raise GwbpError("this view was blended with blend_tokens (no weight store): blend_weights() first for field_compare()")
+        if not torch.is_tensor(features) or not features.is_cuda or features.dtype != torch.float32 or features.dim() != 2:
+            raise GwbpError("features must be a float32 [N, D] HIP tensor")
+        if features.shape[0] != self.n:
+            raise GwbpError(f"engine was sized for {self.n} Gaussians, the field has {features.shape[0]} rows")
+        D = features.shape[1]
+        if not 1 <= D <= 2048:
+            raise GwbpError(f"D must be in [1, 2048], got {D}")
+        if (D > 1 and features.stride(1) != 1) or (self.n > 1 and features.stride(0) < D):
+            features = features.contiguous()
+        ld = int(features.stride(0)) if self.n > 1 else D
+        sy, sx, sc, Dm = self._feat_strides(fmap, view, lowres=index is not None)
+        if Dm != D:
+            raise GwbpError(f"the field has D = {D}, the map D = {Dm}")
+        if D > 1 and sc != 1:
+            raise GwbpError("the map's channels must be contiguous (unit last stride)")
+        if fmap.device.index != self._dev_index:
+            raise GwbpError(f"the map must be on the engine's device cuda:{self._dev_index}, got {fmap.device}")
+        ymap = xmap = None
+        lr_h = lr_w = 0
+        if index is not None:
+            ymap, xmap = index
+            for t, n, name in ((ymap, view.height, "ymap [H]"), (xmap, view.width, "xmap [W]")):
+                if (not torch.is_tensor(t) or t.dtype != torch.int32 or not t.is_cuda or tuple(t.shape) != (n,)
+                        or not t.is_contiguous()):
+                    raise GwbpError(f"index must be (ymap [H], xmap [W]) contiguous int32 HIP tensors; bad {name}")
+            lr_h, lr_w = int(fmap.shape[0]), int(fmap.shape[1])
+        if table is None:
+            table = torch.empty(8, dtype=torch.float64, device=self.device)
+        elif (not torch.is_tensor(table) or table.dtype != torch.float64 or not table.is_cuda or tuple(table.shape) != (8,)
+              or not table.is_contiguous()):
+            raise GwbpError("table must be a contiguous float64 [8] HIP tensor")
+        planes = torch.empty(6, view.height, view.width, device=self.device) if want_planes else None
+        self._call("gwbp_field_compare", *self._args(), byref(view), ptr(features), c_int64(ld), D, ptr(fmap),
+                   MAP_TYPES[fmap.dtype], c_int64(sy), c_int64(sx), lr_h, lr_w, ptr(ymap), ptr(xmap), ptr(planes), ptr(table),
+                   self._stream())
+        return planes, table
+
     def render_pixels(self, view, colors, want_alphas=True):
         """Pixel-parallel forward render for 1..32 channels; needs project + bin_sort of `view` (not the weight store)."""
         colors = _req(colors, "colors")

@@ -592,6 +592,38 @@ GWBP_API int gwbp_render_labels(const gwbp_caps *caps, void *workspace, size_t w
                                 float *argmax_sums, float min_opacity, const int32_t *gt, int32_t cut, uint64_t *counts,
                                 void *stream);
 
+/* ---- a finished field scored against the 2-D map of a view it was lifted from ------------------------------------------------------
+ * Needs the view's weight store in the workspace, exactly as gwbp_render does (gwbp_project or gwbp_project_camera + gwbp_bin_sort +
+ * a storing blend).  With r(p) = sum_g w_g(p) features[g * ldf + 0..D-1] -- gwbp_render's values bit for bit: the same front-to-back
+ * fmaf chain per pixel and channel -- and m(p, :) the map row of pixel p, the kernel forms per pixel, in fp32,
+ *     dot = sum_c r m     rr = sum_c r r     mm = sum_c m m     l1 = sum_c |r - m|     l2 = sum_c (r - m)^2
+ * and cosine = dot / sqrt(rr mm) (float64 arithmetic on the fp32 sums, one rounding to fp32; NaN where rr mm == 0).  The [H, W, D]
+ * render is never made.
+ *   map     element type map_type (GWBP_MAP_F32 / F16 / BF16, read natively with the value of a conversion to fp32), unit channel
+ *           stride, pixel (y, x) at map + y * ms_y + x * ms_x (strides in elements, >= 0).  Full resolution [H, W, D] with ymap =
+ *           xmap = NULL; or a low-resolution [lr_h, lr_w, D] map with ymap int32 [H] / xmap int32 [W], the row / column of every
+ *           output row / column (F.interpolate(mode="nearest")'s index maps; clamped into the map by the kernel).
+ *   planes  float [6][H][W] or NULL: dot, rr, mm, l1, l2, cosine.  NULL costs no store.
+ *   table   double [8], overwritten: sum cosine, sum l1, sum l2, sum mm, n_valid, n_bad, n_pixels (= H W), D.
+ * A pixel whose map row holds a non-finite element is BAD: NaN in all six planes, counted in n_bad.  A pixel is VALID when it is not
+ * bad, its five sums are finite, rr > 0 and mm > 0; the four sums of the table run over the valid pixels only.  Pixels of a partial
+ * edge tile outside the image are neither read nor written.
+ * Order of additions (depends on D alone -- not on alignment, the map's type or shape): per block of 256 channels a lane's four
+ * channels in ascending order, the 64 lanes by a fixed tree, the blocks in ascending order; the table in float64: a tile row's 16
+ * pixels by a fixed butterfly, the rows in a fixed order.  No atomics: two calls give the same bits, and the table does not depend
+ * on whether planes are asked for.  Rows whose addresses and strides allow 16-B (field) and four-element (map) loads are read so,
+ * others element by element, with bit-equal results.
+ * The rows' partial sums use the workspace's carry slices (the 256-channel scatter kernel's): like every call on a workspace, it
+ * must not run beside another call on the same workspace.  Views of at most GWBP_FIELD_COMPARE_MAX_TILES 16 x 16 tiles.
+ * GWBP_EINVAL (after the caps, the workspace and the view, before any HIP call): an unknown map type, D outside [1, GWBP_PCA_MAX_D],
+ * ldf < D, null or misaligned features (a scene of 0 Gaussians may pass NULL), map, index maps, planes (4 B) or table (8 B), negative
+ * strides, one index map without the other, index maps without lr_h, lr_w >= 1, more tiles than the limit. */
+#define GWBP_FIELD_COMPARE_MAX_TILES 262144
+GWBP_API int gwbp_field_compare(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                                const float *features, int64_t ldf, int32_t D, const void *map, int32_t map_type, int64_t ms_y,
+                                int64_t ms_x, int32_t lr_h, int32_t lr_w, const int32_t *ymap, const int32_t *xmap, float *planes,
+                                double *table, void *stream);
+
 /* Adds this view's counters into `accum` (device, gwbp_stats) -- used by bench/driver to total pairs. */
 GWBP_API int gwbp_accumulate_stats(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, gwbp_stats *accum,
                           void *stream);
