@@ -672,7 +672,9 @@ int orc_sh_colors(int64_t N, int degree, int K, const float *means, const float 
     for (int64_t i = 0; i < N; ++i) {
         double x = (double)means[3 * i] - campos[0], y = (double)means[3 * i + 1] - campos[1],
                z = (double)means[3 * i + 2] - campos[2];
-        const double n = sqrt(x * x + y * y + z * z);
+        /* a Gaussian AT the camera centre has no direction: the floor keeps it at 0 (the DC term alone), like k_sh_colors and
+         * tests/ref_sh.py; 0 / 0 would turn every band above the first into NaN, which the clamp below then hides as 0 */
+        const double n = fmax(sqrt(x * x + y * y + z * z), 1e-12);
         x /= n, y /= n, z /= n;
         double b[16];
         const double xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;

@@ -18,7 +18,9 @@ Gaussians, 4 views 400 x 300, D = 32: the fused blend + scatter kernels), T1 wit
 and commits the resulting .npz DATA files (inputs are already committed; nothing of gsplat's or the reference's source
 travels).  tests/test_oracle.py::test_oracle_against_gsplat_capture (CPU) and tests/test_gpu_parity.py::
 test_hip_against_gsplat_capture (GPU) consume the files when present and are skipped otherwise; CAMERA_CASES (fisheye,
-ortho, pinhole + antialiased on T1) go to tests/golden/gsplat_camera_*.npz for tests/test_gpu_camera_models_capture.py.
+ortho, pinhole + antialiased on T1) go to tests/golden/gsplat_camera_*.npz for tests/test_gpu_camera_models_capture.py.  RENDER_CASES
+(forward renders under "ED" / "RGB+ED" with a background whose depth entry is non-zero) go to tests/golden/gsplat_render_*.npz:
+they settle the order of "divide by alpha" and "add the background" (DESIGN.md section 7); nothing consumes them yet.
 
 What is captured, per view, mirrors the reference's per-view body (backproject.py:115-151) literally:
   * rasterization(means, quats, scales, opacities, zeros[N, D], viewmat[None], K[None], width=W, height=H)
@@ -57,6 +59,16 @@ CAMERA_CASES = [
     ("gsplat_camera_t1_ortho.npz", "T1", "ortho", "classic"),
     ("gsplat_camera_t1_pinhole_antialiased.npz", "T1", "pinhole", "antialiased"),
 ]
+# forward renders whose semantics the drop-in cannot settle by reading: (file, seeded config, render_mode, backgrounds row).
+# "RGB+ED" with a NON-ZERO depth entry in the background decides whether gsplat divides the depth channel by alpha before or
+# after it adds (1 - alpha) * background ("Open: ED with a background"); the zero-entry twin is the case
+# where both orders agree.  View 0, colours = the seeded RGB table of render_case_colors().
+RENDER_CASES = [
+    ("gsplat_render_t1_rgbed_bg_depth.npz", "T1", "RGB+ED", (0.2, 0.4, 0.6, 2.5)),
+    ("gsplat_render_t1_rgbed_bg_zero_depth.npz", "T1", "RGB+ED", (0.2, 0.4, 0.6, 0.0)),
+    ("gsplat_render_t1_ed_bg_depth.npz", "T1", "ED", (2.5,)),
+]
+RENDER_COLOR_SEED = 5
 ENCODER_SEED = 7
 TOKEN_SEED0 = 500
 
@@ -155,6 +167,33 @@ def capture(inp, out_path, per_view=True):
     print("wrote", out_path, {k: getattr(v, "shape", v) for k, v in save.items()})
 
 
+def render_case_colors(n):
+    """The seeded [n, 3] RGB table of RENDER_CASES (shared with whoever consumes the files)."""
+    import torch
+    return torch.rand(n, 3, generator=torch.Generator().manual_seed(RENDER_COLOR_SEED)).numpy()
+
+
+def capture_render(inp, out_path, render_mode, background):
+    """One forward rasterization() of view 0 under `render_mode` with and without `backgrounds`: the renders and the alpha map."""
+    import torch
+    from gsplat import rasterization
+    import gsplat
+    dev = torch.device(os.environ.get("GWBP_CAPTURE_DEVICE", "cuda"))
+    t = {k: torch.from_numpy(np.asarray(inp[k])).to(dev) for k in ("means", "quats", "scales", "opac", "K", "vms")}
+    W, H = int(2 * float(inp["K"][0][2])), int(2 * float(inp["K"][1][2]))
+    colors = torch.from_numpy(render_case_colors(t["means"].shape[0])).to(dev)
+    bg = torch.tensor([list(background)], dtype=torch.float32, device=dev)
+    save = dict(gsplat_version=np.array(gsplat.__version__), render_mode=np.array(render_mode), background=bg.cpu().numpy())
+    with torch.no_grad():
+        for name, kw in (("plain", {}), ("bg", dict(backgrounds=bg))):
+            out, alphas, _ = rasterization(t["means"], t["quats"], t["scales"], t["opac"], colors, t["vms"][:1], t["K"][None],
+                                           width=W, height=H, render_mode=render_mode, **kw)
+            save["out_" + name] = out[0].cpu().numpy()
+            save["alphas_" + name] = alphas[0, ..., 0].cpu().numpy()
+    np.savez_compressed(out_path, **save)
+    print("wrote", out_path, {k: getattr(v, "shape", v) for k, v in save.items()})
+
+
 def main():
     for fname, cfgname, dim, enc_dim in CASES:
         if cfgname is None:
@@ -170,6 +209,8 @@ def main():
         capture(token_case_inputs(cfgname, dim, grid), os.path.join(GOLD, fname), per_view=False)
     for fname, cfgname, model, mode in CAMERA_CASES:
         capture({**case_inputs(cfgname), "camera_model": model, "rasterize_mode": mode}, os.path.join(GOLD, fname))
+    for fname, cfgname, mode, background in RENDER_CASES:
+        capture_render(case_inputs(cfgname, 1), os.path.join(GOLD, fname), mode, background)
 
 
 if __name__ == "__main__":
