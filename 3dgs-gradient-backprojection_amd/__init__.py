@@ -13,6 +13,8 @@ JojiJoseph/3dgs-gradient-backprojection), hand-written HIP kernels behind a C AB
     from gsbp_amd import recolor_by_labels          # maps, their mIoU / recall against ground truth, and the scene tinted by label
     from gsbp_amd import render_field_agreement, score_field_views, field_fidelity, agreement_weights  # a field scored against the
                                                     # maps it was lifted from, fused; and the weight map for a second, robust lift
+    from gsbp_amd import decoded_loss, decoded_field_gradients, fit_decoded_field, decode_field  # a latent field and its decoder
+                                                    # fitted on frozen Gaussians (the reference's Feature-3DGS baseline), fused
 """
 from . import synthetic  # noqa: F401
 from ._lib import GwbpError, build, lib  # noqa: F401
@@ -25,4 +27,5 @@ from .pca import PCABasis, fit_pca, pca_colors, pca_transform, render_pca  # noq
 from .segment import ClickSession, apply_mask3d, probe_pixels, prompt_mask, prompt_scores, render_prompt_mask  # noqa: F401
 from .label_render import miou_recall, recolor_by_labels, render_label_argmax, render_label_maps, score_label_views  # noqa: F401
 from .fidelity import agreement_weights, field_fidelity, render_field_agreement, score_field_views  # noqa: F401
+from .decoded_field import decode_field, decoded_field_gradients, decoded_loss, fit_decoded_field  # noqa: F401
 from .pruning import check_proper_pruning, gradient_mask, prune_by_gradients  # noqa: F401

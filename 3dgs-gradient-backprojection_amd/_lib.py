@@ -200,7 +200,13 @@ ARGTYPES = {
     "gwbp_render_labels": _WSV + [_P, _I32, _P, _P, _P, _P, _F, _P, _I32, _P, _P],
     # features, ldf, D, map, map_type, ms_y, ms_x, lr_h, lr_w, ymap, xmap, planes, table, stream
     "gwbp_field_compare": _WSV + [_P, _I64, _I32, _P, _I32, _I64, _I64, _I32, _I32, _P, _P, _P, _P, _P],
+    # d, D, bytes*  /  height, width, d, D, R, ldr, C, ldc, map, map_type, ms_y, ms_x, pixel weights, loss_kind, scale, GR, ldg,
+    # GC, ldgc, table, workspace, bytes, stream
+    "gwbp_decode_loss_workspace_size": [_I32, _I32, C.POINTER(C.c_size_t)],
+    "gwbp_decode_loss": [_I32, _I32, _I32, _I32, _P, _I64, _P, _I64, _P, _I32, _I64, _I64, C.POINTER(PixelWeights), _I32, _F, _P,
+                         _I64, _P, _I64, _P, _P, _SZ, _P],
 }
+LOSS_KINDS = {"l1": 0, "l2": 1}  # GWBP_LOSS_*
 # every symbol of include/gwbp.h: the two functions that return strings, then the int-returning ones declared above
 EXPORTS = ["gwbp_version", "gwbp_last_error_string", *ARGTYPES]
 

@@ -1114,6 +1114,67 @@ int gwbp_field_compare(const gwbp_caps *caps, void *workspace, size_t workspace_
                                 xmap, planes, table, B.s);
 }
 
+// the shape contract of the decode-loss kernels: what they are not built for is unsupported, not invalid
+static int check_decode_shape(const char *what, int32_t d, int32_t D)
+{
+    if (d < 16 || d > 128 || d % 16)
+        return set_error(GWBP_EUNSUPPORTED, "%s: d must be a multiple of 16 in [16, 128] (got %d)", what, (int)d);
+    if (D < 16 || D > GWBP_PCA_MAX_D || D % 16)
+        return set_error(GWBP_EUNSUPPORTED, "%s: D must be a multiple of 16 in [16, %d] (got %d)", what, GWBP_PCA_MAX_D, (int)D);
+    return GWBP_OK;
+}
+
+int gwbp_decode_loss_workspace_size(int32_t d, int32_t D, size_t *bytes)
+{
+    const int rc = check_decode_shape("decode_loss_workspace_size", d, D);
+    if (rc)
+        return rc;
+    if (!bytes)
+        return set_error(GWBP_EINVAL, "decode_loss_workspace_size: null bytes");
+    *bytes = decode_loss_workspace_bytes(d, D);
+    return GWBP_OK;
+}
+
+int gwbp_decode_loss(int32_t height, int32_t width, int32_t d, int32_t D, const float *R, int64_t ldr, const float *C, int64_t ldc,
+                     const void *map, int32_t map_type, int64_t ms_y, int64_t ms_x, const gwbp_pixel_weights *pixel_weights,
+                     int32_t loss_kind, float scale, float *GR, int64_t ldg, float *GC, int64_t ldgc, double *table, void *workspace,
+                     size_t workspace_bytes, void *stream)
+{
+    // the pixel weights first (as every call that takes them), then the shape contract, then each kind of argument once
+    PixW Pw;
+    const PixW *pw;
+    int rc = check_pixel_weights(pixel_weights, &Pw, &pw);
+    if (rc || (rc = check_decode_shape("decode_loss", d, D)))
+        return rc;
+    if (height < 0 || width < 0)
+        return set_error(GWBP_EINVAL, "decode_loss: negative image size %d x %d", (int)width, (int)height);
+    const int64_t P = (int64_t)height * width;
+    if (P > GWBP_DECODE_MAX_PIXELS)
+        return set_error(GWBP_EUNSUPPORTED, "decode_loss: %lld pixels exceed GWBP_DECODE_MAX_PIXELS = %d", (long long)P,
+                         GWBP_DECODE_MAX_PIXELS);
+    if (!known_map_type(map_type))
+        return set_error(GWBP_EINVAL, "decode_loss: unknown map type %d", (int)map_type);
+    if (loss_kind != GWBP_LOSS_L1 && loss_kind != GWBP_LOSS_L2)
+        return set_error(GWBP_EINVAL, "decode_loss: unknown loss kind %d", (int)loss_kind);
+    if (ldr < d || ldg < d || ldc < D || ldgc < D)
+        return set_error(GWBP_EINVAL, "decode_loss: row strides (R %lld, GR %lld, C %lld, GC %lld) below d = %d / D = %d",
+                         (long long)ldr, (long long)ldg, (long long)ldc, (long long)ldgc, (int)d, (int)D);
+    if (ms_y < 0 || ms_x < 0)
+        return set_error(GWBP_EINVAL, "decode_loss: negative map strides (%lld %lld)", (long long)ms_y, (long long)ms_x);
+    if (!C || !GC || !table || !workspace || (P > 0 && (!R || !map || !GR)))
+        return set_error(GWBP_EINVAL, "decode_loss: null R, C, map, GR, GC, table or workspace");
+    if ((reinterpret_cast<uintptr_t>(R) & 3) || (reinterpret_cast<uintptr_t>(C) & 3) || (reinterpret_cast<uintptr_t>(GR) & 3) ||
+        (reinterpret_cast<uintptr_t>(GC) & 3) || (reinterpret_cast<uintptr_t>(map) & (map_type == GWBP_MAP_F32 ? 3 : 1)))
+        return set_error(GWBP_EINVAL, "decode_loss: R, C, GR and GC must be 4-B aligned, the map to its element type");
+    if ((reinterpret_cast<uintptr_t>(table) & 7) || (reinterpret_cast<uintptr_t>(workspace) & 7))
+        return set_error(GWBP_EINVAL, "decode_loss: table and workspace must be 8-B aligned");
+    const size_t need = decode_loss_workspace_bytes(d, D);
+    if (workspace_bytes < need)
+        return set_error(GWBP_EWORKSPACE, "decode_loss: workspace has %zu bytes, needs %zu", workspace_bytes, need);
+    return launch_decode_loss(height, width, d, D, R, ldr, C, ldc, map, map_type, ms_y, ms_x, pw, loss_kind == GWBP_LOSS_L2, scale,
+                              GR, ldg, GC, ldgc, table, workspace, as_stream(stream));
+}
+
 int gwbp_accumulate_stats(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, gwbp_stats *accum,
                           void *stream)
 {

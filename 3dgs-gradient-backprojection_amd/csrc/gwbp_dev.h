@@ -266,6 +266,12 @@ size_t field_compare_scratch_bytes(int n_tiles);
 int launch_field_compare(const Layout &L, const Ws &W, const ViewDev &V, const float *feats, int64_t ldf, int D, const void *map,
                          int mt, int64_t ms_y, int64_t ms_x, int lr_h, int lr_w, const int32_t *ymap, const int32_t *xmap,
                          float *planes, double *table, hipStream_t s);
+// decode, compare and the gradients back through the decoder of a rendered latent field (decode_loss.hip); table [8] float64; ws:
+// the caller's decode_loss_workspace_bytes(d, D) bytes
+size_t decode_loss_workspace_bytes(int d, int D);
+int launch_decode_loss(int H, int W, int d, int D, const float *R, int64_t ldr, const float *C, int64_t ldc, const void *map, int mt,
+                       int64_t ms_y, int64_t ms_x, const PixW *pw, int l2, float scale, float *GR, int64_t ldg, float *GC,
+                       int64_t ldgc, double *table, void *ws, hipStream_t s);
 int launch_encode_map(const float *feats, int64_t fs_y, int64_t fs_x, int H, int W, int K, const float *enc, int n_out,
                       float *out, int workgroups, hipStream_t s);
 int launch_finalize(int64_t N, int D, const float *F, const float *d, float *out, hipStream_t s);

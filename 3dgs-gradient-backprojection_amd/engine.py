@@ -870,6 +870,76 @@ class Engine:
                    self._stream())
         return planes, table
 
+    def _decode_workspace(self, d: int, D: int):
+        """The slice partials of gwbp_decode_loss: a function of (d, D) alone, kept between calls (one buffer serves every call of
+        this engine: they run in stream order), made on the stream this engine's kernels run on."""
+        need = c_size_t(0)
+        self._call("gwbp_decode_loss_workspace_size", d, D, byref(need))
+        ws = getattr(self, "_decode_ws", None)
+        if ws is None or ws.numel() < need.value:
+            with self._on_stream():
+                ws = self._decode_ws = torch.empty(int(need.value), dtype=torch.uint8, device=self.device)
+        return ws
+
+    def decode_loss(self, rendered, decoder, fmap, loss: str = "l1", scale: Optional[float] = None,
+                    pixel_weights: Optional[torch.Tensor] = None, grad_rendered: Optional[torch.Tensor] = None):
+        """Decode, compare and both gradients of one view of a latent field in one call (gwbp_decode_loss; no [H, W, D] tensor):
+        with y = rendered @ decoder, e = y - fmap and w_p = scale * pixel_weights[p],
+            loss = sum w_p |e| ("l1") or sum w_p e^2 ("l2"), grad_rendered = d loss / d rendered [H, W, d],
+            grad_decoder = d loss / d decoder [d, D].
+        Returns (loss, grad_rendered, grad_decoder, table): loss a float64 0-d device tensor (= table[0]), table float64 [8] =
+        loss, n_pixels, n_bad, P, d, D, 0, 0.  A pixel whose map row holds a non-finite value adds nothing anywhere, has a zero
+        gradient row and counts in n_bad.
+        rendered: float32 [H, W, d], d % 16 == 0, 16 <= d <= 128 (rows of another layout are copied once).  decoder: float32
+        [d, D], D % 16 == 0, 16 <= D <= 2048.  fmap: [H, W, D] float32 / float16 / bfloat16 read as stored, unit channel stride,
+        any non-negative pixel strides.  pixel_weights: [H, W] as blend_weighted takes it.  grad_rendered: the float32 [H, W, d]
+        tensor to fill; it may be `rendered` itself."""
+        if loss not in _lib.LOSS_KINDS:
+            raise GwbpError(f"loss must be 'l1' or 'l2', got {loss!r}")
+        for t, name in ((rendered, "rendered"), (decoder, "decoder")):
+            if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or t.device.index != self._dev_index:
+                raise GwbpError(f"{name} must be a float32 HIP tensor on cuda:{self._dev_index} (there is no CPU path)")
+        if rendered.dim() != 3 or decoder.dim() != 2 or rendered.shape[2] != decoder.shape[0]:
+            raise GwbpError(f"rendered must be [H, W, d] and decoder [d, D], got {tuple(rendered.shape)} and {tuple(decoder.shape)}")
+        H, W, d = (int(v) for v in rendered.shape)
+        D = int(decoder.shape[1])
+        if not torch.is_tensor(fmap) or fmap.dim() != 3 or tuple(fmap.shape) != (H, W, D):
+            raise GwbpError(f"the feature map must be [H, W, D] = [{H}, {W}, {D}], got "
+                            f"{tuple(fmap.shape) if torch.is_tensor(fmap) else type(fmap).__name__}")
+        if fmap.dtype not in MAP_TYPES or not fmap.is_cuda or fmap.device.index != self._dev_index:
+            raise GwbpError(f"the feature map must be float32, float16 or bfloat16 on cuda:{self._dev_index}, got {fmap.dtype} "
+                            f"on {fmap.device}")
+        sy, sx, sc = fmap.stride()
+        if sc != 1 or sy < 0 or sx < 0:
+            raise GwbpError("the map's channels must be contiguous (unit last stride) and its pixel strides non-negative")
+
+        def flat_rows(t):  # [H, W, d] whose pixel p = y W + x lies at p * row stride
+            return t.stride(2) == 1 and t.stride(1) >= d and (H <= 1 or t.stride(0) == W * t.stride(1))
+        with self._on_stream():
+            if not flat_rows(rendered):
+                rendered = rendered.contiguous()
+            if decoder.stride(1) != 1 or decoder.stride(0) < D:
+                decoder = decoder.contiguous()
+            if grad_rendered is None:
+                grad_rendered = torch.empty(H, W, d, device=self.device)
+            elif (not torch.is_tensor(grad_rendered) or grad_rendered.dtype != torch.float32 or not grad_rendered.is_cuda
+                  or tuple(grad_rendered.shape) != (H, W, d) or not flat_rows(grad_rendered)):
+                raise GwbpError(f"grad_rendered must be a float32 HIP tensor [{H}, {W}, {d}] with flat pixel rows")
+            grad_decoder = torch.empty(d, D, device=self.device)
+            table = torch.empty(8, dtype=torch.float64, device=self.device)
+        pw = None
+        if pixel_weights is not None:
+            class _Shape:
+                height, width = H, W
+            pw = byref(self.pixel_weights(pixel_weights, _Shape))
+        ws = self._decode_workspace(d, D)
+        self._call("gwbp_decode_loss", H, W, d, D, ptr(rendered), c_int64(rendered.stride(1)), ptr(decoder),
+                   c_int64(decoder.stride(0)), ptr(fmap), MAP_TYPES[fmap.dtype], c_int64(sy), c_int64(sx), pw,
+                   _lib.LOSS_KINDS[loss], c_float(1.0 if scale is None else float(scale)), ptr(grad_rendered),
+                   c_int64(grad_rendered.stride(1)), ptr(grad_decoder), c_int64(D), ptr(table), ptr(ws), c_size_t(ws.numel()),
+                   self._stream())
+        return table[0], grad_rendered, grad_decoder, table
+
     def render_pixels(self, view, colors, want_alphas=True):
         """Pixel-parallel forward render for 1..32 channels; needs project + bin_sort of `view` (not the weight store)."""
         colors = _req(colors, "colors")

@@ -232,6 +232,10 @@ def load_checkpoint(checkpoint: str, data_dir: str, format: Optional[str] = "gsp
         p = model["splats"]
         splats = {"active_sh_degree": 3, "means": p["means"], "features_dc": p["sh0"], "features_rest": p["shN"],
                   "scaling": p["scales"], "rotation": p["quats"], "opacity": p["opacities"]}
+        # a Feature-3DGS checkpoint (utils.load_checkpoint_f3dgs, utils.py:157-158): the latent table and its decoder, as
+        # decoded_field.fit_decoded_field returns them; a checkpoint without them loads exactly as before
+        if "features" in p and "conv" in p:
+            splats["conv"], splats["features"] = p["conv"], p["features"]
     elif format == "ply":
         splats = read_gaussian_ply(checkpoint)
     else:

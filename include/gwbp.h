@@ -624,6 +624,39 @@ GWBP_API int gwbp_field_compare(const gwbp_caps *caps, void *workspace, size_t w
                                 int64_t ms_x, int32_t lr_h, int32_t lr_w, const int32_t *ymap, const int32_t *xmap, float *planes,
                                 double *table, void *stream);
 
+/* ---- a latent field and its decoder: decode, compare and the gradients back through the decoder, in one call ----------------------
+ * Between the render of a [N, d] latent table and the scatter of its gradient (gwbp_render, gwbp_scatter).  Takes no workspace of a
+ * view: R [P, d] are the rendered rows of the P = height * width pixels (row-major, row stride ldr), C [d, D] the decoder (row
+ * stride ldc), map the view's [height, width, D] map (GWBP_MAP_*, unit channel stride, pixel (y, x) at map + y * ms_y + x * ms_x,
+ * strides in elements, >= 0), pixel_weights an optional per-pixel weight c_p (NULL: 1).  With w_p = scale * c_p (one rounding),
+ *     y[p, j] = sum_k R[p, k] C[k, j]      e = y - map[p, j]
+ *     g = w_p sign(e), sign(0) = 0  (GWBP_LOSS_L1)    |    g = w_p (e + e)  (GWBP_LOSS_L2)
+ *     table[0] = loss = sum w_p |e|  |  sum w_p e^2                                      (float64)
+ *     GR[p, :] = sum_j g[p, j] C[:, j]     float [P, d], row stride ldg; GR may be R itself
+ *     GC[k, j] = sum_p R[p, k] g[p, j]     float [d, D], row stride ldgc
+ *     table    = loss, n_pixels (not bad), n_bad, P, d, D, 0, 0                          (double [8], overwritten)
+ * No [P, D] array is made: two kernels derive g by the same fused-multiply-add chain.  A pixel whose map row holds a non-finite
+ * element is BAD: it adds nothing to the loss, GR or GC, its GR row is zero, and it counts in n_bad.
+ * Arithmetic: every product sum is one chain of fp32 fused multiply-adds (v_mfma_f32_16x16x4_f32) from +0 in an order fixed by
+ * (d, D) and the slice plan, which depends on P alone: 64-pixel blocks, ceil(blocks / GWBP_DECODE_MAX_SLICES) blocks per slice; GC
+ * and the loss are the slices' partials added in ascending order in float64 (csrc/decode_loss.hip gives every order).  No atomics:
+ * two calls give the same bits, and they do not depend on alignment, strides, the map's type beyond its values, or aliasing.
+ * workspace: gwbp_decode_loss_workspace_size(d, D) bytes (the slices' partials: a function of d and D alone, never of P), 8-B
+ * aligned, free again when the call's kernels have run.
+ * GWBP_EUNSUPPORTED (before anything else but the pixel weights): d % 16 != 0 or d outside [16, 128], D % 16 != 0 or D outside
+ * [16, GWBP_PCA_MAX_D], more than GWBP_DECODE_MAX_PIXELS pixels.  GWBP_EINVAL: negative height or width, an unknown map type or
+ * loss kind, row strides below the row lengths, negative map strides, null or misaligned C, GC, table or workspace -- and R, map or
+ * GR when P > 0 (4 B; the map to its element type; table and workspace 8 B).  GWBP_EWORKSPACE: a workspace below the size. */
+#define GWBP_LOSS_L1 0
+#define GWBP_LOSS_L2 1
+#define GWBP_DECODE_MAX_SLICES 512
+#define GWBP_DECODE_MAX_PIXELS (1 << 25)
+GWBP_API int gwbp_decode_loss_workspace_size(int32_t d, int32_t D, size_t *bytes);
+GWBP_API int gwbp_decode_loss(int32_t height, int32_t width, int32_t d, int32_t D, const float *R, int64_t ldr, const float *C,
+                              int64_t ldc, const void *map, int32_t map_type, int64_t ms_y, int64_t ms_x,
+                              const gwbp_pixel_weights *pixel_weights, int32_t loss_kind, float scale, float *GR, int64_t ldg,
+                              float *GC, int64_t ldgc, double *table, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Adds this view's counters into `accum` (device, gwbp_stats) -- used by bench/driver to total pairs. */
 GWBP_API int gwbp_accumulate_stats(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, gwbp_stats *accum,
                           void *stream);
