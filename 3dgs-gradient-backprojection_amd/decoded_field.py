@@ -20,7 +20,9 @@ from typing import Callable, Dict, Optional
 import torch
 
 from ._lib import GwbpError
-from .label_render import _raster_kw
+from ._views import front, require_device
+from ._views import raster_kw as merged_raster_kw
+from .rasterization import PIXEL_RENDER_MAX_DIM, engine_on, get_engine
 
 REDUCTIONS = ("mean", "sum")
 
@@ -37,21 +39,12 @@ def _literal(rendered, decoder, target, loss, pixel_weights, reduction):
     return t.mean() if reduction == "mean" else t.sum()
 
 
-def _engine_on(device):
-    """An engine of this device for a call that needs no view workspace: one rasterization() already made if there is one."""
-    from .rasterization import _ENGINES, get_engine
-    for key, eng in _ENGINES.items():
-        if key[0] == str(device):
-            return eng
-    return get_engine(device, 1, 16, 16)
-
-
 class _DecodedLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rendered, decoder, target, loss, pixel_weights, reduction):
         h, w, _ = rendered.shape
         scale = 1.0 / max(1, h * w * decoder.shape[1]) if reduction == "mean" else 1.0
-        value, g_rendered, g_decoder, _ = _engine_on(rendered.device).decode_loss(
+        value, g_rendered, g_decoder, _ = engine_on(rendered.device).decode_loss(
             rendered.detach(), decoder.detach(), target, loss=loss, scale=scale, pixel_weights=pixel_weights)
         ctx.save_for_backward(rendered, decoder, target, g_rendered, g_decoder)
         ctx.args = (loss, pixel_weights, reduction)
@@ -106,20 +99,17 @@ def decoded_field_gradients(means, quats, scales, opacities, latents, decoder, f
     decoded_loss(rasterization(..., latents, ...)[0], decoder, feature_map).backward() leaves in latents.grad and decoder.grad.
     The engine and the front cache are rasterization()'s.  raster_kw: near_plane, far_plane, eps2d, radius_clip, camera_model,
     rasterize_mode."""
-    from .rasterization import PIXEL_RENDER_MAX_DIM, _run_front, get_engine
     if reduction not in REDUCTIONS:
         raise GwbpError(f"reduction must be 'mean' or 'sum', got {reduction!r}")
-    if not means.is_cuda:
-        raise GwbpError("decoded_field_gradients() needs HIP tensors (there is no CPU path)")
+    require_device("decoded_field_gradients", means)
     if not torch.is_tensor(latents) or latents.dim() != 2 or latents.shape[0] != means.shape[0] or latents.dtype != torch.float32:
         raise GwbpError(f"latents must be float32 [N, d] with N = {means.shape[0]}")
-    kw = _raster_kw("decoded_field_gradients", raster_kw)
+    kw = merged_raster_kw("decoded_field_gradients", raster_kw)
     width, height = int(width), int(height)
     n, d = latents.shape
-    eng = get_engine(means.device, n, width, height)
-    view = eng.view(viewmat, K, width, height, **kw)
-    eng.set_narrow_scatter(True)  # d <= 128: the 128-channel scatter kernel, as rasterization()'s backward picks it
-    _run_front(eng, view, means, quats, scales, opacities, False, False)
+    # d <= 128: the 128-channel scatter kernel, as rasterization()'s backward picks it (the flag must be in place before the blend)
+    get_engine(means.device, n, width, height).set_narrow_scatter(True)
+    eng, view, _ = front("decoded_field_gradients", means, quats, scales, opacities, viewmat, K, width, height, kw, want_store=True)
     table_in = latents.detach().contiguous()
     rendered = eng.render(view, table_in) if d > PIXEL_RENDER_MAX_DIM else eng.render_pixels(view, table_in)[0]
     scale = 1.0 / max(1, height * width * int(decoder.shape[1])) if reduction == "mean" else 1.0
@@ -143,8 +133,7 @@ def fit_decoded_field(means, quats, scales, opacities, viewmats, K, width, heigh
     a torch.rand decoder (drawn on the host from the same seeded generator) -- or (latents0, decoder0) to continue from.
     pixel_weight_fn(v): the view's [H, W] weights or None.  callback(step, loss, latents, decoder) runs after every step with the
     loss as a device tensor.  viewmats [V, 4, 4]; K [3, 3] or [V, 3, 3]."""
-    if not means.is_cuda:
-        raise GwbpError("fit_decoded_field() needs HIP tensors (there is no CPU path)")
+    require_device("fit_decoded_field", means)
     dev, n = means.device, means.shape[0]
     gen = torch.Generator().manual_seed(int(seed))
     if init is None:

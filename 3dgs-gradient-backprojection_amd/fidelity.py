@@ -23,9 +23,9 @@ from typing import Callable, Dict, Optional
 import torch
 
 from ._lib import GwbpError
-from .engine import Engine
-from .label_render import _raster_kw
-from .transfer import _rows
+from ._views import front, require_device, rows, score_views
+from ._views import raster_kw as merged_raster_kw
+from .rasterization import get_engine
 
 MAX_D = 2048  # GWBP_PCA_MAX_D
 PLANES = ("dot", "rr", "mm", "l1", "l2", "cosine")
@@ -33,9 +33,8 @@ TABLE_COLUMNS = ("sum_cosine", "sum_l1", "sum_l2", "sum_mm", "n_valid", "n_bad",
 
 
 def _field(fn: str, means, features) -> torch.Tensor:
-    if not means.is_cuda:
-        raise GwbpError(f"{fn}() needs HIP tensors (there is no CPU path)")
-    x = _rows(features, "features")
+    require_device(fn, means)
+    x = rows(features, "features")
     if x.shape[0] != means.shape[0]:
         raise GwbpError(f"{x.shape[0]} feature rows for {means.shape[0]} Gaussians")
     if not 1 <= x.shape[1] <= MAX_D:
@@ -52,7 +51,7 @@ def _check_upsample(fn: str, upsample: Optional[str]) -> None:
         raise GwbpError(f"upsample must be None or 'nearest', got {upsample!r}")
 
 
-def _map_and_index(fn: str, eng: Engine, fmap, d: int, width: int, height: int, upsample: Optional[str]):
+def _map_and_index(fn: str, eng, fmap, d: int, width: int, height: int, upsample: Optional[str]):
     """(map, index) as Engine.field_compare takes them: the full-resolution [H, W, D] map, or with upsample="nearest" the
     low-resolution [h, w, D] map and F.interpolate(mode="nearest")'s index maps."""
     if not torch.is_tensor(fmap) or fmap.dim() != 3:
@@ -78,15 +77,14 @@ def render_field_agreement(means, quats, scales, opacities, features, feature_ma
     row holds a non-finite value is NaN in every plane but alpha.  raster_kw: near_plane, far_plane, eps2d, radius_clip,
     camera_model, rasterize_mode.  The engine and the front cache are rasterization()'s: after a rendered frame of the same view
     nothing is projected or blended again."""
-    from .rasterization import _run_front, get_engine
     _check_upsample("render_field_agreement", upsample)
     x = _field("render_field_agreement", means, features)
-    kw = _raster_kw("render_field_agreement", raster_kw)
+    kw = merged_raster_kw("render_field_agreement", raster_kw)
     width, height = int(width), int(height)
-    eng = get_engine(means.device, means.shape[0], width, height)
-    fmap, index = _map_and_index("render_field_agreement", eng, feature_map, x.shape[1], width, height, upsample)
-    view = eng.view(viewmat, K, width, height, **kw)
-    _, _, alphas, _ = _run_front(eng, view, means, quats, scales, opacities, True, False)
+    fmap, index = _map_and_index("render_field_agreement", get_engine(means.device, means.shape[0], width, height), feature_map,
+                                 x.shape[1], width, height, upsample)
+    eng, view, alphas = front("render_field_agreement", means, quats, scales, opacities, viewmat, K, width, height, kw,
+                              want_alphas=True, want_store=True)
     planes, _ = eng.field_compare(view, x, fmap, index=index)
     out = {name: planes[i] for i, name in enumerate(PLANES)}
     out["alpha"] = alphas
@@ -102,35 +100,20 @@ def score_field_views(means, quats, scales, opacities, features, viewmats, K, wi
     or None to skip the view (its row stays zero).  viewmats [V, 4, 4]; K [3, 3] or [V, 3, 3].  No plane is written and no
     [H, W] tensor allocated; nothing inside the loop waits for the device: the workspace's capacity is checked once behind it
     (an overflow grows the workspace and runs the views again)."""
-    from .rasterization import get_engine
     _check_upsample("score_field_views", upsample)
     x = _field("score_field_views", means, features)
-    kw = _raster_kw("score_field_views", raster_kw)
-    width, height = int(width), int(height)
-    n_views = viewmats.shape[0]
-    vm_host, K_host = viewmats.detach().cpu(), K.detach().cpu()
-    eng = get_engine(means.device, means.shape[0], width, height)
-    for _ in range(6):
-        table = torch.zeros(n_views, 8, dtype=torch.float64, device=means.device)
-        accum = torch.zeros(32, dtype=torch.uint8, device=means.device)
-        eng.front_cache = None  # the workspace holds the last scored view from here on, and no stats of it
-        for v in range(n_views):
-            fmap = feature_fn(v)
-            if fmap is None:
-                continue
-            fmap, index = _map_and_index("score_field_views", eng, fmap, x.shape[1], width, height, upsample)
-            view = eng.view(vm_host[v], K_host if K_host.dim() == 2 else K_host[v], width, height, **kw)
-            eng.project(view, means, quats, scales, opacities)
-            eng.bin_sort(view)
-            eng.blend_weights(view)
-            eng.generation += 1
-            eng.field_compare(view, x, fmap, index=index, want_planes=False, table=table[v])
-            eng.accumulate_stats(accum)
-        stats = Engine.decode_stats(accum)
-        if not stats["overflow"]:
-            return table
-        eng.grow(stats, views=n_views)
-    raise RuntimeError(f"score_field_views: no pass over the views finished without a workspace overflow (flags {stats['overflow']})")
+    width, height, device = int(width), int(height), means.device
+
+    def per_view(eng, v, table):
+        fmap = feature_fn(v)
+        if fmap is None:
+            return None
+        fmap, index = _map_and_index("score_field_views", eng, fmap, x.shape[1], width, height, upsample)
+        return lambda view: eng.field_compare(view, x, fmap, index=index, want_planes=False, table=table[v])
+
+    return score_views("score_field_views", means, quats, scales, opacities, viewmats, K, width, height, raster_kw,
+                       make_result=lambda: torch.zeros(viewmats.shape[0], 8, dtype=torch.float64, device=device),
+                       per_view=per_view, blend=True)
 
 
 def field_fidelity(table) -> Dict[str, object]:

@@ -20,30 +20,9 @@ from typing import Callable, Dict, Optional, Sequence
 import torch
 
 from ._lib import GwbpError
-from .engine import Engine
+from ._views import front, score_views
 
 C0 = 0.28209479177387814  # the SH basis' constant term, 1 / sqrt(4 pi)
-_RASTER_KW = dict(near_plane=0.01, far_plane=1e10, eps2d=0.3, radius_clip=0.0, camera_model="pinhole", rasterize_mode="classic")
-
-
-def _raster_kw(fn: str, raster_kw: dict) -> dict:
-    unknown = set(raster_kw) - set(_RASTER_KW)
-    if unknown:
-        raise TypeError(f"{fn}() got unexpected keyword arguments {sorted(unknown)}")
-    return dict(_RASTER_KW, **raster_kw)
-
-
-def _front(fn: str, means, quats, scales, opacities, viewmat, K, width, height, raster_kw):
-    """(engine, view) with the view projected and sorted: rasterization()'s engine and front cache, as probe_pixels uses them."""
-    from .rasterization import _run_front, get_engine
-    if not means.is_cuda:
-        raise GwbpError(f"{fn}() needs HIP tensors (there is no CPU path)")
-    kw = _raster_kw(fn, raster_kw)
-    width, height = int(width), int(height)
-    eng = get_engine(means.device, means.shape[0], width, height)
-    view = eng.view(viewmat, K, width, height, **kw)
-    _run_front(eng, view, means, quats, scales, opacities, False, False, want_store=False)
-    return eng, view
 
 
 def render_label_maps(means, quats, scales, opacities, labels, num_classes: int, viewmat, K, width, height, **raster_kw):
@@ -52,7 +31,7 @@ def render_label_maps(means, quats, scales, opacities, labels, num_classes: int,
     [N, num_classes] table, which is never built.  labels: integer [N] on the device; a label outside [0, num_classes) adds to
     alphas and to no class.  raster_kw: near_plane, far_plane, eps2d, radius_clip, camera_model, rasterize_mode.  The engine and
     the front cache are rasterization()'s: a label render after a rendered frame of the same view projects nothing."""
-    eng, view = _front("render_label_maps", means, quats, scales, opacities, viewmat, K, width, height, raster_kw)
+    eng, view, _ = front("render_label_maps", means, quats, scales, opacities, viewmat, K, width, height, raster_kw)
     maps, alphas, _, _ = eng.render_labels(view, labels, num_classes)
     return maps, alphas
 
@@ -61,7 +40,7 @@ def render_label_argmax(means, quats, scales, opacities, labels, num_classes: in
                         min_opacity: float = 0.0, **raster_kw):
     """The 2-D segmentation of one view, int32 [H, W]: per pixel the class of the largest opacity (the lowest index among equals),
     -1 where no class contributes or that opacity lies below min_opacity.  No [H, W, num_classes] image is made."""
-    eng, view = _front("render_label_argmax", means, quats, scales, opacities, viewmat, K, width, height, raster_kw)
+    eng, view, _ = front("render_label_argmax", means, quats, scales, opacities, viewmat, K, width, height, raster_kw)
     return eng.render_labels(view, labels, num_classes, want_maps=False, want_alphas=False, want_argmax=True,
                              min_opacity=min_opacity)[2]
 
@@ -75,33 +54,18 @@ def score_label_views(means, quats, scales, opacities, labels, num_classes: int,
     whose gt_type is "automatic"); a skipped view's row stays zero.  Values of the map outside [0, num_classes) match no class.
     viewmats [V, 4, 4]; K [3, 3] or [V, 3, 3].  Nothing inside the loop waits for the device: the workspace's capacity is
     checked once behind it (an overflow grows the workspace and runs the views again)."""
-    from .rasterization import get_engine
-    if not means.is_cuda:
-        raise GwbpError("score_label_views() needs HIP tensors (there is no CPU path)")
-    kw = _raster_kw("score_label_views", raster_kw)
-    width, height, n_classes = int(width), int(height), int(num_classes)
-    n_views = viewmats.shape[0]
-    vm_host, K_host = viewmats.detach().cpu(), K.detach().cpu()
-    eng = get_engine(means.device, means.shape[0], width, height)
-    for _ in range(6):
-        counts = torch.zeros(n_views, max(n_classes, 0), 3, dtype=torch.int64, device=means.device)
-        accum = torch.zeros(32, dtype=torch.uint8, device=means.device)
-        eng.front_cache = None  # the workspace holds the last scored view from here on, and no stats of it
-        for v in range(n_views):
-            gt = gt_fn(v)
-            if gt is None:
-                continue
-            view = eng.view(vm_host[v], K_host if K_host.dim() == 2 else K_host[v], width, height, **kw)
-            eng.project(view, means, quats, scales, opacities)
-            eng.bin_sort(view)
-            eng.generation += 1
-            eng.render_labels(view, labels, n_classes, want_maps=False, want_alphas=False, gt=gt, counts=counts[v], cut=cut)
-            eng.accumulate_stats(accum)
-        stats = Engine.decode_stats(accum)
-        if not stats["overflow"]:
-            return counts
-        eng.grow(stats, views=n_views)
-    raise RuntimeError(f"score_label_views: no pass over the views finished without a workspace overflow (flags {stats['overflow']})")
+    n_classes, device = int(num_classes), means.device
+
+    def per_view(eng, v, counts):
+        gt = gt_fn(v)
+        if gt is None:
+            return None
+        return lambda view: eng.render_labels(view, labels, n_classes, want_maps=False, want_alphas=False, gt=gt, counts=counts[v],
+                                              cut=cut)
+
+    return score_views("score_label_views", means, quats, scales, opacities, viewmats, K, width, height, raster_kw,
+                       make_result=lambda: torch.zeros(viewmats.shape[0], max(n_classes, 0), 3, dtype=torch.int64, device=device),
+                       per_view=per_view, blend=False)
 
 
 def miou_recall(counts, classes: Optional[Sequence[int]] = None, n_present: Optional[int] = None) -> Dict[str, object]:

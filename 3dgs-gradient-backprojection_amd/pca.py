@@ -20,7 +20,7 @@ from typing import Iterator, Optional
 import torch
 
 from ._lib import GwbpError, check, lib, ptr
-from .transfer import _ld, _rows, _run
+from ._views import ld, rows, run
 
 MAX_K = 16            # GWBP_PCA_MAX_K
 MAX_D = 2048          # GWBP_PCA_MAX_D
@@ -88,15 +88,15 @@ def _covariance(features: torch.Tensor):
     """(mean [D] float32, covariance [D, D] float64, both on the device) of the rows: gwbp_column_means + gwbp_centered_gram,
     the Gram over N - 1."""
     _check_sizes(features, None, 2)
-    x = _rows(features, "features")
+    x = rows(features, "features")
     n, d = x.shape
     need = C.c_size_t(0)
     check(lib().gwbp_pca_workspace_size(n, d, C.byref(need)), "gwbp_pca_workspace_size")
     ws = torch.empty(max(need.value, 8), dtype=torch.uint8, device=x.device)
     mean = torch.empty(d, dtype=torch.float32, device=x.device)
     gram = torch.empty(d, d, dtype=torch.float64, device=x.device)
-    _run("gwbp_column_means", x.device, C.c_int64(n), d, ptr(x), C.c_int64(_ld(x)), ptr(mean), ptr(ws), ws.numel())
-    _run("gwbp_centered_gram", x.device, C.c_int64(n), d, ptr(x), C.c_int64(_ld(x)), ptr(mean), ptr(gram), ptr(ws), ws.numel())
+    run("gwbp_column_means", x.device, C.c_int64(n), d, ptr(x), C.c_int64(ld(x)), ptr(mean), ptr(ws), ws.numel())
+    run("gwbp_centered_gram", x.device, C.c_int64(n), d, ptr(x), C.c_int64(ld(x)), ptr(mean), ptr(gram), ptr(ws), ws.numel())
     return mean, gram / float(n - 1)
 
 
@@ -110,7 +110,7 @@ def _project(x: torch.Tensor, mean: torch.Tensor, components: torch.Tensor):
     components = components.to(device=x.device, dtype=torch.float32).contiguous()
     y = torch.empty(n, k, dtype=torch.float32, device=x.device)
     mm = torch.empty(-(-n // PROJECT_ROWS), 2, dtype=torch.float32, device=x.device)
-    _run("gwbp_pca_project", x.device, C.c_int64(n), d, k, ptr(x), C.c_int64(_ld(x)), ptr(mean), ptr(components), ptr(y), ptr(mm))
+    run("gwbp_pca_project", x.device, C.c_int64(n), d, k, ptr(x), C.c_int64(ld(x)), ptr(mean), ptr(components), ptr(y), ptr(mm))
     return y, mm
 
 
@@ -128,7 +128,7 @@ def fit_pca(features: torch.Tensor, n_components: int = 3) -> PCABasis:
 def pca_transform(features: torch.Tensor, basis: PCABasis) -> torch.Tensor:
     """pca.transform(features): Y [N, k] = (features - mean) @ components.T in one pass over the rows (exact fp32)."""
     _check_sizes(features, None, 1)
-    return _project(_rows(features, "features"), basis.mean, basis.components)[0]
+    return _project(rows(features, "features"), basis.mean, basis.components)[0]
 
 
 def pca_colors(features: torch.Tensor, basis: Optional[PCABasis] = None):
@@ -138,10 +138,10 @@ def pca_colors(features: torch.Tensor, basis: Optional[PCABasis] = None):
     if basis is None:
         basis = fit_pca(features, 3)
     _check_sizes(features, None, 1)
-    y, mm = _project(_rows(features, "features"), basis.mean, basis.components)
+    y, mm = _project(rows(features, "features"), basis.mean, basis.components)
     lo_hi = torch.stack([mm[:, 0].min(), mm[:, 1].max()])
     colors = torch.empty_like(y)
-    _run("gwbp_pca_colors", y.device, C.c_int64(y.numel()), ptr(y), ptr(lo_hi), ptr(colors))
+    run("gwbp_pca_colors", y.device, C.c_int64(y.numel()), ptr(y), ptr(lo_hi), ptr(colors))
     return colors, lo_hi[0], lo_hi[1]
 
 
@@ -170,7 +170,7 @@ def _pca_frames(means, quats, scales, opacities, features, viewmats, K, width, h
     colors, lo, hi = pca_colors(features, basis)
     offset = None
     if mode == "renderings":
-        x = _rows(features, "features")
+        x = rows(features, "features")
         colors = _project(x, torch.zeros_like(basis.mean), basis.components)[0]
         offset = (basis.components.double() @ basis.mean.double()).float().to(x.device)
     Ks = K if K.dim() == 3 else K[None].expand(viewmats.shape[0], 3, 3)

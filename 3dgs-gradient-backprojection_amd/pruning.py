@@ -19,7 +19,7 @@ from .engine import Engine
 from .rasterization import rasterization
 from .synthetic import view_shard
 
-_PER_GAUSSIAN = ("means", "features_dc", "features_rest", "scaling", "rotation", "opacity", "features")
+PER_GAUSSIAN = ("means", "features_dc", "features_rest", "scaling", "rotation", "opacity", "features")
 
 
 def _activated(splats: Dict[str, torch.Tensor]):
@@ -73,7 +73,7 @@ def prune_by_gradients(splats: Dict[str, torch.Tensor], viewmats: torch.Tensor, 
     splats["colmap_project"]."""
     mask = gradient_mask(splats, viewmats, K, width, height, camera_model, rasterize_mode)
     out = dict(splats)
-    for k in _PER_GAUSSIAN:
+    for k in PER_GAUSSIAN:
         if k in out:
             out[k] = out[k][mask]
     return out, mask

@@ -129,6 +129,14 @@ def get_engine(device, n: int, width: int, height: int) -> Engine:
     return eng
 
 
+def engine_on(device) -> Engine:
+    """An engine of this device for a call that needs no view workspace: one rasterization() already made if there is one."""
+    for key, eng in _ENGINES.items():
+        if key[0] == str(device):
+            return eng
+    return get_engine(device, 1, 16, 16)
+
+
 def _front_key(view, tensors):
     """Identity of a front-stage result: the view parameters and the Gaussian tensors' in-place versions and shapes.  The
     tensors THEMSELVES are kept in the cache entry and compared with `is` (_same_tensors): a (data_ptr, _version) key alone
@@ -141,7 +149,7 @@ def _same_tensors(held, tensors) -> bool:
     return held is not None and len(held) == len(tensors) and all(a is b for a, b in zip(held, tensors))
 
 
-def _run_front(eng: Engine, view, means, quats, scales, opacities, want_alphas, want_meta, want_store=True):
+def run_front(eng: Engine, view, means, quats, scales, opacities, want_alphas, want_meta, want_store=True):
     """project -> sort (-> blend) with auto-grow of the capacities (one host sync per call: this is the
     API-compatible path; the fused driver in backproject.py amortises the check).
 
@@ -185,7 +193,7 @@ class _Rasterize(torch.autograd.Function):
         # back-propagated through (backproject.py:67-72,115-129,133-147) -- the render of zeros is zeros, for any D
         if harvest is None:
             harvest = colors.requires_grad and _is_zero_table(colors)
-        proj, bins, alphas, st = _run_front(eng, view, means, quats, scales, opacities, D > PIXEL_RENDER_MAX_DIM or harvest,
+        proj, bins, alphas, st = run_front(eng, view, means, quats, scales, opacities, D > PIXEL_RENDER_MAX_DIM or harvest,
                                             holder is not None, want_store=need_store)
         if harvest:
             out = _zero_render(dev, view.height, view.width, D)  # (alphas: the blend's, kept with the front-stage result)
@@ -218,7 +226,7 @@ class _Rasterize(torch.autograd.Function):
             eng = get_engine(means.device, means.shape[0], view.width, view.height)
             eng.set_narrow_scatter(ctx.shape[1] % 256 != 0)
             eng.front_cache = None
-            _run_front(eng, view, means, quats, scales, opacities, False, False)
+            run_front(eng, view, means, quats, scales, opacities, False, False)
         # The reference keeps ONE grad tensor per colour table alive (it clones and zeroes it in place, backproject.py:130-131),
         # so a returned gradient would be ADDED to it by autograd: a 2 GB temporary, its memset and a 6 GB read-modify-write
         # per view at C2.  The scatter kernel accumulates anyway: add straight into the leaf's .grad and hand autograd nothing

@@ -21,8 +21,9 @@ from typing import Dict, Iterator, List, Optional, Tuple
 import torch
 
 from ._lib import GwbpError, ptr
-from .pruning import _PER_GAUSSIAN
-from .transfer import _ld, _rows, _run
+from ._views import front, ld, require_device, rows, run
+from ._views import raster_kw as merged_raster_kw
+from .pruning import PER_GAUSSIAN
 
 MAX_P = 32            # GWBP_QUERY_MAX_P
 MAX_D = 2048          # GWBP_PCA_MAX_D
@@ -41,7 +42,7 @@ def _prompts(prompts, d: int, device) -> torch.Tensor:
 
 
 def _query(features, prompts, n_pos: int, threshold, normalize: bool, want_mask: bool, want_scores: bool):
-    x = _rows(features, "features")
+    x = rows(features, "features")
     n, d = x.shape
     if d > MAX_D:
         raise GwbpError(f"D must be in [1, {MAX_D}], got {d}")
@@ -54,7 +55,7 @@ def _query(features, prompts, n_pos: int, threshold, normalize: bool, want_mask:
     thr = C.byref(C.c_float(float(threshold))) if threshold is not None else None
     mask = torch.empty(n, dtype=torch.uint8, device=x.device) if want_mask else None
     scores = torch.empty(n, p, dtype=torch.float32, device=x.device) if want_scores else None
-    _run("gwbp_prompt_scores", x.device, C.c_int64(n), d, p, n_pos, ptr(x), C.c_int64(_ld(x)), ptr(t), int(bool(normalize)), thr,
+    run("gwbp_prompt_scores", x.device, C.c_int64(n), d, p, n_pos, ptr(x), C.c_int64(ld(x)), ptr(t), int(bool(normalize)), thr,
          ptr(mask), ptr(scores))
     return mask, scores
 
@@ -97,15 +98,9 @@ def probe_pixels(means, quats, scales, opacities, features, viewmat, K, width, h
     H W - M pixels (click_and_segment.py:241-262).  A pixel outside the image gives zeros.  depth is gsplat's accumulated "D"
     channel, not the expected depth.  raster_kw: near_plane, far_plane, eps2d, radius_clip, camera_model, rasterize_mode.  The
     engine and the front cache are rasterization()'s: a probe after a rendered frame of the same view re-projects nothing."""
-    from .rasterization import _run_front, get_engine
-    if not means.is_cuda:
-        raise GwbpError("probe_pixels() needs HIP tensors (there is no CPU path)")
-    kw = dict(near_plane=0.01, far_plane=1e10, eps2d=0.3, radius_clip=0.0, camera_model="pinhole", rasterize_mode="classic")
-    unknown = set(raster_kw) - set(kw)
-    if unknown:
-        raise TypeError(f"probe_pixels() got unexpected keyword arguments {sorted(unknown)}")
-    kw.update(raster_kw)
-    x = _rows(features, "features")
+    require_device("probe_pixels", means)
+    kw = merged_raster_kw("probe_pixels", raster_kw)
+    x = rows(features, "features")
     if x.shape[0] != means.shape[0]:
         raise GwbpError(f"{x.shape[0]} feature rows for {means.shape[0]} Gaussians")
     if x.shape[1] > MAX_D:
@@ -113,10 +108,7 @@ def probe_pixels(means, quats, scales, opacities, features, viewmat, K, width, h
     xy = torch.as_tensor(xy, device=means.device).reshape(-1, 2).to(torch.int32)
     if not 1 <= xy.shape[0] <= MAX_PROBES:
         raise GwbpError(f"the number of probed pixels must be in [1, {MAX_PROBES}], got {xy.shape[0]}")
-    width, height = int(width), int(height)
-    eng = get_engine(means.device, means.shape[0], width, height)
-    view = eng.view(viewmat, K, width, height, **kw)
-    _run_front(eng, view, means, quats, scales, opacities, False, False, want_store=False)
+    eng, view, _ = front("probe_pixels", means, quats, scales, opacities, viewmat, K, width, height, kw)
     feats, _, alpha = eng.probe_pixels(view, xy, x, want_depth=False)
     # the depths as rasterization() computes them for its "+D" channel (one torch expression), rendered as a one-channel table
     vm = viewmat.to(means.device)
@@ -231,7 +223,7 @@ def apply_mask3d(splats: Dict[str, torch.Tensor], mask: torch.Tensor):
     out = []
     for keep in (mask, ~mask):
         cut = dict(splats)
-        for k in _PER_GAUSSIAN:
+        for k in PER_GAUSSIAN:
             if k in cut:
                 cut[k] = cut[k][keep.to(cut[k].device)]
         out.append(cut)

@@ -16,34 +16,10 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ._lib import GwbpError, check, lib, ptr
+from ._lib import GwbpError, ptr
+from ._views import ld, rows, run
 
 MAX_K = 32
-
-
-def _rows(t: torch.Tensor, name: str) -> torch.Tensor:
-    """A [rows, D] float32 device tensor with unit stride inside a row and a non-negative row stride >= D, as the kernel reads it."""
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise GwbpError(f"{name} must be a HIP tensor (no CPU fallback exists for this path)")
-    if t.dim() != 2 or t.shape[1] < 1:
-        raise GwbpError(f"{name} must be [rows, D] with D >= 1, got {tuple(t.shape)}")
-    if t.dtype in (torch.float16, torch.bfloat16):
-        t = t.float()
-    if t.dtype != torch.float32:
-        raise GwbpError(f"{name} must be float32, float16 or bfloat16, got {t.dtype}")
-    if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-        t = t.contiguous()
-    return t
-
-
-def _ld(t: torch.Tensor) -> int:
-    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])  # (the stride of a single row means nothing)
-
-
-def _run(name: str, device, *args):
-    fn = getattr(lib(), name)
-    with torch.cuda.device(device):
-        check(fn(*args, C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), name)
 
 
 def knn_search(features: torch.Tensor, sources: torch.Tensor, k: int):
@@ -54,7 +30,7 @@ def knn_search(features: torch.Tensor, sources: torch.Tensor, k: int):
     features / sources may have any row stride >= D (a field still in padded storage, a column slice of a wider tensor) and are
     read in place; a tensor whose stride within a row is not 1 is copied with .contiguous(); float16 / bfloat16 inputs are
     converted with .float().  1 <= k <= 32, k <= M."""
-    q, s = _rows(features, "features"), _rows(sources, "sources")
+    q, s = rows(features, "features"), rows(sources, "sources")
     if q.shape[1] != s.shape[1]:
         raise GwbpError(f"features have D = {q.shape[1]}, sources D = {s.shape[1]}")
     if q.device != s.device:
@@ -67,7 +43,7 @@ def knn_search(features: torch.Tensor, sources: torch.Tensor, k: int):
     n, m, d = q.shape[0], s.shape[0], q.shape[1]
     idx = torch.empty(n, k, dtype=torch.int32, device=q.device)
     score = torch.empty(n, k, dtype=torch.float32, device=q.device)
-    _run("gwbp_knn_search", q.device, C.c_int64(n), m, d, k, ptr(q), C.c_int64(_ld(q)), ptr(s), C.c_int64(_ld(s)), ptr(idx),
+    run("gwbp_knn_search", q.device, C.c_int64(n), m, d, k, ptr(q), C.c_int64(ld(q)), ptr(s), C.c_int64(ld(s)), ptr(idx),
          ptr(score))
     return score, idx
 
@@ -110,7 +86,7 @@ def vote_labels(indices: torch.Tensor, labels: torch.Tensor, num_classes: int, r
     n, k = indices.shape
     out = torch.empty(n, dtype=torch.int32, device=indices.device)
     counts = torch.empty(n, num_classes, dtype=torch.int32, device=indices.device) if return_counts else None
-    _run("gwbp_knn_vote", indices.device, C.c_int64(n), int(labels.shape[0]), k, ptr(indices), ptr(labels), int(num_classes),
+    run("gwbp_knn_vote", indices.device, C.c_int64(n), int(labels.shape[0]), k, ptr(indices), ptr(labels), int(num_classes),
          ptr(out), ptr(counts), C.c_int64(num_classes))
     return (out, counts) if return_counts else out
 
@@ -121,7 +97,7 @@ def transfer_labels(features: torch.Tensor, sources: torch.Tensor, labels, k: in
     k nearest (largest inner product) rows of sources[M, D], ties to the smallest label.  Returns labels[N] int32 (with
     return_counts also counts[N, num_classes] int32).  features, sources, k: as knn_search.  labels: [M] or [M, 1], integer or
     whole-valued float (narrow_source_labels); num_classes defaults to max label + 1."""
-    s = _rows(sources, "sources")
+    s = rows(sources, "sources")
     lab, nc = narrow_source_labels(labels, num_classes)
     if lab.shape[0] != s.shape[0]:
         raise GwbpError(f"{lab.shape[0]} labels for {s.shape[0]} sources")

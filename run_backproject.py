@@ -164,13 +164,14 @@ def main(argv=None):
     dev = torch.device("cuda", torch.cuda.current_device())
     rank = dist.get_rank() if dist.is_initialized() else 0
 
-    from gsbp_amd import scene_io, synthetic as syn
+    from gsbp_amd import cli, scene_io, synthetic as syn
 
+    # (a synthetic scene is activated on the device, a checkpoint on the host, backproject.py:55-57 -- as ever: the last bit differs)
+    scene = cli.load_scene(args, dev, activate_on_host=not args.synthetic)
+    splats, (means, quats, scales, opac), K, viewmats, W, H = scene[:6]  # splats: pre-activation, the reference's key names
+    names, cfg = scene.names, scene.cfg  # the views in the reference's order: images sorted by name (backproject.py:74)
     if args.synthetic:
-        cfg = syn.CONFIGS[args.synthetic]
-        splats = {k: v.to(dev) for k, v in syn.make_scene(cfg).items()}  # pre-activation, the reference's key names
-        means, quats, scales, opac = syn.activate(splats)
-        K, viewmats, W, H, dim = syn.intrinsics(cfg), syn.make_cameras(cfg), cfg.width, cfg.height, cfg.feat_dim
+        dim = cfg.feat_dim
         encoder = syn.make_encoder(cfg).to(dev) if cfg.encoder_dim else None
 
         # (DINO64 / LSEG480: the network's own low-resolution map, upsampled inside the kernels like the reference's F.interpolate)
@@ -194,37 +195,29 @@ def main(argv=None):
             def pixel_weight_fn(v):
                 return syn.make_pixel_weights(cfg, v, device=dev, kind=args.pixel_weights)
     else:
-        splats = scene_io.load_checkpoint(args.checkpoint, args.data_dir, format=args.format,
-                                          data_factor=args.data_factor, rasterizer=args.rasterizer)
-        means, quats = splats["means"].to(dev).float(), splats["rotation"].to(dev).float()
-        scales, opac = torch.exp(splats["scaling"]).to(dev).float(), torch.sigmoid(splats["opacity"]).to(dev).float()
-        splats = {k: (v.to(dev).float() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in splats.items()}
-        K = splats["camera_matrix"]
+        splats = {k: (v.float() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in splats.items()}
         if rank == 0:
             for line in camera_warnings(next(iter(splats["colmap_project"].cameras.values())), args.camera_model):
                 print(line, file=sys.stderr)
-        W, H = int(K[0, 2] * 2), int(K[1, 2] * 2)  # backproject.py:85-86
-        images = sorted(splats["colmap_project"].images.values(), key=lambda im: im.name)  # backproject.py:74
-        viewmats = torch.stack([scene_io.get_viewmat_from_colmap_image(im) for im in images])
         if labels_mode:
             # a map at another resolution than the view's is read with F.interpolate(mode="nearest")'s index maps in the kernel
-            first_labels = load_label_map(args.label_maps, images[0].name)
+            first_labels = load_label_map(args.label_maps, names[0])
             label_upsample = "nearest" if tuple(first_labels.shape) != (H, W) else None
 
             def label_fn(v):
-                return load_label_map(args.label_maps, images[v].name).to(dev)
+                return load_label_map(args.label_maps, names[v]).to(dev)
         elif masks_mode:
-            first_labels, first_table = load_mask_features(args.mask_features, images[0].name)
+            first_labels, first_table = load_mask_features(args.mask_features, names[0])
             label_upsample = "nearest" if tuple(first_labels.shape) != (H, W) else None
             dim = int(first_table.shape[1])
 
             def mask_fn(v):
-                lab, tab = load_mask_features(args.mask_features, images[v].name)
+                lab, tab = load_mask_features(args.mask_features, names[v])
                 return lab.to(dev), tab.to(dev)
         elif not args.feature_maps:
             raise SystemExit("--feature-maps is required (no LSeg/DINO weights offline)")
         encoder = torch.load(args.encoder).to(dev).float() if args.encoder else None
-        first = (torch.load(os.path.join(args.feature_maps, images[0].name + ".pt"))
+        first = (torch.load(os.path.join(args.feature_maps, names[0] + ".pt"))
                  if not (labels_mode or masks_mode) else None)
         if not masks_mode:
             dim = first.shape[-1] if first is not None else None
@@ -234,13 +227,13 @@ def main(argv=None):
         pixel_weight_fn = None
         if args.pixel_weights:
             def pixel_weight_fn(v):
-                return load_pixel_weights(args.pixel_weights, images[v].name, H, W).to(dev)
+                return load_pixel_weights(args.pixel_weights, names[v], H, W).to(dev)
         mode = "nearest" if args.feature == "dino" else "bilinear"
         upsample = mode if (first is not None and tuple(first.shape[:2]) != (H, W) and encoder is None) else None
         reduction = "mean" if args.feature == "dino" else "sum"  # backproject.py:263,283 vs :127,145
 
         def feature_fn(v):
-            f = torch.load(os.path.join(args.feature_maps, images[v].name + ".pt")).to(dev)
+            f = torch.load(os.path.join(args.feature_maps, names[v] + ".pt")).to(dev)
             if args.map_dtype == "float32" or f.dtype not in (torch.float16, torch.bfloat16):
                 f = f.float()
             if upsample is not None or tuple(f.shape[:2]) == (H, W):
@@ -256,7 +249,6 @@ def main(argv=None):
     # all-reduced, so every rank holds the SAME mask and the shapes of the collectives that follow agree by construction.
     n_all = means.shape[0]
     keep = None
-    vm_dev, K_dev = viewmats.to(dev), K.to(dev)
 
     def report_and_check(keep):
         if rank == 0:
@@ -264,8 +256,8 @@ def main(argv=None):
             print("Pruned", int((~keep).sum()), "splats")
             print("Remaining", int(keep.sum()), "splats")
         if "features_dc" in splats:  # utils.test_proper_pruning renders with the SH colours (checkpoints only)
-            pruned = {k: (v[keep] if k in gsbp_amd.pruning._PER_GAUSSIAN else v) for k, v in splats.items()}
-            rep = gsbp_amd.check_proper_pruning(splats, pruned, vm_dev, K_dev, W, H, **cam_kw)
+            pruned = {k: (v[keep] if k in gsbp_amd.pruning.PER_GAUSSIAN else v) for k, v in splats.items()}
+            rep = gsbp_amd.check_proper_pruning(splats, pruned, viewmats, K, W, H, **cam_kw)
             if rank == 0:
                 print("Percentage pruned: ", rep["percentage_pruned"])  # utils.py:348-359
                 print("Max pixel error: ", rep["max_pixel_error"])
@@ -289,7 +281,7 @@ def main(argv=None):
         return
 
     if not args.no_prune and not args.prune_by_product:
-        keep = gsbp_amd.pruning.gradient_mask(splats, vm_dev, K_dev, W, H, **cam_kw)
+        keep = gsbp_amd.pruning.gradient_mask(splats, viewmats, K, W, H, **cam_kw)
         report_and_check(keep)
         means, quats, scales, opac = means[keep], quats[keep], scales[keep], opac[keep]
 

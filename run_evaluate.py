@@ -23,7 +23,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from run_segment import FrameWriter  # noqa: E402
+from gsbp_amd import cli  # noqa: E402
 
 # render_affordance's palette (class 0, the background, grey)
 PALETTE = [[125, 125, 125], [255, 0, 0], [0, 255, 0], [0, 0, 255], [255, 255, 0], [255, 0, 255], [0, 255, 255], [128, 0, 0]]
@@ -37,14 +37,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--cut", type=int, default=64, help="predicted where uint8(clamp(opacity, 0, 1) * 255) > cut")
     ap.add_argument("--num-classes", type=int, default=None)
     ap.add_argument("--min-opacity", type=float, default=0.0, help="argmax frames: -1 (black) below this opacity")
-    ap.add_argument("--data-dir", default="./data/garden")
-    ap.add_argument("--checkpoint", default="./data/garden/ckpts/ckpt_29999_rank0.pt")
-    ap.add_argument("--format", choices=["inria", "gsplat", "ply"], default="gsplat")
-    ap.add_argument("--data-factor", type=int, default=4)
-    ap.add_argument("--synthetic", default=None, help="a seeded synthetic config (C1, ...) instead of files")
-    ap.add_argument("--camera-model", choices=["pinhole", "ortho", "fisheye"], default="pinhole")
-    ap.add_argument("--rasterize-mode", choices=["classic", "antialiased"], default="classic")
-    ap.add_argument("--max-views", type=int, default=None, help="score only the first views")
+    cli.add_scene_arguments(ap)
     ap.add_argument("--out", default="./results/evaluate")
     return ap
 
@@ -73,21 +66,18 @@ def main(argv=None) -> int:
     if not args.synthetic and not (args.labels and args.gt):
         ap.error("give --labels and --gt (and the scene arguments), or --synthetic")
     import gsbp_amd
-    from gsbp_amd import scene_io, synthetic as syn
-    if not torch.cuda.is_available():
-        raise SystemExit("run_evaluate.py needs a GPU (there is no CPU path)")
+    from gsbp_amd import synthetic as syn
+    cli.require_gpu("run_evaluate.py")
     dev = torch.device("cuda")
     os.makedirs(args.out, exist_ok=True)
+    if args.synthetic and args.num_classes is None:
+        ap.error("--synthetic needs --num-classes")
+    scene = cli.load_scene(args, dev)
+    splats, gauss, K, W, H, cfg = scene.splats, scene.gauss, scene.K, scene.width, scene.height, scene.cfg
     if args.synthetic:
-        if args.num_classes is None:
-            ap.error("--synthetic needs --num-classes")
-        cfg = syn.CONFIGS[args.synthetic]
-        splats = {k: t.to(dev) for k, t in syn.make_scene(cfg).items()}
-        K, viewmats, W, H = syn.intrinsics(cfg).to(dev), syn.make_cameras(cfg).to(dev), cfg.width, cfg.height
         splats["features_dc"] = (torch.rand(cfg.n_gaussians, 1, 3, generator=torch.Generator().manual_seed(syn.SH_SEED)).to(dev)
                                  - 0.5) / gsbp_amd.label_render.C0
         splats["features_rest"] = torch.zeros(cfg.n_gaussians, 0, 3, device=dev)
-        names = [f"view_{v:04d}" for v in range(viewmats.shape[0])]
         if args.labels:
             labels = torch.load(args.labels, map_location="cpu")
         else:
@@ -97,27 +87,18 @@ def main(argv=None) -> int:
         def gt_of(v):
             return syn.make_label_map(cfg, v, args.num_classes, device=dev)
     else:
-        splats = scene_io.load_checkpoint(args.checkpoint, args.data_dir, format=args.format, data_factor=args.data_factor)
-        splats = {k: (t.to(dev) if torch.is_tensor(t) else t) for k, t in splats.items()}
-        K = splats["camera_matrix"].float()
-        W, H = int(K[0, 2] * 2), int(K[1, 2] * 2)
-        images = sorted(splats["colmap_project"].images.values(), key=lambda im: im.name)
-        viewmats = torch.stack([scene_io.get_viewmat_from_colmap_image(im) for im in images]).to(dev)
-        names = [im.name for im in images]
         labels = torch.load(args.labels, map_location="cpu")
 
         def gt_of(v):
-            return load_gt(args.gt, names[v])
+            return load_gt(args.gt, scene.names[v])
     labels = torch.as_tensor(labels).reshape(-1).long().to(dev)
     n = splats["means"].shape[0]
     if labels.shape[0] != n:
         raise SystemExit(f"{labels.shape[0]} labels for {n} Gaussians")
     k = args.num_classes if args.num_classes is not None else int(labels.max()) + 1
-    if args.max_views is not None:
-        viewmats, names = viewmats[:args.max_views], names[:args.max_views]
+    scene = scene.first_views(args.max_views)
+    viewmats, names = scene.viewmats, scene.names
     raster_kw = dict(camera_model=args.camera_model, rasterize_mode=args.rasterize_mode)
-    gauss = (splats["means"].float(), splats["rotation"].float(), torch.exp(splats["scaling"]).float(),
-             torch.sigmoid(splats["opacity"]).float())
 
     counts = gsbp_amd.score_label_views(*gauss, labels, k, viewmats, K, W, H, gt_of, cut=args.cut, **raster_kw)
     torch.save(counts.cpu(), os.path.join(args.out, "counts.pt"))
@@ -135,7 +116,7 @@ def main(argv=None) -> int:
     tinted = gsbp_amd.recolor_by_labels(splats, labels, palette)
     sh = torch.cat([tinted["features_dc"], tinted["features_rest"]], dim=1).float()
     sh_degree = {1: 0, 4: 1, 9: 2, 16: 3}[sh.shape[1]]
-    writers = {name: FrameWriter(os.path.join(args.out, name)) for name in ("argmax", "tinted")}
+    writers = {name: cli.FrameWriter(os.path.join(args.out, name)) for name in ("argmax", "tinted")}
     for v in range(viewmats.shape[0]):
         seg = gsbp_amd.render_label_argmax(*gauss, labels, k, viewmats[v], K, W, H, min_opacity=args.min_opacity, **raster_kw)
         writers["argmax"].add(v, (shade[seg.long() + 1] * 255.0).to(torch.uint8))

@@ -26,6 +26,8 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from gsbp_amd import cli  # noqa: E402
+
 
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
@@ -35,14 +37,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--weights-out", default=None, metavar="DIR", help="write one agreement weight map per view here")
     ap.add_argument("--cosine-min", type=float, default=None, help="weight 1 where the per-pixel cosine is at least this")
     ap.add_argument("--quantile", type=float, default=None, help="weight 0 for this share of each view's lowest cosines")
-    ap.add_argument("--data-dir", default="./data/garden")
-    ap.add_argument("--checkpoint", default="./data/garden/ckpts/ckpt_29999_rank0.pt")
-    ap.add_argument("--format", choices=["inria", "gsplat", "ply"], default="gsplat")
-    ap.add_argument("--data-factor", type=int, default=4)
-    ap.add_argument("--synthetic", default=None, help="a seeded synthetic config (C1, ...) instead of files")
-    ap.add_argument("--camera-model", choices=["pinhole", "ortho", "fisheye"], default="pinhole")
-    ap.add_argument("--rasterize-mode", choices=["classic", "antialiased"], default="classic")
-    ap.add_argument("--max-views", type=int, default=None, help="score only the first views")
+    cli.add_scene_arguments(ap)
     ap.add_argument("--out", default="./results/fidelity")
     return ap
 
@@ -59,17 +54,14 @@ def main(argv=None) -> int:
     if args.weights_out and (args.cosine_min is None) == (args.quantile is None):
         ap.error("--weights-out needs exactly one of --cosine-min and --quantile")
     import gsbp_amd
-    from gsbp_amd import scene_io, synthetic as syn
-    if not torch.cuda.is_available():
-        raise SystemExit("run_fidelity.py needs a GPU (there is no CPU path)")
+    from gsbp_amd import synthetic as syn
+    cli.require_gpu("run_fidelity.py")
     dev = torch.device("cuda")
     os.makedirs(args.out, exist_ok=True)
     raster_kw = dict(camera_model=args.camera_model, rasterize_mode=args.rasterize_mode)
+    scene = cli.load_scene(args, dev, activate_on_host=True)
+    gauss, K, viewmats, W, H, names, cfg = scene.gauss, scene.K, scene.viewmats, scene.width, scene.height, scene.names, scene.cfg
     if args.synthetic:
-        cfg = syn.CONFIGS[args.synthetic]
-        gauss = tuple(t.to(dev).contiguous() for t in syn.activate(syn.make_scene(cfg)))
-        K, viewmats, W, H = syn.intrinsics(cfg).to(dev), syn.make_cameras(cfg).to(dev), cfg.width, cfg.height
-        names = [f"view_{v:04d}" for v in range(viewmats.shape[0])]
         upsample = cfg.upsample if cfg.lowres else None
         if upsample == "bilinear":
             raise SystemExit(f"{args.synthetic} has bilinear low-resolution maps: the comparison takes the upsampled map")
@@ -82,14 +74,6 @@ def main(argv=None) -> int:
             features = gsbp_amd.create_feature_field(*gauss, viewmats, K, W, H, map_of, cfg.feat_dim, reduction=cfg.reduction,
                                                      upsample=upsample, **raster_kw)
     else:
-        splats = scene_io.load_checkpoint(args.checkpoint, args.data_dir, format=args.format, data_factor=args.data_factor)
-        K = splats["camera_matrix"].float().to(dev)
-        W, H = int(K[0, 2] * 2), int(K[1, 2] * 2)
-        images = sorted(splats["colmap_project"].images.values(), key=lambda im: im.name)
-        viewmats = torch.stack([scene_io.get_viewmat_from_colmap_image(im) for im in images]).to(dev)
-        names = [im.name for im in images]
-        gauss = (splats["means"].to(dev).float(), splats["rotation"].to(dev).float(), torch.exp(splats["scaling"]).to(dev).float(),
-                 torch.sigmoid(splats["opacity"]).to(dev).float())
         features = torch.load(args.features, map_location="cpu")
         upsample = args.upsample
 
@@ -101,8 +85,8 @@ def main(argv=None) -> int:
     if features.dim() != 2 or features.shape[0] != n:
         raise SystemExit(f"the field has shape {tuple(features.shape)}, the scene {n} Gaussians (a field built on the pruned scene "
                          "does not fit the checkpoint: build it with run_backproject.py --no-prune)")
-    if args.max_views is not None:
-        viewmats, names = viewmats[:args.max_views], names[:args.max_views]
+    scene = scene.first_views(args.max_views)
+    viewmats, names = scene.viewmats, scene.names
 
     table = gsbp_amd.score_field_views(*gauss, features, viewmats, K, W, H, map_of, upsample=upsample, **raster_kw)
     torch.save(table.cpu(), os.path.join(args.out, "table.pt"))

@@ -23,11 +23,13 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from gsbp_amd import cli  # noqa: E402
+
 
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--maps", default=None, help="directory of <image name>.pt feature maps [H, W, D]")
-    ap.add_argument("--synthetic", default=None, help="a seeded synthetic config (C1, ...) instead of files")
+    cli.add_scene_arguments(ap, only=("synthetic",))
     ap.add_argument("--pixel-weights", default=None, metavar="DIR", help="directory of <image name>.pt weight maps [H, W]")
     ap.add_argument("--latent-dim", type=int, default=128, help="channels of the latent table: a multiple of 16 in [16, 128]")
     ap.add_argument("--steps", type=int, default=1000)
@@ -35,10 +37,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--lr", type=float, default=2.5e-3)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--score", action="store_true", help="also score the decoded and the lifted field against the maps")
-    ap.add_argument("--data-dir", default="./data/garden")
-    ap.add_argument("--checkpoint", default="./data/garden/ckpts/ckpt_29999_rank0.pt")
-    ap.add_argument("--format", choices=["inria", "gsplat", "ply"], default="gsplat")
-    ap.add_argument("--data-factor", type=int, default=4)
+    cli.add_scene_arguments(ap, only=("data-dir", "checkpoint", "format", "data-factor"))
     ap.add_argument("--out", default="./results/fit_field")
     return ap
 
@@ -53,34 +52,25 @@ def main(argv=None) -> int:
     if bool(args.synthetic) == bool(args.maps):
         ap.error("give exactly one of --maps (with the scene arguments) and --synthetic")
     import gsbp_amd
-    from gsbp_amd import scene_io, synthetic as syn
-    if not torch.cuda.is_available():
-        raise SystemExit("run_fit_field.py needs a GPU (there is no CPU path)")
+    from gsbp_amd import synthetic as syn
+    cli.require_gpu("run_fit_field.py")
     dev = torch.device("cuda")
     os.makedirs(args.out, exist_ok=True)
+    if args.synthetic and syn.CONFIGS[args.synthetic].lowres:
+        raise SystemExit(f"{args.synthetic} has low-resolution maps: the fit takes full-resolution [H, W, D] maps")
+    scene = cli.load_scene(args, dev, activate_on_host=True)
+    gauss, K, viewmats, W, H, names, cfg = scene.gauss, scene.K, scene.viewmats, scene.width, scene.height, scene.names, scene.cfg
     if args.synthetic:
-        cfg = syn.CONFIGS[args.synthetic]
-        if cfg.lowres:
-            raise SystemExit(f"{args.synthetic} has low-resolution maps: the fit takes full-resolution [H, W, D] maps")
-        gauss = tuple(t.to(dev).contiguous() for t in syn.activate(syn.make_scene(cfg)))
-        K, viewmats, W, H, dim = syn.intrinsics(cfg).to(dev), syn.make_cameras(cfg).to(dev), cfg.width, cfg.height, cfg.feat_dim
-        names = [f"view_{v:04d}" for v in range(viewmats.shape[0])]
+        dim = cfg.feat_dim
         maps = [syn.make_feature_map(cfg, v, device=dev) for v in range(viewmats.shape[0])]
 
         def map_of(v):
             return maps[v]
     else:
-        splats = scene_io.load_checkpoint(args.checkpoint, args.data_dir, format=args.format, data_factor=args.data_factor)
-        K = splats["camera_matrix"].float().to(dev)
-        W, H = int(K[0, 2] * 2), int(K[1, 2] * 2)
-        images = sorted(splats["colmap_project"].images.values(), key=lambda im: im.name)
-        images = [im for im in images if os.path.exists(os.path.join(args.maps, im.name + ".pt"))]
-        if not images:
+        have = [v for v, name in enumerate(names) if os.path.exists(os.path.join(args.maps, name + ".pt"))]
+        if not have:
             raise SystemExit(f"no <image name>.pt map of this scene in {args.maps}")
-        viewmats = torch.stack([scene_io.get_viewmat_from_colmap_image(im) for im in images]).to(dev)
-        names = [im.name for im in images]
-        gauss = (splats["means"].to(dev).float(), splats["rotation"].to(dev).float(), torch.exp(splats["scaling"]).to(dev).float(),
-                 torch.sigmoid(splats["opacity"]).to(dev).float())
+        viewmats, names = viewmats[have], [names[v] for v in have]
 
         def map_of(v):
             return torch.load(os.path.join(args.maps, names[v] + ".pt")).to(dev)

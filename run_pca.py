@@ -21,20 +21,16 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from gsbp_amd import cli  # noqa: E402
+
 
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--features", default=None, help=".pt tensor [N, D]: the finished feature field")
-    ap.add_argument("--data-dir", default="./data/garden")
-    ap.add_argument("--checkpoint", default="./data/garden/ckpts/ckpt_29999_rank0.pt")
-    ap.add_argument("--format", choices=["inria", "gsplat", "ply"], default="gsplat")
-    ap.add_argument("--data-factor", type=int, default=4)
-    ap.add_argument("--synthetic", default=None, help="a seeded synthetic config (C1, ...) instead of files")
+    cli.add_scene_arguments(ap, only=("data-dir", "checkpoint", "format", "data-factor", "synthetic"))
     ap.add_argument("--mode", choices=["gaussians", "renderings"], default="gaussians")
     ap.add_argument("--scale", type=float, default=None, help="factor on the Gaussians' scales (default 0.2 / 1.0 by --mode)")
-    ap.add_argument("--camera-model", choices=["pinhole", "ortho", "fisheye"], default="pinhole")
-    ap.add_argument("--rasterize-mode", choices=["classic", "antialiased"], default="classic")
-    ap.add_argument("--max-views", type=int, default=None, help="render only the first views")
+    cli.add_scene_arguments(ap, only=("camera-model", "rasterize-mode", "max-views"), max_views_help="render only the first views")
     ap.add_argument("--out", default="./results/pca")
     return ap
 
@@ -45,34 +41,21 @@ def main(argv=None) -> int:
     if not args.synthetic and not args.features:
         ap.error("give --features (and the scene arguments), or --synthetic")
     import gsbp_amd
-    from gsbp_amd import scene_io, synthetic as syn
-    if not torch.cuda.is_available():
-        raise SystemExit("run_pca.py needs a GPU (there is no CPU path)")
+    from gsbp_amd import synthetic as syn
+    cli.require_gpu("run_pca.py")
     dev = torch.device("cuda")
     os.makedirs(args.out, exist_ok=True)
-    if args.synthetic:
-        cfg = syn.CONFIGS[args.synthetic]
-        means, quats, scales, opac = (t.to(dev) for t in syn.activate(syn.make_scene(cfg)))
-        K, viewmats, W, H = syn.intrinsics(cfg).to(dev), syn.make_cameras(cfg).to(dev), cfg.width, cfg.height
-        if args.features:
-            feats = torch.load(args.features, map_location=dev)
-        else:
-            feats = gsbp_amd.create_feature_field(means, quats, scales, opac, viewmats, K, W, H,
-                                                  lambda v: syn.make_feature_map(cfg, v, device=dev), cfg.feat_dim)
-            torch.save(feats.cpu(), os.path.join(args.out, "features.pt"))
-    else:
-        splats = scene_io.load_checkpoint(args.checkpoint, args.data_dir, format=args.format, data_factor=args.data_factor)
-        means, quats = splats["means"].to(dev).float(), splats["rotation"].to(dev).float()
-        scales, opac = torch.exp(splats["scaling"]).to(dev).float(), torch.sigmoid(splats["opacity"]).to(dev).float()
-        K = splats["camera_matrix"].to(dev).float()
-        W, H = int(K[0, 2] * 2), int(K[1, 2] * 2)
-        images = sorted(splats["colmap_project"].images.values(), key=lambda im: im.name)
-        viewmats = torch.stack([scene_io.get_viewmat_from_colmap_image(im) for im in images]).to(dev)
+    scene = cli.load_scene(args, dev, activate_on_host=True)
+    (means, quats, scales, opac), K, viewmats, W, H, cfg = scene.gauss, scene.K, scene.viewmats, scene.width, scene.height, scene.cfg
+    if args.features:
         feats = torch.load(args.features, map_location=dev)
+    else:
+        feats = gsbp_amd.create_feature_field(means, quats, scales, opac, viewmats, K, W, H,
+                                              lambda v: syn.make_feature_map(cfg, v, device=dev), cfg.feat_dim)
+        torch.save(feats.cpu(), os.path.join(args.out, "features.pt"))
     if feats.shape[0] != means.shape[0]:
         raise SystemExit(f"{feats.shape[0]} feature rows for {means.shape[0]} Gaussians (prune the scene as run_backproject.py did)")
-    if args.max_views is not None:
-        viewmats = viewmats[:args.max_views]
+    viewmats = scene.first_views(args.max_views).viewmats
 
     basis = gsbp_amd.fit_pca(feats, 3)
     colors, lo, hi = gsbp_amd.pca_colors(feats, basis)

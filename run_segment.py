@@ -23,6 +23,8 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from gsbp_amd import cli  # noqa: E402
+
 
 def parse_click(text: str):
     try:
@@ -42,40 +44,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--click", type=parse_click, action="append", default=[], metavar="VIEW:X,Y", help="a positive click")
     ap.add_argument("--neg-click", type=parse_click, action="append", default=[], metavar="VIEW:X,Y", help="a negative click")
     ap.add_argument("--encoder", default=None, help=".pt tensor [D_in, D]: prompts @ encoder, renormalised (compressed field)")
-    ap.add_argument("--data-dir", default="./data/garden")
-    ap.add_argument("--checkpoint", default="./data/garden/ckpts/ckpt_29999_rank0.pt")
-    ap.add_argument("--format", choices=["inria", "gsplat", "ply"], default="gsplat")
-    ap.add_argument("--data-factor", type=int, default=4)
-    ap.add_argument("--synthetic", default=None, help="a seeded synthetic config (C1, ...) instead of files")
-    ap.add_argument("--camera-model", choices=["pinhole", "ortho", "fisheye"], default="pinhole")
-    ap.add_argument("--rasterize-mode", choices=["classic", "antialiased"], default="classic")
-    ap.add_argument("--max-views", type=int, default=None, help="render only the first views")
+    cli.add_scene_arguments(ap, max_views_help="render only the first views")
     ap.add_argument("--export", action="store_true", help="also write extracted.pt / deleted.pt")
     ap.add_argument("--out", default="./results/segment")
     return ap
-
-
-class FrameWriter:
-    """frame_0000.png ... in a directory when PIL imports, else one frames.pt (uint8 [C, H, W, 3]) there."""
-
-    def __init__(self, directory: str):
-        os.makedirs(directory, exist_ok=True)
-        self.dir, self.kept = directory, []
-        try:
-            from PIL import Image
-            self.image = Image
-        except ImportError:
-            self.image = None
-
-    def add(self, v: int, frame: torch.Tensor) -> None:
-        if self.image is not None:
-            self.image.fromarray(frame.cpu().numpy(), "RGB").save(os.path.join(self.dir, f"frame_{v:04d}.png"))
-        else:
-            self.kept.append(frame.cpu())
-
-    def close(self) -> None:
-        if self.image is None and self.kept:
-            torch.save(torch.stack(self.kept), os.path.join(self.dir, "frames.pt"))
 
 
 def main(argv=None) -> int:
@@ -84,22 +56,19 @@ def main(argv=None) -> int:
     if not args.synthetic and not (args.features and args.prompts):
         ap.error("give --features and --prompts (and the scene arguments), or --synthetic")
     import gsbp_amd
-    from gsbp_amd import scene_io, segment as seg, synthetic as syn
-    if not torch.cuda.is_available():
-        raise SystemExit("run_segment.py needs a GPU (there is no CPU path)")
+    from gsbp_amd import segment as seg, synthetic as syn
+    cli.require_gpu("run_segment.py")
     dev = torch.device("cuda")
     os.makedirs(args.out, exist_ok=True)
+    scene = cli.load_scene(args, dev)
+    splats, gauss, K, W, H, cfg = scene.splats, scene.gauss, scene.K, scene.width, scene.height, scene.cfg
     sh_degree = None
     if args.synthetic:
-        cfg = syn.CONFIGS[args.synthetic]
-        splats = {k: t.to(dev) for k, t in syn.make_scene(cfg).items()}
-        K, viewmats, W, H = syn.intrinsics(cfg).to(dev), syn.make_cameras(cfg).to(dev), cfg.width, cfg.height
         colors = torch.rand(cfg.n_gaussians, 3, generator=torch.Generator().manual_seed(syn.SH_SEED)).to(dev)
-        means, quats, scales, opac = syn.activate(splats)
         if args.features:
             feats = torch.load(args.features, map_location=dev)
         else:
-            feats = gsbp_amd.create_feature_field(means, quats, scales, opac, viewmats, K, W, H,
+            feats = gsbp_amd.create_feature_field(*gauss, scene.viewmats, K, W, H,
                                                   lambda v: syn.make_feature_map(cfg, v, device=dev), cfg.feat_dim)
             torch.save(feats.cpu(), os.path.join(args.out, "features.pt"))
         if args.prompts:
@@ -108,20 +77,13 @@ def main(argv=None) -> int:
             prompts, n_pos = syn.make_prompts(feats)
             seg.save_prompts(os.path.join(args.out, "prompts.pt"), prompts, n_pos)
     else:
-        splats = scene_io.load_checkpoint(args.checkpoint, args.data_dir, format=args.format, data_factor=args.data_factor)
-        splats = {k: (t.to(dev) if torch.is_tensor(t) else t) for k, t in splats.items()}
-        K = splats["camera_matrix"].float()
-        W, H = int(K[0, 2] * 2), int(K[1, 2] * 2)
-        images = sorted(splats["colmap_project"].images.values(), key=lambda im: im.name)
-        viewmats = torch.stack([scene_io.get_viewmat_from_colmap_image(im) for im in images]).to(dev)
         colors, sh_degree = torch.cat([splats["features_dc"], splats["features_rest"]], dim=1).float(), 3
         feats = torch.load(args.features, map_location=dev)
         prompts, n_pos = seg.load_prompts(args.prompts)
     n = splats["means"].shape[0]
     if feats.shape[0] != n:
         raise SystemExit(f"{feats.shape[0]} feature rows for {n} Gaussians (prune the scene as run_backproject.py did)")
-    if args.max_views is not None:
-        viewmats = viewmats[:args.max_views]
+    viewmats = scene.first_views(args.max_views).viewmats
     if args.encoder:
         prompts = seg.encode_prompts(prompts, torch.load(args.encoder, map_location="cpu"))
     raster_kw = dict(camera_model=args.camera_model, rasterize_mode=args.rasterize_mode)
@@ -129,7 +91,6 @@ def main(argv=None) -> int:
     def activated(s):
         return s["means"].float(), s["rotation"].float(), torch.exp(s["scaling"]).float(), torch.sigmoid(s["opacity"]).float()
 
-    gauss = activated(splats)
     pos, neg = list(prompts[:n_pos].to(dev)), list(prompts[n_pos:].to(dev))
     for clicks, side in ((args.click, pos), (args.neg_click, neg)):
         for view, x, y in clicks:
@@ -149,7 +110,7 @@ def main(argv=None) -> int:
         torch.save(seg.checkpoint_layout(extracted), os.path.join(args.out, "extracted.pt"))
         torch.save(seg.checkpoint_layout(deleted), os.path.join(args.out, "deleted.pt"))
 
-    writers = {k: FrameWriter(os.path.join(args.out, k)) for k in ("mask2d", "extracted", "deleted")}
+    writers = {k: cli.FrameWriter(os.path.join(args.out, k)) for k in ("mask2d", "extracted", "deleted")}
     if n_pos < prompts.shape[0]:
         frames = gsbp_amd.render_prompt_mask(*gauss, feats, viewmats, K, W, H, prompts, n_pos, colors=colors, sh_degree=sh_degree,
                                              **raster_kw)

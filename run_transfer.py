@@ -19,6 +19,8 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from gsbp_amd import cli  # noqa: E402
+
 
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
@@ -40,8 +42,7 @@ def main(argv=None) -> int:
         ap.error("give --features and --examples, or --synthetic")
     import gsbp_amd
     from gsbp_amd import transfer
-    if not torch.cuda.is_available():
-        raise SystemExit("run_transfer.py needs a GPU (there is no CPU path)")
+    cli.require_gpu("run_transfer.py")
     dev = torch.device("cuda")
     if args.synthetic:
         feats, src, labels = transfer.synthetic_transfer()

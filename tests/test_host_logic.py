@@ -518,3 +518,33 @@ def test_feature_field_plan_depth_split_threshold_and_late_queue_downgrade(monke
     with pytest.warns(RuntimeWarning, match="ONE stream"):
         p = plan(1_000_000, 1600, 1060, 16, encoder=enc)
     assert not p.pipelined and p.first_map is None and fetched == []
+
+
+def test_raster_kw_merges_the_defaults_and_names_the_caller():
+    from gsbp_amd import _views
+    kw = _views.raster_kw("render_label_maps", dict(camera_model="fisheye", eps2d=0.1))
+    assert kw == dict(_views.RASTER_KW, camera_model="fisheye", eps2d=0.1) and set(kw) == set(_views.RASTER_KW)
+    assert _views.raster_kw("f", {}) == _views.RASTER_KW and _views.raster_kw("f", {}) is not _views.RASTER_KW
+    with pytest.raises(TypeError, match=r"probe_pixels\(\) got unexpected keyword arguments \['sh_degree', 'tile'\]"):
+        _views.raster_kw("probe_pixels", dict(tile=16, near_plane=0.1, sh_degree=3))
+    with pytest.raises(gsbp_amd.GwbpError, match=r"score_label_views\(\) needs HIP tensors \(there is no CPU path\)"):
+        _views.require_device("score_label_views", torch.zeros(3, 3))
+    with pytest.raises(gsbp_amd.GwbpError, match="features must be a HIP tensor"):
+        _views.rows(torch.zeros(3, 3), "features")
+    assert _views.ld(torch.zeros(4, 6)[:, :3]) == 6 and _views.ld(torch.zeros(1, 6)[:, :3]) == 3
+
+
+def test_no_module_imports_a_private_name_from_a_sibling():
+    """from .X import _name only for X in {_lib, _views}: the modules of the package share through those two, not through each other."""
+    import ast
+    pkg = os.path.dirname(gsbp_amd.__file__)
+    found = []
+    for name in sorted(os.listdir(pkg)):
+        if not name.endswith(".py"):
+            continue
+        with open(os.path.join(pkg, name)) as f:
+            tree = ast.parse(f.read(), name)
+        for node in ast.walk(tree):
+            if isinstance(node, ast.ImportFrom) and node.level == 1 and node.module not in (None, "_lib", "_views"):
+                found += [(name, node.module, a.name) for a in node.names if a.name.startswith("_")]
+    assert not found, found

@@ -29,7 +29,7 @@ import torch  # noqa: E402
 from gsbp_amd import pca  # noqa: E402
 from gsbp_amd import synthetic as syn  # noqa: E402
 from gsbp_amd._lib import lib, ptr  # noqa: E402
-from gsbp_amd.transfer import _run  # noqa: E402
+from gsbp_amd._views import run as _run  # noqa: E402
 
 PEAK = 157.3e12
 HBM = 6.29e12
