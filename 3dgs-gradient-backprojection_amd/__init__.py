@@ -15,6 +15,8 @@ JojiJoseph/3dgs-gradient-backprojection), hand-written HIP kernels behind a C AB
                                                     # maps it was lifted from, fused; and the weight map for a second, robust lift
     from gsbp_amd import decoded_loss, decoded_field_gradients, fit_decoded_field, decode_field  # a latent field and its decoder
                                                     # fitted on frozen Gaussians (the reference's Feature-3DGS baseline), fused
+    from gsbp_amd import spatial_knn, knn_distances, init_scales  # which Gaussians are next to each other: exact 3-D k-NN on a grid
+    from gsbp_amd import smooth_labels, smooth_mask, remove_outliers, smooth_features  # and a finished lift cleaned with it
 """
 from . import synthetic  # noqa: F401
 from ._lib import GwbpError, build, lib  # noqa: F401
@@ -28,4 +30,6 @@ from .segment import ClickSession, apply_mask3d, probe_pixels, prompt_mask, prom
 from .label_render import miou_recall, recolor_by_labels, render_label_argmax, render_label_maps, score_label_views  # noqa: F401
 from .fidelity import agreement_weights, field_fidelity, render_field_agreement, score_field_views  # noqa: F401
 from .decoded_field import decode_field, decoded_field_gradients, decoded_loss, fit_decoded_field  # noqa: F401
+from . import spatial  # noqa: F401
+from .spatial import init_scales, knn_distances, plan_grid, remove_outliers, smooth_features, smooth_labels, smooth_mask, spatial_knn  # noqa: F401
 from .pruning import check_proper_pruning, gradient_mask, prune_by_gradients  # noqa: F401

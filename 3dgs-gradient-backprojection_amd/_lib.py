@@ -185,6 +185,13 @@ ARGTYPES = {
     # N, M, D, k, Q, ldq, S, lds, idx, score, stream  /  N, M, k, idx, labels, num_classes, label_out, counts, ldc, stream
     "gwbp_knn_search": [_I64, _I32, _I32, _I32, _P, _I64, _P, _I64, _P, _P, _P],
     "gwbp_knn_vote": [_I64, _I32, _I32, _P, _P, _I32, _P, _P, _I64, _P],
+    # spatial k-NN: n, points, ldp, lo_x, lo_y, lo_z, cell_size, nx, ny, nz, keys, stream  /  n, points, ldp, sorted_keys, perm,
+    # n_cells, sorted, cell_start, stream  /  n, sorted, cell_start, lo_x, lo_y, lo_z, cell_size, nx, ny, nz, q, queries, ldq, order,
+    # k, idx, dist, stream  /  n, m, D, k, idx, features, ldf, out, ldo, stream
+    "gwbp_spatial_cell_keys": [_I64, _P, _I64, _F, _F, _F, _F, _I32, _I32, _I32, _P, _P],
+    "gwbp_spatial_build": [_I64, _P, _I64, _P, _P, _I64, _P, _P, _P],
+    "gwbp_spatial_knn": [_I64, _P, _P, _F, _F, _F, _F, _I32, _I32, _I32, _I64, _P, _I64, _P, _I32, _P, _P, _P],
+    "gwbp_neighbor_mean": [_I64, _I64, _I32, _I32, _P, _P, _I64, _P, _I64, _P],
     # PCA: N, D, bytes*  /  N, D, X, ldx, mean, workspace, bytes, stream  /  N, D, X, ldx, mean, gram, workspace, bytes, stream  /
     # N, D, k, X, ldx, mean, components, Y, minmax, stream  /  n, Y, lo_hi, colors, stream
     "gwbp_pca_workspace_size": [_I64, _I32, C.POINTER(C.c_size_t)],

@@ -1,4 +1,5 @@
 // capi.hip -- extern "C" entry points of libgwbp.so (see include/gwbp.h for the contract).
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -908,6 +909,103 @@ int gwbp_knn_vote(int64_t N, int32_t M, int32_t k, const int32_t *idx, const int
     if (!labels || (N > 0 && (!idx || !label_out)))
         return set_error(GWBP_EINVAL, "knn_vote: null idx, labels or label_out");
     return launch_knn_vote(N, M, k, idx, labels, num_classes, label_out, counts, ldc, as_stream(stream));
+}
+
+// the grid of the spatial entry points: finite lo, a positive finite cell edge, 1 .. 1024 cells per axis, 2^24 in all
+static int check_spatial_grid(const char *what, float lo_x, float lo_y, float lo_z, float h, int32_t nx, int32_t ny, int32_t nz)
+{
+    if (!(fabsf(lo_x) < INFINITY && fabsf(lo_y) < INFINITY && fabsf(lo_z) < INFINITY))
+        return set_error(GWBP_EINVAL, "%s: the grid's origin must be finite", what);
+    if (!(h >= GWBP_SPATIAL_MIN_CELL && h < INFINITY))
+        return set_error(GWBP_EINVAL, "%s: cell size must be finite and at least %g (got %g)", what, (double)GWBP_SPATIAL_MIN_CELL,
+                         (double)h);
+    if (nx < 1 || ny < 1 || nz < 1 || nx > GWBP_SPATIAL_MAX_DIM || ny > GWBP_SPATIAL_MAX_DIM || nz > GWBP_SPATIAL_MAX_DIM ||
+        (int64_t)nx * ny * nz > GWBP_SPATIAL_MAX_CELLS)
+        return set_error(GWBP_EINVAL, "%s: grid dimensions %d x %d x %d outside [1, %d] per axis, %d cells in all", what, (int)nx,
+                         (int)ny, (int)nz, GWBP_SPATIAL_MAX_DIM, GWBP_SPATIAL_MAX_CELLS);
+    return GWBP_OK;
+}
+
+static int check_spatial_points(const char *what, const char *name, int64_t n, const float *P, int64_t ldp)
+{
+    if (n < 0 || n > 0x7FFFFFFF)
+        return set_error(GWBP_EINVAL, "%s: bad number of %s (%lld): 0 .. 2^31 - 1", what, name, (long long)n);
+    if (ldp < 3)
+        return set_error(GWBP_EINVAL, "%s: row stride %lld of %s below 3", what, (long long)ldp, name);
+    if (n > 0 && !P)
+        return set_error(GWBP_EINVAL, "%s: null %s", what, name);
+    if (reinterpret_cast<uintptr_t>(P) & 3)
+        return set_error(GWBP_EINVAL, "%s: %s must be 4-B aligned", what, name);
+    return GWBP_OK;
+}
+
+int gwbp_spatial_cell_keys(int64_t n, const float *points, int64_t ldp, float lo_x, float lo_y, float lo_z, float cell_size,
+                           int32_t nx, int32_t ny, int32_t nz, int32_t *keys, void *stream)
+{
+    if (int rc = check_spatial_points("spatial_cell_keys", "points", n, points, ldp))
+        return rc;
+    if (int rc = check_spatial_grid("spatial_cell_keys", lo_x, lo_y, lo_z, cell_size, nx, ny, nz))
+        return rc;
+    if (n > 0 && !keys)
+        return set_error(GWBP_EINVAL, "spatial_cell_keys: null keys");
+    const float lo[3] = {lo_x, lo_y, lo_z};
+    const int32_t dims[3] = {nx, ny, nz};
+    return launch_spatial_cell_keys(n, points, ldp, lo, cell_size, dims, keys, as_stream(stream));
+}
+
+int gwbp_spatial_build(int64_t n, const float *points, int64_t ldp, const int32_t *sorted_keys, const int64_t *perm,
+                       int64_t n_cells, float *sorted, int32_t *cell_start, void *stream)
+{
+    if (int rc = check_spatial_points("spatial_build", "points", n, points, ldp))
+        return rc;
+    if (n_cells < 1 || n_cells > GWBP_SPATIAL_MAX_CELLS)
+        return set_error(GWBP_EINVAL, "spatial_build: n_cells = %lld outside [1, %d]", (long long)n_cells, GWBP_SPATIAL_MAX_CELLS);
+    if (!cell_start || (n > 0 && (!sorted_keys || !perm || !sorted)))
+        return set_error(GWBP_EINVAL, "spatial_build: null sorted_keys, perm, sorted or cell_start");
+    if (reinterpret_cast<uintptr_t>(sorted) & 15)
+        return set_error(GWBP_EINVAL, "spatial_build: sorted must be 16-B aligned");
+    return launch_spatial_build(n, points, ldp, sorted_keys, perm, n_cells, sorted, cell_start, as_stream(stream));
+}
+
+int gwbp_spatial_knn(int64_t n, const float *sorted, const int32_t *cell_start, float lo_x, float lo_y, float lo_z, float cell_size,
+                     int32_t nx, int32_t ny, int32_t nz, int64_t q, const float *queries, int64_t ldq, const int64_t *order,
+                     int32_t k, int32_t *idx, float *dist, void *stream)
+{
+    if (n < 1 || n > 0x7FFFFFFF)
+        return set_error(GWBP_EINVAL, "spatial_knn: bad number of points (%lld): 1 .. 2^31 - 1", (long long)n);
+    if (k < 1 || k > 32)
+        return set_error(GWBP_EINVAL, "spatial_knn: k must be in [1, 32] (got %d)", (int)k);
+    if (k > n)
+        return set_error(GWBP_EINVAL, "spatial_knn: k = %d exceeds the number of points N = %lld", (int)k, (long long)n);
+    if (int rc = check_spatial_points("spatial_knn", "queries", q, queries, ldq))
+        return rc;
+    if (int rc = check_spatial_grid("spatial_knn", lo_x, lo_y, lo_z, cell_size, nx, ny, nz))
+        return rc;
+    if (!sorted || !cell_start || (q > 0 && (!order || !idx || !dist)))
+        return set_error(GWBP_EINVAL, "spatial_knn: null sorted, cell_start, order, idx or dist");
+    if (reinterpret_cast<uintptr_t>(sorted) & 15)
+        return set_error(GWBP_EINVAL, "spatial_knn: sorted must be 16-B aligned");
+    const float lo[3] = {lo_x, lo_y, lo_z};
+    const int32_t dims[3] = {nx, ny, nz};
+    return launch_spatial_knn(sorted, cell_start, lo, cell_size, dims, q, queries, ldq, order, k, idx, dist, as_stream(stream));
+}
+
+int gwbp_neighbor_mean(int64_t n, int64_t m, int32_t D, int32_t k, const int32_t *idx, const float *features, int64_t ldf,
+                       float *out, int64_t ldo, void *stream)
+{
+    if (n < 0 || m < 1 || m > 0x7FFFFFFF || D < 1)
+        return set_error(GWBP_EINVAL, "neighbor_mean: bad sizes (n=%lld m=%lld D=%d)", (long long)n, (long long)m, (int)D);
+    if (k < 1 || k > 32)
+        return set_error(GWBP_EINVAL, "neighbor_mean: k must be in [1, 32] (got %d)", (int)k);
+    if (ldf < D || ldo < D)
+        return set_error(GWBP_EINVAL, "neighbor_mean: row strides (%lld, %lld) below D = %d", (long long)ldf, (long long)ldo, (int)D);
+    if (!features || (n > 0 && (!idx || !out)))
+        return set_error(GWBP_EINVAL, "neighbor_mean: null idx, features or out");
+    if ((reinterpret_cast<uintptr_t>(features) & 3) || (reinterpret_cast<uintptr_t>(out) & 3))
+        return set_error(GWBP_EINVAL, "neighbor_mean: features and out must be 4-B aligned");
+    if (features == out)
+        return set_error(GWBP_EINVAL, "neighbor_mean: out must not be the features");
+    return launch_neighbor_mean(n, m, D, k, idx, features, ldf, out, ldo, as_stream(stream));
 }
 
 // the checks the two passes of the fit share

@@ -280,6 +280,16 @@ int launch_knn_search(int64_t N, int M, int D, int k, const float *Q, int64_t ld
                       float *score, hipStream_t s);
 int launch_knn_vote(int64_t N, int M, int k, const int32_t *idx, const int32_t *labels, int num_classes, int32_t *label_out,
                     int32_t *counts, int64_t ldc, hipStream_t s);
+// exact Euclidean k-NN of 3-D points on a uniform grid and the neighbour average of a field (spatial.hip).  lo: float[3] and
+// dims: int32[3] on the host
+int launch_spatial_cell_keys(int64_t N, const float *P, int64_t ldp, const float *lo, float h, const int32_t *dims, int32_t *keys,
+                             hipStream_t s);
+int launch_spatial_build(int64_t N, const float *P, int64_t ldp, const int32_t *skeys, const int64_t *perm, int64_t n_cells,
+                         float *sorted, int32_t *cell_start, hipStream_t s);
+int launch_spatial_knn(const float *sorted, const int32_t *cell_start, const float *lo, float h, const int32_t *dims, int64_t Q,
+                       const float *queries, int64_t ldq, const int64_t *order, int k, int32_t *idx, float *dist, hipStream_t s);
+int launch_neighbor_mean(int64_t N, int64_t M, int D, int k, const int32_t *idx, const float *F, int64_t ldf, float *out,
+                         int64_t ldo, hipStream_t s);
 // PCA of a finished field (pca.hip): column means, centred Gram, projection onto k <= 16 components, colours.  ws: the caller's
 // pca_workspace_bytes(N, D) bytes (the slices' partial sums), free again when the call's kernels have run.
 size_t pca_workspace_bytes(int64_t N, int D);

@@ -490,6 +490,48 @@ GWBP_API int gwbp_knn_search(int64_t N, int32_t M, int32_t D, int32_t k, const f
 GWBP_API int gwbp_knn_vote(int64_t N, int32_t M, int32_t k, const int32_t *idx, const int32_t *labels, int32_t num_classes,
                            int32_t *label_out, int32_t *counts, int64_t ldc, void *stream);
 
+/* ---- Spatial neighbours: exact Euclidean k-NN of 3-D points on a uniform grid (the reference's knn(),
+ * f3dgs/utils_simple_trainer.py:141-145: sklearn NearestNeighbors on a host copy) -------------------------------------------------
+ * The grid: cubic cells of edge cell_size over a box that starts at (lo_x, lo_y, lo_z), nx x ny x nz cells, x fastest.  A point's
+ * cell along an axis is floorf((x - lo) / cell_size) clamped to [0, n - 1]: the border cells extend to infinity.  The result of the
+ * search does not depend on the grid, only its cost does.
+ * The three calls of one search, with the caller's stable sort of the keys between the first two:
+ *   gwbp_spatial_cell_keys  keys[i] = the linear cell of points[i * ldp + 0..2] (int32); a point with a non-finite coordinate gets
+ *                           the key nx * ny * nz, which sorts last and belongs to no cell.
+ *   gwbp_spatial_build      from the keys in ascending order (sorted_keys[n]) and the permutation that sorts them (perm[n], int64):
+ *                           sorted[i] = (x, y, z, original index as int32 bits) of point perm[i] (float [n, 4], 16-B aligned), and
+ *                           cell_start[c], c <= n_cells = nx * ny * nz (int32 [n_cells + 1]): the first sorted position whose key
+ *                           is >= c.  No atomics.
+ *   gwbp_spatial_knn        for every query row queries[g * ldq + 0..2], g < q, the k points of smallest distance: idx[q, k] (int32,
+ *                           original indices) and dist[q, k] (fp32), dense, each row sorted by distance ascending, then index
+ *                           ascending.  order[q] (int64): the order in which lanes take the queries -- a permutation of 0 .. q-1,
+ *                           by ascending cell key of the queries for speed (for queries == points: perm).
+ * Arithmetic: squared distance is fmaf(dz, dz, fmaf(dy, dy, dx * dx)) with dx = p.x - q.x in fp32; dist is its correctly rounded
+ * sqrtf.  The search is exact for that expression: ties by index, results independent of the grid and of the launch, no atomics,
+ * two runs give the same bits.  A non-finite point is nobody's neighbour; a non-finite query gets idx -1 and dist NaN; a query
+ * with fewer than k finite points gets idx -1 and dist +inf in the tail.  1 <= k <= 32, k <= n < 2^31; 1 <= nx, ny, nz <= 1024,
+ * nx * ny * nz <= 2^24; cell_size finite and >= GWBP_SPATIAL_MIN_CELL; row strides (in floats) >= 3.
+ * GWBP_EINVAL before any HIP call: a size, k, grid dimension, cell size or stride outside these, a null or misaligned pointer. */
+#define GWBP_SPATIAL_MAX_DIM 1024
+#define GWBP_SPATIAL_MAX_CELLS (1 << 24)
+#define GWBP_SPATIAL_MIN_CELL 1e-30f
+GWBP_API int gwbp_spatial_cell_keys(int64_t n, const float *points, int64_t ldp, float lo_x, float lo_y, float lo_z,
+                                    float cell_size, int32_t nx, int32_t ny, int32_t nz, int32_t *keys, void *stream);
+GWBP_API int gwbp_spatial_build(int64_t n, const float *points, int64_t ldp, const int32_t *sorted_keys, const int64_t *perm,
+                                int64_t n_cells, float *sorted, int32_t *cell_start, void *stream);
+GWBP_API int gwbp_spatial_knn(int64_t n, const float *sorted, const int32_t *cell_start, float lo_x, float lo_y, float lo_z,
+                              float cell_size, int32_t nx, int32_t ny, int32_t nz, int64_t q, const float *queries, int64_t ldq,
+                              const int64_t *order, int32_t k, int32_t *idx, float *dist, void *stream);
+
+/* The average of a field over each row's neighbour list: out[g * ldo + c] = (sum over the valid j, in the list's order, of
+ * features[idx[g * k + j] * ldf + c]) / (the number of valid j), g < n, c < D, fp32.  An index outside [0, m) is skipped (the -1 of
+ * gwbp_spatial_knn); a row with no valid index is zero.  features is read in place at any row stride ldf >= D; out is another
+ * buffer, ldo >= D.  Rows whose addresses and strides are 16-B aligned move with 16-B loads and stores (same results).  No atomics.
+ * GWBP_EINVAL before any HIP call: n < 0, m < 1, D < 1, k outside [1, 32], a stride below D, a null or misaligned pointer,
+ * out == features. */
+GWBP_API int gwbp_neighbor_mean(int64_t n, int64_t m, int32_t D, int32_t k, const int32_t *idx, const float *features,
+                                int64_t ldf, float *out, int64_t ldo, void *stream);
+
 /* ---- PCA of a finished field (the reference's visualize_pca.py: sklearn PCA(3) on the host copy of the [N, D] field) -------------
  * The [N, D] passes of the fit and of the transform; the D x D eigen-decomposition between them is the caller's (float64 eigh of
  * gram / (N - 1); sklearn's covariance_eigh solver does the same).  X[g * ldx + 0..D-1], g < N, is read in place, fp32, any row
