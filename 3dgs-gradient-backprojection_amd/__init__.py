@@ -17,6 +17,8 @@ JojiJoseph/3dgs-gradient-backprojection), hand-written HIP kernels behind a C AB
                                                     # fitted on frozen Gaussians (the reference's Feature-3DGS baseline), fused
     from gsbp_amd import spatial_knn, knn_distances, init_scales  # which Gaussians are next to each other: exact 3-D k-NN on a grid
     from gsbp_amd import smooth_labels, smooth_mask, remove_outliers, smooth_features  # and a finished lift cleaned with it
+    from gsbp_amd import fit_kmeans, kmeans_assign, cluster_sums, class_prototypes  # a field clustered without prompts: k-means on
+    from gsbp_amd import quantize_field, dequantize_field, codebook_prompt_scores   # the matrix cores; the field as a codebook
 """
 from . import synthetic  # noqa: F401
 from ._lib import GwbpError, build, lib  # noqa: F401
@@ -32,4 +34,6 @@ from .fidelity import agreement_weights, field_fidelity, render_field_agreement,
 from .decoded_field import decode_field, decoded_field_gradients, decoded_loss, fit_decoded_field  # noqa: F401
 from . import spatial  # noqa: F401
 from .spatial import init_scales, knn_distances, plan_grid, remove_outliers, smooth_features, smooth_labels, smooth_mask, spatial_knn  # noqa: F401
+from . import cluster  # noqa: F401
+from .cluster import KMeans, class_prototypes, cluster_sums, codebook_prompt_mask, codebook_prompt_scores, dequantize_field, fit_kmeans, kmeans_assign, quantize_field, synthetic_clusters  # noqa: F401
 from .pruning import check_proper_pruning, gradient_mask, prune_by_gradients  # noqa: F401

@@ -199,6 +199,11 @@ ARGTYPES = {
     "gwbp_centered_gram": [_I64, _I32, _P, _I64, _P, _P, _P, _SZ, _P],
     "gwbp_pca_project": [_I64, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P],
     "gwbp_pca_colors": [_I64, _P, _P, _P, _P],
+    # clustering: N, K, D, X, ldx, C, ldc, b, label, best, stream  /  N, D, K, bytes*  /  N, D, K, X, ldx, w, order, start, sums, wsum,
+    # workspace, bytes, stream
+    "gwbp_kmeans_assign": [_I64, _I32, _I32, _P, _I64, _P, _I64, _P, _P, _P, _P],
+    "gwbp_cluster_workspace_size": [_I64, _I32, _I32, C.POINTER(C.c_size_t)],
+    "gwbp_cluster_sums": [_I64, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _SZ, _P],
     # queries: N, D, P, n_pos, X, ldx, prompts, normalize, threshold*, mask, scores, stream  /
     # M, xy, X, ldx, D, out, depth, alpha, stream
     "gwbp_prompt_scores": [_I64, _I32, _I32, _I32, _P, _I64, _P, _I32, C.POINTER(C.c_float), _P, _P, _P],

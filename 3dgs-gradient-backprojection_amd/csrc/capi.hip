@@ -1082,6 +1082,76 @@ int gwbp_pca_colors(int64_t n, const float *Y, const float *lo_hi, float *colors
     return launch_pca_colors(n, Y, lo_hi, colors, as_stream(stream));
 }
 
+// What the clustering entry points share: the sizes, and the field's stride and pointer, checked once for all of them.
+static int check_cluster_sizes(const char *what, int64_t N, int32_t K, int32_t D)
+{
+    if (N < 0)
+        return set_error(GWBP_EINVAL, "%s: N must not be negative (got %lld)", what, (long long)N);
+    if (K < 1 || K > GWBP_CLUSTER_MAX_K)
+        return set_error(GWBP_EINVAL, "%s: K must be in [1, %d] (got %d)", what, GWBP_CLUSTER_MAX_K, (int)K);
+    if (D < 1)
+        return set_error(GWBP_EINVAL, "%s: D must be positive (got %d)", what, (int)D);
+    return GWBP_OK;
+}
+
+static int check_cluster_rows(const char *what, int64_t N, int32_t K, int32_t D, const float *X, int64_t ldx)
+{
+    if (int rc = check_cluster_sizes(what, N, K, D))
+        return rc;
+    if (ldx < D)
+        return set_error(GWBP_EINVAL, "%s: row stride %lld of X below D = %d", what, (long long)ldx, (int)D);
+    if (N > 0 && !X)
+        return set_error(GWBP_EINVAL, "%s: null X", what);
+    if (reinterpret_cast<uintptr_t>(X) & 3)
+        return set_error(GWBP_EINVAL, "%s: X must be 4-B aligned", what);
+    return GWBP_OK;
+}
+
+int gwbp_kmeans_assign(int64_t N, int32_t K, int32_t D, const float *X, int64_t ldx, const float *C, int64_t ldc, const float *b,
+                       int32_t *label, float *best, void *stream)
+{
+    if (int rc = check_cluster_rows("kmeans_assign", N, K, D, X, ldx))
+        return rc;
+    if (ldc < D)
+        return set_error(GWBP_EINVAL, "kmeans_assign: row stride ldc = %lld of C below D = %d", (long long)ldc, (int)D);
+    if (!C || (N > 0 && (!label || !best)))
+        return set_error(GWBP_EINVAL, "kmeans_assign: null C, label or best");
+    if ((reinterpret_cast<uintptr_t>(C) & 3) || (reinterpret_cast<uintptr_t>(b) & 3) || (reinterpret_cast<uintptr_t>(label) & 3) ||
+        (reinterpret_cast<uintptr_t>(best) & 3))
+        return set_error(GWBP_EINVAL, "kmeans_assign: C, b, label and best must be 4-B aligned");
+    return launch_kmeans_assign(N, K, D, X, ldx, C, ldc, b, label, best, as_stream(stream));
+}
+
+int gwbp_cluster_workspace_size(int64_t N, int32_t D, int32_t K, size_t *bytes)
+{
+    if (int rc = check_cluster_sizes("cluster_workspace_size", N, K, D))
+        return rc;
+    if (!bytes)
+        return set_error(GWBP_EINVAL, "cluster_workspace_size: null bytes");
+    *bytes = cluster_workspace_bytes(N, D, K);
+    return GWBP_OK;
+}
+
+int gwbp_cluster_sums(int64_t N, int32_t D, int32_t K, const float *X, int64_t ldx, const float *w, const int64_t *order,
+                      const int64_t *start, double *sums, double *wsum, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (int rc = check_cluster_rows("cluster_sums", N, K, D, X, ldx))
+        return rc;
+    if (!start || (N > 0 && !order))
+        return set_error(GWBP_EINVAL, "cluster_sums: null start or order");
+    if (!sums || !wsum || !workspace)
+        return set_error(GWBP_EINVAL, "cluster_sums: null sums, wsum or workspace");
+    if (reinterpret_cast<uintptr_t>(w) & 3)
+        return set_error(GWBP_EINVAL, "cluster_sums: w must be 4-B aligned");
+    if ((reinterpret_cast<uintptr_t>(order) & 7) || (reinterpret_cast<uintptr_t>(start) & 7) || (reinterpret_cast<uintptr_t>(sums) & 7) ||
+        (reinterpret_cast<uintptr_t>(wsum) & 7) || (reinterpret_cast<uintptr_t>(workspace) & 7))
+        return set_error(GWBP_EINVAL, "cluster_sums: order, start, sums, wsum and the workspace must be 8-B aligned");
+    const size_t need = cluster_workspace_bytes(N, D, K);
+    if (workspace_bytes < need)
+        return set_error(GWBP_EWORKSPACE, "cluster_sums: workspace has %zu bytes, needs %zu", workspace_bytes, need);
+    return launch_cluster_sums(N, D, K, X, ldx, w, order, start, sums, wsum, workspace, as_stream(stream));
+}
+
 // The field as the two queries read it: D, the row stride and the pointer, checked once for both.
 static int check_field_rows(const char *what, int32_t D, const float *X, int64_t ldx)
 {

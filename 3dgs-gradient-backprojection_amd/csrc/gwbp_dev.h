@@ -298,6 +298,13 @@ int launch_centered_gram(int64_t N, int D, const float *X, int64_t ldx, const fl
 int launch_pca_project(int64_t N, int D, int k, const float *X, int64_t ldx, const float *mean, const float *V, float *Y,
                        float *minmax, hipStream_t s);
 int launch_pca_colors(int64_t n, const float *Y, const float *lo_hi, float *colors, hipStream_t s);
+// clustering a finished field (cluster.hip): the k-means assignment (k_knn_search's score + a per-centroid bias, argmax only) and
+// the per-cluster float64 column sums of rows grouped by the caller.  ws: the caller's cluster_workspace_bytes(N, D, K) bytes.
+int launch_kmeans_assign(int64_t N, int K, int D, const float *X, int64_t ldx, const float *C, int64_t ldc, const float *bias,
+                         int32_t *label, float *best, hipStream_t s);
+size_t cluster_workspace_bytes(int64_t N, int D, int K);
+int launch_cluster_sums(int64_t N, int D, int K, const float *X, int64_t ldx, const float *w, const int64_t *order,
+                        const int64_t *start, double *sums, double *wsum, void *ws, hipStream_t s);
 // questions asked of a finished field (query.hip): prompt scores + 3-D mask in one pass over X; the field rendered at M pixels
 // of a projected and sorted view.  threshold: host pointer or nullptr.
 int launch_prompt_scores(int64_t N, int D, int P, int n_pos, const float *X, int64_t ldx, const float *prompts, int normalize,

@@ -8,8 +8,9 @@
 // sources, finishes each 128 x 128 score tile over the full D on the fp32 matrix cores, drops it into LDS (over the operand
 // staging, which is idle by then) and lets the thread that owns a query scan its row against the query's current k-th best.
 //
-// ARITHMETIC CONTRACT.  A score is ONE chain of fp32 fused multiply-adds over the D index, starting from +0, in an order that
-// depends only on D: v_mfma_f32_16x16x4_f32 is bit for bit a k-ordered chain of fmaf (see encode.hip), and every output element
+// ARITHMETIC CONTRACT (the staging and the MFMA tile are knn_tile.h, shared with cluster.hip's k_kmeans_assign).  A score is ONE
+// chain of fp32 fused multiply-adds over the D index, starting from +0, in an order that depends only on D:
+// v_mfma_f32_16x16x4_f32 is bit for bit a k-ordered chain of fmaf (see encode.hip), and every output element
 // of every tile consumes k = 32 c + 16 b + 4 q + i in the order (c, b, i, q) -- chunk, 16-block, MFMA step, slot.  Columns D ..
 // 32 ceil(D / 32) - 1 are zero-filled in LDS for queries and sources alike (fmaf(0, 0, acc) == acc).  The chain does not depend on
 // the row's position in Q or S, on N, M, k or the grid, so: permuting Q's rows permutes the result rows bit for bit; identical
@@ -22,36 +23,13 @@
 // Every loop has a trip count that is uniform over the workgroup (tiles, chunks, k, the 128 columns of a score row); the rare
 // insert runs under a lane mask inside such a loop, never as a loop of its own.
 #include "gwbp_dev.h"
+#include "knn_tile.h"
 
 namespace gwbp {
 
 namespace {
 
-constexpr int kKnnThreads = 256;         // 4 waves, 2 (queries) x 2 (sources); each wave owns a 64 x 64 block of the score tile
-constexpr int kKnnQ = 128;               // queries per workgroup
-constexpr int kKnnS = 128;               // sources per tile
-constexpr int kKnnKC = 32;               // D-chunk staged per step
-constexpr int kKnnLd = kKnnKC + 4;       // LDS row stride of a staged chunk (floats): 16 rows x ds_read_b128 hit 64 distinct banks
-constexpr int kKnnScoreLd = kKnnS + 4;   // LDS row stride of the score tile
-constexpr int kKnnStage = (kKnnQ + kKnnS) * kKnnLd; // floats of one staging buffer (queries, then sources)
 constexpr int kKnnMaxK = 32;
-static_assert(2 * kKnnStage >= kKnnQ * kKnnScoreLd, "the score tile lies over the two staging buffers");
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ u32 score_key(float s)
-{
-    if (s != s)
-        return 0u;
-    const u32 b = __float_as_uint(s + 0.0f); // -0 -> +0
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float key_score(u32 key)
-{
-    if (key == 0u)
-        return __uint_as_float(0x7FC00000u);
-    return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(kKnnThreads) void k_knn_search(int64_t N, int M, int D, int k, const float *__restrict__ Q,
@@ -59,22 +37,10 @@ __global__ __launch_bounds__(kKnnThreads) void k_knn_search(int64_t N, int M, in
                                                             int32_t *__restrict__ idx, float *__restrict__ score)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float *stage = smem;                                          // [2][kKnnQ + kKnnS][kKnnLd]; the score tile lies over it
     u64 *list = reinterpret_cast<u64 *>(smem + 2 * kKnnStage);    // [k][kKnnQ] keys of the running top-k, unordered
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wq = wave >> 1, ws = wave & 1;
-    const int m = lane & 15, qd = lane >> 4;
+    const int tid = threadIdx.x;
     const int64_t q0 = (int64_t)blockIdx.x * kKnnQ;
-
-    // staging role: float4 column c4 of rows r0 + 32 i (i < 4) of the query block and of the source tile
-    const int c4 = (tid & 7) * 4, r0 = tid >> 3;
-    const float *qrow[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int64_t g = q0 + r0 + 32 * i;
-        qrow[i] = g < N ? Q + g * ldq : nullptr;
-    }
 
     // selection role (threads 0..127): query q0 + tid, its k-th best key and that key's score
     u64 thr = 0;
@@ -84,126 +50,40 @@ __global__ __launch_bounds__(kKnnThreads) void k_knn_search(int64_t N, int M, in
         for (int j = 0; j < k; ++j)
             list[j * kKnnQ + tid] = 0; // below every candidate: key 0 with index 0xFFFFFFFF
 
-    const int n_chunk = (D + kKnnKC - 1) / kKnnKC;
-    const int n_tile = (M + kKnnS - 1) / kKnnS;
-    const int64_t n_it = (int64_t)n_tile * n_chunk;
-
-    float4 pq[4], ps[4];
-    auto prefetch = [&](int tile, int chunk) {
-        const int c = chunk * kKnnKC + c4;
+    knn_score_tiles<VEC>(N, M, D, Q, ldq, S, lds_, smem, [&](int tile, const float *sc) {
+        if (tid < kKnnQ) {
+            const u32 s0 = (u32)tile * kKnnS;
+            const float *row = sc + tid * kKnnScoreLd;
+            for (int c = 0; c < kKnnS; c += 4) { // uniform trip count; columns at or beyond M are masked
+                const float4 v = *reinterpret_cast<const float4 *>(row + c);
+                const float vs[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            pq[i] = load4<VEC>(qrow[i], c, D);
-            const u32 j = (u32)tile * kKnnS + r0 + 32 * i; // (M < 2^31: no wrap)
-            ps[i] = load4<VEC>(j < (u32)M ? S + (int64_t)j * lds_ : nullptr, c, D);
-        }
-    };
-    prefetch(0, 0);
-
-    f32x4 acc[4][4]; // [source block a][query block b]: lane holds query 16 b + m, sources 16 a + 4 qd + r
-    int tile = 0, chunk = 0;
-    for (int64_t it = 0; it < n_it; ++it) {
-        if (chunk == 0) {
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b)
-                    acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        float *buf = stage + (it & 1) * kKnnStage;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            *reinterpret_cast<float4 *>(buf + (r0 + 32 * i) * kKnnLd + c4) = pq[i];
-            *reinterpret_cast<float4 *>(buf + (kKnnQ + r0 + 32 * i) * kKnnLd + c4) = ps[i];
-        }
-        __syncthreads();
-        int ntile = tile, nchunk = chunk + 1;
-        if (nchunk == n_chunk) {
-            nchunk = 0;
-            ++ntile;
-        }
-        if (it + 1 < n_it)
-            prefetch(ntile, nchunk); // in flight beside this chunk's MFMAs
-
-        const float *bq = buf + (wq * 64 + m) * kKnnLd + 4 * qd;
-        const float *bs = buf + (kKnnQ + ws * 64 + m) * kKnnLd + 4 * qd;
-#pragma unroll
-        for (int kb = 0; kb < kKnnKC / 16; ++kb) {
-            float4 fa[4], fb[4];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                fa[a] = *reinterpret_cast<const float4 *>(bs + a * 16 * kKnnLd + kb * 16);
-                fb[a] = *reinterpret_cast<const float4 *>(bq + a * 16 * kKnnLd + kb * 16);
-            }
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b)
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[a].x, fb[b].x, acc[a][b], 0, 0, 0);
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b)
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[a].y, fb[b].y, acc[a][b], 0, 0, 0);
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b)
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[a].z, fb[b].z, acc[a][b], 0, 0, 0);
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b)
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[a].w, fb[b].w, acc[a][b], 0, 0, 0);
-        }
-
-        if (chunk == n_chunk - 1) {
-            // the tile's scores are complete: drop them into LDS as tile[query][source] and select
-            __syncthreads(); // every wave is done reading the staging buffers
-            float *sc = smem;
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b)
-                    *reinterpret_cast<f32x4 *>(sc + (wq * 64 + b * 16 + m) * kKnnScoreLd + ws * 64 + a * 16 + 4 * qd) = acc[a][b];
-            __syncthreads();
-            if (tid < kKnnQ) {
-                const u32 s0 = (u32)tile * kKnnS;
-                const float *row = sc + tid * kKnnScoreLd;
-                for (int c = 0; c < kKnnS; c += 4) { // uniform trip count; columns at or beyond M are masked
-                    const float4 v = *reinterpret_cast<const float4 *>(row + c);
-                    const float vs[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const u32 j = s0 + c + u;
-                        // a score below the k-th best is out (almost every one after the first tiles); equal, NaN, or an open
-                        // list (thr_f NaN) go on to the exact comparison of the keys
-                        if (j < (u32)M && !(vs[u] < thr_f)) {
-                            const u64 key = ((u64)score_key(vs[u]) << 32) | (u64)(0xFFFFFFFFu - j);
-                            if (key > thr) {
-                                list[thr_at * kKnnQ + tid] = key; // replaces the k-th best; find the new one
-                                u64 lo = key;
-                                int at = thr_at;
-                                for (int t = 0; t < k; ++t) {
-                                    const u64 e = list[t * kKnnQ + tid];
-                                    if (e < lo) {
-                                        lo = e;
-                                        at = t;
-                                    }
+                for (int u = 0; u < 4; ++u) {
+                    const u32 j = s0 + c + u;
+                    // a score below the k-th best is out (almost every one after the first tiles); equal, NaN, or an open
+                    // list (thr_f NaN) go on to the exact comparison of the keys
+                    if (j < (u32)M && !(vs[u] < thr_f)) {
+                        const u64 key = ((u64)score_key(vs[u]) << 32) | (u64)(0xFFFFFFFFu - j);
+                        if (key > thr) {
+                            list[thr_at * kKnnQ + tid] = key; // replaces the k-th best; find the new one
+                            u64 lo = key;
+                            int at = thr_at;
+                            for (int t = 0; t < k; ++t) {
+                                const u64 e = list[t * kKnnQ + tid];
+                                if (e < lo) {
+                                    lo = e;
+                                    at = t;
                                 }
-                                thr = lo;
-                                thr_at = at;
-                                thr_f = key_score((u32)(lo >> 32));
                             }
+                            thr = lo;
+                            thr_at = at;
+                            thr_f = key_score((u32)(lo >> 32));
                         }
                     }
                 }
             }
-            __syncthreads(); // the score tile is consumed before the next chunk is staged over it
         }
-        tile = ntile;
-        chunk = nchunk;
-    }
+    });
 
     // the k keys of each query in descending order: k passes, each takes the largest key that is left
     if (tid < kKnnQ && q0 + tid < N) {

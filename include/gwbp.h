@@ -573,6 +573,46 @@ GWBP_API int gwbp_pca_project(int64_t N, int32_t D, int32_t k, const float *X, i
  * channel: visualize_pca.py takes np.min / np.max over all three); hi == lo gives 0.5 everywhere.  colors may alias Y. */
 GWBP_API int gwbp_pca_colors(int64_t n, const float *Y, const float *lo_hi, float *colors, void *stream);
 
+/* ---- Clustering a finished field: the two [N, D] passes of a k-means (Lloyd) step (cluster.hip) -----------------------------------
+ * gwbp_kmeans_assign: for every row X[g * ldx + 0..D-1], g < N, against the K centroid rows C[j * ldc + 0..D-1]:
+ *   score(g, j) = <X[g, :], C[j, :]> + b[j],   label[g] = argmax_j score(g, j) (int32 [N]),   best[g] = that score (fp32 [N]).
+ * The inner product is gwbp_knn_search's score bit for bit: one chain of fp32 fused multiply-adds over the D index in an order that
+ * depends only on D (the fp32 matrix cores; no reduced-precision operand).  b (fp32 [K], may be NULL): with NULL the score is the
+ * chain itself -- the cosine / inner-product metric, and label / best equal column 0 of gwbp_knn_search(..., k = 1) bit for bit on
+ * rows that have a score that is a number; otherwise ONE fp32 addition of b[j] follows the finished chain.  b[j] = -|c_j|^2 / 2
+ * (computed by the caller in float64, rounded once) makes the argmax the Euclidean nearest centroid.  Ties go to the lowest index,
+ * -0 counts as +0 (and is returned as +0); a NaN score orders after every number and is never chosen: a row whose scores are all
+ * NaN gets label -1 and best NaN.  No score reaches global memory, there is no top-k list and no workspace.  X and C are read in
+ * place at any row stride >= D (in floats); rows whose addresses and strides are 16-B aligned are read with 16-B loads, others
+ * element by element (same results).  1 <= K <= GWBP_CLUSTER_MAX_K, D >= 1.
+ * GWBP_EINVAL before any HIP call: N < 0, K < 1 or K > GWBP_CLUSTER_MAX_K, D < 1, ldx < D, ldc < D, a null X (N > 0), C, label or
+ * best (N > 0), a pointer that is not 4-B aligned. */
+#define GWBP_CLUSTER_MAX_K (1 << 20)
+#define GWBP_CLUSTER_RUN 256 /* members per run of gwbp_cluster_sums: part of its arithmetic contract */
+GWBP_API int gwbp_kmeans_assign(int64_t N, int32_t K, int32_t D, const float *X, int64_t ldx, const float *C, int64_t ldc,
+                                const float *b, int32_t *label, float *best, void *stream);
+
+/* Bytes of device workspace gwbp_cluster_sums needs: the per-run partial sums, (min(N, ceil(N / GWBP_CLUSTER_RUN) + K)) x (D + 1)
+ * float64, plus K + 1 int64.  The workspace carries nothing between calls.  GWBP_EINVAL: N < 0, K or D out of range, null bytes. */
+GWBP_API int gwbp_cluster_workspace_size(int64_t N, int32_t D, int32_t K, size_t *bytes);
+
+/* Per-cluster, optionally weighted, column sums of the rows of X (the k-means update; the class prototypes of a labelling):
+ *   sums[k * D + c] = sum_{g: label[g] = k} w[g] X[g * ldx + c]  (float64, dense [K, D]),   wsum[k] = sum w[g]  (float64 [K]).
+ * The caller groups the rows first: order[N] (int64) lists the rows by label ascending, row index ascending inside a label (a
+ * STABLE sort of the labels), and start[K + 1] (int64) holds the first position of every label in it, start[K] the end of label
+ * K - 1.  Rows before start[0] and from start[K] on -- labels outside [0, K) -- take no part.  w (fp32 [N], may be NULL: weights
+ * of 1) is indexed by row.  Contract: every term w x is formed in float64 (exact); a cluster's member list is cut into runs of
+ * GWBP_CLUSTER_RUN members; each (run, column) is summed in float64 in ascending member order; a cluster's runs are added in
+ * ascending order; no atomics.  The result depends on (X, labels, w) alone: two runs, another stream, another alignment (16-B
+ * loads where addresses allow, element loads otherwise) give the same bits.  A cluster without members gets a zero row and wsum 0.
+ * Entries of order outside [0, N) are skipped and start values are clamped into [0, N]: no call reads outside X.
+ * GWBP_EINVAL before any HIP call: N < 0, K < 1 or K > GWBP_CLUSTER_MAX_K, D < 1, ldx < D, a null X or order (N > 0), a null
+ * start, sums, wsum or workspace, a pointer that is not aligned to its element (X, w: 4 B; the others: 8 B);
+ * GWBP_EWORKSPACE: a workspace below gwbp_cluster_workspace_size. */
+GWBP_API int gwbp_cluster_sums(int64_t N, int32_t D, int32_t K, const float *X, int64_t ldx, const float *w, const int64_t *order,
+                               const int64_t *start, double *sums, double *wsum, void *workspace, size_t workspace_bytes,
+                               void *stream);
+
 /* ---- questions asked of a finished field (the reference's segment.py, segment_compressed.py, click_and_segment.py) ---------------
  * Scores of every row of X[g * ldx + 0..D-1], g < N, against P prompt vectors prompts[j * D + 0..D-1] (dense), and the 3-D mask of
  * get_mask3d_lseg, in ONE pass over X; no workspace, no view.
