@@ -8,7 +8,10 @@
 // ARITHMETIC CONTRACT of k_prompt_scores (the shape of k_pca_project's, pca.hip).  Every dot product AND the row's sum of squares
 // is one chain of fp32 fused multiply-adds over the channel index (v_mfma_f32_16x16x4_f32 is bit for bit a k-ordered fmaf chain; the
 // sum of squares is the diagonal of the row block's own 16 x 16 product, so it runs through the columns in the very order of the
-// dot products), in an order that depends only on D.  The norm is one correctly rounded sqrt, the score one correctly rounded
+// dot products), in an order that depends only on D: every chain consumes k = 32 c + 16 b + 4 q + i in the order (c, b, i, q) --
+// the 32-column chunk staged per step, its 16-column block, the float4 component that feeds one MFMA, the quarter wave (the MFMA's
+// k slot) -- which is knn_tile.h's order.  Columns D .. 32 ceil(D / 32) - 1 are zero-filled in LDS and their steps are executed
+// (fmaf(0, 0, acc) == acc, but -0 becomes +0).  The norm is one correctly rounded sqrt, the score one correctly rounded
 // divide.  Nothing depends on the row's position, on N, on P (the 16 prompts of a block are independent output columns) or on the
 // launch; rows whose address and stride are 16-B aligned are read with 16-B loads, others element by element: same values, same
 // chains.  Padding beyond D is never read (load4 masks it).  No atomics.  The two maxima propagate NaN as torch.max does, so a NaN

@@ -2,10 +2,11 @@
 
 brute(): all distances in float64, each row ordered by (distance, index).
 grid_knn_ref(): a numpy mirror IN FLOAT32 of the kernel's cell assignment, ring walk and stop rule -- the only way to check the stop
-rule without a GPU.  Its fused multiply-adds are float64 products and sums rounded once to float32, which is the fp32 fmaf
-whenever the float64 sum is exact (always on the lattice sets the tests use).
+rule without a GPU.  Its fused multiply-adds are chain_ref.fma32: the fp32 fmaf, correctly rounded on every input.
 """
 import numpy as np
+
+from chain_ref import fma32  # noqa: F401  (d2_f32 below; the tests call it by this name)
 
 F = np.float32
 NO_INDEX = 0x7FFFFFFF
@@ -58,10 +59,6 @@ def build(points, lo, h, dims):
     cells = dims[0] * dims[1] * dims[2]
     cell_start = np.searchsorted(keys[perm], np.arange(cells + 1), side="left")
     return p[perm], perm, cell_start
-
-
-def fma32(a, b, c):
-    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(F)
 
 
 def d2_f32(p, q):

@@ -5,7 +5,9 @@ Every row of every case passes checks 1-4 (knn_ref.check_rows): distinct in-rang
 each score within eps / 2 of the float64 score of its index; each index's float64 score at least the float64 k-th best - eps; label
 and counts equal bincount().argmax() and the histogram of the row's own indices.  Rows whose float64 gap between the k-th and
 (k+1)-th best exceeds eps also pass check 5: the index set and the label equal the reference's.  At most 1 % of a case's rows may be
-left out of check 5, asserted on the reference alone before the kernel's output is looked at."""
+left out of check 5, asserted on the reference alone before the kernel's output is looked at.  (At shapes small enough to mirror,
+tests/test_gpu_chain_exact.py compares every score and index list with the documented fmaf chain bit for bit, D = 1024 / 1028
+included; the bounds here cover the shapes too large for that.)"""
 import numpy as np
 import pytest
 import torch
