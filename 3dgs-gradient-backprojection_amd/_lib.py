@@ -192,6 +192,13 @@ ARGTYPES = {
     "gwbp_spatial_build": [_I64, _P, _I64, _P, _P, _I64, _P, _P, _P],
     "gwbp_spatial_knn": [_I64, _P, _P, _F, _F, _F, _F, _I32, _I32, _I32, _I64, _P, _I64, _P, _I32, _P, _P, _P],
     "gwbp_neighbor_mean": [_I64, _I64, _I32, _I32, _P, _P, _I64, _P, _I64, _P],
+    # radius components: n, sorted, cell_start, lo_x, lo_y, lo_z, cell_size, nx, ny, nz, group, r2, then  q, queries, ldq, order,
+    # query_group, cap, count, visited, stream  /  count, min_points, parent, status, stream  /  count, min_points, attach, stream;
+    # n, count, min_points, attach, parent, root, status, stream
+    "gwbp_radius_count": [_I64, _P, _P, _F, _F, _F, _F, _I32, _I32, _I32, _P, _F, _I64, _P, _I64, _P, _P, _I32, _P, _P, _P],
+    "gwbp_radius_union": [_I64, _P, _P, _F, _F, _F, _F, _I32, _I32, _I32, _P, _F, _P, _I32, _P, _P, _P],
+    "gwbp_radius_attach": [_I64, _P, _P, _F, _F, _F, _F, _I32, _I32, _I32, _P, _F, _P, _I32, _P, _P],
+    "gwbp_components_flatten": [_I64, _P, _I32, _P, _P, _P, _P, _P],
     # PCA: N, D, bytes*  /  N, D, X, ldx, mean, workspace, bytes, stream  /  N, D, X, ldx, mean, gram, workspace, bytes, stream  /
     # N, D, k, X, ldx, mean, components, Y, minmax, stream  /  n, Y, lo_hi, colors, stream
     "gwbp_pca_workspace_size": [_I64, _I32, C.POINTER(C.c_size_t)],

@@ -1008,6 +1008,99 @@ int gwbp_neighbor_mean(int64_t n, int64_t m, int32_t D, int32_t k, const int32_t
     return launch_neighbor_mean(n, m, D, k, idx, features, ldf, out, ldo, as_stream(stream));
 }
 
+// what the three walks of the radius components share: the built grid of n points, r2 and (when not null) aligned int32 arrays
+static int check_radius_walk(const char *what, int64_t n, const float *sorted, const int32_t *cell_start, float lo_x, float lo_y,
+                             float lo_z, float h, int32_t nx, int32_t ny, int32_t nz, const int32_t *group, float r2)
+{
+    if (n < 1 || n > 0x7FFFFFFF)
+        return set_error(GWBP_EINVAL, "%s: bad number of points (%lld): 1 .. 2^31 - 1", what, (long long)n);
+    if (!(r2 >= 0.0f))
+        return set_error(GWBP_EINVAL, "%s: r2 must be >= 0 (got %g)", what, (double)r2);
+    if (int rc = check_spatial_grid(what, lo_x, lo_y, lo_z, h, nx, ny, nz))
+        return rc;
+    if (!sorted || !cell_start)
+        return set_error(GWBP_EINVAL, "%s: null sorted or cell_start", what);
+    if (reinterpret_cast<uintptr_t>(sorted) & 15)
+        return set_error(GWBP_EINVAL, "%s: sorted must be 16-B aligned", what);
+    if ((reinterpret_cast<uintptr_t>(cell_start) & 3) || (reinterpret_cast<uintptr_t>(group) & 3))
+        return set_error(GWBP_EINVAL, "%s: cell_start and group must be 4-B aligned", what);
+    return GWBP_OK;
+}
+
+int gwbp_radius_count(int64_t n, const float *sorted, const int32_t *cell_start, float lo_x, float lo_y, float lo_z, float cell_size,
+                      int32_t nx, int32_t ny, int32_t nz, const int32_t *group, float r2, int64_t q, const float *queries,
+                      int64_t ldq, const int64_t *order, const int32_t *query_group, int32_t cap, int32_t *count, int32_t *visited,
+                      void *stream)
+{
+    if (int rc = check_radius_walk("radius_count", n, sorted, cell_start, lo_x, lo_y, lo_z, cell_size, nx, ny, nz, group, r2))
+        return rc;
+    if (cap < 1)
+        return set_error(GWBP_EINVAL, "radius_count: cap must be at least 1 (got %d)", (int)cap);
+    if (int rc = check_spatial_points("radius_count", "queries", q, queries, ldq))
+        return rc;
+    if (q > 0 && (!order || !count))
+        return set_error(GWBP_EINVAL, "radius_count: null order or count");
+    if ((reinterpret_cast<uintptr_t>(order) & 7) || (reinterpret_cast<uintptr_t>(query_group) & 3) ||
+        (reinterpret_cast<uintptr_t>(count) & 3) || (reinterpret_cast<uintptr_t>(visited) & 3))
+        return set_error(GWBP_EINVAL, "radius_count: order must be 8-B aligned, query_group, count and visited 4-B");
+    const float lo[3] = {lo_x, lo_y, lo_z};
+    const int32_t dims[3] = {nx, ny, nz};
+    return launch_radius_count(sorted, cell_start, lo, cell_size, dims, group, r2, q, queries, ldq, order, query_group, cap, count,
+                               visited, as_stream(stream));
+}
+
+int gwbp_radius_union(int64_t n, const float *sorted, const int32_t *cell_start, float lo_x, float lo_y, float lo_z, float cell_size,
+                      int32_t nx, int32_t ny, int32_t nz, const int32_t *group, float r2, const int32_t *count, int32_t min_points,
+                      int32_t *parent, int32_t *status, void *stream)
+{
+    if (int rc = check_radius_walk("radius_union", n, sorted, cell_start, lo_x, lo_y, lo_z, cell_size, nx, ny, nz, group, r2))
+        return rc;
+    if (min_points < 1)
+        return set_error(GWBP_EINVAL, "radius_union: min_points must be at least 1 (got %d)", (int)min_points);
+    if (!count || !parent || !status)
+        return set_error(GWBP_EINVAL, "radius_union: null count, parent or status");
+    if ((reinterpret_cast<uintptr_t>(count) & 3) || (reinterpret_cast<uintptr_t>(parent) & 3) || (reinterpret_cast<uintptr_t>(status) & 3))
+        return set_error(GWBP_EINVAL, "radius_union: count, parent and status must be 4-B aligned");
+    const float lo[3] = {lo_x, lo_y, lo_z};
+    const int32_t dims[3] = {nx, ny, nz};
+    return launch_radius_union(n, sorted, cell_start, lo, cell_size, dims, group, r2, count, min_points, parent, status,
+                               as_stream(stream));
+}
+
+int gwbp_radius_attach(int64_t n, const float *sorted, const int32_t *cell_start, float lo_x, float lo_y, float lo_z, float cell_size,
+                       int32_t nx, int32_t ny, int32_t nz, const int32_t *group, float r2, const int32_t *count, int32_t min_points,
+                       int32_t *attach, void *stream)
+{
+    if (int rc = check_radius_walk("radius_attach", n, sorted, cell_start, lo_x, lo_y, lo_z, cell_size, nx, ny, nz, group, r2))
+        return rc;
+    if (min_points < 1)
+        return set_error(GWBP_EINVAL, "radius_attach: min_points must be at least 1 (got %d)", (int)min_points);
+    if (!count || !attach)
+        return set_error(GWBP_EINVAL, "radius_attach: null count or attach");
+    if ((reinterpret_cast<uintptr_t>(count) & 3) || (reinterpret_cast<uintptr_t>(attach) & 3))
+        return set_error(GWBP_EINVAL, "radius_attach: count and attach must be 4-B aligned");
+    const float lo[3] = {lo_x, lo_y, lo_z};
+    const int32_t dims[3] = {nx, ny, nz};
+    return launch_radius_attach(n, sorted, cell_start, lo, cell_size, dims, group, r2, count, min_points, attach, as_stream(stream));
+}
+
+int gwbp_components_flatten(int64_t n, const int32_t *count, int32_t min_points, const int32_t *attach, int32_t *parent,
+                            int32_t *root, int32_t *status, void *stream)
+{
+    if (n < 1 || n > 0x7FFFFFFF)
+        return set_error(GWBP_EINVAL, "components_flatten: bad number of points (%lld): 1 .. 2^31 - 1", (long long)n);
+    if (min_points < 1)
+        return set_error(GWBP_EINVAL, "components_flatten: min_points must be at least 1 (got %d)", (int)min_points);
+    if (!count || !parent || !root || !status)
+        return set_error(GWBP_EINVAL, "components_flatten: null count, parent, root or status");
+    if ((reinterpret_cast<uintptr_t>(count) & 3) || (reinterpret_cast<uintptr_t>(attach) & 3) || (reinterpret_cast<uintptr_t>(parent) & 3) ||
+        (reinterpret_cast<uintptr_t>(root) & 3) || (reinterpret_cast<uintptr_t>(status) & 3))
+        return set_error(GWBP_EINVAL, "components_flatten: count, attach, parent, root and status must be 4-B aligned");
+    if (root == parent)
+        return set_error(GWBP_EINVAL, "components_flatten: root must not be parent");
+    return launch_components_flatten(n, count, min_points, attach, parent, root, status, as_stream(stream));
+}
+
 // the checks the two passes of the fit share
 static int check_pca_rows(const char *what, int64_t N, int32_t D, const float *X, int64_t ldx, const void *workspace,
                           size_t workspace_bytes)

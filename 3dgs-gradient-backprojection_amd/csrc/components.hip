@@ -1,0 +1,320 @@
+// components.hip -- which points form one object: connected components of 3-D points under "within a radius of each other, and in
+// the same group", as DBSCAN with a deterministic border rule (sklearn DBSCAN / Open3D cluster_dbscan / PCL Euclidean cluster
+// extraction; the reference would run sklearn on a host copy, as for its only neighbour search, f3dgs/utils_simple_trainer.py:141-145).
+// On the grid of spatial.hip: gwbp_spatial_cell_keys, the host's stable sort and gwbp_spatial_build make the sorted points
+// (x, y, z, original index) and cell_start; spatial_grid.h holds the one cell expression and the bounds both files use.
+//
+//   d2(p, q) = fmaf(dz, dz, fmaf(dy, dy, dx * dx)),  dx = p.x - q.x (fp32; symmetric);   r2 = the host's fp32 radius * radius
+//   live(i)      = finite coordinates and group[i] >= 0 (no group: every finite point)
+//   i ~ j        = both live, group[i] == group[j], d2 <= r2            (a point is its own neighbour)
+//   count[i]     = |{j : i ~ j}|;   core(i) = count[i] >= min_points
+//   components   = the classes of the core points under chains of ~ through core points; a live non-core point with a core
+//                  neighbour goes with its nearest core neighbour by (d2, index); everything else is noise
+//
+// RADIUS WALK.  One lane per query, queries in the order of their cell keys.  Rings of Chebyshev radius r = 0, 1, 2, ... around the
+// query's cell, clipped to the grid, with the empty-slab skip and the x-run spans of k_spatial_knn.  The lane stops after ring r
+// when r2 < fl(LB * LB), STRICTLY, LB the smallest of bound_above / bound_below over the sides that still have cells, and when no
+// side has cells left.  spatial.hip's argument carries over unchanged: after ring r an unvisited point p sits in a cell at least
+// r + 1 away from the query's along some axis; the rounded cell assignment puts its exact distance along that axis at LB or more
+// (LB keeps a margin for the roundings of the assignment and of its own expression); rounding is monotone, so the COMPUTED
+// |dx| >= LB, fl(dx * dx) >= fl(LB * LB), and each fmaf adds a non-negative term before a monotone rounding: every unvisited point
+// has a computed d2 >= fl(LB * LB) > r2 and is no neighbour.  (Strictly: a point at exactly the bound may have d2 == r2, which
+// counts.)  The margin errs towards one more ring, never towards stopping.  Trip count: at most max(nx, ny, nz) + 1.  Nothing in
+// the walk depends on which cell a point was assigned to beyond that bound, so the set of neighbours found is the brute-force
+// set, whatever the grid.
+//
+// UNION-FIND BY INDEX (k_radius_union, k_components_flatten).  parent[v] is the identity on entry.
+//   - A hook is an agent-scope compare-and-swap parent[ra]: ra -> rb with rb < ra, on a ROOT ra (it succeeds only while parent[ra]
+//     == ra).  Path halving lowers parent[v] of a NON-root v to its grandparent with an agent-scope atomic min.  Both store a
+//     smaller index of the same component over a larger one, so parent[v] <= v always, parent[v] never grows, and a node that
+//     has stopped being a root never becomes one again.
+//   - find therefore walks strictly decreasing indices: at most n steps, whatever value it reads -- a stale read (the per-XCD L2s are
+//     not coherent with each other; the loads are relaxed agent-scope atomic loads) is an older, larger ancestor of the same
+//     component, and the walk from it ends at a node that was a root when it was read.
+//   - unite(a, b): ra = find(a), rb = find(b); equal: done (they were joined when the later of the two was read).  Otherwise hook the
+//     larger under the smaller.  A failed swap returns the value another lane stored there, an ancestor of ra below ra; the retry
+//     starts from THAT value (not from a plain re-read), so max(ra, rb) strictly decreases from one try to the next: at most n
+//     tries.  After a successful hook a and b have a common ancestor for good, since links are only ever replaced by links to
+//     ancestors.
+//   - A component's final root is its smallest member: a root is never hooked under a larger index, and when all unites are done
+//     every pair i ~ j of core points shares its root, hence a whole component does, and the smallest member can have no parent but
+//     itself.  The roots are read in a launch of their own (k_components_flatten), where every hook is visible.
+//   - No lane ever waits for a value another lane has yet to write: no flag, no lock, no barrier; every loop ends by its own
+//     progress.  Each loop still carries a trip cap of n + 1 that the argument above rules out; reaching it sets *status, which the
+//     host turns into an error.
+// The results do not depend on the order of the hooks: the partition is the transitive closure of the united pairs, and the root is
+// a function of the partition.
+#include "gwbp_dev.h"
+#include "spatial_grid.h"
+
+namespace gwbp {
+
+namespace {
+
+constexpr int kRadiusThreads = 128; // lanes (queries) per workgroup of a walk: two waves walking neighbouring cells
+
+// The ring walk of one query (header): visit(d2, id) for every point with d2 <= r2, until it returns true ("enough") or the stop
+// rule fires.  Returns the number of points whose distance was computed.
+template <class Visit>
+__device__ __forceinline__ int radius_walk(const float4 *__restrict__ S, const int32_t *__restrict__ cell_start, const SpatialGrid &G,
+                                           float qx, float qy, float qz, float r2, Visit &&visit)
+{
+    const int nx = G.n[0], ny = G.n[1], nz = G.n[2];
+    const float h = G.h;
+    const int cx = cell_axis(qx, G.lo[0], h, nx), cy = cell_axis(qy, G.lo[1], h, ny), cz = cell_axis(qz, G.lo[2], h, nz);
+    const float ax = qx - G.lo[0], ay = qy - G.lo[1], az = qz - G.lo[2];
+    int seen = 0;
+    bool enough = false;
+
+    auto scan = [&](int b, int e) {
+        for (int p = b; p < e && !enough; ++p) {
+            const float4 v = S[p];
+            const float dx = v.x - qx, dy = v.y - qy, dz = v.z - qz;
+            const float d2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+            ++seen;
+            if (d2 <= r2)
+                enough = visit(d2, __float_as_int(v.w));
+        }
+    };
+
+    const int r_max = max(nx, max(ny, nz)); // the ring has left the grid on every side by then
+    for (int r = 0; r <= r_max && !enough; ++r) {
+        const int z0 = max(cz - r, 0), z1 = min(cz + r, nz - 1);
+        const int y0 = max(cy - r, 0), y1 = min(cy + r, ny - 1);
+        const int x0 = max(cx - r, 0), x1 = min(cx + r, nx - 1);
+        for (int z = z0; z <= z1 && !enough; ++z) {
+            // rows y0 .. y1 of this slab over the grid's full width hold everything the ring visits in it (k_spatial_knn's skip)
+            if (cell_start[(z * ny + y0) * nx] == cell_start[(z * ny + y1) * nx + nx])
+                continue;
+            for (int y = y0; y <= y1 && !enough; ++y) {
+                const int base = (z * ny + y) * nx;
+                if (abs(z - cz) == r || abs(y - cy) == r) { // the whole run along x lies in the ring
+                    scan(cell_start[base + x0], cell_start[base + x1 + 1]);
+                } else { // (r > 0) only the two ends do
+                    if (cx - r >= 0)
+                        scan(cell_start[base + cx - r], cell_start[base + cx - r + 1]);
+                    if (cx + r <= nx - 1)
+                        scan(cell_start[base + cx + r], cell_start[base + cx + r + 1]);
+                }
+            }
+        }
+        // what is left lies r + 1 cells or more away along some axis: the smallest bound over the sides that still have cells
+        float lb = __builtin_inff();
+        bool any = false;
+        if (cx + r + 1 <= nx - 1) {
+            lb = fminf(lb, bound_above(ax, cx + r + 1, h));
+            any = true;
+        }
+        if (cx - r - 1 >= 0) {
+            lb = fminf(lb, bound_below(ax, cx - r, h));
+            any = true;
+        }
+        if (cy + r + 1 <= ny - 1) {
+            lb = fminf(lb, bound_above(ay, cy + r + 1, h));
+            any = true;
+        }
+        if (cy - r - 1 >= 0) {
+            lb = fminf(lb, bound_below(ay, cy - r, h));
+            any = true;
+        }
+        if (cz + r + 1 <= nz - 1) {
+            lb = fminf(lb, bound_above(az, cz + r + 1, h));
+            any = true;
+        }
+        if (cz - r - 1 >= 0) {
+            lb = fminf(lb, bound_below(az, cz - r, h));
+            any = true;
+        }
+        if (!any || r2 < lb * lb)
+            break;
+    }
+    return seen;
+}
+
+__global__ __launch_bounds__(kRadiusThreads) void k_radius_count(const float4 *__restrict__ S, const int32_t *__restrict__ cell_start,
+                                                                  SpatialGrid G, const int32_t *__restrict__ group, float r2, int64_t Q,
+                                                                  const float *__restrict__ queries, int64_t ldq,
+                                                                  const int64_t *__restrict__ order,
+                                                                  const int32_t *__restrict__ query_group, int cap,
+                                                                  int32_t *__restrict__ count, int32_t *__restrict__ visited)
+{
+    const int64_t slot = (int64_t)blockIdx.x * kRadiusThreads + threadIdx.x;
+    if (slot >= Q)
+        return;
+    const int64_t g = order[slot];
+    const float qx = queries[g * ldq], qy = queries[g * ldq + 1], qz = queries[g * ldq + 2];
+    const int qg = query_group ? query_group[g] : 0;
+    int c = 0, seen = 0;
+    if (finite3(qx, qy, qz) && qg >= 0)
+        seen = radius_walk(S, cell_start, G, qx, qy, qz, r2, [&](float, int id) {
+            if (!group || group[id] == qg)
+                ++c;
+            return c >= cap;
+        });
+    count[g] = c;
+    if (visited)
+        visited[g] = seen;
+}
+
+// ---- union-find by index (header) ------------------------------------------------------------------------------------------------
+
+__device__ __forceinline__ int uf_load(int32_t *parent, int v)
+{
+    return __hip_atomic_load(parent + v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the root of v as far as this lane can see, with path halving; cap: the trip cap (n + 1)
+__device__ __forceinline__ int uf_find(int32_t *parent, int v, int cap, int32_t *status)
+{
+    for (int t = 0; t < cap; ++t) {
+        const int p = uf_load(parent, v);
+        if (p == v)
+            return v;
+        const int gp = uf_load(parent, p);
+        if (gp < p) // v is no root and never will be again: point it at its grandparent (smaller, same component)
+            __hip_atomic_fetch_min(parent + v, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        v = gp; // <= p < v
+    }
+    *status = 1;
+    return v;
+}
+
+// joins the components of a and b; returns the root both had when it was done
+__device__ __forceinline__ int uf_unite(int32_t *parent, int a, int b, int cap, int32_t *status)
+{
+    int ra = uf_find(parent, a, cap, status), rb = uf_find(parent, b, cap, status);
+    for (int t = 0; t < cap; ++t) {
+        if (ra == rb)
+            return ra;
+        if (ra < rb) {
+            const int x = ra;
+            ra = rb;
+            rb = x;
+        }
+        int seen = ra; // hook the larger root under the smaller one, if it still is a root
+        if (__hip_atomic_compare_exchange_strong(parent + ra, &seen, rb, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+            return rb;
+        ra = uf_find(parent, seen, cap, status); // from what the swap returned: an ancestor of ra below ra
+        rb = uf_find(parent, rb, cap, status);
+    }
+    *status = 1;
+    return rb;
+}
+
+// lane = sorted position; the lanes of core points unite with their core neighbours of smaller index
+__global__ __launch_bounds__(kRadiusThreads) void k_radius_union(int64_t N, const float4 *__restrict__ S,
+                                                                  const int32_t *__restrict__ cell_start, SpatialGrid G,
+                                                                  const int32_t *__restrict__ group, float r2,
+                                                                  const int32_t *__restrict__ count, int min_points, int32_t *parent,
+                                                                  int32_t *status)
+{
+    const int64_t slot = (int64_t)blockIdx.x * kRadiusThreads + threadIdx.x;
+    if (slot >= N)
+        return;
+    const float4 v = S[slot];
+    const int i = __float_as_int(v.w);
+    if (!finite3(v.x, v.y, v.z) || count[i] < min_points) // (count is 0 for a point that is not live)
+        return;
+    const int gi = group ? group[i] : 0;
+    const int cap = (int)min(N + 1, (int64_t)0x7FFFFFFF);
+    int mine = i; // an ancestor of i: where the next find starts
+    radius_walk(S, cell_start, G, v.x, v.y, v.z, r2, [&](float, int j) {
+        if (j < i && count[j] >= min_points && (!group || group[j] == gi))
+            mine = uf_unite(parent, mine, j, cap, status);
+        return false;
+    });
+}
+
+// lane = sorted position; a live non-core point's nearest core neighbour by (d2, index)
+__global__ __launch_bounds__(kRadiusThreads) void k_radius_attach(int64_t N, const float4 *__restrict__ S,
+                                                                   const int32_t *__restrict__ cell_start, SpatialGrid G,
+                                                                   const int32_t *__restrict__ group, float r2,
+                                                                   const int32_t *__restrict__ count, int min_points,
+                                                                   int32_t *__restrict__ attach)
+{
+    const int64_t slot = (int64_t)blockIdx.x * kRadiusThreads + threadIdx.x;
+    if (slot >= N)
+        return;
+    const float4 v = S[slot];
+    const int i = __float_as_int(v.w);
+    int best = -1;
+    if (finite3(v.x, v.y, v.z) && count[i] > 0 && count[i] < min_points) {
+        const int gi = group ? group[i] : 0;
+        float bd = __builtin_inff();
+        radius_walk(S, cell_start, G, v.x, v.y, v.z, r2, [&](float d2, int j) {
+            if (count[j] >= min_points && (!group || group[j] == gi) && (best < 0 || d2 < bd || (d2 == bd && j < best))) {
+                bd = d2;
+                best = j;
+            }
+            return false;
+        });
+    }
+    attach[i] = best;
+}
+
+__global__ __launch_bounds__(256) void k_components_flatten(int64_t N, const int32_t *__restrict__ count, int min_points,
+                                                            const int32_t *__restrict__ attach, int32_t *parent,
+                                                            int32_t *__restrict__ root, int32_t *status)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N)
+        return;
+    const int cap = (int)min(N + 1, (int64_t)0x7FFFFFFF);
+    int from = -1;
+    if (count[i] >= min_points)
+        from = (int)i;
+    else if (attach)
+        from = attach[i];
+    root[i] = from >= 0 ? uf_find(parent, from, cap, status) : -1;
+}
+
+} // namespace
+
+int launch_radius_count(const float *sorted, const int32_t *cell_start, const float *lo, float h, const int32_t *dims,
+                        const int32_t *group, float r2, int64_t Q, const float *queries, int64_t ldq, const int64_t *order,
+                        const int32_t *query_group, int cap, int32_t *count, int32_t *visited, hipStream_t s)
+{
+    if (Q == 0)
+        return GWBP_OK;
+    unsigned grid;
+    if (int rc = grid_of("radius_count", Q, &grid, kRadiusThreads))
+        return rc;
+    hipLaunchKernelGGL(k_radius_count, dim3(grid), dim3(kRadiusThreads), 0, s, reinterpret_cast<const float4 *>(sorted), cell_start,
+                       make_grid(lo, h, dims), group, r2, Q, queries, ldq, order, query_group, cap, count, visited);
+    return check_hip(hipGetLastError(), "radius_count launch");
+}
+
+int launch_radius_union(int64_t N, const float *sorted, const int32_t *cell_start, const float *lo, float h, const int32_t *dims,
+                        const int32_t *group, float r2, const int32_t *count, int min_points, int32_t *parent, int32_t *status,
+                        hipStream_t s)
+{
+    unsigned grid;
+    if (int rc = grid_of("radius_union", N, &grid, kRadiusThreads))
+        return rc;
+    hipLaunchKernelGGL(k_radius_union, dim3(grid), dim3(kRadiusThreads), 0, s, N, reinterpret_cast<const float4 *>(sorted), cell_start,
+                       make_grid(lo, h, dims), group, r2, count, min_points, parent, status);
+    return check_hip(hipGetLastError(), "radius_union launch");
+}
+
+int launch_radius_attach(int64_t N, const float *sorted, const int32_t *cell_start, const float *lo, float h, const int32_t *dims,
+                         const int32_t *group, float r2, const int32_t *count, int min_points, int32_t *attach, hipStream_t s)
+{
+    unsigned grid;
+    if (int rc = grid_of("radius_attach", N, &grid, kRadiusThreads))
+        return rc;
+    hipLaunchKernelGGL(k_radius_attach, dim3(grid), dim3(kRadiusThreads), 0, s, N, reinterpret_cast<const float4 *>(sorted), cell_start,
+                       make_grid(lo, h, dims), group, r2, count, min_points, attach);
+    return check_hip(hipGetLastError(), "radius_attach launch");
+}
+
+int launch_components_flatten(int64_t N, const int32_t *count, int min_points, const int32_t *attach, int32_t *parent, int32_t *root,
+                              int32_t *status, hipStream_t s)
+{
+    unsigned grid;
+    if (int rc = grid_of("components_flatten", N, &grid, 256))
+        return rc;
+    hipLaunchKernelGGL(k_components_flatten, dim3(grid), dim3(256), 0, s, N, count, min_points, attach, parent, root, status);
+    return check_hip(hipGetLastError(), "components_flatten launch");
+}
+
+} // namespace gwbp

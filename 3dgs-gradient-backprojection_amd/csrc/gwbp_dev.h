@@ -290,6 +290,18 @@ int launch_spatial_knn(const float *sorted, const int32_t *cell_start, const flo
                        const float *queries, int64_t ldq, const int64_t *order, int k, int32_t *idx, float *dist, hipStream_t s);
 int launch_neighbor_mean(int64_t N, int64_t M, int D, int k, const int32_t *idx, const float *F, int64_t ldf, float *out,
                          int64_t ldo, hipStream_t s);
+// radius components on the same grid (components.hip): neighbour counts within a radius, the union-find over the core points, the
+// border points' nearest core neighbour, and the roots.  group / query_group / attach / visited may be nullptr
+int launch_radius_count(const float *sorted, const int32_t *cell_start, const float *lo, float h, const int32_t *dims,
+                        const int32_t *group, float r2, int64_t Q, const float *queries, int64_t ldq, const int64_t *order,
+                        const int32_t *query_group, int cap, int32_t *count, int32_t *visited, hipStream_t s);
+int launch_radius_union(int64_t N, const float *sorted, const int32_t *cell_start, const float *lo, float h, const int32_t *dims,
+                        const int32_t *group, float r2, const int32_t *count, int min_points, int32_t *parent, int32_t *status,
+                        hipStream_t s);
+int launch_radius_attach(int64_t N, const float *sorted, const int32_t *cell_start, const float *lo, float h, const int32_t *dims,
+                         const int32_t *group, float r2, const int32_t *count, int min_points, int32_t *attach, hipStream_t s);
+int launch_components_flatten(int64_t N, const int32_t *count, int min_points, const int32_t *attach, int32_t *parent, int32_t *root,
+                              int32_t *status, hipStream_t s);
 // PCA of a finished field (pca.hip): column means, centred Gram, projection onto k <= 16 components, colours.  ws: the caller's
 // pca_workspace_bytes(N, D) bytes (the slices' partial sums), free again when the call's kernels have run.
 size_t pca_workspace_bytes(int64_t N, int D);

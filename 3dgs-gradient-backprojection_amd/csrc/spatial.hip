@@ -39,6 +39,7 @@
 // with a smaller index.  A direction whose next ring has left the grid has no points (its bound is infinite); when all six have,
 // everything has been visited.  An open list has k-th d2 = +inf and never stops early.  The trip count is at most max(nx, ny, nz).
 #include "gwbp_dev.h"
+#include "spatial_grid.h" // SpatialGrid, finite3, cell_axis, bound_above / bound_below, make_grid, grid_of
 
 namespace gwbp {
 
@@ -46,24 +47,6 @@ namespace {
 
 constexpr int kSpatialThreads = 128; // lanes (queries) per workgroup of the search; LDS = k * 128 * 8 B <= 32 KiB
 constexpr int kNoIndex = 0x7FFFFFFF; // an empty slot of the list: orders after every point at equal distance
-
-struct SpatialGrid {
-    float lo[3];
-    float h;
-    int n[3];
-};
-
-__device__ __forceinline__ bool finite3(float x, float y, float z)
-{
-    return fabsf(x) < __builtin_inff() && fabsf(y) < __builtin_inff() && fabsf(z) < __builtin_inff(); // false for NaN
-}
-
-// THE cell assignment (see the header): every kernel and the stop rule's derivation use this one expression.
-__device__ __forceinline__ int cell_axis(float x, float lo, float h, int n)
-{
-    const float t = floorf((x - lo) / h);
-    return (int)fminf(fmaxf(t, 0.0f), (float)(n - 1)); // (finite x: an overflowed difference is +-inf, and clamps to a border cell)
-}
 
 __global__ __launch_bounds__(256) void k_spatial_cell_keys(int64_t N, const float *__restrict__ P, int64_t ldp, SpatialGrid G,
                                                            int32_t *__restrict__ keys)
@@ -100,20 +83,6 @@ __global__ __launch_bounds__(256) void k_spatial_build(int64_t N, const float *_
         }
         cell_start[i] = (int32_t)a;
     }
-}
-
-// lower bounds of the stop rule (header): on the distance along one axis to any point in a cell >= kf / in a cell < kf
-__device__ __forceinline__ float bound_above(float A, int kf, float h)
-{
-    const float KH = (float)kf * h;
-    const float LB = (KH - A) - (fabsf(KH) + fabsf(A)) * 0x1p-21f;
-    return LB > 0.0f ? LB : 0.0f;
-}
-__device__ __forceinline__ float bound_below(float A, int kf, float h)
-{
-    const float KH = (float)kf * h;
-    const float LB = (A - KH) - (fabsf(KH) + fabsf(A)) * 0x1p-21f;
-    return LB > 0.0f ? LB : 0.0f;
 }
 
 __global__ __launch_bounds__(kSpatialThreads) void k_spatial_knn(const float4 *__restrict__ S, const int32_t *__restrict__ cell_start,
@@ -282,26 +251,6 @@ __global__ __launch_bounds__(256) void k_neighbor_mean(int64_t N, int64_t M, int
                 o[c + 3] = acc.w;
         }
     }
-}
-
-SpatialGrid make_grid(const float *lo, float h, const int32_t *dims)
-{
-    SpatialGrid G;
-    for (int a = 0; a < 3; ++a) {
-        G.lo[a] = lo[a];
-        G.n[a] = dims[a];
-    }
-    G.h = h;
-    return G;
-}
-
-int grid_of(const char *what, int64_t n, unsigned *grid, int per_block)
-{
-    const int64_t g = (n + per_block - 1) / per_block;
-    if (g > 0x7FFFFFFF)
-        return set_error(GWBP_EINVAL, "%s: %lld items need more than 2^31 - 1 workgroups", what, (long long)n);
-    *grid = (unsigned)g;
-    return GWBP_OK;
 }
 
 } // namespace

@@ -126,6 +126,10 @@ def _sorted_keys(p: torch.Tensor, grid: Grid):
     return torch.sort(keys, stable=True)
 
 
+# what components.py (the radius components on the same grid) shares with this module
+as_points, check_grid, grid_args, sorted_keys = _points, _check_grid, _grid_args, _sorted_keys
+
+
 def grid_stats(grid: Grid, cell_start: torch.Tensor) -> dict:
     """What a search on this grid costs: cells, occupied cells, the largest and the 99th-percentile occupancy (over the occupied
     cells), and the points that sit in cells at all (the finite ones)."""

@@ -532,6 +532,51 @@ GWBP_API int gwbp_spatial_knn(int64_t n, const float *sorted, const int32_t *cel
 GWBP_API int gwbp_neighbor_mean(int64_t n, int64_t m, int32_t D, int32_t k, const int32_t *idx, const float *features,
                                 int64_t ldf, float *out, int64_t ldo, void *stream);
 
+/* ---- Radius components: which points form one object (DBSCAN with a deterministic border rule; PCL's Euclidean cluster extraction
+ * at min_points = 1) on the grid of the spatial search above ------------------------------------------------------------------------
+ * sorted / cell_start / the grid arguments: what gwbp_spatial_cell_keys + the caller's stable sort + gwbp_spatial_build made of
+ * points[n, 3].  group (optional, may be NULL: every point in group 0): int32 [n] in the points' ORIGINAL order.  The contract:
+ *   d2(p, q) = fmaf(dz, dz, fmaf(dy, dy, dx * dx)), dx = p.x - q.x in fp32 (gwbp_spatial_knn's); r2 = the caller's fp32 product
+ *     radius * radius; a point is LIVE when its coordinates are finite and its group is >= 0;
+ *   i and j are NEIGHBOURS when both are live, group[i] == group[j] and d2 <= r2 (a point is its own neighbour);
+ *   count[i] = the number of neighbours of i; i is CORE when count[i] >= min_points;
+ *   two core points are in one COMPONENT when a chain of core points, each a neighbour of the next, joins them;
+ *   a live non-core point with a core neighbour is a BORDER point of the component of its nearest core neighbour by (d2, index).
+ * The results are pure functions of the points, the groups, r2 and min_points: they do not depend on the grid, on the launch or on
+ * the order in which lanes run, and two runs give the same bits.
+ *   gwbp_radius_count        count[g] (int32 [q]) = min(cap, the number of points with d2 <= r2 to query row queries[g * ldq + 0..2]
+ *                            whose group equals the query's), g < q.  query_group (optional: every query in group 0): int32 [q].  A
+ *                            non-finite query or one with a negative group gets 0.  order[q]: as for gwbp_spatial_knn.  The walk of
+ *                            a query ends once its count has reached cap (cap >= 1; INT32_MAX: the full count).  visited (optional):
+ *                            int32 [q], the number of points whose distance the query's lane computed.
+ *   gwbp_radius_union        for every core point i (count[i] >= min_points) and every core neighbour j < i: unite(i, j) in
+ *                            parent[n] (int32, the identity on entry), a union-find by index: a hook stores a smaller index over a
+ *                            root with an agent-scope compare-and-swap, so parent[v] <= v always, a find walks strictly decreasing
+ *                            indices, and a component's final root is its smallest member.  No lane waits for another.  count: as
+ *                            written by gwbp_radius_count for queries == points, order == perm, query_group == group, cap >=
+ *                            min_points.  The roots are read by gwbp_components_flatten, a launch of its own.
+ *   gwbp_radius_attach       attach[i] (int32 [n]) = for a live non-core point (0 < count[i] < min_points) its nearest core
+ *                            neighbour by (d2, index), -1 if it has none; -1 for every other point.
+ *   gwbp_components_flatten  root[i] (int32 [n]) = the root of i for a core point, of attach[i] for a point with attach[i] >= 0
+ *                            (attach may be NULL: no border points), else -1.
+ * status (int32 [1], zero on entry): set to 1 if a loop of the union-find reached its trip cap of n + 1, which the invariant above
+ * rules out; the caller reads it after gwbp_components_flatten.
+ * 1 <= n < 2^31; r2 >= 0 (+inf allowed: everything is within reach); min_points, cap >= 1; the grid as for gwbp_spatial_knn.
+ * GWBP_EINVAL before any HIP call: a size, r2, cap, min_points, grid dimension, cell size or stride outside these, a null or
+ * misaligned pointer. */
+GWBP_API int gwbp_radius_count(int64_t n, const float *sorted, const int32_t *cell_start, float lo_x, float lo_y, float lo_z,
+                               float cell_size, int32_t nx, int32_t ny, int32_t nz, const int32_t *group, float r2, int64_t q,
+                               const float *queries, int64_t ldq, const int64_t *order, const int32_t *query_group, int32_t cap,
+                               int32_t *count, int32_t *visited, void *stream);
+GWBP_API int gwbp_radius_union(int64_t n, const float *sorted, const int32_t *cell_start, float lo_x, float lo_y, float lo_z,
+                               float cell_size, int32_t nx, int32_t ny, int32_t nz, const int32_t *group, float r2,
+                               const int32_t *count, int32_t min_points, int32_t *parent, int32_t *status, void *stream);
+GWBP_API int gwbp_radius_attach(int64_t n, const float *sorted, const int32_t *cell_start, float lo_x, float lo_y, float lo_z,
+                                float cell_size, int32_t nx, int32_t ny, int32_t nz, const int32_t *group, float r2,
+                                const int32_t *count, int32_t min_points, int32_t *attach, void *stream);
+GWBP_API int gwbp_components_flatten(int64_t n, const int32_t *count, int32_t min_points, const int32_t *attach, int32_t *parent,
+                                     int32_t *root, int32_t *status, void *stream);
+
 /* ---- PCA of a finished field (the reference's visualize_pca.py: sklearn PCA(3) on the host copy of the [N, D] field) -------------
  * The [N, D] passes of the fit and of the transform; the D x D eigen-decomposition between them is the caller's (float64 eigh of
  * gram / (N - 1); sklearn's covariance_eigh solver does the same).  X[g * ldx + 0..D-1], g < N, is read in place, fp32, any row
