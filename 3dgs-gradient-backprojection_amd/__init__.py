@@ -21,6 +21,8 @@ JojiJoseph/3dgs-gradient-backprojection), hand-written HIP kernels behind a C AB
     from gsbp_amd import quantize_field, dequantize_field, codebook_prompt_scores   # the matrix cores; the field as a codebook
     from gsbp_amd import radius_components, radius_count, suggest_radius  # which Gaussians form one object: radius components
     from gsbp_amd import select_components, split_instances  # (DBSCAN on the grid), and masks / label fields split into instances
+    from gsbp_amd import associate_masks, associated_label_fn, match_masks, remap_masks  # per-view instance masks with unrelated ids
+                                                    # associated into consistent 3-D groups: integer overlap and vote kernels
 """
 from . import synthetic  # noqa: F401
 from ._lib import GwbpError, build, lib  # noqa: F401
@@ -40,4 +42,6 @@ from . import cluster  # noqa: F401
 from .cluster import KMeans, class_prototypes, cluster_sums, codebook_prompt_mask, codebook_prompt_scores, dequantize_field, fit_kmeans, kmeans_assign, quantize_field, synthetic_clusters  # noqa: F401
 from . import components  # noqa: F401
 from .components import Components, Instances, radius_components, radius_count, select_components, split_instances, suggest_radius, synthetic_instances  # noqa: F401
+from . import associate  # noqa: F401
+from .associate import Association, associate_masks, associated_label_fn, match_masks, quantize_weights, remap_masks  # noqa: F401
 from .pruning import check_proper_pruning, gradient_mask, prune_by_gradients  # noqa: F401

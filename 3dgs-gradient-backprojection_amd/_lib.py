@@ -182,6 +182,9 @@ ARGTYPES = {
     # the votes: labels, label_type, ls_y, ls_x, ymap, xmap, then (seen | pixel weights), num_classes, C, ldc, n, stream
     "gwbp_vote_labels": _WSV + [_P, _I32, _I64, _I64, _P, _P, _I32, _P, _P, _I64, _P, _P],
     "gwbp_vote_projected": _WSV + [_P, _I32, _I64, _I64, _P, _P, C.POINTER(PixelWeights), _I32, _P, _I64, _P, _P],
+    # the association walks: labels, label_type, ls_y, ls_x, num_labels, ymap, xmap, (group | remap), n_cols, (O | V), ld, stream
+    "gwbp_label_overlap": _WSV + [_P, _I32, _I64, _I64, _I32, _P, _P, _P, _I32, _P, _I64, _P],
+    "gwbp_label_votes": _WSV + [_P, _I32, _I64, _I64, _I32, _P, _P, _P, _I32, _P, _I64, _P],
     # N, M, D, k, Q, ldq, S, lds, idx, score, stream  /  N, M, k, idx, labels, num_classes, label_out, counts, ldc, stream
     "gwbp_knn_search": [_I64, _I32, _I32, _I32, _P, _I64, _P, _I64, _P, _P, _P],
     "gwbp_knn_vote": [_I64, _I32, _I32, _P, _P, _I32, _P, _P, _I64, _P],

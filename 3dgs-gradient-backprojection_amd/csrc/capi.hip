@@ -338,6 +338,30 @@ static int check_label_args(const char *fn, const void *labels, int32_t label_ty
     return check_label_map(labels, ls_y, ls_x);
 }
 
+// The label map, the int32 table (`aux`: group of gwbp_label_overlap, remap of gwbp_label_votes) and the int64 accumulator of the
+// two association walks (`acc` and `ld` are its name and its leading dimension's in the messages).
+static int check_assoc_args(const char *fn, const void *labels, int32_t label_type, int64_t ls_y, int64_t ls_x, const int32_t *ymap,
+                            const int32_t *xmap, int32_t num_labels, const char *aux_name, const int32_t *aux, int32_t n_cols,
+                            const char *acc, const int64_t *A, const char *ld, int64_t lda)
+{
+    int rc = check_label_type(label_type);
+    if (rc)
+        return rc;
+    if (num_labels <= 0)
+        return set_error(GWBP_EINVAL, "num_labels must be positive (got %d)", (int)num_labels);
+    if (n_cols <= 0)
+        return set_error(GWBP_EINVAL, "n_cols must be positive (got %d)", (int)n_cols);
+    if (lda < n_cols)
+        return set_error(GWBP_EINVAL, "%s %lld < n_cols %d", ld, (long long)lda, (int)n_cols);
+    if (!aux)
+        return set_error(GWBP_EINVAL, "null %s", aux_name);
+    if (!A || (reinterpret_cast<uintptr_t>(A) & 7))
+        return set_error(GWBP_EINVAL, "%s must be a non-null, 8-B aligned int64 array", acc);
+    if ((rc = check_index_maps(fn, ymap, xmap)))
+        return rc;
+    return check_label_map(labels, ls_y, ls_x);
+}
+
 extern "C" {
 
 const char *gwbp_version(void)
@@ -795,6 +819,34 @@ int gwbp_vote_projected(const gwbp_caps *caps, void *workspace, size_t workspace
     if ((rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B)))
         return rc;
     return launch_vote_projected(B.L, B.W, B.V, labels, label_type, ls_y, ls_x, ymap, xmap, pw, num_classes, C, ldc, n, B.s);
+}
+
+int gwbp_label_overlap(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                       const void *labels, int32_t label_type, int64_t ls_y, int64_t ls_x, int32_t num_labels, const int32_t *ymap,
+                       const int32_t *xmap, const int32_t *group, int32_t n_cols, int64_t *O, int64_t ldo, void *stream)
+{
+    Bound B;
+    int rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B);
+    if (rc)
+        return rc;
+    if ((rc = check_assoc_args("gwbp_label_overlap", labels, label_type, ls_y, ls_x, ymap, xmap, num_labels, "group", group, n_cols,
+                               "O", O, "ldo", ldo)))
+        return rc;
+    return launch_label_overlap(B.L, B.W, B.V, labels, label_type, ls_y, ls_x, ymap, xmap, num_labels, group, n_cols, O, ldo, B.s);
+}
+
+int gwbp_label_votes(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host, const void *labels,
+                     int32_t label_type, int64_t ls_y, int64_t ls_x, int32_t num_labels, const int32_t *ymap, const int32_t *xmap,
+                     const int32_t *remap, int32_t n_cols, int64_t *V, int64_t ldv, void *stream)
+{
+    Bound B;
+    int rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B);
+    if (rc)
+        return rc;
+    if ((rc = check_assoc_args("gwbp_label_votes", labels, label_type, ls_y, ls_x, ymap, xmap, num_labels, "remap", remap, n_cols,
+                               "V", V, "ldv", ldv)))
+        return rc;
+    return launch_label_votes(B.L, B.W, B.V, labels, label_type, ls_y, ls_x, ymap, xmap, num_labels, remap, n_cols, V, ldv, B.s);
 }
 
 int gwbp_render(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,

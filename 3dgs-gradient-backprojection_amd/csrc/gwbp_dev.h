@@ -250,6 +250,14 @@ int launch_vote_labels(const Layout &L, const Ws &W, const ViewDev &V, const voi
 int launch_vote_projected(const Layout &L, const Ws &W, const ViewDev &V, const void *labels, int label_type, int64_t ls_y,
                           int64_t ls_x, const int32_t *ymap, const int32_t *xmap, const PixW *pw, int K, float *C, int64_t ldc,
                           float *n, hipStream_t s);
+// the integer walks of the weight store behind the mask association (associate.hip), q(w) = rint(clamp(w, 0, 4) * 2^20):
+// O[row(L(p)), group[g] + 1] += q (int64 [K + 1, ldo]) and V[g, remap[L(p)]] += q (int64 [N, ldv])
+int launch_label_overlap(const Layout &L, const Ws &W, const ViewDev &V, const void *labels, int label_type, int64_t ls_y,
+                         int64_t ls_x, const int32_t *ymap, const int32_t *xmap, int K, const int32_t *group, int n_cols, int64_t *O,
+                         int64_t ldo, hipStream_t s);
+int launch_label_votes(const Layout &L, const Ws &W, const ViewDev &V, const void *labels, int label_type, int64_t ls_y,
+                       int64_t ls_x, const int32_t *ymap, const int32_t *xmap, int K, const int32_t *remap, int n_cols, int64_t *Vt,
+                       int64_t ldv, hipStream_t s);
 int launch_render(const Layout &L, const Ws &W, const ViewDev &V, const float *colors, int D, float *out,
                   hipStream_t s);
 int launch_render_px(const Ws &W, const ViewDev &V, const float *colors, int D, float *out, float *alphas,

@@ -682,6 +682,48 @@ class Engine:
                    c_int64(sy), c_int64(sx), ptr(ymap), ptr(xmap), pw, K, ptr(C), c_int64(C.stride(0)),
                    ptr(n), self._stream())
 
+    # ---- the integer walks of the mask association (gwbp_label_overlap, gwbp_label_votes; associate.py) ----------------------
+    def _assoc_args(self, what: str, view, labels, num_labels: int, upsample, aux, aux_name: str, aux_len: int, acc, acc_name: str,
+                    acc_rows: int):
+        """(label map as read, ymap, xmap, K, n_cols) of label_overlap (aux = group [N], acc = O [K + 1, n_cols]) and label_votes
+        (aux = remap [K], acc = V [N, n_cols]): the map through _label_map, the int32 table and the int64 accumulator checked."""
+        if self._tokens is not None:
+            raise GwbpError(f"this view was blended with blend_tokens (no weight store): blend_weights() first for {what}()")
+        K = int(num_labels)
+        if K < 1:
+            raise GwbpError(f"num_labels must be positive, got {K}")
+        labels, ymap, xmap = self._label_map(view, labels, K, upsample)
+        rows, n = int(acc_rows), int(aux_len)
+        if (not torch.is_tensor(acc) or acc.dtype != torch.int64 or not acc.is_cuda or acc.dim() != 2 or acc.shape[0] != rows
+                or acc.shape[1] < 1 or (acc.shape[1] > 1 and acc.stride(1) != 1) or acc.stride(0) < acc.shape[1]):
+            raise GwbpError(f"{acc_name} must be an int64 HIP tensor [{rows}, n_cols] with unit column stride")
+        if (not torch.is_tensor(aux) or aux.dtype != torch.int32 or not aux.is_cuda or not aux.is_contiguous()
+                or tuple(aux.shape) != (n,)):
+            raise GwbpError(f"{aux_name} must be a contiguous int32 HIP tensor [{n}]")
+        return labels, ymap, xmap, K, int(acc.shape[1])
+
+    def label_overlap(self, view, labels, group, O, num_labels: int, upsample: Optional[str] = None):
+        """O[row, group[g] + 1] += q(w) over the view's weight store (gwbp_label_overlap), q the fixed-point weight of
+        associate.quantize_weights: row = labels[p] if it lies in [0, num_labels), else num_labels (the ignored pixels' row);
+        group: int32 [N], -1 (or anything outside [-1, n_cols - 2]) = column 0, "not yet assigned".  O: int64
+        [num_labels + 1, n_cols] with unit column stride, ADDED to.  Integer sums: the same bits on every run.  labels, upsample: as
+        scatter_labels."""
+        labels, ymap, xmap, K, n_cols = self._assoc_args("label_overlap", view, labels, num_labels, upsample, group, "group", self.n,
+                                                         O, "O", int(num_labels) + 1)
+        sy, sx = labels.stride()
+        self._call("gwbp_label_overlap", *self._args(), byref(view), ptr(labels), LABEL_TYPES[labels.dtype], c_int64(sy),
+                   c_int64(sx), K, ptr(ymap), ptr(xmap), ptr(group), n_cols, ptr(O), c_int64(O.stride(0)), self._stream())
+
+    def label_votes(self, view, labels, remap, V, num_labels: int, upsample: Optional[str] = None):
+        """V[g, remap[labels[p]]] += q(w) over the view's weight store (gwbp_label_votes).  remap: int32 [num_labels] with values in
+        [-1, n_cols); a label outside [0, num_labels) or a negative entry adds nothing.  V: int64 [N, n_cols] with unit column
+        stride, ADDED to.  Integer sums, as label_overlap."""
+        labels, ymap, xmap, K, n_cols = self._assoc_args("label_votes", view, labels, num_labels, upsample, remap, "remap", int(num_labels),
+                                                         V, "V", self.n)
+        sy, sx = labels.stride()
+        self._call("gwbp_label_votes", *self._args(), byref(view), ptr(labels), LABEL_TYPES[labels.dtype], c_int64(sy),
+                   c_int64(sx), K, ptr(ymap), ptr(xmap), ptr(remap), n_cols, ptr(V), c_int64(V.stride(0)), self._stream())
+
     @staticmethod
     def mask_fast_path(dim: int) -> bool:
         """Table widths gwbp_scatter_mask_features takes (every other width materialises table[labels], see

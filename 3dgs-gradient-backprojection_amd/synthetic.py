@@ -113,6 +113,12 @@ def make_cameras(cfg: Config, seed: int = CAMERA_SEED, n_views: Optional[int] = 
     az = 2.0 * math.pi * torch.rand(v, generator=g)
     el = torch.deg2rad(10.0 + 30.0 * torch.rand(v, generator=g))
     rad = 3.5 * (1.0 + 0.1 * (2.0 * torch.rand(v, generator=g) - 1.0))
+    return _look_at_origin(az, el, rad)
+
+
+def _look_at_origin(az: torch.Tensor, el: torch.Tensor, rad: torch.Tensor) -> torch.Tensor:
+    """[V,4,4] world->camera matrices of cameras at azimuth / elevation (radians) / distance that look at the origin, z up."""
+    v = az.shape[0]
     c = torch.stack([rad * torch.cos(el) * torch.cos(az), rad * torch.cos(el) * torch.sin(az), rad * torch.sin(el)], 1)
     fwd = -c / c.norm(dim=1, keepdim=True)  # look at the origin
     up = torch.tensor([0.0, 0.0, 1.0]).expand_as(fwd)
@@ -126,6 +132,61 @@ def make_cameras(cfg: Config, seed: int = CAMERA_SEED, n_views: Optional[int] = 
     vm[:, :3, 3] = t
     vm[:, 3, 3] = 1.0
     return vm.contiguous()
+
+
+def make_orbit(cfg: Config, n_views: int, elevation_deg: float = 25.0, radius: float = 3.5) -> torch.Tensor:
+    """[n_views,4,4] world->camera matrices of an orbit: evenly spaced azimuths at one elevation and distance, looking at the
+    origin like make_cameras' (consecutive views overlap, which a sequential association of per-view masks relies on)."""
+    az = 2.0 * math.pi * torch.arange(n_views, dtype=torch.float32) / float(n_views)
+    el = torch.deg2rad(torch.full((n_views,), float(elevation_deg)))
+    return _look_at_origin(az, el, torch.full((n_views,), float(radius)))
+
+
+INSTANCE_SEED = 60_000
+
+
+def make_instances(means: torch.Tensor, n_instances: int = 4, seed: int = INSTANCE_SEED) -> torch.Tensor:
+    """int32 [N] true instance of every Gaussian: the 3-D Voronoi cells of n_instances seeded sites in the means' bounding box."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    m = means.detach().cpu().float()
+    lo, hi = m.min(dim=0).values, m.max(dim=0).values
+    sites = lo + (hi - lo) * torch.rand(n_instances, 3, generator=g)
+    return torch.cdist(m, sites).argmin(dim=1).to(torch.int32)
+
+
+def make_instance_views(cfg: Config, viewmats: torch.Tensor, n_instances: int = 4, seed: int = INSTANCE_SEED, n_ids: Optional[int] = None,
+                        device=None, argmax_fn=None):
+    """(instance int32 [N], maps, perms): per-view instance maps as an "everything" segmenter gives them, ids unrelated between
+    views.  instance = make_instances(means of make_scene(cfg)); view v's map is the argmax instance per pixel, -1 where the
+    pixel's alpha lies below 0.5, with the ids renamed by perms[v], a seeded permutation (seed + 1 + v) of [0, n_ids) (n_ids
+    defaults to n_instances): map = perms[v][instance id].  Rendered on `device` by the package's label render; with
+    argmax_fn(v, instance) -> (argmax integer [H, W], alphas [H, W]) by the caller instead (the CPU oracle's render in the tests).
+    maps: int32 [H, W] tensors on `device` (on the host with argmax_fn and no device)."""
+    means, quats, scales, opac = activate(make_scene(cfg))
+    instance = make_instances(means, n_instances, seed)
+    n_ids = n_instances if n_ids is None else int(n_ids)
+    if n_ids < n_instances:
+        raise ValueError("n_ids must be at least n_instances")
+    K = intrinsics(cfg)
+    if argmax_fn is None:
+        from ._views import front
+        gauss = [t.to(device) for t in (means, quats, scales, opac)]
+        inst_dev, K = instance.to(device), K.to(device)
+    maps, perms = [], []
+    for v in range(viewmats.shape[0]):
+        if argmax_fn is None:
+            eng, view, _ = front("make_instance_views", *gauss, viewmats[v].to(device), K, cfg.width, cfg.height, {})
+            _, alphas, seg, _ = eng.render_labels(view, inst_dev, n_instances, want_maps=False, want_alphas=True, want_argmax=True)
+        else:
+            seg, alphas = (torch.as_tensor(t) for t in argmax_fn(v, instance))
+            if device is not None:
+                seg, alphas = seg.to(device), alphas.to(device)
+        perm = torch.randperm(n_ids, generator=torch.Generator(device="cpu").manual_seed(seed + 1 + v)).to(torch.int32)
+        seg = seg.to(torch.int64)
+        ok = (seg >= 0) & (alphas >= 0.5)
+        maps.append(torch.where(ok, perm.to(seg.device)[torch.where(ok, seg, 0)], -1).to(torch.int32))
+        perms.append(perm)
+    return instance, maps, perms
 
 
 def make_feature_map(cfg: Config, view: int, device="cpu", dim: Optional[int] = None) -> torch.Tensor:

@@ -403,6 +403,36 @@ GWBP_API int gwbp_vote_projected(const gwbp_caps *caps, void *workspace, size_t 
                                  const int32_t *xmap, const gwbp_pixel_weights *pixel_weights, int32_t num_classes, float *C,
                                  int64_t ldc, float *n, void *stream);
 
+/* ---- ASSOCIATION of per-view instance masks (which 3-D group does a mask of a new view continue?) ------------------------
+ * Two INTEGER walks of the view's weight store.  Every entry (g, p, w) contributes the fixed-point weight
+ *     q = (uint32) rintf(fminf(fmaxf(w, 0), 4) * 1048576)
+ * (2^-20 steps, round to nearest and half to even; a NaN or negative stored weight gives 0, a weight above 4 -- possible only
+ * with a pixel weight map -- saturates), and every sum of q is an integer sum into int64: the results have the same bits on
+ * every run, whatever the order of the atomics.  A record's per-label sum fits uint32 (256 entries of at most 2^22).
+ *
+ * gwbp_label_overlap:  O[row * ldo + col] += q,  row = L(p) if 0 <= L(p) < num_labels, else num_labels (the ignored pixels
+ * have a row of their own, so that a column's sum over all rows is the group's whole weight in this view);  col = group[g] + 1
+ * with group int32 [N] (device) in [-1, n_cols - 2], any other value counting as -1: column 0 is "not yet assigned".
+ * O is int64 [num_labels + 1, ldo] row-major (device), ldo >= n_cols; the call ADDS (the caller zeroes O).
+ *
+ * gwbp_label_votes:  V[g * ldv + remap[L(p)]] += q  with remap int32 [num_labels] (device) in [-1, n_cols): a label outside
+ * [0, num_labels), a negative remap entry or one >= n_cols adds nothing.  V is int64 [N, ldv] row-major (device), ldv >= n_cols.
+ *
+ * labels, label_type, ls_y, ls_x, ymap, xmap: as gwbp_scatter_labels.  The caps, the workspace and the view are checked first, as
+ * for every call on a view; then, still before any device call, GWBP_EINVAL for an unknown label_type, num_labels <= 0,
+ * n_cols <= 0, a leading dimension below n_cols, a NULL labels, group / remap or output, an output that is not 8-B aligned,
+ * negative strides, or exactly one of ymap / xmap NULL.  Both need the weight store of the view (gwbp_blend_weights or its _d /
+ * _ex / _rgb forms, with or without GWBP_FLAG_NARROW_SCATTER); after gwbp_blend_scatter / gwbp_blend_scatter_encoded /
+ * gwbp_blend_tokens the workspace holds none: the call then sets gwbp_stats.overflow bit 2 and leaves its output untouched. */
+GWBP_API int gwbp_label_overlap(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                                const void *labels, int32_t label_type, int64_t ls_y, int64_t ls_x, int32_t num_labels,
+                                const int32_t *ymap, const int32_t *xmap, const int32_t *group, int32_t n_cols, int64_t *O,
+                                int64_t ldo, void *stream);
+GWBP_API int gwbp_label_votes(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                              const void *labels, int32_t label_type, int64_t ls_y, int64_t ls_x, int32_t num_labels,
+                              const int32_t *ymap, const int32_t *xmap, const int32_t *remap, int32_t n_cols, int64_t *V,
+                              int64_t ldv, void *stream);
+
 /* Bytes of gwbp_scatter_mask_features' slot store per (Gaussian, tile) intersection: four (int32 label, fp32 sum) slots. */
 #define GWBP_MASK_SLOT_BYTES 32
 
