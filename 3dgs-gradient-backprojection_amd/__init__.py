@@ -23,6 +23,8 @@ JojiJoseph/3dgs-gradient-backprojection), hand-written HIP kernels behind a C AB
     from gsbp_amd import select_components, split_instances  # (DBSCAN on the grid), and masks / label fields split into instances
     from gsbp_amd import associate_masks, associated_label_fn, match_masks, remap_masks  # per-view instance masks with unrelated ids
                                                     # associated into consistent 3-D groups: integer overlap and vote kernels
+    from gsbp_amd import similarity_components, similarity_levels, neighbor_similarity  # regions by geometry AND features: the
+    from gsbp_amd import edge_strength, region_prompt_mask  # spatial k-NN graph cut where the features' cosine falls below a threshold
 """
 from . import synthetic  # noqa: F401
 from ._lib import GwbpError, build, lib  # noqa: F401
@@ -44,4 +46,6 @@ from . import components  # noqa: F401
 from .components import Components, Instances, radius_components, radius_count, select_components, split_instances, suggest_radius, synthetic_instances  # noqa: F401
 from . import associate  # noqa: F401
 from .associate import Association, associate_masks, associated_label_fn, match_masks, quantize_weights, remap_masks  # noqa: F401
+from . import regions  # noqa: F401
+from .regions import edge_strength, neighbor_similarity, region_prompt_mask, similarity_components, similarity_levels, synthetic_regions  # noqa: F401
 from .pruning import check_proper_pruning, gradient_mask, prune_by_gradients  # noqa: F401

@@ -202,6 +202,10 @@ ARGTYPES = {
     "gwbp_radius_union": [_I64, _P, _P, _F, _F, _F, _F, _I32, _I32, _I32, _P, _F, _P, _I32, _P, _P, _P],
     "gwbp_radius_attach": [_I64, _P, _P, _F, _F, _F, _F, _I32, _I32, _I32, _P, _F, _P, _I32, _P, _P],
     "gwbp_components_flatten": [_I64, _P, _I32, _P, _P, _P, _P, _P],
+    # regions: n, D, k, idx, features, ldf, sim, live, stream  /  n, k, idx, sim, live, dist, group, sim_min, max_dist, count,
+    # parent, status, stream
+    "gwbp_neighbor_similarity": [_I64, _I32, _I32, _P, _P, _I64, _P, _P, _P],
+    "gwbp_edge_union": [_I64, _I32, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P],
     # PCA: N, D, bytes*  /  N, D, X, ldx, mean, workspace, bytes, stream  /  N, D, X, ldx, mean, gram, workspace, bytes, stream  /
     # N, D, k, X, ldx, mean, components, Y, minmax, stream  /  n, Y, lo_hi, colors, stream
     "gwbp_pca_workspace_size": [_I64, _I32, C.POINTER(C.c_size_t)],

@@ -80,6 +80,9 @@ def _group(group, mask, n: int, dev, what: str = "group") -> Optional[torch.Tens
     return group.to(dev).clamp(min=-1, max=INT32_MAX).to(torch.int32).contiguous()
 
 
+as_group = _group  # what regions.py (components over a neighbour list) shares with this module
+
+
 def _plan(p: torch.Tensor, radius: float, cell_size: Optional[float], grid: Optional[Grid]) -> Grid:
     """The grid of a walk: the caller's, or cells of max(radius, the automatic edge), so that a radius reaches one ring."""
     if grid is not None:

@@ -1153,6 +1153,74 @@ int gwbp_components_flatten(int64_t n, const int32_t *count, int32_t min_points,
     return launch_components_flatten(n, count, min_points, attach, parent, root, status, as_stream(stream));
 }
 
+// an array a region entry point writes must be none of the arrays it reads, and no two written arrays the same
+static int check_regions_distinct(const char *what, const void *const *written, int n_written, const void *const *read, int n_read)
+{
+    for (int a = 0; a < n_written; ++a) {
+        for (int b = a + 1; b < n_written; ++b)
+            if (written[a] == written[b])
+                return set_error(GWBP_EINVAL, "%s: two output arrays are the same array", what);
+        for (int b = 0; b < n_read; ++b)
+            if (read[b] && written[a] == read[b])
+                return set_error(GWBP_EINVAL, "%s: an output array must not be one of the input arrays", what);
+    }
+    return GWBP_OK;
+}
+
+// what the two region entry points share: the neighbour list idx[n, k] and the similarities of its entries
+static int check_neighbor_list(const char *what, int64_t n, int32_t k, const int32_t *idx, const float *sim)
+{
+    if (n < 1 || n > 0x7FFFFFFF)
+        return set_error(GWBP_EINVAL, "%s: bad number of rows (%lld): 1 .. 2^31 - 1", what, (long long)n);
+    if (k < 1 || k > GWBP_REGIONS_MAX_K)
+        return set_error(GWBP_EINVAL, "%s: k must be in [1, %d] (got %d)", what, GWBP_REGIONS_MAX_K, (int)k);
+    if (!idx || !sim)
+        return set_error(GWBP_EINVAL, "%s: null idx or sim", what);
+    if ((reinterpret_cast<uintptr_t>(idx) & 3) || (reinterpret_cast<uintptr_t>(sim) & 3))
+        return set_error(GWBP_EINVAL, "%s: idx and sim must be 4-B aligned", what);
+    return GWBP_OK;
+}
+
+int gwbp_neighbor_similarity(int64_t n, int32_t D, int32_t k, const int32_t *idx, const float *features, int64_t ldf, float *sim,
+                             int32_t *live, void *stream)
+{
+    if (int rc = check_neighbor_list("neighbor_similarity", n, k, idx, sim))
+        return rc;
+    if (D < 1 || D > GWBP_REGIONS_MAX_D)
+        return set_error(GWBP_EINVAL, "neighbor_similarity: D must be in [1, %d] (got %d)", GWBP_REGIONS_MAX_D, (int)D);
+    if (ldf < D)
+        return set_error(GWBP_EINVAL, "neighbor_similarity: row stride %lld below D = %d", (long long)ldf, (int)D);
+    if (!features || !live)
+        return set_error(GWBP_EINVAL, "neighbor_similarity: null features or live");
+    if ((reinterpret_cast<uintptr_t>(features) & 3) || (reinterpret_cast<uintptr_t>(live) & 3))
+        return set_error(GWBP_EINVAL, "neighbor_similarity: features and live must be 4-B aligned");
+    const void *const written[] = {sim, live}, *const read[] = {idx, features};
+    if (int rc = check_regions_distinct("neighbor_similarity", written, 2, read, 2))
+        return rc;
+    return launch_neighbor_similarity(n, D, k, idx, features, ldf, sim, live, as_stream(stream));
+}
+
+int gwbp_edge_union(int64_t n, int32_t k, const int32_t *idx, const float *sim, const int32_t *live, const float *dist,
+                    const int32_t *group, float sim_min, float max_dist, int32_t *count, int32_t *parent, int32_t *status,
+                    void *stream)
+{
+    if (int rc = check_neighbor_list("edge_union", n, k, idx, sim))
+        return rc;
+    if (sim_min != sim_min)
+        return set_error(GWBP_EINVAL, "edge_union: sim_min must not be NaN");
+    if (!(max_dist >= 0.0f))
+        return set_error(GWBP_EINVAL, "edge_union: max_dist must be >= 0 or +inf (got %g)", (double)max_dist);
+    if (!live || !count || !parent || !status)
+        return set_error(GWBP_EINVAL, "edge_union: null live, count, parent or status");
+    if ((reinterpret_cast<uintptr_t>(live) & 3) || (reinterpret_cast<uintptr_t>(dist) & 3) || (reinterpret_cast<uintptr_t>(group) & 3) ||
+        (reinterpret_cast<uintptr_t>(count) & 3) || (reinterpret_cast<uintptr_t>(parent) & 3) || (reinterpret_cast<uintptr_t>(status) & 3))
+        return set_error(GWBP_EINVAL, "edge_union: live, dist, group, count, parent and status must be 4-B aligned");
+    const void *const written[] = {count, parent, status}, *const read[] = {idx, sim, live, dist, group};
+    if (int rc = check_regions_distinct("edge_union", written, 3, read, 5))
+        return rc;
+    return launch_edge_union(n, k, idx, sim, live, dist, group, sim_min, max_dist, count, parent, status, as_stream(stream));
+}
+
 // the checks the two passes of the fit share
 static int check_pca_rows(const char *what, int64_t N, int32_t D, const float *X, int64_t ldx, const void *workspace,
                           size_t workspace_bytes)

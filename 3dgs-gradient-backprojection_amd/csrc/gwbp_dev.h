@@ -310,6 +310,13 @@ int launch_radius_attach(int64_t N, const float *sorted, const int32_t *cell_sta
                          const int32_t *group, float r2, const int32_t *count, int min_points, int32_t *attach, hipStream_t s);
 int launch_components_flatten(int64_t N, const int32_t *count, int min_points, const int32_t *attach, int32_t *parent, int32_t *root,
                               int32_t *status, hipStream_t s);
+// regions over a neighbour list by feature similarity (regions.hip): the cosine of every listed pair and each row's liveness, then
+// the union-find of union_find.h over the edges that pass; launch_components_flatten reads the roots.  dist / group may be nullptr
+int launch_neighbor_similarity(int64_t N, int D, int k, const int32_t *idx, const float *F, int64_t ldf, float *sim, int32_t *live,
+                               hipStream_t s);
+int launch_edge_union(int64_t N, int k, const int32_t *idx, const float *sim, const int32_t *live, const float *dist,
+                      const int32_t *group, float sim_min, float max_dist, int32_t *count, int32_t *parent, int32_t *status,
+                      hipStream_t s);
 // PCA of a finished field (pca.hip): column means, centred Gram, projection onto k <= 16 components, colours.  ws: the caller's
 // pca_workspace_bytes(N, D) bytes (the slices' partial sums), free again when the call's kernels have run.
 size_t pca_workspace_bytes(int64_t N, int D);

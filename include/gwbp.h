@@ -607,6 +607,47 @@ GWBP_API int gwbp_radius_attach(int64_t n, const float *sorted, const int32_t *c
 GWBP_API int gwbp_components_flatten(int64_t n, const int32_t *count, int32_t min_points, const int32_t *attach, int32_t *parent,
                                      int32_t *root, int32_t *status, void *stream);
 
+/* ---- Regions: the connected components of a neighbour list whose edges pass a cosine threshold (region growing on the feature
+ * field over the spatial k-NN graph) --------------------------------------------------------------------------------------------------
+ * features[n, D]: fp32, row i at features + i * ldf, ldf >= D.  idx[n, k]: int32, dense; an entry < 0 or >= n is NO NEIGHBOUR; an
+ * entry == i is allowed and ignored by the union.  dist[n, k] (optional, may be NULL): fp32, gwbp_spatial_knn's distances for the
+ * same list.  group[n] (optional, may be NULL: every point in group 0): int32.  The contract:
+ *   dot(i, j) = sum_c F[i, c] * F[j, c] and sq(i) = dot(i, i) are each ONE fixed arrangement of fp32 operations that depends on D
+ *     alone: lane l of 64 owns the channels 256 s + 4 l + e (s = 0, 1, ...; e = 0 .. 3; those < D) and runs acc = fmaf(a, b, acc)
+ *     from acc = +0 in the order (s, e); the 64 partial sums are then combined by the butterfly p_l = p_l + p_(l xor o) for o = 1,
+ *     2, 4, 8, 16, 32.  (A channel >= D may be skipped or enter as a product of zeros: the bits are the same, since an accumulator
+ *     that starts at +0 never becomes -0.)  The arrangement is symmetric -- dot(i, j) has the bits of dot(j, i), and sq(j) has the
+ *     same bits whichever row's wave computes it -- and independent of n, k, the row's position, ldf, the alignment and the launch;
+ *   norm(i) = sqrtf(sq(i)), correctly rounded; row i is FEATURE-LIVE when sq(i) is finite and norm(i) >= 1e-12f (F.normalize's
+ *     epsilon; a zero row and a row with a NaN or an infinity are dead);
+ *   sim[i, c] = dot(i, j) / (norm(i) * norm(j)), j = idx[i, c]: one fp32 multiply and one correctly rounded divide; NaN when j is
+ *     no neighbour or either row is not feature-live.  (sim of two bit-identical rows is whatever this gives, not always 1.)
+ *   live(i) = row i is feature-live and group[i] >= 0;
+ *   i -- j is an EDGE when j = idx[i, c] for some c (or i = idx[j, c]), i != j, both are live, group[i] == group[j], sim[i, c] >=
+ *     sim_min (NaN fails), and, when a cut is given (dist not NULL and max_dist < +inf), dist[i, c] <= max_dist;
+ *   the COMPONENTS are those of the live points under the edges (a live point without an edge is a component of one); a
+ *     component's root is its smallest member; everything else gets root -1.
+ * The results are pure functions of (features, idx, dist, group, sim_min, max_dist), whatever the order in which lanes run; two
+ * runs give the same bits.
+ *   gwbp_neighbor_similarity  sim[n, k] (fp32, dense) and live[n] (int32 0 / 1: FEATURE-live only).  One wave per row; rows whose
+ *                             addresses and stride are 16-B aligned are read with 16-B loads, others element by element, with the
+ *                             same chains and bits.  No atomics.
+ *   gwbp_edge_union           for every edge found in row i's list: unite(i, j) in parent[n] (int32, the identity on entry), the
+ *                             union-find by index of gwbp_radius_union; count[i] (int32 [n]) = live[i] && group[i] >= 0.  sim and
+ *                             live: as written by gwbp_neighbor_similarity for the same idx.  gwbp_components_flatten(n, count, 1,
+ *                             NULL, parent, root, status) then reads the roots, in a launch of its own.  status: as above.
+ * 1 <= n < 2^31, 1 <= D <= GWBP_REGIONS_MAX_D, 1 <= k <= GWBP_REGIONS_MAX_K, ldf >= D; sim_min is not NaN; max_dist >= 0 or +inf.
+ * Every array is a buffer of its own: an output (sim, live; count, parent, status) is none of the call's inputs and no other output.
+ * GWBP_EINVAL before any HIP call: a size, stride, sim_min or max_dist outside these, a null required pointer, a misaligned
+ * pointer (4-B), an output array that is an input array or another output. */
+#define GWBP_REGIONS_MAX_D 2048
+#define GWBP_REGIONS_MAX_K 64
+GWBP_API int gwbp_neighbor_similarity(int64_t n, int32_t D, int32_t k, const int32_t *idx, const float *features, int64_t ldf,
+                                      float *sim, int32_t *live, void *stream);
+GWBP_API int gwbp_edge_union(int64_t n, int32_t k, const int32_t *idx, const float *sim, const int32_t *live, const float *dist,
+                             const int32_t *group, float sim_min, float max_dist, int32_t *count, int32_t *parent, int32_t *status,
+                             void *stream);
+
 /* ---- PCA of a finished field (the reference's visualize_pca.py: sklearn PCA(3) on the host copy of the [N, D] field) -------------
  * The [N, D] passes of the fit and of the transform; the D x D eigen-decomposition between them is the caller's (float64 eigh of
  * gram / (N - 1); sklearn's covariance_eigh solver does the same).  X[g * ldx + 0..D-1], g < N, is read in place, fp32, any row
