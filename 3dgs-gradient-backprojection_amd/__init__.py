@@ -25,6 +25,8 @@ JojiJoseph/3dgs-gradient-backprojection), hand-written HIP kernels behind a C AB
                                                     # associated into consistent 3-D groups: integer overlap and vote kernels
     from gsbp_amd import similarity_components, similarity_levels, neighbor_similarity  # regions by geometry AND features: the
     from gsbp_amd import edge_strength, region_prompt_mask  # spatial k-NN graph cut where the features' cosine falls below a threshold
+    from gsbp_amd import point_gaussians, sample_field, sample_labels, transfer_field, score_point_labels  # the field and its labels
+                                                    # at arbitrary 3-D points, by each Gaussian's own scale, rotation and opacity
 """
 from . import synthetic  # noqa: F401
 from ._lib import GwbpError, build, lib  # noqa: F401
@@ -48,4 +50,6 @@ from . import associate  # noqa: F401
 from .associate import Association, associate_masks, associated_label_fn, match_masks, quantize_weights, remap_masks  # noqa: F401
 from . import regions  # noqa: F401
 from .regions import edge_strength, neighbor_similarity, region_prompt_mask, similarity_components, similarity_levels, synthetic_regions  # noqa: F401
+from . import sample  # noqa: F401
+from .sample import PointGaussians, neighbor_blend, point_gaussians, sample_field, sample_labels, score_point_labels, suggest_sample_radius, synthetic_points, transfer_field, weighted_vote  # noqa: F401
 from .pruning import check_proper_pruning, gradient_mask, prune_by_gradients  # noqa: F401

@@ -206,6 +206,13 @@ ARGTYPES = {
     # parent, status, stream
     "gwbp_neighbor_similarity": [_I64, _I32, _I32, _P, _P, _I64, _P, _P, _P],
     "gwbp_edge_union": [_I64, _I32, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P],
+    # point samples: n, means, ldm, quats, ldq, scales, lds, opacities, live, perm, pack, stream  /  n, sorted, cell_start, lo_x, lo_y,
+    # lo_z, cell_size, nx, ny, nz, pack, r2, alpha_min, q, queries, ldq, order, k, idx, w, n_contrib, visited, stream  /  q, m, D, k, idx,
+    # w, features, ldf, out, ldo, wsum, stream  /  q, m, k, idx, w, labels, num_classes, out_label, out_share, stream
+    "gwbp_gaussian_pack": [_I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _P],
+    "gwbp_point_gaussians": [_I64, _P, _P, _F, _F, _F, _F, _I32, _I32, _I32, _P, _F, _F, _I64, _P, _I64, _P, _I32, _P, _P, _P, _P, _P],
+    "gwbp_neighbor_blend": [_I64, _I64, _I32, _I32, _P, _P, _P, _I64, _P, _I64, _P, _P],
+    "gwbp_weighted_vote": [_I64, _I64, _I32, _P, _P, _P, _I32, _P, _P, _P],
     # PCA: N, D, bytes*  /  N, D, X, ldx, mean, workspace, bytes, stream  /  N, D, X, ldx, mean, gram, workspace, bytes, stream  /
     # N, D, k, X, ldx, mean, components, Y, minmax, stream  /  n, Y, lo_hi, colors, stream
     "gwbp_pca_workspace_size": [_I64, _I32, C.POINTER(C.c_size_t)],

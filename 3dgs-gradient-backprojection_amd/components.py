@@ -104,6 +104,9 @@ def _build(p: torch.Tensor, grid: Grid):
     return pts, cell_start, perm
 
 
+r2_of, plan_walk, build_grid = _r2, _plan, _build  # what sample.py (the Gaussians that weigh on a point, on the same grid) shares
+
+
 def _walk_args(n: int, pts, cell_start, grid: Grid, group, r2: float):
     return (C.c_int64(n), ptr(pts), ptr(cell_start), *grid_args(grid), ptr(group), C.c_float(r2))
 

@@ -1221,6 +1221,109 @@ int gwbp_edge_union(int64_t n, int32_t k, const int32_t *idx, const float *sim, 
     return launch_edge_union(n, k, idx, sim, live, dist, group, sim_min, max_dist, count, parent, status, as_stream(stream));
 }
 
+// ---- point samples (sample.hip) ----------------------------------------------------------------------------------------------------
+static bool misaligned(const void *p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+
+// a neighbour list with weights: idx[q, k] and w[q, k], dense
+static int check_weighted_list(const char *what, int64_t q, int64_t m, int32_t k, const int32_t *idx, const float *w)
+{
+    if (q < 0 || q > 0x7FFFFFFF || m < 1 || m > 0x7FFFFFFF)
+        return set_error(GWBP_EINVAL, "%s: bad sizes (q=%lld m=%lld): 0 <= q < 2^31, 1 <= m < 2^31", what, (long long)q, (long long)m);
+    if (k < 1 || k > GWBP_SAMPLE_MAX_K)
+        return set_error(GWBP_EINVAL, "%s: k must be in [1, %d] (got %d)", what, GWBP_SAMPLE_MAX_K, (int)k);
+    if (q > 0 && (!idx || !w))
+        return set_error(GWBP_EINVAL, "%s: null idx or w", what);
+    if (misaligned(idx, 3) || misaligned(w, 3))
+        return set_error(GWBP_EINVAL, "%s: idx and w must be 4-B aligned", what);
+    return GWBP_OK;
+}
+
+int gwbp_gaussian_pack(int64_t n, const float *means, int64_t ldm, const float *quats, int64_t ldq, const float *scales, int64_t lds_,
+                       const float *opacities, const uint8_t *live, const int64_t *perm, float *pack, void *stream)
+{
+    if (n < 1 || n > 0x7FFFFFFF)
+        return set_error(GWBP_EINVAL, "gaussian_pack: bad number of Gaussians (%lld): 1 .. 2^31 - 1", (long long)n);
+    if (ldm < 3 || ldq < 4 || lds_ < 3)
+        return set_error(GWBP_EINVAL, "gaussian_pack: row strides (%lld, %lld, %lld) of means, quats, scales below (3, 4, 3)",
+                         (long long)ldm, (long long)ldq, (long long)lds_);
+    if (!means || !quats || !scales || !opacities || !perm || !pack)
+        return set_error(GWBP_EINVAL, "gaussian_pack: null means, quats, scales, opacities, perm or pack");
+    if (misaligned(means, 3) || misaligned(quats, 3) || misaligned(scales, 3) || misaligned(opacities, 3) || misaligned(perm, 7) ||
+        misaligned(pack, 15))
+        return set_error(GWBP_EINVAL, "gaussian_pack: means, quats, scales and opacities must be 4-B aligned, perm 8-B, pack 16-B");
+    const void *const written[] = {pack}, *const read[] = {means, quats, scales, opacities, live, perm};
+    if (int rc = check_regions_distinct("gaussian_pack", written, 1, read, 6))
+        return rc;
+    return launch_gaussian_pack(n, means, ldm, quats, ldq, scales, lds_, opacities, live, perm, pack, as_stream(stream));
+}
+
+int gwbp_point_gaussians(int64_t n, const float *sorted, const int32_t *cell_start, float lo_x, float lo_y, float lo_z, float cell_size,
+                         int32_t nx, int32_t ny, int32_t nz, const float *pack, float r2, float alpha_min, int64_t q,
+                         const float *queries, int64_t ldq, const int64_t *order, int32_t k, int32_t *idx, float *w, int32_t *n_contrib,
+                         int32_t *visited, void *stream)
+{
+    if (int rc = check_radius_walk("point_gaussians", n, sorted, cell_start, lo_x, lo_y, lo_z, cell_size, nx, ny, nz, nullptr, r2))
+        return rc;
+    if (k < 1 || k > GWBP_SAMPLE_MAX_K)
+        return set_error(GWBP_EINVAL, "point_gaussians: k must be in [1, %d] (got %d)", GWBP_SAMPLE_MAX_K, (int)k);
+    if (!(alpha_min >= GWBP_SAMPLE_MIN_ALPHA && alpha_min <= 1.0f))
+        return set_error(GWBP_EINVAL, "point_gaussians: alpha_min must be in [%g, 1] (got %g)", (double)GWBP_SAMPLE_MIN_ALPHA,
+                         (double)alpha_min);
+    if (int rc = check_spatial_points("point_gaussians", "queries", q, queries, ldq))
+        return rc;
+    if (!pack || (q > 0 && (!order || !idx || !w || !n_contrib)))
+        return set_error(GWBP_EINVAL, "point_gaussians: null pack, order, idx, w or n_contrib");
+    if (misaligned(pack, 15) || misaligned(order, 7) || misaligned(idx, 3) || misaligned(w, 3) || misaligned(n_contrib, 3) ||
+        misaligned(visited, 3))
+        return set_error(GWBP_EINVAL, "point_gaussians: pack must be 16-B aligned, order 8-B, idx, w, n_contrib and visited 4-B");
+    const void *const written[] = {idx, w, n_contrib, visited}, *const read[] = {sorted, cell_start, pack, queries, order};
+    if (q > 0)
+        if (int rc = check_regions_distinct("point_gaussians", written, visited ? 4 : 3, read, 5))
+            return rc;
+    const float lo[3] = {lo_x, lo_y, lo_z};
+    const int32_t dims[3] = {nx, ny, nz};
+    return launch_point_gaussians(sorted, cell_start, lo, cell_size, dims, pack, r2, alpha_min, q, queries, ldq, order, k, idx, w,
+                                  n_contrib, visited, as_stream(stream));
+}
+
+int gwbp_neighbor_blend(int64_t q, int64_t m, int32_t D, int32_t k, const int32_t *idx, const float *w, const float *features,
+                        int64_t ldf, float *out, int64_t ldo, float *wsum, void *stream)
+{
+    if (int rc = check_weighted_list("neighbor_blend", q, m, k, idx, w))
+        return rc;
+    if (D < 1)
+        return set_error(GWBP_EINVAL, "neighbor_blend: D must be at least 1 (got %d)", (int)D);
+    if (ldf < D || ldo < D)
+        return set_error(GWBP_EINVAL, "neighbor_blend: row strides (%lld, %lld) below D = %d", (long long)ldf, (long long)ldo, (int)D);
+    if (!features || (q > 0 && (!out || !wsum)))
+        return set_error(GWBP_EINVAL, "neighbor_blend: null features, out or wsum");
+    if (misaligned(features, 3) || misaligned(out, 3) || misaligned(wsum, 3))
+        return set_error(GWBP_EINVAL, "neighbor_blend: features, out and wsum must be 4-B aligned");
+    const void *const written[] = {out, wsum}, *const read[] = {idx, w, features};
+    if (q > 0)
+        if (int rc = check_regions_distinct("neighbor_blend", written, 2, read, 3))
+            return rc;
+    return launch_neighbor_blend(q, m, D, k, idx, w, features, ldf, out, ldo, wsum, as_stream(stream));
+}
+
+int gwbp_weighted_vote(int64_t q, int64_t m, int32_t k, const int32_t *idx, const float *w, const int32_t *labels, int32_t num_classes,
+                       int32_t *out_label, float *out_share, void *stream)
+{
+    if (int rc = check_weighted_list("weighted_vote", q, m, k, idx, w))
+        return rc;
+    if (num_classes < 1)
+        return set_error(GWBP_EINVAL, "weighted_vote: num_classes must be at least 1 (got %d)", (int)num_classes);
+    if (!labels || (q > 0 && (!out_label || !out_share)))
+        return set_error(GWBP_EINVAL, "weighted_vote: null labels, out_label or out_share");
+    if (misaligned(labels, 3) || misaligned(out_label, 3) || misaligned(out_share, 3))
+        return set_error(GWBP_EINVAL, "weighted_vote: labels, out_label and out_share must be 4-B aligned");
+    const void *const written[] = {out_label, out_share}, *const read[] = {idx, w, labels};
+    if (q > 0)
+        if (int rc = check_regions_distinct("weighted_vote", written, 2, read, 3))
+            return rc;
+    return launch_weighted_vote(q, m, k, idx, w, labels, num_classes, out_label, out_share, as_stream(stream));
+}
+
 // the checks the two passes of the fit share
 static int check_pca_rows(const char *what, int64_t N, int32_t D, const float *X, int64_t ldx, const void *workspace,
                           size_t workspace_bytes)

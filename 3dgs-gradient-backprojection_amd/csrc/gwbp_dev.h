@@ -317,6 +317,17 @@ int launch_neighbor_similarity(int64_t N, int D, int k, const int32_t *idx, cons
 int launch_edge_union(int64_t N, int k, const int32_t *idx, const float *sim, const int32_t *live, const float *dist,
                       const int32_t *group, float sim_min, float max_dist, int32_t *count, int32_t *parent, int32_t *status,
                       hipStream_t s);
+// a field asked at arbitrary 3-D points (sample.hip): the packed Gaussians in the grid's sorted order, each query's k Gaussians of
+// largest weight, the field blended over such a list, and the weighted vote of a label field.  live / visited may be nullptr
+int launch_gaussian_pack(int64_t N, const float *means, int64_t ldm, const float *quats, int64_t ldq, const float *scales, int64_t lds_,
+                         const float *opac, const uint8_t *live, const int64_t *perm, float *pack, hipStream_t s);
+int launch_point_gaussians(const float *sorted, const int32_t *cell_start, const float *lo, float h, const int32_t *dims,
+                           const float *pack, float r2, float alpha_min, int64_t Q, const float *queries, int64_t ldq,
+                           const int64_t *order, int k, int32_t *idx, float *w, int32_t *n_contrib, int32_t *visited, hipStream_t s);
+int launch_neighbor_blend(int64_t Q, int64_t M, int D, int k, const int32_t *idx, const float *w, const float *F, int64_t ldf,
+                          float *out, int64_t ldo, float *wsum, hipStream_t s);
+int launch_weighted_vote(int64_t Q, int64_t M, int k, const int32_t *idx, const float *w, const int32_t *labels, int K,
+                         int32_t *out_label, float *out_share, hipStream_t s);
 // PCA of a finished field (pca.hip): column means, centred Gram, projection onto k <= 16 components, colours.  ws: the caller's
 // pca_workspace_bytes(N, D) bytes (the slices' partial sums), free again when the call's kernels have run.
 size_t pca_workspace_bytes(int64_t N, int D);

@@ -648,6 +648,64 @@ GWBP_API int gwbp_edge_union(int64_t n, int32_t k, const int32_t *idx, const flo
                              const int32_t *group, float sim_min, float max_dist, int32_t *count, int32_t *parent, int32_t *status,
                              void *stream);
 
+/* ---- Point samples: what a finished field says at an arbitrary 3-D point, by the Gaussians' own shape (scale, rotation, opacity),
+ * on the grid of the spatial search above ---------------------------------------------------------------------------------------------
+ * means[n, 3], quats[n, 4] (wxyz, not normalised), scales[n, 3] (after exp), opacities[n] (after sigmoid): as for the projection, fp32,
+ * read in place at row strides ldm >= 3, ldq >= 4, lds >= 3.  live[n] (optional, may be NULL: every Gaussian): uint8.  The contract:
+ *   a Gaussian is LIVE when its mean is finite; its quaternion is finite with 0 < n2 < +inf, n2 = fmaf(q3, q3, fmaf(q2, q2, fmaf(q1,
+ *     q1, q0 * q0))); its scales are finite and > 0; its opacity is finite and > 0; live[i] != 0;
+ *   PACK, fp32, every operation written out and rounded once: inv = 1 / sqrtf(n2) (a correctly rounded sqrt and divide);
+ *     (w, x, y, z) = (q0 inv, q1 inv, q2 inv, q3 inv); x2 = x x, y2 = y y, z2 = z z, xy = x y, xz = x z, yz = y z, wx = w x, wy = w y,
+ *     wz = w z;  R (gsplat's quat_to_rotmat) = [1 - 2 (y2 + z2), 2 (xy - wz), 2 (xz + wy); 2 (xy + wz), 1 - 2 (x2 + z2), 2 (yz - wx);
+ *     2 (xz - wy), 2 (yz + wx), 1 - 2 (x2 + y2)];  M[a][b] = R[b][a] / s[a], one correctly rounded divide each;  o = the opacity.
+ *     A dead Gaussian has M = 0 and o = 0.  Rotate-then-divide on purpose: a precomputed inverse covariance loses (s_max / s_min)^2
+ *     eps in sigma on needle-shaped Gaussians, this form about (|d| / s_min) eps |u|.  (q, -q and 2 q give the same bits.)
+ *     The record: GWBP_SAMPLE_PACK = 12 floats, (M00 M01 M02 o) (M10 M11 M12 0) (M20 M21 M22 0);
+ *   WEIGHT of Gaussian i at x: d = x - mean, each component in fp32; u_a = fmaf(M[a][2], d_z, fmaf(M[a][1], d_y, M[a][0] * d_x));
+ *     m2 = fmaf(u_2, u_2, fmaf(u_1, u_1, u_0 * u_0)); sigma = 0.5f * m2; w = o * exp_neg(-sigma), exp_neg the blend's deterministic
+ *     exponential (ln 2 range reduction, degree-7 Horner polynomial, no transcendental unit).  The weight is KEPT when sigma <= 80
+ *     and w >= alpha_min, else it is 0.  alpha_min = 1/255 (0x1.010102p-8f) makes the rule "a Gaussian counts at a point exactly
+ *     where the rasteriser would let it count at a pixel"; alpha_min in [GWBP_SAMPLE_MIN_ALPHA, 1], so that no subnormal is kept;
+ *   the CANDIDATES of a query are the Gaussians with a finite mean whose centre has d2 <= r2, d2 gwbp_spatial_knn's expression, r2
+ *     the caller's fp32 radius * radius as for gwbp_radius_count (a dead candidate has weight 0 and is never kept);
+ *   the RESULT of a query: the k candidates of largest kept weight, ordered by (weight descending, index ascending): idx[q, k]
+ *     (int32, original indices, tail -1), w[q, k] (fp32, tail 0), and n_contrib[q] (int32) = the number of candidates with a kept
+ *     weight; n_contrib > k says the list was truncated.  A non-finite query gets the empty result.
+ * The result is a pure function of the inputs: it does not depend on the grid, the launch or the order of the walk, and two runs give
+ * the same bits.  Nothing is summed across candidates in the walk, which is why it returns a count and not a mass.
+ *   gwbp_gaussian_pack     pack[p] (float [n, GWBP_SAMPLE_PACK], 16-B aligned) = the record of Gaussian perm[p]: the grid's SORTED
+ *                          order (perm: the permutation gwbp_spatial_build was given), so that a walk position indexes it.
+ *   gwbp_point_gaussians   the result above for the query rows queries[g * ldq + 0..2], g < q.  sorted / cell_start / the grid: what
+ *                          gwbp_spatial_build made of the means.  order[q]: as for gwbp_spatial_knn.  visited (optional): int32 [q],
+ *                          the number of Gaussians whose distance the query's lane computed.  Lane-private lists: no atomics.
+ *   gwbp_neighbor_blend    over a list (idx[q, k], w[q, k]) and features[m, D] (row i at features + i * ldf): an entry with an index
+ *                          outside [0, m) or with w == 0 is SKIPPED and its row is not read (a NaN row behind a zero weight does
+ *                          not leak).  W = the chain acc = w_j + acc from +0 over the entries left, in list order; out[g * ldo + c]
+ *                          = (the chain acc = fmaf(w_j, features[idx_j, c], acc) from +0, same order) / W, one correctly rounded
+ *                          divide; wsum[g] = W.  A row with no entry left is zero and its wsum is 0.  Rows whose addresses and
+ *                          strides are 16-B aligned move with 16-B loads and stores, with the same bits.  No atomics.
+ *   gwbp_weighted_vote     over a list and labels[m] (int32): an entry takes part when it is not skipped (as above) and its label c
+ *                          = labels[idx_j] is in [0, num_classes).  S[c] = the chain acc = w_j + acc from +0 over the entries of
+ *                          class c, in list order; T = the same chain over all entries that take part.  out_label[g] = the class of
+ *                          largest S, ties to the smallest class, -1 when nothing took part; out_share[g] = S[best] / T (0 then).
+ * 1 <= n, m < 2^31; 0 <= q < 2^31; 1 <= k <= GWBP_SAMPLE_MAX_K; D >= 1; r2 >= 0 (+inf allowed); the grid as for gwbp_spatial_knn.
+ * GWBP_EINVAL before any HIP call: a size, k, D, num_classes, r2, alpha_min, grid dimension, cell size or stride outside these, a
+ * null required pointer, a misaligned pointer, an output array that is an input array or another output. */
+#define GWBP_SAMPLE_PACK 12
+#define GWBP_SAMPLE_MAX_K 32
+#define GWBP_SAMPLE_MIN_ALPHA 1e-30f
+GWBP_API int gwbp_gaussian_pack(int64_t n, const float *means, int64_t ldm, const float *quats, int64_t ldq, const float *scales,
+                                int64_t lds, const float *opacities, const uint8_t *live, const int64_t *perm, float *pack,
+                                void *stream);
+GWBP_API int gwbp_point_gaussians(int64_t n, const float *sorted, const int32_t *cell_start, float lo_x, float lo_y, float lo_z,
+                                  float cell_size, int32_t nx, int32_t ny, int32_t nz, const float *pack, float r2, float alpha_min,
+                                  int64_t q, const float *queries, int64_t ldq, const int64_t *order, int32_t k, int32_t *idx, float *w,
+                                  int32_t *n_contrib, int32_t *visited, void *stream);
+GWBP_API int gwbp_neighbor_blend(int64_t q, int64_t m, int32_t D, int32_t k, const int32_t *idx, const float *w, const float *features,
+                                 int64_t ldf, float *out, int64_t ldo, float *wsum, void *stream);
+GWBP_API int gwbp_weighted_vote(int64_t q, int64_t m, int32_t k, const int32_t *idx, const float *w, const int32_t *labels,
+                                int32_t num_classes, int32_t *out_label, float *out_share, void *stream);
+
 /* ---- PCA of a finished field (the reference's visualize_pca.py: sklearn PCA(3) on the host copy of the [N, D] field) -------------
  * The [N, D] passes of the fit and of the transform; the D x D eigen-decomposition between them is the caller's (float64 eigh of
  * gram / (N - 1); sklearn's covariance_eigh solver does the same).  X[g * ldx + 0..D-1], g < N, is read in place, fp32, any row
