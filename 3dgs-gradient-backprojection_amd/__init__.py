@@ -23,6 +23,9 @@ JojiJoseph/3dgs-gradient-backprojection), hand-written HIP kernels behind a C AB
     from gsbp_amd import select_components, split_instances  # (DBSCAN on the grid), and masks / label fields split into instances
     from gsbp_amd import associate_masks, associated_label_fn, match_masks, remap_masks  # per-view instance masks with unrelated ids
                                                     # associated into consistent 3-D groups: integer overlap and vote kernels
+    from gsbp_amd import new_sparse_votes, sparse_votes_groups, sparse_votes_canonical, sparse_votes_dense, sparse_votes_stats
+    from gsbp_amd import create_sparse_label_field, sparse_label_argmax, sparse_label_dense  # the votes in per-Gaussian slot lists:
+                                                    # thousands of groups or classes without a dense [N, K] table
     from gsbp_amd import similarity_components, similarity_levels, neighbor_similarity  # regions by geometry AND features: the
     from gsbp_amd import edge_strength, region_prompt_mask  # spatial k-NN graph cut where the features' cosine falls below a threshold
     from gsbp_amd import point_gaussians, sample_field, sample_labels, transfer_field, score_point_labels  # the field and its labels
@@ -48,6 +51,9 @@ from . import components  # noqa: F401
 from .components import Components, Instances, radius_components, radius_count, select_components, split_instances, suggest_radius, synthetic_instances  # noqa: F401
 from . import associate  # noqa: F401
 from .associate import Association, associate_masks, associated_label_fn, match_masks, quantize_weights, remap_masks  # noqa: F401
+from . import sparse_votes  # noqa: F401
+from .associate import create_sparse_label_field  # noqa: F401
+from .sparse_votes import SparseLabelField, SparseVotes, new_sparse_votes, sparse_label_argmax, sparse_label_dense, sparse_votes_bytes, sparse_votes_canonical, sparse_votes_dense, sparse_votes_groups, sparse_votes_stats  # noqa: F401
 from . import regions  # noqa: F401
 from .regions import edge_strength, neighbor_similarity, region_prompt_mask, similarity_components, similarity_levels, synthetic_regions  # noqa: F401
 from . import sample  # noqa: F401

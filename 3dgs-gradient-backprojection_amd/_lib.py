@@ -85,6 +85,7 @@ FLAG_NARROW_SCATTER = 4  # GWBP_FLAG_NARROW_SCATTER
 FLAG_SPLIT_ENCODER = 16  # GWBP_FLAG_SPLIT_ENCODER
 MAP_F32, MAP_F16, MAP_BF16 = 0, 1, 2  # GWBP_MAP_* (feature-map element type of the typed scatter entry points)
 LABEL_U8, LABEL_I16, LABEL_I32 = 0, 1, 2  # GWBP_LABEL_* (element type of gwbp_scatter_labels' label map)
+SPARSE_MAX_SLOTS = 32  # GWBP_SPARSE_MAX_SLOTS (gwbp_label_votes_sparse' slots per Gaussian)
 MASK_SLOT_BYTES = 32  # GWBP_MASK_SLOT_BYTES (gwbp_scatter_mask_features' slot store per intersection)
 
 # gwbp_project_camera: gsplat.rasterization's camera_model / rasterize_mode names -> GWBP_CAMERA_* / GWBP_RASTERIZE_*
@@ -185,6 +186,8 @@ ARGTYPES = {
     # the association walks: labels, label_type, ls_y, ls_x, num_labels, ymap, xmap, (group | remap), n_cols, (O | V), ld, stream
     "gwbp_label_overlap": _WSV + [_P, _I32, _I64, _I64, _I32, _P, _P, _P, _I32, _P, _I64, _P],
     "gwbp_label_votes": _WSV + [_P, _I32, _I64, _I64, _I32, _P, _P, _P, _I32, _P, _I64, _P],
+    # the votes into slot lists: labels .. remap as above, then slots, keys, ld_keys, vals, ld_vals, spill, total, stream
+    "gwbp_label_votes_sparse": _WSV + [_P, _I32, _I64, _I64, _I32, _P, _P, _P, _I32, _P, _I64, _P, _I64, _P, _P, _P],
     # N, M, D, k, Q, ldq, S, lds, idx, score, stream  /  N, M, k, idx, labels, num_classes, label_out, counts, ldc, stream
     "gwbp_knn_search": [_I64, _I32, _I32, _I32, _P, _I64, _P, _I64, _P, _P, _P],
     "gwbp_knn_vote": [_I64, _I32, _I32, _P, _P, _I32, _P, _P, _I64, _P],

@@ -15,16 +15,23 @@ masks to groups one-to-one by IoU (match_masks) and opens groups for what is lef
 to the per-Gaussian group votes.  Both kernels sum fixed-point integers (quantize_weights), so the tables -- and with them every
 decision, each of which feeds the next view -- are exact and the same on every run.  There is no merging of groups behind the pass
 and no second pass.  The defaults iou_min = 0.2 and min_mass = 1.0 come from one synthetic scene and are not tuned.
+
+votes="sparse" keeps the evidence in per-Gaussian slot lists (sparse_votes.py, gwbp_label_votes_sparse) instead of the dense
+[N, max_groups] table -- N * (12 * slots + 8) bytes whatever the number of groups -- and sizes the per-view overlap table by the
+groups that exist; max_groups is then a bound on ids only.  create_sparse_label_field is create_label_field's P in that form.
 """
 from __future__ import annotations
 
-from typing import Callable, Dict, List, NamedTuple, Optional, Sequence
+import warnings
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Union
 
 import numpy as np
 import torch
 
 from ._lib import GwbpError
 from .engine import Engine
+from .sparse_votes import (SparseLabelField, SparseVotes, new_sparse_votes, sparse_label_field_of, sparse_votes_canonical,
+                           sparse_votes_groups)
 
 WEIGHT_SCALE = 2 ** 20  # fixed-point steps per unit of blend weight
 WEIGHT_CLAMP = 4.0      # a stored weight saturates here (above 1 only with a pixel weight map)
@@ -96,9 +103,11 @@ def match_masks(O, n_groups: int, iou_min: float = 0.2, min_mass: float = 1.0, m
 class Association(NamedTuple):
     maps: List[torch.Tensor]   # per view (view-index order): int32 [max_masks] on the device, mask id -> group id or -1
     groups: torch.Tensor       # int32 [N]: every Gaussian's group, -1 without one
-    votes: torch.Tensor        # int64 [N, max_groups]: fixed-point evidence per group (votes / WEIGHT_SCALE is blend weight)
+    votes: Union[torch.Tensor, SparseVotes]  # int64 [N, max_groups]: fixed-point evidence per group (votes / WEIGHT_SCALE is
+    #                            blend weight); with votes="sparse" the slot lists, in canonical order
     n_groups: int
     views: List[Dict]          # per processed view, in processing order: view, matched, opened, dropped, dead, unassigned_share
+    #                            (sparse: and overflow_rows, the rows with spill after the view)
 
 
 def remap_masks(labels: torch.Tensor, remap) -> torch.Tensor:
@@ -122,11 +131,34 @@ def group_of_votes(votes: torch.Tensor) -> torch.Tensor:
     return torch.where(best > 0, arg, -1).to(torch.int32)
 
 
+def _blend_view(what: str, eng: Engine, v: int, view, gauss, weights, after=None):
+    """The front of one view for the drivers of this module: project, sort, blend_weights (blend_weighted with `weights`), then
+    after() -- what has to be enqueued before the one synchronisation that reads the overflow word; its result is returned.  The
+    drivers' policy: overflow bits 0 / 1 are capacities (grow the workspace, run the view again, six attempts; nothing of the
+    view has been added to an accumulator yet), anything else cannot be cured."""
+    for attempt in range(6):
+        eng.project(view, *gauss)
+        eng.bin_sort(view)
+        if weights is not None:
+            eng.blend_weighted(view, weights())
+        else:
+            eng.blend_weights(view)
+        out = after() if after is not None else None
+        stats = eng.stats()
+        if not stats["overflow"]:
+            return out
+        if stats["overflow"] & ~3 or attempt == 5:
+            raise RuntimeError(f"{what}: view {v} ended with gwbp_stats.overflow = {stats['overflow']}"
+                               + (" after five enlargements" if not stats["overflow"] & ~3 else ""))
+        eng.grow(stats)
+
+
 def associate_masks(means, quats, scales, opacities, viewmats, K, width: int, height: int,
                     mask_fn: Callable[[int], torch.Tensor], max_masks: int, max_groups: int = 256, iou_min: float = 0.2,
                     min_mass: float = 1.0, order: Optional[Sequence[int]] = None,
                     pixel_weight_fn: Optional[Callable[[int], torch.Tensor]] = None, upsample: Optional[str] = None,
-                    engine: Optional[Engine] = None, **raster_kw) -> Association:
+                    engine: Optional[Engine] = None, votes: str = "dense", slots: int = 8, on_overflow: str = "warn",
+                    **raster_kw) -> Association:
     """Associate the views' instance maps into 3-D groups (module docstring).  mask_fn(v) -> the view's integer [height, width]
     map on the device (with upsample="nearest": any [h, w]), ids in [0, max_masks); anything else is ignored, as in
     create_label_field.  Per view of `order` (default 0 .. V-1): project, sort, blend_weights (blend_weighted with
@@ -134,7 +166,16 @@ def associate_masks(means, quats, scales, opacities, viewmats, K, width: int, he
     view: the algorithm is sequential by nature), match_masks, label_votes with the new remap, groups = argmax of the votes.
     A workspace overflow grows the workspace and runs that view again; nothing of an overflowed view has been added.
     raster_kw: near_plane, far_plane, eps2d, radius_clip, camera_model, rasterize_mode.
-    Memory: the votes take 8 * N * max_groups bytes -- 2 GB at N = 1 M and 256 groups."""
+    Memory: the votes take 8 * N * max_groups bytes -- 2 GB at N = 1 M and 256 groups.
+
+    votes="sparse": the evidence goes into `slots` (1 .. 32) slots per Gaussian (label_votes_sparse), N * (12 * slots + 8) bytes,
+    and the per-view argmax comes from the lists; Association.votes is a SparseVotes in canonical order.  The overlap table is
+    zeroed and copied with the columns 0 .. n_groups only (its buffer grows geometrically), so max_groups bounds ids and nothing
+    else and may be 65536.  While no row spills, every decision equals the dense mode's, bit for bit and on every run.  A row that
+    has received more than `slots` distinct groups spills (WHICH rows is a function of the input; which groups keep their slots
+    is not): on_overflow="raise" raises at the first view that leaves such a row, "warn" warns once and goes on -- the groups
+    that feed the next view are then no longer promised to be the same on every run.  Every entry of Association.views gains
+    overflow_rows."""
     from ._views import raster_kw as _raster_kw, require_device
     require_device("associate_masks", means)
     kw = _raster_kw("associate_masks", raster_kw)
@@ -144,41 +185,97 @@ def associate_masks(means, quats, scales, opacities, viewmats, K, width: int, he
     n_masks, max_groups = int(max_masks), int(max_groups)
     if n_masks < 1 or max_groups < 1:
         raise ValueError("max_masks and max_groups must be positive")
+    if votes not in ("dense", "sparse"):
+        raise ValueError(f"votes must be 'dense' or 'sparse', got {votes!r}")
+    if on_overflow not in ("warn", "raise"):
+        raise ValueError(f"on_overflow must be 'warn' or 'raise', got {on_overflow!r}")
+    sparse = votes == "sparse"
     width, height = int(width), int(height)
     n_views = int(viewmats.shape[0])
     order = list(range(n_views)) if order is None else [int(v) for v in order]
     vm_host, K_host = viewmats.detach().cpu(), K.detach().cpu()
     eng = engine or Engine(n, width, height, device=dev, tight_binning=True)
-    votes = torch.zeros(n, max_groups, dtype=torch.int64, device=dev)
+    gauss = (means, quats, scales, opacities)
+
+    def weights_of(v):
+        return None if pixel_weight_fn is None else (lambda: pixel_weight_fn(v))
+    acc = new_sparse_votes(n, slots, device=dev) if sparse else torch.zeros(n, max_groups, dtype=torch.int64, device=dev)
     groups = torch.full((n,), -1, dtype=torch.int32, device=dev)
-    O = torch.empty(n_masks + 1, max_groups + 1, dtype=torch.int64, device=dev)
+    # dense: one table as wide as max_groups.  sparse: as wide as the groups that exist (the buffer doubles when they outgrow it)
+    O_store = torch.empty(n_masks + 1, min(max_groups, 15) + 1 if sparse else max_groups + 1, dtype=torch.int64, device=dev)
+    warned = False
     maps = [torch.full((n_masks,), -1, dtype=torch.int32, device=dev) for _ in range(n_views)]
     n_groups, table = 0, []
     for v in order:
         labels = mask_fn(v)
+        if sparse and n_groups + 1 > O_store.shape[1]:
+            O_store = torch.empty(n_masks + 1, min(max_groups, max(2 * O_store.shape[1] - 2, n_groups)) + 1, dtype=torch.int64,
+                                  device=dev)
+        O = O_store[:, :n_groups + 1] if sparse else O_store  # (a row stride wider than n_cols: label_overlap takes it)
         view = eng.view(vm_host[v], K_host if K_host.dim() == 2 else K_host[v], width, height, **kw)
-        for attempt in range(6):
-            eng.project(view, means, quats, scales, opacities)
-            eng.bin_sort(view)
-            if pixel_weight_fn is not None:
-                eng.blend_weighted(view, pixel_weight_fn(v))
-            else:
-                eng.blend_weights(view)
+
+        def overlap(view=view, labels=labels, O=O, groups=groups):
             O.zero_()
             eng.label_overlap(view, labels, groups, O, n_masks, upsample=upsample)
-            O_host = O.cpu().numpy()
-            stats = eng.stats()
-            if not stats["overflow"]:
-                break
-            # the drivers' policy: bits 0 / 1 are capacities (grow, run the view again, six attempts); anything else cannot be cured
-            if stats["overflow"] & ~3 or attempt == 5:
-                raise RuntimeError(f"associate_masks: view {v} ended with gwbp_stats.overflow = {stats['overflow']}"
-                                   + (" after five enlargements" if not stats["overflow"] & ~3 else ""))
-            eng.grow(stats)
+            return O.cpu().numpy()
+
+        O_host = _blend_view("associate_masks", eng, v, view, gauss, weights_of(v), overlap)
         remap, n_groups, counts = match_masks(O_host, n_groups, iou_min, min_mass, max_groups, return_counts=True)
         maps[v] = torch.from_numpy(remap).to(dev)
-        eng.label_votes(view, labels, maps[v], votes, n_masks, upsample=upsample)
-        groups = group_of_votes(votes)
         total = int(O_host.sum())
         table.append(dict(view=v, **counts, unassigned_share=float(O_host[:, 0].sum()) / total if total else 0.0))
-    return Association(maps, groups, votes, n_groups, table)
+        if not sparse:
+            eng.label_votes(view, labels, maps[v], acc, n_masks, upsample=upsample)
+            groups = group_of_votes(acc)
+            continue
+        eng.label_votes_sparse(view, labels, maps[v], acc, n_masks, upsample=upsample)
+        groups, _ = sparse_votes_groups(acc)
+        table[-1]["overflow_rows"] = spilled = int((acc.spill > 0).sum())
+        if spilled and on_overflow == "raise":
+            raise GwbpError(f"associate_masks: after view {v}, {spilled} Gaussians have received more than {slots} distinct groups "
+                            "(their votes spilled): raise slots")
+        if spilled and not warned:
+            warned = True
+            warnings.warn(f"associate_masks: after view {v}, {spilled} Gaussians have received more than {slots} distinct groups; "
+                          "which of them keep a slot depends on the order of the run, so the groups that feed the next views "
+                          "are no longer promised to be the same on every run (raise slots, or on_overflow='raise')",
+                          RuntimeWarning, stacklevel=2)
+    return Association(maps, groups, sparse_votes_canonical(acc) if sparse else acc, n_groups, table)
+
+
+def create_sparse_label_field(means, quats, scales, opacities, viewmats, K, width: int, height: int,
+                              label_fn: Callable[[int], torch.Tensor], num_classes: int, slots: int = 8,
+                              pixel_weight_fn: Optional[Callable[[int], torch.Tensor]] = None, upsample: Optional[str] = None,
+                              engine: Optional[Engine] = None, **raster_kw) -> SparseLabelField:
+    """create_label_field's P[g, k] = F[g, k] / d[g] restricted to each Gaussian's non-zero classes: SparseLabelField(ids int32
+    [N, slots], fractions float32 [N, slots], spill_fraction float32 [N], total int64 [N]) in canonical order (largest share first,
+    then the smaller id; -1 = empty), N * (12 * slots + 16) bytes of accumulator whatever num_classes.  Per view (in order, one
+    stream): project, sort, blend_weights (blend_weighted with pixel_weight_fn(v)), label_votes_sparse with the identity remap and
+    total; a workspace overflow grows the workspace and runs the view again before anything of it has been added.  The sums are
+    the fixed-point integers of quantize_weights, so fractions = vals / total (one float64 division, then narrowed) differs from
+    P by the quantisation (at most 2^-21 per stored entry) and P's own float error; total is d in the same fixed point.  A
+    Gaussian that saw more than `slots` classes keeps `slots` of them (which ones depends on the run) and reports the rest as
+    spill_fraction.  label_fn, upsample, raster_kw: as associate_masks' mask_fn, upsample, raster_kw."""
+    from ._views import raster_kw as _raster_kw, require_device
+    require_device("create_sparse_label_field", means)
+    kw = _raster_kw("create_sparse_label_field", raster_kw)
+    if upsample not in (None, "nearest"):
+        raise ValueError(f"upsample must be None or 'nearest' for label maps, got {upsample!r}")
+    n, dev, n_classes = int(means.shape[0]), means.device, int(num_classes)
+    if n_classes < 1:
+        raise ValueError("num_classes must be positive")
+    width, height = int(width), int(height)
+    vm_host, K_host = viewmats.detach().cpu(), K.detach().cpu()
+    eng = engine or Engine(n, width, height, device=dev, tight_binning=True)
+    gauss = (means, quats, scales, opacities)
+
+    def weights_of(v):
+        return None if pixel_weight_fn is None else (lambda: pixel_weight_fn(v))
+    sv = new_sparse_votes(n, slots, device=dev, total=True)
+    identity = torch.arange(n_classes, dtype=torch.int32, device=dev)
+    for v in range(int(viewmats.shape[0])):
+        labels = label_fn(v)
+        view = eng.view(vm_host[v], K_host if K_host.dim() == 2 else K_host[v], width, height, **kw)
+        _blend_view("create_sparse_label_field", eng, v, view, gauss, weights_of(v))
+        eng.label_votes_sparse(view, labels, identity, sv, n_classes, upsample=upsample)
+    return sparse_label_field_of(sv)

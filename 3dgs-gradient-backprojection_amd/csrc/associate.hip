@@ -1,13 +1,15 @@
-// associate.hip -- the two integer walks of the weight store behind associate_masks (associate.py): which 3-D group does a mask
+// associate.hip -- the integer walks of the weight store behind associate_masks (associate.py): which 3-D group does a mask
 // of a new view continue?
 //     overlap:  O[row(L(p)), group[g] + 1] += q(w)       one int64 table per view, "mask m x existing group j"
 //     votes:    V[g, remap[L(p)]]          += q(w)       int64 [N, ldv], a Gaussian's evidence per group
+//     sparse:   slot(g, remap[L(p)])       += q(w)       the votes into S (key, sum) slots per Gaussian instead of a dense row
 // with q(w) = (uint32) rintf(fminf(fmaxf(w, 0), 4) * 2^20): every sum is an INTEGER sum, so the tables have the same bits whatever
 // the order of the atomics, the split between the leader path and the left-over path, or what the LDS table combined first.  That
 // is what a sequential association needs: each view's table decides the next view's input.
 //
-// k_label_assoc<T, kVotes>: the walk of k_scatter_labels (label.hip) -- one workgroup per tile in tile_order, the tile's 256 labels
-// staged once in LDS (through the nearest-index maps for a low-resolution map), a record's entries read as the two dense runs,
+// assoc_walk<T, kMode>, the body of k_label_assoc<T, kVotes> and k_label_votes_sparse<T>: the walk of k_scatter_labels (label.hip)
+// -- one workgroup per tile in tile_order, the tile's 256 labels staged once in LDS (through the nearest-index maps for a
+// low-resolution map), a record's entries read as the two dense runs,
 // reduce by key with kAssocRounds leaders and the left-over entries one by one.
 //   - overlap: the staged value is the ROW (L(p), or num_labels for an ignored pixel: column sums stay complete); the column is
 //     the record's.  Every workgroup would hit the same few hundred addresses of O, so the sums go into an LDS table keyed by
@@ -16,7 +18,14 @@
 //     integer either way.  The leader sums of several records go into the table together, one lane each (the batch below)
 //   - votes: the staged value is the COLUMN remap[L(p)] (-1: adds nothing).  Adds go to many rows: one 8-byte atomic per (record,
 //     distinct column), batched as k_scatter_labels batches its float adds -- lane i holds the i-th (address, value) of the wave.
-// A record's per-key sum fits uint32 (256 entries x 2^22).  No float atomics; every loop is wave-uniform and bounded.
+//   - sparse: the votes' walk; the destination is found, not computed.  A lane carries (row, key, value), probes the row's slots
+//     0 .. S-1 in index order -- a relaxed agent-scope load of the key, a 4-byte compare-and-swap (empty -> key) only where the load
+//     saw empty -- and adds with one 8-byte atomic to the slot whose key is its own, or to spill[row] after S misses.  A key never
+//     changes once set, so a load can be stale only as "empty" (which costs the compare-and-swap, whose answer is the truth), and
+//     a lane claims slot s only after it has SEEN another key in every slot before s: no key can sit in two slots of a row.
+//     total[row] (optional) takes the record's whole sum, whatever the labels, as one more staged entry (key kAssocTotal).
+// A record's per-key sum fits uint32 (256 entries x 2^22).  No float atomics; every loop is wave-uniform and bounded (the probe
+// loop by S <= 32, left by a ballot as `combine`'s): no retry, no spin, no loop inside a divergent branch.
 #include "gwbp_dev.h"
 
 namespace gwbp {
@@ -29,6 +38,17 @@ constexpr int kAssocSlots = 4;     // a record holds at most 256 entries: four p
 constexpr int kAssocTable = 512;
 constexpr int kAssocProbes = 8;
 constexpr u64 kAssocEmpty = ~0ull; // (a key is an element's offset in O, below 2^63)
+enum AssocMode { kAssocOverlap = 0, kAssocVotes = 1, kAssocSparse = 2 };
+constexpr int kAssocTotal = -2;    // sparse: the staged key of a record's sum for total[] (a vote's key is >= 0)
+
+// the per-Gaussian slot lists of gwbp_label_votes_sparse (include/gwbp.h): keys int32 [N, ldk] (-1 = empty), vals int64 [N, ldv],
+// spill int64 [N], total int64 [N] or NULL
+struct SparseDev {
+    int32_t *keys;
+    u64 *vals, *spill, *total;
+    int64_t ldk, ldv;
+    int slots;
+};
 
 __device__ __forceinline__ u32 assoc_quantize(float w)
 {
@@ -52,14 +72,17 @@ __device__ __forceinline__ u32 wave_sum_u32(u32 v)
            (u32)__builtin_amdgcn_readlane((int)v, 32) + (u32)__builtin_amdgcn_readlane((int)v, 48);
 }
 
-// aux: group int32 [N] (overlap) or remap int32 [K] (votes); out: O int64 [K + 1, ld] or V int64 [N, ld]
-template <typename T, bool kVotes>
-__global__ __launch_bounds__(kAssocThreads) void k_label_assoc(
-    ViewDev V, const u32 *__restrict__ tile_order, const u32 *__restrict__ tile_offsets, const u32 *__restrict__ hdr_count,
+// The walk, shared by the kernels below (a device function, so that k_label_assoc keeps its arguments and its code as they were).
+// aux: group int32 [N] (overlap) or remap int32 [K] (votes, sparse); out: O int64 [K + 1, ld] or V int64 [N, ld]; sparse: SP
+template <typename T, int kMode>
+__device__ __forceinline__ void assoc_walk(
+    const ViewDev &V, const u32 *__restrict__ tile_order, const u32 *__restrict__ tile_offsets, const u32 *__restrict__ hdr_count,
     const Header *__restrict__ headers, const WPair *__restrict__ wpool, const T *__restrict__ labels, int64_t ls_y, int64_t ls_x,
     const int32_t *__restrict__ ymap, const int32_t *__restrict__ xmap, int K, const int32_t *__restrict__ aux, int n_cols,
-    u64 *__restrict__ out, int64_t ld, Counters *__restrict__ ctr)
+    u64 *__restrict__ out, int64_t ld, Counters *__restrict__ ctr, const SparseDev &SP)
 {
+    constexpr bool kSparse = kMode == kAssocSparse;
+    constexpr bool kVotes = kMode != kAssocOverlap; // the votes' walk: the staged value is a column / key, adds go to row gid
     const u32 kind = ctr->blend_kind;
     if (kind == kBlendFused || kind == kBlendToken) { // the workspace holds no weight store: refuse, flag (as k_scatter_labels does)
         if (blockIdx.x == 0 && threadIdx.x == 0)
@@ -85,7 +108,7 @@ __global__ __launch_bounds__(kAssocThreads) void k_label_assoc(
             const bool in = v >= 0 && v < K;
             if (kVotes) {
                 const int c = in ? aux[v] : -1;
-                lab = (c >= 0 && c < n_cols) ? c : -1;
+                lab = (c >= 0 && (kSparse || c < n_cols)) ? c : -1; // (sparse: any c >= 0 is a key)
             } else {
                 lab = in ? v : K;
             }
@@ -131,8 +154,38 @@ __global__ __launch_bounds__(kAssocThreads) void k_label_assoc(
         if (act)
             atomicAdd(out + key, (u64)q);
     };
+    // sparse: v to the slot of `row` whose key is `key` (the first empty one becomes it), else to spill[row]; key kAssocTotal: to
+    // total[row].  Slots in index order, one probe per trip, the trip count wave-uniform
+    auto sparse_add = [&](bool act, u32 row, int key, u32 v) {
+        act = act && v != 0u;
+        if (act && key == kAssocTotal) {
+            atomicAdd(SP.total + row, (u64)v);
+            act = false;
+        }
+        int32_t *kp = SP.keys + (int64_t)row * SP.ldk;
+        u64 *vp = SP.vals + (int64_t)row * SP.ldv;
+        for (int s = 0; s < SP.slots; ++s) {
+            if (__builtin_amdgcn_ballot_w64(act) == 0ull)
+                break;
+            if (act) {
+                int cur = __hip_atomic_load(kp + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (cur == -1) {
+                    cur = atomicCAS(kp + s, -1, key);
+                    cur = cur == -1 ? key : cur; // ours now; or somebody else's key, which stays
+                }
+                if (cur == key) {
+                    atomicAdd(vp + s, (u64)v);
+                    act = false;
+                }
+            }
+        }
+        if (act)
+            atomicAdd(SP.spill + row, (u64)v);
+    };
     auto flush = [&]() {
-        if (kVotes) {
+        if (kSparse) {
+            sparse_add((u32)lane < n_out, (u32)(out_at >> 32), (int)(u32)out_at, out_v);
+        } else if (kVotes) {
             if ((u32)lane < n_out && out_v != 0u)
                 atomicAdd(out + out_at, (u64)out_v);
         } else {
@@ -143,7 +196,7 @@ __global__ __launch_bounds__(kAssocThreads) void k_label_assoc(
     static_assert(kAssocTable == 512, "the slot hash keeps 9 bits");
 
     for (u32 h = wave; h < nh; h += kAssocThreads / 64) {
-        if (n_out > 64u - kAssocRounds) // a record stages at most kAssocRounds sums
+        if (n_out > 64u - kAssocRounds - (kSparse ? 1u : 0u)) // a record stages at most kAssocRounds sums (sparse: and its total)
             flush();
         const Header *hp = hb + h;
         const u32 gid = uniform(hp->gid), w0 = uniform(hp->woff[0]), w2 = uniform(hp->woff[2]);
@@ -155,6 +208,8 @@ __global__ __launch_bounds__(kAssocThreads) void k_label_assoc(
             const int g = (int)uniform((u32)aux[gid]);
             base = (g >= 0 && g <= n_cols - 2) ? (u64)(g + 1) : 0ull;
         }
+        if (kSparse)
+            base = (u64)gid << 32; // a staged entry is (row, key)
         const u64 step = kVotes ? 1ull : (u64)ld; // a staged value k lies at base + k * step
 
         int lab[kAssocSlots];
@@ -171,6 +226,8 @@ __global__ __launch_bounds__(kAssocThreads) void k_label_assoc(
             }
             pend[k] = lab[k] >= 0 && q[k] != 0u;
         }
+        if (kSparse && SP.total) // every entry counts here, whatever its label: the exact denominator of a label field
+            stage(base | (u64)(u32)kAssocTotal, wave_sum_u32(q[0] + q[1] + q[2] + q[3]));
 
         for (int r = 0; r < kAssocRounds; ++r) {
             u64 any = 0ull;
@@ -199,7 +256,9 @@ __global__ __launch_bounds__(kAssocThreads) void k_label_assoc(
             if (__builtin_amdgcn_ballot_w64(pend[k]) == 0ull)
                 continue;
             const u64 at = base + (u64)(pend[k] ? lab[k] : 0) * step;
-            if (kVotes) {
+            if (kSparse) {
+                sparse_add(pend[k], gid, lab[k], q[k]);
+            } else if (kVotes) {
                 if (pend[k])
                     atomicAdd(out + at, (u64)q[k]);
             } else {
@@ -219,26 +278,54 @@ __global__ __launch_bounds__(kAssocThreads) void k_label_assoc(
 }
 
 template <typename T, bool kVotes>
-static void launch_assoc_t(const Ws &W, const ViewDev &V, const void *labels, int64_t ls_y, int64_t ls_x, const int32_t *ymap,
-                           const int32_t *xmap, int K, const int32_t *aux, int n_cols, int64_t *out, int64_t ld, hipStream_t s)
+__global__ __launch_bounds__(kAssocThreads) void k_label_assoc(
+    ViewDev V, const u32 *__restrict__ tile_order, const u32 *__restrict__ tile_offsets, const u32 *__restrict__ hdr_count,
+    const Header *__restrict__ headers, const WPair *__restrict__ wpool, const T *__restrict__ labels, int64_t ls_y, int64_t ls_x,
+    const int32_t *__restrict__ ymap, const int32_t *__restrict__ xmap, int K, const int32_t *__restrict__ aux, int n_cols,
+    u64 *__restrict__ out, int64_t ld, Counters *__restrict__ ctr)
 {
-    const int n_tiles = V.tile_w * V.tile_h;
-    hipLaunchKernelGGL((k_label_assoc<T, kVotes>), dim3(n_tiles), dim3(kAssocThreads), 0, s, V, W.tile_order, W.tile_offsets,
-                       W.hdr_count, W.headers, W.wpool, static_cast<const T *>(labels), ls_y, ls_x, ymap, xmap, K, aux, n_cols,
-                       reinterpret_cast<u64 *>(out), ld, W.counters);
+    assoc_walk<T, kVotes ? kAssocVotes : kAssocOverlap>(V, tile_order, tile_offsets, hdr_count, headers, wpool, labels, ls_y, ls_x, ymap,
+                                                        xmap, K, aux, n_cols, out, ld, ctr, SparseDev{});
 }
 
-template <bool kVotes>
+template <typename T>
+__global__ __launch_bounds__(kAssocThreads) void k_label_votes_sparse(
+    ViewDev V, const u32 *__restrict__ tile_order, const u32 *__restrict__ tile_offsets, const u32 *__restrict__ hdr_count,
+    const Header *__restrict__ headers, const WPair *__restrict__ wpool, const T *__restrict__ labels, int64_t ls_y, int64_t ls_x,
+    const int32_t *__restrict__ ymap, const int32_t *__restrict__ xmap, int K, const int32_t *__restrict__ remap, SparseDev SP,
+    Counters *__restrict__ ctr)
+{
+    assoc_walk<T, kAssocSparse>(V, tile_order, tile_offsets, hdr_count, headers, wpool, labels, ls_y, ls_x, ymap, xmap, K, remap, 0,
+                                nullptr, 0, ctr, SP);
+}
+
+template <typename T, int kMode>
+static void launch_assoc_t(const Ws &W, const ViewDev &V, const void *labels, int64_t ls_y, int64_t ls_x, const int32_t *ymap,
+                           const int32_t *xmap, int K, const int32_t *aux, int n_cols, int64_t *out, int64_t ld,
+                           const SparseDev &SP, hipStream_t s)
+{
+    const int n_tiles = V.tile_w * V.tile_h;
+    if (kMode == kAssocSparse)
+        hipLaunchKernelGGL((k_label_votes_sparse<T>), dim3(n_tiles), dim3(kAssocThreads), 0, s, V, W.tile_order, W.tile_offsets,
+                           W.hdr_count, W.headers, W.wpool, static_cast<const T *>(labels), ls_y, ls_x, ymap, xmap, K, aux, SP,
+                           W.counters);
+    else
+        hipLaunchKernelGGL((k_label_assoc<T, kMode == kAssocVotes>), dim3(n_tiles), dim3(kAssocThreads), 0, s, V, W.tile_order,
+                           W.tile_offsets, W.hdr_count, W.headers, W.wpool, static_cast<const T *>(labels), ls_y, ls_x, ymap, xmap, K,
+                           aux, n_cols, reinterpret_cast<u64 *>(out), ld, W.counters);
+}
+
+template <int kMode>
 static void launch_assoc(const Ws &W, const ViewDev &V, const void *labels, int label_type, int64_t ls_y, int64_t ls_x,
                          const int32_t *ymap, const int32_t *xmap, int K, const int32_t *aux, int n_cols, int64_t *out, int64_t ld,
-                         hipStream_t s)
+                         const SparseDev &SP, hipStream_t s)
 {
     if (label_type == GWBP_LABEL_U8)
-        launch_assoc_t<uint8_t, kVotes>(W, V, labels, ls_y, ls_x, ymap, xmap, K, aux, n_cols, out, ld, s);
+        launch_assoc_t<uint8_t, kMode>(W, V, labels, ls_y, ls_x, ymap, xmap, K, aux, n_cols, out, ld, SP, s);
     else if (label_type == GWBP_LABEL_I16)
-        launch_assoc_t<int16_t, kVotes>(W, V, labels, ls_y, ls_x, ymap, xmap, K, aux, n_cols, out, ld, s);
+        launch_assoc_t<int16_t, kMode>(W, V, labels, ls_y, ls_x, ymap, xmap, K, aux, n_cols, out, ld, SP, s);
     else
-        launch_assoc_t<int32_t, kVotes>(W, V, labels, ls_y, ls_x, ymap, xmap, K, aux, n_cols, out, ld, s);
+        launch_assoc_t<int32_t, kMode>(W, V, labels, ls_y, ls_x, ymap, xmap, K, aux, n_cols, out, ld, SP, s);
 }
 
 int launch_label_overlap(const Layout &L, const Ws &W, const ViewDev &V, const void *labels, int label_type, int64_t ls_y,
@@ -246,7 +333,7 @@ int launch_label_overlap(const Layout &L, const Ws &W, const ViewDev &V, const v
                          int64_t ldo, hipStream_t s)
 {
     (void)L;
-    launch_assoc<false>(W, V, labels, label_type, ls_y, ls_x, ymap, xmap, K, group, n_cols, O, ldo, s);
+    launch_assoc<kAssocOverlap>(W, V, labels, label_type, ls_y, ls_x, ymap, xmap, K, group, n_cols, O, ldo, SparseDev{}, s);
     return check_hip(hipGetLastError(), "label_overlap launch");
 }
 
@@ -255,8 +342,24 @@ int launch_label_votes(const Layout &L, const Ws &W, const ViewDev &V, const voi
                        int64_t ldv, hipStream_t s)
 {
     (void)L;
-    launch_assoc<true>(W, V, labels, label_type, ls_y, ls_x, ymap, xmap, K, remap, n_cols, Vt, ldv, s);
+    launch_assoc<kAssocVotes>(W, V, labels, label_type, ls_y, ls_x, ymap, xmap, K, remap, n_cols, Vt, ldv, SparseDev{}, s);
     return check_hip(hipGetLastError(), "label_votes launch");
+}
+
+int launch_label_votes_sparse(const Layout &L, const Ws &W, const ViewDev &V, const void *labels, int label_type, int64_t ls_y,
+                              int64_t ls_x, const int32_t *ymap, const int32_t *xmap, int K, const int32_t *remap, int slots,
+                              int32_t *keys, int64_t ld_keys, int64_t *vals, int64_t ld_vals, int64_t *spill, int64_t *total,
+                              hipStream_t s)
+{
+    (void)L;
+    SparseDev SP;
+    SP.keys = keys;
+    SP.vals = reinterpret_cast<u64 *>(vals);
+    SP.spill = reinterpret_cast<u64 *>(spill);
+    SP.total = reinterpret_cast<u64 *>(total);
+    SP.ldk = ld_keys, SP.ldv = ld_vals, SP.slots = slots;
+    launch_assoc<kAssocSparse>(W, V, labels, label_type, ls_y, ls_x, ymap, xmap, K, remap, 0, nullptr, 0, SP, s);
+    return check_hip(hipGetLastError(), "label_votes_sparse launch");
 }
 
 } // namespace gwbp

@@ -362,6 +362,42 @@ static int check_assoc_args(const char *fn, const void *labels, int32_t label_ty
     return check_label_map(labels, ls_y, ls_x);
 }
 
+// The slot lists of gwbp_label_votes_sparse over n rows: each array present and aligned, the row strides, and no two of the byte
+// ranges the kernel may write overlapping each other.
+static int check_sparse_lists(int64_t n, int32_t slots, const int32_t *keys, int64_t ld_keys, const int64_t *vals, int64_t ld_vals,
+                              const int64_t *spill, const int64_t *total)
+{
+    if (slots < 1 || slots > GWBP_SPARSE_MAX_SLOTS)
+        return set_error(GWBP_EINVAL, "slots must lie in [1, %d] (got %d)", GWBP_SPARSE_MAX_SLOTS, (int)slots);
+    if (ld_keys < slots)
+        return set_error(GWBP_EINVAL, "ld_keys %lld < slots %d", (long long)ld_keys, (int)slots);
+    if (ld_vals < slots)
+        return set_error(GWBP_EINVAL, "ld_vals %lld < slots %d", (long long)ld_vals, (int)slots);
+    if (!keys || (reinterpret_cast<uintptr_t>(keys) & 3))
+        return set_error(GWBP_EINVAL, "keys must be a non-null, 4-B aligned int32 array");
+    if (!vals || (reinterpret_cast<uintptr_t>(vals) & 7))
+        return set_error(GWBP_EINVAL, "vals must be a non-null, 8-B aligned int64 array");
+    if (!spill || (reinterpret_cast<uintptr_t>(spill) & 7))
+        return set_error(GWBP_EINVAL, "spill must be a non-null, 8-B aligned int64 array");
+    if (reinterpret_cast<uintptr_t>(total) & 7)
+        return set_error(GWBP_EINVAL, "total must be an 8-B aligned int64 array (or NULL)");
+    const uint64_t rows = n > 0 ? (uint64_t)n : 0u;
+    const uint64_t span = rows ? rows - 1u : 0u; // (a list of n rows ends `slots` elements into its last row)
+    struct Range {
+        const char *name;
+        uintptr_t lo;
+        uint64_t bytes;
+    } r[4] = {{"keys", reinterpret_cast<uintptr_t>(keys), rows ? (span * (uint64_t)ld_keys + (uint64_t)slots) * 4u : 0u},
+              {"vals", reinterpret_cast<uintptr_t>(vals), rows ? (span * (uint64_t)ld_vals + (uint64_t)slots) * 8u : 0u},
+              {"spill", reinterpret_cast<uintptr_t>(spill), rows * 8u},
+              {"total", reinterpret_cast<uintptr_t>(total), total ? rows * 8u : 0u}};
+    for (int i = 0; i < 4; ++i)
+        for (int j = i + 1; j < 4; ++j)
+            if (r[i].bytes && r[j].bytes && r[i].lo < r[j].lo + r[j].bytes && r[j].lo < r[i].lo + r[i].bytes)
+                return set_error(GWBP_EINVAL, "%s and %s overlap", r[i].name, r[j].name);
+    return GWBP_OK;
+}
+
 extern "C" {
 
 const char *gwbp_version(void)
@@ -847,6 +883,31 @@ int gwbp_label_votes(const gwbp_caps *caps, void *workspace, size_t workspace_by
                                "V", V, "ldv", ldv)))
         return rc;
     return launch_label_votes(B.L, B.W, B.V, labels, label_type, ls_y, ls_x, ymap, xmap, num_labels, remap, n_cols, V, ldv, B.s);
+}
+
+int gwbp_label_votes_sparse(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                            const void *labels, int32_t label_type, int64_t ls_y, int64_t ls_x, int32_t num_labels, const int32_t *ymap,
+                            const int32_t *xmap, const int32_t *remap, int32_t slots, int32_t *keys, int64_t ld_keys, int64_t *vals,
+                            int64_t ld_vals, int64_t *spill, int64_t *total, void *stream)
+{
+    Bound B;
+    int rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B);
+    if (rc)
+        return rc;
+    if ((rc = check_label_type(label_type)))
+        return rc;
+    if (num_labels <= 0)
+        return set_error(GWBP_EINVAL, "num_labels must be positive (got %d)", (int)num_labels);
+    if (!remap)
+        return set_error(GWBP_EINVAL, "null remap");
+    if ((rc = check_sparse_lists(B.L.n, slots, keys, ld_keys, vals, ld_vals, spill, total)))
+        return rc;
+    if ((rc = check_index_maps("gwbp_label_votes_sparse", ymap, xmap)))
+        return rc;
+    if ((rc = check_label_map(labels, ls_y, ls_x)))
+        return rc;
+    return launch_label_votes_sparse(B.L, B.W, B.V, labels, label_type, ls_y, ls_x, ymap, xmap, num_labels, remap, slots, keys, ld_keys,
+                                     vals, ld_vals, spill, total, B.s);
 }
 
 int gwbp_render(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,

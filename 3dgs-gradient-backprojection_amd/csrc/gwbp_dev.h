@@ -258,6 +258,11 @@ int launch_label_overlap(const Layout &L, const Ws &W, const ViewDev &V, const v
 int launch_label_votes(const Layout &L, const Ws &W, const ViewDev &V, const void *labels, int label_type, int64_t ls_y,
                        int64_t ls_x, const int32_t *ymap, const int32_t *xmap, int K, const int32_t *remap, int n_cols, int64_t *Vt,
                        int64_t ldv, hipStream_t s);
+// the votes into per-Gaussian slot lists: keys int32 [N, ld_keys] (-1 empty), vals int64 [N, ld_vals], spill, total (or NULL) [N]
+int launch_label_votes_sparse(const Layout &L, const Ws &W, const ViewDev &V, const void *labels, int label_type, int64_t ls_y,
+                              int64_t ls_x, const int32_t *ymap, const int32_t *xmap, int K, const int32_t *remap, int slots,
+                              int32_t *keys, int64_t ld_keys, int64_t *vals, int64_t ld_vals, int64_t *spill, int64_t *total,
+                              hipStream_t s);
 int launch_render(const Layout &L, const Ws &W, const ViewDev &V, const float *colors, int D, float *out,
                   hipStream_t s);
 int launch_render_px(const Ws &W, const ViewDev &V, const float *colors, int D, float *out, float *alphas,

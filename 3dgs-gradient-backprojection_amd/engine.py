@@ -724,6 +724,32 @@ class Engine:
         self._call("gwbp_label_votes", *self._args(), byref(view), ptr(labels), LABEL_TYPES[labels.dtype], c_int64(sy),
                    c_int64(sx), K, ptr(ymap), ptr(xmap), ptr(remap), n_cols, ptr(V), c_int64(V.stride(0)), self._stream())
 
+    def label_votes_sparse(self, view, labels, remap, sv, num_labels: int, upsample: Optional[str] = None):
+        """label_votes into per-Gaussian slot lists (gwbp_label_votes_sparse; sparse_votes.py): q(w) goes to the slot of row g whose
+        key is remap[labels[p]] -- the first empty slot takes the key for good -- or to sv.spill[g] when the row's S slots hold
+        other keys; with sv.total every non-zero q also counts in total[g], whatever its label.  Any remap entry >= 0 is a key:
+        there is no column count.  sv: a SparseVotes (new_sparse_votes) -- keys int32 [N, S] (-1 empty) and vals int64 [N, S] with
+        unit column stride and 1 <= S <= 32, spill int64 [N], total int64 [N] or None, none sharing memory; ADDED to.  Integer
+        sums: without spill a row holds exactly the dense row's non-zero entries on every run, in a slot order that may differ."""
+        keys, vals, spill, total = sv
+        if not torch.is_tensor(vals) or vals.dim() != 2 or not 1 <= vals.shape[1] <= _lib.SPARSE_MAX_SLOTS:
+            raise GwbpError(f"vals must be an int64 HIP tensor [{self.n}, S] with 1 <= S <= {_lib.SPARSE_MAX_SLOTS} slots")
+        labels, ymap, xmap, K, S = self._assoc_args("label_votes_sparse", view, labels, num_labels, upsample, remap, "remap",
+                                                    int(num_labels), vals, "vals", self.n)
+        if (not torch.is_tensor(keys) or keys.dtype != torch.int32 or not keys.is_cuda or tuple(keys.shape) != (self.n, S)
+                or (S > 1 and keys.stride(1) != 1) or keys.stride(0) < S):
+            raise GwbpError(f"keys must be an int32 HIP tensor [{self.n}, {S}] (the shape of vals) with unit column stride")
+        for t, name in ((spill, "spill"), (total, "total")):
+            if t is None and name == "total":
+                continue
+            if (not torch.is_tensor(t) or t.dtype != torch.int64 or not t.is_cuda or tuple(t.shape) != (self.n,)
+                    or not t.is_contiguous()):
+                raise GwbpError(f"{name} must be a contiguous int64 HIP tensor [{self.n}]" + (" or None" if name == "total" else ""))
+        sy, sx = labels.stride()
+        self._call("gwbp_label_votes_sparse", *self._args(), byref(view), ptr(labels), LABEL_TYPES[labels.dtype], c_int64(sy),
+                   c_int64(sx), K, ptr(ymap), ptr(xmap), ptr(remap), S, ptr(keys), c_int64(keys.stride(0)), ptr(vals),
+                   c_int64(vals.stride(0)), ptr(spill), ptr(total), self._stream())
+
     @staticmethod
     def mask_fast_path(dim: int) -> bool:
         """Table widths gwbp_scatter_mask_features takes (every other width materialises table[labels], see

@@ -433,6 +433,44 @@ GWBP_API int gwbp_label_votes(const gwbp_caps *caps, void *workspace, size_t wor
                               const int32_t *ymap, const int32_t *xmap, const int32_t *remap, int32_t n_cols, int64_t *V,
                               int64_t ldv, void *stream);
 
+/* ---- The votes into per-Gaussian SLOT LISTS: label lifts beyond a dense [N, K] -------------------------------------------
+ * gwbp_label_votes' walk and arithmetic with a fixed-capacity list of (key, integer sum) slots per Gaussian in place of the
+ * dense row: N * (12 * slots + 8) bytes (+ 8 * N with total) whatever the number of ids.
+ *
+ * The accumulator persists across views and belongs to the caller (device memory):
+ *     keys  int32 [N, ld_keys]   -1 = empty; the caller fills it with -1 before the first call
+ *     vals  int64 [N, ld_vals]   zero-initialised
+ *     spill int64 [N]            zero-initialised
+ *     total int64 [N]            zero-initialised; optional, NULL = none
+ * with 1 <= slots <= GWBP_SPARSE_MAX_SLOTS = 32 columns in use, unit column stride, and a row stride of its own for keys and for
+ * vals (ld_keys, ld_vals >= slots, in elements; columns beyond slots are never touched).
+ *
+ * The add: for every stored entry (g, p, w) of the view's weight store, c = remap[L(p)] and q as above.  Nothing is added when
+ * L(p) lies outside [0, num_labels), when c < 0, or when q == 0.  ANY c >= 0 is a valid key: there is no column count.
+ * Otherwise q goes to the slot of row g whose key is c; if no slot has that key, to the first empty slot in index order, which
+ * takes the key c for good; if there is neither, to spill[g].  With total, every entry with q != 0 also adds q to total[g],
+ * whatever its label: the exact integer denominator of a label field.
+ *
+ * Invariants (none depends on the order in which the lanes run):
+ *   1. a key is never evicted and never appears twice in a row; each slot holds the complete sum of its key over all calls so far;
+ *   2. spill[g] is the complete sum of the keys that found no slot; spill[g] > 0 exactly when row g has received more than
+ *      `slots` distinct keys with non-zero q: the set of overflowed rows is a function of the input alone;
+ *   3. the sum of a row's vals plus spill[g] equals the sum of the dense row gwbp_label_votes would have written;
+ *   4. a row without spill holds, as a set, exactly the non-zero entries of that dense row.  Only the slot order depends on the
+ *      run; the canonical order removes that: value descending, then key ascending, empties last;
+ *   5. in an overflowed row, WHICH `slots` keys hold slots depends on the order of the run: such a row is never exact.
+ *
+ * The caps, the workspace and the view are checked first; then, before any device call, GWBP_EINVAL for an unknown label_type,
+ * num_labels < 1, a NULL remap, slots outside [1, 32], a row stride below slots, a NULL or misaligned keys (4 B), vals or spill
+ * (8 B), a misaligned total, byte ranges of keys / vals / spill / total (over the caps' N rows) that overlap each other, exactly
+ * one of ymap / xmap NULL, a NULL labels or negative strides.  labels ... xmap, remap and the weight store: as gwbp_label_votes
+ * (without one: gwbp_stats.overflow bit 2, the lists untouched). */
+#define GWBP_SPARSE_MAX_SLOTS 32
+GWBP_API int gwbp_label_votes_sparse(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                                     const void *labels, int32_t label_type, int64_t ls_y, int64_t ls_x, int32_t num_labels,
+                                     const int32_t *ymap, const int32_t *xmap, const int32_t *remap, int32_t slots, int32_t *keys,
+                                     int64_t ld_keys, int64_t *vals, int64_t ld_vals, int64_t *spill, int64_t *total, void *stream);
+
 /* Bytes of gwbp_scatter_mask_features' slot store per (Gaussian, tile) intersection: four (int32 label, fp32 sum) slots. */
 #define GWBP_MASK_SLOT_BYTES 32
 

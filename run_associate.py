@@ -19,6 +19,10 @@ weight on Gaussians without a group, the group sizes), with --save-votes votes.p
 8 * N * max_groups bytes) and with --frames every view's render_label_argmax of the groups.  With --synthetic and no --masks: seeded
 instance maps with ids permuted per view (synthetic.make_instance_views).  The defaults --iou-min 0.2 and --min-mass 1.0 come from
 one synthetic scene and are not tuned on real segmenter output.
+
+--votes sparse [--slots S] [--on-overflow raise]: the evidence in S slots per Gaussian instead of the dense table.  association.pt
+then also carries 'keys' int32 [N, S], 'vals' int64 [N, S], 'spill' int64 [N] and 'certain' bool [N]; associate.json gains
+'sparse_votes': the overflowed rows, the spilled share, the histogram of slots in use.
 """
 import argparse
 import json
@@ -48,6 +52,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--pixel-weights", default=None, help="directory with <image name>.pt [H,W] per-pixel weight maps")
     ap.add_argument("--frames", action="store_true", help="render every view's argmax of the groups")
     ap.add_argument("--save-votes", action="store_true", help="also write votes.pt, int64 [N, max_groups]")
+    ap.add_argument("--votes", choices=["dense", "sparse"], default="dense",
+                    help="sparse: the evidence in --slots (group, sum) slots per Gaussian instead of a dense [N, max_groups] table: "
+                         "N * (12 * slots + 8) bytes whatever --max-groups, which may then be 65536")
+    ap.add_argument("--slots", type=int, default=8, help="slots per Gaussian of --votes sparse (1 .. 32)")
+    ap.add_argument("--on-overflow", choices=["warn", "raise"], default="warn",
+                    help="--votes sparse: a Gaussian that has received more than --slots distinct groups spills; warn once and go "
+                         "on (the later decisions may then differ from run to run), or stop at the first such view")
     ap.add_argument("--out", required=True, help="output directory")
     return ap
 
@@ -95,22 +106,32 @@ def main(argv=None) -> int:
     raster_kw = dict(camera_model=args.camera_model, rasterize_mode=args.rasterize_mode)
     assoc = gsbp_amd.associate_masks(*scene.gauss, scene.viewmats, scene.K, W, H, mask_fn, max_masks, max_groups=args.max_groups,
                                      iou_min=args.iou_min, min_mass=args.min_mass, pixel_weight_fn=weight_fn, upsample=upsample,
-                                     **raster_kw)
+                                     votes=args.votes, slots=args.slots, on_overflow=args.on_overflow, **raster_kw)
+    sparse = args.votes == "sparse"
 
     os.makedirs(os.path.join(args.out, "maps"), exist_ok=True)
-    torch.save({"maps": torch.stack(assoc.maps).cpu(), "groups": assoc.groups.cpu(), "n_groups": assoc.n_groups},
-               os.path.join(args.out, "association.pt"))
+    saved = {"maps": torch.stack(assoc.maps).cpu(), "groups": assoc.groups.cpu(), "n_groups": assoc.n_groups}
+    if sparse:  # the lists are small: they always go along (canonical order; keys -1 = empty)
+        saved.update(keys=assoc.votes.keys.cpu(), vals=assoc.votes.vals.cpu(), spill=assoc.votes.spill.cpu())
+        saved["certain"] = gsbp_amd.sparse_votes_groups(assoc.votes)[1].cpu()
+    torch.save(saved, os.path.join(args.out, "association.pt"))
     for v in range(n_views):
         torch.save(gsbp_amd.remap_masks(mask_fn(v), assoc.maps[v]).cpu(), os.path.join(args.out, "maps", scene.names[v] + ".pt"))
     sizes = torch.bincount(assoc.groups[assoc.groups >= 0].long(), minlength=max(assoc.n_groups, 1))[:max(assoc.n_groups, 0)]
     report = {"n": n, "views": n_views, "max_masks": max_masks, "max_groups": args.max_groups, "iou_min": args.iou_min,
               "min_mass": args.min_mass, "upsample": upsample, "pixel_weights": bool(args.pixel_weights), "n_groups": assoc.n_groups,
-              "grouped": int((assoc.groups >= 0).sum()), "group_sizes": sizes.cpu().tolist(), "per_view": assoc.views}
+              "grouped": int((assoc.groups >= 0).sum()), "group_sizes": sizes.cpu().tolist(), "per_view": assoc.views,
+              "votes": args.votes}
+    if sparse:
+        report["sparse_votes"] = gsbp_amd.sparse_votes_stats(assoc.votes)
     with open(os.path.join(args.out, "associate.json"), "w") as f:
         json.dump(report, f, indent=1)
     wrote = "association.pt, maps/, associate.json"
     if args.save_votes:
-        torch.save(assoc.votes.cpu(), os.path.join(args.out, "votes.pt"))
+        if sparse and assoc.n_groups > 4096:
+            raise SystemExit(f"--save-votes would densify {assoc.n_groups} groups: the lists are in association.pt")
+        dense = gsbp_amd.sparse_votes_dense(assoc.votes, max(assoc.n_groups, 1)) if sparse else assoc.votes
+        torch.save(dense.cpu(), os.path.join(args.out, "votes.pt"))
         wrote += ", votes.pt"
     if args.frames:
         k = max(assoc.n_groups, 1)

@@ -88,6 +88,16 @@ def build_parser() -> argparse.ArgumentParser:
     return ap
 
 
+def add_later_options(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
+    """The options that came after the set tests/golden/cli_options.json records for build_parser(); main() declares both."""
+    ap.add_argument("--sparse-slots", type=int, default=None, metavar="S",
+                    help="with --label-maps (or --synthetic) and --num-classes: keep S (1 .. 32) (class, share) slots per Gaussian "
+                         "instead of the dense [N, K] field (create_sparse_label_field: N * (12 S + 16) bytes whatever K): writes "
+                         "sparse_label_field.pt = {'ids': int32 [N, S] (-1 empty), 'fractions': float32 [N, S], 'spill_fraction': "
+                         "[N], 'total': int64 [N], 'num_classes', 'slots', 'stats'}, largest share first.  One process")
+    return ap
+
+
 def camera_warnings(cam, camera_model_arg):
     """One-line warnings about a COLMAP camera the projection does not model exactly: a fisheye model without --camera-model
     (it is projected as a pinhole), and fisheye distortion coefficients (gsplat's fisheye model ignores them too)."""
@@ -135,7 +145,7 @@ def load_pixel_weights(weight_dir: str, image_name: str, H: int, W: int) -> torc
 
 
 def main(argv=None):
-    ap = build_parser()
+    ap = add_later_options(build_parser())
     args = ap.parse_args(argv)
     labels_mode = bool(args.label_maps) or (bool(args.synthetic) and args.num_classes is not None)
     if labels_mode and (args.num_classes is None or args.num_classes < 1):
@@ -144,6 +154,11 @@ def main(argv=None):
         ap.error("--encoder applies to feature maps, not to --label-maps / --num-classes")
     if args.votes and not labels_mode:
         ap.error("--votes needs label maps: --label-maps DIR --num-classes K, or --synthetic CFG --num-classes K")
+    if args.sparse_slots is not None and (not labels_mode or args.votes or not 1 <= args.sparse_slots <= 32):
+        ap.error("--sparse-slots S (1 .. 32) goes with --label-maps DIR --num-classes K (or --synthetic CFG --num-classes K), "
+                 "without --votes")
+    if args.sparse_slots is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("--sparse-slots runs in one process (the slot lists of two ranks are not merged)")
     masks_mode = bool(args.mask_features)
     if masks_mode and (args.encoder or args.num_classes is not None):
         ap.error("--mask-features takes neither --encoder nor --num-classes")
@@ -284,6 +299,33 @@ def main(argv=None):
         keep = gsbp_amd.pruning.gradient_mask(splats, viewmats, K, W, H, **cam_kw)
         report_and_check(keep)
         means, quats, scales, opac = means[keep], quats[keep], scales[keep], opac[keep]
+
+    if labels_mode and args.sparse_slots is not None:
+        # the same prune step, then every Gaussian's non-zero class fractions in S slots (sparse_label_field.pt)
+        field = gsbp_amd.create_sparse_label_field(means, quats, scales, opac, viewmats, K, W, H, label_fn, args.num_classes,
+                                                   slots=args.sparse_slots, pixel_weight_fn=pixel_weight_fn,
+                                                   upsample=label_upsample, **cam_kw)
+        if args.prune_by_product and not args.no_prune:
+            keep = field.total > 0
+            report_and_check(keep)
+            field = gsbp_amd.SparseLabelField(*(t[keep] for t in field))
+        over = int((field.spill_fraction > 0).sum())
+        stats = {"overflow_rows": over, "slots_in_use": torch.bincount((field.ids >= 0).sum(dim=1),
+                                                                       minlength=args.sparse_slots + 1).tolist()}
+        if rank == 0:
+            os.makedirs(args.results_dir, exist_ok=True)
+            path = os.path.join(args.results_dir, "sparse_label_field.pt")
+            torch.save({**{k: t.cpu() for k, t in field._asdict().items()}, "num_classes": args.num_classes,
+                        "slots": args.sparse_slots, "stats": stats}, path)
+            print("saved", path, tuple(field.ids.shape), f"(of {n_all} Gaussians)", stats)
+            if over:
+                print(f"warning: {over} Gaussians saw more than {args.sparse_slots} classes; their spill_fraction says how much "
+                      "weight has no slot (raise --sparse-slots)", file=sys.stderr)
+            if keep is not None:
+                torch.save(keep.cpu(), os.path.join(args.results_dir, "prune_mask.pt"))
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        return
 
     if labels_mode:
         # the same prune step, then the [N_kept, K] class fractions of every Gaussian's blend weight (label_field.pt)
