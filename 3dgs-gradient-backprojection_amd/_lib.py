@@ -242,9 +242,25 @@ ARGTYPES = {
     "gwbp_decode_loss": [_I32, _I32, _I32, _I32, _P, _I64, _P, _I64, _P, _I32, _I64, _I64, C.POINTER(PixelWeights), _I32, _F, _P,
                          _I64, _P, _I64, _P, _P, _SZ, _P],
 }
+# The typed forms of the entry points that read a finished [N, D] FIELD (or, gwbp_finalize_typed, write one): the untyped function's
+# arguments with the field's element type (GWBP_MAP_*, MAP_TYPES' codes) behind the field pointer.  A table of their own: they take no
+# (caps, workspace, view), which is what the "_typed" names of ARGTYPES -- the typed scatters -- all start with.
+FIELD_ARGTYPES = {
+    "gwbp_finalize_typed": [_I64, _I32, _P, _P, _P, _I32, _P],
+    "gwbp_knn_search_typed": [_I64, _I32, _I32, _I32, _P, _I32, _I64, _P, _I64, _P, _P, _P],
+    "gwbp_neighbor_mean_typed": [_I64, _I64, _I32, _I32, _P, _P, _I32, _I64, _P, _I64, _P],
+    "gwbp_neighbor_similarity_typed": [_I64, _I32, _I32, _P, _P, _I32, _I64, _P, _P, _P],
+    "gwbp_neighbor_blend_typed": [_I64, _I64, _I32, _I32, _P, _P, _P, _I32, _I64, _P, _I64, _P, _P],
+    "gwbp_column_means_typed": [_I64, _I32, _P, _I32, _I64, _P, _P, _SZ, _P],
+    "gwbp_centered_gram_typed": [_I64, _I32, _P, _I32, _I64, _P, _P, _P, _SZ, _P],
+    "gwbp_pca_project_typed": [_I64, _I32, _I32, _P, _I32, _I64, _P, _P, _P, _P, _P],
+    "gwbp_kmeans_assign_typed": [_I64, _I32, _I32, _P, _I32, _I64, _P, _I64, _P, _P, _P, _P],
+    "gwbp_cluster_sums_typed": [_I64, _I32, _I32, _P, _I32, _I64, _P, _P, _P, _P, _P, _P, _SZ, _P],
+    "gwbp_prompt_scores_typed": [_I64, _I32, _I32, _I32, _P, _I32, _I64, _P, _I32, C.POINTER(C.c_float), _P, _P, _P],
+}
 LOSS_KINDS = {"l1": 0, "l2": 1}  # GWBP_LOSS_*
 # every symbol of include/gwbp.h: the two functions that return strings, then the int-returning ones declared above
-EXPORTS = ["gwbp_version", "gwbp_last_error_string", *ARGTYPES]
+EXPORTS = ["gwbp_version", "gwbp_last_error_string", *ARGTYPES, *FIELD_ARGTYPES]
 
 _lib: Optional[C.CDLL] = None
 _lib_path = LIB_PATH
@@ -276,7 +292,7 @@ def lib() -> C.CDLL:
             raise GwbpError(f"{path} is a PROFILE build ({L.gwbp_version().decode()}); it is only loaded through "
                             "use_library(path, allow_profile=True) (bench.py --lib, tools/stamp_scatter.py)")
         L.gwbp_last_error_string.restype = C.c_char_p
-        for name, argtypes in ARGTYPES.items():
+        for name, argtypes in {**ARGTYPES, **FIELD_ARGTYPES}.items():
             if path != LIB_PATH and not hasattr(L, name):
                 continue  # an older A/B build; calling the missing entry point still raises
             fn = getattr(L, name)

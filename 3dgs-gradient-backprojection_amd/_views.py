@@ -11,6 +11,7 @@ from typing import Callable
 import torch
 
 from ._lib import GwbpError, check, lib
+from .engine import MAP_TYPES as FIELD_TYPES  # dtype -> GWBP_MAP_*: a finished field has a feature map's element types
 from .engine import Engine
 from .rasterization import get_engine, run_front
 
@@ -43,6 +44,23 @@ def rows(t: torch.Tensor, name: str) -> torch.Tensor:
     if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
         t = t.contiguous()
     return t
+
+
+
+
+def field_rows(t: torch.Tensor, name: str):
+    """(tensor, GWBP_MAP_* code) of a finished [rows, D] FIELD as it is stored: float32, float16 or bfloat16, read by the *_typed entry
+    points without a float32 copy.  rows()'s shape and stride rules, in elements; a layout the kernels cannot read is made contiguous in
+    the tensor's own dtype."""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise GwbpError(f"{name} must be a HIP tensor (no CPU fallback exists for this path)")
+    if t.dim() != 2 or t.shape[1] < 1:
+        raise GwbpError(f"{name} must be [rows, D] with D >= 1, got {tuple(t.shape)}")
+    if t.dtype not in FIELD_TYPES:
+        raise GwbpError(f"{name} must be float32, float16 or bfloat16, got {t.dtype}")
+    if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    return t, FIELD_TYPES[t.dtype]
 
 
 def ld(t: torch.Tensor) -> int:

@@ -95,14 +95,16 @@ def gather_rows(rows: torch.Tensor, n: int) -> torch.Tensor:
     return full[:n]
 
 
-def finalize_reference(F: torch.Tensor, d: torch.Tensor) -> torch.Tensor:
+def finalize_reference(F: torch.Tensor, d: torch.Tensor, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """backproject.py:63,166-169 in plain torch (host logic used by the CPU/gloo tests; the GPU path calls
-    Engine.finalize -> gwbp_finalize)."""
+    Engine.finalize / Engine.finalize_typed -> gwbp_finalize_typed).  dtype (float32, float16 or bfloat16): the fp32 result rounded once, to nearest even."""
+    if dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise ValueError(f"dtype must be float32, float16 or bfloat16, got {dtype}")
     den = 1e-12 + d
     x = F / den[:, None]
     x = x / x.norm(dim=-1, keepdim=True)
     x[torch.isnan(x)] = 0
-    return x
+    return x if dtype == torch.float32 else x.to(dtype)
 
 
 # verdict of wide_kernel_selfcheck per (library path, device index): the check runs once per process and device
@@ -848,7 +850,8 @@ def create_feature_field(means, quats, scales, opacities, viewmats, K, width: in
                          encoder_split: Optional[bool] = None, camera_model: str = "pinhole",
                          rasterize_mode: str = "classic",
                          pixel_weight_fn: Optional[Callable[[int], torch.Tensor]] = None,
-                         render_colors: Optional[torch.Tensor] = None, sh_degree: Optional[int] = None):
+                         render_colors: Optional[torch.Tensor] = None, sh_degree: Optional[int] = None,
+                         out_dtype: torch.dtype = torch.float32):
     """Build the [N, dim_out] per-Gaussian feature field.
 
     means/quats/scales/opacities: post-activation Gaussians (backproject.py:55-57), device tensors.
@@ -918,7 +921,14 @@ def create_feature_field(means, quats, scales, opacities, viewmats, K, width: in
     the same workspace before their blend.  Not with view_fn.
     feature_fn may be called more than once per view: a workspace overflow restarts the job with larger capacities, and every
     view's map is asked for again.
+    out_dtype: torch.float32 (default), torch.float16 or torch.bfloat16 -- the type of the returned field.  The accumulators F and d
+    stay float32; the finalise writes its row block in out_dtype (the float32 value rounded once, to nearest even: bit for bit
+    field.to(out_dtype), without the float32 field) and the all-gather moves that.  A finalised row has unit norm, so both half
+    types hold it; prompt_scores, knn_search, fit_pca, fit_kmeans, neighbor_similarity, smooth_features and sample_field read
+    such a field as it is.
     """
+    if out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise ValueError(f"out_dtype must be torch.float32, torch.float16 or torch.bfloat16, got {out_dtype}")
     render = _render_of(render_colors, sh_degree, means.shape[0], means.device, view_fn)
     dist, rank, world = _dist()
     n = means.shape[0]
@@ -963,7 +973,10 @@ def create_feature_field(means, quats, scales, opacities, viewmats, K, width: in
     # (backproject.py:166-169 needs nothing but the row), and an all-gather of the finalised blocks only when the caller
     # wants the whole field on every rank (the reference writes one file, backproject.py:330).
     F_rows, d_rows, row0 = reduce_partials_sharded(F, d, F_store)
-    out_rows = eng.finalize(F_rows, d_rows) if eng is not None else finalize_reference(F_rows, d_rows)
+    if eng is None:
+        out_rows = finalize_reference(F_rows, d_rows, out_dtype)
+    else:
+        out_rows = eng.finalize(F_rows, d_rows) if out_dtype == torch.float32 else eng.finalize_typed(F_rows, d_rows, out_dtype)
     out = gather_rows(out_rows, n) if gather else out_rows
     if verbose and rank == 0:
         print("Time taken for feature backprojection", time.time() - t0)  # backproject.py:171
@@ -1232,7 +1245,8 @@ def create_mask_feature_field(means, quats, scales, opacities, viewmats, K, widt
                               gather: bool = True, return_partials: bool = False, camera_model: str = "pinhole",
                               rasterize_mode: str = "classic", engine: Optional[Engine] = None,
                               pixel_weight_fn: Optional[Callable[[int], torch.Tensor]] = None,
-                              render_colors: Optional[torch.Tensor] = None, sh_degree: Optional[int] = None):
+                              render_colors: Optional[torch.Tensor] = None, sh_degree: Optional[int] = None,
+                              out_dtype: torch.dtype = torch.float32):
     """Build the [N, dim] feature field from MASK-POOLED features: per view a segmenter's mask or instance map L_v and one
     embedding per mask, table E_v [M_v, dim] (SAM masks with a CLIP / LSeg vector each, superpixel-pooled DINO features).  The
     result equals create_feature_field(feature_fn=lambda v: E_v[L_v]) -- a zero row wherever a label lies outside [0, M_v), whose
@@ -1249,7 +1263,10 @@ def create_mask_feature_field(means, quats, scales, opacities, viewmats, K, widt
     pixel_weight_fn: as create_feature_field.  stats (return_partials) gains "mask_spilled": records with more than four
     distinct labels, whose rest was added with atomics (F is then no longer the same bit for bit from run to run).
     render_colors / sh_degree: as create_feature_field's -- mask_fn is then called as mask_fn(v, image) with the view's RGB
-    render, made by the front stage's blend; mask_fn may be called more than once per view (an overflow restarts the job)."""
+    render, made by the front stage's blend; mask_fn may be called more than once per view (an overflow restarts the job).
+    out_dtype: as create_feature_field's -- the finalised field in float32, float16 or bfloat16; the accumulators stay float32."""
+    if out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise ValueError(f"out_dtype must be torch.float32, torch.float16 or torch.bfloat16, got {out_dtype}")
     if upsample not in (None, "nearest"):
         raise ValueError(f"upsample must be None or 'nearest' for mask maps, got {upsample!r}")
     render = _render_of(render_colors, sh_degree, means.shape[0], means.device)
@@ -1282,7 +1299,7 @@ def create_mask_feature_field(means, quats, scales, opacities, viewmats, K, widt
         F.zero_()
         d.zero_()
     F_rows, d_rows, row0 = reduce_partials_sharded(F, d, F_store)
-    out_rows = eng.finalize(F_rows, d_rows)
+    out_rows = eng.finalize(F_rows, d_rows) if out_dtype == torch.float32 else eng.finalize_typed(F_rows, d_rows, out_dtype)
     out = gather_rows(out_rows, n) if gather else out_rows
     if return_partials:
         return out, F_rows, d, dict(stats, row0=row0)

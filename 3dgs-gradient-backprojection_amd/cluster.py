@@ -21,7 +21,7 @@ from typing import Callable, List, NamedTuple, Optional, Tuple, Union
 import torch
 
 from ._lib import GwbpError, check, lib, ptr
-from ._views import ld, rows, run
+from ._views import FIELD_TYPES, field_rows, ld, rows, run  # noqa: F401  (rows: geometry and small operands; callers of _assign)
 from .transfer import narrow_source_labels
 
 MAX_K = 1 << 20          # GWBP_CLUSTER_MAX_K
@@ -67,24 +67,26 @@ def _centroids(centroids, d: int, device) -> torch.Tensor:
 
 
 def _assign(x: torch.Tensor, c: torch.Tensor, bias: Optional[torch.Tensor]):
+    """x: checked field rows in their own dtype (field_rows); c, bias: float32."""
     n, d = x.shape
     labels = torch.empty(n, dtype=torch.int32, device=x.device)
     best = torch.empty(n, dtype=torch.float32, device=x.device)
-    run("gwbp_kmeans_assign", x.device, C.c_int64(n), int(c.shape[0]), d, ptr(x), C.c_int64(ld(x)), ptr(c), C.c_int64(ld(c)),
-        ptr(bias), ptr(labels), ptr(best))
+    run("gwbp_kmeans_assign_typed", x.device, C.c_int64(n), int(c.shape[0]), d, ptr(x), FIELD_TYPES[x.dtype], C.c_int64(ld(x)), ptr(c),
+        C.c_int64(ld(c)), ptr(bias), ptr(labels), ptr(best))
     return labels, best
 
 
 def _norms(x: torch.Tensor) -> torch.Tensor:
-    return torch.linalg.vector_norm(x, dim=1)  # one pass over the field, no [N, D] temporary
+    return torch.linalg.vector_norm(x, dim=1, dtype=torch.float32)  # one pass over the field (half: widened in the reduction), no [N, D] temporary
 
 
 def kmeans_assign(features: torch.Tensor, centroids: torch.Tensor, metric: str = "cosine"):
     """The nearest centroid of every row: (labels [N] int32, score [N] float32).  cosine: score = <x, c> (the largest inner
     product; give unit centroids), euclidean: score = <x, c> - |c|^2 / 2 (the smallest distance; |x - c|^2 = |x|^2 - 2 score).
     Exact fp32, knn_search's arithmetic; ties go to the lowest index; a row of zero norm and a row with a NaN get label -1.
-    features: as knn_search (any row stride >= D, read in place; float16 / bfloat16 through .float())."""
-    x = rows(features, "features")
+    features: as knn_search (any row stride >= D, read in place; float16 / bfloat16 as stored, widened exactly in the kernel: the
+    bits of the result on features.float(), without that copy)."""
+    x, _ = field_rows(features, "features")
     c = _centroids(centroids, x.shape[1], x.device)
     labels, best = _assign(x, c, centroid_bias(c, metric))
     labels[_norms(x) == 0] = -1
@@ -110,8 +112,8 @@ def _sums(x: torch.Tensor, lab: torch.Tensor, k: int, w: Optional[torch.Tensor])
     ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
     sums = torch.empty(k, d, dtype=torch.float64, device=dev)
     wsum = torch.empty(k, dtype=torch.float64, device=dev)
-    run("gwbp_cluster_sums", dev, C.c_int64(n), d, k, ptr(x), C.c_int64(ld(x)), ptr(w), ptr(order), ptr(start), ptr(sums),
-        ptr(wsum), ptr(ws), C.c_size_t(nbytes.value))
+    run("gwbp_cluster_sums_typed", dev, C.c_int64(n), d, k, ptr(x), FIELD_TYPES[x.dtype], C.c_int64(ld(x)), ptr(w), ptr(order), ptr(start),
+        ptr(sums), ptr(wsum), ptr(ws), C.c_size_t(nbytes.value))
     return sums, wsum, start[1:] - start[:-1]
 
 
@@ -119,8 +121,9 @@ def cluster_sums(features: torch.Tensor, labels: torch.Tensor, num_classes: int,
     """(sums [K, D] float64, wsum [K] float64, counts [K] int64): sums[k] = the sum of weights[g] * features[g] over the rows with
     labels[g] == k, wsum[k] the sum of their weights (weights None: 1), counts[k] their number.  Labels outside [0, K) take no
     part.  Every term is formed in float64 (exact); a class's members are cut into runs of 256 in row order, each run is summed in
-    ascending row order, the runs are added in ascending order: no atomics, the same bits on every run."""
-    x = rows(features, "features")
+    ascending row order, the runs are added in ascending order: no atomics, the same bits on every run.  float16 / bfloat16 features
+    are read as stored (widening is exact: the sums are those of features.float())."""
+    x, _ = field_rows(features, "features")
     k = int(num_classes)
     if not 1 <= k <= MAX_K:
         raise GwbpError(f"num_classes must be in [1, {MAX_K}], got {k}")
@@ -282,7 +285,7 @@ def init_kmeanspp(x: torch.Tensor, valid_rows: torch.Tensor, k: int, metric: str
 
 def _distance_term(metric: str) -> Callable:
     def distance(xc: torch.Tensor, centre: torch.Tensor) -> torch.Tensor:
-        c = _unit(centre) if metric == "cosine" else centre.contiguous()
+        c = _unit(centre) if metric == "cosine" else centre.float().contiguous()
         _, best = _assign(xc, c, centroid_bias(c, metric))
         if metric == "cosine":
             return 1.0 - best.double() / _norms(xc).double()
@@ -303,7 +306,7 @@ def fit_kmeans(features: torch.Tensor, k: int, metric: str = "cosine", iters: in
     give the same bits in every output.  weights: [N] non-negative row weights (e.g. the lift's d).  One host synchronisation per
     step."""
     _metric(metric)
-    x = rows(features, "features")
+    x, _ = field_rows(features, "features")  # float16 / bfloat16 fields stay as stored; centroids, sums and norms are float32 / 64
     n, d = x.shape
     k = int(k)
     if not 1 <= k <= MAX_K:
@@ -319,7 +322,7 @@ def fit_kmeans(features: torch.Tensor, k: int, metric: str = "cosine", iters: in
     elif init in ("sample", "kmeans++"):
         valid = torch.nonzero((norms > 0) & torch.isfinite(norms)).squeeze(1)
         pick = init_sample(valid, k, gen) if init == "sample" else init_kmeanspp(x, valid, k, metric, gen, _distance_term(metric), w)
-        c0 = _unit(x[pick]) if metric == "cosine" else x[pick].contiguous()
+        c0 = _unit(x[pick]) if metric == "cosine" else x[pick].float().contiguous()
     else:
         raise GwbpError(f"init must be 'kmeans++', 'sample' or a [k, D] tensor, got {init!r}")
 

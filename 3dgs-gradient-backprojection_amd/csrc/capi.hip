@@ -32,7 +32,7 @@ int check_hip(hipError_t e, const char *what)
 namespace {
 struct DevCache {
     int n_cu;
-    unsigned lds_mask;
+    unsigned long long lds_mask;
 };
 DevCache g_dev[64]; // benign races: every writer stores the same value
 DevCache *dev_cache()
@@ -65,12 +65,12 @@ int ensure_dynamic_lds(const void *func, int bytes, int slot)
     DevCache *c = dev_cache();
     if (!c)
         return set_error(GWBP_EINVAL, "cannot query the current device");
-    if (c->lds_mask & (1u << slot))
+    if (c->lds_mask & (1ull << slot))
         return GWBP_OK;
     const int rc = check_hip(hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, bytes),
                              "dynamic LDS attribute");
     if (rc == GWBP_OK)
-        c->lds_mask |= 1u << slot;
+        c->lds_mask |= 1ull << slot;
     return rc;
 }
 
@@ -297,6 +297,26 @@ static int check_blend_extras(const gwbp_pixel_weights *pixel_weights, const flo
 }
 
 static bool known_map_type(int32_t mt) { return mt == GWBP_MAP_F32 || mt == GWBP_MAP_F16 || mt == GWBP_MAP_BF16; }
+
+// The element type of a finished field handed to a *_typed entry point (or of gwbp_finalize_typed's output): checked before anything else.
+static int check_field_type(const char *what, int32_t field_type)
+{
+    if (!known_map_type(field_type))
+        return set_error(GWBP_EINVAL, "%s: unknown field_type %d (GWBP_MAP_F32, GWBP_MAP_F16 or GWBP_MAP_BF16)", what, (int)field_type);
+    return GWBP_OK;
+}
+// A field pointer that is not aligned to its element.  The fp32 case stays with each entry point's own check and message (fp32_off
+// is then part of that check's condition); a half field (2-B elements) is refused here.
+static bool fp32_off(const void *p, int32_t field_type)
+{
+    return field_type == GWBP_MAP_F32 && (reinterpret_cast<uintptr_t>(p) & 3) != 0;
+}
+static int check_half_alignment(const char *what, const char *name, const void *p, int32_t field_type)
+{
+    if (field_type != GWBP_MAP_F32 && (reinterpret_cast<uintptr_t>(p) & 1))
+        return set_error(GWBP_EINVAL, "%s: a half %s must be 2-B aligned", what, name);
+    return GWBP_OK;
+}
 
 static int check_label_type(int32_t label_type)
 {
@@ -983,16 +1003,31 @@ int gwbp_encode_map(const float *feats, int64_t fs_y, int64_t fs_x, int32_t heig
                              as_stream(stream));
 }
 
-int gwbp_finalize(int64_t N, int32_t D, const float *F, const float *d, float *out, void *stream)
+int gwbp_finalize_typed(int64_t N, int32_t D, const float *F, const float *d, void *out, int32_t out_type, void *stream)
 {
+    if (int rc = check_field_type("finalize", out_type))
+        return rc;
     if (N < 0 || D < 1 || (N > 0 && (!F || !d || !out)))
         return set_error(GWBP_EINVAL, "bad finalize arguments");
-    return launch_finalize(N, D, F, d, out, as_stream(stream));
+    if (fp32_off(out, out_type))
+        return set_error(GWBP_EINVAL, "finalize: out must be 4-B aligned");
+    if (int rc = check_half_alignment("finalize", "out", out, out_type))
+        return rc;
+    if (out_type != GWBP_MAP_F32 && out == static_cast<const void *>(F))
+        return set_error(GWBP_EINVAL, "finalize: a half out cannot alias F");
+    return launch_finalize(N, D, F, d, out, out_type, as_stream(stream));
 }
 
-int gwbp_knn_search(int64_t N, int32_t M, int32_t D, int32_t k, const float *Q, int64_t ldq, const float *S, int64_t lds_,
-                    int32_t *idx, float *score, void *stream)
+int gwbp_finalize(int64_t N, int32_t D, const float *F, const float *d, float *out, void *stream)
 {
+    return gwbp_finalize_typed(N, D, F, d, out, GWBP_MAP_F32, stream);
+}
+
+int gwbp_knn_search_typed(int64_t N, int32_t M, int32_t D, int32_t k, const void *Q, int32_t field_type, int64_t ldq, const float *S,
+                          int64_t lds_, int32_t *idx, float *score, void *stream)
+{
+    if (int rc = check_field_type("knn_search", field_type))
+        return rc;
     if (N < 0 || M < 1 || D < 1)
         return set_error(GWBP_EINVAL, "knn_search: bad sizes (N=%lld M=%d D=%d)", (long long)N, (int)M, (int)D);
     if (k < 1 || k > 32)
@@ -1003,9 +1038,17 @@ int gwbp_knn_search(int64_t N, int32_t M, int32_t D, int32_t k, const float *Q, 
         return set_error(GWBP_EINVAL, "knn_search: row strides (%lld, %lld) below D = %d", (long long)ldq, (long long)lds_, (int)D);
     if (!S || (N > 0 && (!Q || !idx || !score)))
         return set_error(GWBP_EINVAL, "knn_search: null Q, S, idx or score");
-    if ((reinterpret_cast<uintptr_t>(Q) & 3) || (reinterpret_cast<uintptr_t>(S) & 3))
+    if (fp32_off(Q, field_type) || (reinterpret_cast<uintptr_t>(S) & 3))
         return set_error(GWBP_EINVAL, "knn_search: Q and S must be 4-B aligned");
-    return launch_knn_search(N, M, D, k, Q, ldq, S, lds_, idx, score, as_stream(stream));
+    if (int rc = check_half_alignment("knn_search", "Q", Q, field_type))
+        return rc;
+    return launch_knn_search(N, M, D, k, Q, field_type, ldq, S, lds_, idx, score, as_stream(stream));
+}
+
+int gwbp_knn_search(int64_t N, int32_t M, int32_t D, int32_t k, const float *Q, int64_t ldq, const float *S, int64_t lds_,
+                    int32_t *idx, float *score, void *stream)
+{
+    return gwbp_knn_search_typed(N, M, D, k, Q, GWBP_MAP_F32, ldq, S, lds_, idx, score, stream);
 }
 
 int gwbp_knn_vote(int64_t N, int32_t M, int32_t k, const int32_t *idx, const int32_t *labels, int32_t num_classes,
@@ -1103,9 +1146,11 @@ int gwbp_spatial_knn(int64_t n, const float *sorted, const int32_t *cell_start, 
     return launch_spatial_knn(sorted, cell_start, lo, cell_size, dims, q, queries, ldq, order, k, idx, dist, as_stream(stream));
 }
 
-int gwbp_neighbor_mean(int64_t n, int64_t m, int32_t D, int32_t k, const int32_t *idx, const float *features, int64_t ldf,
-                       float *out, int64_t ldo, void *stream)
+int gwbp_neighbor_mean_typed(int64_t n, int64_t m, int32_t D, int32_t k, const int32_t *idx, const void *features, int32_t field_type,
+                             int64_t ldf, float *out, int64_t ldo, void *stream)
 {
+    if (int rc = check_field_type("neighbor_mean", field_type))
+        return rc;
     if (n < 0 || m < 1 || m > 0x7FFFFFFF || D < 1)
         return set_error(GWBP_EINVAL, "neighbor_mean: bad sizes (n=%lld m=%lld D=%d)", (long long)n, (long long)m, (int)D);
     if (k < 1 || k > 32)
@@ -1114,11 +1159,19 @@ int gwbp_neighbor_mean(int64_t n, int64_t m, int32_t D, int32_t k, const int32_t
         return set_error(GWBP_EINVAL, "neighbor_mean: row strides (%lld, %lld) below D = %d", (long long)ldf, (long long)ldo, (int)D);
     if (!features || (n > 0 && (!idx || !out)))
         return set_error(GWBP_EINVAL, "neighbor_mean: null idx, features or out");
-    if ((reinterpret_cast<uintptr_t>(features) & 3) || (reinterpret_cast<uintptr_t>(out) & 3))
+    if (fp32_off(features, field_type) || (reinterpret_cast<uintptr_t>(out) & 3))
         return set_error(GWBP_EINVAL, "neighbor_mean: features and out must be 4-B aligned");
-    if (features == out)
+    if (int rc = check_half_alignment("neighbor_mean", "features", features, field_type))
+        return rc;
+    if (features == static_cast<const void *>(out))
         return set_error(GWBP_EINVAL, "neighbor_mean: out must not be the features");
-    return launch_neighbor_mean(n, m, D, k, idx, features, ldf, out, ldo, as_stream(stream));
+    return launch_neighbor_mean(n, m, D, k, idx, features, field_type, ldf, out, ldo, as_stream(stream));
+}
+
+int gwbp_neighbor_mean(int64_t n, int64_t m, int32_t D, int32_t k, const int32_t *idx, const float *features, int64_t ldf,
+                       float *out, int64_t ldo, void *stream)
+{
+    return gwbp_neighbor_mean_typed(n, m, D, k, idx, features, GWBP_MAP_F32, ldf, out, ldo, stream);
 }
 
 // what the three walks of the radius components share: the built grid of n points, r2 and (when not null) aligned int32 arrays
@@ -1242,9 +1295,11 @@ static int check_neighbor_list(const char *what, int64_t n, int32_t k, const int
     return GWBP_OK;
 }
 
-int gwbp_neighbor_similarity(int64_t n, int32_t D, int32_t k, const int32_t *idx, const float *features, int64_t ldf, float *sim,
-                             int32_t *live, void *stream)
+int gwbp_neighbor_similarity_typed(int64_t n, int32_t D, int32_t k, const int32_t *idx, const void *features, int32_t field_type,
+                                   int64_t ldf, float *sim, int32_t *live, void *stream)
 {
+    if (int rc = check_field_type("neighbor_similarity", field_type))
+        return rc;
     if (int rc = check_neighbor_list("neighbor_similarity", n, k, idx, sim))
         return rc;
     if (D < 1 || D > GWBP_REGIONS_MAX_D)
@@ -1253,12 +1308,20 @@ int gwbp_neighbor_similarity(int64_t n, int32_t D, int32_t k, const int32_t *idx
         return set_error(GWBP_EINVAL, "neighbor_similarity: row stride %lld below D = %d", (long long)ldf, (int)D);
     if (!features || !live)
         return set_error(GWBP_EINVAL, "neighbor_similarity: null features or live");
-    if ((reinterpret_cast<uintptr_t>(features) & 3) || (reinterpret_cast<uintptr_t>(live) & 3))
+    if (fp32_off(features, field_type) || (reinterpret_cast<uintptr_t>(live) & 3))
         return set_error(GWBP_EINVAL, "neighbor_similarity: features and live must be 4-B aligned");
+    if (int rc = check_half_alignment("neighbor_similarity", "features", features, field_type))
+        return rc;
     const void *const written[] = {sim, live}, *const read[] = {idx, features};
     if (int rc = check_regions_distinct("neighbor_similarity", written, 2, read, 2))
         return rc;
-    return launch_neighbor_similarity(n, D, k, idx, features, ldf, sim, live, as_stream(stream));
+    return launch_neighbor_similarity(n, D, k, idx, features, field_type, ldf, sim, live, as_stream(stream));
+}
+
+int gwbp_neighbor_similarity(int64_t n, int32_t D, int32_t k, const int32_t *idx, const float *features, int64_t ldf, float *sim,
+                             int32_t *live, void *stream)
+{
+    return gwbp_neighbor_similarity_typed(n, D, k, idx, features, GWBP_MAP_F32, ldf, sim, live, stream);
 }
 
 int gwbp_edge_union(int64_t n, int32_t k, const int32_t *idx, const float *sim, const int32_t *live, const float *dist,
@@ -1347,9 +1410,11 @@ int gwbp_point_gaussians(int64_t n, const float *sorted, const int32_t *cell_sta
                                   n_contrib, visited, as_stream(stream));
 }
 
-int gwbp_neighbor_blend(int64_t q, int64_t m, int32_t D, int32_t k, const int32_t *idx, const float *w, const float *features,
-                        int64_t ldf, float *out, int64_t ldo, float *wsum, void *stream)
+int gwbp_neighbor_blend_typed(int64_t q, int64_t m, int32_t D, int32_t k, const int32_t *idx, const float *w, const void *features,
+                              int32_t field_type, int64_t ldf, float *out, int64_t ldo, float *wsum, void *stream)
 {
+    if (int rc = check_field_type("neighbor_blend", field_type))
+        return rc;
     if (int rc = check_weighted_list("neighbor_blend", q, m, k, idx, w))
         return rc;
     if (D < 1)
@@ -1358,13 +1423,21 @@ int gwbp_neighbor_blend(int64_t q, int64_t m, int32_t D, int32_t k, const int32_
         return set_error(GWBP_EINVAL, "neighbor_blend: row strides (%lld, %lld) below D = %d", (long long)ldf, (long long)ldo, (int)D);
     if (!features || (q > 0 && (!out || !wsum)))
         return set_error(GWBP_EINVAL, "neighbor_blend: null features, out or wsum");
-    if (misaligned(features, 3) || misaligned(out, 3) || misaligned(wsum, 3))
+    if (fp32_off(features, field_type) || misaligned(out, 3) || misaligned(wsum, 3))
         return set_error(GWBP_EINVAL, "neighbor_blend: features, out and wsum must be 4-B aligned");
+    if (int rc = check_half_alignment("neighbor_blend", "features", features, field_type))
+        return rc;
     const void *const written[] = {out, wsum}, *const read[] = {idx, w, features};
     if (q > 0)
         if (int rc = check_regions_distinct("neighbor_blend", written, 2, read, 3))
             return rc;
-    return launch_neighbor_blend(q, m, D, k, idx, w, features, ldf, out, ldo, wsum, as_stream(stream));
+    return launch_neighbor_blend(q, m, D, k, idx, w, features, field_type, ldf, out, ldo, wsum, as_stream(stream));
+}
+
+int gwbp_neighbor_blend(int64_t q, int64_t m, int32_t D, int32_t k, const int32_t *idx, const float *w, const float *features,
+                        int64_t ldf, float *out, int64_t ldo, float *wsum, void *stream)
+{
+    return gwbp_neighbor_blend_typed(q, m, D, k, idx, w, features, GWBP_MAP_F32, ldf, out, ldo, wsum, stream);
 }
 
 int gwbp_weighted_vote(int64_t q, int64_t m, int32_t k, const int32_t *idx, const float *w, const int32_t *labels, int32_t num_classes,
@@ -1386,9 +1459,11 @@ int gwbp_weighted_vote(int64_t q, int64_t m, int32_t k, const int32_t *idx, cons
 }
 
 // the checks the two passes of the fit share
-static int check_pca_rows(const char *what, int64_t N, int32_t D, const float *X, int64_t ldx, const void *workspace,
+static int check_pca_rows(const char *what, int64_t N, int32_t D, const void *X, int32_t field_type, int64_t ldx, const void *workspace,
                           size_t workspace_bytes)
 {
+    if (int rc = check_field_type(what, field_type))
+        return rc;
     if (N < 2 || D < 1 || D > GWBP_PCA_MAX_D)
         return set_error(GWBP_EINVAL, "%s: bad sizes (N=%lld D=%d): N >= 2, 1 <= D <= %d", what, (long long)N, (int)D,
                          GWBP_PCA_MAX_D);
@@ -1396,8 +1471,10 @@ static int check_pca_rows(const char *what, int64_t N, int32_t D, const float *X
         return set_error(GWBP_EINVAL, "%s: row stride %lld below D = %d", what, (long long)ldx, (int)D);
     if (!X || !workspace)
         return set_error(GWBP_EINVAL, "%s: null X or workspace", what);
-    if ((reinterpret_cast<uintptr_t>(X) & 3) || (reinterpret_cast<uintptr_t>(workspace) & 7))
+    if (fp32_off(X, field_type) || (reinterpret_cast<uintptr_t>(workspace) & 7))
         return set_error(GWBP_EINVAL, "%s: X must be 4-B aligned, the workspace 8-B", what);
+    if (int rc = check_half_alignment(what, "X", X, field_type))
+        return rc;
     const size_t need = pca_workspace_bytes(N, D);
     if (workspace_bytes < need)
         return set_error(GWBP_EWORKSPACE, "%s: workspace has %zu bytes, needs %zu", what, workspace_bytes, need);
@@ -1413,31 +1490,45 @@ int gwbp_pca_workspace_size(int64_t N, int32_t D, size_t *bytes)
     return GWBP_OK;
 }
 
-int gwbp_column_means(int64_t N, int32_t D, const float *X, int64_t ldx, float *mean_out, void *workspace, size_t workspace_bytes,
-                      void *stream)
+int gwbp_column_means_typed(int64_t N, int32_t D, const void *X, int32_t field_type, int64_t ldx, float *mean_out, void *workspace,
+                            size_t workspace_bytes, void *stream)
 {
-    const int rc = check_pca_rows("column_means", N, D, X, ldx, workspace, workspace_bytes);
+    const int rc = check_pca_rows("column_means", N, D, X, field_type, ldx, workspace, workspace_bytes);
     if (rc)
         return rc;
     if (!mean_out)
         return set_error(GWBP_EINVAL, "column_means: null mean_out");
-    return launch_column_means(N, D, X, ldx, mean_out, workspace, as_stream(stream));
+    return launch_column_means(N, D, X, field_type, ldx, mean_out, workspace, as_stream(stream));
+}
+
+int gwbp_column_means(int64_t N, int32_t D, const float *X, int64_t ldx, float *mean_out, void *workspace, size_t workspace_bytes,
+                      void *stream)
+{
+    return gwbp_column_means_typed(N, D, X, GWBP_MAP_F32, ldx, mean_out, workspace, workspace_bytes, stream);
+}
+
+int gwbp_centered_gram_typed(int64_t N, int32_t D, const void *X, int32_t field_type, int64_t ldx, const float *mean, double *gram_out,
+                             void *workspace, size_t workspace_bytes, void *stream)
+{
+    const int rc = check_pca_rows("centered_gram", N, D, X, field_type, ldx, workspace, workspace_bytes);
+    if (rc)
+        return rc;
+    if (!mean || !gram_out || (reinterpret_cast<uintptr_t>(gram_out) & 7))
+        return set_error(GWBP_EINVAL, "centered_gram: null mean or gram_out, or gram_out not 8-B aligned");
+    return launch_centered_gram(N, D, X, field_type, ldx, mean, gram_out, workspace, as_stream(stream));
 }
 
 int gwbp_centered_gram(int64_t N, int32_t D, const float *X, int64_t ldx, const float *mean, double *gram_out, void *workspace,
                        size_t workspace_bytes, void *stream)
 {
-    const int rc = check_pca_rows("centered_gram", N, D, X, ldx, workspace, workspace_bytes);
-    if (rc)
-        return rc;
-    if (!mean || !gram_out || (reinterpret_cast<uintptr_t>(gram_out) & 7))
-        return set_error(GWBP_EINVAL, "centered_gram: null mean or gram_out, or gram_out not 8-B aligned");
-    return launch_centered_gram(N, D, X, ldx, mean, gram_out, workspace, as_stream(stream));
+    return gwbp_centered_gram_typed(N, D, X, GWBP_MAP_F32, ldx, mean, gram_out, workspace, workspace_bytes, stream);
 }
 
-int gwbp_pca_project(int64_t N, int32_t D, int32_t k, const float *X, int64_t ldx, const float *mean, const float *components,
-                     float *Y, float *minmax_partials, void *stream)
+int gwbp_pca_project_typed(int64_t N, int32_t D, int32_t k, const void *X, int32_t field_type, int64_t ldx, const float *mean,
+                           const float *components, float *Y, float *minmax_partials, void *stream)
 {
+    if (int rc = check_field_type("pca_project", field_type))
+        return rc;
     if (N < 1 || D < 1 || D > GWBP_PCA_MAX_D)
         return set_error(GWBP_EINVAL, "pca_project: bad sizes (N=%lld D=%d): N >= 1, 1 <= D <= %d", (long long)N, (int)D,
                          GWBP_PCA_MAX_D);
@@ -1447,9 +1538,17 @@ int gwbp_pca_project(int64_t N, int32_t D, int32_t k, const float *X, int64_t ld
         return set_error(GWBP_EINVAL, "pca_project: row stride %lld below D = %d", (long long)ldx, (int)D);
     if (!X || !mean || !components || !Y || !minmax_partials)
         return set_error(GWBP_EINVAL, "pca_project: null X, mean, components, Y or minmax_partials");
-    if (reinterpret_cast<uintptr_t>(X) & 3)
+    if (fp32_off(X, field_type))
         return set_error(GWBP_EINVAL, "pca_project: X must be 4-B aligned");
-    return launch_pca_project(N, D, k, X, ldx, mean, components, Y, minmax_partials, as_stream(stream));
+    if (int rc = check_half_alignment("pca_project", "X", X, field_type))
+        return rc;
+    return launch_pca_project(N, D, k, X, field_type, ldx, mean, components, Y, minmax_partials, as_stream(stream));
+}
+
+int gwbp_pca_project(int64_t N, int32_t D, int32_t k, const float *X, int64_t ldx, const float *mean, const float *components,
+                     float *Y, float *minmax_partials, void *stream)
+{
+    return gwbp_pca_project_typed(N, D, k, X, GWBP_MAP_F32, ldx, mean, components, Y, minmax_partials, stream);
 }
 
 int gwbp_pca_colors(int64_t n, const float *Y, const float *lo_hi, float *colors, void *stream)
@@ -1471,23 +1570,25 @@ static int check_cluster_sizes(const char *what, int64_t N, int32_t K, int32_t D
     return GWBP_OK;
 }
 
-static int check_cluster_rows(const char *what, int64_t N, int32_t K, int32_t D, const float *X, int64_t ldx)
+static int check_cluster_rows(const char *what, int64_t N, int32_t K, int32_t D, const void *X, int32_t field_type, int64_t ldx)
 {
+    if (int rc = check_field_type(what, field_type))
+        return rc;
     if (int rc = check_cluster_sizes(what, N, K, D))
         return rc;
     if (ldx < D)
         return set_error(GWBP_EINVAL, "%s: row stride %lld of X below D = %d", what, (long long)ldx, (int)D);
     if (N > 0 && !X)
         return set_error(GWBP_EINVAL, "%s: null X", what);
-    if (reinterpret_cast<uintptr_t>(X) & 3)
+    if (fp32_off(X, field_type))
         return set_error(GWBP_EINVAL, "%s: X must be 4-B aligned", what);
-    return GWBP_OK;
+    return check_half_alignment(what, "X", X, field_type);
 }
 
-int gwbp_kmeans_assign(int64_t N, int32_t K, int32_t D, const float *X, int64_t ldx, const float *C, int64_t ldc, const float *b,
-                       int32_t *label, float *best, void *stream)
+int gwbp_kmeans_assign_typed(int64_t N, int32_t K, int32_t D, const void *X, int32_t field_type, int64_t ldx, const float *C, int64_t ldc,
+                             const float *b, int32_t *label, float *best, void *stream)
 {
-    if (int rc = check_cluster_rows("kmeans_assign", N, K, D, X, ldx))
+    if (int rc = check_cluster_rows("kmeans_assign", N, K, D, X, field_type, ldx))
         return rc;
     if (ldc < D)
         return set_error(GWBP_EINVAL, "kmeans_assign: row stride ldc = %lld of C below D = %d", (long long)ldc, (int)D);
@@ -1496,7 +1597,13 @@ int gwbp_kmeans_assign(int64_t N, int32_t K, int32_t D, const float *X, int64_t 
     if ((reinterpret_cast<uintptr_t>(C) & 3) || (reinterpret_cast<uintptr_t>(b) & 3) || (reinterpret_cast<uintptr_t>(label) & 3) ||
         (reinterpret_cast<uintptr_t>(best) & 3))
         return set_error(GWBP_EINVAL, "kmeans_assign: C, b, label and best must be 4-B aligned");
-    return launch_kmeans_assign(N, K, D, X, ldx, C, ldc, b, label, best, as_stream(stream));
+    return launch_kmeans_assign(N, K, D, X, field_type, ldx, C, ldc, b, label, best, as_stream(stream));
+}
+
+int gwbp_kmeans_assign(int64_t N, int32_t K, int32_t D, const float *X, int64_t ldx, const float *C, int64_t ldc, const float *b,
+                       int32_t *label, float *best, void *stream)
+{
+    return gwbp_kmeans_assign_typed(N, K, D, X, GWBP_MAP_F32, ldx, C, ldc, b, label, best, stream);
 }
 
 int gwbp_cluster_workspace_size(int64_t N, int32_t D, int32_t K, size_t *bytes)
@@ -1509,10 +1616,11 @@ int gwbp_cluster_workspace_size(int64_t N, int32_t D, int32_t K, size_t *bytes)
     return GWBP_OK;
 }
 
-int gwbp_cluster_sums(int64_t N, int32_t D, int32_t K, const float *X, int64_t ldx, const float *w, const int64_t *order,
-                      const int64_t *start, double *sums, double *wsum, void *workspace, size_t workspace_bytes, void *stream)
+int gwbp_cluster_sums_typed(int64_t N, int32_t D, int32_t K, const void *X, int32_t field_type, int64_t ldx, const float *w,
+                            const int64_t *order, const int64_t *start, double *sums, double *wsum, void *workspace,
+                            size_t workspace_bytes, void *stream)
 {
-    if (int rc = check_cluster_rows("cluster_sums", N, K, D, X, ldx))
+    if (int rc = check_cluster_rows("cluster_sums", N, K, D, X, field_type, ldx))
         return rc;
     if (!start || (N > 0 && !order))
         return set_error(GWBP_EINVAL, "cluster_sums: null start or order");
@@ -1526,11 +1634,17 @@ int gwbp_cluster_sums(int64_t N, int32_t D, int32_t K, const float *X, int64_t l
     const size_t need = cluster_workspace_bytes(N, D, K);
     if (workspace_bytes < need)
         return set_error(GWBP_EWORKSPACE, "cluster_sums: workspace has %zu bytes, needs %zu", workspace_bytes, need);
-    return launch_cluster_sums(N, D, K, X, ldx, w, order, start, sums, wsum, workspace, as_stream(stream));
+    return launch_cluster_sums(N, D, K, X, field_type, ldx, w, order, start, sums, wsum, workspace, as_stream(stream));
+}
+
+int gwbp_cluster_sums(int64_t N, int32_t D, int32_t K, const float *X, int64_t ldx, const float *w, const int64_t *order,
+                      const int64_t *start, double *sums, double *wsum, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return gwbp_cluster_sums_typed(N, D, K, X, GWBP_MAP_F32, ldx, w, order, start, sums, wsum, workspace, workspace_bytes, stream);
 }
 
 // The field as the two queries read it: D, the row stride and the pointer, checked once for both.
-static int check_field_rows(const char *what, int32_t D, const float *X, int64_t ldx)
+static int check_field_rows(const char *what, int32_t D, const void *X, int64_t ldx, int32_t field_type = GWBP_MAP_F32)
 {
     if (D < 1 || D > GWBP_PCA_MAX_D)
         return set_error(GWBP_EINVAL, "%s: D must be in [1, %d] (got %d)", what, GWBP_PCA_MAX_D, (int)D);
@@ -1538,21 +1652,24 @@ static int check_field_rows(const char *what, int32_t D, const float *X, int64_t
         return set_error(GWBP_EINVAL, "%s: row stride %lld below D = %d", what, (long long)ldx, (int)D);
     if (!X)
         return set_error(GWBP_EINVAL, "%s: null X", what);
-    if (reinterpret_cast<uintptr_t>(X) & 3)
+    if (fp32_off(X, field_type))
         return set_error(GWBP_EINVAL, "%s: X must be 4-B aligned", what);
-    return GWBP_OK;
+    return check_half_alignment(what, "X", X, field_type);
 }
 
-int gwbp_prompt_scores(int64_t N, int32_t D, int32_t P, int32_t n_pos, const float *X, int64_t ldx, const float *prompts,
-                       int32_t normalize, const float *threshold_host, uint8_t *mask, float *scores, void *stream)
+int gwbp_prompt_scores_typed(int64_t N, int32_t D, int32_t P, int32_t n_pos, const void *X, int32_t field_type, int64_t ldx,
+                             const float *prompts, int32_t normalize, const float *threshold_host, uint8_t *mask, float *scores,
+                             void *stream)
 {
+    if (int rc = check_field_type("prompt_scores", field_type))
+        return rc;
     if (N < 0)
         return set_error(GWBP_EINVAL, "prompt_scores: N must not be negative (got %lld)", (long long)N);
     if (P < 1 || P > GWBP_QUERY_MAX_P)
         return set_error(GWBP_EINVAL, "prompt_scores: P must be in [1, %d] (got %d)", GWBP_QUERY_MAX_P, (int)P);
     if (n_pos < 1 || n_pos > P)
         return set_error(GWBP_EINVAL, "prompt_scores: n_pos must be in [1, P = %d] (got %d)", (int)P, (int)n_pos);
-    const int rc = check_field_rows("prompt_scores", D, X, ldx);
+    const int rc = check_field_rows("prompt_scores", D, X, ldx, field_type);
     if (rc)
         return rc;
     if (!prompts || (reinterpret_cast<uintptr_t>(prompts) & 3))
@@ -1563,7 +1680,14 @@ int gwbp_prompt_scores(int64_t N, int32_t D, int32_t P, int32_t n_pos, const flo
         return set_error(GWBP_EINVAL, "prompt_scores: scores must be 4-B aligned");
     if (mask && n_pos == P && !threshold_host)
         return set_error(GWBP_EINVAL, "prompt_scores: a mask without negative prompts (n_pos == P) needs a threshold");
-    return launch_prompt_scores(N, D, P, n_pos, X, ldx, prompts, normalize != 0, threshold_host, mask, scores, as_stream(stream));
+    return launch_prompt_scores(N, D, P, n_pos, X, field_type, ldx, prompts, normalize != 0, threshold_host, mask, scores,
+                                as_stream(stream));
+}
+
+int gwbp_prompt_scores(int64_t N, int32_t D, int32_t P, int32_t n_pos, const float *X, int64_t ldx, const float *prompts,
+                       int32_t normalize, const float *threshold_host, uint8_t *mask, float *scores, void *stream)
+{
+    return gwbp_prompt_scores_typed(N, D, P, n_pos, X, GWBP_MAP_F32, ldx, prompts, normalize, threshold_host, mask, scores, stream);
 }
 
 int gwbp_probe_pixels(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host, int32_t M,

@@ -30,8 +30,10 @@ namespace gwbp {
 namespace {
 
 // ---- assignment -----------------------------------------------------------------------------------------------------------------
-template <bool VEC>
-__global__ __launch_bounds__(kKnnThreads) void k_kmeans_assign(int64_t N, int K, int D, const float *__restrict__ X, int64_t ldx,
+// MT (both kernels): the element type of X, widened as it is loaded; centroids, bias, weights and every output are what they were
+template <int MT, bool VEC>
+__global__ __launch_bounds__(kKnnThreads) void k_kmeans_assign(int64_t N, int K, int D,
+                                                               const typename MapElem<MT>::raw *__restrict__ X, int64_t ldx,
                                                                const float *__restrict__ C, int64_t ldc,
                                                                const float *__restrict__ bias, int32_t *__restrict__ label,
                                                                float *__restrict__ best)
@@ -45,7 +47,7 @@ __global__ __launch_bounds__(kKnnThreads) void k_kmeans_assign(int64_t N, int K,
     float bv = 0.f; // the running best of this thread's half of query q0 + q; bj < 0: none yet
     int bj = -1;
 
-    knn_score_tiles<VEC>(N, K, D, X, ldx, C, ldc, smem, [&](int tile, const float *sc) {
+    knn_score_tiles<MT, VEC>(N, K, D, X, ldx, C, ldc, smem, [&](int tile, const float *sc) {
         const int s0 = tile * kKnnS + half * (kKnnS / 2);
         const float *row = sc + q * kKnnScoreLd + half * (kKnnS / 2);
         for (int c = 0; c < kKnnS / 2; c += 4) { // uniform trip count; columns at or beyond K are masked
@@ -161,9 +163,9 @@ __global__ __launch_bounds__(kScanThreads) void k_cluster_runs(int64_t N, int K,
         run_start[K] = base; // (the last thread's clusters are the last ones: its base is the total)
 }
 
-template <bool VEC>
+template <int MT, bool VEC>
 __global__ __launch_bounds__(64 * kSumWaves) void k_cluster_sums(int64_t N, int D, int K, int64_t slots,
-                                                                  const float *__restrict__ X, int64_t ldx,
+                                                                  const typename MapElem<MT>::raw *__restrict__ X, int64_t ldx,
                                                                   const float *__restrict__ w, const int64_t *__restrict__ order,
                                                                   const int64_t *__restrict__ start,
                                                                   const int64_t *__restrict__ run_start,
@@ -191,22 +193,23 @@ __global__ __launch_bounds__(64 * kSumWaves) void k_cluster_sums(int64_t N, int 
     const int c = (int)blockIdx.y * kSumCols + 4 * lane;
     double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, aw = 0.0;
     for (int64_t p = p0; p < p1; p += kSumFlight) { // uniform trip count; positions at or beyond p1 are masked
-        float4 v[kSumFlight];
+        typename MapElem<MT>::raw4 v[kSumFlight]; // (the bits as loaded: eight rows in flight, widened where they are added)
         float wg[kSumFlight];
 #pragma unroll
         for (int i = 0; i < kSumFlight; ++i) {
             const int64_t g = p + i < p1 ? order[p + i] : -1;
             const bool on = g >= 0 && g < N;
-            v[i] = load4<VEC>(on ? X + g * ldx : nullptr, c, D);
+            v[i] = load4raw<MT, VEC>(on ? X + g * ldx : nullptr, c, D);
             wg[i] = on ? (w ? w[g] : 1.0f) : 0.0f;
         }
 #pragma unroll
         for (int i = 0; i < kSumFlight; ++i) { // ascending member order; a masked term adds +0
             const double wd = (double)wg[i];
-            a0 += wd * (double)v[i].x;
-            a1 += wd * (double)v[i].y;
-            a2 += wd * (double)v[i].z;
-            a3 += wd * (double)v[i].w;
+            const float4 x = widen4<MT>(v[i]);
+            a0 += wd * (double)x.x;
+            a1 += wd * (double)x.y;
+            a2 += wd * (double)x.z;
+            a3 += wd * (double)x.w;
             aw += wd;
         }
     }
@@ -248,32 +251,59 @@ __global__ __launch_bounds__(256) void k_cluster_reduce(int D, int64_t slots, co
 
 } // namespace
 
-int launch_kmeans_assign(int64_t N, int K, int D, const float *X, int64_t ldx, const float *C, int64_t ldc, const float *bias,
-                         int32_t *label, float *best, hipStream_t s)
+// slot: the first of the instantiation pair's two bits of ensure_dynamic_lds (vector, then element loads)
+template <int MT>
+static int launch_kmeans_assign_t(int slot, int64_t N, int K, int D, const void *Xv, int64_t ldx, const float *C, int64_t ldc,
+                                  const float *bias, int32_t *label, float *best, hipStream_t s)
 {
-    if (N == 0)
-        return GWBP_OK;
-    const bool vec = !(reinterpret_cast<uintptr_t>(X) & 15) && !(reinterpret_cast<uintptr_t>(C) & 15) && !(ldx & 3) && !(ldc & 3);
+    const typename MapElem<MT>::raw *X = static_cast<const typename MapElem<MT>::raw *>(Xv);
+    const bool vec = field_rows_vec(Xv, ldx, MT) && field_rows_vec(C, ldc, GWBP_MAP_F32);
     const int lds = 2 * kKnnStage * (int)sizeof(float);
-    const void *fn = vec ? reinterpret_cast<const void *>(k_kmeans_assign<true>) : reinterpret_cast<const void *>(k_kmeans_assign<false>);
-    const int rc = ensure_dynamic_lds(fn, lds, vec ? 29 : 30);
+    const void *fn =
+        vec ? reinterpret_cast<const void *>(k_kmeans_assign<MT, true>) : reinterpret_cast<const void *>(k_kmeans_assign<MT, false>);
+    const int rc = ensure_dynamic_lds(fn, lds, vec ? slot : slot + 1);
     if (rc)
         return rc;
     const int64_t grid = (N + kKnnQ - 1) / kKnnQ;
     if (grid > 0x7FFFFFFF)
         return set_error(GWBP_EINVAL, "kmeans_assign: N = %lld needs more than 2^31 - 1 workgroups", (long long)N);
     if (vec)
-        hipLaunchKernelGGL(k_kmeans_assign<true>, dim3((unsigned)grid), dim3(kKnnThreads), lds, s, N, K, D, X, ldx, C, ldc, bias,
+        hipLaunchKernelGGL((k_kmeans_assign<MT, true>), dim3((unsigned)grid), dim3(kKnnThreads), lds, s, N, K, D, X, ldx, C, ldc, bias,
                            label, best);
     else
-        hipLaunchKernelGGL(k_kmeans_assign<false>, dim3((unsigned)grid), dim3(kKnnThreads), lds, s, N, K, D, X, ldx, C, ldc, bias,
+        hipLaunchKernelGGL((k_kmeans_assign<MT, false>), dim3((unsigned)grid), dim3(kKnnThreads), lds, s, N, K, D, X, ldx, C, ldc, bias,
                            label, best);
     return check_hip(hipGetLastError(), "kmeans_assign launch");
 }
 
+int launch_kmeans_assign(int64_t N, int K, int D, const void *X, int mt, int64_t ldx, const float *C, int64_t ldc, const float *bias,
+                         int32_t *label, float *best, hipStream_t s)
+{
+    if (N == 0)
+        return GWBP_OK;
+    if (mt == GWBP_MAP_F16)
+        return launch_kmeans_assign_t<GWBP_MAP_F16>(36, N, K, D, X, ldx, C, ldc, bias, label, best, s);
+    if (mt == GWBP_MAP_BF16)
+        return launch_kmeans_assign_t<GWBP_MAP_BF16>(38, N, K, D, X, ldx, C, ldc, bias, label, best, s);
+    return launch_kmeans_assign_t<GWBP_MAP_F32>(29, N, K, D, X, ldx, C, ldc, bias, label, best, s);
+}
+
 size_t cluster_workspace_bytes(int64_t N, int D, int K) { return sum_ws(nullptr, N, D, K).bytes; }
 
-int launch_cluster_sums(int64_t N, int D, int K, const float *X, int64_t ldx, const float *w, const int64_t *order,
+template <int MT>
+static void launch_cluster_sums_t(dim3 g, hipStream_t s, int64_t N, int D, int K, int64_t slots, const void *Xv, int64_t ldx,
+                                  const float *w, const int64_t *order, const int64_t *start, const SumWs &W)
+{
+    const typename MapElem<MT>::raw *X = static_cast<const typename MapElem<MT>::raw *>(Xv);
+    if (field_rows_vec(Xv, ldx, MT))
+        hipLaunchKernelGGL((k_cluster_sums<MT, true>), g, dim3(64 * kSumWaves), 0, s, N, D, K, slots, X, ldx, w, order, start,
+                           W.run_start, W.partial, W.wpartial);
+    else
+        hipLaunchKernelGGL((k_cluster_sums<MT, false>), g, dim3(64 * kSumWaves), 0, s, N, D, K, slots, X, ldx, w, order, start,
+                           W.run_start, W.partial, W.wpartial);
+}
+
+int launch_cluster_sums(int64_t N, int D, int K, const void *X, int mt, int64_t ldx, const float *w, const int64_t *order,
                         const int64_t *start, double *sums, double *wsum, void *ws, hipStream_t s)
 {
     const SumWs W = sum_ws(ws, N, D, K);
@@ -284,14 +314,13 @@ int launch_cluster_sums(int64_t N, int D, int K, const float *X, int64_t ldx, co
         return set_error(GWBP_EINVAL, "cluster_sums: N = %lld, D = %d need too many workgroups", (long long)N, D);
     hipLaunchKernelGGL(k_cluster_runs, dim3(1), dim3(kScanThreads), 0, s, N, K, start, W.run_start);
     if (N > 0) {
-        const bool vec = !(reinterpret_cast<uintptr_t>(X) & 15) && !(ldx & 3);
         const dim3 g((unsigned)grid, (unsigned)col_blocks);
-        if (vec)
-            hipLaunchKernelGGL(k_cluster_sums<true>, g, dim3(64 * kSumWaves), 0, s, N, D, K, slots, X, ldx, w, order, start,
-                               W.run_start, W.partial, W.wpartial);
+        if (mt == GWBP_MAP_F16)
+            launch_cluster_sums_t<GWBP_MAP_F16>(g, s, N, D, K, slots, X, ldx, w, order, start, W);
+        else if (mt == GWBP_MAP_BF16)
+            launch_cluster_sums_t<GWBP_MAP_BF16>(g, s, N, D, K, slots, X, ldx, w, order, start, W);
         else
-            hipLaunchKernelGGL(k_cluster_sums<false>, g, dim3(64 * kSumWaves), 0, s, N, D, K, slots, X, ldx, w, order, start,
-                               W.run_start, W.partial, W.wpartial);
+            launch_cluster_sums_t<GWBP_MAP_F32>(g, s, N, D, K, slots, X, ldx, w, order, start, W);
     }
     hipLaunchKernelGGL(k_cluster_reduce, dim3((unsigned)K), dim3(256), 0, s, D, slots, W.run_start, W.partial, W.wpartial, sums,
                        wsum);

@@ -130,7 +130,7 @@ int bind_workspace(const gwbp_caps *caps, void *ws, size_t bytes, Layout *L, Ws 
 int set_error(int code, const char *fmt, ...);
 int check_hip(hipError_t e, const char *what);
 // Per-device facts, cached per device ORDINAL (a process may drive several GPUs): CU count of the current device, and
-// "this kernel's dynamic-LDS limit has been raised on the current device" (slot = one bit per kernel, < 32).
+// "this kernel's dynamic-LDS limit has been raised on the current device" (slot = one bit per kernel, < 64).
 int device_cus(int *n_cu);
 int ensure_dynamic_lds(const void *func, int bytes, int slot);
 // Profiling / ablation knobs (GWBP_ABLATE, GWBP_ABLATE_BLEND, GWBP_BLEND_LDS): an environment variable is read only by a
@@ -153,6 +153,14 @@ inline int sort_passes(int n_tiles)
     while ((1 << tile_bits) < n_tiles)
         ++tile_bits;
     return (tile_bits + 7) / 8;
+}
+
+// A finished field's element type (GWBP_MAP_*) on the host side of a launcher: the bytes of an element, and whether rows at p with a
+// stride of ld ELEMENTS may take load4t's vector path (16-B loads of fp32 rows, 8-B loads of half rows).
+inline size_t field_elem_bytes(int mt) { return mt == GWBP_MAP_F32 ? 4 : 2; }
+inline bool field_rows_vec(const void *p, int64_t ld, int mt)
+{
+    return !(reinterpret_cast<uintptr_t>(p) & (mt == GWBP_MAP_F32 ? 15u : 7u)) && !(ld & 3);
 }
 
 // stage launchers (one per .hip file)
@@ -287,9 +295,11 @@ int launch_decode_loss(int H, int W, int d, int D, const float *R, int64_t ldr, 
                        int64_t ldgc, double *table, void *ws, hipStream_t s);
 int launch_encode_map(const float *feats, int64_t fs_y, int64_t fs_x, int H, int W, int K, const float *enc, int n_out,
                       float *out, int workgroups, hipStream_t s);
-int launch_finalize(int64_t N, int D, const float *F, const float *d, float *out, hipStream_t s);
+// ot (GWBP_MAP_*): the element type of out; a half out is the fp32 result rounded once to nearest even
+int launch_finalize(int64_t N, int D, const float *F, const float *d, void *out, int ot, hipStream_t s);
 // inner-product k-NN search and the majority label of each row's neighbours (knn.hip)
-int launch_knn_search(int64_t N, int M, int D, int k, const float *Q, int64_t ldq, const float *S, int64_t lds_, int32_t *idx,
+// (here and below: mt (GWBP_MAP_*) is the element type of the FIELD operand in front of it, strides in elements; all else is fp32)
+int launch_knn_search(int64_t N, int M, int D, int k, const void *Q, int mt, int64_t ldq, const float *S, int64_t lds_, int32_t *idx,
                       float *score, hipStream_t s);
 int launch_knn_vote(int64_t N, int M, int k, const int32_t *idx, const int32_t *labels, int num_classes, int32_t *label_out,
                     int32_t *counts, int64_t ldc, hipStream_t s);
@@ -301,7 +311,7 @@ int launch_spatial_build(int64_t N, const float *P, int64_t ldp, const int32_t *
                          float *sorted, int32_t *cell_start, hipStream_t s);
 int launch_spatial_knn(const float *sorted, const int32_t *cell_start, const float *lo, float h, const int32_t *dims, int64_t Q,
                        const float *queries, int64_t ldq, const int64_t *order, int k, int32_t *idx, float *dist, hipStream_t s);
-int launch_neighbor_mean(int64_t N, int64_t M, int D, int k, const int32_t *idx, const float *F, int64_t ldf, float *out,
+int launch_neighbor_mean(int64_t N, int64_t M, int D, int k, const int32_t *idx, const void *F, int mt, int64_t ldf, float *out,
                          int64_t ldo, hipStream_t s);
 // radius components on the same grid (components.hip): neighbour counts within a radius, the union-find over the core points, the
 // border points' nearest core neighbour, and the roots.  group / query_group / attach / visited may be nullptr
@@ -317,8 +327,8 @@ int launch_components_flatten(int64_t N, const int32_t *count, int min_points, c
                               int32_t *status, hipStream_t s);
 // regions over a neighbour list by feature similarity (regions.hip): the cosine of every listed pair and each row's liveness, then
 // the union-find of union_find.h over the edges that pass; launch_components_flatten reads the roots.  dist / group may be nullptr
-int launch_neighbor_similarity(int64_t N, int D, int k, const int32_t *idx, const float *F, int64_t ldf, float *sim, int32_t *live,
-                               hipStream_t s);
+int launch_neighbor_similarity(int64_t N, int D, int k, const int32_t *idx, const void *F, int mt, int64_t ldf, float *sim,
+                               int32_t *live, hipStream_t s);
 int launch_edge_union(int64_t N, int k, const int32_t *idx, const float *sim, const int32_t *live, const float *dist,
                       const int32_t *group, float sim_min, float max_dist, int32_t *count, int32_t *parent, int32_t *status,
                       hipStream_t s);
@@ -329,29 +339,33 @@ int launch_gaussian_pack(int64_t N, const float *means, int64_t ldm, const float
 int launch_point_gaussians(const float *sorted, const int32_t *cell_start, const float *lo, float h, const int32_t *dims,
                            const float *pack, float r2, float alpha_min, int64_t Q, const float *queries, int64_t ldq,
                            const int64_t *order, int k, int32_t *idx, float *w, int32_t *n_contrib, int32_t *visited, hipStream_t s);
-int launch_neighbor_blend(int64_t Q, int64_t M, int D, int k, const int32_t *idx, const float *w, const float *F, int64_t ldf,
+int launch_neighbor_blend(int64_t Q, int64_t M, int D, int k, const int32_t *idx, const float *w, const void *F, int mt, int64_t ldf,
                           float *out, int64_t ldo, float *wsum, hipStream_t s);
 int launch_weighted_vote(int64_t Q, int64_t M, int k, const int32_t *idx, const float *w, const int32_t *labels, int K,
                          int32_t *out_label, float *out_share, hipStream_t s);
 // PCA of a finished field (pca.hip): column means, centred Gram, projection onto k <= 16 components, colours.  ws: the caller's
 // pca_workspace_bytes(N, D) bytes (the slices' partial sums), free again when the call's kernels have run.
 size_t pca_workspace_bytes(int64_t N, int D);
-int launch_column_means(int64_t N, int D, const float *X, int64_t ldx, float *mean, void *ws, hipStream_t s);
-int launch_centered_gram(int64_t N, int D, const float *X, int64_t ldx, const float *mean, double *gram, void *ws, hipStream_t s);
-int launch_pca_project(int64_t N, int D, int k, const float *X, int64_t ldx, const float *mean, const float *V, float *Y,
+int launch_column_means(int64_t N, int D, const void *X, int mt, int64_t ldx, float *mean, void *ws, hipStream_t s);
+int launch_centered_gram(int64_t N, int D, const void *X, int mt, int64_t ldx, const float *mean, double *gram, void *ws,
+                         hipStream_t s);
+int launch_pca_project(int64_t N, int D, int k, const void *X, int mt, int64_t ldx, const float *mean, const float *V, float *Y,
                        float *minmax, hipStream_t s);
 int launch_pca_colors(int64_t n, const float *Y, const float *lo_hi, float *colors, hipStream_t s);
 // clustering a finished field (cluster.hip): the k-means assignment (k_knn_search's score + a per-centroid bias, argmax only) and
 // the per-cluster float64 column sums of rows grouped by the caller.  ws: the caller's cluster_workspace_bytes(N, D, K) bytes.
-int launch_kmeans_assign(int64_t N, int K, int D, const float *X, int64_t ldx, const float *C, int64_t ldc, const float *bias,
+int launch_kmeans_assign(int64_t N, int K, int D, const void *X, int mt, int64_t ldx, const float *C, int64_t ldc, const float *bias,
                          int32_t *label, float *best, hipStream_t s);
 size_t cluster_workspace_bytes(int64_t N, int D, int K);
-int launch_cluster_sums(int64_t N, int D, int K, const float *X, int64_t ldx, const float *w, const int64_t *order,
+int launch_cluster_sums(int64_t N, int D, int K, const void *X, int mt, int64_t ldx, const float *w, const int64_t *order,
                         const int64_t *start, double *sums, double *wsum, void *ws, hipStream_t s);
 // questions asked of a finished field (query.hip): prompt scores + 3-D mask in one pass over X; the field rendered at M pixels
 // of a projected and sorted view.  threshold: host pointer or nullptr.
-int launch_prompt_scores(int64_t N, int D, int P, int n_pos, const float *X, int64_t ldx, const float *prompts, int normalize,
+int launch_prompt_scores(int64_t N, int D, int P, int n_pos, const void *X, int mt, int64_t ldx, const float *prompts, int normalize,
                          const float *threshold, uint8_t *mask, float *scores, hipStream_t s);
+// the fp16 / bf16 instantiations of k_prompt_scores (query_half.hip); the caller checks the launch
+void launch_prompt_scores_half(unsigned grid, hipStream_t s, int64_t N, int D, int P, int n_pos, const void *X, int mt, int64_t ldx,
+                               const float *prompts, int normalize, int use_thr, float thr, uint8_t *mask, float *scores);
 int launch_probe_pixels(const Ws &W, const ViewDev &V, int M, const int32_t *xy, const float *X, int64_t ldx, int D, float *out,
                         float *depth, float *alpha, hipStream_t s);
 int launch_dump_pairs(const Layout &L, const Ws &W, const ViewDev &V, int64_t cap, int32_t *gid, int32_t *pix,
@@ -489,6 +503,65 @@ __device__ __forceinline__ float4 load4(const float *__restrict__ p, int c, int 
     if (c + 3 < D)
         v.w = p[c + 3];
     return v;
+}
+
+// The same four columns of a row of a finished FIELD whose elements have type MT (GWBP_MAP_*), zero beyond D, no load for a null
+// row, in two steps so that a kernel can keep loads in flight: load4raw lands the BITS (MapElem<MT>::raw4: a float4, or the four
+// packed halves in a uint2; zero bits are +0 in every type) and widen4 turns them into four fp32 values (exact) where they are
+// used -- a conversion next to the load would make the wave wait for the load there.  VEC, half rows: ONE 8-B load -- the row address
+// is 8-B aligned, the row stride a multiple of 4 elements and c a multiple of 4; otherwise 2-B element loads, packed.  For
+// GWBP_MAP_F32 load4raw IS load4 and widen4 the identity: a kernel's fp32 instantiation compiles to what it was before it had a
+// typed operand.  load4t is both at once, for a value used where it is loaded.
+template <int MT, bool VEC>
+__device__ __forceinline__ typename MapElem<MT>::raw4 load4raw(const void *__restrict__ row, int c, int D)
+{
+    if constexpr (MT == GWBP_MAP_F32) {
+        return load4<VEC>(static_cast<const float *>(row), c, D);
+    } else {
+        const unsigned short *p = static_cast<const unsigned short *>(row);
+        if (!p)
+            return make_uint2(0u, 0u);
+        if (VEC && c + 4 <= D)
+            return *reinterpret_cast<const uint2 *>(p + c);
+        u32 e0 = 0u, e1 = 0u, e2 = 0u, e3 = 0u;
+        if (c < D)
+            e0 = p[c];
+        if (c + 1 < D)
+            e1 = p[c + 1];
+        if (c + 2 < D)
+            e2 = p[c + 2];
+        if (c + 3 < D)
+            e3 = p[c + 3];
+        return make_uint2(e0 | (e1 << 16), e2 | (e3 << 16));
+    }
+}
+template <int MT>
+__device__ __forceinline__ float4 widen4(typename MapElem<MT>::raw4 r)
+{
+    return MapElem<MT>::cvt4(r);
+}
+template <int MT, bool VEC>
+__device__ __forceinline__ float4 load4t(const void *__restrict__ row, int c, int D)
+{
+    return widen4<MT>(load4raw<MT, VEC>(row, c, D));
+}
+
+// One fp32 value rounded ONCE, to nearest even, to the element type OT of a typed output (k_finalize): torch's x.to(dtype) bit for
+// bit.  bf16 in integer arithmetic on the fp32 bits (a NaN becomes the quiet NaN 0x7FC0, an infinity stays one, a carry out of the
+// mantissa is the correct rounding up to the next binade or to infinity); fp16 is the compiler's conversion, subnormal results kept.
+template <int OT>
+__device__ __forceinline__ typename MapElem<OT>::raw narrow(float x)
+{
+    if constexpr (OT == GWBP_MAP_F32) {
+        return x;
+    } else if constexpr (OT == GWBP_MAP_F16) {
+        return __builtin_bit_cast(unsigned short, (_Float16)x);
+    } else {
+        const u32 b = __float_as_uint(x);
+        if ((b & 0x7FFFFFFFu) > 0x7F800000u)
+            return (unsigned short)0x7FC0u;
+        return (unsigned short)((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16);
+    }
 }
 
 __device__ __forceinline__ u32 uniform(u32 v) { return (u32)__builtin_amdgcn_readfirstlane((int)v); }

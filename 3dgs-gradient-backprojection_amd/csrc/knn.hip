@@ -31,9 +31,10 @@ namespace {
 
 constexpr int kKnnMaxK = 32;
 
-template <bool VEC>
-__global__ __launch_bounds__(kKnnThreads) void k_knn_search(int64_t N, int M, int D, int k, const float *__restrict__ Q,
-                                                            int64_t ldq, const float *__restrict__ S, int64_t lds_,
+template <int QT, bool VEC>
+__global__ __launch_bounds__(kKnnThreads) void k_knn_search(int64_t N, int M, int D, int k,
+                                                            const typename MapElem<QT>::raw *__restrict__ Q, int64_t ldq,
+                                                            const float *__restrict__ S, int64_t lds_,
                                                             int32_t *__restrict__ idx, float *__restrict__ score)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -50,7 +51,7 @@ __global__ __launch_bounds__(kKnnThreads) void k_knn_search(int64_t N, int M, in
         for (int j = 0; j < k; ++j)
             list[j * kKnnQ + tid] = 0; // below every candidate: key 0 with index 0xFFFFFFFF
 
-    knn_score_tiles<VEC>(N, M, D, Q, ldq, S, lds_, smem, [&](int tile, const float *sc) {
+    knn_score_tiles<QT, VEC>(N, M, D, Q, ldq, S, lds_, smem, [&](int tile, const float *sc) {
         if (tid < kKnnQ) {
             const u32 s0 = (u32)tile * kKnnS;
             const float *row = sc + tid * kKnnScoreLd;
@@ -154,16 +155,17 @@ __global__ __launch_bounds__(256) void k_knn_vote(int64_t N, int M, int k, const
 
 } // namespace
 
-int launch_knn_search(int64_t N, int M, int D, int k, const float *Q, int64_t ldq, const float *S, int64_t lds_, int32_t *idx,
-                      float *score, hipStream_t s)
+// slot: the first of the instantiation pair's two bits of ensure_dynamic_lds (vector, then element loads)
+template <int QT>
+static int launch_knn_search_t(int slot, int64_t N, int M, int D, int k, const void *Qv, int64_t ldq, const float *S, int64_t lds_,
+                               int32_t *idx, float *score, hipStream_t s)
 {
-    if (N == 0)
-        return GWBP_OK;
-    const bool vec = !(reinterpret_cast<uintptr_t>(Q) & 15) && !(reinterpret_cast<uintptr_t>(S) & 15) && !(ldq & 3) && !(lds_ & 3);
+    const typename MapElem<QT>::raw *Q = static_cast<const typename MapElem<QT>::raw *>(Qv);
+    const bool vec = field_rows_vec(Qv, ldq, QT) && field_rows_vec(S, lds_, GWBP_MAP_F32);
     // always the largest request (k = 32): ensure_dynamic_lds remembers "raised" per (device, slot), not the size
     const int lds_max = 2 * kKnnStage * (int)sizeof(float) + kKnnMaxK * kKnnQ * (int)sizeof(u64);
-    const void *fn = vec ? reinterpret_cast<const void *>(k_knn_search<true>) : reinterpret_cast<const void *>(k_knn_search<false>);
-    const int rc = ensure_dynamic_lds(fn, lds_max, vec ? 24 : 25);
+    const void *fn = vec ? reinterpret_cast<const void *>(k_knn_search<QT, true>) : reinterpret_cast<const void *>(k_knn_search<QT, false>);
+    const int rc = ensure_dynamic_lds(fn, lds_max, vec ? slot : slot + 1);
     if (rc)
         return rc;
     const size_t lds = 2 * kKnnStage * sizeof(float) + (size_t)k * kKnnQ * sizeof(u64);
@@ -171,12 +173,24 @@ int launch_knn_search(int64_t N, int M, int D, int k, const float *Q, int64_t ld
     if (grid > 0x7FFFFFFF)
         return set_error(GWBP_EINVAL, "knn_search: N = %lld needs more than 2^31 - 1 workgroups", (long long)N);
     if (vec)
-        hipLaunchKernelGGL(k_knn_search<true>, dim3((unsigned)grid), dim3(kKnnThreads), lds, s, N, M, D, k, Q, ldq, S, lds_, idx,
+        hipLaunchKernelGGL((k_knn_search<QT, true>), dim3((unsigned)grid), dim3(kKnnThreads), lds, s, N, M, D, k, Q, ldq, S, lds_, idx,
                            score);
     else
-        hipLaunchKernelGGL(k_knn_search<false>, dim3((unsigned)grid), dim3(kKnnThreads), lds, s, N, M, D, k, Q, ldq, S, lds_, idx,
+        hipLaunchKernelGGL((k_knn_search<QT, false>), dim3((unsigned)grid), dim3(kKnnThreads), lds, s, N, M, D, k, Q, ldq, S, lds_, idx,
                            score);
     return check_hip(hipGetLastError(), "knn_search launch");
+}
+
+int launch_knn_search(int64_t N, int M, int D, int k, const void *Q, int mt, int64_t ldq, const float *S, int64_t lds_, int32_t *idx,
+                      float *score, hipStream_t s)
+{
+    if (N == 0)
+        return GWBP_OK;
+    if (mt == GWBP_MAP_F16)
+        return launch_knn_search_t<GWBP_MAP_F16>(32, N, M, D, k, Q, ldq, S, lds_, idx, score, s);
+    if (mt == GWBP_MAP_BF16)
+        return launch_knn_search_t<GWBP_MAP_BF16>(34, N, M, D, k, Q, ldq, S, lds_, idx, score, s);
+    return launch_knn_search_t<GWBP_MAP_F32>(24, N, M, D, k, Q, ldq, S, lds_, idx, score, s);
 }
 
 int launch_knn_vote(int64_t N, int M, int k, const int32_t *idx, const int32_t *labels, int num_classes, int32_t *label_out,

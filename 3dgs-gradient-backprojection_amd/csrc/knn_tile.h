@@ -43,9 +43,10 @@ __device__ __forceinline__ float key_score(u32 key)
 // Runs the workgroup's 128 queries (rows blockIdx.x * 128 ... of Q) against every tile of S.  smem: 2 * kKnnStage floats, 16-B
 // aligned.  select(tile, sc) is called by all 256 threads once per tile, between two barriers, with sc[q * kKnnScoreLd + s] = the
 // score of query q of the workgroup against source tile * 128 + s (rows beyond N and sources beyond M hold scores of zero rows:
-// the selection masks them).
-template <bool VEC, class Select>
-__device__ __forceinline__ void knn_score_tiles(int64_t N, int M, int D, const float *__restrict__ Q, int64_t ldq,
+// the selection masks them).  QT: the element type of Q, the field operand (a half row is widened as it is loaded, so the staged
+// values and every chain are those of the fp32 tile on the widened rows); S is fp32.  VEC: both operands take their vector loads.
+template <int QT, bool VEC, class Select>
+__device__ __forceinline__ void knn_score_tiles(int64_t N, int M, int D, const typename MapElem<QT>::raw *__restrict__ Q, int64_t ldq,
                                                 const float *__restrict__ S, int64_t lds_, float *smem, Select select)
 {
     float *stage = smem; // [2][kKnnQ + kKnnS][kKnnLd]; the score tile lies over it
@@ -57,7 +58,7 @@ __device__ __forceinline__ void knn_score_tiles(int64_t N, int M, int D, const f
 
     // staging role: float4 column c4 of rows r0 + 32 i (i < 4) of the query block and of the source tile
     const int c4 = (tid & 7) * 4, r0 = tid >> 3;
-    const float *qrow[4];
+    const typename MapElem<QT>::raw *qrow[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int64_t g = q0 + r0 + 32 * i;
@@ -68,12 +69,13 @@ __device__ __forceinline__ void knn_score_tiles(int64_t N, int M, int D, const f
     const int n_tile = (M + kKnnS - 1) / kKnnS;
     const int64_t n_it = (int64_t)n_tile * n_chunk;
 
-    float4 pq[4], ps[4];
+    typename MapElem<QT>::raw4 pq[4]; // (the bits as loaded: widened where the staging writes them)
+    float4 ps[4];
     auto prefetch = [&](int tile, int chunk) {
         const int c = chunk * kKnnKC + c4;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            pq[i] = load4<VEC>(qrow[i], c, D);
+            pq[i] = load4raw<QT, VEC>(qrow[i], c, D);
             const u32 j = (u32)tile * kKnnS + r0 + 32 * i; // (M < 2^31: no wrap)
             ps[i] = load4<VEC>(j < (u32)M ? S + (int64_t)j * lds_ : nullptr, c, D);
         }
@@ -93,7 +95,7 @@ __device__ __forceinline__ void knn_score_tiles(int64_t N, int M, int D, const f
         float *buf = stage + (it & 1) * kKnnStage;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            *reinterpret_cast<float4 *>(buf + (r0 + 32 * i) * kKnnLd + c4) = pq[i];
+            *reinterpret_cast<float4 *>(buf + (r0 + 32 * i) * kKnnLd + c4) = widen4<QT>(pq[i]);
             *reinterpret_cast<float4 *>(buf + (kKnnQ + r0 + 32 * i) * kKnnLd + c4) = ps[i];
         }
         __syncthreads();

@@ -48,7 +48,10 @@ MeanPlan mean_plan(int64_t N)
     return {(int)((N + rows - 1) / rows), rows};
 }
 
-__global__ __launch_bounds__(kMeanCols *kMeanRowLanes) void k_column_sums(int64_t N, int D, const float *__restrict__ X,
+// MT (the three passes over X): the element type of X, widened as it is loaded (exact); everything else is what it was
+template <int MT>
+__global__ __launch_bounds__(kMeanCols *kMeanRowLanes) void k_column_sums(int64_t N, int D,
+                                                                          const typename MapElem<MT>::raw *__restrict__ X,
                                                                           int64_t ldx, int64_t rows_per_slice,
                                                                           double *__restrict__ partial)
 {
@@ -58,20 +61,21 @@ __global__ __launch_bounds__(kMeanCols *kMeanRowLanes) void k_column_sums(int64_
     const bool on = c < D;
     const int64_t g0 = (int64_t)blockIdx.y * rows_per_slice;
     const int64_t g1 = g0 + rows_per_slice < N ? g0 + rows_per_slice : N;
-    const float *col = X + (on ? c : 0);
+    typedef MapElem<MT> E;
+    const typename E::raw *col = X + (on ? c : 0);
     double acc = 0.0;
     int64_t g = g0 + rl;
     for (; g + 3 * kMeanRowLanes < g1; g += 4 * kMeanRowLanes) { // four rows in flight per thread
         float v[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-            v[i] = on ? col[(g + i * kMeanRowLanes) * ldx] : 0.f;
+            v[i] = on ? E::cvt(col[(g + i * kMeanRowLanes) * ldx]) : 0.f;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
             acc += (double)v[i];
     }
     for (; g < g1; g += kMeanRowLanes)
-        acc += on ? (double)col[g * ldx] : 0.0;
+        acc += on ? (double)E::cvt(col[g * ldx]) : 0.0;
     red[rl][cl] = acc;
     __syncthreads();
     if (rl == 0 && on)
@@ -119,10 +123,10 @@ GramPlan gram_plan(int64_t N, int D)
     return p;
 }
 
-template <bool VEC>
-__global__ __launch_bounds__(kGramThreads) void k_centered_gram(int64_t N, int D, const float *__restrict__ X, int64_t ldx,
-                                                                const float *__restrict__ mean, int64_t rows_per_slice, int n_tb,
-                                                                float *__restrict__ partial)
+template <int MT, bool VEC>
+__global__ __launch_bounds__(kGramThreads) void k_centered_gram(int64_t N, int D, const typename MapElem<MT>::raw *__restrict__ X,
+                                                                int64_t ldx, const float *__restrict__ mean, int64_t rows_per_slice,
+                                                                int n_tb, float *__restrict__ partial)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[]; // [2][kGramKC][kGramLd]
 
@@ -149,18 +153,18 @@ __global__ __launch_bounds__(kGramThreads) void k_centered_gram(int64_t N, int D
     const int ca = ti * kGramT + c4, cb = tj * kGramT + c4;
     const float4 ma = load4<false>(mean, ca, D), mb = load4<false>(mean, cb, D); // 0 beyond D, like the columns themselves
 
-    float4 pa[4], pb[4];
+    typename MapElem<MT>::raw4 pa[4], pb[4]; // (the bits as loaded: widened where the staging writes them)
     int live = 0; // bit i: row r0 + 8 i of the prefetched chunk exists
     auto prefetch = [&](int it) {
         live = 0;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int64_t g = g0 + (int64_t)it * kGramKC + r0 + 8 * i;
-            const float *row = g < g1 ? X + g * ldx : nullptr;
+            const typename MapElem<MT>::raw *row = g < g1 ? X + g * ldx : nullptr;
             live |= (row ? 1 : 0) << i;
-            pa[i] = load4<VEC>(row, ca, D);
+            pa[i] = load4raw<MT, VEC>(row, ca, D);
             if (!diag)
-                pb[i] = load4<VEC>(row, cb, D);
+                pb[i] = load4raw<MT, VEC>(row, cb, D);
         }
     };
     auto centred = [](float4 v, float4 mu, bool on) {
@@ -180,9 +184,9 @@ __global__ __launch_bounds__(kGramThreads) void k_centered_gram(int64_t N, int D
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const bool on = (live >> i) & 1;
-            *reinterpret_cast<float4 *>(buf + (r0 + 8 * i) * kGramLd + c4) = centred(pa[i], ma, on);
+            *reinterpret_cast<float4 *>(buf + (r0 + 8 * i) * kGramLd + c4) = centred(widen4<MT>(pa[i]), ma, on);
             if (!diag)
-                *reinterpret_cast<float4 *>(buf + (r0 + 8 * i) * kGramLd + kGramT + c4) = centred(pb[i], mb, on);
+                *reinterpret_cast<float4 *>(buf + (r0 + 8 * i) * kGramLd + kGramT + c4) = centred(widen4<MT>(pb[i]), mb, on);
         }
         __syncthreads(); // (the buffer written here was last read two steps ago, before the previous barrier)
         if (it + 1 < n_it)
@@ -248,8 +252,9 @@ constexpr int kProjLd = kProjKC + 4;
 constexpr int kProjMaxK = 16;
 static_assert(kProjRows == 128, "four waves x two 16-row MFMA blocks");
 
-template <bool VEC>
-__global__ __launch_bounds__(kProjThreads) void k_pca_project(int64_t N, int D, int k, const float *__restrict__ X, int64_t ldx,
+template <int MT, bool VEC>
+__global__ __launch_bounds__(kProjThreads) void k_pca_project(int64_t N, int D, int k,
+                                                              const typename MapElem<MT>::raw *__restrict__ X, int64_t ldx,
                                                               const float *__restrict__ mean, const float *__restrict__ V,
                                                               float *__restrict__ Y, float *__restrict__ minmax)
 {
@@ -263,7 +268,7 @@ __global__ __launch_bounds__(kProjThreads) void k_pca_project(int64_t N, int D, 
 
     // staging role: float4 column c4 of rows r0 + 32 i (i < 4) of X, and (threads 0..127) of component r0
     const int c4 = (tid & 7) * 4, r0 = tid >> 3;
-    const float *xrow[4];
+    const typename MapElem<MT>::raw *xrow[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int64_t g = q0 + r0 + 32 * i;
@@ -272,12 +277,13 @@ __global__ __launch_bounds__(kProjThreads) void k_pca_project(int64_t N, int D, 
     const float *vrow = (tid < kProjMaxK * 8 && r0 < k) ? V + (int64_t)r0 * D : nullptr;
 
     const int n_chunk = (D + kProjKC - 1) / kProjKC;
-    float4 px[4], pv, pm;
+    typename MapElem<MT>::raw4 px[4];
+    float4 pv, pm;
     auto prefetch = [&](int chunk) {
         const int c = chunk * kProjKC + c4;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-            px[i] = load4<VEC>(xrow[i], c, D);
+            px[i] = load4raw<MT, VEC>(xrow[i], c, D);
         pv = load4<false>(vrow, c, D);
         pm = load4<false>(mean, c, D);
     };
@@ -287,9 +293,10 @@ __global__ __launch_bounds__(kProjThreads) void k_pca_project(int64_t N, int D, 
     for (int chunk = 0; chunk < n_chunk; ++chunk) {
         float *bx = sx[chunk & 1], *bv = sv[chunk & 1];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) // (a row beyond N stages -mu: its Y is never written or counted)
-            *reinterpret_cast<float4 *>(bx + (r0 + 32 * i) * kProjLd + c4) =
-                make_float4(px[i].x - pm.x, px[i].y - pm.y, px[i].z - pm.z, px[i].w - pm.w);
+        for (int i = 0; i < 4; ++i) { // (a row beyond N stages -mu: its Y is never written or counted)
+            const float4 x = widen4<MT>(px[i]);
+            *reinterpret_cast<float4 *>(bx + (r0 + 32 * i) * kProjLd + c4) = make_float4(x.x - pm.x, x.y - pm.y, x.z - pm.z, x.w - pm.w);
+        }
         if (tid < kProjMaxK * 8)
             *reinterpret_cast<float4 *>(bv + r0 * kProjLd + c4) = pv;
         __syncthreads();
@@ -364,8 +371,6 @@ __global__ __launch_bounds__(256) void k_pca_colors(int64_t n, const float *__re
     out[e] = span > 0.f ? (Y[e] - lo) / span : 0.5f;
 }
 
-bool rows_vec(const float *X, int64_t ldx) { return !(reinterpret_cast<uintptr_t>(X) & 15) && !(ldx & 3); }
-
 int grid_of(int64_t n, int per, const char *what, unsigned *grid)
 {
     const int64_t g = (n + per - 1) / per;
@@ -384,46 +389,87 @@ size_t pca_workspace_bytes(int64_t N, int D)
     return means > gram ? means : gram;
 }
 
-int launch_column_means(int64_t N, int D, const float *X, int64_t ldx, float *mean, void *ws, hipStream_t s)
+template <int MT>
+static void launch_column_sums_t(dim3 grid, hipStream_t s, int64_t N, int D, const void *X, int64_t ldx, int64_t rows, double *partial)
+{
+    hipLaunchKernelGGL(k_column_sums<MT>, grid, dim3(kMeanCols * kMeanRowLanes), 0, s, N, D,
+                       static_cast<const typename MapElem<MT>::raw *>(X), ldx, rows, partial);
+}
+
+int launch_column_means(int64_t N, int D, const void *X, int mt, int64_t ldx, float *mean, void *ws, hipStream_t s)
 {
     const MeanPlan p = mean_plan(N);
     double *partial = static_cast<double *>(ws);
-    hipLaunchKernelGGL(k_column_sums, dim3((unsigned)((D + kMeanCols - 1) / kMeanCols), (unsigned)p.slices),
-                       dim3(kMeanCols * kMeanRowLanes), 0, s, N, D, X, ldx, p.rows, partial);
+    const dim3 grid((unsigned)((D + kMeanCols - 1) / kMeanCols), (unsigned)p.slices);
+    if (mt == GWBP_MAP_F16)
+        launch_column_sums_t<GWBP_MAP_F16>(grid, s, N, D, X, ldx, p.rows, partial);
+    else if (mt == GWBP_MAP_BF16)
+        launch_column_sums_t<GWBP_MAP_BF16>(grid, s, N, D, X, ldx, p.rows, partial);
+    else
+        launch_column_sums_t<GWBP_MAP_F32>(grid, s, N, D, X, ldx, p.rows, partial);
     hipLaunchKernelGGL(k_column_means, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, s, N, D, p.slices, partial, mean);
     return check_hip(hipGetLastError(), "column_means launch");
 }
 
-int launch_centered_gram(int64_t N, int D, const float *X, int64_t ldx, const float *mean, double *gram, void *ws, hipStream_t s)
+// slot: the first of the instantiation pair's two bits of ensure_dynamic_lds (vector, then element loads)
+template <int MT>
+static int launch_centered_gram_t(int slot, const GramPlan &p, int64_t N, int D, const void *Xv, int64_t ldx, const float *mean,
+                                  float *partial, hipStream_t s)
 {
-    const GramPlan p = gram_plan(N, D);
-    const bool vec = rows_vec(X, ldx);
+    const typename MapElem<MT>::raw *X = static_cast<const typename MapElem<MT>::raw *>(Xv);
+    const bool vec = field_rows_vec(Xv, ldx, MT);
     const int lds = 2 * kGramStage * (int)sizeof(float);
-    const void *fn = vec ? reinterpret_cast<const void *>(k_centered_gram<true>) : reinterpret_cast<const void *>(k_centered_gram<false>);
-    int rc = ensure_dynamic_lds(fn, lds, vec ? 26 : 27);
+    const void *fn =
+        vec ? reinterpret_cast<const void *>(k_centered_gram<MT, true>) : reinterpret_cast<const void *>(k_centered_gram<MT, false>);
+    const int rc = ensure_dynamic_lds(fn, lds, vec ? slot : slot + 1);
     if (rc)
         return rc;
-    float *partial = static_cast<float *>(ws);
     const dim3 grid((unsigned)p.n_tiles, (unsigned)p.slices);
     if (vec)
-        hipLaunchKernelGGL(k_centered_gram<true>, grid, dim3(kGramThreads), lds, s, N, D, X, ldx, mean, p.rows, p.n_tb, partial);
+        hipLaunchKernelGGL((k_centered_gram<MT, true>), grid, dim3(kGramThreads), lds, s, N, D, X, ldx, mean, p.rows, p.n_tb, partial);
     else
-        hipLaunchKernelGGL(k_centered_gram<false>, grid, dim3(kGramThreads), lds, s, N, D, X, ldx, mean, p.rows, p.n_tb, partial);
+        hipLaunchKernelGGL((k_centered_gram<MT, false>), grid, dim3(kGramThreads), lds, s, N, D, X, ldx, mean, p.rows, p.n_tb, partial);
+    return GWBP_OK;
+}
+
+int launch_centered_gram(int64_t N, int D, const void *X, int mt, int64_t ldx, const float *mean, double *gram, void *ws,
+                         hipStream_t s)
+{
+    const GramPlan p = gram_plan(N, D);
+    float *partial = static_cast<float *>(ws);
+    const int rc = mt == GWBP_MAP_F16    ? launch_centered_gram_t<GWBP_MAP_F16>(40, p, N, D, X, ldx, mean, partial, s)
+                   : mt == GWBP_MAP_BF16 ? launch_centered_gram_t<GWBP_MAP_BF16>(42, p, N, D, X, ldx, mean, partial, s)
+                                         : launch_centered_gram_t<GWBP_MAP_F32>(26, p, N, D, X, ldx, mean, partial, s);
+    if (rc)
+        return rc;
     hipLaunchKernelGGL(k_gram_reduce, dim3((unsigned)(((int64_t)D * D + 255) / 256)), dim3(256), 0, s, D, p.slices, partial, gram);
     return check_hip(hipGetLastError(), "centered_gram launch");
 }
 
-int launch_pca_project(int64_t N, int D, int k, const float *X, int64_t ldx, const float *mean, const float *V, float *Y,
+template <int MT>
+static void launch_pca_project_t(unsigned grid, hipStream_t s, int64_t N, int D, int k, const void *Xv, int64_t ldx, const float *mean,
+                                 const float *V, float *Y, float *minmax)
+{
+    const typename MapElem<MT>::raw *X = static_cast<const typename MapElem<MT>::raw *>(Xv);
+    if (field_rows_vec(Xv, ldx, MT))
+        hipLaunchKernelGGL((k_pca_project<MT, true>), dim3(grid), dim3(kProjThreads), 0, s, N, D, k, X, ldx, mean, V, Y, minmax);
+    else
+        hipLaunchKernelGGL((k_pca_project<MT, false>), dim3(grid), dim3(kProjThreads), 0, s, N, D, k, X, ldx, mean, V, Y, minmax);
+}
+
+int launch_pca_project(int64_t N, int D, int k, const void *X, int mt, int64_t ldx, const float *mean, const float *V, float *Y,
                        float *minmax, hipStream_t s)
 {
     unsigned grid = 0;
     const int rc = grid_of(N, kProjRows, "pca_project", &grid);
     if (rc)
         return rc;
-    if (rows_vec(X, ldx))
-        hipLaunchKernelGGL(k_pca_project<true>, dim3(grid), dim3(kProjThreads), 0, s, N, D, k, X, ldx, mean, V, Y, minmax);
+    if (mt == GWBP_MAP_F16)
+        launch_pca_project_t<GWBP_MAP_F16>(grid, s, N, D, k, X, ldx, mean, V, Y, minmax);
+    else if (mt == GWBP_MAP_BF16)
+        launch_pca_project_t<GWBP_MAP_BF16>(grid, s, N, D, k, X, ldx, mean, V, Y, minmax);
     else
-        hipLaunchKernelGGL(k_pca_project<false>, dim3(grid), dim3(kProjThreads), 0, s, N, D, k, X, ldx, mean, V, Y, minmax);
+        launch_pca_project_t<GWBP_MAP_F32>(grid, s, N, D, k, X, ldx, mean, V, Y, minmax);
     return check_hip(hipGetLastError(), "pca_project launch");
 }
 

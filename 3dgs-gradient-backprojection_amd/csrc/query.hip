@@ -5,6 +5,9 @@
 //                     max_{j < n_pos} s[g, j] > max_{j >= n_pos} s[g, j]  (&& s[g, 0] > threshold): ONE pass over X
 //   k_probe_pixels    out[m, :] = sum_g w_g(p_m) X[g, :] at M pixels only, + the accumulated depth and alpha of those pixels
 //
+// k_prompt_scores itself is query_kernel.h, a template over the element type of X: this file instantiates it for fp32 fields,
+// query_half.hip for fp16 / bf16 ones (widened exactly as they are loaded: the same staged values, chains and results).
+//
 // ARITHMETIC CONTRACT of k_prompt_scores (the shape of k_pca_project's, pca.hip).  Every dot product AND the row's sum of squares
 // is one chain of fp32 fused multiply-adds over the channel index (v_mfma_f32_16x16x4_f32 is bit for bit a k-ordered fmaf chain; the
 // sum of squares is the diagonal of the row block's own 16 x 16 product, so it runs through the columns in the very order of the
@@ -30,148 +33,11 @@
 // pixel is summed front to back by its one owner").  Every loop is wave-uniform with a finite trip count (list batches, 64
 // entries of a batch, the set bits of a 64-bit mask); T advances on values made uniform with v_readfirstlane.
 #include "gwbp_dev.h"
+#include "query_kernel.h"
 
 namespace gwbp {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// ---- prompt scores --------------------------------------------------------------------------------------------------------------
-constexpr int kQThreads = 256; // 4 waves, each owns 32 of the workgroup's rows
-constexpr int kQRows = 128;
-constexpr int kQKC = 32;       // columns staged per step
-constexpr int kQLd = kQKC + 4; // LDS row stride (floats): the operand reads are ds_read_b128 at 144-B steps, conflict-free per 8 lanes
-
-// torch.max's rule: a NaN on either side is the result
-__device__ __forceinline__ float max_nan(float a, float b) { return (a != a) ? a : ((b > a || b != b) ? b : a); }
-
-// NPB: 16-prompt blocks (1: P <= 16, 2: P <= 32)
-template <bool VEC, int NPB>
-__global__ __launch_bounds__(kQThreads) void k_prompt_scores(int64_t N, int D, int P, int n_pos, const float *__restrict__ X,
-                                                             int64_t ldx, const float *__restrict__ prompts, int normalize,
-                                                             int use_thr, float thr, uint8_t *__restrict__ mask,
-                                                             float *__restrict__ scores)
-{
-    __shared__ __attribute__((aligned(16))) float sx[2][kQRows * kQLd];
-    __shared__ __attribute__((aligned(16))) float sp[2][NPB * 16 * kQLd];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int m = lane & 15, qd = lane >> 4;
-    const int64_t q0 = (int64_t)blockIdx.x * kQRows;
-
-    // staging role: float4 column c4 of rows r0 + 32 i (i < 4) of X, and (threads 0 .. 128 NPB - 1) of prompt r0
-    const int c4 = (tid & 7) * 4, r0 = tid >> 3;
-    const float *xrow[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int64_t g = q0 + r0 + 32 * i;
-        xrow[i] = g < N ? X + g * ldx : nullptr;
-    }
-    const bool stages_p = tid < NPB * 16 * 8;
-    const float *prow = (stages_p && r0 < P) ? prompts + (int64_t)r0 * D : nullptr; // a prompt beyond P stages zeros
-
-    const int n_chunk = (D + kQKC - 1) / kQKC;
-    float4 px[4], pp;
-    auto prefetch = [&](int chunk) {
-        const int c = chunk * kQKC + c4;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            px[i] = load4<VEC>(xrow[i], c, D);
-        pp = load4<false>(prow, c, D);
-    };
-    prefetch(0);
-
-    const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
-    f32x4 acc[NPB][2]; // [pb][rb]: row 32 wave + 16 rb + m, prompts 16 pb + 4 qd + r
-    f32x4 sq[2];       // [rb]: rows 16 rb + 4 qd + r against row 16 rb + m of the wave's block; the diagonal is the sum of squares
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb) {
-        sq[rb] = zero;
-#pragma unroll
-        for (int pb = 0; pb < NPB; ++pb)
-            acc[pb][rb] = zero;
-    }
-
-    for (int chunk = 0; chunk < n_chunk; ++chunk) {
-        float *bx = sx[chunk & 1], *bp = sp[chunk & 1];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) // (a row beyond N stages zeros: nothing of it is ever written)
-            *reinterpret_cast<float4 *>(bx + (r0 + 32 * i) * kQLd + c4) = px[i];
-        if (stages_p)
-            *reinterpret_cast<float4 *>(bp + r0 * kQLd + c4) = pp;
-        __syncthreads(); // (the buffers written here were last read two steps ago, before the previous barrier)
-        if (chunk + 1 < n_chunk)
-            prefetch(chunk + 1);
-
-        const float *ox = bx + (wave * 32 + m) * kQLd + 4 * qd;
-        const float *op = bp + m * kQLd + 4 * qd;
-#pragma unroll
-        for (int kb = 0; kb < kQKC / 16; ++kb) {
-            float4 fp[NPB], fx[2];
-#pragma unroll
-            for (int pb = 0; pb < NPB; ++pb)
-                fp[pb] = *reinterpret_cast<const float4 *>(op + pb * 16 * kQLd + kb * 16);
-#pragma unroll
-            for (int rb = 0; rb < 2; ++rb)
-                fx[rb] = *reinterpret_cast<const float4 *>(ox + rb * 16 * kQLd + kb * 16);
-#define GWBP_Q_STEP(E)                                                                                                \
-    _Pragma("unroll") for (int rb = 0; rb < 2; ++rb)                                                                  \
-    {                                                                                                                 \
-        _Pragma("unroll") for (int pb = 0; pb < NPB; ++pb) acc[pb][rb] =                                              \
-            __builtin_amdgcn_mfma_f32_16x16x4f32(fp[pb].E, fx[rb].E, acc[pb][rb], 0, 0, 0);                           \
-        sq[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(fx[rb].E, fx[rb].E, sq[rb], 0, 0, 0);                           \
-    }
-            GWBP_Q_STEP(x)
-            GWBP_Q_STEP(y)
-            GWBP_Q_STEP(z)
-            GWBP_Q_STEP(w)
-#undef GWBP_Q_STEP
-        }
-    }
-
-    // ---- epilogue, in registers: the row's norm, the divide, the two maxima, the compare, the byte -----------------------------
-    const float ninf = -__builtin_inff();
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb) {
-        const int64_t g = q0 + wave * 32 + 16 * rb + m;
-        // sum of squares of row m: entry (m, m) of the block's product, held by lane (qd = m >> 2) as element m & 3
-        const int e = m & 3;
-        const float mine = e == 0 ? sq[rb][0] : e == 1 ? sq[rb][1] : e == 2 ? sq[rb][2] : sq[rb][3];
-        const float ss = __shfl(mine, (m >> 2) * 16 + m, 64);
-        const float den = __builtin_fmaxf(__builtin_sqrtf(ss), 1e-12f);
-        float best_pos = ninf, best_neg = ninf, s0 = 0.f;
-#pragma unroll
-        for (int pb = 0; pb < NPB; ++pb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int j = 16 * pb + 4 * qd + r;
-                const float dot = acc[pb][rb][r];
-                const float s = normalize ? dot / den : dot;
-                if (j < P) {
-                    if (scores && g < N)
-                        scores[g * P + j] = s;
-                    if (j < n_pos)
-                        best_pos = max_nan(best_pos, s);
-                    else
-                        best_neg = max_nan(best_neg, s);
-                }
-                if (pb == 0 && r == 0)
-                    s0 = s; // (lanes qd = 0: prompt 0)
-            }
-        // the four lanes of a row (qd = 0 .. 3) hold its prompts 4 qd .. 4 qd + 3 of each block
-        best_pos = max_nan(best_pos, __shfl_xor(best_pos, 16, 64));
-        best_neg = max_nan(best_neg, __shfl_xor(best_neg, 16, 64));
-        best_pos = max_nan(best_pos, __shfl_xor(best_pos, 32, 64));
-        best_neg = max_nan(best_neg, __shfl_xor(best_neg, 32, 64));
-        if (mask && qd == 0 && g < N) {
-            bool in = n_pos < P ? best_pos > best_neg : true;
-            if (use_thr)
-                in = in && s0 > thr;
-            mask[g] = in ? 1 : 0;
-        }
-    }
-}
 
 // ---- probe ----------------------------------------------------------------------------------------------------------------------
 constexpr int kProbeChunk = 256; // channels per wave: four per lane
@@ -271,7 +137,7 @@ bool rows_vec(const float *X, int64_t ldx) { return !(reinterpret_cast<uintptr_t
 
 } // namespace
 
-int launch_prompt_scores(int64_t N, int D, int P, int n_pos, const float *X, int64_t ldx, const float *prompts, int normalize,
+int launch_prompt_scores(int64_t N, int D, int P, int n_pos, const void *X, int mt, int64_t ldx, const float *prompts, int normalize,
                          const float *threshold, uint8_t *mask, float *scores, hipStream_t s)
 {
     if (N == 0)
@@ -281,22 +147,10 @@ int launch_prompt_scores(int64_t N, int D, int P, int n_pos, const float *X, int
         return set_error(GWBP_EINVAL, "prompt_scores: %lld rows need more than 2^31 - 1 workgroups", (long long)N);
     const int use_thr = threshold ? 1 : 0;
     const float thr = threshold ? *threshold : 0.f;
-    const bool vec = rows_vec(X, ldx);
-#define GWBP_Q(VEC, NPB)                                                                                              \
-    hipLaunchKernelGGL((k_prompt_scores<VEC, NPB>), dim3((unsigned)grid), dim3(kQThreads), 0, s, N, D, P, n_pos, X, ldx, prompts, \
-                       normalize, use_thr, thr, mask, scores)
-    if (P <= 16) {
-        if (vec)
-            GWBP_Q(true, 1);
-        else
-            GWBP_Q(false, 1);
-    } else {
-        if (vec)
-            GWBP_Q(true, 2);
-        else
-            GWBP_Q(false, 2);
-    }
-#undef GWBP_Q
+    if (mt != GWBP_MAP_F32) // the half instantiations are query_half.hip's
+        launch_prompt_scores_half((unsigned)grid, s, N, D, P, n_pos, X, mt, ldx, prompts, normalize, use_thr, thr, mask, scores);
+    else
+        launch_prompt_scores_t<GWBP_MAP_F32>((unsigned)grid, s, N, D, P, n_pos, X, ldx, prompts, normalize, use_thr, thr, mask, scores);
     return check_hip(hipGetLastError(), "prompt_scores launch");
 }
 

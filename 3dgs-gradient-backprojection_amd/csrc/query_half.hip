@@ -1,0 +1,17 @@
+// query_half.hip -- the fp16 / bf16 instantiations of k_prompt_scores (query_kernel.h): a half field is widened as it is loaded, so the
+// staged values, the chains and every result are those of the fp32 kernel on the widened field.
+#include "gwbp_dev.h"
+#include "query_kernel.h"
+
+namespace gwbp {
+
+void launch_prompt_scores_half(unsigned grid, hipStream_t s, int64_t N, int D, int P, int n_pos, const void *X, int mt, int64_t ldx,
+                               const float *prompts, int normalize, int use_thr, float thr, uint8_t *mask, float *scores)
+{
+    if (mt == GWBP_MAP_F16)
+        launch_prompt_scores_t<GWBP_MAP_F16>(grid, s, N, D, P, n_pos, X, ldx, prompts, normalize, use_thr, thr, mask, scores);
+    else
+        launch_prompt_scores_t<GWBP_MAP_BF16>(grid, s, N, D, P, n_pos, X, ldx, prompts, normalize, use_thr, thr, mask, scores);
+}
+
+} // namespace gwbp

@@ -60,12 +60,21 @@ __device__ __forceinline__ float lane_chain(const float4 (&a)[NS], const float4 
     return acc;
 }
 
-template <bool VEC, int NS>
-__device__ __forceinline__ void load_row(float4 (&r)[NS], const float *__restrict__ p, int lane, int D)
+// MT: the element type of the field.  load_row lands a row's bits (zeros beyond D and for p == nullptr, without a load); widen_row
+// turns them into the registers the fp32 kernel's loads fill (exact; fp32: the identity) once every load of the step is issued.
+template <int MT, bool VEC, int NS>
+__device__ __forceinline__ void load_row(typename MapElem<MT>::raw4 (&r)[NS], const void *__restrict__ p, int lane, int D)
 {
 #pragma unroll
     for (int s = 0; s < NS; ++s)
-        r[s] = load4<VEC>(p, 256 * s + 4 * lane, D); // (zeros beyond D and for p == nullptr, without a load)
+        r[s] = load4raw<MT, VEC>(p, 256 * s + 4 * lane, D);
+}
+template <int MT, int NS>
+__device__ __forceinline__ void widen_row(float4 (&x)[NS], const typename MapElem<MT>::raw4 (&r)[NS])
+{
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+        x[s] = widen4<MT>(r[s]);
 }
 
 __device__ __forceinline__ bool feature_live(float sq, float norm)
@@ -84,17 +93,19 @@ __device__ __forceinline__ float similarity(const float4 (&a)[NS], const float4 
     return valid && live_i && feature_live(sq, norm) ? s : __builtin_nanf("");
 }
 
-template <bool VEC, int NS>
+template <int MT, bool VEC, int NS>
 __global__ __launch_bounds__(256) void k_neighbor_similarity(int64_t N, int D, int k, const int32_t *__restrict__ idx,
-                                                             const float *__restrict__ F, int64_t ldf, float *__restrict__ sim,
-                                                             int32_t *__restrict__ live)
+                                                             const typename MapElem<MT>::raw *__restrict__ F, int64_t ldf,
+                                                             float *__restrict__ sim, int32_t *__restrict__ live)
 {
     const int lane = threadIdx.x & 63;
     const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); // wave-uniform
     if (g >= N)
         return;
     float4 a[NS], b0[NS], b1[NS];
-    load_row<VEC, NS>(a, F + g * ldf, lane, D);
+    typename MapElem<MT>::raw4 r0[NS], r1[NS];
+    load_row<MT, VEC, NS>(r0, F + g * ldf, lane, D);
+    widen_row<MT, NS>(a, r0);
     const float sq_i = wave_sum(lane_chain<NS>(a, a));
     const float norm_i = __builtin_sqrtf(sq_i);
     const bool live_i = feature_live(sq_i, norm_i);
@@ -104,8 +115,10 @@ __global__ __launch_bounds__(256) void k_neighbor_similarity(int64_t N, int D, i
         const int j0 = (int)uniform((u32)row[c]);
         const int j1 = c + 1 < k ? (int)uniform((u32)row[c + 1]) : -1;
         const bool v0 = j0 >= 0 && j0 < N, v1 = j1 >= 0 && j1 < N;
-        load_row<VEC, NS>(b0, v0 ? F + (int64_t)j0 * ldf : nullptr, lane, D);
-        load_row<VEC, NS>(b1, v1 ? F + (int64_t)j1 * ldf : nullptr, lane, D);
+        load_row<MT, VEC, NS>(r0, v0 ? F + (int64_t)j0 * ldf : nullptr, lane, D);
+        load_row<MT, VEC, NS>(r1, v1 ? F + (int64_t)j1 * ldf : nullptr, lane, D);
+        widen_row<MT, NS>(b0, r0);
+        widen_row<MT, NS>(b1, r1);
         const float s0 = similarity<NS>(a, b0, v0, live_i, norm_i);
         const float s1 = similarity<NS>(a, b1, v1, live_i, norm_i);
         if (lane == 0) {
@@ -149,30 +162,43 @@ __global__ __launch_bounds__(kUnionThreads) void k_edge_union(int64_t N, int k, 
     }
 }
 
-template <bool VEC>
-void launch_similarity(unsigned grid, hipStream_t s, int64_t N, int D, int k, const int32_t *idx, const float *F, int64_t ldf,
+template <int MT, bool VEC>
+void launch_similarity(unsigned grid, hipStream_t s, int64_t N, int D, int k, const int32_t *idx, const void *Fv, int64_t ldf,
                        float *sim, int32_t *live)
 {
+    const typename MapElem<MT>::raw *F = static_cast<const typename MapElem<MT>::raw *>(Fv);
     if (D <= 256)
-        hipLaunchKernelGGL((k_neighbor_similarity<VEC, 1>), dim3(grid), dim3(256), 0, s, N, D, k, idx, F, ldf, sim, live);
+        hipLaunchKernelGGL((k_neighbor_similarity<MT, VEC, 1>), dim3(grid), dim3(256), 0, s, N, D, k, idx, F, ldf, sim, live);
     else if (D <= 512)
-        hipLaunchKernelGGL((k_neighbor_similarity<VEC, 2>), dim3(grid), dim3(256), 0, s, N, D, k, idx, F, ldf, sim, live);
+        hipLaunchKernelGGL((k_neighbor_similarity<MT, VEC, 2>), dim3(grid), dim3(256), 0, s, N, D, k, idx, F, ldf, sim, live);
     else if (D <= 1024)
-        hipLaunchKernelGGL((k_neighbor_similarity<VEC, 4>), dim3(grid), dim3(256), 0, s, N, D, k, idx, F, ldf, sim, live);
+        hipLaunchKernelGGL((k_neighbor_similarity<MT, VEC, 4>), dim3(grid), dim3(256), 0, s, N, D, k, idx, F, ldf, sim, live);
     else
-        hipLaunchKernelGGL((k_neighbor_similarity<VEC, 8>), dim3(grid), dim3(256), 0, s, N, D, k, idx, F, ldf, sim, live);
+        hipLaunchKernelGGL((k_neighbor_similarity<MT, VEC, 8>), dim3(grid), dim3(256), 0, s, N, D, k, idx, F, ldf, sim, live);
+}
+
+template <int MT>
+void launch_similarity_t(unsigned grid, hipStream_t s, int64_t N, int D, int k, const int32_t *idx, const void *F, int64_t ldf,
+                         float *sim, int32_t *live)
+{
+    if (field_rows_vec(F, ldf, MT))
+        launch_similarity<MT, true>(grid, s, N, D, k, idx, F, ldf, sim, live);
+    else
+        launch_similarity<MT, false>(grid, s, N, D, k, idx, F, ldf, sim, live);
 }
 
 } // namespace
 
-int launch_neighbor_similarity(int64_t N, int D, int k, const int32_t *idx, const float *F, int64_t ldf, float *sim, int32_t *live,
-                               hipStream_t s)
+int launch_neighbor_similarity(int64_t N, int D, int k, const int32_t *idx, const void *F, int mt, int64_t ldf, float *sim,
+                               int32_t *live, hipStream_t s)
 {
     const unsigned grid = (unsigned)((N + 3) / 4); // (N < 2^31, checked by the caller)
-    if (!(reinterpret_cast<uintptr_t>(F) & 15) && !(ldf & 3))
-        launch_similarity<true>(grid, s, N, D, k, idx, F, ldf, sim, live);
+    if (mt == GWBP_MAP_F16)
+        launch_similarity_t<GWBP_MAP_F16>(grid, s, N, D, k, idx, F, ldf, sim, live);
+    else if (mt == GWBP_MAP_BF16)
+        launch_similarity_t<GWBP_MAP_BF16>(grid, s, N, D, k, idx, F, ldf, sim, live);
     else
-        launch_similarity<false>(grid, s, N, D, k, idx, F, ldf, sim, live);
+        launch_similarity_t<GWBP_MAP_F32>(grid, s, N, D, k, idx, F, ldf, sim, live);
     return check_hip(hipGetLastError(), "neighbor_similarity launch");
 }
 

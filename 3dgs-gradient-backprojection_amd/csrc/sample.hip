@@ -155,9 +155,11 @@ __device__ __forceinline__ void fma4(float4 &acc, float w, const float4 &v)
     acc.w = __builtin_fmaf(w, v.w, acc.w);
 }
 
-template <bool VEC>
+// MT: the element type of F (a half row is widened as it is loaded; weights, chains and out are fp32)
+template <int MT, bool VEC>
 __global__ __launch_bounds__(256) void k_neighbor_blend(int64_t Q, int64_t M, int D, int k, const int32_t *__restrict__ idx,
-                                                        const float *__restrict__ wts, const float *__restrict__ F, int64_t ldf,
+                                                        const float *__restrict__ wts,
+                                                        const typename MapElem<MT>::raw *__restrict__ F, int64_t ldf,
                                                         float *__restrict__ out, int64_t ldo, float *__restrict__ wsum)
 {
     const int lane = threadIdx.x & 63;
@@ -196,12 +198,12 @@ __global__ __launch_bounds__(256) void k_neighbor_blend(int64_t Q, int64_t M, in
             const float w0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_w), j));
             const float w1 = j + 1 < k ? __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_w), j + 1)) : 0.0f;
             // both rows requested before the first use (nullptr: no load)
-            const float4 v0 = load4<VEC>(j0 >= 0 ? F + (int64_t)j0 * ldf : nullptr, c, D);
-            const float4 v1 = load4<VEC>(j1 >= 0 ? F + (int64_t)j1 * ldf : nullptr, c, D);
+            const auto r0 = load4raw<MT, VEC>(j0 >= 0 ? F + (int64_t)j0 * ldf : nullptr, c, D);
+            const auto r1 = load4raw<MT, VEC>(j1 >= 0 ? F + (int64_t)j1 * ldf : nullptr, c, D);
             if (j0 >= 0)
-                fma4(acc, w0, v0);
+                fma4(acc, w0, widen4<MT>(r0));
             if (j1 >= 0)
-                fma4(acc, w1, v1);
+                fma4(acc, w1, widen4<MT>(r1));
         }
         if (any)
             acc = make_float4(acc.x / W, acc.y / W, acc.z / W, acc.w / W);
@@ -300,7 +302,19 @@ int launch_point_gaussians(const float *sorted, const int32_t *cell_start, const
     return check_hip(hipGetLastError(), "point_gaussians launch");
 }
 
-int launch_neighbor_blend(int64_t Q, int64_t M, int D, int k, const int32_t *idx, const float *w, const float *F, int64_t ldf,
+template <int MT>
+static void launch_neighbor_blend_t(unsigned grid, hipStream_t s, int64_t Q, int64_t M, int D, int k, const int32_t *idx, const float *w,
+                                    const void *Fv, int64_t ldf, float *out, int64_t ldo, float *wsum)
+{
+    const typename MapElem<MT>::raw *F = static_cast<const typename MapElem<MT>::raw *>(Fv);
+    const bool vec = field_rows_vec(Fv, ldf, MT) && field_rows_vec(out, ldo, GWBP_MAP_F32);
+    if (vec)
+        hipLaunchKernelGGL((k_neighbor_blend<MT, true>), dim3(grid), dim3(256), 0, s, Q, M, D, k, idx, w, F, ldf, out, ldo, wsum);
+    else
+        hipLaunchKernelGGL((k_neighbor_blend<MT, false>), dim3(grid), dim3(256), 0, s, Q, M, D, k, idx, w, F, ldf, out, ldo, wsum);
+}
+
+int launch_neighbor_blend(int64_t Q, int64_t M, int D, int k, const int32_t *idx, const float *w, const void *F, int mt, int64_t ldf,
                           float *out, int64_t ldo, float *wsum, hipStream_t s)
 {
     if (Q == 0)
@@ -308,11 +322,12 @@ int launch_neighbor_blend(int64_t Q, int64_t M, int D, int k, const int32_t *idx
     unsigned grid;
     if (int rc = grid_of("neighbor_blend", Q, &grid, 4))
         return rc;
-    const bool vec = !(reinterpret_cast<uintptr_t>(F) & 15) && !(reinterpret_cast<uintptr_t>(out) & 15) && !(ldf & 3) && !(ldo & 3);
-    if (vec)
-        hipLaunchKernelGGL(k_neighbor_blend<true>, dim3(grid), dim3(256), 0, s, Q, M, D, k, idx, w, F, ldf, out, ldo, wsum);
+    if (mt == GWBP_MAP_F16)
+        launch_neighbor_blend_t<GWBP_MAP_F16>(grid, s, Q, M, D, k, idx, w, F, ldf, out, ldo, wsum);
+    else if (mt == GWBP_MAP_BF16)
+        launch_neighbor_blend_t<GWBP_MAP_BF16>(grid, s, Q, M, D, k, idx, w, F, ldf, out, ldo, wsum);
     else
-        hipLaunchKernelGGL(k_neighbor_blend<false>, dim3(grid), dim3(256), 0, s, Q, M, D, k, idx, w, F, ldf, out, ldo, wsum);
+        launch_neighbor_blend_t<GWBP_MAP_F32>(grid, s, Q, M, D, k, idx, w, F, ldf, out, ldo, wsum);
     return check_hip(hipGetLastError(), "neighbor_blend launch");
 }
 

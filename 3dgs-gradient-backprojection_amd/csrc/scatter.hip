@@ -201,9 +201,11 @@ __global__ __launch_bounds__(kScatterThreads) void k_scatter(
     }
 }
 
-// backproject.py:63,166-169 -- one wave per Gaussian row.
+// backproject.py:63,166-169 -- one wave per Gaussian row.  OT: the element type of out; a half out is the fp32 value (NaN -> 0
+// included) rounded once to nearest even (narrow), and cannot alias F.
+template <int OT>
 __global__ __launch_bounds__(256) void k_finalize(int64_t N, int D, const float *__restrict__ F,
-                                                  const float *__restrict__ d, float *__restrict__ out)
+                                                  const float *__restrict__ d, typename MapElem<OT>::raw *__restrict__ out)
 {
     const int lane = threadIdx.x & 63;
     const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -211,7 +213,7 @@ __global__ __launch_bounds__(256) void k_finalize(int64_t N, int D, const float 
         return;
     const float den = 1e-12f + d[g];
     const float *Fg = F + g * D;
-    float *og = out + g * D;
+    typename MapElem<OT>::raw *og = out + g * D;
     float ss = 0.f;
     for (int c = lane; c < D; c += 64) {
         const float xv = Fg[c] / den;
@@ -225,7 +227,7 @@ __global__ __launch_bounds__(256) void k_finalize(int64_t N, int D, const float 
         float xv = (Fg[c] / den) / nrm;
         if (xv != xv)
             xv = 0.f;
-        og[c] = xv;
+        og[c] = narrow<OT>(xv);
     }
 }
 
@@ -318,11 +320,17 @@ int launch_scatter(const Layout &L, const Ws &W, const ViewDev &V, const FeatMap
     return check_hip(hipGetLastError(), "scatter launch");
 }
 
-int launch_finalize(int64_t N, int D, const float *F, const float *d, float *out, hipStream_t s)
+int launch_finalize(int64_t N, int D, const float *F, const float *d, void *out, int ot, hipStream_t s)
 {
     if (N == 0)
         return GWBP_OK;
-    hipLaunchKernelGGL(k_finalize, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, N, D, F, d, out);
+    const dim3 grid((unsigned)((N + 3) / 4));
+    if (ot == GWBP_MAP_F16)
+        hipLaunchKernelGGL(k_finalize<GWBP_MAP_F16>, grid, dim3(256), 0, s, N, D, F, d, static_cast<unsigned short *>(out));
+    else if (ot == GWBP_MAP_BF16)
+        hipLaunchKernelGGL(k_finalize<GWBP_MAP_BF16>, grid, dim3(256), 0, s, N, D, F, d, static_cast<unsigned short *>(out));
+    else
+        hipLaunchKernelGGL(k_finalize<GWBP_MAP_F32>, grid, dim3(256), 0, s, N, D, F, d, static_cast<float *>(out));
     return check_hip(hipGetLastError(), "finalize launch");
 }
 

@@ -208,10 +208,12 @@ __global__ __launch_bounds__(kSpatialThreads) void k_spatial_knn(const float4 *_
 }
 
 // One wave per row g: out[g, :] = (sum over the valid j, in list order, of F[idx[g, j], :]) / (their number); lanes over
-// channels, four per lane.  An index outside [0, M) is skipped; a row with none left is zero.
-template <bool VEC>
+// channels, four per lane.  An index outside [0, M) is skipped; a row with none left is zero.  MT: the element type of F (a half
+// row is widened as it is loaded; the sums and out are fp32).
+template <int MT, bool VEC>
 __global__ __launch_bounds__(256) void k_neighbor_mean(int64_t N, int64_t M, int D, int k, const int32_t *__restrict__ idx,
-                                                       const float *__restrict__ F, int64_t ldf, float *__restrict__ out, int64_t ldo)
+                                                       const typename MapElem<MT>::raw *__restrict__ F, int64_t ldf,
+                                                       float *__restrict__ out, int64_t ldo)
 {
     const int lane = threadIdx.x & 63;
     const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -227,7 +229,7 @@ __global__ __launch_bounds__(256) void k_neighbor_mean(int64_t N, int64_t M, int
             if (id < 0 || id >= M)
                 continue;
             ++nv;
-            const float4 v = load4<VEC>(F + (int64_t)id * ldf, c, D);
+            const float4 v = load4t<MT, VEC>(F + (int64_t)id * ldf, c, D);
             acc.x += v.x;
             acc.y += v.y;
             acc.z += v.z;
@@ -292,7 +294,19 @@ int launch_spatial_knn(const float *sorted, const int32_t *cell_start, const flo
     return check_hip(hipGetLastError(), "spatial_knn launch");
 }
 
-int launch_neighbor_mean(int64_t N, int64_t M, int D, int k, const int32_t *idx, const float *F, int64_t ldf, float *out,
+template <int MT>
+static void launch_neighbor_mean_t(unsigned grid, hipStream_t s, int64_t N, int64_t M, int D, int k, const int32_t *idx, const void *Fv,
+                                   int64_t ldf, float *out, int64_t ldo)
+{
+    const typename MapElem<MT>::raw *F = static_cast<const typename MapElem<MT>::raw *>(Fv);
+    const bool vec = field_rows_vec(Fv, ldf, MT) && field_rows_vec(out, ldo, GWBP_MAP_F32);
+    if (vec)
+        hipLaunchKernelGGL((k_neighbor_mean<MT, true>), dim3(grid), dim3(256), 0, s, N, M, D, k, idx, F, ldf, out, ldo);
+    else
+        hipLaunchKernelGGL((k_neighbor_mean<MT, false>), dim3(grid), dim3(256), 0, s, N, M, D, k, idx, F, ldf, out, ldo);
+}
+
+int launch_neighbor_mean(int64_t N, int64_t M, int D, int k, const int32_t *idx, const void *F, int mt, int64_t ldf, float *out,
                          int64_t ldo, hipStream_t s)
 {
     if (N == 0)
@@ -300,11 +314,12 @@ int launch_neighbor_mean(int64_t N, int64_t M, int D, int k, const int32_t *idx,
     unsigned grid;
     if (int rc = grid_of("neighbor_mean", N, &grid, 4))
         return rc;
-    const bool vec = !(reinterpret_cast<uintptr_t>(F) & 15) && !(reinterpret_cast<uintptr_t>(out) & 15) && !(ldf & 3) && !(ldo & 3);
-    if (vec)
-        hipLaunchKernelGGL(k_neighbor_mean<true>, dim3(grid), dim3(256), 0, s, N, M, D, k, idx, F, ldf, out, ldo);
+    if (mt == GWBP_MAP_F16)
+        launch_neighbor_mean_t<GWBP_MAP_F16>(grid, s, N, M, D, k, idx, F, ldf, out, ldo);
+    else if (mt == GWBP_MAP_BF16)
+        launch_neighbor_mean_t<GWBP_MAP_BF16>(grid, s, N, M, D, k, idx, F, ldf, out, ldo);
     else
-        hipLaunchKernelGGL(k_neighbor_mean<false>, dim3(grid), dim3(256), 0, s, N, M, D, k, idx, F, ldf, out, ldo);
+        launch_neighbor_mean_t<GWBP_MAP_F32>(grid, s, N, M, D, k, idx, F, ldf, out, ldo);
     return check_hip(hipGetLastError(), "neighbor_mean launch");
 }
 

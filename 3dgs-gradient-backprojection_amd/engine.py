@@ -1268,6 +1268,20 @@ class Engine:
         self._call("gwbp_finalize", c_int64(F.shape[0]), F.shape[1], ptr(F), ptr(d), ptr(out), self._stream())
         return out
 
+    def finalize_typed(self, F, d, dtype, out=None):
+        """finalize() with the field written in dtype (torch.float32, torch.float16 or torch.bfloat16; gwbp_finalize_typed): the fp32
+        value of finalize() -- normalize(F / (1e-12 + d)), NaN -> 0 -- rounded once, to nearest even: bit for bit
+        finalize(F, d).to(dtype), without the fp32 field.  out (optional): a contiguous tensor of F's shape and that dtype; a half out
+        cannot be F.  (A method of its own: finalize()'s signature is part of the driver's recorded call schedule.)"""
+        if dtype not in MAP_TYPES:
+            raise GwbpError(f"finalize_typed: dtype must be float32, float16 or bfloat16, got {dtype}")
+        if out is None:
+            out = torch.empty(F.shape, dtype=dtype, device=F.device)
+        elif out.dtype != dtype or out.shape != F.shape or not out.is_contiguous():
+            raise GwbpError(f"finalize_typed: out must be a contiguous {dtype} tensor of shape {tuple(F.shape)}")
+        self._call("gwbp_finalize_typed", c_int64(F.shape[0]), F.shape[1], ptr(F), ptr(d), ptr(out), MAP_TYPES[dtype], self._stream())
+        return out
+
     # ---- counters ----------------------------------------------------------------------------------------
     def accumulate_stats(self, accum: torch.Tensor):
         """accum: uint8[32] device tensor holding a gwbp_stats struct (zero-initialised by the caller)."""

@@ -20,7 +20,7 @@ from typing import Iterator, Optional
 import torch
 
 from ._lib import GwbpError, check, lib, ptr
-from ._views import ld, rows, run
+from ._views import FIELD_TYPES, field_rows, ld, rows, run  # noqa: F401
 
 MAX_K = 16            # GWBP_PCA_MAX_K
 MAX_D = 2048          # GWBP_PCA_MAX_D
@@ -88,20 +88,20 @@ def _covariance(features: torch.Tensor):
     """(mean [D] float32, covariance [D, D] float64, both on the device) of the rows: gwbp_column_means + gwbp_centered_gram,
     the Gram over N - 1."""
     _check_sizes(features, None, 2)
-    x = rows(features, "features")
+    x, ft = field_rows(features, "features")
     n, d = x.shape
     need = C.c_size_t(0)
     check(lib().gwbp_pca_workspace_size(n, d, C.byref(need)), "gwbp_pca_workspace_size")
     ws = torch.empty(max(need.value, 8), dtype=torch.uint8, device=x.device)
     mean = torch.empty(d, dtype=torch.float32, device=x.device)
     gram = torch.empty(d, d, dtype=torch.float64, device=x.device)
-    run("gwbp_column_means", x.device, C.c_int64(n), d, ptr(x), C.c_int64(ld(x)), ptr(mean), ptr(ws), ws.numel())
-    run("gwbp_centered_gram", x.device, C.c_int64(n), d, ptr(x), C.c_int64(ld(x)), ptr(mean), ptr(gram), ptr(ws), ws.numel())
+    run("gwbp_column_means_typed", x.device, C.c_int64(n), d, ptr(x), ft, C.c_int64(ld(x)), ptr(mean), ptr(ws), ws.numel())
+    run("gwbp_centered_gram_typed", x.device, C.c_int64(n), d, ptr(x), ft, C.c_int64(ld(x)), ptr(mean), ptr(gram), ptr(ws), ws.numel())
     return mean, gram / float(n - 1)
 
 
 def _project(x: torch.Tensor, mean: torch.Tensor, components: torch.Tensor):
-    """(Y [N, k], minmax [ceil(N / 128), 2]) of gwbp_pca_project on checked rows."""
+    """(Y [N, k], minmax [ceil(N / 128), 2]) of gwbp_pca_project on checked rows (field_rows: in their own dtype)."""
     n, d = x.shape
     k = components.shape[0]
     if components.shape != (k, d) or mean.shape != (d,) or not 1 <= k <= MAX_K:
@@ -110,14 +110,16 @@ def _project(x: torch.Tensor, mean: torch.Tensor, components: torch.Tensor):
     components = components.to(device=x.device, dtype=torch.float32).contiguous()
     y = torch.empty(n, k, dtype=torch.float32, device=x.device)
     mm = torch.empty(-(-n // PROJECT_ROWS), 2, dtype=torch.float32, device=x.device)
-    run("gwbp_pca_project", x.device, C.c_int64(n), d, k, ptr(x), C.c_int64(ld(x)), ptr(mean), ptr(components), ptr(y), ptr(mm))
+    run("gwbp_pca_project_typed", x.device, C.c_int64(n), d, k, ptr(x), FIELD_TYPES[x.dtype], C.c_int64(ld(x)), ptr(mean), ptr(components),
+        ptr(y), ptr(mm))
     return y, mm
 
 
 def fit_pca(features: torch.Tensor, n_components: int = 3) -> PCABasis:
     """sklearn.decomposition.PCA(n_components).fit(features) on a [N, D] device tensor, N >= 2, D <= 2048, n_components <=
-    min(16, D).  features may have any row stride >= D and are read in place (float16 / bfloat16 are converted with .float(), a
-    tensor without unit stride inside a row with .contiguous()).  Two fits of one tensor are bit-equal.  NaN or infinite
+    min(16, D).  features may have any row stride >= D and are read in place (float16 / bfloat16 as stored: widened exactly in the
+    kernels, so the fit has the bits of the fit of features.float() without that copy; a tensor without unit stride inside a row is
+    copied with .contiguous()).  Two fits of one tensor are bit-equal.  NaN or infinite
     entries raise GwbpError.  A field without spread (all rows equal) gives variance 0, ratio 0 and unit-vector components."""
     _check_sizes(features, n_components, 2)
     mean, cov = _covariance(features)
@@ -128,7 +130,7 @@ def fit_pca(features: torch.Tensor, n_components: int = 3) -> PCABasis:
 def pca_transform(features: torch.Tensor, basis: PCABasis) -> torch.Tensor:
     """pca.transform(features): Y [N, k] = (features - mean) @ components.T in one pass over the rows (exact fp32)."""
     _check_sizes(features, None, 1)
-    return _project(rows(features, "features"), basis.mean, basis.components)[0]
+    return _project(field_rows(features, "features")[0], basis.mean, basis.components)[0]
 
 
 def pca_colors(features: torch.Tensor, basis: Optional[PCABasis] = None):
@@ -138,7 +140,7 @@ def pca_colors(features: torch.Tensor, basis: Optional[PCABasis] = None):
     if basis is None:
         basis = fit_pca(features, 3)
     _check_sizes(features, None, 1)
-    y, mm = _project(rows(features, "features"), basis.mean, basis.components)
+    y, mm = _project(field_rows(features, "features")[0], basis.mean, basis.components)
     lo_hi = torch.stack([mm[:, 0].min(), mm[:, 1].max()])
     colors = torch.empty_like(y)
     run("gwbp_pca_colors", y.device, C.c_int64(y.numel()), ptr(y), ptr(lo_hi), ptr(colors))
@@ -170,7 +172,7 @@ def _pca_frames(means, quats, scales, opacities, features, viewmats, K, width, h
     colors, lo, hi = pca_colors(features, basis)
     offset = None
     if mode == "renderings":
-        x = rows(features, "features")
+        x = field_rows(features, "features")[0]
         colors = _project(x, torch.zeros_like(basis.mean), basis.components)[0]
         offset = (basis.components.double() @ basis.mean.double()).float().to(x.device)
     Ks = K if K.dim() == 3 else K[None].expand(viewmats.shape[0], 3, 3)

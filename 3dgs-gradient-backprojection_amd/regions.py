@@ -35,7 +35,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from ._lib import GwbpError, ptr
-from ._views import ld, rows, run
+from ._views import FIELD_TYPES, field_rows, ld, rows, run  # noqa: F401
 from .cluster import class_prototypes, codebook_prompt_mask
 from .components import Components, as_group, dense_labels
 from .spatial import MAX_K as SPATIAL_MAX_K, as_points, spatial_knn
@@ -46,7 +46,7 @@ DEFAULT_SIM_MIN = 0.9   # a guess, not a tuned value: nothing is claimed about r
 
 
 def _field(features: torch.Tensor) -> torch.Tensor:
-    f = rows(features, "features")
+    f = field_rows(features, "features")[0]  # float16 / bfloat16 rows are read as stored (gwbp_neighbor_similarity_typed)
     if f.shape[1] > MAX_D:
         raise GwbpError(f"features: D = {f.shape[1]} exceeds {MAX_D}")
     if f.shape[0] >= 2 ** 31:
@@ -68,7 +68,8 @@ def _similarity(f: torch.Tensor, idx: torch.Tensor) -> Tuple[torch.Tensor, torch
     n, k = idx.shape
     sim = torch.empty(n, k, dtype=torch.float32, device=f.device)
     live = torch.empty(n, dtype=torch.int32, device=f.device)
-    run("gwbp_neighbor_similarity", f.device, C.c_int64(n), f.shape[1], k, ptr(idx), ptr(f), C.c_int64(ld(f)), ptr(sim), ptr(live))
+    run("gwbp_neighbor_similarity_typed", f.device, C.c_int64(n), f.shape[1], k, ptr(idx), ptr(f), FIELD_TYPES[f.dtype], C.c_int64(ld(f)),
+        ptr(sim), ptr(live))
     return sim, live
 
 

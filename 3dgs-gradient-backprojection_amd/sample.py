@@ -26,7 +26,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from ._lib import GwbpError, ptr
-from ._views import ld, require_device, rows, run
+from ._views import field_rows, ld, require_device, rows, run
 from .components import build_grid, plan_walk, r2_of
 from .regions import similarity_quantiles
 from .spatial import MAX_K, Grid, as_points, grid_args, grid_stats, sorted_keys, spatial_knn
@@ -160,15 +160,16 @@ def _list(idx, weights, dev):
 def neighbor_blend(features: torch.Tensor, idx: torch.Tensor, weights: torch.Tensor):
     """(out float32 [Q, D], wsum float32 [Q]): out[g] = sum_j w[g, j] features[idx[g, j]] / sum_j w[g, j], both sums chained in the
     list's order in fp32, over the entries with an index in [0, M) and w != 0 (the others are skipped, their rows not read); a
-    zero row and wsum 0 where none is left.  features [M, D] is read in place at any row stride >= D."""
-    f = rows(features, "features")
+    zero row and wsum 0 where none is left.  features [M, D] is read in place at any row stride >= D (float16 / bfloat16 as stored,
+    widened exactly as they are loaded; out is float32)."""
+    f, ft = field_rows(features, "features")
     idx, weights = _list(idx, weights, f.device)
     nq, k = idx.shape
     d = f.shape[1]
     out = torch.empty(nq, d, dtype=torch.float32, device=f.device)
     wsum = torch.empty(nq, dtype=torch.float32, device=f.device)
-    run("gwbp_neighbor_blend", f.device, C.c_int64(nq), C.c_int64(f.shape[0]), d, k, ptr(idx), ptr(weights), ptr(f), C.c_int64(ld(f)),
-        ptr(out), C.c_int64(d), ptr(wsum))
+    run("gwbp_neighbor_blend_typed", f.device, C.c_int64(nq), C.c_int64(f.shape[0]), d, k, ptr(idx), ptr(weights), ptr(f), ft,
+        C.c_int64(ld(f)), ptr(out), C.c_int64(d), ptr(wsum))
     return out, wsum
 
 
@@ -203,7 +204,7 @@ def sample_field(features: torch.Tensor, pg: PointGaussians, fallback: str = "no
         raise GwbpError(f"fallback must be 'none' or 'nearest', got {fallback!r}")
     if not isinstance(pg, PointGaussians):
         raise GwbpError("pg must be point_gaussians()'s result")
-    f = rows(features, "features")
+    f = field_rows(features, "features")[0]
     if f.shape[0] != pg.means.shape[0]:
         raise GwbpError(f"features must be [N = {pg.means.shape[0]}, D], got {tuple(f.shape)}")
     out, wsum = neighbor_blend(f, pg.idx, pg.weights)
@@ -215,7 +216,7 @@ def sample_field(features: torch.Tensor, pg: PointGaussians, fallback: str = "no
             ok = near[:, 0] >= 0
             if fallback_radius is not None:
                 ok &= dist[:, 0] <= float(fallback_radius)
-            out[need[ok]] = f[near[ok, 0].long()]
+            out[need[ok]] = f[near[ok, 0].long()].float()
     return (out, valid, wsum) if return_wsum else (out, valid)
 
 

@@ -21,7 +21,7 @@ from typing import Dict, Iterator, List, Optional, Tuple
 import torch
 
 from ._lib import GwbpError, ptr
-from ._views import front, ld, require_device, rows, run
+from ._views import field_rows, front, ld, require_device, rows, run
 from ._views import raster_kw as merged_raster_kw
 from .pruning import PER_GAUSSIAN
 
@@ -42,7 +42,7 @@ def _prompts(prompts, d: int, device) -> torch.Tensor:
 
 
 def _query(features, prompts, n_pos: int, threshold, normalize: bool, want_mask: bool, want_scores: bool):
-    x = rows(features, "features")
+    x, ft = field_rows(features, "features")  # float16 / bfloat16 fields are read as stored: no float32 copy
     n, d = x.shape
     if d > MAX_D:
         raise GwbpError(f"D must be in [1, {MAX_D}], got {d}")
@@ -55,8 +55,8 @@ def _query(features, prompts, n_pos: int, threshold, normalize: bool, want_mask:
     thr = C.byref(C.c_float(float(threshold))) if threshold is not None else None
     mask = torch.empty(n, dtype=torch.uint8, device=x.device) if want_mask else None
     scores = torch.empty(n, p, dtype=torch.float32, device=x.device) if want_scores else None
-    run("gwbp_prompt_scores", x.device, C.c_int64(n), d, p, n_pos, ptr(x), C.c_int64(ld(x)), ptr(t), int(bool(normalize)), thr,
-         ptr(mask), ptr(scores))
+    run("gwbp_prompt_scores_typed", x.device, C.c_int64(n), d, p, n_pos, ptr(x), ft, C.c_int64(ld(x)), ptr(t), int(bool(normalize)),
+        thr, ptr(mask), ptr(scores))
     return mask, scores
 
 

@@ -21,7 +21,7 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 
 from ._lib import GwbpError, ptr
-from ._views import ld, rows, run
+from ._views import field_rows, ld, rows, run
 from .transfer import narrow_source_labels, vote_labels
 
 MAX_K = 32
@@ -291,8 +291,9 @@ def remove_outliers(means: torch.Tensor, mask: Optional[torch.Tensor] = None, k:
 
 def neighbor_mean(features: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """out[i, :] = the mean of features[idx[i, j], :] over the valid j (idx >= 0), summed in the list's order in fp32; a zero row
-    where none is valid.  features [M, D] is read in place at any row stride >= D; the result is a new [N, D] tensor."""
-    f = rows(features, "features")
+    where none is valid.  features [M, D] is read in place at any row stride >= D (float16 / bfloat16 as stored, widened exactly as
+    they are loaded); the result is a new float32 [N, D] tensor."""
+    f, ft = field_rows(features, "features")
     if not torch.is_tensor(idx) or not idx.is_cuda or idx.dtype != torch.int32 or idx.dim() != 2 or idx.device != f.device:
         raise GwbpError("idx must be an int32 [N, k] tensor on the device of the features")
     idx = idx.contiguous()
@@ -301,8 +302,8 @@ def neighbor_mean(features: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
         raise GwbpError(f"idx must have 1 .. {MAX_K} columns, got {k}")
     d = f.shape[1]
     out = torch.empty(n, d, dtype=torch.float32, device=f.device)
-    run("gwbp_neighbor_mean", f.device, C.c_int64(n), C.c_int64(f.shape[0]), d, k, ptr(idx), ptr(f), C.c_int64(ld(f)), ptr(out),
-        C.c_int64(d))
+    run("gwbp_neighbor_mean_typed", f.device, C.c_int64(n), C.c_int64(f.shape[0]), d, k, ptr(idx), ptr(f), ft, C.c_int64(ld(f)),
+        ptr(out), C.c_int64(d))
     return out
 
 

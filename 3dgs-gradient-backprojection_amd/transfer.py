@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from ._lib import GwbpError, ptr
-from ._views import ld, rows, run
+from ._views import field_rows, ld, rows, run
 
 MAX_K = 32
 
@@ -28,9 +28,10 @@ def knn_search(features: torch.Tensor, sources: torch.Tensor, k: int):
     descending, then index ascending; NaN scores come last.  Exact fp32 (one fused multiply-add chain per score).
 
     features / sources may have any row stride >= D (a field still in padded storage, a column slice of a wider tensor) and are
-    read in place; a tensor whose stride within a row is not 1 is copied with .contiguous(); float16 / bfloat16 inputs are
-    converted with .float().  1 <= k <= 32, k <= M."""
-    q, s = rows(features, "features"), rows(sources, "sources")
+    read in place; a tensor whose stride within a row is not 1 is copied with .contiguous().  float16 / bfloat16 FEATURES are read
+    as stored and widened exactly in the kernel (the result has the bits of the search on features.float(), and no such copy is
+    made); float16 / bfloat16 sources, the small operand, are converted with .float().  1 <= k <= 32, k <= M."""
+    (q, ft), s = field_rows(features, "features"), rows(sources, "sources")
     if q.shape[1] != s.shape[1]:
         raise GwbpError(f"features have D = {q.shape[1]}, sources D = {s.shape[1]}")
     if q.device != s.device:
@@ -43,8 +44,8 @@ def knn_search(features: torch.Tensor, sources: torch.Tensor, k: int):
     n, m, d = q.shape[0], s.shape[0], q.shape[1]
     idx = torch.empty(n, k, dtype=torch.int32, device=q.device)
     score = torch.empty(n, k, dtype=torch.float32, device=q.device)
-    run("gwbp_knn_search", q.device, C.c_int64(n), m, d, k, ptr(q), C.c_int64(ld(q)), ptr(s), C.c_int64(ld(s)), ptr(idx),
-         ptr(score))
+    run("gwbp_knn_search_typed", q.device, C.c_int64(n), m, d, k, ptr(q), ft, C.c_int64(ld(q)), ptr(s), C.c_int64(ld(s)), ptr(idx),
+        ptr(score))
     return score, idx
 
 

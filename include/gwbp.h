@@ -317,7 +317,8 @@ GWBP_API int gwbp_scatter_bilinear(const gwbp_caps *caps, void *workspace, size_
                           int32_t lr_w, const int32_t *y0, const float *ly, const int32_t *x0, const float *lx,
                           float scale_f, float scale_d, float *F, float *d, void *stream);
 
-/* Element type of the feature map of the typed scatter entry points below. */
+/* Element type of the feature map of the typed scatter entry points below, and of a finished field of the *_typed entry points that
+ * read one (gwbp_finalize_typed writes one). */
 #define GWBP_MAP_F32 0  /* float32 */
 #define GWBP_MAP_F16 1  /* IEEE binary16 */
 #define GWBP_MAP_BF16 2 /* bfloat16 (the upper half of a float32) */
@@ -535,6 +536,13 @@ GWBP_API int gwbp_encode_map(const float *feats, int64_t fs_y, int64_t fs_x, int
 /* backproject.py:63,166-169: out = normalize(F / (1e-12 + d)), NaN -> 0.  out may alias F. */
 GWBP_API int gwbp_finalize(int64_t N, int32_t D, const float *F, const float *d, float *out, void *stream);
 
+/* gwbp_finalize with a typed OUTPUT: out holds N x D elements of `out_type` (GWBP_MAP_F32 / _F16 / _BF16), dense.  An unknown out_type
+ * is GWBP_EINVAL, checked before anything else; an out that is not aligned to its element is GWBP_EINVAL before any HIP call.
+ * GWBP_MAP_F32 does exactly what gwbp_finalize does (which is a call of this one).  For a half type the fp32 value gwbp_finalize
+ * computes (NaN -> 0 included) is rounded ONCE, to nearest even, subnormal fp16 results kept: out equals the fp32 result converted by
+ * torch's .to(dtype), bit for bit.  F and d stay fp32.  A half out cannot alias F (GWBP_EINVAL). */
+GWBP_API int gwbp_finalize_typed(int64_t N, int32_t D, const float *F, const float *d, void *out, int32_t out_type, void *stream);
+
 /* Inner-product k-nearest-neighbour search on a finished field (faiss IndexFlatIP.search; the reference's transfer_affordance,
  * affordance_transfer/demo_affordance_transfer.py:1377-1396): for every query row Q[g * ldq + 0..D-1], g < N, the k source rows
  * S[j * lds_ + 0..D-1], j < M, of largest inner product.  idx[N, k] (int32) and score[N, k] (fp32) are dense; each row is sorted
@@ -549,6 +557,16 @@ GWBP_API int gwbp_finalize(int64_t N, int32_t D, const float *F, const float *d,
  * GWBP_EINVAL before any HIP call: N < 0, M < 1, D < 1, k outside [1, 32], k > M, a stride below D, a null or misaligned pointer. */
 GWBP_API int gwbp_knn_search(int64_t N, int32_t M, int32_t D, int32_t k, const float *Q, int64_t ldq, const float *S,
                              int64_t lds_, int32_t *idx, float *score, void *stream);
+
+/* gwbp_knn_search with a typed QUERY field Q: `field_type` (GWBP_MAP_F32 / _F16 / _BF16) is the element type of that one operand and its row stride counts
+ * ELEMENTS.  An unknown field_type is GWBP_EINVAL, checked before anything else; a field pointer that is not aligned to its element
+ * (4 B, 2 B) is GWBP_EINVAL before any HIP call, as are the untyped function's own invalid cases.  GWBP_MAP_F32 does exactly what
+ * the untyped function does (which is a call of this one).  A half field is widened to fp32 as it is loaded or staged -- exact --
+ * so every result has the BITS the untyped function gives on the fp32 copy of the field, and no such copy is made.  Half rows whose
+ * address is 8-B aligned and whose stride is a multiple of 4 elements move with one 8-B load per four channels, others element by
+ * element, with the same bits. The sources S, idx and score stay fp32 / int32. */
+GWBP_API int gwbp_knn_search_typed(int64_t N, int32_t M, int32_t D, int32_t k, const void *Q, int32_t field_type, int64_t ldq,
+                                   const float *S, int64_t lds_, int32_t *idx, float *score, void *stream);
 
 /* The majority label of each row of gwbp_knn_search's idx[N, k]: label_out[g] = the most frequent of labels[idx[g, 0..k-1]], the
  * SMALLEST label among equally frequent ones (np.bincount(row).argmax()).  labels: int32 [M]; a label outside [0, num_classes)
@@ -599,6 +617,16 @@ GWBP_API int gwbp_spatial_knn(int64_t n, const float *sorted, const int32_t *cel
  * out == features. */
 GWBP_API int gwbp_neighbor_mean(int64_t n, int64_t m, int32_t D, int32_t k, const int32_t *idx, const float *features,
                                 int64_t ldf, float *out, int64_t ldo, void *stream);
+
+/* gwbp_neighbor_mean with a typed field `features`: `field_type` (GWBP_MAP_F32 / _F16 / _BF16) is the element type of that one operand and its row stride counts
+ * ELEMENTS.  An unknown field_type is GWBP_EINVAL, checked before anything else; a field pointer that is not aligned to its element
+ * (4 B, 2 B) is GWBP_EINVAL before any HIP call, as are the untyped function's own invalid cases.  GWBP_MAP_F32 does exactly what
+ * the untyped function does (which is a call of this one).  A half field is widened to fp32 as it is loaded or staged -- exact --
+ * so every result has the BITS the untyped function gives on the fp32 copy of the field, and no such copy is made.  Half rows whose
+ * address is 8-B aligned and whose stride is a multiple of 4 elements move with one 8-B load per four channels, others element by
+ * element, with the same bits. out stays fp32. */
+GWBP_API int gwbp_neighbor_mean_typed(int64_t n, int64_t m, int32_t D, int32_t k, const int32_t *idx, const void *features,
+                                      int32_t field_type, int64_t ldf, float *out, int64_t ldo, void *stream);
 
 /* ---- Radius components: which points form one object (DBSCAN with a deterministic border rule; PCL's Euclidean cluster extraction
  * at min_points = 1) on the grid of the spatial search above ------------------------------------------------------------------------
@@ -682,6 +710,16 @@ GWBP_API int gwbp_components_flatten(int64_t n, const int32_t *count, int32_t mi
 #define GWBP_REGIONS_MAX_K 64
 GWBP_API int gwbp_neighbor_similarity(int64_t n, int32_t D, int32_t k, const int32_t *idx, const float *features, int64_t ldf,
                                       float *sim, int32_t *live, void *stream);
+
+/* gwbp_neighbor_similarity with a typed field `features` (own and neighbour rows): `field_type` (GWBP_MAP_F32 / _F16 / _BF16) is the element type of that one operand and its row stride counts
+ * ELEMENTS.  An unknown field_type is GWBP_EINVAL, checked before anything else; a field pointer that is not aligned to its element
+ * (4 B, 2 B) is GWBP_EINVAL before any HIP call, as are the untyped function's own invalid cases.  GWBP_MAP_F32 does exactly what
+ * the untyped function does (which is a call of this one).  A half field is widened to fp32 as it is loaded or staged -- exact --
+ * so every result has the BITS the untyped function gives on the fp32 copy of the field, and no such copy is made.  Half rows whose
+ * address is 8-B aligned and whose stride is a multiple of 4 elements move with one 8-B load per four channels, others element by
+ * element, with the same bits. sim and live stay fp32 / int32. */
+GWBP_API int gwbp_neighbor_similarity_typed(int64_t n, int32_t D, int32_t k, const int32_t *idx, const void *features,
+                                            int32_t field_type, int64_t ldf, float *sim, int32_t *live, void *stream);
 GWBP_API int gwbp_edge_union(int64_t n, int32_t k, const int32_t *idx, const float *sim, const int32_t *live, const float *dist,
                              const int32_t *group, float sim_min, float max_dist, int32_t *count, int32_t *parent, int32_t *status,
                              void *stream);
@@ -741,6 +779,17 @@ GWBP_API int gwbp_point_gaussians(int64_t n, const float *sorted, const int32_t 
                                   int32_t *n_contrib, int32_t *visited, void *stream);
 GWBP_API int gwbp_neighbor_blend(int64_t q, int64_t m, int32_t D, int32_t k, const int32_t *idx, const float *w, const float *features,
                                  int64_t ldf, float *out, int64_t ldo, float *wsum, void *stream);
+
+/* gwbp_neighbor_blend with a typed field `features`: `field_type` (GWBP_MAP_F32 / _F16 / _BF16) is the element type of that one operand and its row stride counts
+ * ELEMENTS.  An unknown field_type is GWBP_EINVAL, checked before anything else; a field pointer that is not aligned to its element
+ * (4 B, 2 B) is GWBP_EINVAL before any HIP call, as are the untyped function's own invalid cases.  GWBP_MAP_F32 does exactly what
+ * the untyped function does (which is a call of this one).  A half field is widened to fp32 as it is loaded or staged -- exact --
+ * so every result has the BITS the untyped function gives on the fp32 copy of the field, and no such copy is made.  Half rows whose
+ * address is 8-B aligned and whose stride is a multiple of 4 elements move with one 8-B load per four channels, others element by
+ * element, with the same bits. The weights w, out and wsum stay fp32. */
+GWBP_API int gwbp_neighbor_blend_typed(int64_t q, int64_t m, int32_t D, int32_t k, const int32_t *idx, const float *w,
+                                       const void *features, int32_t field_type, int64_t ldf, float *out, int64_t ldo, float *wsum,
+                                       void *stream);
 GWBP_API int gwbp_weighted_vote(int64_t q, int64_t m, int32_t k, const int32_t *idx, const float *w, const int32_t *labels,
                                 int32_t num_classes, int32_t *out_label, float *out_share, void *stream);
 
@@ -767,6 +816,16 @@ GWBP_API int gwbp_pca_workspace_size(int64_t N, int32_t D, size_t *bytes);
 GWBP_API int gwbp_column_means(int64_t N, int32_t D, const float *X, int64_t ldx, float *mean_out, void *workspace,
                                size_t workspace_bytes, void *stream);
 
+/* gwbp_column_means with a typed field X: `field_type` (GWBP_MAP_F32 / _F16 / _BF16) is the element type of that one operand and its row stride counts
+ * ELEMENTS.  An unknown field_type is GWBP_EINVAL, checked before anything else; a field pointer that is not aligned to its element
+ * (4 B, 2 B) is GWBP_EINVAL before any HIP call, as are the untyped function's own invalid cases.  GWBP_MAP_F32 does exactly what
+ * the untyped function does (which is a call of this one).  A half field is widened to fp32 as it is loaded or staged -- exact --
+ * so every result has the BITS the untyped function gives on the fp32 copy of the field, and no such copy is made.  Half rows whose
+ * address is 8-B aligned and whose stride is a multiple of 4 elements move with one 8-B load per four channels, others element by
+ * element, with the same bits. mean_out stays fp32, the workspace is the untyped function's. */
+GWBP_API int gwbp_column_means_typed(int64_t N, int32_t D, const void *X, int32_t field_type, int64_t ldx, float *mean_out,
+                                     void *workspace, size_t workspace_bytes, void *stream);
+
 /* gram_out[a * D + b] (float64, dense [D, D], symmetric) = sum_g (X[g, a] - mean[a]) (X[g, b] - mean[b]).  The rows are cut into
  * slices that depend on (N, D) alone; within a slice every entry of the upper triangle is one chain of fp32 fused multiply-adds
  * over the rows (the fp32 matrix cores; no reduced-precision operand); the slices are added in ascending order in float64 and
@@ -774,12 +833,32 @@ GWBP_API int gwbp_column_means(int64_t N, int32_t D, const float *X, int64_t ldx
 GWBP_API int gwbp_centered_gram(int64_t N, int32_t D, const float *X, int64_t ldx, const float *mean, double *gram_out,
                                 void *workspace, size_t workspace_bytes, void *stream);
 
+/* gwbp_centered_gram with a typed field X: `field_type` (GWBP_MAP_F32 / _F16 / _BF16) is the element type of that one operand and its row stride counts
+ * ELEMENTS.  An unknown field_type is GWBP_EINVAL, checked before anything else; a field pointer that is not aligned to its element
+ * (4 B, 2 B) is GWBP_EINVAL before any HIP call, as are the untyped function's own invalid cases.  GWBP_MAP_F32 does exactly what
+ * the untyped function does (which is a call of this one).  A half field is widened to fp32 as it is loaded or staged -- exact --
+ * so every result has the BITS the untyped function gives on the fp32 copy of the field, and no such copy is made.  Half rows whose
+ * address is 8-B aligned and whose stride is a multiple of 4 elements move with one 8-B load per four channels, others element by
+ * element, with the same bits. mean stays fp32, gram_out float64, the workspace is the untyped function's. */
+GWBP_API int gwbp_centered_gram_typed(int64_t N, int32_t D, const void *X, int32_t field_type, int64_t ldx, const float *mean,
+                                      double *gram_out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Y[g * k + j] = sum_c (X[g, c] - mean[c]) components[j * D + c], j < k <= GWBP_PCA_MAX_K: one pass over X, one chain of fp32
  * fused multiply-adds per entry in an order that depends only on D.  minmax_partials[2 * w], [2 * w + 1], w < ceil(N /
  * GWBP_PCA_PROJECT_ROWS): the smallest and the largest Y entry of rows w * GWBP_PCA_PROJECT_ROWS ...; min and max are exact, so
  * the smallest / largest of them is Y's (NaN entries are skipped).  N >= 1 here. */
 GWBP_API int gwbp_pca_project(int64_t N, int32_t D, int32_t k, const float *X, int64_t ldx, const float *mean,
                               const float *components, float *Y, float *minmax_partials, void *stream);
+
+/* gwbp_pca_project with a typed field X: `field_type` (GWBP_MAP_F32 / _F16 / _BF16) is the element type of that one operand and its row stride counts
+ * ELEMENTS.  An unknown field_type is GWBP_EINVAL, checked before anything else; a field pointer that is not aligned to its element
+ * (4 B, 2 B) is GWBP_EINVAL before any HIP call, as are the untyped function's own invalid cases.  GWBP_MAP_F32 does exactly what
+ * the untyped function does (which is a call of this one).  A half field is widened to fp32 as it is loaded or staged -- exact --
+ * so every result has the BITS the untyped function gives on the fp32 copy of the field, and no such copy is made.  Half rows whose
+ * address is 8-B aligned and whose stride is a multiple of 4 elements move with one 8-B load per four channels, others element by
+ * element, with the same bits. mean, components, Y and minmax_partials stay fp32. */
+GWBP_API int gwbp_pca_project_typed(int64_t N, int32_t D, int32_t k, const void *X, int32_t field_type, int64_t ldx, const float *mean,
+                                    const float *components, float *Y, float *minmax_partials, void *stream);
 
 /* colors[e] = (Y[e] - lo) / (hi - lo), e < n, with lo = lo_hi[0], hi = lo_hi[1] read from DEVICE memory (one pair for every
  * channel: visualize_pca.py takes np.min / np.max over all three); hi == lo gives 0.5 everywhere.  colors may alias Y. */
@@ -804,6 +883,16 @@ GWBP_API int gwbp_pca_colors(int64_t n, const float *Y, const float *lo_hi, floa
 GWBP_API int gwbp_kmeans_assign(int64_t N, int32_t K, int32_t D, const float *X, int64_t ldx, const float *C, int64_t ldc,
                                 const float *b, int32_t *label, float *best, void *stream);
 
+/* gwbp_kmeans_assign with a typed field X: `field_type` (GWBP_MAP_F32 / _F16 / _BF16) is the element type of that one operand and its row stride counts
+ * ELEMENTS.  An unknown field_type is GWBP_EINVAL, checked before anything else; a field pointer that is not aligned to its element
+ * (4 B, 2 B) is GWBP_EINVAL before any HIP call, as are the untyped function's own invalid cases.  GWBP_MAP_F32 does exactly what
+ * the untyped function does (which is a call of this one).  A half field is widened to fp32 as it is loaded or staged -- exact --
+ * so every result has the BITS the untyped function gives on the fp32 copy of the field, and no such copy is made.  Half rows whose
+ * address is 8-B aligned and whose stride is a multiple of 4 elements move with one 8-B load per four channels, others element by
+ * element, with the same bits. The centroids C, the bias b, label and best stay fp32 / int32. */
+GWBP_API int gwbp_kmeans_assign_typed(int64_t N, int32_t K, int32_t D, const void *X, int32_t field_type, int64_t ldx, const float *C,
+                                      int64_t ldc, const float *b, int32_t *label, float *best, void *stream);
+
 /* Bytes of device workspace gwbp_cluster_sums needs: the per-run partial sums, (min(N, ceil(N / GWBP_CLUSTER_RUN) + K)) x (D + 1)
  * float64, plus K + 1 int64.  The workspace carries nothing between calls.  GWBP_EINVAL: N < 0, K or D out of range, null bytes. */
 GWBP_API int gwbp_cluster_workspace_size(int64_t N, int32_t D, int32_t K, size_t *bytes);
@@ -825,6 +914,18 @@ GWBP_API int gwbp_cluster_sums(int64_t N, int32_t D, int32_t K, const float *X, 
                                const int64_t *start, double *sums, double *wsum, void *workspace, size_t workspace_bytes,
                                void *stream);
 
+/* gwbp_cluster_sums with a typed field X: `field_type` (GWBP_MAP_F32 / _F16 / _BF16) is the element type of that one operand and its row stride counts
+ * ELEMENTS.  An unknown field_type is GWBP_EINVAL, checked before anything else; a field pointer that is not aligned to its element
+ * (4 B, 2 B) is GWBP_EINVAL before any HIP call, as are the untyped function's own invalid cases.  GWBP_MAP_F32 does exactly what
+ * the untyped function does (which is a call of this one).  A half field is widened to fp32 as it is loaded or staged -- exact --
+ * so every result has the BITS the untyped function gives on the fp32 copy of the field, and no such copy is made.  Half rows whose
+ * address is 8-B aligned and whose stride is a multiple of 4 elements move with one 8-B load per four channels, others element by
+ * element, with the same bits. The weights w stay fp32, sums and wsum float64, the workspace is the untyped
+ * function's. */
+GWBP_API int gwbp_cluster_sums_typed(int64_t N, int32_t D, int32_t K, const void *X, int32_t field_type, int64_t ldx, const float *w,
+                                     const int64_t *order, const int64_t *start, double *sums, double *wsum, void *workspace,
+                                     size_t workspace_bytes, void *stream);
+
 /* ---- questions asked of a finished field (the reference's segment.py, segment_compressed.py, click_and_segment.py) ---------------
  * Scores of every row of X[g * ldx + 0..D-1], g < N, against P prompt vectors prompts[j * D + 0..D-1] (dense), and the 3-D mask of
  * get_mask3d_lseg, in ONE pass over X; no workspace, no view.
@@ -844,6 +945,17 @@ GWBP_API int gwbp_cluster_sums(int64_t N, int32_t D, int32_t K, const float *X, 
 #define GWBP_QUERY_MAX_P 32
 GWBP_API int gwbp_prompt_scores(int64_t N, int32_t D, int32_t P, int32_t n_pos, const float *X, int64_t ldx, const float *prompts,
                                 int32_t normalize, const float *threshold_host, uint8_t *mask, float *scores, void *stream);
+
+/* gwbp_prompt_scores with a typed field X: `field_type` (GWBP_MAP_F32 / _F16 / _BF16) is the element type of that one operand and its row stride counts
+ * ELEMENTS.  An unknown field_type is GWBP_EINVAL, checked before anything else; a field pointer that is not aligned to its element
+ * (4 B, 2 B) is GWBP_EINVAL before any HIP call, as are the untyped function's own invalid cases.  GWBP_MAP_F32 does exactly what
+ * the untyped function does (which is a call of this one).  A half field is widened to fp32 as it is loaded or staged -- exact --
+ * so every result has the BITS the untyped function gives on the fp32 copy of the field, and no such copy is made.  Half rows whose
+ * address is 8-B aligned and whose stride is a multiple of 4 elements move with one 8-B load per four channels, others element by
+ * element, with the same bits. The prompts, the threshold, mask and scores stay fp32 / uint8. */
+GWBP_API int gwbp_prompt_scores_typed(int64_t N, int32_t D, int32_t P, int32_t n_pos, const void *X, int32_t field_type, int64_t ldx,
+                                      const float *prompts, int32_t normalize, const float *threshold_host, uint8_t *mask,
+                                      float *scores, void *stream);
 
 /* The field rendered at M pixels only (click_and_segment.py:241-254 renders all [H, W, D + 1] values to read one pixel's): needs
  * gwbp_project (or gwbp_project_camera) + gwbp_bin_sort of the view in the workspace, like gwbp_render_pixels; no weight store.

@@ -95,7 +95,15 @@ def add_later_options(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
                          "instead of the dense [N, K] field (create_sparse_label_field: N * (12 S + 16) bytes whatever K): writes "
                          "sparse_label_field.pt = {'ids': int32 [N, S] (-1 empty), 'fractions': float32 [N, S], 'spill_fraction': "
                          "[N], 'total': int64 [N], 'num_classes', 'slots', 'stats'}, largest share first.  One process")
+    ap.add_argument("--field-dtype", choices=["fp32", "fp16", "bf16"], default="fp32",
+                    help="element type of the feature field that is written (features_<feature>.pt; not label fields): fp16 / bf16 "
+                         "halve the file and the memory of everything that loads it.  The accumulators stay fp32 and the finalise "
+                         "rounds once; run_segment.py, run_pca.py, run_cluster.py, run_transfer.py, run_regions.py, run_clean.py and "
+                         "run_sample.py read such a field as it is stored")
     return ap
+
+
+FIELD_DTYPES = {"fp32": torch.float32, "fp16": torch.float16, "bf16": torch.bfloat16}
 
 
 def camera_warnings(cam, camera_model_arg):
@@ -336,12 +344,13 @@ def main(argv=None):
         # the feature field of the maps table[labels], built from the masks and their embeddings (features_<feature>.pt)
         out, F, d, stats = gsbp_amd.create_mask_feature_field(means, quats, scales, opac, viewmats, K, W, H, mask_fn, dim,
                                                               reduction=reduction, upsample=label_upsample,
-                                                              return_partials=True, pixel_weight_fn=pixel_weight_fn, **cam_kw)
+                                                              return_partials=True, pixel_weight_fn=pixel_weight_fn,
+                                                              out_dtype=FIELD_DTYPES[args.field_dtype], **cam_kw)
     else:
         out, F, d, stats = gsbp_amd.create_feature_field(means, quats, scales, opac, viewmats, K, W, H, feature_fn, dim,
                                                          reduction=reduction, encoder=encoder, return_partials=True,
                                                          verbose=True, upsample=upsample, pixel_weight_fn=pixel_weight_fn,
-                                                         **cam_kw)
+                                                         out_dtype=FIELD_DTYPES[args.field_dtype], **cam_kw)
     if args.prune_by_product and not args.no_prune:
         # "the mask comes free from the fused kernel" -- d is the all-reduced denominator of every Gaussian,
         # identical on every rank

@@ -105,7 +105,7 @@ def main(argv=None) -> int:
     scene = cli.load_scene(args, dev).first_views(args.max_views)
     means = scene.gauss[0]
     n = means.shape[0]
-    feats = _load(args.features, ("features", "field")).float() if args.features else regions.synthetic_regions(means)[0]
+    feats = _load(args.features, ("features", "field")) if args.features else regions.synthetic_regions(means)[0]
     if feats.dim() != 2 or feats.shape[0] != n:
         raise SystemExit(f"--features: shape {tuple(feats.shape)} for {n} Gaussians")
     feats = feats.to(dev)

@@ -137,7 +137,7 @@ def main(argv=None) -> int:
     feats = labels = None
     num_classes = args.num_classes
     if args.features:
-        feats = _load(args.features, ("features", "field")).float()
+        feats = _load(args.features, ("features", "field"))  # (fp16 / bf16 fields are sampled as stored)
     if args.labels:
         labels = _load(args.labels, ("labels",))
     if args.synthetic and feats is None and labels is None:
