@@ -1426,8 +1426,8 @@ int launch_blend(const Layout &L, const Ws &W, const ViewDev &V, float *alphas, 
         int n_cu = 0;
         int rc = device_cus(&n_cu);
         const int lds_max = kEncMaxK * kFusedCh * 4 + kPcRing * kPcTileFloats * 4 + 64;
-        if (rc || (rc = pw ? ensure_dynamic_lds(reinterpret_cast<const void *>(k_blend<kFusedPC, kPcWaves, true>), lds_max, 15)
-                           : ensure_dynamic_lds(reinterpret_cast<const void *>(k_blend<kFusedPC, kPcWaves, false>), lds_max, 14)))
+        if (rc || (rc = pw ? ensure_dynamic_lds(reinterpret_cast<const void *>(k_blend<kFusedPC, kPcWaves, true>), lds_max)
+                           : ensure_dynamic_lds(reinterpret_cast<const void *>(k_blend<kFusedPC, kPcWaves, false>), lds_max)))
             return rc;
         fu.pc_queue = W.shards + kPcTileCounter;
         GWBP_LAUNCH(k_blend<kFusedPC GWBP_COMMA kPcWaves, dim3(n_cu), dim3(64 * kPcWaves), lds, V, W.tile_offsets, W.vals[fin], W.g2d,

@@ -5,6 +5,9 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <map>
+#include <mutex>
+
 #include "gwbp_dev.h"
 #include "mask_features.h"
 
@@ -31,10 +34,14 @@ int check_hip(hipError_t e, const char *what)
 
 namespace {
 struct DevCache {
-    int n_cu;
-    unsigned long long lds_mask;
+    int n_cu;                         // benign race: every writer stores the same value
+    std::map<const void *, int> lds;  // kernel -> the largest dynamic-LDS limit set on this device (under g_lds_mutex)
 };
-DevCache g_dev[64]; // benign races: every writer stores the same value
+DevCache g_dev[64];
+// One lock for every device's map: launches come from a few host threads, so it is uncontended, and a lookup costs nanoseconds beside
+// a launch's microseconds.  It is held across hipFuncSetAttribute on purpose, so that two threads never set one kernel's limit at once
+// and the recorded size is the one in force.
+std::mutex g_lds_mutex;
 DevCache *dev_cache()
 {
     int dev = 0;
@@ -60,17 +67,19 @@ int device_cus(int *n_cu)
     return GWBP_OK;
 }
 
-int ensure_dynamic_lds(const void *func, int bytes, int slot)
+int ensure_dynamic_lds(const void *func, int bytes)
 {
     DevCache *c = dev_cache();
     if (!c)
         return set_error(GWBP_EINVAL, "cannot query the current device");
-    if (c->lds_mask & (1ull << slot))
+    std::lock_guard<std::mutex> lock(g_lds_mutex);
+    const auto it = c->lds.find(func);
+    if (it != c->lds.end() && bytes <= it->second)
         return GWBP_OK;
     const int rc = check_hip(hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, bytes),
                              "dynamic LDS attribute");
     if (rc == GWBP_OK)
-        c->lds_mask |= 1ull << slot;
+        c->lds[func] = bytes;
     return rc;
 }
 

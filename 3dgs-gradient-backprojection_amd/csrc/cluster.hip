@@ -251,76 +251,45 @@ __global__ __launch_bounds__(256) void k_cluster_reduce(int D, int64_t slots, co
 
 } // namespace
 
-// slot: the first of the instantiation pair's two bits of ensure_dynamic_lds (vector, then element loads)
-template <int MT>
-static int launch_kmeans_assign_t(int slot, int64_t N, int K, int D, const void *Xv, int64_t ldx, const float *C, int64_t ldc,
-                                  const float *bias, int32_t *label, float *best, hipStream_t s)
-{
-    const typename MapElem<MT>::raw *X = static_cast<const typename MapElem<MT>::raw *>(Xv);
-    const bool vec = field_rows_vec(Xv, ldx, MT) && field_rows_vec(C, ldc, GWBP_MAP_F32);
-    const int lds = 2 * kKnnStage * (int)sizeof(float);
-    const void *fn =
-        vec ? reinterpret_cast<const void *>(k_kmeans_assign<MT, true>) : reinterpret_cast<const void *>(k_kmeans_assign<MT, false>);
-    const int rc = ensure_dynamic_lds(fn, lds, vec ? slot : slot + 1);
-    if (rc)
-        return rc;
-    const int64_t grid = (N + kKnnQ - 1) / kKnnQ;
-    if (grid > 0x7FFFFFFF)
-        return set_error(GWBP_EINVAL, "kmeans_assign: N = %lld needs more than 2^31 - 1 workgroups", (long long)N);
-    if (vec)
-        hipLaunchKernelGGL((k_kmeans_assign<MT, true>), dim3((unsigned)grid), dim3(kKnnThreads), lds, s, N, K, D, X, ldx, C, ldc, bias,
-                           label, best);
-    else
-        hipLaunchKernelGGL((k_kmeans_assign<MT, false>), dim3((unsigned)grid), dim3(kKnnThreads), lds, s, N, K, D, X, ldx, C, ldc, bias,
-                           label, best);
-    return check_hip(hipGetLastError(), "kmeans_assign launch");
-}
-
 int launch_kmeans_assign(int64_t N, int K, int D, const void *X, int mt, int64_t ldx, const float *C, int64_t ldc, const float *bias,
                          int32_t *label, float *best, hipStream_t s)
 {
     if (N == 0)
         return GWBP_OK;
-    if (mt == GWBP_MAP_F16)
-        return launch_kmeans_assign_t<GWBP_MAP_F16>(36, N, K, D, X, ldx, C, ldc, bias, label, best, s);
-    if (mt == GWBP_MAP_BF16)
-        return launch_kmeans_assign_t<GWBP_MAP_BF16>(38, N, K, D, X, ldx, C, ldc, bias, label, best, s);
-    return launch_kmeans_assign_t<GWBP_MAP_F32>(29, N, K, D, X, ldx, C, ldc, bias, label, best, s);
+    unsigned grid;
+    if (int rc = grid_of("kmeans_assign", N, &grid, kKnnQ))
+        return rc;
+    const bool vec = field_rows_vec(X, ldx, mt) && field_rows_vec(C, ldc, GWBP_MAP_F32);
+    const int lds = 2 * kKnnStage * (int)sizeof(float);
+    return with_field_type(mt, vec, [&](auto MT, auto VEC) {
+        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(k_kmeans_assign<MT, VEC>), lds))
+            return rc;
+        hipLaunchKernelGGL((k_kmeans_assign<MT, VEC>), dim3(grid), dim3(kKnnThreads), lds, s, N, K, D, field_ptr<MT>(X), ldx, C, ldc,
+                           bias, label, best);
+        return check_hip(hipGetLastError(), "kmeans_assign launch");
+    });
 }
 
 size_t cluster_workspace_bytes(int64_t N, int D, int K) { return sum_ws(nullptr, N, D, K).bytes; }
-
-template <int MT>
-static void launch_cluster_sums_t(dim3 g, hipStream_t s, int64_t N, int D, int K, int64_t slots, const void *Xv, int64_t ldx,
-                                  const float *w, const int64_t *order, const int64_t *start, const SumWs &W)
-{
-    const typename MapElem<MT>::raw *X = static_cast<const typename MapElem<MT>::raw *>(Xv);
-    if (field_rows_vec(Xv, ldx, MT))
-        hipLaunchKernelGGL((k_cluster_sums<MT, true>), g, dim3(64 * kSumWaves), 0, s, N, D, K, slots, X, ldx, w, order, start,
-                           W.run_start, W.partial, W.wpartial);
-    else
-        hipLaunchKernelGGL((k_cluster_sums<MT, false>), g, dim3(64 * kSumWaves), 0, s, N, D, K, slots, X, ldx, w, order, start,
-                           W.run_start, W.partial, W.wpartial);
-}
 
 int launch_cluster_sums(int64_t N, int D, int K, const void *X, int mt, int64_t ldx, const float *w, const int64_t *order,
                         const int64_t *start, double *sums, double *wsum, void *ws, hipStream_t s)
 {
     const SumWs W = sum_ws(ws, N, D, K);
     const int64_t slots = run_slots(N, K);
-    const int64_t grid = (slots + kSumWaves - 1) / kSumWaves;
+    unsigned grid;
+    if (int rc = grid_of("cluster_sums", slots, &grid, kSumWaves))
+        return rc;
     const int col_blocks = (D + kSumCols - 1) / kSumCols;
-    if (grid > 0x7FFFFFFF || col_blocks > 65535)
-        return set_error(GWBP_EINVAL, "cluster_sums: N = %lld, D = %d need too many workgroups", (long long)N, D);
+    if (col_blocks > 65535)
+        return set_error(GWBP_EINVAL, "cluster_sums: D = %d needs more than 65535 column blocks", D);
     hipLaunchKernelGGL(k_cluster_runs, dim3(1), dim3(kScanThreads), 0, s, N, K, start, W.run_start);
     if (N > 0) {
-        const dim3 g((unsigned)grid, (unsigned)col_blocks);
-        if (mt == GWBP_MAP_F16)
-            launch_cluster_sums_t<GWBP_MAP_F16>(g, s, N, D, K, slots, X, ldx, w, order, start, W);
-        else if (mt == GWBP_MAP_BF16)
-            launch_cluster_sums_t<GWBP_MAP_BF16>(g, s, N, D, K, slots, X, ldx, w, order, start, W);
-        else
-            launch_cluster_sums_t<GWBP_MAP_F32>(g, s, N, D, K, slots, X, ldx, w, order, start, W);
+        const dim3 g(grid, (unsigned)col_blocks);
+        with_field_type(mt, field_rows_vec(X, ldx, mt), [&](auto MT, auto VEC) {
+            hipLaunchKernelGGL((k_cluster_sums<MT, VEC>), g, dim3(64 * kSumWaves), 0, s, N, D, K, slots, field_ptr<MT>(X), ldx, w, order,
+                               start, W.run_start, W.partial, W.wpartial);
+        });
     }
     hipLaunchKernelGGL(k_cluster_reduce, dim3((unsigned)K), dim3(256), 0, s, D, slots, W.run_start, W.partial, W.wpartial, sums,
                        wsum);

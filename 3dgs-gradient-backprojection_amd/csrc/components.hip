@@ -11,24 +11,19 @@
 //   components   = the classes of the core points under chains of ~ through core points; a live non-core point with a core
 //                  neighbour goes with its nearest core neighbour by (d2, index); everything else is noise
 //
-// RADIUS WALK (radius_walk.h, which sample.hip shares).  One lane per query, queries in the order of their cell keys.  Rings of
-// Chebyshev radius r = 0, 1, 2, ... around the
-// query's cell, clipped to the grid, with the empty-slab skip and the x-run spans of k_spatial_knn.  The lane stops after ring r
-// when r2 < fl(LB * LB), STRICTLY, LB the smallest of bound_above / bound_below over the sides that still have cells, and when no
-// side has cells left.  spatial.hip's argument carries over unchanged: after ring r an unvisited point p sits in a cell at least
-// r + 1 away from the query's along some axis; the rounded cell assignment puts its exact distance along that axis at LB or more
-// (LB keeps a margin for the roundings of the assignment and of its own expression); rounding is monotone, so the COMPUTED
-// |dx| >= LB, fl(dx * dx) >= fl(LB * LB), and each fmaf adds a non-negative term before a monotone rounding: every unvisited point
-// has a computed d2 >= fl(LB * LB) > r2 and is no neighbour.  (Strictly: a point at exactly the bound may have d2 == r2, which
-// counts.)  The margin errs towards one more ring, never towards stopping.  Trip count: at most max(nx, ny, nz) + 1.  Nothing in
-// the walk depends on which cell a point was assigned to beyond that bound, so the set of neighbours found is the brute-force
-// set, whatever the grid.
+// RADIUS WALK (radius_walk of ring_walk.h: the walk of k_spatial_knn with the fixed cut r2, whose header has the bounds and the
+// stop rule).  One lane per query, queries in the order of their cell keys; the lane stops after a ring when r2 < fl(LB * LB), and
+// every unvisited point then has a computed d2 > r2 and is no neighbour.  STRICTLY: a point at exactly the bound may have d2 == r2,
+// which counts.  The set of neighbours found is the brute-force set, whatever the grid.
+//
+// BORDER RULE.  A live non-core point goes with its nearest core neighbour by (d2, index): a total order on a set, so the result
+// does not depend on the order in which the walk visits the neighbours.
 //
 // UNION-FIND BY INDEX (k_radius_union, k_components_flatten): uf_find / uf_unite of union_find.h, which regions.hip shares; the
 // header has the argument.  parent[v] is the identity on entry, a hook stores a smaller index over a root, a component's final root
 // is its smallest member, no lane ever waits for another, and the results do not depend on the order of the hooks.
 #include "gwbp_dev.h"
-#include "radius_walk.h"
+#include "ring_walk.h"
 #include "spatial_grid.h"
 #include "union_find.h"
 
@@ -83,7 +78,6 @@ __global__ __launch_bounds__(kRadiusThreads) void k_radius_union(int64_t N, cons
     radius_walk(S, cell_start, G, v.x, v.y, v.z, r2, [&](float, int j) {
         if (j < i && count[j] >= min_points && (!group || group[j] == gi))
             mine = uf_unite(parent, mine, j, cap, status);
-        return false;
     });
 }
 
@@ -108,7 +102,6 @@ __global__ __launch_bounds__(kRadiusThreads) void k_radius_attach(int64_t N, con
                 bd = d2;
                 best = j;
             }
-            return false;
         });
     }
     attach[i] = best;

@@ -394,11 +394,7 @@ int launch_field_compare(const Layout &L, const Ws &W, const ViewDev &V, const f
                      (reinterpret_cast<uintptr_t>(map) & malign) == 0 && ms_y % 4 == 0 && ms_x % 4 == 0;
     const bool wide2 = vec && D >= 512;
     const int empty = L.n == 0;
-    switch (mt) {
-    case GWBP_MAP_F32: launch_compare_mt<GWBP_MAP_F32>(wide2, vec, grid, s, V, empty, W, feats, ldf, D, M, planes, rowsums); break;
-    case GWBP_MAP_F16: launch_compare_mt<GWBP_MAP_F16>(wide2, vec, grid, s, V, empty, W, feats, ldf, D, M, planes, rowsums); break;
-    default: launch_compare_mt<GWBP_MAP_BF16>(wide2, vec, grid, s, V, empty, W, feats, ldf, D, M, planes, rowsums); break;
-    }
+    with_map_type(mt, [&](auto MT) { launch_compare_mt<MT>(wide2, vec, grid, s, V, empty, W, feats, ldf, D, M, planes, rowsums); });
     int rc = check_hip(hipGetLastError(), "field_compare launch");
     if (rc)
         return rc;

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/gwbp.h"
 
 namespace gwbp {
@@ -129,10 +131,19 @@ int make_layout(const gwbp_caps *caps, Layout *L);
 int bind_workspace(const gwbp_caps *caps, void *ws, size_t bytes, Layout *L, Ws *W);
 int set_error(int code, const char *fmt, ...);
 int check_hip(hipError_t e, const char *what);
-// Per-device facts, cached per device ORDINAL (a process may drive several GPUs): CU count of the current device, and
-// "this kernel's dynamic-LDS limit has been raised on the current device" (slot = one bit per kernel, < 64).
+// Per-device facts, cached per device ORDINAL (a process may drive several GPUs): CU count of the current device, and the largest
+// dynamic-LDS limit each kernel has been given on the current device (raised when a kernel is new there or asks for more).
 int device_cus(int *n_cu);
-int ensure_dynamic_lds(const void *func, int bytes, int slot);
+int ensure_dynamic_lds(const void *func, int bytes);
+// workgroups of per_block items for n of them, or GWBP_EINVAL beyond what a grid's x dimension takes
+inline int grid_of(const char *what, int64_t n, unsigned *grid, int per_block)
+{
+    const int64_t g = (n + per_block - 1) / per_block;
+    if (g > 0x7FFFFFFF)
+        return set_error(GWBP_EINVAL, "%s: %lld items need more than 2^31 - 1 workgroups", what, (long long)n);
+    *grid = (unsigned)g;
+    return GWBP_OK;
+}
 // Profiling / ablation knobs (GWBP_ABLATE, GWBP_ABLATE_BLEND, GWBP_BLEND_LDS): an environment variable is read only by a
 // library built with -DGWBP_PROFILE (make PROFILE=1 -> libgwbp_profile.so); the product library always gets 0.
 int profile_knob(const char *name);
@@ -504,6 +515,23 @@ __device__ __forceinline__ float4 load4(const float *__restrict__ p, int c, int 
         v.w = p[c + 3];
     return v;
 }
+// ... and written: the columns of v that lie below D.
+template <bool VEC>
+__device__ __forceinline__ void store4(float *__restrict__ p, int c, int D, float4 v)
+{
+    if (VEC && c + 4 <= D) {
+        *reinterpret_cast<float4 *>(p + c) = v;
+        return;
+    }
+    if (c < D)
+        p[c] = v.x;
+    if (c + 1 < D)
+        p[c + 1] = v.y;
+    if (c + 2 < D)
+        p[c + 2] = v.z;
+    if (c + 3 < D)
+        p[c + 3] = v.w;
+}
 
 // The same four columns of a row of a finished FIELD whose elements have type MT (GWBP_MAP_*), zero beyond D, no load for a null
 // row, in two steps so that a kernel can keep loads in flight: load4raw lands the BITS (MapElem<MT>::raw4: a float4, or the four
@@ -544,6 +572,36 @@ template <int MT, bool VEC>
 __device__ __forceinline__ float4 load4t(const void *__restrict__ row, int c, int D)
 {
     return widen4<MT>(load4raw<MT, VEC>(row, c, D));
+}
+
+// The host side of a typed operand: a launcher turns its run-time element type mt (GWBP_MAP_*, checked by the C ABI layer) and "the
+// rows take the vector path" into template arguments HERE, so that each kernel's launch line is written once:
+//     with_field_type(mt, vec, [&](auto MT, auto VEC) { hipLaunchKernelGGL((k<MT, VEC>), ..., field_ptr<MT>(X), ...); });
+template <class Fn>
+auto with_map_type(int mt, Fn &&fn)
+{
+    if (mt == GWBP_MAP_F16)
+        return fn(std::integral_constant<int, GWBP_MAP_F16>{});
+    if (mt == GWBP_MAP_BF16)
+        return fn(std::integral_constant<int, GWBP_MAP_BF16>{});
+    return fn(std::integral_constant<int, GWBP_MAP_F32>{});
+}
+template <class Fn>
+auto with_bool(bool b, Fn &&fn)
+{
+    if (b)
+        return fn(std::true_type{});
+    return fn(std::false_type{});
+}
+template <class Fn>
+auto with_field_type(int mt, bool vec, Fn &&fn)
+{
+    return with_map_type(mt, [&](auto MT) { return with_bool(vec, [&](auto VEC) { return fn(MT, VEC); }); });
+}
+template <int MT>
+const typename MapElem<MT>::raw *field_ptr(const void *p)
+{
+    return static_cast<const typename MapElem<MT>::raw *>(p);
 }
 
 // One fp32 value rounded ONCE, to nearest even, to the element type OT of a typed output (k_finalize): torch's x.to(dtype) bit for

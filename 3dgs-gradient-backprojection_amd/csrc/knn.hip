@@ -155,42 +155,24 @@ __global__ __launch_bounds__(256) void k_knn_vote(int64_t N, int M, int k, const
 
 } // namespace
 
-// slot: the first of the instantiation pair's two bits of ensure_dynamic_lds (vector, then element loads)
-template <int QT>
-static int launch_knn_search_t(int slot, int64_t N, int M, int D, int k, const void *Qv, int64_t ldq, const float *S, int64_t lds_,
-                               int32_t *idx, float *score, hipStream_t s)
-{
-    const typename MapElem<QT>::raw *Q = static_cast<const typename MapElem<QT>::raw *>(Qv);
-    const bool vec = field_rows_vec(Qv, ldq, QT) && field_rows_vec(S, lds_, GWBP_MAP_F32);
-    // always the largest request (k = 32): ensure_dynamic_lds remembers "raised" per (device, slot), not the size
-    const int lds_max = 2 * kKnnStage * (int)sizeof(float) + kKnnMaxK * kKnnQ * (int)sizeof(u64);
-    const void *fn = vec ? reinterpret_cast<const void *>(k_knn_search<QT, true>) : reinterpret_cast<const void *>(k_knn_search<QT, false>);
-    const int rc = ensure_dynamic_lds(fn, lds_max, vec ? slot : slot + 1);
-    if (rc)
-        return rc;
-    const size_t lds = 2 * kKnnStage * sizeof(float) + (size_t)k * kKnnQ * sizeof(u64);
-    const int64_t grid = (N + kKnnQ - 1) / kKnnQ;
-    if (grid > 0x7FFFFFFF)
-        return set_error(GWBP_EINVAL, "knn_search: N = %lld needs more than 2^31 - 1 workgroups", (long long)N);
-    if (vec)
-        hipLaunchKernelGGL((k_knn_search<QT, true>), dim3((unsigned)grid), dim3(kKnnThreads), lds, s, N, M, D, k, Q, ldq, S, lds_, idx,
-                           score);
-    else
-        hipLaunchKernelGGL((k_knn_search<QT, false>), dim3((unsigned)grid), dim3(kKnnThreads), lds, s, N, M, D, k, Q, ldq, S, lds_, idx,
-                           score);
-    return check_hip(hipGetLastError(), "knn_search launch");
-}
-
 int launch_knn_search(int64_t N, int M, int D, int k, const void *Q, int mt, int64_t ldq, const float *S, int64_t lds_, int32_t *idx,
                       float *score, hipStream_t s)
 {
     if (N == 0)
         return GWBP_OK;
-    if (mt == GWBP_MAP_F16)
-        return launch_knn_search_t<GWBP_MAP_F16>(32, N, M, D, k, Q, ldq, S, lds_, idx, score, s);
-    if (mt == GWBP_MAP_BF16)
-        return launch_knn_search_t<GWBP_MAP_BF16>(34, N, M, D, k, Q, ldq, S, lds_, idx, score, s);
-    return launch_knn_search_t<GWBP_MAP_F32>(24, N, M, D, k, Q, ldq, S, lds_, idx, score, s);
+    unsigned grid;
+    if (int rc = grid_of("knn_search", N, &grid, kKnnQ))
+        return rc;
+    const bool vec = field_rows_vec(Q, ldq, mt) && field_rows_vec(S, lds_, GWBP_MAP_F32);
+    const int lds_max = 2 * kKnnStage * (int)sizeof(float) + kKnnMaxK * kKnnQ * (int)sizeof(u64); // the largest request (k = 32)
+    const size_t lds = 2 * kKnnStage * sizeof(float) + (size_t)k * kKnnQ * sizeof(u64);
+    return with_field_type(mt, vec, [&](auto QT, auto VEC) {
+        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(k_knn_search<QT, VEC>), lds_max))
+            return rc;
+        hipLaunchKernelGGL((k_knn_search<QT, VEC>), dim3(grid), dim3(kKnnThreads), lds, s, N, M, D, k, field_ptr<QT>(Q), ldq, S, lds_, idx,
+                           score);
+        return check_hip(hipGetLastError(), "knn_search launch");
+    });
 }
 
 int launch_knn_vote(int64_t N, int M, int k, const int32_t *idx, const int32_t *labels, int num_classes, int32_t *label_out,
@@ -198,10 +180,10 @@ int launch_knn_vote(int64_t N, int M, int k, const int32_t *idx, const int32_t *
 {
     if (N == 0)
         return GWBP_OK;
-    const int64_t grid = (N + 255) / 256;
-    if (grid > 0x7FFFFFFF)
-        return set_error(GWBP_EINVAL, "knn_vote: N = %lld needs more than 2^31 - 1 workgroups", (long long)N);
-    hipLaunchKernelGGL(k_knn_vote, dim3((unsigned)grid), dim3(256), 0, s, N, M, k, idx, labels, num_classes, label_out, counts,
+    unsigned grid;
+    if (int rc = grid_of("knn_vote", N, &grid, 256))
+        return rc;
+    hipLaunchKernelGGL(k_knn_vote, dim3(grid), dim3(256), 0, s, N, M, k, idx, labels, num_classes, label_out, counts,
                        ldc);
     return check_hip(hipGetLastError(), "knn_vote launch");
 }

@@ -173,7 +173,7 @@ int launch_render_labels(const Ws &W, const ViewDev &V, const int32_t *labels, i
     const int n_tiles = V.tile_w * V.tile_h;
     const int fin = sort_passes(n_tiles) & 1;
     // static (staging, counters) + dynamic (class sums) LDS pass the 64 KB a kernel gets unasked from 54 classes on
-    int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(k_render_labels), kLabelChunk * 256 * (int)sizeof(float), 28);
+    int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(k_render_labels), kLabelChunk * 256 * (int)sizeof(float));
     if (rc)
         return rc;
     for (int base = 0; base < K; base += kLabelChunk) {

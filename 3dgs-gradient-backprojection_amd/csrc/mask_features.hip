@@ -432,15 +432,9 @@ int launch_mask_features(const Layout &L, const Ws &W, const ViewDev &V, const v
     if (L.n == 0)
         return GWBP_OK;
     hipLaunchKernelGGL(k_zero_mask_sums, dim3(1024), dim3(256), 0, s, S.sums, W.counters);
-    if (table_type == GWBP_MAP_F16)
-        launch_reduce_mt<GWBP_MAP_F16>(label_type, W, V, labels, ls_y, ls_x, ymap, xmap, M, table, ts_row, D, scale_f, scale_d, F,
-                                       d, S, n_spilled, s);
-    else if (table_type == GWBP_MAP_BF16)
-        launch_reduce_mt<GWBP_MAP_BF16>(label_type, W, V, labels, ls_y, ls_x, ymap, xmap, M, table, ts_row, D, scale_f, scale_d,
-                                        F, d, S, n_spilled, s);
-    else
-        launch_reduce_mt<GWBP_MAP_F32>(label_type, W, V, labels, ls_y, ls_x, ymap, xmap, M, table, ts_row, D, scale_f, scale_d,
-                                       F, d, S, n_spilled, s);
+    with_map_type(table_type, [&](auto MT) {
+        launch_reduce_mt<MT>(label_type, W, V, labels, ls_y, ls_x, ymap, xmap, M, table, ts_row, D, scale_f, scale_d, F, d, S, n_spilled, s);
+    });
     int rc = check_hip(hipGetLastError(), "mask_reduce launch");
     if (rc)
         return rc;
@@ -457,12 +451,7 @@ int launch_mask_features(const Layout &L, const Ws &W, const ViewDev &V, const v
     if (blocks > 0x7FFFFFFFll)
         return set_error(GWBP_EINVAL, "gwbp_scatter_mask_features: grid too large");
     const dim3 grid((unsigned)blocks);
-    if (table_type == GWBP_MAP_F16)
-        launch_apply_mt<GWBP_MAP_F16>(A, nc, full, grid, s);
-    else if (table_type == GWBP_MAP_BF16)
-        launch_apply_mt<GWBP_MAP_BF16>(A, nc, full, grid, s);
-    else
-        launch_apply_mt<GWBP_MAP_F32>(A, nc, full, grid, s);
+    with_map_type(table_type, [&](auto MT) { launch_apply_mt<MT>(A, nc, full, grid, s); });
     return check_hip(hipGetLastError(), "mask_apply launch");
 }
 

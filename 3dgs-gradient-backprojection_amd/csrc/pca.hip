@@ -371,15 +371,6 @@ __global__ __launch_bounds__(256) void k_pca_colors(int64_t n, const float *__re
     out[e] = span > 0.f ? (Y[e] - lo) / span : 0.5f;
 }
 
-int grid_of(int64_t n, int per, const char *what, unsigned *grid)
-{
-    const int64_t g = (n + per - 1) / per;
-    if (g > 0x7FFFFFFF)
-        return set_error(GWBP_EINVAL, "%s: %lld items need more than 2^31 - 1 workgroups", what, (long long)n);
-    *grid = (unsigned)g;
-    return GWBP_OK;
-}
-
 } // namespace
 
 size_t pca_workspace_bytes(int64_t N, int D)
@@ -389,47 +380,16 @@ size_t pca_workspace_bytes(int64_t N, int D)
     return means > gram ? means : gram;
 }
 
-template <int MT>
-static void launch_column_sums_t(dim3 grid, hipStream_t s, int64_t N, int D, const void *X, int64_t ldx, int64_t rows, double *partial)
-{
-    hipLaunchKernelGGL(k_column_sums<MT>, grid, dim3(kMeanCols * kMeanRowLanes), 0, s, N, D,
-                       static_cast<const typename MapElem<MT>::raw *>(X), ldx, rows, partial);
-}
-
 int launch_column_means(int64_t N, int D, const void *X, int mt, int64_t ldx, float *mean, void *ws, hipStream_t s)
 {
     const MeanPlan p = mean_plan(N);
     double *partial = static_cast<double *>(ws);
     const dim3 grid((unsigned)((D + kMeanCols - 1) / kMeanCols), (unsigned)p.slices);
-    if (mt == GWBP_MAP_F16)
-        launch_column_sums_t<GWBP_MAP_F16>(grid, s, N, D, X, ldx, p.rows, partial);
-    else if (mt == GWBP_MAP_BF16)
-        launch_column_sums_t<GWBP_MAP_BF16>(grid, s, N, D, X, ldx, p.rows, partial);
-    else
-        launch_column_sums_t<GWBP_MAP_F32>(grid, s, N, D, X, ldx, p.rows, partial);
+    with_map_type(mt, [&](auto MT) {
+        hipLaunchKernelGGL(k_column_sums<MT>, grid, dim3(kMeanCols * kMeanRowLanes), 0, s, N, D, field_ptr<MT>(X), ldx, p.rows, partial);
+    });
     hipLaunchKernelGGL(k_column_means, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, s, N, D, p.slices, partial, mean);
     return check_hip(hipGetLastError(), "column_means launch");
-}
-
-// slot: the first of the instantiation pair's two bits of ensure_dynamic_lds (vector, then element loads)
-template <int MT>
-static int launch_centered_gram_t(int slot, const GramPlan &p, int64_t N, int D, const void *Xv, int64_t ldx, const float *mean,
-                                  float *partial, hipStream_t s)
-{
-    const typename MapElem<MT>::raw *X = static_cast<const typename MapElem<MT>::raw *>(Xv);
-    const bool vec = field_rows_vec(Xv, ldx, MT);
-    const int lds = 2 * kGramStage * (int)sizeof(float);
-    const void *fn =
-        vec ? reinterpret_cast<const void *>(k_centered_gram<MT, true>) : reinterpret_cast<const void *>(k_centered_gram<MT, false>);
-    const int rc = ensure_dynamic_lds(fn, lds, vec ? slot : slot + 1);
-    if (rc)
-        return rc;
-    const dim3 grid((unsigned)p.n_tiles, (unsigned)p.slices);
-    if (vec)
-        hipLaunchKernelGGL((k_centered_gram<MT, true>), grid, dim3(kGramThreads), lds, s, N, D, X, ldx, mean, p.rows, p.n_tb, partial);
-    else
-        hipLaunchKernelGGL((k_centered_gram<MT, false>), grid, dim3(kGramThreads), lds, s, N, D, X, ldx, mean, p.rows, p.n_tb, partial);
-    return GWBP_OK;
 }
 
 int launch_centered_gram(int64_t N, int D, const void *X, int mt, int64_t ldx, const float *mean, double *gram, void *ws,
@@ -437,39 +397,31 @@ int launch_centered_gram(int64_t N, int D, const void *X, int mt, int64_t ldx, c
 {
     const GramPlan p = gram_plan(N, D);
     float *partial = static_cast<float *>(ws);
-    const int rc = mt == GWBP_MAP_F16    ? launch_centered_gram_t<GWBP_MAP_F16>(40, p, N, D, X, ldx, mean, partial, s)
-                   : mt == GWBP_MAP_BF16 ? launch_centered_gram_t<GWBP_MAP_BF16>(42, p, N, D, X, ldx, mean, partial, s)
-                                         : launch_centered_gram_t<GWBP_MAP_F32>(26, p, N, D, X, ldx, mean, partial, s);
+    const int lds = 2 * kGramStage * (int)sizeof(float);
+    const dim3 grid((unsigned)p.n_tiles, (unsigned)p.slices);
+    const int rc = with_field_type(mt, field_rows_vec(X, ldx, mt), [&](auto MT, auto VEC) {
+        if (int e = ensure_dynamic_lds(reinterpret_cast<const void *>(k_centered_gram<MT, VEC>), lds))
+            return e;
+        hipLaunchKernelGGL((k_centered_gram<MT, VEC>), grid, dim3(kGramThreads), lds, s, N, D, field_ptr<MT>(X), ldx, mean, p.rows,
+                           p.n_tb, partial);
+        return (int)GWBP_OK;
+    });
     if (rc)
         return rc;
     hipLaunchKernelGGL(k_gram_reduce, dim3((unsigned)(((int64_t)D * D + 255) / 256)), dim3(256), 0, s, D, p.slices, partial, gram);
     return check_hip(hipGetLastError(), "centered_gram launch");
 }
 
-template <int MT>
-static void launch_pca_project_t(unsigned grid, hipStream_t s, int64_t N, int D, int k, const void *Xv, int64_t ldx, const float *mean,
-                                 const float *V, float *Y, float *minmax)
-{
-    const typename MapElem<MT>::raw *X = static_cast<const typename MapElem<MT>::raw *>(Xv);
-    if (field_rows_vec(Xv, ldx, MT))
-        hipLaunchKernelGGL((k_pca_project<MT, true>), dim3(grid), dim3(kProjThreads), 0, s, N, D, k, X, ldx, mean, V, Y, minmax);
-    else
-        hipLaunchKernelGGL((k_pca_project<MT, false>), dim3(grid), dim3(kProjThreads), 0, s, N, D, k, X, ldx, mean, V, Y, minmax);
-}
-
 int launch_pca_project(int64_t N, int D, int k, const void *X, int mt, int64_t ldx, const float *mean, const float *V, float *Y,
                        float *minmax, hipStream_t s)
 {
     unsigned grid = 0;
-    const int rc = grid_of(N, kProjRows, "pca_project", &grid);
-    if (rc)
+    if (int rc = grid_of("pca_project", N, &grid, kProjRows))
         return rc;
-    if (mt == GWBP_MAP_F16)
-        launch_pca_project_t<GWBP_MAP_F16>(grid, s, N, D, k, X, ldx, mean, V, Y, minmax);
-    else if (mt == GWBP_MAP_BF16)
-        launch_pca_project_t<GWBP_MAP_BF16>(grid, s, N, D, k, X, ldx, mean, V, Y, minmax);
-    else
-        launch_pca_project_t<GWBP_MAP_F32>(grid, s, N, D, k, X, ldx, mean, V, Y, minmax);
+    with_field_type(mt, field_rows_vec(X, ldx, mt), [&](auto MT, auto VEC) {
+        hipLaunchKernelGGL((k_pca_project<MT, VEC>), dim3(grid), dim3(kProjThreads), 0, s, N, D, k, field_ptr<MT>(X), ldx, mean, V, Y,
+                           minmax);
+    });
     return check_hip(hipGetLastError(), "pca_project launch");
 }
 
@@ -478,8 +430,7 @@ int launch_pca_colors(int64_t n, const float *Y, const float *lo_hi, float *colo
     if (n == 0)
         return GWBP_OK;
     unsigned grid = 0;
-    const int rc = grid_of(n, 256, "pca_colors", &grid);
-    if (rc)
+    if (int rc = grid_of("pca_colors", n, &grid, 256))
         return rc;
     hipLaunchKernelGGL(k_pca_colors, dim3(grid), dim3(256), 0, s, n, Y, lo_hi, colors);
     return check_hip(hipGetLastError(), "pca_colors launch");

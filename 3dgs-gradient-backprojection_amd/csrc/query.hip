@@ -116,15 +116,7 @@ __global__ __launch_bounds__(64) void k_probe_pixels(ViewDev V, const u32 *__res
             }
         }
     }
-    float *o = out + (int64_t)probe * D;
-    if (c < D)
-        o[c] = acc.x;
-    if (c + 1 < D)
-        o[c + 1] = acc.y;
-    if (c + 2 < D)
-        o[c + 2] = acc.z;
-    if (c + 3 < D)
-        o[c + 3] = acc.w;
+    store4<false>(out + (int64_t)probe * D, c, D, acc);
     if (chunk == 0 && lane == 0) {
         if (depth)
             depth[probe] = zacc;
@@ -142,15 +134,15 @@ int launch_prompt_scores(int64_t N, int D, int P, int n_pos, const void *X, int 
 {
     if (N == 0)
         return GWBP_OK;
-    const int64_t grid = (N + kQRows - 1) / kQRows;
-    if (grid > 0x7FFFFFFF)
-        return set_error(GWBP_EINVAL, "prompt_scores: %lld rows need more than 2^31 - 1 workgroups", (long long)N);
+    unsigned grid;
+    if (int rc = grid_of("prompt_scores", N, &grid, kQRows))
+        return rc;
     const int use_thr = threshold ? 1 : 0;
     const float thr = threshold ? *threshold : 0.f;
     if (mt != GWBP_MAP_F32) // the half instantiations are query_half.hip's
-        launch_prompt_scores_half((unsigned)grid, s, N, D, P, n_pos, X, mt, ldx, prompts, normalize, use_thr, thr, mask, scores);
+        launch_prompt_scores_half(grid, s, N, D, P, n_pos, X, mt, ldx, prompts, normalize, use_thr, thr, mask, scores);
     else
-        launch_prompt_scores_t<GWBP_MAP_F32>((unsigned)grid, s, N, D, P, n_pos, X, ldx, prompts, normalize, use_thr, thr, mask, scores);
+        launch_prompt_scores_t<GWBP_MAP_F32>(grid, s, N, D, P, n_pos, X, ldx, prompts, normalize, use_thr, thr, mask, scores);
     return check_hip(hipGetLastError(), "prompt_scores launch");
 }
 

@@ -152,23 +152,12 @@ template <int MT>
 void launch_prompt_scores_t(unsigned grid, hipStream_t s, int64_t N, int D, int P, int n_pos, const void *Xv, int64_t ldx,
                             const float *prompts, int normalize, int use_thr, float thr, uint8_t *mask, float *scores)
 {
-    const typename MapElem<MT>::raw *X = static_cast<const typename MapElem<MT>::raw *>(Xv);
-    const bool vec = field_rows_vec(Xv, ldx, MT);
-#define GWBP_Q(VEC, NPB)                                                                                              \
-    hipLaunchKernelGGL((k_prompt_scores<MT, VEC, NPB>), dim3(grid), dim3(kQThreads), 0, s, N, D, P, n_pos, X, ldx, prompts, \
-                       normalize, use_thr, thr, mask, scores)
-    if (P <= 16) {
-        if (vec)
-            GWBP_Q(true, 1);
-        else
-            GWBP_Q(false, 1);
-    } else {
-        if (vec)
-            GWBP_Q(true, 2);
-        else
-            GWBP_Q(false, 2);
-    }
-#undef GWBP_Q
+    with_bool(field_rows_vec(Xv, ldx, MT), [&](auto VEC) {
+        with_bool(P <= 16, [&](auto ONE) { // 16-prompt blocks: one or two
+            hipLaunchKernelGGL((k_prompt_scores<MT, VEC, ONE ? 1 : 2>), dim3(grid), dim3(kQThreads), 0, s, N, D, P, n_pos,
+                               field_ptr<MT>(Xv), ldx, prompts, normalize, use_thr, thr, mask, scores);
+        });
+    });
 }
 
 } // namespace

@@ -162,11 +162,12 @@ __global__ __launch_bounds__(kUnionThreads) void k_edge_union(int64_t N, int k, 
     }
 }
 
+// the third dispatch level, particular to this kernel: CH 256-channel steps per row held in registers
 template <int MT, bool VEC>
 void launch_similarity(unsigned grid, hipStream_t s, int64_t N, int D, int k, const int32_t *idx, const void *Fv, int64_t ldf,
                        float *sim, int32_t *live)
 {
-    const typename MapElem<MT>::raw *F = static_cast<const typename MapElem<MT>::raw *>(Fv);
+    const auto F = field_ptr<MT>(Fv);
     if (D <= 256)
         hipLaunchKernelGGL((k_neighbor_similarity<MT, VEC, 1>), dim3(grid), dim3(256), 0, s, N, D, k, idx, F, ldf, sim, live);
     else if (D <= 512)
@@ -177,28 +178,14 @@ void launch_similarity(unsigned grid, hipStream_t s, int64_t N, int D, int k, co
         hipLaunchKernelGGL((k_neighbor_similarity<MT, VEC, 8>), dim3(grid), dim3(256), 0, s, N, D, k, idx, F, ldf, sim, live);
 }
 
-template <int MT>
-void launch_similarity_t(unsigned grid, hipStream_t s, int64_t N, int D, int k, const int32_t *idx, const void *F, int64_t ldf,
-                         float *sim, int32_t *live)
-{
-    if (field_rows_vec(F, ldf, MT))
-        launch_similarity<MT, true>(grid, s, N, D, k, idx, F, ldf, sim, live);
-    else
-        launch_similarity<MT, false>(grid, s, N, D, k, idx, F, ldf, sim, live);
-}
-
 } // namespace
 
 int launch_neighbor_similarity(int64_t N, int D, int k, const int32_t *idx, const void *F, int mt, int64_t ldf, float *sim,
                                int32_t *live, hipStream_t s)
 {
     const unsigned grid = (unsigned)((N + 3) / 4); // (N < 2^31, checked by the caller)
-    if (mt == GWBP_MAP_F16)
-        launch_similarity_t<GWBP_MAP_F16>(grid, s, N, D, k, idx, F, ldf, sim, live);
-    else if (mt == GWBP_MAP_BF16)
-        launch_similarity_t<GWBP_MAP_BF16>(grid, s, N, D, k, idx, F, ldf, sim, live);
-    else
-        launch_similarity_t<GWBP_MAP_F32>(grid, s, N, D, k, idx, F, ldf, sim, live);
+    with_field_type(mt, field_rows_vec(F, ldf, mt),
+                    [&](auto MT, auto VEC) { launch_similarity<MT, VEC>(grid, s, N, D, k, idx, F, ldf, sim, live); });
     return check_hip(hipGetLastError(), "neighbor_similarity launch");
 }
 

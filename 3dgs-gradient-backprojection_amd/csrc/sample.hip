@@ -1,6 +1,6 @@
 // sample.hip -- what a finished field says at an arbitrary 3-D point: the Gaussians that weigh on the point, by their own shape
 // (scale, rotation, opacity), the field blended over them, and a weighted vote of their labels.  On the grid of spatial.hip with the
-// ring walk of radius_walk.h.  (The reference has nothing of the kind; its users sample a field at the Gaussians' centres only.)
+// ring walk of ring_walk.h.  (The reference has nothing of the kind; its users sample a field at the Gaussians' centres only.)
 //
 // THE CONTRACT (include/gwbp.h, DESIGN 4.0d and tests/sample_ref.py say the same).
 //   LIVE(i): finite mean; finite quaternion with 0 < n2 < inf, n2 = fmaf(q3, q3, fmaf(q2, q2, fmaf(q1, q1, q0 * q0))); finite scales
@@ -24,8 +24,8 @@
 //
 // k_gaussian_pack: one lane per sorted position.
 // k_point_gaussians: one lane per query, queries in the order of their cell keys (k_radius_count's shape).  The visitor loads the
-//   record (three 16-B loads), computes w and inserts into the lane's sorted list in LDS, [k][threads] weights then [k][threads]
-//   indices (k_spatial_knn's layout, k * threads * 8 bytes <= 32 KiB).  Lists are lane-private: no atomics, no barrier, no waits.
+//   record (three 16-B loads), computes w and offers it to the lane's sorted list in LDS, LaneTopK<HeaviestFirst> (lane_topk.h:
+//   k_spatial_knn's list under the other order, k * threads * 8 bytes <= 32 KiB).  Lists are lane-private: no atomics, no waits.
 // k_neighbor_blend: one wave per query, four per workgroup, lanes over channels four at a time (k_neighbor_mean's shape).  Lane j < k
 //   reads entry j of the row's list once; the wave takes every entry from that lane by readlane (the loop index is wave-uniform).
 //   W = the chain acc = w_j + acc from +0 over the entries that are not skipped, in list order; out[c] = (acc = fmaf(w_j, F[idx_j, c],
@@ -34,7 +34,8 @@
 // k_weighted_vote: one lane per query; the list's labels (-1 for an entry that takes no part) and weights staged in the lane's LDS
 //   columns, then for each first occurrence of a class the chain of its weights in list order: O(k^2), no K-sized array.
 #include "gwbp_dev.h"
-#include "radius_walk.h"
+#include "lane_topk.h"
+#include "ring_walk.h"
 #include "spatial_grid.h"
 
 namespace gwbp {
@@ -42,7 +43,6 @@ namespace gwbp {
 namespace {
 
 constexpr int kSampleThreads = 128; // lanes (queries) per workgroup of the walk and the vote; LDS = k * 128 * 8 B <= 32 KiB
-constexpr int kNoIndex = 0x7FFFFFFF; // an empty slot of the list: orders after every Gaussian at equal weight
 constexpr int kPack4 = GWBP_SAMPLE_PACK / 4;
 static_assert(GWBP_SAMPLE_PACK == 12, "the record is three float4");
 
@@ -90,21 +90,14 @@ __global__ __launch_bounds__(kSampleThreads) void k_point_gaussians(const float4
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int T = kSampleThreads;
-    const int tid = threadIdx.x;
-    float *lw = smem + tid;                                 // [k][T] kept weights, descending
-    int *lid = reinterpret_cast<int *>(smem + k * T) + tid; // [k][T] their indices
+    LaneTopK<HeaviestFirst, T> best(smem, k, threadIdx.x); // kept weights, descending
 
-    const int64_t slot = (int64_t)blockIdx.x * T + tid;
+    const int64_t slot = (int64_t)blockIdx.x * T + threadIdx.x;
     if (slot >= Q)
         return; // (no barrier anywhere below)
     const int64_t g = order[slot];
     const float qx = queries[g * ldq], qy = queries[g * ldq + 1], qz = queries[g * ldq + 2];
-    for (int j = 0; j < k; ++j) {
-        lw[j * T] = 0.0f;
-        lid[j * T] = kNoIndex;
-    }
-    float kw = 0.0f; // the list's last entry: the k-th best so far (a kept weight is > 0, so an open list takes anything)
-    int ki = kNoIndex;
+    best.init();
     int nc = 0, seen = 0;
     if (finite3(qx, qy, qz))
         seen = radius_walk_at(S, cell_start, G, qx, qy, qz, r2, [&](float, const float4 &v, int p) {
@@ -116,31 +109,13 @@ __global__ __launch_bounds__(kSampleThreads) void k_point_gaussians(const float4
             const float sigma = 0.5f * __builtin_fmaf(u2, u2, __builtin_fmaf(u1, u1, u0 * u0));
             const float w = m0.w * exp_neg(-sigma);
             if (!(sigma <= 80.0f && w >= alpha_min))
-                return false;
+                return;
             ++nc;
-            const int id = __float_as_int(v.w);
-            if (w > kw || (w == kw && id < ki)) {
-                int j = k - 1; // sorted insert: shift the entries that order after (w, id) one down
-                while (j > 0) {
-                    const float pw = lw[(j - 1) * T];
-                    const int pi = lid[(j - 1) * T];
-                    if (pw > w || (pw == w && pi < id))
-                        break;
-                    lw[j * T] = pw;
-                    lid[j * T] = pi;
-                    --j;
-                }
-                lw[j * T] = w;
-                lid[j * T] = id;
-                kw = lw[(k - 1) * T];
-                ki = lid[(k - 1) * T];
-            }
-            return false;
+            best.offer(w, __float_as_int(v.w));
         });
     for (int j = 0; j < k; ++j) {
-        const int id = lid[j * T];
-        idx[g * k + j] = id == kNoIndex ? -1 : id;
-        wout[g * k + j] = lw[j * T]; // (0 in an empty slot)
+        idx[g * k + j] = best.index(j);
+        wout[g * k + j] = best.key(j); // (0 in an empty slot)
     }
     n_contrib[g] = nc;
     if (visited)
@@ -207,18 +182,7 @@ __global__ __launch_bounds__(256) void k_neighbor_blend(int64_t Q, int64_t M, in
         }
         if (any)
             acc = make_float4(acc.x / W, acc.y / W, acc.z / W, acc.w / W);
-        if (VEC && c + 4 <= D) {
-            *reinterpret_cast<float4 *>(o + c) = acc;
-        } else {
-            if (c < D)
-                o[c] = acc.x;
-            if (c + 1 < D)
-                o[c + 1] = acc.y;
-            if (c + 2 < D)
-                o[c + 2] = acc.z;
-            if (c + 3 < D)
-                o[c + 3] = acc.w;
-        }
+        store4<VEC>(o, c, D, acc);
     }
 }
 
@@ -228,10 +192,10 @@ __global__ __launch_bounds__(kSampleThreads) void k_weighted_vote(int64_t Q, int
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int T = kSampleThreads;
-    const int tid = threadIdx.x;
-    float *lw = smem + tid;                                  // [k][T] the entries' weights
-    int *lab = reinterpret_cast<int *>(smem + k * T) + tid;  // [k][T] their classes, -1 for an entry that takes no part
-    const int64_t g = (int64_t)blockIdx.x * T + tid;
+    const LaneColumns<T> col(smem, k, threadIdx.x);
+    float *lw = col.f; // [k][T] the entries' weights
+    int *lab = col.i;  // [k][T] their classes, -1 for an entry that takes no part
+    const int64_t g = (int64_t)blockIdx.x * T + threadIdx.x;
     if (g >= Q)
         return; // (no barrier anywhere below)
     float total = 0.0f;
@@ -295,23 +259,11 @@ int launch_point_gaussians(const float *sorted, const int32_t *cell_start, const
     unsigned grid;
     if (int rc = grid_of("point_gaussians", Q, &grid, kSampleThreads))
         return rc;
-    const size_t lds = (size_t)k * kSampleThreads * (sizeof(float) + sizeof(int)); // <= 32 KiB: below the default limit
+    const size_t lds = lane_columns_bytes(k, kSampleThreads); // <= 32 KiB: below the default limit
     hipLaunchKernelGGL(k_point_gaussians, dim3(grid), dim3(kSampleThreads), lds, s, reinterpret_cast<const float4 *>(sorted), cell_start,
                        make_grid(lo, h, dims), reinterpret_cast<const float4 *>(pack), r2, alpha_min, Q, queries, ldq, order, k, idx, w,
                        n_contrib, visited);
     return check_hip(hipGetLastError(), "point_gaussians launch");
-}
-
-template <int MT>
-static void launch_neighbor_blend_t(unsigned grid, hipStream_t s, int64_t Q, int64_t M, int D, int k, const int32_t *idx, const float *w,
-                                    const void *Fv, int64_t ldf, float *out, int64_t ldo, float *wsum)
-{
-    const typename MapElem<MT>::raw *F = static_cast<const typename MapElem<MT>::raw *>(Fv);
-    const bool vec = field_rows_vec(Fv, ldf, MT) && field_rows_vec(out, ldo, GWBP_MAP_F32);
-    if (vec)
-        hipLaunchKernelGGL((k_neighbor_blend<MT, true>), dim3(grid), dim3(256), 0, s, Q, M, D, k, idx, w, F, ldf, out, ldo, wsum);
-    else
-        hipLaunchKernelGGL((k_neighbor_blend<MT, false>), dim3(grid), dim3(256), 0, s, Q, M, D, k, idx, w, F, ldf, out, ldo, wsum);
 }
 
 int launch_neighbor_blend(int64_t Q, int64_t M, int D, int k, const int32_t *idx, const float *w, const void *F, int mt, int64_t ldf,
@@ -322,12 +274,11 @@ int launch_neighbor_blend(int64_t Q, int64_t M, int D, int k, const int32_t *idx
     unsigned grid;
     if (int rc = grid_of("neighbor_blend", Q, &grid, 4))
         return rc;
-    if (mt == GWBP_MAP_F16)
-        launch_neighbor_blend_t<GWBP_MAP_F16>(grid, s, Q, M, D, k, idx, w, F, ldf, out, ldo, wsum);
-    else if (mt == GWBP_MAP_BF16)
-        launch_neighbor_blend_t<GWBP_MAP_BF16>(grid, s, Q, M, D, k, idx, w, F, ldf, out, ldo, wsum);
-    else
-        launch_neighbor_blend_t<GWBP_MAP_F32>(grid, s, Q, M, D, k, idx, w, F, ldf, out, ldo, wsum);
+    const bool vec = field_rows_vec(F, ldf, mt) && field_rows_vec(out, ldo, GWBP_MAP_F32);
+    with_field_type(mt, vec, [&](auto MT, auto VEC) {
+        hipLaunchKernelGGL((k_neighbor_blend<MT, VEC>), dim3(grid), dim3(256), 0, s, Q, M, D, k, idx, w, field_ptr<MT>(F), ldf, out, ldo,
+                           wsum);
+    });
     return check_hip(hipGetLastError(), "neighbor_blend launch");
 }
 
@@ -339,7 +290,7 @@ int launch_weighted_vote(int64_t Q, int64_t M, int k, const int32_t *idx, const 
     unsigned grid;
     if (int rc = grid_of("weighted_vote", Q, &grid, kSampleThreads))
         return rc;
-    const size_t lds = (size_t)k * kSampleThreads * (sizeof(float) + sizeof(int));
+    const size_t lds = lane_columns_bytes(k, kSampleThreads);
     hipLaunchKernelGGL(k_weighted_vote, dim3(grid), dim3(kSampleThreads), lds, s, Q, M, k, idx, w, labels, K, out_label, out_share);
     return check_hip(hipGetLastError(), "weighted_vote launch");
 }

@@ -298,7 +298,7 @@ int launch_scatter(const Layout &L, const Ws &W, const ViewDev &V, const FeatMap
     const int pitch = chunk_pitch(D);
     const size_t lds_bytes = (size_t)kTilePix * pitch * sizeof(float) + 16;
     {
-        const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(k_scatter), 160 * 1024 - 64, 5);
+        const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(k_scatter), 160 * 1024 - 64);
         if (rc)
             return rc;
     }
@@ -325,12 +325,9 @@ int launch_finalize(int64_t N, int D, const float *F, const float *d, void *out,
     if (N == 0)
         return GWBP_OK;
     const dim3 grid((unsigned)((N + 3) / 4));
-    if (ot == GWBP_MAP_F16)
-        hipLaunchKernelGGL(k_finalize<GWBP_MAP_F16>, grid, dim3(256), 0, s, N, D, F, d, static_cast<unsigned short *>(out));
-    else if (ot == GWBP_MAP_BF16)
-        hipLaunchKernelGGL(k_finalize<GWBP_MAP_BF16>, grid, dim3(256), 0, s, N, D, F, d, static_cast<unsigned short *>(out));
-    else
-        hipLaunchKernelGGL(k_finalize<GWBP_MAP_F32>, grid, dim3(256), 0, s, N, D, F, d, static_cast<float *>(out));
+    with_map_type(ot, [&](auto OT) {
+        hipLaunchKernelGGL(k_finalize<OT>, grid, dim3(256), 0, s, N, D, F, d, static_cast<typename MapElem<OT>::raw *>(out));
+    });
     return check_hip(hipGetLastError(), "finalize launch");
 }
 

@@ -51,12 +51,12 @@ int launch_scatter_full(const Layout &L, const Ws &W, const ViewDev &V, const Fe
                           reinterpret_cast<const void *>(k_scatter_full<false, 2, GWBP_MAP_F32>),
                           reinterpret_cast<const void *>(k_scatter_full<true, 0, GWBP_MAP_F32>)};
     for (int i = 0; i < 4; ++i) {
-        const int rc = ensure_dynamic_lds(fns[i], i < 3 ? (int)kLdsBytes : 65536 + 16, 1 + i);
+        const int rc = ensure_dynamic_lds(fns[i], i < 3 ? (int)kLdsBytes : 65536 + 16);
         if (rc)
             return rc;
     }
     if (enc) {
-        const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(k_scatter_full<true, 3, GWBP_MAP_F32>), 16384 + 16 + 1024 * kEncN * 4, 8);
+        const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(k_scatter_full<true, 3, GWBP_MAP_F32>), 16384 + 16 + 1024 * kEncN * 4);
         if (rc)
             return rc;
     }

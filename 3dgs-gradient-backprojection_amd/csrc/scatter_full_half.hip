@@ -10,12 +10,12 @@ namespace {
 
 template <int MT>
 int launch_half(const Layout &L, const Ws &W, const ViewDev &V, const FeatMap &M, int D, float scale_f, float scale_d, float *F,
-                float *d, hipStream_t s, int slot)
+                float *d, hipStream_t s)
 {
     const bool bil = M.bilinear();
     const void *fn = bil ? reinterpret_cast<const void *>(k_scatter_full<false, 2, MT>)
                          : reinterpret_cast<const void *>(k_scatter_full<false, 1, MT>);
-    int rc = ensure_dynamic_lds(fn, (int)kLdsBytes, slot + (bil ? 1 : 0));
+    int rc = ensure_dynamic_lds(fn, (int)kLdsBytes);
     if (rc)
         return rc;
     int n_cu = 0;
@@ -47,9 +47,9 @@ int launch_scatter_full_half(const Layout &L, const Ws &W, const ViewDev &V, con
                                             "multiples of 8 elements and a 16-B aligned map (D=%d strides %lld %lld %lld)",
                          D, (long long)M.fs_y, (long long)M.fs_x, (long long)M.fs_c);
     if (mt == GWBP_MAP_F16)
-        return launch_half<GWBP_MAP_F16>(L, W, V, M, D, scale_f, scale_d, F, d, s, 20);
+        return launch_half<GWBP_MAP_F16>(L, W, V, M, D, scale_f, scale_d, F, d, s);
     if (mt == GWBP_MAP_BF16)
-        return launch_half<GWBP_MAP_BF16>(L, W, V, M, D, scale_f, scale_d, F, d, s, 22);
+        return launch_half<GWBP_MAP_BF16>(L, W, V, M, D, scale_f, scale_d, F, d, s);
     return set_error(GWBP_EINVAL, "scatter_full: unknown map type %d", mt);
 }
 

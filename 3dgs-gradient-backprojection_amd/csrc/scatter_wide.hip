@@ -73,7 +73,7 @@ extern "C" int gwbp_profile_read_wide(unsigned long long *out8_host)
 int launch_scatter_wide(const Layout &L, const Ws &W, const ViewDev &V, const FeatMap &M, int D, float scale_f,
                         float *F, hipStream_t s)
 {
-    return launch_scatter_wide_t<GWBP_MAP_F32>(L, W, V, M, D, scale_f, F, s, 0, 9);
+    return launch_scatter_wide_t<GWBP_MAP_F32>(L, W, V, M, D, scale_f, F, s);
 }
 
 } // namespace gwbp

@@ -15,9 +15,9 @@ int launch_scatter_wide_half(const Layout &L, const Ws &W, const ViewDev &V, con
                              hipStream_t s, int mt)
 {
     if (mt == GWBP_MAP_F16)
-        return launch_scatter_wide_t<GWBP_MAP_F16>(L, W, V, M, D, scale_f, F, s, 16, 17);
+        return launch_scatter_wide_t<GWBP_MAP_F16>(L, W, V, M, D, scale_f, F, s);
     if (mt == GWBP_MAP_BF16)
-        return launch_scatter_wide_t<GWBP_MAP_BF16>(L, W, V, M, D, scale_f, F, s, 18, 19);
+        return launch_scatter_wide_t<GWBP_MAP_BF16>(L, W, V, M, D, scale_f, F, s);
     return set_error(GWBP_EINVAL, "scatter_wide: unknown map type %d", mt);
 }
 

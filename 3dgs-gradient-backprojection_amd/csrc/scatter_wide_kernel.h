@@ -710,14 +710,15 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(76))) void
 
 } // namespace
 
-// The launch of one map type: LDS slots (ensure_dynamic_lds) of the full-resolution and the bilinear instantiation
+// The launch of one map type: the full-resolution or the bilinear instantiation
 template <int MT>
 int launch_scatter_wide_t(const Layout &L, const Ws &W, const ViewDev &V, const FeatMap &M, int D, float scale_f, float *F,
-                          hipStream_t s, int slot, int slot_bil)
+                          hipStream_t s)
 {
     const bool bil = M.bilinear();
-    int rc = bil ? ensure_dynamic_lds(reinterpret_cast<const void *>(k_scatter_wide<true, MT>), (int)kLdsBytes, slot_bil)
-                 : ensure_dynamic_lds(reinterpret_cast<const void *>(k_scatter_wide<false, MT>), (int)kLdsBytes, slot);
+    int rc = ensure_dynamic_lds(bil ? reinterpret_cast<const void *>(k_scatter_wide<true, MT>)
+                                    : reinterpret_cast<const void *>(k_scatter_wide<false, MT>),
+                                (int)kLdsBytes);
     if (rc)
         return rc;
     int n_cu = 0;

@@ -524,11 +524,11 @@ __global__ __launch_bounds__(kSmallThreads) void k_sort_small(u32 *__restrict__ 
 }
 
 template <int IPT>
-static int launch_sort_small(u32 *keys, u32 *vals, u32 n, int prio, int slot, const SmallEmit &em, hipStream_t s)
+static int launch_sort_small(u32 *keys, u32 *vals, u32 n, int prio, const SmallEmit &em, hipStream_t s)
 {
     const size_t lds = (size_t)(2 * IPT * kSmallThreads + kSmallWaves * 256 + 4) * sizeof(u32);
     if (lds > 64 * 1024) {
-        const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(k_sort_small<IPT>), (int)lds, slot);
+        const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(k_sort_small<IPT>), (int)lds);
         if (rc)
             return rc;
     }
@@ -682,11 +682,11 @@ int launch_bin_sort(const Layout &L, const Ws &W, const ViewDev &V, int64_t *ise
             const SmallEmit em = {W.touched, W.blocksums, W.counters, (u32)L.isect_cap};
             int rc1;
             if (L.n <= 4 * kSmallThreads)
-                rc1 = launch_sort_small<4>(W.dkeys[0], W.dvals[0], (u32)L.n, prio, 11, em, s);
+                rc1 = launch_sort_small<4>(W.dkeys[0], W.dvals[0], (u32)L.n, prio, em, s);
             else if (L.n <= 8 * kSmallThreads)
-                rc1 = launch_sort_small<8>(W.dkeys[0], W.dvals[0], (u32)L.n, prio, 12, em, s);
+                rc1 = launch_sort_small<8>(W.dkeys[0], W.dvals[0], (u32)L.n, prio, em, s);
             else
-                rc1 = launch_sort_small<12>(W.dkeys[0], W.dvals[0], (u32)L.n, prio, 13, em, s);
+                rc1 = launch_sort_small<12>(W.dkeys[0], W.dvals[0], (u32)L.n, prio, em, s);
             if (rc1 || (rc1 = launch_emit_scanned(L, W, V, W.dvals[0], s)))
                 return rc1;
         } else {

@@ -14,39 +14,24 @@
 // fills a run of empty cells).
 //
 // SEARCH.  One lane per query, queries in the order of their own cell keys, so that the lanes of a wave walk the same cells.
-// The running top-k is a sorted list in LDS, [k][threads], one column per lane.  Rings of Chebyshev radius r = 0, 1, 2, ...
-// around the query's cell, clipped to the grid; within a ring every run of cells along x is one contiguous span of the sorted
-// points.  No lane waits for another lane or workgroup: there is no barrier and no flag in the kernel.
+// The running top-k is LaneTopK<NearestFirst> (lane_topk.h): a sorted list in LDS, one column per lane.  The walk is ring_walk.h's,
+// whose header derives the bounds and the stop rule; nothing but the cut is particular to this kernel.  No lane waits for another
+// lane or workgroup: there is no barrier and no flag in the kernel.
 //
-// STOP RULE, and why it is exact although points are assigned to cells by a ROUNDED expression.  After ring r every unvisited
-// point p sits in a cell that differs from the query's by at least r + 1 along some axis, say cell(p) >= kf = cq + r + 1 (the
-// other side is symmetric).  Clamping only lowers a cell index from above, so the unclamped t(p) >= kf as well, i.e. the rounded
-// quotient u = fl(fl(p.x - lo) / h) >= kf.  A subtraction and a correctly rounded division are each within a factor
-// (1 +- 2^-24) of the exact result, so in exact arithmetic
-//       p.x - lo  >=  kf * h / (1 + 2^-24)^2  >=  kf * h * (1 - 2^-22).
-// This bounds the point's position relative to lo by the FACE's position, whatever the magnitude of p.x: the error of the
-// assignment is an ulp of |x - lo| scaled to cell units, not an ulp of the bound.  The exact distance along that axis is then
-//       (p.x - lo) - (q.x - lo)  >=  kf * h * (1 - 2^-22) - a,        a = q.x - lo.
-// In fp32: A = fl(q.x - lo) (|A - a| <= 2^-24 |a|), KH = fl(kf * h) (kf <= 1024 is exact, |KH - kf h| <= 2^-24 kf h),
-// B = fl(KH - A) (|B - (KH - A)| <= 2^-24 (KH + |A|)).  Together the exact bound is at least
-//       B - [ KH (2^-22 + 2^-23) + |A| 2^-23 ] (1 + small)   >   B - (KH + |A|) * 0.75 * 2^-21,
-// and LB = fl(B - fl((KH + |A|) * 2^-21)) keeps the remaining quarter for its own two roundings.  A non-positive or NaN LB
-// becomes 0 ("no bound").  The margin errs towards one more ring, never towards stopping.
-// From an exact |p.x - q.x| >= LB with LB a float, rounding being monotone gives |dx| = |fl(p.x - q.x)| >= LB, then
-// fl(dx * dx) >= fl(LB * LB), and each fmaf adds a non-negative term before a monotone rounding: the COMPUTED d2(p, q) >= fl(LB *
-// LB), whichever axis carried the bound.  The lane stops after ring r when its k-th d2 is STRICTLY below fl(LB * LB), LB the
-// smallest bound over the (up to six) directions that still have cells: strictly, because a point at exactly the bound could tie
-// with a smaller index.  A direction whose next ring has left the grid has no points (its bound is infinite); when all six have,
-// everything has been visited.  An open list has k-th d2 = +inf and never stops early.  The trip count is at most max(nx, ny, nz).
+// WHY THE k-TH d2 IS A VALID CUT.  The walk stops after a ring when cut() < fl(LB * LB), i.e. when every unvisited point has a
+// computed d2 strictly above the list's k-th d2 so far: no such point can enter the list, and the list only improves, so the cut
+// only falls.  STRICTLY, because a point at exactly the k-th d2 could tie with it and win by a smaller index.  An open list has
+// k-th d2 = +inf and never stops early.
 #include "gwbp_dev.h"
-#include "spatial_grid.h" // SpatialGrid, finite3, cell_axis, bound_above / bound_below, make_grid, grid_of
+#include "lane_topk.h"
+#include "ring_walk.h"
+#include "spatial_grid.h" // SpatialGrid, finite3, cell_axis, make_grid
 
 namespace gwbp {
 
 namespace {
 
 constexpr int kSpatialThreads = 128; // lanes (queries) per workgroup of the search; LDS = k * 128 * 8 B <= 32 KiB
-constexpr int kNoIndex = 0x7FFFFFFF; // an empty slot of the list: orders after every point at equal distance
 
 __global__ __launch_bounds__(256) void k_spatial_cell_keys(int64_t N, const float *__restrict__ P, int64_t ldp, SpatialGrid G,
                                                            int32_t *__restrict__ keys)
@@ -93,8 +78,7 @@ __global__ __launch_bounds__(kSpatialThreads) void k_spatial_knn(const float4 *_
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int T = kSpatialThreads;
     const int tid = threadIdx.x;
-    float *ld2 = smem + tid;                                   // [k][T] squared distances, ascending
-    int *lid = reinterpret_cast<int *>(smem + k * T) + tid;    // [k][T] their indices
+    LaneTopK<NearestFirst, T> best(smem, k, tid); // squared distances, ascending
 
     const int64_t slot = (int64_t)blockIdx.x * T + tid;
     if (slot >= Q)
@@ -110,100 +94,13 @@ __global__ __launch_bounds__(kSpatialThreads) void k_spatial_knn(const float4 *_
         }
         return;
     }
+    best.init();
+    ring_walk(S, cell_start, G, qx, qy, qz, [&] { return best.last_key; },
+              [&](float d2, const float4 &v, int) { best.offer(d2, __float_as_int(v.w)); });
     for (int j = 0; j < k; ++j) {
-        ld2[j * T] = __builtin_inff();
-        lid[j * T] = kNoIndex;
-    }
-    float kd = __builtin_inff(); // the list's last entry: the k-th best so far
-    int ki = kNoIndex;
-
-    const int nx = G.n[0], ny = G.n[1], nz = G.n[2];
-    const float h = G.h;
-    const int cx = cell_axis(qx, G.lo[0], h, nx), cy = cell_axis(qy, G.lo[1], h, ny), cz = cell_axis(qz, G.lo[2], h, nz);
-    const float ax = qx - G.lo[0], ay = qy - G.lo[1], az = qz - G.lo[2];
-
-    auto scan = [&](int b, int e) {
-        for (int p = b; p < e; ++p) {
-            const float4 v = S[p];
-            const float dx = v.x - qx, dy = v.y - qy, dz = v.z - qz;
-            const float d2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-            const int id = __float_as_int(v.w);
-            if (d2 < kd || (d2 == kd && id < ki)) {
-                int j = k - 1; // sorted insert: shift the entries that order after (d2, id) one down
-                while (j > 0) {
-                    const float pd = ld2[(j - 1) * T];
-                    const int pi = lid[(j - 1) * T];
-                    if (pd < d2 || (pd == d2 && pi < id))
-                        break;
-                    ld2[j * T] = pd;
-                    lid[j * T] = pi;
-                    --j;
-                }
-                ld2[j * T] = d2;
-                lid[j * T] = id;
-                kd = ld2[(k - 1) * T];
-                ki = lid[(k - 1) * T];
-            }
-        }
-    };
-
-    const int r_max = max(nx, max(ny, nz)); // the ring has left the grid on every side by then
-    for (int r = 0; r <= r_max; ++r) {
-        const int z0 = max(cz - r, 0), z1 = min(cz + r, nz - 1);
-        const int y0 = max(cy - r, 0), y1 = min(cy + r, ny - 1);
-        const int x0 = max(cx - r, 0), x1 = min(cx + r, nx - 1);
-        for (int z = z0; z <= z1; ++z) {
-            // rows y0 .. y1 of this slab over the grid's full width hold everything the ring visits in it: nothing there, nothing
-            // to visit (a floater in a border cell crosses the empty part of the grid in O(r) steps per ring, not O(r^2))
-            if (cell_start[(z * ny + y0) * nx] == cell_start[(z * ny + y1) * nx + nx])
-                continue;
-            for (int y = y0; y <= y1; ++y) {
-                const int base = (z * ny + y) * nx;
-                if (abs(z - cz) == r || abs(y - cy) == r) { // the whole run along x lies in the ring
-                    scan(cell_start[base + x0], cell_start[base + x1 + 1]);
-                } else { // (r > 0) only the two ends do
-                    if (cx - r >= 0)
-                        scan(cell_start[base + cx - r], cell_start[base + cx - r + 1]);
-                    if (cx + r <= nx - 1)
-                        scan(cell_start[base + cx + r], cell_start[base + cx + r + 1]);
-                }
-            }
-        }
-        // what is left lies r + 1 cells or more away along some axis: the smallest bound over the sides that still have cells
-        float lb = __builtin_inff();
-        bool any = false;
-        if (cx + r + 1 <= nx - 1) {
-            lb = fminf(lb, bound_above(ax, cx + r + 1, h));
-            any = true;
-        }
-        if (cx - r - 1 >= 0) {
-            lb = fminf(lb, bound_below(ax, cx - r, h));
-            any = true;
-        }
-        if (cy + r + 1 <= ny - 1) {
-            lb = fminf(lb, bound_above(ay, cy + r + 1, h));
-            any = true;
-        }
-        if (cy - r - 1 >= 0) {
-            lb = fminf(lb, bound_below(ay, cy - r, h));
-            any = true;
-        }
-        if (cz + r + 1 <= nz - 1) {
-            lb = fminf(lb, bound_above(az, cz + r + 1, h));
-            any = true;
-        }
-        if (cz - r - 1 >= 0) {
-            lb = fminf(lb, bound_below(az, cz - r, h));
-            any = true;
-        }
-        if (!any || kd < lb * lb)
-            break;
-    }
-
-    for (int j = 0; j < k; ++j) {
-        const int id = lid[j * T];
-        oi[j] = id == kNoIndex ? -1 : id;
-        od[j] = id == kNoIndex ? __builtin_inff() : sqrtf(ld2[j * T]);
+        const int id = best.index(j);
+        oi[j] = id;
+        od[j] = id < 0 ? __builtin_inff() : sqrtf(best.key(j)); // (the select keeps this loop scalar: 9 VGPRs fewer than without)
     }
 }
 
@@ -239,19 +136,7 @@ __global__ __launch_bounds__(256) void k_neighbor_mean(int64_t N, int64_t M, int
             const float n = (float)nv;
             acc = make_float4(acc.x / n, acc.y / n, acc.z / n, acc.w / n);
         }
-        float *o = out + g * ldo;
-        if (VEC && c + 4 <= D) {
-            *reinterpret_cast<float4 *>(o + c) = acc;
-        } else {
-            if (c < D)
-                o[c] = acc.x;
-            if (c + 1 < D)
-                o[c + 1] = acc.y;
-            if (c + 2 < D)
-                o[c + 2] = acc.z;
-            if (c + 3 < D)
-                o[c + 3] = acc.w;
-        }
+        store4<VEC>(out + g * ldo, c, D, acc);
     }
 }
 
@@ -288,22 +173,10 @@ int launch_spatial_knn(const float *sorted, const int32_t *cell_start, const flo
     unsigned grid;
     if (int rc = grid_of("spatial_knn", Q, &grid, kSpatialThreads))
         return rc;
-    const size_t lds = (size_t)k * kSpatialThreads * (sizeof(float) + sizeof(int)); // <= 32 KiB: below the default limit
+    const size_t lds = lane_columns_bytes(k, kSpatialThreads); // <= 32 KiB: below the default limit
     hipLaunchKernelGGL(k_spatial_knn, dim3(grid), dim3(kSpatialThreads), lds, s, reinterpret_cast<const float4 *>(sorted), cell_start,
                        make_grid(lo, h, dims), Q, queries, ldq, order, k, idx, dist);
     return check_hip(hipGetLastError(), "spatial_knn launch");
-}
-
-template <int MT>
-static void launch_neighbor_mean_t(unsigned grid, hipStream_t s, int64_t N, int64_t M, int D, int k, const int32_t *idx, const void *Fv,
-                                   int64_t ldf, float *out, int64_t ldo)
-{
-    const typename MapElem<MT>::raw *F = static_cast<const typename MapElem<MT>::raw *>(Fv);
-    const bool vec = field_rows_vec(Fv, ldf, MT) && field_rows_vec(out, ldo, GWBP_MAP_F32);
-    if (vec)
-        hipLaunchKernelGGL((k_neighbor_mean<MT, true>), dim3(grid), dim3(256), 0, s, N, M, D, k, idx, F, ldf, out, ldo);
-    else
-        hipLaunchKernelGGL((k_neighbor_mean<MT, false>), dim3(grid), dim3(256), 0, s, N, M, D, k, idx, F, ldf, out, ldo);
 }
 
 int launch_neighbor_mean(int64_t N, int64_t M, int D, int k, const int32_t *idx, const void *F, int mt, int64_t ldf, float *out,
@@ -314,12 +187,10 @@ int launch_neighbor_mean(int64_t N, int64_t M, int D, int k, const int32_t *idx,
     unsigned grid;
     if (int rc = grid_of("neighbor_mean", N, &grid, 4))
         return rc;
-    if (mt == GWBP_MAP_F16)
-        launch_neighbor_mean_t<GWBP_MAP_F16>(grid, s, N, M, D, k, idx, F, ldf, out, ldo);
-    else if (mt == GWBP_MAP_BF16)
-        launch_neighbor_mean_t<GWBP_MAP_BF16>(grid, s, N, M, D, k, idx, F, ldf, out, ldo);
-    else
-        launch_neighbor_mean_t<GWBP_MAP_F32>(grid, s, N, M, D, k, idx, F, ldf, out, ldo);
+    const bool vec = field_rows_vec(F, ldf, mt) && field_rows_vec(out, ldo, GWBP_MAP_F32);
+    with_field_type(mt, vec, [&](auto MT, auto VEC) {
+        hipLaunchKernelGGL((k_neighbor_mean<MT, VEC>), dim3(grid), dim3(256), 0, s, N, M, D, k, idx, field_ptr<MT>(F), ldf, out, ldo);
+    });
     return check_hip(hipGetLastError(), "neighbor_mean launch");
 }
 

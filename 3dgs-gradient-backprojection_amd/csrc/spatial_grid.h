@@ -1,6 +1,6 @@
-// spatial_grid.h -- the uniform grid that spatial.hip (k nearest neighbours) and components.hip (radius components) share: the grid
-// itself, THE cell assignment, and the lower bounds of the ring walk's stop rule.  The derivation of the bounds is in the header of
-// spatial.hip; both files' stop rules rest on it, and on every kernel using this one cell expression.
+// spatial_grid.h -- the uniform grid that spatial.hip (k nearest neighbours), components.hip (radius components) and sample.hip
+// share: the grid itself, THE cell assignment, and the lower bounds of the ring walk's stop rule.  The derivation of the bounds is in
+// the header of ring_walk.h; the stop rule rests on it, and on every kernel using this one cell expression.
 #pragma once
 #include "gwbp_dev.h"
 
@@ -19,14 +19,14 @@ __device__ __forceinline__ bool finite3(float x, float y, float z)
     return fabsf(x) < __builtin_inff() && fabsf(y) < __builtin_inff() && fabsf(z) < __builtin_inff(); // false for NaN
 }
 
-// THE cell assignment (see the header of spatial.hip): every kernel and the stop rule's derivation use this one expression.
+// THE cell assignment (see the header of spatial.hip for the grid): every kernel and the stop rule's derivation use this one expression.
 __device__ __forceinline__ int cell_axis(float x, float lo, float h, int n)
 {
     const float t = floorf((x - lo) / h);
     return (int)fminf(fmaxf(t, 0.0f), (float)(n - 1)); // (finite x: an overflowed difference is +-inf, and clamps to a border cell)
 }
 
-// lower bounds of the stop rule (header of spatial.hip): on the distance along one axis to any point in a cell >= kf / in a cell < kf
+// lower bounds of the stop rule (header of ring_walk.h): on the distance along one axis to any point in a cell >= kf / in a cell < kf
 __device__ __forceinline__ float bound_above(float A, int kf, float h)
 {
     const float KH = (float)kf * h;
@@ -49,15 +49,6 @@ __device__ __forceinline__ float bound_below(float A, int kf, float h)
     }
     G.h = h;
     return G;
-}
-
-[[maybe_unused]] int grid_of(const char *what, int64_t n, unsigned *grid, int per_block)
-{
-    const int64_t g = (n + per_block - 1) / per_block;
-    if (g > 0x7FFFFFFF)
-        return set_error(GWBP_EINVAL, "%s: %lld items need more than 2^31 - 1 workgroups", what, (long long)n);
-    *grid = (unsigned)g;
-    return GWBP_OK;
 }
 
 } // namespace
