@@ -244,7 +244,8 @@ ARGTYPES = {
 }
 # The typed forms of the entry points that read a finished [N, D] FIELD (or, gwbp_finalize_typed, write one): the untyped function's
 # arguments with the field's element type (GWBP_MAP_*, MAP_TYPES' codes) behind the field pointer.  A table of their own: they take no
-# (caps, workspace, view), which is what the "_typed" names of ARGTYPES -- the typed scatters -- all start with.
+# (caps, workspace, view), which is what the "_typed" names of ARGTYPES -- the typed scatters -- all start with; the four at the end,
+# which read a field as a render payload, do.  The two _out_typed forms add the element type of `out` behind its pointer.
 FIELD_ARGTYPES = {
     "gwbp_finalize_typed": [_I64, _I32, _P, _P, _P, _I32, _P],
     "gwbp_knn_search_typed": [_I64, _I32, _I32, _I32, _P, _I32, _I64, _P, _I64, _P, _P, _P],
@@ -257,6 +258,15 @@ FIELD_ARGTYPES = {
     "gwbp_kmeans_assign_typed": [_I64, _I32, _I32, _P, _I32, _I64, _P, _I64, _P, _P, _P, _P],
     "gwbp_cluster_sums_typed": [_I64, _I32, _I32, _P, _I32, _I64, _P, _P, _P, _P, _P, _P, _SZ, _P],
     "gwbp_prompt_scores_typed": [_I64, _I32, _I32, _I32, _P, _I32, _I64, _P, _I32, C.POINTER(C.c_float), _P, _P, _P],
+    "gwbp_neighbor_mean_out_typed": [_I64, _I64, _I32, _I32, _P, _P, _I32, _I64, _P, _I32, _I64, _P],
+    "gwbp_neighbor_blend_out_typed": [_I64, _I64, _I32, _I32, _P, _P, _P, _I32, _I64, _P, _I32, _I64, _P, _P],
+    # colors, color_type, ldc, D, out, out_type, stream  /  colors, color_type, ldc, D, out, alphas, stream
+    "gwbp_render_typed": _WSV + [_P, _I32, _I64, _I32, _P, _I32, _P],
+    "gwbp_render_pixels_typed": _WSV + [_P, _I32, _I64, _I32, _P, _P, _P],
+    # M, xy, X, field_type, ldx, D, out, depth, alpha, stream
+    "gwbp_probe_pixels_typed": _WSV + [_I32, _P, _P, _I32, _I64, _I32, _P, _P, _P, _P],
+    # features, field_type, ldf, D, map, map_type, ms_y, ms_x, lr_h, lr_w, ymap, xmap, planes, table, stream
+    "gwbp_field_compare_typed": _WSV + [_P, _I32, _I64, _I32, _P, _I32, _I64, _I64, _I32, _I32, _P, _P, _P, _P, _P],
 }
 LOSS_KINDS = {"l1": 0, "l2": 1}  # GWBP_LOSS_*
 # every symbol of include/gwbp.h: the two functions that return strings, then the int-returning ones declared above

@@ -13,6 +13,8 @@ import torch
 from ._lib import GwbpError, check, lib
 from .engine import MAP_TYPES as FIELD_TYPES  # dtype -> GWBP_MAP_*: a finished field has a feature map's element types
 from .engine import Engine
+from .engine import field_rows  # noqa: F401  (the Engine's own payload check; re-exported for the modules on a finished field)
+from .engine import row_stride as ld  # noqa: F401
 from .rasterization import get_engine, run_front
 
 RASTER_KW = dict(near_plane=0.01, far_plane=1e10, eps2d=0.3, radius_clip=0.0, camera_model="pinhole", rasterize_mode="classic")
@@ -46,25 +48,12 @@ def rows(t: torch.Tensor, name: str) -> torch.Tensor:
     return t
 
 
-
-
-def field_rows(t: torch.Tensor, name: str):
-    """(tensor, GWBP_MAP_* code) of a finished [rows, D] FIELD as it is stored: float32, float16 or bfloat16, read by the *_typed entry
-    points without a float32 copy.  rows()'s shape and stride rules, in elements; a layout the kernels cannot read is made contiguous in
-    the tensor's own dtype."""
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise GwbpError(f"{name} must be a HIP tensor (no CPU fallback exists for this path)")
-    if t.dim() != 2 or t.shape[1] < 1:
-        raise GwbpError(f"{name} must be [rows, D] with D >= 1, got {tuple(t.shape)}")
-    if t.dtype not in FIELD_TYPES:
-        raise GwbpError(f"{name} must be float32, float16 or bfloat16, got {t.dtype}")
-    if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-        t = t.contiguous()
-    return t, FIELD_TYPES[t.dtype]
-
-
-def ld(t: torch.Tensor) -> int:
-    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])  # (the stride of a single row means nothing)
+def out_type(fn: str, out_dtype):
+    """(torch dtype, GWBP_MAP_* code) of an out_dtype keyword: None means float32."""
+    dtype = torch.float32 if out_dtype is None else out_dtype
+    if dtype not in FIELD_TYPES:
+        raise GwbpError(f"{fn}: out_dtype must be None, float32, float16 or bfloat16, got {out_dtype!r}")
+    return dtype, FIELD_TYPES[dtype]
 
 
 def run(name: str, device, *args):

@@ -15,6 +15,8 @@ import torch
 
 from . import scene_io, synthetic as syn
 
+# the names the command lines give a field's element type (--field-dtype, --out-dtype)
+FIELD_DTYPES = {"fp32": torch.float32, "fp16": torch.float16, "bf16": torch.bfloat16}
 SCENE_OPTIONS = ("data-dir", "checkpoint", "format", "data-factor", "synthetic", "camera-model", "rasterize-mode", "max-views")
 
 

@@ -939,28 +939,70 @@ int gwbp_label_votes_sparse(const gwbp_caps *caps, void *workspace, size_t works
                                      vals, ld_vals, spill, total, B.s);
 }
 
-int gwbp_render(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
-                const float *colors, int32_t D, float *out, void *stream)
+// What the two typed renders add to the untyped functions' checks: the table's row stride and the alignment of the table and of out to
+// their elements (an fp32 pointer of the untyped functions was never looked at: a misaligned one is refused here as well).
+static int check_render_payload(const char *what, const void *colors, int32_t color_type, int64_t ldc, int32_t D, const void *out,
+                                int32_t out_type)
 {
+    if (ldc < D)
+        return set_error(GWBP_EINVAL, "%s: row stride %lld below D = %d", what, (long long)ldc, (int)D);
+    if (fp32_off(colors, color_type) || fp32_off(out, out_type))
+        return set_error(GWBP_EINVAL, "%s: fp32 colors and out must be 4-B aligned", what);
+    if (int rc = check_half_alignment(what, "colors", colors, color_type))
+        return rc;
+    if (int rc = check_half_alignment(what, "out", out, out_type))
+        return rc;
+    if (out_type != GWBP_MAP_F32 && colors == static_cast<const void *>(out))
+        return set_error(GWBP_EINVAL, "%s: a half out must not alias colors", what);
+    return GWBP_OK;
+}
+
+int gwbp_render_typed(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host, const void *colors,
+                      int32_t color_type, int64_t ldc, int32_t D, void *out, int32_t out_type, void *stream)
+{
+    if (int rc = check_field_type("render (color_type)", color_type))
+        return rc;
+    if (int rc = check_field_type("render (out_type)", out_type))
+        return rc;
     Bound B;
     int rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B);
     if (rc)
         return rc;
     if (!colors || !out || D < 1)
         return set_error(GWBP_EINVAL, "bad render arguments");
-    return launch_render(B.L, B.W, B.V, colors, D, out, B.s);
+    if ((rc = check_render_payload("render", colors, color_type, ldc, D, out, out_type)))
+        return rc;
+    return launch_render(B.L, B.W, B.V, colors, color_type, ldc, D, out, out_type, B.s);
 }
 
-int gwbp_render_pixels(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
-                       const float *colors, int32_t D, float *out, float *alphas, void *stream)
+int gwbp_render(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                const float *colors, int32_t D, float *out, void *stream)
 {
+    return gwbp_render_typed(caps, workspace, workspace_bytes, view_host, colors, GWBP_MAP_F32, D, D, out, GWBP_MAP_F32, stream);
+}
+
+int gwbp_render_pixels_typed(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                             const void *colors, int32_t color_type, int64_t ldc, int32_t D, float *out, float *alphas, void *stream)
+{
+    if (int rc = check_field_type("render_pixels", color_type))
+        return rc;
     Bound B;
     int rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B);
     if (rc)
         return rc;
     if (!colors || !out || D < 1 || D > 32)
         return set_error(GWBP_EINVAL, "render_pixels needs colors, out and 1 <= D <= 32 (got D=%d)", D);
-    return launch_render_px(B.W, B.V, colors, D, out, alphas, B.s);
+    if ((rc = check_render_payload("render_pixels", colors, color_type, ldc, D, out, GWBP_MAP_F32)))
+        return rc;
+    if (reinterpret_cast<uintptr_t>(alphas) & 3)
+        return set_error(GWBP_EINVAL, "render_pixels: alphas must be 4-B aligned");
+    return launch_render_px(B.W, B.V, colors, color_type, ldc, D, out, alphas, B.s);
+}
+
+int gwbp_render_pixels(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                       const float *colors, int32_t D, float *out, float *alphas, void *stream)
+{
+    return gwbp_render_pixels_typed(caps, workspace, workspace_bytes, view_host, colors, GWBP_MAP_F32, D, D, out, alphas, stream);
 }
 
 int gwbp_sh_colors(int64_t N, int32_t degree, int32_t K, const float *means, const float *coeffs,
@@ -1155,10 +1197,12 @@ int gwbp_spatial_knn(int64_t n, const float *sorted, const int32_t *cell_start, 
     return launch_spatial_knn(sorted, cell_start, lo, cell_size, dims, q, queries, ldq, order, k, idx, dist, as_stream(stream));
 }
 
-int gwbp_neighbor_mean_typed(int64_t n, int64_t m, int32_t D, int32_t k, const int32_t *idx, const void *features, int32_t field_type,
-                             int64_t ldf, float *out, int64_t ldo, void *stream)
+int gwbp_neighbor_mean_out_typed(int64_t n, int64_t m, int32_t D, int32_t k, const int32_t *idx, const void *features,
+                                 int32_t field_type, int64_t ldf, void *out, int32_t out_type, int64_t ldo, void *stream)
 {
     if (int rc = check_field_type("neighbor_mean", field_type))
+        return rc;
+    if (int rc = check_field_type("neighbor_mean (out_type)", out_type))
         return rc;
     if (n < 0 || m < 1 || m > 0x7FFFFFFF || D < 1)
         return set_error(GWBP_EINVAL, "neighbor_mean: bad sizes (n=%lld m=%lld D=%d)", (long long)n, (long long)m, (int)D);
@@ -1168,13 +1212,21 @@ int gwbp_neighbor_mean_typed(int64_t n, int64_t m, int32_t D, int32_t k, const i
         return set_error(GWBP_EINVAL, "neighbor_mean: row strides (%lld, %lld) below D = %d", (long long)ldf, (long long)ldo, (int)D);
     if (!features || (n > 0 && (!idx || !out)))
         return set_error(GWBP_EINVAL, "neighbor_mean: null idx, features or out");
-    if (fp32_off(features, field_type) || (reinterpret_cast<uintptr_t>(out) & 3))
+    if (fp32_off(features, field_type) || fp32_off(out, out_type))
         return set_error(GWBP_EINVAL, "neighbor_mean: features and out must be 4-B aligned");
     if (int rc = check_half_alignment("neighbor_mean", "features", features, field_type))
         return rc;
+    if (int rc = check_half_alignment("neighbor_mean", "out", out, out_type))
+        return rc;
     if (features == static_cast<const void *>(out))
-        return set_error(GWBP_EINVAL, "neighbor_mean: out must not be the features");
-    return launch_neighbor_mean(n, m, D, k, idx, features, field_type, ldf, out, ldo, as_stream(stream));
+        return set_error(GWBP_EINVAL, "neighbor_mean: out must not be the features (no alias, whatever its type)");
+    return launch_neighbor_mean(n, m, D, k, idx, features, field_type, ldf, out, out_type, ldo, as_stream(stream));
+}
+
+int gwbp_neighbor_mean_typed(int64_t n, int64_t m, int32_t D, int32_t k, const int32_t *idx, const void *features, int32_t field_type,
+                             int64_t ldf, float *out, int64_t ldo, void *stream)
+{
+    return gwbp_neighbor_mean_out_typed(n, m, D, k, idx, features, field_type, ldf, out, GWBP_MAP_F32, ldo, stream);
 }
 
 int gwbp_neighbor_mean(int64_t n, int64_t m, int32_t D, int32_t k, const int32_t *idx, const float *features, int64_t ldf,
@@ -1419,10 +1471,12 @@ int gwbp_point_gaussians(int64_t n, const float *sorted, const int32_t *cell_sta
                                   n_contrib, visited, as_stream(stream));
 }
 
-int gwbp_neighbor_blend_typed(int64_t q, int64_t m, int32_t D, int32_t k, const int32_t *idx, const float *w, const void *features,
-                              int32_t field_type, int64_t ldf, float *out, int64_t ldo, float *wsum, void *stream)
+int gwbp_neighbor_blend_out_typed(int64_t q, int64_t m, int32_t D, int32_t k, const int32_t *idx, const float *w, const void *features,
+                                  int32_t field_type, int64_t ldf, void *out, int32_t out_type, int64_t ldo, float *wsum, void *stream)
 {
     if (int rc = check_field_type("neighbor_blend", field_type))
+        return rc;
+    if (int rc = check_field_type("neighbor_blend (out_type)", out_type))
         return rc;
     if (int rc = check_weighted_list("neighbor_blend", q, m, k, idx, w))
         return rc;
@@ -1432,15 +1486,23 @@ int gwbp_neighbor_blend_typed(int64_t q, int64_t m, int32_t D, int32_t k, const 
         return set_error(GWBP_EINVAL, "neighbor_blend: row strides (%lld, %lld) below D = %d", (long long)ldf, (long long)ldo, (int)D);
     if (!features || (q > 0 && (!out || !wsum)))
         return set_error(GWBP_EINVAL, "neighbor_blend: null features, out or wsum");
-    if (fp32_off(features, field_type) || misaligned(out, 3) || misaligned(wsum, 3))
+    if (fp32_off(features, field_type) || fp32_off(out, out_type) || misaligned(wsum, 3))
         return set_error(GWBP_EINVAL, "neighbor_blend: features, out and wsum must be 4-B aligned");
     if (int rc = check_half_alignment("neighbor_blend", "features", features, field_type))
+        return rc;
+    if (int rc = check_half_alignment("neighbor_blend", "out", out, out_type))
         return rc;
     const void *const written[] = {out, wsum}, *const read[] = {idx, w, features};
     if (q > 0)
         if (int rc = check_regions_distinct("neighbor_blend", written, 2, read, 3))
             return rc;
-    return launch_neighbor_blend(q, m, D, k, idx, w, features, field_type, ldf, out, ldo, wsum, as_stream(stream));
+    return launch_neighbor_blend(q, m, D, k, idx, w, features, field_type, ldf, out, out_type, ldo, wsum, as_stream(stream));
+}
+
+int gwbp_neighbor_blend_typed(int64_t q, int64_t m, int32_t D, int32_t k, const int32_t *idx, const float *w, const void *features,
+                              int32_t field_type, int64_t ldf, float *out, int64_t ldo, float *wsum, void *stream)
+{
+    return gwbp_neighbor_blend_out_typed(q, m, D, k, idx, w, features, field_type, ldf, out, GWBP_MAP_F32, ldo, wsum, stream);
 }
 
 int gwbp_neighbor_blend(int64_t q, int64_t m, int32_t D, int32_t k, const int32_t *idx, const float *w, const float *features,
@@ -1699,14 +1761,16 @@ int gwbp_prompt_scores(int64_t N, int32_t D, int32_t P, int32_t n_pos, const flo
     return gwbp_prompt_scores_typed(N, D, P, n_pos, X, GWBP_MAP_F32, ldx, prompts, normalize, threshold_host, mask, scores, stream);
 }
 
-int gwbp_probe_pixels(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host, int32_t M,
-                      const int32_t *xy, const float *X, int64_t ldx, int32_t D, float *out, float *depth, float *alpha,
-                      void *stream)
+int gwbp_probe_pixels_typed(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host, int32_t M,
+                            const int32_t *xy, const void *X, int32_t field_type, int64_t ldx, int32_t D, float *out, float *depth,
+                            float *alpha, void *stream)
 {
+    if (int rc0 = check_field_type("probe_pixels", field_type))
+        return rc0;
     // the probe's own arguments first: nothing of the caps, the workspace or the view is looked at before they pass
     if (M < 1 || M > GWBP_PROBE_MAX_PIXELS)
         return set_error(GWBP_EINVAL, "probe_pixels: M must be in [1, %d] (got %d)", GWBP_PROBE_MAX_PIXELS, (int)M);
-    int rc = check_field_rows("probe_pixels", D, X, ldx);
+    int rc = check_field_rows("probe_pixels", D, X, ldx, field_type);
     if (rc)
         return rc;
     if (!xy || !out || (reinterpret_cast<uintptr_t>(xy) & 3) || (reinterpret_cast<uintptr_t>(out) & 3))
@@ -1716,7 +1780,14 @@ int gwbp_probe_pixels(const gwbp_caps *caps, void *workspace, size_t workspace_b
     Bound B;
     if ((rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B)))
         return rc;
-    return launch_probe_pixels(B.W, B.V, M, xy, X, ldx, D, out, depth, alpha, B.s);
+    return launch_probe_pixels(B.W, B.V, M, xy, X, field_type, ldx, D, out, depth, alpha, B.s);
+}
+
+int gwbp_probe_pixels(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host, int32_t M,
+                      const int32_t *xy, const float *X, int64_t ldx, int32_t D, float *out, float *depth, float *alpha,
+                      void *stream)
+{
+    return gwbp_probe_pixels_typed(caps, workspace, workspace_bytes, view_host, M, xy, X, GWBP_MAP_F32, ldx, D, out, depth, alpha, stream);
 }
 
 int gwbp_render_labels(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
@@ -1752,11 +1823,13 @@ int gwbp_render_labels(const gwbp_caps *caps, void *workspace, size_t workspace_
                                 reinterpret_cast<u64 *>(counts), B.s);
 }
 
-int gwbp_field_compare(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
-                       const float *features, int64_t ldf, int32_t D, const void *map, int32_t map_type, int64_t ms_y, int64_t ms_x,
-                       int32_t lr_h, int32_t lr_w, const int32_t *ymap, const int32_t *xmap, float *planes, double *table,
-                       void *stream)
+int gwbp_field_compare_typed(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                             const void *features, int32_t field_type, int64_t ldf, int32_t D, const void *map, int32_t map_type,
+                             int64_t ms_y, int64_t ms_x, int32_t lr_h, int32_t lr_w, const int32_t *ymap, const int32_t *xmap,
+                             float *planes, double *table, void *stream)
 {
+    if (int rc0 = check_field_type("field_compare", field_type))
+        return rc0;
     // the caps, the workspace and the view first (as gwbp_render), then the call's own arguments, each kind once
     Bound B;
     int rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B);
@@ -1768,8 +1841,10 @@ int gwbp_field_compare(const gwbp_caps *caps, void *workspace, size_t workspace_
         return set_error(GWBP_EINVAL, "field_compare: D must be in [1, %d] (got %d)", GWBP_PCA_MAX_D, (int)D);
     if (ldf < D)
         return set_error(GWBP_EINVAL, "field_compare: row stride %lld below D = %d", (long long)ldf, (int)D);
-    if ((!features && B.L.n > 0) || (reinterpret_cast<uintptr_t>(features) & 3))
+    if ((!features && B.L.n > 0) || fp32_off(features, field_type))
         return set_error(GWBP_EINVAL, "field_compare: features must be a non-null, 4-B aligned [N, D] array");
+    if ((rc = check_half_alignment("field_compare", "features", features, field_type)))
+        return rc;
     if (!map || (reinterpret_cast<uintptr_t>(map) & (map_type == GWBP_MAP_F32 ? 3 : 1)))
         return set_error(GWBP_EINVAL, "field_compare: the map must be non-null and aligned to its element type");
     if (ms_y < 0 || ms_x < 0)
@@ -1788,8 +1863,17 @@ int gwbp_field_compare(const gwbp_caps *caps, void *workspace, size_t workspace_
     if (B.V.tile_w * B.V.tile_h > GWBP_FIELD_COMPARE_MAX_TILES)
         return set_error(GWBP_EINVAL, "field_compare: a view of %d tiles exceeds GWBP_FIELD_COMPARE_MAX_TILES = %d",
                          B.V.tile_w * B.V.tile_h, GWBP_FIELD_COMPARE_MAX_TILES);
-    return launch_field_compare(B.L, B.W, B.V, features, ldf, D, map, map_type, ms_y, ms_x, ymap ? lr_h : 0, ymap ? lr_w : 0, ymap,
-                                xmap, planes, table, B.s);
+    return launch_field_compare(B.L, B.W, B.V, features, field_type, ldf, D, map, map_type, ms_y, ms_x, ymap ? lr_h : 0, ymap ? lr_w : 0,
+                                ymap, xmap, planes, table, B.s);
+}
+
+int gwbp_field_compare(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                       const float *features, int64_t ldf, int32_t D, const void *map, int32_t map_type, int64_t ms_y, int64_t ms_x,
+                       int32_t lr_h, int32_t lr_w, const int32_t *ymap, const int32_t *xmap, float *planes, double *table,
+                       void *stream)
+{
+    return gwbp_field_compare_typed(caps, workspace, workspace_bytes, view_host, features, GWBP_MAP_F32, ldf, D, map, map_type, ms_y,
+                                    ms_x, lr_h, lr_w, ymap, xmap, planes, table, stream);
 }
 
 // the shape contract of the decode-loss kernels: what they are not built for is unsupported, not invalid

@@ -282,9 +282,12 @@ int launch_label_votes_sparse(const Layout &L, const Ws &W, const ViewDev &V, co
                               int64_t ls_x, const int32_t *ymap, const int32_t *xmap, int K, const int32_t *remap, int slots,
                               int32_t *keys, int64_t ld_keys, int64_t *vals, int64_t ld_vals, int64_t *spill, int64_t *total,
                               hipStream_t s);
-int launch_render(const Layout &L, const Ws &W, const ViewDev &V, const float *colors, int D, float *out,
+// mt / ot (GWBP_MAP_*): the element types of colors (row stride ldc, in elements) and of out (dense [H, W, D])
+int launch_render(const Layout &L, const Ws &W, const ViewDev &V, const void *colors, int mt, int64_t ldc, int D, void *out, int ot,
                   hipStream_t s);
-int launch_render_px(const Ws &W, const ViewDev &V, const float *colors, int D, float *out, float *alphas,
+// the instantiations with a half table or a half output (render_wide_half.hip); the caller checks the launch
+void launch_render_half(const Ws &W, const ViewDev &V, const void *colors, int mt, int64_t ldc, int D, void *out, int ot, hipStream_t s);
+int launch_render_px(const Ws &W, const ViewDev &V, const void *colors, int mt, int64_t ldc, int D, float *out, float *alphas,
                      hipStream_t s);
 int launch_sh_colors(int64_t N, int degree, int K, const float *means, const float *coeffs, const float *campos,
                      float *out, hipStream_t s);
@@ -295,9 +298,13 @@ int launch_render_labels(const Ws &W, const ViewDev &V, const int32_t *labels, i
 // a field rendered from the weight store and compared with the view's map (field_compare.hip): planes [6][H][W] or nullptr, table
 // [8] float64; the rows' partial sums take field_compare_scratch_bytes(tiles) of the workspace's carry slices
 size_t field_compare_scratch_bytes(int n_tiles);
-int launch_field_compare(const Layout &L, const Ws &W, const ViewDev &V, const float *feats, int64_t ldf, int D, const void *map,
+// (ft: the element type of feats, ldf in its elements)
+int launch_field_compare(const Layout &L, const Ws &W, const ViewDev &V, const void *feats, int ft, int64_t ldf, int D, const void *map,
                          int mt, int64_t ms_y, int64_t ms_x, int lr_h, int lr_w, const int32_t *ymap, const int32_t *xmap,
                          float *planes, double *table, hipStream_t s);
+// the half-field instantiations (field_compare_half.hip); cmp_map: field_compare_kernel.h's CmpMap; the caller checks the launch
+void launch_field_compare_half(int ft, int mt, bool wide2, bool vec, unsigned grid, hipStream_t s, const ViewDev &V, int empty, const Ws &W,
+                               const void *feats, int64_t ldf, int D, const void *cmp_map, float *planes, double *rowsums);
 // decode, compare and the gradients back through the decoder of a rendered latent field (decode_loss.hip); table [8] float64; ws:
 // the caller's decode_loss_workspace_bytes(d, D) bytes
 size_t decode_loss_workspace_bytes(int d, int D);
@@ -322,7 +329,8 @@ int launch_spatial_build(int64_t N, const float *P, int64_t ldp, const int32_t *
                          float *sorted, int32_t *cell_start, hipStream_t s);
 int launch_spatial_knn(const float *sorted, const int32_t *cell_start, const float *lo, float h, const int32_t *dims, int64_t Q,
                        const float *queries, int64_t ldq, const int64_t *order, int k, int32_t *idx, float *dist, hipStream_t s);
-int launch_neighbor_mean(int64_t N, int64_t M, int D, int k, const int32_t *idx, const void *F, int mt, int64_t ldf, float *out,
+// (ot: the element type of out, ldo in ITS elements)
+int launch_neighbor_mean(int64_t N, int64_t M, int D, int k, const int32_t *idx, const void *F, int mt, int64_t ldf, void *out, int ot,
                          int64_t ldo, hipStream_t s);
 // radius components on the same grid (components.hip): neighbour counts within a radius, the union-find over the core points, the
 // border points' nearest core neighbour, and the roots.  group / query_group / attach / visited may be nullptr
@@ -351,7 +359,7 @@ int launch_point_gaussians(const float *sorted, const int32_t *cell_start, const
                            const float *pack, float r2, float alpha_min, int64_t Q, const float *queries, int64_t ldq,
                            const int64_t *order, int k, int32_t *idx, float *w, int32_t *n_contrib, int32_t *visited, hipStream_t s);
 int launch_neighbor_blend(int64_t Q, int64_t M, int D, int k, const int32_t *idx, const float *w, const void *F, int mt, int64_t ldf,
-                          float *out, int64_t ldo, float *wsum, hipStream_t s);
+                          void *out, int ot, int64_t ldo, float *wsum, hipStream_t s);
 int launch_weighted_vote(int64_t Q, int64_t M, int k, const int32_t *idx, const float *w, const int32_t *labels, int K,
                          int32_t *out_label, float *out_share, hipStream_t s);
 // PCA of a finished field (pca.hip): column means, centred Gram, projection onto k <= 16 components, colours.  ws: the caller's
@@ -377,8 +385,10 @@ int launch_prompt_scores(int64_t N, int D, int P, int n_pos, const void *X, int 
 // the fp16 / bf16 instantiations of k_prompt_scores (query_half.hip); the caller checks the launch
 void launch_prompt_scores_half(unsigned grid, hipStream_t s, int64_t N, int D, int P, int n_pos, const void *X, int mt, int64_t ldx,
                                const float *prompts, int normalize, int use_thr, float thr, uint8_t *mask, float *scores);
-int launch_probe_pixels(const Ws &W, const ViewDev &V, int M, const int32_t *xy, const float *X, int64_t ldx, int D, float *out,
+int launch_probe_pixels(const Ws &W, const ViewDev &V, int M, const int32_t *xy, const void *X, int mt, int64_t ldx, int D, float *out,
                         float *depth, float *alpha, hipStream_t s);
+void launch_probe_pixels_half(const Ws &W, const ViewDev &V, int M, const int32_t *xy, const void *X, int mt, int64_t ldx, int D,
+                              float *out, float *depth, float *alpha, hipStream_t s);
 int launch_dump_pairs(const Layout &L, const Ws &W, const ViewDev &V, int64_t cap, int32_t *gid, int32_t *pix,
                       float *w, u64 *n_dev, hipStream_t s);
 int launch_accum_stats(const Ws &W, gwbp_stats *accum, hipStream_t s);
@@ -620,6 +630,36 @@ __device__ __forceinline__ typename MapElem<OT>::raw narrow(float x)
             return (unsigned short)0x7FC0u;
         return (unsigned short)((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16);
     }
+}
+
+// store4 for a row of a typed OUTPUT: the columns of v below D, each narrow<OT>'d.  VEC, half rows: ONE 8-B store (load4raw's rule: the
+// row address 8-B aligned, the row stride a multiple of 4 elements, c a multiple of 4).  For GWBP_MAP_F32 it IS store4.
+template <int OT, bool VEC>
+__device__ __forceinline__ void store4t(void *__restrict__ row, int c, int D, float4 v)
+{
+    if constexpr (OT == GWBP_MAP_F32) {
+        store4<VEC>(static_cast<float *>(row), c, D, v);
+    } else {
+        unsigned short *p = static_cast<unsigned short *>(row);
+        const unsigned short e0 = narrow<OT>(v.x), e1 = narrow<OT>(v.y), e2 = narrow<OT>(v.z), e3 = narrow<OT>(v.w);
+        if (VEC && c + 4 <= D) {
+            *reinterpret_cast<uint2 *>(p + c) = make_uint2((u32)e0 | ((u32)e1 << 16), (u32)e2 | ((u32)e3 << 16));
+            return;
+        }
+        if (c < D)
+            p[c] = e0;
+        if (c + 1 < D)
+            p[c + 1] = e1;
+        if (c + 2 < D)
+            p[c + 2] = e2;
+        if (c + 3 < D)
+            p[c + 3] = e3;
+    }
+}
+template <int OT>
+typename MapElem<OT>::raw *out_ptr(void *p)
+{
+    return static_cast<typename MapElem<OT>::raw *>(p);
 }
 
 __device__ __forceinline__ u32 uniform(u32 v) { return (u32)__builtin_amdgcn_readfirstlane((int)v); }

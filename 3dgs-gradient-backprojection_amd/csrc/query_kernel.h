@@ -1,5 +1,5 @@
-// query_kernel.h -- k_prompt_scores (see query.hip for the contract) as a template over the element type of the field, and its typed
-// launcher: query.hip instantiates it for fp32 fields, query_half.hip for fp16 / bf16 ones.
+// query_kernel.h -- k_prompt_scores and k_probe_pixels (see query.hip for the contracts) as templates over the element type of the
+// field, and their typed launchers: query.hip instantiates it for fp32 fields, query_half.hip for fp16 / bf16 ones.
 #pragma once
 #include "gwbp_dev.h"
 
@@ -157,6 +157,107 @@ void launch_prompt_scores_t(unsigned grid, hipStream_t s, int64_t N, int D, int 
             hipLaunchKernelGGL((k_prompt_scores<MT, VEC, ONE ? 1 : 2>), dim3(grid), dim3(kQThreads), 0, s, N, D, P, n_pos,
                                field_ptr<MT>(Xv), ldx, prompts, normalize, use_thr, thr, mask, scores);
         });
+    });
+}
+
+// ---- probe ----------------------------------------------------------------------------------------------------------------------
+constexpr int kProbeChunk = 256; // channels per wave: four per lane
+
+__device__ __forceinline__ float uniform_f(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+__device__ __forceinline__ float lane_f(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+
+// One wave per (probe, 256-channel chunk).  Per batch of 64 list entries: lanes = entries compute sigma and alpha; the wave then
+// advances T entry by entry in list order (uniform values) and leaves each entry's weight in its lane; at last the entries that
+// have a weight are added front to back, lanes = channels.
+// MT: the element type of X (a half row is widened where it is loaded: the chains are those of the fp32 kernel on the widened table)
+template <int MT, bool VEC>
+__global__ __launch_bounds__(64) void k_probe_pixels(ViewDev V, const u32 *__restrict__ tile_offsets, const u32 *__restrict__ vals,
+                                                     const G2D *__restrict__ g2d, const int32_t *__restrict__ xy,
+                                                     const typename MapElem<MT>::raw *__restrict__ X, int64_t ldx, int D,
+                                                     float *__restrict__ out,
+                                                     float *__restrict__ depth, float *__restrict__ alpha_out)
+{
+    const int probe = (int)blockIdx.x, chunk = (int)blockIdx.y;
+    const int lane = threadIdx.x;
+    const int c = chunk * kProbeChunk + 4 * lane;
+    const int ix = (int)uniform((u32)xy[2 * probe]), iy = (int)uniform((u32)xy[2 * probe + 1]);
+    const bool inside = ix >= 0 && ix < V.W && iy >= 0 && iy < V.H;
+
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    float zacc = 0.f, T = 1.0f;
+    if (inside) { // wave-uniform
+        const int tile = (iy / kTile) * V.tile_w + ix / kTile;
+        const u32 beg = uniform(tile_offsets[tile]), end = uniform(tile_offsets[tile + 1]);
+        const float px = (float)ix + 0.5f, py = (float)iy + 0.5f;
+        bool done = false;
+        for (u32 batch = beg; batch < end && !done; batch += 64) {
+            const u32 bn = min(64u, end - batch);
+            u32 gid = 0;
+            float alpha = 0.f, z = 0.f;
+            bool ok = false;
+            if ((u32)lane < bn) {
+                gid = vals[batch + lane];
+                const float4 *gp = reinterpret_cast<const float4 *>(g2d + gid);
+                const float4 a = gp[0], b = gp[1];
+                const float dx = a.x - px, dy = a.y - py;
+                const float sigma = __builtin_fmaf(b.y * dx, dy, 0.5f * __builtin_fmaf(b.x * dx, dx, (b.z * dy) * dy));
+                alpha = __builtin_fminf(kAlphaMax, a.z * exp_neg(-__builtin_fmaxf(sigma, 0.f)));
+                ok = (sigma >= 0.f) && (alpha >= kAlphaMin);
+                z = a.w;
+            }
+            const u64 okm = __ballot(ok);
+            // T through the batch in list order; lane j keeps entry j's weight
+            float wv = 0.f;
+            u64 valid = 0ull;
+            for (u32 j = 0; j < bn; ++j) {
+                if (!((okm >> j) & 1ull))
+                    continue;
+                const float al = lane_f(alpha, (int)j);
+                const float next_T = uniform_f(T * (1.0f - al));
+                if (next_T <= kTMin) { // terminates: not counted, nothing behind it either
+                    done = true;
+                    break;
+                }
+                const float w = uniform_f(al * T);
+                wv = (u32)lane == j ? w : wv;
+                valid |= 1ull << j;
+                T = next_T;
+            }
+            // front to back, lanes = channels
+            const int n_valid = __popcll(valid);
+            for (int i = 0; i < n_valid; ++i) {
+                const int j = __ffsll((long long)valid) - 1;
+                valid &= valid - 1ull;
+                const float w = lane_f(wv, j);
+                const u32 g = (u32)__builtin_amdgcn_readlane((int)gid, j);
+                const float4 x = load4t<MT, VEC>(X + (int64_t)g * ldx, c, D);
+                acc.x = __builtin_fmaf(w, x.x, acc.x);
+                acc.y = __builtin_fmaf(w, x.y, acc.y);
+                acc.z = __builtin_fmaf(w, x.z, acc.z);
+                acc.w = __builtin_fmaf(w, x.w, acc.w);
+                zacc = __builtin_fmaf(w, lane_f(z, j), zacc);
+            }
+        }
+    }
+    store4<false>(out + (int64_t)probe * D, c, D, acc);
+    if (chunk == 0 && lane == 0) {
+        if (depth)
+            depth[probe] = zacc;
+        if (alpha_out)
+            alpha_out[probe] = 1.0f - T;
+    }
+}
+
+template <int MT>
+void launch_probe_pixels_t(const Ws &W, const ViewDev &V, int M, const int32_t *xy, const void *Xv, int64_t ldx, int D, float *out,
+                           float *depth, float *alpha, hipStream_t s)
+{
+    const int n_tiles = V.tile_w * V.tile_h;
+    const int fin = sort_passes(n_tiles) & 1;
+    const dim3 grid((unsigned)M, (unsigned)((D + kProbeChunk - 1) / kProbeChunk));
+    with_bool(field_rows_vec(Xv, ldx, MT), [&](auto VEC) {
+        hipLaunchKernelGGL((k_probe_pixels<MT, VEC>), grid, dim3(64), 0, s, V, W.tile_offsets, W.vals[fin], W.g2d, xy, field_ptr<MT>(Xv),
+                           ldx, D, out, depth, alpha);
     });
 }
 

@@ -16,10 +16,13 @@ namespace gwbp {
 // that cost 0.75 + 1.13 ms at C2 -- and two wave-uniform early-outs taken from k_blend, neither of which changes a bit of the
 // result: a candidate whose alpha >= 1/255 ellipse holds no live pixel of the wave's 4 x 16 quarter skips exp and T (sigma
 // above ln(255 o) + margin cannot reach 1/255), one that contributes to no pixel skips its colour reads and FMAs.
-template <int CH>
+// MT: the element type of colors (GWBP_MAP_*), ldc its row stride in elements.  A half row is read by its staging thread as half
+// elements -- VEC: 8-B loads of four (the table 8-B aligned, ldc % 4 == 0), else 2-B loads -- and widened (exact) where s_c is written:
+// the LDS image, and with it the blend loop and every result, are those of the fp32 kernel on the widened table.
+template <int MT, bool VEC, int CH>
 __global__ __launch_bounds__(256) void k_render_px(ViewDev V, const u32 *__restrict__ tile_offsets,
                                                    const u32 *__restrict__ vals, const G2D *__restrict__ g2d,
-                                                   const float *__restrict__ colors, int D,
+                                                   const typename MapElem<MT>::raw *__restrict__ colors, int64_t ldc, int D,
                                                    float *__restrict__ out, float *__restrict__ alphas)
 {
     __shared__ float4 s_a[256]; // mx, my, opac, ln(255 opac) + margin
@@ -48,14 +51,25 @@ __global__ __launch_bounds__(256) void k_render_px(ViewDev V, const u32 *__restr
             const float4 *gp = reinterpret_cast<const float4 *>(g2d + gid);
             s_a[threadIdx.x] = px_stage(gp[0]);
             s_b[threadIdx.x] = gp[1];
-            const float *cp = colors + (size_t)gid * D;
-            float cv[CH];
+            if constexpr (MT == GWBP_MAP_F32) {
+                const float *cp = colors + (int64_t)gid * ldc;
+                float cv[CH];
 #pragma unroll
-            for (int c = 0; c < CH; ++c)
-                cv[c] = c < D ? cp[c] : 0.f;
+                for (int c = 0; c < CH; ++c)
+                    cv[c] = c < D ? cp[c] : 0.f;
 #pragma unroll
-            for (int c4 = 0; c4 < CH / 4; ++c4)
-                s_c[threadIdx.x][c4] = make_float4(cv[4 * c4], cv[4 * c4 + 1], cv[4 * c4 + 2], cv[4 * c4 + 3]);
+                for (int c4 = 0; c4 < CH / 4; ++c4)
+                    s_c[threadIdx.x][c4] = make_float4(cv[4 * c4], cv[4 * c4 + 1], cv[4 * c4 + 2], cv[4 * c4 + 3]);
+            } else {
+                const typename MapElem<MT>::raw *cp = colors + (int64_t)gid * ldc;
+                typename MapElem<MT>::raw4 cr[CH / 4]; // every load of the row issued, then widened
+#pragma unroll
+                for (int c4 = 0; c4 < CH / 4; ++c4)
+                    cr[c4] = load4raw<MT, VEC>(cp, 4 * c4, D);
+#pragma unroll
+                for (int c4 = 0; c4 < CH / 4; ++c4)
+                    s_c[threadIdx.x][c4] = widen4<MT>(cr[c4]);
+            }
         }
         __syncthreads();
         for (u32 j = 0; j < bn; ++j) {
@@ -135,20 +149,26 @@ __global__ __launch_bounds__(256) void k_sh_colors(int64_t N, int degree, int K,
     out[3 * i + 2] = __builtin_fmaxf(bl + 0.5f, 0.f);
 }
 
-int launch_render_px(const Ws &W, const ViewDev &V, const float *colors, int D, float *out, float *alphas,
+int launch_render_px(const Ws &W, const ViewDev &V, const void *colors, int mt, int64_t ldc, int D, float *out, float *alphas,
                      hipStream_t s)
 {
     const int n_tiles = V.tile_w * V.tile_h;
     const int fin = sort_passes(n_tiles) & 1;
-#define GWBP_PX(C)                                                                                                    \
-    hipLaunchKernelGGL(k_render_px<C>, dim3(n_tiles), dim3(256), 0, s, V, W.tile_offsets, W.vals[fin], W.g2d, colors, D, out, alphas)
-    if (D <= 4)
-        GWBP_PX(4);
-    else if (D <= 16)
-        GWBP_PX(16);
-    else
-        GWBP_PX(32);
+    // (the fp32 kernel reads element by element whatever the alignment: one instantiation per CH, as before it had a typed table)
+    const bool vec = mt != GWBP_MAP_F32 && field_rows_vec(colors, ldc, mt);
+    with_field_type(mt, vec, [&](auto MT, auto VEC) {
+        constexpr bool kVec = MT != GWBP_MAP_F32 && decltype(VEC)::value; // (no second fp32 instantiation)
+#define GWBP_PX(C)                                                                                                                \
+    hipLaunchKernelGGL((k_render_px<MT, kVec, C>), dim3(n_tiles), dim3(256), 0, s, V, W.tile_offsets, W.vals[fin], W.g2d,             \
+                       field_ptr<MT>(colors), ldc, D, out, alphas)
+        if (D <= 4)
+            GWBP_PX(4);
+        else if (D <= 16)
+            GWBP_PX(16);
+        else
+            GWBP_PX(32);
 #undef GWBP_PX
+    });
     return check_hip(hipGetLastError(), "render_px launch");
 }
 

@@ -130,12 +130,14 @@ __device__ __forceinline__ void fma4(float4 &acc, float w, const float4 &v)
     acc.w = __builtin_fmaf(w, v.w, acc.w);
 }
 
-// MT: the element type of F (a half row is widened as it is loaded; weights, chains and out are fp32)
-template <int MT, bool VEC>
+// MT: the element type of F (a half row is widened as it is loaded; weights and chains are fp32); OT: that of out (a half out is the
+// fp32 quotient rounded once, narrow<OT>)
+template <int MT, int OT, bool VEC>
 __global__ __launch_bounds__(256) void k_neighbor_blend(int64_t Q, int64_t M, int D, int k, const int32_t *__restrict__ idx,
                                                         const float *__restrict__ wts,
                                                         const typename MapElem<MT>::raw *__restrict__ F, int64_t ldf,
-                                                        float *__restrict__ out, int64_t ldo, float *__restrict__ wsum)
+                                                        typename MapElem<OT>::raw *__restrict__ out, int64_t ldo,
+                                                        float *__restrict__ wsum)
 {
     const int lane = threadIdx.x & 63;
     const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); // wave-uniform
@@ -163,7 +165,7 @@ __global__ __launch_bounds__(256) void k_neighbor_blend(int64_t Q, int64_t M, in
     }
     if (lane == 0)
         wsum[g] = W;
-    float *o = out + g * ldo;
+    typename MapElem<OT>::raw *o = out + g * ldo;
     for (int c0 = 0; c0 < D; c0 += 256) {
         const int c = c0 + 4 * lane;
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -182,7 +184,7 @@ __global__ __launch_bounds__(256) void k_neighbor_blend(int64_t Q, int64_t M, in
         }
         if (any)
             acc = make_float4(acc.x / W, acc.y / W, acc.z / W, acc.w / W);
-        store4<VEC>(o, c, D, acc);
+        store4t<OT, VEC>(o, c, D, acc);
     }
 }
 
@@ -267,17 +269,19 @@ int launch_point_gaussians(const float *sorted, const int32_t *cell_start, const
 }
 
 int launch_neighbor_blend(int64_t Q, int64_t M, int D, int k, const int32_t *idx, const float *w, const void *F, int mt, int64_t ldf,
-                          float *out, int64_t ldo, float *wsum, hipStream_t s)
+                          void *out, int ot, int64_t ldo, float *wsum, hipStream_t s)
 {
     if (Q == 0)
         return GWBP_OK;
     unsigned grid;
     if (int rc = grid_of("neighbor_blend", Q, &grid, 4))
         return rc;
-    const bool vec = field_rows_vec(F, ldf, mt) && field_rows_vec(out, ldo, GWBP_MAP_F32);
+    const bool vec = field_rows_vec(F, ldf, mt) && field_rows_vec(out, ldo, ot);
     with_field_type(mt, vec, [&](auto MT, auto VEC) {
-        hipLaunchKernelGGL((k_neighbor_blend<MT, VEC>), dim3(grid), dim3(256), 0, s, Q, M, D, k, idx, w, field_ptr<MT>(F), ldf, out, ldo,
-                           wsum);
+        with_map_type(ot, [&](auto OT) {
+            hipLaunchKernelGGL((k_neighbor_blend<MT, OT, VEC>), dim3(grid), dim3(256), 0, s, Q, M, D, k, idx, w, field_ptr<MT>(F), ldf,
+                               out_ptr<OT>(out), ldo, wsum);
+        });
     });
     return check_hip(hipGetLastError(), "neighbor_blend launch");
 }

@@ -106,11 +106,11 @@ __global__ __launch_bounds__(kSpatialThreads) void k_spatial_knn(const float4 *_
 
 // One wave per row g: out[g, :] = (sum over the valid j, in list order, of F[idx[g, j], :]) / (their number); lanes over
 // channels, four per lane.  An index outside [0, M) is skipped; a row with none left is zero.  MT: the element type of F (a half
-// row is widened as it is loaded; the sums and out are fp32).
-template <int MT, bool VEC>
+// row is widened as it is loaded; the sums are fp32).  OT: the element type of out (a half out is the fp32 quotient rounded once, narrow<OT>).
+template <int MT, int OT, bool VEC>
 __global__ __launch_bounds__(256) void k_neighbor_mean(int64_t N, int64_t M, int D, int k, const int32_t *__restrict__ idx,
                                                        const typename MapElem<MT>::raw *__restrict__ F, int64_t ldf,
-                                                       float *__restrict__ out, int64_t ldo)
+                                                       typename MapElem<OT>::raw *__restrict__ out, int64_t ldo)
 {
     const int lane = threadIdx.x & 63;
     const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -136,7 +136,7 @@ __global__ __launch_bounds__(256) void k_neighbor_mean(int64_t N, int64_t M, int
             const float n = (float)nv;
             acc = make_float4(acc.x / n, acc.y / n, acc.z / n, acc.w / n);
         }
-        store4<VEC>(out + g * ldo, c, D, acc);
+        store4t<OT, VEC>(out + g * ldo, c, D, acc);
     }
 }
 
@@ -179,7 +179,7 @@ int launch_spatial_knn(const float *sorted, const int32_t *cell_start, const flo
     return check_hip(hipGetLastError(), "spatial_knn launch");
 }
 
-int launch_neighbor_mean(int64_t N, int64_t M, int D, int k, const int32_t *idx, const void *F, int mt, int64_t ldf, float *out,
+int launch_neighbor_mean(int64_t N, int64_t M, int D, int k, const int32_t *idx, const void *F, int mt, int64_t ldf, void *out, int ot,
                          int64_t ldo, hipStream_t s)
 {
     if (N == 0)
@@ -187,9 +187,12 @@ int launch_neighbor_mean(int64_t N, int64_t M, int D, int k, const int32_t *idx,
     unsigned grid;
     if (int rc = grid_of("neighbor_mean", N, &grid, 4))
         return rc;
-    const bool vec = field_rows_vec(F, ldf, mt) && field_rows_vec(out, ldo, GWBP_MAP_F32);
+    const bool vec = field_rows_vec(F, ldf, mt) && field_rows_vec(out, ldo, ot);
     with_field_type(mt, vec, [&](auto MT, auto VEC) {
-        hipLaunchKernelGGL((k_neighbor_mean<MT, VEC>), dim3(grid), dim3(256), 0, s, N, M, D, k, idx, field_ptr<MT>(F), ldf, out, ldo);
+        with_map_type(ot, [&](auto OT) {
+            hipLaunchKernelGGL((k_neighbor_mean<MT, OT, VEC>), dim3(grid), dim3(256), 0, s, N, M, D, k, idx, field_ptr<MT>(F), ldf,
+                               out_ptr<OT>(out), ldo);
+        });
     });
     return check_hip(hipGetLastError(), "neighbor_mean launch");
 }

@@ -70,6 +70,25 @@ def _req(t: torch.Tensor, name: str, shape_tail=None) -> torch.Tensor:
     return t.contiguous()
 
 
+def field_rows(t: torch.Tensor, name: str):
+    """(tensor, GWBP_MAP_* code) of a finished [rows, D] FIELD as it is stored: float32, float16 or bfloat16, read by the *_typed entry
+    points without a float32 copy.  Unit stride inside a row and a non-negative row stride >= D, in elements; a layout the kernels
+    cannot read is made contiguous in the tensor's own dtype."""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise GwbpError(f"{name} must be a HIP tensor (no CPU fallback exists for this path)")
+    if t.dim() != 2 or t.shape[1] < 1:
+        raise GwbpError(f"{name} must be [rows, D] with D >= 1, got {tuple(t.shape)}")
+    if t.dtype not in MAP_TYPES:
+        raise GwbpError(f"{name} must be float32, float16 or bfloat16, got {t.dtype}")
+    if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    return t, MAP_TYPES[t.dtype]
+
+
+def row_stride(t: torch.Tensor) -> int:
+    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])  # (the stride of a single row means nothing)
+
+
 class Engine:
     """Workspace sized for (N Gaussians, max WxH, isect_cap, pair_cap) on one device."""
 
@@ -883,15 +902,23 @@ class Engine:
             self._maps[key] = m
         return m
 
-    def render(self, view, colors):
-        colors = _req(colors, "colors")
+    def render(self, view, colors, out_dtype=None):
+        """out [H, W, D] = the render of the table `colors` [N, D] from the view's weight store (gwbp_render_typed).  colors: float32,
+        float16 or bfloat16, read as stored at any row stride >= D -- a half table gives the bits of colors.float(), without that copy.
+        out_dtype (None = float32, float16, bfloat16): a half out is the float32 render rounded once to nearest even, out32.to(dtype)
+        bit for bit."""
+        colors, ct = field_rows(colors, "colors")
+        if (out_dtype or torch.float32) not in MAP_TYPES:
+            raise GwbpError(f"render: out_dtype must be float32, float16 or bfloat16, got {out_dtype}")
         D = colors.shape[1]
-        out = torch.empty(view.height, view.width, D, device=self.device)
-        self._call("gwbp_render", *self._args(), byref(view), ptr(colors), D, ptr(out), self._stream())
+        out = torch.empty(view.height, view.width, D, dtype=out_dtype or torch.float32, device=self.device)
+        self._call("gwbp_render_typed", *self._args(), byref(view), ptr(colors), ct, c_int64(row_stride(colors)), D, ptr(out),
+                   MAP_TYPES[out.dtype], self._stream())
         return out
 
     def field_compare(self, view, features, fmap, index=None, want_planes=True, table=None):
-        """The field `features` [N, D] (float32, any row stride >= D, read in place) rendered from the view's weight store and
+        """The field `features` [N, D] (float32, float16 or bfloat16, any row stride >= D, read as stored: a half field gives the bits of
+        features.float() without that copy) rendered from the view's weight store and
         compared with the view's map inside the kernel (gwbp_field_compare): needs project + bin_sort + blend_weights of `view`,
         like render().  Returns (planes, table): planes float32 [6, H, W] = dot, rr, mm, l1, l2, cosine of the rendered row r and
         the map row m per pixel (None with want_planes=False: no plane is written), table float64 [8] on the device = sum cosine,
@@ -901,16 +928,13 @@ class Engine:
         table: a float64 [8] device tensor to fill (a row of a [V, 8] table) instead of a new one."""
         if self._tokens is not None:
             raise GwbpError("this view was blended with blend_tokens (no weight store): blend_weights() first for field_compare()")
-        if not torch.is_tensor(features) or not features.is_cuda or features.dtype != torch.float32 or features.dim() != 2:
-            raise GwbpError("features must be a float32 [N, D] HIP tensor")
+        features, ft = field_rows(features, "features")
         if features.shape[0] != self.n:
             raise GwbpError(f"engine was sized for {self.n} Gaussians, the field has {features.shape[0]} rows")
         D = features.shape[1]
         if not 1 <= D <= 2048:
             raise GwbpError(f"D must be in [1, 2048], got {D}")
-        if (D > 1 and features.stride(1) != 1) or (self.n > 1 and features.stride(0) < D):
-            features = features.contiguous()
-        ld = int(features.stride(0)) if self.n > 1 else D
+        ld = row_stride(features)
         sy, sx, sc, Dm = self._feat_strides(fmap, view, lowres=index is not None)
         if Dm != D:
             raise GwbpError(f"the field has D = {D}, the map D = {Dm}")
@@ -933,7 +957,7 @@ class Engine:
               or not table.is_contiguous()):
             raise GwbpError("table must be a contiguous float64 [8] HIP tensor")
         planes = torch.empty(6, view.height, view.width, device=self.device) if want_planes else None
-        self._call("gwbp_field_compare", *self._args(), byref(view), ptr(features), c_int64(ld), D, ptr(fmap),
+        self._call("gwbp_field_compare_typed", *self._args(), byref(view), ptr(features), ft, c_int64(ld), D, ptr(fmap),
                    MAP_TYPES[fmap.dtype], c_int64(sy), c_int64(sx), lr_h, lr_w, ptr(ymap), ptr(xmap), ptr(planes), ptr(table),
                    self._stream())
         return planes, table
@@ -1009,35 +1033,34 @@ class Engine:
         return table[0], grad_rendered, grad_decoder, table
 
     def render_pixels(self, view, colors, want_alphas=True):
-        """Pixel-parallel forward render for 1..32 channels; needs project + bin_sort of `view` (not the weight store)."""
-        colors = _req(colors, "colors")
+        """Pixel-parallel forward render for 1..32 channels; needs project + bin_sort of `view` (not the weight store).  colors: float32,
+        float16 or bfloat16 [N, D] at any row stride >= D, read as stored (a half table: the bits of colors.float(), no copy)."""
+        colors, ct = field_rows(colors, "colors")
         D = colors.shape[1]
         out = torch.empty(view.height, view.width, D, device=self.device)
         alphas = self._alphas(view, want_alphas)
-        self._call("gwbp_render_pixels", *self._args(), byref(view), ptr(colors), D, ptr(out), ptr(alphas),
-                                          self._stream())
+        self._call("gwbp_render_pixels_typed", *self._args(), byref(view), ptr(colors), ct, c_int64(row_stride(colors)), D, ptr(out),
+                   ptr(alphas), self._stream())
         return out, alphas
 
     def probe_pixels(self, view, xy, table, want_depth=True, want_alpha=True):
-        """The render of `table` [N, D] (any row stride >= D, read in place) at the pixels xy [M, 2] (int32, (x, y)) only:
+        """The render of `table` [N, D] (float32, float16 or bfloat16, any row stride >= D, read as stored: a half table gives the bits of
+        table.float() without that copy) at the pixels xy [M, 2] (int32, (x, y)) only:
         (out [M, D], depth [M] or None, alpha [M] or None); needs project + bin_sort of `view` (not the weight store).  depth
         accumulates the PROJECTION's camera depths; rasterization()'s "+D" channel computes its depths in torch -- render that
         column as a one-channel table to get its bits."""
-        if not torch.is_tensor(table) or not table.is_cuda or table.dtype != torch.float32 or table.dim() != 2:
-            raise GwbpError("the probed table must be a float32 [N, D] HIP tensor")
+        table, ft = field_rows(table, "the probed table")
         if table.shape[0] != self.n:
             raise GwbpError(f"engine was sized for {self.n} Gaussians, the table has {table.shape[0]} rows")
-        if (table.shape[1] > 1 and table.stride(1) != 1) or (self.n > 1 and table.stride(0) < table.shape[1]):
-            table = table.contiguous()
         if xy.dtype != torch.int32 or xy.dim() != 2 or xy.shape[1] != 2 or not xy.is_cuda:
             raise GwbpError("xy must be an int32 [M, 2] HIP tensor of (x, y) pixels")
         xy = xy.contiguous()
         M, D = xy.shape[0], table.shape[1]
-        ld = int(table.stride(0)) if self.n > 1 else D
+        ld = row_stride(table)
         out = torch.empty(M, D, device=self.device)
         depth = torch.empty(M, device=self.device) if want_depth else None
         alpha = torch.empty(M, device=self.device) if want_alpha else None
-        self._call("gwbp_probe_pixels", *self._args(), byref(view), M, ptr(xy), ptr(table), c_int64(ld), D, ptr(out), ptr(depth),
+        self._call("gwbp_probe_pixels_typed", *self._args(), byref(view), M, ptr(xy), ptr(table), ft, c_int64(ld), D, ptr(out), ptr(depth),
                    ptr(alpha), self._stream())
         return out, depth, alpha
 

@@ -23,7 +23,7 @@ from typing import Callable, Dict, Optional
 import torch
 
 from ._lib import GwbpError
-from ._views import front, require_device, rows, score_views
+from ._views import field_rows, front, require_device, score_views
 from ._views import raster_kw as merged_raster_kw
 from .rasterization import get_engine
 
@@ -34,7 +34,7 @@ TABLE_COLUMNS = ("sum_cosine", "sum_l1", "sum_l2", "sum_mm", "n_valid", "n_bad",
 
 def _field(fn: str, means, features) -> torch.Tensor:
     require_device(fn, means)
-    x = rows(features, "features")
+    x = field_rows(features, "features")[0]  # float16 / bfloat16 fields are read as stored: no float32 copy
     if x.shape[0] != means.shape[0]:
         raise GwbpError(f"{x.shape[0]} feature rows for {means.shape[0]} Gaussians")
     if not 1 <= x.shape[1] <= MAX_D:
@@ -71,7 +71,8 @@ def render_field_agreement(means, quats, scales, opacities, features, feature_ma
                            upsample: Optional[str] = None, **raster_kw) -> Dict[str, torch.Tensor]:
     """The per-pixel agreement of one view: a dict of float32 [H, W] tensors dot, rr, mm, l1, l2 (the five channel sums of the
     module docstring), cosine (NaN where rr mm == 0: nothing rendered there, or an all-zero map row) and alpha (the render's).
-    features: float32 [N, D], any row stride >= D, read in place; D <= 2048.  feature_map: the view's [H, W, D] map, float32,
+    features: float32, float16 or bfloat16 [N, D], any row stride >= D, read as stored (a half field gives the bits of
+    features.float(), without that copy); D <= 2048.  feature_map: the view's [H, W, D] map, float32,
     float16 or bfloat16 read as stored, channels contiguous, any non-negative pixel strides; with upsample="nearest" the network's
     low-resolution [h, w, D] map, read through F.interpolate(mode="nearest")'s index maps and never expanded.  A pixel whose map
     row holds a non-finite value is NaN in every plane but alpha.  raster_kw: near_plane, far_plane, eps2d, radius_clip,

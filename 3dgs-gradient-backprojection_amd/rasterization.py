@@ -19,7 +19,7 @@ from torch.utils import _pytree
 
 from . import _lib
 from ._lib import GwbpError
-from .engine import TILE, Engine
+from .engine import HALF_TYPES, TILE, Engine
 
 _ENGINES: Dict[Tuple, Engine] = {}
 # The reference's harvesting pattern hands the SAME all-zero colour table to every view (backproject.py:67-72): whether a
@@ -477,6 +477,10 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     camera_model "pinhole" | "ortho" | "fisheye" (gsplat's ideal models, no distortion) and rasterize_mode "classic" |
     "antialiased" (opacity x compensation; meta["opacities"] then holds the compensated opacities, meta["compensations"] the
     factors) select the projection kernel; depth render modes keep camera z for every model, like gsplat.
+    colors [N, D] (sh_degree=None) may be float16 / bfloat16: the table is rendered as it is stored -- no float32 copy of it, at any
+    row stride >= D -- and render_colors is float32 with the bits of the call on colors.float().  There is no gradient through a half
+    table (NotImplementedError if it requires grad); SH coefficient tables are float32 only; the depth render modes concatenate the
+    float32 depth column to the table, which widens it (torch's promotion).
     """
     if tile_size != TILE:
         raise GwbpError(f"tile_size must be {TILE}: the tile rectangle is part of the numerics")
@@ -488,6 +492,9 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
         raise ValueError(render_mode)
     if not means.is_cuda:
         raise GwbpError("rasterization() needs HIP tensors (the reference likewise requires CUDA, backproject.py:314)")
+    if sh_degree is None and colors.dtype in HALF_TYPES and colors.requires_grad:
+        raise NotImplementedError("gradients w.r.t. a float16 / bfloat16 colour table are not implemented: render it detached, or "
+                                  "differentiate the float32 table")
     width, height = int(width), int(height)  # utils.py:247-248 passes 0-d tensors
     C_ = viewmats.shape[0]
     N = means.shape[0]
@@ -512,7 +519,8 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
         if need_depth:
             z = (means @ vm[:3, :3].T + vm[:3, 3])[:, 2:3]
             cols = z if render_mode in ("D", "ED") else torch.cat([cols, z], dim=1)
-        cols = cols.contiguous()
+        if cols.dtype not in HALF_TYPES:  # (a half table is read as stored, row stride included: Engine.render's field_rows)
+            cols = cols.contiguous()
         harvest = bool(cols.requires_grad and _is_zero_table(cols))
         out, alpha = _Rasterize.apply(cols, means, quats, scales, opacities, vm, K, width, height, kw, holder, harvest)
         if _HARVEST_SHORTCUT and harvest and render_mode == "RGB" and backgrounds is None and out.requires_grad:

@@ -26,7 +26,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from ._lib import GwbpError, ptr
-from ._views import field_rows, ld, require_device, rows, run
+from ._views import field_rows, ld, out_type, require_device, rows, run
 from .components import build_grid, plan_walk, r2_of
 from .regions import similarity_quantiles
 from .spatial import MAX_K, Grid, as_points, grid_args, grid_stats, sorted_keys, spatial_knn
@@ -157,19 +157,21 @@ def _list(idx, weights, dev):
     return idx.contiguous(), weights.contiguous()
 
 
-def neighbor_blend(features: torch.Tensor, idx: torch.Tensor, weights: torch.Tensor):
-    """(out float32 [Q, D], wsum float32 [Q]): out[g] = sum_j w[g, j] features[idx[g, j]] / sum_j w[g, j], both sums chained in the
+def neighbor_blend(features: torch.Tensor, idx: torch.Tensor, weights: torch.Tensor, out_dtype=None):
+    """(out [Q, D], wsum float32 [Q]): out[g] = sum_j w[g, j] features[idx[g, j]] / sum_j w[g, j], both sums chained in the
     list's order in fp32, over the entries with an index in [0, M) and w != 0 (the others are skipped, their rows not read); a
     zero row and wsum 0 where none is left.  features [M, D] is read in place at any row stride >= D (float16 / bfloat16 as stored,
-    widened exactly as they are loaded; out is float32)."""
+    widened exactly as they are loaded).  out is float32, or with out_dtype=float16 / bfloat16 the float32 quotient rounded once to
+    nearest even by the kernel's store: the bits of out32.to(out_dtype), without the float32 tensor."""
     f, ft = field_rows(features, "features")
+    dtype, ot = out_type("neighbor_blend", out_dtype)
     idx, weights = _list(idx, weights, f.device)
     nq, k = idx.shape
     d = f.shape[1]
-    out = torch.empty(nq, d, dtype=torch.float32, device=f.device)
+    out = torch.empty(nq, d, dtype=dtype, device=f.device)
     wsum = torch.empty(nq, dtype=torch.float32, device=f.device)
-    run("gwbp_neighbor_blend_typed", f.device, C.c_int64(nq), C.c_int64(f.shape[0]), d, k, ptr(idx), ptr(weights), ptr(f), ft,
-        C.c_int64(ld(f)), ptr(out), C.c_int64(d), ptr(wsum))
+    run("gwbp_neighbor_blend_out_typed", f.device, C.c_int64(nq), C.c_int64(f.shape[0]), d, k, ptr(idx), ptr(weights), ptr(f), ft,
+        C.c_int64(ld(f)), ptr(out), ot, C.c_int64(d), ptr(wsum))
     return out, wsum
 
 
@@ -195,11 +197,12 @@ def weighted_vote(labels: torch.Tensor, num_classes: int, idx: torch.Tensor, wei
 
 
 def sample_field(features: torch.Tensor, pg: PointGaussians, fallback: str = "none", fallback_radius: Optional[float] = None, *,
-                 return_wsum: bool = False):
-    """(out float32 [Q, D], valid bool [Q]): the field at pg's points, features[N, D] blended over each point's list by weight;
+                 return_wsum: bool = False, out_dtype=None):
+    """(out [Q, D], valid bool [Q]): the field at pg's points, features[N, D] blended over each point's list by weight;
     valid where a Gaussian counted (wsum > 0), zero rows elsewhere.  fallback "nearest": an invalid finite point instead takes the
     row of the Gaussian with the nearest centre (spatial_knn(means, 1), on those points only, in torch), within fallback_radius if
-    one is given; valid stays False there, so the caller can tell the two apart.  return_wsum: also the blend's wsum float32 [Q]."""
+    one is given; valid stays False there, so the caller can tell the two apart.  return_wsum: also the blend's wsum float32 [Q].
+    out is float32, or out_dtype (float16 / bfloat16) as neighbor_blend writes it; the fallback's rows are written in out's dtype."""
     if fallback not in ("none", "nearest"):
         raise GwbpError(f"fallback must be 'none' or 'nearest', got {fallback!r}")
     if not isinstance(pg, PointGaussians):
@@ -207,7 +210,7 @@ def sample_field(features: torch.Tensor, pg: PointGaussians, fallback: str = "no
     f = field_rows(features, "features")[0]
     if f.shape[0] != pg.means.shape[0]:
         raise GwbpError(f"features must be [N = {pg.means.shape[0]}, D], got {tuple(f.shape)}")
-    out, wsum = neighbor_blend(f, pg.idx, pg.weights)
+    out, wsum = neighbor_blend(f, pg.idx, pg.weights, out_dtype)
     valid = wsum > 0
     if fallback == "nearest" and pg.means.shape[0] > 0:
         need = torch.nonzero(~valid & torch.isfinite(pg.points).all(dim=1)).squeeze(1)
@@ -216,7 +219,7 @@ def sample_field(features: torch.Tensor, pg: PointGaussians, fallback: str = "no
             ok = near[:, 0] >= 0
             if fallback_radius is not None:
                 ok &= dist[:, 0] <= float(fallback_radius)
-            out[need[ok]] = f[near[ok, 0].long()].float()
+            out[need[ok]] = f[near[ok, 0].long()].float().to(out.dtype)
     return (out, valid, wsum) if return_wsum else (out, valid)
 
 
@@ -246,11 +249,11 @@ def sample_labels(labels: torch.Tensor, num_classes: int, pg: PointGaussians):
 
 def transfer_field(src_means, src_quats, src_scales, src_opacities, features, dst_means, k: int = 8, radius: Optional[float] = None,
                    alpha_min: float = ALPHA_MIN, mask: Optional[torch.Tensor] = None, fallback: str = "nearest",
-                   fallback_radius: Optional[float] = None):
+                   fallback_radius: Optional[float] = None, out_dtype=None):
     """A field carried onto other Gaussians of the same place (a re-trained or densified scene) without the 2-D network and the lift:
-    (field [M, D], valid bool [M], pg) = the source field sampled at the destination's means."""
+    (field [M, D], valid bool [M], pg) = the source field sampled at the destination's means; out_dtype as in sample_field."""
     pg = point_gaussians(dst_means, src_means, src_quats, src_scales, src_opacities, k, radius, alpha_min, mask)
-    out, valid = sample_field(features, pg, fallback, fallback_radius)
+    out, valid = sample_field(features, pg, fallback, fallback_radius, out_dtype=out_dtype)
     return out, valid, pg
 
 

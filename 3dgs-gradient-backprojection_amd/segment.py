@@ -21,7 +21,7 @@ from typing import Dict, Iterator, List, Optional, Tuple
 import torch
 
 from ._lib import GwbpError, ptr
-from ._views import field_rows, front, ld, require_device, rows, run
+from ._views import field_rows, front, ld, require_device, run
 from ._views import raster_kw as merged_raster_kw
 from .pruning import PER_GAUSSIAN
 
@@ -95,12 +95,13 @@ def mask_from_scores(scores: torch.Tensor, n_pos: int, threshold: Optional[float
 def probe_pixels(means, quats, scales, opacities, features, viewmat, K, width, height, xy, **raster_kw):
     """(feats [M, D], depth [M], alpha [M]) of the pixels xy [M, 2] ((x, y) integers) of one view: what
     rasterization(..., colors=features, render_mode="RGB+D") holds at [0, y, x] -- bit for bit -- without rendering the other
-    H W - M pixels (click_and_segment.py:241-262).  A pixel outside the image gives zeros.  depth is gsplat's accumulated "D"
+    H W - M pixels (click_and_segment.py:241-262).  features: float32, float16 or bfloat16 [N, D], read as stored (a half field gives
+    the bits of features.float(), and float32 feats).  A pixel outside the image gives zeros.  depth is gsplat's accumulated "D"
     channel, not the expected depth.  raster_kw: near_plane, far_plane, eps2d, radius_clip, camera_model, rasterize_mode.  The
     engine and the front cache are rasterization()'s: a probe after a rendered frame of the same view re-projects nothing."""
     require_device("probe_pixels", means)
     kw = merged_raster_kw("probe_pixels", raster_kw)
-    x = rows(features, "features")
+    x = field_rows(features, "features")[0]  # float16 / bfloat16 fields are read as stored: no float32 copy
     if x.shape[0] != means.shape[0]:
         raise GwbpError(f"{x.shape[0]} feature rows for {means.shape[0]} Gaussians")
     if x.shape[1] > MAX_D:

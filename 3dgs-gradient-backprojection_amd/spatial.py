@@ -21,7 +21,7 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 
 from ._lib import GwbpError, ptr
-from ._views import field_rows, ld, rows, run
+from ._views import field_rows, ld, out_type, rows, run
 from .transfer import narrow_source_labels, vote_labels
 
 MAX_K = 32
@@ -289,11 +289,13 @@ def remove_outliers(means: torch.Tensor, mask: Optional[torch.Tensor] = None, k:
     return keep
 
 
-def neighbor_mean(features: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+def neighbor_mean(features: torch.Tensor, idx: torch.Tensor, out_dtype=None) -> torch.Tensor:
     """out[i, :] = the mean of features[idx[i, j], :] over the valid j (idx >= 0), summed in the list's order in fp32; a zero row
     where none is valid.  features [M, D] is read in place at any row stride >= D (float16 / bfloat16 as stored, widened exactly as
-    they are loaded); the result is a new float32 [N, D] tensor."""
+    they are loaded); the result is a new [N, D] tensor: float32, or with out_dtype=float16 / bfloat16 the float32 mean rounded once
+    to nearest even by the kernel's store (the bits of out32.to(out_dtype), without the float32 tensor)."""
     f, ft = field_rows(features, "features")
+    dtype, ot = out_type("neighbor_mean", out_dtype)
     if not torch.is_tensor(idx) or not idx.is_cuda or idx.dtype != torch.int32 or idx.dim() != 2 or idx.device != f.device:
         raise GwbpError("idx must be an int32 [N, k] tensor on the device of the features")
     idx = idx.contiguous()
@@ -301,19 +303,21 @@ def neighbor_mean(features: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     if not 1 <= k <= MAX_K:
         raise GwbpError(f"idx must have 1 .. {MAX_K} columns, got {k}")
     d = f.shape[1]
-    out = torch.empty(n, d, dtype=torch.float32, device=f.device)
-    run("gwbp_neighbor_mean_typed", f.device, C.c_int64(n), C.c_int64(f.shape[0]), d, k, ptr(idx), ptr(f), ft, C.c_int64(ld(f)),
-        ptr(out), C.c_int64(d))
+    out = torch.empty(n, d, dtype=dtype, device=f.device)
+    run("gwbp_neighbor_mean_out_typed", f.device, C.c_int64(n), C.c_int64(f.shape[0]), d, k, ptr(idx), ptr(f), ft, C.c_int64(ld(f)),
+        ptr(out), ot, C.c_int64(d))
     return out
 
 
-def smooth_features(means: torch.Tensor, features: torch.Tensor, k: int = 8, neighbors: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """The field averaged over each Gaussian's k spatial neighbours (itself included, uniform weights): a new [N, D] tensor."""
+def smooth_features(means: torch.Tensor, features: torch.Tensor, k: int = 8, neighbors: Optional[torch.Tensor] = None,
+                    out_dtype=None) -> torch.Tensor:
+    """The field averaged over each Gaussian's k spatial neighbours (itself included, uniform weights): a new [N, D] tensor, float32
+    or (out_dtype) float16 / bfloat16 as neighbor_mean writes it."""
     if not means.is_cuda:
         raise GwbpError("smooth_features() needs HIP tensors (there is no CPU path)")
     if features.dim() != 2 or features.shape[0] != means.shape[0]:
         raise GwbpError(f"features must be [N = {means.shape[0]}, D], got {tuple(features.shape)}")
-    return neighbor_mean(features, _neighbors(means, k, neighbors))
+    return neighbor_mean(features, _neighbors(means, k, neighbors), out_dtype)
 
 
 # ---- seeded inputs (the CLI's --synthetic, tools/time_spatial.py) -----------------------------------------------------------------

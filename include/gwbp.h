@@ -504,12 +504,33 @@ GWBP_API int gwbp_scatter_mask_features(const gwbp_caps *caps, void *workspace, 
 GWBP_API int gwbp_render(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
                 const float *colors, int32_t D, float *out, void *stream);
 
+/* gwbp_render with a typed colour table and a typed output.  `color_type` (GWBP_MAP_F32 / _F16 / _BF16) is the element type of colors,
+ * ldc >= D its row stride in ELEMENTS (the untyped function reads a dense table: ldc = D); `out_type` is the element type of the dense
+ * [H, W, D] out.  An unknown type code is GWBP_EINVAL, checked before anything else; then the caps, the workspace and the view as in
+ * gwbp_render; a stride below D, a pointer that is not aligned to its element (4 B, 2 B) or a half out that is colors are GWBP_EINVAL
+ * before any HIP call.  GWBP_MAP_F32 / GWBP_MAP_F32 does exactly what gwbp_render does (which is a call of this one).
+ * A half table is read as stored: the kernels keep the bits a load landed and widen them -- exact -- where they are multiplied, so out
+ * has the BITS gwbp_render gives on the fp32 copy of the table, NaN positions included, and no such copy is made.  A half out is the
+ * fp32 sum rounded ONCE to nearest even (gwbp_finalize_typed's rule): the bits of converting the fp32 out.  The kernel that holds four
+ * or eight channels per lane takes D >= 128, D % 4 == 0, table rows that are 16-B (fp32) / 8-B (half) aligned at a stride that is a
+ * multiple of 4 elements, and an out aligned likewise; every other layout takes the two-channel kernel, with the same bits. */
+GWBP_API int gwbp_render_typed(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                               const void *colors, int32_t color_type, int64_t ldc, int32_t D, void *out, int32_t out_type,
+                               void *stream);
+
 /* Forward render for 1..32 channels (RGB, RGB+D, depth; round 5: the 16-d compressed field) straight from the sorted tile
  * lists (needs gwbp_project + gwbp_bin_sort of the same view, not the weight store): the render the reference feeds to its
  * 2-D feature network (backproject.py:89-100), compares in utils.test_proper_pruning (utils.py:316-340) and scores per frame
  * in segment_compressed.py:154-165.  alphas[H*W] optional. */
 GWBP_API int gwbp_render_pixels(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
                        const float *colors, int32_t D, float *out, float *alphas, void *stream);
+
+/* gwbp_render_pixels with a typed colour table: color_type, ldc and the checks as in gwbp_render_typed; out and alphas stay fp32.  A
+ * half row is read by the thread that stages its Gaussian -- 8-B loads of four elements where the table is 8-B aligned and ldc a
+ * multiple of 4, 2-B loads otherwise -- and widened where it enters LDS: the bits of gwbp_render_pixels on the fp32 copy. */
+GWBP_API int gwbp_render_pixels_typed(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                                      const void *colors, int32_t color_type, int64_t ldc, int32_t D, float *out, float *alphas,
+                                      void *stream);
 
 /* gsplat spherical_harmonics + "+0.5, clamp at 0": coeffs[N,K,3] (K >= (degree+1)^2, degree <= 3), view directions
  * means - campos_host[3]; out[N,3].  What rasterization(..., sh_degree=3) does before rasterising (backproject.py:99). */
@@ -627,6 +648,14 @@ GWBP_API int gwbp_neighbor_mean(int64_t n, int64_t m, int32_t D, int32_t k, cons
  * element, with the same bits. out stays fp32. */
 GWBP_API int gwbp_neighbor_mean_typed(int64_t n, int64_t m, int32_t D, int32_t k, const int32_t *idx, const void *features,
                                       int32_t field_type, int64_t ldf, float *out, int64_t ldo, void *stream);
+
+/* gwbp_neighbor_mean_typed with a typed OUTPUT: `out_type` (GWBP_MAP_*) is the element type of out and ldo counts ITS elements.  A
+ * half out is the fp32 quotient rounded ONCE to nearest even (gwbp_finalize_typed's rule): the bits of converting the fp32 out.  An
+ * unknown out_type is GWBP_EINVAL beside an unknown field_type, before anything else; an out that is not aligned to its element, or
+ * that is the features (whatever its type), is GWBP_EINVAL before any HIP call.  gwbp_neighbor_mean_typed is a call of this function
+ * with GWBP_MAP_F32. */
+GWBP_API int gwbp_neighbor_mean_out_typed(int64_t n, int64_t m, int32_t D, int32_t k, const int32_t *idx, const void *features,
+                                          int32_t field_type, int64_t ldf, void *out, int32_t out_type, int64_t ldo, void *stream);
 
 /* ---- Radius components: which points form one object (DBSCAN with a deterministic border rule; PCL's Euclidean cluster extraction
  * at min_points = 1) on the grid of the spatial search above ------------------------------------------------------------------------
@@ -790,6 +819,12 @@ GWBP_API int gwbp_neighbor_blend(int64_t q, int64_t m, int32_t D, int32_t k, con
 GWBP_API int gwbp_neighbor_blend_typed(int64_t q, int64_t m, int32_t D, int32_t k, const int32_t *idx, const float *w,
                                        const void *features, int32_t field_type, int64_t ldf, float *out, int64_t ldo, float *wsum,
                                        void *stream);
+/* gwbp_neighbor_blend_typed with a typed OUTPUT, as gwbp_neighbor_mean_out_typed: out_type is the element type of out, ldo counts its
+ * elements, a half out is the fp32 quotient rounded once to nearest even and must not be one of the inputs; wsum stays fp32.
+ * gwbp_neighbor_blend_typed is a call of this function with GWBP_MAP_F32. */
+GWBP_API int gwbp_neighbor_blend_out_typed(int64_t q, int64_t m, int32_t D, int32_t k, const int32_t *idx, const float *w,
+                                           const void *features, int32_t field_type, int64_t ldf, void *out, int32_t out_type,
+                                           int64_t ldo, float *wsum, void *stream);
 GWBP_API int gwbp_weighted_vote(int64_t q, int64_t m, int32_t k, const int32_t *idx, const float *w, const int32_t *labels,
                                 int32_t num_classes, int32_t *out_label, float *out_share, void *stream);
 
@@ -971,6 +1006,15 @@ GWBP_API int gwbp_probe_pixels(const gwbp_caps *caps, void *workspace, size_t wo
                                int32_t M, const int32_t *xy, const float *X, int64_t ldx, int32_t D, float *out, float *depth,
                                float *alpha, void *stream);
 
+/* gwbp_probe_pixels with a typed table X: `field_type` (GWBP_MAP_*) is its element type and ldx counts ELEMENTS.  An unknown
+ * field_type is GWBP_EINVAL, checked before anything else; an X that is not aligned to its element is GWBP_EINVAL with the probe's own
+ * invalid cases, before the workspace is looked at.  A half row is widened -- exact -- as it is loaded (8-B loads of four elements
+ * where X is 8-B aligned and ldx a multiple of 4, 2-B loads otherwise): out, depth and alpha have the bits of gwbp_probe_pixels on the
+ * fp32 copy of X, and no such copy is made.  gwbp_probe_pixels is a call of this function with GWBP_MAP_F32. */
+GWBP_API int gwbp_probe_pixels_typed(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                                     int32_t M, const int32_t *xy, const void *X, int32_t field_type, int64_t ldx, int32_t D, float *out,
+                                     float *depth, float *alpha, void *stream);
+
 /* ---- per-Gaussian labels rendered to 2-D class maps and scored (the reference's evaluate_results and render_affordance,
  * affordance_transfer/demo_affordance_transfer.py:1445-1611, 1399-1439) ------------------------------------------------------------
  * One blend pass over a projected and sorted view (gwbp_project or gwbp_project_camera + gwbp_bin_sort, like gwbp_render_pixels; no
@@ -1029,6 +1073,17 @@ GWBP_API int gwbp_field_compare(const gwbp_caps *caps, void *workspace, size_t w
                                 const float *features, int64_t ldf, int32_t D, const void *map, int32_t map_type, int64_t ms_y,
                                 int64_t ms_x, int32_t lr_h, int32_t lr_w, const int32_t *ymap, const int32_t *xmap, float *planes,
                                 double *table, void *stream);
+
+/* gwbp_field_compare with a typed FIELD: `field_type` (GWBP_MAP_*) is the element type of features and ldf counts ELEMENTS; the map
+ * keeps its own map_type.  An unknown field_type is GWBP_EINVAL, checked before anything else; features not aligned to its element is
+ * GWBP_EINVAL with the function's other invalid cases.  A half field is read as stored -- the walk keeps the bits its loads landed and
+ * widens them, exact, where they are multiplied; 8-B loads of four elements where rows allow them, 2-B loads otherwise -- so the
+ * planes and the table have the bits of gwbp_field_compare on the fp32 copy of the field, whatever the map's type, and no such copy is
+ * made.  The reduction order is the one documented above.  gwbp_field_compare is a call of this function with GWBP_MAP_F32. */
+GWBP_API int gwbp_field_compare_typed(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                                      const void *features, int32_t field_type, int64_t ldf, int32_t D, const void *map,
+                                      int32_t map_type, int64_t ms_y, int64_t ms_x, int32_t lr_h, int32_t lr_w, const int32_t *ymap,
+                                      const int32_t *xmap, float *planes, double *table, void *stream);
 
 /* ---- a latent field and its decoder: decode, compare and the gradients back through the decoder, in one call ----------------------
  * Between the render of a [N, d] latent table and the scatter of its gradient (gwbp_render, gwbp_scatter).  Takes no workspace of a

@@ -8,7 +8,7 @@ uniform grid; the reference's only neighbour search is sklearn on the host, f3dg
     python run_clean.py --synthetic C1 --k 8 --remove-outliers --out /tmp/cleaned
 
 --labels: a .pt tensor [N] (or a dict with 'labels', what run_transfer.py writes).  --mask: a .pt bool tensor [N] (or a dict with
-'mask3d' / 'mask').  --features: a .pt tensor [N, D].  Writes into --out whichever of labels.pt, mask3d.pt, features.pt were given,
+'mask3d' / 'mask').  --features: a .pt tensor [N, D] (float32, float16 or bfloat16; --field-dtype: the smoothed one's).  Writes into --out whichever of labels.pt, mask3d.pt, features.pt were given,
 cleaned; neighbors.pt ({'idx': [N, k] int32, 'dist': [N, k] float32}); and clean.json with the counts changed and removed and the
 grid's statistics.  With --synthetic and no inputs: seeded labels (a Voronoi partition of space with 5 % flipped) and a seeded mask
 with floaters on the scene's means.
@@ -35,6 +35,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--num-classes", type=int, default=None, help="labels outside [0, K) are ignored (default: max label + 1)")
     ap.add_argument("--mask", default=None, help=".pt bool tensor [N]: a 3-D mask (or a dict with 'mask3d' / 'mask')")
     ap.add_argument("--features", default=None, help=".pt tensor [N, D]: a field to average over the neighbours")
+    ap.add_argument("--field-dtype", choices=("fp32", "fp16", "bf16"), default="fp32",
+                    help="element type of the smoothed field in features.pt: fp16 / bf16 are the fp32 averages rounded once by the "
+                         "kernel's store (no fp32 field is made); the input field is read as it is stored")
     ap.add_argument("--k", type=int, default=8, help="spatial neighbours per Gaussian, itself included (1..32)")
     ap.add_argument("--iterations", type=int, default=1, help="rounds of the vote")
     ap.add_argument("--min-fraction", type=float, default=0.5, help="a Gaussian stays in the mask with this share of neighbours in it")
@@ -107,9 +110,9 @@ def main(argv=None) -> int:
         report["mask"] = {"before": n, "outliers_removed": n - int(kept.sum()), "after": int(kept.sum())}
         torch.save(kept.cpu(), os.path.join(args.out, "mask3d.pt"))
     if feats is not None:
-        out = gsbp_amd.smooth_features(means, feats.to(dev), neighbors=idx)
+        out = gsbp_amd.smooth_features(means, feats.to(dev), neighbors=idx, out_dtype=cli.FIELD_DTYPES[args.field_dtype])
         torch.save(out.cpu(), os.path.join(args.out, "features.pt"))
-        report["features"] = {"D": int(out.shape[1])}
+        report["features"] = {"D": int(out.shape[1]), "dtype": args.field_dtype}
     with open(os.path.join(args.out, "clean.json"), "w") as f:
         json.dump(report, f, indent=1)
     print(f"wrote {args.out}: {json.dumps({key: report[key] for key in report if key != 'grid'})}")

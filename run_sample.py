@@ -15,7 +15,7 @@ and opacity (the HIP path: csrc/sample.hip), the field blended over them and the
 dict with 'features' / 'field'); --labels: a .pt integer tensor [N] (or a dict with 'labels') with --num-classes; --gt: integer [Q]
 ground truth for the points (-1: not scored).  --radius r, or --radius-quantile q (default 0.99) of the Gaussians' reach; --mask: a
 .pt bool tensor [N], only these Gaussians take part; --fallback nearest: a point where no Gaussian counts takes the field of the
-Gaussian with the nearest centre.  Writes into --out: sampled_features.pt ({'features' [Q, D], 'valid' [Q], 'wsum' [Q]}),
+Gaussian with the nearest centre; --out-dtype fp16 | bf16: the sampled features in half.  Writes into --out: sampled_features.pt ({'features' [Q, D], 'valid' [Q], 'wsum' [Q]}),
 sampled_labels.pt ({'labels' int32 [Q], 'share' [Q]}), point_gaussians.pt ({'idx', 'weights', 'n_contrib', 'points'}), sample.json
 (the radius, the valid / truncated / fallback counts, the quantiles of n_contrib and wsum, the share of Gaussians whose reach
 exceeds the radius, the grid's statistics) and with --gt metrics.json (miou_recall of the points' counts).  With --synthetic and no
@@ -55,6 +55,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--alpha-min", type=float, default=None, help="the smallest weight that counts (default 1/255, the blend's)")
     ap.add_argument("--mask", default=None, help=".pt bool tensor [N]: only these Gaussians take part (or a dict with 'mask3d' / 'mask')")
     ap.add_argument("--fallback", choices=["nearest"], default=None, help="fill the points where no Gaussian counts")
+    ap.add_argument("--out-dtype", choices=("fp32", "fp16", "bf16"), default="fp32",
+                    help="element type of the sampled features: fp16 / bf16 are the fp32 rows rounded once by the kernel's store")
     ap.add_argument("--out", required=True, help="output directory")
     return ap
 
@@ -177,7 +179,8 @@ def main(argv=None) -> int:
               "n_contrib_quantiles": _quantiles(pg.n_contrib), "visited_mean": float(pg.visited.double().mean()) if nq else 0.0,
               "beyond_radius": pg.beyond_radius, "grid": pg.grid_stats}
     if feats is not None:
-        out, ok, wsum = gsbp_amd.sample_field(feats.to(dev), pg, args.fallback or "none", return_wsum=True)
+        out, ok, wsum = gsbp_amd.sample_field(feats.to(dev), pg, args.fallback or "none", return_wsum=True,
+                                              out_dtype=cli.FIELD_DTYPES[args.out_dtype])
         if args.fallback:
             report["fallback"] = sample.fallback_rows(pg, ok)
         torch.save({"features": out.cpu(), "valid": ok.cpu(), "wsum": wsum.cpu()}, os.path.join(args.out, "sampled_features.pt"))
