@@ -108,6 +108,10 @@ typedef struct gwbp_stats {
     uint32_t n_headers;   /* (Gaussian, tile) pairs with at least one contributing pixel */
     uint32_t pool_used;   /* weight-pool entries a uniform shard capacity would need: kShards x fullest shard */
     uint32_t overflow;    /* bit0: isect_cap exceeded, bit1: pair_cap exceeded -> results of this view invalid;
+                           * (bit0: n_isect reads 0 and every later stage sees an EMPTY view.  bit1: the blend itself completes --
+                           * its alpha map is right and n_pairs keeps counting past the exhausted pool, so it is the count an ample
+                           * pool would report and a caller can size its retry from it; the store, n_headers and pool_used of that
+                           * blend are undefined)
                            * bit4: internal error -- a wave of gwbp_blend_scatter_encoded's producer / consumer form gave up waiting on
                            * its ring of encoded tiles (the launch ends instead of hanging; the view's result is invalid);
                            * bit3: gwbp_blend_tokens met a tile that spans more than 2 x 2 tokens (precondition violated) -> invalid;
