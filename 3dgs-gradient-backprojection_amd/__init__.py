@@ -30,6 +30,8 @@ JojiJoseph/3dgs-gradient-backprojection), hand-written HIP kernels behind a C AB
     from gsbp_amd import edge_strength, region_prompt_mask  # spatial k-NN graph cut where the features' cosine falls below a threshold
     from gsbp_amd import point_gaussians, sample_field, sample_labels, transfer_field, score_point_labels  # the field and its labels
                                                     # at arbitrary 3-D points, by each Gaussian's own scale, rotation and opacity
+    from gsbp_amd import pixel_gaussians, render_id_map, median_depth, pick_gaussians, lookup  # which Gaussians a pixel is made of:
+                                                    # per-pixel top-k lists, id maps, median depth, and a click -> Gaussian indices
 """
 from . import synthetic  # noqa: F401
 from ._lib import GwbpError, build, lib  # noqa: F401
@@ -58,4 +60,6 @@ from . import regions  # noqa: F401
 from .regions import edge_strength, neighbor_similarity, region_prompt_mask, similarity_components, similarity_levels, synthetic_regions  # noqa: F401
 from . import sample  # noqa: F401
 from .sample import PointGaussians, neighbor_blend, point_gaussians, sample_field, sample_labels, score_point_labels, suggest_sample_radius, synthetic_points, transfer_field, weighted_vote  # noqa: F401
+from . import pixels  # noqa: F401
+from .pixels import PixelGaussians, dominance_counts, lookup, median_depth, pick_gaussians, pixel_gaussians, render_id_map  # noqa: F401
 from .pruning import check_proper_pruning, gradient_mask, prune_by_gradients  # noqa: F401

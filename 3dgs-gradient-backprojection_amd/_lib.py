@@ -232,6 +232,8 @@ ARGTYPES = {
     # M, xy, X, ldx, D, out, depth, alpha, stream
     "gwbp_prompt_scores": [_I64, _I32, _I32, _I32, _P, _I64, _P, _I32, C.POINTER(C.c_float), _P, _P, _P],
     "gwbp_probe_pixels": _WSV + [_I32, _P, _P, _I64, _I32, _P, _P, _P, _P],
+    # k, M, xy, ids, weights, n_contrib, alpha, median_id, median_depth, stream
+    "gwbp_pixel_gaussians": _WSV + [_I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
     # labels, num_classes, maps, alphas, argmax, argmax_sums, min_opacity, gt, cut, counts, stream
     "gwbp_render_labels": _WSV + [_P, _I32, _P, _P, _P, _P, _F, _P, _I32, _P, _P],
     # features, ldf, D, map, map_type, ms_y, ms_x, lr_h, lr_w, ymap, xmap, planes, table, stream

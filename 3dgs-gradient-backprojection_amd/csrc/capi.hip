@@ -1790,6 +1790,28 @@ int gwbp_probe_pixels(const gwbp_caps *caps, void *workspace, size_t workspace_b
     return gwbp_probe_pixels_typed(caps, workspace, workspace_bytes, view_host, M, xy, X, GWBP_MAP_F32, ldx, D, out, depth, alpha, stream);
 }
 
+int gwbp_pixel_gaussians(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host, int32_t k, int32_t M,
+                         const int32_t *xy, int32_t *ids, float *weights, int32_t *n_contrib, float *alpha, int32_t *median_id,
+                         float *median_depth, void *stream)
+{
+    // the call's own arguments first: nothing of the caps, the workspace or the view is looked at before they pass
+    if (k < 1 || k > GWBP_PIXEL_TOPK_MAX)
+        return set_error(GWBP_EINVAL, "pixel_gaussians: k must be in [1, %d] (got %d)", GWBP_PIXEL_TOPK_MAX, (int)k);
+    if (xy && (M < 1 || M > GWBP_PROBE_MAX_PIXELS))
+        return set_error(GWBP_EINVAL, "pixel_gaussians: M must be in [1, %d] (got %d)", GWBP_PROBE_MAX_PIXELS, (int)M);
+    if (reinterpret_cast<uintptr_t>(xy) & 3)
+        return set_error(GWBP_EINVAL, "pixel_gaussians: xy must be 4-B aligned");
+    if (!ids || !weights || (reinterpret_cast<uintptr_t>(ids) & 3) || (reinterpret_cast<uintptr_t>(weights) & 3))
+        return set_error(GWBP_EINVAL, "pixel_gaussians: ids and weights must be non-null and 4-B aligned");
+    if ((reinterpret_cast<uintptr_t>(n_contrib) & 3) || (reinterpret_cast<uintptr_t>(alpha) & 3) ||
+        (reinterpret_cast<uintptr_t>(median_id) & 3) || (reinterpret_cast<uintptr_t>(median_depth) & 3))
+        return set_error(GWBP_EINVAL, "pixel_gaussians: n_contrib, alpha, median_id and median_depth must be 4-B aligned");
+    Bound B;
+    if (int rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B))
+        return rc;
+    return launch_pixel_gaussians(B.W, B.V, k, M, xy, ids, weights, n_contrib, alpha, median_id, median_depth, B.s);
+}
+
 int gwbp_render_labels(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
                        const int32_t *labels, int32_t num_classes, float *maps, float *alphas, int32_t *argmax, float *argmax_sums,
                        float min_opacity, const int32_t *gt, int32_t cut, uint64_t *counts, void *stream)

@@ -389,6 +389,10 @@ int launch_probe_pixels(const Ws &W, const ViewDev &V, int M, const int32_t *xy,
                         float *depth, float *alpha, hipStream_t s);
 void launch_probe_pixels_half(const Ws &W, const ViewDev &V, int M, const int32_t *xy, const void *X, int mt, int64_t ldx, int D,
                               float *out, float *depth, float *alpha, hipStream_t s);
+// the Gaussians a pixel is made of (pixels.hip): xy == nullptr: every pixel of the view, else the M pixels of xy; ids and weights
+// [P, k], the four per-pixel outputs may be nullptr
+int launch_pixel_gaussians(const Ws &W, const ViewDev &V, int k, int M, const int32_t *xy, int32_t *ids, float *weights,
+                           int32_t *n_contrib, float *alphas, int32_t *median_id, float *median_depth, hipStream_t s);
 int launch_dump_pairs(const Layout &L, const Ws &W, const ViewDev &V, int64_t cap, int32_t *gid, int32_t *pix,
                       float *w, u64 *n_dev, hipStream_t s);
 int launch_accum_stats(const Ws &W, gwbp_stats *accum, hipStream_t s);

@@ -17,6 +17,8 @@ TILE = 16
 # feature-map element types the scatter entry points take (GWBP_MAP_*); everything else the Engine computes in is float32
 MAP_TYPES = {torch.float32: _lib.MAP_F32, torch.float16: _lib.MAP_F16, torch.bfloat16: _lib.MAP_BF16}
 HALF_TYPES = (torch.float16, torch.bfloat16)
+PIXEL_TOPK_MAX = 16      # GWBP_PIXEL_TOPK_MAX (gwbp_pixel_gaussians' list length)
+PROBE_MAX_PIXELS = 4096  # GWBP_PROBE_MAX_PIXELS
 
 
 def nearest_index(n_in: int, n_out: int) -> torch.Tensor:
@@ -1063,6 +1065,33 @@ class Engine:
         self._call("gwbp_probe_pixels_typed", *self._args(), byref(view), M, ptr(xy), ptr(table), ft, c_int64(ld), D, ptr(out), ptr(depth),
                    ptr(alpha), self._stream())
         return out, depth, alpha
+
+    def pixel_gaussians(self, view, k: int, xy=None, want_median=True):
+        """The Gaussians each pixel is made of (gwbp_pixel_gaussians; needs project + bin_sort of `view`, not the weight store, and leaves
+        the workspace as it was): (ids int32 [P.., k], weights [P.., k], n_contrib int32 [P..], alpha [P..], median_id int32 [P..] or None,
+        median_depth [P..] or None) with P.. = [H, W], or [M] at the pixels xy [M, 2] (int32, (x, y)) only.  ids / weights: the k
+        contributing records of largest weight alpha T, heaviest first, equal weights by id; empty slots -1 / 0.  n_contrib > k: the
+        list was cut.  median: the record after which T <= 0.5 and its projected camera depth, -1 / 0 where T stays above one half."""
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= PIXEL_TOPK_MAX:
+            raise GwbpError(f"k must be an int in [1, {PIXEL_TOPK_MAX}], got {k!r}")
+        if xy is None:
+            M, shape = 0, (view.height, view.width)
+        else:
+            if not torch.is_tensor(xy) or xy.dtype != torch.int32 or xy.dim() != 2 or xy.shape[1] != 2 or not xy.is_cuda:
+                raise GwbpError("xy must be an int32 [M, 2] HIP tensor of (x, y) pixels")
+            xy = xy.contiguous()
+            M, shape = xy.shape[0], (xy.shape[0],)
+            if not 1 <= M <= PROBE_MAX_PIXELS:
+                raise GwbpError(f"the number of pixels must be in [1, {PROBE_MAX_PIXELS}], got {M}")
+        ids = torch.empty(*shape, k, dtype=torch.int32, device=self.device)
+        weights = torch.empty(*shape, k, device=self.device)
+        n_contrib = torch.empty(shape, dtype=torch.int32, device=self.device)
+        alpha = torch.empty(shape, device=self.device)
+        median_id = torch.empty(shape, dtype=torch.int32, device=self.device) if want_median else None
+        median_depth = torch.empty(shape, device=self.device) if want_median else None
+        self._call("gwbp_pixel_gaussians", *self._args(), byref(view), k, M, ptr(xy), ptr(ids), ptr(weights), ptr(n_contrib), ptr(alpha),
+                   ptr(median_id), ptr(median_depth), self._stream())
+        return ids, weights, n_contrib, alpha, median_id, median_depth
 
     def render_labels(self, view, labels, num_classes: int, want_maps=True, want_alphas=True, want_argmax=False, gt=None,
                       counts=None, cut: int = 64, min_opacity: float = 0.0):

@@ -1019,6 +1019,26 @@ GWBP_API int gwbp_probe_pixels_typed(const gwbp_caps *caps, void *workspace, siz
                                      int32_t M, const int32_t *xy, const void *X, int32_t field_type, int64_t ldx, int32_t D, float *out,
                                      float *depth, float *alpha, void *stream);
 
+/* The Gaussians a pixel is made of -- the 2-D counterpart of gwbp_point_gaussians: needs gwbp_project (or gwbp_project_camera) +
+ * gwbp_bin_sort of the view in the workspace, like gwbp_render_pixels; no weight store.  It reads the workspace and writes nothing
+ * into it.  xy == NULL: every pixel of the view, P = height * width, row-major, M ignored.  xy != NULL: the P = M pixels p_m = (xy[2 m],
+ * xy[2 m + 1]) = (x, y), int32 on the DEVICE, 1 <= M <= GWBP_PROBE_MAX_PIXELS; a pixel outside the image gives an empty list,
+ * n_contrib 0, alpha 0 and median -1.  Both forms give the same bits at the same pixel.  With w_g(p) = alpha T, the blend's bits:
+ *   ids int32 [P, k], weights float [P, k]: the k contributing records of largest weight, by weight descending, equal weights by
+ *             Gaussian id ascending; empty slots hold id -1 and weight 0.  1 <= k <= GWBP_PIXEL_TOPK_MAX.  With k >= n_contrib[p] the
+ *             list is the complete row p of the view's weight matrix.
+ *   n_contrib int32 [P]: the number of contributing records; n_contrib[p] > k means the list was cut.
+ *   alpha float [P]: 1 - T, the bits of gwbp_render_pixels' alphas.
+ *   median_id int32 [P], median_depth float [P]: the first contributing record, in list (depth) order, after which T <= 0.5, and its
+ *             camera depth (the projection's: the z gwbp_probe_pixels' depth accumulates); -1 and 0 where T stays above one half.
+ * ids and weights are required; the other four may be NULL, which costs no store.
+ * GWBP_EINVAL before the workspace is looked at: k out of range, M out of range (with xy), a null or (4-B) misaligned ids or weights,
+ * a misaligned xy or optional output. */
+#define GWBP_PIXEL_TOPK_MAX 16
+GWBP_API int gwbp_pixel_gaussians(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host, int32_t k,
+                                  int32_t M, const int32_t *xy, int32_t *ids, float *weights, int32_t *n_contrib, float *alpha,
+                                  int32_t *median_id, float *median_depth, void *stream);
+
 /* ---- per-Gaussian labels rendered to 2-D class maps and scored (the reference's evaluate_results and render_affordance,
  * affordance_transfer/demo_affordance_transfer.py:1445-1611, 1399-1439) ------------------------------------------------------------
  * One blend pass over a projected and sorted view (gwbp_project or gwbp_project_camera + gwbp_bin_sort, like gwbp_render_pixels; no
