@@ -32,6 +32,8 @@ JojiJoseph/3dgs-gradient-backprojection), hand-written HIP kernels behind a C AB
                                                     # at arbitrary 3-D points, by each Gaussian's own scale, rotation and opacity
     from gsbp_amd import pixel_gaussians, render_id_map, median_depth, pick_gaussians, lookup  # which Gaussians a pixel is made of:
                                                     # per-pixel top-k lists, id maps, median depth, and a click -> Gaussian indices
+    from gsbp_amd import project_torch, sh_colors_torch  # rasterization() also trains: gradients w.r.t. means, quats, scales and
+                                                    # opacities -- a HIP blend backward, then autograd through these torch restatements
 """
 from . import synthetic  # noqa: F401
 from ._lib import GwbpError, build, lib  # noqa: F401
@@ -39,6 +41,7 @@ from .backproject import ViewPipeline, create_feature_field, create_label_field,
 from .engine import Engine, bilinear_index, narrow_labels, nearest_index  # noqa: F401
 from . import scene_io  # noqa: F401
 from .rasterization import rasterization  # noqa: F401
+from .projection import project_torch, sh_colors_torch  # noqa: F401
 from .transfer import knn_search, transfer_labels, vote_labels  # noqa: F401
 from .pca import PCABasis, fit_pca, pca_colors, pca_transform, render_pca  # noqa: F401
 from .segment import ClickSession, apply_mask3d, probe_pixels, prompt_mask, prompt_scores, render_prompt_mask  # noqa: F401

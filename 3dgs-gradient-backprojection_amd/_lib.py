@@ -163,6 +163,8 @@ ARGTYPES = {
                                           _P],
     "gwbp_render": _WSV + [_P, _I32, _P, _P],
     "gwbp_render_pixels": _WSV + [_P, _I32, _P, _P, _P],
+    # colors, ldc, D, v_out, v_alpha, v_colors, v_g2d, stream
+    "gwbp_render_pixels_backward": _WSV + [_P, _I64, _I32, _P, _P, _P, _P, _P],
     "gwbp_sh_colors": [_I64, _I32, _I32, _P, _P, C.POINTER(C.c_float), _P, _P],
     "gwbp_backproject_view": _WSV + [_P] * 4 + _MAP + [_F, _F, _P, _P, _P],
     "gwbp_encode_map": [_P, _I64, _I64, _I32, _I32, _I32, _P, _I32, _P, _I32, _P],

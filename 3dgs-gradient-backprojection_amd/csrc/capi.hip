@@ -1005,6 +1005,26 @@ int gwbp_render_pixels(const gwbp_caps *caps, void *workspace, size_t workspace_
     return gwbp_render_pixels_typed(caps, workspace, workspace_bytes, view_host, colors, GWBP_MAP_F32, D, D, out, alphas, stream);
 }
 
+int gwbp_render_pixels_backward(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                                const float *colors, int64_t ldc, int32_t D, const float *v_out, const float *v_alpha, float *v_colors,
+                                float *v_g2d, void *stream)
+{
+    Bound B;
+    int rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B);
+    if (rc)
+        return rc;
+    if (D < 1 || D > 32)
+        return set_error(GWBP_EINVAL, "render_pixels_backward needs 1 <= D <= 32 (got D=%d)", D);
+    if (!colors || !v_out || !v_g2d)
+        return set_error(GWBP_EINVAL, "render_pixels_backward needs colors, v_out and v_g2d (got %s colors, %s v_out, %s v_g2d)",
+                         colors ? "a" : "null", v_out ? "a" : "null", v_g2d ? "a" : "null");
+    if ((rc = check_render_payload("render_pixels_backward", colors, GWBP_MAP_F32, ldc, D, v_out, GWBP_MAP_F32)))
+        return rc;
+    if ((reinterpret_cast<uintptr_t>(v_alpha) | reinterpret_cast<uintptr_t>(v_colors) | reinterpret_cast<uintptr_t>(v_g2d)) & 3)
+        return set_error(GWBP_EINVAL, "render_pixels_backward: v_alpha, v_colors and v_g2d must be 4-B aligned");
+    return launch_render_px_bwd(B.W, B.V, colors, ldc, D, v_out, v_alpha, v_colors, v_g2d, B.s);
+}
+
 int gwbp_sh_colors(int64_t N, int32_t degree, int32_t K, const float *means, const float *coeffs,
                    const float *campos_host, float *out, void *stream)
 {

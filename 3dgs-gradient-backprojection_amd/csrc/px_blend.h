@@ -47,6 +47,16 @@ __device__ __forceinline__ bool px_step(float sigma, float opac, float &T, bool 
     return valid;
 }
 
+// The record's alpha at a pixel as px_step computes it (the same expression: the same bits), with its two factors: vis = exp(-sigma)
+// and raw = opac * vis, the value before the clamp at kAlphaMax.  For the walk back over a pixel's list (k_render_px_bwd), which
+// needs d(alpha) / d(sigma, opac) and has no T / done to advance.
+__device__ __forceinline__ float px_alpha(float sigma, float opac, float &vis, float &raw)
+{
+    vis = exp_neg(-__builtin_fmaxf(sigma, 0.f));
+    raw = opac * vis;
+    return __builtin_fminf(kAlphaMax, raw);
+}
+
 // Wave-uniform: nobody in the wave takes anything from this record (skips the payload's reads and adds).
 __device__ __forceinline__ bool px_nobody(bool valid) { return __ballot(valid) == 0ull; }
 

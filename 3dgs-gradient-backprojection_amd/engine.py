@@ -1045,6 +1045,31 @@ class Engine:
                    ptr(alphas), self._stream())
         return out, alphas
 
+    def render_pixels_backward(self, view, colors, v_out, v_alpha=None, want_colors=True):
+        """Backward of render_pixels (gwbp_render_pixels_backward; needs project + bin_sort of `view`, not the weight store): from the
+        gradient v_out [H, W, D] (and v_alpha [H, W]) that reaches the render of the float32 table colors [N, D], D <= 32, the pair
+        (v_colors [N, D] or None, v_g2d [N, 6]); v_g2d = d / d(mx, my, ca, cb, cc, o) of the projected records, o the opacity the blend
+        read (under the antialiased mode: opacity x compensation).  Float atomics in an order that is not fixed: not bit-reproducible
+        from run to run."""
+        colors, ct = field_rows(colors, "colors")
+        if ct != _lib.MAP_F32:
+            raise GwbpError(f"render_pixels_backward reads a float32 colour table, got {colors.dtype}")
+        if colors.shape[0] != self.n:
+            raise GwbpError(f"engine was sized for {self.n} Gaussians, got a table of {colors.shape[0]} rows")
+        D = colors.shape[1]
+        v_out = _req(v_out, "v_out")
+        if tuple(v_out.shape) != (view.height, view.width, D):
+            raise GwbpError(f"v_out has shape {tuple(v_out.shape)}, expected {(view.height, view.width, D)}")
+        if v_alpha is not None:
+            v_alpha = _req(v_alpha, "v_alpha")
+            if v_alpha.numel() != view.height * view.width:
+                raise GwbpError(f"v_alpha has shape {tuple(v_alpha.shape)}, expected {(view.height, view.width)}")
+        v_g2d = torch.zeros(self.n, 6, device=self.device)
+        v_colors = torch.zeros(self.n, D, device=self.device) if want_colors else None
+        self._call("gwbp_render_pixels_backward", *self._args(), byref(view), ptr(colors), c_int64(row_stride(colors)), D, ptr(v_out),
+                   ptr(v_alpha), ptr(v_colors), ptr(v_g2d), self._stream())
+        return v_colors, v_g2d
+
     def probe_pixels(self, view, xy, table, want_depth=True, want_alpha=True):
         """The render of `table` [N, D] (float32, float16 or bfloat16, any row stride >= D, read as stored: a half table gives the bits of
         table.float() without that copy) at the pixels xy [M, 2] (int32, (x, y)) only:

@@ -6,8 +6,11 @@ Signature, defaults and return triple follow gsplat 1.4.0 (SURVEY.md section 3.2
 
 Forward  = project -> bin/sort -> blend_weights -> render   (all HIP kernels behind the C ABI)
 Backward = scatter with v_render_colors as the feature map: colors.grad[g,:] += sum_p w_g(p) v_render[p,:]
-           -- exactly what backproject.py:127-131 harvests.  Only `colors` receives a gradient (the reference
-           differentiates nothing else on this path); requesting other gradients raises.
+           -- exactly what backproject.py:127-131 harvests.  That is the whole backward while only `colors` requires grad.
+           When means / quats / scales / opacities do (and the table has at most 32 float32 channels) it is instead
+           gwbp_render_pixels_backward, the HIP backward of the per-pixel blend, followed by torch autograd through
+           projection.project_torch, the projection kernel restated in torch ops (_geometry_backward).  Gradients w.r.t.
+           viewmats / Ks, absgrad and meta["means2d"].grad (densification) are not offered; asking for them raises.
 """
 from __future__ import annotations
 
@@ -20,6 +23,7 @@ from torch.utils import _pytree
 from . import _lib
 from ._lib import GwbpError
 from .engine import HALF_TYPES, TILE, Engine
+from .projection import project_torch, sh_colors_torch
 
 _ENGINES: Dict[Tuple, Engine] = {}
 # The reference's harvesting pattern hands the SAME all-zero colour table to every view (backproject.py:67-72): whether a
@@ -38,6 +42,9 @@ _SAMPLE_ROWS = 257
 # C2: 0.59 ms for RGB, 0.91 ms for 16 channels, where blend + weight-store render take 0.75 + 1.13; the kernel goes up to 32
 # channels, but at 1.88 ms it no longer beats that route there)
 PIXEL_RENDER_MAX_DIM = 16
+# gradients w.r.t. means / quats / scales / opacities exist beside colour tables of at most this many channels (the blend backward
+# kernel, gwbp_render_pixels_backward, holds a pixel's channels in registers)
+GEOMETRY_GRAD_MAX_DIM = 32
 
 
 def invalidate_zero_table_cache() -> None:
@@ -178,6 +185,45 @@ def run_front(eng: Engine, view, means, quats, scales, opacities, want_alphas, w
         eng.grow(st)
 
 
+def _geometry_path(needs, colors: torch.Tensor) -> bool:
+    """Does this call's backward go through the blend backward kernel?  Some of means / quats / scales / opacities needs a gradient
+    (`needs`) and the table is one the kernel reads: float32, at most GEOMETRY_GRAD_MAX_DIM channels."""
+    return bool(any(needs)) and colors.shape[1] <= GEOMETRY_GRAD_MAX_DIM and colors.dtype == torch.float32
+
+
+def _geometry_backward(ctx, g_out, g_alpha):
+    """Backward of one view w.r.t. everything but the camera: the HIP kernel differentiates the per-pixel blend (H x W x list
+    length) down to each projected record -- 2-D mean, conic, filed opacity -- and to the colour table; torch autograd carries the
+    N-sized rest through project_torch, k_project restated in torch ops, on the rows the kernel's projection kept.  Float atomics in
+    an order that is not fixed: these gradients are not bit-reproducible from run to run."""
+    eng, view = ctx.eng, ctx.view
+    means, quats, scales, opacities, colors = ctx.saved_tensors
+    if eng.generation != ctx.gen or eng.n != means.shape[0]:
+        # the workspace was reused by another call since forward: project and sort this view again (no weight store needed)
+        eng = get_engine(means.device, means.shape[0], view.width, view.height)
+        eng.front_cache = None
+        run_front(eng, view, means, quats, scales, opacities, False, False, want_store=False)
+    needs = ctx.needs_input_grad
+    if g_out is None:
+        g_out = torch.zeros(view.height, view.width, ctx.shape[1], device=means.device)
+    v_colors, v_g2d = eng.render_pixels_backward(view, colors.detach(), g_out.detach(),
+                                                 g_alpha.detach() if g_alpha is not None else None, want_colors=needs[0])
+    # The chain through the projection runs in float64: it is N-sized (a few dozen elementwise passes over the visible rows, against
+    # H x W x list length for the blend), and the 2 x 2 inverse it differentiates loses, in float32, more than the blend kernel does
+    # (scales on the stacked test scenes: 4e-7 .. 6e-7 relative from a float32 chain on the device fed with exact record gradients).
+    with torch.enable_grad():
+        ins = [t.detach().double().requires_grad_(bool(n)) for t, n in zip((means, quats, scales, opacities), needs[1:5])]
+        vm = torch.tensor(list(view.viewmat), dtype=torch.float64).reshape(4, 4)
+        K = torch.tensor(list(view.K), dtype=torch.float64).reshape(3, 3)
+        model, mode = _lib.camera_of(view)
+        projected = project_torch(*ins, vm, K, view.width, view.height, float(view.eps2d), model, mode, ctx.visible)
+        wanted = [t for t in ins if t.requires_grad]
+        v = v_g2d.double()
+        got = iter(torch.autograd.grad(projected, wanted, (v[:, :2], v[:, 2:5], v[:, 5]), allow_unused=True))
+    grads = tuple(next(got) if t.requires_grad else None for t in ins)
+    return (v_colors,) + tuple(g if g is None else g.float() for g in grads) + (None,) * 7
+
+
 class _Rasterize(torch.autograd.Function):
     @staticmethod
     def forward(ctx, colors, means, quats, scales, opacities, viewmat, K, width, height, kw, holder, harvest=None):
@@ -185,16 +231,21 @@ class _Rasterize(torch.autograd.Function):
         eng = get_engine(dev, means.shape[0], width, height)
         view = eng.view(viewmat, K, width, height, **kw)
         D = colors.shape[1]
-        need_store = colors.requires_grad or D > PIXEL_RENDER_MAX_DIM  # the weight store is only needed for backward / the wide render
+        # means / quats / scales / opacities want a gradient and the blend backward kernel can give it (_geometry_backward): that
+        # kernel needs the sorted lists only, hands the colour gradient back as well, and reads which rows the projection kept
+        geo = _geometry_path(ctx.needs_input_grad[1:5], colors)
+        # the weight store is only needed for the colour backward / the wide render
+        need_store = (colors.requires_grad and not geo) or D > PIXEL_RENDER_MAX_DIM
         # a backward with D % 256 == 0 channels goes through the 256-channel scatter kernel, which needs the blend's
         # half-tile lists: the flag must be in place before this view's blend
         eng.set_narrow_scatter(not (colors.requires_grad and D % 256 == 0))
         # the reference's harvesting pattern: an all-zero differentiable colour table whose render is only there to be
         # back-propagated through (backproject.py:67-72,115-129,133-147) -- the render of zeros is zeros, for any D
         if harvest is None:
-            harvest = colors.requires_grad and _is_zero_table(colors)
+            harvest = colors.requires_grad and not geo and _is_zero_table(colors)
+        harvest = harvest and not geo  # (the zero render has no alpha-map or geometry history to offer)
         proj, bins, alphas, st = run_front(eng, view, means, quats, scales, opacities, D > PIXEL_RENDER_MAX_DIM or harvest,
-                                            holder is not None, want_store=need_store)
+                                            holder is not None or geo, want_store=need_store)
         if harvest:
             out = _zero_render(dev, view.height, view.width, D)  # (alphas: the blend's, kept with the front-stage result)
         elif D <= PIXEL_RENDER_MAX_DIM:  # RGB / RGB+D / depth / the 16-d compressed field (segment_compressed.py:154-165):
@@ -206,19 +257,27 @@ class _Rasterize(torch.autograd.Function):
         if holder is not None:
             holder.update(proj=proj, bins=bins, stats=st)
         ctx.eng, ctx.view, ctx.gen = eng, view, eng.generation
-        ctx.save_for_backward(means, quats, scales, opacities)
+        ctx.save_for_backward(*((means, quats, scales, opacities) + ((colors,) if geo else ())))
         ctx.shape = colors.shape
         # the leaf whose .grad the backward may add into directly (see backward)
         ctx.leaf = weakref.ref(colors) if (colors.requires_grad and colors.is_leaf) else None
         ctx.leaf_node = _accumulate_node(colors) if ctx.leaf is not None else None
-        ctx.mark_non_differentiable(alphas)
+        ctx.geo = geo
+        if geo:  # (the alpha map depends on the geometry and the opacities: it carries a gradient here)
+            ctx.visible = proj["radii"] > 0
+        else:
+            ctx.mark_non_differentiable(alphas)
         return out, alphas
 
     @staticmethod
     def backward(ctx, g_out, g_alpha):
-        if any(ctx.needs_input_grad[1:7]):
-            raise NotImplementedError("only d/d(colors) is implemented: the reference differentiates nothing else "
-                                      "(backproject.py:67-72,129,147)")
+        if any(ctx.needs_input_grad[5:7]) or (any(ctx.needs_input_grad[1:5]) and not ctx.geo):
+            raise NotImplementedError(
+                "gradients are implemented w.r.t. colors and, beside a float32 colour table of at most "
+                f"{GEOMETRY_GRAD_MAX_DIM} channels, w.r.t. means, quats, scales and opacities; not w.r.t. viewmats / Ks, and not "
+                "w.r.t. the geometry beside a wider or a float16 / bfloat16 table")
+        if ctx.geo:
+            return _geometry_backward(ctx, g_out, g_alpha)
         eng, view = ctx.eng, ctx.view
         means, quats, scales, opacities = ctx.saved_tensors
         if eng.generation != ctx.gen or eng.n != means.shape[0] or not ctx.has_store:
@@ -481,6 +540,10 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     row stride >= D -- and render_colors is float32 with the bits of the call on colors.float().  There is no gradient through a half
     table (NotImplementedError if it requires grad); SH coefficient tables are float32 only; the depth render modes concatenate the
     float32 depth column to the table, which widens it (torch's promotion).
+    Gradients: w.r.t. colors always (and SH coefficients); w.r.t. means, quats, scales and opacities when the rendered table (the depth
+    column included) is float32 with at most 32 channels -- every camera model, both rasterize modes, backgrounds and every render
+    mode; these sums use float atomics and are not bit-reproducible from run to run.  Not w.r.t. viewmats / Ks; meta["means2d"]
+    carries no gradient, so densification by means2d.grad is not offered yet.
     """
     if tile_size != TILE:
         raise GwbpError(f"tile_size must be {TILE}: the tile rectangle is part of the numerics")
@@ -509,9 +572,14 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
             sh = colors if colors.dim() == 3 else colors[c]
             vm_h = vm.detach().cpu()
             campos = (-(vm_h[:3, :3].T @ vm_h[:3, 3])).tolist()
-            if sh.requires_grad:
-                raise NotImplementedError("gradients w.r.t. SH coefficients are not on the reference's path")
-            cols = get_engine(means.device, N, width, height).sh_colors(sh_degree, means, sh, campos)
+            if torch.is_grad_enabled() and (sh.requires_grad or means.requires_grad):
+                # k_sh_colors in torch ops: autograd carries the colour gradient to the coefficients and, through the view
+                # direction, to means
+                if sh.dtype != torch.float32:
+                    raise GwbpError(f"sh coefficients must be float32, got {sh.dtype}")
+                cols = sh_colors_torch(sh_degree, means, sh, campos)
+            else:
+                cols = get_engine(means.device, N, width, height).sh_colors(sh_degree, means, sh, campos)
         else:
             cols = colors if colors.dim() == 2 else colors[c]
         holder = {} if (want_meta or "D" in render_mode) else None
@@ -521,7 +589,8 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
             cols = z if render_mode in ("D", "ED") else torch.cat([cols, z], dim=1)
         if cols.dtype not in HALF_TYPES:  # (a half table is read as stored, row stride included: Engine.render's field_rows)
             cols = cols.contiguous()
-        harvest = bool(cols.requires_grad and _is_zero_table(cols))
+        geo = torch.is_grad_enabled() and _geometry_path([t.requires_grad for t in (means, quats, scales, opacities)], cols)
+        harvest = bool(cols.requires_grad and not geo and _is_zero_table(cols))
         out, alpha = _Rasterize.apply(cols, means, quats, scales, opacities, vm, K, width, height, kw, holder, harvest)
         if _HARVEST_SHORTCUT and harvest and render_mode == "RGB" and backgrounds is None and out.requires_grad:
             out = out.as_subclass(_HarvestRender)  # recognises `(render * feats).sum()`, behaves like a tensor otherwise

@@ -536,6 +536,23 @@ GWBP_API int gwbp_render_pixels_typed(const gwbp_caps *caps, void *workspace, si
                                       const void *colors, int32_t color_type, int64_t ldc, int32_t D, float *out, float *alphas,
                                       void *stream);
 
+/* Backward of gwbp_render_pixels for an fp32 table (gsplat's rasterize_to_pixels_bwd): needs gwbp_project (or gwbp_project_camera) +
+ * gwbp_bin_sort of the same view in the workspace, not the weight store, and writes nothing into the workspace.
+ *   colors float [N, ldc], 1 <= D <= 32, ldc >= D: the table that was rendered.
+ *   v_out float [H, W, D] (dense), v_alpha float [H, W] or NULL: the gradient that reaches the render and its alpha map.
+ *   v_g2d float [N, 6], ADDED INTO: d / d(mx, my, ca, cb, cc, o) of each projected record -- the 2-D mean, the conic and the opacity the
+ *          blend read, which under the antialiased mode already holds the compensation.  A pair whose o exp(-sigma) was clamped at
+ *          0.999 adds nothing here (its alpha does not move), as in gsplat.
+ *   v_colors float [N, D] (dense) or NULL, ADDED INTO: d / d(colors).
+ * The caller zeroes the outputs.  The kernel replays the forward walk with the render's own expressions (the same valid pairs, the
+ * same T bit for bit), then walks each tile's list back to front; each record's sums over a tile are added with one float atomic per
+ * value, in an order that is not fixed: the results are NOT bit-reproducible from run to run.
+ * After the caps, the workspace and the view: D outside [1, 32], a null colors, v_out or v_g2d, ldc < D or a pointer that is not 4-B
+ * aligned are GWBP_EINVAL before any HIP call. */
+GWBP_API int gwbp_render_pixels_backward(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                                         const float *colors, int64_t ldc, int32_t D, const float *v_out, const float *v_alpha,
+                                         float *v_colors, float *v_g2d, void *stream);
+
 /* gsplat spherical_harmonics + "+0.5, clamp at 0": coeffs[N,K,3] (K >= (degree+1)^2, degree <= 3), view directions
  * means - campos_host[3]; out[N,3].  What rasterization(..., sh_degree=3) does before rasterising (backproject.py:99). */
 GWBP_API int gwbp_sh_colors(int64_t N, int32_t degree, int32_t K, const float *means, const float *coeffs,
