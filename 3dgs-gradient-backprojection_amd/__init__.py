@@ -33,7 +33,10 @@ JojiJoseph/3dgs-gradient-backprojection), hand-written HIP kernels behind a C AB
     from gsbp_amd import pixel_gaussians, render_id_map, median_depth, pick_gaussians, lookup  # which Gaussians a pixel is made of:
                                                     # per-pixel top-k lists, id maps, median depth, and a click -> Gaussian indices
     from gsbp_amd import project_torch, sh_colors_torch  # rasterization() also trains: gradients w.r.t. means, quats, scales and
-                                                    # opacities -- a HIP blend backward, then autograd through these torch restatements
+                                                    # opacities -- a HIP blend backward, then a HIP projection backward; these are the
+                                                    # torch restatements the tests measure them against
+    from gsbp_amd import refine_pose, se3_exp, pose_error  # and it localises: rasterization(camera_grad=True) differentiates the view
+                                                    # matrix; refine_pose finds where an image or feature map was taken from
 """
 from . import synthetic  # noqa: F401
 from ._lib import GwbpError, build, lib  # noqa: F401
@@ -65,4 +68,6 @@ from . import sample  # noqa: F401
 from .sample import PointGaussians, neighbor_blend, point_gaussians, sample_field, sample_labels, score_point_labels, suggest_sample_radius, synthetic_points, transfer_field, weighted_vote  # noqa: F401
 from . import pixels  # noqa: F401
 from .pixels import PixelGaussians, dominance_counts, lookup, median_depth, pick_gaussians, pixel_gaussians, render_id_map  # noqa: F401
+from . import pose  # noqa: F401
+from .pose import pose_error, refine_pose, se3_exp  # noqa: F401
 from .pruning import check_proper_pruning, gradient_mask, prune_by_gradients  # noqa: F401

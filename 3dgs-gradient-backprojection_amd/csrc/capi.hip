@@ -1025,6 +1025,47 @@ int gwbp_render_pixels_backward(const gwbp_caps *caps, void *workspace, size_t w
     return launch_render_px_bwd(B.W, B.V, colors, ldc, D, v_out, v_alpha, v_colors, v_g2d, B.s);
 }
 
+int gwbp_project_backward_blocks(int64_t n_gaussians)
+{
+    if (n_gaussians < 0 || (n_gaussians + kScanBlock - 1) / kScanBlock > 0x7FFFFFFF)
+        return set_error(GWBP_EINVAL, "project_backward_blocks: %lld Gaussians out of range", (long long)n_gaussians);
+    return project_backward_blocks(n_gaussians);
+}
+
+int gwbp_project_backward(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                          int32_t camera_model, int32_t rasterize_mode, const float *means, const float *quats, const float *scales,
+                          const float *opacities, const float *v_g2d, float *v_means, float *v_quats, float *v_scales,
+                          float *v_opacities, double *v_viewmat, double *scratch, void *stream)
+{
+    Bound B;
+    int rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B);
+    if (rc)
+        return rc;
+    if (camera_model != GWBP_CAMERA_PINHOLE && camera_model != GWBP_CAMERA_ORTHO && camera_model != GWBP_CAMERA_FISHEYE)
+        return set_error(GWBP_EINVAL, "unknown camera model %d", (int)camera_model);
+    if (rasterize_mode != GWBP_RASTERIZE_CLASSIC && rasterize_mode != GWBP_RASTERIZE_ANTIALIASED)
+        return set_error(GWBP_EINVAL, "unknown rasterize mode %d", (int)rasterize_mode);
+    if (!means || !quats || !scales || !opacities || !v_g2d)
+        return set_error(GWBP_EINVAL, "project_backward needs means, quats, scales, opacities and v_g2d (got %s means, %s quats, %s "
+                         "scales, %s opacities, %s v_g2d)", means ? "a" : "null", quats ? "a" : "null", scales ? "a" : "null",
+                         opacities ? "a" : "null", v_g2d ? "a" : "null");
+    if (!v_means && !v_quats && !v_scales && !v_opacities && !v_viewmat)
+        return set_error(GWBP_EINVAL, "project_backward: every output is null");
+    if (v_viewmat && !scratch)
+        return set_error(GWBP_EINVAL, "project_backward: v_viewmat needs the scratch (gwbp_project_backward_blocks(N) x 12 doubles)");
+    if ((reinterpret_cast<uintptr_t>(quats) | reinterpret_cast<uintptr_t>(v_quats)) & 15)
+        return set_error(GWBP_EINVAL, "project_backward: quats and v_quats must be 16-B aligned");
+    if ((reinterpret_cast<uintptr_t>(means) | reinterpret_cast<uintptr_t>(scales) | reinterpret_cast<uintptr_t>(opacities) |
+         reinterpret_cast<uintptr_t>(v_g2d) | reinterpret_cast<uintptr_t>(v_means) | reinterpret_cast<uintptr_t>(v_scales) |
+         reinterpret_cast<uintptr_t>(v_opacities)) & 3)
+        return set_error(GWBP_EINVAL, "project_backward: means, scales, opacities, v_g2d, v_means, v_scales and v_opacities must be "
+                         "4-B aligned");
+    if ((reinterpret_cast<uintptr_t>(v_viewmat) | reinterpret_cast<uintptr_t>(scratch)) & 7)
+        return set_error(GWBP_EINVAL, "project_backward: v_viewmat and scratch must be 8-B aligned");
+    return launch_project_bwd(B.L, B.W, B.V, camera_model, rasterize_mode, means, quats, scales, opacities, v_g2d, v_means, v_quats,
+                              v_scales, v_opacities, v_viewmat, scratch, B.s);
+}
+
 int gwbp_sh_colors(int64_t N, int32_t degree, int32_t K, const float *means, const float *coeffs,
                    const float *campos_host, float *out, void *stream)
 {

@@ -294,6 +294,12 @@ int launch_sh_colors(int64_t N, int degree, int K, const float *means, const flo
 // backward of launch_render_px for an fp32 table (render_grad.hip): adds into v_g2d [N, 6] and, unless nullptr, v_colors [N, D]
 int launch_render_px_bwd(const Ws &W, const ViewDev &V, const float *colors, int64_t ldc, int D, const float *v_out,
                          const float *v_alpha, float *v_colors, float *v_g2d, hipStream_t s);
+// backward of launch_project (project_grad.hip) on the records the projection of the same view left in the workspace: WRITES the
+// per-Gaussian gradients (each may be nullptr) and v_viewmat [12] (nullptr, or with scratch [project_backward_blocks(n), 12])
+int project_backward_blocks(int64_t n);
+int launch_project_bwd(const Layout &L, const Ws &W, const ViewDev &V, int camera_model, int rasterize_mode, const float *means,
+                       const float *quats, const float *scales, const float *opac, const float *v_g2d, float *v_means, float *v_quats,
+                       float *v_scales, float *v_opac, double *v_viewmat, double *scratch, hipStream_t s);
 // per-Gaussian labels rendered to class maps, their argmax and the counts against a ground-truth map (label_render.hip); every
 // output may be nullptr; best: the largest class sum per pixel, needed beside argmax from K > 64 on (the carry between chunks)
 int launch_render_labels(const Ws &W, const ViewDev &V, const int32_t *labels, int K, float *maps, float *alphas, int32_t *argmax,

@@ -1070,6 +1070,42 @@ class Engine:
                    ptr(v_alpha), ptr(v_colors), ptr(v_g2d), self._stream())
         return v_colors, v_g2d
 
+    def project_backward(self, view, means, quats, scales, opacities, v_g2d, needs=(True,) * 4, want_viewmat=False):
+        """Backward of project (gwbp_project_backward; needs the projection of `view` and of these Gaussians in the workspace, which
+        says which rows are visible): from v_g2d [N, 6] = d / d(mx, my, ca, cb, cc, o) of the projected records, as
+        render_pixels_backward returns it, the tuple (v_means [N, 3], v_quats [N, 4], v_scales [N, 3], v_opacities [N], v_viewmat).
+        needs: which of the four float32 per-Gaussian gradients to compute (the others are None); want_viewmat: also the gradient of
+        the view matrix, float64 [4, 4] with a zero bottom row (None otherwise).  The chain is evaluated in float64 per Gaussian and
+        rounded once; culled rows get exact zeros; the view sums take no atomics: the same inputs give the same bits."""
+        means, quats = _req(means, "means", (3,)), _req(quats, "quats", (4,))
+        scales, opacities = _req(scales, "scales", (3,)), _req(opacities, "opacities")
+        v_g2d = _req(v_g2d, "v_g2d", (6,))
+        if not (means.shape[0] == quats.shape[0] == scales.shape[0] == opacities.shape[0] == v_g2d.shape[0] == self.n):
+            raise GwbpError(f"engine was sized for {self.n} Gaussians, got {means.shape[0]} means and {v_g2d.shape[0]} v_g2d rows")
+        needs = tuple(bool(x) for x in needs)
+        if len(needs) != 4 or not (any(needs) or want_viewmat):
+            raise GwbpError("project_backward: needs must have four entries, and at least one gradient must be asked for")
+        model, mode = _lib.camera_of(view)
+        with self._on_stream():
+            outs = [torch.empty((self.n,) + tail, device=self.device) if need else None
+                    for need, tail in zip(needs, ((3,), (4,), (3,), ()))]
+            flat = scratch = None
+            if want_viewmat:
+                blocks = int(self.lib.gwbp_project_backward_blocks(c_int64(self.n)))
+                if blocks < 0:
+                    check(blocks, "gwbp_project_backward_blocks")
+                flat = torch.empty(12, dtype=torch.float64, device=self.device)
+                scratch = torch.empty(max(1, blocks) * 12, dtype=torch.float64, device=self.device)
+            self._call("gwbp_project_backward", *self._args(), byref(view), _lib.CAMERA_MODELS[model], _lib.RASTERIZE_MODES[mode],
+                       ptr(means), ptr(quats), ptr(scales), ptr(opacities), ptr(v_g2d), *(ptr(t) for t in outs), ptr(flat),
+                       ptr(scratch), self._stream())
+            v_viewmat = None
+            if want_viewmat:
+                v_viewmat = torch.zeros(4, 4, dtype=torch.float64, device=self.device)
+                v_viewmat[:3, :3] = flat[:9].view(3, 3)
+                v_viewmat[:3, 3] = flat[9:]
+        return (*outs, v_viewmat)
+
     def probe_pixels(self, view, xy, table, want_depth=True, want_alpha=True):
         """The render of `table` [N, D] (float32, float16 or bfloat16, any row stride >= D, read as stored: a half table gives the bits of
         table.float() without that copy) at the pixels xy [M, 2] (int32, (x, y)) only:

@@ -1,11 +1,12 @@
 """The projection kernel and the SH colour kernel restated in differentiable torch ops.
 
 `rasterization()` differentiates the per-pixel blend with a HIP kernel (gwbp_render_pixels_backward), which leaves the gradient with
-respect to each projected record: 2-D mean, conic, opacity.  The chain rule from there back to means / quats / scales / opacities is
-N-sized, and torch autograd does it on `project_torch`: k_project's arithmetic (csrc/project.hip) for the three camera models and both
-rasterize modes, operation by operation where that matters for the FUNCTION (the pinhole clamp of x/z and y/z inside the Jacobian, the
-eps2d low-pass, the antialiasing compensation), not for the bits.  It never decides what is visible: the rows the kernel kept
-(`radii > 0`) come in as `visible`, every other row is zero and takes no gradient.
+respect to each projected record: 2-D mean, conic, opacity.  The chain rule from there back to means / quats / scales / opacities and
+the view matrix is N-sized and a second HIP kernel (gwbp_project_backward, csrc/project_grad.h).  `project_torch` is the function that
+kernel differentiates, and what the tests measure it against with torch autograd: k_project's arithmetic (csrc/project.hip) for the
+three camera models and both rasterize modes, operation by operation where that matters for the FUNCTION (the pinhole clamp of x/z and
+y/z inside the Jacobian, the eps2d low-pass, the antialiasing compensation), not for the bits.  It never decides what is visible: the
+rows the kernel kept (`radii > 0`) come in as `visible`, every other row is zero and takes no gradient.
 
 `sh_colors_torch` is k_sh_colors (csrc/render.hip) the same way: same basis constants, "+0.5", clamp at 0.
 """
@@ -77,7 +78,8 @@ def project_torch(means: torch.Tensor, quats: torch.Tensor, scales: torch.Tensor
     if visible is not None:
         idx = torch.nonzero(visible.to(dev))[:, 0]
         means, quats, scales, opacities = (t.index_select(0, idx) for t in (means, quats, scales, opacities))
-    vm, Km = viewmat.detach().to(dev, dt), K.detach().to(dev, dt)
+    # (a view matrix that requires grad stays attached: the yardstick of the camera gradient differentiates it)
+    vm, Km = (viewmat if viewmat.requires_grad else viewmat.detach()).to(dev, dt), K.detach().to(dev, dt)
     R, t = vm[:3, :3], vm[:3, 3]
     fx, fy, cx, cy = Km[0, 0], Km[1, 1], Km[0, 2], Km[1, 2]
     pc = means @ R.T + t

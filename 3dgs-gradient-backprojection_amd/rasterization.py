@@ -8,9 +8,10 @@ Forward  = project -> bin/sort -> blend_weights -> render   (all HIP kernels beh
 Backward = scatter with v_render_colors as the feature map: colors.grad[g,:] += sum_p w_g(p) v_render[p,:]
            -- exactly what backproject.py:127-131 harvests.  That is the whole backward while only `colors` requires grad.
            When means / quats / scales / opacities do (and the table has at most 32 float32 channels) it is instead
-           gwbp_render_pixels_backward, the HIP backward of the per-pixel blend, followed by torch autograd through
-           projection.project_torch, the projection kernel restated in torch ops (_geometry_backward).  Gradients w.r.t.
-           viewmats / Ks, absgrad and meta["means2d"].grad (densification) are not offered; asking for them raises.
+           gwbp_render_pixels_backward, the HIP backward of the per-pixel blend, followed by gwbp_project_backward, the HIP
+           backward of the projection (_geometry_backward); with camera_grad=True the same kernel also sums the gradient
+           w.r.t. viewmats.  Gradients w.r.t. Ks, absgrad and meta["means2d"].grad (densification) are not offered; asking
+           for them raises, and so does a default call whose viewmats require grad.
 """
 from __future__ import annotations
 
@@ -23,7 +24,7 @@ from torch.utils import _pytree
 from . import _lib
 from ._lib import GwbpError
 from .engine import HALF_TYPES, TILE, Engine
-from .projection import project_torch, sh_colors_torch
+from .projection import sh_colors_torch
 
 _ENGINES: Dict[Tuple, Engine] = {}
 # The reference's harvesting pattern hands the SAME all-zero colour table to every view (backproject.py:67-72): whether a
@@ -186,16 +187,18 @@ def run_front(eng: Engine, view, means, quats, scales, opacities, want_alphas, w
 
 
 def _geometry_path(needs, colors: torch.Tensor) -> bool:
-    """Does this call's backward go through the blend backward kernel?  Some of means / quats / scales / opacities needs a gradient
-    (`needs`) and the table is one the kernel reads: float32, at most GEOMETRY_GRAD_MAX_DIM channels."""
+    """Does this call's backward go through the blend backward kernel?  Some of means / quats / scales / opacities -- or, under
+    camera_grad=True, the view matrix -- needs a gradient (`needs`) and the table is one the kernel reads: float32, at most
+    GEOMETRY_GRAD_MAX_DIM channels."""
     return bool(any(needs)) and colors.shape[1] <= GEOMETRY_GRAD_MAX_DIM and colors.dtype == torch.float32
 
 
 def _geometry_backward(ctx, g_out, g_alpha):
-    """Backward of one view w.r.t. everything but the camera: the HIP kernel differentiates the per-pixel blend (H x W x list
-    length) down to each projected record -- 2-D mean, conic, filed opacity -- and to the colour table; torch autograd carries the
-    N-sized rest through project_torch, k_project restated in torch ops, on the rows the kernel's projection kept.  Float atomics in
-    an order that is not fixed: these gradients are not bit-reproducible from run to run."""
+    """Backward of one view: one HIP kernel differentiates the per-pixel blend (H x W x list length) down to each projected record --
+    2-D mean, conic, filed opacity -- and to the colour table; a second one (Engine.project_backward) carries the N-sized rest through
+    the projection in float64, on the rows the forward's projection kept, to means / quats / scales / opacities and, when the call
+    asked for it, to the view matrix.  The blend backward adds with float atomics in an order that is not fixed: these gradients are
+    not bit-reproducible from run to run end to end; the projection step itself is (same v_g2d, same bits)."""
     eng, view = ctx.eng, ctx.view
     means, quats, scales, opacities, colors = ctx.saved_tensors
     if eng.generation != ctx.gen or eng.n != means.shape[0]:
@@ -208,32 +211,24 @@ def _geometry_backward(ctx, g_out, g_alpha):
         g_out = torch.zeros(view.height, view.width, ctx.shape[1], device=means.device)
     v_colors, v_g2d = eng.render_pixels_backward(view, colors.detach(), g_out.detach(),
                                                  g_alpha.detach() if g_alpha is not None else None, want_colors=needs[0])
-    # The chain through the projection runs in float64: it is N-sized (a few dozen elementwise passes over the visible rows, against
-    # H x W x list length for the blend), and the 2 x 2 inverse it differentiates loses, in float32, more than the blend kernel does
-    # (scales on the stacked test scenes: 4e-7 .. 6e-7 relative from a float32 chain on the device fed with exact record gradients).
-    with torch.enable_grad():
-        ins = [t.detach().double().requires_grad_(bool(n)) for t, n in zip((means, quats, scales, opacities), needs[1:5])]
-        vm = torch.tensor(list(view.viewmat), dtype=torch.float64).reshape(4, 4)
-        K = torch.tensor(list(view.K), dtype=torch.float64).reshape(3, 3)
-        model, mode = _lib.camera_of(view)
-        projected = project_torch(*ins, vm, K, view.width, view.height, float(view.eps2d), model, mode, ctx.visible)
-        wanted = [t for t in ins if t.requires_grad]
-        v = v_g2d.double()
-        got = iter(torch.autograd.grad(projected, wanted, (v[:, :2], v[:, 2:5], v[:, 5]), allow_unused=True))
-    grads = tuple(next(got) if t.requires_grad else None for t in ins)
-    return (v_colors,) + tuple(g if g is None else g.float() for g in grads) + (None,) * 7
+    grads = eng.project_backward(view, means.detach(), quats.detach(), scales.detach(), opacities.detach(), v_g2d, needs=needs[1:5],
+                                 want_viewmat=bool(ctx.camera_grad and needs[5]))
+    v_vm = None if grads[4] is None else grads[4].to(ctx.vm_dtype)
+    return (v_colors,) + tuple(grads[:4]) + (v_vm,) + (None,) * 7
 
 
 class _Rasterize(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, colors, means, quats, scales, opacities, viewmat, K, width, height, kw, holder, harvest=None):
+    def forward(ctx, colors, means, quats, scales, opacities, viewmat, K, width, height, kw, holder, harvest=None, camera_grad=False):
         dev = means.device
         eng = get_engine(dev, means.shape[0], width, height)
         view = eng.view(viewmat, K, width, height, **kw)
         D = colors.shape[1]
         # means / quats / scales / opacities want a gradient and the blend backward kernel can give it (_geometry_backward): that
         # kernel needs the sorted lists only, hands the colour gradient back as well, and reads which rows the projection kept
-        geo = _geometry_path(ctx.needs_input_grad[1:5], colors)
+        # (camera_grad=True: the view matrix as well, through the same two kernels)
+        camera_grad = bool(camera_grad and ctx.needs_input_grad[5])
+        geo = _geometry_path(tuple(ctx.needs_input_grad[1:5]) + (camera_grad,), colors)
         # the weight store is only needed for the colour backward / the wide render
         need_store = (colors.requires_grad and not geo) or D > PIXEL_RENDER_MAX_DIM
         # a backward with D % 256 == 0 channels goes through the 256-channel scatter kernel, which needs the blend's
@@ -245,7 +240,7 @@ class _Rasterize(torch.autograd.Function):
             harvest = colors.requires_grad and not geo and _is_zero_table(colors)
         harvest = harvest and not geo  # (the zero render has no alpha-map or geometry history to offer)
         proj, bins, alphas, st = run_front(eng, view, means, quats, scales, opacities, D > PIXEL_RENDER_MAX_DIM or harvest,
-                                            holder is not None or geo, want_store=need_store)
+                                            holder is not None, want_store=need_store)
         if harvest:
             out = _zero_render(dev, view.height, view.width, D)  # (alphas: the blend's, kept with the front-stage result)
         elif D <= PIXEL_RENDER_MAX_DIM:  # RGB / RGB+D / depth / the 16-d compressed field (segment_compressed.py:154-165):
@@ -262,20 +257,20 @@ class _Rasterize(torch.autograd.Function):
         # the leaf whose .grad the backward may add into directly (see backward)
         ctx.leaf = weakref.ref(colors) if (colors.requires_grad and colors.is_leaf) else None
         ctx.leaf_node = _accumulate_node(colors) if ctx.leaf is not None else None
-        ctx.geo = geo
-        if geo:  # (the alpha map depends on the geometry and the opacities: it carries a gradient here)
-            ctx.visible = proj["radii"] > 0
-        else:
+        ctx.geo, ctx.camera_grad, ctx.vm_dtype = geo, camera_grad, viewmat.dtype
+        if not geo:  # (under geo the alpha map depends on the geometry, the opacities and the camera: it carries a gradient)
             ctx.mark_non_differentiable(alphas)
         return out, alphas
 
     @staticmethod
     def backward(ctx, g_out, g_alpha):
-        if any(ctx.needs_input_grad[5:7]) or (any(ctx.needs_input_grad[1:5]) and not ctx.geo):
+        needs = ctx.needs_input_grad
+        if needs[6] or (needs[5] and not (ctx.geo and ctx.camera_grad)) or (any(needs[1:5]) and not ctx.geo):
             raise NotImplementedError(
                 "gradients are implemented w.r.t. colors and, beside a float32 colour table of at most "
-                f"{GEOMETRY_GRAD_MAX_DIM} channels, w.r.t. means, quats, scales and opacities; not w.r.t. viewmats / Ks, and not "
-                "w.r.t. the geometry beside a wider or a float16 / bfloat16 table")
+                f"{GEOMETRY_GRAD_MAX_DIM} channels, w.r.t. means, quats, scales and opacities, and w.r.t. viewmats in a call with "
+                "camera_grad=True; not w.r.t. Ks, not w.r.t. viewmats in a default call (camera_grad=False), and not w.r.t. the "
+                "geometry or the camera beside a wider or a float16 / bfloat16 table")
         if ctx.geo:
             return _geometry_backward(ctx, g_out, g_alpha)
         eng, view = ctx.eng, ctx.view
@@ -298,10 +293,10 @@ class _Rasterize(torch.autograd.Function):
                 and _grad_is_unobserved(leaf, ctx.leaf_node)):
             _scatter_grad(eng, view, g_out, acc)
             acc[:0].add_(0)  # the kernel wrote through data_ptr: move .grad's version counter like an in-place op would
-            return (None,) * 12
+            return (None,) * 13
         v_colors = torch.zeros(ctx.shape, device=means.device, dtype=torch.float32)
         _scatter_grad(eng, view, g_out, v_colors)
-        return (v_colors,) + (None,) * 11
+        return (v_colors,) + (None,) * 12
 
 
 def _scatter_grad(eng: Engine, view, g_out: torch.Tensor, acc: torch.Tensor) -> None:
@@ -528,7 +523,7 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
                   sh_degree: Optional[int] = None, packed: bool = True, tile_size: int = 16, backgrounds=None,
                   render_mode: str = "RGB", sparse_grad: bool = False, absgrad: bool = False,
                   rasterize_mode: str = "classic", channel_chunk: int = 32, distributed: bool = False,
-                  camera_model: str = "pinhole", covars=None, want_meta: bool = True):
+                  camera_model: str = "pinhole", covars=None, want_meta: bool = True, camera_grad: bool = False):
     """Same call signature / defaults / returns as gsplat.rasterization (1.4.0).
 
     Returns (render_colors [C,H,W,D'], render_alphas [C,H,W,1], meta).  `channel_chunk`, `packed`, `sparse_grad`
@@ -542,8 +537,13 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     float32 depth column to the table, which widens it (torch's promotion).
     Gradients: w.r.t. colors always (and SH coefficients); w.r.t. means, quats, scales and opacities when the rendered table (the depth
     column included) is float32 with at most 32 channels -- every camera model, both rasterize modes, backgrounds and every render
-    mode; these sums use float atomics and are not bit-reproducible from run to run.  Not w.r.t. viewmats / Ks; meta["means2d"]
-    carries no gradient, so densification by means2d.grad is not offered yet.
+    mode; these sums use float atomics and are not bit-reproducible from run to run (the projection step of the backward by itself is).
+    camera_grad=True (an addition to gsplat's signature) also differentiates w.r.t. viewmats beside such a table, whether or not a
+    Gaussian tensor requires grad: viewmats.grad is float32 [C, 4, 4] with a zero bottom row; the depth column of the "D" render modes
+    is a torch function of viewmats[c] and adds its own share.  Without the keyword a call whose viewmats require grad raises in
+    backward, as it always did.  With it, Ks.requires_grad, sh_degree (the SH view direction uses a detached camera centre) and a wider
+    or half table raise at the call.  Not w.r.t. Ks; meta["means2d"] carries no gradient, so densification by means2d.grad is not
+    offered yet.
     """
     if tile_size != TILE:
         raise GwbpError(f"tile_size must be {TILE}: the tile rectangle is part of the numerics")
@@ -559,6 +559,12 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
         raise NotImplementedError("gradients w.r.t. a float16 / bfloat16 colour table are not implemented: render it detached, or "
                                   "differentiate the float32 table")
     width, height = int(width), int(height)  # utils.py:247-248 passes 0-d tensors
+    camera = bool(camera_grad) and torch.is_grad_enabled() and viewmats.requires_grad
+    if camera_grad and Ks.requires_grad:
+        raise NotImplementedError("gradients w.r.t. Ks are not implemented (camera_grad=True differentiates viewmats only)")
+    if camera and sh_degree is not None:
+        raise NotImplementedError("camera_grad=True with sh_degree: the SH view direction uses a detached camera centre, so the "
+                                  "gradient w.r.t. viewmats would miss it; pass colours, or detach viewmats")
     C_ = viewmats.shape[0]
     N = means.shape[0]
     kw = dict(near_plane=near_plane, far_plane=far_plane, eps2d=eps2d, radius_clip=radius_clip, camera_model=camera_model,
@@ -589,9 +595,12 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
             cols = z if render_mode in ("D", "ED") else torch.cat([cols, z], dim=1)
         if cols.dtype not in HALF_TYPES:  # (a half table is read as stored, row stride included: Engine.render's field_rows)
             cols = cols.contiguous()
-        geo = torch.is_grad_enabled() and _geometry_path([t.requires_grad for t in (means, quats, scales, opacities)], cols)
+        if camera and (cols.shape[1] > GEOMETRY_GRAD_MAX_DIM or cols.dtype != torch.float32):
+            raise NotImplementedError(f"camera_grad=True needs a float32 table of at most {GEOMETRY_GRAD_MAX_DIM} channels (the depth "
+                                      f"column included), got {cols.dtype} with {cols.shape[1]}")
+        geo = torch.is_grad_enabled() and _geometry_path([t.requires_grad for t in (means, quats, scales, opacities)] + [camera], cols)
         harvest = bool(cols.requires_grad and not geo and _is_zero_table(cols))
-        out, alpha = _Rasterize.apply(cols, means, quats, scales, opacities, vm, K, width, height, kw, holder, harvest)
+        out, alpha = _Rasterize.apply(cols, means, quats, scales, opacities, vm, K, width, height, kw, holder, harvest, camera)
         if _HARVEST_SHORTCUT and harvest and render_mode == "RGB" and backgrounds is None and out.requires_grad:
             out = out.as_subclass(_HarvestRender)  # recognises `(render * feats).sum()`, behaves like a tensor otherwise
         alpha = alpha[..., None]

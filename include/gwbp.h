@@ -553,6 +553,30 @@ GWBP_API int gwbp_render_pixels_backward(const gwbp_caps *caps, void *workspace,
                                          const float *colors, int64_t ldc, int32_t D, const float *v_out, const float *v_alpha,
                                          float *v_colors, float *v_g2d, void *stream);
 
+/* Backward of gwbp_project / gwbp_project_camera (gsplat's fully_fused_projection_bwd, and the view-matrix gradient with it): needs
+ * the projection of the same view (same camera_model, rasterize_mode and Gaussians) in the workspace -- a row is visible when its
+ * record there has radius > 0 -- and writes nothing into the workspace.
+ *   means, quats, scales, opacities: what was projected.  v_g2d float [N, 6]: d / d(mx, my, ca, cb, cc, o) of each projected record,
+ *          as gwbp_render_pixels_backward leaves it.
+ *   v_means [N, 3], v_quats [N, 4], v_scales [N, 3], v_opacities [N], float, each may be NULL: WRITTEN, not added into.  The chain is
+ *          evaluated in float64 from the stored float32 inputs (the forward is recomputed; the filed float32 conic is not read) and each
+ *          value rounded once.  The function differentiated is the projection's: the quaternion normalised inside, the pinhole clamp of
+ *          x/z and y/z inside the Jacobian passing no gradient where it binds, the eps2d low-pass, and under the antialiased mode the
+ *          compensation (zero gradient where det(S) / det(S + eps2d I) is not positive).  A culled row gets zeros and is not evaluated.
+ *   v_viewmat double [12] or NULL: d / d(viewmat[:3, :3]) row-major, then d / d(viewmat[:3, 3]), summed over the visible rows without
+ *          atomics in a fixed order (wave, block, then the blocks in order): the same inputs give the same bits.  It needs
+ *   scratch double [gwbp_project_backward_blocks(N), 12], which the call overwrites.
+ * After the caps, the workspace and the view: an unknown camera model or rasterize mode, a null means / quats / scales / opacities /
+ * v_g2d, every output null, v_viewmat without scratch, quats or v_quats not 16-B aligned, v_viewmat or scratch not 8-B aligned or any
+ * other pointer not 4-B aligned are GWBP_EINVAL before any HIP call. */
+GWBP_API int gwbp_project_backward(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                                   int32_t camera_model, int32_t rasterize_mode, const float *means, const float *quats,
+                                   const float *scales, const float *opacities, const float *v_g2d, float *v_means, float *v_quats,
+                                   float *v_scales, float *v_opacities, double *v_viewmat, double *scratch, void *stream);
+
+/* Rows of gwbp_project_backward's scratch for n_gaussians Gaussians (one per workgroup of 256: ceil(n / 256)), or GWBP_EINVAL. */
+GWBP_API int gwbp_project_backward_blocks(int64_t n_gaussians);
+
 /* gsplat spherical_harmonics + "+0.5, clamp at 0": coeffs[N,K,3] (K >= (degree+1)^2, degree <= 3), view directions
  * means - campos_host[3]; out[N,3].  What rasterization(..., sh_degree=3) does before rasterising (backproject.py:99). */
 GWBP_API int gwbp_sh_colors(int64_t N, int32_t degree, int32_t K, const float *means, const float *coeffs,
