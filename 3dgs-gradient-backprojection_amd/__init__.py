@@ -37,6 +37,9 @@ JojiJoseph/3dgs-gradient-backprojection), hand-written HIP kernels behind a C AB
                                                     # torch restatements the tests measure them against
     from gsbp_amd import refine_pose, se3_exp, pose_error  # and it localises: rasterization(camera_grad=True) differentiates the view
                                                     # matrix; refine_pose finds where an image or feature map was taken from
+    from gsbp_amd import photometric_loss, image_metrics, ssim_map, image_sums, gaussian_window  # the loss scenes are trained with,
+                                                    # (1 - lambda) L1 + lambda (1 - SSIM), and PSNR / SSIM: a fused HIP kernel pair
+    from gsbp_amd import polish_scene, score_image_views  # Adam on chosen tensors of a fixed set of Gaussians against images
 """
 from . import synthetic  # noqa: F401
 from ._lib import GwbpError, build, lib  # noqa: F401
@@ -70,4 +73,8 @@ from . import pixels  # noqa: F401
 from .pixels import PixelGaussians, dominance_counts, lookup, median_depth, pick_gaussians, pixel_gaussians, render_id_map  # noqa: F401
 from . import pose  # noqa: F401
 from .pose import pose_error, refine_pose, se3_exp  # noqa: F401
+from . import photometric  # noqa: F401
+from .photometric import gaussian_window, image_metrics, image_sums, photometric_loss, ssim_map  # noqa: F401
+from . import polish  # noqa: F401
+from .polish import polish_scene, score_image_views  # noqa: F401
 from .pruning import check_proper_pruning, gradient_mask, prune_by_gradients  # noqa: F401

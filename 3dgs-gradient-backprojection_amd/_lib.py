@@ -249,6 +249,10 @@ ARGTYPES = {
     "gwbp_decode_loss_workspace_size": [_I32, _I32, C.POINTER(C.c_size_t)],
     "gwbp_decode_loss": [_I32, _I32, _I32, _I32, _P, _I64, _P, _I64, _P, _I32, _I64, _I64, C.POINTER(PixelWeights), _I32, _F, _P,
                          _I64, _P, _I64, _P, _P, _SZ, _P],
+    # height, width, D, want_grad, bytes*  /  height, width, D, x, xs, y, ys, pixel weights, padding, ssim_lambda, map, grad, gs,
+    # table, workspace, bytes, stream
+    "gwbp_image_loss_workspace_size": [_I32, _I32, _I32, _I32, C.POINTER(C.c_size_t)],
+    "gwbp_image_loss": [_I32, _I32, _I32, _P, _I64, _P, _I64, C.POINTER(PixelWeights), _I32, _F, _P, _P, _I64, _P, _P, _SZ, _P],
 }
 # The typed forms of the entry points that read a finished [N, D] FIELD (or, gwbp_finalize_typed, write one): the untyped function's
 # arguments with the field's element type (GWBP_MAP_*, MAP_TYPES' codes) behind the field pointer.  A table of their own: they take no
@@ -277,6 +281,9 @@ FIELD_ARGTYPES = {
     "gwbp_field_compare_typed": _WSV + [_P, _I32, _I64, _I32, _P, _I32, _I64, _I64, _I32, _I32, _P, _P, _P, _P, _P],
 }
 LOSS_KINDS = {"l1": 0, "l2": 1}  # GWBP_LOSS_*
+SSIM_PADDINGS = {"valid": 0, "same": 1}  # GWBP_SSIM_*
+SSIM_TILE = (16, 64)  # GWBP_SSIM_TILE_Y, GWBP_SSIM_TILE_X
+IMAGE_LOSS_MAX_D = 32  # GWBP_IMAGE_LOSS_MAX_D
 # every symbol of include/gwbp.h: the two functions that return strings, then the int-returning ones declared above
 EXPORTS = ["gwbp_version", "gwbp_last_error_string", *ARGTYPES, *FIELD_ARGTYPES]
 

@@ -2020,6 +2020,62 @@ int gwbp_decode_loss(int32_t height, int32_t width, int32_t d, int32_t D, const 
                               GR, ldg, GC, ldgc, table, workspace, as_stream(stream));
 }
 
+// the shape contract of the photometric loss; `what` names the entry point
+static int check_image_loss_shape(const char *what, int32_t height, int32_t width, int32_t D, int32_t padding)
+{
+    if (D < 1 || D > GWBP_IMAGE_LOSS_MAX_D)
+        return set_error(GWBP_EINVAL, "%s: D must be in [1, %d] (got %d)", what, GWBP_IMAGE_LOSS_MAX_D, (int)D);
+    if (padding != GWBP_SSIM_VALID && padding != GWBP_SSIM_SAME)
+        return set_error(GWBP_EINVAL, "%s: unknown padding %d", what, (int)padding);
+    if (height < 1 || width < 1)
+        return set_error(GWBP_EINVAL, "%s: an image of %d x %d pixels (width x height)", what, (int)width, (int)height);
+    if (padding == GWBP_SSIM_VALID && (height < 11 || width < 11))
+        return set_error(GWBP_EINVAL, "%s: valid padding needs width and height >= 11, the window's size (got %d x %d)", what,
+                         (int)width, (int)height);
+    if ((int64_t)height * width > GWBP_IMAGE_LOSS_MAX_PIXELS)
+        return set_error(GWBP_EINVAL, "%s: %lld pixels exceed GWBP_IMAGE_LOSS_MAX_PIXELS = %d", what,
+                         (long long)((int64_t)height * width), GWBP_IMAGE_LOSS_MAX_PIXELS);
+    return GWBP_OK;
+}
+
+int gwbp_image_loss_workspace_size(int32_t height, int32_t width, int32_t D, int32_t want_grad, size_t *bytes)
+{
+    // (the size does not depend on the padding: the tiles cover the image under both)
+    const int rc = check_image_loss_shape("image_loss_workspace_size", height, width, D, GWBP_SSIM_SAME);
+    if (rc)
+        return rc;
+    if (!bytes)
+        return set_error(GWBP_EINVAL, "image_loss_workspace_size: null bytes");
+    *bytes = image_loss_workspace_bytes(height, width, D, want_grad != 0);
+    return GWBP_OK;
+}
+
+int gwbp_image_loss(int32_t height, int32_t width, int32_t D, const float *x, int64_t xs, const float *y, int64_t ys,
+                    const gwbp_pixel_weights *pixel_weights, int32_t padding, float ssim_lambda, float *map, float *grad, int64_t gs,
+                    double *table, void *workspace, size_t workspace_bytes, void *stream)
+{
+    PixW Pw;
+    const PixW *pw;
+    int rc = check_pixel_weights(pixel_weights, &Pw, &pw);
+    if (rc || (rc = check_image_loss_shape("image_loss", height, width, D, padding)))
+        return rc;
+    if (xs < D || ys < D || (grad && gs < D))
+        return set_error(GWBP_EINVAL, "image_loss: pixel strides (x %lld, y %lld, grad %lld) below D = %d", (long long)xs,
+                         (long long)ys, (long long)gs, (int)D);
+    if (!x || !y || !table || !workspace)
+        return set_error(GWBP_EINVAL, "image_loss: null x, y, table or workspace");
+    if ((reinterpret_cast<uintptr_t>(x) & 3) || (reinterpret_cast<uintptr_t>(y) & 3) || (reinterpret_cast<uintptr_t>(map) & 3) ||
+        (reinterpret_cast<uintptr_t>(grad) & 3))
+        return set_error(GWBP_EINVAL, "image_loss: x, y, map and grad must be 4-B aligned");
+    if ((reinterpret_cast<uintptr_t>(table) & 7) || (reinterpret_cast<uintptr_t>(workspace) & 7))
+        return set_error(GWBP_EINVAL, "image_loss: table and workspace must be 8-B aligned");
+    const size_t need = image_loss_workspace_bytes(height, width, D, grad != nullptr);
+    if (workspace_bytes < need)
+        return set_error(GWBP_EWORKSPACE, "image_loss: workspace has %zu bytes, needs %zu", workspace_bytes, need);
+    return launch_image_loss(height, width, D, x, xs, y, ys, pw, padding == GWBP_SSIM_SAME, ssim_lambda, map, grad, gs, table,
+                             workspace, as_stream(stream));
+}
+
 int gwbp_accumulate_stats(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, gwbp_stats *accum,
                           void *stream)
 {

@@ -320,6 +320,12 @@ size_t decode_loss_workspace_bytes(int d, int D);
 int launch_decode_loss(int H, int W, int d, int D, const float *R, int64_t ldr, const float *C, int64_t ldc, const void *map, int mt,
                        int64_t ms_y, int64_t ms_x, const PixW *pw, int l2, float scale, float *GR, int64_t ldg, float *GC,
                        int64_t ldgc, double *table, void *ws, hipStream_t s);
+// the photometric loss (1 - lambda) L1 + lambda (1 - SSIM) of x against y, float32 [H, W, D] with pixel strides xs / ys (ssim.hip):
+// forward, reduce and -- grad != nullptr -- backward; map [H', W', D] or nullptr; table [8] float64; ws: the caller's
+// image_loss_workspace_bytes(H, W, D, grad != nullptr) bytes
+size_t image_loss_workspace_bytes(int H, int W, int D, int want_grad);
+int launch_image_loss(int H, int W, int D, const float *x, int64_t xs, const float *y, int64_t ys, const PixW *pw, int same,
+                      float lambda, float *map, float *grad, int64_t gs, double *table, void *ws, hipStream_t s);
 int launch_encode_map(const float *feats, int64_t fs_y, int64_t fs_x, int H, int W, int K, const float *enc, int n_out,
                       float *out, int workgroups, hipStream_t s);
 // ot (GWBP_MAP_*): the element type of out; a half out is the fp32 result rounded once to nearest even

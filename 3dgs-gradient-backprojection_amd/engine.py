@@ -1034,6 +1034,61 @@ class Engine:
                    self._stream())
         return table[0], grad_rendered, grad_decoder, table
 
+    def image_loss(self, x, y, ssim_lambda: float = 0.2, padding: str = "valid", pixel_weights: Optional[torch.Tensor] = None,
+                   want_map: bool = False, want_grad: bool = False, grad_out: Optional[torch.Tensor] = None):
+        """The photometric loss (1 - ssim_lambda) L1 + ssim_lambda (1 - SSIM) of a render x against a target y in one call
+        (gwbp_image_loss: forward, reduce and -- want_grad -- backward, no host read in between).  Returns (table, map, grad):
+        table float64 [8] = sum w ssim, sum w |x - y|, sum w (x - y)^2, Wv, Wa, windows, H W, D; map float32 [H', W', D] or None;
+        grad = d loss / d x, float32 [H, W, D], or None.  x, y: float32 [H, W, D], 1 <= D <= 32, unit channel stride and flat pixel
+        rows (stride(1) >= D, stride(0) == W stride(1)), each with its own pixel stride: `out[..., :3]` of an RGB+D render goes in
+        without a copy; another layout is copied once.  padding "valid": the windows wholly inside the image (H, W >= 11),
+        "same": all H W windows, zeros outside.  pixel_weights: [H, W] as blend_weighted takes it.  grad_out: the tensor to fill.
+        Non-finite inputs are not masked: they propagate."""
+        if padding not in _lib.SSIM_PADDINGS:
+            raise GwbpError(f"padding must be 'valid' or 'same', got {padding!r}")
+        for t, name in ((x, "x"), (y, "y")):
+            if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or t.device.index != self._dev_index:
+                raise GwbpError(f"{name} must be a float32 HIP tensor on cuda:{self._dev_index} (there is no CPU path)")
+        if x.dim() != 3 or x.shape != y.shape:
+            raise GwbpError(f"x and y must be [H, W, D] of one shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+        H, W, D = (int(v) for v in x.shape)
+
+        def pixel_stride(t):  # (the stride of a dimension of size 1 means nothing)
+            return int(t.stride(1)) if W > 1 else int(t.stride(0)) if H > 1 else D
+
+        def flat_rows(t):
+            return ((D <= 1 or t.stride(2) == 1) and pixel_stride(t) >= D
+                    and (H <= 1 or W <= 1 or t.stride(0) == W * t.stride(1)))
+        off = 0 if padding == "same" else 5
+        with self._on_stream():
+            if not flat_rows(x):
+                x = x.contiguous()
+            if not flat_rows(y):
+                y = y.contiguous()
+            grad = None
+            if want_grad or grad_out is not None:
+                grad = grad_out if grad_out is not None else torch.empty(H, W, D, device=self.device)
+                if (not torch.is_tensor(grad) or grad.dtype != torch.float32 or not grad.is_cuda or tuple(grad.shape) != (H, W, D)
+                        or not flat_rows(grad)):
+                    raise GwbpError(f"grad_out must be a float32 HIP tensor [{H}, {W}, {D}] with flat pixel rows")
+            ssim = torch.empty(max(0, H - 2 * off), max(0, W - 2 * off), D, device=self.device) if want_map else None
+            table = torch.empty(8, dtype=torch.float64, device=self.device)
+        pw = None
+        if pixel_weights is not None:
+            class _Shape:
+                height, width = H, W
+            pw = byref(self.pixel_weights(pixel_weights, _Shape))
+        need = c_size_t(0)
+        self._call("gwbp_image_loss_workspace_size", H, W, D, int(grad is not None), byref(need))
+        ws = getattr(self, "_image_loss_ws", None)
+        if ws is None or ws.numel() < need.value:
+            with self._on_stream():
+                ws = self._image_loss_ws = torch.empty(int(need.value), dtype=torch.uint8, device=self.device)
+        self._call("gwbp_image_loss", H, W, D, ptr(x), c_int64(pixel_stride(x)), ptr(y), c_int64(pixel_stride(y)), pw,
+                   _lib.SSIM_PADDINGS[padding], c_float(float(ssim_lambda)), ptr(ssim), ptr(grad),
+                   c_int64(pixel_stride(grad) if grad is not None else D), ptr(table), ptr(ws), c_size_t(ws.numel()), self._stream())
+        return table, ssim, grad
+
     def render_pixels(self, view, colors, want_alphas=True):
         """Pixel-parallel forward render for 1..32 channels; needs project + bin_sort of `view` (not the weight store).  colors: float32,
         float16 or bfloat16 [N, D] at any row stride >= D, read as stored (a half table: the bits of colors.float(), no copy)."""

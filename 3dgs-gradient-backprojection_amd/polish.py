@@ -1,0 +1,100 @@
+"""Polish a scene against images: Adam on chosen pre-activation tensors of a FIXED set of Gaussians under the photometric loss the
+reference trainer uses (f3dgs/simple_trainer_feature_3dgs.py: (1 - 0.2) L1 + 0.2 (1 - SSIM)), and the trainer's evaluation without LPIPS.
+
+    splats, history = polish_scene(splats, viewmats, K, W, H, image_fn, params=("opacities", "sh0"), steps=300)
+    table = score_image_views(splats, viewmats, K, W, H, image_fn)      # per view: psnr, ssim, l1, mse
+
+The uses: re-fit the opacities after apply_mask3d took Gaussians away, touch a scene up before a lift.  N is fixed: no densification,
+no pruning, no opacity reset.  A step renders one view with rasterization() (whose backward is the HIP blend and projection backward)
+and compares it with photometric_loss (csrc/ssim.hip).  A splat dict carries the reference's key names (means, scaling, rotation,
+opacity, features_dc [N, 1, 3], features_rest [N, K - 1, 3]); the parameters go by the trainer's names.
+"""
+from __future__ import annotations
+
+import math
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
+
+import torch
+
+from ._lib import GwbpError
+from .photometric import image_metrics, photometric_loss
+from .rasterization import rasterization
+
+# the trainer's name of a parameter -> its key in a splat dict (pre-activation: scales are logs, opacities logits)
+PARAM_KEYS = {"means": "means", "scales": "scaling", "quats": "rotation", "opacities": "opacity", "sh0": "features_dc",
+              "shN": "features_rest"}
+# the reference trainer's learning rates (its means rate is further multiplied by the scene's scale there; here it is not)
+DEFAULT_LRS = {"means": 1.6e-4, "scales": 5e-3, "quats": 1e-3, "opacities": 5e-2, "sh0": 2.5e-3, "shN": 2.5e-3 / 20}
+
+
+def render_splats(splats: Dict[str, torch.Tensor], viewmat, K, width: int, height: int, **raster_kw) -> torch.Tensor:
+    """The [H, W, 3] image of a splat dict from one camera, as the trainer renders it: scales = exp, opacities = sigmoid, raw quats,
+    the SH colours of features_dc and features_rest at the degree their count gives.  Differentiable in every tensor of the dict."""
+    sh = torch.cat([splats["features_dc"], splats["features_rest"]], dim=1) if "features_rest" in splats else splats["features_dc"]
+    degree = int(round(math.sqrt(sh.shape[1]))) - 1
+    if (degree + 1) ** 2 != sh.shape[1]:
+        raise GwbpError(f"{sh.shape[1]} SH coefficients per Gaussian are no full degree")
+    out, _, _ = rasterization(splats["means"], splats["rotation"], torch.exp(splats["scaling"]), torch.sigmoid(splats["opacity"]),
+                              sh, viewmat[None], K[None], width, height, sh_degree=degree, want_meta=False, **raster_kw)
+    return out[0]
+
+
+def _view_K(K, v):
+    return K if K.dim() == 2 else K[v]
+
+
+def polish_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, image_fn: Callable[[int], torch.Tensor],
+                 params: Sequence[str] = ("opacities", "sh0"), steps: int = 300, ssim_lambda: float = 0.2,
+                 lrs: Optional[Dict[str, float]] = None, seed: int = 0, **raster_kw) -> Tuple[Dict[str, torch.Tensor], List[float]]:
+    """Adam on the named parameters of `splats` against the views' images.  Returns (a new splat dict -- the named tensors replaced by
+    their polished values, the others shared -- and the steps' losses, read from the device once behind the loop).
+    params: names out of means, scales, quats, opacities, sh0, shN; one Adam group each at lrs[name] (default: the reference
+    trainer's, DEFAULT_LRS; eps 1e-15 as there).  Each step takes one view, drawn from torch.Generator().manual_seed(seed) on the
+    host as a fresh permutation per pass over the views.  image_fn(v): the view's float32 [H, W, 3] image in [0, 1] on the device.
+    viewmats [V, 4, 4]; K [3, 3] or [V, 3, 3].  raster_kw: camera_model, rasterize_mode and the other keywords of rasterization()."""
+    unknown = [p for p in params if p not in PARAM_KEYS]
+    if unknown or not params:
+        raise GwbpError(f"params must be names out of {sorted(PARAM_KEYS)}, got {list(params)}")
+    if not splats["means"].is_cuda:
+        raise GwbpError("polish_scene() needs HIP tensors (there is no CPU path)")
+    rates = dict(DEFAULT_LRS, **(lrs or {}))
+    width, height = int(width), int(height)
+    work = {k: (t.detach() if torch.is_tensor(t) else t) for k, t in splats.items()}
+    if "features_dc" not in work:
+        raise GwbpError("the splat dict has no features_dc: polish_scene() renders SH colours")
+    groups = []
+    for name in params:
+        key = PARAM_KEYS[name]
+        if key not in work:
+            raise GwbpError(f"the splat dict has no {key!r} (parameter {name!r})")
+        work[key] = work[key].float().clone().requires_grad_(True)
+        groups.append(dict(params=[work[key]], lr=float(rates[name])))
+    opt = torch.optim.Adam(groups, eps=1e-15)
+    gen = torch.Generator().manual_seed(int(seed))
+    n_views = viewmats.shape[0]
+    losses, order = [], []
+    for _ in range(int(steps)):
+        if not order:
+            order = torch.randperm(n_views, generator=gen).tolist()
+        v = order.pop(0)
+        opt.zero_grad(set_to_none=True)
+        image = render_splats(work, viewmats[v], _view_K(K, v), width, height, **raster_kw)
+        loss = photometric_loss(image, image_fn(v), ssim_lambda=ssim_lambda)
+        loss.backward()
+        opt.step()
+        losses.append(loss.detach())
+    history = torch.stack(losses).cpu().tolist() if losses else []
+    return {k: (t.detach() if torch.is_tensor(t) else t) for k, t in work.items()}, history
+
+
+def score_image_views(splats: Dict[str, torch.Tensor], viewmats, K, width, height, image_fn: Callable[[int], torch.Tensor],
+                      **raster_kw) -> Dict:
+    """The reference's evaluation without LPIPS: every view rendered and compared with its image.  Returns {"views": [{"view": v,
+    "psnr", "ssim", "l1", "mse"}, ...], "mean": the same four averaged over the views}."""
+    rows = []
+    with torch.no_grad():
+        for v in range(viewmats.shape[0]):
+            image = render_splats(splats, viewmats[v], _view_K(K, v), int(width), int(height), **raster_kw)
+            rows.append(dict(view=v, **image_metrics(image.clamp(0.0, 1.0), image_fn(v))))
+    keys = ("psnr", "ssim", "l1", "mse")
+    return dict(views=rows, mean={k: sum(r[k] for r in rows) / len(rows) for k in keys} if rows else {})

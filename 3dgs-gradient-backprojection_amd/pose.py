@@ -56,15 +56,20 @@ def pose_error(vm_a: torch.Tensor, vm_b: torch.Tensor) -> Tuple[float, float]:
     return float(angle), float((ca - cb).norm())
 
 
-def pose_loss(out: torch.Tensor, target: torch.Tensor, weights: Optional[torch.Tensor], loss: str) -> torch.Tensor:
+def pose_loss(out: torch.Tensor, target: torch.Tensor, weights: Optional[torch.Tensor], loss: str,
+              ssim_lambda: float = 0.2) -> torch.Tensor:
     """The refiner's loss of a render [H, W, D] against its target: "l2": the (weighted) mean over pixels of the squared distance,
-    "cosine": of one minus the cosine of the two D-vectors."""
+    "cosine": of one minus the cosine of the two D-vectors, "photometric": photometric.photometric_loss, the trainer's
+    (1 - ssim_lambda) L1 + ssim_lambda (1 - SSIM) from the fused kernels (device tensors only)."""
+    if loss == "photometric":
+        from .photometric import photometric_loss
+        return photometric_loss(out, target, ssim_lambda=ssim_lambda, weights=weights)
     if loss == "l2":
         per = ((out - target) ** 2).sum(dim=-1)
     elif loss == "cosine":
         per = 1.0 - torch.nn.functional.cosine_similarity(out, target, dim=-1, eps=1e-8)
     else:
-        raise ValueError(f"loss must be l2 or cosine, got {loss!r}")
+        raise ValueError(f"loss must be l2, cosine or photometric, got {loss!r}")
     if weights is None:
         return per.mean()
     return (per * weights).sum() / weights.sum().clamp_min(1e-12)
@@ -89,11 +94,13 @@ def optimize_twist(value_of, viewmat0: torch.Tensor, steps: int, lr: float):
 
 
 def refine_pose(means, quats, scales, opacities, table, target, viewmat0, K, width, height, *, steps: int = 100, lr: float = 5e-3,
-                weights=None, loss: str = "l2", camera_model: str = "pinhole", rasterize_mode: str = "classic", eps2d: float = 0.3):
+                weights=None, loss: str = "l2", camera_model: str = "pinhole", rasterize_mode: str = "classic", eps2d: float = 0.3,
+                ssim_lambda: float = 0.2):
     """Refine a camera pose against `target` [H, W, D], the image or feature map seen from the unknown pose: Adam on the six numbers
     of a twist, viewmat = se3_exp(twist) @ viewmat0, one rasterization(camera_grad=True) of `table` [N, D] (float32, D <= 32) per step.
     weights [H, W] or None weighs the pixels.  Returns dict(viewmat [4, 4] float32, twist [6] float64, history: the loss of each step,
-    taken before that step's update).  The Gaussians and the table are detached."""
+    taken before that step's update).  The Gaussians and the table are detached.  loss: "l2", "cosine" or "photometric" (pose_loss;
+    ssim_lambda belongs to the last)."""
     if table.dim() != 2 or table.shape[1] > GEOMETRY_GRAD_MAX_DIM or table.dtype != torch.float32:
         raise ValueError(f"table must be float32 [N, D] with D <= {GEOMETRY_GRAD_MAX_DIM}, got {table.dtype} {tuple(table.shape)}")
     width, height = int(width), int(height)
@@ -111,7 +118,7 @@ def refine_pose(means, quats, scales, opacities, table, target, viewmat0, K, wid
     def value_of(vm):
         out, _, _ = rasterization(*gauss, vm.float()[None], Ks, width, height, eps2d=eps2d, camera_model=camera_model,
                                   rasterize_mode=rasterize_mode, want_meta=False, camera_grad=True)
-        return pose_loss(out[0], target, weights, loss)
+        return pose_loss(out[0], target, weights, loss, ssim_lambda)
 
     res = optimize_twist(value_of, vm0, steps, lr)
     res["viewmat"] = res["viewmat"].float()

@@ -1183,6 +1183,38 @@ GWBP_API int gwbp_decode_loss(int32_t height, int32_t width, int32_t d, int32_t 
                               const gwbp_pixel_weights *pixel_weights, int32_t loss_kind, float scale, float *GR, int64_t ldg,
                               float *GC, int64_t ldgc, double *table, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- the photometric loss of 3DGS training: (1 - lambda) L1 + lambda (1 - SSIM), its sums and its gradient, in one call -------------
+ * x is the render, y the target: float32 [height, width, D], 1 <= D <= GWBP_IMAGE_LOSS_MAX_D, unit channel stride, pixel (r, c) at
+ * x + (r * width + c) * xs (flat pixel rows; xs, ys >= D in elements, each tensor its own).  pixel_weights: an optional [height,
+ * width] map w (NULL: 1).  Everything is per channel.  SSIM is the 11-tap, sigma 1.5 Gaussian-window form with C1 = 0.01^2,
+ * C2 = 0.03^2 (data range 1); DESIGN.md 4 gives the arithmetic, csrc/ssim_math.h its expressions in their order.
+ * padding GWBP_SSIM_VALID: the windows wholly inside the image, centres 5 <= r < height - 5, 5 <= c < width - 5 (needs height, width
+ * >= 11); GWBP_SSIM_SAME: all height * width windows, zeros outside the image.
+ *     table = sum w(q) ssim(q), sum w(p) |x - y|, sum w(p) (x - y)^2, Wv = sum over windows w(q), Wa = sum over pixels w(p),
+ *             the number of windows, height * width, D                                       (double [8], overwritten)
+ *     loss  = (1 - lambda) table[1] / (D Wa) + lambda (1 - table[0] / (D Wv))               (the caller's; a zero weight sum: 0)
+ *     map   (NULL: not stored) float [H', W', D], the SSIM of every window and channel
+ *     grad  (NULL: no backward) float [height, width, D] at pixel stride gs >= D: d loss / d x.  y receives no gradient.
+ * Non-finite inputs are not masked: they propagate into the sums and the gradient.
+ * One forward launch over tiles of GWBP_SSIM_TILE_Y x GWBP_SSIM_TILE_X pixels, one reduce launch (the tiles' float64 partials in
+ * ascending tile order) and, with grad, one backward launch that reads Wv and Wa from the table on the device: no host read, no
+ * atomics, two calls give the same bits, and a blur's chain does not depend on the tiling.
+ * workspace: gwbp_image_loss_workspace_size(height, width, D, want_grad) = 40 * tiles + (want_grad ? 12 * height * width * D : 0)
+ * bytes, tiles = ceil(height / GWBP_SSIM_TILE_Y) * ceil(width / GWBP_SSIM_TILE_X); 8-B aligned; free when the kernels have run.
+ * GWBP_EINVAL: D outside [1, GWBP_IMAGE_LOSS_MAX_D], height or width < 1 (< 11 under GWBP_SSIM_VALID) or more than
+ * GWBP_IMAGE_LOSS_MAX_PIXELS pixels, an unknown padding, pixel strides below D, null or misaligned x, y, table or workspace (4 B;
+ * table and workspace 8 B), a misaligned map or grad.  GWBP_EWORKSPACE: a workspace below the size. */
+#define GWBP_SSIM_VALID 0
+#define GWBP_SSIM_SAME 1
+#define GWBP_SSIM_TILE_Y 16
+#define GWBP_SSIM_TILE_X 64
+#define GWBP_IMAGE_LOSS_MAX_D 32
+#define GWBP_IMAGE_LOSS_MAX_PIXELS (1 << 26)
+GWBP_API int gwbp_image_loss_workspace_size(int32_t height, int32_t width, int32_t D, int32_t want_grad, size_t *bytes);
+GWBP_API int gwbp_image_loss(int32_t height, int32_t width, int32_t D, const float *x, int64_t xs, const float *y, int64_t ys,
+                             const gwbp_pixel_weights *pixel_weights, int32_t padding, float ssim_lambda, float *map, float *grad,
+                             int64_t gs, double *table, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Adds this view's counters into `accum` (device, gwbp_stats) -- used by bench/driver to total pairs. */
 GWBP_API int gwbp_accumulate_stats(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, gwbp_stats *accum,
                           void *stream);

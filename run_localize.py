@@ -72,7 +72,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--perturb", type=parse_twist, default=None, metavar="W0,W1,W2,V0,V1,V2", help="a twist applied to the initial pose")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--lr", type=float, default=5e-3)
-    ap.add_argument("--loss", choices=["l2", "cosine"], default="l2")
+    ap.add_argument("--loss", choices=["l2", "cosine", "photometric"], default="l2",
+                    help="photometric: the trainer's (1 - lambda) L1 + lambda (1 - SSIM), from the fused kernels")
+    ap.add_argument("--ssim-lambda", type=float, default=0.2, help="lambda of --loss photometric")
     ap.add_argument("--out", required=True, help="the JSON file to write")
     return ap
 
@@ -108,7 +110,8 @@ def main(argv=None) -> int:
     if args.perturb is not None:
         vm0 = gsbp_amd.se3_exp(torch.tensor(args.perturb, dtype=torch.float64)) @ vm0
     res = gsbp_amd.refine_pose(*scene.gauss, table, target, vm0, scene.K, scene.width, scene.height, steps=args.steps, lr=args.lr,
-                               weights=weights, loss=args.loss, camera_model=args.camera_model, rasterize_mode=args.rasterize_mode)
+                               weights=weights, loss=args.loss, camera_model=args.camera_model, rasterize_mode=args.rasterize_mode,
+                               ssim_lambda=args.ssim_lambda)
     angle, dist = gsbp_amd.pose_error(res["viewmat"], vm0)
     report = {"viewmat": res["viewmat"].double().cpu().tolist(), "twist": res["twist"].cpu().tolist(), "history": res["history"],
               "initial_viewmat": vm0.tolist(), "moved": {"angle_rad": angle, "distance": dist}, "loss": args.loss, "steps": args.steps,
