@@ -40,6 +40,9 @@ JojiJoseph/3dgs-gradient-backprojection), hand-written HIP kernels behind a C AB
     from gsbp_amd import photometric_loss, image_metrics, ssim_map, image_sums, gaussian_window  # the loss scenes are trained with,
                                                     # (1 - lambda) L1 + lambda (1 - SSIM), and PSNR / SSIM: a fused HIP kernel pair
     from gsbp_amd import polish_scene, score_image_views  # Adam on chosen tensors of a fixed set of Gaussians against images
+    from gsbp_amd import train_scene, densify, DensifyState, DensifyConfig, reset_opacity, init_splats_from_points  # and of a set
+                                                    # that grows and shrinks: rasterization(means2d_grad=True), gsplat's default
+                                                    # densification rule as HIP plan / emit / gather kernels
 """
 from . import synthetic  # noqa: F401
 from ._lib import GwbpError, build, lib  # noqa: F401
@@ -77,4 +80,6 @@ from . import photometric  # noqa: F401
 from .photometric import gaussian_window, image_metrics, image_sums, photometric_loss, ssim_map  # noqa: F401
 from . import polish  # noqa: F401
 from .polish import polish_scene, score_image_views  # noqa: F401
+# (gsbp_amd.densify is the function, as gsbp_amd.rasterization is; the module is reached as `from gsbp_amd.densify import ...`)
+from .densify import DensifyConfig, DensifyState, densify, init_splats_from_points, reset_opacity, train_scene  # noqa: F401
 from .pruning import check_proper_pruning, gradient_mask, prune_by_gradients  # noqa: F401

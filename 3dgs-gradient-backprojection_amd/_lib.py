@@ -253,6 +253,15 @@ ARGTYPES = {
     # table, workspace, bytes, stream
     "gwbp_image_loss_workspace_size": [_I32, _I32, _I32, _I32, C.POINTER(C.c_size_t)],
     "gwbp_image_loss": [_I32, _I32, _I32, _P, _I64, _P, _I64, C.POINTER(PixelWeights), _I32, _F, _P, _P, _I64, _P, _P, _SZ, _P],
+    # densification: n, n_cameras, v_means2d, radii, sx, sy, grad2d, count, stream  /  n, bytes*  /  n, grad2d, count, scaling, lds,
+    # opacity, t_grad, t_small, t_big, t_opa, log16, prune_big, kind, offsets, workspace, bytes, stream  /  n, n_out, kind, offsets,
+    # means, scaling, rotation, opacity, noise, log16, parent, child, out_means, out_scaling, out_rotation, out_opacity, stream  /
+    # n, n_out, w, table, ldt, parent, child, kind, mode, out, ldo, stream
+    "gwbp_densify_accumulate": [_I64, _I32, _P, _P, _F, _F, _P, _P, _P],
+    "gwbp_densify_plan_workspace_size": [_I64, C.POINTER(C.c_size_t)],
+    "gwbp_densify_plan": [_I64, _P, _P, _P, _I64, _P, _F, _F, _F, _F, _F, _I32, _P, _P, _P, _SZ, _P],
+    "gwbp_densify_emit": [_I64, _I64, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P],
+    "gwbp_densify_gather": [_I64, _I64, _I32, _P, _I64, _P, _P, _P, _I32, _P, _I64, _P],
 }
 # The typed forms of the entry points that read a finished [N, D] FIELD (or, gwbp_finalize_typed, write one): the untyped function's
 # arguments with the field's element type (GWBP_MAP_*, MAP_TYPES' codes) behind the field pointer.  A table of their own: they take no
@@ -284,6 +293,10 @@ LOSS_KINDS = {"l1": 0, "l2": 1}  # GWBP_LOSS_*
 SSIM_PADDINGS = {"valid": 0, "same": 1}  # GWBP_SSIM_*
 SSIM_TILE = (16, 64)  # GWBP_SSIM_TILE_Y, GWBP_SSIM_TILE_X
 IMAGE_LOSS_MAX_D = 32  # GWBP_IMAGE_LOSS_MAX_D
+DENSIFY_KINDS = {"pruned": 0, "keep": 1, "clone": 2, "split": 3}  # GWBP_DENSIFY_KIND_*
+DENSIFY_MODES = {"copy": 0, "zero_new": 1}  # GWBP_DENSIFY_COPY / _ZERO_NEW
+DENSIFY_BLOCK = 256  # GWBP_DENSIFY_BLOCK: the Gaussians of one workgroup of the plan's scan
+DENSIFY_MAX_WIDTH = 65536  # GWBP_DENSIFY_MAX_WIDTH
 # every symbol of include/gwbp.h: the two functions that return strings, then the int-returning ones declared above
 EXPORTS = ["gwbp_version", "gwbp_last_error_string", *ARGTYPES, *FIELD_ARGTYPES]
 

@@ -2076,6 +2076,117 @@ int gwbp_image_loss(int32_t height, int32_t width, int32_t D, const float *x, in
                              workspace, as_stream(stream));
 }
 
+// ---- densification (densify.hip) ---------------------------------------------------------------------------------------------------
+static int check_densify_count(const char *what, int64_t n)
+{
+    if (n < 0 || n > 0x7FFFFFFF)
+        return set_error(GWBP_EINVAL, "%s: bad number of Gaussians (%lld): 0 .. 2^31 - 1", what, (long long)n);
+    return GWBP_OK;
+}
+
+// n_out rows out of n parents: each leaves at most two
+static int check_densify_out(const char *what, int64_t n, int64_t n_out)
+{
+    if (int rc = check_densify_count(what, n))
+        return rc;
+    if (n_out < 0 || n_out > 2 * n)
+        return set_error(GWBP_EINVAL, "%s: n_out = %lld disagrees with offsets of %lld parents (0 .. %lld rows)", what, (long long)n_out,
+                         (long long)n, (long long)(2 * n));
+    return GWBP_OK;
+}
+
+int gwbp_densify_accumulate(int64_t n, int32_t n_cameras, const float *v_means2d, const int32_t *radii, float sx, float sy, float *grad2d,
+                            float *count, void *stream)
+{
+    if (int rc = check_densify_count("densify_accumulate", n))
+        return rc;
+    if (n_cameras < 1)
+        return set_error(GWBP_EINVAL, "densify_accumulate: n_cameras must be at least 1 (got %d)", (int)n_cameras);
+    if (n > 0 && (!v_means2d || !radii || !grad2d || !count))
+        return set_error(GWBP_EINVAL, "densify_accumulate: null v_means2d, radii, grad2d or count");
+    if (misaligned(v_means2d, 7) || misaligned(radii, 3) || misaligned(grad2d, 3) || misaligned(count, 3))
+        return set_error(GWBP_EINVAL, "densify_accumulate: v_means2d must be 8-B aligned, radii, grad2d and count 4-B");
+    if (grad2d && grad2d == count)
+        return set_error(GWBP_EINVAL, "densify_accumulate: grad2d and count are the same array");
+    return launch_densify_accumulate(n, n_cameras, v_means2d, radii, sx, sy, grad2d, count, as_stream(stream));
+}
+
+int gwbp_densify_plan_workspace_size(int64_t n, size_t *bytes)
+{
+    if (int rc = check_densify_count("densify_plan_workspace_size", n))
+        return rc;
+    if (!bytes)
+        return set_error(GWBP_EINVAL, "densify_plan_workspace_size: null bytes");
+    *bytes = densify_plan_workspace_bytes(n);
+    return GWBP_OK;
+}
+
+int gwbp_densify_plan(int64_t n, const float *grad2d, const float *count, const float *scaling, int64_t lds_, const float *opacity,
+                      float t_grad, float t_small, float t_big, float t_opa, float log16, int32_t prune_big, uint8_t *kind,
+                      int64_t *offsets, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (int rc = check_densify_count("densify_plan", n))
+        return rc;
+    if (lds_ < 3)
+        return set_error(GWBP_EINVAL, "densify_plan: row stride %lld of scaling below 3", (long long)lds_);
+    if (!offsets || !workspace || (n > 0 && (!grad2d || !count || !scaling || !opacity || !kind)))
+        return set_error(GWBP_EINVAL, "densify_plan: null grad2d, count, scaling, opacity, kind, offsets or workspace");
+    if (misaligned(grad2d, 3) || misaligned(count, 3) || misaligned(scaling, 3) || misaligned(opacity, 3))
+        return set_error(GWBP_EINVAL, "densify_plan: grad2d, count, scaling and opacity must be 4-B aligned");
+    if (misaligned(offsets, 7) || misaligned(workspace, 7))
+        return set_error(GWBP_EINVAL, "densify_plan: offsets and workspace must be 8-B aligned");
+    const size_t need = densify_plan_workspace_bytes(n);
+    if (workspace_bytes < need)
+        return set_error(GWBP_EWORKSPACE, "densify_plan: workspace has %zu bytes, needs %zu", workspace_bytes, need);
+    const float thresholds[5] = {t_grad, t_small, t_big, t_opa, log16};
+    return launch_densify_plan(n, grad2d, count, scaling, lds_, opacity, thresholds, prune_big != 0, kind, offsets, workspace,
+                               as_stream(stream));
+}
+
+int gwbp_densify_emit(int64_t n, int64_t n_out, const uint8_t *kind, const int64_t *offsets, const float *means, const float *scaling,
+                      const float *rotation, const float *opacity, const float *noise, float log16, int32_t *parent, uint8_t *child,
+                      float *out_means, float *out_scaling, float *out_rotation, float *out_opacity, void *stream)
+{
+    if (int rc = check_densify_out("densify_emit", n, n_out))
+        return rc;
+    if (n > 0 && (!kind || !offsets || !means || !scaling || !rotation || !opacity || !noise))
+        return set_error(GWBP_EINVAL, "densify_emit: null kind, offsets, means, scaling, rotation, opacity or noise");
+    if (n_out > 0 && (!parent || !child || !out_means || !out_scaling || !out_rotation || !out_opacity))
+        return set_error(GWBP_EINVAL, "densify_emit: null parent, child or output table");
+    if (misaligned(offsets, 7))
+        return set_error(GWBP_EINVAL, "densify_emit: offsets must be 8-B aligned");
+    if (misaligned(means, 3) || misaligned(scaling, 3) || misaligned(rotation, 3) || misaligned(opacity, 3) || misaligned(noise, 3) ||
+        misaligned(parent, 3) || misaligned(out_means, 3) || misaligned(out_scaling, 3) || misaligned(out_rotation, 3) ||
+        misaligned(out_opacity, 3))
+        return set_error(GWBP_EINVAL, "densify_emit: the float tables and parent must be 4-B aligned");
+    const void *const written[] = {out_means, out_scaling, out_rotation, out_opacity}, *const read[] = {means, scaling, rotation, opacity, noise};
+    if (n_out > 0)
+        if (int rc = check_regions_distinct("densify_emit", written, 4, read, 5))
+            return rc;
+    return launch_densify_emit(n, n_out, kind, offsets, means, scaling, rotation, opacity, noise, log16, parent, child, out_means,
+                               out_scaling, out_rotation, out_opacity, as_stream(stream));
+}
+
+int gwbp_densify_gather(int64_t n, int64_t n_out, int32_t w, const float *table, int64_t ldt, const int32_t *parent, const uint8_t *child,
+                        const uint8_t *kind, int32_t mode, float *out, int64_t ldo, void *stream)
+{
+    if (int rc = check_densify_out("densify_gather", n, n_out))
+        return rc;
+    if (w < 1 || w > GWBP_DENSIFY_MAX_WIDTH)
+        return set_error(GWBP_EINVAL, "densify_gather: w must be in [1, %d] (got %d)", GWBP_DENSIFY_MAX_WIDTH, (int)w);
+    if (ldt < w || ldo < w)
+        return set_error(GWBP_EINVAL, "densify_gather: row strides (%lld, %lld) below w = %d", (long long)ldt, (long long)ldo, (int)w);
+    if (mode != GWBP_DENSIFY_COPY && mode != GWBP_DENSIFY_ZERO_NEW)
+        return set_error(GWBP_EINVAL, "densify_gather: unknown mode %d", (int)mode);
+    if (n_out > 0 && (!table || !parent || !out || (mode == GWBP_DENSIFY_ZERO_NEW && (!child || !kind))))
+        return set_error(GWBP_EINVAL, "densify_gather: null table, parent or out (child or kind under GWBP_DENSIFY_ZERO_NEW)");
+    if (misaligned(table, 3) || misaligned(parent, 3) || misaligned(out, 3))
+        return set_error(GWBP_EINVAL, "densify_gather: table, parent and out must be 4-B aligned");
+    if (out && out == table)
+        return set_error(GWBP_EINVAL, "densify_gather: out must not be the table");
+    return launch_densify_gather(n, n_out, w, table, ldt, parent, child, kind, mode == GWBP_DENSIFY_ZERO_NEW, out, ldo, as_stream(stream));
+}
+
 int gwbp_accumulate_stats(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, gwbp_stats *accum,
                           void *stream)
 {

@@ -326,6 +326,19 @@ int launch_decode_loss(int H, int W, int d, int D, const float *R, int64_t ldr, 
 size_t image_loss_workspace_bytes(int H, int W, int D, int want_grad);
 int launch_image_loss(int H, int W, int D, const float *x, int64_t xs, const float *y, int64_t ys, const PixW *pw, int same,
                       float lambda, float *map, float *grad, int64_t gs, double *table, void *ws, hipStream_t s);
+// densification (densify.hip): the per-step statistics, the plan (kind + the exclusive scan of the rows out; ws: the caller's
+// densify_plan_workspace_bytes(N) bytes; thresholds: t_grad, t_small, t_big, t_opa, log16 on the host), the children, and the relocation
+// of a [N, w] table.  child / kind may be nullptr without zero_new
+size_t densify_plan_workspace_bytes(int64_t n);
+int launch_densify_accumulate(int64_t N, int C, const float *v, const int32_t *radii, float sx, float sy, float *grad2d, float *count,
+                              hipStream_t s);
+int launch_densify_plan(int64_t N, const float *grad2d, const float *count, const float *scaling, int64_t lds_, const float *opacity,
+                        const float *thresholds, int prune_big, uint8_t *kind, int64_t *offsets, void *ws, hipStream_t s);
+int launch_densify_emit(int64_t N, int64_t n_out, const uint8_t *kind, const int64_t *offsets, const float *means, const float *scaling,
+                        const float *rotation, const float *opacity, const float *noise, float log16, int32_t *parent, uint8_t *child,
+                        float *o_means, float *o_scaling, float *o_rotation, float *o_opacity, hipStream_t s);
+int launch_densify_gather(int64_t N, int64_t n_out, int w, const float *table, int64_t ldt, const int32_t *parent, const uint8_t *child,
+                          const uint8_t *kind, int zero_new, float *out, int64_t ldo, hipStream_t s);
 int launch_encode_map(const float *feats, int64_t fs_y, int64_t fs_x, int H, int W, int K, const float *enc, int n_out,
                       float *out, int workgroups, hipStream_t s);
 // ot (GWBP_MAP_*): the element type of out; a half out is the fp32 result rounded once to nearest even

@@ -27,16 +27,17 @@ PARAM_KEYS = {"means": "means", "scales": "scaling", "quats": "rotation", "opaci
 DEFAULT_LRS = {"means": 1.6e-4, "scales": 5e-3, "quats": 1e-3, "opacities": 5e-2, "sh0": 2.5e-3, "shN": 2.5e-3 / 20}
 
 
-def render_splats(splats: Dict[str, torch.Tensor], viewmat, K, width: int, height: int, **raster_kw) -> torch.Tensor:
+def render_splats(splats: Dict[str, torch.Tensor], viewmat, K, width: int, height: int, return_meta: bool = False, **raster_kw):
     """The [H, W, 3] image of a splat dict from one camera, as the trainer renders it: scales = exp, opacities = sigmoid, raw quats,
-    the SH colours of features_dc and features_rest at the degree their count gives.  Differentiable in every tensor of the dict."""
+    the SH colours of features_dc and features_rest at the degree their count gives.  Differentiable in every tensor of the dict.
+    return_meta: (image, meta) -- the eager part of rasterization()'s meta, which under means2d_grad=True holds the means2d leaf."""
     sh = torch.cat([splats["features_dc"], splats["features_rest"]], dim=1) if "features_rest" in splats else splats["features_dc"]
     degree = int(round(math.sqrt(sh.shape[1]))) - 1
     if (degree + 1) ** 2 != sh.shape[1]:
         raise GwbpError(f"{sh.shape[1]} SH coefficients per Gaussian are no full degree")
-    out, _, _ = rasterization(splats["means"], splats["rotation"], torch.exp(splats["scaling"]), torch.sigmoid(splats["opacity"]),
-                              sh, viewmat[None], K[None], width, height, sh_degree=degree, want_meta=False, **raster_kw)
-    return out[0]
+    out, _, meta = rasterization(splats["means"], splats["rotation"], torch.exp(splats["scaling"]), torch.sigmoid(splats["opacity"]),
+                                 sh, viewmat[None], K[None], width, height, sh_degree=degree, want_meta=False, **raster_kw)
+    return (out[0], meta) if return_meta else out[0]
 
 
 def _view_K(K, v):

@@ -10,7 +10,8 @@ Backward = scatter with v_render_colors as the feature map: colors.grad[g,:] += 
            When means / quats / scales / opacities do (and the table has at most 32 float32 channels) it is instead
            gwbp_render_pixels_backward, the HIP backward of the per-pixel blend, followed by gwbp_project_backward, the HIP
            backward of the projection (_geometry_backward); with camera_grad=True the same kernel also sums the gradient
-           w.r.t. viewmats.  Gradients w.r.t. Ks, absgrad and meta["means2d"].grad (densification) are not offered; asking
+           w.r.t. viewmats; with means2d_grad=True each view's blend backward also leaves its d loss / d (2-D mean) in
+           meta["means2d"].grad, which densification reads (densify.py).  Gradients w.r.t. Ks and absgrad are not offered; asking
            for them raises, and so does a default call whose viewmats require grad.
 """
 from __future__ import annotations
@@ -137,6 +138,14 @@ def get_engine(device, n: int, width: int, height: int) -> Engine:
     return eng
 
 
+def release_engines(device, keep_n: Optional[int] = None) -> None:
+    """Drop this device's cached workspaces, all of them or those sized for another number of Gaussians than keep_n.  A training run
+    whose N changes every round (densify.train_scene) calls it after a round: the cache would otherwise hold the workspace of the set
+    that no longer exists beside the new one until a third size arrives."""
+    for k in [k for k in _ENGINES if k[0] == str(device) and (keep_n is None or k[1] != keep_n)]:
+        del _ENGINES[k]
+
+
 def engine_on(device) -> Engine:
     """An engine of this device for a call that needs no view workspace: one rasterization() already made if there is one."""
     for key, eng in _ENGINES.items():
@@ -188,8 +197,8 @@ def run_front(eng: Engine, view, means, quats, scales, opacities, want_alphas, w
 
 def _geometry_path(needs, colors: torch.Tensor) -> bool:
     """Does this call's backward go through the blend backward kernel?  Some of means / quats / scales / opacities -- or, under
-    camera_grad=True, the view matrix -- needs a gradient (`needs`) and the table is one the kernel reads: float32, at most
-    GEOMETRY_GRAD_MAX_DIM channels."""
+    camera_grad=True, the view matrix, or, under means2d_grad=True, the projected means -- needs a gradient (`needs`) and the table is
+    one the kernel reads: float32, at most GEOMETRY_GRAD_MAX_DIM channels."""
     return bool(any(needs)) and colors.shape[1] <= GEOMETRY_GRAD_MAX_DIM and colors.dtype == torch.float32
 
 
@@ -211,15 +220,38 @@ def _geometry_backward(ctx, g_out, g_alpha):
         g_out = torch.zeros(view.height, view.width, ctx.shape[1], device=means.device)
     v_colors, v_g2d = eng.render_pixels_backward(view, colors.detach(), g_out.detach(),
                                                  g_alpha.detach() if g_alpha is not None else None, want_colors=needs[0])
+    if ctx.means2d is not None:
+        _add_means2d_grad(*ctx.means2d, v_g2d)
+    want_viewmat = bool(ctx.camera_grad and needs[5])
+    if not (any(needs[1:5]) or want_viewmat):  # (a call that only asked for means2d.grad beside its colours)
+        return (v_colors,) + (None,) * 13
     grads = eng.project_backward(view, means.detach(), quats.detach(), scales.detach(), opacities.detach(), v_g2d, needs=needs[1:5],
-                                 want_viewmat=bool(ctx.camera_grad and needs[5]))
+                                 want_viewmat=want_viewmat)
     v_vm = None if grads[4] is None else grads[4].to(ctx.vm_dtype)
-    return (v_colors,) + tuple(grads[:4]) + (v_vm,) + (None,) * 7
+    return (v_colors,) + tuple(grads[:4]) + (v_vm,) + (None,) * 8
+
+
+def _add_means2d_grad(slot: dict, c: int, v_g2d: torch.Tensor) -> None:
+    """Camera c's d loss / d (2-D mean), columns 0 and 1 of the blend backward's v_g2d (zeros on the rows the projection culled), added
+    into row c of the .grad of the call's meta["means2d"] leaf -- the side effect on a leaf's .grad that _Rasterize.backward uses for a
+    colour table.  The leaf is reached through `slot`, which rasterization() fills behind the forwards; a call whose meta nobody kept
+    still has it."""
+    leaf = slot.get("leaf")
+    if leaf is None:
+        return
+    with torch.no_grad():
+        if leaf.grad is None:
+            if leaf.shape[0] == 1:  # one camera: the gradient is the copy itself, no zero fill in front of an add
+                leaf.grad = v_g2d[:, :2].contiguous()[None]
+                return
+            leaf.grad = torch.zeros_like(leaf)
+        leaf.grad[c].add_(v_g2d[:, :2])
 
 
 class _Rasterize(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, colors, means, quats, scales, opacities, viewmat, K, width, height, kw, holder, harvest=None, camera_grad=False):
+    def forward(ctx, colors, means, quats, scales, opacities, viewmat, K, width, height, kw, holder, harvest=None, camera_grad=False,
+                means2d=None):
         dev = means.device
         eng = get_engine(dev, means.shape[0], width, height)
         view = eng.view(viewmat, K, width, height, **kw)
@@ -228,7 +260,8 @@ class _Rasterize(torch.autograd.Function):
         # kernel needs the sorted lists only, hands the colour gradient back as well, and reads which rows the projection kept
         # (camera_grad=True: the view matrix as well, through the same two kernels)
         camera_grad = bool(camera_grad and ctx.needs_input_grad[5])
-        geo = _geometry_path(tuple(ctx.needs_input_grad[1:5]) + (camera_grad,), colors)
+        # means2d: None, or (slot, camera index) of a means2d_grad=True call: the blend backward runs whoever else needs it
+        geo = _geometry_path(tuple(ctx.needs_input_grad[1:5]) + (camera_grad, means2d is not None), colors)
         # the weight store is only needed for the colour backward / the wide render
         need_store = (colors.requires_grad and not geo) or D > PIXEL_RENDER_MAX_DIM
         # a backward with D % 256 == 0 channels goes through the 256-channel scatter kernel, which needs the blend's
@@ -258,6 +291,7 @@ class _Rasterize(torch.autograd.Function):
         ctx.leaf = weakref.ref(colors) if (colors.requires_grad and colors.is_leaf) else None
         ctx.leaf_node = _accumulate_node(colors) if ctx.leaf is not None else None
         ctx.geo, ctx.camera_grad, ctx.vm_dtype = geo, camera_grad, viewmat.dtype
+        ctx.means2d = means2d if geo else None
         if not geo:  # (under geo the alpha map depends on the geometry, the opacities and the camera: it carries a gradient)
             ctx.mark_non_differentiable(alphas)
         return out, alphas
@@ -293,10 +327,10 @@ class _Rasterize(torch.autograd.Function):
                 and _grad_is_unobserved(leaf, ctx.leaf_node)):
             _scatter_grad(eng, view, g_out, acc)
             acc[:0].add_(0)  # the kernel wrote through data_ptr: move .grad's version counter like an in-place op would
-            return (None,) * 13
+            return (None,) * 14
         v_colors = torch.zeros(ctx.shape, device=means.device, dtype=torch.float32)
         _scatter_grad(eng, view, g_out, v_colors)
-        return (v_colors,) + (None,) * 12
+        return (v_colors,) + (None,) * 13
 
 
 def _scatter_grad(eng: Engine, view, g_out: torch.Tensor, acc: torch.Tensor) -> None:
@@ -466,6 +500,7 @@ class LazyMeta(dict):
     def __init__(self, eager, holders, n_cameras, antialiased=False):
         super().__init__(eager)
         self._h, self._c = holders, n_cameras
+        self._pinned = tuple(k for k in ("radii", "means2d") if k in eager)  # unpacked by a means2d_grad=True call: kept as given
         self._aa = antialiased
         if antialiased:  # gsplat: meta["opacities"] are the compensated opacities the blend used, meta["compensations"] beside
             self._LAZY = self._LAZY + ("compensations",)
@@ -493,15 +528,17 @@ class LazyMeta(dict):
             offs.append(b["tile_offsets"][:-1] + sum(x.numel() for x in flat[:-1]))
             base += vis.numel()
         self["camera_ids"], self["gaussian_ids"] = torch.cat(cams), torch.cat(gids)
+        packed = {k: torch.cat(parts[k]) for k in parts}
         for k in parts:
-            self[k] = torch.cat(parts[k])
+            if k not in self._pinned:
+                self[k] = packed[k]
         self["opacities"] = self._opac[self["gaussian_ids"]]
         if self._aa:
             self["opacities"] = self["opacities"] * self["compensations"]
         self["isect_ids"], self["flatten_ids"] = torch.cat(isect), torch.cat(flat)
         self["isect_offsets"] = torch.stack(offs).reshape(self._c, self["tile_height"], self["tile_width"])
-        r = self["radii"].to(torch.float32) / TILE
-        m = self["means2d"] / TILE
+        r = packed["radii"].to(torch.float32) / TILE
+        m = packed["means2d"] / TILE
         tw, th = self["tile_width"], self["tile_height"]
         x0 = torch.clamp(torch.floor(m[:, 0] - r), 0, tw)
         x1 = torch.clamp(torch.ceil(m[:, 0] + r), 0, tw)
@@ -523,7 +560,8 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
                   sh_degree: Optional[int] = None, packed: bool = True, tile_size: int = 16, backgrounds=None,
                   render_mode: str = "RGB", sparse_grad: bool = False, absgrad: bool = False,
                   rasterize_mode: str = "classic", channel_chunk: int = 32, distributed: bool = False,
-                  camera_model: str = "pinhole", covars=None, want_meta: bool = True, camera_grad: bool = False):
+                  camera_model: str = "pinhole", covars=None, want_meta: bool = True, camera_grad: bool = False,
+                  means2d_grad: bool = False):
     """Same call signature / defaults / returns as gsplat.rasterization (1.4.0).
 
     Returns (render_colors [C,H,W,D'], render_alphas [C,H,W,1], meta).  `channel_chunk`, `packed`, `sparse_grad`
@@ -542,8 +580,17 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     Gaussian tensor requires grad: viewmats.grad is float32 [C, 4, 4] with a zero bottom row; the depth column of the "D" render modes
     is a torch function of viewmats[c] and adds its own share.  Without the keyword a call whose viewmats require grad raises in
     backward, as it always did.  With it, Ks.requires_grad, sh_degree (the SH view direction uses a detached camera centre) and a wider
-    or half table raise at the call.  Not w.r.t. Ks; meta["means2d"] carries no gradient, so densification by means2d.grad is not
-    offered yet.
+    or half table raise at the call.  Not w.r.t. Ks.
+    means2d_grad=True (an addition to gsplat's signature; it does nothing under torch.no_grad()) is the hook of gsplat's densification
+    strategies.  meta["means2d"] is then a float32 [C, N, 2] leaf that requires grad -- the projected means in pixels; .retain_grad() on
+    it is accepted -- and meta["radii"] the int32 [C, N] radii beside it (both unpacked, as gsplat's packed=False lays them out; a row
+    whose radius is 0 was culled and its means2d entry holds nothing defined; the other keys of meta stay packed).  Every backward pass
+    through the call ADDS d loss / d means2d into meta["means2d"].grad: row [c] is columns 0 and 1 of camera c's blend backward, in
+    pixels and unnormalised as in gsplat, exact zeros on culled rows.  It is a side effect on the leaf's .grad, not an edge of the
+    graph: torch.autograd.grad() does not return it.  The call takes the blend backward kernel whether or not a Gaussian tensor requires
+    grad, so the table must be float32 with at most 32 channels (NotImplementedError at the call otherwise); the kernel computes the
+    columns anyway, so nothing is launched for them but the copy into .grad.  Still not offered: absgrad (a second, absolute sum
+    inside the blend backward), packed mode's sparse gradients.
     """
     if tile_size != TILE:
         raise GwbpError(f"tile_size must be {TILE}: the tile rectangle is part of the numerics")
@@ -553,6 +600,12 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
                                   "single-process calls without covars / absgrad are implemented")
     if render_mode not in ("RGB", "D", "ED", "RGB+D", "RGB+ED"):
         raise ValueError(render_mode)
+    m2d = {} if (means2d_grad and torch.is_grad_enabled()) else None
+    if m2d is not None and sh_degree is None:
+        d_table = (0 if render_mode in ("D", "ED") else colors.shape[-1]) + (1 if "D" in render_mode else 0)
+        if d_table > GEOMETRY_GRAD_MAX_DIM or colors.dtype != torch.float32:
+            raise NotImplementedError(f"means2d_grad=True needs a float32 table of at most {GEOMETRY_GRAD_MAX_DIM} channels (the depth "
+                                      f"column included), got {colors.dtype} with {d_table}")
     if not means.is_cuda:
         raise GwbpError("rasterization() needs HIP tensors (the reference likewise requires CUDA, backproject.py:314)")
     if sh_degree is None and colors.dtype in HALF_TYPES and colors.requires_grad:
@@ -588,7 +641,7 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
                 cols = get_engine(means.device, N, width, height).sh_colors(sh_degree, means, sh, campos)
         else:
             cols = colors if colors.dim() == 2 else colors[c]
-        holder = {} if (want_meta or "D" in render_mode) else None
+        holder = {} if (want_meta or "D" in render_mode or m2d is not None) else None
         need_depth = render_mode in ("D", "ED", "RGB+D", "RGB+ED")
         if need_depth:
             z = (means @ vm[:3, :3].T + vm[:3, 3])[:, 2:3]
@@ -598,9 +651,14 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
         if camera and (cols.shape[1] > GEOMETRY_GRAD_MAX_DIM or cols.dtype != torch.float32):
             raise NotImplementedError(f"camera_grad=True needs a float32 table of at most {GEOMETRY_GRAD_MAX_DIM} channels (the depth "
                                       f"column included), got {cols.dtype} with {cols.shape[1]}")
-        geo = torch.is_grad_enabled() and _geometry_path([t.requires_grad for t in (means, quats, scales, opacities)] + [camera], cols)
+        if m2d is not None and (cols.shape[1] > GEOMETRY_GRAD_MAX_DIM or cols.dtype != torch.float32):
+            raise NotImplementedError(f"means2d_grad=True needs a float32 table of at most {GEOMETRY_GRAD_MAX_DIM} channels, got "
+                                      f"{cols.dtype} with {cols.shape[1]}")
+        geo = torch.is_grad_enabled() and _geometry_path([t.requires_grad for t in (means, quats, scales, opacities)]
+                                                         + [camera, m2d is not None], cols)
         harvest = bool(cols.requires_grad and not geo and _is_zero_table(cols))
-        out, alpha = _Rasterize.apply(cols, means, quats, scales, opacities, vm, K, width, height, kw, holder, harvest, camera)
+        out, alpha = _Rasterize.apply(cols, means, quats, scales, opacities, vm, K, width, height, kw, holder, harvest, camera,
+                                      None if m2d is None else (m2d, c))
         if _HARVEST_SHORTCUT and harvest and render_mode == "RGB" and backgrounds is None and out.requires_grad:
             out = out.as_subclass(_HarvestRender)  # recognises `(render * feats).sum()`, behaves like a tensor otherwise
         alpha = alpha[..., None]
@@ -613,6 +671,11 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
         holders.append(holder)
     tw, th = -(-width // TILE), -(-height // TILE)
     eager = dict(tile_width=tw, tile_height=th, width=width, height=height, tile_size=TILE, n_cameras=C_)
+    if m2d is not None:
+        # the leaf the views' backwards add into (_add_means2d_grad); one camera: a view of the projection's output, no copy
+        proj = [h["proj"] for h in holders]
+        m2d["leaf"] = (proj[0]["means2d"].detach()[None] if C_ == 1 else torch.stack([p["means2d"] for p in proj])).requires_grad_(True)
+        eager.update(means2d=m2d["leaf"], radii=proj[0]["radii"][None] if C_ == 1 else torch.stack([p["radii"] for p in proj]))
     meta = LazyMeta(eager, holders, C_, antialiased=rasterize_mode == "antialiased") if want_meta else eager
     if want_meta:
         meta._opac = opacities

@@ -1215,6 +1215,54 @@ GWBP_API int gwbp_image_loss(int32_t height, int32_t width, int32_t D, const flo
                              const gwbp_pixel_weights *pixel_weights, int32_t padding, float ssim_lambda, float *map, float *grad,
                              int64_t gs, double *table, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- densification: growing and pruning the set of Gaussians during training (gsplat's DefaultStrategy) --------------
+ * Four calls that need no workspace of a view.  All arrays are dense unless a stride is named; float32 unless a type is named.  No
+ * atomics: the same inputs give the same bits.  csrc/densify_math.h holds the expressions in their order.
+ *
+ * gwbp_densify_accumulate  (every training step)  v_means2d [n_cameras, n, 2]: d loss / d (2-D mean) in pixels, as
+ *     rasterization(means2d_grad=True) leaves it in meta["means2d"].grad; radii int32 [n_cameras, n].  For each camera in order, where
+ *     radii > 0:  grad2d[i] += sqrtf(a a + b b), a = gx sx, b = gy sy;  count[i] += 1.   (sx = W / 2 n_cameras, sy = H / 2 n_cameras)
+ * gwbp_densify_plan  kind[i] (uint8, GWBP_DENSIFY_KIND_*) and offsets (int64 [n + 1]), the exclusive scan of the rows each Gaussian
+ *     leaves behind (0, 1, 2, 2); offsets[n] is the size of the new set.  With m = the largest of scaling[i, 0..2] (logs; row stride
+ *     lds), g = grad2d[i] / max(count[i], 1), low = opacity[i] < t_opa (logits), high = g > t_grad, small = m <= t_small:
+ *         low -> pruned;  high and not small -> split, pruned if prune_big and m - log16 > t_big;
+ *         else pruned if prune_big and m > t_big;  else clone if high, keep if not.
+ *     Every comparison is in pre-activation space; one with a NaN is false.  workspace: gwbp_densify_plan_workspace_size(n) bytes, 8-B
+ *     aligned, free when the kernels have run.  n = 0 writes offsets[0] = 0.
+ * gwbp_densify_emit  every parent p writes its children at rows offsets[p] ..: parent (int32 [n_out]), child (uint8 [n_out]: 0 the
+ *     original or first child, 1 the second) and the new means [n_out, 3], scaling [n_out, 3], rotation [n_out, 4], opacity [n_out].
+ *     keep and clone copy the row's bits.  split, child k: mean + R(q / |q|) (exp(scaling) * noise[p, k, :]), scaling - log16, rotation
+ *     and opacity copied; noise [n, 2, 3] is read on split rows only.  A row at or beyond n_out is not written.
+ * gwbp_densify_gather  out[r, 0..w) = table[parent[r], 0..w) for r < n_out (row strides ldt, ldo >= w).  mode GWBP_DENSIFY_ZERO_NEW
+ *     (optimiser moments): a row whose parent was split, or was cloned and child[r] != 0, is zeros instead; so is a row whose parent lies
+ *     outside [0, n).  GWBP_DENSIFY_COPY reads neither child nor kind (they may be NULL).
+ * GWBP_EINVAL before any HIP call: n outside [0, 2^31 - 1], n_cameras < 1, n_out outside [0, 2 n], w outside
+ * [1, GWBP_DENSIFY_MAX_WIDTH], a row stride below its row, an unknown mode, a null or misaligned array (4 B; v_means2d, offsets and the
+ * workspace 8 B) where n (n_out) > 0.  Whether n_out IS offsets[n] cannot be seen on the host: the kernels check every row index instead.
+ * GWBP_EWORKSPACE: a workspace below the size. */
+#define GWBP_DENSIFY_KIND_PRUNED 0
+#define GWBP_DENSIFY_KIND_KEEP 1
+#define GWBP_DENSIFY_KIND_CLONE 2
+#define GWBP_DENSIFY_KIND_SPLIT 3
+#define GWBP_DENSIFY_COPY 0
+#define GWBP_DENSIFY_ZERO_NEW 1
+#define GWBP_DENSIFY_BLOCK 256
+#define GWBP_DENSIFY_GATHER_MAX_ROWS 1024
+#define GWBP_DENSIFY_MAX_WIDTH 65536
+GWBP_API int gwbp_densify_accumulate(int64_t n, int32_t n_cameras, const float *v_means2d, const int32_t *radii, float sx, float sy,
+                                     float *grad2d, float *count, void *stream);
+GWBP_API int gwbp_densify_plan_workspace_size(int64_t n, size_t *bytes);
+GWBP_API int gwbp_densify_plan(int64_t n, const float *grad2d, const float *count, const float *scaling, int64_t lds,
+                               const float *opacity, float t_grad, float t_small, float t_big, float t_opa, float log16,
+                               int32_t prune_big, uint8_t *kind, int64_t *offsets, void *workspace, size_t workspace_bytes,
+                               void *stream);
+GWBP_API int gwbp_densify_emit(int64_t n, int64_t n_out, const uint8_t *kind, const int64_t *offsets, const float *means,
+                               const float *scaling, const float *rotation, const float *opacity, const float *noise, float log16,
+                               int32_t *parent, uint8_t *child, float *out_means, float *out_scaling, float *out_rotation,
+                               float *out_opacity, void *stream);
+GWBP_API int gwbp_densify_gather(int64_t n, int64_t n_out, int32_t w, const float *table, int64_t ldt, const int32_t *parent,
+                                 const uint8_t *child, const uint8_t *kind, int32_t mode, float *out, int64_t ldo, void *stream);
+
 /* Adds this view's counters into `accum` (device, gwbp_stats) -- used by bench/driver to total pairs. */
 GWBP_API int gwbp_accumulate_stats(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, gwbp_stats *accum,
                           void *stream);

@@ -1,0 +1,144 @@
+#!/usr/bin/env python3
+"""Train a scene against its images on the HIP path with densification: Adam under the reference trainer's loss while the set of
+Gaussians grows and shrinks by gsplat's default rule (gsbp_amd.train_scene; the rounds are the kernels of csrc/densify.hip).
+
+    python run_train.py --colmap data/garden/sparse/0 --images data/garden/images_4 --data-factor 4 --steps 7000 --out trained/
+    python run_train.py --synthetic T0 --steps 60 --refine-start 10 --refine-every 10 --out /tmp/train
+
+--colmap DIR: cameras.bin, images.bin and points3D.bin of a COLMAP sparse model; the start is its point cloud (gsbp_amd.
+init_splats_from_points).  --images DIR: per view the image <image name> itself (read with PIL when it imports), or <image name>.pt /
+.npy, [H, W, 3] in [0, 1] (uint8 images are divided by 255); views without a file take no part.  --synthetic CFG: the targets are
+renders of the seeded scene with seeded colours, and the start is every --start-stride'th Gaussian of it.
+Writes into --out: trained.pt (the splat dict's tensors, pre-activation, under the reference's key names), history.json (the steps'
+losses and sizes, the rounds' counts, the resets) and metrics.json ({"before", "after"}: per-view and mean PSNR / SSIM / L1 / MSE,
+gsbp_amd.score_image_views).
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from gsbp_amd import cli  # noqa: E402
+from run_polish import load_image  # noqa: E402
+
+PARAMS = ("means", "scales", "quats", "opacities", "sh0", "shN")
+
+
+def build_parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--colmap", default=None, metavar="DIR", help="a COLMAP sparse model: cameras.bin, images.bin, points3D.bin")
+    ap.add_argument("--images", default=None, metavar="DIR", help="the views' images (with --colmap)")
+    ap.add_argument("--data-factor", type=int, default=1, help="the images are this many times smaller than the model's cameras")
+    cli.add_scene_arguments(ap, only=["synthetic", "camera-model", "rasterize-mode"])
+    ap.add_argument("--start-stride", type=int, default=2, help="--synthetic: start from every n-th Gaussian of the scene")
+    ap.add_argument("--params", nargs="+", choices=PARAMS, default=list(PARAMS))
+    ap.add_argument("--steps", type=int, default=7000)
+    ap.add_argument("--sh-degree", type=int, default=3, help="--colmap: the SH degree of the start")
+    ap.add_argument("--ssim-lambda", type=float, default=0.2)
+    ap.add_argument("--seed", type=int, default=0)
+    # the schedule (gsbp_amd.DensifyConfig; gsplat's defaults)
+    ap.add_argument("--prune-opa", type=float, default=0.005)
+    ap.add_argument("--grow-grad2d", type=float, default=2e-4)
+    ap.add_argument("--grow-scale3d", type=float, default=0.01)
+    ap.add_argument("--prune-scale3d", type=float, default=0.1)
+    ap.add_argument("--refine-start", type=int, default=500)
+    ap.add_argument("--refine-stop", type=int, default=15000)
+    ap.add_argument("--refine-every", type=int, default=100)
+    ap.add_argument("--reset-every", type=int, default=3000)
+    ap.add_argument("--pause-refine-after-reset", type=int, default=0)
+    ap.add_argument("--scene-scale", type=float, default=None,
+                    help="default: 1.1 x the largest distance of a camera from the cameras' centre (--colmap), 1 (--synthetic)")
+    ap.add_argument("--max-gaussians", type=int, default=None)
+    ap.add_argument("--out", default="./results/train")
+    return ap
+
+
+def camera_extent(viewmats: torch.Tensor) -> float:
+    """The largest distance of a camera centre from the centres' mean (what gsplat's trainer multiplies by 1.1 for its scene scale)."""
+    vm = viewmats.detach().double().cpu()
+    centres = -(vm[:, :3, :3].transpose(1, 2) @ vm[:, :3, 3:]).squeeze(-1)
+    return float((centres - centres.mean(dim=0)).norm(dim=1).max())
+
+
+def main(argv=None) -> int:
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if bool(args.synthetic) == bool(args.colmap):
+        ap.error("give exactly one of --colmap (with --images) and --synthetic")
+    if args.colmap and not args.images:
+        ap.error("--colmap needs --images")
+    if args.steps < 1 or args.start_stride < 1:
+        ap.error("--steps and --start-stride must be at least 1")
+    import gsbp_amd
+    from gsbp_amd import scene_io, synthetic as syn
+    from gsbp_amd.polish import render_splats
+    cli.require_gpu("run_train.py")
+    dev = torch.device("cuda")
+    os.makedirs(args.out, exist_ok=True)
+    kw = dict(camera_model=args.camera_model, rasterize_mode=args.rasterize_mode)
+    if args.synthetic:
+        cfg = syn.CONFIGS[args.synthetic]
+        full = {k: t.to(dev) for k, t in syn.make_scene(cfg).items()}
+        n = full["means"].shape[0]
+        gen = torch.Generator().manual_seed(syn.SH_SEED)
+        full["features_dc"] = ((torch.rand(n, 1, 3, generator=gen) - 0.5) / 0.28209479177387814).to(dev)
+        full["features_rest"] = torch.zeros(n, 0, 3, device=dev)
+        K, viewmats, W, H = syn.intrinsics(cfg).to(dev), syn.make_cameras(cfg).to(dev), cfg.width, cfg.height
+        names = [f"view_{v:04d}" for v in range(viewmats.shape[0])]
+        with torch.no_grad():
+            images = [render_splats(full, viewmats[v], K, W, H, **kw).clamp(0.0, 1.0) for v in range(viewmats.shape[0])]
+        splats = {k: t[::args.start_stride].contiguous() for k, t in full.items()}
+        scene_scale = 1.0 if args.scene_scale is None else args.scene_scale
+
+        def image_of(v):
+            return images[v]
+    else:
+        proj = scene_io.read_colmap_model(args.colmap)
+        if proj.points3D is None or len(proj.points3D) == 0:
+            raise SystemExit(f"{args.colmap} has no points3D.bin: there is nothing to start from")
+        K = scene_io.camera_matrix(next(iter(proj.cameras.values())), args.data_factor).float().to(dev)
+        W, H = int(K[0, 2] * 2), int(K[1, 2] * 2)
+        viewmats = scene_io.sorted_viewmats(proj).to(dev)
+        names = sorted(im.name for im in proj.images.values())
+        have = [v for v, name in enumerate(names) if load_image(args.images, name, "cpu") is not None]
+        if not have:
+            raise SystemExit(f"no image of this model's views in {args.images}")
+        viewmats, names = viewmats[have], [names[v] for v in have]
+        splats = gsbp_amd.init_splats_from_points(torch.from_numpy(proj.points3D).float().to(dev),
+                                                  torch.from_numpy(proj.point3D_colors).to(dev), sh_degree=args.sh_degree)
+        scene_scale = 1.1 * camera_extent(viewmats) if args.scene_scale is None else args.scene_scale
+
+        def image_of(v):
+            return load_image(args.images, names[v], dev)
+
+    cfg = gsbp_amd.DensifyConfig(prune_opa=args.prune_opa, grow_grad2d=args.grow_grad2d, grow_scale3d=args.grow_scale3d,
+                                 prune_scale3d=args.prune_scale3d, refine_start_iter=args.refine_start, refine_stop_iter=args.refine_stop,
+                                 refine_every=args.refine_every, reset_every=args.reset_every,
+                                 pause_refine_after_reset=args.pause_refine_after_reset, scene_scale=scene_scale,
+                                 max_gaussians=args.max_gaussians)
+    before = gsbp_amd.score_image_views(splats, viewmats, K, W, H, image_of, **kw)
+    n_start = splats["means"].shape[0]
+    trained, history = gsbp_amd.train_scene(splats, viewmats, K, W, H, image_of, args.steps, cfg, params=args.params,
+                                            ssim_lambda=args.ssim_lambda, seed=args.seed, **kw)
+    after = gsbp_amd.score_image_views(trained, viewmats, K, W, H, image_of, **kw)
+    torch.save({k: t.cpu() for k, t in trained.items() if torch.is_tensor(t)}, os.path.join(args.out, "trained.pt"))
+    with open(os.path.join(args.out, "history.json"), "w") as f:
+        json.dump(dict(params=list(args.params), steps=args.steps, ssim_lambda=args.ssim_lambda, seed=args.seed, views=names,
+                       config={k: getattr(cfg, k) for k in cfg.__dataclass_fields__}, loss=history["loss"], n=history["n"],
+                       rounds=history["rounds"], resets=history["resets"]), f, indent=1)
+    with open(os.path.join(args.out, "metrics.json"), "w") as f:
+        json.dump(dict(before=before, after=after), f, indent=1)
+    print(f"{n_start} -> {trained['means'].shape[0]} Gaussians in {len(history['rounds'])} rounds; loss {history['loss'][0]:.6e} -> "
+          f"{history['loss'][-1]:.6e} over {len(history['loss'])} steps; mean PSNR {before['mean']['psnr']:.3f} -> "
+          f"{after['mean']['psnr']:.3f} dB, SSIM {before['mean']['ssim']:.4f} -> {after['mean']['ssim']:.4f}")
+    print(f"wrote {args.out}: trained.pt, history.json, metrics.json")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
