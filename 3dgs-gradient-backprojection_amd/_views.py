@@ -103,7 +103,7 @@ def score_views(fn: str, means, quats, scales, opacities, viewmats, K, width, he
             eng.bin_sort(view)
             if blend:
                 eng.blend_weights(view)
-            eng.generation += 1
+            eng.holds_new_view()
             launch(view)
             eng.accumulate_stats(accum)
         stats = Engine.decode_stats(accum)

@@ -22,6 +22,7 @@ import torch
 from ._lib import GwbpError
 from ._views import front, require_device
 from ._views import raster_kw as merged_raster_kw
+from .polish import view_schedule
 from .rasterization import PIXEL_RENDER_MAX_DIM, engine_on, get_engine
 
 REDUCTIONS = ("mean", "sum")
@@ -147,13 +148,9 @@ def fit_decoded_field(means, quats, scales, opacities, viewmats, K, width, heigh
     latents.requires_grad_(True)
     decoder.requires_grad_(True)
     opt = torch.optim.Adam([latents, decoder], lr=lr)
-    n_views = viewmats.shape[0]
     vm_host, k_host = viewmats.detach().cpu(), K.detach().cpu()
-    losses, order = [], []
-    for step in range(int(steps)):
-        if not order:
-            order = torch.randperm(n_views, generator=gen).tolist()
-        v = order.pop(0)
+    losses = []
+    for step, v in enumerate(view_schedule(viewmats.shape[0], gen, steps)):  # (gen: the draws follow the decoder's above)
         out = decoded_field_gradients(means, quats, scales, opacities, latents, decoder, feature_fn(v), vm_host[v],
                                       k_host if k_host.dim() == 2 else k_host[v], width, height, loss=loss,
                                       pixel_weights=pixel_weight_fn(v) if pixel_weight_fn is not None else None, **raster_kw)

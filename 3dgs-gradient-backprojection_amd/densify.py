@@ -32,7 +32,7 @@ from . import _lib
 from ._lib import GwbpError, ptr
 from ._views import ld, run
 from .photometric import photometric_loss
-from .polish import DEFAULT_LRS, PARAM_KEYS, render_splats
+from .polish import PARAM_KEYS, render_splats, trainable, view_K, view_schedule
 from .rasterization import release_engines
 
 GEOMETRY_KEYS = ("means", "scaling", "rotation", "opacity")  # what the emit kernel writes; every other [N, ...] tensor is gathered
@@ -303,39 +303,17 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
     resets = the steps of the opacity resets; carry = the relocated `carry` tables).
     The view of a step and the split noise come from seeded generators: the same call gives the same schedule of rounds."""
     cfg = cfg if cfg is not None else DensifyConfig()
-    unknown = [p for p in params if p not in PARAM_KEYS]
-    if unknown or not params:
-        raise GwbpError(f"params must be names out of {sorted(PARAM_KEYS)}, got {list(params)}")
-    if not splats["means"].is_cuda:
-        raise GwbpError("train_scene() needs HIP tensors (there is no CPU path)")
-    if "features_dc" not in splats:
-        raise GwbpError("the splat dict has no features_dc: train_scene() renders SH colours")
-    rates = dict(DEFAULT_LRS, **(lrs or {}))
-    width, height = int(width), int(height)
-    dev = splats["means"].device
-    work = {k: (t.detach() if torch.is_tensor(t) else t) for k, t in splats.items()}
-    groups = []
-    for name in params:
-        key = PARAM_KEYS[name]
-        if key not in work:
-            raise GwbpError(f"the splat dict has no {key!r} (parameter {name!r})")
-        work[key] = work[key].float().clone().requires_grad_(True)
-        groups.append(dict(params=[work[key]], lr=float(rates[name])))
+    work, opt = trainable(splats, params, lrs, "train_scene")
+    dev, width, height = splats["means"].device, int(width), int(height)
     for key in GEOMETRY_KEYS:  # what the rounds write must be float32 whether it is trained or not
         work[key] = work[key] if work[key].requires_grad else work[key].float()
-    opt = torch.optim.Adam(groups, eps=1e-15)
-    gen = torch.Generator().manual_seed(int(seed))
     noise_gen = torch.Generator(device=dev).manual_seed(int(seed))
     state = DensifyState(work["means"].shape[0], dev)
     carried = dict(carry or {})
-    n_views = viewmats.shape[0]
-    losses, sizes, rounds, resets, order = [], [], [], [], []
-    for step in range(int(steps)):
-        if not order:
-            order = torch.randperm(n_views, generator=gen).tolist()
-        v = order.pop(0)
+    losses, sizes, rounds, resets = [], [], [], []
+    for step, v in enumerate(view_schedule(viewmats.shape[0], seed, steps)):
         opt.zero_grad(set_to_none=True)
-        image, meta = render_splats(work, viewmats[v], K if K.dim() == 2 else K[v], width, height, return_meta=True, means2d_grad=True, **raster_kw)
+        image, meta = render_splats(work, viewmats[v], view_K(K, v), width, height, return_meta=True, means2d_grad=True, **raster_kw)
         loss = photometric_loss(image, image_fn(v), ssim_lambda=ssim_lambda)
         loss.backward()
         if step < cfg.refine_stop_iter:

@@ -115,7 +115,13 @@ class Engine:
         self._halves = False  # the workspace holds the half-tile lists + weight sums of the view blended last
         self._tokens = None   # (h, w) of the map whose token-quadrant weight sums the workspace holds (blend_tokens)
         self.stream, self._stream_handle = None, None
+        self.generation, self.front_cache = 0, None  # see holds_new_view
         self._alloc()
+
+    def holds_new_view(self, front_cache: Optional[dict] = None) -> None:
+        """The workspace holds another view now; whoever projects one into it says so.  rasterization()'s backwards compare `generation`
+        with their forward's (a missed count is a silently wrong gradient); `front_cache` is run_front's record of its view, or None."""
+        self.generation, self.front_cache = self.generation + 1, front_cache
 
     def _set_flag(self, bit: int, on: bool) -> None:
         if on:

@@ -40,8 +40,40 @@ def render_splats(splats: Dict[str, torch.Tensor], viewmat, K, width: int, heigh
     return (out[0], meta) if return_meta else out[0]
 
 
-def _view_K(K, v):
+def view_K(K, v):
     return K if K.dim() == 2 else K[v]
+
+
+def trainable(splats: Dict[str, torch.Tensor], params: Sequence[str], lrs: Optional[Dict[str, float]], fn: str):
+    """(work, optimizer) of fn(): `splats` detached, each named parameter a float32 leaf of its own, and torch.optim.Adam with ONE
+    tensor per group at lrs[name] over DEFAULT_LRS, eps 1e-15 as in the reference trainer (densify._relocate_adam relies on that layout)."""
+    unknown = [p for p in params if p not in PARAM_KEYS]
+    if unknown or not params:
+        raise GwbpError(f"params must be names out of {sorted(PARAM_KEYS)}, got {list(params)}")
+    if not splats["means"].is_cuda:
+        raise GwbpError(f"{fn}() needs HIP tensors (there is no CPU path)")
+    if "features_dc" not in splats:
+        raise GwbpError(f"the splat dict has no features_dc: {fn}() renders SH colours")
+    rates = dict(DEFAULT_LRS, **(lrs or {}))
+    work = {k: (t.detach() if torch.is_tensor(t) else t) for k, t in splats.items()}
+    groups = []
+    for name in params:
+        key = PARAM_KEYS[name]
+        if key not in work:
+            raise GwbpError(f"the splat dict has no {key!r} (parameter {name!r})")
+        work[key] = work[key].float().clone().requires_grad_(True)
+        groups.append(dict(params=[work[key]], lr=float(rates[name])))
+    return work, torch.optim.Adam(groups, eps=1e-15)
+
+
+def view_schedule(n_views: int, seed: int, steps: int):
+    """The view of each step: a fresh permutation per pass over the views, drawn on the host from `seed` (an int or the caller's generator)."""
+    gen = seed if isinstance(seed, torch.Generator) else torch.Generator().manual_seed(int(seed))
+    order = []
+    for _ in range(int(steps)):
+        if not order:
+            order = torch.randperm(n_views, generator=gen).tolist()
+        yield order.pop(0)
 
 
 def polish_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, image_fn: Callable[[int], torch.Tensor],
@@ -53,33 +85,11 @@ def polish_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, im
     trainer's, DEFAULT_LRS; eps 1e-15 as there).  Each step takes one view, drawn from torch.Generator().manual_seed(seed) on the
     host as a fresh permutation per pass over the views.  image_fn(v): the view's float32 [H, W, 3] image in [0, 1] on the device.
     viewmats [V, 4, 4]; K [3, 3] or [V, 3, 3].  raster_kw: camera_model, rasterize_mode and the other keywords of rasterization()."""
-    unknown = [p for p in params if p not in PARAM_KEYS]
-    if unknown or not params:
-        raise GwbpError(f"params must be names out of {sorted(PARAM_KEYS)}, got {list(params)}")
-    if not splats["means"].is_cuda:
-        raise GwbpError("polish_scene() needs HIP tensors (there is no CPU path)")
-    rates = dict(DEFAULT_LRS, **(lrs or {}))
-    width, height = int(width), int(height)
-    work = {k: (t.detach() if torch.is_tensor(t) else t) for k, t in splats.items()}
-    if "features_dc" not in work:
-        raise GwbpError("the splat dict has no features_dc: polish_scene() renders SH colours")
-    groups = []
-    for name in params:
-        key = PARAM_KEYS[name]
-        if key not in work:
-            raise GwbpError(f"the splat dict has no {key!r} (parameter {name!r})")
-        work[key] = work[key].float().clone().requires_grad_(True)
-        groups.append(dict(params=[work[key]], lr=float(rates[name])))
-    opt = torch.optim.Adam(groups, eps=1e-15)
-    gen = torch.Generator().manual_seed(int(seed))
-    n_views = viewmats.shape[0]
-    losses, order = [], []
-    for _ in range(int(steps)):
-        if not order:
-            order = torch.randperm(n_views, generator=gen).tolist()
-        v = order.pop(0)
+    work, opt = trainable(splats, params, lrs, "polish_scene")
+    width, height, losses = int(width), int(height), []
+    for v in view_schedule(viewmats.shape[0], seed, steps):
         opt.zero_grad(set_to_none=True)
-        image = render_splats(work, viewmats[v], _view_K(K, v), width, height, **raster_kw)
+        image = render_splats(work, viewmats[v], view_K(K, v), width, height, **raster_kw)
         loss = photometric_loss(image, image_fn(v), ssim_lambda=ssim_lambda)
         loss.backward()
         opt.step()
@@ -95,7 +105,7 @@ def score_image_views(splats: Dict[str, torch.Tensor], viewmats, K, width, heigh
     rows = []
     with torch.no_grad():
         for v in range(viewmats.shape[0]):
-            image = render_splats(splats, viewmats[v], _view_K(K, v), int(width), int(height), **raster_kw)
+            image = render_splats(splats, viewmats[v], view_K(K, v), int(width), int(height), **raster_kw)
             rows.append(dict(view=v, **image_metrics(image.clamp(0.0, 1.0), image_fn(v))))
     keys = ("psnr", "ssim", "l1", "mse")
     return dict(views=rows, mean={k: sum(r[k] for r in rows) / len(rows) for k in keys} if rows else {})

@@ -17,7 +17,8 @@ Backward = scatter with v_render_colors as the feature map: colors.grad[g,:] += 
 from __future__ import annotations
 
 import weakref
-from typing import Dict, Optional, Tuple
+from types import SimpleNamespace
+from typing import Callable, Dict, NamedTuple, Optional, Tuple
 
 import torch
 from torch.utils import _pytree
@@ -134,7 +135,6 @@ def get_engine(device, n: int, width: int, height: int) -> Engine:
         for k in mine[:max(0, len(mine) - 1)]:
             del _ENGINES[k]
         eng = _ENGINES[key] = Engine(n, width, height, device=device)
-        eng.generation = 0
     return eng
 
 
@@ -176,7 +176,7 @@ def run_front(eng: Engine, view, means, quats, scales, opacities, want_alphas, w
     whole front.  Tensors that are equal but not identical (a fresh .clone() per call) are projected again."""
     gauss = (means, quats, scales, opacities)
     key = _front_key(view, gauss)
-    c = getattr(eng, "front_cache", None)
+    c = eng.front_cache
     if (c is not None and c["key"] == key and _same_tensors(c["tensors"], gauss) and (c["store"] or not want_store) and (c["meta"] or not want_meta)
             and (c["alphas"] is not None or not want_alphas) and (c["halves"] or not eng._wide_requested())):
         return c["proj"], c["bins"], (c["alphas"].clone() if want_alphas else None), c["stats"]
@@ -187,19 +187,49 @@ def run_front(eng: Engine, view, means, quats, scales, opacities, want_alphas, w
         alphas = eng.blend_weights(view, want_alphas=want_alphas) if want_store else None
         st = eng.stats()
         if not st["overflow"]:
-            eng.generation += 1
             # `tensors`: strong references -- they pin the storages, so the identity test above cannot be fooled by reuse
-            eng.front_cache = dict(key=key, tensors=gauss, proj=proj, bins=bins, alphas=alphas, stats=st,
-                                   store=want_store, meta=want_meta, halves=want_store and eng._halves)
+            eng.holds_new_view(dict(key=key, tensors=gauss, proj=proj, bins=bins, alphas=alphas, stats=st,
+                                    store=want_store, meta=want_meta, halves=want_store and eng._halves))
             return proj, bins, alphas, st
         eng.grow(st)
 
 
-def _geometry_path(needs, colors: torch.Tensor) -> bool:
-    """Does this call's backward go through the blend backward kernel?  Some of means / quats / scales / opacities -- or, under
-    camera_grad=True, the view matrix, or, under means2d_grad=True, the projected means -- needs a gradient (`needs`) and the table is
-    one the kernel reads: float32, at most GEOMETRY_GRAD_MAX_DIM channels."""
-    return bool(any(needs)) and colors.shape[1] <= GEOMETRY_GRAD_MAX_DIM and colors.dtype == torch.float32
+def _geometry_table(d: int, dtype, keyword: Optional[str] = None, note: str = " (the depth column included)") -> bool:
+    """Is a [N, d] table of this dtype one the blend backward kernel reads?  With the keyword that needs one (if any): raise if it is not."""
+    ok = d <= GEOMETRY_GRAD_MAX_DIM and dtype == torch.float32
+    if keyword and not ok:
+        raise NotImplementedError(f"{keyword}=True needs a float32 table of at most {GEOMETRY_GRAD_MAX_DIM} channels{note}, got {dtype} with {d}")
+    return ok
+
+
+class _Route(NamedTuple):
+    """Every choice rasterization() makes for one view: _route() decides them once per camera, _Rasterize reads them."""
+    # the backward is the blend backward + the projection backward (_geometry_backward), not the colour scatter: a Gaussian tensor -- or the
+    # view matrix, or the projected means -- wants a gradient; that kernel needs the sorted lists only, gives the colour gradient too and reads the kept rows
+    geo: bool
+    camera: bool       # ... and it sums the gradient w.r.t. the view matrix as well (camera_grad=True)
+    # the reference's harvesting pattern (backproject.py:67-72,115-129,133-147): an all-zero differentiable table whose render is only there to
+    # be back-propagated through -- zeros for any D: the cached buffer, no kernel.  Never under geo: the zero render has no alpha-map or geometry history
+    harvest: bool
+    need_store: bool   # the blend writes its weight store: only needed for the colour backward / the wide render
+    # off: a backward with D % 256 == 0 channels goes through the 256-channel scatter kernel, which needs the blend's half-tile lists --
+    # the engine's flag must be in place before this view's blend
+    narrow: bool
+    want_alphas: bool  # the alpha map is the front stage's (the blend's); render_pixels makes its own
+    # "zero": harvest | "pixels": RGB / RGB+D / depth / the 16-d compressed field (segment_compressed.py:154-165), the pixel-parallel
+    # rasteriser straight from the sorted tile lists | "wide": the weight-store render
+    render: str
+
+
+def _route(d: int, dtype, table_grad: bool, gauss_grad: bool, camera: bool, means2d: bool, zero: Callable[[], bool]) -> _Route:
+    """The route of one view from the rendered table's channels, dtype and requires_grad; whether some of means / quats / scales / opacities
+    requires grad -- WHATEVER the grad mode, as needs_input_grad reports it inside a Function; whether the call differentiates viewmats and
+    has a meta["means2d"] leaf (both with the grad mode in them); zero(), the table's all-zero verdict, asked only where it matters."""
+    geo = bool(gauss_grad or camera or means2d) and _geometry_table(d, dtype)
+    harvest = bool(table_grad and not geo and zero())
+    wide = d > PIXEL_RENDER_MAX_DIM
+    return _Route(geo, bool(camera), harvest, need_store=bool(table_grad and not geo) or wide, narrow=not (table_grad and d % 256 == 0),
+                  want_alphas=wide or harvest, render="zero" if harvest else ("wide" if wide else "pixels"))
 
 
 def _geometry_backward(ctx, g_out, g_alpha):
@@ -220,15 +250,19 @@ def _geometry_backward(ctx, g_out, g_alpha):
         g_out = torch.zeros(view.height, view.width, ctx.shape[1], device=means.device)
     v_colors, v_g2d = eng.render_pixels_backward(view, colors.detach(), g_out.detach(),
                                                  g_alpha.detach() if g_alpha is not None else None, want_colors=needs[0])
-    if ctx.means2d is not None:
-        _add_means2d_grad(*ctx.means2d, v_g2d)
-    want_viewmat = bool(ctx.camera_grad and needs[5])
+    if ctx.call.means2d is not None:
+        _add_means2d_grad(*ctx.call.means2d, v_g2d)
+    want_viewmat = ctx.call.route.camera
     if not (any(needs[1:5]) or want_viewmat):  # (a call that only asked for means2d.grad beside its colours)
-        return (v_colors,) + (None,) * 13
+        return _grads(ctx, v_colors)
     grads = eng.project_backward(view, means.detach(), quats.detach(), scales.detach(), opacities.detach(), v_g2d, needs=needs[1:5],
                                  want_viewmat=want_viewmat)
     v_vm = None if grads[4] is None else grads[4].to(ctx.vm_dtype)
-    return (v_colors,) + tuple(grads[:4]) + (v_vm,) + (None,) * 8
+    return _grads(ctx, v_colors, *grads[:4], v_vm)
+
+
+def _grads(ctx, *given):  # a backward's return: the gradients it has, in the order of apply's arguments, None for every argument behind
+    return given + (None,) * (len(ctx.needs_input_grad) - len(given))
 
 
 def _add_means2d_grad(slot: dict, c: int, v_g2d: torch.Tensor) -> None:
@@ -250,69 +284,48 @@ def _add_means2d_grad(slot: dict, c: int, v_g2d: torch.Tensor) -> None:
 
 class _Rasterize(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, colors, means, quats, scales, opacities, viewmat, K, width, height, kw, holder, harvest=None, camera_grad=False,
-                means2d=None):
-        dev = means.device
-        eng = get_engine(dev, means.shape[0], width, height)
-        view = eng.view(viewmat, K, width, height, **kw)
-        D = colors.shape[1]
-        # means / quats / scales / opacities want a gradient and the blend backward kernel can give it (_geometry_backward): that
-        # kernel needs the sorted lists only, hands the colour gradient back as well, and reads which rows the projection kept
-        # (camera_grad=True: the view matrix as well, through the same two kernels)
-        camera_grad = bool(camera_grad and ctx.needs_input_grad[5])
-        # means2d: None, or (slot, camera index) of a means2d_grad=True call: the blend backward runs whoever else needs it
-        geo = _geometry_path(tuple(ctx.needs_input_grad[1:5]) + (camera_grad, means2d is not None), colors)
-        # the weight store is only needed for the colour backward / the wide render
-        need_store = (colors.requires_grad and not geo) or D > PIXEL_RENDER_MAX_DIM
-        # a backward with D % 256 == 0 channels goes through the 256-channel scatter kernel, which needs the blend's
-        # half-tile lists: the flag must be in place before this view's blend
-        eng.set_narrow_scatter(not (colors.requires_grad and D % 256 == 0))
-        # the reference's harvesting pattern: an all-zero differentiable colour table whose render is only there to be
-        # back-propagated through (backproject.py:67-72,115-129,133-147) -- the render of zeros is zeros, for any D
-        if harvest is None:
-            harvest = colors.requires_grad and not geo and _is_zero_table(colors)
-        harvest = harvest and not geo  # (the zero render has no alpha-map or geometry history to offer)
-        proj, bins, alphas, st = run_front(eng, view, means, quats, scales, opacities, D > PIXEL_RENDER_MAX_DIM or harvest,
-                                            holder is not None, want_store=need_store)
-        if harvest:
-            out = _zero_render(dev, view.height, view.width, D)  # (alphas: the blend's, kept with the front-stage result)
-        elif D <= PIXEL_RENDER_MAX_DIM:  # RGB / RGB+D / depth / the 16-d compressed field (segment_compressed.py:154-165):
-            # pixel-parallel rasteriser straight from the sorted tile lists
+    def forward(ctx, colors, means, quats, scales, opacities, viewmat, K, call):
+        # call: width, height, kw (Engine.view's), holder (proj / bins / stats go there for the meta, or None), route, means2d (see _add_means2d_grad, or None)
+        route, holder, dev = call.route, call.holder, means.device
+        eng = get_engine(dev, means.shape[0], call.width, call.height)
+        view = eng.view(viewmat, K, call.width, call.height, **call.kw)
+        eng.set_narrow_scatter(route.narrow)
+        proj, bins, alphas, st = run_front(eng, view, means, quats, scales, opacities, route.want_alphas, holder is not None,
+                                            want_store=route.need_store)
+        if route.render == "zero":
+            out = _zero_render(dev, view.height, view.width, colors.shape[1])  # (alphas: the blend's, kept with the front-stage result)
+        elif route.render == "pixels":
             out, alphas = eng.render_pixels(view, colors.detach())
         else:
             out = eng.render(view, colors.detach())
-        ctx.has_store = need_store
         if holder is not None:
             holder.update(proj=proj, bins=bins, stats=st)
-        ctx.eng, ctx.view, ctx.gen = eng, view, eng.generation
-        ctx.save_for_backward(*((means, quats, scales, opacities) + ((colors,) if geo else ())))
-        ctx.shape = colors.shape
+        ctx.call, ctx.eng, ctx.view, ctx.gen, ctx.shape, ctx.vm_dtype = call, eng, view, eng.generation, colors.shape, viewmat.dtype
+        ctx.save_for_backward(*((means, quats, scales, opacities) + ((colors,) if route.geo else ())))
         # the leaf whose .grad the backward may add into directly (see backward)
         ctx.leaf = weakref.ref(colors) if (colors.requires_grad and colors.is_leaf) else None
         ctx.leaf_node = _accumulate_node(colors) if ctx.leaf is not None else None
-        ctx.geo, ctx.camera_grad, ctx.vm_dtype = geo, camera_grad, viewmat.dtype
-        ctx.means2d = means2d if geo else None
-        if not geo:  # (under geo the alpha map depends on the geometry, the opacities and the camera: it carries a gradient)
+        if not route.geo:  # (under geo the alpha map depends on the geometry, the opacities and the camera: it carries a gradient)
             ctx.mark_non_differentiable(alphas)
         return out, alphas
 
     @staticmethod
     def backward(ctx, g_out, g_alpha):
-        needs = ctx.needs_input_grad
-        if needs[6] or (needs[5] and not (ctx.geo and ctx.camera_grad)) or (any(needs[1:5]) and not ctx.geo):
+        needs, route = ctx.needs_input_grad, ctx.call.route
+        if needs[6] or (needs[5] and not (route.geo and route.camera)) or (any(needs[1:5]) and not route.geo):
             raise NotImplementedError(
                 "gradients are implemented w.r.t. colors and, beside a float32 colour table of at most "
                 f"{GEOMETRY_GRAD_MAX_DIM} channels, w.r.t. means, quats, scales and opacities, and w.r.t. viewmats in a call with "
                 "camera_grad=True; not w.r.t. Ks, not w.r.t. viewmats in a default call (camera_grad=False), and not w.r.t. the "
                 "geometry or the camera beside a wider or a float16 / bfloat16 table")
-        if ctx.geo:
+        if route.geo:
             return _geometry_backward(ctx, g_out, g_alpha)
         eng, view = ctx.eng, ctx.view
         means, quats, scales, opacities = ctx.saved_tensors
-        if eng.generation != ctx.gen or eng.n != means.shape[0] or not ctx.has_store:
+        if eng.generation != ctx.gen or eng.n != means.shape[0] or not route.need_store:
             # the workspace was reused by another call since forward: rebuild this view's weight store
             eng = get_engine(means.device, means.shape[0], view.width, view.height)
-            eng.set_narrow_scatter(ctx.shape[1] % 256 != 0)
+            eng.set_narrow_scatter(route.narrow)
             eng.front_cache = None
             run_front(eng, view, means, quats, scales, opacities, False, False)
         # The reference keeps ONE grad tensor per colour table alive (it clones and zeroes it in place, backproject.py:130-131),
@@ -327,10 +340,10 @@ class _Rasterize(torch.autograd.Function):
                 and _grad_is_unobserved(leaf, ctx.leaf_node)):
             _scatter_grad(eng, view, g_out, acc)
             acc[:0].add_(0)  # the kernel wrote through data_ptr: move .grad's version counter like an in-place op would
-            return (None,) * 14
+            return _grads(ctx)
         v_colors = torch.zeros(ctx.shape, device=means.device, dtype=torch.float32)
         _scatter_grad(eng, view, g_out, v_colors)
-        return (v_colors,) + (None,) * 13
+        return _grads(ctx, v_colors)
 
 
 def _scatter_grad(eng: Engine, view, g_out: torch.Tensor, acc: torch.Tensor) -> None:
@@ -497,9 +510,9 @@ class LazyMeta(dict):
     """meta dict of gsplat.rasterization (packed=True layout); the packed index tensors are materialised on
     first access because building them (nonzero) synchronises the host."""
 
-    def __init__(self, eager, holders, n_cameras, antialiased=False):
+    def __init__(self, eager, holders, n_cameras, opacities, antialiased=False):
         super().__init__(eager)
-        self._h, self._c = holders, n_cameras
+        self._h, self._c, self._opac = holders, n_cameras, opacities
         self._pinned = tuple(k for k in ("radii", "means2d") if k in eager)  # unpacked by a means2d_grad=True call: kept as given
         self._aa = antialiased
         if antialiased:  # gsplat: meta["opacities"] are the compensated opacities the blend used, meta["compensations"] beside
@@ -555,6 +568,34 @@ class LazyMeta(dict):
         return k in self._LAZY or dict.__contains__(self, k)
 
 
+def _camera_table(c: int, means, colors, vm, sh_degree, render_mode, width, height, camera, m2d) -> torch.Tensor:
+    """The [N, D] table camera c renders: the colours as given or the SH colours from its centre, the depth modes' camera z behind or alone."""
+    if sh_degree is not None:
+        # colors is [N,K,3] (or [C,N,K,3]); view-dependent colour + 0.5, clamped at 0 (gsplat semantics)
+        sh = colors if colors.dim() == 3 else colors[c]
+        vm_h = vm.detach().cpu()
+        campos = (-(vm_h[:3, :3].T @ vm_h[:3, 3])).tolist()
+        if torch.is_grad_enabled() and (sh.requires_grad or means.requires_grad):
+            # k_sh_colors in torch ops: autograd carries the colour gradient to the coefficients and, through the view
+            # direction, to means
+            if sh.dtype != torch.float32:
+                raise GwbpError(f"sh coefficients must be float32, got {sh.dtype}")
+            cols = sh_colors_torch(sh_degree, means, sh, campos)
+        else:
+            cols = get_engine(means.device, means.shape[0], width, height).sh_colors(sh_degree, means, sh, campos)
+    else:
+        cols = colors if colors.dim() == 2 else colors[c]
+    if "D" in render_mode:
+        z = (means @ vm[:3, :3].T + vm[:3, 3])[:, 2:3]
+        cols = z if render_mode in ("D", "ED") else torch.cat([cols, z], dim=1)
+    if cols.dtype not in HALF_TYPES:  # (a half table is read as stored, row stride included: Engine.render's field_rows)
+        cols = cols.contiguous()
+    _geometry_table(cols.shape[1], cols.dtype, camera and "camera_grad")
+    # (the check at the call is at least as strict on the table as given; this one sees what means of another dtype made of it)
+    _geometry_table(cols.shape[1], cols.dtype, m2d is not None and "means2d_grad", note="")
+    return cols
+
+
 def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane: float = 0.01,
                   far_plane: float = 1e10, radius_clip: float = 0.0, eps2d: float = 0.3,
                   sh_degree: Optional[int] = None, packed: bool = True, tile_size: int = 16, backgrounds=None,
@@ -592,6 +633,7 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     columns anyway, so nothing is launched for them but the copy into .grad.  Still not offered: absgrad (a second, absolute sum
     inside the blend backward), packed mode's sparse gradients.
     """
+    # 1. check the call: raise for what it cannot have
     if tile_size != TILE:
         raise GwbpError(f"tile_size must be {TILE}: the tile rectangle is part of the numerics")
     if (camera_model not in _lib.CAMERA_MODELS or covars is not None or distributed or absgrad
@@ -602,10 +644,8 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
         raise ValueError(render_mode)
     m2d = {} if (means2d_grad and torch.is_grad_enabled()) else None
     if m2d is not None and sh_degree is None:
-        d_table = (0 if render_mode in ("D", "ED") else colors.shape[-1]) + (1 if "D" in render_mode else 0)
-        if d_table > GEOMETRY_GRAD_MAX_DIM or colors.dtype != torch.float32:
-            raise NotImplementedError(f"means2d_grad=True needs a float32 table of at most {GEOMETRY_GRAD_MAX_DIM} channels (the depth "
-                                      f"column included), got {colors.dtype} with {d_table}")
+        _geometry_table((0 if render_mode in ("D", "ED") else colors.shape[-1]) + (1 if "D" in render_mode else 0), colors.dtype,
+                        "means2d_grad")
     if not means.is_cuda:
         raise GwbpError("rasterization() needs HIP tensors (the reference likewise requires CUDA, backproject.py:314)")
     if sh_degree is None and colors.dtype in HALF_TYPES and colors.requires_grad:
@@ -618,48 +658,18 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     if camera and sh_degree is not None:
         raise NotImplementedError("camera_grad=True with sh_degree: the SH view direction uses a detached camera centre, so the "
                                   "gradient w.r.t. viewmats would miss it; pass colours, or detach viewmats")
-    C_ = viewmats.shape[0]
-    N = means.shape[0]
     kw = dict(near_plane=near_plane, far_plane=far_plane, eps2d=eps2d, radius_clip=radius_clip, camera_model=camera_model,
               rasterize_mode=rasterize_mode)
-
+    gauss_grad = any(t.requires_grad for t in (means, quats, scales, opacities))  # (whatever the grad mode, as needs_input_grad says it)
     outs, alphas, holders = [], [], []
-    for c in range(C_):
+    for c in range(viewmats.shape[0]):  # 2. per camera: build its table, route it, render it
         vm, K = viewmats[c], Ks[c]
-        if sh_degree is not None:
-            # colors is [N,K,3] (or [C,N,K,3]); view-dependent colour + 0.5, clamped at 0 (gsplat semantics)
-            sh = colors if colors.dim() == 3 else colors[c]
-            vm_h = vm.detach().cpu()
-            campos = (-(vm_h[:3, :3].T @ vm_h[:3, 3])).tolist()
-            if torch.is_grad_enabled() and (sh.requires_grad or means.requires_grad):
-                # k_sh_colors in torch ops: autograd carries the colour gradient to the coefficients and, through the view
-                # direction, to means
-                if sh.dtype != torch.float32:
-                    raise GwbpError(f"sh coefficients must be float32, got {sh.dtype}")
-                cols = sh_colors_torch(sh_degree, means, sh, campos)
-            else:
-                cols = get_engine(means.device, N, width, height).sh_colors(sh_degree, means, sh, campos)
-        else:
-            cols = colors if colors.dim() == 2 else colors[c]
+        cols = _camera_table(c, means, colors, vm, sh_degree, render_mode, width, height, camera, m2d)
+        route = _route(cols.shape[1], cols.dtype, cols.requires_grad, gauss_grad, camera, m2d is not None, lambda: _is_zero_table(cols))
         holder = {} if (want_meta or "D" in render_mode or m2d is not None) else None
-        need_depth = render_mode in ("D", "ED", "RGB+D", "RGB+ED")
-        if need_depth:
-            z = (means @ vm[:3, :3].T + vm[:3, 3])[:, 2:3]
-            cols = z if render_mode in ("D", "ED") else torch.cat([cols, z], dim=1)
-        if cols.dtype not in HALF_TYPES:  # (a half table is read as stored, row stride included: Engine.render's field_rows)
-            cols = cols.contiguous()
-        if camera and (cols.shape[1] > GEOMETRY_GRAD_MAX_DIM or cols.dtype != torch.float32):
-            raise NotImplementedError(f"camera_grad=True needs a float32 table of at most {GEOMETRY_GRAD_MAX_DIM} channels (the depth "
-                                      f"column included), got {cols.dtype} with {cols.shape[1]}")
-        if m2d is not None and (cols.shape[1] > GEOMETRY_GRAD_MAX_DIM or cols.dtype != torch.float32):
-            raise NotImplementedError(f"means2d_grad=True needs a float32 table of at most {GEOMETRY_GRAD_MAX_DIM} channels, got "
-                                      f"{cols.dtype} with {cols.shape[1]}")
-        geo = torch.is_grad_enabled() and _geometry_path([t.requires_grad for t in (means, quats, scales, opacities)]
-                                                         + [camera, m2d is not None], cols)
-        harvest = bool(cols.requires_grad and not geo and _is_zero_table(cols))
-        out, alpha = _Rasterize.apply(cols, means, quats, scales, opacities, vm, K, width, height, kw, holder, harvest, camera,
-                                      None if m2d is None else (m2d, c))
-        if _HARVEST_SHORTCUT and harvest and render_mode == "RGB" and backgrounds is None and out.requires_grad:
+        call = SimpleNamespace(width=width, height=height, kw=kw, holder=holder, route=route, means2d=None if m2d is None else (m2d, c))
+        out, alpha = _Rasterize.apply(cols, means, quats, scales, opacities, vm, K, call)
+        if _HARVEST_SHORTCUT and route.harvest and render_mode == "RGB" and backgrounds is None and out.requires_grad:
             out = out.as_subclass(_HarvestRender)  # recognises `(render * feats).sum()`, behaves like a tensor otherwise
         alpha = alpha[..., None]
         if render_mode in ("ED", "RGB+ED"):
@@ -669,16 +679,16 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
         outs.append(out)
         alphas.append(alpha)
         holders.append(holder)
-    tw, th = -(-width // TILE), -(-height // TILE)
-    eager = dict(tile_width=tw, tile_height=th, width=width, height=height, tile_size=TILE, n_cameras=C_)
+    # 3. assemble the meta from what the cameras' forwards left in `holders`
+    n_cameras = len(holders)
+    eager = dict(tile_width=-(-width // TILE), tile_height=-(-height // TILE), width=width, height=height, tile_size=TILE,
+                 n_cameras=n_cameras)
     if m2d is not None:
         # the leaf the views' backwards add into (_add_means2d_grad); one camera: a view of the projection's output, no copy
         proj = [h["proj"] for h in holders]
-        m2d["leaf"] = (proj[0]["means2d"].detach()[None] if C_ == 1 else torch.stack([p["means2d"] for p in proj])).requires_grad_(True)
-        eager.update(means2d=m2d["leaf"], radii=proj[0]["radii"][None] if C_ == 1 else torch.stack([p["radii"] for p in proj]))
-    meta = LazyMeta(eager, holders, C_, antialiased=rasterize_mode == "antialiased") if want_meta else eager
-    if want_meta:
-        meta._opac = opacities
-    if C_ == 1:  # (no copy of a 3.5 GB render: a view with the camera axis in front)
+        m2d["leaf"] = (proj[0]["means2d"].detach()[None] if n_cameras == 1 else torch.stack([p["means2d"] for p in proj])).requires_grad_(True)
+        eager.update(means2d=m2d["leaf"], radii=proj[0]["radii"][None] if n_cameras == 1 else torch.stack([p["radii"] for p in proj]))
+    meta = LazyMeta(eager, holders, n_cameras, opacities, antialiased=rasterize_mode == "antialiased") if want_meta else eager
+    if len(outs) == 1:  # (no copy of a 3.5 GB render: a view with the camera axis in front)
         return one_camera_batch(outs[0]), alphas[0][None], meta
     return torch.stack(outs), torch.stack(alphas), meta

@@ -71,7 +71,7 @@ class Recorder:
         return {k: self.summary(v) for k, v in b.arguments.items() if k not in ("self", "viewmat", "K")}
 
 
-def _install(monkeypatch, rec):
+def _install(monkeypatch, rec, names=RECORDED):
     E = gsbp_amd.Engine
 
     def wrap(name, orig):
@@ -85,7 +85,7 @@ def _install(monkeypatch, rec):
             return out
         return f
 
-    for name in RECORDED:
+    for name in names:
         monkeypatch.setattr(E, name, wrap(name, getattr(E, name)))
     orig_init = E.__init__
 

@@ -47,7 +47,6 @@ def test_a_pass_that_overflows_grows_the_workspace_and_gives_the_same_bits(dev, 
     assert n_isect > 3000  # the small engine below cannot hold the view: its first pass must overflow
     del _ENGINES[key]
     small = _ENGINES[key] = gsbp_amd.Engine(cfg.n_gaussians, cfg.width, cfg.height, device=dev, isect_cap=3000)
-    small.generation = 0
     got = _score(which, t1)
     assert got.dtype == want.dtype and torch.equal(got.view(torch.int64), want.view(torch.int64))
     assert _ENGINES[key] is small and small.isect_cap > 3000

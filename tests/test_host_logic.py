@@ -548,3 +548,75 @@ def test_no_module_imports_a_private_name_from_a_sibling():
             if isinstance(node, ast.ImportFrom) and node.level == 1 and node.module not in (None, "_lib", "_views"):
                 found += [(name, node.module, a.name) for a in node.names if a.name.startswith("_")]
     assert not found, found
+
+
+def _parent_route(D, dtype, table_grad, gauss_grad, camera, m2d, grad_mode, zero):
+    """The oracle of the route test: the expressions rasterization.py held in two places before _route, copied.  Step 1 is the
+    per-camera loop of rasterization(), step 2 _Rasterize.forward, which saw the Gaussian tensors' requires_grad through
+    needs_input_grad -- whatever the grad mode -- and the loop's harvest verdict as an argument."""
+    def geometry_path(needs):
+        return bool(any(needs)) and D <= 32 and dtype == torch.float32
+    gauss = [gauss_grad, False, False, False]  # (requires_grad of means, quats, scales, opacities)
+    # step 1
+    geo = grad_mode and geometry_path(gauss + [camera, m2d])
+    harvest = bool(table_grad and not geo and zero)
+    # step 2
+    needs = (table_grad,) + tuple(gauss) + (camera, False)  # (a camera call's viewmats require grad)
+    camera_grad = bool(camera and needs[5])
+    geo = geometry_path(tuple(needs[1:5]) + (camera_grad, m2d))
+    need_store = (table_grad and not geo) or D > 16
+    narrow = not (table_grad and D % 256 == 0)
+    harvest = harvest and not geo
+    want_alphas = D > 16 or harvest
+    render = "zero" if harvest else ("pixels" if D <= 16 else "wide")
+    return (geo, camera_grad, harvest, need_store, narrow, want_alphas, render)
+
+
+def test_route_reproduces_both_of_the_parents_computations_over_the_full_product():
+    import itertools
+    from gsbp_amd.rasterization import _route
+    yes_no = (True, False)
+    seen = 0
+    for D, dtype, table_grad, gauss_grad, camera, m2d, grad_mode, zero in itertools.product(
+            (1, 3, 16, 17, 32, 33, 256, 512), (torch.float32, torch.float16), yes_no, yes_no, yes_no, yes_no, yes_no, yes_no):
+        # what rasterization() rejects at the call: a half table that requires grad, and camera or means2d beside a table the blend
+        # backward does not read
+        if (dtype == torch.float16 and table_grad) or ((camera or m2d) and (D > 32 or dtype != torch.float32)):
+            continue
+        seen += 1
+        asked = []
+        got = _route(D, dtype, table_grad, gauss_grad, camera, m2d, lambda: asked.append(1) or zero)
+        want = _parent_route(D, dtype, table_grad, gauss_grad, camera, m2d, grad_mode, zero)
+        assert tuple(got) == want and got._fields == ("geo", "camera", "harvest", "need_store", "narrow", "want_alphas", "render"), \
+            (D, dtype, table_grad, gauss_grad, camera, m2d, grad_mode, zero, got, want)
+        # the zero-table verdict (a reduction and a host synchronisation) is asked for once where it decides something, else never
+        assert len(asked) == (1 if table_grad and not got.geo else 0)
+    # 1024 combinations; 256 are half tables that require grad; of the other 768, camera or means2d (3 of 4) sit beside a float32
+    # table wider than 32 in 3 * 2 * 2 * 3 * 2 * 2 = 144 and beside a float16 one in 8 * 2 * 3 * 2 * 2 = 192
+    assert seen == 1024 - 256 - 144 - 192 == 432
+    # the no_grad corner: Gaussian tensors that require grad and a zero table that requires grad, under torch.no_grad().  The parent's
+    # loop said "harvest", its forward "geometry path": the pixel render from the sorted lists, no weight store, no zero render
+    def never():
+        raise AssertionError("the zero-table verdict was computed where the parent threw it away")
+    corner = _route(3, torch.float32, True, True, False, False, never)
+    assert tuple(corner) == _parent_route(3, torch.float32, True, True, False, False, False, True) == \
+        (True, False, False, False, True, False, "pixels")
+
+
+def test_view_schedule_draws_what_the_literal_loop_drew():
+    from gsbp_amd.polish import view_schedule
+    n_views = 5
+    for seed in (0, 1, 7):
+        gen = torch.Generator().manual_seed(seed)
+        want, order = [], []
+        for _ in range(3 * n_views):
+            if not order:
+                order = torch.randperm(n_views, generator=gen).tolist()
+            want.append(order.pop(0))
+        assert list(view_schedule(n_views, seed, 3 * n_views)) == want
+        assert all(sorted(want[i:i + n_views]) == list(range(n_views)) for i in range(0, 3 * n_views, n_views))
+        # a caller's own generator (fit_decoded_field draws its decoder from it first): the draws continue where it stands
+        gen, mine = torch.Generator().manual_seed(seed), torch.Generator().manual_seed(seed)
+        torch.rand(4, generator=gen), torch.rand(4, generator=mine)
+        first, second = [torch.randperm(n_views, generator=gen).tolist() for _ in range(2)]
+        assert list(view_schedule(n_views, mine, 7)) == first + second[:2]

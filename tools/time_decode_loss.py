@@ -116,11 +116,10 @@ def main():
         view = eng.view(vms[step], K, W, H)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(stages) + 1)]
         ev[0].record()
-        eng.front_cache = None
         eng.project(view, *gauss)
         eng.bin_sort(view)
         eng.blend_weights(view)
-        eng.generation += 1
+        eng.holds_new_view()
         ev[1].record()
         rendered = eng.render(view, latents.detach())
         ev[2].record()

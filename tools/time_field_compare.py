@@ -94,11 +94,10 @@ def main():
         peak, last = {}, {}
         for v in range(a.views + a.warmup):
             view = eng.view(vms[v], K, W, H)
-            eng.front_cache = None
             eng.project(view, *gauss)
             eng.bin_sort(view)
             eng.blend_weights(view)
-            eng.generation += 1
+            eng.holds_new_view()
             state["view"] = view
             for i in range(len(names)):
                 name = names[(i + v) % len(names)]

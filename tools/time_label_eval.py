@@ -76,7 +76,7 @@ def main():
             view = eng.view(vm_host[v], K_host, W, H)
             eng.project(view, *gauss)
             eng.bin_sort(view)
-            eng.generation += 1
+            eng.holds_new_view()
             return eng.render_labels(view, labels, k, want_maps=maps, want_alphas=maps, gt=gts[v], cut=a.cut)[3]
 
         def one_hot_torch(v):
