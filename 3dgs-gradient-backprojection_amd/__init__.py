@@ -43,6 +43,8 @@ JojiJoseph/3dgs-gradient-backprojection), hand-written HIP kernels behind a C AB
     from gsbp_amd import train_scene, densify, DensifyState, DensifyConfig, reset_opacity, init_splats_from_points  # and of a set
                                                     # that grows and shrinks: rasterization(means2d_grad=True), gsplat's default
                                                     # densification rule as HIP plan / emit / gather kernels
+    from gsbp_amd import MCMCConfig, relocate, sample_add, inject_noise  # or under a fixed budget: gsplat's MCMC strategy
+                                                    # (train_scene(strategy=MCMCConfig(cap_max=...))), HIP plan / draw / update / move
 """
 from . import synthetic  # noqa: F401
 from ._lib import GwbpError, build, lib  # noqa: F401
@@ -82,4 +84,6 @@ from . import polish  # noqa: F401
 from .polish import polish_scene, score_image_views  # noqa: F401
 # (gsbp_amd.densify is the function, as gsbp_amd.rasterization is; the module is reached as `from gsbp_amd.densify import ...`)
 from .densify import DensifyConfig, DensifyState, densify, init_splats_from_points, reset_opacity, train_scene  # noqa: F401
+from . import mcmc  # noqa: F401
+from .mcmc import MCMCConfig, inject_noise, relocate, sample_add  # noqa: F401
 from .pruning import check_proper_pruning, gradient_mask, prune_by_gradients  # noqa: F401

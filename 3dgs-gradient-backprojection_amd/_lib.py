@@ -262,6 +262,14 @@ ARGTYPES = {
     "gwbp_densify_plan": [_I64, _P, _P, _P, _I64, _P, _F, _F, _F, _F, _F, _I32, _P, _P, _P, _SZ, _P],
     "gwbp_densify_emit": [_I64, _I64, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P],
     "gwbp_densify_gather": [_I64, _I64, _I32, _P, _I64, _P, _P, _P, _I32, _P, _I64, _P],
+    "gwbp_mcmc_plan_workspace_size": [_I64, C.POINTER(C.c_size_t)],
+    "gwbp_mcmc_plan": [_I64, _P, _F, _I32, _P, _P, _P, _P, _SZ, _P],
+    "gwbp_mcmc_draw": [_I64, _I64, _P, _P, _P, _P],
+    "gwbp_mcmc_update": [_I64, _I64, _P, _F, _P, _P, _I64, _P, _P],
+    "gwbp_mcmc_move": [_I64, _I64, _I32, _P, _P, _P, _I64, _P],
+    "gwbp_mcmc_zero_rows": [_I64, _I32, _P, _P, _I64, _P],
+    "gwbp_mcmc_noise": [_I64, _P, _P, _P, _P, _P, _F, _P],
+    "gwbp_mcmc_libm": [_I64, _I32, _P, _P, _P, _P],
 }
 # The typed forms of the entry points that read a finished [N, D] FIELD (or, gwbp_finalize_typed, write one): the untyped function's
 # arguments with the field's element type (GWBP_MAP_*, MAP_TYPES' codes) behind the field pointer.  A table of their own: they take no
@@ -297,6 +305,9 @@ DENSIFY_KINDS = {"pruned": 0, "keep": 1, "clone": 2, "split": 3}  # GWBP_DENSIFY
 DENSIFY_MODES = {"copy": 0, "zero_new": 1}  # GWBP_DENSIFY_COPY / _ZERO_NEW
 DENSIFY_BLOCK = 256  # GWBP_DENSIFY_BLOCK: the Gaussians of one workgroup of the plan's scan
 DENSIFY_MAX_WIDTH = 65536  # GWBP_DENSIFY_MAX_WIDTH
+MCMC_MODES = {"relocate": 0, "add": 1}  # GWBP_MCMC_RELOCATE / _ADD
+MCMC_MAX_RATIO = 51  # GWBP_MCMC_MAX_RATIO
+MCMC_LIBM = {"exp": 0, "log": 1, "pow": 2}  # GWBP_MCMC_LIBM_*
 # every symbol of include/gwbp.h: the two functions that return strings, then the int-returning ones declared above
 EXPORTS = ["gwbp_version", "gwbp_last_error_string", *ARGTYPES, *FIELD_ARGTYPES]
 

@@ -2187,6 +2187,140 @@ int gwbp_densify_gather(int64_t n, int64_t n_out, int32_t w, const float *table,
     return launch_densify_gather(n, n_out, w, table, ldt, parent, child, kind, mode == GWBP_DENSIFY_ZERO_NEW, out, ldo, as_stream(stream));
 }
 
+// ---- the MCMC strategy (mcmc.hip) ----------------------------------------------------------------------------------------------------
+static int check_mcmc_counts(const char *what, int64_t n, int64_t m)
+{
+    if (int rc = check_densify_count(what, n))
+        return rc;
+    if (m < 0 || m > 0x7FFFFFFF)
+        return set_error(GWBP_EINVAL, "%s: bad number of draws (%lld): 0 .. 2^31 - 1", what, (long long)m);
+    return GWBP_OK;
+}
+
+static int check_mcmc_table(const char *what, int32_t w, int64_t ldt)
+{
+    if (w < 1 || w > GWBP_DENSIFY_MAX_WIDTH)
+        return set_error(GWBP_EINVAL, "%s: w must be in [1, %d] (got %d)", what, GWBP_DENSIFY_MAX_WIDTH, (int)w);
+    if (ldt < w)
+        return set_error(GWBP_EINVAL, "%s: row stride %lld below w = %d", what, (long long)ldt, (int)w);
+    return GWBP_OK;
+}
+
+int gwbp_mcmc_plan_workspace_size(int64_t n, size_t *bytes)
+{
+    if (int rc = check_densify_count("mcmc_plan_workspace_size", n))
+        return rc;
+    if (!bytes)
+        return set_error(GWBP_EINVAL, "mcmc_plan_workspace_size: null bytes");
+    *bytes = mcmc_plan_workspace_bytes(n);
+    return GWBP_OK;
+}
+
+int gwbp_mcmc_plan(int64_t n, const float *opacity, float t_opa, int32_t mode, int64_t *cdf, int64_t *dead_offsets, int32_t *dead_idx,
+                   void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (int rc = check_densify_count("mcmc_plan", n))
+        return rc;
+    if (mode != GWBP_MCMC_RELOCATE && mode != GWBP_MCMC_ADD)
+        return set_error(GWBP_EINVAL, "mcmc_plan: unknown mode %d", (int)mode);
+    if (!cdf || !dead_offsets || !workspace || (n > 0 && (!opacity || !dead_idx)))
+        return set_error(GWBP_EINVAL, "mcmc_plan: null opacity, cdf, dead_offsets, dead_idx or workspace");
+    if (misaligned(opacity, 3) || misaligned(dead_idx, 3))
+        return set_error(GWBP_EINVAL, "mcmc_plan: opacity and dead_idx must be 4-B aligned");
+    if (misaligned(cdf, 7) || misaligned(dead_offsets, 7) || misaligned(workspace, 7))
+        return set_error(GWBP_EINVAL, "mcmc_plan: cdf, dead_offsets and workspace must be 8-B aligned");
+    if (cdf == dead_offsets)
+        return set_error(GWBP_EINVAL, "mcmc_plan: cdf and dead_offsets are the same array");
+    const size_t need = mcmc_plan_workspace_bytes(n);
+    if (workspace_bytes < need)
+        return set_error(GWBP_EWORKSPACE, "mcmc_plan: workspace has %zu bytes, needs %zu", workspace_bytes, need);
+    return launch_mcmc_plan(n, opacity, t_opa, mode == GWBP_MCMC_ADD, cdf, dead_offsets, dead_idx, workspace, as_stream(stream));
+}
+
+int gwbp_mcmc_draw(int64_t n, int64_t m, const int64_t *cdf, const double *u, int32_t *parent, void *stream)
+{
+    if (int rc = check_mcmc_counts("mcmc_draw", n, m))
+        return rc;
+    if (m > 0 && (!cdf || !u || !parent))
+        return set_error(GWBP_EINVAL, "mcmc_draw: null cdf, u or parent");
+    if (misaligned(cdf, 7) || misaligned(u, 7))
+        return set_error(GWBP_EINVAL, "mcmc_draw: cdf and u must be 8-B aligned");
+    if (misaligned(parent, 3))
+        return set_error(GWBP_EINVAL, "mcmc_draw: parent must be 4-B aligned");
+    return launch_mcmc_draw(n, m, cdf, u, parent, as_stream(stream));
+}
+
+int gwbp_mcmc_update(int64_t n, int64_t m, const int32_t *parent, float min_opacity, float *opacity, float *scaling, int64_t lds_,
+                     int32_t *count, void *stream)
+{
+    if (int rc = check_mcmc_counts("mcmc_update", n, m))
+        return rc;
+    if (!(min_opacity > 0.0f && min_opacity < 1.0f))
+        return set_error(GWBP_EINVAL, "mcmc_update: min_opacity must be in (0, 1) (got %g)", (double)min_opacity);
+    if (lds_ < 3)
+        return set_error(GWBP_EINVAL, "mcmc_update: row stride %lld of scaling below 3", (long long)lds_);
+    if ((n > 0 && (!opacity || !scaling || !count)) || (n > 0 && m > 0 && !parent))
+        return set_error(GWBP_EINVAL, "mcmc_update: null parent, opacity, scaling or count");
+    if (misaligned(parent, 3) || misaligned(opacity, 3) || misaligned(scaling, 3) || misaligned(count, 3))
+        return set_error(GWBP_EINVAL, "mcmc_update: parent, opacity, scaling and count must be 4-B aligned");
+    return launch_mcmc_update(n, m, parent, min_opacity, opacity, scaling, lds_, count, as_stream(stream));
+}
+
+int gwbp_mcmc_move(int64_t n, int64_t m, int32_t w, const int32_t *parent, const int32_t *dead_idx, float *table, int64_t ldt, void *stream)
+{
+    if (int rc = check_mcmc_counts("mcmc_move", n, m))
+        return rc;
+    if (int rc = check_mcmc_table("mcmc_move", w, ldt))
+        return rc;
+    if (n > 0 && m > 0 && (!parent || !dead_idx || !table))
+        return set_error(GWBP_EINVAL, "mcmc_move: null parent, dead_idx or table");
+    if (misaligned(parent, 3) || misaligned(dead_idx, 3) || misaligned(table, 3))
+        return set_error(GWBP_EINVAL, "mcmc_move: parent, dead_idx and table must be 4-B aligned");
+    return launch_mcmc_move(n, m, w, parent, dead_idx, table, ldt, as_stream(stream));
+}
+
+int gwbp_mcmc_zero_rows(int64_t n, int32_t w, const int32_t *count, float *table, int64_t ldt, void *stream)
+{
+    if (int rc = check_densify_count("mcmc_zero_rows", n))
+        return rc;
+    if (int rc = check_mcmc_table("mcmc_zero_rows", w, ldt))
+        return rc;
+    if (n > 0 && (!count || !table))
+        return set_error(GWBP_EINVAL, "mcmc_zero_rows: null count or table");
+    if (misaligned(count, 3) || misaligned(table, 3))
+        return set_error(GWBP_EINVAL, "mcmc_zero_rows: count and table must be 4-B aligned");
+    return launch_mcmc_zero_rows(n, w, count, table, ldt, as_stream(stream));
+}
+
+int gwbp_mcmc_noise(int64_t n, float *means, const float *scaling, const float *rotation, const float *opacity, const float *z, float scaler,
+                    void *stream)
+{
+    if (int rc = check_densify_count("mcmc_noise", n))
+        return rc;
+    if (n > 0 && (!means || !scaling || !rotation || !opacity || !z))
+        return set_error(GWBP_EINVAL, "mcmc_noise: null means, scaling, rotation, opacity or z");
+    if (misaligned(means, 3) || misaligned(scaling, 3) || misaligned(rotation, 3) || misaligned(opacity, 3) || misaligned(z, 3))
+        return set_error(GWBP_EINVAL, "mcmc_noise: the tables must be 4-B aligned");
+    const void *const written[] = {means}, *const read[] = {scaling, rotation, opacity, z};
+    if (n > 0)
+        if (int rc = check_regions_distinct("mcmc_noise", written, 1, read, 4))
+            return rc;
+    return launch_mcmc_noise(n, means, scaling, rotation, opacity, z, scaler, as_stream(stream));
+}
+
+int gwbp_mcmc_libm(int64_t n, int32_t op, const float *a, const float *b, float *out, void *stream)
+{
+    if (int rc = check_densify_count("mcmc_libm", n))
+        return rc;
+    if (op != GWBP_MCMC_LIBM_EXP && op != GWBP_MCMC_LIBM_LOG && op != GWBP_MCMC_LIBM_POW)
+        return set_error(GWBP_EINVAL, "mcmc_libm: unknown op %d", (int)op);
+    if (n > 0 && (!a || !out || (op == GWBP_MCMC_LIBM_POW && !b)))
+        return set_error(GWBP_EINVAL, "mcmc_libm: null a, out (or b under GWBP_MCMC_LIBM_POW)");
+    if (misaligned(a, 3) || misaligned(b, 3) || misaligned(out, 3))
+        return set_error(GWBP_EINVAL, "mcmc_libm: a, b and out must be 4-B aligned");
+    return launch_mcmc_libm(n, op, a, b, out, as_stream(stream));
+}
+
 int gwbp_accumulate_stats(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, gwbp_stats *accum,
                           void *stream)
 {

@@ -6,8 +6,8 @@
 //                         visible.  One pass over [C, N, 2] + [C, N]; the per-step hot path.
 //   k_densify_plan        a lane per Gaussian: kind (pruned, keep, clone, split) and rows out (0, 1, 2, 2); the workgroup's exclusive scan
 //                         of the rows (wave scan by shuffles, the four wave totals through LDS) goes to offsets, its total to sums[block].
-//   k_densify_scan_blocks ONE workgroup walks sums in chunks of 256 in ascending order with a running carry: sums becomes its own
-//                         exclusive scan, offsets[N] the grand total.
+//   k_scan_block_sums     (block_scan.h, shared with mcmc.hip) ONE workgroup walks sums in chunks of 256 in ascending order with a
+//                         running carry: sums becomes its own exclusive scan, offsets[N] the grand total.
 //   k_densify_add         offsets[i] += sums[i / 256].
 //   k_densify_emit        a lane per parent: its 0, 1 or 2 children at offsets[p], in parent order.
 //   k_densify_gather      out[r, :] = table[parent[r], :], lanes along the rows of a workgroup's RB consecutive output rows (the RB
@@ -19,6 +19,7 @@
 // offsets array that does not belong to n_out, or a parent outside [0, n), writes nothing out of bounds (emit drops the row, gather writes
 // a zero row).
 #include "gwbp_dev.h"
+#include "block_scan.h"
 #include "densify_math.h"
 
 namespace gwbp {
@@ -46,26 +47,6 @@ __global__ __launch_bounds__(256) void k_densify_accumulate(int64_t N, int C, co
     grad2d[i] = g, count[i] = n;
 }
 
-// exclusive scan of one value per thread over the workgroup; *total: the workgroup's sum, the same in every thread
-template <typename T> __device__ __forceinline__ T block_exclusive(T v, T *wave_tot, T *total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    T incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T up = __shfl_up(incl, o, 64);
-        if (lane >= o)
-            incl += up;
-    }
-    if (lane == 63)
-        wave_tot[wave] = incl;
-    __syncthreads();
-    const T t0 = wave_tot[0], t1 = wave_tot[1], t2 = wave_tot[2], t3 = wave_tot[3];
-    *total = ((t0 + t1) + t2) + t3;
-    const T before = wave == 0 ? (T)0 : wave == 1 ? t0 : wave == 2 ? t0 + t1 : (t0 + t1) + t2;
-    return before + (incl - v);
-}
-
 __global__ __launch_bounds__(256) void k_densify_plan(int64_t N, const float *__restrict__ grad2d, const float *__restrict__ count,
                                                       const float *__restrict__ scaling, int64_t lds_, const float *__restrict__ opacity,
                                                       DensifyThresholds T, uint8_t *__restrict__ kind, int64_t *__restrict__ offsets,
@@ -86,24 +67,6 @@ __global__ __launch_bounds__(256) void k_densify_plan(int64_t N, const float *__
         offsets[i] = before;
     if (threadIdx.x == 0)
         sums[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(256) void k_densify_scan_blocks(int64_t n_blocks, int64_t *__restrict__ sums, int64_t *__restrict__ grand)
-{
-    __shared__ long long wave_tot[4];
-    long long carry = 0;
-    for (int64_t b0 = 0; b0 < n_blocks; b0 += kBlock) {
-        const int64_t b = b0 + threadIdx.x;
-        const long long v = b < n_blocks ? (long long)sums[b] : 0;
-        long long total;
-        const long long before = block_exclusive<long long>(v, wave_tot, &total);
-        if (b < n_blocks)
-            sums[b] = carry + before;
-        carry += total;
-        __syncthreads(); // the wave totals are read; the next chunk may write them
-    }
-    if (threadIdx.x == 0)
-        *grand = carry;
 }
 
 __global__ __launch_bounds__(256) void k_densify_add(int64_t N, const int64_t *__restrict__ sums, int64_t *__restrict__ offsets)
@@ -224,7 +187,7 @@ int launch_densify_plan(int64_t N, const float *grad2d, const float *count, cons
     T.prune_big = prune_big != 0;
     if (grid > 0)
         hipLaunchKernelGGL(k_densify_plan, dim3(grid), dim3(kBlock), 0, s, N, grad2d, count, scaling, lds_, opacity, T, kind, offsets, sums);
-    hipLaunchKernelGGL(k_densify_scan_blocks, dim3(1), dim3(kBlock), 0, s, (int64_t)grid, sums, offsets + N);
+    hipLaunchKernelGGL(k_scan_block_sums, dim3(1), dim3(kBlock), 0, s, (int64_t)grid, sums, offsets + N);
     if (grid > 0)
         hipLaunchKernelGGL(k_densify_add, dim3(grid), dim3(kBlock), 0, s, N, sums, offsets);
     return check_hip(hipGetLastError(), "densify_plan launch");

@@ -339,6 +339,20 @@ int launch_densify_emit(int64_t N, int64_t n_out, const uint8_t *kind, const int
                         float *o_means, float *o_scaling, float *o_rotation, float *o_opacity, hipStream_t s);
 int launch_densify_gather(int64_t N, int64_t n_out, int w, const float *table, int64_t ldt, const int32_t *parent, const uint8_t *child,
                           const uint8_t *kind, int zero_new, float *out, int64_t ldo, hipStream_t s);
+// the MCMC strategy (mcmc.hip): the plan (integer weights and dead flags, their exclusive scans and the compaction of the dead; ws: the
+// caller's mcmc_plan_workspace_bytes(N) bytes), the draws, the parents' new opacity and scale, the in-place move of a [N, w] table's
+// dead rows, the zeroing of the parents' rows, the per-step noise, and the device's expf / logf / powf for the tests
+size_t mcmc_plan_workspace_bytes(int64_t n);
+int launch_mcmc_plan(int64_t N, const float *opacity, float t_opa, int add_mode, int64_t *cdf, int64_t *dead_offsets, int32_t *dead_idx,
+                     void *ws, hipStream_t s);
+int launch_mcmc_draw(int64_t N, int64_t M, const int64_t *cdf, const double *u, int32_t *parent, hipStream_t s);
+int launch_mcmc_update(int64_t N, int64_t M, const int32_t *parent, float min_opacity, float *opacity, float *scaling, int64_t lds_,
+                       int32_t *count, hipStream_t s);
+int launch_mcmc_move(int64_t N, int64_t M, int w, const int32_t *parent, const int32_t *dead_idx, float *table, int64_t ldt, hipStream_t s);
+int launch_mcmc_zero_rows(int64_t N, int w, const int32_t *count, float *table, int64_t ldt, hipStream_t s);
+int launch_mcmc_noise(int64_t N, float *means, const float *scaling, const float *rotation, const float *opacity, const float *z,
+                      float scaler, hipStream_t s);
+int launch_mcmc_libm(int64_t N, int op, const float *a, const float *b, float *out, hipStream_t s);
 int launch_encode_map(const float *feats, int64_t fs_y, int64_t fs_x, int H, int W, int K, const float *enc, int n_out,
                       float *out, int workgroups, hipStream_t s);
 // ot (GWBP_MAP_*): the element type of out; a half out is the fp32 result rounded once to nearest even

@@ -16,8 +16,9 @@ means, scales, rotations and opacities, children adjacent, in parent order) and 
 moments among them.  One host read per round: the size of the new set.  Splat dicts carry the reference's key names, pre-activation
 (polish.py).  There is no PyTorch fallback: CPU tensors raise GwbpError.
 
-Not offered: absgrad, the radius criteria (grow_scale2d, prune_scale2d, refine_scale2d_stop_iter), revised_opacity, MCMC relocation,
-packed mode.
+Not offered: absgrad, the radius criteria (grow_scale2d, prune_scale2d, refine_scale2d_stop_iter), revised_opacity, packed mode.
+gsplat's other strategy, MCMCStrategy, is mcmc.py; train_scene(strategy=MCMCConfig(...)) runs it (without packed mode and sparse
+gradients).
 """
 from __future__ import annotations
 
@@ -39,7 +40,7 @@ GEOMETRY_KEYS = ("means", "scaling", "rotation", "opacity")  # what the emit ker
 SH_C0 = 0.28209479177387814
 
 
-def _f32(x: float) -> float:
+def f32(x: float) -> float:
     """x rounded to float32 once (the thresholds are computed in float64 on the host)."""
     return C.c_float(x).value
 
@@ -81,9 +82,9 @@ class DensifyConfig:
     def thresholds(self) -> Tuple[float, float, float, float, float]:
         """(t_grad, t_small, t_big, t_opa, log16): every comparison of the plan happens in pre-activation space, so the thresholds
         are what moves -- float64 here, rounded to float32 once."""
-        return (_f32(self.grow_grad2d), _f32(math.log(self.grow_scale3d * self.scene_scale)),
-                _f32(math.log(self.prune_scale3d * self.scene_scale)), _f32(math.log(self.prune_opa / (1.0 - self.prune_opa))),
-                _f32(math.log(1.6)))
+        return (f32(self.grow_grad2d), f32(math.log(self.grow_scale3d * self.scene_scale)),
+                f32(math.log(self.prune_scale3d * self.scene_scale)), f32(math.log(self.prune_opa / (1.0 - self.prune_opa))),
+                f32(math.log(1.6)))
 
     def refines_at(self, step: int) -> bool:
         return (step < self.refine_stop_iter and step > self.refine_start_iter and step % self.refine_every == 0
@@ -93,7 +94,7 @@ class DensifyConfig:
         return 0 < step < self.refine_stop_iter and step % self.reset_every == 0
 
 
-def _device_f32(t, name: str, tail=None) -> torch.Tensor:
+def device_f32(t, name: str, tail=None) -> torch.Tensor:
     if not torch.is_tensor(t) or not t.is_cuda:
         raise GwbpError(f"{name} must be a HIP tensor (there is no CPU path)")
     if t.dtype != torch.float32:
@@ -127,12 +128,12 @@ class DensifyState:
         if tuple(g.shape) != (n_cam, self.n, 2) or tuple(radii.shape) != (n_cam, self.n) or radii.dtype != torch.int32:
             raise GwbpError(f"the state holds {self.n} Gaussians; meta has means2d.grad {tuple(g.shape)} and {radii.dtype} radii "
                             f"{tuple(radii.shape)} of {n_cam} cameras")
-        g, radii = _device_f32(g, "means2d.grad"), radii.contiguous()
+        g, radii = device_f32(g, "means2d.grad"), radii.contiguous()
         run("gwbp_densify_accumulate", self.device, C.c_int64(self.n), n_cam, ptr(g), ptr(radii),
             C.c_float(float(meta["width"]) / 2.0 * n_cam), C.c_float(float(meta["height"]) / 2.0 * n_cam), ptr(self.grad2d), ptr(self.count))
 
 
-def _as_rows(t: torch.Tensor, n: int) -> torch.Tensor:
+def as_rows(t: torch.Tensor, n: int) -> torch.Tensor:
     """A per-Gaussian float32 tensor as the [n, w] table the gather kernel reads: a view where the layout allows it."""
     if t.dim() == 2 and (t.shape[1] <= 1 or t.stride(1) == 1) and (n <= 1 or t.stride(0) >= t.shape[1]):
         return t
@@ -152,7 +153,7 @@ def gather_rows(table: torch.Tensor, parent: torch.Tensor, n: int, child=None, k
     w = int(math.prod(table.shape[1:]))
     if n_out == 0 or w == 0:
         return out
-    rows = _as_rows(table, n)
+    rows = as_rows(table, n)
     run("gwbp_densify_gather", table.device, C.c_int64(n), C.c_int64(n_out), int(w), ptr(rows), C.c_int64(ld(rows)), ptr(parent),
         ptr(child), ptr(kind), _lib.DENSIFY_MODES[mode], ptr(out), C.c_int64(w))
     return out
@@ -161,8 +162,8 @@ def gather_rows(table: torch.Tensor, parent: torch.Tensor, n: int, child=None, k
 def plan(grad2d, count, scaling, opacity, thresholds: Sequence[float], prune_big: bool):
     """(kind uint8 [n], offsets int64 [n + 1]) of gwbp_densify_plan: what becomes of each Gaussian (0 pruned, 1 keep, 2 clone, 3 split)
     and the exclusive scan of the rows it leaves behind; offsets[n] is the size of the new set.  No host read."""
-    scaling, opacity = _device_f32(scaling, "scaling", (3,)), _device_f32(opacity, "opacity", ())
-    grad2d, count = _device_f32(grad2d, "grad2d", ()), _device_f32(count, "count", ())
+    scaling, opacity = device_f32(scaling, "scaling", (3,)), device_f32(opacity, "opacity", ())
+    grad2d, count = device_f32(grad2d, "grad2d", ()), device_f32(count, "count", ())
     n, dev = scaling.shape[0], scaling.device
     if not (opacity.shape[0] == grad2d.shape[0] == count.shape[0] == n):
         raise GwbpError(f"{n} scaling rows, {opacity.shape[0]} opacities and statistics of {grad2d.shape[0]} Gaussians")
@@ -179,10 +180,10 @@ def plan(grad2d, count, scaling, opacity, thresholds: Sequence[float], prune_big
 
 def emit(kind, offsets, n_out: int, means, scaling, rotation, opacity, noise, log16: float):
     """The new set's geometry (gwbp_densify_emit): dict(parent int32 [n_out], child uint8 [n_out], means, scaling, rotation, opacity)."""
-    means, scaling = _device_f32(means, "means", (3,)), _device_f32(scaling, "scaling", (3,))
-    rotation, opacity = _device_f32(rotation, "rotation", (4,)), _device_f32(opacity, "opacity", ())
+    means, scaling = device_f32(means, "means", (3,)), device_f32(scaling, "scaling", (3,))
+    rotation, opacity = device_f32(rotation, "rotation", (4,)), device_f32(opacity, "opacity", ())
     n, dev = means.shape[0], means.device
-    noise = _device_f32(noise, "noise", (2, 3))
+    noise = device_f32(noise, "noise", (2, 3))
     if not (scaling.shape[0] == rotation.shape[0] == opacity.shape[0] == noise.shape[0] == kind.shape[0] == n and offsets.shape[0] == n + 1):
         raise GwbpError(f"emit: the tables of {n} Gaussians do not agree in their first dimension")
     out = dict(parent=torch.empty(n_out, dtype=torch.int32, device=dev), child=torch.empty(n_out, dtype=torch.uint8, device=dev),
@@ -254,8 +255,9 @@ def densify(splats: Dict[str, torch.Tensor], state: DensifyState, cfg: DensifyCo
     return out, info
 
 
-def _relocate_adam(optimizer, old: Dict, new: Dict, parent, child, kind, n: int) -> None:
-    """Swap the optimiser's parameters for the new set's leaves and carry the Adam moments over (zero_new)."""
+def swap_adam_leaves(optimizer, old: Dict, new: Dict, moments: Callable[[torch.Tensor], torch.Tensor]) -> None:
+    """Swap the optimiser's parameters for the new set's leaves (densify, mcmc.sample_add): every group must hold one tensor of `old`;
+    new[key] becomes a leaf and takes the group, the Adam moments follow as moments(table), `step` is kept."""
     if not isinstance(optimizer, torch.optim.Adam):
         raise GwbpError(f"densify() relocates the state of torch.optim.Adam, got {type(optimizer).__name__}")
     by_id = {id(t): k for k, t in old.items() if torch.is_tensor(t)}
@@ -270,10 +272,15 @@ def _relocate_adam(optimizer, old: Dict, new: Dict, parent, child, kind, n: int)
         group["params"][0] = leaf
         if st:
             for name in ("exp_avg", "exp_avg_sq"):
-                st[name] = gather_rows(st[name], parent, n, child, kind, "zero_new")
+                st[name] = moments(st[name])
             if "max_exp_avg_sq" in st:
-                st["max_exp_avg_sq"] = gather_rows(st["max_exp_avg_sq"], parent, n, child, kind, "zero_new")
+                st["max_exp_avg_sq"] = moments(st["max_exp_avg_sq"])
             optimizer.state[leaf] = st
+
+
+def _relocate_adam(optimizer, old: Dict, new: Dict, parent, child, kind, n: int) -> None:
+    """Swap the optimiser's parameters for the new set's leaves and carry the Adam moments over (zero_new)."""
+    swap_adam_leaves(optimizer, old, new, lambda t: gather_rows(t, parent, n, child, kind, "zero_new"))
 
 
 def reset_opacity(splats: Dict[str, torch.Tensor], optimizer, cfg: DensifyConfig) -> Dict[str, torch.Tensor]:
@@ -292,7 +299,8 @@ def reset_opacity(splats: Dict[str, torch.Tensor], optimizer, cfg: DensifyConfig
 
 def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, image_fn: Callable[[int], torch.Tensor], steps: int,
                 cfg: Optional[DensifyConfig] = None, params: Sequence[str] = tuple(PARAM_KEYS), lrs: Optional[Dict[str, float]] = None,
-                seed: int = 0, ssim_lambda: float = 0.2, carry: Optional[Dict[str, torch.Tensor]] = None, **raster_kw):
+                seed: int = 0, ssim_lambda: float = 0.2, carry: Optional[Dict[str, torch.Tensor]] = None, strategy=None,
+                opacity_reg: float = 0.0, scale_reg: float = 0.0, **raster_kw):
     """polish_scene's loop with the schedule: Adam on the named parameters under the photometric loss, the set growing and shrinking
     on the way.  Step s (from 0) renders one view with means2d_grad=True, runs the backward, adds the view into the statistics while
     s < refine_stop_iter, steps the optimiser, runs a densify round when s > refine_start_iter, s % refine_every == 0 and
@@ -301,8 +309,22 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
     Returns (the trained splat dict, history): history = dict(loss = the steps' losses, read once behind the loop; n = the number
     of Gaussians each step rendered; rounds = one dict per densify round: step, n_before, n_after, pruned, kept, cloned, split;
     resets = the steps of the opacity resets; carry = the relocated `carry` tables).
-    The view of a step and the split noise come from seeded generators: the same call gives the same schedule of rounds."""
-    cfg = cfg if cfg is not None else DensifyConfig()
+    The view of a step and the split noise come from seeded generators: the same call gives the same schedule of rounds.
+    strategy: None or a DensifyConfig (the same as cfg=) runs the loop above; an mcmc.MCMCConfig runs gsplat's MCMCStrategy instead:
+    no means2d gradient, no statistics and no opacity reset; after the optimiser step a relocate round and an add round when
+    refine_start_iter < s < refine_stop_iter and s % refine_every == 0, and noise on the means at EVERY step, scaled by the means
+    group's current learning rate (none when the means are not trained).  history["rounds"] then holds step, n_before, n_after,
+    relocated, added.
+    opacity_reg, scale_reg: weights of mean(sigmoid(opacity)) and mean(exp(scaling)), added to the loss when they are not zero (the
+    reference's mcmc configuration sets both to 0.01)."""
+    from .mcmc import MCMCConfig, inject_noise, relocate, sample_add
+    if strategy is not None and cfg is not None:
+        raise GwbpError("train_scene() takes cfg= or strategy=, not both")
+    if strategy is not None and not isinstance(strategy, (DensifyConfig, MCMCConfig)):
+        raise GwbpError(f"strategy must be None, a DensifyConfig or an MCMCConfig, got {type(strategy).__name__}")
+    mcmc = strategy if isinstance(strategy, MCMCConfig) else None
+    cfg = strategy if isinstance(strategy, DensifyConfig) else cfg if cfg is not None else DensifyConfig()
+    opacity_reg, scale_reg = float(opacity_reg), float(scale_reg)
     work, opt = trainable(splats, params, lrs, "train_scene")
     dev, width, height = splats["means"].device, int(width), int(height)
     for key in GEOMETRY_KEYS:  # what the rounds write must be float32 whether it is trained or not
@@ -313,14 +335,34 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
     losses, sizes, rounds, resets = [], [], [], []
     for step, v in enumerate(view_schedule(viewmats.shape[0], seed, steps)):
         opt.zero_grad(set_to_none=True)
-        image, meta = render_splats(work, viewmats[v], view_K(K, v), width, height, return_meta=True, means2d_grad=True, **raster_kw)
+        image, meta = render_splats(work, viewmats[v], view_K(K, v), width, height, return_meta=True, means2d_grad=mcmc is None,
+                                    **raster_kw)
         loss = photometric_loss(image, image_fn(v), ssim_lambda=ssim_lambda)
+        if opacity_reg != 0.0:
+            loss = loss + opacity_reg * torch.sigmoid(work["opacity"]).mean()
+        if scale_reg != 0.0:
+            loss = loss + scale_reg * torch.exp(work["scaling"]).mean()
         loss.backward()
-        if step < cfg.refine_stop_iter:
+        if mcmc is None and step < cfg.refine_stop_iter:
             state.update(meta)
         opt.step()
         losses.append(loss.detach())
-        sizes.append(state.n)
+        sizes.append(int(work["means"].shape[0]))
+        if mcmc is not None:
+            if mcmc.refines_at(step):
+                del image, meta, loss
+                n_before = sizes[-1]
+                work, moved = relocate(work, mcmc, optimizer=opt, carry=carried, generator=noise_gen)
+                work, added = sample_add(work, mcmc, mcmc.n_new(n_before), optimizer=opt, carry=moved["carry"], generator=noise_gen)
+                carried = added["carry"]
+                rounds.append(dict(step=step, n_before=n_before, n_after=added["n_after"], relocated=moved["relocated"],
+                                   added=added["added"]))
+                if added["added"]:
+                    release_engines(dev, keep_n=added["n_after"])
+            rate = next((g["lr"] for g in opt.param_groups if g["params"][0] is work["means"]), None)
+            if rate is not None:
+                inject_noise(work, rate, mcmc, generator=noise_gen)
+            continue
         if cfg.refines_at(step):
             del image, meta, loss  # (the graph holds the old set's workspace)
             work, info = densify(work, state, cfg, step, optimizer=opt, carry=carried, generator=noise_gen)

@@ -1263,6 +1263,50 @@ GWBP_API int gwbp_densify_emit(int64_t n, int64_t n_out, const uint8_t *kind, co
 GWBP_API int gwbp_densify_gather(int64_t n, int64_t n_out, int32_t w, const float *table, int64_t ldt, const int32_t *parent,
                                  const uint8_t *child, const uint8_t *kind, int32_t mode, float *out, int64_t ldo, void *stream);
 
+/* ---- the MCMC strategy: relocation of dead Gaussians, growth to a cap, noise on the means (gsplat's MCMCStrategy) ----
+ * All arrays are dense unless a stride is named; float32 unless a type is named.  No atomics: the same inputs give the same bits.
+ * csrc/mcmc_math.h holds the expressions in their order.  n Gaussians, m draws.
+ *
+ * gwbp_mcmc_plan  weight[i] = floor(sigmoid(opacity[i]) 2^24) as int64, 0 where !(opacity[i] > t_opa) under GWBP_MCMC_RELOCATE (logits;
+ *     a NaN is dead); under GWBP_MCMC_ADD only a NaN has weight 0.  dead[i] = !(opacity[i] > t_opa) in both modes.  cdf and dead_offsets
+ *     (int64 [n + 1]) are the exclusive scans of the two, cdf[n] and dead_offsets[n] the totals; dead_idx (int32 [n]) holds the dead
+ *     Gaussians in ascending order in its first dead_offsets[n] entries.  workspace: gwbp_mcmc_plan_workspace_size(n) bytes, 8-B
+ *     aligned, free when the kernels have run.  n = 0 writes cdf[0] = dead_offsets[0] = 0.
+ * gwbp_mcmc_draw  parent[j] (int32 [m]) = the i with cdf[i] <= t < cdf[i + 1], t = min((int64)(u[j] cdf[n]), cdf[n] - 1); u float64
+ *     [m] in [0, 1), ASCENDING (then parent is ascending, which gwbp_mcmc_update needs).  cdf[n] = 0: parent[j] = -1.
+ * gwbp_mcmc_update  count[i] (int32 [n]) = the number of draws of i.  Where it is positive, opacity[i] and scaling[i, 0..2] (row
+ *     stride lds) become, IN PLACE and in pre-activation form, with r = min(count[i] + 1, GWBP_MCMC_MAX_RATIO):
+ *         o' = 1 - (1 - o)^(1 / r), clamped to [min_opacity, 1 - 2^-23];   s' = s o / D(o', r)   (D of the unclamped o')
+ * gwbp_mcmc_move  table[dead_idx[j], 0..w) = table[parent[j], 0..w) for j < m, IN PLACE (row stride ldt >= w).  A dead Gaussian is
+ *     never a parent, so no row is both read and written; a pair with an index outside [0, n) moves nothing.
+ * gwbp_mcmc_zero_rows  table[i, 0..w) = 0 where count[i] > 0, i < n (optimiser moments of the parents).
+ * gwbp_mcmc_noise  (every training step)  means[i] += R diag(exp(2 scaling[i])) R^T (z[i] g scaler), R of rotation[i] / |rotation[i]|,
+ *     g = 1 / (1 + exp(-100 ((1 - sigmoid(opacity[i])) - 0.995))); means [n, 3] in place, z [n, 3].
+ * gwbp_mcmc_libm  out[i] = expf(a[i]), logf(a[i]) or powf(a[i], b[i]) as the kernels above evaluate them (b is read by POW only): what a
+ *     test needs to hold them to a restatement bit for bit.
+ * GWBP_EINVAL before any HIP call: n or m outside [0, 2^31 - 1], an unknown mode or op, w outside [1, GWBP_DENSIFY_MAX_WIDTH], a row
+ * stride below its row, a min_opacity outside (0, 1), a null or misaligned array (4 B; cdf, dead_offsets, u and the workspace 8 B)
+ * where n (m) > 0.  Whether u IS ascending cannot be seen on the host: the kernels check every row index instead.
+ * GWBP_EWORKSPACE: a workspace below the size. */
+#define GWBP_MCMC_RELOCATE 0
+#define GWBP_MCMC_ADD 1
+#define GWBP_MCMC_MAX_RATIO 51
+#define GWBP_MCMC_LIBM_EXP 0
+#define GWBP_MCMC_LIBM_LOG 1
+#define GWBP_MCMC_LIBM_POW 2
+GWBP_API int gwbp_mcmc_plan_workspace_size(int64_t n, size_t *bytes);
+GWBP_API int gwbp_mcmc_plan(int64_t n, const float *opacity, float t_opa, int32_t mode, int64_t *cdf, int64_t *dead_offsets,
+                            int32_t *dead_idx, void *workspace, size_t workspace_bytes, void *stream);
+GWBP_API int gwbp_mcmc_draw(int64_t n, int64_t m, const int64_t *cdf, const double *u, int32_t *parent, void *stream);
+GWBP_API int gwbp_mcmc_update(int64_t n, int64_t m, const int32_t *parent, float min_opacity, float *opacity, float *scaling,
+                              int64_t lds, int32_t *count, void *stream);
+GWBP_API int gwbp_mcmc_move(int64_t n, int64_t m, int32_t w, const int32_t *parent, const int32_t *dead_idx, float *table,
+                            int64_t ldt, void *stream);
+GWBP_API int gwbp_mcmc_zero_rows(int64_t n, int32_t w, const int32_t *count, float *table, int64_t ldt, void *stream);
+GWBP_API int gwbp_mcmc_noise(int64_t n, float *means, const float *scaling, const float *rotation, const float *opacity,
+                             const float *z, float scaler, void *stream);
+GWBP_API int gwbp_mcmc_libm(int64_t n, int32_t op, const float *a, const float *b, float *out, void *stream);
+
 /* Adds this view's counters into `accum` (device, gwbp_stats) -- used by bench/driver to total pairs. */
 GWBP_API int gwbp_accumulate_stats(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, gwbp_stats *accum,
                           void *stream);

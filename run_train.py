@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
 """Train a scene against its images on the HIP path with densification: Adam under the reference trainer's loss while the set of
-Gaussians grows and shrinks by gsplat's default rule (gsbp_amd.train_scene; the rounds are the kernels of csrc/densify.hip).
+Gaussians grows and shrinks by gsplat's default rule (gsbp_amd.train_scene; the rounds are the kernels of csrc/densify.hip), or,
+with --strategy mcmc, by its MCMCStrategy: dead Gaussians relocated onto alive ones, growth by 5 % a round up to --cap-max, noise on
+the means every step (csrc/mcmc.hip), and the reference's opacity and scale regularisers.
 
     python run_train.py --colmap data/garden/sparse/0 --images data/garden/images_4 --data-factor 4 --steps 7000 --out trained/
     python run_train.py --synthetic T0 --steps 60 --refine-start 10 --refine-every 10 --out /tmp/train
+    python run_train.py --synthetic T0 --steps 60 --strategy mcmc --cap-max 300 --refine-start 10 --refine-every 10 --out /tmp/train
 
 --colmap DIR: cameras.bin, images.bin and points3D.bin of a COLMAP sparse model; the start is its point cloud (gsbp_amd.
 init_splats_from_points).  --images DIR: per view the image <image name> itself (read with PIL when it imports), or <image name>.pt /
@@ -47,13 +50,21 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--grow-scale3d", type=float, default=0.01)
     ap.add_argument("--prune-scale3d", type=float, default=0.1)
     ap.add_argument("--refine-start", type=int, default=500)
-    ap.add_argument("--refine-stop", type=int, default=15000)
+    ap.add_argument("--refine-stop", type=int, default=15000, help="--strategy mcmc: 25000 unless the option is given")
     ap.add_argument("--refine-every", type=int, default=100)
     ap.add_argument("--reset-every", type=int, default=3000)
     ap.add_argument("--pause-refine-after-reset", type=int, default=0)
     ap.add_argument("--scene-scale", type=float, default=None,
                     help="default: 1.1 x the largest distance of a camera from the cameras' centre (--colmap), 1 (--synthetic)")
     ap.add_argument("--max-gaussians", type=int, default=None)
+    # --strategy mcmc (gsbp_amd.MCMCConfig; gsplat's defaults).  It shares --refine-start and --refine-every; its --refine-stop
+    # defaults to 25000
+    ap.add_argument("--strategy", choices=("default", "mcmc"), default="default")
+    ap.add_argument("--cap-max", type=int, default=1_000_000)
+    ap.add_argument("--noise-lr", type=float, default=5e5)
+    ap.add_argument("--min-opacity", type=float, default=0.005)
+    ap.add_argument("--opacity-reg", type=float, default=None, help="default: 0 (--strategy default), 0.01 (--strategy mcmc)")
+    ap.add_argument("--scale-reg", type=float, default=None, help="default: 0 (--strategy default), 0.01 (--strategy mcmc)")
     ap.add_argument("--out", default="./results/train")
     return ap
 
@@ -68,6 +79,7 @@ def camera_extent(viewmats: torch.Tensor) -> float:
 def main(argv=None) -> int:
     ap = build_parser()
     args = ap.parse_args(argv)
+    stop_given = any(a.split("=")[0] == "--refine-stop" for a in (sys.argv[1:] if argv is None else argv))
     if bool(args.synthetic) == bool(args.colmap):
         ap.error("give exactly one of --colmap (with --images) and --synthetic")
     if args.colmap and not args.images:
@@ -116,20 +128,29 @@ def main(argv=None) -> int:
         def image_of(v):
             return load_image(args.images, names[v], dev)
 
-    cfg = gsbp_amd.DensifyConfig(prune_opa=args.prune_opa, grow_grad2d=args.grow_grad2d, grow_scale3d=args.grow_scale3d,
-                                 prune_scale3d=args.prune_scale3d, refine_start_iter=args.refine_start, refine_stop_iter=args.refine_stop,
-                                 refine_every=args.refine_every, reset_every=args.reset_every,
-                                 pause_refine_after_reset=args.pause_refine_after_reset, scene_scale=scene_scale,
-                                 max_gaussians=args.max_gaussians)
+    mcmc = args.strategy == "mcmc"
+    reg = dict(opacity_reg=(0.01 if mcmc else 0.0) if args.opacity_reg is None else args.opacity_reg,
+               scale_reg=(0.01 if mcmc else 0.0) if args.scale_reg is None else args.scale_reg)
+    if mcmc:
+        cfg = gsbp_amd.MCMCConfig(cap_max=args.cap_max, noise_lr=args.noise_lr, refine_start_iter=args.refine_start,
+                                  refine_stop_iter=args.refine_stop if stop_given else 25000,
+                                  refine_every=args.refine_every, min_opacity=args.min_opacity)
+    else:
+        cfg = gsbp_amd.DensifyConfig(prune_opa=args.prune_opa, grow_grad2d=args.grow_grad2d, grow_scale3d=args.grow_scale3d,
+                                     prune_scale3d=args.prune_scale3d, refine_start_iter=args.refine_start,
+                                     refine_stop_iter=args.refine_stop,
+                                     refine_every=args.refine_every, reset_every=args.reset_every,
+                                     pause_refine_after_reset=args.pause_refine_after_reset, scene_scale=scene_scale,
+                                     max_gaussians=args.max_gaussians)
     before = gsbp_amd.score_image_views(splats, viewmats, K, W, H, image_of, **kw)
     n_start = splats["means"].shape[0]
-    trained, history = gsbp_amd.train_scene(splats, viewmats, K, W, H, image_of, args.steps, cfg, params=args.params,
-                                            ssim_lambda=args.ssim_lambda, seed=args.seed, **kw)
+    trained, history = gsbp_amd.train_scene(splats, viewmats, K, W, H, image_of, args.steps, strategy=cfg, params=args.params,
+                                            ssim_lambda=args.ssim_lambda, seed=args.seed, **reg, **kw)
     after = gsbp_amd.score_image_views(trained, viewmats, K, W, H, image_of, **kw)
     torch.save({k: t.cpu() for k, t in trained.items() if torch.is_tensor(t)}, os.path.join(args.out, "trained.pt"))
     with open(os.path.join(args.out, "history.json"), "w") as f:
         json.dump(dict(params=list(args.params), steps=args.steps, ssim_lambda=args.ssim_lambda, seed=args.seed, views=names,
-                       config={k: getattr(cfg, k) for k in cfg.__dataclass_fields__}, loss=history["loss"], n=history["n"],
+                       strategy=args.strategy, **reg, config={k: getattr(cfg, k) for k in cfg.__dataclass_fields__}, loss=history["loss"], n=history["n"],
                        rounds=history["rounds"], resets=history["resets"]), f, indent=1)
     with open(os.path.join(args.out, "metrics.json"), "w") as f:
         json.dump(dict(before=before, after=after), f, indent=1)
