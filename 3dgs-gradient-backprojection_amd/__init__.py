@@ -35,6 +35,8 @@ JojiJoseph/3dgs-gradient-backprojection), hand-written HIP kernels behind a C AB
     from gsbp_amd import project_torch, sh_colors_torch  # rasterization() also trains: gradients w.r.t. means, quats, scales and
                                                     # opacities -- a HIP blend backward, then a HIP projection backward; these are the
                                                     # torch restatements the tests measure them against
+    from gsbp_amd import sh_colors                  # the SH colours of a training step and their gradients w.r.t. coefficients (stored
+                                                    # in one table or as features_dc + features_rest) and means: a HIP kernel pair
     from gsbp_amd import refine_pose, se3_exp, pose_error  # and it localises: rasterization(camera_grad=True) differentiates the view
                                                     # matrix; refine_pose finds where an image or feature map was taken from
     from gsbp_amd import photometric_loss, image_metrics, ssim_map, image_sums, gaussian_window  # the loss scenes are trained with,
@@ -53,6 +55,7 @@ from .engine import Engine, bilinear_index, narrow_labels, nearest_index  # noqa
 from . import scene_io  # noqa: F401
 from .rasterization import rasterization  # noqa: F401
 from .projection import project_torch, sh_colors_torch  # noqa: F401
+from .sh import sh_colors  # noqa: F401
 from .transfer import knn_search, transfer_labels, vote_labels  # noqa: F401
 from .pca import PCABasis, fit_pca, pca_colors, pca_transform, render_pca  # noqa: F401
 from .segment import ClickSession, apply_mask3d, probe_pixels, prompt_mask, prompt_scores, render_prompt_mask  # noqa: F401

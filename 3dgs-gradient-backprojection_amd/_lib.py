@@ -270,6 +270,10 @@ ARGTYPES = {
     "gwbp_mcmc_zero_rows": [_I64, _I32, _P, _P, _I64, _P],
     "gwbp_mcmc_noise": [_I64, _P, _P, _P, _P, _P, _F, _P],
     "gwbp_mcmc_libm": [_I64, _I32, _P, _P, _P, _P],
+    # the SH colours over split tables: N, degree, K_head, K_tail, means, head, tail, campos (host), out, stream  /  ..., campos,
+    # v_colors, v_head, v_tail, v_means, stream
+    "gwbp_sh_eval": [_I64, _I32, _I32, _I32, _P, _P, _P, C.POINTER(C.c_float), _P, _P],
+    "gwbp_sh_eval_backward": [_I64, _I32, _I32, _I32, _P, _P, _P, C.POINTER(C.c_float), _P, _P, _P, _P, _P],
 }
 # The typed forms of the entry points that read a finished [N, D] FIELD (or, gwbp_finalize_typed, write one): the untyped function's
 # arguments with the field's element type (GWBP_MAP_*, MAP_TYPES' codes) behind the field pointer.  A table of their own: they take no
@@ -308,6 +312,7 @@ DENSIFY_MAX_WIDTH = 65536  # GWBP_DENSIFY_MAX_WIDTH
 MCMC_MODES = {"relocate": 0, "add": 1}  # GWBP_MCMC_RELOCATE / _ADD
 MCMC_MAX_RATIO = 51  # GWBP_MCMC_MAX_RATIO
 MCMC_LIBM = {"exp": 0, "log": 1, "pow": 2}  # GWBP_MCMC_LIBM_*
+SH_MAX_K = 16  # GWBP_SH_MAX_K
 # every symbol of include/gwbp.h: the two functions that return strings, then the int-returning ones declared above
 EXPORTS = ["gwbp_version", "gwbp_last_error_string", *ARGTYPES, *FIELD_ARGTYPES]
 

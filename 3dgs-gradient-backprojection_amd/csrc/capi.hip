@@ -2321,6 +2321,78 @@ int gwbp_mcmc_libm(int64_t n, int32_t op, const float *a, const float *b, float 
     return launch_mcmc_libm(n, op, a, b, out, as_stream(stream));
 }
 
+// what gwbp_sh_eval and gwbp_sh_eval_backward share: the degree, the split of the coefficient row and the input arrays
+static int check_sh_tables(const char *what, int64_t n, int32_t degree, int32_t k_head, int32_t k_tail, const float *means,
+                           const float *head, const float *tail, const float *campos_host)
+{
+    if (int rc = check_densify_count(what, n))
+        return rc;
+    if (degree < 0 || degree > 3)
+        return set_error(GWBP_EINVAL, "%s: degree must be in [0, 3] (got %d)", what, (int)degree);
+    if (k_head < 1 || k_tail < 0)
+        return set_error(GWBP_EINVAL, "%s: K_head must be at least 1 and K_tail at least 0 (got %d, %d)", what, (int)k_head, (int)k_tail);
+    if ((int64_t)k_head + k_tail < (degree + 1) * (degree + 1))
+        return set_error(GWBP_EINVAL, "%s: %d + %d coefficients are fewer than the %d of degree %d", what, (int)k_head, (int)k_tail,
+                         (degree + 1) * (degree + 1), (int)degree);
+    if ((int64_t)k_head + k_tail > GWBP_SH_MAX_K)
+        return set_error(GWBP_EINVAL, "%s: %d + %d coefficients are more than GWBP_SH_MAX_K = %d", what, (int)k_head, (int)k_tail,
+                         GWBP_SH_MAX_K);
+    if (!tail && k_tail > 0)
+        return set_error(GWBP_EINVAL, "%s: null tail with K_tail = %d", what, (int)k_tail);
+    if (tail && k_tail == 0)
+        return set_error(GWBP_EINVAL, "%s: a tail with K_tail = 0", what);
+    if (!campos_host)
+        return set_error(GWBP_EINVAL, "%s: null campos_host", what);
+    if (n > 0 && (!means || !head))
+        return set_error(GWBP_EINVAL, "%s: null means or head", what);
+    if (misaligned(means, 3) || misaligned(head, 3) || misaligned(tail, 3))
+        return set_error(GWBP_EINVAL, "%s: means, head and tail must be 4-B aligned", what);
+    return GWBP_OK;
+}
+
+int gwbp_sh_eval(int64_t N, int32_t degree, int32_t K_head, int32_t K_tail, const float *means, const float *head, const float *tail,
+                 const float *campos_host, float *out, void *stream)
+{
+    if (int rc = check_sh_tables("sh_eval", N, degree, K_head, K_tail, means, head, tail, campos_host))
+        return rc;
+    if (N > 0 && !out)
+        return set_error(GWBP_EINVAL, "sh_eval: null out");
+    if (misaligned(out, 3))
+        return set_error(GWBP_EINVAL, "sh_eval: out must be 4-B aligned");
+    const void *const written[] = {out}, *const read[] = {means, head, tail};
+    if (N > 0)
+        if (int rc = check_regions_distinct("sh_eval", written, 1, read, 3))
+            return rc;
+    return launch_sh_eval(N, degree, K_head, K_tail, means, head, tail, campos_host, out, as_stream(stream));
+}
+
+int gwbp_sh_eval_backward(int64_t N, int32_t degree, int32_t K_head, int32_t K_tail, const float *means, const float *head,
+                          const float *tail, const float *campos_host, const float *v_colors, float *v_head, float *v_tail,
+                          float *v_means, void *stream)
+{
+    if (int rc = check_sh_tables("sh_eval_backward", N, degree, K_head, K_tail, means, head, tail, campos_host))
+        return rc;
+    if (!v_head && !v_tail && !v_means)
+        return set_error(GWBP_EINVAL, "sh_eval_backward: every output (v_head, v_tail, v_means) is null");
+    if (v_tail && K_tail == 0)
+        return set_error(GWBP_EINVAL, "sh_eval_backward: v_tail with K_tail = 0");
+    if (N > 0 && !v_colors)
+        return set_error(GWBP_EINVAL, "sh_eval_backward: null v_colors");
+    if (misaligned(v_colors, 3) || misaligned(v_head, 3) || misaligned(v_tail, 3) || misaligned(v_means, 3))
+        return set_error(GWBP_EINVAL, "sh_eval_backward: v_colors, v_head, v_tail and v_means must be 4-B aligned");
+    const void *written[3];
+    int n_written = 0;
+    for (const void *p : {(const void *)v_head, (const void *)v_tail, (const void *)v_means})
+        if (p)
+            written[n_written++] = p;
+    const void *const read[] = {means, head, tail, v_colors};
+    if (N > 0)
+        if (int rc = check_regions_distinct("sh_eval_backward", written, n_written, read, 4))
+            return rc;
+    return launch_sh_eval_bwd(N, degree, K_head, K_tail, means, head, tail, campos_host, v_colors, v_head, v_tail, v_means,
+                              as_stream(stream));
+}
+
 int gwbp_accumulate_stats(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, gwbp_stats *accum,
                           void *stream)
 {

@@ -291,6 +291,12 @@ int launch_render_px(const Ws &W, const ViewDev &V, const void *colors, int mt, 
                      hipStream_t s);
 int launch_sh_colors(int64_t N, int degree, int K, const float *means, const float *coeffs, const float *campos,
                      float *out, hipStream_t s);
+// the SH colours over a coefficient row split into head [N, k_head, 3] and tail [N, k_tail, 3] (tail may be nullptr), and their backward
+// (sh.hip): v_head, v_tail and v_means may each be nullptr; campos on the host
+int launch_sh_eval(int64_t N, int degree, int k_head, int k_tail, const float *means, const float *head, const float *tail,
+                   const float *campos, float *out, hipStream_t s);
+int launch_sh_eval_bwd(int64_t N, int degree, int k_head, int k_tail, const float *means, const float *head, const float *tail,
+                       const float *campos, const float *v_colors, float *v_head, float *v_tail, float *v_means, hipStream_t s);
 // backward of launch_render_px for an fp32 table (render_grad.hip): adds into v_g2d [N, 6] and, unless nullptr, v_colors [N, D]
 int launch_render_px_bwd(const Ws &W, const ViewDev &V, const float *colors, int64_t ldc, int D, const float *v_out,
                          const float *v_alpha, float *v_colors, float *v_g2d, hipStream_t s);

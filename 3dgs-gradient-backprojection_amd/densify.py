@@ -33,7 +33,8 @@ from . import _lib
 from ._lib import GwbpError, ptr
 from ._views import ld, run
 from .photometric import photometric_loss
-from .polish import PARAM_KEYS, render_splats, trainable, view_K, view_schedule
+from .polish import (PARAM_KEYS, check_sh_degree_interval, render_splats, scheduled_sh_degree, table_sh_degree, trainable, view_K,
+                     view_schedule)
 from .rasterization import release_engines
 
 GEOMETRY_KEYS = ("means", "scaling", "rotation", "opacity")  # what the emit kernel writes; every other [N, ...] tensor is gathered
@@ -300,7 +301,7 @@ def reset_opacity(splats: Dict[str, torch.Tensor], optimizer, cfg: DensifyConfig
 def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, image_fn: Callable[[int], torch.Tensor], steps: int,
                 cfg: Optional[DensifyConfig] = None, params: Sequence[str] = tuple(PARAM_KEYS), lrs: Optional[Dict[str, float]] = None,
                 seed: int = 0, ssim_lambda: float = 0.2, carry: Optional[Dict[str, torch.Tensor]] = None, strategy=None,
-                opacity_reg: float = 0.0, scale_reg: float = 0.0, **raster_kw):
+                opacity_reg: float = 0.0, scale_reg: float = 0.0, sh_degree_interval: Optional[int] = None, **raster_kw):
     """polish_scene's loop with the schedule: Adam on the named parameters under the photometric loss, the set growing and shrinking
     on the way.  Step s (from 0) renders one view with means2d_grad=True, runs the backward, adds the view into the statistics while
     s < refine_stop_iter, steps the optimiser, runs a densify round when s > refine_start_iter, s % refine_every == 0 and
@@ -316,7 +317,10 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
     group's current learning rate (none when the means are not trained).  history["rounds"] then holds step, n_before, n_after,
     relocated, added.
     opacity_reg, scale_reg: weights of mean(sigmoid(opacity)) and mean(exp(scaling)), added to the loss when they are not zero (the
-    reference's mcmc configuration sets both to 0.01)."""
+    reference's mcmc configuration sets both to 0.01).
+    sh_degree_interval: None renders every step at the tables' SH degree; an int renders step s at min(s // interval, that degree), the
+    reference trainer's schedule (its interval is 1000); rows above a step's degree get zero gradients.  history["sh_degree"]: the
+    degree each step rendered at, one int per step."""
     from .mcmc import MCMCConfig, inject_noise, relocate, sample_add
     if strategy is not None and cfg is not None:
         raise GwbpError("train_scene() takes cfg= or strategy=, not both")
@@ -325,7 +329,9 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
     mcmc = strategy if isinstance(strategy, MCMCConfig) else None
     cfg = strategy if isinstance(strategy, DensifyConfig) else cfg if cfg is not None else DensifyConfig()
     opacity_reg, scale_reg = float(opacity_reg), float(scale_reg)
+    interval = check_sh_degree_interval(sh_degree_interval, "train_scene")
     work, opt = trainable(splats, params, lrs, "train_scene")
+    table_degree, degrees = table_sh_degree(work), []
     dev, width, height = splats["means"].device, int(width), int(height)
     for key in GEOMETRY_KEYS:  # what the rounds write must be float32 whether it is trained or not
         work[key] = work[key] if work[key].requires_grad else work[key].float()
@@ -335,8 +341,9 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
     losses, sizes, rounds, resets = [], [], [], []
     for step, v in enumerate(view_schedule(viewmats.shape[0], seed, steps)):
         opt.zero_grad(set_to_none=True)
+        degrees.append(table_degree if interval is None else scheduled_sh_degree(step, interval, table_degree))
         image, meta = render_splats(work, viewmats[v], view_K(K, v), width, height, return_meta=True, means2d_grad=mcmc is None,
-                                    **raster_kw)
+                                    sh_degree=None if interval is None else degrees[-1], **raster_kw)
         loss = photometric_loss(image, image_fn(v), ssim_lambda=ssim_lambda)
         if opacity_reg != 0.0:
             loss = loss + opacity_reg * torch.sigmoid(work["opacity"]).mean()
@@ -374,7 +381,8 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
         if cfg.resets_at(step):
             reset_opacity(work, opt, cfg)
             resets.append(step)
-    history = dict(loss=torch.stack(losses).cpu().tolist() if losses else [], n=sizes, rounds=rounds, resets=resets, carry=carried)
+    history = dict(loss=torch.stack(losses).cpu().tolist() if losses else [], n=sizes, rounds=rounds, resets=resets, carry=carried,
+                   sh_degree=degrees)
     return {k: (t.detach() if torch.is_tensor(t) else t) for k, t in work.items()}, history
 
 

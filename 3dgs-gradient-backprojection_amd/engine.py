@@ -72,6 +72,48 @@ def _req(t: torch.Tensor, name: str, shape_tail=None) -> torch.Tensor:
     return t.contiguous()
 
 
+def _sh_tables(degree, means, head, tail):
+    """(means, head, tail) as gwbp_sh_eval reads them: float32 HIP tensors, contiguous, [N,3], [N,K_head,3] and None or [N,K_tail,3]."""
+    means = _req(means, "means", (3,))
+    head = _req(head, "sh coefficients")
+    tail = None if tail is None else _req(tail, "sh coefficients (tail)")
+    for t in (head, tail):
+        if t is not None and (t.dim() != 3 or t.shape[2] != 3 or t.shape[0] != means.shape[0] or t.device != means.device):
+            raise GwbpError(f"SH coefficients must be [N,K,3] beside means [{means.shape[0]},3], got {tuple(t.shape)}")
+    if tail is not None and tail.shape[1] == 0:
+        tail = None
+    if isinstance(degree, bool) or int(degree) != degree:
+        raise GwbpError(f"the SH degree must be an int, got {degree!r}")
+    return means, head, tail
+
+
+def sh_eval_tables(call, stream, degree, means, head, tail, campos) -> torch.Tensor:
+    """Engine.sh_eval for whoever brings the caller of the C ABI (call(name, *args)) and the stream handle."""
+    means, head, tail = _sh_tables(degree, means, head, tail)
+    out = torch.empty(means.shape[0], 3, device=means.device)
+    cp = (c_float * 3)(*[float(v) for v in campos])
+    call("gwbp_sh_eval", c_int64(means.shape[0]), int(degree), head.shape[1], 0 if tail is None else tail.shape[1], ptr(means), ptr(head),
+         ptr(tail), cp, ptr(out), stream)
+    return out
+
+
+def sh_eval_tables_backward(call, stream, degree, means, head, tail, campos, v_colors, want_head, want_tail, want_means):
+    """Engine.sh_eval_backward, likewise."""
+    means, head, tail = _sh_tables(degree, means, head, tail)
+    v_colors = _req(v_colors, "v_colors", (3,))
+    if v_colors.shape[0] != means.shape[0]:
+        raise GwbpError(f"v_colors must be [{means.shape[0]},3], got {tuple(v_colors.shape)}")
+    v_head = torch.empty_like(head) if want_head else None
+    v_tail = torch.empty_like(tail) if want_tail and tail is not None else None
+    v_means = torch.empty_like(means) if want_means else None
+    if v_head is None and v_tail is None and v_means is None:
+        raise GwbpError("sh_eval_backward: no output asked for")
+    cp = (c_float * 3)(*[float(v) for v in campos])
+    call("gwbp_sh_eval_backward", c_int64(means.shape[0]), int(degree), head.shape[1], 0 if tail is None else tail.shape[1], ptr(means),
+         ptr(head), ptr(tail), cp, ptr(v_colors), ptr(v_head), ptr(v_tail), ptr(v_means), stream)
+    return v_head, v_tail, v_means
+
+
 def field_rows(t: torch.Tensor, name: str):
     """(tensor, GWBP_MAP_* code) of a finished [rows, D] FIELD as it is stored: float32, float16 or bfloat16, read by the *_typed entry
     points without a float32 copy.  Unit stride inside a row and a non-negative row stride >= D, in elements; a layout the kernels
@@ -1272,6 +1314,19 @@ class Engine:
         self._call("gwbp_sh_colors", c_int64(means.shape[0]), int(degree), coeffs.shape[1], ptr(means), ptr(coeffs),
                                       cp, ptr(out), self._stream())
         return out
+
+    def sh_eval(self, degree: int, means, head, tail, campos):
+        """sh_colors over a coefficient row stored in two tables: head [N,K_head,3] and tail [N,K_tail,3] (None: one table), e.g. a
+        splat dict's features_dc and features_rest as they are stored.  [N,3], the bits of sh_colors on the concatenated table."""
+        return sh_eval_tables(self._call, self._stream(), degree, means, head, tail, campos)
+
+    def sh_eval_backward(self, degree: int, means, head, tail, campos, v_colors, want_head: bool = True, want_tail: bool = True,
+                         want_means: bool = True):
+        """The backward of sh_eval (gwbp_sh_eval_backward): (v_head, v_tail, v_means) from v_colors [N,3], None where not asked for
+        (v_tail also without a tail).  Rows of the tables above the degree's (degree + 1)^2 get exact zeros; v_means is all zero at
+        degree 0.  No atomics: the same bits every run."""
+        return sh_eval_tables_backward(self._call, self._stream(), degree, means, head, tail, campos, v_colors, want_head, want_tail,
+                                       want_means)
 
     # ---- the view's RGB render for the 2-D network (create_feature_field(render_colors=...)) ----------------------------------
     @staticmethod

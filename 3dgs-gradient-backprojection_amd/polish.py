@@ -18,7 +18,8 @@ import torch
 
 from ._lib import GwbpError
 from .photometric import image_metrics, photometric_loss
-from .rasterization import rasterization
+from .rasterization import SH_CAMERA_GRAD_MESSAGE, rasterization, sh_kernel_enabled
+from .sh import sh_colors
 
 # the trainer's name of a parameter -> its key in a splat dict (pre-activation: scales are logs, opacities logits)
 PARAM_KEYS = {"means": "means", "scales": "scaling", "quats": "rotation", "opacities": "opacity", "sh0": "features_dc",
@@ -27,16 +28,52 @@ PARAM_KEYS = {"means": "means", "scales": "scaling", "quats": "rotation", "opaci
 DEFAULT_LRS = {"means": 1.6e-4, "scales": 5e-3, "quats": 1e-3, "opacities": 5e-2, "sh0": 2.5e-3, "shN": 2.5e-3 / 20}
 
 
-def render_splats(splats: Dict[str, torch.Tensor], viewmat, K, width: int, height: int, return_meta: bool = False, **raster_kw):
+def table_sh_degree(splats: Dict[str, torch.Tensor]) -> int:
+    """The SH degree the coefficient count of features_dc and features_rest gives."""
+    k = splats["features_dc"].shape[1] + (splats["features_rest"].shape[1] if "features_rest" in splats else 0)
+    degree = int(round(math.sqrt(k))) - 1
+    if (degree + 1) ** 2 != k:
+        raise GwbpError(f"{k} SH coefficients per Gaussian are no full degree")
+    return degree
+
+
+def scheduled_sh_degree(step: int, interval: Optional[int], table_degree: int) -> Optional[int]:
+    """The reference trainer's sh_degree_to_use of step `step`: min(step // interval, the table's degree); None without an interval."""
+    return None if interval is None else min(step // interval, table_degree)
+
+
+def check_sh_degree_interval(interval, fn: str) -> Optional[int]:
+    if interval is None:
+        return None
+    if isinstance(interval, bool) or not isinstance(interval, int) or interval < 1:
+        raise GwbpError(f"{fn}(): sh_degree_interval must be None or a positive int, got {interval!r}")
+    return interval
+
+
+def render_splats(splats: Dict[str, torch.Tensor], viewmat, K, width: int, height: int, return_meta: bool = False,
+                  sh_degree: Optional[int] = None, **raster_kw):
     """The [H, W, 3] image of a splat dict from one camera, as the trainer renders it: scales = exp, opacities = sigmoid, raw quats,
-    the SH colours of features_dc and features_rest at the degree their count gives.  Differentiable in every tensor of the dict.
+    the SH colours of features_dc and features_rest.  Differentiable in every tensor of the dict.
+    sh_degree: the degree to evaluate, at most the one the tables' coefficient count gives (None: that one).  Below it the rows above
+    (sh_degree + 1)^2 are not read, and their gradients are zeros, not None.
+    The colours come from sh.sh_colors on the two tables as they are stored (no torch.cat, one HIP kernel forward and one backward) and
+    go to rasterization() as an [N, 3] table; camera_grad=True is refused as rasterization() refuses it beside sh_degree.
     return_meta: (image, meta) -- the eager part of rasterization()'s meta, which under means2d_grad=True holds the means2d leaf."""
-    sh = torch.cat([splats["features_dc"], splats["features_rest"]], dim=1) if "features_rest" in splats else splats["features_dc"]
-    degree = int(round(math.sqrt(sh.shape[1]))) - 1
-    if (degree + 1) ** 2 != sh.shape[1]:
-        raise GwbpError(f"{sh.shape[1]} SH coefficients per Gaussian are no full degree")
-    out, _, meta = rasterization(splats["means"], splats["rotation"], torch.exp(splats["scaling"]), torch.sigmoid(splats["opacity"]),
-                                 sh, viewmat[None], K[None], width, height, sh_degree=degree, want_meta=False, **raster_kw)
+    table = table_sh_degree(splats)
+    degree = table if sh_degree is None else sh_degree
+    if isinstance(degree, bool) or not isinstance(degree, int) or not 0 <= degree <= table:
+        raise GwbpError(f"sh_degree must be an int in [0, {table}] (the tables' degree), got {sh_degree!r}")
+    means, dc, rest = splats["means"], splats["features_dc"], splats.get("features_rest")
+    if raster_kw.get("camera_grad") and torch.is_grad_enabled() and viewmat.requires_grad:
+        raise NotImplementedError(SH_CAMERA_GRAD_MESSAGE)
+    geometry = (means, splats["rotation"], torch.exp(splats["scaling"]), torch.sigmoid(splats["opacity"]))
+    if not sh_kernel_enabled() or not means.is_cuda:  # (set_sh_kernel(False): the route before the kernels; CPU tensors: its error)
+        sh = dc if rest is None else torch.cat([dc, rest], dim=1)
+        out, _, meta = rasterization(*geometry, sh, viewmat[None], K[None], width, height, sh_degree=degree, want_meta=False, **raster_kw)
+        return (out[0], meta) if return_meta else out[0]
+    vm_h = viewmat.detach().cpu()  # the camera centre as rasterization() computes it beside sh_degree
+    colors = sh_colors(degree, means, dc, (-(vm_h[:3, :3].T @ vm_h[:3, 3])).tolist(), rest=rest)
+    out, _, meta = rasterization(*geometry, colors, viewmat[None], K[None], width, height, sh_degree=None, want_meta=False, **raster_kw)
     return (out[0], meta) if return_meta else out[0]
 
 
@@ -78,18 +115,24 @@ def view_schedule(n_views: int, seed: int, steps: int):
 
 def polish_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, image_fn: Callable[[int], torch.Tensor],
                  params: Sequence[str] = ("opacities", "sh0"), steps: int = 300, ssim_lambda: float = 0.2,
-                 lrs: Optional[Dict[str, float]] = None, seed: int = 0, **raster_kw) -> Tuple[Dict[str, torch.Tensor], List[float]]:
+                 lrs: Optional[Dict[str, float]] = None, seed: int = 0, sh_degree_interval: Optional[int] = None,
+                 **raster_kw) -> Tuple[Dict[str, torch.Tensor], List[float]]:
     """Adam on the named parameters of `splats` against the views' images.  Returns (a new splat dict -- the named tensors replaced by
     their polished values, the others shared -- and the steps' losses, read from the device once behind the loop).
     params: names out of means, scales, quats, opacities, sh0, shN; one Adam group each at lrs[name] (default: the reference
     trainer's, DEFAULT_LRS; eps 1e-15 as there).  Each step takes one view, drawn from torch.Generator().manual_seed(seed) on the
     host as a fresh permutation per pass over the views.  image_fn(v): the view's float32 [H, W, 3] image in [0, 1] on the device.
-    viewmats [V, 4, 4]; K [3, 3] or [V, 3, 3].  raster_kw: camera_model, rasterize_mode and the other keywords of rasterization()."""
+    viewmats [V, 4, 4]; K [3, 3] or [V, 3, 3].  raster_kw: camera_model, rasterize_mode and the other keywords of rasterization().
+    sh_degree_interval: None renders every step at the tables' SH degree; an int renders step s (from 0) at min(s // interval, that
+    degree), the reference trainer's schedule (its interval is 1000).  Coefficient rows above a step's degree get zero gradients."""
+    interval = check_sh_degree_interval(sh_degree_interval, "polish_scene")
     work, opt = trainable(splats, params, lrs, "polish_scene")
     width, height, losses = int(width), int(height), []
-    for v in view_schedule(viewmats.shape[0], seed, steps):
+    table = table_sh_degree(work)
+    for step, v in enumerate(view_schedule(viewmats.shape[0], seed, steps)):
         opt.zero_grad(set_to_none=True)
-        image = render_splats(work, viewmats[v], view_K(K, v), width, height, **raster_kw)
+        image = render_splats(work, viewmats[v], view_K(K, v), width, height, sh_degree=scheduled_sh_degree(step, interval, table),
+                              **raster_kw)
         loss = photometric_loss(image, image_fn(v), ssim_lambda=ssim_lambda)
         loss.backward()
         opt.step()

@@ -27,6 +27,7 @@ from . import _lib
 from ._lib import GwbpError
 from .engine import HALF_TYPES, TILE, Engine
 from .projection import sh_colors_torch
+from .sh import sh_colors
 
 _ENGINES: Dict[Tuple, Engine] = {}
 # The reference's harvesting pattern hands the SAME all-zero colour table to every view (backproject.py:67-72): whether a
@@ -402,6 +403,25 @@ def set_harvest_shortcut(on: bool) -> None:
     _HARVEST_SHORTCUT = bool(on)
 
 
+_SH_KERNEL = True
+
+
+def set_sh_kernel(on: bool) -> None:
+    """Developer switch: SH coefficients or means that require grad take the HIP kernel pair of sh.sh_colors (default) or, switched
+    off, projection.sh_colors_torch under autograd, as before the kernels existed -- so that one run can time both routes
+    (tools/time_sh_grad.py; DESIGN.md 4.0k has the figures)."""
+    global _SH_KERNEL
+    _SH_KERNEL = bool(on)
+
+
+def sh_kernel_enabled() -> bool:
+    return _SH_KERNEL
+
+
+SH_CAMERA_GRAD_MESSAGE = ("camera_grad=True with sh_degree: the SH view direction uses a detached camera centre, so the "
+                          "gradient w.r.t. viewmats would miss it; pass colours, or detach viewmats")
+
+
 def _plain(t: torch.Tensor) -> torch.Tensor:
     return t.as_subclass(torch.Tensor) if type(t) is not torch.Tensor else t
 
@@ -576,11 +596,11 @@ def _camera_table(c: int, means, colors, vm, sh_degree, render_mode, width, heig
         vm_h = vm.detach().cpu()
         campos = (-(vm_h[:3, :3].T @ vm_h[:3, 3])).tolist()
         if torch.is_grad_enabled() and (sh.requires_grad or means.requires_grad):
-            # k_sh_colors in torch ops: autograd carries the colour gradient to the coefficients and, through the view
-            # direction, to means
+            # k_sh_eval and its backward kernel (sh.sh_colors) carry the colour gradient to the coefficients and, through the view
+            # direction, to means; set_sh_kernel(False): k_sh_colors in torch ops under autograd
             if sh.dtype != torch.float32:
                 raise GwbpError(f"sh coefficients must be float32, got {sh.dtype}")
-            cols = sh_colors_torch(sh_degree, means, sh, campos)
+            cols = (sh_colors if _SH_KERNEL else sh_colors_torch)(sh_degree, means, sh, campos)
         else:
             cols = get_engine(means.device, means.shape[0], width, height).sh_colors(sh_degree, means, sh, campos)
     else:
@@ -656,8 +676,7 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     if camera_grad and Ks.requires_grad:
         raise NotImplementedError("gradients w.r.t. Ks are not implemented (camera_grad=True differentiates viewmats only)")
     if camera and sh_degree is not None:
-        raise NotImplementedError("camera_grad=True with sh_degree: the SH view direction uses a detached camera centre, so the "
-                                  "gradient w.r.t. viewmats would miss it; pass colours, or detach viewmats")
+        raise NotImplementedError(SH_CAMERA_GRAD_MESSAGE)
     kw = dict(near_plane=near_plane, far_plane=far_plane, eps2d=eps2d, radius_clip=radius_clip, camera_model=camera_model,
               rasterize_mode=rasterize_mode)
     gauss_grad = any(t.requires_grad for t in (means, quats, scales, opacities))  # (whatever the grad mode, as needs_input_grad says it)

@@ -582,6 +582,27 @@ GWBP_API int gwbp_project_backward_blocks(int64_t n_gaussians);
 GWBP_API int gwbp_sh_colors(int64_t N, int32_t degree, int32_t K, const float *means, const float *coeffs,
                    const float *campos_host, float *out, void *stream);
 
+/* The same colours from a coefficient row that is stored in two tables, and their backward (csrc/sh.hip, csrc/sh_math.h): what a
+ * training step evaluates from features_dc and features_rest as they are stored.
+ * Coefficient k of Gaussian i is head[i][k] for k < K_head and tail[i][k - K_head] behind; both tables are contiguous float32
+ * [N, K_*, 3]; tail == NULL with K_tail == 0 is the single-table call.  Rows from (degree + 1)^2 on are not used.
+ * gwbp_sh_eval  out[N, 3]: the bits gwbp_sh_colors gives on the concatenated table.
+ * gwbp_sh_eval_backward  from v_colors[N, 3] = d loss / d out, WRITES (each output may be NULL, not all of them):
+ *     v_head[N, K_head, 3], v_tail[N, K_tail, 3]: b_k(dir) v_c for k < (degree + 1)^2, exact +0 in the rows behind; a channel passes
+ *         v_c where the forward's own float32 pre-clamp value r has r + 0.5f >= 0 (torch's clamp_min rule; a NaN passes nothing);
+ *     v_means[N, 3]: the gradient through the view direction dir = d / max(|d|, 1e-12), d = mean - campos:
+ *         (v_dir - dir <dir, v_dir>) / |d| where |d| > 1e-12 and v_dir 1e12 otherwise; zeros at degree 0.
+ * It recomputes the forward from its inputs.  One thread owns a Gaussian, there are no atomics: the same bits every run.
+ * GWBP_EINVAL before any HIP call: N outside [0, 2^31 - 1], degree outside 0..3, K_head < 1, K_tail < 0, K_head + K_tail below
+ * (degree + 1)^2 or above GWBP_SH_MAX_K, tail == NULL with K_tail > 0, a null campos_host, a null required array where N > 0, every
+ * backward output null, an array that is not 4-B aligned, an output that is one of the inputs or another output. */
+#define GWBP_SH_MAX_K 16
+GWBP_API int gwbp_sh_eval(int64_t N, int32_t degree, int32_t K_head, int32_t K_tail, const float *means, const float *head,
+                          const float *tail, const float *campos_host, float *out, void *stream);
+GWBP_API int gwbp_sh_eval_backward(int64_t N, int32_t degree, int32_t K_head, int32_t K_tail, const float *means, const float *head,
+                                   const float *tail, const float *campos_host, const float *v_colors, float *v_head, float *v_tail,
+                                   float *v_means, void *stream);
+
 /* ---- fused entry points --------------------------------------------------------------------------------- */
 
 /* project -> bin_sort -> blend_weights -> scatter for one view: the per-view body of

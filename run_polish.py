@@ -37,6 +37,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--ssim-lambda", type=float, default=0.2)
     ap.add_argument("--seed", type=int, default=0)
+    # (default=SUPPRESS: an option that is not given leaves the parsed namespace as it was before the option existed)
+    ap.add_argument("--sh-degree-interval", type=int, default=argparse.SUPPRESS, metavar="INTERVAL",
+                    help="render step s at SH degree min(s // INTERVAL, the tables' degree), as the reference trainer does with "
+                         "its interval of 1000 (default: off, every step at the full degree)")
     ap.add_argument("--out", default="./results/polish")
     return ap
 
@@ -102,7 +106,8 @@ def main(argv=None) -> int:
 
     before = gsbp_amd.score_image_views(splats, viewmats, K, W, H, image_of, **kw)
     polished, history = gsbp_amd.polish_scene(splats, viewmats, K, W, H, image_of, params=args.params, steps=args.steps,
-                                              ssim_lambda=args.ssim_lambda, seed=args.seed, **kw)
+                                              ssim_lambda=args.ssim_lambda, seed=args.seed,
+                                              sh_degree_interval=getattr(args, "sh_degree_interval", None), **kw)
     after = gsbp_amd.score_image_views(polished, viewmats, K, W, H, image_of, **kw)
     torch.save({k: t.cpu() for k, t in polished.items()}, os.path.join(args.out, "polished.pt"))
     with open(os.path.join(args.out, "history.json"), "w") as f:

@@ -44,6 +44,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--sh-degree", type=int, default=3, help="--colmap: the SH degree of the start")
     ap.add_argument("--ssim-lambda", type=float, default=0.2)
     ap.add_argument("--seed", type=int, default=0)
+    # (default=SUPPRESS: an option that is not given leaves the parsed namespace as it was before the option existed)
+    ap.add_argument("--sh-degree-interval", type=int, default=argparse.SUPPRESS, metavar="INTERVAL",
+                    help="render step s at SH degree min(s // INTERVAL, the tables' degree), as the reference trainer does with "
+                         "its interval of 1000 (default: off, every step at the full degree)")
     # the schedule (gsbp_amd.DensifyConfig; gsplat's defaults)
     ap.add_argument("--prune-opa", type=float, default=0.005)
     ap.add_argument("--grow-grad2d", type=float, default=2e-4)
@@ -145,13 +149,14 @@ def main(argv=None) -> int:
     before = gsbp_amd.score_image_views(splats, viewmats, K, W, H, image_of, **kw)
     n_start = splats["means"].shape[0]
     trained, history = gsbp_amd.train_scene(splats, viewmats, K, W, H, image_of, args.steps, strategy=cfg, params=args.params,
-                                            ssim_lambda=args.ssim_lambda, seed=args.seed, **reg, **kw)
+                                            ssim_lambda=args.ssim_lambda, seed=args.seed,
+                                            sh_degree_interval=getattr(args, "sh_degree_interval", None), **reg, **kw)
     after = gsbp_amd.score_image_views(trained, viewmats, K, W, H, image_of, **kw)
     torch.save({k: t.cpu() for k, t in trained.items() if torch.is_tensor(t)}, os.path.join(args.out, "trained.pt"))
     with open(os.path.join(args.out, "history.json"), "w") as f:
         json.dump(dict(params=list(args.params), steps=args.steps, ssim_lambda=args.ssim_lambda, seed=args.seed, views=names,
                        strategy=args.strategy, **reg, config={k: getattr(cfg, k) for k in cfg.__dataclass_fields__}, loss=history["loss"], n=history["n"],
-                       rounds=history["rounds"], resets=history["resets"]), f, indent=1)
+                       rounds=history["rounds"], resets=history["resets"], sh_degree=history["sh_degree"]), f, indent=1)
     with open(os.path.join(args.out, "metrics.json"), "w") as f:
         json.dump(dict(before=before, after=after), f, indent=1)
     print(f"{n_start} -> {trained['means'].shape[0]} Gaussians in {len(history['rounds'])} rounds; loss {history['loss'][0]:.6e} -> "
