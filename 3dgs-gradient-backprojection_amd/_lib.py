@@ -165,6 +165,8 @@ ARGTYPES = {
     "gwbp_render_pixels": _WSV + [_P, _I32, _P, _P, _P],
     # colors, ldc, D, v_out, v_alpha, v_colors, v_g2d, stream
     "gwbp_render_pixels_backward": _WSV + [_P, _I64, _I32, _P, _P, _P, _P, _P],
+    # colors, ldc, D, v_out, v_alpha, v_g2d, stream
+    "gwbp_render_dots_backward": _WSV + [_P, _I64, _I32, _P, _P, _P, _P],
     # camera_model, rasterize_mode, means, quats, scales, opacities, v_g2d, v_means, v_quats, v_scales, v_opacities, v_viewmat,
     # scratch, stream  /  n_gaussians (returns the scratch's rows, not a status)
     "gwbp_project_backward": _WSV + [_I32, _I32] + [_P] * 12,

@@ -1025,6 +1025,26 @@ int gwbp_render_pixels_backward(const gwbp_caps *caps, void *workspace, size_t w
     return launch_render_px_bwd(B.W, B.V, colors, ldc, D, v_out, v_alpha, v_colors, v_g2d, B.s);
 }
 
+int gwbp_render_dots_backward(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                              const float *colors, int64_t ldc, int32_t D, const float *v_out, const float *v_alpha, float *v_g2d,
+                              void *stream)
+{
+    Bound B;
+    int rc = bind(caps, workspace, workspace_bytes, view_host, stream, &B);
+    if (rc)
+        return rc;
+    if (D < 1 || D > 128)
+        return set_error(GWBP_EINVAL, "render_dots_backward needs 1 <= D <= 128 (got D=%d)", D);
+    if (!colors || !v_out || !v_g2d)
+        return set_error(GWBP_EINVAL, "render_dots_backward needs colors, v_out and v_g2d (got %s colors, %s v_out, %s v_g2d)",
+                         colors ? "a" : "null", v_out ? "a" : "null", v_g2d ? "a" : "null");
+    if ((rc = check_render_payload("render_dots_backward", colors, GWBP_MAP_F32, ldc, D, v_out, GWBP_MAP_F32)))
+        return rc;
+    if ((reinterpret_cast<uintptr_t>(v_alpha) | reinterpret_cast<uintptr_t>(v_g2d)) & 3)
+        return set_error(GWBP_EINVAL, "render_dots_backward: v_alpha and v_g2d must be 4-B aligned");
+    return launch_render_dots_bwd(B.W, B.V, colors, ldc, D, v_out, v_alpha, v_g2d, B.s);
+}
+
 int gwbp_project_backward_blocks(int64_t n_gaussians)
 {
     if (n_gaussians < 0 || (n_gaussians + kScanBlock - 1) / kScanBlock > 0x7FFFFFFF)

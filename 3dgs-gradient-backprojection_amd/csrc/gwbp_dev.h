@@ -300,6 +300,9 @@ int launch_sh_eval_bwd(int64_t N, int degree, int k_head, int k_tail, const floa
 // backward of launch_render_px for an fp32 table (render_grad.hip): adds into v_g2d [N, 6] and, unless nullptr, v_colors [N, D]
 int launch_render_px_bwd(const Ws &W, const ViewDev &V, const float *colors, int64_t ldc, int D, const float *v_out,
                          const float *v_alpha, float *v_colors, float *v_g2d, hipStream_t s);
+// v_g2d alone for tables of up to 128 channels (render_grad_wide.hip): the channels enter through one dot product per pair
+int launch_render_dots_bwd(const Ws &W, const ViewDev &V, const float *colors, int64_t ldc, int D, const float *v_out,
+                           const float *v_alpha, float *v_g2d, hipStream_t s);
 // backward of launch_project (project_grad.hip) on the records the projection of the same view left in the workspace: WRITES the
 // per-Gaussian gradients (each may be nullptr) and v_viewmat [12] (nullptr, or with scratch [project_backward_blocks(n), 12])
 int project_backward_blocks(int64_t n);

@@ -33,8 +33,8 @@ from . import _lib
 from ._lib import GwbpError, ptr
 from ._views import ld, run
 from .photometric import photometric_loss
-from .polish import (PARAM_KEYS, check_sh_degree_interval, render_splats, scheduled_sh_degree, table_sh_degree, trainable, view_K,
-                     view_schedule)
+from .polish import (PARAM_KEYS, check_sh_degree_interval, render_splats, scheduled_sh_degree, splat_geometry, table_sh_degree, trainable,
+                     view_K, view_schedule)
 from .rasterization import release_engines
 
 GEOMETRY_KEYS = ("means", "scaling", "rotation", "opacity")  # what the emit kernel writes; every other [N, ...] tensor is gathered
@@ -298,10 +298,37 @@ def reset_opacity(splats: Dict[str, torch.Tensor], optimizer, cfg: DensifyConfig
     return splats
 
 
+LATENT_RENDER_KW = ("near_plane", "far_plane", "radius_clip", "eps2d", "rasterize_mode", "camera_model")  # render_latents' keywords
+
+
+def _feature_leaves(work: Dict, opt, lrs, feature_dim, latent_dim, decoder, decoder_lr, seed):
+    """train_scene's feature term: (work with the float32 leaf `features` [N, latent_dim] in an Adam group of its own, the decoder
+    leaf [latent_dim, feature_dim], the decoder's own Adam)."""
+    n, dev = int(work["means"].shape[0]), work["means"].device
+    if decoder is None:
+        if feature_dim is None:
+            raise GwbpError("train_scene(feature_fn=...) needs feature_dim (the channels of the maps) or a decoder")
+        decoder = torch.rand(int(latent_dim), int(feature_dim), generator=torch.Generator().manual_seed(int(seed)))
+    decoder = decoder.detach().to(device=dev, dtype=torch.float32).clone()
+    if decoder.dim() != 2 or (feature_dim is not None and decoder.shape[1] != int(feature_dim)):
+        raise GwbpError(f"decoder must be [latent_dim, {feature_dim}], got {tuple(decoder.shape)}")
+    d = int(decoder.shape[0])
+    feats = work.get("features")
+    feats = torch.zeros(n, d, device=dev) if feats is None else feats.detach().to(device=dev, dtype=torch.float32).clone()
+    if tuple(feats.shape) != (n, d):
+        raise GwbpError(f"splats['features'] must be [{n}, {d}] (the decoder's rows), got {tuple(feats.shape)}")
+    work = dict(work, features=feats.requires_grad_(True))
+    opt.add_param_group(dict(params=[work["features"]], lr=float((lrs or {}).get("features", 2.5e-3))))
+    decoder.requires_grad_(True)
+    return work, decoder, torch.optim.Adam([decoder], lr=float(decoder_lr), eps=1e-15)
+
+
 def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, image_fn: Callable[[int], torch.Tensor], steps: int,
                 cfg: Optional[DensifyConfig] = None, params: Sequence[str] = tuple(PARAM_KEYS), lrs: Optional[Dict[str, float]] = None,
                 seed: int = 0, ssim_lambda: float = 0.2, carry: Optional[Dict[str, torch.Tensor]] = None, strategy=None,
-                opacity_reg: float = 0.0, scale_reg: float = 0.0, sh_degree_interval: Optional[int] = None, **raster_kw):
+                opacity_reg: float = 0.0, scale_reg: float = 0.0, sh_degree_interval: Optional[int] = None,
+                feature_fn: Optional[Callable[[int], torch.Tensor]] = None, feature_dim: Optional[int] = None, latent_dim: int = 128,
+                feature_weight: float = 1.0, feature_loss: str = "l1", decoder_lr: float = 2.5e-3, decoder=None, **raster_kw):
     """polish_scene's loop with the schedule: Adam on the named parameters under the photometric loss, the set growing and shrinking
     on the way.  Step s (from 0) renders one view with means2d_grad=True, runs the backward, adds the view into the statistics while
     s < refine_stop_iter, steps the optimiser, runs a densify round when s > refine_start_iter, s % refine_every == 0 and
@@ -320,7 +347,22 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
     reference's mcmc configuration sets both to 0.01).
     sh_degree_interval: None renders every step at the tables' SH degree; an int renders step s at min(s // interval, that degree), the
     reference trainer's schedule (its interval is 1000); rows above a step's degree get zero gradients.  history["sh_degree"]: the
-    degree each step rendered at, one int per step."""
+    degree each step rendered at, one int per step.
+    feature_fn(v): the view's [H, W, feature_dim] map as decoded_loss takes its target.  None: no feature term.  Set, every step renders
+    twice, as the reference's Feature-3DGS trainer does: the SH colours, and render_latents of `features` [N, latent_dim] (splats["features"]
+    if the dict has it, zeros otherwise: the reference's start), which `decoder` [latent_dim, feature_dim] (the caller's -- its row
+    count then IS the latent dimension and the latent_dim keyword is not read -- or a torch.rand draw on the host from
+    torch.Generator().manual_seed(seed)) turns into the feature map; the step's loss is the
+    photometric loss + feature_weight * decoded_loss(render, decoder, feature_fn(v), loss=feature_loss), and its gradient reaches means,
+    rotation, scaling and opacity as well as the latents.  exp(scaling) and sigmoid(opacity) are computed once and handed to both
+    renders; of raster_kw the latent render takes the view's keywords (near_plane, far_plane, radius_clip, eps2d, rasterize_mode,
+    camera_model).  The densify statistics come from the colour render alone.  `features` is a leaf of the returned dict with an Adam
+    group of its own (lrs["features"], default 2.5e-3) and follows every round row by row like any other per-Gaussian table; the
+    decoder is NOT in the dict -- a round moves every tensor of N rows, and a decoder with latent_dim == N is no per-Gaussian table --
+    but in a second torch.optim.Adam (decoder_lr, eps 1e-15).  history gains feature_loss (the term before its weight, per step)
+    and decoder."""
+    from .decoded_field import decoded_loss
+    from .latent_render import render_latents
     from .mcmc import MCMCConfig, inject_noise, relocate, sample_add
     if strategy is not None and cfg is not None:
         raise GwbpError("train_scene() takes cfg= or strategy=, not both")
@@ -339,12 +381,24 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
     state = DensifyState(work["means"].shape[0], dev)
     carried = dict(carry or {})
     losses, sizes, rounds, resets = [], [], [], []
+    opt_dec, feature_losses = None, []
+    if feature_fn is not None:
+        work, decoder, opt_dec = _feature_leaves(work, opt, lrs, feature_dim, latent_dim, decoder, decoder_lr, seed)
+        latent_kw = {k: raster_kw[k] for k in LATENT_RENDER_KW if k in raster_kw}
     for step, v in enumerate(view_schedule(viewmats.shape[0], seed, steps)):
         opt.zero_grad(set_to_none=True)
         degrees.append(table_degree if interval is None else scheduled_sh_degree(step, interval, table_degree))
+        geometry, f_loss = (splat_geometry(work) if feature_fn is not None else None), None  # (one exp and one sigmoid for both renders)
         image, meta = render_splats(work, viewmats[v], view_K(K, v), width, height, return_meta=True, means2d_grad=mcmc is None,
-                                    sh_degree=None if interval is None else degrees[-1], **raster_kw)
+                                    sh_degree=None if interval is None else degrees[-1], geometry=geometry, **raster_kw)
         loss = photometric_loss(image, image_fn(v), ssim_lambda=ssim_lambda)
+        if feature_fn is not None:
+            opt_dec.zero_grad(set_to_none=True)
+            latent_map, _ = render_latents(*geometry, work["features"], viewmats[v], view_K(K, v), width, height, **latent_kw)
+            f_loss = decoded_loss(latent_map, decoder, feature_fn(v), loss=feature_loss)
+            feature_losses.append(f_loss.detach())
+            loss = loss + float(feature_weight) * f_loss
+            del latent_map
         if opacity_reg != 0.0:
             loss = loss + opacity_reg * torch.sigmoid(work["opacity"]).mean()
         if scale_reg != 0.0:
@@ -353,11 +407,13 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
         if mcmc is None and step < cfg.refine_stop_iter:
             state.update(meta)
         opt.step()
+        if opt_dec is not None:
+            opt_dec.step()
         losses.append(loss.detach())
         sizes.append(int(work["means"].shape[0]))
         if mcmc is not None:
             if mcmc.refines_at(step):
-                del image, meta, loss
+                del image, meta, loss, f_loss, geometry
                 n_before = sizes[-1]
                 work, moved = relocate(work, mcmc, optimizer=opt, carry=carried, generator=noise_gen)
                 work, added = sample_add(work, mcmc, mcmc.n_new(n_before), optimizer=opt, carry=moved["carry"], generator=noise_gen)
@@ -371,7 +427,7 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
                 inject_noise(work, rate, mcmc, generator=noise_gen)
             continue
         if cfg.refines_at(step):
-            del image, meta, loss  # (the graph holds the old set's workspace)
+            del image, meta, loss, f_loss, geometry  # (the graph holds the old set's workspace)
             work, info = densify(work, state, cfg, step, optimizer=opt, carry=carried, generator=noise_gen)
             carried = info["carry"]
             if info["n_after"] < 1:
@@ -383,6 +439,8 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
             resets.append(step)
     history = dict(loss=torch.stack(losses).cpu().tolist() if losses else [], n=sizes, rounds=rounds, resets=resets, carry=carried,
                    sh_degree=degrees)
+    if feature_fn is not None:
+        history.update(feature_loss=torch.stack(feature_losses).cpu().tolist() if feature_losses else [], decoder=decoder.detach())
     return {k: (t.detach() if torch.is_tensor(t) else t) for k, t in work.items()}, history
 
 

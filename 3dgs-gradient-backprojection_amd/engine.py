@@ -1173,6 +1173,29 @@ class Engine:
                    ptr(v_alpha), ptr(v_colors), ptr(v_g2d), self._stream())
         return v_colors, v_g2d
 
+    def render_dots_backward(self, view, colors, v_out, v_alpha=None):
+        """The geometry half of the blend backward for a float32 table colors [N, D], D <= 128 (gwbp_render_dots_backward; needs
+        project + bin_sort of `view`, not the weight store): v_g2d [N, 6] as render_pixels_backward returns it, from v_out [H, W, D]
+        (and v_alpha [H, W]).  The channels enter only through <colors_j, v_out_p>; the table's own gradient is scatter(view, v_out)
+        over the weight store of the forward render and is not computed here.  Float atomics: not bit-reproducible from run to run."""
+        colors, ct = field_rows(colors, "colors")
+        if ct != _lib.MAP_F32:
+            raise GwbpError(f"render_dots_backward reads a float32 colour table, got {colors.dtype}")
+        if colors.shape[0] != self.n:
+            raise GwbpError(f"engine was sized for {self.n} Gaussians, got a table of {colors.shape[0]} rows")
+        D = colors.shape[1]
+        v_out = _req(v_out, "v_out")
+        if tuple(v_out.shape) != (view.height, view.width, D):
+            raise GwbpError(f"v_out has shape {tuple(v_out.shape)}, expected {(view.height, view.width, D)}")
+        if v_alpha is not None:
+            v_alpha = _req(v_alpha, "v_alpha")
+            if v_alpha.numel() != view.height * view.width:
+                raise GwbpError(f"v_alpha has shape {tuple(v_alpha.shape)}, expected {(view.height, view.width)}")
+        v_g2d = torch.zeros(self.n, 6, device=self.device)
+        self._call("gwbp_render_dots_backward", *self._args(), byref(view), ptr(colors), c_int64(row_stride(colors)), D, ptr(v_out),
+                   ptr(v_alpha), ptr(v_g2d), self._stream())
+        return v_g2d
+
     def project_backward(self, view, means, quats, scales, opacities, v_g2d, needs=(True,) * 4, want_viewmat=False):
         """Backward of project (gwbp_project_backward; needs the projection of `view` and of these Gaussians in the workspace, which
         says which rows are visible): from v_g2d [N, 6] = d / d(mx, my, ca, cb, cc, o) of the projected records, as

@@ -50,15 +50,22 @@ def check_sh_degree_interval(interval, fn: str) -> Optional[int]:
     return interval
 
 
+def splat_geometry(splats: Dict[str, torch.Tensor]):
+    """(means, quats, scales, opacities) as the trainer renders them: scales = exp, opacities = sigmoid, raw quats."""
+    return (splats["means"], splats["rotation"], torch.exp(splats["scaling"]), torch.sigmoid(splats["opacity"]))
+
+
 def render_splats(splats: Dict[str, torch.Tensor], viewmat, K, width: int, height: int, return_meta: bool = False,
-                  sh_degree: Optional[int] = None, **raster_kw):
+                  sh_degree: Optional[int] = None, geometry=None, **raster_kw):
     """The [H, W, 3] image of a splat dict from one camera, as the trainer renders it: scales = exp, opacities = sigmoid, raw quats,
     the SH colours of features_dc and features_rest.  Differentiable in every tensor of the dict.
     sh_degree: the degree to evaluate, at most the one the tables' coefficient count gives (None: that one).  Below it the rows above
     (sh_degree + 1)^2 are not read, and their gradients are zeros, not None.
     The colours come from sh.sh_colors on the two tables as they are stored (no torch.cat, one HIP kernel forward and one backward) and
     go to rasterization() as an [N, 3] table; camera_grad=True is refused as rasterization() refuses it beside sh_degree.
-    return_meta: (image, meta) -- the eager part of rasterization()'s meta, which under means2d_grad=True holds the means2d leaf."""
+    return_meta: (image, meta) -- the eager part of rasterization()'s meta, which under means2d_grad=True holds the means2d leaf.
+    geometry: splat_geometry(splats) computed by the caller, who hands the same activations to a second render (train_scene's
+    feature term); None computes them here."""
     table = table_sh_degree(splats)
     degree = table if sh_degree is None else sh_degree
     if isinstance(degree, bool) or not isinstance(degree, int) or not 0 <= degree <= table:
@@ -66,7 +73,7 @@ def render_splats(splats: Dict[str, torch.Tensor], viewmat, K, width: int, heigh
     means, dc, rest = splats["means"], splats["features_dc"], splats.get("features_rest")
     if raster_kw.get("camera_grad") and torch.is_grad_enabled() and viewmat.requires_grad:
         raise NotImplementedError(SH_CAMERA_GRAD_MESSAGE)
-    geometry = (means, splats["rotation"], torch.exp(splats["scaling"]), torch.sigmoid(splats["opacity"]))
+    geometry = splat_geometry(splats) if geometry is None else geometry
     if not sh_kernel_enabled() or not means.is_cuda:  # (set_sh_kernel(False): the route before the kernels; CPU tensors: its error)
         sh = dc if rest is None else torch.cat([dc, rest], dim=1)
         out, _, meta = rasterization(*geometry, sh, viewmat[None], K[None], width, height, sh_degree=degree, want_meta=False, **raster_kw)

@@ -553,6 +553,20 @@ GWBP_API int gwbp_render_pixels_backward(const gwbp_caps *caps, void *workspace,
                                          const float *colors, int64_t ldc, int32_t D, const float *v_out, const float *v_alpha,
                                          float *v_colors, float *v_g2d, void *stream);
 
+/* The geometry half of that backward for tables of up to 128 channels: v_g2d alone, from the same workspace state (gwbp_project +
+ * gwbp_bin_sort of the view; the weight store is not read and nothing is written into the workspace).
+ *   colors float [N, ldc], 1 <= D <= 128, ldc >= D; v_out float [H, W, D] (dense); v_alpha float [H, W] or NULL.
+ *   v_g2d float [N, 6], ADDED INTO: as gwbp_render_pixels_backward defines it, with the same valid pairs and the same clamp rule.
+ * The channels enter d loss / d alpha of a (pixel, record j) pair only through m_j = <colors_j, v_out_p>:
+ *     v_alpha_j = T_j m_j - B_j / (1 - alpha_j) + T_final v_alpha_p / (1 - alpha_j),  B_j = sum over the records k behind j of alpha_k T_k m_k,
+ * so a pixel carries one scalar beside its v_out row.  d / d(colors) is NOT computed: it is gwbp_scatter of v_out over the weight
+ * store that a wide forward render (gwbp_blend_weights + gwbp_render) leaves.  Sums are float atomics in an order that is not fixed.
+ * After the caps, the workspace and the view: D outside [1, 128], a null colors, v_out or v_g2d, ldc < D or a pointer that is not 4-B
+ * aligned are GWBP_EINVAL before any HIP call. */
+GWBP_API int gwbp_render_dots_backward(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, const gwbp_view *view_host,
+                                       const float *colors, int64_t ldc, int32_t D, const float *v_out, const float *v_alpha,
+                                       float *v_g2d, void *stream);
+
 /* Backward of gwbp_project / gwbp_project_camera (gsplat's fully_fused_projection_bwd, and the view-matrix gradient with it): needs
  * the projection of the same view (same camera_model, rasterize_mode and Gaussians) in the workspace -- a row is visible when its
  * record there has radius > 0 -- and writes nothing into the workspace.

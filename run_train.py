@@ -7,6 +7,7 @@ the means every step (csrc/mcmc.hip), and the reference's opacity and scale regu
     python run_train.py --colmap data/garden/sparse/0 --images data/garden/images_4 --data-factor 4 --steps 7000 --out trained/
     python run_train.py --synthetic T0 --steps 60 --refine-start 10 --refine-every 10 --out /tmp/train
     python run_train.py --synthetic T0 --steps 60 --strategy mcmc --cap-max 300 --refine-start 10 --refine-every 10 --out /tmp/train
+    python run_train.py --synthetic T0 --steps 60 --feature-dim 32 --latent-dim 16 --out /tmp/train
 
 --colmap DIR: cameras.bin, images.bin and points3D.bin of a COLMAP sparse model; the start is its point cloud (gsbp_amd.
 init_splats_from_points).  --images DIR: per view the image <image name> itself (read with PIL when it imports), or <image name>.pt /
@@ -15,6 +16,12 @@ renders of the seeded scene with seeded colours, and the start is every --start-
 Writes into --out: trained.pt (the splat dict's tensors, pre-activation, under the reference's key names), history.json (the steps'
 losses and sizes, the rounds' counts, the resets) and metrics.json ({"before", "after"}: per-view and mean PSNR / SSIM / L1 / MSE,
 gsbp_amd.score_image_views).
+--feature-dim D adds the reference trainer's feature term (gsbp_amd.train_scene(feature_fn=...)): a second render per step, of a
+[N, --latent-dim] latent table that a [--latent-dim, D] decoder turns into the view's feature map, under --feature-weight x L1.  With
+--synthetic the maps are a hidden seeded latent field and decoder rendered on the true scene; with --colmap they are --feature-maps
+DIR/<image stem>.npy or .pt, [h, w, D], upsampled bilinearly to the view when smaller (as the reference upsamples its network's
+output); views without a map take no part.  Then --out also holds features.pt (the latents, and the decoder under "decoder"), and
+history.json the steps' feature losses.
 """
 import argparse
 import json
@@ -48,6 +55,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--sh-degree-interval", type=int, default=argparse.SUPPRESS, metavar="INTERVAL",
                     help="render step s at SH degree min(s // INTERVAL, the tables' degree), as the reference trainer does with "
                          "its interval of 1000 (default: off, every step at the full degree)")
+    ap.add_argument("--feature-dim", type=int, default=argparse.SUPPRESS, metavar="D",
+                    help="train a latent feature field beside the colours against feature maps of D channels")
+    ap.add_argument("--latent-dim", type=int, default=argparse.SUPPRESS, help="channels of the latent table (default 128)")
+    ap.add_argument("--feature-weight", type=float, default=argparse.SUPPRESS, help="weight of the feature term (default 1)")
+    ap.add_argument("--feature-maps", default=argparse.SUPPRESS, metavar="DIR", help="--colmap: <image stem>.npy / .pt per view")
     # the schedule (gsbp_amd.DensifyConfig; gsplat's defaults)
     ap.add_argument("--prune-opa", type=float, default=0.005)
     ap.add_argument("--grow-grad2d", type=float, default=2e-4)
@@ -73,6 +85,37 @@ def build_parser() -> argparse.ArgumentParser:
     return ap
 
 
+FEATURE_SEED = 1234  # --synthetic: the hidden latent field and decoder of the feature maps
+
+
+def feature_map_path(directory: str, name: str):
+    """The file of the view's feature map, <image stem>.pt or .npy, or None when the directory has neither."""
+    stem = os.path.splitext(name)[0]
+    for path in (os.path.join(directory, stem + ".pt"), os.path.join(directory, stem + ".npy")):
+        if os.path.isfile(path):
+            return path
+    return None
+
+
+def load_feature_map(directory: str, name: str, dev, width: int, height: int, dim: int):
+    """The view's feature map as float32 [H, W, dim] on the device, or None when the directory has none.  A map of another size is
+    resampled to the view on the device with F.interpolate(mode="bilinear"), as the reference resamples its feature network's output."""
+    path = feature_map_path(directory, name)
+    if path is None:
+        return None
+    if path.endswith(".pt"):
+        t = torch.load(path)
+    else:
+        import numpy as np
+        t = torch.from_numpy(np.load(path))
+    t = t.to(dev).float()
+    if t.dim() != 3 or t.shape[2] != dim:
+        raise SystemExit(f"{path}: expected [h, w, {dim}], got {tuple(t.shape)}")
+    if tuple(t.shape[:2]) != (height, width):
+        t = torch.nn.functional.interpolate(t.permute(2, 0, 1)[None], (height, width), mode="bilinear")[0].permute(1, 2, 0)
+    return t.contiguous()
+
+
 def camera_extent(viewmats: torch.Tensor) -> float:
     """The largest distance of a camera centre from the centres' mean (what gsplat's trainer multiplies by 1.1 for its scene scale)."""
     vm = viewmats.detach().double().cpu()
@@ -90,6 +133,12 @@ def main(argv=None) -> int:
         ap.error("--colmap needs --images")
     if args.steps < 1 or args.start_stride < 1:
         ap.error("--steps and --start-stride must be at least 1")
+    feature_dim = getattr(args, "feature_dim", None)
+    latent_dim = getattr(args, "latent_dim", 128)
+    if feature_dim is None and any(hasattr(args, k) for k in ("latent_dim", "feature_weight", "feature_maps")):
+        ap.error("--latent-dim, --feature-weight and --feature-maps need --feature-dim")
+    if feature_dim is not None and bool(args.colmap) != hasattr(args, "feature_maps"):
+        ap.error("--feature-dim takes its maps from --feature-maps with --colmap, and renders them itself with --synthetic")
     import gsbp_amd
     from gsbp_amd import scene_io, synthetic as syn
     from gsbp_amd.polish import render_splats
@@ -108,6 +157,15 @@ def main(argv=None) -> int:
         names = [f"view_{v:04d}" for v in range(viewmats.shape[0])]
         with torch.no_grad():
             images = [render_splats(full, viewmats[v], K, W, H, **kw).clamp(0.0, 1.0) for v in range(viewmats.shape[0])]
+        feature_maps = None
+        if feature_dim is not None:  # a hidden latent field and decoder, rendered on the true scene
+            gen = torch.Generator().manual_seed(FEATURE_SEED)
+            true_latents = torch.rand(n, latent_dim, generator=gen).to(dev)
+            true_decoder = (torch.rand(latent_dim, feature_dim, generator=gen) / latent_dim).to(dev)
+            geometry = (full["means"], full["rotation"], torch.exp(full["scaling"]), torch.sigmoid(full["opacity"]))
+            with torch.no_grad():
+                feature_maps = [gsbp_amd.render_latents(*geometry, true_latents, viewmats[v], K, W, H, **kw)[0] @ true_decoder
+                                for v in range(viewmats.shape[0])]
         splats = {k: t[::args.start_stride].contiguous() for k, t in full.items()}
         scene_scale = 1.0 if args.scene_scale is None else args.scene_scale
 
@@ -124,6 +182,11 @@ def main(argv=None) -> int:
         have = [v for v, name in enumerate(names) if load_image(args.images, name, "cpu") is not None]
         if not have:
             raise SystemExit(f"no image of this model's views in {args.images}")
+        feature_maps = None
+        if feature_dim is not None:
+            have = [v for v in have if feature_map_path(args.feature_maps, names[v]) is not None]
+            if not have:
+                raise SystemExit(f"no feature map of this model's views in {args.feature_maps}")
         viewmats, names = viewmats[have], [names[v] for v in have]
         splats = gsbp_amd.init_splats_from_points(torch.from_numpy(proj.points3D).float().to(dev),
                                                   torch.from_numpy(proj.point3D_colors).to(dev), sh_degree=args.sh_degree)
@@ -146,15 +209,32 @@ def main(argv=None) -> int:
                                      refine_every=args.refine_every, reset_every=args.reset_every,
                                      pause_refine_after_reset=args.pause_refine_after_reset, scene_scale=scene_scale,
                                      max_gaussians=args.max_gaussians)
+    feature_kw = {}
+    if feature_dim is not None:
+        loaded = {}  # --colmap: a view's map is read and resampled once, at the first step that takes the view, and kept
+
+        def feature_of(v):
+            if feature_maps is not None:
+                return feature_maps[v]
+            if v not in loaded:
+                loaded[v] = load_feature_map(args.feature_maps, names[v], dev, W, H, feature_dim)
+            return loaded[v]
+        feature_kw = dict(feature_fn=feature_of, feature_dim=feature_dim, latent_dim=latent_dim,
+                          feature_weight=getattr(args, "feature_weight", 1.0))
     before = gsbp_amd.score_image_views(splats, viewmats, K, W, H, image_of, **kw)
     n_start = splats["means"].shape[0]
     trained, history = gsbp_amd.train_scene(splats, viewmats, K, W, H, image_of, args.steps, strategy=cfg, params=args.params,
                                             ssim_lambda=args.ssim_lambda, seed=args.seed,
-                                            sh_degree_interval=getattr(args, "sh_degree_interval", None), **reg, **kw)
+                                            sh_degree_interval=getattr(args, "sh_degree_interval", None), **reg, **feature_kw, **kw)
     after = gsbp_amd.score_image_views(trained, viewmats, K, W, H, image_of, **kw)
     torch.save({k: t.cpu() for k, t in trained.items() if torch.is_tensor(t)}, os.path.join(args.out, "trained.pt"))
+    extra = {}
+    if feature_dim is not None:
+        torch.save(dict(features=trained["features"].cpu(), decoder=history["decoder"].cpu()), os.path.join(args.out, "features.pt"))
+        extra = dict(feature_loss=history["feature_loss"], feature_dim=feature_dim, latent_dim=latent_dim,
+                     feature_weight=feature_kw["feature_weight"])
     with open(os.path.join(args.out, "history.json"), "w") as f:
-        json.dump(dict(params=list(args.params), steps=args.steps, ssim_lambda=args.ssim_lambda, seed=args.seed, views=names,
+        json.dump(dict(**extra, params=list(args.params), steps=args.steps, ssim_lambda=args.ssim_lambda, seed=args.seed, views=names,
                        strategy=args.strategy, **reg, config={k: getattr(cfg, k) for k in cfg.__dataclass_fields__}, loss=history["loss"], n=history["n"],
                        rounds=history["rounds"], resets=history["resets"], sh_degree=history["sh_degree"]), f, indent=1)
     with open(os.path.join(args.out, "metrics.json"), "w") as f:
@@ -162,6 +242,8 @@ def main(argv=None) -> int:
     print(f"{n_start} -> {trained['means'].shape[0]} Gaussians in {len(history['rounds'])} rounds; loss {history['loss'][0]:.6e} -> "
           f"{history['loss'][-1]:.6e} over {len(history['loss'])} steps; mean PSNR {before['mean']['psnr']:.3f} -> "
           f"{after['mean']['psnr']:.3f} dB, SSIM {before['mean']['ssim']:.4f} -> {after['mean']['ssim']:.4f}")
+    if feature_dim is not None:
+        print(f"feature loss {history['feature_loss'][0]:.6e} -> {history['feature_loss'][-1]:.6e}; wrote features.pt")
     print(f"wrote {args.out}: trained.pt, history.json, metrics.json")
     return 0
 
