@@ -47,6 +47,8 @@ JojiJoseph/3dgs-gradient-backprojection), hand-written HIP kernels behind a C AB
                                                     # densification rule as HIP plan / emit / gather kernels
     from gsbp_amd import MCMCConfig, relocate, sample_add, inject_noise  # or under a fixed budget: gsplat's MCMC strategy
                                                     # (train_scene(strategy=MCMCConfig(cap_max=...))), HIP plan / draw / update / move
+    from gsbp_amd import SplatAdam                  # the optimiser step as one HIP kernel per table, optionally on the Gaussians a
+                                                    # step's view saw alone (train_scene(adam="fused" | "visible", means_lr_final=...))
     from gsbp_amd import render_latents             # the second render of a Feature-3DGS step: a latent table of up to 128 channels,
                                                     # differentiable in the Gaussians and the table (train_scene(feature_fn=...))
 """
@@ -91,6 +93,8 @@ from .polish import polish_scene, score_image_views  # noqa: F401
 from .densify import DensifyConfig, DensifyState, densify, init_splats_from_points, reset_opacity, train_scene  # noqa: F401
 from . import mcmc  # noqa: F401
 from .mcmc import MCMCConfig, inject_noise, relocate, sample_add  # noqa: F401
+from . import adam  # noqa: F401
+from .adam import SplatAdam  # noqa: F401
 from . import latent_render  # noqa: F401
 from .latent_render import render_latents  # noqa: F401
 from .pruning import check_proper_pruning, gradient_mask, prune_by_gradients  # noqa: F401

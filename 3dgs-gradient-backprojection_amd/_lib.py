@@ -276,6 +276,8 @@ ARGTYPES = {
     # v_colors, v_head, v_tail, v_means, stream
     "gwbp_sh_eval": [_I64, _I32, _I32, _I32, _P, _P, _P, C.POINTER(C.c_float), _P, _P],
     "gwbp_sh_eval_backward": [_I64, _I32, _I32, _I32, _P, _P, _P, C.POINTER(C.c_float), _P, _P, _P, _P, _P],
+    # the optimiser step: n, w, p, g, m, v, visible, lr_over_bc1, sqrt_bc2, b1, b2 (float64), eps, stream
+    "gwbp_adam_step": [_I64, _I32, _P, _P, _P, _P, _P, _F, _F, C.c_double, C.c_double, _F, _P],
 }
 # The typed forms of the entry points that read a finished [N, D] FIELD (or, gwbp_finalize_typed, write one): the untyped function's
 # arguments with the field's element type (GWBP_MAP_*, MAP_TYPES' codes) behind the field pointer.  A table of their own: they take no

@@ -2413,6 +2413,28 @@ int gwbp_sh_eval_backward(int64_t N, int32_t degree, int32_t K_head, int32_t K_t
                               as_stream(stream));
 }
 
+// ---- the optimiser step (adam.hip) ------------------------------------------------------------------------------------------------
+int gwbp_adam_step(int64_t n, int32_t w, float *p, const float *g, float *m, float *v, const uint8_t *visible, float lr_over_bc1,
+                   float sqrt_bc2, double b1, double b2, float eps, void *stream)
+{
+    if (int rc = check_densify_count("adam_step", n))
+        return rc;
+    if (w < 1)
+        return set_error(GWBP_EINVAL, "adam_step: w must be at least 1 (got %d)", (int)w);
+    if (!(lr_over_bc1 == lr_over_bc1) || !(sqrt_bc2 > 0.0f) || !(b1 >= 0.0 && b1 < 1.0) || !(b2 >= 0.0 && b2 < 1.0) || !(eps >= 0.0f))
+        return set_error(GWBP_EINVAL, "adam_step: bad scalars (lr_over_bc1 %g, sqrt_bc2 %g > 0, b1 %g and b2 %g in [0, 1), eps %g >= 0)",
+                         (double)lr_over_bc1, (double)sqrt_bc2, b1, b2, (double)eps);
+    if (n > 0 && (!p || !g || !m || !v))
+        return set_error(GWBP_EINVAL, "adam_step: null p, g, m or v");
+    if (misaligned(p, 15) || misaligned(g, 15) || misaligned(m, 15) || misaligned(v, 15))
+        return set_error(GWBP_EINVAL, "adam_step: p, g, m and v must be 16-B aligned");
+    const void *const written[] = {p, m, v}, *const read[] = {g, visible};
+    if (n > 0)
+        if (int rc = check_regions_distinct("adam_step", written, 3, read, 2))
+            return rc;
+    return launch_adam_step(n, w, p, g, m, v, visible, lr_over_bc1, sqrt_bc2, b1, b2, eps, as_stream(stream));
+}
+
 int gwbp_accumulate_stats(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, gwbp_stats *accum,
                           void *stream)
 {

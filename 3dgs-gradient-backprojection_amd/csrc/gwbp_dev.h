@@ -362,6 +362,10 @@ int launch_mcmc_zero_rows(int64_t N, int w, const int32_t *count, float *table, 
 int launch_mcmc_noise(int64_t N, float *means, const float *scaling, const float *rotation, const float *opacity, const float *z,
                       float scaler, hipStream_t s);
 int launch_mcmc_libm(int64_t N, int op, const float *a, const float *b, float *out, hipStream_t s);
+// one Adam step of a [N, w] table in place (adam.hip, adam_math.h); visible: uint8 [N] or nullptr (every row); b1, b2 in float64: the
+// launcher forms 1 - b1 and 1 - b2 there and rounds once
+int launch_adam_step(int64_t N, int w, float *p, const float *g, float *m, float *v, const uint8_t *visible, float lr_over_bc1,
+                     float sqrt_bc2, double b1, double b2, float eps, hipStream_t s);
 int launch_encode_map(const float *feats, int64_t fs_y, int64_t fs_x, int H, int W, int K, const float *enc, int n_out,
                       float *out, int workgroups, hipStream_t s);
 // ot (GWBP_MAP_*): the element type of out; a half out is the fp32 result rounded once to nearest even

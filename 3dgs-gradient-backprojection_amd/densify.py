@@ -17,8 +17,8 @@ moments among them.  One host read per round: the size of the new set.  Splat di
 (polish.py).  There is no PyTorch fallback: CPU tensors raise GwbpError.
 
 Not offered: absgrad, the radius criteria (grow_scale2d, prune_scale2d, refine_scale2d_stop_iter), revised_opacity, packed mode.
-gsplat's other strategy, MCMCStrategy, is mcmc.py; train_scene(strategy=MCMCConfig(...)) runs it (without packed mode and sparse
-gradients).
+gsplat's other strategy, MCMCStrategy, is mcmc.py; train_scene(strategy=MCMCConfig(...)) runs it (without packed mode; the
+counterpart of its sparse gradients is train_scene(adam="visible"): adam.SplatAdam steps the Gaussians a step's view saw).
 """
 from __future__ import annotations
 
@@ -33,8 +33,8 @@ from . import _lib
 from ._lib import GwbpError, ptr
 from ._views import ld, run
 from .photometric import photometric_loss
-from .polish import (PARAM_KEYS, check_sh_degree_interval, render_splats, scheduled_sh_degree, splat_geometry, table_sh_degree, trainable,
-                     view_K, view_schedule)
+from .polish import (PARAM_KEYS, check_adam, check_means_lr_final, check_sh_degree_interval, means_group, means_lr_at, render_splats,
+                     scheduled_sh_degree, splat_geometry, table_sh_degree, trainable, view_K, view_schedule)
 from .rasterization import release_engines
 
 GEOMETRY_KEYS = ("means", "scaling", "rotation", "opacity")  # what the emit kernel writes; every other [N, ...] tensor is gathered
@@ -328,7 +328,8 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
                 seed: int = 0, ssim_lambda: float = 0.2, carry: Optional[Dict[str, torch.Tensor]] = None, strategy=None,
                 opacity_reg: float = 0.0, scale_reg: float = 0.0, sh_degree_interval: Optional[int] = None,
                 feature_fn: Optional[Callable[[int], torch.Tensor]] = None, feature_dim: Optional[int] = None, latent_dim: int = 128,
-                feature_weight: float = 1.0, feature_loss: str = "l1", decoder_lr: float = 2.5e-3, decoder=None, **raster_kw):
+                feature_weight: float = 1.0, feature_loss: str = "l1", decoder_lr: float = 2.5e-3, decoder=None, adam: str = "torch",
+                means_lr_final: Optional[float] = None, **raster_kw):
     """polish_scene's loop with the schedule: Adam on the named parameters under the photometric loss, the set growing and shrinking
     on the way.  Step s (from 0) renders one view with means2d_grad=True, runs the backward, adds the view into the statistics while
     s < refine_stop_iter, steps the optimiser, runs a densify round when s > refine_start_iter, s % refine_every == 0 and
@@ -360,7 +361,19 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
     group of its own (lrs["features"], default 2.5e-3) and follows every round row by row like any other per-Gaussian table; the
     decoder is NOT in the dict -- a round moves every tensor of N rows, and a decoder with latent_dim == N is no per-Gaussian table --
     but in a second torch.optim.Adam (decoder_lr, eps 1e-15).  history gains feature_loss (the term before its weight, per step)
-    and decoder."""
+    and decoder.
+    adam: which optimiser steps the per-Gaussian tables.  "torch" (the default) is torch.optim.Adam, the code path before the keyword
+    existed.  "fused" is adam.SplatAdam: the same arithmetic, one HIP kernel per tensor.  "visible" hands SplatAdam the radii of the
+    step's colour render (which then runs with means2d_grad=True under the MCMC strategy too: that is what reports them), and only the
+    Gaussians the view saw (radii > 0) are stepped -- gsplat's SelectiveAdam, the reference trainer's sparse_grad.  For a Gaussian the
+    view did NOT see, nothing is read or written that step: its parameters and both Adam moments keep their bits, so the moments do
+    not decay and no stale momentum moves it, and the gradient opacity_reg / scale_reg give it (the only one it has) is not applied.
+    The step count, and with it the bias correction, advances for every table at every step.  The `features` leaf of the feature term
+    is in the same optimiser and takes the same mask (the same view, the same geometry); the decoder keeps its torch.optim.Adam.
+    means_lr_final: None, or the factor the means group's learning rate has decayed by at the end: step s of `steps` runs with
+    lr0 * means_lr_final ** (s / steps), computed on the host and written into the group before the optimiser steps -- the reference
+    trainer's schedule (its value is 0.01).  The MCMC noise, scaled by the group's current rate, follows it.  history["means_lr"] then
+    holds the rate of every step; no other group's rate changes, and without the keyword no rate is touched."""
     from .decoded_field import decoded_loss
     from .latent_render import render_latents
     from .mcmc import MCMCConfig, inject_noise, relocate, sample_add
@@ -372,7 +385,12 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
     cfg = strategy if isinstance(strategy, DensifyConfig) else cfg if cfg is not None else DensifyConfig()
     opacity_reg, scale_reg = float(opacity_reg), float(scale_reg)
     interval = check_sh_degree_interval(sh_degree_interval, "train_scene")
-    work, opt = trainable(splats, params, lrs, "train_scene")
+    final = check_means_lr_final(means_lr_final, "train_scene")
+    work, opt = trainable(splats, params, lrs, "train_scene", check_adam(adam, "train_scene"))
+    decayed = means_group(opt, work) if final is not None else None
+    if final is not None and decayed is None:
+        raise GwbpError("train_scene(): means_lr_final decays the means group's rate, and the means are not among params")
+    lr0, means_lrs = (None if decayed is None else decayed["lr"]), []
     table_degree, degrees = table_sh_degree(work), []
     dev, width, height = splats["means"].device, int(width), int(height)
     for key in GEOMETRY_KEYS:  # what the rounds write must be float32 whether it is trained or not
@@ -389,7 +407,8 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
         opt.zero_grad(set_to_none=True)
         degrees.append(table_degree if interval is None else scheduled_sh_degree(step, interval, table_degree))
         geometry, f_loss = (splat_geometry(work) if feature_fn is not None else None), None  # (one exp and one sigmoid for both renders)
-        image, meta = render_splats(work, viewmats[v], view_K(K, v), width, height, return_meta=True, means2d_grad=mcmc is None,
+        image, meta = render_splats(work, viewmats[v], view_K(K, v), width, height, return_meta=True,
+                                    means2d_grad=mcmc is None or adam == "visible",
                                     sh_degree=None if interval is None else degrees[-1], geometry=geometry, **raster_kw)
         loss = photometric_loss(image, image_fn(v), ssim_lambda=ssim_lambda)
         if feature_fn is not None:
@@ -406,7 +425,13 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
         loss.backward()
         if mcmc is None and step < cfg.refine_stop_iter:
             state.update(meta)
-        opt.step()
+        if decayed is not None:  # (the rounds swap a group's leaf, never the group: `decayed` stays the means' group)
+            decayed["lr"] = means_lr_at(lr0, final, step, int(steps))
+            means_lrs.append(decayed["lr"])
+        if adam == "visible":
+            opt.step(visible=meta["radii"])
+        else:
+            opt.step()
         if opt_dec is not None:
             opt_dec.step()
         losses.append(loss.detach())
@@ -439,6 +464,8 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
             resets.append(step)
     history = dict(loss=torch.stack(losses).cpu().tolist() if losses else [], n=sizes, rounds=rounds, resets=resets, carry=carried,
                    sh_degree=degrees)
+    if final is not None:
+        history["means_lr"] = means_lrs
     if feature_fn is not None:
         history.update(feature_loss=torch.stack(feature_losses).cpu().tolist() if feature_losses else [], decoder=decoder.detach())
     return {k: (t.detach() if torch.is_tensor(t) else t) for k, t in work.items()}, history

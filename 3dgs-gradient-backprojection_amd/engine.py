@@ -5,7 +5,7 @@ Everything is enqueued on torch's current HIP stream of the tensors' device; not
 """
 from __future__ import annotations
 
-from ctypes import byref, c_float, c_int64, c_size_t, c_void_p
+from ctypes import byref, c_double, c_float, c_int64, c_size_t, c_void_p
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -112,6 +112,37 @@ def sh_eval_tables_backward(call, stream, degree, means, head, tail, campos, v_c
     call("gwbp_sh_eval_backward", c_int64(means.shape[0]), int(degree), head.shape[1], 0 if tail is None else tail.shape[1], ptr(means),
          ptr(head), ptr(tail), cp, ptr(v_colors), ptr(v_head), ptr(v_tail), ptr(v_means), stream)
     return v_head, v_tail, v_means
+
+
+def adam_scalars(step: int, lr: float, b1: float, b2: float):
+    """(lr / (1 - b1^step), sqrt(1 - b2^step)) in float64, as torch's single-tensor Adam forms them on the host; the C ABI takes each
+    rounded to float32 once."""
+    return float(lr) / (1.0 - float(b1) ** int(step)), (1.0 - float(b2) ** int(step)) ** 0.5
+
+
+def adam_step_tables(call, stream, p, g, m, v, visible, step: int, lr: float, b1: float, b2: float, eps: float) -> None:
+    """Engine.adam_step for whoever brings the caller of the C ABI (call(name, *args)) and the stream handle."""
+    for name, t in (("p", p), ("g", g), ("m", m), ("v", v)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise GwbpError(f"adam_step: {name} must be a HIP tensor (there is no CPU path)")
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise GwbpError(f"adam_step: {name} must be a contiguous float32 tensor, got {t.dtype}, strides {tuple(t.stride())}")
+        if t.shape != p.shape or t.device != p.device:
+            raise GwbpError(f"adam_step: {name} is {tuple(t.shape)} on {t.device} beside p {tuple(p.shape)} on {p.device}")
+    if isinstance(step, bool) or int(step) != step or step < 1:
+        raise GwbpError(f"adam_step: the step count must be a positive int, got {step!r}")
+    n = int(p.shape[0]) if p.dim() else 1
+    w = p.numel() // n if n else 1
+    if n == 0 or w == 0:
+        return
+    if visible is not None:
+        if (not torch.is_tensor(visible) or visible.dtype not in (torch.uint8, torch.bool) or visible.device != p.device
+                or tuple(visible.shape) != (n,) or not visible.is_contiguous()):
+            raise GwbpError(f"adam_step: visible must be a contiguous uint8 or bool tensor [{n}] on {p.device}")
+        visible = visible.view(torch.uint8)
+    step_size, sqrt_bc2 = adam_scalars(step, lr, b1, b2)
+    call("gwbp_adam_step", c_int64(n), int(w), ptr(p), ptr(g), ptr(m), ptr(v), ptr(visible), c_float(step_size), c_float(sqrt_bc2),
+         c_double(float(b1)), c_double(float(b2)), c_float(float(eps)), stream)
 
 
 def field_rows(t: torch.Tensor, name: str):
@@ -1350,6 +1381,13 @@ class Engine:
         degree 0.  No atomics: the same bits every run."""
         return sh_eval_tables_backward(self._call, self._stream(), degree, means, head, tail, campos, v_colors, want_head, want_tail,
                                        want_means)
+
+    def adam_step(self, p, g, m, v, step: int, lr: float, b1: float = 0.9, b2: float = 0.999, eps: float = 1e-8, visible=None) -> None:
+        """One Adam step of the float32 table p [n, ...] IN PLACE from its gradient g, with the moments m and v (gwbp_adam_step;
+        torch.optim.Adam's arithmetic with weight_decay = 0, amsgrad = False, maximize = False), on this engine's stream.  step: the
+        count t >= 1 of this step; the bias corrections are formed on the host in float64, nothing is read back.  visible: None, or a
+        uint8 / bool [n]: rows whose entry is zero keep the bits of p, m and v.  SplatAdam is the optimiser built on it."""
+        adam_step_tables(self._call, self._stream(), p, g, m, v, visible, step, lr, b1, b2, eps)
 
     # ---- the view's RGB render for the 2-D network (create_feature_field(render_colors=...)) ----------------------------------
     @staticmethod

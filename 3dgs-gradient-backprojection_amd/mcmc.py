@@ -18,7 +18,8 @@ none per add round.  There is no PyTorch fallback: CPU tensors raise GwbpError.
 
 What differs from gsplat: the sampling weights are the integers floor(opacity 2^24); the draws are sorted, so the
 j-th dead Gaussian in index order gets the j-th parent in index order instead of multinomial order; o'^(k+1) is a running product.
-Not offered: packed mode, sparse gradients, the binomial table beyond n_max = 51.
+Not offered: packed mode, sparse gradient tensors (train_scene(adam="visible") steps the visible rows of dense ones), the binomial
+table beyond n_max = 51.
 """
 from __future__ import annotations
 

@@ -88,9 +88,40 @@ def view_K(K, v):
     return K if K.dim() == 2 else K[v]
 
 
-def trainable(splats: Dict[str, torch.Tensor], params: Sequence[str], lrs: Optional[Dict[str, float]], fn: str):
+ADAM_KINDS = ("torch", "fused", "visible")
+
+
+def check_adam(adam, fn: str) -> str:
+    if adam not in ADAM_KINDS:
+        raise GwbpError(f"{fn}(): adam must be one of {list(ADAM_KINDS)}, got {adam!r}")
+    return adam
+
+
+def check_means_lr_final(value, fn: str) -> Optional[float]:
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not (0.0 < float(value) and math.isfinite(float(value))):
+        raise GwbpError(f"{fn}(): means_lr_final must be None or a positive finite number, got {value!r}")
+    return float(value)
+
+
+def means_lr_at(lr0: float, final: float, step: int, steps: int) -> float:
+    """The means group's learning rate of step `step` (from 0) of `steps`: lr0 * final ** (step / steps), the reference trainer's
+    exponential decay (its final is 0.01), in closed form on the host."""
+    return float(lr0) * float(final) ** (step / steps)
+
+
+def means_group(opt, work: Dict[str, torch.Tensor]):
+    """The optimiser's group that holds work["means"], or None when the means are not trained."""
+    return next((g for g in opt.param_groups if g["params"][0] is work["means"]), None)
+
+
+def trainable(splats: Dict[str, torch.Tensor], params: Sequence[str], lrs: Optional[Dict[str, float]], fn: str, adam: str = "torch"):
     """(work, optimizer) of fn(): `splats` detached, each named parameter a float32 leaf of its own, and torch.optim.Adam with ONE
-    tensor per group at lrs[name] over DEFAULT_LRS, eps 1e-15 as in the reference trainer (densify._relocate_adam relies on that layout)."""
+    tensor per group at lrs[name] over DEFAULT_LRS, eps 1e-15 as in the reference trainer (densify._relocate_adam relies on that layout).
+    adam: "torch" is that optimiser; "fused" and "visible" build adam.SplatAdam over the same groups (one HIP kernel per tensor; the
+    caller of "visible" hands step() the view's radii)."""
+    check_adam(adam, fn)
     unknown = [p for p in params if p not in PARAM_KEYS]
     if unknown or not params:
         raise GwbpError(f"params must be names out of {sorted(PARAM_KEYS)}, got {list(params)}")
@@ -107,6 +138,9 @@ def trainable(splats: Dict[str, torch.Tensor], params: Sequence[str], lrs: Optio
             raise GwbpError(f"the splat dict has no {key!r} (parameter {name!r})")
         work[key] = work[key].float().clone().requires_grad_(True)
         groups.append(dict(params=[work[key]], lr=float(rates[name])))
+    if adam != "torch":
+        from .adam import SplatAdam
+        return work, SplatAdam(groups, eps=1e-15)
     return work, torch.optim.Adam(groups, eps=1e-15)
 
 
@@ -123,6 +157,7 @@ def view_schedule(n_views: int, seed: int, steps: int):
 def polish_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, image_fn: Callable[[int], torch.Tensor],
                  params: Sequence[str] = ("opacities", "sh0"), steps: int = 300, ssim_lambda: float = 0.2,
                  lrs: Optional[Dict[str, float]] = None, seed: int = 0, sh_degree_interval: Optional[int] = None,
+                 adam: str = "torch", means_lr_final: Optional[float] = None,
                  **raster_kw) -> Tuple[Dict[str, torch.Tensor], List[float]]:
     """Adam on the named parameters of `splats` against the views' images.  Returns (a new splat dict -- the named tensors replaced by
     their polished values, the others shared -- and the steps' losses, read from the device once behind the loop).
@@ -131,18 +166,38 @@ def polish_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, im
     host as a fresh permutation per pass over the views.  image_fn(v): the view's float32 [H, W, 3] image in [0, 1] on the device.
     viewmats [V, 4, 4]; K [3, 3] or [V, 3, 3].  raster_kw: camera_model, rasterize_mode and the other keywords of rasterization().
     sh_degree_interval: None renders every step at the tables' SH degree; an int renders step s (from 0) at min(s // interval, that
-    degree), the reference trainer's schedule (its interval is 1000).  Coefficient rows above a step's degree get zero gradients."""
+    degree), the reference trainer's schedule (its interval is 1000).  Coefficient rows above a step's degree get zero gradients.
+    adam: "torch" steps torch.optim.Adam (the default, and the code path before the keyword existed); "fused" steps adam.SplatAdam, the
+    same arithmetic in one HIP kernel per tensor; "visible" steps it on the Gaussians the step's view saw (radii > 0; the step then
+    renders with means2d_grad=True, which is what reports the radii): a Gaussian the view did not see keeps every bit of its parameters
+    and of both Adam moments -- the moments do not decay, and no stale momentum moves it.
+    means_lr_final: None, or the factor the means group's learning rate has decayed by at the end: step s of `steps` runs with
+    lr0 * means_lr_final ** (s / steps), the reference trainer's schedule (its value is 0.01); no other group's rate changes."""
     interval = check_sh_degree_interval(sh_degree_interval, "polish_scene")
-    work, opt = trainable(splats, params, lrs, "polish_scene")
+    final = check_means_lr_final(means_lr_final, "polish_scene")
+    work, opt = trainable(splats, params, lrs, "polish_scene", adam)
     width, height, losses = int(width), int(height), []
     table = table_sh_degree(work)
+    decayed = means_group(opt, work) if final is not None else None
+    if final is not None and decayed is None:
+        raise GwbpError("polish_scene(): means_lr_final decays the means group's rate, and the means are not among params")
+    lr0 = None if decayed is None else decayed["lr"]
     for step, v in enumerate(view_schedule(viewmats.shape[0], seed, steps)):
         opt.zero_grad(set_to_none=True)
-        image = render_splats(work, viewmats[v], view_K(K, v), width, height, sh_degree=scheduled_sh_degree(step, interval, table),
-                              **raster_kw)
+        if adam == "visible":
+            image, meta = render_splats(work, viewmats[v], view_K(K, v), width, height, return_meta=True, means2d_grad=True,
+                                        sh_degree=scheduled_sh_degree(step, interval, table), **raster_kw)
+        else:
+            image = render_splats(work, viewmats[v], view_K(K, v), width, height, sh_degree=scheduled_sh_degree(step, interval, table),
+                                  **raster_kw)
         loss = photometric_loss(image, image_fn(v), ssim_lambda=ssim_lambda)
         loss.backward()
-        opt.step()
+        if decayed is not None:
+            decayed["lr"] = means_lr_at(lr0, final, step, int(steps))
+        if adam == "visible":
+            opt.step(visible=meta["radii"])
+        else:
+            opt.step()
         losses.append(loss.detach())
     history = torch.stack(losses).cpu().tolist() if losses else []
     return {k: (t.detach() if torch.is_tensor(t) else t) for k, t in work.items()}, history

@@ -20,7 +20,7 @@ from ._lib import GwbpError, check
 from .engine import sh_eval_tables, sh_eval_tables_backward
 
 
-def _caller(device):
+def device_caller(device):
     def call(name: str, *args):
         fn = getattr(_lib.lib(), name)
         if device.index is None or torch.cuda.current_device() == device.index:
@@ -34,7 +34,7 @@ def _caller(device):
 class _ShColors(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means, head, tail, degree, campos):
-        call, stream = _caller(means.device)
+        call, stream = device_caller(means.device)
         out = sh_eval_tables(call, stream, degree, means, head, tail, campos)
         ctx.save_for_backward(means, head, tail)
         ctx.degree, ctx.campos = degree, campos
@@ -52,7 +52,7 @@ class _ShColors(torch.autograd.Function):
             return torch.zeros_like(means), None, v_tail, None, None  # (no dependence on the means at degree 0)
         v_head = v_means = None
         if want_head or want_tail or want_means:
-            call, stream = _caller(means.device)
+            call, stream = device_caller(means.device)
             v_head, v_t, v_means = sh_eval_tables_backward(call, stream, ctx.degree, means, head, tail, ctx.campos, v_colors, want_head,
                                                            want_tail, want_means)
             v_tail = v_t if want_tail else v_tail

@@ -1342,6 +1342,20 @@ GWBP_API int gwbp_mcmc_noise(int64_t n, float *means, const float *scaling, cons
                              const float *z, float scaler, void *stream);
 GWBP_API int gwbp_mcmc_libm(int64_t n, int32_t op, const float *a, const float *b, float *out, void *stream);
 
+/* ---- the optimiser step of training: Adam on one table, with an optional row mask (csrc/adam.hip) ----
+ * gwbp_adam_step  p, m, v (float32 [n, w], dense, IN PLACE) from the gradient g [n, w], as torch.optim.Adam does with weight_decay = 0,
+ *     amsgrad = False, maximize = False; csrc/adam_math.h holds the expressions in their order:
+ *         m' = m + (1 - b1) (g - m);  v' = b2 v + ((1 - b2) g) g;  p' = p - lr_over_bc1 (m' / (sqrtf(v') / sqrt_bc2 + eps))
+ *     lr_over_bc1 = lr / (1 - b1^t) and sqrt_bc2 = sqrt(1 - b2^t) of the step count t are the caller's, computed in float64 and rounded
+ *     once; b1 and b2 are float64 so that 1 - b1 and 1 - b2 are formed there and rounded once.  Nothing is read back, nothing waits.
+ *     visible == NULL: every row.  Otherwise uint8 [n]: row i is updated where visible[i] != 0, and the bits of p, m and v of every
+ *     other row stay as they are; a 16-B chunk whose rows are all invisible is neither loaded nor stored.
+ *     g == 0 where m == v == 0 leaves the bits of p, m and v (eps > 0).  No atomics: the same inputs give the same bits.
+ * GWBP_EINVAL before any HIP call: n outside [0, 2^31 - 1], w < 1, a NaN lr_over_bc1, sqrt_bc2 <= 0, b1 or b2 outside [0, 1), eps < 0,
+ * a null p, g, m or v where n > 0, one of them not 16-B aligned, p, m, v not distinct or one of them g or visible.  n = 0: nothing. */
+GWBP_API int gwbp_adam_step(int64_t n, int32_t w, float *p, const float *g, float *m, float *v, const uint8_t *visible,
+                            float lr_over_bc1, float sqrt_bc2, double b1, double b2, float eps, void *stream);
+
 /* Adds this view's counters into `accum` (device, gwbp_stats) -- used by bench/driver to total pairs. */
 GWBP_API int gwbp_accumulate_stats(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, gwbp_stats *accum,
                           void *stream);

@@ -41,6 +41,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--sh-degree-interval", type=int, default=argparse.SUPPRESS, metavar="INTERVAL",
                     help="render step s at SH degree min(s // INTERVAL, the tables' degree), as the reference trainer does with "
                          "its interval of 1000 (default: off, every step at the full degree)")
+    ap.add_argument("--adam", choices=("torch", "fused", "visible"), default=argparse.SUPPRESS,
+                    help="the optimiser step: torch.optim.Adam (the default), the fused HIP kernel, or that kernel on the Gaussians "
+                         "each step's view saw (the others keep their parameters and Adam moments)")
+    ap.add_argument("--means-lr-final", type=float, default=argparse.SUPPRESS, metavar="FACTOR",
+                    help="decay the means' learning rate exponentially to FACTOR of its start over the run, as the reference trainer "
+                         "does with 0.01 (default: off)")
     ap.add_argument("--out", default="./results/polish")
     return ap
 
@@ -107,7 +113,8 @@ def main(argv=None) -> int:
     before = gsbp_amd.score_image_views(splats, viewmats, K, W, H, image_of, **kw)
     polished, history = gsbp_amd.polish_scene(splats, viewmats, K, W, H, image_of, params=args.params, steps=args.steps,
                                               ssim_lambda=args.ssim_lambda, seed=args.seed,
-                                              sh_degree_interval=getattr(args, "sh_degree_interval", None), **kw)
+                                              sh_degree_interval=getattr(args, "sh_degree_interval", None),
+                                              **{k: getattr(args, k) for k in ("adam", "means_lr_final") if hasattr(args, k)}, **kw)
     after = gsbp_amd.score_image_views(polished, viewmats, K, W, H, image_of, **kw)
     torch.save({k: t.cpu() for k, t in polished.items()}, os.path.join(args.out, "polished.pt"))
     with open(os.path.join(args.out, "history.json"), "w") as f:

@@ -55,6 +55,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--sh-degree-interval", type=int, default=argparse.SUPPRESS, metavar="INTERVAL",
                     help="render step s at SH degree min(s // INTERVAL, the tables' degree), as the reference trainer does with "
                          "its interval of 1000 (default: off, every step at the full degree)")
+    ap.add_argument("--adam", choices=("torch", "fused", "visible"), default=argparse.SUPPRESS,
+                    help="the optimiser step: torch.optim.Adam (the default), the fused HIP kernel, or that kernel on the Gaussians "
+                         "each step's view saw (the others keep their parameters and Adam moments)")
+    ap.add_argument("--means-lr-final", type=float, default=argparse.SUPPRESS, metavar="FACTOR",
+                    help="decay the means' learning rate exponentially to FACTOR of its start over the run, as the reference trainer "
+                         "does with 0.01 (default: off)")
     ap.add_argument("--feature-dim", type=int, default=argparse.SUPPRESS, metavar="D",
                     help="train a latent feature field beside the colours against feature maps of D channels")
     ap.add_argument("--latent-dim", type=int, default=argparse.SUPPRESS, help="channels of the latent table (default 128)")
@@ -225,7 +231,8 @@ def main(argv=None) -> int:
     n_start = splats["means"].shape[0]
     trained, history = gsbp_amd.train_scene(splats, viewmats, K, W, H, image_of, args.steps, strategy=cfg, params=args.params,
                                             ssim_lambda=args.ssim_lambda, seed=args.seed,
-                                            sh_degree_interval=getattr(args, "sh_degree_interval", None), **reg, **feature_kw, **kw)
+                                            sh_degree_interval=getattr(args, "sh_degree_interval", None), **reg, **feature_kw,
+                                            **{k: getattr(args, k) for k in ("adam", "means_lr_final") if hasattr(args, k)}, **kw)
     after = gsbp_amd.score_image_views(trained, viewmats, K, W, H, image_of, **kw)
     torch.save({k: t.cpu() for k, t in trained.items() if torch.is_tensor(t)}, os.path.join(args.out, "trained.pt"))
     extra = {}
@@ -236,7 +243,9 @@ def main(argv=None) -> int:
     with open(os.path.join(args.out, "history.json"), "w") as f:
         json.dump(dict(**extra, params=list(args.params), steps=args.steps, ssim_lambda=args.ssim_lambda, seed=args.seed, views=names,
                        strategy=args.strategy, **reg, config={k: getattr(cfg, k) for k in cfg.__dataclass_fields__}, loss=history["loss"], n=history["n"],
-                       rounds=history["rounds"], resets=history["resets"], sh_degree=history["sh_degree"]), f, indent=1)
+                       rounds=history["rounds"], resets=history["resets"], sh_degree=history["sh_degree"],
+                       **({"adam": args.adam} if hasattr(args, "adam") else {}),
+                       **({"means_lr": history["means_lr"]} if "means_lr" in history else {})), f, indent=1)
     with open(os.path.join(args.out, "metrics.json"), "w") as f:
         json.dump(dict(before=before, after=after), f, indent=1)
     print(f"{n_start} -> {trained['means'].shape[0]} Gaussians in {len(history['rounds'])} rounds; loss {history['loss'][0]:.6e} -> "

@@ -1,0 +1,200 @@
+"""train_scene and polish_scene under adam="fused" and adam="visible", and the means' learning-rate decay.
+
+The one-step tests run on the 32 x 16 pixels at the centre of T0's views, for two reasons.  The crop leaves part of the scene outside the
+frustum (the numpy reference projection says how much; the test asserts the share), which is what "visible" is about.  And on two tiles
+training is reproducible bit for bit (tests/test_gpu_mcmc.py, test_the_default_path_is_unchanged: the blend backward's float atomics
+add at most two partial sums onto zero), so that three runs from the same start -- torch's Adam, the fused step, and the replica of
+the step written out below to get at the gradients and the moments -- see the same gradient bits.
+
+TRAIN_FACTOR.  One step of adam="fused" against adam="torch" from the same start and the same gradient, the float64 chain on that
+gradient as the truth: measured on an MI355X over the six tables x 2 figures, ratios 0.223 .. 0.562 (the largest on the max-abs
+figure of the opacities); TRAIN_FACTOR = ceil(2 x 0.562) = 2.
+
+The 60-step runs (four densify rounds; five MCMC rounds): mean loss of the last pass over the views / of the first, measured on an
+MI355X -- densify: fused 0.9640, visible 0.9681, torch 0.9640; MCMC: fused 0.6116, visible 0.6135, torch 0.6116.  Asserted: fused and
+visible below 1; the settings are not asserted against each other.  The densify runs cap the set at 512 Gaussians, the size of the
+scene the target images were rendered from (the start is every second Gaussian of it): gsplat's default grow threshold is set for
+real scenes, under it T0 doubles at every round (256 -> 492 -> 965 -> 1876 -> 3639), and the split noise of a round ten steps before
+the end then outweighs what sixty steps have learnt -- under torch's Adam exactly as under the fused step (1.3165 both, 1.3238 visible).
+"""
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import adam_ref
+import gsbp_amd
+import ref_np
+from gsbp_amd.polish import DEFAULT_LRS, PARAM_KEYS, means_lr_at, render_splats, trainable
+from test_gpu_densify import t0_training_setup
+from test_mcmc_cpu import same_bits
+
+pytestmark = pytest.mark.gpu
+TRAIN_FACTOR = 2.0
+CROP_W, CROP_H = 32, 16
+KEYS = tuple(PARAM_KEYS.values())
+
+
+@pytest.fixture(scope="module")
+def crop(dev):
+    """T0's training setup seen through the centre crop, with SH tables of degree 1 so that features_rest is a trained table too."""
+    cfg, start, K, vms, images = t0_training_setup(dev)
+    n = start["means"].shape[0]
+    start = dict(start, features_rest=0.05 * torch.randn(n, 3, 3, generator=torch.Generator().manual_seed(11)).to(dev))
+    x0, y0 = (cfg.width - CROP_W) // 2, (cfg.height - CROP_H) // 2
+    Kc = K.clone()
+    Kc[0, 2] -= x0
+    Kc[1, 2] -= y0
+    crops = [im[y0:y0 + CROP_H, x0:x0 + CROP_W].contiguous() for im in images]
+    return cfg, start, Kc, vms, crops
+
+
+def replica_step(start, vms, Kc, crops, v, adam):
+    """The first step of train_scene(adam=...) written out, to reach what it does not return: (work, optimiser, radii [N], the
+    gradients, the tables before the step)."""
+    work, opt = trainable(start, tuple(PARAM_KEYS), None, "train_scene", adam)
+    before = {k: work[k].detach().clone() for k in KEYS}
+    image, meta = render_splats(work, vms[v], Kc, CROP_W, CROP_H, return_meta=True, means2d_grad=True)
+    gsbp_amd.photometric_loss(image, crops[v]).backward()
+    grads = {k: work[k].grad.detach().clone() for k in KEYS}
+    if adam == "visible":
+        opt.step(visible=meta["radii"])
+    else:
+        opt.step()
+    return work, opt, meta["radii"][0].clone(), grads, before
+
+
+def first_view(n_views, seed):
+    return next(iter(gsbp_amd.polish.view_schedule(n_views, seed, 1)))
+
+
+def test_one_visible_step_touches_the_rows_the_view_saw_and_no_other(dev, crop):
+    cfg, start, Kc, vms, crops = crop
+    v = first_view(vms.shape[0], 3)
+    # the view, chosen on the CPU: the numpy reference projection of the start through the crop
+    means, quats, scales, _ = (t.cpu().numpy() for t in gsbp_amd.polish.splat_geometry(start))
+    ok = ref_np.project(means, quats, scales, vms[v].cpu().numpy(), Kc.cpu().numpy(), CROP_W, CROP_H)["ok"]
+    share = 1.0 - ok.mean()
+    print(f"view {v} through the {CROP_W} x {CROP_H} crop: {share:.3f} of {len(ok)} Gaussians have radii == 0")
+    assert 0.10 <= share <= 0.90
+    trained, hist = gsbp_amd.train_scene(start, vms, Kc, CROP_W, CROP_H, lambda i: crops[i], 1, seed=3, adam="visible")
+    work, opt, radii, grads, before = replica_step(start, vms, Kc, crops, v, "visible")
+    unseen = (radii == 0).cpu().numpy()
+    # (the device projects in float32: a Gaussian whose radius just reaches the crop's edge may fall on the other side there)
+    assert (unseen != ~ok).mean() <= 0.02 and 0.10 <= unseen.mean() <= 0.90
+    assert hist["n"] == [len(ok)] and "means_lr" not in hist
+    for k in KEYS:
+        old, new, g = before[k].cpu().numpy(), trained[k].cpu().numpy(), grads[k].cpu().numpy().reshape(len(ok), -1)
+        assert same_bits(new[unseen], old[unseen]), k                       # rows the view did not see: every bit
+        moved = (new != old).reshape(len(ok), -1).any(1)
+        live = ~unseen & (g != 0).any(1)
+        assert live.sum() > 10 and moved[live].all(), (k, int(live.sum()), int((live & ~moved).sum()))
+        # the replica is the same step (two tiles: the same bits), and its moments say the same
+        assert same_bits(work[k].detach().cpu().numpy(), new), k
+        st = opt.state[work[k]]
+        for name in ("exp_avg", "exp_avg_sq"):
+            m = st[name].cpu().numpy().reshape(len(ok), -1)
+            assert not m[unseen].view(np.uint32).any() and (m[live] != 0).any(1).all(), (k, name)
+        assert float(st["step"]) == 1.0
+    # a second step from the other view: rows it does not see keep the parameters AND the non-zero moments the first step left
+    keep = {k: (work[k].detach().clone(), opt.state[work[k]]["exp_avg"].clone(), opt.state[work[k]]["exp_avg_sq"].clone()) for k in KEYS}
+    opt.zero_grad(set_to_none=True)
+    image, meta = render_splats(work, vms[1 - v], Kc, CROP_W, CROP_H, return_meta=True, means2d_grad=True)
+    (gsbp_amd.photometric_loss(image, crops[1 - v]) + 0.01 * torch.sigmoid(work["opacity"]).mean()).backward()
+    opt.step(visible=meta["radii"])
+    unseen2 = meta["radii"][0] == 0
+    held = unseen2 & (radii > 0)
+    assert int(held.sum()) > 10 and bool(work["opacity"].grad[unseen2].ne(0).all())  # (the regulariser's gradient, not applied)
+    for k in KEYS:
+        st = opt.state[work[k]]
+        for got, want in zip((work[k].detach(), st["exp_avg"], st["exp_avg_sq"]), keep[k]):
+            assert torch.equal(got[unseen2], want[unseen2]), k
+        assert bool(keep[k][1][held].ne(0).any()) and float(st["step"]) == 2.0
+
+
+def test_one_fused_step_against_one_torch_step_by_the_floor_rule(dev, crop):
+    cfg, start, Kc, vms, crops = crop
+    v = first_view(vms.shape[0], 3)
+
+    def run(adam):
+        return gsbp_amd.train_scene(start, vms, Kc, CROP_W, CROP_H, lambda i: crops[i], 1, seed=3, adam=adam)[0]
+    fused, plain = run("fused"), run("torch")
+    _, _, _, grads, before = replica_step(start, vms, Kc, crops, v, "fused")
+    lo, hi = float("inf"), 0.0
+    for name, k in PARAM_KEYS.items():
+        p0, g = before[k].cpu().numpy(), grads[k].cpu().numpy()
+        zero = np.zeros_like(p0)
+        truth = dict(zip(("p", "m", "v"), adam_ref.chain64(p0, g, zero, zero, 1, DEFAULT_LRS[name])))
+        r = adam_ref.ratios(dict(truth, p=fused[k].cpu().numpy()), truth, dict(truth, p=plain[k].cpu().numpy()))
+        r = {key: val for key, val in r.items() if key[0] == "p"}
+        worst = max(r, key=r.get)
+        print(f"{k}: fused / torch, largest {r[worst]:.3f} at {worst}")
+        lo, hi = min(lo, min(r.values())), max(hi, r[worst])
+        assert r[worst] <= TRAIN_FACTOR, (k, r)
+        assert not np.array_equal(fused[k].cpu().numpy(), p0)
+    print(f"fused / torch over the six tables: {lo:.3f} .. {hi:.3f}")
+
+
+def pass_ratio(losses, n_views):
+    return float(np.mean(losses[-n_views:]) / np.mean(losses[:n_views]))
+
+
+@pytest.mark.parametrize("adam", ["fused", "visible"])
+@pytest.mark.parametrize("strategy", ["densify", "mcmc"])
+def test_sixty_steps_with_rounds(dev, strategy, adam):
+    cfg, start, K, vms, images = t0_training_setup(dev)
+    n0 = start["means"].shape[0]
+    if strategy == "densify":
+        kw = dict(strategy=gsbp_amd.DensifyConfig(refine_start_iter=5, refine_every=10, refine_stop_iter=50, max_gaussians=2 * n0))
+        steps_of_rounds = [10, 20, 30, 40]
+    else:
+        kw = dict(strategy=gsbp_amd.MCMCConfig(refine_start_iter=5, refine_every=10, cap_max=290), opacity_reg=0.01, scale_reg=0.01)
+        steps_of_rounds = [10, 20, 30, 40, 50]
+    trained, hist = gsbp_amd.train_scene(start, vms, K, cfg.width, cfg.height, lambda v: images[v], 60, seed=3, adam=adam, **kw)
+    sizes, rounds = hist["n"], hist["rounds"]
+    assert len(hist["loss"]) == len(sizes) == 60 and [r["step"] for r in rounds] == steps_of_rounds and sizes[0] == n0
+    for r in rounds:
+        assert sizes[r["step"]] == r["n_before"] and sizes[r["step"] + 1] == r["n_after"]
+    assert trained["means"].shape[0] == rounds[-1]["n_after"] == sizes[-1]
+    if strategy == "mcmc":
+        assert sizes[-1] == 290 and rounds[0]["added"] == int(1.05 * n0) - n0
+    assert all(np.isfinite(hist["loss"])) and all(bool(torch.isfinite(trained[k]).all()) for k in KEYS if k in trained)
+    ratio = pass_ratio(hist["loss"], vms.shape[0])
+    print(f"T0, 60 steps, {strategy}, adam={adam}: N {n0} -> {sizes[-1]}, last pass / first pass = {ratio:.4f}")
+    assert ratio < 1.0
+
+
+def test_means_lr_final_decays_the_means_rate_and_no_other(dev, crop, monkeypatch):
+    cfg, start, Kc, vms, crops = crop
+    module = sys.modules["gsbp_amd.densify"]
+    made = []
+
+    def recording(*a, **kw):
+        work, opt = trainable(*a, **kw)
+        made.append(opt)
+        return work, opt
+    monkeypatch.setattr(module, "trainable", recording)
+    steps = 12
+    for adam in ("torch", "visible"):
+        _, hist = gsbp_amd.train_scene(start, vms, Kc, CROP_W, CROP_H, lambda i: crops[i], steps, seed=3, adam=adam, means_lr_final=0.01,
+                                       strategy=gsbp_amd.MCMCConfig(refine_start_iter=3, refine_every=4, cap_max=270))
+        lr0 = DEFAULT_LRS["means"]
+        assert len(hist["means_lr"]) == steps and len(hist["rounds"]) == 2
+        for s, got in enumerate(hist["means_lr"]):
+            want = lr0 * 0.01 ** (s / steps)
+            assert abs(got - want) <= 1e-12 * want and got == means_lr_at(lr0, 0.01, s, steps)
+        opt = made[-1]
+        assert isinstance(opt, gsbp_amd.SplatAdam) == (adam == "visible")
+        assert opt.param_groups[0]["lr"] == hist["means_lr"][-1] < lr0
+        assert [g["lr"] for g in opt.param_groups[1:]] == [DEFAULT_LRS[name] for name in list(PARAM_KEYS)[1:]]
+    # without the keyword no rate is touched: the same floats after the run as before
+    _, hist = gsbp_amd.train_scene(start, vms, Kc, CROP_W, CROP_H, lambda i: crops[i], 5, seed=3, adam="fused")
+    assert "means_lr" not in hist and [g["lr"] for g in made[-1].param_groups] == [DEFAULT_LRS[name] for name in PARAM_KEYS]
+    with pytest.raises(gsbp_amd.GwbpError, match="means are not among params"):
+        gsbp_amd.train_scene(start, vms, Kc, CROP_W, CROP_H, lambda i: crops[i], 5, params=("opacities",), means_lr_final=0.01)
+    # polish_scene takes both keywords too
+    polished, losses = gsbp_amd.polish_scene(start, vms, Kc, CROP_W, CROP_H, lambda i: crops[i], params=("means", "opacities", "sh0"),
+                                             steps=8, seed=3, adam="visible", means_lr_final=0.01)
+    assert len(losses) == 8 and all(np.isfinite(losses)) and not torch.equal(polished["opacity"], start["opacity"])
+    assert torch.equal(polished["scaling"], start["scaling"])
