@@ -51,6 +51,9 @@ JojiJoseph/3dgs-gradient-backprojection), hand-written HIP kernels behind a C AB
                                                     # step's view saw alone (train_scene(adam="fused" | "visible", means_lr_final=...))
     from gsbp_amd import render_latents             # the second render of a Feature-3DGS step: a latent table of up to 128 channels,
                                                     # differentiable in the Gaussians and the table (train_scene(feature_fn=...))
+    from gsbp_amd import depth_point_loss, depth_map_loss  # depth supervision: the render's expected depth against the view's
+                                                    # triangulated points (scene_io.view_depth_points) or a depth map, a HIP kernel
+                                                    # pair each (train_scene(depth_fn=...))
 """
 from . import synthetic  # noqa: F401
 from ._lib import GwbpError, build, lib  # noqa: F401
@@ -95,6 +98,8 @@ from . import mcmc  # noqa: F401
 from .mcmc import MCMCConfig, inject_noise, relocate, sample_add  # noqa: F401
 from . import adam  # noqa: F401
 from .adam import SplatAdam  # noqa: F401
+from . import depth  # noqa: F401
+from .depth import depth_map_loss, depth_point_loss, sample_expected_depth  # noqa: F401
 from . import latent_render  # noqa: F401
 from .latent_render import render_latents  # noqa: F401
 from .pruning import check_proper_pruning, gradient_mask, prune_by_gradients  # noqa: F401

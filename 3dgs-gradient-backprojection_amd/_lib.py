@@ -278,6 +278,15 @@ ARGTYPES = {
     "gwbp_sh_eval_backward": [_I64, _I32, _I32, _I32, _P, _P, _P, C.POINTER(C.c_float), _P, _P, _P, _P, _P],
     # the optimiser step: n, w, p, g, m, v, visible, lr_over_bc1, sqrt_bc2, b1, b2 (float64), eps, stream
     "gwbp_adam_step": [_I64, _I32, _P, _P, _P, _P, _P, _F, _F, C.c_double, C.c_double, _F, _P],
+    # the depth losses: height, width, Dp, ch, render, alpha, then
+    #   M, points, depths, scale, loss, per_point, workspace, workspace_bytes, stream
+    #   M, points, depths, scale, upstream, v_render, v_alpha, stream
+    #   depth, weights, kind, scale, loss, sums, workspace, workspace_bytes, stream
+    #   depth, weights, kind, scale, sums, upstream, v_render, v_alpha, stream
+    "gwbp_depth_points_loss": [_I32, _I32, _I32, _I32, _P, _P, _I64, _P, _P, _F, _P, _P, _P, _SZ, _P],
+    "gwbp_depth_points_backward": [_I32, _I32, _I32, _I32, _P, _P, _I64, _P, _P, _F, _P, _P, _P, _P],
+    "gwbp_depth_map_loss": [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _F, _P, _P, _P, _SZ, _P],
+    "gwbp_depth_map_backward": [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _F, _P, _P, _P, _P, _P],
 }
 # The typed forms of the entry points that read a finished [N, D] FIELD (or, gwbp_finalize_typed, write one): the untyped function's
 # arguments with the field's element type (GWBP_MAP_*, MAP_TYPES' codes) behind the field pointer.  A table of their own: they take no
@@ -317,6 +326,13 @@ MCMC_MODES = {"relocate": 0, "add": 1}  # GWBP_MCMC_RELOCATE / _ADD
 MCMC_MAX_RATIO = 51  # GWBP_MCMC_MAX_RATIO
 MCMC_LIBM = {"exp": 0, "log": 1, "pow": 2}  # GWBP_MCMC_LIBM_*
 SH_MAX_K = 16  # GWBP_SH_MAX_K
+DEPTH_KINDS = {"disparity": 0, "depth": 1}  # GWBP_DEPTH_KIND_*
+DEPTH_BLOCK = 256  # GWBP_DEPTH_BLOCK: the points of one workgroup of the point term
+
+
+def depth_workspace_bytes(n: int) -> int:
+    """GWBP_DEPTH_WORKSPACE_BYTES(n): n = the points of the point term, or the pixels of the map term."""
+    return (int(n) + DEPTH_BLOCK - 1) // DEPTH_BLOCK * 16
 # every symbol of include/gwbp.h: the two functions that return strings, then the int-returning ones declared above
 EXPORTS = ["gwbp_version", "gwbp_last_error_string", *ARGTYPES, *FIELD_ARGTYPES]
 

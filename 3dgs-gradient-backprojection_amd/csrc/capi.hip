@@ -2435,6 +2435,131 @@ int gwbp_adam_step(int64_t n, int32_t w, float *p, const float *g, float *m, flo
     return launch_adam_step(n, w, p, g, m, v, visible, lr_over_bc1, sqrt_bc2, b1, b2, eps, as_stream(stream));
 }
 
+// ---- the depth losses (depth_loss.hip) --------------------------------------------------------------------------------------------
+// the render, its alpha map and the channel of all four entry points; `what` names the entry point
+static int check_depth_image(const char *what, int32_t height, int32_t width, int32_t Dp, int32_t ch, const float *render,
+                             const float *alpha)
+{
+    if (height < 1 || width < 1 || height > (1 << 24) || width > (1 << 24))
+        return set_error(GWBP_EINVAL, "%s: an image of %d x %d pixels (width x height; each in [1, 2^24])", what, (int)width, (int)height);
+    if ((int64_t)height * width > 0x7FFFFFFF)
+        return set_error(GWBP_EINVAL, "%s: an image of %lld pixels (at most 2^31 - 1)", what, (long long)((int64_t)height * width));
+    if (Dp < 1 || ch < 0 || ch >= Dp)
+        return set_error(GWBP_EINVAL, "%s: channel %d of a render with %d channels", what, (int)ch, (int)Dp);
+    if (!render || !alpha)
+        return set_error(GWBP_EINVAL, "%s: null render or alpha", what);
+    if (misaligned(render, 3) || misaligned(alpha, 3))
+        return set_error(GWBP_EINVAL, "%s: render and alpha must be 4-B aligned", what);
+    return GWBP_OK;
+}
+
+static int check_depth_points(const char *what, int64_t M, const float *points, const float *depths)
+{
+    if (M < 0 || M > 0x7FFFFFFF)
+        return set_error(GWBP_EINVAL, "%s: bad number of points (%lld): 0 .. 2^31 - 1", what, (long long)M);
+    if (M > 0 && (!points || !depths))
+        return set_error(GWBP_EINVAL, "%s: null points or depths", what);
+    if (misaligned(points, 3) || misaligned(depths, 3))
+        return set_error(GWBP_EINVAL, "%s: points and depths must be 4-B aligned", what);
+    return GWBP_OK;
+}
+
+static int check_depth_map(const char *what, const float *depth, const float *weights, int32_t kind)
+{
+    if (kind != GWBP_DEPTH_KIND_DISPARITY && kind != GWBP_DEPTH_KIND_DEPTH)
+        return set_error(GWBP_EINVAL, "%s: unknown kind %d", what, (int)kind);
+    if (!depth)
+        return set_error(GWBP_EINVAL, "%s: null depth map", what);
+    if (misaligned(depth, 3) || misaligned(weights, 3))
+        return set_error(GWBP_EINVAL, "%s: the depth map and the weights must be 4-B aligned", what);
+    return GWBP_OK;
+}
+
+// the outputs of a backward and the device scalar it reads
+static int check_depth_grads(const char *what, const float *upstream, const float *v_render, const float *v_alpha)
+{
+    if (!upstream || !v_render || !v_alpha)
+        return set_error(GWBP_EINVAL, "%s: null upstream, v_render or v_alpha", what);
+    if (misaligned(upstream, 3) || misaligned(v_render, 3) || misaligned(v_alpha, 3))
+        return set_error(GWBP_EINVAL, "%s: upstream, v_render and v_alpha must be 4-B aligned", what);
+    return GWBP_OK;
+}
+
+static int check_depth_workspace(const char *what, const void *workspace, size_t workspace_bytes, size_t need)
+{
+    if (need == 0)
+        return GWBP_OK;
+    if (!workspace || misaligned(workspace, 7))
+        return set_error(GWBP_EINVAL, "%s: null workspace, or one that is not 8-B aligned", what);
+    if (workspace_bytes < need)
+        return set_error(GWBP_EWORKSPACE, "%s: workspace has %zu bytes, needs %zu", what, workspace_bytes, need);
+    return GWBP_OK;
+}
+
+int gwbp_depth_points_loss(int32_t height, int32_t width, int32_t Dp, int32_t ch, const float *render, const float *alpha, int64_t M,
+                           const float *points, const float *depths, float scale, float *loss, float *per_point, void *workspace,
+                           size_t workspace_bytes, void *stream)
+{
+    const char *what = "depth_points_loss";
+    int rc = check_depth_image(what, height, width, Dp, ch, render, alpha);
+    if (rc || (rc = check_depth_points(what, M, points, depths)))
+        return rc;
+    if (!loss || misaligned(loss, 3) || misaligned(per_point, 3))
+        return set_error(GWBP_EINVAL, "%s: null loss, or a loss or per_point that is not 4-B aligned", what);
+    if ((rc = check_depth_workspace(what, workspace, workspace_bytes, depth_points_workspace_bytes(M))))
+        return rc;
+    return launch_depth_points_loss(height, width, Dp, ch, render, alpha, M, points, depths, scale, loss, per_point,
+                                    static_cast<double *>(workspace), as_stream(stream));
+}
+
+int gwbp_depth_points_backward(int32_t height, int32_t width, int32_t Dp, int32_t ch, const float *render, const float *alpha,
+                               int64_t M, const float *points, const float *depths, float scale, const float *upstream,
+                               float *v_render, float *v_alpha, void *stream)
+{
+    const char *what = "depth_points_backward";
+    int rc = check_depth_image(what, height, width, Dp, ch, render, alpha);
+    if (rc || (rc = check_depth_points(what, M, points, depths)) || (rc = check_depth_grads(what, upstream, v_render, v_alpha)))
+        return rc;
+    const void *const written[] = {v_render, v_alpha}, *const read[] = {render, alpha, points, depths, upstream};
+    if ((rc = check_regions_distinct(what, written, 2, read, 5)))
+        return rc;
+    return launch_depth_points_backward(height, width, Dp, ch, render, alpha, M, points, depths, scale, upstream, v_render, v_alpha,
+                                        as_stream(stream));
+}
+
+int gwbp_depth_map_loss(int32_t height, int32_t width, int32_t Dp, int32_t ch, const float *render, const float *alpha,
+                        const float *depth, const float *weights, int32_t kind, float scale, float *loss, double *sums,
+                        void *workspace, size_t workspace_bytes, void *stream)
+{
+    const char *what = "depth_map_loss";
+    int rc = check_depth_image(what, height, width, Dp, ch, render, alpha);
+    if (rc || (rc = check_depth_map(what, depth, weights, kind)))
+        return rc;
+    if (!loss || !sums || misaligned(loss, 3) || misaligned(sums, 7))
+        return set_error(GWBP_EINVAL, "%s: null loss or sums, or a loss that is not 4-B or sums that are not 8-B aligned", what);
+    if ((rc = check_depth_workspace(what, workspace, workspace_bytes, depth_map_workspace_bytes(height, width))))
+        return rc;
+    return launch_depth_map_loss(height, width, Dp, ch, render, alpha, depth, weights, kind, scale, loss, sums,
+                                 static_cast<double *>(workspace), as_stream(stream));
+}
+
+int gwbp_depth_map_backward(int32_t height, int32_t width, int32_t Dp, int32_t ch, const float *render, const float *alpha,
+                            const float *depth, const float *weights, int32_t kind, float scale, const double *sums,
+                            const float *upstream, float *v_render, float *v_alpha, void *stream)
+{
+    const char *what = "depth_map_backward";
+    int rc = check_depth_image(what, height, width, Dp, ch, render, alpha);
+    if (rc || (rc = check_depth_map(what, depth, weights, kind)) || (rc = check_depth_grads(what, upstream, v_render, v_alpha)))
+        return rc;
+    if (!sums || misaligned(sums, 7))
+        return set_error(GWBP_EINVAL, "%s: null sums, or sums that are not 8-B aligned", what);
+    const void *const written[] = {v_render, v_alpha}, *const read[] = {render, alpha, depth, weights, upstream, sums};
+    if ((rc = check_regions_distinct(what, written, 2, read, 6)))
+        return rc;
+    return launch_depth_map_backward(height, width, Dp, ch, render, alpha, depth, weights, kind, scale, sums, upstream, v_render,
+                                     v_alpha, as_stream(stream));
+}
+
 int gwbp_accumulate_stats(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, gwbp_stats *accum,
                           void *stream)
 {

@@ -366,6 +366,20 @@ int launch_mcmc_libm(int64_t N, int op, const float *a, const float *b, float *o
 // launcher forms 1 - b1 and 1 - b2 there and rounds once
 int launch_adam_step(int64_t N, int w, float *p, const float *g, float *m, float *v, const uint8_t *visible, float lr_over_bc1,
                      float sqrt_bc2, double b1, double b2, float eps, hipStream_t s);
+// the depth losses of training (depth_loss.hip, depth_math.h): the point term and the map term, each forward (the float32 loss to a
+// device scalar through per-workgroup float64 partials in ws) and backward (the upstream gradient read from the device)
+size_t depth_points_workspace_bytes(int64_t M);
+size_t depth_map_workspace_bytes(int H, int W);
+int launch_depth_points_loss(int H, int W, int Dp, int ch, const float *render, const float *alpha, int64_t M, const float *points,
+                             const float *depths, float scale, float *loss, float *per_point, double *ws, hipStream_t s);
+int launch_depth_points_backward(int H, int W, int Dp, int ch, const float *render, const float *alpha, int64_t M, const float *points,
+                                 const float *depths, float scale, const float *upstream, float *v_render, float *v_alpha,
+                                 hipStream_t s);
+int launch_depth_map_loss(int H, int W, int Dp, int ch, const float *render, const float *alpha, const float *depth,
+                          const float *weights, int kind, float scale, float *loss, double *sums, double *ws, hipStream_t s);
+int launch_depth_map_backward(int H, int W, int Dp, int ch, const float *render, const float *alpha, const float *depth,
+                              const float *weights, int kind, float scale, const double *sums, const float *upstream, float *v_render,
+                              float *v_alpha, hipStream_t s);
 int launch_encode_map(const float *feats, int64_t fs_y, int64_t fs_x, int H, int W, int K, const float *enc, int n_out,
                       float *out, int workgroups, hipStream_t s);
 // ot (GWBP_MAP_*): the element type of out; a half out is the fp32 result rounded once to nearest even
@@ -521,6 +535,29 @@ __device__ __forceinline__ float wave_sum(float v)
     const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
     const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
     return (r0 + r1) + (r2 + r3);
+}
+// wave_sum for a double: the two halves move through the same DPP controls.
+template <int CTRL>
+__device__ __forceinline__ double dpp_d(double x)
+{
+    const long long b = __double_as_longlong(x);
+    const u32 lo = (u32)__builtin_amdgcn_update_dpp(0, (int)(u32)b, CTRL, 0xF, 0xF, true);
+    const u32 hi = (u32)__builtin_amdgcn_update_dpp(0, (int)(u32)(b >> 32), CTRL, 0xF, 0xF, true);
+    return __longlong_as_double((long long)(((u64)hi << 32) | lo));
+}
+__device__ __forceinline__ double lane_d(double x, int l)
+{
+    const long long b = __double_as_longlong(x);
+    const u32 lo = (u32)__builtin_amdgcn_readlane((int)(u32)b, l), hi = (u32)__builtin_amdgcn_readlane((int)(u32)(b >> 32), l);
+    return __longlong_as_double((long long)(((u64)hi << 32) | lo));
+}
+__device__ __forceinline__ double wave_sum_d(double v)
+{
+    v += dpp_d<0xB1>(v);  // quad_perm [1,0,3,2]
+    v += dpp_d<0x4E>(v);  // quad_perm [2,3,0,1]
+    v += dpp_d<0x141>(v); // row_half_mirror
+    v += dpp_d<0x140>(v); // row_mirror
+    return (lane_d(v, 0) + lane_d(v, 16)) + (lane_d(v, 32) + lane_d(v, 48));
 }
 // ---- feature-map element types (GWBP_MAP_*) ------------------------------------------------------------------------------
 // A half map is widened to fp32 exactly where the staging writes it into LDS (or, for a value used at once, where it is

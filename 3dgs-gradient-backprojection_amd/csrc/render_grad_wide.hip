@@ -21,29 +21,7 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 
 constexpr int kDotBatch = 64; // records of pass 2 staged per batch (128 channels: 32 KiB of colour rows), and flushed together
 
-// wave_sum (gwbp_dev.h) for a double: the two halves move through the same DPP controls.
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double x)
-{
-    const long long b = __double_as_longlong(x);
-    const u32 lo = (u32)__builtin_amdgcn_update_dpp(0, (int)(u32)b, CTRL, 0xF, 0xF, true);
-    const u32 hi = (u32)__builtin_amdgcn_update_dpp(0, (int)(u32)(b >> 32), CTRL, 0xF, 0xF, true);
-    return __longlong_as_double((long long)(((u64)hi << 32) | lo));
-}
-__device__ __forceinline__ double lane_d(double x, int l)
-{
-    const long long b = __double_as_longlong(x);
-    const u32 lo = (u32)__builtin_amdgcn_readlane((int)(u32)b, l), hi = (u32)__builtin_amdgcn_readlane((int)(u32)(b >> 32), l);
-    return __longlong_as_double((long long)(((u64)hi << 32) | lo));
-}
-__device__ __forceinline__ double wave_sum_d(double v)
-{
-    v += dpp_d<0xB1>(v);  // quad_perm [1,0,3,2]
-    v += dpp_d<0x4E>(v);  // quad_perm [2,3,0,1]
-    v += dpp_d<0x141>(v); // row_half_mirror
-    v += dpp_d<0x140>(v); // row_mirror
-    return (lane_d(v, 0) + lane_d(v, 16)) + (lane_d(v, 32) + lane_d(v, 48));
-}
+// (wave_sum_d, the float64 wave sum on wave_sum's DPP controls, is in gwbp_dev.h)
 
 // exp(-max(sigma, 0)) in float64 to about 1e-10 relative, for sigma up to 80: n = rint(x log2 e), a degree-9 Taylor sum on
 // r = x - n ln 2 (|r| <= 0.35: the first term left out is below 1e-11), times 2^n.

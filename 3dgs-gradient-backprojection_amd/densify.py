@@ -298,6 +298,7 @@ def reset_opacity(splats: Dict[str, torch.Tensor], optimizer, cfg: DensifyConfig
     return splats
 
 
+DEPTH_KINDS = tuple(_lib.DEPTH_KINDS)  # train_scene(depth_kind=...): depth.depth_map_loss's kinds
 LATENT_RENDER_KW = ("near_plane", "far_plane", "radius_clip", "eps2d", "rasterize_mode", "camera_model")  # render_latents' keywords
 
 
@@ -329,7 +330,8 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
                 opacity_reg: float = 0.0, scale_reg: float = 0.0, sh_degree_interval: Optional[int] = None,
                 feature_fn: Optional[Callable[[int], torch.Tensor]] = None, feature_dim: Optional[int] = None, latent_dim: int = 128,
                 feature_weight: float = 1.0, feature_loss: str = "l1", decoder_lr: float = 2.5e-3, decoder=None, adam: str = "torch",
-                means_lr_final: Optional[float] = None, **raster_kw):
+                means_lr_final: Optional[float] = None, depth_fn: Optional[Callable[[int], object]] = None, depth_lambda: float = 1e-2,
+                depth_scale: float = 1.0, depth_kind: str = "disparity", **raster_kw):
     """polish_scene's loop with the schedule: Adam on the named parameters under the photometric loss, the set growing and shrinking
     on the way.  Step s (from 0) renders one view with means2d_grad=True, runs the backward, adds the view into the statistics while
     s < refine_stop_iter, steps the optimiser, runs a densify round when s > refine_start_iter, s % refine_every == 0 and
@@ -373,8 +375,17 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
     means_lr_final: None, or the factor the means group's learning rate has decayed by at the end: step s of `steps` runs with
     lr0 * means_lr_final ** (s / steps), computed on the host and written into the group before the optimiser steps -- the reference
     trainer's schedule (its value is 0.01).  The MCMC noise, scaled by the group's current rate, follows it.  history["means_lr"] then
-    holds the rate of every step; no other group's rate changes, and without the keyword no rate is touched."""
+    holds the rate of every step; no other group's rate changes, and without the keyword no rate is touched.
+    depth_fn(v): the view's depth supervision, or None for a view that has none.  None (the default): no depth term, and nothing of the
+    step changes.  Set, the colour render runs with render_mode="RGB+D" (a render_mode in raster_kw then raises GwbpError), the
+    photometric loss takes its channels 0:3, and the step adds depth_lambda * the depth loss with scale=depth_scale, as the reference
+    trainer's depth_loss option does (its depth_lambda is 1e-2 and its scale the scene's scale): depth.depth_point_loss for a
+    (points [M, 2], depths [M]) pair -- scene_io.view_depth_points makes one from a COLMAP model -- or depth.depth_map_loss(kind=
+    depth_kind) for an [H, W] depth map.  Both read the render's accumulated depth and alpha in place.  The densify statistics see the
+    gradient of the summed loss, as in the reference.  history["depth_loss"]: the term before its weight, one value per step (0 for a
+    view without supervision), read once behind the loop."""
     from .decoded_field import decoded_loss
+    from .depth import depth_map_loss, depth_point_loss
     from .latent_render import render_latents
     from .mcmc import MCMCConfig, inject_noise, relocate, sample_add
     if strategy is not None and cfg is not None:
@@ -386,6 +397,18 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
     opacity_reg, scale_reg = float(opacity_reg), float(scale_reg)
     interval = check_sh_degree_interval(sh_degree_interval, "train_scene")
     final = check_means_lr_final(means_lr_final, "train_scene")
+    depth_kw, depth_losses = {}, []
+    if depth_fn is not None:
+        if not callable(depth_fn):
+            raise GwbpError(f"train_scene(): depth_fn must be a callable of the view's index, got {type(depth_fn).__name__}")
+        if "render_mode" in raster_kw:
+            raise GwbpError("train_scene(depth_fn=...) renders with render_mode='RGB+D': leave render_mode out of the raster keywords")
+        if depth_kind not in DEPTH_KINDS:
+            raise GwbpError(f"train_scene(): depth_kind must be one of {list(DEPTH_KINDS)}, got {depth_kind!r}")
+        for name, value in (("depth_lambda", depth_lambda), ("depth_scale", depth_scale)):
+            if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(float(value)):
+                raise GwbpError(f"train_scene(): {name} must be a finite number, got {value!r}")
+        depth_kw = dict(render_mode="RGB+D", return_alpha=True)
     work, opt = trainable(splats, params, lrs, "train_scene", check_adam(adam, "train_scene"))
     decayed = means_group(opt, work) if final is not None else None
     if final is not None and decayed is None:
@@ -407,10 +430,24 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
         opt.zero_grad(set_to_none=True)
         degrees.append(table_degree if interval is None else scheduled_sh_degree(step, interval, table_degree))
         geometry, f_loss = (splat_geometry(work) if feature_fn is not None else None), None  # (one exp and one sigmoid for both renders)
-        image, meta = render_splats(work, viewmats[v], view_K(K, v), width, height, return_meta=True,
-                                    means2d_grad=mcmc is None or adam == "visible",
-                                    sh_degree=None if interval is None else degrees[-1], geometry=geometry, **raster_kw)
-        loss = photometric_loss(image, image_fn(v), ssim_lambda=ssim_lambda)
+        image, *alpha, meta = render_splats(work, viewmats[v], view_K(K, v), width, height, return_meta=True,
+                                            means2d_grad=mcmc is None or adam == "visible",
+                                            sh_degree=None if interval is None else degrees[-1], geometry=geometry, **depth_kw,
+                                            **raster_kw)
+        loss = photometric_loss(image[..., :3] if depth_fn is not None else image, image_fn(v), ssim_lambda=ssim_lambda)
+        if depth_fn is not None:
+            target = depth_fn(v)
+            if target is None:
+                d_loss = torch.zeros((), device=dev)
+            elif isinstance(target, (tuple, list)) and len(target) == 2:
+                d_loss = depth_point_loss(image, alpha[0], target[0], target[1], scale=float(depth_scale))
+            elif torch.is_tensor(target):
+                d_loss = depth_map_loss(image, alpha[0], target, kind=depth_kind, scale=float(depth_scale))
+            else:
+                raise GwbpError(f"depth_fn({v}) must return a (points, depths) pair, an [H, W] tensor or None, got {type(target).__name__}")
+            depth_losses.append(d_loss.detach())
+            loss = loss + float(depth_lambda) * d_loss
+            del target, d_loss
         if feature_fn is not None:
             opt_dec.zero_grad(set_to_none=True)
             latent_map, _ = render_latents(*geometry, work["features"], viewmats[v], view_K(K, v), width, height, **latent_kw)
@@ -438,7 +475,7 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
         sizes.append(int(work["means"].shape[0]))
         if mcmc is not None:
             if mcmc.refines_at(step):
-                del image, meta, loss, f_loss, geometry
+                del image, alpha, meta, loss, f_loss, geometry
                 n_before = sizes[-1]
                 work, moved = relocate(work, mcmc, optimizer=opt, carry=carried, generator=noise_gen)
                 work, added = sample_add(work, mcmc, mcmc.n_new(n_before), optimizer=opt, carry=moved["carry"], generator=noise_gen)
@@ -452,7 +489,7 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
                 inject_noise(work, rate, mcmc, generator=noise_gen)
             continue
         if cfg.refines_at(step):
-            del image, meta, loss, f_loss, geometry  # (the graph holds the old set's workspace)
+            del image, alpha, meta, loss, f_loss, geometry  # (the graph holds the old set's workspace)
             work, info = densify(work, state, cfg, step, optimizer=opt, carry=carried, generator=noise_gen)
             carried = info["carry"]
             if info["n_after"] < 1:
@@ -466,6 +503,8 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
                    sh_degree=degrees)
     if final is not None:
         history["means_lr"] = means_lrs
+    if depth_fn is not None:
+        history["depth_loss"] = torch.stack(depth_losses).cpu().tolist() if depth_losses else []
     if feature_fn is not None:
         history.update(feature_loss=torch.stack(feature_losses).cpu().tolist() if feature_losses else [], decoder=decoder.detach())
     return {k: (t.detach() if torch.is_tensor(t) else t) for k, t in work.items()}, history

@@ -145,6 +145,51 @@ def adam_step_tables(call, stream, p, g, m, v, visible, step: int, lr: float, b1
          c_double(float(b1)), c_double(float(b2)), c_float(float(eps)), stream)
 
 
+def depth_image_args(fn: str, render, alpha, channel: int):
+    """(render, alpha [H, W], H, W, Dp, ch) of a depth loss: render a float32 HIP tensor [H, W, Dp], alpha [H, W] or [H, W, 1] on the same
+    device, channel an index into Dp (negative: from the end).  Both are read in place; another layout than a dense one is copied."""
+    for name, t in (("render", render), ("alpha", alpha)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise GwbpError(f"{fn}: {name} must be a HIP tensor (there is no CPU path)")
+        if t.dtype != torch.float32:
+            raise GwbpError(f"{fn}: {name} must be float32, got {t.dtype}")
+    if render.dim() != 3 or render.shape[0] < 1 or render.shape[1] < 1 or render.shape[2] < 1:
+        raise GwbpError(f"{fn}: render must be [H, W, D'] with H, W, D' >= 1, got {tuple(render.shape)}")
+    H, W, Dp = (int(v) for v in render.shape)
+    if tuple(alpha.shape) not in ((H, W), (H, W, 1)) or alpha.device != render.device:
+        raise GwbpError(f"{fn}: alpha must be [{H}, {W}] or [{H}, {W}, 1] on {render.device}, got {tuple(alpha.shape)} on {alpha.device}")
+    if isinstance(channel, bool) or not isinstance(channel, int) or not -Dp <= channel < Dp:
+        raise GwbpError(f"{fn}: channel must be an int in [{-Dp}, {Dp}), got {channel!r}")
+    return render.contiguous(), alpha.reshape(H, W).contiguous(), H, W, Dp, channel % Dp
+
+
+def depth_point_args(fn: str, render, points, depths):
+    """(points [M, 2], depths [M], M) of the point term: float32 tensors on the render's device."""
+    for name, t in (("points", points), ("depths", depths)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise GwbpError(f"{fn}: {name} must be a HIP tensor (there is no CPU path)")
+        if t.dtype != torch.float32 or t.device != render.device:
+            raise GwbpError(f"{fn}: {name} must be float32 on {render.device}, got {t.dtype} on {t.device}")
+    if points.dim() != 2 or points.shape[1] != 2 or tuple(depths.shape) != (points.shape[0],):
+        raise GwbpError(f"{fn}: points must be [M, 2] and depths [M], got {tuple(points.shape)} and {tuple(depths.shape)}")
+    return points.contiguous(), depths.contiguous(), int(points.shape[0])
+
+
+def depth_map_args(fn: str, render, depth, weights, kind: str):
+    """(depth [H, W], weights [H, W] or None, GWBP_DEPTH_KIND_*) of the map term: float32 tensors on the render's device."""
+    if kind not in _lib.DEPTH_KINDS:
+        raise GwbpError(f"{fn}: kind must be one of {list(_lib.DEPTH_KINDS)}, got {kind!r}")
+    H, W = int(render.shape[0]), int(render.shape[1])
+    for name, t in (("depth", depth), ("weights", weights)):
+        if t is None and name == "weights":
+            continue
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise GwbpError(f"{fn}: {name} must be a HIP tensor (there is no CPU path)")
+        if t.dtype != torch.float32 or t.device != render.device or tuple(t.shape) != (H, W):
+            raise GwbpError(f"{fn}: {name} must be float32 [{H}, {W}] on {render.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return depth.contiguous(), (None if weights is None else weights.contiguous()), _lib.DEPTH_KINDS[kind]
+
+
 def field_rows(t: torch.Tensor, name: str):
     """(tensor, GWBP_MAP_* code) of a finished [rows, D] FIELD as it is stored: float32, float16 or bfloat16, read by the *_typed entry
     points without a float32 copy.  Unit stride inside a row and a non-negative row stride >= D, in elements; a layout the kernels
@@ -1388,6 +1433,82 @@ class Engine:
         count t >= 1 of this step; the bias corrections are formed on the host in float64, nothing is read back.  visible: None, or a
         uint8 / bool [n]: rows whose entry is zero keep the bits of p, m and v.  SplatAdam is the optimiser built on it."""
         adam_step_tables(self._call, self._stream(), p, g, m, v, visible, step, lr, b1, b2, eps)
+
+    # ---- depth supervision (csrc/depth_loss.hip; DESIGN.md 4.0o) --------------------------------------------------------------
+    def _depth_workspace(self, n: int):
+        need = max(_lib.depth_workspace_bytes(n), 16)
+        ws = getattr(self, "_depth_ws", None)
+        if ws is None or ws.numel() < need:
+            with self._on_stream():
+                ws = self._depth_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return ws
+
+    def _depth_upstream(self, fn: str, upstream) -> torch.Tensor:
+        if not torch.is_tensor(upstream) or upstream.device != self.device or upstream.numel() != 1:
+            raise GwbpError(f"{fn}: upstream must be a one-element tensor on {self.device} (it is read on the device)")
+        with self._on_stream():
+            return upstream.detach().to(torch.float32).reshape(1).contiguous()
+
+    def depth_points_loss(self, render, alpha, points, depths, channel: int = -1, scale: float = 1.0, want_per_point: bool = False):
+        """The reference trainer's depth term (gwbp_depth_points_loss): scale * mean |1 / d - 1 / depths| with d the bilinear sample of
+        the expected depth render[..., channel] / max(alpha, 1e-10) at the points (column index x, row index y: grid_sample's
+        align_corners=True coordinates, zero padding).  Returns (loss, per_point): a float32 0-dim device tensor, nothing read back,
+        the same bits every call; per_point [M, 2] = (d, t) per point with want_per_point, else None.  A sample with d <= 0
+        contributes 1 / depths; M = 0 gives 0."""
+        fn = "depth_points_loss"
+        render, alpha, H, W, Dp, ch = depth_image_args(fn, render, alpha, channel)
+        points, depths, M = depth_point_args(fn, render, points, depths)
+        with self._on_stream():
+            loss = torch.empty((), device=self.device)
+            per_point = torch.empty(M, 2, device=self.device) if want_per_point else None
+        ws = self._depth_workspace(M)
+        self._call("gwbp_" + fn, H, W, Dp, ch, ptr(render), ptr(alpha), c_int64(M), ptr(points), ptr(depths), c_float(float(scale)),
+                   ptr(loss), ptr(per_point), ptr(ws), c_size_t(ws.numel()), self._stream())
+        return loss, per_point
+
+    def depth_points_backward(self, render, alpha, points, depths, upstream, channel: int = -1, scale: float = 1.0):
+        """(v_render [H, W, D'], v_alpha [H, W]) = upstream * the gradient of depth_points_loss (gwbp_depth_points_backward); upstream
+        is a one-element DEVICE tensor, read by the kernel.  v_render is zero outside `channel`.  Float atomics where points share a
+        corner: not bit-reproducible.  A sample with d <= 0 adds exact zeros."""
+        fn = "depth_points_backward"
+        render, alpha, H, W, Dp, ch = depth_image_args(fn, render, alpha, channel)
+        points, depths, M = depth_point_args(fn, render, points, depths)
+        upstream = self._depth_upstream(fn, upstream)
+        with self._on_stream():
+            v_render, v_alpha = torch.zeros(H, W, Dp, device=self.device), torch.zeros(H, W, device=self.device)
+        self._call("gwbp_" + fn, H, W, Dp, ch, ptr(render), ptr(alpha), c_int64(M), ptr(points), ptr(depths), c_float(float(scale)),
+                   ptr(upstream), ptr(v_render), ptr(v_alpha), self._stream())
+        return v_render, v_alpha
+
+    def depth_map_loss(self, render, alpha, depth, weights=None, kind: str = "disparity", channel: int = -1, scale: float = 1.0):
+        """The depth term against a depth map (gwbp_depth_map_loss): scale * sum w t / sum w over the pixels with depth > 0 (and
+        weights > 0), t = |1 / e - 1 / depth| ("disparity") or |e - depth| ("depth") of the expected depth e.  Returns (loss, sums):
+        a float32 0-dim device tensor and the float64 [2] device tensor (sum w t, sum w) the backward reads."""
+        fn = "depth_map_loss"
+        render, alpha, H, W, Dp, ch = depth_image_args(fn, render, alpha, channel)
+        depth, weights, code = depth_map_args(fn, render, depth, weights, kind)
+        with self._on_stream():
+            loss, sums = torch.empty((), device=self.device), torch.empty(2, dtype=torch.float64, device=self.device)
+        ws = self._depth_workspace(H * W)
+        self._call("gwbp_" + fn, H, W, Dp, ch, ptr(render), ptr(alpha), ptr(depth), ptr(weights), code, c_float(float(scale)),
+                   ptr(loss), ptr(sums), ptr(ws), c_size_t(ws.numel()), self._stream())
+        return loss, sums
+
+    def depth_map_backward(self, render, alpha, depth, sums, upstream, weights=None, kind: str = "disparity", channel: int = -1,
+                           scale: float = 1.0):
+        """(v_render [H, W, D'], v_alpha [H, W]) = upstream * the gradient of depth_map_loss (gwbp_depth_map_backward), every element
+        stored once: no atomics, the same bits every call.  sums: what depth_map_loss returned."""
+        fn = "depth_map_backward"
+        render, alpha, H, W, Dp, ch = depth_image_args(fn, render, alpha, channel)
+        depth, weights, code = depth_map_args(fn, render, depth, weights, kind)
+        if not torch.is_tensor(sums) or sums.dtype != torch.float64 or sums.device != self.device or tuple(sums.shape) != (2,):
+            raise GwbpError(f"{fn}: sums must be the float64 [2] tensor depth_map_loss returned")
+        upstream = self._depth_upstream(fn, upstream)
+        with self._on_stream():
+            v_render, v_alpha = torch.empty(H, W, Dp, device=self.device), torch.empty(H, W, device=self.device)
+        self._call("gwbp_" + fn, H, W, Dp, ch, ptr(render), ptr(alpha), ptr(depth), ptr(weights), code, c_float(float(scale)),
+                   ptr(sums.contiguous()), ptr(upstream), ptr(v_render), ptr(v_alpha), self._stream())
+        return v_render, v_alpha
 
     # ---- the view's RGB render for the 2-D network (create_feature_field(render_colors=...)) ----------------------------------
     @staticmethod

@@ -56,7 +56,7 @@ def splat_geometry(splats: Dict[str, torch.Tensor]):
 
 
 def render_splats(splats: Dict[str, torch.Tensor], viewmat, K, width: int, height: int, return_meta: bool = False,
-                  sh_degree: Optional[int] = None, geometry=None, **raster_kw):
+                  sh_degree: Optional[int] = None, geometry=None, return_alpha: bool = False, **raster_kw):
     """The [H, W, 3] image of a splat dict from one camera, as the trainer renders it: scales = exp, opacities = sigmoid, raw quats,
     the SH colours of features_dc and features_rest.  Differentiable in every tensor of the dict.
     sh_degree: the degree to evaluate, at most the one the tables' coefficient count gives (None: that one).  Below it the rows above
@@ -65,7 +65,9 @@ def render_splats(splats: Dict[str, torch.Tensor], viewmat, K, width: int, heigh
     go to rasterization() as an [N, 3] table; camera_grad=True is refused as rasterization() refuses it beside sh_degree.
     return_meta: (image, meta) -- the eager part of rasterization()'s meta, which under means2d_grad=True holds the means2d leaf.
     geometry: splat_geometry(splats) computed by the caller, who hands the same activations to a second render (train_scene's
-    feature term); None computes them here."""
+    feature term); None computes them here.
+    return_alpha: also hand back the [H, W, 1] alpha map of the same render, behind the image: (image, alpha) or (image, alpha, meta).
+    With render_mode="RGB+D" in raster_kw the image is [H, W, 4], the accumulated depth last (what depth.depth_point_loss takes)."""
     table = table_sh_degree(splats)
     degree = table if sh_degree is None else sh_degree
     if isinstance(degree, bool) or not isinstance(degree, int) or not 0 <= degree <= table:
@@ -76,12 +78,18 @@ def render_splats(splats: Dict[str, torch.Tensor], viewmat, K, width: int, heigh
     geometry = splat_geometry(splats) if geometry is None else geometry
     if not sh_kernel_enabled() or not means.is_cuda:  # (set_sh_kernel(False): the route before the kernels; CPU tensors: its error)
         sh = dc if rest is None else torch.cat([dc, rest], dim=1)
-        out, _, meta = rasterization(*geometry, sh, viewmat[None], K[None], width, height, sh_degree=degree, want_meta=False, **raster_kw)
-        return (out[0], meta) if return_meta else out[0]
+        out, alphas, meta = rasterization(*geometry, sh, viewmat[None], K[None], width, height, sh_degree=degree, want_meta=False, **raster_kw)
+        return _render_result(out, alphas, meta, return_alpha, return_meta)
     vm_h = viewmat.detach().cpu()  # the camera centre as rasterization() computes it beside sh_degree
     colors = sh_colors(degree, means, dc, (-(vm_h[:3, :3].T @ vm_h[:3, 3])).tolist(), rest=rest)
-    out, _, meta = rasterization(*geometry, colors, viewmat[None], K[None], width, height, sh_degree=None, want_meta=False, **raster_kw)
-    return (out[0], meta) if return_meta else out[0]
+    out, alphas, meta = rasterization(*geometry, colors, viewmat[None], K[None], width, height, sh_degree=None, want_meta=False, **raster_kw)
+    return _render_result(out, alphas, meta, return_alpha, return_meta)
+
+
+def _render_result(out, alphas, meta, return_alpha: bool, return_meta: bool):
+    if not return_alpha:  # (the returns before the keyword existed)
+        return (out[0], meta) if return_meta else out[0]
+    return (out[0], alphas[0], meta) if return_meta else (out[0], alphas[0])
 
 
 def view_K(K, v):

@@ -168,6 +168,49 @@ def get_viewmat_from_colmap_image(image: Image) -> torch.Tensor:
     return vm
 
 
+def image_point_rows(project: ColmapProject) -> Dict[int, np.ndarray]:
+    """image_id -> the rows of project.points3D whose tracks name that image, one entry per track element, in the order of
+    points3D.bin (the reference parser's point_indices).  Built once per project, in one pass over the concatenated tracks, and kept
+    on it."""
+    cached = getattr(project, "_image_point_rows", None)
+    if cached is not None and cached[0] is project.point3D_ids:
+        return cached[1]
+    tracks = [project.point3D_id_to_images[int(pid)][:, 0] for pid in project.point3D_ids]
+    table: Dict[int, np.ndarray] = {}
+    if tracks:
+        images = np.concatenate(tracks).astype(np.int64)
+        rows = np.repeat(np.arange(len(tracks), dtype=np.int64), [len(t) for t in tracks])
+        order = np.argsort(images, kind="stable")  # (stable: inside an image the rows stay in points3D.bin's order)
+        ids, starts = np.unique(images[order], return_index=True)
+        table = {int(i): r for i, r in zip(ids, np.split(rows[order], starts[1:]))}
+    project._image_point_rows = (project.point3D_ids, table)
+    return table
+
+
+def view_depth_points(project: ColmapProject, image, K, width: int, height: int):
+    """(points [M, 2], depths [M]) as float32 CPU tensors: the view's triangulated points and their true depths, what the reference's
+    loader hands its trainer's depth term (datasets/colmap.py, load_depths) and what depth.depth_point_loss takes.
+    The 3-D points whose TRACKS name this image (one entry per track element, in the order of points3D.bin), transformed by the
+    image's world-to-camera pose, projected with K -- (x, y) = (K p)[:2] / (K p)[2], so x is a column index in the loader's
+    convention -- and kept where 0 <= x < width, 0 <= y < height and z > 0.  Computed in float64, rounded once.
+    image: an Image of the project or its image_id.  K: [3, 3], the intrinsics of the images as they are trained on
+    (camera_matrix(cam, data_factor))."""
+    im = image if isinstance(image, Image) else project.images[int(image)]
+    if project.points3D is None or project.point3D_ids is None:
+        raise ValueError("the project has no points3D (read_colmap_model found no points3D.bin)")
+    Kd = np.asarray(K.detach().cpu().numpy() if torch.is_tensor(K) else K, dtype=np.float64)
+    if Kd.shape != (3, 3):
+        raise ValueError(f"K must be [3, 3], got {Kd.shape}")
+    world = project.points3D[image_point_rows(project).get(im.image_id, np.zeros(0, np.int64))].reshape(-1, 3)
+    cam = world @ im.R().T + np.asarray(im.tvec, dtype=np.float64)[None, :]
+    proj = cam @ Kd.T
+    with np.errstate(divide="ignore", invalid="ignore"):
+        xy = proj[:, :2] / proj[:, 2:3]
+    z = cam[:, 2]
+    keep = (xy[:, 0] >= 0) & (xy[:, 0] < width) & (xy[:, 1] >= 0) & (xy[:, 1] < height) & (z > 0)
+    return torch.from_numpy(xy[keep].astype(np.float32)), torch.from_numpy(z[keep].astype(np.float32))
+
+
 def read_gaussian_ply(path: str) -> Dict[str, torch.Tensor]:
     """3DGS (inria) .ply -> the reference's splat keys (utils.py:68-85), including its reshape of f_rest_*
     to (-1, 15, 3) exactly as written there."""

@@ -1356,6 +1356,47 @@ GWBP_API int gwbp_mcmc_libm(int64_t n, int32_t op, const float *a, const float *
 GWBP_API int gwbp_adam_step(int64_t n, int32_t w, float *p, const float *g, float *m, float *v, const uint8_t *visible,
                             float lr_over_bc1, float sqrt_bc2, double b1, double b2, float eps, void *stream);
 
+/* ---- depth supervision of training: the expected depth of a render against triangulated points or a depth map (csrc/depth_loss.hip;
+ * DESIGN.md 4.0o; csrc/depth_math.h holds the expressions in their order) ----
+ * render: float32 [height, width, Dp], dense, of an accumulated-depth mode (RGB+D, D): channel ch holds the accumulated depth A and is
+ * read in place.  alpha: float32 [height, width], dense.  The expected depth of a pixel is e = A / max(alpha, 1e-10), +0 outside the
+ * image.
+ * gwbp_depth_points_loss      loss[0] (float32, device) = scale (sum_i t_i) / M over the M points (x_i, y_i) of points [M, 2] with
+ *     true depths depths [M]: d_i the bilinear sample of e at column index x_i and row index y_i (column j is sampled at x = j, zero
+ *     padding: the reference's grid_sample(align_corners=True) coordinates), q_i = d_i > 0 ? 1 / d_i : 0, t_i = |q_i - 1 / depths_i|.
+ *     per_point: NULL, or float32 [M, 2] that takes (d_i, t_i).  M = 0: loss 0.  The sum is formed in float64 in a fixed order: the
+ *     same inputs give the same bits.  workspace: GWBP_DEPTH_WORKSPACE_BYTES(M) bytes, 8-B aligned.
+ * gwbp_depth_points_backward  ADDS upstream[0] * d loss / d render into channel ch of v_render [height, width, Dp] and
+ *     upstream[0] * d loss / d alpha into v_alpha [height, width] (both zero-filled by the caller) with float atomics in an order that
+ *     is not fixed: points share corners, the result is not bit-reproducible.  upstream: a float32 scalar ON THE DEVICE.  A sample with
+ *     d_i <= 0 adds exact zeros (the torch expression gives NaN there), and so does M = 0.
+ * gwbp_depth_map_loss         the same loss against a depth map depth [height, width] with optional weights [height, width] (NULL:
+ *     all 1) over the valid pixels (depth > 0 and weight > 0): t = |q(e) - 1 / depth| (GWBP_DEPTH_KIND_DISPARITY) or |e - depth|
+ *     (GWBP_DEPTH_KIND_DEPTH), loss[0] = scale (sum w t) / (sum w), 0 without a valid pixel; sums [2] (float64, device) takes the two
+ *     sums.  workspace: GWBP_DEPTH_WORKSPACE_BYTES(height * width) bytes.
+ * gwbp_depth_map_backward     STORES every element of v_render [height, width, Dp] (zeros outside channel ch) and of v_alpha: no
+ *     atomics, the same bits every run.  sums: what the forward wrote.  A pixel with e <= 0 takes zeros.
+ * Non-finite inputs and depths <= 0 of the point term are not masked: they propagate.
+ * GWBP_EINVAL before any HIP call: height or width outside [1, 2^24] or more than 2^31 - 1 pixels, Dp < 1, ch outside [0, Dp), M outside [0, 2^31 - 1], an unknown
+ * kind, a null or 4-B misaligned pointer (8-B: sums, workspace) among those the call reads or writes (points and depths may be NULL
+ * when M = 0, and so may the workspace).  GWBP_EWORKSPACE: a workspace below the size above. */
+#define GWBP_DEPTH_KIND_DISPARITY 0
+#define GWBP_DEPTH_KIND_DEPTH 1
+#define GWBP_DEPTH_BLOCK 256 /* points per workgroup of the point term */
+#define GWBP_DEPTH_WORKSPACE_BYTES(n) ((((size_t)(n) + GWBP_DEPTH_BLOCK - 1) / GWBP_DEPTH_BLOCK) * 16)
+GWBP_API int gwbp_depth_points_loss(int32_t height, int32_t width, int32_t Dp, int32_t ch, const float *render, const float *alpha,
+                                    int64_t M, const float *points, const float *depths, float scale, float *loss, float *per_point,
+                                    void *workspace, size_t workspace_bytes, void *stream);
+GWBP_API int gwbp_depth_points_backward(int32_t height, int32_t width, int32_t Dp, int32_t ch, const float *render, const float *alpha,
+                                        int64_t M, const float *points, const float *depths, float scale, const float *upstream,
+                                        float *v_render, float *v_alpha, void *stream);
+GWBP_API int gwbp_depth_map_loss(int32_t height, int32_t width, int32_t Dp, int32_t ch, const float *render, const float *alpha,
+                                 const float *depth, const float *weights, int32_t kind, float scale, float *loss, double *sums,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+GWBP_API int gwbp_depth_map_backward(int32_t height, int32_t width, int32_t Dp, int32_t ch, const float *render, const float *alpha,
+                                     const float *depth, const float *weights, int32_t kind, float scale, const double *sums,
+                                     const float *upstream, float *v_render, float *v_alpha, void *stream);
+
 /* Adds this view's counters into `accum` (device, gwbp_stats) -- used by bench/driver to total pairs. */
 GWBP_API int gwbp_accumulate_stats(const gwbp_caps *caps, void *workspace, size_t workspace_bytes, gwbp_stats *accum,
                           void *stream);

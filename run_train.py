@@ -22,6 +22,10 @@ gsbp_amd.score_image_views).
 DIR/<image stem>.npy or .pt, [h, w, D], upsampled bilinearly to the view when smaller (as the reference upsamples its network's
 output); views without a map take no part.  Then --out also holds features.pt (the latents, and the decoder under "decoder"), and
 history.json the steps' feature losses.
+--depth-loss adds the reference trainer's depth term (gsbp_amd.train_scene(depth_fn=...)): --depth-lambda x scene scale x the mean
+|1 / depth - 1 / true depth| of the render's expected depth sampled at the view's points.  With --colmap the points are the view's
+triangulated COLMAP points (gsbp_amd.scene_io.view_depth_points); with --synthetic 256 seeded positions per view with the true scene's
+depth there.  history.json then holds the steps' depth losses under "depth_loss".
 """
 import argparse
 import json
@@ -61,6 +65,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--means-lr-final", type=float, default=argparse.SUPPRESS, metavar="FACTOR",
                     help="decay the means' learning rate exponentially to FACTOR of its start over the run, as the reference trainer "
                          "does with 0.01 (default: off)")
+    ap.add_argument("--depth-loss", action="store_true", default=argparse.SUPPRESS,
+                    help="add the reference trainer's depth term: the render's expected depth against the view's triangulated COLMAP "
+                         "points (--colmap), or against 256 seeded samples of the true scene's depth per view (--synthetic)")
+    ap.add_argument("--depth-lambda", type=float, default=argparse.SUPPRESS, help="weight of the depth term (default 0.01)")
+    ap.add_argument("--depth-kind", choices=("disparity", "depth"), default=argparse.SUPPRESS,
+                    help="what a depth MAP is compared in (train_scene(depth_kind=...)).  Both sources this script has hand over POINTS, "
+                         "which are always compared in disparity: the switch is passed on and changes nothing until a map source exists")
     ap.add_argument("--feature-dim", type=int, default=argparse.SUPPRESS, metavar="D",
                     help="train a latent feature field beside the colours against feature maps of D channels")
     ap.add_argument("--latent-dim", type=int, default=argparse.SUPPRESS, help="channels of the latent table (default 128)")
@@ -92,6 +103,24 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 FEATURE_SEED = 1234  # --synthetic: the hidden latent field and decoder of the feature maps
+DEPTH_SEED, DEPTH_POINTS = 4321, 256  # --synthetic --depth-loss: the seeded positions per view
+
+
+def synthetic_depth_points(full, viewmats, K, W, H, dev, **kw):
+    """--synthetic --depth-loss: per view, DEPTH_POINTS seeded uniform positions with the depths the TARGET scene's expected-depth
+    render has there under the depth loss's own bilinear rule; positions whose sample is 0 (nothing rendered there) are dropped."""
+    import gsbp_amd
+    from gsbp_amd.polish import render_splats
+    gen = torch.Generator().manual_seed(DEPTH_SEED)
+    out = []
+    for v in range(viewmats.shape[0]):
+        xy = (torch.rand(DEPTH_POINTS, 2, generator=gen) * torch.tensor([W - 1.0, H - 1.0])).to(dev)
+        with torch.no_grad():
+            render, alpha = render_splats(full, viewmats[v], K, W, H, render_mode="RGB+D", return_alpha=True, **kw)
+            d = gsbp_amd.sample_expected_depth(render, alpha, xy)
+        keep = d > 0
+        out.append((xy[keep].contiguous(), d[keep].contiguous()))
+    return out
 
 
 def feature_map_path(directory: str, name: str):
@@ -143,6 +172,9 @@ def main(argv=None) -> int:
     latent_dim = getattr(args, "latent_dim", 128)
     if feature_dim is None and any(hasattr(args, k) for k in ("latent_dim", "feature_weight", "feature_maps")):
         ap.error("--latent-dim, --feature-weight and --feature-maps need --feature-dim")
+    depth_loss = getattr(args, "depth_loss", False)
+    if not depth_loss and any(hasattr(args, k) for k in ("depth_lambda", "depth_kind")):
+        ap.error("--depth-lambda and --depth-kind need --depth-loss")
     if feature_dim is not None and bool(args.colmap) != hasattr(args, "feature_maps"):
         ap.error("--feature-dim takes its maps from --feature-maps with --colmap, and renders them itself with --synthetic")
     import gsbp_amd
@@ -172,6 +204,7 @@ def main(argv=None) -> int:
             with torch.no_grad():
                 feature_maps = [gsbp_amd.render_latents(*geometry, true_latents, viewmats[v], K, W, H, **kw)[0] @ true_decoder
                                 for v in range(viewmats.shape[0])]
+        depth_points = synthetic_depth_points(full, viewmats, K, W, H, dev, **kw) if depth_loss else None
         splats = {k: t[::args.start_stride].contiguous() for k, t in full.items()}
         scene_scale = 1.0 if args.scene_scale is None else args.scene_scale
 
@@ -194,6 +227,10 @@ def main(argv=None) -> int:
             if not have:
                 raise SystemExit(f"no feature map of this model's views in {args.feature_maps}")
         viewmats, names = viewmats[have], [names[v] for v in have]
+        depth_points = None
+        if depth_loss:  # the views' triangulated points, as the reference's loader hands them to its trainer
+            by_name = {im.name: im for im in proj.images.values()}
+            depth_points = [tuple(t.to(dev) for t in scene_io.view_depth_points(proj, by_name[name], K, W, H)) for name in names]
         splats = gsbp_amd.init_splats_from_points(torch.from_numpy(proj.points3D).float().to(dev),
                                                   torch.from_numpy(proj.point3D_colors).to(dev), sh_degree=args.sh_degree)
         scene_scale = 1.1 * camera_extent(viewmats) if args.scene_scale is None else args.scene_scale
@@ -227,12 +264,17 @@ def main(argv=None) -> int:
             return loaded[v]
         feature_kw = dict(feature_fn=feature_of, feature_dim=feature_dim, latent_dim=latent_dim,
                           feature_weight=getattr(args, "feature_weight", 1.0))
+    depth_kw = {}
+    if depth_loss:  # (depth_scale: the reference multiplies its depth term by the scene's scale)
+        depth_kw = dict(depth_fn=lambda v: depth_points[v], depth_scale=scene_scale,
+                        **{k: getattr(args, k) for k in ("depth_lambda", "depth_kind") if hasattr(args, k)})
     before = gsbp_amd.score_image_views(splats, viewmats, K, W, H, image_of, **kw)
     n_start = splats["means"].shape[0]
     trained, history = gsbp_amd.train_scene(splats, viewmats, K, W, H, image_of, args.steps, strategy=cfg, params=args.params,
                                             ssim_lambda=args.ssim_lambda, seed=args.seed,
                                             sh_degree_interval=getattr(args, "sh_degree_interval", None), **reg, **feature_kw,
-                                            **{k: getattr(args, k) for k in ("adam", "means_lr_final") if hasattr(args, k)}, **kw)
+                                            **{k: getattr(args, k) for k in ("adam", "means_lr_final") if hasattr(args, k)}, **depth_kw,
+                                            **kw)
     after = gsbp_amd.score_image_views(trained, viewmats, K, W, H, image_of, **kw)
     torch.save({k: t.cpu() for k, t in trained.items() if torch.is_tensor(t)}, os.path.join(args.out, "trained.pt"))
     extra = {}
@@ -245,7 +287,9 @@ def main(argv=None) -> int:
                        strategy=args.strategy, **reg, config={k: getattr(cfg, k) for k in cfg.__dataclass_fields__}, loss=history["loss"], n=history["n"],
                        rounds=history["rounds"], resets=history["resets"], sh_degree=history["sh_degree"],
                        **({"adam": args.adam} if hasattr(args, "adam") else {}),
-                       **({"means_lr": history["means_lr"]} if "means_lr" in history else {})), f, indent=1)
+                       **({"means_lr": history["means_lr"]} if "means_lr" in history else {}),
+                       **({"depth_loss": history["depth_loss"], "depth_lambda": getattr(args, "depth_lambda", 1e-2),
+                           "depth_scale": scene_scale} if depth_loss else {})), f, indent=1)
     with open(os.path.join(args.out, "metrics.json"), "w") as f:
         json.dump(dict(before=before, after=after), f, indent=1)
     print(f"{n_start} -> {trained['means'].shape[0]} Gaussians in {len(history['rounds'])} rounds; loss {history['loss'][0]:.6e} -> "
