@@ -87,7 +87,7 @@ from .sample import PointGaussians, neighbor_blend, point_gaussians, sample_fiel
 from . import pixels  # noqa: F401
 from .pixels import PixelGaussians, dominance_counts, lookup, median_depth, pick_gaussians, pixel_gaussians, render_id_map  # noqa: F401
 from . import pose  # noqa: F401
-from .pose import pose_error, refine_pose, se3_exp  # noqa: F401
+from .pose import PoseAdjust, pose_error, refine_pose, se3_exp  # noqa: F401
 from . import photometric  # noqa: F401
 from .photometric import gaussian_window, image_metrics, image_sums, photometric_loss, ssim_map  # noqa: F401
 from . import polish  # noqa: F401

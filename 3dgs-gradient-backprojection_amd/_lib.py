@@ -276,6 +276,11 @@ ARGTYPES = {
     # v_colors, v_head, v_tail, v_means, stream
     "gwbp_sh_eval": [_I64, _I32, _I32, _I32, _P, _P, _P, C.POINTER(C.c_float), _P, _P],
     "gwbp_sh_eval_backward": [_I64, _I32, _I32, _I32, _P, _P, _P, C.POINTER(C.c_float), _P, _P, _P, _P, _P],
+    # the same with campos on the device: ..., campos (device), out, stream  /  ..., campos, v_colors, v_head, v_tail, v_means, v_campos,
+    # scratch, stream  /  n_gaussians (returns the scratch's rows, not a status)
+    "gwbp_sh_eval_dev": [_I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P],
+    "gwbp_sh_eval_backward_dev": [_I64, _I32, _I32, _I32] + [_P] * 11,
+    "gwbp_sh_eval_backward_blocks": [_I64],
     # the optimiser step: n, w, p, g, m, v, visible, lr_over_bc1, sqrt_bc2, b1, b2 (float64), eps, stream
     "gwbp_adam_step": [_I64, _I32, _P, _P, _P, _P, _P, _F, _F, C.c_double, C.c_double, _F, _P],
     # the depth losses: height, width, Dp, ch, render, alpha, then

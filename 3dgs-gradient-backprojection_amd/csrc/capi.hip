@@ -2413,6 +2413,62 @@ int gwbp_sh_eval_backward(int64_t N, int32_t degree, int32_t K_head, int32_t K_t
                               as_stream(stream));
 }
 
+// the same pair with the centre on the device (never dereferenced here), and the centre's gradient
+int gwbp_sh_eval_dev(int64_t N, int32_t degree, int32_t K_head, int32_t K_tail, const float *means, const float *head,
+                     const float *tail, const float *campos, float *out, void *stream)
+{
+    if (int rc = check_sh_tables("sh_eval_dev", N, degree, K_head, K_tail, means, head, tail, campos))
+        return rc;
+    if (N > 0 && !out)
+        return set_error(GWBP_EINVAL, "sh_eval_dev: null out");
+    if (misaligned(out, 3) || misaligned(campos, 3))
+        return set_error(GWBP_EINVAL, "sh_eval_dev: campos and out must be 4-B aligned");
+    const void *const written[] = {out}, *const read[] = {means, head, tail, campos};
+    if (N > 0)
+        if (int rc = check_regions_distinct("sh_eval_dev", written, 1, read, 4))
+            return rc;
+    return launch_sh_eval_dev(N, degree, K_head, K_tail, means, head, tail, campos, out, as_stream(stream));
+}
+
+int gwbp_sh_eval_backward_blocks(int64_t n_gaussians)
+{
+    if (n_gaussians < 0 || n_gaussians > 0x7FFFFFFF)
+        return set_error(GWBP_EINVAL, "sh_eval_backward_blocks: %lld Gaussians out of range", (long long)n_gaussians);
+    return sh_eval_backward_blocks(n_gaussians);
+}
+
+int gwbp_sh_eval_backward_dev(int64_t N, int32_t degree, int32_t K_head, int32_t K_tail, const float *means, const float *head,
+                              const float *tail, const float *campos, const float *v_colors, float *v_head, float *v_tail,
+                              float *v_means, double *v_campos, double *scratch, void *stream)
+{
+    if (int rc = check_sh_tables("sh_eval_backward_dev", N, degree, K_head, K_tail, means, head, tail, campos))
+        return rc;
+    if (!v_head && !v_tail && !v_means && !v_campos)
+        return set_error(GWBP_EINVAL, "sh_eval_backward_dev: every output (v_head, v_tail, v_means, v_campos) is null");
+    if (v_tail && K_tail == 0)
+        return set_error(GWBP_EINVAL, "sh_eval_backward_dev: v_tail with K_tail = 0");
+    if (N > 0 && !v_colors)
+        return set_error(GWBP_EINVAL, "sh_eval_backward_dev: null v_colors");
+    if (N > 0 && v_campos && !scratch)
+        return set_error(GWBP_EINVAL, "sh_eval_backward_dev: v_campos needs the scratch (gwbp_sh_eval_backward_blocks(N) x 3 doubles)");
+    if (misaligned(campos, 3) || misaligned(v_colors, 3) || misaligned(v_head, 3) || misaligned(v_tail, 3) || misaligned(v_means, 3))
+        return set_error(GWBP_EINVAL, "sh_eval_backward_dev: campos, v_colors, v_head, v_tail and v_means must be 4-B aligned");
+    if (misaligned(v_campos, 7) || misaligned(scratch, 7))
+        return set_error(GWBP_EINVAL, "sh_eval_backward_dev: v_campos and scratch must be 8-B aligned");
+    const void *written[5];
+    int n_written = 0;
+    for (const void *p : {(const void *)v_head, (const void *)v_tail, (const void *)v_means, (const void *)v_campos,
+                          (const void *)(v_campos ? scratch : nullptr)})
+        if (p)
+            written[n_written++] = p;
+    const void *const read[] = {means, head, tail, campos, v_colors};
+    if (N > 0)
+        if (int rc = check_regions_distinct("sh_eval_backward_dev", written, n_written, read, 5))
+            return rc;
+    return launch_sh_eval_bwd_dev(N, degree, K_head, K_tail, means, head, tail, campos, v_colors, v_head, v_tail, v_means, v_campos,
+                                  scratch, as_stream(stream));
+}
+
 // ---- the optimiser step (adam.hip) ------------------------------------------------------------------------------------------------
 int gwbp_adam_step(int64_t n, int32_t w, float *p, const float *g, float *m, float *v, const uint8_t *visible, float lr_over_bc1,
                    float sqrt_bc2, double b1, double b2, float eps, void *stream)

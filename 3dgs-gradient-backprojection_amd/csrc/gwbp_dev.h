@@ -297,6 +297,14 @@ int launch_sh_eval(int64_t N, int degree, int k_head, int k_tail, const float *m
                    const float *campos, float *out, hipStream_t s);
 int launch_sh_eval_bwd(int64_t N, int degree, int k_head, int k_tail, const float *means, const float *head, const float *tail,
                        const float *campos, const float *v_colors, float *v_head, float *v_tail, float *v_means, hipStream_t s);
+// the same two with campos a device pointer to three floats; v_campos [3] (nullptr, or with scratch [sh_eval_backward_blocks(N), 3]):
+// minus the sum of the rows' v_means values, in a fixed order
+int launch_sh_eval_dev(int64_t N, int degree, int k_head, int k_tail, const float *means, const float *head, const float *tail,
+                       const float *campos_dev, float *out, hipStream_t s);
+int sh_eval_backward_blocks(int64_t n);
+int launch_sh_eval_bwd_dev(int64_t N, int degree, int k_head, int k_tail, const float *means, const float *head, const float *tail,
+                           const float *campos_dev, const float *v_colors, float *v_head, float *v_tail, float *v_means,
+                           double *v_campos, double *scratch, hipStream_t s);
 // backward of launch_render_px for an fp32 table (render_grad.hip): adds into v_g2d [N, 6] and, unless nullptr, v_colors [N, D]
 int launch_render_px_bwd(const Ws &W, const ViewDev &V, const float *colors, int64_t ldc, int D, const float *v_out,
                          const float *v_alpha, float *v_colors, float *v_g2d, hipStream_t s);

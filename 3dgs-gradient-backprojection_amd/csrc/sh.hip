@@ -5,6 +5,8 @@
 //                       head[i][k] for k < K_head and tail[i][k - K_head] behind (tail == nullptr: one table).
 //   k_sh_eval_bwd<DEG>  v_head, v_tail (the rows' gradients, exact +0 from row (DEG + 1)^2 on) and v_means from v_colors; each output
 //                       may be nullptr.  It recomputes direction, basis and pre-clamp colour: the forward saves nothing.
+//   k_sh_eval_dev<DEG>, k_sh_eval_bwd_dev<DEG>, k_sh_campos_sum   the same with the camera centre read on the device, and its
+//                       gradient v_campos (a pose that is trained with the Gaussians); described where they stand.
 //
 // Memory shape.  A thread owns a Gaussian, but a lane-per-row walk of 180-B or 192-B rows would scatter every load over 64 rows.  The
 // rows of a workgroup's 256 Gaussians are one contiguous span of each table: the workgroup copies the span into LDS with consecutive
@@ -154,6 +156,131 @@ __global__ __launch_bounds__(kShBlock) void k_sh_eval_bwd(int64_t N, int k_head,
         sh_copy_span<true>(v_tail + (size_t)first * 3 * k_tail, rows * 3u * k_tail, 3u * k_tail, s_rows, 3 * k_head, stride);
 }
 
+// ---- the centre on the device, and its gradient ------------------------------------------------------------------------------------
+// k_sh_eval_dev / k_sh_eval_bwd_dev are the two kernels above with `campos` a device pointer to three floats: every thread loads
+// them (one address for the whole grid), everything behind the loads is the same expression, so the same three values give the same
+// bits.  The backward adds v_campos: dir = mean - campos, so d loss / d campos = -sum_i vm_i over the rows' float32 v_means values.
+// The sum follows project_grad.hip: each thread widens its three values to double (rows >= N hold exact 0), the lanes of a wave are
+// added by shuffles, the waves of a block in LDS in wave order, each block stores its [3] with plain stores into the caller's scratch
+// [n_blocks, 3], and k_sh_campos_sum, one workgroup, adds the blocks in block order and negates.  No atomics: same inputs, same bits.
+constexpr int kCamGrad = 3;
+
+template <int DEG>
+__global__ __launch_bounds__(kShBlock) void k_sh_eval_dev(int64_t N, int k_head, int k_tail, const float *__restrict__ means,
+                                                          const float *head, const float *tail, const float *__restrict__ campos,
+                                                          float *__restrict__ out)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_rows[];
+    const float cx = campos[0], cy = campos[1], cz = campos[2];
+    const int64_t first = (int64_t)blockIdx.x * kShBlock;
+    const int64_t left = N - first;
+    const unsigned rows = left < kShBlock ? (unsigned)left : (unsigned)kShBlock;
+    const int stride = sh_stride(k_head + k_tail);
+    sh_copy_span<false>(const_cast<float *>(head) + (size_t)first * 3 * k_head, rows * 3u * k_head, 3u * k_head, s_rows, 0, stride);
+    if (tail)
+        sh_copy_span<false>(const_cast<float *>(tail) + (size_t)first * 3 * k_tail, rows * 3u * k_tail, 3u * k_tail, s_rows, 3 * k_head,
+                            stride);
+    __syncthreads();
+    if (threadIdx.x < rows) {
+        const int64_t i = first + threadIdx.x;
+        const float m[3] = {means[3 * i], means[3 * i + 1], means[3 * i + 2]};
+        float c[3];
+        sh_forward_row<DEG>(m, cx, cy, cz, s_rows + threadIdx.x * stride, c);
+        out[3 * i] = c[0], out[3 * i + 1] = c[1], out[3 * i + 2] = c[2];
+    }
+}
+
+template <int DEG>
+__global__ __launch_bounds__(kShBlock) void k_sh_eval_bwd_dev(int64_t N, int k_head, int k_tail, const float *__restrict__ means,
+                                                              const float *head, const float *tail,
+                                                              const float *__restrict__ campos, const float *__restrict__ v_colors,
+                                                              float *v_head, float *v_tail, float *__restrict__ v_means,
+                                                              double *__restrict__ partials)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_rows[];
+    const float cx = campos[0], cy = campos[1], cz = campos[2];
+    const int64_t first = (int64_t)blockIdx.x * kShBlock;
+    const int64_t left = N - first;
+    const unsigned rows = left < kShBlock ? (unsigned)left : (unsigned)kShBlock;
+    const int stride = sh_stride(k_head + k_tail);
+    sh_copy_span<false>(const_cast<float *>(head) + (size_t)first * 3 * k_head, rows * 3u * k_head, 3u * k_head, s_rows, 0, stride);
+    if (tail)
+        sh_copy_span<false>(const_cast<float *>(tail) + (size_t)first * 3 * k_tail, rows * 3u * k_tail, 3u * k_tail, s_rows, 3 * k_head,
+                            stride);
+    __syncthreads();
+    float vm[3] = {0.f, 0.f, 0.f}; // (rows >= N keep the zeros and add them below)
+    if (threadIdx.x < rows) {
+        const int64_t i = first + threadIdx.x;
+        const float m[3] = {means[3 * i], means[3 * i + 1], means[3 * i + 2]};
+        const float v[3] = {v_colors[3 * i], v_colors[3 * i + 1], v_colors[3 * i + 2]};
+        float *row = s_rows + threadIdx.x * stride;
+        float *const v_row = (v_head || v_tail) ? row : nullptr;
+        if (v_means || partials) {
+            sh_backward_row<DEG>(m, cx, cy, cz, row, k_head + k_tail, v, v_row, vm);
+            if (v_means)
+                v_means[3 * i] = vm[0], v_means[3 * i + 1] = vm[1], v_means[3 * i + 2] = vm[2];
+        } else {
+            sh_backward_row<DEG>(m, cx, cy, cz, row, k_head + k_tail, v, v_row, nullptr);
+        }
+    }
+    __syncthreads();
+    if (v_head)
+        sh_copy_span<true>(v_head + (size_t)first * 3 * k_head, rows * 3u * k_head, 3u * k_head, s_rows, 0, stride);
+    if (v_tail)
+        sh_copy_span<true>(v_tail + (size_t)first * 3 * k_tail, rows * 3u * k_tail, 3u * k_tail, s_rows, 3 * k_head, stride);
+
+    // The centre's sums, in an LDS array of their own (s_rows may still be read by a slower wave's copy-out).  `partials` is a kernel
+    // argument: the branch is uniform over the grid, and inside it every thread takes part in every shuffle and reaches the barrier.
+    if (partials) {
+        __shared__ double s_wave[kShBlock / 64][kCamGrad];
+        double acc[kCamGrad] = {(double)vm[0], (double)vm[1], (double)vm[2]};
+#pragma unroll
+        for (int k = 0; k < kCamGrad; ++k)
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1)
+                acc[k] += __shfl_down(acc[k], o, 64);
+        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+        if (lane == 0) {
+#pragma unroll
+            for (int k = 0; k < kCamGrad; ++k)
+                s_wave[wave][k] = acc[k];
+        }
+        __syncthreads();
+        if (threadIdx.x < kCamGrad) {
+            double sum = s_wave[0][threadIdx.x];
+#pragma unroll
+            for (int w = 1; w < kShBlock / 64; ++w)
+                sum += s_wave[w][threadIdx.x];
+            partials[(int64_t)blockIdx.x * kCamGrad + threadIdx.x] = sum;
+        }
+    }
+}
+
+// out[k] = -(the blocks' partial sums in block order): thread (c, k) adds value k of the blocks of chunk c, first to last; after the
+// barrier the chunks are added first to last.  0.0 - sum, not -sum: a sum of zeros (degree 0) gives +0.  One workgroup; every thread
+// reaches the barrier.
+constexpr int kCamChunks = 85; // 85 x 3 = 255 of 256 threads
+__global__ __launch_bounds__(256) void k_sh_campos_sum(int n_blocks, const double *__restrict__ partials, double *__restrict__ out)
+{
+    __shared__ double s_chunk[kCamChunks][kCamGrad];
+    const int c = threadIdx.x / kCamGrad, k = threadIdx.x % kCamGrad;
+    const int per = (n_blocks + kCamChunks - 1) / kCamChunks;
+    if (c < kCamChunks) {
+        double sum = 0.0;
+        const int begin = min(n_blocks, c * per), end = min(n_blocks, (c + 1) * per);
+        for (int b = begin; b < end; ++b)
+            sum += partials[(int64_t)b * kCamGrad + k];
+        s_chunk[c][k] = sum;
+    }
+    __syncthreads();
+    if (threadIdx.x < kCamGrad) {
+        double sum = s_chunk[0][threadIdx.x];
+        for (int j = 1; j < kCamChunks; ++j)
+            sum += s_chunk[j][threadIdx.x];
+        out[threadIdx.x] = 0.0 - sum;
+    }
+}
+
 } // namespace
 
 size_t sh_lds_bytes(int k_total) { return (size_t)kShBlock * sh_stride(k_total) * sizeof(float); }
@@ -200,6 +327,57 @@ int launch_sh_eval_bwd(int64_t N, int degree, int k_head, int k_tail, const floa
     }
 #undef GWBP_SH
     return check_hip(hipGetLastError(), "sh_eval_backward launch");
+}
+
+int launch_sh_eval_dev(int64_t N, int degree, int k_head, int k_tail, const float *means, const float *head, const float *tail,
+                       const float *campos_dev, float *out, hipStream_t s)
+{
+    unsigned grid;
+    if (int rc = grid_of("sh_eval_dev", N, &grid, kShBlock))
+        return rc;
+    if (grid == 0)
+        return GWBP_OK;
+    const size_t lds = sh_lds_bytes(k_head + k_tail);
+#define GWBP_SH(D)                                                                                                                \
+    hipLaunchKernelGGL(k_sh_eval_dev<D>, dim3(grid), dim3(kShBlock), lds, s, N, k_head, k_tail, means, head, tail, campos_dev, out)
+    switch (degree) {
+    case 0: GWBP_SH(0); break;
+    case 1: GWBP_SH(1); break;
+    case 2: GWBP_SH(2); break;
+    default: GWBP_SH(3); break;
+    }
+#undef GWBP_SH
+    return check_hip(hipGetLastError(), "sh_eval_dev launch");
+}
+
+int sh_eval_backward_blocks(int64_t n) { return (int)((n + kShBlock - 1) / kShBlock); }
+
+int launch_sh_eval_bwd_dev(int64_t N, int degree, int k_head, int k_tail, const float *means, const float *head, const float *tail,
+                           const float *campos_dev, const float *v_colors, float *v_head, float *v_tail, float *v_means,
+                           double *v_campos, double *scratch, hipStream_t s)
+{
+    unsigned grid;
+    if (int rc = grid_of("sh_eval_backward_dev", N, &grid, kShBlock))
+        return rc;
+    if (grid == 0) {
+        if (v_campos)
+            return check_hip(hipMemsetAsync(v_campos, 0, kCamGrad * sizeof(double), s), "memset v_campos");
+        return GWBP_OK;
+    }
+    const size_t lds = sh_lds_bytes(k_head + k_tail);
+#define GWBP_SH(D)                                                                                                                \
+    hipLaunchKernelGGL(k_sh_eval_bwd_dev<D>, dim3(grid), dim3(kShBlock), lds, s, N, k_head, k_tail, means, head, tail, campos_dev,    \
+                       v_colors, v_head, v_tail, v_means, v_campos ? scratch : nullptr)
+    switch (degree) {
+    case 0: GWBP_SH(0); break;
+    case 1: GWBP_SH(1); break;
+    case 2: GWBP_SH(2); break;
+    default: GWBP_SH(3); break;
+    }
+#undef GWBP_SH
+    if (v_campos)
+        hipLaunchKernelGGL(k_sh_campos_sum, dim3(1), dim3(256), 0, s, (int)grid, scratch, v_campos);
+    return check_hip(hipGetLastError(), "sh_eval_backward_dev launch");
 }
 
 } // namespace gwbp

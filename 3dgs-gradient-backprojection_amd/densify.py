@@ -331,7 +331,8 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
                 feature_fn: Optional[Callable[[int], torch.Tensor]] = None, feature_dim: Optional[int] = None, latent_dim: int = 128,
                 feature_weight: float = 1.0, feature_loss: str = "l1", decoder_lr: float = 2.5e-3, decoder=None, adam: str = "torch",
                 means_lr_final: Optional[float] = None, depth_fn: Optional[Callable[[int], object]] = None, depth_lambda: float = 1e-2,
-                depth_scale: float = 1.0, depth_kind: str = "disparity", **raster_kw):
+                depth_scale: float = 1.0, depth_kind: str = "disparity", pose_opt: bool = False, pose_opt_lr: float = 1e-5,
+                pose_opt_reg: float = 1e-6, pose_noise: float = 0.0, **raster_kw):
     """polish_scene's loop with the schedule: Adam on the named parameters under the photometric loss, the set growing and shrinking
     on the way.  Step s (from 0) renders one view with means2d_grad=True, runs the backward, adds the view into the statistics while
     s < refine_stop_iter, steps the optimiser, runs a densify round when s > refine_start_iter, s % refine_every == 0 and
@@ -383,11 +384,21 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
     (points [M, 2], depths [M]) pair -- scene_io.view_depth_points makes one from a COLMAP model -- or depth.depth_map_loss(kind=
     depth_kind) for an [H, W] depth map.  Both read the render's accumulated depth and alpha in place.  The densify statistics see the
     gradient of the summed loss, as in the reference.  history["depth_loss"]: the term before its weight, one value per step (0 for a
-    view without supervision), read once behind the loop."""
+    view without supervision), read once behind the loop.
+    pose_noise > 0: a fixed pose.PoseAdjust, drawn once from `seed` with std = pose_noise, perturbs every view first (the reference's
+    pose_perturb: captures whose COLMAP poses are slightly off).  pose_opt: a zero-initialised PoseAdjust is applied behind the noise and
+    trained with the Gaussians by its own torch.optim.Adam(lr=pose_opt_lr, weight_decay=pose_opt_reg), step s at pose_opt_lr *
+    0.01 ** (s / steps); the colour render then runs with pose_grad=True and the latent render with camera_grad=True (the depth column is
+    a torch function of the view matrix already).  history gains viewmats [V, 4, 4] (the views as they ended), pose_adjust [V, 9] under
+    pose_opt -- in history, not in the splat dict: a round moves every tensor of N rows, and V may equal N -- and under pose_noise
+    pose_err: per step, the mean absolute difference between the true and the used camera-to-world matrices over all views, read once
+    behind the loop.  A negative or non-finite value, and either option without a view, raise GwbpError.  pose.PoseTraining holds all of
+    it; without these keywords nothing of the step changes."""
     from .decoded_field import decoded_loss
     from .depth import depth_map_loss, depth_point_loss
     from .latent_render import render_latents
     from .mcmc import MCMCConfig, inject_noise, relocate, sample_add
+    from .pose import PoseTraining, check_pose_options
     if strategy is not None and cfg is not None:
         raise GwbpError("train_scene() takes cfg= or strategy=, not both")
     if strategy is not None and not isinstance(strategy, (DensifyConfig, MCMCConfig)):
@@ -409,7 +420,10 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
             if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(float(value)):
                 raise GwbpError(f"train_scene(): {name} must be a finite number, got {value!r}")
         depth_kw = dict(render_mode="RGB+D", return_alpha=True)
+    posed = check_pose_options("train_scene", int(viewmats.shape[0]), pose_opt, pose_opt_lr, pose_opt_reg, pose_noise)
     work, opt = trainable(splats, params, lrs, "train_scene", check_adam(adam, "train_scene"))
+    poses = PoseTraining(viewmats.to(work["means"].device), steps, seed, pose_opt, pose_opt_lr, pose_opt_reg, pose_noise) if posed else None
+    pose_kw, latent_pose_kw = (dict(pose_grad=True), dict(camera_grad=True)) if pose_opt else ({}, {})
     decayed = means_group(opt, work) if final is not None else None
     if final is not None and decayed is None:
         raise GwbpError("train_scene(): means_lr_final decays the means group's rate, and the means are not among params")
@@ -430,10 +444,11 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
         opt.zero_grad(set_to_none=True)
         degrees.append(table_degree if interval is None else scheduled_sh_degree(step, interval, table_degree))
         geometry, f_loss = (splat_geometry(work) if feature_fn is not None else None), None  # (one exp and one sigmoid for both renders)
-        image, *alpha, meta = render_splats(work, viewmats[v], view_K(K, v), width, height, return_meta=True,
+        viewmat = viewmats[v] if poses is None else poses.view(v)
+        image, *alpha, meta = render_splats(work, viewmat, view_K(K, v), width, height, return_meta=True,
                                             means2d_grad=mcmc is None or adam == "visible",
                                             sh_degree=None if interval is None else degrees[-1], geometry=geometry, **depth_kw,
-                                            **raster_kw)
+                                            **pose_kw, **raster_kw)
         loss = photometric_loss(image[..., :3] if depth_fn is not None else image, image_fn(v), ssim_lambda=ssim_lambda)
         if depth_fn is not None:
             target = depth_fn(v)
@@ -450,7 +465,8 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
             del target, d_loss
         if feature_fn is not None:
             opt_dec.zero_grad(set_to_none=True)
-            latent_map, _ = render_latents(*geometry, work["features"], viewmats[v], view_K(K, v), width, height, **latent_kw)
+            latent_map, _ = render_latents(*geometry, work["features"], viewmat, view_K(K, v), width, height, **latent_kw,
+                                           **latent_pose_kw)
             f_loss = decoded_loss(latent_map, decoder, feature_fn(v), loss=feature_loss)
             feature_losses.append(f_loss.detach())
             loss = loss + float(feature_weight) * f_loss
@@ -471,11 +487,13 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
             opt.step()
         if opt_dec is not None:
             opt_dec.step()
+        if poses is not None:
+            poses.step(step)
         losses.append(loss.detach())
         sizes.append(int(work["means"].shape[0]))
         if mcmc is not None:
             if mcmc.refines_at(step):
-                del image, alpha, meta, loss, f_loss, geometry
+                del image, alpha, meta, loss, f_loss, geometry, viewmat
                 n_before = sizes[-1]
                 work, moved = relocate(work, mcmc, optimizer=opt, carry=carried, generator=noise_gen)
                 work, added = sample_add(work, mcmc, mcmc.n_new(n_before), optimizer=opt, carry=moved["carry"], generator=noise_gen)
@@ -489,7 +507,7 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
                 inject_noise(work, rate, mcmc, generator=noise_gen)
             continue
         if cfg.refines_at(step):
-            del image, alpha, meta, loss, f_loss, geometry  # (the graph holds the old set's workspace)
+            del image, alpha, meta, loss, f_loss, geometry, viewmat  # (the graph holds the old set's workspace)
             work, info = densify(work, state, cfg, step, optimizer=opt, carry=carried, generator=noise_gen)
             carried = info["carry"]
             if info["n_after"] < 1:
@@ -505,6 +523,8 @@ def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, ima
         history["means_lr"] = means_lrs
     if depth_fn is not None:
         history["depth_loss"] = torch.stack(depth_losses).cpu().tolist() if depth_losses else []
+    if poses is not None:
+        history.update(poses.history())
     if feature_fn is not None:
         history.update(feature_loss=torch.stack(feature_losses).cpu().tolist() if feature_losses else [], decoder=decoder.detach())
     return {k: (t.detach() if torch.is_tensor(t) else t) for k, t in work.items()}, history

@@ -114,6 +114,51 @@ def sh_eval_tables_backward(call, stream, degree, means, head, tail, campos, v_c
     return v_head, v_tail, v_means
 
 
+def _sh_campos_dev(campos, means) -> torch.Tensor:
+    """The camera centre as gwbp_sh_eval_dev reads it: three float32 values on means' device, never read on the host."""
+    if not torch.is_tensor(campos) or not campos.is_cuda or campos.dtype != torch.float32 or campos.numel() != 3 \
+            or campos.device != means.device:
+        raise GwbpError("the device camera centre must be a float32 HIP tensor of three elements on the means' device")
+    return campos.detach().reshape(3).contiguous()
+
+
+def sh_eval_tables_dev(call, stream, degree, means, head, tail, campos) -> torch.Tensor:
+    """sh_eval_tables with the centre a device tensor (gwbp_sh_eval_dev): the same bits for the same three values."""
+    means, head, tail = _sh_tables(degree, means, head, tail)
+    cp = _sh_campos_dev(campos, means)
+    out = torch.empty(means.shape[0], 3, device=means.device)
+    call("gwbp_sh_eval_dev", c_int64(means.shape[0]), int(degree), head.shape[1], 0 if tail is None else tail.shape[1], ptr(means),
+         ptr(head), ptr(tail), ptr(cp), ptr(out), stream)
+    return out
+
+
+def sh_eval_tables_backward_dev(call, stream, degree, means, head, tail, campos, v_colors, want_head, want_tail, want_means,
+                                want_campos):
+    """sh_eval_tables_backward with the centre a device tensor (gwbp_sh_eval_backward_dev): (v_head, v_tail, v_means, v_campos), the
+    last float64 [3] = minus the fixed-order sum of the rows' v_means values."""
+    means, head, tail = _sh_tables(degree, means, head, tail)
+    cp = _sh_campos_dev(campos, means)
+    v_colors = _req(v_colors, "v_colors", (3,))
+    if v_colors.shape[0] != means.shape[0]:
+        raise GwbpError(f"v_colors must be [{means.shape[0]},3], got {tuple(v_colors.shape)}")
+    v_head = torch.empty_like(head) if want_head else None
+    v_tail = torch.empty_like(tail) if want_tail and tail is not None else None
+    v_means = torch.empty_like(means) if want_means else None
+    v_campos = scratch = None
+    if want_campos:
+        blocks = int(_lib.lib().gwbp_sh_eval_backward_blocks(c_int64(means.shape[0])))
+        if blocks < 0:
+            check(blocks, "gwbp_sh_eval_backward_blocks")
+        v_campos = torch.empty(3, dtype=torch.float64, device=means.device)
+        scratch = torch.empty(max(blocks, 1), 3, dtype=torch.float64, device=means.device)
+    if v_head is None and v_tail is None and v_means is None and v_campos is None:
+        raise GwbpError("sh_eval_backward: no output asked for")
+    call("gwbp_sh_eval_backward_dev", c_int64(means.shape[0]), int(degree), head.shape[1], 0 if tail is None else tail.shape[1],
+         ptr(means), ptr(head), ptr(tail), ptr(cp), ptr(v_colors), ptr(v_head), ptr(v_tail), ptr(v_means), ptr(v_campos), ptr(scratch),
+         stream)
+    return v_head, v_tail, v_means, v_campos
+
+
 def adam_scalars(step: int, lr: float, b1: float, b2: float):
     """(lr / (1 - b1^step), sqrt(1 - b2^step)) in float64, as torch's single-tensor Adam forms them on the host; the C ABI takes each
     rounded to float32 once."""
@@ -1426,6 +1471,19 @@ class Engine:
         degree 0.  No atomics: the same bits every run."""
         return sh_eval_tables_backward(self._call, self._stream(), degree, means, head, tail, campos, v_colors, want_head, want_tail,
                                        want_means)
+
+    def sh_eval_dev(self, degree: int, means, head, tail, campos):
+        """sh_eval with campos a float32 HIP tensor of three elements that the kernel loads (gwbp_sh_eval_dev): no host read, and
+        sh_eval's bits for the same three values."""
+        return sh_eval_tables_dev(self._call, self._stream(), degree, means, head, tail, campos)
+
+    def sh_eval_backward_dev(self, degree: int, means, head, tail, campos, v_colors, want_head: bool = True, want_tail: bool = True,
+                             want_means: bool = True, want_campos: bool = True):
+        """The backward of sh_eval_dev (gwbp_sh_eval_backward_dev): (v_head, v_tail, v_means, v_campos).  The first three have
+        sh_eval_backward's bits; v_campos is float64 [3], minus the sum of the rows' v_means values taken without atomics in a fixed
+        order (exact +0 at degree 0)."""
+        return sh_eval_tables_backward_dev(self._call, self._stream(), degree, means, head, tail, campos, v_colors, want_head,
+                                           want_tail, want_means, want_campos)
 
     def adam_step(self, p, g, m, v, step: int, lr: float, b1: float = 0.9, b2: float = 0.999, eps: float = 1e-8, visible=None) -> None:
         """One Adam step of the float32 table p [n, ...] IN PLACE from its gradient g, with the moments m and v (gwbp_adam_step;

@@ -18,6 +18,7 @@ import torch
 
 from ._lib import GwbpError
 from .photometric import image_metrics, photometric_loss
+from .projection import sh_colors_torch
 from .rasterization import SH_CAMERA_GRAD_MESSAGE, rasterization, sh_kernel_enabled
 from .sh import sh_colors
 
@@ -56,13 +57,17 @@ def splat_geometry(splats: Dict[str, torch.Tensor]):
 
 
 def render_splats(splats: Dict[str, torch.Tensor], viewmat, K, width: int, height: int, return_meta: bool = False,
-                  sh_degree: Optional[int] = None, geometry=None, return_alpha: bool = False, **raster_kw):
+                  sh_degree: Optional[int] = None, geometry=None, return_alpha: bool = False, pose_grad: bool = False, **raster_kw):
     """The [H, W, 3] image of a splat dict from one camera, as the trainer renders it: scales = exp, opacities = sigmoid, raw quats,
     the SH colours of features_dc and features_rest.  Differentiable in every tensor of the dict.
     sh_degree: the degree to evaluate, at most the one the tables' coefficient count gives (None: that one).  Below it the rows above
     (sh_degree + 1)^2 are not read, and their gradients are zeros, not None.
     The colours come from sh.sh_colors on the two tables as they are stored (no torch.cat, one HIP kernel forward and one backward) and
     go to rasterization() as an [N, 3] table; camera_grad=True is refused as rasterization() refuses it beside sh_degree.
+    pose_grad=True with a viewmat that requires grad also differentiates the view matrix: the SH centre -(R^T t) is computed in torch on
+    the device and stays attached, sh_colors(campos_grad=True) carries the colour gradient to it, and the table goes to
+    rasterization(camera_grad=True); the view matrix is not read on the host for the colours.  Under torch.no_grad() or with a viewmat
+    that does not require grad it is the plain call.
     return_meta: (image, meta) -- the eager part of rasterization()'s meta, which under means2d_grad=True holds the means2d leaf.
     geometry: splat_geometry(splats) computed by the caller, who hands the same activations to a second render (train_scene's
     feature term); None computes them here.
@@ -73,9 +78,20 @@ def render_splats(splats: Dict[str, torch.Tensor], viewmat, K, width: int, heigh
     if isinstance(degree, bool) or not isinstance(degree, int) or not 0 <= degree <= table:
         raise GwbpError(f"sh_degree must be an int in [0, {table}] (the tables' degree), got {sh_degree!r}")
     means, dc, rest = splats["means"], splats["features_dc"], splats.get("features_rest")
-    if raster_kw.get("camera_grad") and torch.is_grad_enabled() and viewmat.requires_grad:
+    if raster_kw.get("camera_grad") and not pose_grad and torch.is_grad_enabled() and viewmat.requires_grad:
         raise NotImplementedError(SH_CAMERA_GRAD_MESSAGE)
     geometry = splat_geometry(splats) if geometry is None else geometry
+    if pose_grad and torch.is_grad_enabled() and viewmat.requires_grad:
+        if not means.is_cuda:
+            raise GwbpError("render_splats(pose_grad=True) needs HIP tensors (there is no CPU path)")
+        campos = -(viewmat[:3, :3].T @ viewmat[:3, 3])  # on the device, attached: no host read of the view matrix
+        if sh_kernel_enabled():
+            colors = sh_colors(degree, means, dc, campos.float(), rest=rest, campos_grad=True)
+        else:  # (set_sh_kernel(False): the torch form with the same attached centre, the other side of a timing)
+            colors = sh_colors_torch(degree, means, dc if rest is None else torch.cat([dc, rest], dim=1), campos)
+        out, alphas, meta = rasterization(*geometry, colors, viewmat[None], K[None], width, height, sh_degree=None, want_meta=False,
+                                          **dict(raster_kw, camera_grad=True))
+        return _render_result(out, alphas, meta, return_alpha, return_meta)
     if not sh_kernel_enabled() or not means.is_cuda:  # (set_sh_kernel(False): the route before the kernels; CPU tensors: its error)
         sh = dc if rest is None else torch.cat([dc, rest], dim=1)
         out, alphas, meta = rasterization(*geometry, sh, viewmat[None], K[None], width, height, sh_degree=degree, want_meta=False, **raster_kw)

@@ -617,6 +617,24 @@ GWBP_API int gwbp_sh_eval_backward(int64_t N, int32_t degree, int32_t K_head, in
                                    const float *tail, const float *campos_host, const float *v_colors, float *v_head, float *v_tail,
                                    float *v_means, void *stream);
 
+/* The same pair for a camera centre that lives on the device (a pose that is trained with the Gaussians): campos is a DEVICE pointer
+ * to three floats, loaded by the kernels and never read on the host.  For the same three values gwbp_sh_eval_dev gives gwbp_sh_eval's
+ * bits, and gwbp_sh_eval_backward_dev gives gwbp_sh_eval_backward's v_head, v_tail and v_means bits.  It adds
+ *   v_campos double [3] or NULL: d loss / d campos = minus the sum over the rows of their float32 v_means values (the direction is
+ *          mean - campos), each widened to double and added without atomics in a fixed order (wave, block, then the blocks in
+ *          order): the same inputs give the same bits; exact +0 at degree 0 and at N = 0.  Where N > 0 it needs
+ *   scratch double [gwbp_sh_eval_backward_blocks(N), 3], which the call overwrites.
+ * GWBP_EINVAL before any HIP call: as for the pair above (campos in the place of campos_host, and 4-B aligned), every one of the four
+ * outputs null, v_campos without scratch where N > 0, v_campos or scratch not 8-B aligned, an output or the scratch that is one of the
+ * inputs or another output. */
+GWBP_API int gwbp_sh_eval_dev(int64_t N, int32_t degree, int32_t K_head, int32_t K_tail, const float *means, const float *head,
+                              const float *tail, const float *campos, float *out, void *stream);
+GWBP_API int gwbp_sh_eval_backward_dev(int64_t N, int32_t degree, int32_t K_head, int32_t K_tail, const float *means,
+                                       const float *head, const float *tail, const float *campos, const float *v_colors,
+                                       float *v_head, float *v_tail, float *v_means, double *v_campos, double *scratch, void *stream);
+/* Rows of gwbp_sh_eval_backward_dev's scratch for n_gaussians Gaussians (one per workgroup of 256: ceil(n / 256)), or GWBP_EINVAL. */
+GWBP_API int gwbp_sh_eval_backward_blocks(int64_t n_gaussians);
+
 /* ---- fused entry points --------------------------------------------------------------------------------- */
 
 /* project -> bin_sort -> blend_weights -> scatter for one view: the per-view body of

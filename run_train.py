@@ -8,6 +8,7 @@ the means every step (csrc/mcmc.hip), and the reference's opacity and scale regu
     python run_train.py --synthetic T0 --steps 60 --refine-start 10 --refine-every 10 --out /tmp/train
     python run_train.py --synthetic T0 --steps 60 --strategy mcmc --cap-max 300 --refine-start 10 --refine-every 10 --out /tmp/train
     python run_train.py --synthetic T0 --steps 60 --feature-dim 32 --latent-dim 16 --out /tmp/train
+    python run_train.py --synthetic T0 --steps 60 --pose-opt --pose-opt-lr 2e-3 --pose-noise 0.02 --out /tmp/train
 
 --colmap DIR: cameras.bin, images.bin and points3D.bin of a COLMAP sparse model; the start is its point cloud (gsbp_amd.
 init_splats_from_points).  --images DIR: per view the image <image name> itself (read with PIL when it imports), or <image name>.pt /
@@ -26,6 +27,12 @@ history.json the steps' feature losses.
 |1 / depth - 1 / true depth| of the render's expected depth sampled at the view's points.  With --colmap the points are the view's
 triangulated COLMAP points (gsbp_amd.scene_io.view_depth_points); with --synthetic 256 seeded positions per view with the true scene's
 depth there.  history.json then holds the steps' depth losses under "depth_loss".
+--pose-opt trains a correction per view with the Gaussians (gsbp_amd.train_scene(pose_opt=True): the reference trainer's pose_opt, for
+captures whose COLMAP poses are slightly off) at --pose-opt-lr (decayed to a hundredth over the run) with --pose-opt-reg weight decay;
+--pose-noise STD perturbs every view once, seeded, before anything else (the reference's pose_noise: a test of the former, and it may
+stand alone).  Then --out also holds poses.pt (pose_adjust [V, 9] under --pose-opt, viewmats [V, 4, 4]: the views as they ended, and
+the views' names), metrics.json's "after" is scored with those view matrices, and history.json holds the option values and, under
+--pose-noise, pose_err: per step the mean absolute difference between the true and the used camera-to-world matrices.
 """
 import argparse
 import json
@@ -72,6 +79,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--depth-kind", choices=("disparity", "depth"), default=argparse.SUPPRESS,
                     help="what a depth MAP is compared in (train_scene(depth_kind=...)).  Both sources this script has hand over POINTS, "
                          "which are always compared in disparity: the switch is passed on and changes nothing until a map source exists")
+    ap.add_argument("--pose-opt", action="store_true", default=argparse.SUPPRESS,
+                    help="train a pose correction per view with the Gaussians, as the reference trainer's pose_opt does")
+    ap.add_argument("--pose-opt-lr", type=float, default=argparse.SUPPRESS, help="its learning rate (default 1e-5)")
+    ap.add_argument("--pose-opt-reg", type=float, default=argparse.SUPPRESS, help="its weight decay (default 1e-6)")
+    ap.add_argument("--pose-noise", type=float, default=argparse.SUPPRESS, metavar="STD",
+                    help="perturb every view once by a seeded pose error of this standard deviation (default 0: off)")
     ap.add_argument("--feature-dim", type=int, default=argparse.SUPPRESS, metavar="D",
                     help="train a latent feature field beside the colours against feature maps of D channels")
     ap.add_argument("--latent-dim", type=int, default=argparse.SUPPRESS, help="channels of the latent table (default 128)")
@@ -175,6 +188,9 @@ def main(argv=None) -> int:
     depth_loss = getattr(args, "depth_loss", False)
     if not depth_loss and any(hasattr(args, k) for k in ("depth_lambda", "depth_kind")):
         ap.error("--depth-lambda and --depth-kind need --depth-loss")
+    pose_kw = {k: getattr(args, k) for k in ("pose_opt", "pose_opt_lr", "pose_opt_reg", "pose_noise") if hasattr(args, k)}
+    if "pose_opt" not in pose_kw and any(k in pose_kw for k in ("pose_opt_lr", "pose_opt_reg")):
+        ap.error("--pose-opt-lr and --pose-opt-reg need --pose-opt")
     if feature_dim is not None and bool(args.colmap) != hasattr(args, "feature_maps"):
         ap.error("--feature-dim takes its maps from --feature-maps with --colmap, and renders them itself with --synthetic")
     import gsbp_amd
@@ -274,14 +290,19 @@ def main(argv=None) -> int:
                                             ssim_lambda=args.ssim_lambda, seed=args.seed,
                                             sh_degree_interval=getattr(args, "sh_degree_interval", None), **reg, **feature_kw,
                                             **{k: getattr(args, k) for k in ("adam", "means_lr_final") if hasattr(args, k)}, **depth_kw,
-                                            **kw)
-    after = gsbp_amd.score_image_views(trained, viewmats, K, W, H, image_of, **kw)
+                                            **pose_kw, **kw)
+    after = gsbp_amd.score_image_views(trained, history.get("viewmats", viewmats), K, W, H, image_of, **kw)
     torch.save({k: t.cpu() for k, t in trained.items() if torch.is_tensor(t)}, os.path.join(args.out, "trained.pt"))
     extra = {}
     if feature_dim is not None:
         torch.save(dict(features=trained["features"].cpu(), decoder=history["decoder"].cpu()), os.path.join(args.out, "features.pt"))
         extra = dict(feature_loss=history["feature_loss"], feature_dim=feature_dim, latent_dim=latent_dim,
                      feature_weight=feature_kw["feature_weight"])
+    if pose_kw:
+        torch.save(dict(viewmats=history["viewmats"].cpu(), views=names,
+                        **({"pose_adjust": history["pose_adjust"].cpu()} if "pose_adjust" in history else {})),
+                   os.path.join(args.out, "poses.pt"))
+        extra.update(pose_kw, **({"pose_err": history["pose_err"]} if "pose_err" in history else {}))
     with open(os.path.join(args.out, "history.json"), "w") as f:
         json.dump(dict(**extra, params=list(args.params), steps=args.steps, ssim_lambda=args.ssim_lambda, seed=args.seed, views=names,
                        strategy=args.strategy, **reg, config={k: getattr(cfg, k) for k in cfg.__dataclass_fields__}, loss=history["loss"], n=history["n"],
@@ -297,7 +318,9 @@ def main(argv=None) -> int:
           f"{after['mean']['psnr']:.3f} dB, SSIM {before['mean']['ssim']:.4f} -> {after['mean']['ssim']:.4f}")
     if feature_dim is not None:
         print(f"feature loss {history['feature_loss'][0]:.6e} -> {history['feature_loss'][-1]:.6e}; wrote features.pt")
-    print(f"wrote {args.out}: trained.pt, history.json, metrics.json")
+    if "pose_err" in history:
+        print(f"pose error {history['pose_err'][0]:.6e} -> {history['pose_err'][-1]:.6e}")
+    print(f"wrote {args.out}: trained.pt, history.json, metrics.json" + (", poses.pt" if pose_kw else ""))
     return 0
 
 
