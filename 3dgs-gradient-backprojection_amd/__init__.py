@@ -91,9 +91,9 @@ from .pose import PoseAdjust, pose_error, refine_pose, se3_exp  # noqa: F401
 from . import photometric  # noqa: F401
 from .photometric import gaussian_window, image_metrics, image_sums, photometric_loss, ssim_map  # noqa: F401
 from . import polish  # noqa: F401
-from .polish import polish_scene, score_image_views  # noqa: F401
+from .polish import score_image_views  # noqa: F401
 # (gsbp_amd.densify is the function, as gsbp_amd.rasterization is; the module is reached as `from gsbp_amd.densify import ...`)
-from .densify import DensifyConfig, DensifyState, densify, init_splats_from_points, reset_opacity, train_scene  # noqa: F401
+from .densify import DensifyConfig, DensifyState, densify, init_splats_from_points, reset_opacity  # noqa: F401
 from . import mcmc  # noqa: F401
 from .mcmc import MCMCConfig, inject_noise, relocate, sample_add  # noqa: F401
 from . import adam  # noqa: F401
@@ -102,4 +102,6 @@ from . import depth  # noqa: F401
 from .depth import depth_map_loss, depth_point_loss, sample_expected_depth  # noqa: F401
 from . import latent_render  # noqa: F401
 from .latent_render import render_latents  # noqa: F401
+from . import train  # noqa: F401
+from .train import polish_scene, train_scene  # noqa: F401
 from .pruning import check_proper_pruning, gradient_mask, prune_by_gradients  # noqa: F401

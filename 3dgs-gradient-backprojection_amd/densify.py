@@ -2,11 +2,11 @@
 written there is the contract, not the library), on HIP kernels (csrc/densify.hip).
 
     state = DensifyState(n, device)
-    ...  render with rasterization(means2d_grad=True), loss.backward()  ...
+    ...  render with rasterization(means2d_grad=True), run the backward  ...
     state.update(meta)                                        # every step: one fused pass over meta["means2d"].grad
     splats, info = densify(splats, state, cfg, step, optimizer=opt, carry={"field": field})     # every refine_every steps
     reset_opacity(splats, opt, cfg)                           # every reset_every steps
-    splats, history = train_scene(splats, viewmats, K, W, H, image_fn, steps=7000, cfg=DensifyConfig())
+    splats, history = train.train_scene(splats, viewmats, K, W, H, image_fn, steps=7000, cfg=DensifyConfig())   # the loop (train.py)
     splats = init_splats_from_points(points, rgb)             # the start: a COLMAP point cloud
 
 A Gaussian whose screen-space gradient norm, averaged over the steps that saw it, is above grow_grad2d is duplicated when it is small
@@ -17,7 +17,7 @@ moments among them.  One host read per round: the size of the new set.  Splat di
 (polish.py).  There is no PyTorch fallback: CPU tensors raise GwbpError.
 
 Not offered: absgrad, the radius criteria (grow_scale2d, prune_scale2d, refine_scale2d_stop_iter), revised_opacity, packed mode.
-gsplat's other strategy, MCMCStrategy, is mcmc.py; train_scene(strategy=MCMCConfig(...)) runs it (without packed mode; the
+gsplat's other strategy, MCMCStrategy, is mcmc.py; train.train_scene(strategy=MCMCConfig(...)) runs it (without packed mode; the
 counterpart of its sparse gradients is train_scene(adam="visible"): adam.SplatAdam steps the Gaussians a step's view saw).
 """
 from __future__ import annotations
@@ -32,9 +32,6 @@ import torch
 from . import _lib
 from ._lib import GwbpError, ptr
 from ._views import ld, run
-from .photometric import photometric_loss
-from .polish import (PARAM_KEYS, check_adam, check_means_lr_final, check_sh_degree_interval, means_group, means_lr_at, render_splats,
-                     scheduled_sh_degree, splat_geometry, table_sh_degree, trainable, view_K, view_schedule)
 from .rasterization import release_engines
 
 GEOMETRY_KEYS = ("means", "scaling", "rotation", "opacity")  # what the emit kernel writes; every other [N, ...] tensor is gathered
@@ -118,7 +115,7 @@ class DensifyState:
         self.count = torch.zeros(self.n, device=device)
 
     def update(self, meta) -> None:
-        """After loss.backward() of a rasterization(means2d_grad=True) call: one kernel adds the call's cameras into the statistics
+        """After the backward of a rasterization(means2d_grad=True) call: one kernel adds the call's cameras into the statistics
         (gwbp_densify_accumulate), the norm in units of half the image times the number of cameras, as gsplat normalises it."""
         leaf = meta["means2d"]
         g = leaf.grad
@@ -298,236 +295,32 @@ def reset_opacity(splats: Dict[str, torch.Tensor], optimizer, cfg: DensifyConfig
     return splats
 
 
-DEPTH_KINDS = tuple(_lib.DEPTH_KINDS)  # train_scene(depth_kind=...): depth.depth_map_loss's kinds
-LATENT_RENDER_KW = ("near_plane", "far_plane", "radius_clip", "eps2d", "rasterize_mode", "camera_model")  # render_latents' keywords
+class DensifyRounds:
+    """train_scene's rounds under this strategy (mcmc.MCMCRounds has the same members): the colour render reports means2d.grad,
+    after_backward adds it into the statistics, after_step -- behind the optimiser's step -- runs the round and then the opacity reset
+    that cfg schedules at the step.  rounds and resets are the history's; generator draws the split noise."""
+    means2d_grad = True
 
+    def __init__(self, cfg: DensifyConfig, n: int, device, generator: Optional[torch.Generator]):
+        self.cfg, self.generator, self.state, self.rounds, self.resets = cfg, generator, DensifyState(n, device), [], []
 
-def _feature_leaves(work: Dict, opt, lrs, feature_dim, latent_dim, decoder, decoder_lr, seed):
-    """train_scene's feature term: (work with the float32 leaf `features` [N, latent_dim] in an Adam group of its own, the decoder
-    leaf [latent_dim, feature_dim], the decoder's own Adam)."""
-    n, dev = int(work["means"].shape[0]), work["means"].device
-    if decoder is None:
-        if feature_dim is None:
-            raise GwbpError("train_scene(feature_fn=...) needs feature_dim (the channels of the maps) or a decoder")
-        decoder = torch.rand(int(latent_dim), int(feature_dim), generator=torch.Generator().manual_seed(int(seed)))
-    decoder = decoder.detach().to(device=dev, dtype=torch.float32).clone()
-    if decoder.dim() != 2 or (feature_dim is not None and decoder.shape[1] != int(feature_dim)):
-        raise GwbpError(f"decoder must be [latent_dim, {feature_dim}], got {tuple(decoder.shape)}")
-    d = int(decoder.shape[0])
-    feats = work.get("features")
-    feats = torch.zeros(n, d, device=dev) if feats is None else feats.detach().to(device=dev, dtype=torch.float32).clone()
-    if tuple(feats.shape) != (n, d):
-        raise GwbpError(f"splats['features'] must be [{n}, {d}] (the decoder's rows), got {tuple(feats.shape)}")
-    work = dict(work, features=feats.requires_grad_(True))
-    opt.add_param_group(dict(params=[work["features"]], lr=float((lrs or {}).get("features", 2.5e-3))))
-    decoder.requires_grad_(True)
-    return work, decoder, torch.optim.Adam([decoder], lr=float(decoder_lr), eps=1e-15)
+    def after_backward(self, meta, step: int) -> None:
+        if step < self.cfg.refine_stop_iter:
+            self.state.update(meta)
 
-
-def train_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, image_fn: Callable[[int], torch.Tensor], steps: int,
-                cfg: Optional[DensifyConfig] = None, params: Sequence[str] = tuple(PARAM_KEYS), lrs: Optional[Dict[str, float]] = None,
-                seed: int = 0, ssim_lambda: float = 0.2, carry: Optional[Dict[str, torch.Tensor]] = None, strategy=None,
-                opacity_reg: float = 0.0, scale_reg: float = 0.0, sh_degree_interval: Optional[int] = None,
-                feature_fn: Optional[Callable[[int], torch.Tensor]] = None, feature_dim: Optional[int] = None, latent_dim: int = 128,
-                feature_weight: float = 1.0, feature_loss: str = "l1", decoder_lr: float = 2.5e-3, decoder=None, adam: str = "torch",
-                means_lr_final: Optional[float] = None, depth_fn: Optional[Callable[[int], object]] = None, depth_lambda: float = 1e-2,
-                depth_scale: float = 1.0, depth_kind: str = "disparity", pose_opt: bool = False, pose_opt_lr: float = 1e-5,
-                pose_opt_reg: float = 1e-6, pose_noise: float = 0.0, **raster_kw):
-    """polish_scene's loop with the schedule: Adam on the named parameters under the photometric loss, the set growing and shrinking
-    on the way.  Step s (from 0) renders one view with means2d_grad=True, runs the backward, adds the view into the statistics while
-    s < refine_stop_iter, steps the optimiser, runs a densify round when s > refine_start_iter, s % refine_every == 0 and
-    s % reset_every >= pause_refine_after_reset, and resets the opacities when s > 0 and s % reset_every == 0 (both only below
-    refine_stop_iter; a reset at step 0 would cap the opacities of the scene that was handed in before anything was learnt).
-    Returns (the trained splat dict, history): history = dict(loss = the steps' losses, read once behind the loop; n = the number
-    of Gaussians each step rendered; rounds = one dict per densify round: step, n_before, n_after, pruned, kept, cloned, split;
-    resets = the steps of the opacity resets; carry = the relocated `carry` tables).
-    The view of a step and the split noise come from seeded generators: the same call gives the same schedule of rounds.
-    strategy: None or a DensifyConfig (the same as cfg=) runs the loop above; an mcmc.MCMCConfig runs gsplat's MCMCStrategy instead:
-    no means2d gradient, no statistics and no opacity reset; after the optimiser step a relocate round and an add round when
-    refine_start_iter < s < refine_stop_iter and s % refine_every == 0, and noise on the means at EVERY step, scaled by the means
-    group's current learning rate (none when the means are not trained).  history["rounds"] then holds step, n_before, n_after,
-    relocated, added.
-    opacity_reg, scale_reg: weights of mean(sigmoid(opacity)) and mean(exp(scaling)), added to the loss when they are not zero (the
-    reference's mcmc configuration sets both to 0.01).
-    sh_degree_interval: None renders every step at the tables' SH degree; an int renders step s at min(s // interval, that degree), the
-    reference trainer's schedule (its interval is 1000); rows above a step's degree get zero gradients.  history["sh_degree"]: the
-    degree each step rendered at, one int per step.
-    feature_fn(v): the view's [H, W, feature_dim] map as decoded_loss takes its target.  None: no feature term.  Set, every step renders
-    twice, as the reference's Feature-3DGS trainer does: the SH colours, and render_latents of `features` [N, latent_dim] (splats["features"]
-    if the dict has it, zeros otherwise: the reference's start), which `decoder` [latent_dim, feature_dim] (the caller's -- its row
-    count then IS the latent dimension and the latent_dim keyword is not read -- or a torch.rand draw on the host from
-    torch.Generator().manual_seed(seed)) turns into the feature map; the step's loss is the
-    photometric loss + feature_weight * decoded_loss(render, decoder, feature_fn(v), loss=feature_loss), and its gradient reaches means,
-    rotation, scaling and opacity as well as the latents.  exp(scaling) and sigmoid(opacity) are computed once and handed to both
-    renders; of raster_kw the latent render takes the view's keywords (near_plane, far_plane, radius_clip, eps2d, rasterize_mode,
-    camera_model).  The densify statistics come from the colour render alone.  `features` is a leaf of the returned dict with an Adam
-    group of its own (lrs["features"], default 2.5e-3) and follows every round row by row like any other per-Gaussian table; the
-    decoder is NOT in the dict -- a round moves every tensor of N rows, and a decoder with latent_dim == N is no per-Gaussian table --
-    but in a second torch.optim.Adam (decoder_lr, eps 1e-15).  history gains feature_loss (the term before its weight, per step)
-    and decoder.
-    adam: which optimiser steps the per-Gaussian tables.  "torch" (the default) is torch.optim.Adam, the code path before the keyword
-    existed.  "fused" is adam.SplatAdam: the same arithmetic, one HIP kernel per tensor.  "visible" hands SplatAdam the radii of the
-    step's colour render (which then runs with means2d_grad=True under the MCMC strategy too: that is what reports them), and only the
-    Gaussians the view saw (radii > 0) are stepped -- gsplat's SelectiveAdam, the reference trainer's sparse_grad.  For a Gaussian the
-    view did NOT see, nothing is read or written that step: its parameters and both Adam moments keep their bits, so the moments do
-    not decay and no stale momentum moves it, and the gradient opacity_reg / scale_reg give it (the only one it has) is not applied.
-    The step count, and with it the bias correction, advances for every table at every step.  The `features` leaf of the feature term
-    is in the same optimiser and takes the same mask (the same view, the same geometry); the decoder keeps its torch.optim.Adam.
-    means_lr_final: None, or the factor the means group's learning rate has decayed by at the end: step s of `steps` runs with
-    lr0 * means_lr_final ** (s / steps), computed on the host and written into the group before the optimiser steps -- the reference
-    trainer's schedule (its value is 0.01).  The MCMC noise, scaled by the group's current rate, follows it.  history["means_lr"] then
-    holds the rate of every step; no other group's rate changes, and without the keyword no rate is touched.
-    depth_fn(v): the view's depth supervision, or None for a view that has none.  None (the default): no depth term, and nothing of the
-    step changes.  Set, the colour render runs with render_mode="RGB+D" (a render_mode in raster_kw then raises GwbpError), the
-    photometric loss takes its channels 0:3, and the step adds depth_lambda * the depth loss with scale=depth_scale, as the reference
-    trainer's depth_loss option does (its depth_lambda is 1e-2 and its scale the scene's scale): depth.depth_point_loss for a
-    (points [M, 2], depths [M]) pair -- scene_io.view_depth_points makes one from a COLMAP model -- or depth.depth_map_loss(kind=
-    depth_kind) for an [H, W] depth map.  Both read the render's accumulated depth and alpha in place.  The densify statistics see the
-    gradient of the summed loss, as in the reference.  history["depth_loss"]: the term before its weight, one value per step (0 for a
-    view without supervision), read once behind the loop.
-    pose_noise > 0: a fixed pose.PoseAdjust, drawn once from `seed` with std = pose_noise, perturbs every view first (the reference's
-    pose_perturb: captures whose COLMAP poses are slightly off).  pose_opt: a zero-initialised PoseAdjust is applied behind the noise and
-    trained with the Gaussians by its own torch.optim.Adam(lr=pose_opt_lr, weight_decay=pose_opt_reg), step s at pose_opt_lr *
-    0.01 ** (s / steps); the colour render then runs with pose_grad=True and the latent render with camera_grad=True (the depth column is
-    a torch function of the view matrix already).  history gains viewmats [V, 4, 4] (the views as they ended), pose_adjust [V, 9] under
-    pose_opt -- in history, not in the splat dict: a round moves every tensor of N rows, and V may equal N -- and under pose_noise
-    pose_err: per step, the mean absolute difference between the true and the used camera-to-world matrices over all views, read once
-    behind the loop.  A negative or non-finite value, and either option without a view, raise GwbpError.  pose.PoseTraining holds all of
-    it; without these keywords nothing of the step changes."""
-    from .decoded_field import decoded_loss
-    from .depth import depth_map_loss, depth_point_loss
-    from .latent_render import render_latents
-    from .mcmc import MCMCConfig, inject_noise, relocate, sample_add
-    from .pose import PoseTraining, check_pose_options
-    if strategy is not None and cfg is not None:
-        raise GwbpError("train_scene() takes cfg= or strategy=, not both")
-    if strategy is not None and not isinstance(strategy, (DensifyConfig, MCMCConfig)):
-        raise GwbpError(f"strategy must be None, a DensifyConfig or an MCMCConfig, got {type(strategy).__name__}")
-    mcmc = strategy if isinstance(strategy, MCMCConfig) else None
-    cfg = strategy if isinstance(strategy, DensifyConfig) else cfg if cfg is not None else DensifyConfig()
-    opacity_reg, scale_reg = float(opacity_reg), float(scale_reg)
-    interval = check_sh_degree_interval(sh_degree_interval, "train_scene")
-    final = check_means_lr_final(means_lr_final, "train_scene")
-    depth_kw, depth_losses = {}, []
-    if depth_fn is not None:
-        if not callable(depth_fn):
-            raise GwbpError(f"train_scene(): depth_fn must be a callable of the view's index, got {type(depth_fn).__name__}")
-        if "render_mode" in raster_kw:
-            raise GwbpError("train_scene(depth_fn=...) renders with render_mode='RGB+D': leave render_mode out of the raster keywords")
-        if depth_kind not in DEPTH_KINDS:
-            raise GwbpError(f"train_scene(): depth_kind must be one of {list(DEPTH_KINDS)}, got {depth_kind!r}")
-        for name, value in (("depth_lambda", depth_lambda), ("depth_scale", depth_scale)):
-            if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(float(value)):
-                raise GwbpError(f"train_scene(): {name} must be a finite number, got {value!r}")
-        depth_kw = dict(render_mode="RGB+D", return_alpha=True)
-    posed = check_pose_options("train_scene", int(viewmats.shape[0]), pose_opt, pose_opt_lr, pose_opt_reg, pose_noise)
-    work, opt = trainable(splats, params, lrs, "train_scene", check_adam(adam, "train_scene"))
-    poses = PoseTraining(viewmats.to(work["means"].device), steps, seed, pose_opt, pose_opt_lr, pose_opt_reg, pose_noise) if posed else None
-    pose_kw, latent_pose_kw = (dict(pose_grad=True), dict(camera_grad=True)) if pose_opt else ({}, {})
-    decayed = means_group(opt, work) if final is not None else None
-    if final is not None and decayed is None:
-        raise GwbpError("train_scene(): means_lr_final decays the means group's rate, and the means are not among params")
-    lr0, means_lrs = (None if decayed is None else decayed["lr"]), []
-    table_degree, degrees = table_sh_degree(work), []
-    dev, width, height = splats["means"].device, int(width), int(height)
-    for key in GEOMETRY_KEYS:  # what the rounds write must be float32 whether it is trained or not
-        work[key] = work[key] if work[key].requires_grad else work[key].float()
-    noise_gen = torch.Generator(device=dev).manual_seed(int(seed))
-    state = DensifyState(work["means"].shape[0], dev)
-    carried = dict(carry or {})
-    losses, sizes, rounds, resets = [], [], [], []
-    opt_dec, feature_losses = None, []
-    if feature_fn is not None:
-        work, decoder, opt_dec = _feature_leaves(work, opt, lrs, feature_dim, latent_dim, decoder, decoder_lr, seed)
-        latent_kw = {k: raster_kw[k] for k in LATENT_RENDER_KW if k in raster_kw}
-    for step, v in enumerate(view_schedule(viewmats.shape[0], seed, steps)):
-        opt.zero_grad(set_to_none=True)
-        degrees.append(table_degree if interval is None else scheduled_sh_degree(step, interval, table_degree))
-        geometry, f_loss = (splat_geometry(work) if feature_fn is not None else None), None  # (one exp and one sigmoid for both renders)
-        viewmat = viewmats[v] if poses is None else poses.view(v)
-        image, *alpha, meta = render_splats(work, viewmat, view_K(K, v), width, height, return_meta=True,
-                                            means2d_grad=mcmc is None or adam == "visible",
-                                            sh_degree=None if interval is None else degrees[-1], geometry=geometry, **depth_kw,
-                                            **pose_kw, **raster_kw)
-        loss = photometric_loss(image[..., :3] if depth_fn is not None else image, image_fn(v), ssim_lambda=ssim_lambda)
-        if depth_fn is not None:
-            target = depth_fn(v)
-            if target is None:
-                d_loss = torch.zeros((), device=dev)
-            elif isinstance(target, (tuple, list)) and len(target) == 2:
-                d_loss = depth_point_loss(image, alpha[0], target[0], target[1], scale=float(depth_scale))
-            elif torch.is_tensor(target):
-                d_loss = depth_map_loss(image, alpha[0], target, kind=depth_kind, scale=float(depth_scale))
-            else:
-                raise GwbpError(f"depth_fn({v}) must return a (points, depths) pair, an [H, W] tensor or None, got {type(target).__name__}")
-            depth_losses.append(d_loss.detach())
-            loss = loss + float(depth_lambda) * d_loss
-            del target, d_loss
-        if feature_fn is not None:
-            opt_dec.zero_grad(set_to_none=True)
-            latent_map, _ = render_latents(*geometry, work["features"], viewmat, view_K(K, v), width, height, **latent_kw,
-                                           **latent_pose_kw)
-            f_loss = decoded_loss(latent_map, decoder, feature_fn(v), loss=feature_loss)
-            feature_losses.append(f_loss.detach())
-            loss = loss + float(feature_weight) * f_loss
-            del latent_map
-        if opacity_reg != 0.0:
-            loss = loss + opacity_reg * torch.sigmoid(work["opacity"]).mean()
-        if scale_reg != 0.0:
-            loss = loss + scale_reg * torch.exp(work["scaling"]).mean()
-        loss.backward()
-        if mcmc is None and step < cfg.refine_stop_iter:
-            state.update(meta)
-        if decayed is not None:  # (the rounds swap a group's leaf, never the group: `decayed` stays the means' group)
-            decayed["lr"] = means_lr_at(lr0, final, step, int(steps))
-            means_lrs.append(decayed["lr"])
-        if adam == "visible":
-            opt.step(visible=meta["radii"])
-        else:
-            opt.step()
-        if opt_dec is not None:
-            opt_dec.step()
-        if poses is not None:
-            poses.step(step)
-        losses.append(loss.detach())
-        sizes.append(int(work["means"].shape[0]))
-        if mcmc is not None:
-            if mcmc.refines_at(step):
-                del image, alpha, meta, loss, f_loss, geometry, viewmat
-                n_before = sizes[-1]
-                work, moved = relocate(work, mcmc, optimizer=opt, carry=carried, generator=noise_gen)
-                work, added = sample_add(work, mcmc, mcmc.n_new(n_before), optimizer=opt, carry=moved["carry"], generator=noise_gen)
-                carried = added["carry"]
-                rounds.append(dict(step=step, n_before=n_before, n_after=added["n_after"], relocated=moved["relocated"],
-                                   added=added["added"]))
-                if added["added"]:
-                    release_engines(dev, keep_n=added["n_after"])
-            rate = next((g["lr"] for g in opt.param_groups if g["params"][0] is work["means"]), None)
-            if rate is not None:
-                inject_noise(work, rate, mcmc, generator=noise_gen)
-            continue
-        if cfg.refines_at(step):
-            del image, alpha, meta, loss, f_loss, geometry, viewmat  # (the graph holds the old set's workspace)
-            work, info = densify(work, state, cfg, step, optimizer=opt, carry=carried, generator=noise_gen)
+    def after_step(self, work: Dict[str, torch.Tensor], opt, carried: Dict[str, torch.Tensor], step: int):
+        if self.cfg.refines_at(step):
+            work, info = densify(work, self.state, self.cfg, step, optimizer=opt, carry=carried, generator=self.generator)
             carried = info["carry"]
             if info["n_after"] < 1:
                 raise GwbpError(f"step {step}: the round pruned every Gaussian")
-            rounds.append({k: info[k] for k in ("step", "n_before", "n_after", "pruned", "kept", "cloned", "split")})
-            release_engines(dev, keep_n=info["n_after"])
-        if cfg.resets_at(step):
-            reset_opacity(work, opt, cfg)
-            resets.append(step)
-    history = dict(loss=torch.stack(losses).cpu().tolist() if losses else [], n=sizes, rounds=rounds, resets=resets, carry=carried,
-                   sh_degree=degrees)
-    if final is not None:
-        history["means_lr"] = means_lrs
-    if depth_fn is not None:
-        history["depth_loss"] = torch.stack(depth_losses).cpu().tolist() if depth_losses else []
-    if poses is not None:
-        history.update(poses.history())
-    if feature_fn is not None:
-        history.update(feature_loss=torch.stack(feature_losses).cpu().tolist() if feature_losses else [], decoder=decoder.detach())
-    return {k: (t.detach() if torch.is_tensor(t) else t) for k, t in work.items()}, history
+            self.rounds.append({k: info[k] for k in ("step", "n_before", "n_after", "pruned", "kept", "cloned", "split")})
+            # the old set's workspace goes here: the step is a function that has returned, so no graph, meta or render holds it
+            release_engines(self.state.device, keep_n=info["n_after"])
+        if self.cfg.resets_at(step):
+            reset_opacity(work, opt, self.cfg)
+            self.resets.append(step)
+        return work, carried
 
 
 def init_splats_from_points(points, rgb, sh_degree: int = 3, init_opacity: float = 0.1, init_scale: float = 1.0) -> Dict[str, torch.Tensor]:

@@ -18,15 +18,18 @@ gradients.
 """
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import torch
 
+from . import _lib
 from ._lib import GwbpError
 from .engine import depth_image_args, depth_map_args, depth_point_args
 from .rasterization import engine_on
 
 __all__ = ["depth_point_loss", "depth_map_loss", "sample_expected_depth"]
+DEPTH_KINDS = tuple(_lib.DEPTH_KINDS)  # train_scene(depth_kind=...): depth_map_loss's kinds
 
 
 def _scale(fn: str, scale) -> float:
@@ -117,3 +120,31 @@ def sample_expected_depth(render, alpha, points, channel: int = -1) -> torch.Ten
         depth_point_args(fn, render, points, ones)
         _, per_point = engine_on(render.device).depth_points_loss(render, alpha, points, ones, channel, 1.0, want_per_point=True)
     return per_point[:, 0].contiguous()
+
+
+def check_depth_options(fn: str, depth_fn, depth_lambda, depth_scale, depth_kind, raster_kw) -> dict:
+    """The keywords fn()'s colour render takes under its depth keywords, {} without a depth_fn whatever the others are; GwbpError for a
+    depth_fn that is no callable, a render_mode among raster_kw, an unknown kind, a value that is not finite or no number."""
+    if depth_fn is None:
+        return {}
+    if not callable(depth_fn):
+        raise GwbpError(f"{fn}(): depth_fn must be a callable of the view's index, got {type(depth_fn).__name__}")
+    if "render_mode" in raster_kw:
+        raise GwbpError(f"{fn}(depth_fn=...) renders with render_mode='RGB+D': leave render_mode out of the raster keywords")
+    if depth_kind not in DEPTH_KINDS:
+        raise GwbpError(f"{fn}(): depth_kind must be one of {list(DEPTH_KINDS)}, got {depth_kind!r}")
+    for name, value in (("depth_lambda", depth_lambda), ("depth_scale", depth_scale)):
+        if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(float(value)):
+            raise GwbpError(f"{fn}(): {name} must be a finite number, got {value!r}")
+    return dict(render_mode="RGB+D", return_alpha=True)
+
+
+def depth_term(image, alpha, target, kind: str, scale: float, v: int) -> torch.Tensor:
+    """View v's depth loss against target = depth_fn(v): a (points, depths) pair, an [H, W] map, or None (no supervision: a device 0)."""
+    if target is None:
+        return torch.zeros((), device=image.device)
+    if isinstance(target, (tuple, list)) and len(target) == 2:
+        return depth_point_loss(image, alpha, target[0], target[1], scale=float(scale))
+    if torch.is_tensor(target):
+        return depth_map_loss(image, alpha, target, kind=kind, scale=float(scale))
+    raise GwbpError(f"depth_fn({v}) must return a (points, depths) pair, an [H, W] tensor or None, got {type(target).__name__}")

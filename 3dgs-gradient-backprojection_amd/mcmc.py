@@ -7,7 +7,7 @@ the contract, not the library), on HIP kernels (csrc/mcmc.hip).
         splats, info = relocate(splats, cfg, optimizer=opt, carry={"field": field})          # dead Gaussians move onto alive ones
         splats, info = sample_add(splats, cfg, cfg.n_new(n), optimizer=opt, carry=info["carry"])   # the set grows by 5 % up to cap_max
     inject_noise(splats, lr_means, cfg)                                                        # every step
-    splats, history = train_scene(splats, viewmats, K, W, H, image_fn, steps=30000, strategy=MCMCConfig(), opacity_reg=0.01, scale_reg=0.01)
+    splats, history = train.train_scene(splats, viewmats, K, W, H, image_fn, steps=30000, strategy=MCMCConfig(), opacity_reg=0.01, scale_reg=0.01)
 
 A Gaussian whose opacity is at or below min_opacity is dead.  A relocate round gives every dead Gaussian a parent drawn among the alive
 ones with probability proportional to opacity; a parent drawn c times shares itself with its c copies: ratio r = min(c + 1, 51),
@@ -34,6 +34,8 @@ from . import _lib
 from ._lib import GwbpError, ptr
 from ._views import ld, run
 from .densify import GEOMETRY_KEYS, as_rows, device_f32, f32, gather_rows, swap_adam_leaves
+from .polish import means_group
+from .rasterization import release_engines
 
 
 @dataclass
@@ -303,3 +305,33 @@ def add_noise(means, scaling, rotation, opacity, z, scaler: float) -> None:
     with torch.no_grad():
         run("gwbp_mcmc_noise", means.device, C.c_int64(n), ptr(means.detach()), ptr(scaling), ptr(rotation), ptr(opacity), ptr(z),
             C.c_float(f32(scaler)))
+
+
+class MCMCRounds:
+    """train_scene's rounds under this strategy (densify.DensifyRounds has the same members): no means2d gradient, nothing behind the
+    backward; after_step -- behind the optimiser's step -- runs a relocate and an add round when cfg.refines_at(step) and at EVERY step
+    puts noise on the means at their group's current rate (none when the means are not trained).  generator draws, in this order, for
+    relocate, sample_add and inject_noise."""
+    means2d_grad = False
+
+    def __init__(self, cfg: MCMCConfig, generator: Optional[torch.Generator]):
+        self.cfg, self.generator, self.rounds, self.resets = cfg, generator, [], []
+
+    def after_backward(self, meta, step: int) -> None:
+        pass
+
+    def after_step(self, work: Dict[str, torch.Tensor], opt, carried: Dict[str, torch.Tensor], step: int):
+        cfg = self.cfg
+        if cfg.refines_at(step):
+            n_before = int(work["means"].shape[0])
+            work, moved = relocate(work, cfg, optimizer=opt, carry=carried, generator=self.generator)
+            work, added = sample_add(work, cfg, cfg.n_new(n_before), optimizer=opt, carry=moved["carry"], generator=self.generator)
+            carried = added["carry"]
+            self.rounds.append(dict(step=step, n_before=n_before, n_after=added["n_after"], relocated=moved["relocated"],
+                                    added=added["added"]))
+            if added["added"]:  # (the old set's workspace, as in DensifyRounds.after_step)
+                release_engines(work["means"].device, keep_n=added["n_after"])
+        group = means_group(opt, work)
+        if group is not None:
+            inject_noise(work, group["lr"], cfg, generator=self.generator)
+        return work, carried

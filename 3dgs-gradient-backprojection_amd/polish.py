@@ -1,23 +1,28 @@
-"""Polish a scene against images: Adam on chosen pre-activation tensors of a FIXED set of Gaussians under the photometric loss the
-reference trainer uses (f3dgs/simple_trainer_feature_3dgs.py: (1 - 0.2) L1 + 0.2 (1 - SSIM)), and the trainer's evaluation without LPIPS.
+"""What a training loop over a splat dict is made of, and the trainer's evaluation without LPIPS.  The loops themselves -- polish_scene
+on a FIXED set of Gaussians, train_scene with a strategy's rounds -- are train.py; this is the layer below them, below densify.py and
+mcmc.py, and what a loop written elsewhere imports:
 
-    splats, history = polish_scene(splats, viewmats, K, W, H, image_fn, params=("opacities", "sh0"), steps=300)
+    PARAM_KEYS, DEFAULT_LRS                      the trainer's parameter names, their keys in a splat dict and their learning rates
+    work, opt = trainable(splats, params, lrs, "my_loop")          # detached leaves, one Adam group each
+    for step, v in enumerate(view_schedule(n_views, seed, steps)):  # the seeded view of each step
+        image = render_splats(work, viewmats[v], view_K(K, v), W, H, sh_degree=scheduled_sh_degree(step, interval, table_sh_degree(work)))
+    splat_geometry, means_group, means_lr_at     the activations, the means' Adam group and its decayed rate
+    check_sh_degree_interval, check_adam, check_means_lr_final, means_lr_decay     the loops' keyword checks
     table = score_image_views(splats, viewmats, K, W, H, image_fn)      # per view: psnr, ssim, l1, mse
 
-The uses: re-fit the opacities after apply_mask3d took Gaussians away, touch a scene up before a lift.  N is fixed: no densification,
-no pruning, no opacity reset.  A step renders one view with rasterization() (whose backward is the HIP blend and projection backward)
-and compares it with photometric_loss (csrc/ssim.hip).  A splat dict carries the reference's key names (means, scaling, rotation,
-opacity, features_dc [N, 1, 3], features_rest [N, K - 1, 3]); the parameters go by the trainer's names.
+A render is rasterization() (whose backward is the HIP blend and projection backward) on the SH colours of sh.sh_colors.  A splat dict
+carries the reference's key names (means, scaling, rotation, opacity, features_dc [N, 1, 3], features_rest [N, K - 1, 3]),
+pre-activation; the parameters go by the trainer's names.
 """
 from __future__ import annotations
 
 import math
-from typing import Callable, Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, Optional, Sequence
 
 import torch
 
 from ._lib import GwbpError
-from .photometric import image_metrics, photometric_loss
+from .photometric import image_metrics
 from .projection import sh_colors_torch
 from .rasterization import SH_CAMERA_GRAD_MESSAGE, rasterization, sh_kernel_enabled
 from .sh import sh_colors
@@ -140,6 +145,14 @@ def means_group(opt, work: Dict[str, torch.Tensor]):
     return next((g for g in opt.param_groups if g["params"][0] is work["means"]), None)
 
 
+def means_lr_decay(opt, work: Dict[str, torch.Tensor], final: Optional[float], fn: str):
+    """What fn(means_lr_final=final) decays: (the means' group, its first rate, final); None without the keyword."""
+    group = means_group(opt, work) if final is not None else None
+    if final is not None and group is None:
+        raise GwbpError(f"{fn}(): means_lr_final decays the means group's rate, and the means are not among params")
+    return None if group is None else (group, group["lr"], final)
+
+
 def trainable(splats: Dict[str, torch.Tensor], params: Sequence[str], lrs: Optional[Dict[str, float]], fn: str, adam: str = "torch"):
     """(work, optimizer) of fn(): `splats` detached, each named parameter a float32 leaf of its own, and torch.optim.Adam with ONE
     tensor per group at lrs[name] over DEFAULT_LRS, eps 1e-15 as in the reference trainer (densify._relocate_adam relies on that layout).
@@ -176,55 +189,6 @@ def view_schedule(n_views: int, seed: int, steps: int):
         if not order:
             order = torch.randperm(n_views, generator=gen).tolist()
         yield order.pop(0)
-
-
-def polish_scene(splats: Dict[str, torch.Tensor], viewmats, K, width, height, image_fn: Callable[[int], torch.Tensor],
-                 params: Sequence[str] = ("opacities", "sh0"), steps: int = 300, ssim_lambda: float = 0.2,
-                 lrs: Optional[Dict[str, float]] = None, seed: int = 0, sh_degree_interval: Optional[int] = None,
-                 adam: str = "torch", means_lr_final: Optional[float] = None,
-                 **raster_kw) -> Tuple[Dict[str, torch.Tensor], List[float]]:
-    """Adam on the named parameters of `splats` against the views' images.  Returns (a new splat dict -- the named tensors replaced by
-    their polished values, the others shared -- and the steps' losses, read from the device once behind the loop).
-    params: names out of means, scales, quats, opacities, sh0, shN; one Adam group each at lrs[name] (default: the reference
-    trainer's, DEFAULT_LRS; eps 1e-15 as there).  Each step takes one view, drawn from torch.Generator().manual_seed(seed) on the
-    host as a fresh permutation per pass over the views.  image_fn(v): the view's float32 [H, W, 3] image in [0, 1] on the device.
-    viewmats [V, 4, 4]; K [3, 3] or [V, 3, 3].  raster_kw: camera_model, rasterize_mode and the other keywords of rasterization().
-    sh_degree_interval: None renders every step at the tables' SH degree; an int renders step s (from 0) at min(s // interval, that
-    degree), the reference trainer's schedule (its interval is 1000).  Coefficient rows above a step's degree get zero gradients.
-    adam: "torch" steps torch.optim.Adam (the default, and the code path before the keyword existed); "fused" steps adam.SplatAdam, the
-    same arithmetic in one HIP kernel per tensor; "visible" steps it on the Gaussians the step's view saw (radii > 0; the step then
-    renders with means2d_grad=True, which is what reports the radii): a Gaussian the view did not see keeps every bit of its parameters
-    and of both Adam moments -- the moments do not decay, and no stale momentum moves it.
-    means_lr_final: None, or the factor the means group's learning rate has decayed by at the end: step s of `steps` runs with
-    lr0 * means_lr_final ** (s / steps), the reference trainer's schedule (its value is 0.01); no other group's rate changes."""
-    interval = check_sh_degree_interval(sh_degree_interval, "polish_scene")
-    final = check_means_lr_final(means_lr_final, "polish_scene")
-    work, opt = trainable(splats, params, lrs, "polish_scene", adam)
-    width, height, losses = int(width), int(height), []
-    table = table_sh_degree(work)
-    decayed = means_group(opt, work) if final is not None else None
-    if final is not None and decayed is None:
-        raise GwbpError("polish_scene(): means_lr_final decays the means group's rate, and the means are not among params")
-    lr0 = None if decayed is None else decayed["lr"]
-    for step, v in enumerate(view_schedule(viewmats.shape[0], seed, steps)):
-        opt.zero_grad(set_to_none=True)
-        if adam == "visible":
-            image, meta = render_splats(work, viewmats[v], view_K(K, v), width, height, return_meta=True, means2d_grad=True,
-                                        sh_degree=scheduled_sh_degree(step, interval, table), **raster_kw)
-        else:
-            image = render_splats(work, viewmats[v], view_K(K, v), width, height, sh_degree=scheduled_sh_degree(step, interval, table),
-                                  **raster_kw)
-        loss = photometric_loss(image, image_fn(v), ssim_lambda=ssim_lambda)
-        loss.backward()
-        if decayed is not None:
-            decayed["lr"] = means_lr_at(lr0, final, step, int(steps))
-        if adam == "visible":
-            opt.step(visible=meta["radii"])
-        else:
-            opt.step()
-        losses.append(loss.detach())
-    history = torch.stack(losses).cpu().tolist() if losses else []
-    return {k: (t.detach() if torch.is_tensor(t) else t) for k, t in work.items()}, history
 
 
 def score_image_views(splats: Dict[str, torch.Tensor], viewmats, K, width, height, image_fn: Callable[[int], torch.Tensor],

@@ -133,7 +133,7 @@ def check_pose_options(fn: str, n_views: int, pose_opt, pose_opt_lr, pose_opt_re
 
 
 class PoseTraining:
-    """What train_scene(pose_opt=..., pose_noise=...) keeps beside its loop: the fixed perturbation (pose_noise > 0: a PoseAdjust drawn
+    """What train.train_scene(pose_opt=..., pose_noise=...) keeps beside its loop: the fixed perturbation (pose_noise > 0: a PoseAdjust drawn
     once from `seed` with std = pose_noise, the reference's pose_perturb), the learnt correction behind it (pose_opt: a zero PoseAdjust
     whose table is a leaf of its own torch.optim.Adam(lr=pose_opt_lr, weight_decay=pose_opt_reg); step s of `steps` runs at
     pose_opt_lr * 0.01 ** (s / steps), the reference's ExponentialLR), and the monitor.  dtype: float32 as train_scene runs it; a

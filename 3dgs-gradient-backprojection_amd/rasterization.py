@@ -141,7 +141,7 @@ def get_engine(device, n: int, width: int, height: int) -> Engine:
 
 def release_engines(device, keep_n: Optional[int] = None) -> None:
     """Drop this device's cached workspaces, all of them or those sized for another number of Gaussians than keep_n.  A training run
-    whose N changes every round (densify.train_scene) calls it after a round: the cache would otherwise hold the workspace of the set
+    whose N changes every round (train.train_scene's rounds) calls it after a round: the cache would otherwise hold the workspace of the set
     that no longer exists beside the new one until a third size arrives."""
     for k in [k for k in _ENGINES if k[0] == str(device) and (keep_n is None or k[1] != keep_n)]:
         del _ENGINES[k]

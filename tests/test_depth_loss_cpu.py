@@ -380,3 +380,27 @@ def test_depth_py_and_the_keywords_refuse_without_a_device():
     assert sig["depth_fn"].default is None and sig["depth_lambda"].default == 1e-2 and sig["depth_scale"].default == 1.0
     assert sig["depth_kind"].default == "disparity"
     assert inspect.signature(gsbp_amd.polish.render_splats).parameters["return_alpha"].default is False
+
+
+def test_check_depth_options_alone():
+    """depth.check_depth_options, the check train_scene makes: {} without a depth_fn whatever the other values are, the render's
+    keywords with one, and for each bad value the text the test above expects from train_scene."""
+    from gsbp_amd.depth import DEPTH_KINDS, check_depth_options
+
+    def fn(v):
+        return None
+    for other in ((1e-2, 1.0, "disparity", {}), (float("nan"), None, "inverse", dict(render_mode="RGB+ED")), ("1", True, 7, dict(eps2d=0.3))):
+        assert check_depth_options("train_scene", None, *other) == {}
+    assert check_depth_options("train_scene", fn, 0.5, 2, "depth", dict(eps2d=0.3)) == dict(render_mode="RGB+D", return_alpha=True)
+    assert DEPTH_KINDS == tuple(_lib.DEPTH_KINDS) == ("disparity", "depth")
+    with pytest.raises(gsbp_amd.GwbpError, match=r"train_scene\(depth_fn=\.\.\.\) renders with render_mode='RGB\+D'"):
+        check_depth_options("train_scene", fn, 1e-2, 1.0, "disparity", dict(render_mode="RGB+ED"))
+    with pytest.raises(gsbp_amd.GwbpError, match=r"train_scene\(\): depth_fn must be a callable of the view's index, got tuple"):
+        check_depth_options("train_scene", (1, 2), 1e-2, 1.0, "disparity", {})
+    with pytest.raises(gsbp_amd.GwbpError, match=r"train_scene\(\): depth_kind must be one of \['disparity', 'depth'\], got 'inverse'"):
+        check_depth_options("train_scene", fn, 1e-2, 1.0, "inverse", {})
+    for name in ("depth_lambda", "depth_scale"):
+        for bad in (float("nan"), float("inf"), "1", True, None):
+            values = dict(dict(depth_lambda=1e-2, depth_scale=1.0), **{name: bad})
+            with pytest.raises(gsbp_amd.GwbpError, match=rf"my_loop\(\): {name} must be a finite number, got "):
+                check_depth_options("my_loop", fn, values["depth_lambda"], values["depth_scale"], "disparity", {})

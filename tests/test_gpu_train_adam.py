@@ -167,7 +167,7 @@ def test_sixty_steps_with_rounds(dev, strategy, adam):
 
 def test_means_lr_final_decays_the_means_rate_and_no_other(dev, crop, monkeypatch):
     cfg, start, Kc, vms, crops = crop
-    module = sys.modules["gsbp_amd.densify"]
+    module = sys.modules["gsbp_amd.train"]  # (both loops call trainable from there)
     made = []
 
     def recording(*a, **kw):
